@@ -28,6 +28,9 @@ Rank 0 prints ONE JSON line:
                       recorded from the reference) on a bounded sample: 1 process; cpu_baseline_mpi: R = 8 processes
                       in the reference's launch model (oracle/cpu_ddppo.py, gloo); cpu_baseline_c1: C1 exactly.
                       Rank 0, N = 1 only; fresh CPU-only child processes, run before the GPU is touched.
+  dump_outputs        with --dump-outputs DIR: the arrays the last timed step of --config computed (dump_outputs()),
+                      written to DIR as .npy right after the timed region; inputs are seeded, so two builds run with
+                      the same arguments can be compared array by array
 """
 import argparse
 import json
@@ -129,6 +132,9 @@ def parse():
                         "critic 256^3, E=2048, ICM + obs/reward normalisers and clippers | C4 dims: SimpleSpread MAPPO, 3 agents, "
                         "O=18, O_c=54, Discrete(5), E=1024 per rank | C5 dims: same env, MATPolicy (embedding 64, "
                         "1 block, 1 head, critic view local), E=1024 per rank")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step of --config computed (rollout buffer "
+                        "fields, trained parameters and Adam moments, epoch statistics) as DIR/<name>.npy (rank 0)")
     return p.parse_args()
 
 
@@ -226,6 +232,53 @@ def build_config(name, args, device, rank):
     return ppo, ppo.policies["cartpole"], dict(E=E, T=T, A=A, O=O, workload=workload)
 
 
+DUMP_BYTES_MAX = 60 << 20           # (under 64 MB with the files' headers)
+
+
+def dump_outputs(ppo, pol, out_dir):
+    """
+    --dump-outputs: what the last timed iteration handed its caller, as DIR/<name>.npy -- the rollout buffer the
+    dataset is built on (per transition row: observations, actions, log-probs, values after the epochs' write-back,
+    advantages, rewards-to-go), the trained parameter buckets with their Adam moments, and the policy's status
+    entries (float64, in status_dict order).  Rollout rows beyond DUMP_BYTES_MAX are thinned to a fixed
+    default_rng(0) sample of rows (rollout_rows.npy lists them), so two builds run with the same arguments can be
+    compared file by file.
+    """
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    b = pol.buffer
+    n = b.num_transitions
+    rows = {k: getattr(b, k).reshape(n, -1) for k in ("observations", "actions", "log_probs", "values", "advantages",
+                                                       "rewards_to_go")}
+    state = {}
+    if getattr(pol, "agent_grouping", False) and hasattr(pol, "actor_critic"):
+        opt = pol.actor_critic_optim
+        state.update(params=pol.actor_critic.flat_params, adam_exp_avg=opt.exp_avg, adam_exp_avg_sq=opt.exp_avg_sq)
+    else:
+        state.update(params=pol.policy_params, adam_exp_avg=pol.policy_exp_avg, adam_exp_avg_sq=pol.policy_exp_avg_sq)
+    if pol.enable_icm and hasattr(pol.icm_model, "flat_params"):
+        state.update(icm_params=pol.icm_model.flat_params, icm_adam_exp_avg=pol.icm_optim.exp_avg,
+                     icm_adam_exp_avg_sq=pol.icm_optim.exp_avg_sq)
+    out = {k: v.detach().float().cpu().numpy() for k, v in state.items()}
+    status = []
+    for v in ppo.status_dict["cartpole"].values():
+        status += [float(x) for x in (v if isinstance(v, (tuple, list)) else (v,)) if hasattr(x, "__float__")]
+    out["status"] = np.asarray(status, dtype=np.float64)
+    room = DUMP_BYTES_MAX - sum(a.nbytes for a in out.values())
+    per_row = sum(4 * t.shape[1] for t in rows.values()) + 8
+    if n * (per_row - 8) > room:
+        keep = np.sort(np.random.default_rng(0).choice(n, max(room // per_row, 1), replace=False))
+        out["rollout_rows"] = keep.astype(np.float64)
+        idx = torch.as_tensor(keep, dtype=torch.int64, device=b.advantages.device)
+        rows = {k: t[idx] for k, t in rows.items()}
+    out.update({f"rollout_{k}": t.float().cpu().numpy() for k, t in rows.items()})
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES_MAX
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return sorted(out)
+
+
 
 
 def update_kernel_roofline(ppo, pol, B, launches=64, config="C2"):
@@ -313,8 +366,9 @@ def update_kernel_roofline(ppo, pol, B, launches=64, config="C2"):
             "traffic_source": None if pmc is None else f"{pmc['source']}: 2 x FETCH_SIZE + WRITE_SIZE per launch ({pmc['dispatches']} launches)"}
 
 
-def run_config(name, args, device, rank, world, steps, warmup, with_gae_roofline):
-    """Time `steps` PPO iterations of one config -> result dict (value, ms_per_step, rooflines, exchange info)."""
+def run_config(name, args, device, rank, world, steps, warmup, with_gae_roofline, dump_dir=None):
+    """Time `steps` PPO iterations of one config -> result dict (value, ms_per_step, rooflines, exchange info).
+    dump_dir: write the last timed iteration's outputs there (dump_outputs) before anything else runs on the trainer."""
     import torch
     import torch.distributed as dist
     from ppo_and_friends_amd.utils import mpi_utils
@@ -372,6 +426,8 @@ def run_config(name, args, device, rank, world, steps, warmup, with_gae_roofline
            "warmup": warmup, "workload": d["workload"], "E": E, "T": T, "A": A,
            "rollout_s": round(ppo.status_dict["global status"]["rollout time"], 4),
            "train_s": round(ppo.status_dict["global status"]["train time"], 4)}
+    if dump_dir is not None and rank == 0:
+        res["dumped"] = dump_outputs(ppo, pol, dump_dir)
     if with_gae_roofline:
         gae_ms = [K.event_elapsed_ms(a, b) for a, b in gae_events]
         gae_avg_s = (sum(gae_ms) / max(len(gae_ms), 1)) * 1e-3
@@ -469,10 +525,10 @@ def main():
 
     notes = {}
 
-    def run_measured(name, steps, warmup, with_gae):
-        return run_config(name, args, device, rank, world, steps, warmup, with_gae)
+    def run_measured(name, steps, warmup, with_gae, dump_dir=None):
+        return run_config(name, args, device, rank, world, steps, warmup, with_gae, dump_dir)
 
-    main_res = run_measured(args.config, args.steps, args.warmup, True)
+    main_res = run_measured(args.config, args.steps, args.warmup, True, args.dump_outputs)
     update_note = notes.get(args.config)
     others = {}
     # N > 1: the line the driver's scaling run reads is C2's; the other shapes' N > 1 paths (256-wide critics on row pairs,
@@ -505,6 +561,8 @@ def main():
                       "update_kernel": update_note or (main_res.get("roofline_update") or {}).get("kernel"),
                       "other_configs": others or None},
            "roofline": main_res["roofline"]}
+    if args.dump_outputs is not None:
+        out["dump_outputs"] = {"dir": args.dump_outputs, "config": args.config, "arrays": main_res.get("dumped")}
     if main_res.get("roofline_update") is not None:
         out["roofline_update"] = main_res["roofline_update"]
 

@@ -3,9 +3,15 @@
 size-independent facts that must hold whatever the data (counts, conservation, monotone progress on a
 fixed batch, equality of two execution modes), called through the same C-ABI paths the benchmark uses.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from initial_weights import float64_orthogonal_init  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -150,7 +156,8 @@ def test_full_size_split_wgrad_chain_matches_the_slab_chain(name, monkeypatch):
     grads, totals, epochs = {}, {}, {}
     for split in ("0", "1", "1"):
         monkeypatch.setenv("PPOAF_SPLIT_WGRAD", split)
-        ppo, E, T, A = _c_config(name, use_graphs=len(epochs.get("1", [])) == 0)      # second split run: eager launches
+        with float64_orthogonal_init():    # the same initial weights on every host (tests/helpers/initial_weights.py)
+            ppo, E, T, A = _c_config(name, use_graphs=len(epochs.get("1", [])) == 0)      # second split run: eager launches
         ppo.rollout()
         pol = ppo.policies["p"]
         pol.train()
