@@ -762,6 +762,45 @@ typedef struct {
 int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* args, ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * K18  one-layer LSTM network: LSTMNetwork.forward_logits and its gradients
+ * replaces nn.LSTM -> LayerNorm -> activation -> ff_layers of
+ *          LSTMNetwork.forward                     networks/ppo_networks/lstm.py:103-127
+ *          (hidden-state hand-over of the update   ppo.py:2312-2319; its gradients in
+ *           ppo.py:2408-2441 via loss.backward)
+ * Gate order i, f, g, o (torch's), both b_ih and b_hh; c' = f*c + i*g, h' = o*tanh(c').  The last step's h goes
+ * through LayerNorm(hidden) (eps 1e-5, affine) -> activation -> Linear(hidden, ff_hidden) [-> act -> Linear(ff_hidden,
+ * ff_hidden)] -> act -> Linear(ff_hidden, out_dim): logits, Gaussian mean or value.  f32 throughout.
+ * params / grads point at the network's own bucket: lstm.weight_ih_l0 [4H, in], weight_hh_l0 [4H, H], bias_ih_l0,
+ * bias_hh_l0, layer_norm.weight, layer_norm.bias, then weight / bias of each Linear, every tensor padded to 4 floats
+ * (module parameter order; anything after them, e.g. a Gaussian log_std, is not touched).
+ * x is [rows, steps, in_dim] (batch-first window; steps = 1 for a rollout step), h0 / c0 / hn / cn are [rows, H].
+ * Coverage: hidden 32 / 64 / 128, ff_hidden 16 / 32 / 64 / 128, ff_depth 1 / 2, in_dim <= 256, out_dim <= 8,
+ * steps <= 16, activation PPOAF_ACT_*.
+ * The workspace (floats from ppoaf_lstm_workspace_floats: out[0] = workspace floats, out[1] = bucket floats of the
+ * network) holds what the backward passes read; it is sized for rows x steps and written, never cleared, by
+ * ppoaf_lstm_forward with stash != 0 (stash == 0: inference, no workspace needed).
+ * ppoaf_lstm_backward: d out [rows, out_dim] -> head and LayerNorm gradients and, backwards over the steps, the
+ * pre-activation gate gradients of every (row, step) -- into the workspace; no gradient for x, h0, c0 (data).
+ * ppoaf_lstm_wgrad: ADDS dW_ih, dW_hh, db (to both b_ih and b_hh), the LayerNorm and Linear gradients to grads;
+ * every element is reduced by one workgroup in a fixed order: bitwise reproducible, no atomics.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t in_dim, hidden, ff_hidden, ff_depth, out_dim, activation;
+    int64_t rows, steps;
+    const float* params;
+    float* grads;
+    float* workspace;
+    int64_t workspace_floats;
+} ppoaf_lstm_desc_t;
+
+int ppoaf_lstm_workspace_floats(const ppoaf_lstm_desc_t* desc, int64_t* out /* host [2] */);
+int ppoaf_lstm_forward(const ppoaf_lstm_desc_t* desc, const float* x, const float* h0, const float* c0,
+                       float* out, float* hn /* NULL ok */, float* cn /* NULL ok */, int32_t stash,
+                       ppoaf_stream_t stream);
+int ppoaf_lstm_backward(const ppoaf_lstm_desc_t* desc, const float* c0, const float* dout, ppoaf_stream_t stream);
+int ppoaf_lstm_wgrad(const ppoaf_lstm_desc_t* desc, const float* x, const float* h0, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * K17  gradient exchange between the ranks of one node over peer mappings (xGMI)
  * replaces, inside the per-mini-batch update chain, the comm.Allreduce of
  *          mpi_avg_gradients                       utils/mpi_utils.py:65-86  (called from ppo.py:2443-2448,

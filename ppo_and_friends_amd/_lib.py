@@ -35,6 +35,14 @@ class MlpDesc(C.Structure):
                 ("offset", C.c_int64), ("size", C.c_int64), ("log_std_offset", C.c_int64)]
 
 
+class LstmDesc(C.Structure):
+    """ppoaf_lstm_desc_t (include/ppoaf_hip.h)."""
+    _fields_ = [("in_dim", C.c_int32), ("hidden", C.c_int32), ("ff_hidden", C.c_int32), ("ff_depth", C.c_int32),
+                ("out_dim", C.c_int32), ("activation", C.c_int32), ("rows", C.c_int64), ("steps", C.c_int64),
+                ("params", C.c_void_p), ("grads", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_floats", C.c_int64)]
+
+
 class PpoUpdateArgs(C.Structure):
     """ppoaf_ppo_update_args_t (include/ppoaf_hip.h) -- field order must match the header."""
     _fields_ = [("actor", MlpDesc), ("critic", MlpDesc),
@@ -225,6 +233,10 @@ SIGNATURES = {
     "ppoaf_mat_update_split_workspace_bytes": (C.c_int, [C.POINTER(MatUpdateArgs), C.POINTER(C.c_int64)]),
     "ppoaf_mat_update_norm_partials": (C.c_int, [C.POINTER(MatUpdateArgs)]),
     "ppoaf_mat_policy_step": (C.c_int, [C.POINTER(MatStepArgs), _ptr]),
+    "ppoaf_lstm_workspace_floats": (C.c_int, [C.POINTER(LstmDesc), C.POINTER(C.c_int64)]),
+    "ppoaf_lstm_forward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int32, _ptr]),
+    "ppoaf_lstm_backward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),
+    "ppoaf_lstm_wgrad": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),
     "ppoaf_peer_exchange_create": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "ppoaf_peer_exchange_export": (C.c_int, [_ptr, _ptr]),
     "ppoaf_peer_exchange_connect": (C.c_int, [_ptr, C.c_char_p]),

@@ -101,6 +101,35 @@ def _reduce_totals(upd, totals):
     return out[:-1]
 
 
+class FusedLstm:
+    """
+    Coverage of K18 (csrc/lstm.hip) for an LSTM actor / critic pair.  Such a policy is trained by PPO's mini-batch loop
+    (_minibatch_step): under update_mode="fused" its two networks run forward_logits and its gradients on K18, next to
+    the distribution, loss and Adam kernels that loop already uses.  (FusedPolicyUpdate.unsupported_reason stays the
+    MLP-only test: it also picks the K6 rollout-step kernel, which never sees an LSTM policy.)
+    """
+
+    @staticmethod
+    def unsupported_reason(pol):
+        """'' when K18 covers both networks of this LSTM policy, else why not."""
+        from .networks.lstm import LSTMNetwork
+        if not pol.using_lstm:
+            return "not an LSTM policy"
+        if pol.agent_grouping:
+            return "LSTM inside agent-grouped (MAT) policies is not covered"
+        if not isinstance(pol.actor.distribution, (CategoricalDistribution, GaussianDistribution)):
+            return "actor: only categorical and Gaussian action distributions are covered"
+        for tag, net in (("actor", pol.actor), ("critic", pol.critic)):
+            if not isinstance(net, LSTMNetwork):
+                return f"{tag}: {type(net).__name__} is not an LSTMNetwork"
+            why = net.hip_unsupported_reason()
+            if why:
+                return f"{tag}: {why}"
+        if pol.critic.out_size != 1:
+            return "critic must have one output"
+        return ""
+
+
 class FusedPolicyUpdate:
 
     graph_chunk = 32

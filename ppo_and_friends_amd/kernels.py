@@ -569,3 +569,59 @@ def env_filter_apply(obs_f, cobs_f, rew_f, G, n, records=None):
     check(_lib.load().ppoaf_env_filter_apply(_ref(obs_f), _ref(cobs_f), _ref(rew_f), int(G), int(n),
                                              ptr(records) if records is not None else None, R, stream()),
           "env_filter_apply")
+
+
+# --------------------------------------------------------------------------
+# K18: one-layer LSTM network (LSTMNetwork.forward_logits)
+# --------------------------------------------------------------------------
+def lstm_desc(in_dim, hidden, ff_hidden, ff_depth, out_dim, activation, rows, steps, params, grads=None,
+              workspace=None):
+    """ppoaf_lstm_desc_t over a network's flat buckets (params / grads: float32 device tensors)."""
+    d = _lib.LstmDesc()
+    d.in_dim, d.hidden, d.ff_hidden, d.ff_depth, d.out_dim, d.activation = \
+        int(in_dim), int(hidden), int(ff_hidden), int(ff_depth), int(out_dim), int(activation)
+    d.rows, d.steps = int(rows), int(steps)
+    d.params = ptr(_f32(params, "params"))
+    d.grads = None if grads is None else ptr(_f32(grads, "grads"))
+    d.workspace = None if workspace is None else ptr(_f32(workspace, "workspace"))
+    d.workspace_floats = 0 if workspace is None else workspace.numel()
+    return d
+
+
+def lstm_sizes(desc):
+    """(workspace floats, bucket floats of the network) for this shape."""
+    out = (C.c_int64 * 2)()
+    check(_lib.load().ppoaf_lstm_workspace_floats(C.byref(desc), out), "lstm_workspace_floats")
+    return int(out[0]), int(out[1])
+
+
+def _lstm_state(t, rows, hidden, name):
+    _f32(t, name)
+    _req(t.is_contiguous() and t.numel() == rows * hidden, f"{name} must be contiguous with {rows} x {hidden} floats")
+    return t
+
+
+def lstm_forward(desc, x, h0, c0, stash):
+    """x [rows, steps, in_dim] -> (out [rows, out_dim], h_n [rows, H], c_n [rows, H]); stash: keep what backward reads."""
+    _f32(x, "x")
+    _req(x.is_contiguous() and x.numel() == desc.rows * desc.steps * desc.in_dim,
+         "x must be a contiguous [rows, steps, in_dim] float32 tensor")
+    _lstm_state(h0, desc.rows, desc.hidden, "h0")
+    _lstm_state(c0, desc.rows, desc.hidden, "c0")
+    out = torch.empty(desc.rows, desc.out_dim, dtype=torch.float32, device=x.device)
+    hn = torch.empty(desc.rows, desc.hidden, dtype=torch.float32, device=x.device)
+    cn = torch.empty_like(hn)
+    check(_lib.load().ppoaf_lstm_forward(C.byref(desc), ptr(x), ptr(h0), ptr(c0), ptr(out), ptr(hn), ptr(cn),
+                                         1 if stash else 0, stream()), "lstm_forward")
+    return out, hn, cn
+
+
+def lstm_backward(desc, x, h0, c0, dout):
+    """d out [rows, out_dim] -> dgrad into the workspace, then the weight gradients ADDED to desc.grads."""
+    _f32(dout, "dout")
+    _req(dout.is_contiguous() and dout.numel() == desc.rows * desc.out_dim, "dout must be a contiguous [rows, out_dim] tensor")
+    _lstm_state(h0, desc.rows, desc.hidden, "h0")
+    _lstm_state(c0, desc.rows, desc.hidden, "c0")
+    lib = _lib.load()
+    check(lib.ppoaf_lstm_backward(C.byref(desc), ptr(c0), ptr(dout), stream()), "lstm_backward")
+    check(lib.ppoaf_lstm_wgrad(C.byref(desc), ptr(x), ptr(h0), stream()), "lstm_wgrad")

@@ -250,9 +250,16 @@ class PPO:
             if normalize_values:
                 self.value_normalizers[policy_id] = RunningStatNormalizer(
                     name=f"{policy_id}-value_normalizer", device=self.device)
-        for pol in self.policies.values():
+        for policy_id, pol in self.policies.items():
             pol.finalize(self.status_dict, self.device)
             pol.fused_icm_reward = update_mode != "torch"       # K14's kernels for the rollout-time intrinsic reward
+            if update_mode == "fused" and pol.using_lstm and self.device.type == "cuda":
+                # K18 for both recurrent networks, in the rollout and in the update ("auto" keeps nn.LSTM for now)
+                from .fused_update import FusedLstm
+                why = FusedLstm.unsupported_reason(pol)
+                if why:
+                    raise NotImplementedError(f"update_mode='fused' but policy {policy_id}: {why}")
+                pol.actor.use_hip = pol.critic.use_hip = True
         # ppo.py:663-678: freeze cycling over policy groups (utils/schedulers.py:FreezeCyclingScheduler)
         from .utils.schedulers import FreezeCyclingScheduler
         if freeze_scheduler is None:
@@ -1092,6 +1099,15 @@ class PPO:
         if self.update_mode == "torch" or self.device.type != "cuda":
             return None
         key = (policy_id, B)
+        if key not in self._fused and self.update_mode == "fused" and self.policies[policy_id].using_lstm \
+                and not self.policies[policy_id].agent_grouping:
+            # LSTM policies: the mini-batch loop drives them, every compute launch of it ours (K18 networks, distribution
+            # and loss kernels, FlatAdam); coverage was checked when the networks were switched to K18
+            from .fused_update import FusedLstm
+            why = FusedLstm.unsupported_reason(self.policies[policy_id])
+            if why:
+                raise NotImplementedError(f"update_mode='fused' but {why}")
+            self._fused[key] = None
         if key not in self._fused:
             from .fused_update import FusedMatUpdate, FusedPolicyUpdate
             if self.policies[policy_id].agent_grouping:
