@@ -5,6 +5,9 @@
 #include <stdint.h>
 #include <cstdarg>
 #include <cstdio>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "../../include/ppoaf_hip.h"
 
@@ -30,6 +33,33 @@ inline int check_launch(const char* what) {
             return PPOAF_E_INVALID;                  \
         }                                            \
     } while (0)
+
+// Launches whose workgroups all wait for each other need every workgroup resident at once: PPOAF_OK when `blocks`
+// workgroups of `kernel` (`threads` each, no dynamic LDS) fit on the current device together.  The occupancy is queried
+// once per kernel and device (on the first, eager, launch: nothing but the launch inside a stream capture) and cached
+// under a lock, so launches may come from several threads and devices.
+inline int require_all_resident(const void* kernel, int threads, int blocks, const char* what) {
+    static std::mutex mu;
+    static std::map<std::pair<const void*, int>, std::pair<int, int>> fits;   // (kernel, device) -> (per CU, CUs)
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::pair<int, int> fit;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        auto it = fits.find({kernel, dev});
+        if (it == fits.end()) {
+            int n = 0, cus = 0;
+            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, 0);
+            if (e != hipSuccess) { set_error("%s: occupancy query: %s", what, hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+            it = fits.emplace(std::make_pair(kernel, dev), std::make_pair(n > 0 ? n : -1, cus)).first;
+        }
+        fit = it->second;
+    }
+    PPOAF_REQUIRE(fit.first > 0 && (long)blocks <= (long)fit.first * fit.second,
+                  "%s: %d workgroups cannot be resident together (%d per CU x %d CUs)", what, blocks, fit.first, fit.second);
+    return PPOAF_OK;
+}
 
 // ---- wave64 / workgroup reductions --------------------------------------
 template <typename T>

@@ -1676,17 +1676,10 @@ extern "C" int ppoaf_mat_update_wgrad_adam(const ppoaf_mat_update_args_t* args, 
     td.jobs_a = 1 << 30; td.jobs_c = 0; td.per_xcd = 1;       // one optimiser: every record belongs to the one norm
     PPOAF_REQUIRE(td.nblk <= 64 * kTailMaxRounds, "mat_update_wgrad_adam: %d workgroups, a polling wave holds %d records", td.nblk,
                   64 * kTailMaxRounds);
-    static int per_cu = 0, cus = 0;            // all workgroups wait for each other: they must fit on the device together
-    if (per_cu == 0) {
-        int n = 0, dev = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(mat_update_wgrad_adam_kernel), 256, 0);
-        if (e != hipSuccess) { set_error("mat_update_wgrad_adam: occupancy query: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        per_cu = n > 0 ? n : -1;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    }
-    PPOAF_REQUIRE(per_cu > 0 && (long)(td.nblk + 1) <= (long)per_cu * cus,
-                  "mat_update_wgrad_adam: %d workgroups cannot be resident together (%d per CU x %d CUs)", td.nblk + 1, per_cu, cus);
+    // all workgroups wait for each other: they must fit on the device together
+    const int fit = require_all_resident(reinterpret_cast<const void*>(mat_update_wgrad_adam_kernel), 256, td.nblk + 1,
+                                         "mat_update_wgrad_adam");
+    if (fit) return fit;
     MatAdam ad{exp_avg, exp_avg_sq, lr, beta1, beta2, eps, grad_scale, max_norm, grad_norm_out};
     hipLaunchKernelGGL(mat_update_wgrad_adam_kernel, dim3((unsigned)(td.nblk + 1)), dim3(256), 0, (hipStream_t)stream, u, nsb, ad, td);
     return check_launch("mat_update_wgrad_adam");

@@ -461,18 +461,9 @@ __global__ __launch_bounds__(kWgradThreads) void ppo_update_wgrad_adam_kernel(Up
 template <int HA, int HC, bool XCHG>
 static int tail_launch_as(const UpdateDev& u, const TailDev& td, const TailXchg& xc, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     // every workgroup waits for every other one: all of them must fit on the device at once
-    static int per_cu = 0, cus = 0;            // (queried on the first, eager, launch: nothing but the launch inside a stream capture)
-    if (per_cu == 0) {
-        int n = 0, dev = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(ppo_update_wgrad_adam_kernel<HA, HC, XCHG>),
-                                                                   kWgradThreads, 0);
-        if (e != hipSuccess) { set_error("ppo_update_wgrad_adam: occupancy query: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        per_cu = n > 0 ? n : -1;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    }
-    PPOAF_REQUIRE(per_cu > 0 && (long)(td.nblk + 1) <= (long)per_cu * cus,
-                  "ppo_update_wgrad_adam: %d workgroups cannot be resident together (%d per CU x %d CUs)", td.nblk + 1, per_cu, cus);
+    const int rc = require_all_resident(reinterpret_cast<const void*>(ppo_update_wgrad_adam_kernel<HA, HC, XCHG>), kWgradThreads,
+                                        td.nblk + 1, "ppo_update_wgrad_adam");
+    if (rc) return rc;
     if (e0 || e1)
         hipExtLaunchKernelGGL((ppo_update_wgrad_adam_kernel<HA, HC, XCHG>), dim3((unsigned)(td.nblk + 1)), dim3(kWgradThreads), 0, s, e0, e1, 0, u, td, xc);
     else

@@ -858,18 +858,9 @@ class PPO:
                 t.copy_(keep)
         for t in self._replicated_state():
             mpi_utils.broadcast_flat(t)
-        for f in active:
-            f.xchg.close()
-            f.xchg, f.xchg_reason = None, f"disabled: {why}"
-            for name in ("xchg_sp",):
-                if getattr(f, name, None) is not None:
-                    getattr(f, name).close()
-                    setattr(f, name, None)
-            if type(f).__name__ == "FusedPolicyUpdate":
-                f.split, f.split_reason = f._split_wanted()     # the all-reduce loops run the slab chain
-                f._split_space = None
-            f._graphs.clear()
-            f._args = {}
+        for f in getattr(self, "_fused", {}).values():
+            if f is not None:
+                f.drop_peer_exchange(why)
         self.status_dict["global status"]["peer exchange disabled"] = True
 
     def _ppo_icm_epoch_overlapped(self, loader, policy_id):
@@ -1110,9 +1101,8 @@ class PPO:
             self._fused[key] = None
         if key not in self._fused:
             from .fused_update import FusedMatUpdate, FusedPolicyUpdate
-            if self.policies[policy_id].agent_grouping:
-                FusedPolicyUpdate = FusedMatUpdate                      # K15 instead of K12
-            why = FusedPolicyUpdate.unsupported_reason(self.policies[policy_id], B)
+            driver = FusedMatUpdate if self.policies[policy_id].agent_grouping else FusedPolicyUpdate    # K15 / K12
+            why = driver.unsupported_reason(self.policies[policy_id], B)
             if why:
                 if self.update_mode == "fused":
                     raise NotImplementedError(f"update_mode='fused' but {why}")
@@ -1120,7 +1110,7 @@ class PPO:
                     rank_print(f"policy {policy_id}: torch update path ({why})")
                 self._fused[key] = None
             else:
-                self._fused[key] = FusedPolicyUpdate(self, policy_id)
+                self._fused[key] = driver(self, policy_id)
         return self._fused[key]
 
     def _publish_epoch_stats(self, policy_id, t):

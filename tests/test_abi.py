@@ -99,35 +99,34 @@ def test_every_entry_point_sits_under_a_reference_citation():
         assert needle in src, needle
 
 
-def test_bounded_wait_guard_reports_on_the_host():
+def test_bounded_wait_failure_reports_on_the_host():
     """
     The launches with in-kernel hand-overs (row pairs, fused tail) report a wait that ran out of its budget through an error
-    word; the host side must notice -- never train on -- it: `_persistent_failure` names the reason and switches the form off
-    (the epoch is then redone without it, tests/test_gpu_recovery.py), `_check_persistent` raises it.  Pure host logic:
+    word; the host side must notice -- never train on -- it: `_bounded_wait_failure` names the reason and switches the form
+    off (the epoch is then redone without it, tests/test_gpu_recovery.py), `_check_persistent` raises it.  Pure host logic:
     checked on fabricated control blocks.
     """
-    import types
     import pytest
     import torch
     from ppo_and_friends_amd import _lib
     from ppo_and_friends_amd.fused_update import FusedPolicyUpdate
 
     def block(tail_error, pair_error):
-        ns = types.SimpleNamespace(_tail_ctl=torch.tensor([5, 0, tail_error, 0] + [0] * 12, dtype=torch.int32), _tail_used=True,
-                                   _split_space=torch.zeros(64, dtype=torch.uint8), _pair_region=16, _pairs_used=True,
-                                   _graphs={"x": 1}, _args={"sig": 3, 256: object()})
-        ns._split_space[16:20].view(torch.int32).fill_(pair_error)
-        ns._persistent_failure = lambda: FusedPolicyUpdate._persistent_failure(ns)
-        return ns
+        upd = FusedPolicyUpdate.__new__(FusedPolicyUpdate)
+        upd.__dict__.update(_tail_ctl=torch.tensor([5, 0, tail_error, 0] + [0] * 12, dtype=torch.int32), _tail_used=True,
+                            _split_space=torch.zeros(64, dtype=torch.uint8), _pair_region=16, _pairs_used=True,
+                            _graphs={"x": 1}, _args={"sig": 3, 256: object()})
+        upd._split_space[16:20].view(torch.int32).fill_(pair_error)
+        return upd
 
     ok = block(0, 0)
-    assert FusedPolicyUpdate._persistent_failure(ok) == "" and ok._tail_used is False and ok._pairs_used is False
+    assert ok._bounded_wait_failure() == "" and ok._tail_used is False and ok._pairs_used is False
     bad = block(1, 0)
-    assert "ran out of time" in FusedPolicyUpdate._persistent_failure(bad) and bad._tail_disabled and not bad._graphs
+    assert "ran out of time" in bad._bounded_wait_failure() and bad._tail_disabled and not bad._graphs
     bad = block(0, 1)
-    assert "partner" in FusedPolicyUpdate._persistent_failure(bad) and bad._pairs_disabled and bad._args == {"sig": 3}
+    assert "partner" in bad._bounded_wait_failure() and bad._pairs_disabled and bad._args == {"sig": 3}
     with pytest.raises(_lib.PpoafError, match="ran out of time"):
-        FusedPolicyUpdate._check_persistent(block(1, 0))
+        block(1, 0)._check_persistent()
 
 
 def test_no_memset_in_capturable_paths():

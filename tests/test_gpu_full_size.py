@@ -329,7 +329,7 @@ def test_c5_mat_fused_tail_is_bitwise_the_three_launch_chain(monkeypatch):
     outs = {}
     for tail, graphs in (("0", True), ("1", True), ("1", False)):
         monkeypatch.setenv("PPOAF_FUSED_TAIL", tail)
-        before = fused_update.FusedPolicyUpdate.tail_launches
+        before = fused_update.FusedEpoch.tail_launches
         ppo, E, T, A = _c_config("C5", use_graphs=graphs)
         ppo.rollout()
         pol = ppo.policies["p"]
@@ -343,7 +343,7 @@ def test_c5_mat_fused_tail_is_bitwise_the_three_launch_chain(monkeypatch):
         opt = pol.actor_critic_optim
         n_mb = E * T // 256
         assert t[8] == n_mb and int(opt.step_count.item()) == n_mb
-        assert (fused_update.FusedPolicyUpdate.tail_launches > before) == (tail == "1")
+        assert (fused_update.FusedEpoch.tail_launches > before) == (tail == "1")
         if tail == "1":
             assert fused.tail_reason() == "" and int(fused._tail_ctl[2].item()) == 0 and int(fused._tail_ctl[0].item()) == n_mb
         outs[(tail, graphs)] = (pol.actor_critic.flat_params.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(),

@@ -61,3 +61,35 @@ def test_failed_row_pair_launch_is_redone_with_one_workgroup_per_tile(monkeypatc
     assert "did not answer" in state["updater"].pairs_reason()
     assert torch.equal(rec["w"], tiles["w"]) and torch.equal(rec["m"], tiles["m"])
     assert rec["stats"] == tiles["stats"] and rec["vn"] == tiles["vn"] and rec["steps"] == tiles["steps"]
+
+
+def test_failed_fused_tail_is_redone_with_row_pairs_on(monkeypatch):
+    """
+    A fused tail launch whose workgroups did not all get resident (TailCtl.error, csrc/tail_sync.hpp) costs one epoch's work:
+    the starting state comes back, the fused tail is switched off (with the reason) and the epoch runs again on the wgrad and
+    Adam launches -- with the row pairs still on, so the redo must start from zeroed pair records, not the failed pass's.
+    Bitwise what a run with PPOAF_FUSED_TAIL=0 produces.  Simulated by setting the error word after the first epoch's launches.
+    """
+    from ppo_and_friends_amd import fused_update
+    monkeypatch.setattr(fused_update.FusedPolicyUpdate, "row_pairs", True)
+    monkeypatch.setenv("PPOAF_FUSED_TAIL", "0")
+    three = _run(monkeypatch)
+    monkeypatch.setenv("PPOAF_FUSED_TAIL", "1")
+    before = fused_update.FusedPolicyUpdate.tail_launches
+    orig = fused_update.FusedPolicyUpdate.run_epoch
+    state = {"failed": False, "updater": None}
+
+    def run_epoch(self):
+        orig(self)
+        state["updater"] = self
+        if not state["failed"]:
+            assert self.tail_reason() == "" and self.pairs_reason() == "", (self.tail_reason(), self.pairs_reason())
+            state["failed"] = True
+            self._tail_ctl[2:3].fill_(1)                 # TailCtl.error: "a wait for the norm records ran out of time"
+
+    monkeypatch.setattr(fused_update.FusedPolicyUpdate, "run_epoch", run_epoch)
+    rec = _run(monkeypatch)
+    assert state["failed"] and fused_update.FusedPolicyUpdate.tail_launches > before
+    assert "ran out of time" in state["updater"].tail_reason() and state["updater"].pairs_reason() == ""
+    assert torch.equal(rec["w"], three["w"]) and torch.equal(rec["m"], three["m"])
+    assert rec["stats"] == three["stats"] and rec["vn"] == three["vn"] and rec["steps"] == three["steps"]
