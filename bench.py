@@ -12,25 +12,31 @@ float32 resident in HBM before the timed region, reward 1.0 (CartPole),
 default_rng(1234 + rank).  value = N * E * T * K / max-over-ranks wall time.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full      # + every leg below that takes runs of its own
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line:
+A plain run sets up --config, runs the warm-up and the timed steps, writes --dump-outputs and prints the line; nothing
+else.  Rank 0 prints ONE JSON line:
+  value, ms_per_step  env-steps/s and wall time per step of the timed region (the headline)
   roofline            the GAE kernel (the kernel the metric names), HIP kernel events inside the timed region
-  roofline_update     the kernel that dominates the step: FLOP per launch / its launch time vs the f32-MFMA peak.
-                      Single rank, MLP policies: the two-XCD persistent kernel (ONE launch per epoch = all full
-                      mini-batches; begin / end events of epoch launches made right after the timed region).
-                      Otherwise K12 / K15 fwd_bwd (kernel begin/end events on eager launches of the same chain right
-                      after the timed region -- the in-region launches are hipGraph nodes, which cannot carry stamps)
-  config.other_configs  short runs (2 steps) of the other BASELINE configs' shapes (C3, C4, C5) in the same process
-                      (N = 1; at N > 1 only with PPOAF_BENCH_OTHER_CONFIGS_MULTI=1)
-  cpu_baseline        oracle/cpu_ppo_loop.py (a port with the reference's loop structure, pinned against fixtures
-                      recorded from the reference) on a bounded sample: 1 process; cpu_baseline_mpi: R = 8 processes
-                      in the reference's launch model (oracle/cpu_ddppo.py, gloo); cpu_baseline_c1: C1 exactly.
-                      Rank 0, N = 1 only; fresh CPU-only child processes, run before the GPU is touched.
   dump_outputs        with --dump-outputs DIR: the arrays the last timed step of --config computed (dump_outputs()),
                       written to DIR as .npy right after the timed region; inputs are seeded, so two builds run with
                       the same arguments can be compared array by array
+  full                whether the --full legs ran
+With --full, after the timed region (the CPU baselines before the GPU is touched):
+  roofline_update     the kernel that dominates the step: FLOP per launch / its launch time vs the f32-MFMA peak,
+                      K12 / K15 fwd_bwd (kernel begin/end events on eager launches of the same chain right after the
+                      timed region -- the in-region launches are hipGraph nodes, which cannot carry stamps); single rank
+  exchange_probe      N > 1: what one gradient exchange of the bucket costs (K17 and the process group's all-reduce)
+  config.other_configs  short runs (2 steps) of the other BASELINE configs' shapes (C3, C4, C5) in the same process
+                      (N = 1; at N > 1 only with PPOAF_BENCH_OTHER_CONFIGS_MULTI=1; --no-other-configs drops them)
+  roofline_saturating the GAE kernel at a bandwidth-saturating size (2^28 transitions; --no-saturating drops it)
+  cpu_baseline        oracle/cpu_ppo_loop.py (a port with the reference's loop structure, pinned against fixtures
+                      recorded from the reference) on a bounded sample: 1 process; cpu_baseline_mpi: R = --cpu-ranks
+                      processes in the reference's launch model (oracle/cpu_ddppo.py, gloo); cpu_baseline_c1: C1 exactly.
+                      Rank 0, N = 1, --config C2 only; fresh CPU-only child processes, run before the GPU is touched
+                      (--no-cpu-baseline drops them).
 """
 import argparse
 import json
@@ -120,6 +126,9 @@ def parse():
     p.add_argument("--batch-size", type=int, default=256)
     p.add_argument("--epochs", type=int, default=10)
     p.add_argument("--no-graphs", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs that take runs of their own: roofline_update, exchange_probe, the other configs, "
+                        "roofline_saturating and the CPU baselines (the --no-* options below drop single legs of it)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-sample-envs", type=int, default=256)
     p.add_argument("--no-saturating", action="store_true")
@@ -460,7 +469,7 @@ def run_config(name, args, device, rank, world, steps, warmup, with_gae_roofline
     # K17 kernel and with the process group's all-reduce (back-to-back launches, stream events) -- recorded so that
     # a multi-GPU run documents the latency its scaling number rests on
     probe = None
-    if mpi_utils.distributed_path() and fused and with_gae_roofline:
+    if args.full and mpi_utils.distributed_path() and fused and with_gae_roofline:
         n_f = pol.policy_grads.numel()
         buf = torch.zeros(n_f, dtype=torch.float32, device=device)
         reps = 200
@@ -486,7 +495,7 @@ def run_config(name, args, device, rank, world, steps, warmup, with_gae_roofline
                 dist.all_reduce(buf)
             probe["process_group_allreduce_us"] = round(timed(lambda: dist.all_reduce(buf)), 2)
     res["exchange_probe"] = probe
-    if not mpi_utils.distributed_path():                      # single rank: the eager chain is this rank's own
+    if args.full and not mpi_utils.distributed_path():        # single rank: the eager chain is this rank's own
         res["roofline_update"] = update_kernel_roofline(ppo, pol, args.batch_size, config=name)
     del ppo, pol, fused
     import gc
@@ -507,7 +516,7 @@ def main():
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
     env_rank = int(os.environ.get("RANK", "0"))
     cpu = {}
-    if env_world == 1 and env_rank == 0 and not args.no_cpu_baseline and args.config == "C2":
+    if args.full and env_world == 1 and env_rank == 0 and not args.no_cpu_baseline and args.config == "C2":
         cpu = cpu_baselines(args)                             # CPU-only child processes, before the GPU is touched
 
     import torch
@@ -535,7 +544,7 @@ def main():
     # overlapped PPO / ICM epochs) are rehearsed by `PPOAF_REHEARSE_MULTI_RANK=1 bench.py --config <C>` and the two-process
     # tests, and run here only on request -- a failure in one of them must not cost the headline measurement
     others_wanted = world == 1 or os.environ.get("PPOAF_BENCH_OTHER_CONFIGS_MULTI", "0") == "1"
-    if args.config == "C2" and not args.no_other_configs and others_wanted:
+    if args.full and args.config == "C2" and not args.no_other_configs and others_wanted:
         for name in CONFIGS:
             if name == "C2":
                 continue
@@ -560,13 +569,13 @@ def main():
                       "rollout_s": main_res["rollout_s"], "train_s": main_res["train_s"],
                       "update_kernel": update_note or (main_res.get("roofline_update") or {}).get("kernel"),
                       "other_configs": others or None},
-           "roofline": main_res["roofline"]}
+           "roofline": main_res["roofline"], "full": args.full}
     if args.dump_outputs is not None:
         out["dump_outputs"] = {"dir": args.dump_outputs, "config": args.config, "arrays": main_res.get("dumped")}
     if main_res.get("roofline_update") is not None:
         out["roofline_update"] = main_res["roofline_update"]
 
-    if rank == 0 and not args.no_saturating:
+    if args.full and rank == 0 and not args.no_saturating:
         # companion: same kernel at a bandwidth-saturating size (N = 2^28 transitions)
         Es = (1 << 28) // T
         r = torch.rand(T, Es, device=device); v = torch.randn(T, Es, device=device)

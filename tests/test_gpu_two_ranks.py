@@ -345,7 +345,8 @@ def test_bench_contract_under_the_drivers_two_rank_launch():
     The driver's N > 1 command -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
     127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W` -- rehearsed with N = 2 on the one GPU of
     the box (PPOAF_BACKEND=gloo: RCCL refuses two ranks on a device; PPOAF_SHARE_DEVICE=1: both ranks on device 0).
-    One JSON line from rank 0, whole-job value, weak scaling, the K17 exchange inside graph-replayed chains.
+    One JSON line from rank 0, whole-job value, weak scaling, the K17 exchange inside graph-replayed chains; with --full,
+    so that the other configs' lines ride in it too.
     """
     import json
     import subprocess
@@ -356,7 +357,7 @@ def test_bench_contract_under_the_drivers_two_rank_launch():
     env.pop("PPOAF_GRAD_EXCHANGE", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--epochs", "1", "--no-cpu-baseline", "--no-saturating"]
+           "--epochs", "1", "--full", "--no-cpu-baseline", "--no-saturating"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -2,7 +2,7 @@
 import os, sys, gc
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import bench
-sys.argv = [sys.argv[0], "--no-cpu-baseline", "--no-saturating"]
+sys.argv = [sys.argv[0], "--full", "--no-cpu-baseline", "--no-saturating"]
 args = bench.parse()
 import torch
 from ppo_and_friends_amd.utils import mpi_utils

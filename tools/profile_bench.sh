@@ -12,7 +12,7 @@ HB=$!
 for CFG in "$@"; do
   rm -rf /tmp/prof_$CFG
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$CFG -o $CFG -- \
-      python3 $R/bench.py --config $CFG --steps 1 --warmup 1 --epochs 3 --no-cpu-baseline --no-saturating --no-other-configs \
+      python3 $R/bench.py --config $CFG --steps 1 --warmup 1 --epochs 3 --full --no-cpu-baseline --no-saturating --no-other-configs \
       > $R/gpurun_out/prof/${TAG}_${CFG}_under_rocprof.json 2> /tmp/prof_$CFG.err
   echo "[profile_bench] $CFG rc=$?"
   f=$(find /tmp/prof_$CFG -name "*kernel_stats.csv" | head -1)
