@@ -331,8 +331,15 @@ int ppoaf_adam_step_prenormed(float* params, const float* grads,
 #define PPOAF_ACT_RELU        0
 #define PPOAF_ACT_LEAKY_RELU  1      /* negative slope 0.01 (nn.LeakyReLU default) */
 #define PPOAF_ACT_TANH        2
-#define PPOAF_HEAD_CATEGORICAL 0
-#define PPOAF_HEAD_GAUSSIAN    1
+#define PPOAF_HEAD_CATEGORICAL 0       /* Discrete: softmax -> Categorical, networks/distributions.py:199-269, :1043-1045 */
+#define PPOAF_HEAD_GAUSSIAN    1       /* Box: tanh-Gaussian with a learned log_std, :441-694 */
+/* MultiDiscrete (:272-438, output function :1047-1064): actor.out_dim = the sum of the slice table (n_action_slices,
+ * action_slices[] at the end of the args structs); per slice softmax -> Categorical(probs); log-prob and entropy summed
+ * over the slices.  Raw actions int64 [rows, n_action_slices]. */
+#define PPOAF_HEAD_MULTI_CATEGORICAL 2
+/* MultiBinary (:134-196, output function sigmoid :1111-1113): one bit per actor output, torch Bernoulli(probs =
+ * sigmoid(z)) with its eps clamp; log-prob and entropy summed over the bits.  Raw actions float32 [rows, out_dim], 0 / 1. */
+#define PPOAF_HEAD_BERNOULLI   3
 #define PPOAF_UPDATE_ROWS_PER_WG 16
 
 typedef struct {
@@ -355,7 +362,7 @@ typedef struct {
                                    * + per-workgroup squared-norm partials (actor, critic) of the reduce / norm pass */
     float beta1, beta2, adam_eps, grad_scale, max_norm; int32_t head_kind;
     /* rollout buffer (time-major rows) */
-    const float* obs; const float* critic_obs; const void* raw_actions;  /* int64 [n,1] or f32 [n,D] */
+    const float* obs; const float* critic_obs; const void* raw_actions;  /* int64 [n,1] / [n,D] or f32 [n,D] (head_kind) */
     const float* advantages; const float* old_log_probs; const float* rewards_to_go;
     float* values;                /* write-back target                                     */
     const int64_t* perm; const int32_t* row_map; int64_t n_rows;
@@ -403,6 +410,10 @@ typedef struct {
      * The region's first 32-bit word (byte offset ppoaf_ppo_update_row_pairs_error_offset()) is non-zero after a launch in
      * which a partner did not answer within 2 s; that launch's results are invalid. */
     int32_t row_pairs;
+    /* the slice table of PPOAF_HEAD_MULTI_CATEGORICAL: classes per action dimension, in order, summing to actor.out_dim.
+     * Read only for that head kind (appended: every field above keeps its offset). */
+    int32_t n_action_slices;
+    int32_t action_slices[8];
 } ppoaf_ppo_update_args_t;
 
 int ppoaf_ppo_update_fwd_bwd(const ppoaf_ppo_update_args_t* args, ppoaf_stream_t stream);
@@ -452,7 +463,10 @@ int ppoaf_ppo_update_adam(const ppoaf_ppo_update_args_t* args, int compute_norms
  * running stats when normalize_values), written straight into row t of the
  * rollout buffer.  obs / critic_obs: [E, in_dim] float32; outputs are the row-t
  * slices of the buffer ([E,1] int64 actions for the categorical head, [E,D]
- * float32 for the Gaussian head).  *_copy_out (optional) receive the
+ * float32 for the Gaussian head, [E,D] int64 for the multi-categorical head --
+ * slice j of env e samples with counter offset + j * E + e --, [E,n] float32
+ * 0 / 1 for the Bernoulli head: bit d = u < sigmoid(z_d), u from counter offset + e,
+ * subsequence d / 4).  *_copy_out (optional) receive the
  * observation rows.  Network descriptors as for K12.
  * ------------------------------------------------------------------------ */
 typedef struct {
@@ -468,6 +482,8 @@ typedef struct {
     const float* vn_mean; const float* vn_var;
     void* raw_action_out; void* action_out; float* logp_out; float* value_out;
     float* obs_copy_out; float* critic_obs_copy_out;
+    int32_t n_action_slices;                    /* PPOAF_HEAD_MULTI_CATEGORICAL only, as in ppoaf_ppo_update_args_t */
+    int32_t action_slices[8];
 } ppoaf_policy_step_args_t;
 
 int ppoaf_policy_step(const ppoaf_policy_step_args_t* args, ppoaf_stream_t stream);

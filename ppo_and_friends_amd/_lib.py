@@ -66,7 +66,8 @@ class PpoUpdateArgs(C.Structure):
                 ("loss_partials", C.c_void_p), ("totals", C.c_void_p),
                 ("mb_offset", C.c_int64), ("cursor_advance", C.c_int64),
                 ("split_workspace", C.c_void_p), ("split_workspace_bytes", C.c_int64),
-                ("xcd_half", C.c_int32), ("row_pairs", C.c_int32)]
+                ("xcd_half", C.c_int32), ("row_pairs", C.c_int32),
+                ("n_action_slices", C.c_int32), ("action_slices", C.c_int32 * 8)]
 
 
 ABI_VERSION = 7
@@ -83,7 +84,8 @@ class PolicyStepArgs(C.Structure):
                 ("vn_mean", C.c_void_p), ("vn_var", C.c_void_p),
                 ("raw_action_out", C.c_void_p), ("action_out", C.c_void_p),
                 ("logp_out", C.c_void_p), ("value_out", C.c_void_p),
-                ("obs_copy_out", C.c_void_p), ("critic_obs_copy_out", C.c_void_p)]
+                ("obs_copy_out", C.c_void_p), ("critic_obs_copy_out", C.c_void_p),
+                ("n_action_slices", C.c_int32), ("action_slices", C.c_int32 * 8)]
 
 
 # name -> (restype, argtypes); mirrors include/ppoaf_hip.h one to one.

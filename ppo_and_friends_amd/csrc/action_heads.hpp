@@ -1,0 +1,207 @@
+// MultiDiscrete and MultiBinary heads on <= 8 actor outputs, one lane per row: shared by the rollout step (K6+K7,
+// policy_step.hip) and the fused update (K12, ppo_update_dev.hpp: ppo_head_loss).  Both take a row's log-prob from the
+// same functions here, on output values formed by the same output-layer code, so the log-prob logged for a row and the
+// one its first mini-batch recomputes are bitwise equal.
+//   MultiDiscrete(nvec)  networks/distributions.py:272-438, output function :1047-1064: slice j = outputs
+//                        [o_j, o_j + nvec[j]); per slice softmax -> Categorical(probs) (renormalised, clamp_probs, log);
+//                        log-prob and entropy are sums over the slices.
+//   MultiBinary(n)       :134-196, output function :1111-1113: torch Bernoulli(probs = sigmoid(z)), whose logits are
+//                        l = log q - log1p(-q), q = clamp(p, eps, 1 - eps); log-prob = -BCEWithLogits(l, a), entropy =
+//                        BCEWithLogits(l, p) with the unclamped p as the target, both summed over the bits.
+// Per-class values live in float[8] register arrays that are only ever indexed by unrolled loop counters (a runtime index
+// would put them in scratch); slices are walked through a bit mask instead.
+#pragma once
+#include "mlp_device.hpp"
+
+namespace ppoaf {
+
+// ---- host: the head fields of ppoaf_ppo_update_args_t / ppoaf_policy_step_args_t
+inline int check_action_head(const char* what, int head_kind, const ppoaf_mlp_desc_t& actor, int n_slices,
+                             const int32_t* slices) {
+    PPOAF_REQUIRE(head_kind >= PPOAF_HEAD_CATEGORICAL && head_kind <= PPOAF_HEAD_BERNOULLI,
+                  "%s: head_kind=%d (0 categorical, 1 Gaussian, 2 multi-categorical, 3 Bernoulli)", what, head_kind);
+    if (head_kind == PPOAF_HEAD_GAUSSIAN) {
+        PPOAF_REQUIRE(actor.log_std_offset >= 0, "%s: log_std offset must be given exactly for the Gaussian head", what);
+        return PPOAF_OK;
+    }
+    PPOAF_REQUIRE(actor.log_std_offset < 0, "%s: log_std offset must be given exactly for the Gaussian head (head_kind=%d)",
+                  what, head_kind);
+    if (head_kind == PPOAF_HEAD_MULTI_CATEGORICAL) {
+        PPOAF_REQUIRE(n_slices >= 1 && n_slices <= 8, "%s: n_action_slices=%d out of [1,8]", what, n_slices);
+        int sum = 0;
+        for (int j = 0; j < n_slices; ++j) {
+            PPOAF_REQUIRE(slices[j] >= 1, "%s: action_slices[%d]=%d (every slice needs >= 1 class)", what, j, slices[j]);
+            sum += slices[j];
+        }
+        PPOAF_REQUIRE(sum == actor.out_dim, "%s: action_slices sum to %d, the actor has %d outputs", what, sum,
+                      actor.out_dim);
+    }
+    return PPOAF_OK;       // (Bernoulli: one bit per actor output; out_dim <= 8 is checked with the network)
+}
+
+// ---- MultiDiscrete
+// bit k set where class k opens a slice; every class from sum(nvec) on opens one of its own, so no slice runs into padding
+__device__ __forceinline__ unsigned mcat_starts(const int n_slices, const int* nvec) {
+    unsigned first = 0u;
+    int o = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        if (j < n_slices) { first |= 1u << o; o += nvec[j]; }
+    return first | (0xffu << o);
+}
+
+// every class <- the max / the sum of its slice, formed in ascending class order (as distributions.hip's softmax_row)
+template <bool MAX>
+__device__ __forceinline__ void slice_totals(const float* v, float* t, const unsigned first) {
+    float r = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        r = ((first >> k) & 1u) ? v[k] : (MAX ? fmaxf(r, v[k]) : r + v[k]);
+        t[k] = r;
+    }
+#pragma unroll
+    for (int k = 6; k >= 0; --k)
+        if (!((first >> (k + 1)) & 1u)) t[k] = t[k + 1];
+}
+
+// per-slice F.softmax -> p; the slice's sum of p (Categorical's own renormaliser, ~1) -> s.  Padding classes: p = 0.
+__device__ __forceinline__ void mcat_probs(const float* z, const unsigned first, const int out_dim, float* p, float* s) {
+    float t[8];
+    slice_totals<true>(z, t, first);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) p[k] = k < out_dim ? expf(z[k] - t[k]) : 0.f;
+    slice_totals<false>(p, t, first);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) p[k] = k < out_dim ? p[k] * (1.0f / t[k]) : 0.f;
+    slice_totals<false>(p, s, first);
+}
+
+// the chosen class of every slice as a mask, bit o_j + a_j (a_j clamped into the slice, as the categorical head does)
+template <typename I>
+__device__ __forceinline__ unsigned mcat_pick(const I* a, const int n_slices, const int* nvec) {
+    unsigned pick = 0u;
+    int o = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (j < n_slices) {
+            const long c = (long)a[j];
+            pick |= 1u << (o + (c < 0 ? 0 : (c >= nvec[j] ? nvec[j] - 1 : (int)c)));
+            o += nvec[j];
+        }
+    }
+    return pick;
+}
+
+// K6: slice j of env row e draws Philox (seed, offset + j * E + e, 0).x and takes the inverse CDF over the unnormalised
+// mass (distributions.hip: categorical_sample_kernel) -- the counters of the torch path's per-slice samples
+__device__ __forceinline__ unsigned mcat_sample(const float* p, const float* s, const unsigned first, const int out_dim,
+                                                const unsigned long long seed, const unsigned long long offset,
+                                                const long E, const long e) {
+    unsigned pick = 0u;
+    int j = -1;
+    float uu = 0.f, c = 0.f;
+    bool found = true;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if (k < out_dim) {
+            if ((first >> k) & 1u) {
+                ++j;
+                const Philox4 r = philox4x32_10(seed, offset + (unsigned long long)j * E + e, 0u);
+                uu = u32_to_unit(r.x) * s[k];
+                c = 0.f;
+                found = false;
+            }
+            c += p[k];
+            if (!found && (uu < c || ((first >> (k + 1)) & 1u))) { pick |= 1u << k; found = true; }
+        }
+    }
+    return pick;
+}
+
+// log-prob of the chosen classes: the slices' log(clamp(p / s)), summed in slice order
+__device__ __forceinline__ float mcat_logp(const float* p, const float* s, const unsigned pick) {
+    float lp = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if ((pick >> k) & 1u) lp += logf(clamp_prob_u(p[k] / s[k]));
+    return lp;
+}
+
+// K12: the sum of the slice entropies, and d loss / d z -> dz for d loss / d log-prob = glp, d loss / d entropy = gH:
+// the categorical head's chain z -softmax-> p -(/sum)-> n -clamp,log-> l, slice by slice
+__device__ __forceinline__ float mcat_entropy_grad(const float* p, const float* s, const unsigned first,
+                                                   const unsigned pick, const int out_dim, const float glp,
+                                                   const float gH, float* dz) {
+    float g[8], h[8], t[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        g[k] = 0.f; h[k] = 0.f; t[k] = 0.f;
+        if (k < out_dim) {
+            const float nk = p[k] / s[k], ck = clamp_prob_u(nk), lk = logf(ck);
+            const float in_range = (nk >= FLT_EPSILON && nk <= 1.0f - FLT_EPSILON) ? 1.f : 0.f;
+            h[k] = -(nk * lk);
+            float gk = gH * (-lk - nk * in_range / ck);
+            if ((pick >> k) & 1u) gk += glp * in_range / ck;
+            g[k] = gk;
+            t[k] = gk * nk;
+        }
+    }
+    slice_totals<false>(h, h, first);
+    float ent = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k < out_dim && ((first >> k) & 1u)) ent += h[k];
+    slice_totals<false>(t, t, first);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        g[k] = k < out_dim ? (g[k] - t[k]) / s[k] : 0.f;
+        h[k] = g[k] * p[k];
+    }
+    slice_totals<false>(h, t, first);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dz[k] = k < out_dim ? p[k] * (g[k] - t[k]) : 0.f;
+    return ent;
+}
+
+// ---- MultiBinary
+__device__ __forceinline__ float sigmoid_u(float x) { return 1.0f / (1.0f + expf(-x)); }
+// torch's probs_to_logits(is_binary=True) of the clamped probability q
+__device__ __forceinline__ float bern_logit(float q) { return logf(q) - log1pf(-q); }
+// BCEWithLogits(l, t) = (1 - t) l - log sigmoid(l)
+__device__ __forceinline__ float bce_with_logits(float l, float t) {
+    return (1.0f - t) * l - (fminf(l, 0.f) - log1pf(expf(-fabsf(l))));
+}
+
+// log-prob of the bits a[0 .. n)
+template <typename A>
+__device__ __forceinline__ float bern_logp(const float* z, const A& a, const int n) {
+    float lp = 0.f;
+#pragma unroll
+    for (int d = 0; d < 8; ++d)
+        if (d < n) lp -= bce_with_logits(bern_logit(clamp_prob_u(sigmoid_u(z[d]))), a[d]);
+    return lp;
+}
+
+// K12: entropy, and d loss / d z -> dz as torch autograd forms it: the clamp passes no gradient outside [eps, 1 - eps]
+// (bounds included); the entropy's target p carries a term of its own everywhere
+template <typename A>
+__device__ __forceinline__ float bern_entropy_grad(const float* z, const A& a, const int n, const float glp,
+                                                   const float gH, float* dz) {
+    float ent = 0.f;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        dz[d] = 0.f;
+        if (d < n) {
+            const float p = sigmoid_u(z[d]), q = clamp_prob_u(p), l = bern_logit(q);
+            ent += bce_with_logits(l, p);
+            const float sl = sigmoid_u(l);
+            const float in_range = (p >= FLT_EPSILON && p <= 1.0f - FLT_EPSILON) ? 1.f : 0.f;
+            const float gl = glp * (a[d] - sl) + gH * (sl - p);                 // d / dl of -BCE(l, a) and of BCE(l, p)
+            const float gp = gl * in_range * (1.0f / q + 1.0f / (1.0f - q)) - gH * l;
+            dz[d] = gp * (1.0f - p) * p;
+        }
+    }
+    return ent;
+}
+
+}  // namespace ppoaf

@@ -9,7 +9,7 @@
 // grid = 2 * ceil(E/16) workgroups (XCD-grouped like the update kernel: blocks 0-3 mod 8 actor, 4-7
 // critic), 512 threads: 16 env rows per workgroup, hidden layers on v_mfma_f32_16x16x4_f32 with the same
 // tile code as the update's forward, so a row's log-prob here and in the first mini-batch agree bit for bit.
-#include "mlp_device.hpp"
+#include "action_heads.hpp"
 
 namespace ppoaf {
 
@@ -28,11 +28,14 @@ struct StepDev {
     void* raw_action_out; void* action_out; float* logp_out; float* value_out;
     float* obs_out; float* critic_obs_out;     // buffer rows for the observation copies (may be NULL)
     int n_wg;
+    int n_slices; int slices[8];               // multi-categorical head: classes per action dimension
 };
 
 extern __shared__ __attribute__((aligned(16))) unsigned char policy_step_smem[];
 
-template <int HT>
+// XH: the MultiDiscrete / MultiBinary heads are compiled in (instantiations of their own, so that the categorical and
+// Gaussian ones keep their registers)
+template <int HT, bool XH>
 __device__ __forceinline__ void policy_step_body(const StepDev& u, const int which, const int g) {
     constexpr int H = 16 * HT, HS = H + 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -169,6 +172,54 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
             reinterpret_cast<int64_t*>(u.raw_action_out)[e] = a;
             reinterpret_cast<int64_t*>(u.action_out)[e] = a;
             u.logp_out[e] = logf(clamp_prob_u(pa / s2));
+        } else if (XH) {
+            // MultiDiscrete / MultiBinary: the log-prob by the functions K12 recomputes it with (action_heads.hpp)
+            float z[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) z[k] = k < out_dim ? sOut[s * kMaxOut + k] : 0.f;
+            if (u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL) {
+                const int D = u.n_slices;
+                const unsigned first = mcat_starts(D, u.slices);
+                float p[8], sm[8];
+                mcat_probs(z, first, out_dim, p, sm);
+                const unsigned pick = u.forced_raw_action
+                    ? mcat_pick(reinterpret_cast<const int64_t*>(u.forced_raw_action) + e * D, D, u.slices)
+                    : mcat_sample(p, sm, first, out_dim, u.seed, u.offset, u.E, e);
+                int64_t* raw = reinterpret_cast<int64_t*>(u.raw_action_out) + e * D;
+                int64_t* ac = reinterpret_cast<int64_t*>(u.action_out) + e * D;
+                int j = -1, o = 0;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (k < out_dim) {
+                        if ((first >> k) & 1u) { ++j; o = k; }
+                        if ((pick >> k) & 1u) { raw[j] = k - o; ac[j] = k - o; }
+                    }
+                }
+                u.logp_out[e] = mcat_logp(p, sm, pick);
+            } else {
+                // bit d = u_d < sigmoid(z_d), u_d = component d % 4 of Philox (seed, offset + e, d / 4)
+                const float* forced = reinterpret_cast<const float*>(u.forced_raw_action);
+                float* raw = reinterpret_cast<float*>(u.raw_action_out) + e * out_dim;
+                float* ac = reinterpret_cast<float*>(u.action_out) + e * out_dim;
+                float a[8];
+                Philox4 r = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int d = 0; d < 8; ++d) {
+                    a[d] = 0.f;
+                    if (d < out_dim) {
+                        if (forced) {
+                            a[d] = forced[e * out_dim + d];
+                        } else {
+                            if ((d & 3) == 0) r = philox4x32_10(u.seed, u.offset + (unsigned long long)e, (uint32_t)(d >> 2));
+                            const uint32_t w = (d & 3) == 0 ? r.x : ((d & 3) == 1 ? r.y : ((d & 3) == 2 ? r.z : r.w));
+                            a[d] = u32_to_unit(w) < sigmoid_u(z[d]) ? 1.f : 0.f;
+                        }
+                        raw[d] = a[d];
+                        ac[d] = a[d];
+                    }
+                }
+                u.logp_out[e] = bern_logp(z, a, out_dim);
+            }
         } else {
             const float* log_std = P + nd.log_std_off;
             float* raw = reinterpret_cast<float*>(u.raw_action_out) + e * out_dim;
@@ -205,14 +256,14 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
     }
 }
 
-template <int HTA, int HTC>
+template <int HTA, int HTC, bool XH>
 __global__ __launch_bounds__(kThreadsS) void policy_step_kernel(StepDev u) {
     const int b = blockIdx.x;
     const int which = (b >> 2) & 1;
     const int g = ((b >> 3) << 2) | (b & 3);
     if (g >= u.n_wg) return;
-    if (which == 0) policy_step_body<HTA>(u, 0, g);
-    else policy_step_body<HTC>(u, 1, g);
+    if (which == 0) policy_step_body<HTA, XH>(u, 0, g);
+    else policy_step_body<HTC, XH>(u, 1, g);
 }
 
 static size_t step_lds_bytes(const StepDev& u) {
@@ -226,18 +277,31 @@ static size_t step_lds_bytes(const StepDev& u) {
     return (worst + 15) / 16 * 16;
 }
 
-template <int HTA, int HTC>
+template <int HTA, int HTC, bool XH>
 static int launch_step(const StepDev& u, size_t lds, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_step_kernel<HTA, HTC>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_step_kernel<HTA, HTC, XH>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
         attr_set = true;
     }
     const unsigned grid = 8u * (unsigned)((u.n_wg + 3) / 4);
-    hipLaunchKernelGGL((policy_step_kernel<HTA, HTC>), dim3(grid), dim3(kThreadsS), lds, s, u);
+    hipLaunchKernelGGL((policy_step_kernel<HTA, HTC, XH>), dim3(grid), dim3(kThreadsS), lds, s, u);
     return check_launch("policy_step");
+}
+
+template <bool XH>
+static int launch_widths(const StepDev& u, size_t lds, hipStream_t s) {
+    const int ha = u.net[0].H, hc = u.net[1].H;
+    if (ha == 32 && hc == 32) return launch_step<2, 2, XH>(u, lds, s);
+    if (ha == 64 && hc == 64) return launch_step<4, 4, XH>(u, lds, s);
+    if (ha == 128 && hc == 128) return launch_step<8, 8, XH>(u, lds, s);
+    if (ha == 256 && hc == 256) return launch_step<16, 16, XH>(u, lds, s);
+    if (ha == 128 && hc == 256) return launch_step<8, 16, XH>(u, lds, s);
+    if (ha == 64 && hc == 128) return launch_step<4, 8, XH>(u, lds, s);
+    set_error("policy_step: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
+    return PPOAF_E_INVALID;
 }
 
 }  // namespace ppoaf
@@ -258,10 +322,9 @@ extern "C" int ppoaf_policy_step(const ppoaf_policy_step_args_t* a, ppoaf_stream
                       a->logp_out && a->value_out,
                   "policy_step: null pointer");
     PPOAF_REQUIRE(a->critic.out_dim == 1, "policy_step: critic out_dim must be 1");
-    PPOAF_REQUIRE(a->head_kind == PPOAF_HEAD_CATEGORICAL || a->head_kind == PPOAF_HEAD_GAUSSIAN,
-                  "policy_step: head_kind=%d", a->head_kind);
-    PPOAF_REQUIRE((a->head_kind == PPOAF_HEAD_GAUSSIAN) == (a->actor.log_std_offset >= 0),
-                  "policy_step: log_std offset must be given exactly for the Gaussian head");
+    rc = check_action_head("policy_step", a->head_kind, a->actor,
+                           a->head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? a->n_action_slices : 0, a->action_slices);
+    if (rc) return rc;
     PPOAF_REQUIRE(!a->normalize_values || (a->vn_mean && a->vn_var), "policy_step: normaliser state missing");
     u.params = a->params; u.obs = a->obs; u.critic_obs = a->critic_obs; u.E = a->E;
     PPOAF_REQUIRE((a->act_lo == nullptr) == (a->act_hi == nullptr), "policy_step: give both action bounds or neither");
@@ -272,16 +335,10 @@ extern "C" int ppoaf_policy_step(const ppoaf_policy_step_args_t* a, ppoaf_stream
     u.action_out = a->action_out; u.logp_out = a->logp_out; u.value_out = a->value_out;
     u.obs_out = a->obs_copy_out; u.critic_obs_out = a->critic_obs_copy_out;
     u.n_wg = (int)((a->E + kRows - 1) / kRows);
+    u.n_slices = a->head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? a->n_action_slices : 0;
+    for (int j = 0; j < 8; ++j) u.slices[j] = j < u.n_slices ? a->action_slices[j] : 0;
     const size_t lds = step_lds_bytes(u);
     PPOAF_REQUIRE(lds <= 160 * 1024, "policy_step: needs %zu B of LDS", lds);
     hipStream_t s = (hipStream_t)stream;
-    const int ha = u.net[0].H, hc = u.net[1].H;
-    if (ha == 32 && hc == 32) return launch_step<2, 2>(u, lds, s);
-    if (ha == 64 && hc == 64) return launch_step<4, 4>(u, lds, s);
-    if (ha == 128 && hc == 128) return launch_step<8, 8>(u, lds, s);
-    if (ha == 256 && hc == 256) return launch_step<16, 16>(u, lds, s);
-    if (ha == 128 && hc == 256) return launch_step<8, 16>(u, lds, s);
-    if (ha == 64 && hc == 128) return launch_step<4, 8>(u, lds, s);
-    set_error("policy_step: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
-    return PPOAF_E_INVALID;
+    return u.head_kind >= PPOAF_HEAD_MULTI_CATEGORICAL ? launch_widths<true>(u, lds, s) : launch_widths<false>(u, lds, s);
 }

@@ -313,10 +313,9 @@ int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
                       a->bucket_total == a->actor.size + a->critic.size,
                   "ppo_update: actor and critic must be adjacent in one bucket");
     PPOAF_REQUIRE(a->critic.out_dim == 1 && a->critic.log_std_offset < 0, "ppo_update: critic out_dim must be 1");
-    PPOAF_REQUIRE(a->head_kind == PPOAF_HEAD_CATEGORICAL || a->head_kind == PPOAF_HEAD_GAUSSIAN,
-                  "ppo_update: head_kind=%d", a->head_kind);
-    PPOAF_REQUIRE((a->head_kind == PPOAF_HEAD_GAUSSIAN) == (a->actor.log_std_offset >= 0),
-                  "ppo_update: log_std offset must be given exactly for the Gaussian head");
+    rc = check_action_head("ppo_update", a->head_kind, a->actor,
+                           a->head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? a->n_action_slices : 0, a->action_slices);
+    if (rc) return rc;
     PPOAF_REQUIRE(a->B >= 2 && a->batch_stride >= a->B, "ppo_update: B=%ld stride=%ld", (long)a->B,
                   (long)a->batch_stride);
     PPOAF_REQUIRE(a->params && a->grads && a->exp_avg && a->exp_avg_sq && a->slabs && a->step_counts &&
@@ -334,6 +333,8 @@ int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
     u.slabs = a->slabs; u.bucket_total = a->bucket_total; u.step_counts = a->step_counts; u.lr = a->lr;
     u.norm_scratch = a->norm_scratch; u.beta1 = a->beta1; u.beta2 = a->beta2; u.adam_eps = a->adam_eps;
     u.grad_scale = a->grad_scale; u.max_norm = a->max_norm; u.head_kind = a->head_kind;
+    u.n_slices = a->head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? a->n_action_slices : 0;
+    for (int j = 0; j < 8; ++j) u.slices[j] = j < u.n_slices ? a->action_slices[j] : 0;
     u.obs = a->obs; u.critic_obs = a->critic_obs; u.raw_actions = a->raw_actions; u.adv = a->advantages;
     u.old_lp = a->old_log_probs; u.rtg = a->rewards_to_go; u.values = a->values; u.perm = a->perm;
     u.row_map = a->row_map; u.n_rows = a->n_rows; u.cursor = a->cursor; u.B = a->B;
@@ -514,7 +515,7 @@ extern "C" int ppoaf_ppo_update_chain_allreduce(const ppoaf_ppo_update_args_t* a
     PPOAF_REQUIRE(args && comm, "ppo_update_chain_allreduce: null argument");
     PPOAF_REQUIRE(n_minibatches >= 1 && n_minibatches <= (1 << 20), "ppo_update_chain_allreduce: n_minibatches=%ld", (long)n_minibatches);
     PPOAF_REQUIRE(args->mb_offset == 0, "ppo_update_chain_allreduce: mb_offset must be 0");
-    ppoaf_ppo_update_args_t a = *args;
+    ppoaf_ppo_update_args_t a = copy_update_args(args);
     for (int64_t j = 0; j < n_minibatches; ++j) {
         a.mb_offset = j;
         a.cursor_advance = (j == n_minibatches - 1) ? n_minibatches : 0;

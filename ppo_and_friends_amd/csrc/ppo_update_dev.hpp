@@ -2,7 +2,9 @@
 // persistent form; ppo_update_ws.hip: weight-stationary persistent form): the device view of the C-ABI
 // arguments and the distribution head + loss terms of one 16-row block.
 #pragma once
-#include "mlp_device.hpp"
+#include "action_heads.hpp"
+#include <cstddef>
+#include <cstring>
 
 namespace ppoaf {
 
@@ -38,6 +40,7 @@ struct UpdateDev {
     int confine;         // args->xcd_half: 0 every XCD; 1 / 2: fwd_bwd's workgroups on XCDs 0-3 / 4-7 only (actor on two of them, critic on two)
     int split;           // 1: split-wgrad chain -- fwd_bwd publishes activation / dz panels (sp) instead of weight-gradient slabs
     WsDev sp;
+    int n_slices; int slices[8];   // multi-categorical head: classes per action dimension (action_heads.hpp)
 };
 
 // offset of the output layer's segment (W_out, b_out, log_std) inside a network's bucket, and its length
@@ -157,6 +160,19 @@ __device__ __forceinline__ void ppo_update_bookkeeping_split(const UpdateDev& u)
 // host: validate ppoaf_ppo_update_args_t and fill the device view (ppo_update.hip)
 int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u);
 
+// host: a private copy of the caller's args.  The slice table appended to the struct is read only for the head kind that
+// has one, so a caller built against a header without it is never read past the end of its struct.
+inline ppoaf_ppo_update_args_t copy_update_args(const ppoaf_ppo_update_args_t* args) {
+    ppoaf_ppo_update_args_t a;
+    std::memset(&a, 0, sizeof(a));
+    std::memcpy(&a, args, offsetof(ppoaf_ppo_update_args_t, n_action_slices));
+    if (args->head_kind == PPOAF_HEAD_MULTI_CATEGORICAL) {
+        a.n_action_slices = args->n_action_slices;
+        std::memcpy(a.action_slices, args->action_slices, sizeof(a.action_slices));
+    }
+    return a;
+}
+
 __device__ __forceinline__ unsigned hw_xcc_id() {
     unsigned v;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
@@ -164,7 +180,8 @@ __device__ __forceinline__ unsigned hw_xcc_id() {
 }
 
 // K6 + K3 for the 16 rows of block g of network `which` (0 actor, 1 critic), run by ONE wave (lanes 0..15 hold a
-// row each; the categorical head uses 4 lanes per row): distribution head on the output-layer values sOut[16][16],
+// row each; the categorical head uses 4 lanes per row; the multi-categorical and Bernoulli heads take their log-prob
+// from the functions K6 uses, action_heads.hpp): distribution head on the output-layer values sOut[16][16],
 // PPO / value loss terms (ppo.py:2325-2438), d loss / d out -> sDOut[16][16] (and, Gaussian head, per-row
 // d / d log_std parked in sOut[.][8..]), the block's loss partials -> u.loss_partials, critic values written back.
 //   sRow16[16] dataset row of each block row (-1: dead), sRowF[3][16] adv / old log-prob / rewards-to-go,
@@ -247,6 +264,43 @@ __device__ __forceinline__ void ppo_head_loss(const U& u, const int which, const
             const float r_surr = __shfl(-fminf(surr1, surr2), src, 64), r_ent = __shfl(ent4, src, 64);
             const float r_kl = __shfl(lpo4 - logp4, src, 64), r_bad = __shfl(bad4, src, 64);
             if (live) { part[0] = r_surr; part[3] = r_ent; part[4] = r_kl; part[7] = r_bad; }
+        } else if (u.head_kind >= PPOAF_HEAD_MULTI_CATEGORICAL) {
+            // MultiDiscrete / MultiBinary (action_heads.hpp): one lane per row
+            if (live) {
+                float z[8], dz[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) z[k] = k < out_dim ? sOut[s * kMaxOut + k] : 0.f;
+                const bool mcat = u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL;
+                const float* x = sActF + s * 8;
+                float p[8], sm[8];
+                unsigned first = 0u, pick = 0u;
+                if (mcat) {
+                    first = mcat_starts(u.n_slices, u.slices);
+                    mcat_probs(z, first, out_dim, p, sm);
+                    pick = mcat_pick(reinterpret_cast<const int*>(x), u.n_slices, u.slices);
+                    logp = mcat_logp(p, sm, pick);
+                } else {
+                    logp = bern_logp(z, x, out_dim);
+                }
+                const float ratio = expf(logp - lpo);
+                if (isnan(ratio) || isinf(ratio)) part[7] = 1.f;
+                const float lo = 1.0f - u.surr_clip, hi = 1.0f + u.surr_clip;
+                const float surr1 = ratio * av, surr2 = fminf(fmaxf(ratio, lo), hi) * av;
+                float glp;
+                if (surr1 <= surr2) glp = -av * ratio;
+                else glp = (ratio >= lo && ratio <= hi) ? -av * ratio : 0.f;
+                glp *= inv_B;
+                const float gH = (u.entropy_weight != 0.0f) ? -u.entropy_weight * inv_B : 0.f;
+                ent = mcat ? mcat_entropy_grad(p, sm, first, pick, out_dim, glp, gH, dz)
+                           : bern_entropy_grad(z, x, out_dim, glp, gH, dz);
+                part[0] = -fminf(surr1, surr2);
+                part[3] = ent;
+                part[4] = lpo - logp;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) sDOut[s * kMaxOut + k] = dz[k];
+            } else if (s < kRows) {
+                for (int k = 0; k < kMaxOut; ++k) sDOut[s * kMaxOut + k] = 0.f;
+            }
         } else if (live) {
             // tanh-Gaussian (distributions.py:441-694)
             const float* log_std = log_std_p;

@@ -200,6 +200,10 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, cons
                 av = u.adv[di]; lpo = u.old_lp[di];
                 if (u.head_kind == PPOAF_HEAD_CATEGORICAL)
                     reinterpret_cast<int*>(sActF)[tid * 8] = (int)reinterpret_cast<const int64_t*>(u.raw_actions)[di];
+                else if (u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL)
+                    for (int j = 0; j < u.n_slices; ++j)
+                        reinterpret_cast<int*>(sActF)[tid * 8 + j] =
+                            (int)reinterpret_cast<const int64_t*>(u.raw_actions)[(long)di * u.n_slices + j];
                 else
                     for (int d = 0; d < out_dim; ++d)
                         sActF[tid * 8 + d] = reinterpret_cast<const float*>(u.raw_actions)[(long)di * out_dim + d];

@@ -172,7 +172,7 @@ using namespace ppoaf;
 
 extern "C" int ppoaf_ppo_update_split_workspace_bytes(const ppoaf_ppo_update_args_t* args, int64_t* bytes_out) {
     PPOAF_REQUIRE(args && bytes_out, "ppo_update_split_workspace_bytes: null argument");
-    ppoaf_ppo_update_args_t a = *args;
+    ppoaf_ppo_update_args_t a = copy_update_args(args);
     a.split_workspace = nullptr;
     UpdateDev u;
     int rc = make_update_dev(&a, u);
@@ -188,7 +188,7 @@ extern "C" int ppoaf_ppo_update_split_workspace_bytes(const ppoaf_ppo_update_arg
 
 extern "C" int ppoaf_ppo_update_row_pairs_error_offset(const ppoaf_ppo_update_args_t* args, int64_t* offset_out) {
     PPOAF_REQUIRE(args && offset_out, "ppo_update_row_pairs_error_offset: null argument");
-    ppoaf_ppo_update_args_t a = *args;
+    ppoaf_ppo_update_args_t a = copy_update_args(args);
     a.split_workspace = nullptr;
     UpdateDev u;
     int rc = make_update_dev(&a, u);
@@ -204,7 +204,7 @@ extern "C" int ppoaf_ppo_update_split_blocks(const ppoaf_ppo_update_args_t* args
     UpdateDev u;
     ppoaf_ppo_update_args_t a;
     if (!args) return -1;
-    a = *args;
+    a = copy_update_args(args);
     a.split_workspace = nullptr;
     if (make_update_dev(&a, u)) return -1;
     return split_wgrad_blocks(u);

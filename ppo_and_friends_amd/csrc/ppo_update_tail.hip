@@ -525,7 +525,7 @@ using namespace ppoaf;
 extern "C" int ppoaf_ppo_update_tail_ctl_bytes(const ppoaf_ppo_update_args_t* args, int64_t* bytes_out) {
     UpdateDev u;
     PPOAF_REQUIRE(args && bytes_out, "ppo_update_tail_ctl_bytes: null argument");
-    ppoaf_ppo_update_args_t a = *args;
+    ppoaf_ppo_update_args_t a = copy_update_args(args);
     a.split_workspace = nullptr;
     const int rc = make_update_dev(&a, u);
     if (rc) return rc;
@@ -536,7 +536,7 @@ extern "C" int ppoaf_ppo_update_tail_ctl_bytes(const ppoaf_ppo_update_args_t* ar
 extern "C" int ppoaf_ppo_update_tail_exchange_floats(const ppoaf_ppo_update_args_t* args, int64_t* floats_out) {
     UpdateDev u;
     PPOAF_REQUIRE(args && floats_out, "ppo_update_tail_exchange_floats: null argument");
-    ppoaf_ppo_update_args_t a = *args;
+    ppoaf_ppo_update_args_t a = copy_update_args(args);
     a.split_workspace = nullptr;
     const int rc = make_update_dev(&a, u);
     if (rc) return rc;

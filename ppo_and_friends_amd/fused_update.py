@@ -20,7 +20,8 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
-from .networks.distributions import CategoricalDistribution, GaussianDistribution
+from .networks.distributions import (BernoulliDistribution, CategoricalDistribution, GaussianDistribution,
+                                     MultiCategoricalDistribution)
 from .networks.feed_forward import FeedForwardNetwork
 from .utils import mpi_utils, peer_exchange
 
@@ -33,6 +34,40 @@ def _activation_code(act):
     if isinstance(act, nn.Tanh):
         return K.ACT_TANH
     return None
+
+
+def action_head(pol):
+    """
+    (head kind, slice table, '') of the policy's action distribution on K6 / K12, or (None, None, why not).  The
+    MultiDiscrete and MultiBinary heads (csrc/action_heads.hpp) are taken only for a policy built with
+    update_mode="fused" (PPO sets pol.fused_action_heads); "auto" keeps the torch-ROCm path for them.
+    """
+    dist = pol.actor.distribution
+    if isinstance(dist, CategoricalDistribution):
+        return K.HEAD_CATEGORICAL, (), ""
+    if isinstance(dist, GaussianDistribution):
+        return K.HEAD_GAUSSIAN, (), ""
+    if not isinstance(dist, (MultiCategoricalDistribution, BernoulliDistribution)):
+        return None, None, "unknown action distribution"
+    if not getattr(pol, "fused_action_heads", False):
+        return None, None, "MultiDiscrete / MultiBinary heads run on the fused kernels under update_mode='fused' only"
+    if isinstance(dist, BernoulliDistribution):
+        n = int(pol.action_pred_size)
+        if not 1 <= n <= 8:
+            return None, None, f"MultiBinary({n}): the fused Bernoulli head covers 1 .. 8 bits"
+        return K.HEAD_BERNOULLI, (), ""
+    nvec = tuple(int(k) for k in dist.nvec)
+    if not (1 <= len(nvec) <= 8 and min(nvec) >= 1 and sum(nvec) <= 8):
+        return None, None, (f"MultiDiscrete({list(nvec)}): the fused multi-categorical head covers 1 .. 8 slices of at "
+                            "least one class each, 8 classes in all")
+    return K.HEAD_MULTI_CATEGORICAL, nvec, ""
+
+
+def set_action_slices(args, slices):
+    """The multi-categorical head's slice table into K6's / K12's args (empty for the other heads)."""
+    args.n_action_slices = len(slices)
+    for j in range(8):
+        args.action_slices[j] = slices[j] if j < len(slices) else 0
 
 
 def _describe(net, bucket, with_log_std):
@@ -498,13 +533,9 @@ class FusedPolicyUpdate(FusedEpoch):
         """'' when the fused kernels cover this policy, else why not (the torch path is used then)."""
         if pol.using_lstm or pol.agent_grouping:
             return "LSTM / grouped (MAT) policies are not covered by the fused MLP update"
-        dist = pol.actor.distribution
-        if isinstance(dist, CategoricalDistribution):
-            head = K.HEAD_CATEGORICAL
-        elif isinstance(dist, GaussianDistribution):
-            head = K.HEAD_GAUSSIAN
-        else:
-            return "unknown action distribution"
+        head, _, why = action_head(pol)
+        if head is None:
+            return why
         a, why = _describe(pol.actor, pol.policy_params, head == K.HEAD_GAUSSIAN)
         if a is None:
             return "actor: " + why
@@ -525,8 +556,7 @@ class FusedPolicyUpdate(FusedEpoch):
         super().__init__(ppo, policy_id)
         pol = self.pol
         dev = pol.device
-        self.head = K.HEAD_GAUSSIAN if isinstance(pol.actor.distribution, GaussianDistribution) \
-            else K.HEAD_CATEGORICAL
+        self.head, self.action_slices, _ = action_head(pol)
         self.actor_desc, _ = _describe(pol.actor, pol.policy_params, self.head == K.HEAD_GAUSSIAN)
         self.critic_desc, _ = _describe(pol.critic, pol.policy_params, False)
         self.n_wg = (self.B + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
@@ -671,6 +701,7 @@ class FusedPolicyUpdate(FusedEpoch):
         a.grad_scale = 1.0 / self.world
         a.max_norm = float(pol.gradient_clip) if pol.gradient_clip is not None else 0.0
         a.head_kind = self.head
+        set_action_slices(a, self.action_slices)
         a.obs = self.tables["obs"].data_ptr()
         a.perm = self.rows.data_ptr(); a.row_map = None      # rows = row_map[perm], resolved once per epoch
         a.min_std = float(getattr(pol.actor.distribution, "min_std", 0.01))

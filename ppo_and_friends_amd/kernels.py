@@ -383,7 +383,7 @@ def clip_adam_step(params, grads, exp_avg, exp_avg_sq, step_count, lr, norm_scra
 # K12: fused mini-batch update
 # --------------------------------------------------------------------------
 ACT_RELU, ACT_LEAKY_RELU, ACT_TANH = 0, 1, 2
-HEAD_CATEGORICAL, HEAD_GAUSSIAN = 0, 1
+HEAD_CATEGORICAL, HEAD_GAUSSIAN, HEAD_MULTI_CATEGORICAL, HEAD_BERNOULLI = 0, 1, 2, 3
 UPDATE_ROWS_PER_WG = 16
 
 

@@ -133,6 +133,7 @@ class PPOPolicy:
         self.verbose = verbose
         self.use_huber_loss = use_huber_loss
         self.frozen = False
+        self.fused_action_heads = False      # MultiDiscrete / MultiBinary heads on K6 / K12 (set by PPO(update_mode="fused"))
         self.random_seed = random_seed
         self.lr = _callable(lr)
         self.icm_lr = _callable(icm_lr)
@@ -354,8 +355,9 @@ class PPOPolicy:
 
     def rollout_step(self, t, obs, critic_obs, value_normalizer=None, forced_raw_action=None):
         """
-        forced_raw_action (optional, [E] / [E,1] int64 or [E,D] float32 device tensor): log these raw actions
-        instead of sampling -- replay of a recorded rollout (log-probs, refined actions and values are computed
+        forced_raw_action (optional contiguous device tensor shaped like the step's raw actions: [E] / [E,1] int64
+        (Discrete), [E,D] int64 (MultiDiscrete, one class per slice), [E,D] float32 (Box) or [E,n] float32 of 0 / 1
+        (MultiBinary)): log these raw actions instead of sampling -- replay of a recorded rollout (log-probs, refined actions and values are computed
         as usual).
         One env step of get_rollout_actions + get_critic_values (+ denormalisation) +
         add_episode_info's action/value/log-prob/observation writes, as ONE launch that
@@ -364,19 +366,20 @@ class PPOPolicy:
         `finish_step` once the environment has answered.
         """
         from .. import _lib
-        from ..fused_update import _describe
-        from ..networks.distributions import GaussianDistribution
+        from ..fused_update import _describe, action_head, set_action_slices
         buf = self.buffer
         E = buf.C                       # agents x envs rows, agent-major
         a = getattr(self, "_step_args", None)
         if a is None:
             a = _lib.PolicyStepArgs()
-            gauss = isinstance(self.actor.distribution, GaussianDistribution)
+            head, slices, _ = action_head(self)
+            gauss = head == K.HEAD_GAUSSIAN
             a.actor, _ = _describe(self.actor, self.policy_params, gauss)
             a.critic, _ = _describe(self.critic, self.policy_params, False)
             a.params = self.policy_params.data_ptr()
             a.E = E
-            a.head_kind = K.HEAD_GAUSSIAN if gauss else K.HEAD_CATEGORICAL
+            a.head_kind = head
+            set_action_slices(a, slices)
             a.min_std = float(getattr(self.actor.distribution, "min_std", 0.01))
             lo, hi = self.actor.distribution.bound_tensors() if gauss else (None, None)
             a.act_lo = None if lo is None else lo.data_ptr()
@@ -390,12 +393,15 @@ class PPOPolicy:
         a.obs = obs.data_ptr(); a.critic_obs = critic_obs.data_ptr()
         a.forced_raw_action = None
         if forced_raw_action is not None:
-            want = torch.float32 if a.head_kind == K.HEAD_GAUSSIAN else torch.int64
+            want = torch.float32 if a.head_kind in (K.HEAD_GAUSSIAN, K.HEAD_BERNOULLI) else torch.int64
             K._req(forced_raw_action.is_cuda and forced_raw_action.dtype == want and forced_raw_action.is_contiguous()
                    and forced_raw_action.numel() == buf.raw_actions[t].numel(),
                    "rollout_step: forced_raw_action must be a contiguous device tensor shaped like the step's raw actions")
             a.forced_raw_action = forced_raw_action.data_ptr()
-        a.seed, a.offset = self.actor.distribution.rng.take(E)
+        # Philox counters as the torch path takes them: one per row, one per (slice, row) for MultiDiscrete (slice j of
+        # row e draws offset + j * E + e), one per (row, bit) for MultiBinary
+        per_row = {K.HEAD_MULTI_CATEGORICAL: a.n_action_slices, K.HEAD_BERNOULLI: a.actor.out_dim}.get(a.head_kind, 1)
+        a.seed, a.offset = self.actor.distribution.rng.take(E * per_row)
         if value_normalizer is not None:
             a.normalize_values = 1
             a.vn_mean = value_normalizer.running_stats.mean_t.data_ptr()

@@ -253,6 +253,8 @@ class PPO:
         for policy_id, pol in self.policies.items():
             pol.finalize(self.status_dict, self.device)
             pol.fused_icm_reward = update_mode != "torch"       # K14's kernels for the rollout-time intrinsic reward
+            # the MultiDiscrete / MultiBinary heads of K6 / K12 (csrc/action_heads.hpp); "auto" keeps them on torch-ROCm for now
+            pol.fused_action_heads = update_mode == "fused"
             if update_mode == "fused" and pol.using_lstm and self.device.type == "cuda":
                 # K18 for both recurrent networks, in the rollout and in the update ("auto" keeps nn.LSTM for now)
                 from .fused_update import FusedLstm

@@ -1,0 +1,305 @@
+"""
+-m gpu: the MultiDiscrete and MultiBinary heads on the fused kernels (csrc/action_heads.hpp) -- the K6+K7 rollout step and
+every form of the K12 update under PPO(update_mode="fused") -- against the torch-ROCm path of the same policy
+(networks/distributions.py: MultiCategoricalDistribution, BernoulliDistribution), which fixture g16 pins to the reference.
+
+MultiDiscrete rollouts draw the torch path's Philox counters, so both modes log the same actions; the torch path samples
+MultiBinary actions with torch.rand, so the fused side replays them (PPO.replay_raw_actions).
+"""
+import os
+import socket
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+K12_FORMS = {"chain": {}, "three_launches": {"PPOAF_FUSED_TAIL": "0"}, "slabs": {"PPOAF_SPLIT_WGRAD": "0"}}
+ACTS = {"relu": nn.ReLU, "leaky": nn.LeakyReLU, "tanh": nn.Tanh}
+
+
+def _make(head, mode, E=14, T=20, B=64, epochs=1, O=6, hidden=64, depth=2, act_fn=nn.ReLU, huber=False, term=0.0,
+          use_graphs=False, critic_hidden=None, agents=1, prepare=None):
+    from ppo_and_friends_amd.ppo import PPO
+    from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
+    from ppo_and_friends_amd.spaces import Box, MultiBinary, MultiDiscrete
+    dev = torch.device("cuda", 0)
+    space = MultiDiscrete(head[1]) if head[0] == "md" else MultiBinary(head[1])
+    view = "policy" if agents > 1 else "local"
+    env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, dev, reward="uniform", seed=77, term_prob=term,
+                                              num_agents=agents, critic_view=view)
+    sp, csp = Box(-np.inf, np.inf, (O,), np.float32), Box(-np.inf, np.inf, (O * agents,), np.float32)
+    kw = dict(hidden_size=hidden, hidden_depth=depth, activation=act_fn())
+    pargs = dict(actor_kw_args=kw, critic_kw_args=dict(kw, hidden_size=critic_hidden or hidden), use_huber_loss=huber)
+    ppo = PPO(env_gen, {"p": (None, sp, csp, space, pargs)}, device=dev, random_seed=3, normalize_obs=False,
+              normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=B, epochs_per_iter=epochs,
+              use_graphs=use_graphs, update_mode=mode, save_state=False)
+    if prepare is not None:
+        prepare(ppo)
+    return ppo
+
+
+def _state(ppo):
+    pol = ppo.policies["p"]
+    vs = ppo.value_normalizers["p"].running_stats
+    return (pol.policy_params.detach().cpu().numpy().copy(), dict(ppo.status_dict["p"]),
+            np.array([vs.mean, vs.variance, vs.count], dtype=np.float64), pol.buffer.values.detach().cpu().numpy().copy())
+
+
+def _train_pair(head, B, epochs=1, check=None, **kw):
+    """The same rollout and shuffles through the torch-ROCm update and the fused one -> (fused state, torch state).
+    MultiBinary: the fused PPO replays the torch rollout's raw actions."""
+    from ppo_and_friends_amd.ppo import PermutationLoader
+    out, rec = {}, None
+    for mode in ("auto", "fused"):
+        ppo = _make(head, mode, B=B, epochs=epochs, **kw)
+        upd = ppo._fused_updater("p", B)
+        assert (upd is None) == (mode == "auto")
+        if mode == "fused" and rec is not None:
+            ppo.replay_raw_actions = rec
+        ppo.rollout()
+        pol = ppo.policies["p"]
+        if mode == "auto" and head[0] == "mb":
+            rec = pol.buffer.raw_actions.clone()
+        loader = PermutationLoader(pol.dataset, B, ppo.loader_generator)
+        pol.train()
+        for _ in range(epochs):
+            ppo._ppo_batch_train(loader, "p")
+        if upd is not None and check is not None:
+            check(upd)
+        out[mode] = _state(ppo)
+    return out["fused"], out["auto"]
+
+
+def _assert_close(f, t, loss_tol=(2e-5, 2e-6), w_tol=(1e-4, 2e-5)):
+    (w0, s0, v0, val0), (w1, s1, v1, val1) = f, t
+    for k in ("actor loss", "critic loss", "kl avg", "weighted entropy"):
+        np.testing.assert_allclose(s0[k], s1[k], rtol=loss_tol[0], atol=loss_tol[1], err_msg=k)
+    np.testing.assert_allclose(w0, w1, rtol=w_tol[0], atol=w_tol[1])
+    np.testing.assert_allclose(v0, v1, rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(val0, val1, rtol=w_tol[0], atol=w_tol[1])
+
+
+@pytest.mark.parametrize("head,hidden", [(("md", [3, 4]), 32), (("md", [2, 2, 2, 2]), 128), (("md", [8]), 256),
+                                         (("md", [1, 3]), 128), (("mb", 1), 32), (("mb", 4), 128), (("mb", 8), 256)])
+def test_fused_rollout_step_equals_torch_rollout(head, hidden):
+    """K6+K7 against the torch-ROCm rollout: MultiDiscrete -- the same Philox counters, hence the same actions;
+    MultiBinary -- the torch rollout's actions replayed through the fused step.  Log-probs and values within K6's
+    tolerances (test_fused_rollout_step_equals_torch_rollout)."""
+    bufs, rec = {}, None
+    for mode in ("auto", "fused"):
+        ppo = _make(head, mode, E=20, T=12, hidden=hidden, depth=1 if hidden == 32 else 3)
+        pol = ppo.policies["p"]
+        assert (pol.fused_step_unsupported_reason() == "") == (mode == "fused")
+        if rec is not None:
+            ppo.replay_raw_actions = rec
+        ppo.rollout()
+        if head[0] == "mb":
+            rec = pol.buffer.raw_actions.clone()
+        bufs[mode] = {k: getattr(pol.buffer, k).detach().cpu().numpy().copy()
+                      for k in ("observations", "actions", "raw_actions", "values", "log_probs")}
+    f, t = bufs["fused"], bufs["auto"]
+    np.testing.assert_array_equal(f["observations"], t["observations"])
+    np.testing.assert_array_equal(f["raw_actions"], t["raw_actions"])
+    np.testing.assert_array_equal(f["actions"], t["actions"])
+    np.testing.assert_allclose(f["log_probs"], t["log_probs"], rtol=1e-5, atol=2e-5)
+    np.testing.assert_allclose(f["values"], t["values"], rtol=1e-5, atol=1e-5)
+
+
+UPDATE_CASES = {
+    "md_256_pairs": dict(head=("md", [3, 3, 2]), hidden=256, depth=3, B=100, use_graphs=True),
+    "md_32": dict(head=("md", [2, 5]), hidden=32, depth=1, B=48, act_fn=nn.Tanh, huber=True),
+    "mb_128": dict(head=("mb", 7), hidden=128, depth=2, B=90, act_fn=nn.LeakyReLU, use_graphs=True),
+    "mb_256_pairs": dict(head=("mb", 4), hidden=256, depth=2, B=64),
+}
+
+
+@pytest.mark.parametrize("case", sorted(UPDATE_CASES))
+@pytest.mark.parametrize("k12_form", sorted(K12_FORMS))
+def test_fused_update_equals_torch_update(case, k12_form, monkeypatch):
+    """Every K12 form -- split-wgrad chain with the fused tail (256-wide networks on row pairs), the same with separate
+    wgrad and Adam launches, the slab chain -- with graphs on and off, widths 32 .. 256, depths 1 .. 3, ragged last
+    workgroups and tail mini-batches (N = 280): two epochs against the torch-ROCm update on the same rollout."""
+    for k, v in K12_FORMS[k12_form].items():
+        monkeypatch.setenv(k, v)
+    c = dict(UPDATE_CASES[case])
+    head, B = c.pop("head"), c.pop("B")
+
+    def check(upd):
+        if k12_form == "slabs":
+            assert not upd.split
+        else:
+            # (a 256-wide depth-3 pair has more weight-gradient jobs than the fused tail holds: wgrad + Adam there)
+            fits = upd._split_blocks() <= 512
+            assert upd.split and (upd.tail_reason() == "") == (k12_form == "chain" and fits)
+            if c["hidden"] == 256:
+                assert upd.pairs_reason() == "" and type(upd).pair_launches > pairs_before
+
+    from ppo_and_friends_amd.fused_update import FusedPolicyUpdate
+    pairs_before = FusedPolicyUpdate.pair_launches
+    f, t = _train_pair(head, B, epochs=2, check=check, **c)
+    _assert_close(f, t)
+
+
+def test_fused_heads_fuzz_against_the_torch_path():
+    """Randomised shapes (hypothesis, derandomised): nvec with sum <= 8 or 1-8 bits, observation widths 1-70, every
+    equal-width pair, depth 1-3, batch sizes with ragged workgroups and tails, activations, Huber loss, terminations."""
+    from hypothesis import HealthCheck, given, settings, strategies as st
+
+    @settings(max_examples=14, deadline=None, derandomize=True, suppress_health_check=list(HealthCheck))
+    @given(kind=st.sampled_from(["md", "mb"]), raw=st.lists(st.integers(1, 8), min_size=1, max_size=8),
+           bits=st.integers(1, 8), O=st.integers(1, 70), hidden=st.sampled_from([32, 64, 128, 256]),
+           depth=st.integers(1, 3), B=st.integers(2, 300), E=st.integers(1, 12), T=st.integers(2, 24),
+           act=st.sampled_from(sorted(ACTS)), huber=st.booleans(), term=st.sampled_from([0.0, 0.1]))
+    def run(kind, raw, bits, O, hidden, depth, B, E, T, act, huber, term):
+        nvec = []
+        for k in raw:
+            if sum(nvec) + k <= 8:
+                nvec.append(k)
+        head = ("md", nvec) if kind == "md" else ("mb", bits)
+        f, t = _train_pair(head, B, O=O, hidden=hidden, depth=depth, E=E, T=T, act_fn=ACTS[act], huber=huber, term=term)
+        _assert_close(f, t, loss_tol=(5e-5, 5e-6), w_tol=(2e-4, 3e-5))
+
+    run()
+
+
+@pytest.mark.parametrize("head", [("md", [2, 3, 3]), ("mb", 4)])
+def test_saturated_logits_agree(head):
+    """The actor's output layer is set so that every logit of the first mini-batch sits at +-16 or +-20: the probability
+    clamps and their inclusive bounds (sigmoid(16) rounds to exactly 1 - eps, where the gradient still passes) on both
+    paths."""
+    def saturate(ppo):
+        out = [m for m in ppo.policies["p"].actor.sequential_net.modules() if isinstance(m, nn.Linear)][-1]
+        with torch.no_grad():
+            out.weight.zero_()
+            out.bias.copy_(torch.tensor([(16.0, -16.0, 20.0, -20.0)[k % 4] for k in range(out.bias.numel())]))
+
+    f, t = _train_pair(head, 64, hidden=128, depth=2, prepare=saturate)
+    _assert_close(f, t)
+
+
+@pytest.mark.parametrize("head", [("md", [3, 3, 2]), ("mb", 5)])
+def test_first_minibatch_kl_is_exactly_zero(head):
+    """One mini-batch of all rows, one epoch, default form: K12 recomputes every row's log-prob bit for bit as K6 logged
+    it, so every ratio is exactly 1 and "kl avg" is exactly 0."""
+    from ppo_and_friends_amd.ppo import PermutationLoader
+    E, T = 16, 16
+    ppo = _make(head, "fused", E=E, T=T, B=E * T, hidden=128, depth=3)
+    upd = ppo._fused_updater("p", E * T)
+    assert upd is not None and upd.split and upd.tail_reason() == ""
+    ppo.rollout()
+    pol = ppo.policies["p"]
+    pol.train()
+    ppo._ppo_batch_train(PermutationLoader(pol.dataset, E * T, ppo.loader_generator), "p")
+    assert ppo.status_dict["p"]["kl avg"] == 0.0
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def test_multi_rank_rehearsal_matches_single_rank(tmp_path):
+    """One rank through the N > 1 path (PPOAF_REHEARSE_MULTI_RANK=1: process group, per-mini-batch gradient exchange,
+    record all-gathers) in a child process, against the single-rank path in another."""
+    outs = {}
+    for tag, rehearse in (("single", "0"), ("rehearsal", "1")):
+        env = dict(os.environ, PPOAF_REHEARSE_MULTI_RANK=rehearse, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
+                   HSA_ENABLE_IPC_MODE_LEGACY="0")
+        for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "PPOAF_BACKEND"):
+            env.pop(k, None)
+        out = str(tmp_path / f"{tag}.npz")
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "helpers", "action_heads_rank_run.py"), out],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        outs[tag] = np.load(out)
+    s, r = outs["single"], outs["rehearsal"]
+    assert bool(r["multi"]) and not bool(s["multi"])
+    np.testing.assert_allclose(r["stats"], s["stats"], rtol=2e-5, atol=2e-6)
+    np.testing.assert_allclose(r["params"], s["params"], rtol=1e-4, atol=2e-5)
+
+
+def test_agent_shared_policy_three_agents():
+    """C4's shape with a MultiDiscrete head: 3 agents share one policy (actor 128^3, critic 256^3 on the agents'
+    concatenated observations), agent-major rows through K6 and K12 against the torch-ROCm path."""
+    f, t = _train_pair(("md", [3, 2]), 48, epochs=2, E=6, T=10, O=18, hidden=128, depth=3, critic_hidden=256, agents=3,
+                       term=0.05)
+    _assert_close(f, t)
+
+
+@pytest.mark.parametrize("tag", ["md34", "md2222", "md13", "mb1", "mb4", "mb8"])
+def test_torch_heads_match_reference_golden_g16(golden, tag):
+    """The product's MultiCategoricalDistribution / BernoulliDistribution (the spec the fused heads are held to) against
+    the unmodified reference's classes: log-probs, entropies, both gradients, refined predictions."""
+    from ppo_and_friends_amd.networks.distributions import BernoulliDistribution, MultiCategoricalDistribution
+    g = golden("g16_action_heads")
+    dev = torch.device("cuda", 0)
+    logits = torch.tensor(g[f"{tag}_logits"], device=dev).requires_grad_(True)
+    actions = torch.tensor(g[f"{tag}_actions"], device=dev)
+    d = MultiCategoricalDistribution(g[f"{tag}_nvec"].tolist()) if tag.startswith("md") else BernoulliDistribution()
+    lp, ent = d.get_log_probs_and_entropy(logits, actions)
+    glp, = torch.autograd.grad(lp.sum(), logits, retain_graph=True)
+    gent, = torch.autograd.grad(ent.sum(), logits)
+    np.testing.assert_allclose(lp.detach().cpu().numpy().reshape(-1), g[f"{tag}_log_probs"], rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(ent.detach().cpu().numpy(), g[f"{tag}_entropy"], rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(glp.cpu().numpy(), g[f"{tag}_dlogp_dlogits"], rtol=1e-4, atol=1e-6)
+    np.testing.assert_allclose(gent.cpu().numpy(), g[f"{tag}_dent_dlogits"], rtol=1e-4, atol=1e-6)
+    np.testing.assert_array_equal(d.refine_prediction(logits.detach()).cpu().numpy(), g[f"{tag}_refined"])
+
+
+def _philox4x32_10(seed, counters, stream):
+    """Philox4x32-10 as csrc/common.hpp forms it, for an array of 64-bit counters -> its four 32-bit words."""
+    M = np.uint64(0xFFFFFFFF)
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
+    counters = np.asarray(counters, dtype=np.uint64)
+    c0, c1 = counters & M, counters >> np.uint64(32)
+    c2, c3 = np.full_like(counters, stream), np.zeros_like(counters)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
+    return c0, c1, c2, c3
+
+
+def test_fused_bernoulli_sampler_draws_its_bits():
+    """A fused MultiBinary rollout that samples on its own (no replay).  The actor's output layer is set so that every
+    row's logits are the bias: bits at +-20 come out exactly 1 / 0; each other bit's frequency over E*T draws lies within
+    5 sigma of sigmoid(z); every bit is u < sigmoid(z_d) with u from Philox (seed, offset + e, d / 4) word d % 4, the
+    step taking E * n counters; the logged log-probs are torch's Bernoulli log-probs of the drawn bits."""
+    n, E, T = 8, 64, 32
+    bias = torch.tensor([20.0, -20.0, 0.5, -1.0, 2.0, 0.0, -0.3, 1.5])
+
+    def set_logits(ppo):
+        out = [m for m in ppo.policies["p"].actor.sequential_net.modules() if isinstance(m, nn.Linear)][-1]
+        with torch.no_grad():
+            out.weight.zero_()
+            out.bias.copy_(bias)
+
+    ppo = _make(("mb", n), "fused", E=E, T=T, B=256, prepare=set_logits)
+    pol = ppo.policies["p"]
+    assert pol.fused_step_unsupported_reason() == ""
+    rng = pol.actor.distribution.rng
+    seed, off0 = rng.seed, rng.offset
+    ppo.rollout()
+    assert rng.offset == off0 + T * E * n
+    raw = pol.buffer.raw_actions.detach().cpu().numpy().reshape(T, E, n)
+    np.testing.assert_array_equal(pol.buffer.actions.detach().cpu().numpy().reshape(T, E, n), raw)
+    assert set(np.unique(raw).tolist()) <= {0.0, 1.0}
+    assert (raw[..., 0] == 1.0).all() and (raw[..., 1] == 0.0).all()
+    p = 1.0 / (1.0 + np.exp(-bias.double().numpy()))
+    freq, sigma = raw.reshape(-1, n).mean(0), np.sqrt(p * (1.0 - p) / (E * T))
+    assert (np.abs(freq - p)[2:] <= 5.0 * sigma[2:]).all(), (freq, p)
+    counters = off0 + np.arange(T)[:, None] * (E * n) + np.arange(E)[None, :]
+    p32 = torch.sigmoid(bias).numpy()
+    for d in range(n):
+        u = (_philox4x32_10(seed, counters, d >> 2)[d & 3] >> np.uint64(8)).astype(np.float64) / 16777216.0
+        clear = np.abs(u - p32[d]) > 1e-6                  # (draws on the rounding edge of sigmoid are not compared)
+        np.testing.assert_array_equal(raw[..., d][clear], (u < p32[d])[clear].astype(np.float32), err_msg=f"bit {d}")
+    want = torch.distributions.Bernoulli(probs=torch.sigmoid(bias)).log_prob(torch.from_numpy(raw)).sum(-1)
+    np.testing.assert_allclose(pol.buffer.log_probs.detach().cpu().numpy().reshape(T, E), want.numpy(), rtol=1e-5, atol=1e-5)
