@@ -420,6 +420,11 @@ int ppoaf_ppo_update_fwd_bwd(const ppoaf_ppo_update_args_t* args, ppoaf_stream_t
 /* same launch with the kernel's own begin / end stamped into two events (as ppoaf_gae_rtg_tmajor_timed) */
 int ppoaf_ppo_update_fwd_bwd_timed(const ppoaf_ppo_update_args_t* args, void* start_event, void* stop_event,
                                    ppoaf_stream_t stream);
+/* Host-only query (added within ABI 7: no field or call changed), nothing is launched and no pointer of args is read:
+ * PPOAF_OK when fwd_bwd accepts these shapes (layer tables, bucket, head, batch size, the row-tile body's LDS, the
+ * instantiated width pairs), else PPOAF_E_INVALID with the launch's own message in ppoaf_last_error().  The host
+ * driver's scope test (fused_update.py: FusedPolicyUpdate.unsupported_reason) asks it. */
+int ppoaf_ppo_update_check(const ppoaf_ppo_update_args_t* args);
 int ppoaf_ppo_update_reduce(const ppoaf_ppo_update_args_t* args, int compute_norms, ppoaf_stream_t stream);
 /* Split-wgrad chain: fwd_bwd (args->split_workspace set) -> ppoaf_ppo_update_wgrad -> ppoaf_ppo_update_adam(compute_norms 3).
  * The weight gradients of ppo.py:2443 (loss.backward()) are formed ONCE per mini-batch over all B rows -- one workgroup

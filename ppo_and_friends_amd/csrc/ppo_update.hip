@@ -303,7 +303,8 @@ int fill_net(const ppoaf_mlp_desc_t& d, NetDev& n, const char* what) {
     return PPOAF_OK;
 }
 
-int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
+// the shape checks of make_update_dev: the layer tables, the bucket, the head, the batch size (no pointer is read)
+static int update_shapes(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
     PPOAF_REQUIRE(a, "ppo_update: null args");
     int rc = fill_net(a->actor, u.net[0], "actor");
     if (rc) return rc;
@@ -318,6 +319,12 @@ int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
     if (rc) return rc;
     PPOAF_REQUIRE(a->B >= 2 && a->batch_stride >= a->B, "ppo_update: B=%ld stride=%ld", (long)a->B,
                   (long)a->batch_stride);
+    return PPOAF_OK;
+}
+
+int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
+    int rc = update_shapes(a, u);
+    if (rc) return rc;
     PPOAF_REQUIRE(a->params && a->grads && a->exp_avg && a->exp_avg_sq && a->slabs && a->step_counts &&
                       a->lr && a->norm_scratch && a->obs && a->critic_obs && a->raw_actions &&
                       a->advantages && a->old_log_probs && a->rewards_to_go && a->values && a->perm &&
@@ -370,6 +377,17 @@ int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
 static size_t fwd_bwd_lds_bytes(const UpdateDev& u) {
     const size_t a = rowtile_lds_floats(u.net[0]), c = rowtile_lds_floats(u.net[1]);
     return ((a > c ? a : c) * 4 + 15) / 16 * 16 + kRowtileLineFloats * 4;
+}
+
+// what fwd_bwd refuses beyond make_update_dev: the row-tile body's LDS and the instantiated width pairs
+static int fwd_bwd_fits(const UpdateDev& u) {
+    const size_t lds = fwd_bwd_lds_bytes(u);
+    PPOAF_REQUIRE(lds <= 160 * 1024, "ppo_update_fwd_bwd: needs %zu B of LDS (> 160 KiB)", lds);
+    const int ha = u.net[0].H, hc = u.net[1].H;
+    PPOAF_REQUIRE((ha == 32 && hc == 32) || (ha == 64 && hc == 64) || (ha == 128 && hc == 128) || (ha == 256 && hc == 256) ||
+                      (ha == 128 && hc == 256) || (ha == 64 && hc == 128),
+                  "ppo_update_fwd_bwd: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
+    return PPOAF_OK;
 }
 
 template <int HTA, int HTC, bool SPLIT>
@@ -427,9 +445,9 @@ extern "C" int ppoaf_ppo_update_fwd_bwd_timed(const ppoaf_ppo_update_args_t* arg
     hipEvent_t e0 = (hipEvent_t)start_event, e1 = (hipEvent_t)stop_event;
     UpdateDev u;
     int rc = make_update_dev(args, u);
+    if (rc == PPOAF_OK) rc = fwd_bwd_fits(u);
     if (rc) return rc;
     const size_t lds = fwd_bwd_lds_bytes(u);
-    PPOAF_REQUIRE(lds <= 160 * 1024, "ppo_update_fwd_bwd: needs %zu B of LDS (> 160 KiB)", lds);
     hipStream_t s = (hipStream_t)stream;
     // instantiated (actor width, critic width) pairs; the host falls back to the torch path otherwise
     const int ha = u.net[0].H, hc = u.net[1].H;
@@ -449,6 +467,13 @@ extern "C" int ppoaf_ppo_update_fwd_bwd_timed(const ppoaf_ppo_update_args_t* arg
     if (ha == 64 && hc == 128) return launch_fwd_bwd<4, 8>(u, lds, s, e0, e1);
     set_error("ppo_update_fwd_bwd: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_E_INVALID;
+}
+
+extern "C" int ppoaf_ppo_update_check(const ppoaf_ppo_update_args_t* args) {
+    UpdateDev u;
+    int rc = update_shapes(args, u);
+    if (rc == PPOAF_OK) rc = fwd_bwd_fits(u);
+    return rc;
 }
 
 extern "C" int ppoaf_ppo_update_reduce(const ppoaf_ppo_update_args_t* args, int compute_norms,

@@ -550,6 +550,13 @@ class FusedPolicyUpdate(FusedEpoch):
             return f"hidden widths (actor {a.hidden}, critic {c.hidden}) are not an instantiated pair"
         if batch_size < 2:
             return "batch size < 2"
+        # what the library itself refuses (depth, in_dim, the row-tile body's LDS): host-only, nothing is launched
+        q = _lib.PpoUpdateArgs()
+        q.actor, q.critic, q.bucket_total = a, c, a.size + c.size
+        q.head_kind, q.B, q.batch_stride = head, batch_size, batch_size
+        set_action_slices(q, action_head(pol)[1])
+        if _lib.load().ppoaf_ppo_update_check(C.byref(q)) != 0:
+            return _lib.load().ppoaf_last_error().decode("utf-8", "replace")
         return ""
 
     def __init__(self, ppo, policy_id):

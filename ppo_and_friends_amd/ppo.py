@@ -262,6 +262,12 @@ class PPO:
                 if why:
                     raise NotImplementedError(f"update_mode='fused' but policy {policy_id}: {why}")
                 pol.actor.use_hip = pol.critic.use_hip = True
+            elif update_mode == "fused" and not pol.agent_grouping and self.device.type == "cuda":
+                # K12's scope is known before the first rollout: refuse here, not in the middle of the first epoch
+                from .fused_update import FusedPolicyUpdate
+                why = FusedPolicyUpdate.unsupported_reason(pol, self.batch_size)
+                if why:
+                    raise NotImplementedError(f"update_mode='fused' but policy {policy_id}: {why}")
         # ppo.py:663-678: freeze cycling over policy groups (utils/schedulers.py:FreezeCyclingScheduler)
         from .utils.schedulers import FreezeCyclingScheduler
         if freeze_scheduler is None:

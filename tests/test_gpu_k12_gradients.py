@@ -1,0 +1,343 @@
+"""
+-m gpu: ONE K12 mini-batch against the float64 reference (oracle/k12_oracle.py, pinned to the g12_* fixtures by
+tests/test_k12_oracle.py) at the shape edges where kernels go wrong, on every form of K12: the default chain (split-wgrad
+panels + the fused tail launch, 256-wide networks on row pairs), the same with separate wgrad and Adam launches
+(PPOAF_FUSED_TAIL=0), the slab chain (PPOAF_SPLIT_WGRAD=0) and one workgroup per row tile (row_pairs = False).  Shapes a
+form does not cover fall back by themselves.
+
+Each case steers the inputs in the rollout buffer before begin_epoch: ratios spread over [0.5, 1.6] with both signs of
+advantage (both clip branches carry gradient), rewards-to-go on Huber's linear branch, a value normaliser that is not the
+identity, Gaussian raw actions near |x| = 4.  Kinks: rows with a ReLU / LeakyReLU pre-activation within 1e-4 x its row's
+scale of zero (float64) get new observations from N(0, 1), drawn with numpy generator (seed, round), until none is left.
+Then
+  * the gradient bucket + the eight totals of fused.gradient_only (step counters restored);
+  * one full mini-batch (_one) from a preset m, v and step count, clip active and inactive: the gradient bucket the
+    launch leaves, the parameter step, m and v against the float64 clip + Adam.
+Bound per tensor: |x - x64| <= 1e-5 |x64| + 1e-5 max|x64|, raised to 4 max|x32 - x64| (the same reference in float32 on
+the CPU) where float32 itself cannot do better (ko.deviations).
+"""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+from oracle import k12_oracle as ko
+
+pytestmark = pytest.mark.gpu
+
+FORMS = {"chain": ({}, True), "three_launches": ({"PPOAF_FUSED_TAIL": "0"}, True),
+         "slabs": ({"PPOAF_SPLIT_WGRAD": "0"}, True), "row_tiles": ({}, False)}
+ACTS = {"relu": nn.ReLU, "leaky_relu": nn.LeakyReLU, "tanh": nn.Tanh}
+WORST = {}                     # (form, head) -> (worst fraction of the bound, where)
+# the eight totals are one tensor of the rule (max over all eight): KL and the surrogate are means of O(1) terms that
+# cancel, so their own magnitude is no scale for float32's rounding of the terms
+TOTALS = [("", "totals", 0, (8,))]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    yield
+    lines = [f"{f:15s} {h:18s} {v[0]:.3f}  {v[1]}" for (f, h), v in sorted(WORST.items())]
+    print("\nworst deviation / bound per form and head:\n" + "\n".join(lines))
+    out = os.environ.get("PPOAF_K12_REPORT")
+    if out:
+        with open(out, "w") as fh:
+            json.dump({f"{f}/{h}": v for (f, h), v in sorted(WORST.items())}, fh, indent=1)
+
+
+def case(O=8, ha=64, hc=None, depth=2, B=64, head=("categorical", 3), act="relu", wide_critic=False, norm_adv=True,
+         norm_values=True, huber=True, kl=0.0, ent=0.01, seed=0):
+    return dict(O=O, ha=ha, hc=hc or ha, depth=depth, B=B, head=head, act=act, wide_critic=wide_critic,
+                norm_adv=norm_adv, norm_values=norm_values, huber=huber, kl=kl, ent=ent, seed=seed)
+
+
+CASES = {
+    # in_dim edges (row-tile body branches at 16 / 64, split chain up to 64)
+    **{f"in{O}": case(O=O, head=h, act=a, seed=O) for O, h, a in (
+        (1, ("categorical", 2), "relu"), (3, ("gaussian", 2), "tanh"), (15, ("multi_categorical", (3, 2)), "leaky_relu"),
+        (16, ("bernoulli", 3), "relu"), (17, ("categorical", 8), "tanh"), (63, ("gaussian", 1), "relu"),
+        (64, ("multi_categorical", (1,) * 8), "relu"), (65, ("bernoulli", 8), "leaky_relu"),
+        (128, ("categorical", 4), "relu"), (376, ("gaussian", 8), "tanh"), (1024, ("categorical", 3), "relu"))},
+    # width pairs, critic in_dim twice the actor's
+    **{f"w{a}x{c}": case(O=11, ha=a, hc=c, depth=2, B=96, wide_critic=True, act=act, head=h, seed=a + c)
+       for (a, c), act, h in (((32, 32), "tanh", ("bernoulli", 2)), ((64, 64), "relu", ("gaussian", 3)),
+                              ((128, 128), "leaky_relu", ("multi_categorical", (2, 2, 3))),
+                              ((256, 256), "relu", ("categorical", 5)), ((128, 256), "tanh", ("gaussian", 4)),
+                              ((64, 128), "relu", ("multi_categorical", (4, 4))))},
+    # depth 1 .. 7 where the LDS allows it
+    **{f"d{d}_128": case(O=20, ha=128, depth=d, B=80, act="leaky_relu" if d % 2 else "tanh",
+                         head=("multi_categorical", (3, 3, 2)) if d % 3 == 0 else ("categorical", 4), seed=d)
+       for d in range(1, 8)},
+    "d4_256_in160": case(O=160, ha=256, depth=4, B=64, head=("gaussian", 2), seed=44),
+    "d3_256_in376": case(O=376, ha=256, depth=3, B=48, head=("categorical", 3), act="tanh", seed=45),
+    # batch sizes: ragged last tile, n_wg mod 4 != 0, split chain up to 512, slab fallback above
+    **{f"B{B}": case(O=12, ha=64 if B < 256 else 128, depth=2, B=B, head=h, act=a, seed=B)
+       for B, h, a in ((2, ("categorical", 2), "relu"), (15, ("gaussian", 2), "relu"), (16, ("bernoulli", 1), "tanh"),
+                       (17, ("multi_categorical", (2, 3)), "relu"), (63, ("categorical", 6), "leaky_relu"),
+                       (65, ("gaussian", 5), "relu"), (255, ("bernoulli", 5), "relu"),
+                       (256, ("categorical", 2), "tanh"), (257, ("multi_categorical", (3, 3)), "relu"),
+                       (511, ("gaussian", 3), "leaky_relu"), (512, ("categorical", 7), "relu"),
+                       (513, ("bernoulli", 4), "relu"), (1024, ("gaussian", 6), "relu"))},
+    # loss switches
+    "no_norm_adv": case(norm_adv=False, head=("gaussian", 2), seed=91),
+    "no_norm_values": case(norm_values=False, head=("bernoulli", 6), seed=92),
+    "mse_kl_no_entropy": case(huber=False, kl=0.3, ent=0.0, head=("multi_categorical", (8,)), seed=93),
+    "md_one_slice_of_1": case(head=("multi_categorical", (1, 7)), seed=94),
+}
+
+
+def _space(head):
+    from ppo_and_friends_amd.spaces import Box, Discrete, MultiBinary, MultiDiscrete
+    kind, n = head
+    return {"categorical": lambda: Discrete(n), "gaussian": lambda: Box(-1.0, 1.0, (n,), np.float32),
+            "multi_categorical": lambda: MultiDiscrete(list(n)), "bernoulli": lambda: MultiBinary(n)}[kind]()
+
+
+def _ppo(c, mode="fused"):
+    from ppo_and_friends_amd.ppo import PPO
+    from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
+    from ppo_and_friends_amd.spaces import Box
+    dev = torch.device("cuda", 0)
+    agents = 2 if c["wide_critic"] else 1
+    T = 8
+    E = (c["B"] + agents * T - 1) // (agents * T) + 1
+    space = _space(c["head"])
+    env_gen = lambda: SyntheticFixedLengthEnv(E, c["O"], space, T, dev, reward="uniform", seed=77, num_agents=agents,
+                                              critic_view="policy" if agents > 1 else "local")
+    sp, csp = Box(-np.inf, np.inf, (c["O"],), np.float32), Box(-np.inf, np.inf, (c["O"] * agents,), np.float32)
+    kw = dict(hidden_size=c["ha"], hidden_depth=c["depth"], activation=ACTS[c["act"]]())
+    pargs = dict(actor_kw_args=kw, critic_kw_args=dict(kw, hidden_size=c["hc"]), use_huber_loss=c["huber"],
+                 entropy_weight=c["ent"], kl_loss_weight=c["kl"])
+    return PPO(env_gen, {"p": (None, sp, csp, space, pargs)}, device=dev, random_seed=3, normalize_obs=False,
+               normalize_rewards=False, normalize_adv=c["norm_adv"], normalize_values=c["norm_values"], envs_per_proc=E,
+               ts_per_rollout=T, batch_size=c["B"], epochs_per_iter=1, use_graphs=False, update_mode=mode, save_state=False)
+
+
+class Steered:
+    """The case's PPO after a rollout, with the first mini-batch's inputs steered in the buffer; the float64 / float32
+    references of that mini-batch."""
+
+    def __init__(self, c):
+        from ppo_and_friends_amd.fused_update import FusedPolicyUpdate
+        self.c, B, seed = c, c["B"], c["seed"]
+        self.ppo = ppo = _ppo(c)
+        assert FusedPolicyUpdate.unsupported_reason(ppo.policies["p"], B) == ""
+        ppo.rollout()
+        pol = self.pol = ppo.policies["p"]
+        pol.train()
+        buf = pol.buffer
+        rng = np.random.default_rng(seed)
+        n = len(pol.dataset)
+        self.perm = torch.as_tensor(rng.permutation(n), dtype=torch.int64, device=pol.device)
+        rows = buf.row_map[self.perm[:B]].long()
+        N = buf.num_transitions
+        self.flat = lambda x: x.view((N,) + tuple(x.shape[2:]))
+        self.rows = rows
+        upd = FusedPolicyUpdate(ppo, "p")
+        head = self.head = c["head"][0]
+        self.slices = tuple(c["head"][1]) if head == "multi_categorical" else ()
+        self.actor = ko.Net(upd.actor_desc.in_dim, upd.actor_desc.hidden, upd.actor_desc.depth, upd.actor_desc.out_dim, c["act"])
+        self.critic = ko.Net(upd.critic_desc.in_dim, upd.critic_desc.hidden, upd.critic_desc.depth, 1, c["act"])
+        self.tables, size = ko.bucket_tables(self.actor, self.critic, head)
+        self.na = upd.actor_desc.size
+        assert size == pol.policy_params.numel()
+        self.params = pol.policy_params.detach().double().cpu().numpy()
+        # ---- observations: N(0, 1), kinked rows drawn again
+        obs = rng.normal(0, 1, (B, self.actor.in_dim)).astype(np.float32)
+        cobs = rng.normal(0, 1, (B, self.critic.in_dim)).astype(np.float32)
+        for r in range(50):
+            ka = ko.kinked_rows(self.actor, self.params[:self.na], obs)
+            kc = ko.kinked_rows(self.critic, self.params[self.na:], cobs)
+            if not (ka.any() or kc.any()):
+                break
+            g = np.random.default_rng((seed, r))
+            obs[ka] = g.normal(0, 1, (int(ka.sum()), obs.shape[1]))
+            cobs[kc] = g.normal(0, 1, (int(kc.sum()), cobs.shape[1]))
+        else:
+            pytest.fail("kinked rows left after 50 redraws")
+        self._put("observations", obs)
+        self._put("critic_observations", cobs)
+        if head == "gaussian":
+            acts = rng.normal(0, 1.5, (B, self.actor.out_dim)).astype(np.float32)
+            k = max(1, B // 8)
+            acts[:k] = np.sign(acts[:k]) * rng.uniform(3.8, 4.2, acts[:k].shape)
+            self._put("raw_actions", acts)
+        raw = self._get("raw_actions")
+        # ---- value normaliser, advantages, rewards-to-go (one row in 50 on Huber's linear branch)
+        self.vn = (0.3, 0.25, 5000.0) if c["norm_values"] else (0.0, 1.0, 1e-4)
+        rs = ppo.value_normalizers["p"].running_stats if c["norm_values"] else None
+        if rs is not None:
+            rs.mean_t.fill_(self.vn[0]); rs.var_t.fill_(self.vn[1]); rs.count_t.fill_(self.vn[2])
+        sd = 0.5 if c["norm_values"] else 1.0
+        rtg = (0.3 + sd * rng.normal(0, 1, B)).astype(np.float32)
+        k = max(1, B // 50)
+        rtg[:k] = (0.3 + sd * 20.0 * np.where(rng.random(k) < 0.5, -1.0, 1.0)).astype(np.float32)
+        self._put("rewards_to_go", rtg)
+        self._put("advantages", rng.normal(0.2, 1.0, B).astype(np.float32))
+        self.consts = ko.Consts(c["norm_adv"], c["norm_values"], c["huber"], 10.0, float(pol.surr_clip),
+                                float(pol.entropy_weight()), float(pol.kl_loss_weight),
+                                float(getattr(pol.actor.distribution, "min_std", 0.01)))
+        mb = self._mb(raw, np.zeros(B, np.float32))
+        logp = ko.minibatch(self.params, self.actor, self.critic, head, self.slices, mb, self.consts, self.vn)["logp"]
+        self._put("log_probs", ko.steered_old_log_probs(logp, rng, self.consts.surr_clip))
+        self.mb = self._mb(raw, self._get("log_probs").reshape(-1))
+        self.r64 = self._ref(torch.float64)
+        self.r32 = self._ref(torch.float32)
+        if c["huber"]:
+            d = np.abs(self.r64["values"] - self.r64["rtg"])
+            assert (d > 10.0).any() and np.abs(d - 10.0).min() > 1e-3, "Huber branch steering"
+        ratio = np.exp(self.r64["logp"] - self.mb.old_log_probs)
+        assert B < 8 or ((ratio < 0.8).any() and (ratio > 1.2).any())
+
+    def _put(self, field, x):
+        t = self.flat(getattr(self.pol.buffer, field))
+        t[self.rows] = torch.as_tensor(x).to(t.dtype).to(t.device).reshape((len(x),) + tuple(t.shape[1:]))
+
+    def _get(self, field):
+        return self.flat(getattr(self.pol.buffer, field))[self.rows].detach().cpu().numpy()
+
+    def _mb(self, raw, old):
+        return ko.Minibatch(self._get("observations"), self._get("critic_observations"), raw, old,
+                            self._get("advantages").reshape(-1), self._get("rewards_to_go").reshape(-1))
+
+    def _ref(self, dtype):
+        return ko.minibatch(self.params, self.actor, self.critic, self.head, self.slices, self.mb, self.consts, self.vn,
+                            dtype=dtype)
+
+
+def _check(form, head, what, got, want64, want32, tables):
+    devs = ko.deviations(got, want64, want32, tables)
+    name, frac, _ = max(devs, key=lambda d: d[1])
+    key = (form, head)
+    if frac > WORST.get(key, (-1.0, ""))[0]:
+        WORST[key] = (frac, f"{what}: {name}")
+    bad = ko.failures(got, want64, want32, tables)
+    assert not bad, f"{form} / {what}: " + "; ".join(bad[:6])
+
+
+def _padding(tables, size):
+    used = np.zeros(size, dtype=bool)
+    for _, _, off, shape in tables:
+        used[off:off + int(np.prod(shape))] = True
+    return ~used
+
+
+def run_case(c, monkeypatch):
+    from ppo_and_friends_amd.fused_update import FusedPolicyUpdate
+    s = Steered(c)
+    pol, B, head = s.pol, c["B"], s.head
+    keep = [t.clone() for t in (pol.policy_params, pol.policy_exp_avg, pol.policy_exp_avg_sq, pol.policy_step_counts)]
+    pad = _padding(s.tables, pol.policy_params.numel())
+    # preset optimiser state: step 6 / 9, m and v on the gradients' scale
+    rng = np.random.default_rng(c["seed"] + 1)
+    g = s.r64["grads"]
+    rms = np.sqrt(np.mean(g * g)) + 1e-12
+    m0 = np.where(pad, 0.0, 0.5 * g + rng.normal(0, 0.1 * rms, g.size)).astype(np.float32)
+    v0 = np.where(pad, 0.0, g * g * rng.uniform(0.5, 2.0, g.size) + (0.1 * rms) ** 2).astype(np.float32)
+    steps0 = (6, 9)
+    norms = [np.sqrt((g[:s.na] ** 2).sum()), np.sqrt((g[s.na:] ** 2).sum())]
+    lr = float(pol.policy_lr[0])
+    clip0 = pol.gradient_clip
+    for form, (env, pairs) in FORMS.items():
+        with monkeypatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            mp.setattr(FusedPolicyUpdate, "row_pairs", pairs)
+            upd = FusedPolicyUpdate(s.ppo, "p")
+            # ---- the gradient of one mini-batch
+            upd.begin_epoch(s.perm)
+            args = upd._args_for(B)
+            steps = pol.policy_step_counts.clone()
+            upd.gradient_only(args)
+            torch.cuda.synchronize()
+            pol.policy_step_counts.copy_(steps)
+            grads = pol.policy_grads.detach().double().cpu().numpy()
+            assert not grads[pad].any(), f"{form}: padding of the gradient bucket written"
+            _check(form, head, "gradient", grads, s.r64["grads"], s.r32["grads"], s.tables)
+            _check(form, head, "totals", upd.totals[:8].cpu().numpy(), s.r64["totals"], s.r32["totals"], TOTALS)
+            # ---- one full mini-batch from a non-zero optimiser state, clip active / inactive
+            for max_norm in (0.25 * min(norms), 4.0 * max(norms)):
+                pol.gradient_clip = float(np.float32(max_norm))
+                pol.policy_exp_avg.copy_(torch.from_numpy(m0))
+                pol.policy_exp_avg_sq.copy_(torch.from_numpy(v0))
+                pol.policy_step_counts.copy_(torch.tensor(steps0))
+                pol.policy_params.copy_(keep[0])
+                upd.begin_epoch(s.perm)
+                args = upd._args_for(B)
+                upd._one(args)
+                torch.cuda.synchronize()
+                upd._check_persistent()
+                got = [t.detach().double().cpu().numpy() for t in (pol.policy_grads, pol.policy_params,
+                                                                    pol.policy_exp_avg, pol.policy_exp_avg_sq)]
+                mn = float(np.float32(max_norm))
+                want = ko.clip_adam(s.params, s.r64["grads"], m0, v0, steps0, lr, mn, s.na)
+                want32 = ko.clip_adam(s.params, s.r32["grads"], m0, v0, steps0, lr, mn, s.na, dtype=torch.float32)
+                tag = "clip" if max_norm < min(norms) else "no clip"
+                _check(form, head, f"{tag} gradient", got[0], s.r64["grads"], s.r32["grads"], s.tables)
+                _check(form, head, f"{tag} step", got[1] - s.params, want[0] - s.params, want32[0] - s.params, s.tables)
+                _check(form, head, f"{tag} m", got[2], want[1], want32[1], s.tables)
+                _check(form, head, f"{tag} v", got[3], want[2], want32[2], s.tables)
+                assert (pol.policy_step_counts.cpu().numpy() == np.array(steps0) + 1).all()
+            pol.gradient_clip = clip0
+            for t, k in zip((pol.policy_params, pol.policy_exp_avg, pol.policy_exp_avg_sq, pol.policy_step_counts), keep):
+                t.copy_(k)
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_k12_minibatch_against_float64(name, monkeypatch):
+    run_case(CASES[name], monkeypatch)
+
+
+def test_k12_minibatch_fuzz(monkeypatch):
+    """Derandomised draws over the same space: in_dim, width pair, depth, B, head, activation, loss switches."""
+    from hypothesis import HealthCheck, given, settings, strategies as st
+
+    @settings(max_examples=12, deadline=None, derandomize=True, suppress_health_check=list(HealthCheck))
+    @given(O=st.integers(1, 200), pair=st.sampled_from([(32, 32), (64, 64), (128, 128), (256, 256), (128, 256), (64, 128)]),
+           depth=st.integers(1, 4), B=st.integers(2, 600), kind=st.sampled_from(["categorical", "gaussian",
+                                                                                  "multi_categorical", "bernoulli"]),
+           n=st.integers(1, 8), act=st.sampled_from(sorted(ACTS)), wide=st.booleans(), norm_adv=st.booleans(),
+           norm_values=st.booleans(), huber=st.booleans(), kl=st.sampled_from([0.0, 0.2]), ent=st.sampled_from([0.0, 0.01]),
+           seed=st.integers(0, 1000))
+    def run(O, pair, depth, B, kind, n, act, wide, norm_adv, norm_values, huber, kl, ent, seed):
+        if kind == "categorical":
+            n = max(n, 2)
+        slices = [1 + (i % 3) for i in range(n)]
+        while sum(slices) > 8:
+            slices.pop()
+        head = (kind, tuple(slices) if kind == "multi_categorical" else n)
+        if max(pair) == 256 and depth > 3:
+            O = min(O, 160)
+        run_case(case(O=O, ha=pair[0], hc=pair[1], depth=depth, B=B, head=head, act=act, wide_critic=wide,
+                      norm_adv=norm_adv, norm_values=norm_values, huber=huber, kl=kl, ent=ent, seed=seed), monkeypatch)
+
+    run()
+
+
+# ---------------------------------------------------------------------------------------------------- scope on the GPU
+@pytest.mark.parametrize("O,hidden,depth", [(376, 256, 4), (8, 256, 5), (8, 64, 8)])
+def test_shapes_out_of_scope(O, hidden, depth):
+    """"auto" trains them on the torch path; "fused" refuses them before the first rollout; the kernel itself refuses them
+    (what the first epoch ran into while the Python scope let them through)."""
+    from ppo_and_friends_amd import _lib
+    from ppo_and_friends_amd.fused_update import FusedPolicyUpdate
+    from ppo_and_friends_amd.ppo import PermutationLoader
+    c = case(O=O, ha=hidden, depth=depth, B=32, head=("categorical", 3))
+    with pytest.raises(NotImplementedError, match="update_mode='fused'"):
+        _ppo(c, "fused")
+    ppo = _ppo(c, "auto")
+    assert ppo._fused_updater("p", 32) is None
+    ppo.rollout()
+    pol = ppo.policies["p"]
+    pol.train()
+    before = pol.policy_params.clone()
+    ppo._ppo_batch_train(PermutationLoader(pol.dataset, 32, ppo.loader_generator), "p")
+    assert torch.isfinite(pol.policy_params).all() and not torch.equal(before, pol.policy_params)
+    if depth <= 7:                     # (depth 8: the policy builds, the library's layer table refuses it in the query)
+        upd = FusedPolicyUpdate(ppo, "p")
+        upd.begin_epoch(torch.arange(len(pol.dataset), device=pol.device))
+        with pytest.raises(_lib.PpoafError, match="LDS"):
+            upd._one(upd._args_for(32))
