@@ -27,7 +27,7 @@ namespace ppoaf {
 // pair.  Placement only changes speed; nothing depends on it.
 template <int HTA, int HTC, bool SPLIT>
 __global__ __launch_bounds__(kThreadsU) void ppo_update_fwd_bwd_kernel(UpdateDev u) {
-    const int b = blockIdx.x;
+    const int b = rowtile_request_args(u, blockIdx.x);     // one round trip for the argument block, then the cursor's
     int which = (b >> 2) & 1;                              // b % 8 in {0..3} -> actor, {4..7} -> critic
     int g = ((b >> 3) << 2) | (b & 3);
     if (u.confine) {                                // one half of the XCDs left to another chain (args->xcd_half)
@@ -60,10 +60,10 @@ __global__ __launch_bounds__(kThreadsU) void ppo_update_fwd_bwd_pair_kernel(Upda
     if (g >= u.n_wg) return;                               // uniform per workgroup, before any barrier
     if (which == 0) {
         if constexpr (HTA == 16) ppo_update_fwd_bwd_pair_body<16>(u, 0, g, hf, pd);
-        else ppo_update_fwd_bwd_body<HTA, true>(u, 0, g);
+        else ppo_update_fwd_bwd_body_as<HTA, true, false>(u, 0, g);     // (the 256-wide partner's pairs set this launch's time)
     } else {
         if constexpr (HTC == 16) ppo_update_fwd_bwd_pair_body<16>(u, 1, g, hf, pd);
-        else ppo_update_fwd_bwd_body<HTC, true>(u, 1, g);
+        else ppo_update_fwd_bwd_body_as<HTC, true, false>(u, 1, g);
     }
 }
 

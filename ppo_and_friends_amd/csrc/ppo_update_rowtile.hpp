@@ -46,8 +46,52 @@ __device__ __forceinline__ f32x4 mfma_fwd_set(const float* __restrict__ A, int H
     else return mfma_rows_x_lines<HT>(A, HS, lane, fr, init, scratch);
 }
 
-template <int HT, bool SPLIT = false>
-__device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, const int which, const int g) {
+// The kernel arguments the prologue of a row-tile workgroup needs, asked for in ONE batch at the kernel's entry.  Left to
+// itself the compiler fetches the 1176-byte argument block field group by field group as the code reaches each use, every
+// group with a wait of its own and nothing else in flight (nine of them ahead of the first vector load, the cursor's the
+// fourth).  An empty asm that takes the fields as scalar inputs makes all of them due at one point: their loads go out
+// together, one wait covers them, and the uses below find the values in registers (kernel-argument loads are invariant:
+// the same field is not fetched twice as long as it stays in a register or in a lane of the spill register).  The cursor
+// and the fields both flavours of the body read first make the second trip: 2 scalar waits ahead of the first vector
+// load, of 9.  Both networks' descriptors: a workgroup's network is chosen behind this point.
+__device__ __forceinline__ int rowtile_request_args(const UpdateDev& u, int b) {
+    // (`b`, the workgroup's number, goes through the statement: everything below depends on it, so the statement stays
+    //  where it is without being volatile -- a volatile asm counts as a store to anywhere, and the cursor's load behind it
+    //  would no longer be a scalar load)
+    const NetDev& a = u.net[0];
+    const NetDev& c = u.net[1];
+    // (fields the prologue has no use for are on the list where they lie between ones it needs: adjacent fields are
+    //  fetched by one wide load, and a register of that load that nobody reads is handed to the next load at once --
+    //  which then has to wait for the wide one first)
+    asm("" : "+s"(b)
+        : "s"(a.in_dim), "s"(a.H), "s"(a.depth), "s"(a.out_dim), "s"(a.act), "s"((&a.act)[1]), "s"(a.offset), "s"(a.size), "s"(a.log_std_off),
+          "s"(c.in_dim), "s"(c.H), "s"(c.depth), "s"(c.out_dim), "s"(c.act), "s"((&c.act)[1]), "s"(c.offset), "s"(c.size), "s"(c.log_std_off),
+          "s"(u.params), "s"(u.norm_scratch), "s"(u.head_kind),
+          "s"(u.obs), "s"(u.critic_obs), "s"(u.raw_actions), "s"(u.adv), "s"(u.old_lp), "s"(u.rtg), "s"(u.values), "s"(u.perm),
+          "s"(u.row_map), "s"(u.n_rows), "s"(u.cursor), "s"(u.B), "s"(u.batch_stride), "s"(u.mb_offset), "s"(u.cursor_advance),
+          "s"(u.normalize_values), "s"(u.n_ranks), "s"(u.vn_mean), "s"(u.vn_var), "s"(u.vn_count), "s"(u.vn_records),
+          "s"(u.adv_records), "s"(u.normalize_adv), "s"(u.use_huber), "s"(u.pregathered), "s"(u.surr_clip),
+          "s"(u.n_wg), "s"(u.confine));
+    // second trip: the cursor itself, and with it what both flavours of the body read first behind their dispatch (the
+    // compiler hoists those loads to the dispatch and parks them in lanes of a vector register at once -- two more waits)
+    const long cur = u.cursor[0];
+    asm("" : "+s"(b)
+        : "s"(cur), "s"(u.entropy_weight), "s"(u.kl_loss_weight), "s"(u.huber_delta), "s"(u.min_std), "s"(u.loss_partials),
+          "s"(u.sp.hbuf[0]), "s"(u.sp.hbuf[1]), "s"(u.sp.dbuf[0]), "s"(u.sp.dbuf[1]), "s"(u.sp.outpart[0]), "s"(u.sp.outpart[1]),
+          "s"(u.sp.xbuf[0]), "s"(u.sp.xbuf[1]), "s"(u.sp.W), "s"(u.sp.xcc[0]), "s"(u.sp.xcc[1]), "s"(u.sp.Bp), "s"(u.n_slices),
+          "s"(u.slices[0]), "s"(u.slices[1]), "s"(u.slices[2]), "s"(u.slices[3]), "s"(u.slices[4]), "s"(u.slices[5]),
+          "s"(u.slices[6]), "s"(u.slices[7]));
+    return b;
+}
+
+// TABLES is the flavour the epoch driver of fused_update.py runs at three hidden layers: the deep prefetch below (one
+// output tile per wave) over per-epoch tables in shuffled order that hold row numbers (u.pregathered, no u.row_map).  It is
+// a compile-time flavour, chosen by ppo_update_fwd_bwd_body from the arguments.  As run-time conditions of one body, "are
+// the hidden sets requested" and "do a row's scalars follow the sets as dependent loads" left the compiler several
+// histories to reconcile at every later wait of the prologue, and its safe answer to that is vmcnt(0): each of those waits
+// then waited for the sets as well.  Every other case runs the body as it was (TABLES = false: both decided at run time).
+template <int HT, bool SPLIT, bool TABLES>
+__device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, const int which, const int g) {
     // (NT, mb_extra: what the persistent forms of rounds 2-3 set -- loads at agent scope, the mini-batch's position inside a
     //  launch; the forms are gone, the constants keep the body's text as it was measured)
     constexpr bool NT = false;
@@ -116,8 +160,9 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, cons
     // its registers are refilled with the dgrad fragments of the backward pass (W2 first, then W1).  Every
     // weight load is then in flight for at least two phases -- including the cold first touch after the
     // Adam kernel rewrote the bucket -- instead of one barrier.
-    const bool has_tile = wave < HT;          // waves beyond the tile count idle in MFMA phases (H < 128)
-    const bool deep = depth == 3 && HT <= kNW;
+    const bool has_tile = HT >= kNW || wave < HT;          // waves beyond the tile count idle in MFMA phases (H < 128)
+    static_assert(!TABLES || HT <= kNW, "deep prefetch: one output tile per wave");
+    const bool deep = TABLES || (depth == 3 && HT <= kNW);   // (TABLES: the caller has checked depth == 3)
     float4 fr[HT], fr2[HT];
     // first layer with at most 16 inputs: its 4 weight values per lane are requested early as well
     const bool l0_pre = in_dim <= 16 && HT <= kNW && has_tile;
@@ -162,6 +207,9 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, cons
                 if (i < n_wout) wout_reg[r] = ld1<NT>(P + offW(depth) + i);
             }
         }
+    };
+    // ... and the hidden sets, LAST of the prologue's requests: whatever a wave asks for behind them arrives behind 16 KB
+    auto request_hidden_sets = [&]() {
         if (!NT && deep && has_tile) {
             load_fwd_set<HT, NT>(P + offW(1), wave * 16, lane, fr);
             load_fwd_set<HT, NT>(P + offW(2), wave * 16, lane, fr2);
@@ -172,7 +220,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, cons
     // per-epoch tables in shuffled order: an input row's address depends on the cursor only -- requested now (16 x in_dim <=
     // 1024 values: two per thread), dropped below where the row turns out to be padding
     const float* x_src = which == 0 ? u.obs : u.critic_obs;
-    const bool x_pre = !NT && u.pregathered && kRows * in_dim <= 2 * kThreadsU;
+    const bool x_pre = !NT && (TABLES || u.pregathered) && kRows * in_dim <= 2 * kThreadsU;
     float xr[2] = {0.f, 0.f};
     if (x_pre) {
 #pragma unroll
@@ -181,68 +229,152 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, cons
             if (idx < kRows * in_dim && (long)g * kRows + idx / in_dim < B) xr[q] = x_src[(base + (long)g * kRows) * in_dim + idx];
         }
     }
+    // (a line of text in the assembly: tools/prologue_isa.py reads the TABLES flavour's prologue from here)
+    if constexpr (TABLES) asm volatile("; ppoaf_rowtile_tables_prologue");
     if (!NT) request_weights();
 
-    if (tid < kRows) {
-        const long s = (long)g * kRows + tid;
-        int row = -1;
-        long di = -1;                                      // where this row's inputs are read from
-        if (s < B) {
-            const long p = u.perm[base + s];
-            if (p >= 0 && p < u.n_rows) row = u.row_map ? u.row_map[p] : (int)p;
-            // per-epoch tables in shuffled order: the address depends on the cursor only, so these loads
-            // go out together with the perm load instead of after it
-            di = u.pregathered ? base + s : row;
-        }
-        float av = 0.f, lpo = 0.f, rt = 0.f;
-        if (di >= 0) {
-            if (which == 0) {
-                av = u.adv[di]; lpo = u.old_lp[di];
-                if (u.head_kind == PPOAF_HEAD_CATEGORICAL)
-                    reinterpret_cast<int*>(sActF)[tid * 8] = (int)reinterpret_cast<const int64_t*>(u.raw_actions)[di];
-                else if (u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL)
-                    for (int j = 0; j < u.n_slices; ++j)
-                        reinterpret_cast<int*>(sActF)[tid * 8 + j] =
-                            (int)reinterpret_cast<const int64_t*>(u.raw_actions)[(long)di * u.n_slices + j];
-                else
-                    for (int d = 0; d < out_dim; ++d)
-                        sActF[tid * 8 + d] = reinterpret_cast<const float*>(u.raw_actions)[(long)di * out_dim + d];
+    // Wave 0's row lanes and the statistics lane, in arrival order as well (a wave's loads retire in order): with the
+    // per-epoch tables in shuffled order (u.pregathered) the address of a row's scalars -- like the index itself -- depends
+    // on the cursor only, so they are requested HERE, ahead of the hidden sets, and consumed below where they always were.
+    // Behind the sets, the index alone cost wave 0 the arrival of its whole 16 KB of W_1 / W_2 before layer 0 could start,
+    // and the scalars a further round trip after that.  Outside the TABLES flavour the scalars keep their dependent trip.
+    constexpr int kActRegs = 8;                            // sActF holds 8 action words per row
+    constexpr int kVnPre = 2;                              // per-rank value-normaliser records requested ahead of the sets
+    const bool row_lane = tid < kRows && (long)g * kRows + tid < B;      // rows >= B: no address is formed
+    static_assert(!TABLES || !NT, "per-epoch tables: separate launches only");
+    constexpr bool early = TABLES;                         // (every other case: behind the index, as it was)
+    const int n_act = which != 0 ? 0 : u.head_kind == PPOAF_HEAD_CATEGORICAL ? 1
+                    : u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? u.n_slices : out_dim;
+    long perm_v = -1;
+    float av = 0.f, lpo = 0.f, rt = 0.f;
+    int act_bits[kActRegs];                                // raw actions as sActF keeps them: class indices, or float bits
+#pragma unroll
+    for (int j = 0; j < kActRegs; ++j) act_bits[j] = 0;
+    auto request_row_scalars = [&](const long di) {
+        if (which == 0) {
+            av = u.adv[di]; lpo = u.old_lp[di];
+            if (u.head_kind == PPOAF_HEAD_CATEGORICAL) {
+                act_bits[0] = (int)reinterpret_cast<const int64_t*>(u.raw_actions)[di];
+            } else if (u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL) {
+#pragma unroll
+                for (int j = 0; j < kActRegs; ++j)
+                    if (j < n_act) act_bits[j] = (int)reinterpret_cast<const int64_t*>(u.raw_actions)[(long)di * u.n_slices + j];
             } else {
-                rt = u.rtg[di];
+#pragma unroll
+                for (int d = 0; d < kActRegs; ++d)
+                    if (d < n_act) act_bits[d] = __float_as_int(reinterpret_cast<const float*>(u.raw_actions)[(long)di * out_dim + d]);
+            }
+        } else {
+            rt = u.rtg[di];
+        }
+    };
+    if (row_lane) {
+        const long s = (long)g * kRows + tid;
+        perm_v = u.perm[base + s];
+        if (early) request_row_scalars(base + s);
+    }
+    // the statistics lane's words: the mini-batch's advantage record, or the value normaliser's state and the first
+    // kVnPre per-rank records of the mini-batch (ranks beyond them are read in the merge loop below)
+    const bool stat_lane = tid == 64;
+    double adv_rec[3] = {0.0, 0.0, 0.0}, vn_rec[kVnPre][3];
+    float vn_m = 0.f, vn_v = 0.f;
+    double vn_cnt = 0.0;
+#pragma unroll
+    for (int r = 0; r < kVnPre; ++r) { vn_rec[r][0] = 0.0; vn_rec[r][1] = 0.0; vn_rec[r][2] = 0.0; }
+    if (stat_lane) {
+        if (which == 0) {
+            if (u.normalize_adv) {
+                const double* rec = u.adv_records + mb * 3;
+                adv_rec[0] = rec[0]; adv_rec[1] = rec[1]; adv_rec[2] = rec[2];
+            }
+        } else {
+            const int slot = (int)(mb & 1);
+            vn_m = ld1<NT>(u.vn_mean + slot); vn_v = ld1<NT>(u.vn_var + slot);
+            vn_cnt = ld1<NT>(u.vn_count + slot);
+            if (u.normalize_values) {
+#pragma unroll
+                for (int r = 0; r < kVnPre; ++r) {
+                    if (r < u.n_ranks) {
+                        const double* rec = u.vn_records + (mb * u.n_ranks + r) * 3;
+                        vn_rec[r][0] = rec[0]; vn_rec[r][1] = rec[1]; vn_rec[r][2] = rec[2];
+                    }
+                }
             }
         }
-        sRow[tid] = row;
-        sRowF[tid] = av; sRowF[16 + tid] = lpo; sRowF[32 + tid] = rt;
+    }
+    // Chan merge of the per-rank records of this mini-batch (one step; the reference's order: rank 0 first)
+    double vn_n = 0.0, vn_bm = 0.0, vn_M2 = 0.0;
+    auto vn_merge = [&](const double nb, const double mean, const double m2) {
+        if (nb <= 0.0) return;
+        const double d = mean - vn_bm, nn = vn_n + nb;
+        vn_bm += d * (nb / nn);
+        vn_M2 += m2 + d * d * vn_n * nb / nn;
+        vn_n = nn;
+    };
+    // more ranks than records requested above: their reads depend on nothing but the cursor either, but somebody has to
+    // hold them -- merged here, one dependent trip of this lane's wave ahead of its sets, so that no wait behind the sets
+    // ever waits for a set
+    if (stat_lane && which != 0 && u.normalize_values && u.n_ranks > kVnPre) {
+#pragma unroll
+        for (int r = 0; r < kVnPre; ++r) vn_merge(vn_rec[r][0], vn_rec[r][1], vn_rec[r][2]);
+        for (int r = kVnPre; r < u.n_ranks; ++r) {
+            const double* rec = u.vn_records + (mb * u.n_ranks + r) * 3;
+            vn_merge(rec[0], rec[1], rec[2]);
+        }
+    }
+    if (!NT) request_hidden_sets();
+
+    if (tid < kRows) {
+        auto store_row = [&](const int row, const bool have) {
+            if (have) {
+#pragma unroll
+                for (int j = 0; j < kActRegs; ++j)
+                    if (j < n_act) reinterpret_cast<int*>(sActF)[tid * 8 + j] = act_bits[j];
+            }
+            sRow[tid] = row;
+            sRowF[tid] = av; sRowF[16 + tid] = lpo; sRowF[32 + tid] = rt;
+        };
+        if constexpr (TABLES) {
+            // everything this lane stores was requested ahead of the sets
+            int row = -1;
+            if (row_lane && perm_v >= 0 && perm_v < u.n_rows) row = (int)perm_v;
+            store_row(row, row_lane);
+        } else {
+            int row = -1;
+            long di = -1;                                  // where this row's inputs are read from
+            if (row_lane) {
+                const long p = perm_v;
+                if (p >= 0 && p < u.n_rows) row = u.row_map ? u.row_map[p] : (int)p;
+                di = u.pregathered ? base + (long)g * kRows + tid : row;
+            }
+            if (di >= 0 && !early) request_row_scalars(di);
+            store_row(row, di >= 0);
+        }
     }
 
     // ---- S0: everything that does not depend on the rows is requested first: rows / statistics,
     //      biases + output weights -> LDS, and this wave's first-layer weight fragments -> registers.
-    if (tid == 64) {                                        // a lane of wave 1: mini-batch statistics
+    if (stat_lane) {                                        // a lane of wave 1: mini-batch statistics
         if (which == 0) {
             float mean_f = 0.f, std_f = 1.f;
             if (u.normalize_adv) {                           // ppo.py:2326-2333, from the per-epoch table
-                const double* rec = u.adv_records + mb * 3;
-                mean_f = (float)rec[1];
-                std_f = (float)sqrt(rec[2] / (rec[0] - 1.0));
+                mean_f = (float)adv_rec[1];
+                std_f = (float)sqrt(adv_rec[2] / (adv_rec[0] - 1.0));
             }
             sMisc[0] = mean_f; sMisc[1] = std_f;
         } else {
             const int slot = (int)(mb & 1);
-            float m = ld1<NT>(u.vn_mean + slot), v = ld1<NT>(u.vn_var + slot);
-            double cnt = ld1<NT>(u.vn_count + slot);
+            float m = vn_m, v = vn_v;
+            double cnt = vn_cnt;
             if (u.normalize_values) {
                 // Chan merge of the R per-rank records of this mini-batch, then the reference's
                 // integrate (utils/stats.py:73-94) -- same arithmetic as running_moments_integrate_kernel.
-                double n = 0.0, bm = 0.0, M2 = 0.0;
-                for (int r = 0; r < u.n_ranks; ++r) {
-                    const double* rec = u.vn_records + (mb * u.n_ranks + r) * 3;
-                    const double nb = rec[0];
-                    if (nb <= 0.0) continue;
-                    const double d = rec[1] - bm, nn = n + nb;
-                    bm += d * (nb / nn);
-                    M2 += rec[2] + d * d * n * nb / nn;
-                    n = nn;
+                if (u.n_ranks <= kVnPre) {
+#pragma unroll
+                    for (int r = 0; r < kVnPre; ++r)
+                        if (r < u.n_ranks) vn_merge(vn_rec[r][0], vn_rec[r][1], vn_rec[r][2]);
                 }
+                const double n = vn_n, bm = vn_bm, M2 = vn_M2;
                 if (n > 0.0) {
                     const float batch_mean = (float)bm, batch_var = (float)(M2 / n);
                     const float delta = batch_mean - m;
@@ -289,7 +421,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, cons
         for (int idx = tid; idx < kRows * in_dim; idx += kThreadsU) {
             const int s = idx / in_dim, i = idx - s * in_dim;
             const int row = sRow[s];
-            const long di = u.pregathered ? base + (long)g * kRows + s : row;
+            const long di = (TABLES || u.pregathered) ? base + (long)g * kRows + s : row;
             if (row >= 0) sX[s * INP + i] = src[di * in_dim + i];
         }
     }
@@ -507,6 +639,17 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, cons
     }
     if (l2_touch == 1.2345e38f) u.loss_partials[0] = l2_touch;   // keeps the early line touches alive
     PPOAF_STAMP(9);
+}
+
+template <int HT, bool SPLIT = false>
+__device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, const int which, const int g) {
+    if constexpr (HT <= kNW) {
+        if (u.net[which].depth == 3 && u.pregathered && !u.row_map) {        // uniform
+            ppo_update_fwd_bwd_body_as<HT, SPLIT, true>(u, which, g);
+            return;
+        }
+    }
+    ppo_update_fwd_bwd_body_as<HT, SPLIT, false>(u, which, g);
 }
 
 // dynamic LDS the body needs for one network

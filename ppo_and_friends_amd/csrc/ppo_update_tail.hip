@@ -35,24 +35,69 @@ constexpr int kTailMaxE = 9;                  // output segment: up to 9 element
 // bookkeeping workgroup left them in the control block while it waited (two double pow: ~2 us of one wave); computed
 // here only when the block holds another step's (first launch, restored state).
 struct TailBc { long long t; double bc1, bc2s; };
-__device__ __forceinline__ TailBc tail_bc_load(const UpdateDev& u, const TailDev& td, const int which) {
-    // read at the START of the workgroup: the bookkeeping workgroup rewrites these words only after every workgroup has
-    // published its record, i.e. after all of these reads
-    TailBc r;
-    r.t = td.ctl->bc_t[which];
-    r.bc1 = td.ctl->bc[2 * which];
-    r.bc2s = td.ctl->bc[2 * which + 1];
+
+// What a job workgroup reads of the words the bookkeeping workgroup rewrites: the launch tag's source, the network's Adam
+// step, the learning rate and the control block's bias corrections.  The ordering contract: these words are READ (the
+// load is issued and its value latched) before this workgroup publishes its record; the bookkeeping workgroup rewrites
+// them only after every record carries the launch's tag, i.e. after all of these reads.
+// Request and use are apart on purpose.  tail_pre_request comes right BEHIND the job's state and operand loads: a wave's
+// loads retire in order, so nothing the MFMA phase waits for queues behind these words, and they have the whole MFMA and
+// fold phases to land.  tail_pre_use (behind the fold, in front of wave 0's tail_publish) is where their first arithmetic
+// happens -- the tag's mask and + 1, the step's + 1, the test against bc_t.  Left to itself the compiler hoists that cheap
+// arithmetic up to the loads and plants a full wait with it, a cold round trip with nothing else in flight ahead of the
+// first operand request (two of them, 3.7 k cycles, before this split); the empty asm is what pins the first use down.
+// EVERY wave passes tail_pre_use, although only wave 0 has a use for the words: a load that some path never consumes
+// stays "in flight" in the compiler's wait bookkeeping up to the end of that arm of tail_job, and the arms -- which
+// exclude each other -- follow one another in the compiled text: the other arm's first write to one of those registers
+// then got a `vmcnt` wait sized for THIS arm's history, which on its own history meant "everything requested so far"
+// (a full round trip between the first and the second chunk of operand requests).
+// The loads are relaxed atomics so that they stay where they are written: `seq` at agent scope (`sc1`, as the record
+// traffic), the others at workgroup scope (plain loads, as before).
+// ONE_TRIP (kTailOneTrip: both networks at most 128 wide) is the flavour that does all of this.  With a 256-wide network
+// (369 workgroups at C4, two to three per CU) the same launch measured SLOWER that way in every order of requests tried
+// (`<128,256>`: 10.2 - 10.9 us against 9.6), so those instantiations keep the words' loads at the start of the workgroup
+// (tail_pre_load) and plain state loads, as they were.
+constexpr bool kTailOneTrip(const int ha, const int hc) { return ha <= 128 && hc <= 128; }
+struct TailPre { unsigned long long seq; long long t; float lr; TailBc bc; };
+// !ONE_TRIP: read at the START of the workgroup (`seq` by the kernel, before it branches)
+__device__ __forceinline__ TailPre tail_pre_load(const UpdateDev& u, const TailDev& td, const int which, const unsigned long long seq) {
+    TailPre r;
+    r.seq = seq;
+    r.t = (long long)u.step_counts[which];
+    r.lr = u.lr[0];
+    r.bc.t = td.ctl->bc_t[which];
+    r.bc.bc1 = td.ctl->bc[2 * which];
+    r.bc.bc2s = td.ctl->bc[2 * which + 1];
     return r;
+}
+__device__ __forceinline__ TailPre tail_pre_request(const UpdateDev& u, const TailDev& td, const int which) {
+    TailPre r;
+    r.seq = __hip_atomic_load(&td.ctl->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    r.t = __hip_atomic_load(&u.step_counts[which], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    r.lr = __hip_atomic_load(&u.lr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    r.bc.t = __hip_atomic_load(&td.ctl->bc_t[which], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    r.bc.bc1 = __hip_atomic_load(&td.ctl->bc[2 * which], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    r.bc.bc2s = __hip_atomic_load(&td.ctl->bc[2 * which + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return r;
+}
+__device__ __forceinline__ TailPre tail_pre_use(TailPre r) {
+    asm volatile("" : "+v"(r.seq), "+v"(r.t), "+v"(r.lr), "+v"(r.bc.t), "+v"(r.bc.bc1), "+v"(r.bc.bc2s));
+    return r;
+}
+__device__ __forceinline__ unsigned tail_tag(const unsigned long long seq) {
+    return ((unsigned)seq & 0x7fffffffu) + 1u;                 // never 0: a zero-initialised record is never current
 }
 
 // Wave 0 of the workgroup (all 64 lanes), q = the workgroup's squared-norm partial: publish, wait for everybody's, and
 // leave the step's clip / Adam coefficients (ppo_update_adam_kernel's, expression for expression) in s_coef.
-__device__ __forceinline__ void tail_sync_wave0(const UpdateDev& u, const TailDev& td, const unsigned tag, const int b, const int which,
-                                                const long long t_next, const TailBc& pre, const float lr, const double q,
-                                                float* s_coef) {
+__device__ __forceinline__ void tail_sync_wave0(const UpdateDev& u, const TailDev& td, const int b, const int which,
+                                                const TailPre& pre /* tail_pre_use's */, const double q, float* s_coef) {
+    const unsigned tag = tail_tag(pre.seq);
+    const long long t_next = pre.t + 1;
+    const float lr = pre.lr;
     if (threadIdx.x == 0) tail_publish(td, tag, b, q);
-    double bc1 = pre.bc1, bc2s = pre.bc2s;
-    if (pre.t != t_next) {                                    // uniform
+    double bc1 = pre.bc.bc1, bc2s = pre.bc.bc2s;
+    if (pre.bc.t != t_next) {                                 // uniform
         bc1 = 1.0 - pow((double)u.beta1, (double)t_next);
         bc2s = sqrt(1.0 - pow((double)u.beta2, (double)t_next));
     }
@@ -81,6 +126,14 @@ __device__ __forceinline__ void tail_sync_wave0(const UpdateDev& u, const TailDe
 constexpr int kTailTileFloats = 528;          // 16 x 32 tile + 16 bias sums
 struct TailXchg { XchgDev x; long long seq, wait_ticks; long seg_base[2]; };
 
+// xchg_sequence for a job: requested behind the job's operands, its + 1 pinned there (the same hoisting as tail_pre_use's
+// words: the add would otherwise drag a full wait in front of the first operand request).  Only this workgroup's own
+// thread 0 ever writes group_seq[g] (xchg_advance, at the end of the job).
+__device__ __forceinline__ long long tail_xchg_sequence(const TailXchg& c, const unsigned g) {
+    long long v = c.x.group_seq[g];
+    asm volatile("" : "+v"(v));
+    return v + 1;
+}
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tail_slot_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xFFFFFFFF, 0x00020000);
 }
@@ -159,10 +212,27 @@ __device__ __forceinline__ float tail_xchg_sum1(const TailXchg& c, const long of
     return acc;
 }
 
+// Optimiser state of bucket element idx, through buffer descriptors on the three arrays: ONE 32-bit offset register per
+// element, which stays live (the step's stores need the index again).  As plain global loads every request built a
+// 64-bit address pair, the pairs were reused for the next element's addresses, and the compiler holds a write to the
+// address registers of a load in flight back until that load has returned: the state requests waited for one another,
+// and the first operand request for all of them -- a serial round trip ahead of the operands.  (4 * idx < 2^32: checked
+// on the host, tail_prepare.)  tail_pmv_hold, behind the job's last request, is what keeps those offset registers from
+// being handed to something else while the loads are in flight.
 struct TailPmv { float p, m, v; };
+__device__ __forceinline__ unsigned tail_pmv_off(const long idx) { return 4u * (unsigned)idx; }
+__device__ __forceinline__ void tail_pmv_hold(const unsigned off) { asm volatile("" :: "v"(off)); }
+template <bool ONE_TRIP>
 __device__ __forceinline__ TailPmv tail_pmv_load(const UpdateDev& u, const long idx, const bool ok) {
     TailPmv r = {0.f, 0.f, 0.f};
-    if (ok) { r.p = u.params[idx]; r.m = u.exp_avg[idx]; r.v = u.exp_avg_sq[idx]; }
+    if constexpr (!ONE_TRIP) {
+        if (ok) { r.p = u.params[idx]; r.m = u.exp_avg[idx]; r.v = u.exp_avg_sq[idx]; }
+    } else if (ok) {
+        const unsigned off = tail_pmv_off(idx);
+        r.p = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(tail_slot_rsrc(u.params), off, 0, 0));
+        r.m = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(tail_slot_rsrc(u.exp_avg), off, 0, 0));
+        r.v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(tail_slot_rsrc(u.exp_avg_sq), off, 0, 0));
+    }
     return r;
 }
 // ppo_update_adam_kernel's step on one element (-ffp-contract=off: the same roundings)
@@ -180,10 +250,10 @@ __device__ __forceinline__ void tail_adam1(const UpdateDev& u, const long idx, c
 // The 16 x 32 output tile is formed by wave 0 (C layout) and handed to ALL 256 threads through LDS for the optimiser
 // step: thread t owns tile elements t and t + 256 (row e / 32, column e % 32: whole 128-byte lines of p / m / v), whose
 // state it requested at the start of the job, beside the MFMA operands.
-template <int H, bool XCHG>
-__device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, const unsigned tag, const int b, const int which,
+template <int H, bool XCHG, bool ONE_TRIP>
+__device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, const unsigned long long seq0, const int b, const int which,
                                          const int job, float* sFold /* [3][2][256] + [4][16] */, float* sTile /* [16][32] + [16] */,
-                                         double* s_red, float* s_coef, const TailXchg* xc) {
+                                         double* s_red, float* s_coef, TailXchg* xc) {
     constexpr int MAXC = 8;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -198,15 +268,13 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
     };
     const long nb = nd.offset;                                 // this network's first float in the bucket
     float* G = u.grads + nb;
-    // read BEFORE this workgroup publishes (the bookkeeping workgroup rewrites them after everybody has)
-    const long long t_next = (long long)u.step_counts[which] + 1;
-    const float lr = u.lr[0];
-    const TailBc pre = tail_bc_load(u, td, which);
     constexpr int t = H / 16, t2 = (t + 1) / 2;
     const int n_it0 = (in_dim + 15) / 16, p0 = (n_it0 + 1) / 2;
     const int n_hidden = (depth - 1) * t * t2, n_l0 = t * p0;
     const float sc = u.grad_scale;
     double q = 0.0;
+    TailPre pre;
+    if constexpr (!ONE_TRIP) pre = tail_pre_load(u, td, which, seq0);
     TAIL_STAMP(td, 0);
     if (job < n_hidden + n_l0) {
         int l, ot, itile, n_it;
@@ -224,11 +292,11 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
             const int i = itile * 16 + col;
             eok[k] = (col < 16 || two) && i < ldw;
             eidx[k] = nb + offW(l) + (long)(ot * 16 + row) * ldw + i;
-            se[k] = tail_pmv_load(u, eidx[k], eok[k]);
+            se[k] = tail_pmv_load<ONE_TRIP>(u, eidx[k], eok[k]);
         }
         const bool has_b = itile == 0 && tid >= 64 && tid < 80;
         const long bidx = nb + offB(l) + ot * 16 + (tid - 64);
-        sb = tail_pmv_load(u, bidx, has_b);
+        sb = tail_pmv_load<ONE_TRIP>(u, bidx, has_b);
         const long ldx = l >= 1 ? H : 64;
         const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(u.sp.dbuf[which] + (long)l * plane, 0, 0xFFFFFFFF, 0x00020000);
         const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
@@ -251,6 +319,14 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
                     if (two) x1[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl + 64u, sx, 0));
                 }
             }
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) if constexpr (ONE_TRIP) tail_pmv_hold(tail_pmv_off(eidx[k]));
+        if constexpr (ONE_TRIP) tail_pmv_hold(tail_pmv_off(bidx));
+        // behind the operands: the control words (read before this workgroup publishes) and the exchange's sequence number
+        if constexpr (ONE_TRIP) {
+            pre = tail_pre_request(u, td, which);
+            if (XCHG) xc->seq = tail_xchg_sequence(*xc, (unsigned)b);
         }
         TAIL_STAMP(td, 1);
         tail_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -316,6 +392,7 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
                 if (lane < 16) bg = sTile[512 + lane];
             }
         }
+        const TailPre got = ONE_TRIP ? tail_pre_use(pre) : pre;   // every wave: see tail_pre_use
         if (wave == 0) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -327,7 +404,7 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
             // block_sum(q) of the chain's wgrad launch: only this wave contributes, and its wave sum + three zeros is exact
             q = tail_wave_sum(q);
             TAIL_STAMP(td, 4);
-            tail_sync_wave0(u, td, tag, b, which, t_next, pre, lr, q, s_coef);
+            tail_sync_wave0(u, td, b, which, got, q, s_coef);
         }
         __syncthreads();                                      // s_coef and sTile are visible
         TAIL_STAMP(td, 5);
@@ -352,8 +429,12 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
 #pragma unroll
         for (int k = 0; k < kTailMaxE; ++k) {
             const long idx = tid + (long)kWgradThreads * k;
-            se[k] = tail_pmv_load(u, nb + seg_off + idx, idx < seg_len);
+            se[k] = tail_pmv_load<ONE_TRIP>(u, nb + seg_off + idx, idx < seg_len);
             ge[k] = 0.f;
+        }
+        if constexpr (ONE_TRIP) {                             // behind the state loads, as in the tile jobs
+            pre = tail_pre_request(u, td, which);
+            if (XCHG) xc->seq = tail_xchg_sequence(*xc, (unsigned)b);
         }
 #pragma unroll
         for (int k = 0; k < kTailMaxE; ++k) {
@@ -395,9 +476,10 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
         q = tail_wave_sum(q);
         if (lane == 0) s_red[wave] = q;
         __syncthreads();
+        const TailPre got = ONE_TRIP ? tail_pre_use(pre) : pre;   // every wave: see tail_pre_use
         if (wave == 0) {
             q = tail_wave_sum(lane < 4 ? s_red[lane] : 0.0);
-            tail_sync_wave0(u, td, tag, b, which, t_next, pre, lr, q, s_coef);
+            tail_sync_wave0(u, td, b, which, got, q, s_coef);
         }
         __syncthreads();
         const TailCoef cf = {s_coef[0], s_coef[1], s_coef[2]};
@@ -415,12 +497,15 @@ __global__ __launch_bounds__(kWgradThreads) void ppo_update_wgrad_adam_kernel(Up
     __shared__ __attribute__((aligned(16))) float s_fold[6 * 256 + 64];
     __shared__ float s_tile[16 * 32 + 16];
     __shared__ float s_coef[4];
+    constexpr bool ONE_TRIP = kTailOneTrip(HA, HC);
     const int b = blockIdx.x;
-    const unsigned long long seq = __hip_atomic_load(&td.ctl->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned tag = ((unsigned)seq & 0x7fffffffu) + 1u;              // never 0: a zero-initialised record is never current
-    if (b == td.nblk) {
+    unsigned long long seq0 = 0;
+    if constexpr (!ONE_TRIP) seq0 = __hip_atomic_load(&td.ctl->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (b == td.nblk) {                                       // (needs no loaded value: ONE_TRIP's job workgroups go straight to their requests)
         // bookkeeping: the totals need nobody; what other workgroups read at their start moves only after all have published
         if (threadIdx.x >= 64) return;
+        const unsigned long long seq = ONE_TRIP ? __hip_atomic_load(&td.ctl->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : seq0;
+        const unsigned tag = tail_tag(seq);
         ppo_update_bookkeeping_totals(u);
         // while the others work: the bias corrections of the step being taken (norm_scratch, as ppo_update_bookkeeping_steps
         // leaves them) and of the NEXT step (control block: the next launch's workgroups need not compute them)
@@ -451,10 +536,11 @@ __global__ __launch_bounds__(kWgradThreads) void ppo_update_wgrad_adam_kernel(Up
     }
     const int job = (b & 7) * td.per_xcd + (b >> 3);          // XCD b % 8 works on one run of the layer-major job list
     const bool live = job < td.jobs_a + td.jobs_c;            // the same on every rank
-    if (XCHG && live) xc.seq = xchg_sequence(xc.x, (unsigned)b);
-    if (job < td.jobs_a) tail_job<HA, XCHG>(u, td, tag, b, 0, job, s_fold, s_tile, s_red, s_coef, &xc);
-    else if (live) tail_job<HC, XCHG>(u, td, tag, b, 1, job - td.jobs_a, s_fold, s_tile, s_red, s_coef, &xc);
-    else if (threadIdx.x == 0) tail_publish(td, tag, b, 0.0);
+    if (XCHG && !ONE_TRIP && live) xc.seq = xchg_sequence(xc.x, (unsigned)b);
+    if (job < td.jobs_a) tail_job<HA, XCHG, ONE_TRIP>(u, td, seq0, b, 0, job, s_fold, s_tile, s_red, s_coef, &xc);   // (XCHG, ONE_TRIP: sets xc.seq)
+    else if (live) tail_job<HC, XCHG, ONE_TRIP>(u, td, seq0, b, 1, job - td.jobs_a, s_fold, s_tile, s_red, s_coef, &xc);
+    else if (threadIdx.x == 0)
+        tail_publish(td, tail_tag(ONE_TRIP ? __hip_atomic_load(&td.ctl->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : seq0), b, 0.0);
     if (XCHG && live) xchg_advance(xc.x, xc.seq, (unsigned)b);
 }
 
@@ -494,6 +580,8 @@ static int tail_prepare(const ppoaf_ppo_update_args_t* args, void* ctl, double w
     PPOAF_REQUIRE(u.split, "ppo_update_wgrad_adam: args->split_workspace is not set (the tail of the split-wgrad chain)");
     PPOAF_REQUIRE(ctl && (((uintptr_t)ctl) & 63) == 0, "ppo_update_wgrad_adam: control block missing or not 64-byte aligned");
     PPOAF_REQUIRE(wait_seconds > 0.0 && wait_seconds <= 600.0, "ppo_update_wgrad_adam: wait_seconds=%g", wait_seconds);
+    PPOAF_REQUIRE(u.bucket_total < (1L << 30), "ppo_update_wgrad_adam: bucket of %ld floats (32-bit byte offsets: fewer than 2^30)",
+                  (long)u.bucket_total);
     td.ctl = reinterpret_cast<TailCtl*>(ctl);
     td.budget = (long long)(wait_seconds * 1.0e8);
     td.jobs_a = split_wgrad_jobs(u.net[0]);
