@@ -495,6 +495,59 @@ int ppoaf_policy_step(const ppoaf_policy_step_args_t* args, ppoaf_stream_t strea
 
 
 /* ------------------------------------------------------------------------ *
+ * K19  one evaluation step for all E rows in one launch (actor only)
+ * replaces PPOPolicy.get_inference_actions          policies/ppo_policy.py:796-889
+ *          (under PPO.get_inference_actions         ppo.py:896-1028, the step of testing.py:8-175)
+ *          refine_prediction of the distributions   networks/distributions.py:177-196 (Bernoulli),
+ *                                                   :262-263 (categorical), :404-436 (multi-categorical),
+ *                                                   :580-581,611-631 (Gaussian: tanh + distribution_min/max rescale)
+ * Actor MLP forward (the tile code K6 runs: csrc/mlp_device.hpp, mlp_rows_forward) -> head -> the ENVIRONMENT
+ * action of every row.  ceil(E/16) workgroups of 512 threads.  obs: [E, in_dim] float32.  action_out in K6's
+ * layouts: [E] int64 (categorical), [E,D] float32 (Gaussian), [E,D] int64 (multi-categorical), [E,n] float32 0 / 1
+ * (Bernoulli).  mode:
+ *   PPOAF_INFER_SAMPLE         K6's sampling with K6's Philox counters: for equal (obs, params, seed, offset) the
+ *                              action is bitwise ppoaf_policy_step's action_out
+ *   PPOAF_INFER_DETERMINISTIC  argmax (lowest index on an exact tie), argmax per slice, z >= 0 per bit, tanh(mean)
+ *                              rescaled into [act_lo, act_hi]; seed / offset are not read
+ * No log-prob, no value, no observation copies.  Shapes as K6: hidden width 32 / 64 / 128 / 256, out_dim <= 8.
+ * ------------------------------------------------------------------------ */
+#define PPOAF_INFER_SAMPLE        0
+#define PPOAF_INFER_DETERMINISTIC 1
+
+typedef struct {
+    ppoaf_mlp_desc_t actor;
+    const float* params;
+    const float* obs; int64_t E;
+    int32_t head_kind; int32_t mode;
+    float min_std;
+    int32_t n_action_slices;                    /* PPOAF_HEAD_MULTI_CATEGORICAL only, as in ppoaf_policy_step_args_t */
+    int32_t action_slices[8];
+    const float* act_lo; const float* act_hi;   /* Gaussian head: bounds per action dimension; both NULL = [-1,1] */
+    uint64_t seed, offset;
+    void* action_out;
+} ppoaf_policy_infer_args_t;
+
+int ppoaf_policy_infer(const ppoaf_policy_infer_args_t* args, ppoaf_stream_t stream);
+
+/* Score bookkeeping of an evaluation (testing.py:59-112) for E environments in parallel, one small launch per env
+ * step, nothing read by the host.  Row e owes quota[e] episodes (N // E + (e < N % E) of N test runs: "the first N
+ * to finish" would be the SHORTEST episodes).  While count[e] < quota[e] the row adds score[e] (float32: the natural
+ * reward when the env reports one, else the reward, testing.py:88-91) to run_score[e] and 1 to run_len[e]; where
+ * done[e] (terminated | truncated, one byte per row) it then folds the episode into count / sum / min / max / steps,
+ * clears the running pair and takes 1 off *remaining (one atomic add per finishing row).  A row that has met its quota
+ * is left alone, so surplus steps change nothing.  Sums are float64 adds in step order.  The caller initialises
+ * run_score = sum = 0, run_len = count = steps = 0, min = +inf, max = -inf, *remaining = N. */
+typedef struct {
+    const float* score; const uint8_t* done; const int32_t* quota; int64_t E;
+    double* run_score; int64_t* run_len;
+    int64_t* count; double* sum; double* min; double* max; int64_t* steps;
+    int32_t* remaining;
+} ppoaf_eval_scores_args_t;
+
+int ppoaf_eval_scores_step(const ppoaf_eval_scores_args_t* args, ppoaf_stream_t stream);
+
+
+/* ------------------------------------------------------------------------ *
  * K8  ICM forward-model loss and intrinsic reward
  * replaces the tail of ICM.forward  networks/ppo_networks/icm.py:421-430
  *   intr[i]  = (reward_scale / 2) * sum_d (pred[i,d] - enc2[i,d])^2

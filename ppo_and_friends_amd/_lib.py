@@ -88,6 +88,23 @@ class PolicyStepArgs(C.Structure):
                 ("n_action_slices", C.c_int32), ("action_slices", C.c_int32 * 8)]
 
 
+class PolicyInferArgs(C.Structure):
+    """ppoaf_policy_infer_args_t (include/ppoaf_hip.h)."""
+    _fields_ = [("actor", MlpDesc), ("params", C.c_void_p), ("obs", C.c_void_p), ("E", C.c_int64),
+                ("head_kind", C.c_int32), ("mode", C.c_int32), ("min_std", C.c_float),
+                ("n_action_slices", C.c_int32), ("action_slices", C.c_int32 * 8),
+                ("act_lo", C.c_void_p), ("act_hi", C.c_void_p),
+                ("seed", C.c_uint64), ("offset", C.c_uint64), ("action_out", C.c_void_p)]
+
+
+class EvalScoresArgs(C.Structure):
+    """ppoaf_eval_scores_args_t (include/ppoaf_hip.h)."""
+    _fields_ = [("score", C.c_void_p), ("done", C.c_void_p), ("quota", C.c_void_p), ("E", C.c_int64),
+                ("run_score", C.c_void_p), ("run_len", C.c_void_p),
+                ("count", C.c_void_p), ("sum", C.c_void_p), ("min", C.c_void_p), ("max", C.c_void_p),
+                ("steps", C.c_void_p), ("remaining", C.c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/ppoaf_hip.h one to one.
 class IcmUpdateArgs(C.Structure):
     """ppoaf_icm_update_args_t (include/ppoaf_hip.h) -- field order must match the header."""
@@ -219,6 +236,8 @@ SIGNATURES = {
     "ppoaf_mat_attention_bwd": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, C.c_int64, C.c_int32, C.c_int32,
                                           _ptr, _ptr, _ptr, _ptr]),
     "ppoaf_policy_step": (C.c_int, [C.POINTER(PolicyStepArgs), _ptr]),
+    "ppoaf_policy_infer": (C.c_int, [C.POINTER(PolicyInferArgs), _ptr]),
+    "ppoaf_eval_scores_step": (C.c_int, [C.POINTER(EvalScoresArgs), _ptr]),
     "ppoaf_minibatch_moments": (C.c_int, [_ptr, _ptr, _ptr, C.c_int64, C.c_int64, _ptr, _ptr]),
     "ppoaf_icm_update_fwd_bwd": (C.c_int, [C.POINTER(IcmUpdateArgs), _ptr]),
     "ppoaf_icm_update_reduce": (C.c_int, [C.POINTER(IcmUpdateArgs), _ptr]),

@@ -39,6 +39,62 @@ inline int check_action_head(const char* what, int head_kind, const ppoaf_mlp_de
     return PPOAF_OK;       // (Bernoulli: one bit per actor output; out_dim <= 8 is checked with the network)
 }
 
+// ---- sampling pieces shared by the rollout step (K6) and the evaluation step (K19, policy_infer.hip): one copy, so
+// that a sampled evaluation action is bitwise the rollout's for the same (outputs, seed, counter)
+// Discrete: softmax of the row's <= 8 outputs -> p (padding classes 0); returns the sum of p (Categorical's own
+// renormaliser, ~1)
+__device__ __forceinline__ float cat_probs(const float* z, const int out_dim, float* p) {
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (k < out_dim) m = fmaxf(m, z[k]);
+    float ssum = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { p[k] = k < out_dim ? expf(z[k] - m) : 0.f; ssum += p[k]; }
+    const float inv = 1.0f / ssum;
+    float s2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { p[k] *= inv; s2 += p[k]; }
+    return s2;
+}
+// the row with Philox counter `ctr` draws (seed, ctr, 0).x and takes the inverse CDF over the unnormalised mass
+__device__ __forceinline__ int cat_sample(const float* p, const float s2, const int out_dim,
+                                          const unsigned long long seed, const unsigned long long ctr) {
+    int a = out_dim - 1;
+    float c = 0.f;
+    const Philox4 rnd = philox4x32_10(seed, ctr, 0u);
+    const float uu = u32_to_unit(rnd.x) * s2;
+    bool found = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if (k < out_dim) {
+            c += p[k];
+            if (!found && uu < c) { a = k; found = true; }
+        }
+    }
+    return a;
+}
+// Box: four standard normals (Box-Muller on the Philox block (seed, ctr, q)) for action dimensions 4 q .. 4 q + 3
+__device__ __forceinline__ void gauss_normals4(const unsigned long long seed, const unsigned long long ctr,
+                                               const uint32_t q, float* z) {
+    const Philox4 r = philox4x32_10(seed, ctr, q);
+    const float u0 = u32_to_unit_open0(r.x), u1 = u32_to_unit(r.y);
+    const float u2 = u32_to_unit_open0(r.z), u3 = u32_to_unit(r.w);
+    const float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
+    float sa, ca, sb, cb;
+    sincosf(6.28318530717958647692f * u1, &sa, &ca);
+    sincosf(6.28318530717958647692f * u3, &sb, &cb);
+    z[0] = ra * ca; z[1] = ra * sa; z[2] = rb * cb; z[3] = rb * sb;
+}
+// a squashed action in [-1, 1] -> [lo, hi]                                          distributions.py:580-581
+__device__ __forceinline__ float unit_to_bounds(float a, float lo, float hi) { return ((a + 1.0f) / 2.0f) * (hi - lo) + lo; }
+// MultiBinary: the uniform of bit d = component d % 4 of Philox (seed, ctr, d / 4); r carries the block from bit to bit
+__device__ __forceinline__ float bern_uniform(const unsigned long long seed, const unsigned long long ctr, const int d,
+                                              Philox4& r) {
+    if ((d & 3) == 0) r = philox4x32_10(seed, ctr, (uint32_t)(d >> 2));
+    const uint32_t w = (d & 3) == 0 ? r.x : ((d & 3) == 1 ? r.y : ((d & 3) == 2 ? r.z : r.w));
+    return u32_to_unit(w);
+}
+
 // ---- MultiDiscrete
 // bit k set where class k opens a slice; every class from sum(nvec) on opens one of its own, so no slice runs into padding
 __device__ __forceinline__ unsigned mcat_starts(const int n_slices, const int* nvec) {

@@ -444,6 +444,110 @@ __device__ __forceinline__ void layer_wgrad(const float* __restrict__ D, const f
     }
 }
 
+// ---- the 16-row MLP forward of the rollout step (K6, policy_step.hip) and of the evaluation step (K19,
+// policy_infer.hip): one workgroup of kThreadsU threads takes rows [e0, e0 + 16) of `src` ([E, in_dim]) through the
+// network `nd` of the bucket `params` -- first layer (K = in_dim, zero padded) / hidden layers (same tile code as the
+// update's forward) / output layer (<= 8 outputs, 16 lanes per row) -- and leaves the outputs in LDS: returns
+// sOut[16][kMaxOut], valid after the function's last barrier.  Both kernels instantiate THIS code, so a row's outputs
+// are bitwise the same in both.  `cpy` (may be NULL): the observation rows are copied there on the way in.
+// smem: mlp_rows_forward_lds_floats(nd) floats of dynamic LDS, 16-byte aligned.
+template <int HT>
+__device__ __forceinline__ const float* mlp_rows_forward(const NetDev& nd, const float* __restrict__ params,
+                                                         const float* __restrict__ src, float* __restrict__ cpy,
+                                                         const long E, const long e0, float* smem) {
+    constexpr int H = 16 * HT, HS = H + 4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int in_dim = nd.in_dim, depth = nd.depth, out_dim = nd.out_dim, act = nd.act;
+    const int NT0 = (in_dim + 15) >> 4, INP = 16 * NT0 + 4;
+    const float* P = params + nd.offset;
+    const long szW0 = ((long)H * in_dim + 3) & ~3L;
+    auto offW = [&](int l) -> long { return l == 0 ? 0 : szW0 + H + (long)(l - 1) * (H * H + H); };
+    auto offB = [&](int l) -> long {
+        return l == 0 ? szW0 : offW(l) + (l < depth ? (long)H * H : (((long)out_dim * H + 3) & ~3L));
+    };
+
+    float* sBias = smem;                                   // [(depth+1), H]
+    float* sWout = sBias + (depth + 1) * H;                // [8, H]
+    float* sX = sWout + 8 * H;                             // [16, INP]
+    float* sH0 = sX + kRows * INP;                         // [16, HS] ping
+    float* sH1 = sH0 + kRows * HS;                         // [16, HS] pong
+    float* sOut = sH1 + kRows * HS;                        // [16, 16]
+
+    for (int l = 0; l <= depth; ++l) {
+        const int n = (l == depth) ? out_dim : H;
+        const float* bb = P + offB(l);
+        for (int i = tid; i < n; i += kThreadsU) sBias[l * H + i] = bb[i];
+    }
+    for (int i = tid; i < out_dim * H; i += kThreadsU) sWout[i] = P[offW(depth) + i];
+    for (int idx = tid; idx < kRows * INP; idx += kThreadsU) {
+        const int s = idx / INP, i = idx - s * INP;
+        float x = 0.f;
+        if (i < in_dim && e0 + s < E) {
+            x = src[(e0 + s) * in_dim + i];
+            if (cpy) cpy[(e0 + s) * in_dim + i] = x;
+        }
+        sX[idx] = x;
+    }
+    float4 fr[HT];
+    if (depth > 1 && wave < HT) load_fwd_frags<HT>(P + offW(1), wave * 16, lane, fr);
+    __syncthreads();
+
+    // first layer (K = in_dim, zero padded)
+    for (int nt = wave; nt < HT; nt += kNW) {
+        const int o = nt * 16 + (lane & 15);
+        const float bv = sBias[o];
+        f32x4 acc = {bv, bv, bv, bv};
+        const float* w = P + offW(0) + (long)o * in_dim;
+        const float* arow = sX + (lane & 15) * INP;
+        for (int k0 = 0; k0 < in_dim; k0 += 16) {
+            float bq[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = k0 + 4 * j + (lane >> 4);
+                bq[j] = k < in_dim ? w[k] : 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[k0 + 4 * j + (lane >> 4)], bq[j], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sH0[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
+    }
+    __syncthreads();
+    float* Hp = sH0;
+    float* Hc = sH1;
+    for (int l = 1; l < depth; ++l) {
+        for (int nt = wave; nt < HT; nt += kNW) {
+            if (nt != wave) load_fwd_frags<HT>(P + offW(l), nt * 16, lane, fr);
+            const int o = nt * 16 + (lane & 15);
+            const f32x4 acc = mfma_rows_x_frags<HT>(Hp, HS, lane, fr, sBias[l * H + o]);
+            if (nt + kNW >= HT && l + 1 < depth) load_fwd_frags<HT>(P + offW(l + 1), wave * 16, lane, fr);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
+        }
+        __syncthreads();
+        float* t = Hp; Hp = Hc; Hc = t;
+    }
+    // output layer
+    if (tid < 256) {
+        const int s = tid >> 4, part = tid & 15;
+        for (int k = 0; k < out_dim; ++k) {
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < HT; ++i) acc = fmaf(Hp[s * HS + part + 16 * i], sWout[k * H + part + 16 * i], acc);
+            acc = group16_sum(acc);
+            if (part == 0) sOut[s * kMaxOut + k] = acc + sBias[depth * H + k];
+        }
+    }
+    __syncthreads();
+    return sOut;
+}
+// host: the floats of LDS mlp_rows_forward takes for this network
+inline size_t mlp_rows_forward_lds_floats(const NetDev& n) {
+    const size_t HS = n.H + 4, INP = 16 * ((n.in_dim + 15) / 16) + 4;
+    return (size_t)(n.depth + 1) * n.H + 8 * (size_t)n.H + kRows * INP + 2 * kRows * HS + kRows * kMaxOut;
+}
+
 // host: validate a network descriptor and fill the device view
 int fill_net(const ppoaf_mlp_desc_t& d, NetDev& n, const char* what);
 

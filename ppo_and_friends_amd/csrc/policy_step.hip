@@ -13,8 +13,7 @@
 
 namespace ppoaf {
 
-constexpr int kNWs = 8;
-constexpr int kThreadsS = 64 * kNWs;
+constexpr int kThreadsS = kThreadsU;
 
 struct StepDev {
     NetDev net[2];
@@ -37,98 +36,15 @@ extern __shared__ __attribute__((aligned(16))) unsigned char policy_step_smem[];
 // Gaussian ones keep their registers)
 template <int HT, bool XH>
 __device__ __forceinline__ void policy_step_body(const StepDev& u, const int which, const int g) {
-    constexpr int H = 16 * HT, HS = H + 4;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const NetDev& nd = u.net[which];
-    const int in_dim = nd.in_dim, depth = nd.depth, out_dim = nd.out_dim, act = nd.act;
-    const int NT0 = (in_dim + 15) >> 4, INP = 16 * NT0 + 4;
+    const int out_dim = nd.out_dim;
     const float* P = u.params + nd.offset;
-    const long szW0 = ((long)H * in_dim + 3) & ~3L;
-    auto offW = [&](int l) -> long { return l == 0 ? 0 : szW0 + H + (long)(l - 1) * (H * H + H); };
-    auto offB = [&](int l) -> long {
-        return l == 0 ? szW0 : offW(l) + (l < depth ? (long)H * H : (((long)out_dim * H + 3) & ~3L));
-    };
     const long e0 = (long)g * kRows;
-
-    float* smem = reinterpret_cast<float*>(policy_step_smem);
-    float* sBias = smem;                                   // [(depth+1), H]
-    float* sWout = sBias + (depth + 1) * H;                // [8, H]
-    float* sX = sWout + 8 * H;                             // [16, INP]
-    float* sH0 = sX + kRows * INP;                         // [16, HS] ping
-    float* sH1 = sH0 + kRows * HS;                         // [16, HS] pong
-    float* sOut = sH1 + kRows * HS;                        // [16, 16]
-
-    for (int l = 0; l <= depth; ++l) {
-        const int n = (l == depth) ? out_dim : H;
-        const float* bb = P + offB(l);
-        for (int i = tid; i < n; i += kThreadsS) sBias[l * H + i] = bb[i];
-    }
-    for (int i = tid; i < out_dim * H; i += kThreadsS) sWout[i] = P[offW(depth) + i];
-    {
-        const float* src = which == 0 ? u.obs : u.critic_obs;
-        float* cpy = which == 0 ? u.obs_out : u.critic_obs_out;
-        for (int idx = tid; idx < kRows * INP; idx += kThreadsS) {
-            const int s = idx / INP, i = idx - s * INP;
-            float x = 0.f;
-            if (i < in_dim && e0 + s < u.E) {
-                x = src[(e0 + s) * in_dim + i];
-                if (cpy) cpy[(e0 + s) * in_dim + i] = x;
-            }
-            sX[idx] = x;
-        }
-    }
-    float4 fr[HT];
-    if (depth > 1 && wave < HT) load_fwd_frags<HT>(P + offW(1), wave * 16, lane, fr);
-    __syncthreads();
-
-    // first layer (K = in_dim, zero padded)
-    for (int nt = wave; nt < HT; nt += kNWs) {
-        const int o = nt * 16 + (lane & 15);
-        const float bv = sBias[o];
-        f32x4 acc = {bv, bv, bv, bv};
-        const float* w = P + offW(0) + (long)o * in_dim;
-        const float* arow = sX + (lane & 15) * INP;
-        for (int k0 = 0; k0 < in_dim; k0 += 16) {
-            float bq[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = k0 + 4 * j + (lane >> 4);
-                bq[j] = k < in_dim ? w[k] : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[k0 + 4 * j + (lane >> 4)], bq[j], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sH0[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
-    }
-    __syncthreads();
-    float* Hp = sH0;
-    float* Hc = sH1;
-    for (int l = 1; l < depth; ++l) {
-        for (int nt = wave; nt < HT; nt += kNWs) {
-            if (nt != wave) load_fwd_frags<HT>(P + offW(l), nt * 16, lane, fr);
-            const int o = nt * 16 + (lane & 15);
-            const f32x4 acc = mfma_rows_x_frags<HT>(Hp, HS, lane, fr, sBias[l * H + o]);
-            if (nt + kNWs >= HT && l + 1 < depth) load_fwd_frags<HT>(P + offW(l + 1), wave * 16, lane, fr);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
-        }
-        __syncthreads();
-        float* t = Hp; Hp = Hc; Hc = t;
-    }
-    // output layer
-    if (tid < 256) {
-        const int s = tid >> 4, part = tid & 15;
-        for (int k = 0; k < out_dim; ++k) {
-            float acc = 0.f;
-#pragma unroll
-            for (int i = 0; i < HT; ++i) acc = fmaf(Hp[s * HS + part + 16 * i], sWout[k * H + part + 16 * i], acc);
-            acc = group16_sum(acc);
-            if (part == 0) sOut[s * kMaxOut + k] = acc + sBias[depth * H + k];
-        }
-    }
-    __syncthreads();
+    // the forward K19 runs as well (mlp_device.hpp)
+    const float* sOut = mlp_rows_forward<HT>(nd, u.params, which == 0 ? u.obs : u.critic_obs,
+                                             which == 0 ? u.obs_out : u.critic_obs_out, u.E, e0,
+                                             reinterpret_cast<float*>(policy_step_smem));
 
     // heads: one lane per env row
     if (tid < kRows && e0 + tid < u.E) {
@@ -140,32 +56,14 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
             u.value_out[e] = v;
         } else if (u.head_kind == PPOAF_HEAD_CATEGORICAL) {
             float p[8];
-            float m = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) if (k < out_dim) m = fmaxf(m, sOut[s * kMaxOut + k]);
-            float ssum = 0.f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { p[k] = k < out_dim ? expf(sOut[s * kMaxOut + k] - m) : 0.f; ssum += p[k]; }
-            const float inv = 1.0f / ssum;
-            float s2 = 0.f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { p[k] *= inv; s2 += p[k]; }
-            int a = out_dim - 1;
-            float c = 0.f, pa = p[0];
+            const float s2 = cat_probs(sOut + s * kMaxOut, out_dim, p);
+            int a;
+            float pa = p[0];
             if (u.forced_raw_action) {
                 const long fa = reinterpret_cast<const int64_t*>(u.forced_raw_action)[e];
                 a = fa < 0 ? 0 : (fa >= out_dim ? out_dim - 1 : (int)fa);
             } else {
-                const Philox4 rnd = philox4x32_10(u.seed, u.offset + (unsigned long long)e, 0u);
-                const float uu = u32_to_unit(rnd.x) * s2;
-                bool found = false;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    if (k < out_dim) {
-                        c += p[k];
-                        if (!found && uu < c) { a = k; found = true; }
-                    }
-                }
+                a = cat_sample(p, s2, out_dim, u.seed, u.offset + (unsigned long long)e);
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) if (k == a) pa = p[k];
@@ -210,9 +108,7 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
                         if (forced) {
                             a[d] = forced[e * out_dim + d];
                         } else {
-                            if ((d & 3) == 0) r = philox4x32_10(u.seed, u.offset + (unsigned long long)e, (uint32_t)(d >> 2));
-                            const uint32_t w = (d & 3) == 0 ? r.x : ((d & 3) == 1 ? r.y : ((d & 3) == 2 ? r.z : r.w));
-                            a[d] = u32_to_unit(w) < sigmoid_u(z[d]) ? 1.f : 0.f;
+                            a[d] = bern_uniform(u.seed, u.offset + (unsigned long long)e, d, r) < sigmoid_u(z[d]) ? 1.f : 0.f;
                         }
                         raw[d] = a[d];
                         ac[d] = a[d];
@@ -228,14 +124,8 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
             const float* forced = reinterpret_cast<const float*>(u.forced_raw_action);
             float lp = 0.f, slog = 0.f;
             for (int d0 = 0; d0 < out_dim; d0 += 4) {
-                const Philox4 r = philox4x32_10(u.seed, u.offset + (unsigned long long)e, (uint32_t)(d0 >> 2));
-                const float u0 = u32_to_unit_open0(r.x), u1 = u32_to_unit(r.y);
-                const float u2 = u32_to_unit_open0(r.z), u3 = u32_to_unit(r.w);
-                const float ra = sqrtf(-2.0f * logf(u0)), rb = sqrtf(-2.0f * logf(u2));
-                float sa, ca, sb, cb;
-                sincosf(6.28318530717958647692f * u1, &sa, &ca);
-                sincosf(6.28318530717958647692f * u3, &sb, &cb);
-                const float z[4] = {ra * ca, ra * sa, rb * cb, rb * sb};
+                float z[4];
+                gauss_normals4(u.seed, u.offset + (unsigned long long)e, (uint32_t)(d0 >> 2), z);
                 for (int j = 0; j < 4 && d0 + j < out_dim; ++j) {
                     const int d = d0 + j;
                     const float sd = fmaxf(softplus_u(log_std[d]), u.min_std);
@@ -244,7 +134,7 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
                     raw[d] = x;
                     float a = tanhf(x);
                     slog += logf(fmaxf(1.0f - a * a, 1e-6f));
-                    if (rescale) a = ((a + 1.0f) / 2.0f) * (u.act_hi[d] - u.act_lo[d]) + u.act_lo[d];   // distributions.py:580-581
+                    if (rescale) a = unit_to_bounds(a, u.act_lo[d], u.act_hi[d]);
                     ac[d] = a;
                     const float zz = x - mean;
                     float l = -(zz * zz) / (2.0f * sd * sd) - logf(sd) - 0.91893853320467274178f;
@@ -270,8 +160,7 @@ static size_t step_lds_bytes(const StepDev& u) {
     size_t worst = 0;
     for (int w = 0; w < 2; ++w) {
         const NetDev& n = u.net[w];
-        const size_t HS = n.H + 4, INP = 16 * ((n.in_dim + 15) / 16) + 4;
-        const size_t f = (size_t)(n.depth + 1) * n.H + 8 * (size_t)n.H + kRows * INP + 2 * kRows * HS + kRows * kMaxOut;
+        const size_t f = mlp_rows_forward_lds_floats(n);
         if (f * 4 > worst) worst = f * 4;
     }
     return (worst + 15) / 16 * 16;

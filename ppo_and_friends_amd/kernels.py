@@ -423,6 +423,69 @@ def policy_step(args):
 
 
 # --------------------------------------------------------------------------
+# K19: evaluation step (actor forward -> env action) and the score bookkeeping
+# --------------------------------------------------------------------------
+INFER_SAMPLE, INFER_DETERMINISTIC = 0, 1
+
+
+def policy_infer(args):
+    """ppoaf_policy_infer on a filled _lib.PolicyInferArgs (policies/ppo_policy.py fills it once per policy)."""
+    check(_lib.load().ppoaf_policy_infer(C.byref(args), stream()), "policy_infer")
+
+
+class EvalScores:
+    """
+    Device state of ppoaf_eval_scores_step for E rows that owe `num_test_runs` episodes between them: row e owes
+    N // E + (e < N % E).  `step(score, done)` enqueues one launch; nothing is read by the host until `remaining()`.
+    """
+
+    def __init__(self, E, num_test_runs, device, quota=None):
+        E, N = int(E), int(num_test_runs)
+        _req(E >= 1 and N >= 0, "EvalScores: needs E >= 1 rows and num_test_runs >= 0")
+        dev = torch.device(device)
+        if quota is None:
+            quota = torch.full((E,), N // E, dtype=torch.int32)
+            quota[:N % E] += 1
+        self.E = E
+        self.quota = torch.as_tensor(quota, dtype=torch.int32).to(dev).contiguous()
+        _req(self.quota.numel() == E, "EvalScores: one quota per row")
+        self.run_score = torch.zeros(E, dtype=torch.float64, device=dev)
+        self.run_len = torch.zeros(E, dtype=torch.int64, device=dev)
+        self.count = torch.zeros(E, dtype=torch.int64, device=dev)
+        self.sum = torch.zeros(E, dtype=torch.float64, device=dev)
+        self.min = torch.full((E,), float("inf"), dtype=torch.float64, device=dev)
+        self.max = torch.full((E,), float("-inf"), dtype=torch.float64, device=dev)
+        self.steps = torch.zeros(E, dtype=torch.int64, device=dev)
+        self.remaining_t = torch.full((1,), int(self.quota.sum().item()), dtype=torch.int32, device=dev)
+        a = self.args = _lib.EvalScoresArgs()
+        a.E = E
+        a.quota = ptr(self.quota)
+        for f in ("run_score", "run_len", "count", "sum", "min", "max", "steps"):
+            setattr(a, f, ptr(getattr(self, f)))
+        a.remaining = ptr(self.remaining_t)
+
+    def step(self, score, done):
+        eval_scores_step(self.args, score, done)
+
+    def remaining(self):
+        """The one host read of an evaluation loop: episodes still owed."""
+        return int(self.remaining_t.item())
+
+    def results(self):
+        """Per-row results on the host: dict of numpy arrays count, sum, min, max, steps."""
+        return {k: getattr(self, k).cpu().numpy() for k in ("count", "sum", "min", "max", "steps")}
+
+
+def eval_scores_step(args, score, done):
+    """One env step of the score bookkeeping: score float32[E], done bool / uint8[E] (terminated | truncated)."""
+    _f32(score, "score")
+    _req(done.dtype in (torch.bool, torch.uint8), f"done: expected bool or uint8, got {done.dtype}")
+    _req(score.numel() == args.E and done.numel() == args.E, "eval_scores_step: score and done need one value per row")
+    args.score, args.done = ptr(score), ptr(done)
+    check(_lib.load().ppoaf_eval_scores_step(C.byref(args), stream()), "eval_scores_step")
+
+
+# --------------------------------------------------------------------------
 # K8: ICM forward-model loss / intrinsic reward
 # --------------------------------------------------------------------------
 def icm_forward_loss_fwd(pred, enc2, reward_scale, want_loss=True):

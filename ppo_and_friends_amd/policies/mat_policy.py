@@ -268,6 +268,52 @@ class MATPolicy(PPOPolicy):
                     torch.swapaxes(log_probs, 0, 1).detach())
         return raw_actions, actions, log_probs
 
+    def _get_autoregressive_actions_without_exploration(self, encoded_obs):
+        """mat_policy.py:521-585: the greedy decode -- agent i takes the refined prediction of its distribution,
+        conditioned on the refined actions of agents < i.  -> actions [B, A, action_dim]."""
+        B, A = encoded_obs.shape[0], len(self.agent_ids)
+        block = self._get_tokened_action_block(B)
+        off = 1 if self.action_dtype == "discrete" else 0
+        adt = torch.int64 if self.action_dtype == "discrete" else torch.float32
+        out_a = torch.zeros((B, A, self.action_dim), dtype=adt, device=self.device)
+        with torch.no_grad():
+            for i in range(A):
+                pred = self.actor(block, encoded_obs)[:, i, :].contiguous()
+                action = self.actor.distribution.refine_prediction(pred)
+                out_a[:, i, :] = action.reshape(B, self.action_dim)
+                if i + 1 < A:
+                    if self.action_dtype == "discrete":
+                        block[:, i + 1, off:] = t_func.one_hot(action.reshape(B), num_classes=self.action_pred_size).float()
+                    else:
+                        block[:, i + 1, off:] = action.reshape(B, -1)
+        return out_a
+
+    def inference_unsupported_reason(self):
+        return "agent-grouped policy: the autoregressive decode runs on the network modules (a deterministic K16 is not built)"
+
+    def get_inference_actions(self, obs, deterministic):
+        """
+        mat_policy.py:701-790: encode once with the critic, then decode the agents one after the other -- sampled
+        (from the evaluation's own Philox stream) or greedy.  Device tensors arrive grouped, [E, A, O], and [E, A, .]
+        is returned; numpy arrives in the reference's [A, E, O] and is swapped like there.
+        """
+        if len(obs.shape) < 3:
+            raise ValueError(f"get_inference_actions expects a batch of grouped observations, got shape {obs.shape}")
+        as_numpy = not torch.is_tensor(obs)
+        t_obs = self._to_device(np.swapaxes(obs, 0, 1) if as_numpy else obs)
+        with torch.no_grad():
+            encoded_obs, _ = self.critic(t_obs)
+        if deterministic:
+            actions = self._get_autoregressive_actions_without_exploration(encoded_obs)
+        else:
+            dist = self.actor.distribution
+            rng, dist.rng = dist.rng, self.eval_rng()
+            try:
+                actions = self._get_autoregressive_actions(encoded_obs)[0]
+            finally:
+                dist.rng = rng
+        return torch.swapaxes(actions, 0, 1).cpu().numpy() if as_numpy else actions
+
     def get_critic_values(self, obs):
         """mat_policy.py:660-675."""
         _, values = self.critic(obs)

@@ -473,13 +473,91 @@ class PPOPolicy:
                    "icm_intrinsic_reward")
         return out
 
+    def inference_unsupported_reason(self):
+        """'' when get_inference_actions runs on K19 (ppoaf_policy_infer: the coverage of the K6 rollout step, on a
+        device policy that PPO has not put on the torch path), else why the torch path is taken."""
+        if self.device.type != "cuda":
+            return f"the policy lives on {self.device}: K19 needs a HIP device"
+        if getattr(self, "update_mode", "auto") == "torch":
+            return "update_mode='torch' keeps the policy on the torch-ROCm path"
+        if self.using_lstm:
+            return "LSTM policies go through forward_logits (K18 under update_mode='fused')"
+        # (asked once per evaluation step: the answer is kept for as long as what it depends on stays)
+        key = (self.policy_params.data_ptr(), bool(self.fused_action_heads))
+        if getattr(self, "_infer_reason", (None, ""))[0] != key:
+            self._infer_reason = (key, self.fused_step_unsupported_reason())
+        return self._infer_reason[1]
+
+    def eval_rng(self):
+        """The evaluation's Philox stream (seeded from the policy seed and a fixed tag): sampled evaluation never draws
+        from distribution.rng, so evaluating does not move the training rollout's random stream."""
+        dist = self.actor.distribution
+        if getattr(dist, "eval_rng", None) is None:
+            from ..networks.distributions import _PhiloxStream
+            dist.eval_rng = _PhiloxStream((int(dist.rng.seed) ^ 0x6576616C5F726E67) & 0xFFFFFFFFFFFFFFFF)    # "eval_rng"
+        return dist.eval_rng
+
+    def _infer_step(self, t_obs, deterministic):
+        """K19: one launch, actor forward -> head -> env action, into a reusable output tensor."""
+        from .. import _lib
+        from ..fused_update import _describe, action_head, set_action_slices
+        E = t_obs.shape[0]
+        st = getattr(self, "_infer_state", None)
+        if st is None or st["E"] != E or st["params"] != self.policy_params.data_ptr():
+            a = _lib.PolicyInferArgs()
+            head, slices, _ = action_head(self)
+            gauss = head == K.HEAD_GAUSSIAN
+            a.actor, _ = _describe(self.actor, self.policy_params, gauss)
+            a.params = self.policy_params.data_ptr()
+            a.E = E
+            a.head_kind = head
+            set_action_slices(a, slices)
+            a.min_std = float(getattr(self.actor.distribution, "min_std", 0.01))
+            lo, hi = self.actor.distribution.bound_tensors() if gauss else (None, None)
+            a.act_lo = None if lo is None else lo.data_ptr()
+            a.act_hi = None if hi is None else hi.data_ptr()
+            shape = {K.HEAD_CATEGORICAL: (E,), K.HEAD_MULTI_CATEGORICAL: (E, len(slices))}.get(head, (E, a.actor.out_dim))
+            out = torch.zeros(shape, dtype=torch.float32 if head in (K.HEAD_GAUSSIAN, K.HEAD_BERNOULLI) else torch.int64,
+                              device=self.device)
+            a.action_out = out.data_ptr()
+            st = self._infer_state = dict(E=E, params=self.policy_params.data_ptr(), args=a, out=out)
+        a = st["args"]
+        K._req(t_obs.is_cuda and t_obs.dtype == torch.float32 and t_obs.numel() == E * a.actor.in_dim,
+               "get_inference_actions: obs must hold [E, obs_dim] float32 values")
+        t_obs = t_obs.contiguous()
+        a.obs = t_obs.data_ptr()
+        a.mode = K.INFER_DETERMINISTIC if deterministic else K.INFER_SAMPLE
+        if not deterministic:
+            per_row = {K.HEAD_MULTI_CATEGORICAL: a.n_action_slices, K.HEAD_BERNOULLI: a.actor.out_dim}.get(a.head_kind, 1)
+            a.seed, a.offset = self.eval_rng().take(E * per_row)
+        K.policy_infer(a)
+        return st["out"]
+
     def get_inference_actions(self, obs, deterministic):
+        """
+        ppo_policy.py:796-889 -> the environment action of every row: the distribution's refined prediction when
+        `deterministic`, else a sample.  numpy in -> numpy out, device tensor in -> device tensor out.  On K19 (see
+        inference_unsupported_reason) the result is a reusable tensor that the next call overwrites.
+        """
+        if len(obs.shape) < 2:
+            raise ValueError(f"get_inference_actions expects a batch of observations, got shape {obs.shape}")
+        as_numpy = not torch.is_tensor(obs)
         t_obs = self._to_device(obs)
-        with torch.no_grad():
-            pred = self.actor.forward_logits(t_obs)
-            if deterministic:
-                return self.actor.distribution.refine_prediction(pred)
-            return self.actor.distribution.sample_distribution(pred)[0]
+        if self.inference_unsupported_reason() == "":
+            action = self._infer_step(t_obs, deterministic)
+        else:
+            dist = self.actor.distribution
+            with torch.no_grad():
+                pred = self.actor.forward_logits(t_obs)
+                if deterministic:
+                    action = dist.refine_prediction(pred)
+                else:
+                    rng, dist.rng = dist.rng, self.eval_rng()
+                    try:
+                        action = dist.sample_distribution(pred)[0]
+                    finally:
+                        dist.rng = rng
+        return action.cpu().numpy() if as_numpy else action
 
     def get_critic_values(self, obs):
         """ppo_policy.py:1057-1071."""

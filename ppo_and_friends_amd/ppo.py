@@ -165,12 +165,14 @@ class PPO:
                  soft_resets=False, state_path="./saved_state", load_state=False, checkpoint_every=100,
                  save_train_scores=False, save_avg_ep_len=False, save_running_time=False, save_bs_info=False,
                  save_state=True, use_graphs=True, update_mode="auto", verbose=False, freeze_scheduler=None,
-                 reference_device="cpu", **kw_args):
+                 reference_device="cpu", test_mode=False, **kw_args):
         """
         ppo.py:126-167.  `ts_per_rollout` is per environment (ppo.py:317-318
         multiplies by envs_per_proc).  normalize_obs / normalize_rewards / obs_clip / reward_clip
         put the device filter stack of environments/filter_wrappers.py around `env_generator()`
-        (ppo.py:358-371 -> wrapper_utils.py:81-111); soft_resets as ppo.py:1580-1586.
+        (ppo.py:358-371 -> wrapper_utils.py:81-111); soft_resets as ppo.py:1580-1586.  test_mode (ppo.py:163,344,371,506):
+        the filter stack, the value normalisers, the policies and their networks are built for evaluation -- running
+        statistics frozen, rank-0 files read, nothing saved (see set_test_mode).
         """
         mpi_utils.set_torch_threads()
         self.device = torch.device(device)
@@ -193,6 +195,9 @@ class PPO:
         self.use_graphs = use_graphs and self.device.type == "cuda" and os.environ.get("PPOAF_GRAPHS", "1") != "0"
         # "fused": K12 kernels (MLP policies); "torch": torch-ROCm MLPs + K2..K11; "auto": fused when covered
         self.update_mode = update_mode
+        self.test_mode = bool(test_mode)
+        self._filter_kw = dict(normalize_obs=normalize_obs, normalize_rewards=normalize_rewards, obs_clip=obs_clip,
+                               reward_clip=reward_clip, gamma=gamma)
         self._fused = {}
         self._perm_cache = {}
         self.verbose = verbose
@@ -205,7 +210,7 @@ class PPO:
 
         self.env = wrap_environment(env_generator, normalize_obs=normalize_obs,
                                     normalize_rewards=normalize_rewards, obs_clip=obs_clip,
-                                    reward_clip=reward_clip, gamma=gamma, test_mode=False)
+                                    reward_clip=reward_clip, gamma=gamma, test_mode=self.test_mode)
         self.soft_resets = soft_resets if callable(soft_resets) else CallableValue(bool(soft_resets))
         self.policy_mapping_fn = policy_mapping_fn or (lambda agent_id: next(iter(policy_settings)))
         max_int = int(np.iinfo(np.int32).max)
@@ -232,7 +237,7 @@ class PPO:
             pol = generate_policy(policy_name=policy_id, policy_class=policy_class,
                                   actor_observation_space=obs_space,
                                   critic_observation_space=critic_obs_space, action_space=act_space,
-                                  test_mode=False, envs_per_proc=self.envs_per_proc,
+                                  test_mode=self.test_mode, envs_per_proc=self.envs_per_proc,
                                   random_seed=self.random_seed, **policy_args)
             for agent_id in getattr(self.env, "agent_ids", ["agent0"]):
                 if self.policy_mapping_fn(agent_id) == policy_id:
@@ -249,9 +254,10 @@ class PPO:
                                                     "intr reward range": (max_int, -max_int)})
             if normalize_values:
                 self.value_normalizers[policy_id] = RunningStatNormalizer(
-                    name=f"{policy_id}-value_normalizer", device=self.device)
+                    name=f"{policy_id}-value_normalizer", device=self.device, test_mode=self.test_mode)
         for policy_id, pol in self.policies.items():
             pol.finalize(self.status_dict, self.device)
+            pol.update_mode = update_mode                       # "torch" keeps get_inference_actions off K19 as well
             pol.fused_icm_reward = update_mode != "torch"       # K14's kernels for the rollout-time intrinsic reward
             # the MultiDiscrete / MultiBinary heads of K6 / K12 (csrc/action_heads.hpp); "auto" keeps them on torch-ROCm for now
             pol.fused_action_heads = update_mode == "fused"
@@ -641,6 +647,116 @@ class PPO:
         for k in ("longest episode", "shortest episode", "average episode"):
             gs[k] = st[k]
 
+    # ------------------------------------------------------------------ evaluation
+    @staticmethod
+    def _filter_stack(env):
+        """The wrappers of a filter stack, outermost first."""
+        while env is not None and hasattr(env, "_plan"):
+            yield env
+            env = env.env
+
+    def set_test_mode(self, test_mode):
+        """
+        ppo.py:2853-2865: the flag on everything that depends on it -- the env's filter stack, the value normalisers,
+        the policies and their networks -- and the filter stack's `update` switches to `not test_mode` (the reference's
+        filters read self.test_mode where they decide to update, filter_wrappers.py:155-268).
+        """
+        test_mode = bool(test_mode)
+        self.test_mode = test_mode
+        for w in self._filter_stack(self.env):
+            w.test_mode = test_mode
+            if hasattr(w, "update_stats"):
+                w.update_stats = not test_mode
+                w._cfg["update"] = not test_mode
+        for vn in self.value_normalizers.values():
+            vn.test_mode = test_mode
+        for pol in self.policies.values():
+            pol.test_mode = test_mode
+            for net in (getattr(pol, "actor", None), getattr(pol, "critic", None), getattr(pol, "actor_critic", None),
+                        getattr(pol, "icm_model", None)):
+                if net is not None and hasattr(net, "test_mode"):
+                    net.test_mode = test_mode
+
+    def make_eval_env(self, env_generator):
+        """
+        An evaluation env for test_policy(env=...) during training: `env_generator()` under a filter stack of its own
+        that SHARES the training stack's statistics tensors (no copy: it always normalises with the current statistics)
+        with `update` off, so stepping it moves nothing the training run reads.
+        """
+        env = wrap_environment(env_generator, test_mode=True, **self._filter_kw)
+        mine = {type(w): w for w in self._filter_stack(self.env)}
+        for w in self._filter_stack(env):
+            src = mine.get(type(w))
+            if src is None or not hasattr(w, "_cfg"):
+                continue
+            if not src._plan._ready:
+                src._plan._setup()
+            for key in ("stats", "critic_stats"):
+                if key in src._cfg:
+                    w._cfg[key] = src._cfg[key]
+            if "state" in src._cfg:
+                # the running discounted return belongs to the env being stepped; mean / variance / count are shared
+                rr = torch.zeros(int(getattr(env, "num_agents", 1)) * int(env.get_batch_size()), dtype=torch.float64,
+                                 device=self.device)
+                w._cfg["state"] = (rr,) + tuple(src._cfg["state"][1:])
+        if callable(getattr(env, "finalize", None)):
+            env.finalize(self.status_dict)
+        return env
+
+    def _policy_agent_rows(self, env):
+        """[(policy_id, policy, its agents in env order, their indices)] -- the index sets _rollout_multi_policy builds."""
+        agent_ids = list(getattr(env, "agent_ids", ["agent0"]))
+        out = []
+        for policy_id, pol in self.policies.items():
+            idx = sorted(agent_ids.index(a) for a in pol.agent_ids)
+            out.append((policy_id, pol, [agent_ids[i] for i in idx], idx))
+        return out
+
+    def get_inference_actions(self, obs, deterministic, critic_obs=None, env=None):
+        """
+        ppo.py:896-1028 for this package's batched contract: `obs` is what the env hands over (agent-major rows
+        [A*E, .] or a dict keyed by agent id); every policy acts on its own agents' rows and the env's action tensor
+        (or dict) is returned.  Agent-grouped policies (MAT) receive [E, A, .] in their slot order -- of `critic_obs`
+        when their actor sees the critic's observation (mat_policy.py:808-853).
+        """
+        env = self.env if env is None else env
+        n_envs = env.get_batch_size()
+        groups = self._policy_agent_rows(env)
+        A = sum(len(g[3]) for g in groups)
+        if isinstance(obs, dict):
+            actions = {}
+            for _, pol, agents, _ in groups:
+                a = pol.get_inference_actions(torch.cat([obs[k] for k in agents], 0).contiguous(), deterministic)
+                per_agent = a.reshape((len(agents), n_envs) + tuple(a.shape[1:]))
+                for i, agent_id in enumerate(agents):
+                    actions[agent_id] = per_agent[i]
+            return actions
+        if len(groups) == 1:
+            pol = groups[0][1]
+            if pol.agent_grouping:
+                order = torch.as_tensor(pol.agent_slot_order(), device=obs.device)
+                if pol.expanded_actor_space:
+                    if critic_obs is None:
+                        raise ValueError("this policy's actor sees the critic's observation: pass critic_obs")
+                    obs = critic_obs
+                g = obs.reshape((A, n_envs) + tuple(obs.shape[1:]))[order].transpose(0, 1).contiguous()
+                a = pol.get_inference_actions(g, deterministic)                     # [E, A, .]
+                return a.transpose(0, 1)[torch.argsort(order)].reshape((A * n_envs,) + tuple(a.shape[2:]))
+            return pol.get_inference_actions(obs, deterministic)
+        actions = None
+        for _, pol, agents, idx in groups:
+            ix = torch.as_tensor(idx, device=obs.device)
+            o = obs.reshape((A, n_envs) + tuple(obs.shape[1:]))[ix].reshape((len(idx) * n_envs,) + tuple(obs.shape[1:]))
+            a = pol.get_inference_actions(o.contiguous(), deterministic)
+            if a.dim() == 1:
+                a = a.unsqueeze(-1)
+            if actions is None:
+                actions = torch.zeros((A, n_envs) + tuple(a.shape[1:]), dtype=a.dtype, device=a.device)
+            elif a.dtype != actions.dtype or tuple(a.shape[1:]) != tuple(actions.shape[2:]):
+                raise ValueError("policies with different action spaces need an env that exchanges dicts keyed by agent id")
+            actions[ix] = a.reshape((len(idx), n_envs) + tuple(a.shape[1:]))
+        return actions.reshape((A * n_envs,) + tuple(actions.shape[2:]))
+
     # ------------------------------------------------------------------ update
     def learn(self, num_timesteps):
         """ppo.py:2112-2272."""
@@ -697,6 +813,9 @@ class PPO:
         `<state>/env_info/<tag>/...` (filter and value-normaliser statistics) and `<state>/state_0.pickle`
         (the status dict), in the reference's file names and payload formats (utils/reference_io.py).
         """
+        if self.test_mode:                                   # ppo.py:2581-2584
+            rank_print("WARNING: save() was called while in test mode. Disregarding.")
+            return
         if not self.save_state:
             return
         if mpi_utils.get_rank() == 0:

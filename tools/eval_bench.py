@@ -1,0 +1,180 @@
+"""
+Evaluation env-steps/s of `ppo_and_friends_amd.testing.test_policy` at two shapes, two legs in one process, alternated:
+
+  shapes  c2  BatchedCartPoleEnv, E = 4096, actor 4 -> 128^3 -> 2 (Discrete(2)), observation / reward normalisers
+          c3  SyntheticFixedLengthEnv, E = 4096, actor 17 -> 256^3 -> 6 (Box(6), C3's actor shape), no filters
+  legs    a   this package: test_policy (K19 `ppoaf_policy_infer` + `ppoaf_eval_scores_step` per step, one host read
+              of `remaining` every check_every steps)
+          b   the baseline: the same loop written only with what the package had before K19 -- the torch forward of
+              PPOPolicy.get_inference_actions (actor.forward_logits + refine_prediction) and torch ops for the
+              scores, same quotas, same host read
+
+Both legs play the same number of test runs from the same env seed; env-steps/s = E x loop steps / wall time, printed as
+median and spread (min .. max) over `--repeats`, then one JSON line.  `--leg a|b --shape c2|c3 --repeats 1` under
+`rocprofv3 --kernel-trace --stats` gives the launches per evaluation step of one leg (the loop steps are printed).
+
+    python tools/eval_bench.py [--shape both|c2|c3] [--leg both|a|b] [--envs 4096] [--runs-per-env 2] [--repeats 5]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DEV = torch.device("cuda", 0)
+
+
+def count_steps(ppo):
+    """Counts the raw env's steps (the loop steps of either leg) in ppo.loop_steps[0]."""
+    raw = ppo.env
+    while hasattr(raw, "env"):
+        raw = raw.env
+    ppo.loop_steps = [0]
+    inner = raw.step
+
+    def step(action):
+        ppo.loop_steps[0] += 1
+        return inner(action)
+    raw.step = step
+
+
+def make(shape, E):
+    from ppo_and_friends_amd.ppo import PPO
+    from ppo_and_friends_amd.environments.cartpole import BatchedCartPoleEnv
+    from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
+    from ppo_and_friends_amd.spaces import Box, Discrete
+    if shape == "c2":
+        env_gen = lambda: BatchedCartPoleEnv(E, DEV, seed=0, max_episode_steps=200)
+        probe = BatchedCartPoleEnv(1, DEV)
+        net = dict(hidden_size=128, hidden_depth=3, activation=nn.ReLU())
+        settings = {"p": (None, probe.observation_space, probe.observation_space, Discrete(2),
+                          dict(actor_kw_args=dict(net), critic_kw_args=dict(net)))}
+        ppo = PPO(env_gen, settings, device=DEV, random_seed=1, envs_per_proc=E, ts_per_rollout=32, save_state=False)
+    else:
+        space = Box(-1.0, 1.0, (6,), np.float32)
+
+        def env_gen():
+            env = SyntheticFixedLengthEnv(E, 17, space, 64, DEV, reward="uniform", seed=1234, term_prob=0.02)
+            env.term_table[-1] = True                 # every row finishes at least once per 64 steps
+            return env
+        sp = Box(-np.inf, np.inf, (17,), np.float32)
+        net = dict(hidden_size=256, hidden_depth=3, activation=nn.Tanh())
+        settings = {"p": (None, sp, sp, space, dict(actor_kw_args=dict(net), critic_kw_args=dict(net)))}
+        ppo = PPO(env_gen, settings, device=DEV, random_seed=1, envs_per_proc=E, ts_per_rollout=32, normalize_obs=False,
+                  normalize_rewards=False, save_state=False)
+    ppo.rollout()                                     # filter statistics that are not the identity
+    count_steps(ppo)
+    return ppo
+
+
+def leg_a(ppo, N, check_every):
+    from ppo_and_friends_amd.testing import test_policy
+    return test_policy(ppo, N, deterministic=True, check_every=check_every)
+
+
+def leg_b(ppo, N, check_every):
+    """The evaluation loop with the torch forward and torch bookkeeping (no K19, no scores kernel)."""
+    env, pol = ppo.env, ppo.policies["p"]
+    E = env.get_batch_size()
+    quota = torch.full((E,), N // E, dtype=torch.int64, device=DEV)
+    quota[:N % E] += 1
+    z = lambda dt: torch.zeros(E, dtype=dt, device=DEV)
+    run_score, run_len, count, total, steps = z(torch.float64), z(torch.int64), z(torch.int64), z(torch.float64), z(torch.int64)
+    lo = torch.full((E,), float("inf"), dtype=torch.float64, device=DEV)
+    hi = torch.full((E,), float("-inf"), dtype=torch.float64, device=DEV)
+    stack = [w for w in ppo._filter_stack(env) if hasattr(w, "update_stats")]
+    saved = [w._cfg["update"] for w in stack]
+    for w in stack:
+        w._cfg["update"] = False
+    pol.eval()
+    try:
+        obs, _ = env.reset()
+        t, remaining = 0, N
+        while remaining > 0:
+            with torch.no_grad():                     # PPOPolicy.get_inference_actions as it was: torch forward + refine
+                action = pol.actor.distribution.refine_prediction(pol.actor.forward_logits(obs))
+            obs, _, reward, terminated, truncated, _ = env.step(action)
+            score = ppo._natural_reward(env, reward)
+            done = terminated | truncated
+            live = count < quota
+            run_score = torch.where(live, run_score + score.double(), run_score)
+            run_len = torch.where(live, run_len + 1, run_len)
+            fin = live & done
+            count = count + fin
+            total = torch.where(fin, total + run_score, total)
+            lo = torch.where(fin, torch.minimum(lo, run_score), lo)
+            hi = torch.where(fin, torch.maximum(hi, run_score), hi)
+            steps = torch.where(fin, steps + run_len, steps)
+            run_score = torch.where(fin, torch.zeros_like(run_score), run_score)
+            run_len = torch.where(fin, torch.zeros_like(run_len), run_len)
+            t += 1
+            if t % check_every == 0:
+                remaining = int((quota - count).sum().item())
+    finally:
+        for w, u in zip(stack, saved):
+            w._cfg["update"] = u
+    return {"num_test_runs": N, "total_time_steps": int(steps.sum().item()),
+            "p": {"low_score": float(lo.min().item()), "high_score": float(hi.max().item()),
+                  "avg_score": float(total.sum().item() / N)}}
+
+
+def timed(fn, ppo, N, check_every):
+    ppo.loop_steps[0] = 0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    info = fn(ppo, N, check_every)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, ppo.loop_steps[0], info
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", default="both", choices=["both", "c2", "c3"])
+    ap.add_argument("--leg", default="both", choices=["both", "a", "b"])
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--runs-per-env", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    args = ap.parse_args()
+    from ppo_and_friends_amd import testing
+    testing.rank_print = lambda *a, **k: None        # the score report is not what is timed
+    shapes = ["c2", "c3"] if args.shape == "both" else [args.shape]
+    legs = {"a": leg_a, "b": leg_b}
+    legs = legs if args.leg == "both" else {args.leg: legs[args.leg]}
+    E, N = args.envs, args.envs * args.runs_per_env
+    result = {"envs": E, "num_test_runs": N}
+    for shape in shapes:
+        ppo = make(shape, E)
+        check_every = 64 if shape == "c3" else 50
+        assert ppo.policies["p"].inference_unsupported_reason() == "", ppo.policies["p"].inference_unsupported_reason()
+        for name, fn in legs.items():
+            for _ in range(args.warmup):
+                timed(fn, ppo, N, check_every)
+        times = {k: [] for k in legs}
+        for _ in range(args.repeats):
+            for name, fn in legs.items():             # alternating: drifts of clock / neighbours hit both legs alike
+                dt, steps, info = timed(fn, ppo, N, check_every)
+                times[name].append((dt, steps))
+                result[f"{shape}_{name}_avg_score"] = info["p"]["avg_score"]
+        for name in legs:
+            sps = np.array([E * s / dt for dt, s in times[name]])
+            result[f"{shape}_{name}_env_steps_per_s"] = float(np.median(sps))
+            result[f"{shape}_{name}_spread"] = [float(sps.min()), float(sps.max())]
+            result[f"{shape}_{name}_loop_steps"] = [s for _, s in times[name]]
+            print(f"{shape} leg {name}: env-steps/s median {np.median(sps):12.0f}  spread {sps.min():12.0f} .. {sps.max():12.0f}"
+                  f"  (loop steps {times[name][0][1]}, {np.median([dt for dt, _ in times[name]]) * 1e3:.1f} ms)", flush=True)
+        if len(legs) == 2:
+            result[f"{shape}_a_over_b"] = result[f"{shape}_a_env_steps_per_s"] / result[f"{shape}_b_env_steps_per_s"]
+        del ppo
+    print(json.dumps(result), flush=True)
+
+
+if __name__ == "__main__":
+    main()
