@@ -546,6 +546,27 @@ typedef struct {
 
 int ppoaf_eval_scores_step(const ppoaf_eval_scores_args_t* args, ppoaf_stream_t stream);
 
+/* The score books of a multi-agent evaluation (testing.py:59-112, the per-agent and per-policy sums of :93-98) in ONE
+ * launch per env step instead of one ppoaf_eval_scores_step per agent and one more per agent for its policy's book.
+ * score: [num_agents, E] float32, agent-major (what the env hands over); done: [E]; quota: [E], shared by every book.
+ * Book b keeps its own rows of the [n_books, E] state arrays and its own remaining[b], and sums the agents whose bit is
+ * set in book_mask[b] (bit a = agent a, num_agents <= 16, n_books <= 32):
+ *   one bit     an agent's book: exactly the rule of ppoaf_eval_scores_step on score[a]
+ *   more bits   a policy's book: exactly the chain of ppoaf_eval_scores_step calls it replaces -- the agents of the mask
+ *               in ascending order, run_score += score[a][e] in float64 agent by agent, run_len + 1 PER AGENT, and the
+ *               episode closes (done[e]) with the last agent of the mask
+ * Results are bitwise those of the chain.  The caller initialises every book as ppoaf_eval_scores_step asks. */
+typedef struct {
+    const float* score; const uint8_t* done; const int32_t* quota; int64_t E;
+    int32_t num_agents; int32_t n_books;
+    int32_t book_mask[32];
+    double* run_score; int64_t* run_len;
+    int64_t* count; double* sum; double* min; double* max; int64_t* steps;
+    int32_t* remaining;
+} ppoaf_eval_books_args_t;
+
+int ppoaf_eval_scores_step_books(const ppoaf_eval_books_args_t* args, ppoaf_stream_t stream);
+
 
 /* ------------------------------------------------------------------------ *
  * K8  ICM forward-model loss and intrinsic reward
@@ -834,6 +855,38 @@ typedef struct {
 } ppoaf_mat_step_args_t;
 
 int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* args, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * K20  one evaluation step of a MATPolicy for all E envs in one launch
+ * replaces MATPolicy.get_inference_actions                              policies/mat_policy.py:701-790
+ *          _get_autoregressive_actions_without_exploration (greedy)     mat_policy.py:521-585
+ *          _get_autoregressive_actions (sampled)                        mat_policy.py:441-519
+ *          (the step of the evaluation loop                             testing.py:8-175)
+ * The encoder runs once (up to rep_enc: no value), the decoder A times (agent i's env action is agent i+1's token);
+ * only the int64 env actions are stored.  Shapes as K16; offsets as K15 (checked).  mode:
+ *   PPOAF_INFER_SAMPLE         K16's categorical draw with K16's Philox counter (offset + env * A + slot): for equal
+ *                              (obs, params, seed, offset) in grouped layout the actions are bitwise
+ *                              ppoaf_mat_policy_step's action_out
+ *   PPOAF_INFER_DETERMINISTIC  argmax of the logits, the lowest index on an exact tie; seed / offset are not read
+ * Layout: slot s of env e reads the obs_dim floats of observation ROW slot_agent[s] * obs_agent_stride + e * obs_env_stride
+ * and writes action ELEMENT slot_agent[s] * act_agent_stride + e * act_env_stride.  slot_agent is the policy's (shuffled)
+ * slot order, a permutation of 0..A-1.  Grouped [E, A, .]: env stride A, agent stride 1, identity order; the env's
+ * agent-major [A * E, .]: env stride 1, agent stride E, MATPolicy.agent_slot_order().  E == 0: nothing to do.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t obs_dim, num_agents, num_actions, embedding;
+    int64_t offsets[64];
+    const float* params;
+    const float* obs; int64_t E;
+    int64_t obs_env_stride, obs_agent_stride;
+    int32_t slot_agent[16];
+    int32_t mode;
+    uint64_t seed, offset;
+    int64_t* action_out;
+    int64_t act_env_stride, act_agent_stride;
+} ppoaf_mat_infer_args_t;
+
+int ppoaf_mat_policy_infer(const ppoaf_mat_infer_args_t* args, ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
  * K18  one-layer LSTM network: LSTMNetwork.forward_logits and its gradients

@@ -105,6 +105,15 @@ class EvalScoresArgs(C.Structure):
                 ("steps", C.c_void_p), ("remaining", C.c_void_p)]
 
 
+class EvalBooksArgs(C.Structure):
+    """ppoaf_eval_books_args_t (include/ppoaf_hip.h)."""
+    _fields_ = [("score", C.c_void_p), ("done", C.c_void_p), ("quota", C.c_void_p), ("E", C.c_int64),
+                ("num_agents", C.c_int32), ("n_books", C.c_int32), ("book_mask", C.c_int32 * 32),
+                ("run_score", C.c_void_p), ("run_len", C.c_void_p),
+                ("count", C.c_void_p), ("sum", C.c_void_p), ("min", C.c_void_p), ("max", C.c_void_p),
+                ("steps", C.c_void_p), ("remaining", C.c_void_p)]
+
+
 # name -> (restype, argtypes); mirrors include/ppoaf_hip.h one to one.
 class IcmUpdateArgs(C.Structure):
     """ppoaf_icm_update_args_t (include/ppoaf_hip.h) -- field order must match the header."""
@@ -160,6 +169,17 @@ class MatStepArgs(C.Structure):
                 ("action_out", C.c_void_p), ("raw_action_out", C.c_void_p), ("logp_out", C.c_void_p),
                 ("value_out", C.c_void_p), ("critic_obs_copy_out", C.c_void_p), ("obs_copy_out", C.c_void_p),
                 ("forced_action", C.c_void_p)]
+
+
+class MatInferArgs(C.Structure):
+    """ppoaf_mat_infer_args_t (include/ppoaf_hip.h)."""
+    _fields_ = [("obs_dim", C.c_int32), ("num_agents", C.c_int32), ("num_actions", C.c_int32), ("embedding", C.c_int32),
+                ("offsets", C.c_int64 * 64), ("params", C.c_void_p),
+                ("obs", C.c_void_p), ("E", C.c_int64),
+                ("obs_env_stride", C.c_int64), ("obs_agent_stride", C.c_int64),
+                ("slot_agent", C.c_int32 * 16), ("mode", C.c_int32),
+                ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("action_out", C.c_void_p), ("act_env_stride", C.c_int64), ("act_agent_stride", C.c_int64)]
 
 
 class ObsFilter(C.Structure):
@@ -238,6 +258,7 @@ SIGNATURES = {
     "ppoaf_policy_step": (C.c_int, [C.POINTER(PolicyStepArgs), _ptr]),
     "ppoaf_policy_infer": (C.c_int, [C.POINTER(PolicyInferArgs), _ptr]),
     "ppoaf_eval_scores_step": (C.c_int, [C.POINTER(EvalScoresArgs), _ptr]),
+    "ppoaf_eval_scores_step_books": (C.c_int, [C.POINTER(EvalBooksArgs), _ptr]),
     "ppoaf_minibatch_moments": (C.c_int, [_ptr, _ptr, _ptr, C.c_int64, C.c_int64, _ptr, _ptr]),
     "ppoaf_icm_update_fwd_bwd": (C.c_int, [C.POINTER(IcmUpdateArgs), _ptr]),
     "ppoaf_icm_update_reduce": (C.c_int, [C.POINTER(IcmUpdateArgs), _ptr]),
@@ -255,6 +276,7 @@ SIGNATURES = {
     "ppoaf_mat_update_split_workspace_bytes": (C.c_int, [C.POINTER(MatUpdateArgs), C.POINTER(C.c_int64)]),
     "ppoaf_mat_update_norm_partials": (C.c_int, [C.POINTER(MatUpdateArgs)]),
     "ppoaf_mat_policy_step": (C.c_int, [C.POINTER(MatStepArgs), _ptr]),
+    "ppoaf_mat_policy_infer": (C.c_int, [C.POINTER(MatInferArgs), _ptr]),
     "ppoaf_lstm_workspace_floats": (C.c_int, [C.POINTER(LstmDesc), C.POINTER(C.c_int64)]),
     "ppoaf_lstm_forward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int32, _ptr]),
     "ppoaf_lstm_backward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),

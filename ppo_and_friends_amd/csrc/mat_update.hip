@@ -450,13 +450,34 @@ __device__ __forceinline__ void head_out_bwd(const float* __restrict__ W, int n_
 // and run without one.
 #define MAT_SYNC() __syncthreads()
 
-// LDS carve shared by the update kernel (K15) and the rollout step kernel (K16)
-struct MatCtx {
+// tile indices: saved activations of the critic (0-11) and the actor (12-27), scratch (28-33)
+enum { cZ1_ = 0, cN0_, cQ_, cK_, cV_, cY_, cN1_, cZM_, cN2_, cENC_, cZH_, cNH_,
+       aZ_, aN0_, aQ1_, aK1_, aV1_, aY1_, aN1_, aK2_, aV2_, aQ2_, aY2_, aN2_, aZM_, aN3_, aZH_, aNH_,
+       S0_, S1_, S2_, S3_, S4_, DENC_, MAT_NUM_TILES };
+
+// Forward-only carve (K20): nothing is read back by a backward pass, so tiles whose lives never overlap share storage.
+//   0 rep_enc (live through every decoder pass)   1-4 S0..S3   5 every pre-GELU tile (written by a linear, read by the
+//   next phase's GELU)   6 / 7 / 8 q / k / v of the attention in flight   9 its y -- and every saved x-hat: a LayerNorm
+//   writes it and nobody reads it, and no LayerNorm runs between an attention and the projection that consumes y
+constexpr int kMatFwdTiles = 10;
+constexpr int mat_fwd_tile(int k) {
+    return k == cENC_ ? 0
+         : (k >= S0_ && k <= S3_) ? 1 + (k - S0_)
+         : (k == cZ1_ || k == cZM_ || k == cZH_ || k == aZ_ || k == aZM_ || k == aZH_) ? 5
+         : (k == cQ_ || k == aQ1_ || k == aQ2_) ? 6
+         : (k == cK_ || k == aK1_ || k == aK2_) ? 7
+         : (k == cV_ || k == aV1_ || k == aV2_) ? 8
+         : 9;                                                // y, x-hat; S4 / DENC exist only in the backward
+}
+
+// LDS carve shared by the update kernel (K15), the rollout step kernel (K16) and, with FWD, the evaluation step (K20)
+template <bool FWD>
+struct MatCtxT {
     const float* P; const long* off;
     int O, L, NA, Ain, OS, n_rows;
     int* sRow; int* sAct; float* sMisc; float* sRowF; float* sRstd;
     float *sOutC, *sOutA, *sDOutC, *sDOutA, *sP0, *sP1, *sP2, *sS, *sXA, *sXO, *sYO, *T;
-    __device__ __forceinline__ float* tile(int k) const { return T + (long)k * kMTile; }
+    __device__ __forceinline__ float* tile(int k) const { return T + (long)(FWD ? mat_fwd_tile(k) : k) * kMTile; }
     __device__ __forceinline__ float* rstd(int k) const { return sRstd + 16 * k; }
     __device__ __forceinline__ const float* W(int k) const { return P + off[k]; }
     __device__ __forceinline__ void carve(float* sm, int O_) {
@@ -468,22 +489,28 @@ struct MatCtx {
         sRstd = sm + 96;                                   // [10][16]
         sOutC = sm + 256;                                  // [16][8] critic output (col 0)
         sOutA = sOutC + 128;                               // [16][8] logits
-        sDOutC = sOutA + 128;
-        sDOutA = sDOutC + 128;
-        sP0 = sDOutA + 128;                                // 3 probability tiles + 1 dS scratch, [16][17] each
-        sP1 = sP0 + 272;
-        sP2 = sP1 + 272;
-        sS = sP2 + 272;
-        sXA = sS + 272;                                    // [16][kMXS] action tokens
-        sXO = sXA + kRows * kMXS;                          // [16][OS] xhat of the observation LayerNorm
-        sYO = sXO + kRows * OS;                            // [16][OS] its output (input of the encoder linear)
-        T = sYO + kRows * OS;                              // [16][68] tiles from here on
+        if constexpr (FWD) {
+            sDOutC = sDOutA = nullptr;
+            sP0 = sP1 = sP2 = sS = sOutA + 128;            // one probability tile [16][17]: the attentions run one at a time
+            sXA = sP0 + 272;                               // [16][kMXS] action tokens
+            sYO = sXA + kRows * kMXS;                      // [16][OS] observations, then the observation LayerNorm's output
+            T = sYO + kRows * OS;
+            sXO = tile(cY_);                               // its x-hat: unread (OS <= kMHS, so it fits the tile)
+        } else {
+            sDOutC = sOutA + 128;
+            sDOutA = sDOutC + 128;
+            sP0 = sDOutA + 128;                            // 3 probability tiles + 1 dS scratch, [16][17] each
+            sP1 = sP0 + 272;
+            sP2 = sP1 + 272;
+            sS = sP2 + 272;
+            sXA = sS + 272;                                // [16][kMXS] action tokens
+            sXO = sXA + kRows * kMXS;                      // [16][OS] xhat of the observation LayerNorm
+            sYO = sXO + kRows * OS;                        // [16][OS] its output (input of the encoder linear)
+            T = sYO + kRows * OS;                          // [16][68] tiles from here on
+        }
     }
 };
-// tile indices: saved activations of the critic (0-11) and the actor (12-27), scratch (28-33)
-enum { cZ1_ = 0, cN0_, cQ_, cK_, cV_, cY_, cN1_, cZM_, cN2_, cENC_, cZH_, cNH_,
-       aZ_, aN0_, aQ1_, aK1_, aV1_, aY1_, aN1_, aK2_, aV2_, aQ2_, aY2_, aN2_, aZM_, aN3_, aZH_, aNH_,
-       S0_, S1_, S2_, S3_, S4_, DENC_, MAT_NUM_TILES };
+using MatCtx = MatCtxT<false>;
 
 #define MAT_TILES(c)                                                                                              \
     float *cZ1 = c.tile(cZ1_), *cN0 = c.tile(cN0_), *cQ = c.tile(cQ_), *cK = c.tile(cK_), *cV = c.tile(cV_),       \
@@ -521,8 +548,9 @@ struct MatPanelPub {
 // else (K16: its registers are spoken for) at the point of use
 #define MAT_LIN(r, Wk, Bk, A, out) do { if (!PF) pf_fwd(W(Wk), W(Bk), wave, lane, r); lin_fwd_r(r, A, out, wave, lane); } while (0)
 #define MAT_NEXT(r, Wk, Bk) do { if (PF) pf_fwd(W(Wk), W(Bk), wave, lane, r); } while (0)
-template <bool PF, typename Pub = MatNoPub>
-__device__ __forceinline__ void mat_encoder_forward(const MatCtx& c, int tid, int wave, int lane, const Pub pub = Pub()) {
+// VALUE = false (K20): stops at rep_enc, after a barrier -- the three phases of the value head are not run
+template <bool PF, typename Pub = MatNoPub, bool VALUE = true, typename Ctx = MatCtx>
+__device__ __forceinline__ void mat_encoder_forward(const Ctx& c, int tid, int wave, int lane, const Pub pub = Pub()) {
     MAT_TILES(c);
     MatFr rq, rk, rv, rp, rm1, rm2, rh1;
     MAT_NEXT(rq, C_Q_W, C_Q_B); MAT_NEXT(rk, C_K_W, C_K_B); MAT_NEXT(rv, C_V_W, C_V_B);       // two phases ahead of their use
@@ -573,6 +601,7 @@ __device__ __forceinline__ void mat_encoder_forward(const MatCtx& c, int tid, in
     MAT_SYNC();
     MAT_STAMP(26);
     pub(X_ENC, cENC);
+    if constexpr (!VALUE) return;
     MAT_LIN(rh1, C_H1_W, C_H1_B, cENC, cZH);
     MAT_SYNC();
     MAT_STAMP(27);
@@ -585,8 +614,8 @@ __device__ __forceinline__ void mat_encoder_forward(const MatCtx& c, int tid, in
 }
 
 // actor (decoder): token block in sXA + rep_enc in cENC -> logits in sOutA; starts and ends with the tiles settled
-template <bool PF, typename Pub = MatNoPub>
-__device__ __forceinline__ void mat_decoder_forward(const MatCtx& c, int tid, int wave, int lane, const Pub pub = Pub()) {
+template <bool PF, typename Pub = MatNoPub, typename Ctx = MatCtx>
+__device__ __forceinline__ void mat_decoder_forward(const Ctx& c, int tid, int wave, int lane, const Pub pub = Pub()) {
     MAT_TILES(c);
     MatFr rk1, rq1, rv1, rp1, rk2, rv2, rq2, rp2, rm1, rm2, rh1;
     MAT_NEXT(rk1, A_K1_W, A_K1_B); MAT_NEXT(rq1, A_Q1_W, A_Q1_B); MAT_NEXT(rv1, A_V1_W, A_V1_B);
@@ -1104,6 +1133,101 @@ __global__ __launch_bounds__(kMT) void mat_policy_step_kernel(MatStepDev u) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// K20: one evaluation step of a MATPolicy for all envs in one launch (mat_policy.py:701-790 over :521-585 greedy and
+// :441-519 sampled): the encoder up to rep_enc, then L decoder passes -- agent i's env action, the argmax of pass i's
+// logits (lowest index on an exact tie) or K16's categorical draw with K16's Philox counter, becomes agent i+1's token --
+// and only the int64 env actions are stored.  No value, no log-prob, no buffer rows.  Token row s of a tile is
+// (env seq0 + s / L, slot s % L); the slot's observation row and action element are found through slot_agent and the
+// strides, so grouped [E, A, .] and the env's agent-major [A * E, .] tensors are both read and written in place.
+// COMPACT: the forward-only carve (MatCtxT<true>, 10 tiles instead of 34: three workgroups per CU instead of one).
+// ------------------------------------------------------------------------------------------------
+struct MatInferDev {
+    long off[64];
+    int O, L, NA, Ain, per_tile, mode;
+    const float* params;
+    const float* obs; long E;
+    long obs_env_stride, obs_agent_stride, act_env_stride, act_agent_stride;
+    unsigned long long seed, offset;
+    int64_t* action_out;
+    unsigned char slot_agent[16];
+};
+
+// Diagnostic builds only (-DPPOAF_MAT_INFER_VARIANT=bits, the A/B legs of profiles/eval_bench.txt): 1 = K16's full carve,
+// 2 = run the value head as K16 does.  The shipped library is variant 0.
+#ifndef PPOAF_MAT_INFER_VARIANT
+#define PPOAF_MAT_INFER_VARIANT 0
+#endif
+constexpr bool kInferCompact = !(PPOAF_MAT_INFER_VARIANT & 1);
+constexpr bool kInferValue = (PPOAF_MAT_INFER_VARIANT & 2) != 0;
+
+template <bool COMPACT, bool VALUE>
+__global__ __launch_bounds__(kMT) void mat_policy_infer_kernel(MatInferDev u) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long seq0 = (long)blockIdx.x * u.per_tile;
+    const long rem = u.E - seq0;
+    const int n_seq = (int)(rem < u.per_tile ? (rem < 0 ? 0 : rem) : u.per_tile);
+    MatCtxT<COMPACT> c;
+    c.P = u.params; c.off = u.off; c.L = u.L; c.NA = u.NA; c.Ain = u.Ain; c.n_rows = n_seq * u.L;
+    c.carve(reinterpret_cast<float*>(mat_smem), u.O);
+    MAT_TILES(c);
+    for (int i = tid; i < kRows * OS; i += kMT) sYO[i] = 0.f;
+    for (int i = tid; i < kRows * kMXS; i += kMT) sXA[i] = 0.f;
+    MAT_SYNC();
+    for (int idx = tid; idx < n_rows * O; idx += kMT) {
+        const int s = idx / O, i = idx - s * O;
+        const int q = s / L;
+        const long row = (long)u.slot_agent[s - q * L] * u.obs_agent_stride + (seq0 + q) * u.obs_env_stride;
+        sYO[s * OS + i] = u.obs[row * O + i];
+    }
+    if (tid < n_rows && tid % L == 0) sXA[tid * kMXS] = 1.0f;     // start token of agent 0 (mat_policy.py:325-333)
+    MAT_SYNC();
+    mat_encoder_forward<false, MatNoPub, VALUE>(c, tid, wave, lane);
+    MAT_SYNC();
+    const long tok0 = seq0 * L;                                  // K16's Philox counter: offset + env * L + slot
+    for (int i = 0; i < L; ++i) {
+        mat_decoder_forward<false>(c, tid, wave, lane);           // ends with a barrier
+        if (tid < n_rows && tid % L == i) {
+            int a = 0;
+            if (u.mode == PPOAF_INFER_DETERMINISTIC) {
+                float best = sOutA[tid * 8];
+#pragma unroll
+                for (int k = 1; k < 8; ++k)
+                    if (k < NA && sOutA[tid * 8 + k] > best) { best = sOutA[tid * 8 + k]; a = k; }
+            } else {
+                // K16's draw, operation for operation (mat_policy_step_kernel): the actions must be bitwise its action_out
+                float p[8];
+                float m = -INFINITY;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) if (k < NA) m = fmaxf(m, sOutA[tid * 8 + k]);
+                float ssum = 0.f;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { p[k] = k < NA ? expf(sOutA[tid * 8 + k] - m) : 0.f; ssum += p[k]; }
+                const float inv = 1.0f / ssum;
+                float s2 = 0.f;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { p[k] *= inv; s2 += p[k]; }
+                a = NA - 1;
+                float cum = 0.f;
+                const Philox4 rnd = philox4x32_10(u.seed, u.offset + (unsigned long long)(tok0 + tid), 0u);
+                const float uu = u32_to_unit(rnd.x) * s2;
+                bool found = false;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (k < NA && !found) {
+                        cum += p[k];
+                        if (uu < cum) { a = k; found = true; }
+                    }
+                }
+            }
+            const int q = tid / L;
+            u.action_out[(long)u.slot_agent[i] * u.act_agent_stride + (seq0 + q) * u.act_env_stride] = a;
+            if (i + 1 < L) sXA[(tid + 1) * kMXS + 1 + a] = 1.0f;  // agent i+1 sees agent i's action
+        }
+        MAT_SYNC();
+    }
+}
+
 // slabs -> gradient bucket in a fixed order (each thread owns a float4 column, 8 slab loads in flight at a
 // time, no LDS staging); the last workgroup folds the loss partials and advances the cursor
 constexpr int kMatRedThreads = 256;
@@ -1498,6 +1622,34 @@ static size_t mat_lds_bytes(int O) {
     return (256 + 4 * 128 + 4 * 272 + kRows * kMXS + 2 * kRows * OS + 34 * (size_t)kMTile) * 4;
 }
 
+// the offset table of MATActorCritic's parameters in module order, every tensor padded to 4 floats -> want[]; returns the
+// bucket's size in floats
+static long mat_offset_table(long O, long NA, long* want) {
+    const long D = kMD, Ain = NA + 1;
+    auto pad4 = [](long x) { return (x + 3) / 4 * 4; };
+    long sizes[MAT_NUM_PARAMS];
+    int k = 0;
+    sizes[k++] = D * Ain;
+    for (int i = 0; i < 8; ++i) sizes[k++] = D;                       // a.ln, ln1, ln2, ln3 (g, b)
+    for (int i = 0; i < 8; ++i) { sizes[k++] = D * D; sizes[k++] = D; }   // attn1 k,q,v,proj; attn2 k,q,v,proj
+    for (int i = 0; i < 2; ++i) { sizes[k++] = D * D; sizes[k++] = D; }   // mlp.0, mlp.2
+    sizes[k++] = D * D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = NA * D; sizes[k++] = NA;   // head
+    sizes[k++] = O; sizes[k++] = O; sizes[k++] = D * O; sizes[k++] = D;   // obs_encoder
+    for (int i = 0; i < 6; ++i) sizes[k++] = D;                       // c.ln, ln1, ln2
+    for (int i = 0; i < 4; ++i) { sizes[k++] = D * D; sizes[k++] = D; }   // attn k,q,v,proj
+    for (int i = 0; i < 2; ++i) { sizes[k++] = D * D; sizes[k++] = D; }   // mlp
+    sizes[k++] = D * D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = 1;         // head
+    static_assert(1 + 8 + 16 + 4 + 6 + 4 + 6 + 8 + 4 + 6 == MAT_NUM_PARAMS, "size table");
+    long off = 0;
+    for (int i = 0; i < MAT_NUM_PARAMS; ++i) { want[i] = off; off += pad4(sizes[i]); }
+    return off;
+}
+
+static size_t mat_fwd_lds_bytes(int O) {
+    const size_t OS = 16 * ((O + 15) / 16) + 4;
+    return (256 + 2 * 128 + 272 + kRows * kMXS + kRows * OS + kMatFwdTiles * (size_t)kMTile) * 4;
+}
+
 static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u) {
     PPOAF_REQUIRE(a, "mat_update: null args");
     PPOAF_REQUIRE(a->embedding == kMD, "mat_update: embedding=%d (the fused kernel is built for 64)", a->embedding);
@@ -1513,26 +1665,10 @@ static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u) {
     PPOAF_REQUIRE(!a->normalize_adv || a->adv_records, "mat_update: adv_records missing");
     PPOAF_REQUIRE(a->bucket_total % 4 == 0 && ((uintptr_t)a->params & 15) == 0 && ((uintptr_t)a->grads & 15) == 0 &&
                       ((uintptr_t)a->slabs & 15) == 0, "mat_update: buckets must be 16-byte aligned");
-    // the offset table must describe MATActorCritic's module order with every tensor padded to 4 floats
-    const long D = kMD, O = a->obs_dim, NA = a->num_actions, Ain = NA + 1;
-    auto pad4 = [](long x) { return (x + 3) / 4 * 4; };
+    const long Ain = a->num_actions + 1;
     long want[MAT_NUM_PARAMS];
     {
-        long sizes[MAT_NUM_PARAMS];
-        int k = 0;
-        sizes[k++] = D * Ain;
-        for (int i = 0; i < 8; ++i) sizes[k++] = D;                       // a.ln, ln1, ln2, ln3 (g, b)
-        for (int i = 0; i < 8; ++i) { sizes[k++] = D * D; sizes[k++] = D; }   // attn1 k,q,v,proj; attn2 k,q,v,proj
-        for (int i = 0; i < 2; ++i) { sizes[k++] = D * D; sizes[k++] = D; }   // mlp.0, mlp.2
-        sizes[k++] = D * D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = NA * D; sizes[k++] = NA;   // head
-        sizes[k++] = O; sizes[k++] = O; sizes[k++] = D * O; sizes[k++] = D;   // obs_encoder
-        for (int i = 0; i < 6; ++i) sizes[k++] = D;                       // c.ln, ln1, ln2
-        for (int i = 0; i < 4; ++i) { sizes[k++] = D * D; sizes[k++] = D; }   // attn k,q,v,proj
-        for (int i = 0; i < 2; ++i) { sizes[k++] = D * D; sizes[k++] = D; }   // mlp
-        sizes[k++] = D * D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = D; sizes[k++] = 1;         // head
-        PPOAF_REQUIRE(k == MAT_NUM_PARAMS, "mat_update: internal size table (%d)", k);
-        long off = 0;
-        for (int i = 0; i < MAT_NUM_PARAMS; ++i) { want[i] = off; off += pad4(sizes[i]); }
+        const long off = mat_offset_table(a->obs_dim, a->num_actions, want);
         PPOAF_REQUIRE(off == a->bucket_total, "mat_update: bucket_total=%ld, the topology needs %ld", (long)a->bucket_total, off);
     }
     for (int i = 0; i < MAT_NUM_PARAMS; ++i) {
@@ -1736,6 +1872,79 @@ extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_strea
     PPOAF_REQUIRE(n_wg <= 0x7fffffffL, "mat_policy_step: too many envs");
     hipLaunchKernelGGL(mat_policy_step_kernel, dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
     return check_launch("mat_policy_step");
+}
+
+#define PPOAF_LAYOUT(T, f, off) static_assert(offsetof(T, f) == off, #T "." #f)
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, obs_dim, 0);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, num_agents, 4);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, num_actions, 8);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, embedding, 12);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, offsets, 16);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, params, 528);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, obs, 536);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, E, 544);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, obs_env_stride, 552);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, obs_agent_stride, 560);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, slot_agent, 568);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, mode, 632);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, seed, 640);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, offset, 648);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, action_out, 656);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, act_env_stride, 664);
+PPOAF_LAYOUT(ppoaf_mat_infer_args_t, act_agent_stride, 672);
+static_assert(sizeof(ppoaf_mat_infer_args_t) == 680, "ppoaf_mat_infer_args_t");
+
+extern "C" int ppoaf_mat_policy_infer(const ppoaf_mat_infer_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_policy_infer: null args");
+    PPOAF_REQUIRE(a->embedding == kMD, "mat_policy_infer: embedding=%d (built for 64)", a->embedding);
+    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= 64 &&
+                      a->num_actions >= 1 && a->num_actions <= 8,
+                  "mat_policy_infer: sizes (agents %d, obs %d, actions %d) outside K16's limits (16, 64, 8)", a->num_agents,
+                  a->obs_dim, a->num_actions);
+    PPOAF_REQUIRE(a->mode == PPOAF_INFER_SAMPLE || a->mode == PPOAF_INFER_DETERMINISTIC,
+                  "mat_policy_infer: mode=%d (0 sample, 1 deterministic)", a->mode);
+    PPOAF_REQUIRE(a->E >= 0, "mat_policy_infer: negative E");
+    PPOAF_REQUIRE(a->E <= (1L << 27), "mat_policy_infer: E too large");
+    PPOAF_REQUIRE(a->params && a->obs && a->action_out, "mat_policy_infer: null pointer");
+    PPOAF_REQUIRE(((uintptr_t)a->params & 15) == 0, "mat_policy_infer: params must be 16-byte aligned");
+    PPOAF_REQUIRE(a->obs_env_stride >= 1 && a->obs_agent_stride >= 1 && a->act_env_stride >= 1 && a->act_agent_stride >= 1,
+                  "mat_policy_infer: strides must be >= 1 (obs %ld / %ld, action %ld / %ld)", (long)a->obs_env_stride,
+                  (long)a->obs_agent_stride, (long)a->act_env_stride, (long)a->act_agent_stride);
+    unsigned seen = 0;
+    for (int i = 0; i < a->num_agents; ++i) {
+        const int v = a->slot_agent[i];
+        PPOAF_REQUIRE(v >= 0 && v < a->num_agents && !((seen >> v) & 1u),
+                      "mat_policy_infer: slot_agent is not a permutation of 0..%d (slot %d holds %d)", a->num_agents - 1, i, v);
+        seen |= 1u << v;
+    }
+    long want[MAT_NUM_PARAMS];
+    mat_offset_table(a->obs_dim, a->num_actions, want);
+    for (int i = 0; i < MAT_NUM_PARAMS; ++i)
+        PPOAF_REQUIRE(a->offsets[i] == want[i], "mat_policy_infer: parameter %d sits at %ld, expected %ld", i, (long)a->offsets[i],
+                      want[i]);
+    if (a->E == 0) return PPOAF_OK;
+    MatInferDev u;
+    for (int i = 0; i < 64; ++i) u.off[i] = i < MAT_NUM_PARAMS ? a->offsets[i] : 0;
+    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = a->num_actions + 1;
+    u.per_tile = 16 / u.L; u.mode = a->mode;
+    u.params = a->params; u.obs = a->obs; u.E = a->E;
+    u.obs_env_stride = a->obs_env_stride; u.obs_agent_stride = a->obs_agent_stride;
+    u.act_env_stride = a->act_env_stride; u.act_agent_stride = a->act_agent_stride;
+    u.seed = a->seed; u.offset = a->offset; u.action_out = a->action_out;
+    for (int i = 0; i < 16; ++i) u.slot_agent[i] = (unsigned char)(i < u.L ? a->slot_agent[i] : 0);
+    const size_t lds = kInferCompact ? mat_fwd_lds_bytes(u.O) : mat_lds_bytes(u.O);
+    PPOAF_REQUIRE(lds <= 160 * 1024, "mat_policy_infer: needs %zu B of LDS (> 160 KiB)", lds);
+    const void* fn = reinterpret_cast<const void*>(mat_policy_infer_kernel<kInferCompact, kInferValue>);
+    static bool attr_set = false;
+    if (!attr_set && lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+        attr_set = true;
+    }
+    const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
+    hipLaunchKernelGGL((mat_policy_infer_kernel<kInferCompact, kInferValue>), dim3((unsigned)n_wg), dim3(kMT), lds,
+                       (hipStream_t)stream, u);
+    return check_launch("mat_policy_infer");
 }
 
 // mpi_avg_gradients at the MAT update's per-mini-batch call site (mat_policy.py:692) when the K17 peer exchange is not

@@ -179,6 +179,45 @@ __global__ __launch_bounds__(256) void eval_scores_kernel(ScoresDev u) {
     u.run_len[e] = rl;
 }
 
+// ---- the books of a multi-agent evaluation, one thread per (book, env row): the chain of eval_scores_kernel launches
+// testing.py made per agent and per policy, call for call in a register
+struct BooksDev {
+    const float* score; const uint8_t* done; const int32_t* quota; long E;
+    int A, n_books; unsigned mask[32];
+    double* run_score; int64_t* run_len;
+    int64_t* count; double* sum; double* min; double* max; int64_t* steps;
+    int32_t* remaining;
+};
+
+__global__ __launch_bounds__(256) void eval_scores_books_kernel(BooksDev u) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= u.E * u.n_books) return;
+    const int b = (int)(i / u.E);
+    const long e = i - (long)b * u.E;
+    const int64_t c = u.count[i];
+    if (c >= (int64_t)u.quota[e]) return;                 // (the count moves only where the episode closes: one test serves the chain)
+    const unsigned mask = u.mask[b];
+    double rs = u.run_score[i];
+    int64_t rl = u.run_len[i];
+    for (int a = 0; a < u.A; ++a) {
+        if (!((mask >> a) & 1u)) continue;
+        rs += (double)u.score[(long)a * u.E + e];
+        rl += 1;
+    }
+    if (u.done[e]) {                                      // with the last agent of the mask
+        u.count[i] = c + 1;
+        u.sum[i] += rs;
+        u.min[i] = fmin(u.min[i], rs);
+        u.max[i] = fmax(u.max[i], rs);
+        u.steps[i] += rl;
+        rs = 0.0;
+        rl = 0;
+        atomicSub(u.remaining + b, 1);
+    }
+    u.run_score[i] = rs;
+    u.run_len[i] = rl;
+}
+
 }  // namespace ppoaf
 
 using namespace ppoaf;
@@ -213,6 +252,22 @@ PPOAF_LAYOUT(ppoaf_eval_scores_args_t, max, 72);
 PPOAF_LAYOUT(ppoaf_eval_scores_args_t, steps, 80);
 PPOAF_LAYOUT(ppoaf_eval_scores_args_t, remaining, 88);
 static_assert(sizeof(ppoaf_eval_scores_args_t) == 96, "ppoaf_eval_scores_args_t");
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, score, 0);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, done, 8);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, quota, 16);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, E, 24);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, num_agents, 32);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, n_books, 36);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, book_mask, 40);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, run_score, 168);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, run_len, 176);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, count, 184);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, sum, 192);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, min, 200);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, max, 208);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, steps, 216);
+PPOAF_LAYOUT(ppoaf_eval_books_args_t, remaining, 224);
+static_assert(sizeof(ppoaf_eval_books_args_t) == 232, "ppoaf_eval_books_args_t");
 
 extern "C" int ppoaf_policy_infer(const ppoaf_policy_infer_args_t* a, ppoaf_stream_t stream) {
     PPOAF_REQUIRE(a, "policy_infer: null args");
@@ -252,4 +307,28 @@ extern "C" int ppoaf_eval_scores_step(const ppoaf_eval_scores_args_t* a, ppoaf_s
                 a->steps, a->remaining};
     hipLaunchKernelGGL(eval_scores_kernel, dim3((unsigned)((a->E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u);
     return check_launch("eval_scores_step");
+}
+
+extern "C" int ppoaf_eval_scores_step_books(const ppoaf_eval_books_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "eval_scores_step_books: null args");
+    PPOAF_REQUIRE(a->E >= 0 && a->E <= (1L << 27), "eval_scores_step_books: E=%ld out of range", (long)a->E);
+    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16, "eval_scores_step_books: num_agents=%d out of [1,16]", a->num_agents);
+    PPOAF_REQUIRE(a->n_books >= 1 && a->n_books <= 32, "eval_scores_step_books: n_books=%d out of [1,32]", a->n_books);
+    for (int b = 0; b < a->n_books; ++b)
+        PPOAF_REQUIRE(a->book_mask[b] > 0 && a->book_mask[b] < (1 << a->num_agents),
+                      "eval_scores_step_books: book_mask[%d]=0x%x names no agent or one beyond %d", b, (unsigned)a->book_mask[b],
+                      a->num_agents - 1);
+    PPOAF_REQUIRE(a->score && a->done && a->quota && a->run_score && a->run_len && a->count && a->sum && a->min &&
+                      a->max && a->steps && a->remaining,
+                  "eval_scores_step_books: null pointer");
+    if (a->E == 0) return PPOAF_OK;
+    BooksDev u;
+    u.score = a->score; u.done = a->done; u.quota = a->quota; u.E = (long)a->E;
+    u.A = a->num_agents; u.n_books = a->n_books;
+    for (int b = 0; b < 32; ++b) u.mask[b] = b < a->n_books ? (unsigned)a->book_mask[b] : 0u;
+    u.run_score = a->run_score; u.run_len = a->run_len; u.count = a->count; u.sum = a->sum; u.min = a->min; u.max = a->max;
+    u.steps = a->steps; u.remaining = a->remaining;
+    const long n = u.E * u.n_books;
+    hipLaunchKernelGGL(eval_scores_books_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u);
+    return check_launch("eval_scores_step_books");
 }

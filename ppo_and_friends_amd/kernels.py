@@ -485,6 +485,74 @@ def eval_scores_step(args, score, done):
     check(_lib.load().ppoaf_eval_scores_step(C.byref(args), stream()), "eval_scores_step")
 
 
+class EvalScoreBooks:
+    """
+    Device state of ppoaf_eval_scores_step_books: `len(masks)` books over the same E rows and quotas, book b summing the
+    agents whose bit is set in masks[b] (one bit: an agent's book; several: a policy's book, its agents added in
+    ascending order).  `step(score, done)` -- score float32 [num_agents, E] agent-major, done [E] -- enqueues ONE launch
+    for all books; nothing is read by the host until `remaining()`.
+    """
+
+    def __init__(self, E, num_test_runs, device, num_agents, masks, quota=None):
+        E, N, A = int(E), int(num_test_runs), int(num_agents)
+        masks = [int(m) for m in masks]
+        _req(E >= 1 and N >= 0, "EvalScoreBooks: needs E >= 1 rows and num_test_runs >= 0")
+        _req(1 <= A <= 16 and 1 <= len(masks) <= 32, "EvalScoreBooks: at most 16 agents and 32 books")
+        _req(all(0 < m < (1 << A) for m in masks), "EvalScoreBooks: every mask names at least one of the agents")
+        dev = torch.device(device)
+        if quota is None:
+            quota = torch.full((E,), N // E, dtype=torch.int32)
+            quota[:N % E] += 1
+        self.E, self.A, self.masks = E, A, masks
+        nb = len(masks)
+        self.quota = torch.as_tensor(quota, dtype=torch.int32).to(dev).contiguous()
+        _req(self.quota.numel() == E, "EvalScoreBooks: one quota per row")
+        self.run_score = torch.zeros((nb, E), dtype=torch.float64, device=dev)
+        self.run_len = torch.zeros((nb, E), dtype=torch.int64, device=dev)
+        self.count = torch.zeros((nb, E), dtype=torch.int64, device=dev)
+        self.sum = torch.zeros((nb, E), dtype=torch.float64, device=dev)
+        self.min = torch.full((nb, E), float("inf"), dtype=torch.float64, device=dev)
+        self.max = torch.full((nb, E), float("-inf"), dtype=torch.float64, device=dev)
+        self.steps = torch.zeros((nb, E), dtype=torch.int64, device=dev)
+        self.remaining_t = torch.full((nb,), int(self.quota.sum().item()), dtype=torch.int32, device=dev)
+        a = self.args = _lib.EvalBooksArgs()
+        a.E, a.num_agents, a.n_books = E, A, nb
+        for b, m in enumerate(masks):
+            a.book_mask[b] = m
+        a.quota = ptr(self.quota)
+        for f in ("run_score", "run_len", "count", "sum", "min", "max", "steps"):
+            setattr(a, f, ptr(getattr(self, f)))
+        a.remaining = ptr(self.remaining_t)
+
+    def step(self, score, done):
+        a = self.args
+        _f32(score, "score")
+        _req(done.dtype in (torch.bool, torch.uint8), f"done: expected bool or uint8, got {done.dtype}")
+        _req(score.numel() == self.A * self.E and done.numel() == self.E,
+             "EvalScoreBooks.step: score needs one value per agent and row, done one per row")
+        a.score, a.done = ptr(score), ptr(done)
+        check(_lib.load().ppoaf_eval_scores_step_books(C.byref(a), stream()), "eval_scores_step_books")
+
+    def remaining(self, book=0):
+        """The one host read of an evaluation loop: episodes `book` still owes."""
+        return int(self.remaining_t[book].item())
+
+    def results(self, book=None):
+        """Per-row results of `book` on the host, as EvalScores.results() gives them (dict of numpy arrays count, sum,
+        min, max, steps); book=None: the list over all books."""
+        host = {k: getattr(self, k).cpu().numpy() for k in ("count", "sum", "min", "max", "steps")}
+        per_book = [{k: v[b] for k, v in host.items()} for b in range(len(self.masks))]
+        return per_book if book is None else per_book[book]
+
+
+# --------------------------------------------------------------------------
+# K20: evaluation step of a MATPolicy (encoder + A decoder passes -> env actions)
+# --------------------------------------------------------------------------
+def mat_policy_infer(args):
+    """ppoaf_mat_policy_infer on a filled _lib.MatInferArgs (policies/mat_policy.py fills it once per policy)."""
+    check(_lib.load().ppoaf_mat_policy_infer(C.byref(args), stream()), "mat_policy_infer")
+
+
 # --------------------------------------------------------------------------
 # K8: ICM forward-model loss / intrinsic reward
 # --------------------------------------------------------------------------

@@ -10,7 +10,8 @@ use_huber_loss defaults to True (:27-29).
 
 Layout: a dataset row is one env step of one env with its A agents side by side
 ([A, .] items of PPOSharedEpisodeDataset); tensors are [rows, A, .] on the device.  The attention
-core is the f32-MFMA kernel K9; linears / LayerNorm / GELU are torch-ROCm.
+core is the f32-MFMA kernel K9; linears / LayerNorm / GELU are torch-ROCm.  Rollout steps (K16), mini-batch updates
+(K15) and evaluation steps (K20) of the covered shapes are one launch each.
 """
 import numpy as np
 import torch
@@ -289,18 +290,78 @@ class MATPolicy(PPOPolicy):
         return out_a
 
     def inference_unsupported_reason(self):
-        return "agent-grouped policy: the autoregressive decode runs on the network modules (a deterministic K16 is not built)"
+        """'' when get_inference_actions runs on K20 (ppoaf_mat_policy_infer: the coverage of K16 and K15, on a device
+        policy that PPO has not put on the torch path), else why the network modules decode."""
+        if self.device.type != "cuda":
+            return f"the policy lives on {self.device}: K20 needs a HIP device"
+        if getattr(self, "update_mode", "auto") == "torch":
+            return "update_mode='torch' keeps the policy on the torch-ROCm path"
+        # (asked once per evaluation step: the answer is kept for as long as the parameter bucket stays)
+        key = self.policy_params.data_ptr()
+        if getattr(self, "_infer_reason", (None, ""))[0] != key:
+            self._infer_reason = (key, self.fused_step_unsupported_reason())
+        return self._infer_reason[1]
+
+    def _infer_step(self, t_obs, deterministic, agent_major=False):
+        """
+        K20: one launch, encoder + A decoder passes -> env actions, into a reusable output tensor.  t_obs holds E * A
+        observation rows, grouped ([E, A, O], slot order; -> [E, A, 1]) or, with agent_major, as the env hands them
+        ([A * E, O], env agent order; -> [A * E, 1]): the slot order then travels in the arguments.
+        """
+        from .. import _lib
+        from .. import kernels as K
+        from ..fused_update import _describe_mat
+        A = len(self.agent_ids)
+        st = getattr(self, "_infer_state", None)
+        if st is None or st["params"] != self.policy_params.data_ptr():
+            topo, why = _describe_mat(self)
+            if topo is None:
+                raise _lib.PpoafError(f"mat inference step: {why}")
+            a = _lib.MatInferArgs()
+            a.obs_dim, a.num_agents, a.num_actions, a.embedding = topo["obs_dim"], topo["num_agents"], topo["num_actions"], 64
+            for i, o in enumerate(topo["offsets"]):
+                a.offsets[i] = o
+            a.params = self.policy_params.data_ptr()
+            st = self._infer_state = dict(params=a.params, args=a, out={}, order=None)
+        a = st["args"]
+        K._req(t_obs.is_cuda and t_obs.dtype == torch.float32 and t_obs.numel() % (A * a.obs_dim) == 0,
+               f"get_inference_actions: obs must hold [E, {A}, {a.obs_dim}] float32 values on the device")
+        E = t_obs.numel() // (A * a.obs_dim)
+        out = st["out"].get((E, agent_major))
+        if out is None:
+            out = st["out"][(E, agent_major)] = torch.zeros((A * E, 1) if agent_major else (E, A, 1), dtype=torch.int64,
+                                                            device=self.device)
+        order = tuple(self.agent_ids) if agent_major else None
+        if st["order"] != (agent_major, order):
+            for i, k in enumerate(self.agent_slot_order() if agent_major else range(A)):
+                a.slot_agent[i] = int(k)
+            st["order"] = (agent_major, order)
+        a.E = E
+        a.obs_env_stride, a.obs_agent_stride = (1, E) if agent_major else (A, 1)
+        a.act_env_stride, a.act_agent_stride = a.obs_env_stride, a.obs_agent_stride
+        t_obs = t_obs.contiguous()
+        a.obs, a.action_out = t_obs.data_ptr(), out.data_ptr()
+        a.mode = K.INFER_DETERMINISTIC if deterministic else K.INFER_SAMPLE
+        if not deterministic:
+            a.seed, a.offset = self.eval_rng().take(E * A)
+        K.mat_policy_infer(a)
+        return out
 
     def get_inference_actions(self, obs, deterministic):
         """
         mat_policy.py:701-790: encode once with the critic, then decode the agents one after the other -- sampled
         (from the evaluation's own Philox stream) or greedy.  Device tensors arrive grouped, [E, A, O], and [E, A, .]
-        is returned; numpy arrives in the reference's [A, E, O] and is swapped like there.
+        is returned; numpy arrives in the reference's [A, E, O] and is swapped like there.  On K20 (see
+        inference_unsupported_reason) all of it is one launch and the result is a reusable tensor that the next call
+        overwrites; else the network modules decode.
         """
         if len(obs.shape) < 3:
             raise ValueError(f"get_inference_actions expects a batch of grouped observations, got shape {obs.shape}")
         as_numpy = not torch.is_tensor(obs)
         t_obs = self._to_device(np.swapaxes(obs, 0, 1) if as_numpy else obs)
+        if self.inference_unsupported_reason() == "":
+            actions = self._infer_step(t_obs, deterministic)
+            return torch.swapaxes(actions, 0, 1).cpu().numpy() if as_numpy else actions
         with torch.no_grad():
             encoded_obs, _ = self.critic(t_obs)
         if deterministic:
@@ -313,6 +374,11 @@ class MATPolicy(PPOPolicy):
             finally:
                 dist.rng = rng
         return torch.swapaxes(actions, 0, 1).cpu().numpy() if as_numpy else actions
+
+    def get_inference_actions_agent_major(self, obs, deterministic):
+        """get_inference_actions on the env's own layout, K20 only: obs [A * E, O] (rows of env agent a at a * E ..) ->
+        the env's action tensor [A * E, 1]; no regrouping on the host, the slot order is an argument of the launch."""
+        return self._infer_step(obs, deterministic, agent_major=True)
 
     def get_critic_values(self, obs):
         """mat_policy.py:660-675."""

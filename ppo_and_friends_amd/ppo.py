@@ -717,7 +717,7 @@ class PPO:
         ppo.py:896-1028 for this package's batched contract: `obs` is what the env hands over (agent-major rows
         [A*E, .] or a dict keyed by agent id); every policy acts on its own agents' rows and the env's action tensor
         (or dict) is returned.  Agent-grouped policies (MAT) receive [E, A, .] in their slot order -- of `critic_obs`
-        when their actor sees the critic's observation (mat_policy.py:808-853).
+        when their actor sees the critic's observation (mat_policy.py:808-853) -- or, on K20, the env's tensor as it is.
         """
         env = self.env if env is None else env
         n_envs = env.get_batch_size()
@@ -734,11 +734,15 @@ class PPO:
         if len(groups) == 1:
             pol = groups[0][1]
             if pol.agent_grouping:
-                order = torch.as_tensor(pol.agent_slot_order(), device=obs.device)
                 if pol.expanded_actor_space:
                     if critic_obs is None:
                         raise ValueError("this policy's actor sees the critic's observation: pass critic_obs")
                     obs = critic_obs
+                if torch.is_tensor(obs) and obs.is_cuda and pol.inference_unsupported_reason() == "":
+                    # K20 reads the env's agent-major rows and writes its action tensor in place: the slot order is an
+                    # argument of the launch
+                    return pol.get_inference_actions_agent_major(obs, deterministic)
+                order = torch.as_tensor(pol.agent_slot_order(), device=obs.device)
                 g = obs.reshape((A, n_envs) + tuple(obs.shape[1:]))[order].transpose(0, 1).contiguous()
                 a = pol.get_inference_actions(g, deterministic)                     # [E, A, .]
                 return a.transpose(0, 1)[torch.argsort(order)].reshape((A * n_envs,) + tuple(a.shape[2:]))

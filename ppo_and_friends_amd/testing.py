@@ -5,9 +5,11 @@ The reference plays `num_test_runs` episodes one after the other in one env.  He
 play in parallel, and taking "the first N episodes to finish" would take the SHORTEST ones -- a bias for every env
 whose return grows with its length (CartPole).  So every env row owes a quota, N // E + (e < N % E) episodes, and the
 score bookkeeping (ppoaf_eval_scores_step, csrc/policy_infer.hip) enforces it on the device: per step the package's own
-share is the filter stack, one K19 launch per policy (ppoaf_policy_infer: actor forward -> env action) and the small
-bookkeeping launches; the host reads one int32 (`remaining`) every `check_every` steps and nothing else.  With E = 1
-this is the reference's loop.
+share is the filter stack, one launch per policy for the actions -- K19 (ppoaf_policy_infer: actor forward -> env action)
+for an MLP policy, K20 (ppoaf_mat_policy_infer: encoder + A decoder passes -> env actions, straight from and into the
+env's agent-major tensors) for a multi-agent transformer -- and one bookkeeping launch: ppoaf_eval_scores_step with one
+agent, ppoaf_eval_scores_step_books with several (every agent's book and every shared policy's book together).  The host
+reads one int32 (`remaining`) every `check_every` steps and nothing else.  With E = 1 this is the reference's loop.
 """
 import os
 
@@ -137,14 +139,21 @@ def test_policy(ppo, num_test_runs, deterministic=False, save_test_scores=False,
         check_every = int(getattr(env, "max_episode_steps", 0) or 16)
     check_every = max(1, int(check_every))
     policy_of = {a: ppo.policy_mapping_fn(a) for a in agent_ids}
-    make = (lambda: K.EvalScores(E, N, device)) if device.type == "cuda" else (lambda: _HostScores(E, N, device))
-    agent_scores = {a: make() for a in agent_ids}
     policy_agents = {p: [a for a in agent_ids if policy_of[a] == p] for p in ppo.policies}
     # a policy with one agent scores what its agent scores; with several, its episode score is the float64 sum of
     # their scores added agent by agent within a step (testing.py:93-98): one bookkeeping call per agent, the episode
     # closing with the last one
-    policy_scores = {p: make() for p, mine in policy_agents.items() if len(mine) > 1}
-    never = torch.zeros(E, dtype=torch.bool, device=device)
+    shared = [p for p, mine in policy_agents.items() if len(mine) > 1]
+    books = None
+    if device.type == "cuda" and A > 1:
+        # every agent's book and every shared policy's book in ONE launch per env step
+        masks = [1 << i for i in range(A)] + [sum(1 << agent_ids.index(a) for a in policy_agents[p]) for p in shared]
+        books = K.EvalScoreBooks(E, N, device, A, masks)
+    else:
+        make = (lambda: K.EvalScores(E, N, device)) if device.type == "cuda" else (lambda: _HostScores(E, N, device))
+        agent_scores = {a: make() for a in agent_ids}
+        policy_scores = {p: make() for p in shared}
+        never = torch.zeros(E, dtype=torch.bool, device=device)
 
     # ---- state to put back
     stack = list(ppo._filter_stack(env))
@@ -179,14 +188,19 @@ def test_policy(ppo, num_test_runs, deterministic=False, save_test_scores=False,
             else:
                 done = (terminated | truncated).reshape(-1)[:E].contiguous()
                 score = score.reshape(A, E)
-            for i, a in enumerate(agent_ids):
-                s = (score[a] if isinstance(score, dict) else score[i]).to(torch.float32).contiguous()
-                agent_scores[a].step(s, done)
-                mine = policy_agents[policy_of[a]]
-                if len(mine) > 1:
-                    policy_scores[policy_of[a]].step(s, done if a == mine[-1] else never)
+            if books is not None:
+                if isinstance(score, dict):
+                    score = torch.stack([score[a].reshape(E) for a in agent_ids])
+                books.step(score.to(torch.float32).contiguous(), done)
+            else:
+                for i, a in enumerate(agent_ids):
+                    s = (score[a] if isinstance(score, dict) else score[i]).to(torch.float32).contiguous()
+                    agent_scores[a].step(s, done)
+                    mine = policy_agents[policy_of[a]]
+                    if len(mine) > 1:
+                        policy_scores[policy_of[a]].step(s, done if a == mine[-1] else never)
             if steps % check_every == 0:
-                remaining = agent_scores[agent_ids[0]].remaining()
+                remaining = books.remaining() if books is not None else agent_scores[agent_ids[0]].remaining()
     finally:
         for w, upd, flag in switches:
             w._cfg["update"] = upd
@@ -197,7 +211,13 @@ def test_policy(ppo, num_test_runs, deterministic=False, save_test_scores=False,
             net.hidden_state = state
 
     score_info = {"num_test_runs": N}
-    rows = {a: agent_scores[a].results() for a in agent_ids}
+    if books is not None:
+        per_book = books.results()
+        rows = {a: per_book[i] for i, a in enumerate(agent_ids)}
+        policy_rows = {p: per_book[A + j] for j, p in enumerate(shared)}
+    else:
+        rows = {a: agent_scores[a].results() for a in agent_ids}
+        policy_rows = {p: policy_scores[p].results() for p in shared}
     score_info["total_time_steps"] = _reduce(rows[agent_ids[0]], N)[3]
     for a in agent_ids:
         lo, hi, avg, _ = _reduce(rows[a], N)
@@ -205,7 +225,7 @@ def test_policy(ppo, num_test_runs, deterministic=False, save_test_scores=False,
     for p, mine in policy_agents.items():
         if not mine:
             continue
-        lo, hi, avg, _ = _reduce(policy_scores[p].results() if len(mine) > 1 else rows[mine[0]], N)
+        lo, hi, avg, _ = _reduce(policy_rows[p] if len(mine) > 1 else rows[mine[0]], N)
         score_info[p] = {"low_score": lo, "high_score": hi, "avg_score": avg}
 
     num_steps = score_info["total_time_steps"]

@@ -1,19 +1,24 @@
 """
-Evaluation env-steps/s of `ppo_and_friends_amd.testing.test_policy` at two shapes, two legs in one process, alternated:
+Evaluation env-steps/s of `ppo_and_friends_amd.testing.test_policy` at three shapes, two legs in one process, alternated:
 
   shapes  c2  BatchedCartPoleEnv, E = 4096, actor 4 -> 128^3 -> 2 (Discrete(2)), observation / reward normalisers
           c3  SyntheticFixedLengthEnv, E = 4096, actor 17 -> 256^3 -> 6 (Box(6), C3's actor shape), no filters
+          c5  SyntheticFixedLengthEnv, E = 4096, O = 18, Discrete(5), 3 agents, MATPolicy defaults (C5's shape), no
+              filters; only with --shape c5 ("both" stays c2 + c3)
   legs    a   this package: test_policy (K19 `ppoaf_policy_infer` + `ppoaf_eval_scores_step` per step, one host read
               of `remaining` every check_every steps)
           b   the baseline: the same loop written only with what the package had before K19 -- the torch forward of
               PPOPolicy.get_inference_actions (actor.forward_logits + refine_prediction) and torch ops for the
               scores, same quotas, same host read
+              c5: the path evaluation took before K20 on the same object -- `inference_unsupported_reason` forced
+              non-empty, so PPO.get_inference_actions regroups and the network modules decode, and one
+              `ppoaf_eval_scores_step` launch per agent and one more per agent for the policy's book
 
 Both legs play the same number of test runs from the same env seed; env-steps/s = E x loop steps / wall time, printed as
 median and spread (min .. max) over `--repeats`, then one JSON line.  `--leg a|b --shape c2|c3 --repeats 1` under
 `rocprofv3 --kernel-trace --stats` gives the launches per evaluation step of one leg (the loop steps are printed).
 
-    python tools/eval_bench.py [--shape both|c2|c3] [--leg both|a|b] [--envs 4096] [--runs-per-env 2] [--repeats 5]
+    python tools/eval_bench.py [--shape both|c2|c3|c5] [--leg both|a|b] [--envs 4096] [--runs-per-env 2] [--repeats 5]
 """
 import argparse
 import json
@@ -57,6 +62,16 @@ def make(shape, E):
         settings = {"p": (None, probe.observation_space, probe.observation_space, Discrete(2),
                           dict(actor_kw_args=dict(net), critic_kw_args=dict(net)))}
         ppo = PPO(env_gen, settings, device=DEV, random_seed=1, envs_per_proc=E, ts_per_rollout=32, save_state=False)
+    elif shape == "c5":
+        from ppo_and_friends_amd.policies.mat_policy import MATPolicy
+
+        def env_gen():
+            env = SyntheticFixedLengthEnv(E, 18, Discrete(5), 64, DEV, reward="uniform", seed=1234, term_prob=0.02, num_agents=3)
+            env.term_table[-1] = True                 # every row finishes at least once per 64 steps
+            return env
+        sp = Box(-np.inf, np.inf, (18,), np.float32)
+        ppo = PPO(env_gen, {"p": (MATPolicy, sp, sp, Discrete(5), {})}, device=DEV, random_seed=1, envs_per_proc=E,
+                  ts_per_rollout=32, normalize_obs=False, normalize_rewards=False, save_state=False)
     else:
         space = Box(-1.0, 1.0, (6,), np.float32)
 
@@ -125,6 +140,43 @@ def leg_b(ppo, N, check_every):
                   "avg_score": float(total.sum().item() / N)}}
 
 
+def leg_b_mat(ppo, N, check_every):
+    """test_policy as it ran before K20 and the books: module decode behind PPO.get_inference_actions' regrouping, and the
+    per-agent chain of ppoaf_eval_scores_step launches (agent books + the shared policy's book)."""
+    from ppo_and_friends_amd import kernels as K
+    from ppo_and_friends_amd.testing import _reduce
+    env, pol = ppo.env, ppo.policies["p"]
+    E, agent_ids = env.get_batch_size(), list(env.agent_ids)
+    A = len(agent_ids)
+    agent_scores = [K.EvalScores(E, N, DEV) for _ in agent_ids]
+    policy_scores = K.EvalScores(E, N, DEV)
+    never = torch.zeros(E, dtype=torch.bool, device=DEV)
+    training = pol.actor_critic.training
+    pol.inference_unsupported_reason = lambda: "eval_bench leg b: the module decode"
+    pol.eval()
+    try:
+        obs, critic_obs = ppo.apply_policy_reset_constraints(*env.reset())
+        t, remaining = 0, N
+        while remaining > 0:
+            actions = ppo.get_inference_actions(obs, True, critic_obs=critic_obs, env=env)
+            obs, critic_obs, reward, terminated, truncated, _ = ppo.apply_policy_step_constraints(*env.step(actions))
+            score = ppo._natural_reward(env, reward).reshape(A, E)
+            done = (terminated | truncated).reshape(-1)[:E].contiguous()
+            for i in range(A):
+                s = score[i].to(torch.float32).contiguous()
+                agent_scores[i].step(s, done)
+                policy_scores.step(s, done if i == A - 1 else never)
+            t += 1
+            if t % check_every == 0:
+                remaining = agent_scores[0].remaining()
+    finally:
+        del pol.inference_unsupported_reason
+        pol.train() if training else pol.eval()
+    lo, hi, avg, steps = _reduce(policy_scores.results(), N)
+    return {"num_test_runs": N, "total_time_steps": _reduce(agent_scores[0].results(), N)[3],
+            "p": {"low_score": lo, "high_score": hi, "avg_score": avg}}
+
+
 def timed(fn, ppo, N, check_every):
     ppo.loop_steps[0] = 0
     torch.cuda.synchronize()
@@ -136,7 +188,7 @@ def timed(fn, ppo, N, check_every):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", default="both", choices=["both", "c2", "c3"])
+    ap.add_argument("--shape", default="both", choices=["both", "c2", "c3", "c5"])
     ap.add_argument("--leg", default="both", choices=["both", "a", "b"])
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--runs-per-env", type=int, default=2)
@@ -152,8 +204,11 @@ def main():
     result = {"envs": E, "num_test_runs": N}
     for shape in shapes:
         ppo = make(shape, E)
-        check_every = 64 if shape == "c3" else 50
-        assert ppo.policies["p"].inference_unsupported_reason() == "", ppo.policies["p"].inference_unsupported_reason()
+        check_every = 50 if shape == "c2" else 64
+        if "a" in legs:
+            assert ppo.policies["p"].inference_unsupported_reason() == "", ppo.policies["p"].inference_unsupported_reason()
+        if shape == "c5" and "b" in legs:
+            legs = dict(legs, b=leg_b_mat)
         for name, fn in legs.items():
             for _ in range(args.warmup):
                 timed(fn, ppo, N, check_every)
