@@ -14,6 +14,7 @@
 // (inverse, forward model) for the heads.  float32 MFMA (v_mfma_f32_16x16x4_f32) keeps fmaf
 // chains exact, weight gradients are written to private slabs and summed in a fixed order.
 #include "ppo_update_rowpair.hpp"
+#include "wgrad_tile.hpp"
 #include <algorithm>
 #include <cstdlib>
 
@@ -811,21 +812,26 @@ __global__ __launch_bounds__(kThreadsU) void icm_fused_kernel(IcmDev u, unsigned
 // ------------------------------------------------------------------------------------------------
 constexpr int kIcmRedThreads = 256;
 
+// the bookkeeping workgroup of a mini-batch's last launch, by ONE wave (threads 0..63): loss -> totals, cursor++
+__device__ __forceinline__ void icm_bookkeeping(const IcmDev& u) {
+    const int lane = threadIdx.x;
+    float inv = 0.f, fl = 0.f;
+    for (int g = lane; g < u.nT; g += 64) { inv += u.loss_partials[g * 2]; fl += u.loss_partials[g * 2 + 1]; }
+    inv = wave_sum(inv); fl = wave_sum(fl);
+    if (lane == 0) {
+        const float n = (float)u.B;
+        inv = u.discrete ? inv / n : inv / (n * (float)u.A);
+        fl = fl / (n * (float)u.H);
+        u.totals[0] += (double)((1.0f - u.icm_beta) * fl + u.icm_beta * inv);
+        u.totals[1] += 1.0;
+        u.cursor[0] += 1;
+    }
+}
+
 __global__ __launch_bounds__(kIcmRedThreads) void icm_reduce_kernel(IcmDev u) {
-    if (blockIdx.x == gridDim.x - 1) {                       // bookkeeping workgroup: loss -> totals, cursor++
+    if (blockIdx.x == gridDim.x - 1) {
         if (threadIdx.x >= 64) return;
-        const int lane = threadIdx.x;
-        float inv = 0.f, fl = 0.f;
-        for (int g = lane; g < u.nT; g += 64) { inv += u.loss_partials[g * 2]; fl += u.loss_partials[g * 2 + 1]; }
-        inv = wave_sum(inv); fl = wave_sum(fl);
-        if (lane == 0) {
-            const float n = (float)u.B;
-            inv = u.discrete ? inv / n : inv / (n * (float)u.A);
-            fl = fl / (n * (float)u.H);
-            u.totals[0] += (double)((1.0f - u.icm_beta) * fl + u.icm_beta * inv);
-            u.totals[1] += 1.0;
-            u.cursor[0] += 1;
-        }
+        icm_bookkeeping(u);
         return;
     }
     const long n4 = u.total >> 2;
@@ -851,15 +857,12 @@ __global__ __launch_bounds__(kIcmRedThreads) void icm_reduce_kernel(IcmDev u) {
         float4 pp = reinterpret_cast<float4*>(const_cast<float*>(u.params))[idx];
         float4 m = reinterpret_cast<float4*>(u.exp_avg)[idx];
         float4 v = reinterpret_cast<float4*>(u.exp_avg_sq)[idx];
-#define PPOAF_ADAM1(cc)                                                          \
-        {                                                                        \
-            const float gi = acc.cc * gs;                                        \
-            m.cc = u.beta1 * m.cc + (1.0f - u.beta1) * gi;                       \
-            v.cc = u.beta2 * v.cc + (1.0f - u.beta2) * gi * gi;                  \
-            pp.cc = pp.cc - step_size * (m.cc / (sqrtf(v.cc) / bc2_sqrt + u.adam_eps)); \
-        }
-        PPOAF_ADAM1(x) PPOAF_ADAM1(y) PPOAF_ADAM1(z) PPOAF_ADAM1(w)
-#undef PPOAF_ADAM1
+        auto step = [&](float& pe, float& me, float& ve, const float g) {
+            Pmv e = {pe, me, ve};
+            adam_update(e, u.beta1, u.beta2, u.adam_eps, g, gs, step_size, bc2_sqrt);
+            pe = e.p; me = e.m; ve = e.v;
+        };
+        step(pp.x, m.x, v.x, acc.x); step(pp.y, m.y, v.y, acc.y); step(pp.z, m.z, v.z, acc.z); step(pp.w, m.w, v.w, acc.w);
         reinterpret_cast<float4*>(const_cast<float*>(u.params))[idx] = pp;
         reinterpret_cast<float4*>(u.exp_avg)[idx] = m;
         reinterpret_cast<float4*>(u.exp_avg_sq)[idx] = v;
@@ -873,40 +876,15 @@ __global__ __launch_bounds__(kIcmRedThreads) void icm_reduce_kernel(IcmDev u) {
 // 16-row chunk and are folded in wave order), the biases as column sums of dz in the jobs of input piece 0.  With
 // fused_adam the job applies Adam to its elements right away (the ICM update does not clip: ppo.py:2559-2562).  Jobs are
 // dealt to XCDs in runs of the block-major list (workgroup b runs on XCD b % 8).  Last workgroup: loss -> totals, cursor.
-// (p, m, v) of one element, requested at the start of the job -- beside the operand panels, not one cold round trip after
-// the MFMAs -- and the Adam step on it (icm_reduce_kernel's arithmetic)
-struct IcmPmv { float p, m, v; };
-__device__ __forceinline__ IcmPmv icm_pmv_load(const IcmDev& u, long idx, bool ok) {
-    IcmPmv r = {0.f, 0.f, 0.f};
-    if (ok) { r.p = u.params[idx]; r.m = u.exp_avg[idx]; r.v = u.exp_avg_sq[idx]; }
-    return r;
-}
-__device__ __forceinline__ void icm_adam1(const IcmDev& u, long idx, float g, const IcmPmv& s, float step_size, float bc2_sqrt) {
-    const float gi = g * u.grad_scale;
-    const float m = u.beta1 * s.m + (1.0f - u.beta1) * gi;
-    const float v = u.beta2 * s.v + (1.0f - u.beta2) * gi * gi;
-    const_cast<float*>(u.params)[idx] = s.p - step_size * (m / (sqrtf(v) / bc2_sqrt + u.adam_eps));
-    u.exp_avg[idx] = m;
-    u.exp_avg_sq[idx] = v;
-}
-
+// The optimiser state of an element is requested at the start of the job -- beside the operand panels, not one cold round
+// trip after the MFMAs.
 __global__ __launch_bounds__(256) void icm_wgrad_kernel(IcmDev u, IcmWg w, int per_xcd) {
-    __shared__ __attribute__((aligned(16))) float s_fold[6 * 256 + 64];
+    __shared__ __attribute__((aligned(16))) float s_fold[kWgradFoldFloats];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: chunk bases below stay in scalar registers
-    if (b == 8 * per_xcd) {                                   // bookkeeping workgroup: loss -> totals, cursor++
+    if (b == 8 * per_xcd) {
         if (tid >= 64) return;
-        float inv = 0.f, fl = 0.f;
-        for (int g = lane; g < u.nT; g += 64) { inv += u.loss_partials[g * 2]; fl += u.loss_partials[g * 2 + 1]; }
-        inv = wave_sum(inv); fl = wave_sum(fl);
-        if (lane == 0) {
-            const float n = (float)u.B;
-            inv = u.discrete ? inv / n : inv / (n * (float)u.A);
-            fl = fl / (n * (float)u.H);
-            u.totals[0] += (double)((1.0f - u.icm_beta) * fl + u.icm_beta * inv);
-            u.totals[1] += 1.0;
-            u.cursor[0] += 1;
-        }
+        icm_bookkeeping(u);
         return;
     }
     const int job = w.xcd_job0[b & 7] + (b >> 3);
@@ -920,29 +898,29 @@ __global__ __launch_bounds__(256) void icm_wgrad_kernel(IcmDev u, IcmWg w, int p
     // output elements that are never stored.
     const int oc = min(ot * 16 + (lane & 15), k.n_o - 1);
     const int ic0 = min(ip * 32 + (lane & 15), k.n_i - 1), ic1 = min(ip * 32 + 16 + (lane & 15), k.n_i - 1);
-    // buffer loads: resource = the panel's base, scalar offset = segment + chunk + row quad (scalar ALU), vector offset =
-    // the lane's constant byte offset -- no vector address arithmetic per load
     const unsigned dl = 4u * (unsigned)((lane >> 4) * k.ldd + oc);
     const unsigned xl0 = 4u * (unsigned)((lane >> 4) * k.ldx + ic0), xl1 = 4u * (unsigned)((lane >> 4) * k.ldx + ic1);
-    const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(k.D), 0, 0xFFFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(k.X), 0, 0xFFFFFFFF, 0x00020000);
     // wave 0 owns the output (C layout: column = lane & 15, rows 4 (lane >> 4) + r): its elements' optimiser state first
     const int i0 = ip * 32 + (lane & 15);
     const bool adam = u.fused_adam && wave == 0;
-    IcmPmv s0[4], s1[4], sb;
+    auto state = [&](long idx, bool ok) { return pmv_load<false>(u.params, u.exp_avg, u.exp_avg_sq, idx, ok); };
+    Pmv s0[4], s1[4], sb;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int o = ot * 16 + 4 * (lane >> 4) + r;
         const long base = k.w + (long)o * k.ldw;
-        s0[r] = icm_pmv_load(u, base + i0, adam && o < k.n_o && i0 < k.n_i);
-        s1[r] = icm_pmv_load(u, base + i0 + 16, adam && o < k.n_o && i0 + 16 < k.n_i);
+        s0[r] = state(base + i0, adam && o < k.n_o && i0 < k.n_i);
+        s1[r] = state(base + i0 + 16, adam && o < k.n_o && i0 + 16 < k.n_i);
     }
     const bool has_b = ip == 0 && k.b >= 0 && lane < 16 && ot * 16 + lane < k.n_o;
-    sb = icm_pmv_load(u, k.b + ot * 16 + lane, adam && has_b);
-    const int nc = u.nT, ncs = nc * k.n_seg;                  // 16-row chunks, over all segments
+    sb = state(k.b + ot * 16 + lane, adam && has_b);
+    const int nc = u.nT;                                      // 16-row chunks of a segment; the job runs over all segments
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     float bsum = 0.f;
     constexpr int MAXC = 8;                                   // B = 256, two streams: 32 chunks over 4 waves in one batch
+    // (wgrad_accumulate's loop, kept in the kernel: as a call this kernel's register allocation grows by 6 VGPRs)
+    const __amdgpu_buffer_rsrc_t rd = wgrad_rsrc(k.D), rx = wgrad_rsrc(k.X);
+    const int ncs = nc * k.n_seg;
     const unsigned d16 = 16u * (unsigned)k.ldd, x16 = 16u * (unsigned)k.ldx;       // bytes per 4 rows
     for (int c0 = wave; c0 < ncs; c0 += 4 * MAXC) {           // wave-uniform trip count
         float a[MAXC][4], x0[MAXC][4], x1[MAXC][4];
@@ -950,60 +928,37 @@ __global__ __launch_bounds__(256) void icm_wgrad_kernel(IcmDev u, IcmWg w, int p
         for (int c = 0; c < MAXC; ++c) {
             const int ci = c0 + 4 * c;
             if (ci < ncs) {                                   // wave-uniform
+                // scalar offset = segment + chunk + row quad (scalar ALU)
                 const int sg = ci / nc, ch = ci - sg * nc;
                 const unsigned sd = (unsigned)(4 * (sg * k.seg_d + (long)ch * 16 * k.ldd));
                 const unsigned sx = (unsigned)(4 * (sg * k.seg_x + (long)ch * 16 * k.ldx));
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    a[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, dl, sd + j * d16, 0));
-                    x0[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl0, sx + j * x16, 0));
-                    x1[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl1, sx + j * x16, 0));
-                }
+                for (int j = 0; j < 4; ++j)
+                    wgrad_request_quad(rd, rx, dl, xl0, xl1, true, WgradOff{sd + j * d16, sx + j * x16}, a[c][j], x0[c][j], x1[c][j]);
             }
         }
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            if (c0 + 4 * c < ncs) {                           // wave-uniform
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x0[c][j], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x1[c][j], acc1, 0, 0, 0);
-                    bsum += a[c][j];
-                }
-            }
-        }
+        wgrad_mfma<MAXC>(a, x0, x1, true, c0, ncs, acc0, acc1, bsum);
     }
-    if (wave > 0) {
-        *reinterpret_cast<f32x4*>(s_fold + (((wave - 1) * 2 + 0) * 64 + lane) * 4) = acc0;
-        *reinterpret_cast<f32x4*>(s_fold + (((wave - 1) * 2 + 1) * 64 + lane) * 4) = acc1;
-    }
-    bsum += __shfl_xor(bsum, 16, 64);
-    bsum += __shfl_xor(bsum, 32, 64);
-    if (lane < 16) s_fold[1536 + wave * 16 + lane] = bsum;
-    __syncthreads();
+    wgrad_park(s_fold, wave, lane, acc0, acc1, bsum);
     if (wave != 0) return;
-#pragma unroll
-    for (int ww = 0; ww < 3; ++ww) {
-        acc0 += *reinterpret_cast<const f32x4*>(s_fold + ((ww * 2 + 0) * 64 + lane) * 4);
-        acc1 += *reinterpret_cast<const f32x4*>(s_fold + ((ww * 2 + 1) * 64 + lane) * 4);
-    }
+    wgrad_fold(s_fold, lane, acc0, acc1);
     float step_size = 0.f, bc2_sqrt = 1.f;
     if (u.fused_adam) { step_size = u.loss_partials[2 * u.nT]; bc2_sqrt = u.loss_partials[2 * u.nT + 1]; }
+    // the ICM update does not clip: gs = grad_scale
+    auto emit = [&](long idx, float g, const Pmv& s) {
+        u.grads[idx] = g;
+        if (u.fused_adam) adam_element(u.params, u.exp_avg, u.exp_avg_sq, u.beta1, u.beta2, u.adam_eps, idx, g, s, u.grad_scale, step_size, bc2_sqrt);
+    };
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int o = ot * 16 + 4 * (lane >> 4) + r;
         if (o < k.n_o) {
             const long base = k.w + (long)o * k.ldw;
-            if (i0 < k.n_i) { u.grads[base + i0] = acc0[r]; if (u.fused_adam) icm_adam1(u, base + i0, acc0[r], s0[r], step_size, bc2_sqrt); }
-            if (i0 + 16 < k.n_i) { u.grads[base + i0 + 16] = acc1[r]; if (u.fused_adam) icm_adam1(u, base + i0 + 16, acc1[r], s1[r], step_size, bc2_sqrt); }
+            if (i0 < k.n_i) emit(base + i0, acc0[r], s0[r]);
+            if (i0 + 16 < k.n_i) emit(base + i0 + 16, acc1[r], s1[r]);
         }
     }
-    if (has_b) {
-        const float bg = s_fold[1536 + lane] + s_fold[1536 + 16 + lane] + s_fold[1536 + 32 + lane] + s_fold[1536 + 48 + lane];
-        const long idx = k.b + ot * 16 + lane;
-        u.grads[idx] = bg;
-        if (u.fused_adam) icm_adam1(u, idx, bg, sb, step_size, bc2_sqrt);
-    }
+    if (has_b) emit(k.b + ot * 16 + lane, wgrad_bias_fold(s_fold, lane), sb);
 }
 
 static int jobs_of(const IcmBlk* blk, int i, int n, int jobs) { return (i + 1 < n ? blk[i + 1].job0 : jobs) - blk[i].job0; }

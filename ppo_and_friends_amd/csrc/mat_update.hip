@@ -17,6 +17,7 @@
 // bound, not MFMA bound -- the point is that they replace ~270 separate kernel launches.
 #include "mlp_device.hpp"
 #include "tail_sync.hpp"
+#include "wgrad_tile.hpp"
 #include <hip/hip_ext.h>
 #include <cstdlib>
 
@@ -1293,13 +1294,79 @@ __global__ __launch_bounds__(kMatRedThreads) void mat_update_reduce_kernel(MatDe
 //     -> gradient bucket, in slab order (as mat_update_reduce_kernel);
 //   last workgroup: loss partials -> totals, cursor, step counter.
 // fuse_norm: one squared-norm partial per workgroup in norm_scratch[2 + b].
+// The fused tail (round 4; single rank; mat_update_wgrad_adam_kernel) carries the same jobs through to the optimiser
+// step -- every workgroup requests the optimiser state of its elements beside its operands, forms its piece of the
+// gradient (same tiles, folds and orders), publishes its squared-norm partial as a tagged record (tail_sync.hpp), waits
+// for all records, and applies clip + Adam (ppoaf_adam_step_prenormed's arithmetic: mat_policy.py:677-699, ONE optimiser
+// over actor + critic) to exactly those elements.  mat_update_wgrad_kernel + clip_adam_kernel (7.6 + 5.1 us at C5) become
+// one launch.  Parameters, moments and the gradient bucket end bitwise as after the two launches.
 constexpr int kMatWgJobs = kMatLin * 8;
-__global__ __launch_bounds__(256) void mat_update_wgrad_kernel(MatDev u, int n_small_blocks) {
-    __shared__ double s_red[17];
-    __shared__ __attribute__((aligned(16))) float s_fold[2 * 3 * 256 + 64];
+struct MatAdam { float* exp_avg; float* exp_avg_sq; const float* lr; float beta1, beta2, eps, grad_scale, max_norm; float* grad_norm_out; };
+
+// element sidx of the compact slabs of the small tensors, added in slab order: one float per thread, every slab's value
+// requested before the first add (one cold round trip for nT <= 64; float4 columns would need 256 registers for that and
+// halve the job workgroups' occupancy) ...
+__device__ __forceinline__ float mat_small_fold(const MatDev& u, const int sidx) {
+    const long stride = u.slab_stride;
+    float acc = 0.f;
+    constexpr int SB = 64;
+    for (int g0 = 0; g0 < u.nT; g0 += SB) {
+        float v[SB];
+#pragma unroll
+        for (int kk = 0; kk < SB; ++kk) v[kk] = (g0 + kk < u.nT) ? u.slabs[(long)(g0 + kk) * stride + sidx] : 0.f;
+#pragma unroll
+        for (int kk = 0; kk < SB; ++kk) acc += v[kk];
+    }
+    return acc;
+}
+// ... and its place in the bucket
+__device__ __forceinline__ long mat_small_dst(const MatDev& u, const int sidx) {
+    int seg = 0;
+    for (int j = 1; j < u.n_seg; ++j) if (sidx >= u.seg_start[j]) seg = j;
+    return (long)u.seg_dst[seg] + (sidx - u.seg_start[seg]);
+}
+
+// TAIL == false: the gradient goes to the bucket, fuse_norm leaves the workgroup's squared-norm partial in
+// norm_scratch[2 + b] (s_tile, s_coef, ad and td are not used).  TAIL == true: the fused tail.
+template <bool TAIL>
+__device__ __forceinline__ void mat_wgrad_body(const MatDev& u, const int n_small_blocks, const MatAdam& ad, const TailDev& td, double* s_red,
+                                               float* s_fold, float* s_tile, float* s_coef) {
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // scalar: the chunk offsets below stay in scalar registers
-    if (b == kMatWgJobs + n_small_blocks) { mat_update_bookkeeping(u); return; }          // uniform per workgroup
+    TailPre pre = {};
+    if constexpr (TAIL) {
+        // read BEFORE this workgroup publishes: the bookkeeping workgroup rewrites them only after everybody has
+        pre.seq = __hip_atomic_load(&td.ctl->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pre.t = (long long)u.step_count[0];
+        pre.lr = ad.lr[0];
+        pre.bc.t = td.ctl->bc_t[0];
+        pre.bc.bc1 = td.ctl->bc[0];
+        pre.bc.bc2s = td.ctl->bc[1];
+        if (b == td.nblk) {
+            // bookkeeping: totals and cursor need nobody; the step counter and the launch tag move after all have published
+            if (tid >= 64) return;
+            MatDev ub = u;
+            ub.fuse_norm = 0;                                  // (the step counter is advanced below, after the wait)
+            mat_update_bookkeeping(ub);
+            const long long t_next = pre.t + 1;
+            double c_next[2] = {0.0, 0.0};
+            if (tid == 0) {
+                c_next[0] = 1.0 - pow((double)ad.beta1, (double)(t_next + 1));
+                c_next[1] = sqrt(1.0 - pow((double)ad.beta2, (double)(t_next + 1)));
+            }
+            double sq, unused;
+            tail_gather(td, tail_tag(pre.seq), sq, unused);
+            if (tid == 0) {
+                u.step_count[0] = t_next;
+                u.norm_scratch[0] = sq;
+                td.ctl->bc_t[0] = t_next + 1;
+                td.ctl->bc[0] = c_next[0];
+                td.ctl->bc[1] = c_next[1];
+                __hip_atomic_store(&td.ctl->seq, pre.seq + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            return;
+        }
+    } else if (b == kMatWgJobs + n_small_blocks) { mat_update_bookkeeping(u); return; }   // uniform per workgroup
     double q = 0.0;
     if (b < kMatWgJobs) {
         // a job = 16 output rows x 32 input columns of one linear's dW: the X operand then uses whole 128-byte lines and
@@ -1310,311 +1377,116 @@ __global__ __launch_bounds__(256) void mat_update_wgrad_kernel(MatDev u, int n_s
         const int k = job >> 3, ot = (job >> 1) & 3, ih = job & 1;
         const int wk = kMatLinW[k];
         const long plane = (long)u.R * kMD;
-        // buffer loads: resource = the panel, scalar offset = chunk + row quad, vector offset = the lane's constant byte
-        // offset: no vector address arithmetic per load (the same launch with 64-bit addresses spent as many VALU
-        // instructions on addresses as on everything else)
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(u.dpanel + (long)k * plane, 0, 0xFFFFFFFF, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(u.xpanel + (long)kMatLinX[k] * plane, 0, 0xFFFFFFFF, 0x00020000);
-        const unsigned dl = 4u * (unsigned)((lane >> 4) * kMD + ot * 16 + (lane & 15));
-        const unsigned xl = 4u * (unsigned)((lane >> 4) * kMD + ih * 32 + (lane & 15));
-        const int nc = u.nT;                                   // 16-row chunks
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        float bsum = 0.f;
+        // TAIL: this thread's two elements of the 16 x 32 piece (row e / 32, column e % 32) and, threads 64..79 of the jobs
+        // of input half 0, one bias: optimiser state first
+        long eidx[2] = {0, 0};
+        Pmv se[2], sb;
+        const bool has_b = ih == 0 && tid >= 64 && tid < 80;
+        const long bidx = u.off[wk + 1] + ot * 16 + (tid - 64);
+        if constexpr (TAIL) {
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {
+                const int e = tid + 256 * kk, row = e >> 5, col = e & 31;
+                eidx[kk] = u.off[wk] + (long)(ot * 16 + row) * kMD + ih * 32 + col;
+                se[kk] = pmv_load<false>(u.params, ad.exp_avg, ad.exp_avg_sq, eidx[kk], true);
+            }
+            sb = pmv_load<false>(u.params, ad.exp_avg, ad.exp_avg_sq, bidx, has_b);
+        }
         // every operand of the job is requested before the first MFMA (the panels were written by other XCDs a moment
         // ago: each batch is one cold round trip, so there must be one batch at the BASELINE sizes: 52 chunks / 4 waves)
         constexpr int MAXC = 16;
-        for (int c0 = wave; c0 < nc; c0 += 4 * MAXC) {         // wave-uniform trip count
-            float a[MAXC][4], x0[MAXC][4], x1[MAXC][4];
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                const int ch = c0 + 4 * c;
-                if (ch < nc) {                                 // wave-uniform
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const unsigned so = 4u * (unsigned)((16 * ch + 4 * j) * kMD);
-                        a[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, dl, so, 0));
-                        x0[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl, so, 0));
-                        x1[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl + 64u, so, 0));
-                    }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                if (c0 + 4 * c < nc) {                         // wave-uniform
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x0[c][j], acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x1[c][j], acc1, 0, 0, 0);
-                        bsum += a[c][j];
-                    }
-                }
-            }
-        }
-        // fold the four waves' partial tiles in wave order (waves 1..3 park theirs in LDS)
-        if (wave > 0) {
-            *reinterpret_cast<f32x4*>(s_fold + (((wave - 1) * 2 + 0) * 64 + lane) * 4) = acc0;
-            *reinterpret_cast<f32x4*>(s_fold + (((wave - 1) * 2 + 1) * 64 + lane) * 4) = acc1;
-        }
-        bsum += __shfl_xor(bsum, 16, 64);
-        bsum += __shfl_xor(bsum, 32, 64);
-        if (lane < 16) s_fold[1536 + wave * 16 + lane] = bsum;
-        __syncthreads();
+        const unsigned dl = 4u * (unsigned)((lane >> 4) * kMD + ot * 16 + (lane & 15));
+        const unsigned xl = 4u * (unsigned)((lane >> 4) * kMD + ih * 32 + (lane & 15));
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        float bsum = 0.f;
+        wgrad_accumulate<MAXC>(wgrad_rsrc(u.dpanel + (long)k * plane), wgrad_rsrc(u.xpanel + (long)kMatLinX[k] * plane), dl, xl, xl + 64u, wave,
+                               u.nT /* 16-row chunks */, [](int ch) { const unsigned so = 4u * (unsigned)(16 * ch * kMD); return WgradOff{so, so}; },
+                               WgradOff{16u * kMD, 16u * kMD},
+                               acc0, acc1, bsum);
+        wgrad_park(s_fold, wave, lane, acc0, acc1, bsum);
         if (wave == 0) {
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                acc0 += *reinterpret_cast<const f32x4*>(s_fold + ((w * 2 + 0) * 64 + lane) * 4);
-                acc1 += *reinterpret_cast<const f32x4*>(s_fold + ((w * 2 + 1) * 64 + lane) * 4);
-            }
+            wgrad_fold(s_fold, lane, acc0, acc1);
             float* GW = u.grads + u.off[wk];
             const int i = ih * 32 + (lane & 15);               // C layout: column = lane & 15, rows 4 (lane >> 4) + r
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int o = ot * 16 + 4 * (lane >> 4) + r;
-                GW[o * kMD + i] = acc0[r];
-                GW[o * kMD + i + 16] = acc1[r];
+                const int row = 4 * (lane >> 4) + r;
+                if constexpr (TAIL) {
+                    s_tile[row * 32 + (lane & 15)] = acc0[r];
+                    s_tile[row * 32 + 16 + (lane & 15)] = acc1[r];
+                } else {
+                    GW[(ot * 16 + row) * kMD + i] = acc0[r];
+                    GW[(ot * 16 + row) * kMD + i + 16] = acc1[r];
+                }
                 q += (double)acc0[r] * acc0[r] + (double)acc1[r] * acc1[r];
             }
             if (ih == 0 && lane < 16) {
-                const float bg = s_fold[1536 + lane] + s_fold[1536 + 16 + lane] + s_fold[1536 + 32 + lane] + s_fold[1536 + 48 + lane];
-                u.grads[u.off[wk + 1] + ot * 16 + lane] = bg;
+                const float bg = wgrad_bias_fold(s_fold, lane);
+                if constexpr (TAIL) s_tile[512 + lane] = bg;
+                else u.grads[u.off[wk + 1] + ot * 16 + lane] = bg;
                 q += (double)bg * bg;
             }
+            if constexpr (TAIL) {
+                q = tail_wave_sum(q);                          // block_sum of the wgrad launch: this wave's sum + three exact zeros
+                tail_sync_wave0(td, b, pre, ad.beta1, ad.beta2, ad.max_norm, ad.grad_scale, 0, ad.grad_norm_out, q, s_coef);
+            }
+        }
+        if constexpr (TAIL) {
+            __syncthreads();
+            const float gs = s_coef[0], step_size = s_coef[1], bc2_sqrt = s_coef[2];
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+                adam_element(u.params, ad.exp_avg, ad.exp_avg_sq, ad.beta1, ad.beta2, ad.eps, eidx[kk], s_tile[tid + 256 * kk], se[kk], gs, step_size, bc2_sqrt);
+            if (has_b) adam_element(u.params, ad.exp_avg, ad.exp_avg_sq, ad.beta1, ad.beta2, ad.eps, bidx, s_tile[512 + tid - 64], sb, gs, step_size, bc2_sqrt);
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) u.grads[eidx[kk]] = s_tile[tid + 256 * kk];
+            if (has_b) u.grads[bidx] = s_tile[512 + tid - 64];
         }
     } else {
-        // one float per thread, every slab's value requested before the first add (one cold round trip for nT <= 64;
-        // float4 columns would need 256 registers for that and halve the job workgroups' occupancy)
         const int sidx = (b - kMatWgJobs) * 256 + tid;
-        if (sidx < 4 * u.n_small4) {
-            const long stride = u.slab_stride;
+        const bool live = sidx < 4 * u.n_small4;
+        if constexpr (TAIL) {
+            const long gidx = live ? mat_small_dst(u, sidx) : 0;
+            const Pmv st = pmv_load<false>(u.params, ad.exp_avg, ad.exp_avg_sq, gidx, live);
             float acc = 0.f;
-            constexpr int SB = 64;
-            for (int g0 = 0; g0 < u.nT; g0 += SB) {
-                float v[SB];
-#pragma unroll
-                for (int kk = 0; kk < SB; ++kk) v[kk] = (g0 + kk < u.nT) ? u.slabs[(long)(g0 + kk) * stride + sidx] : 0.f;
-#pragma unroll
-                for (int kk = 0; kk < SB; ++kk) acc += v[kk];
+            if (live) {
+                acc = mat_small_fold(u, sidx);
+                u.grads[gidx] = acc;
+                q = (double)acc * acc;
             }
-            int seg = 0;
-            for (int j = 1; j < u.n_seg; ++j) if (sidx >= u.seg_start[j]) seg = j;
-            u.grads[u.seg_dst[seg] + (sidx - u.seg_start[seg])] = acc;
+            // block_sum(q) in its own association: wave sums, then the wave sum of the four of them
+            q = tail_wave_sum(q);
+            if (lane == 0) s_red[wave] = q;
+            __syncthreads();
+            if (wave == 0) {
+                q = tail_wave_sum(lane < 4 ? s_red[lane] : 0.0);
+                tail_sync_wave0(td, b, pre, ad.beta1, ad.beta2, ad.max_norm, ad.grad_scale, 0, ad.grad_norm_out, q, s_coef);
+            }
+            __syncthreads();
+            if (live) adam_element(u.params, ad.exp_avg, ad.exp_avg_sq, ad.beta1, ad.beta2, ad.eps, gidx, acc, st, s_coef[0], s_coef[1], s_coef[2]);
+        } else if (live) {
+            const float acc = mat_small_fold(u, sidx);
+            u.grads[mat_small_dst(u, sidx)] = acc;
             q = (double)acc * acc;
         }
     }
-    if (u.fuse_norm) {                                          // uniform per launch
+    if (!TAIL && u.fuse_norm) {                                 // uniform per launch
         q = block_sum(q, s_red);
         if (tid == 0) u.norm_scratch[2 + b] = q;
     }
 }
 
-// ---- fused tail of K15's split-wgrad chain (round 4; single rank): mat_update_wgrad_kernel's jobs carried through to the
-// optimiser step -- every workgroup requests the optimiser state of its elements beside its operands, forms its piece of
-// the gradient (same tiles, folds and orders), publishes its squared-norm partial as a tagged record (tail_sync.hpp),
-// waits for all records, and applies clip + Adam (ppoaf_adam_step_prenormed's arithmetic: mat_policy.py:677-699, ONE
-// optimiser over actor + critic) to exactly those elements.  mat_update_wgrad_kernel + clip_adam_kernel (7.6 + 5.1 us at
-// C5) become one launch.  Parameters, moments and the gradient bucket end bitwise as after the two launches.
-struct MatAdam { float* exp_avg; float* exp_avg_sq; const float* lr; float beta1, beta2, eps, grad_scale, max_norm; float* grad_norm_out; };
-struct MatPmv { float p, m, v; };
-__device__ __forceinline__ MatPmv mat_pmv_load(const MatDev& u, const MatAdam& ad, const long idx, const bool ok) {
-    MatPmv r = {0.f, 0.f, 0.f};
-    if (ok) { r.p = u.params[idx]; r.m = ad.exp_avg[idx]; r.v = ad.exp_avg_sq[idx]; }
-    return r;
+__global__ __launch_bounds__(256) void mat_update_wgrad_kernel(MatDev u, int n_small_blocks) {
+    __shared__ double s_red[17];
+    __shared__ __attribute__((aligned(16))) float s_fold[kWgradFoldFloats];
+    mat_wgrad_body<false>(u, n_small_blocks, MatAdam(), TailDev(), s_red, s_fold, nullptr, nullptr);
 }
-__device__ __forceinline__ void mat_adam1(const MatDev& u, const MatAdam& ad, const long idx, const float g, const MatPmv& s,
-                                          const float gs, const float step_size, const float bc2_sqrt) {
-    const float gi = g * gs;                                   // clip_adam_kernel, expression for expression
-    const float mi = ad.beta1 * s.m + (1.0f - ad.beta1) * gi;
-    const float vi = ad.beta2 * s.v + (1.0f - ad.beta2) * gi * gi;
-    ad.exp_avg[idx] = mi;
-    ad.exp_avg_sq[idx] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + ad.eps;
-    const_cast<float*>(u.params)[idx] = s.p - step_size * (mi / denom);
-}
-// wave 0 of a workgroup: publish q, wait for everybody's, coefficients into s_coef (t = the step being taken)
-__device__ __forceinline__ void mat_tail_sync_wave0(const MatAdam& ad, const TailDev& td, const unsigned tag, const int b, const long long t_next,
-                                                    const long long pre_t, double bc1, double bc2s, const float lr, const double q, float* s_coef) {
-    if (threadIdx.x == 0) tail_publish(td, tag, b, q);
-    if (pre_t != t_next) {                                     // uniform: first launch / restored state
-        bc1 = 1.0 - pow((double)ad.beta1, (double)t_next);
-        bc2s = sqrt(1.0 - pow((double)ad.beta2, (double)t_next));
-    }
-    double sq, unused;
-    tail_gather(td, tag, sq, unused);
-    if (threadIdx.x == 0) {
-        const float total_norm = (float)sqrt(sq);
-        float coef = 1.0f;
-        if (ad.max_norm > 0.f) coef = fminf(ad.max_norm / (total_norm + 1e-6f), 1.0f);
-        s_coef[0] = ad.grad_scale * coef;
-        s_coef[1] = (float)((double)lr / bc1);
-        s_coef[2] = (float)bc2s;
-        if (b == 0 && ad.grad_norm_out) ad.grad_norm_out[0] = total_norm;
-    }
-}
-
 __global__ __launch_bounds__(256) void mat_update_wgrad_adam_kernel(MatDev u, int n_small_blocks, MatAdam ad, TailDev td) {
     __shared__ double s_red[17];
-    __shared__ __attribute__((aligned(16))) float s_fold[2 * 3 * 256 + 64];
+    __shared__ __attribute__((aligned(16))) float s_fold[kWgradFoldFloats];
     __shared__ float s_tile[16 * 32 + 16];
     __shared__ float s_coef[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned long long seq = __hip_atomic_load(&td.ctl->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned tag = ((unsigned)seq & 0x7fffffffu) + 1u;
-    // read BEFORE this workgroup publishes: the bookkeeping workgroup rewrites them only after everybody has
-    const long long t_next = (long long)u.step_count[0] + 1;
-    const float lr = ad.lr[0];
-    const long long pre_t = td.ctl->bc_t[0];
-    const double pre_bc1 = td.ctl->bc[0], pre_bc2s = td.ctl->bc[1];
-    if (b == td.nblk) {
-        // bookkeeping: totals and cursor need nobody; the step counter and the launch tag move after all have published
-        if (tid >= 64) return;
-        const int keep_fuse = u.fuse_norm;
-        MatDev ub = u;
-        ub.fuse_norm = 0;                                      // (the step counter is advanced below, after the wait)
-        mat_update_bookkeeping(ub);
-        (void)keep_fuse;
-        double c_next[2] = {0.0, 0.0};
-        if (tid == 0) {
-            c_next[0] = 1.0 - pow((double)ad.beta1, (double)(t_next + 1));
-            c_next[1] = sqrt(1.0 - pow((double)ad.beta2, (double)(t_next + 1)));
-        }
-        double sq, unused;
-        tail_gather(td, tag, sq, unused);
-        if (tid == 0) {
-            u.step_count[0] = t_next;
-            u.norm_scratch[0] = sq;
-            td.ctl->bc_t[0] = t_next + 1;
-            td.ctl->bc[0] = c_next[0];
-            td.ctl->bc[1] = c_next[1];
-            __hip_atomic_store(&td.ctl->seq, seq + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        return;
-    }
-    double q = 0.0;
-    if (b < kMatWgJobs) {
-        constexpr int per_xcd = kMatWgJobs / 8;
-        const int job = (b & 7) * per_xcd + (b >> 3);
-        const int k = job >> 3, ot = (job >> 1) & 3, ih = job & 1;
-        const int wk = kMatLinW[k];
-        const long plane = (long)u.R * kMD;
-        // this thread's two elements of the 16 x 32 piece (row e / 32, column e % 32) and, threads 64..79 of the jobs of
-        // input half 0, one bias: optimiser state first
-        long eidx[2];
-        MatPmv se[2], sb;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const int e = tid + 256 * kk, row = e >> 5, col = e & 31;
-            eidx[kk] = u.off[wk] + (long)(ot * 16 + row) * kMD + ih * 32 + col;
-            se[kk] = mat_pmv_load(u, ad, eidx[kk], true);
-        }
-        const bool has_b = ih == 0 && tid >= 64 && tid < 80;
-        const long bidx = u.off[wk + 1] + ot * 16 + (tid - 64);
-        sb = mat_pmv_load(u, ad, bidx, has_b);
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(u.dpanel + (long)k * plane, 0, 0xFFFFFFFF, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(u.xpanel + (long)kMatLinX[k] * plane, 0, 0xFFFFFFFF, 0x00020000);
-        const unsigned dl = 4u * (unsigned)((lane >> 4) * kMD + ot * 16 + (lane & 15));
-        const unsigned xl = 4u * (unsigned)((lane >> 4) * kMD + ih * 32 + (lane & 15));
-        const int nc = u.nT;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        float bsum = 0.f;
-        constexpr int MAXC = 16;
-        for (int c0 = wave; c0 < nc; c0 += 4 * MAXC) {         // wave-uniform trip count
-            float a[MAXC][4], x0[MAXC][4], x1[MAXC][4];
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                const int ch = c0 + 4 * c;
-                if (ch < nc) {                                 // wave-uniform
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const unsigned so = 4u * (unsigned)((16 * ch + 4 * j) * kMD);
-                        a[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, dl, so, 0));
-                        x0[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl, so, 0));
-                        x1[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl + 64u, so, 0));
-                    }
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < MAXC; ++c) {
-                if (c0 + 4 * c < nc) {                         // wave-uniform
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x0[c][j], acc0, 0, 0, 0);
-                        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x1[c][j], acc1, 0, 0, 0);
-                        bsum += a[c][j];
-                    }
-                }
-            }
-        }
-        if (wave > 0) {
-            *reinterpret_cast<f32x4*>(s_fold + (((wave - 1) * 2 + 0) * 64 + lane) * 4) = acc0;
-            *reinterpret_cast<f32x4*>(s_fold + (((wave - 1) * 2 + 1) * 64 + lane) * 4) = acc1;
-        }
-        bsum += __shfl_xor(bsum, 16, 64);
-        bsum += __shfl_xor(bsum, 32, 64);
-        if (lane < 16) s_fold[1536 + wave * 16 + lane] = bsum;
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                acc0 += *reinterpret_cast<const f32x4*>(s_fold + ((w * 2 + 0) * 64 + lane) * 4);
-                acc1 += *reinterpret_cast<const f32x4*>(s_fold + ((w * 2 + 1) * 64 + lane) * 4);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 4 * (lane >> 4) + r;
-                s_tile[row * 32 + (lane & 15)] = acc0[r];
-                s_tile[row * 32 + 16 + (lane & 15)] = acc1[r];
-                q += (double)acc0[r] * acc0[r] + (double)acc1[r] * acc1[r];
-            }
-            if (ih == 0 && lane < 16) {
-                const float bg = s_fold[1536 + lane] + s_fold[1536 + 16 + lane] + s_fold[1536 + 32 + lane] + s_fold[1536 + 48 + lane];
-                s_tile[512 + lane] = bg;
-                q += (double)bg * bg;
-            }
-            q = tail_wave_sum(q);                              // block_sum of the wgrad launch: this wave's sum + three exact zeros
-            mat_tail_sync_wave0(ad, td, tag, b, t_next, pre_t, pre_bc1, pre_bc2s, lr, q, s_coef);
-        }
-        __syncthreads();
-        const float gs = s_coef[0], step_size = s_coef[1], bc2_sqrt = s_coef[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) mat_adam1(u, ad, eidx[kk], s_tile[tid + 256 * kk], se[kk], gs, step_size, bc2_sqrt);
-        if (has_b) mat_adam1(u, ad, bidx, s_tile[512 + tid - 64], sb, gs, step_size, bc2_sqrt);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) u.grads[eidx[kk]] = s_tile[tid + 256 * kk];
-        if (has_b) u.grads[bidx] = s_tile[512 + tid - 64];
-    } else {
-        // compact slabs of the small tensors: one float per thread (mat_update_wgrad_kernel's fold), then its Adam step
-        const int sidx = (b - kMatWgJobs) * 256 + tid;
-        const bool live = sidx < 4 * u.n_small4;
-        int seg = 0;
-        for (int j = 1; j < u.n_seg; ++j) if (sidx >= u.seg_start[j]) seg = j;
-        const long gidx = live ? (long)u.seg_dst[seg] + (sidx - u.seg_start[seg]) : 0;
-        const MatPmv st = mat_pmv_load(u, ad, gidx, live);
-        float acc = 0.f;
-        if (live) {
-            const long stride = u.slab_stride;
-            constexpr int SB = 64;
-            for (int g0 = 0; g0 < u.nT; g0 += SB) {
-                float v[SB];
-#pragma unroll
-                for (int kk = 0; kk < SB; ++kk) v[kk] = (g0 + kk < u.nT) ? u.slabs[(long)(g0 + kk) * stride + sidx] : 0.f;
-#pragma unroll
-                for (int kk = 0; kk < SB; ++kk) acc += v[kk];
-            }
-            u.grads[gidx] = acc;
-            q = (double)acc * acc;
-        }
-        // block_sum(q) in its own association: wave sums, then the wave sum of the four of them
-        q = tail_wave_sum(q);
-        if (lane == 0) s_red[wave] = q;
-        __syncthreads();
-        if (wave == 0) {
-            q = tail_wave_sum(lane < 4 ? s_red[lane] : 0.0);
-            mat_tail_sync_wave0(ad, td, tag, b, t_next, pre_t, pre_bc1, pre_bc2s, lr, q, s_coef);
-        }
-        __syncthreads();
-        if (live) mat_adam1(u, ad, gidx, acc, st, s_coef[0], s_coef[1], s_coef[2]);
-    }
+    mat_wgrad_body<true>(u, n_small_blocks, ad, td, s_red, s_fold, s_tile, s_coef);
 }
 
 static size_t mat_lds_bytes(int O) {

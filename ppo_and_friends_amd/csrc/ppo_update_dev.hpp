@@ -1,8 +1,9 @@
-// Shared by the fused PPO update kernels (ppo_update.hip: row-tiled three-launch chain and its single-XCD
-// persistent form; ppo_update_ws.hip: weight-stationary persistent form): the device view of the C-ABI
-// arguments and the distribution head + loss terms of one 16-row block.
+// Shared by the fused PPO update kernels (ppo_update.hip: fwd_bwd and the separate reduce / Adam launches;
+// ppo_update_split.hip, ppo_update_tail.hip: the split-wgrad chain): the device view of the C-ABI arguments, the job
+// list of the split-wgrad launches and the distribution head + loss terms of one 16-row block.
 #pragma once
 #include "action_heads.hpp"
+#include "wgrad_tile.hpp"
 #include <cstddef>
 #include <cstring>
 
@@ -115,6 +116,60 @@ inline size_t pair_region_layout(const UpdateDev& u, PairDev* p, char* region) {
 }
 
 constexpr int kWgradThreads = 256;
+
+// One job of a network's layer-major job list (split_wgrad_jobs): a 16 x 32 piece of layer l's dW -- output tile ot, input
+// tiles itile and itile + 1 (the second may not exist: odd tile counts) -- or, behind those, the output layer's segment.
+// Offsets are floats inside the network's part of the bucket.
+struct SplitJob {
+    int l, ot, itile;
+    bool two;                                             // uniform per workgroup
+    long ldw;                                             // row stride of W_l
+    long off_w, off_b;                                    // W_l, b_l
+};
+template <int H>
+__device__ __forceinline__ long split_off_w(const NetDev& nd, const int l) {
+    const long szW0 = ((long)H * nd.in_dim + 3) & ~3L;
+    return l == 0 ? 0 : szW0 + H + (long)(l - 1) * ((long)H * H + H);
+}
+// false: `job` is the network's output-segment job (which starts at split_off_w<H>(nd, nd.depth))
+template <int H>
+__device__ __forceinline__ bool split_job_decode(const UpdateDev& u, const int which, const int job, SplitJob& sj) {
+    const auto& nd = u.net[which];
+    const int in_dim = nd.in_dim, depth = nd.depth;
+    constexpr int t = H / 16, t2 = (t + 1) / 2;
+    const int n_it0 = (in_dim + 15) / 16, p0 = (n_it0 + 1) / 2;
+    const int n_hidden = (depth - 1) * t * t2, n_l0 = t * p0;
+    if (job >= n_hidden + n_l0) return false;
+    int n_it;
+    if (job < n_hidden) { sj.l = 1 + job / (t * t2); const int jj = job % (t * t2); sj.ot = jj / t2; sj.itile = 2 * (jj % t2); n_it = t; }
+    else { sj.l = 0; const int jj = job - n_hidden; sj.ot = jj / p0; sj.itile = 2 * (jj % p0); n_it = n_it0; }
+    const int l = sj.l;
+    sj.two = sj.itile + 1 < n_it;
+    sj.ldw = l >= 1 ? H : in_dim;
+    sj.off_w = split_off_w<H>(nd, l);
+    sj.off_b = l == 0 ? (((long)H * in_dim + 3) & ~3L)
+                      : sj.off_w + (l < depth ? (long)H * H : (((long)nd.out_dim * H + 3) & ~3L));
+    return true;
+}
+// layer l's dz panel and input panel (the mini-batch's gathered input rows for layer 0) as buffer resources
+template <int H> __device__ __forceinline__ __amdgpu_buffer_rsrc_t split_panel_d(const UpdateDev& u, const int which, const int l) {
+    return wgrad_rsrc(u.sp.dbuf[which] + (long)l * ((long)u.sp.Bp * H));
+}
+template <int H> __device__ __forceinline__ __amdgpu_buffer_rsrc_t split_panel_x(const UpdateDev& u, const int which, const int l) {
+    return wgrad_rsrc(l >= 1 ? u.sp.hbuf[which] + (long)(l - 1) * ((long)u.sp.Bp * H) : u.sp.xbuf[which]);
+}
+// Element idx of the output layer's segment (+ log_std): fwd_bwd's row-block partials added in block order, 8 in flight
+__device__ __forceinline__ float split_out_fold(const float* outpart, const int n_hb, const long seg_len, const long idx) {
+    float acc = 0.f;
+    for (int g0 = 0; g0 < n_hb; g0 += 8) {
+        float pv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pv[k] = outpart[(long)(g0 + k < n_hb ? g0 + k : 0) * seg_len + idx];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) if (g0 + k < n_hb) acc += pv[k];
+    }
+    return acc;
+}
 
 // per-mini-batch bookkeeping of the split-wgrad chain, by ONE wave (threads 0..63 of a workgroup): loss partials -> totals
 __device__ __forceinline__ void ppo_update_bookkeeping_totals(const UpdateDev& u) {

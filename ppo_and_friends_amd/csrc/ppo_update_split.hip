@@ -22,41 +22,27 @@ namespace ppoaf {
 // ------------------------------------------------------------------------------------------------------------
 // MAXC = chunks of 16 rows a wave may own (B <= 512: 32 chunks over 4 waves)
 template <int H>
-__device__ __forceinline__ double split_wgrad_job(const UpdateDev& u, const int which, const int job, float* sFold /* [3][2][256] + [4][16] */) {
+__device__ __forceinline__ double split_wgrad_job(const UpdateDev& u, const int which, const int job, float* sFold /* wgrad_tile.hpp */) {
     constexpr int MAXC = 8;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // scalar: the chunk offsets below stay in scalar registers
     const auto& nd = u.net[which];
-    const int in_dim = nd.in_dim, depth = nd.depth, out_dim = nd.out_dim;
     const int B = (int)u.B;
-    const long plane = (long)u.sp.Bp * H;
-    const long szW0 = ((long)H * in_dim + 3) & ~3L;
-    auto offW = [&](int l) -> long { return l == 0 ? 0 : szW0 + H + (long)(l - 1) * ((long)H * H + H); };
-    auto offB = [&](int l) -> long {
-        return l == 0 ? szW0 : offW(l) + (l < depth ? (long)H * H : (((long)out_dim * H + 3) & ~3L));
-    };
     float* G = u.grads + nd.offset;
-    constexpr int t = H / 16, t2 = (t + 1) / 2;
-    const int n_it0 = (in_dim + 15) / 16, p0 = (n_it0 + 1) / 2;
-    const int n_hidden = (depth - 1) * t * t2, n_l0 = t * p0;
     const float sc = u.grad_scale;
     double q = 0.0;
-    if (job < n_hidden + n_l0) {
-        // 16 output rows x 32 input columns: input tiles itile and itile + 1 (the second may not exist: odd tile counts)
-        int l, ot, itile, n_it;
-        if (job < n_hidden) { l = 1 + job / (t * t2); const int jj = job % (t * t2); ot = jj / t2; itile = 2 * (jj % t2); n_it = t; }
-        else { l = 0; const int jj = job - n_hidden; ot = jj / p0; itile = 2 * (jj % p0); n_it = n_it0; }
-        const bool two = itile + 1 < n_it;                    // uniform per workgroup
+    SplitJob sj;
+    if (split_job_decode<H>(u, which, job, sj)) {
+        const int ot = sj.ot, itile = sj.itile;
+        const bool two = sj.two;
         // buffer loads: resource = the layer's panel, scalar offset = chunk + row quad, vector offset = the lane's constant
-        // byte offset (no vector address arithmetic per load).  Rows of the last chunk beyond B are dead rows of their
-        // tile: their dz is zero and their activations finite, exactly as the slab form sums them.
-        const long ldx = l >= 1 ? H : 64;
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(u.sp.dbuf[which] + (long)l * plane, 0, 0xFFFFFFFF, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            l >= 1 ? u.sp.hbuf[which] + (long)(l - 1) * plane : u.sp.xbuf[which], 0, 0xFFFFFFFF, 0x00020000);
+        // byte offset.  Rows of the last chunk beyond B are dead rows of their tile: their dz is zero and their activations
+        // finite, exactly as the slab form sums them.
+        const long ldx = sj.l >= 1 ? H : 64;                  // row stride of the input panel (layer 0: the gathered input rows)
+        const __amdgpu_buffer_rsrc_t rd = split_panel_d<H>(u, which, sj.l), rx = split_panel_x<H>(u, which, sj.l);
         const unsigned dl = 4u * (unsigned)((lane >> 4) * H + ot * 16 + (lane & 15));
         const unsigned xl = 4u * (unsigned)((lane >> 4) * (int)ldx + itile * 16 + (lane & 15));
-        const int nc = (B + 15) >> 4;                         // 16-row chunks of the mini-batch
+        const int nc = (B + 15) >> 4;                         // 16-row chunks of the mini-batch: one batch
         float a[MAXC][4], x0[MAXC][4], x1[MAXC][4];
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
@@ -66,74 +52,39 @@ __device__ __forceinline__ double split_wgrad_job(const UpdateDev& u, const int 
             if (ch < nc) {                                    // wave-uniform
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const unsigned sd = 4u * (unsigned)((16 * ch + 4 * j) * H), sx = 4u * (unsigned)((16 * ch + 4 * j) * (int)ldx);
-                    a[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, dl, sd, 0));
-                    x0[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl, sx, 0));
-                    if (two) x1[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl + 64u, sx, 0));
+                    const WgradOff so = {4u * (unsigned)((16 * ch + 4 * j) * H), 4u * (unsigned)((16 * ch + 4 * j) * (int)ldx)};
+                    wgrad_request_quad(rd, rx, dl, xl, xl + 64u, two, so, a[c][j], x0[c][j], x1[c][j]);
                 }
             }
         }
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         float bsum = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            if (wave + 4 * c < nc) {                          // wave-uniform
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x0[c][j], acc0, 0, 0, 0);
-                    if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x1[c][j], acc1, 0, 0, 0);
-                    bsum += a[c][j];
-                }
-            }
-        }
-        // fold the four waves' partial tiles in wave order (waves 1..3 park theirs in LDS)
-        if (wave > 0) {
-            *reinterpret_cast<f32x4*>(sFold + (((wave - 1) * 2 + 0) * 64 + lane) * 4) = acc0;
-            *reinterpret_cast<f32x4*>(sFold + (((wave - 1) * 2 + 1) * 64 + lane) * 4) = acc1;
-        }
-        // bias: column o = lane & 15 summed over this lane group's rows, then over the 4 lane groups, then over the waves
-        bsum += __shfl_xor(bsum, 16, 64);
-        bsum += __shfl_xor(bsum, 32, 64);
-        if (lane < 16) sFold[1536 + wave * 16 + lane] = bsum;
-        __syncthreads();
-        if (wave == 0) {
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                acc0 += *reinterpret_cast<const f32x4*>(sFold + ((w * 2 + 0) * 64 + lane) * 4);
-                acc1 += *reinterpret_cast<const f32x4*>(sFold + ((w * 2 + 1) * 64 + lane) * 4);
-            }
-        }
-        const long ldw = l >= 1 ? H : in_dim;
+        wgrad_mfma<MAXC>(a, x0, x1, two, wave, nc, acc0, acc1, bsum);
+        wgrad_park(sFold, wave, lane, acc0, acc1, bsum);
+        if (wave == 0) wgrad_fold(sFold, lane, acc0, acc1);
+        const long ldw = sj.ldw;
         const int i = itile * 16 + (lane & 15);               // C layout: column = lane & 15, rows 4 (lane >> 4) + r
         float bg = 0.f;
-        if (wave == 0 && itile == 0 && lane < 16)
-            bg = sFold[1536 + lane] + sFold[1536 + 16 + lane] + sFold[1536 + 32 + lane] + sFold[1536 + 48 + lane];
+        if (wave == 0 && itile == 0 && lane < 16) bg = wgrad_bias_fold(sFold, lane);
         if (wave == 0) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int o = ot * 16 + 4 * (lane >> 4) + r;
-                if (i < ldw) { G[offW(l) + (long)o * ldw + i] = acc0[r]; q += (double)(acc0[r] * sc) * (acc0[r] * sc); }
-                if (two && i + 16 < ldw) { G[offW(l) + (long)o * ldw + i + 16] = acc1[r]; q += (double)(acc1[r] * sc) * (acc1[r] * sc); }
+                if (i < ldw) { G[sj.off_w + (long)o * ldw + i] = acc0[r]; q += (double)(acc0[r] * sc) * (acc0[r] * sc); }
+                if (two && i + 16 < ldw) { G[sj.off_w + (long)o * ldw + i + 16] = acc1[r]; q += (double)(acc1[r] * sc) * (acc1[r] * sc); }
             }
             if (itile == 0 && lane < 16) {
-                G[offB(l) + ot * 16 + lane] = bg;
+                G[sj.off_b + ot * 16 + lane] = bg;
                 q += (double)(bg * sc) * (bg * sc);
             }
         }
     } else {
         // output layer (+ log_std): row-block partials -> gradient, in block order
-        const long seg_off = offW(depth), seg_len = nd.size - seg_off;
+        const long seg_off = split_off_w<H>(nd, nd.depth), seg_len = nd.size - seg_off;
         const float* outpart = u.sp.outpart[which];
         const int n_hb = (B + 15) >> 4;
         for (long idx = tid; idx < seg_len; idx += kWgradThreads) {
-            float acc = 0.f;
-            for (int g0 = 0; g0 < n_hb; g0 += 8) {
-                float pv[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) pv[k] = outpart[(long)(g0 + k < n_hb ? g0 + k : 0) * seg_len + idx];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) if (g0 + k < n_hb) acc += pv[k];
-            }
+            const float acc = split_out_fold(outpart, n_hb, seg_len, idx);
             G[seg_off + idx] = acc;
             q += (double)(acc * sc) * (acc * sc);
         }
@@ -144,7 +95,7 @@ __device__ __forceinline__ double split_wgrad_job(const UpdateDev& u, const int 
 template <int HA, int HC>
 __global__ __launch_bounds__(kWgradThreads) void ppo_update_wgrad_kernel(UpdateDev u, int jobs_a, int jobs_c, int per_xcd) {
     __shared__ double s_red[17];
-    __shared__ __attribute__((aligned(16))) float s_fold[6 * 256 + 64];
+    __shared__ __attribute__((aligned(16))) float s_fold[kWgradFoldFloats];
     const int b = blockIdx.x;
     if (b == 8 * per_xcd) { ppo_update_bookkeeping_split(u); return; }           // uniform per workgroup
     const int job = (b & 7) * per_xcd + (b >> 3);             // XCD b % 8 works on one run of the layer-major job list

@@ -31,13 +31,8 @@ namespace ppoaf {
 
 constexpr int kTailMaxE = 9;                  // output segment: up to 9 elements per thread (8 x 256 weights + bias + log_std)
 
-// The bias corrections of Adam step t of network `which` (ppo_update_bookkeeping_steps' expressions): the previous launch's
-// bookkeeping workgroup left them in the control block while it waited (two double pow: ~2 us of one wave); computed
-// here only when the block holds another step's (first launch, restored state).
-struct TailBc { long long t; double bc1, bc2s; };
-
-// What a job workgroup reads of the words the bookkeeping workgroup rewrites: the launch tag's source, the network's Adam
-// step, the learning rate and the control block's bias corrections.  The ordering contract: these words are READ (the
+// What a job workgroup reads of the words the bookkeeping workgroup rewrites (TailPre, tail_sync.hpp): the launch tag's
+// source, the network's Adam step, the learning rate and the control block's bias corrections.  The ordering contract: these words are READ (the
 // load is issued and its value latched) before this workgroup publishes its record; the bookkeeping workgroup rewrites
 // them only after every record carries the launch's tag, i.e. after all of these reads.
 // Request and use are apart on purpose.  tail_pre_request comes right BEHIND the job's state and operand loads: a wave's
@@ -58,7 +53,6 @@ struct TailBc { long long t; double bc1, bc2s; };
 // (`<128,256>`: 10.2 - 10.9 us against 9.6), so those instantiations keep the words' loads at the start of the workgroup
 // (tail_pre_load) and plain state loads, as they were.
 constexpr bool kTailOneTrip(const int ha, const int hc) { return ha <= 128 && hc <= 128; }
-struct TailPre { unsigned long long seq; long long t; float lr; TailBc bc; };
 // !ONE_TRIP: read at the START of the workgroup (`seq` by the kernel, before it branches)
 __device__ __forceinline__ TailPre tail_pre_load(const UpdateDev& u, const TailDev& td, const int which, const unsigned long long seq) {
     TailPre r;
@@ -84,35 +78,6 @@ __device__ __forceinline__ TailPre tail_pre_use(TailPre r) {
     asm volatile("" : "+v"(r.seq), "+v"(r.t), "+v"(r.lr), "+v"(r.bc.t), "+v"(r.bc.bc1), "+v"(r.bc.bc2s));
     return r;
 }
-__device__ __forceinline__ unsigned tail_tag(const unsigned long long seq) {
-    return ((unsigned)seq & 0x7fffffffu) + 1u;                 // never 0: a zero-initialised record is never current
-}
-
-// Wave 0 of the workgroup (all 64 lanes), q = the workgroup's squared-norm partial: publish, wait for everybody's, and
-// leave the step's clip / Adam coefficients (ppo_update_adam_kernel's, expression for expression) in s_coef.
-__device__ __forceinline__ void tail_sync_wave0(const UpdateDev& u, const TailDev& td, const int b, const int which,
-                                                const TailPre& pre /* tail_pre_use's */, const double q, float* s_coef) {
-    const unsigned tag = tail_tag(pre.seq);
-    const long long t_next = pre.t + 1;
-    const float lr = pre.lr;
-    if (threadIdx.x == 0) tail_publish(td, tag, b, q);
-    double bc1 = pre.bc.bc1, bc2s = pre.bc.bc2s;
-    if (pre.bc.t != t_next) {                                 // uniform
-        bc1 = 1.0 - pow((double)u.beta1, (double)t_next);
-        bc2s = sqrt(1.0 - pow((double)u.beta2, (double)t_next));
-    }
-    double sq0, sq1;
-    tail_gather(td, tag, sq0, sq1);
-    if (threadIdx.x == 0) {
-        const float total_norm = (float)sqrt(which ? sq1 : sq0);
-        float coef = 1.0f;
-        if (u.max_norm > 0.f) coef = fminf(u.max_norm / (total_norm + 1e-6f), 1.0f);
-        s_coef[0] = u.grad_scale * coef;
-        s_coef[1] = (float)((double)lr / bc1);
-        s_coef[2] = (float)bc2s;
-    }
-}
-
 // ---- N > 1: the K17 gradient exchange as a phase of the job (mpi_avg_gradients, utils/mpi_utils.py:89-111, at its call
 // sites ppo_policy.py:1035,1048).  Workgroup b of every rank runs the same job, so exchange group b depends only on
 // group b of its peers: the job's 16 x 32 sums (+ 16 bias sums) go to THIS rank's slot as 16-byte system-scope stores
@@ -133,9 +98,6 @@ __device__ __forceinline__ long long tail_xchg_sequence(const TailXchg& c, const
     long long v = c.x.group_seq[g];
     asm volatile("" : "+v"(v));
     return v + 1;
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tail_slot_rsrc(const void* base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0xFFFFFFFF, 0x00020000);
 }
 __device__ __forceinline__ void tail_xchg_publish_wait(const TailXchg& c, const unsigned g) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -164,23 +126,23 @@ __device__ __forceinline__ void tail_xchg_publish_wait(const TailXchg& c, const 
     __syncthreads();
 }
 // float offset `off` (a multiple of 4) inside the slot of this launch's parity: own value out, rank-ordered sum back
-__device__ __forceinline__ void tail_xchg_store4(const TailXchg& c, const long off, const tail_f32x4 v) {
+__device__ __forceinline__ void tail_xchg_store4(const TailXchg& c, const long off, const f32x4 v) {
     const long byte = ((c.seq & 1) * c.x.n4 * 4 + off) * 4;
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tail_u32x4, v), tail_slot_rsrc(c.x.my_slots), (unsigned)byte, 0, 17 /* sc0 sc1 */);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(tail_u32x4, v), wgrad_rsrc(c.x.my_slots), (unsigned)byte, 0, 17 /* sc0 sc1 */);
 }
-__device__ __forceinline__ tail_f32x4 tail_xchg_sum4(const TailXchg& c, const long off, const tail_f32x4 own) {
+__device__ __forceinline__ f32x4 tail_xchg_sum4(const TailXchg& c, const long off, const f32x4 own) {
     const long byte = ((c.seq & 1) * c.x.n4 * 4 + off) * 4;
-    tail_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int p0 = 0; p0 < kMaxPeers; p0 += 8) {
         if (p0 >= c.x.n_ranks) break;
-        tail_f32x4 v[8];
+        f32x4 v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const int p = p0 + k;
-            if (p >= c.x.n_ranks) v[k] = tail_f32x4{0.f, 0.f, 0.f, 0.f};
+            if (p >= c.x.n_ranks) v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
             else if (p == c.x.rank) v[k] = own;
-            else v[k] = __builtin_bit_cast(tail_f32x4, __builtin_amdgcn_raw_buffer_load_b128(tail_slot_rsrc(c.x.peer_slots[p]), (unsigned)byte, 0, 17));
+            else v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wgrad_rsrc(c.x.peer_slots[p]), (unsigned)byte, 0, 17));
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) if (p0 + k < c.x.n_ranks) acc += v[k];
@@ -212,95 +174,63 @@ __device__ __forceinline__ float tail_xchg_sum1(const TailXchg& c, const long of
     return acc;
 }
 
-// Optimiser state of bucket element idx, through buffer descriptors on the three arrays: ONE 32-bit offset register per
-// element, which stays live (the step's stores need the index again).  As plain global loads every request built a
-// 64-bit address pair, the pairs were reused for the next element's addresses, and the compiler holds a write to the
-// address registers of a load in flight back until that load has returned: the state requests waited for one another,
-// and the first operand request for all of them -- a serial round trip ahead of the operands.  (4 * idx < 2^32: checked
-// on the host, tail_prepare.)  tail_pmv_hold, behind the job's last request, is what keeps those offset registers from
-// being handed to something else while the loads are in flight.
-struct TailPmv { float p, m, v; };
-__device__ __forceinline__ unsigned tail_pmv_off(const long idx) { return 4u * (unsigned)idx; }
-__device__ __forceinline__ void tail_pmv_hold(const unsigned off) { asm volatile("" :: "v"(off)); }
+// Optimiser state of bucket element idx (ONE_TRIP: through buffer descriptors, wgrad_tile.hpp; 4 * idx < 2^32 is checked on
+// the host, tail_prepare) and the step on it with the coefficients tail_sync_wave0 left
+struct TailCoef { float gs, step_size, bc2_sqrt; };
 template <bool ONE_TRIP>
-__device__ __forceinline__ TailPmv tail_pmv_load(const UpdateDev& u, const long idx, const bool ok) {
-    TailPmv r = {0.f, 0.f, 0.f};
-    if constexpr (!ONE_TRIP) {
-        if (ok) { r.p = u.params[idx]; r.m = u.exp_avg[idx]; r.v = u.exp_avg_sq[idx]; }
-    } else if (ok) {
-        const unsigned off = tail_pmv_off(idx);
-        r.p = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(tail_slot_rsrc(u.params), off, 0, 0));
-        r.m = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(tail_slot_rsrc(u.exp_avg), off, 0, 0));
-        r.v = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(tail_slot_rsrc(u.exp_avg_sq), off, 0, 0));
-    }
-    return r;
+__device__ __forceinline__ Pmv tail_pmv_load(const UpdateDev& u, const long idx, const bool ok) {
+    return pmv_load<ONE_TRIP>(u.params, u.exp_avg, u.exp_avg_sq, idx, ok);
 }
-// ppo_update_adam_kernel's step on one element (-ffp-contract=off: the same roundings)
-__device__ __forceinline__ void tail_adam1(const UpdateDev& u, const long idx, const float g, const TailPmv& s, const TailCoef& c) {
-    const float gi = g * c.gs;
-    const float m = u.beta1 * s.m + (1.0f - u.beta1) * gi;
-    const float v = u.beta2 * s.v + (1.0f - u.beta2) * gi * gi;
-    const_cast<float*>(u.params)[idx] = s.p - c.step_size * (m / (sqrtf(v) / c.bc2_sqrt + u.adam_eps));
-    u.exp_avg[idx] = m;
-    u.exp_avg_sq[idx] = v;
+__device__ __forceinline__ void tail_adam1(const UpdateDev& u, const long idx, const float g, const Pmv& s, const TailCoef& c) {
+    adam_element(u.params, u.exp_avg, u.exp_avg_sq, u.beta1, u.beta2, u.adam_eps, idx, g, s, c.gs, c.step_size, c.bc2_sqrt);
 }
 
-// One job of the split-wgrad job list (ppo_update_ws.hip: split_wgrad_job -- same tiles, same operand loads, same fold
+// One job of the split-wgrad job list (ppo_update_split.hip: split_wgrad_job -- same tiles, same operand loads, same fold
 // and summation orders), carried through to the optimiser step.  Offsets of p / m / v / G are bucket offsets.
 // The 16 x 32 output tile is formed by wave 0 (C layout) and handed to ALL 256 threads through LDS for the optimiser
 // step: thread t owns tile elements t and t + 256 (row e / 32, column e % 32: whole 128-byte lines of p / m / v), whose
 // state it requested at the start of the job, beside the MFMA operands.
 template <int H, bool XCHG, bool ONE_TRIP>
 __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, const unsigned long long seq0, const int b, const int which,
-                                         const int job, float* sFold /* [3][2][256] + [4][16] */, float* sTile /* [16][32] + [16] */,
+                                         const int job, float* sFold /* wgrad_tile.hpp */, float* sTile /* [16][32] + [16] */,
                                          double* s_red, float* s_coef, TailXchg* xc) {
     constexpr int MAXC = 8;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const auto& nd = u.net[which];
-    const int in_dim = nd.in_dim, depth = nd.depth, out_dim = nd.out_dim;
     const int B = (int)u.B;
-    const long plane = (long)u.sp.Bp * H;
-    const long szW0 = ((long)H * in_dim + 3) & ~3L;
-    auto offW = [&](int l) -> long { return l == 0 ? 0 : szW0 + H + (long)(l - 1) * ((long)H * H + H); };
-    auto offB = [&](int l) -> long {
-        return l == 0 ? szW0 : offW(l) + (l < depth ? (long)H * H : (((long)out_dim * H + 3) & ~3L));
-    };
     const long nb = nd.offset;                                 // this network's first float in the bucket
     float* G = u.grads + nb;
-    constexpr int t = H / 16, t2 = (t + 1) / 2;
-    const int n_it0 = (in_dim + 15) / 16, p0 = (n_it0 + 1) / 2;
-    const int n_hidden = (depth - 1) * t * t2, n_l0 = t * p0;
     const float sc = u.grad_scale;
     double q = 0.0;
     TailPre pre;
     if constexpr (!ONE_TRIP) pre = tail_pre_load(u, td, which, seq0);
     TAIL_STAMP(td, 0);
-    if (job < n_hidden + n_l0) {
-        int l, ot, itile, n_it;
-        if (job < n_hidden) { l = 1 + job / (t * t2); const int jj = job % (t * t2); ot = jj / t2; itile = 2 * (jj % t2); n_it = t; }
-        else { l = 0; const int jj = job - n_hidden; ot = jj / p0; itile = 2 * (jj % p0); n_it = n_it0; }
-        const bool two = itile + 1 < n_it;                    // uniform per workgroup
-        const long ldw = l >= 1 ? H : in_dim;
+    SplitJob sj;
+    if (split_job_decode<H>(u, which, job, sj)) {
+        const int ot = sj.ot, itile = sj.itile;
+        const bool two = sj.two;
+        const long ldw = sj.ldw;
         // this thread's two tile elements (and, threads 64..79 of the jobs of input piece 0, one bias): optimiser state first
         long eidx[2];
         bool eok[2];
-        TailPmv se[2], sb;
+        Pmv se[2], sb;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int e = tid + 256 * k, row = e >> 5, col = e & 31;
             const int i = itile * 16 + col;
             eok[k] = (col < 16 || two) && i < ldw;
-            eidx[k] = nb + offW(l) + (long)(ot * 16 + row) * ldw + i;
+            eidx[k] = nb + sj.off_w + (long)(ot * 16 + row) * ldw + i;
             se[k] = tail_pmv_load<ONE_TRIP>(u, eidx[k], eok[k]);
         }
         const bool has_b = itile == 0 && tid >= 64 && tid < 80;
-        const long bidx = nb + offB(l) + ot * 16 + (tid - 64);
+        const long bidx = nb + sj.off_b + ot * 16 + (tid - 64);
         sb = tail_pmv_load<ONE_TRIP>(u, bidx, has_b);
-        const long ldx = l >= 1 ? H : 64;
-        const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc(u.sp.dbuf[which] + (long)l * plane, 0, 0xFFFFFFFF, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-            l >= 1 ? u.sp.hbuf[which] + (long)(l - 1) * plane : u.sp.xbuf[which], 0, 0xFFFFFFFF, 0x00020000);
+        // buffer loads: resource = the layer's panel, scalar offset = chunk + row quad, vector offset = the lane's constant
+        // byte offset.  Rows of the last chunk beyond B are dead rows of their tile: their dz is zero and their activations
+        // finite, exactly as the slab form sums them.
+        const long ldx = sj.l >= 1 ? H : 64;                  // row stride of the input panel (layer 0: the gathered input rows)
+        const __amdgpu_buffer_rsrc_t rd = split_panel_d<H>(u, which, sj.l), rx = split_panel_x<H>(u, which, sj.l);
         const unsigned dl = 4u * (unsigned)((lane >> 4) * H + ot * 16 + (lane & 15));
         const unsigned xl = 4u * (unsigned)((lane >> 4) * (int)ldx + itile * 16 + (lane & 15));
         const int nc = (B + 15) >> 4;
@@ -313,54 +243,30 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
             if (ch < nc) {                                    // wave-uniform
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const unsigned sd = 4u * (unsigned)((16 * ch + 4 * j) * H), sx = 4u * (unsigned)((16 * ch + 4 * j) * (int)ldx);
-                    a[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rd, dl, sd, 0));
-                    x0[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl, sx, 0));
-                    if (two) x1[c][j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rx, xl + 64u, sx, 0));
+                    const WgradOff so = {4u * (unsigned)((16 * ch + 4 * j) * H), 4u * (unsigned)((16 * ch + 4 * j) * (int)ldx)};
+                    wgrad_request_quad(rd, rx, dl, xl, xl + 64u, two, so, a[c][j], x0[c][j], x1[c][j]);
                 }
             }
         }
 #pragma unroll
-        for (int k = 0; k < 2; ++k) if constexpr (ONE_TRIP) tail_pmv_hold(tail_pmv_off(eidx[k]));
-        if constexpr (ONE_TRIP) tail_pmv_hold(tail_pmv_off(bidx));
+        for (int k = 0; k < 2; ++k) if constexpr (ONE_TRIP) pmv_hold(pmv_off(eidx[k]));
+        if constexpr (ONE_TRIP) pmv_hold(pmv_off(bidx));
         // behind the operands: the control words (read before this workgroup publishes) and the exchange's sequence number
         if constexpr (ONE_TRIP) {
             pre = tail_pre_request(u, td, which);
             if (XCHG) xc->seq = tail_xchg_sequence(*xc, (unsigned)b);
         }
         TAIL_STAMP(td, 1);
-        tail_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         float bsum = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            if (wave + 4 * c < nc) {                          // wave-uniform
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x0[c][j], acc0, 0, 0, 0);
-                    if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][j], x1[c][j], acc1, 0, 0, 0);
-                    bsum += a[c][j];
-                }
-            }
-        }
+        wgrad_mfma<MAXC>(a, x0, x1, two, wave, nc, acc0, acc1, bsum);
         TAIL_STAMP(td, 2);
-        if (wave > 0) {
-            *reinterpret_cast<tail_f32x4*>(sFold + (((wave - 1) * 2 + 0) * 64 + lane) * 4) = acc0;
-            *reinterpret_cast<tail_f32x4*>(sFold + (((wave - 1) * 2 + 1) * 64 + lane) * 4) = acc1;
-        }
-        bsum += __shfl_xor(bsum, 16, 64);
-        bsum += __shfl_xor(bsum, 32, 64);
-        if (lane < 16) sFold[1536 + wave * 16 + lane] = bsum;
-        __syncthreads();
+        wgrad_park(sFold, wave, lane, acc0, acc1, bsum);
         const int i = itile * 16 + (lane & 15);               // C layout: column = lane & 15, rows 4 (lane >> 4) + r
         float bg = 0.f;
         if (wave == 0) {
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                acc0 += *reinterpret_cast<const tail_f32x4*>(sFold + ((w * 2 + 0) * 64 + lane) * 4);
-                acc1 += *reinterpret_cast<const tail_f32x4*>(sFold + ((w * 2 + 1) * 64 + lane) * 4);
-            }
-            if (itile == 0 && lane < 16)
-                bg = sFold[1536 + lane] + sFold[1536 + 16 + lane] + sFold[1536 + 32 + lane] + sFold[1536 + 48 + lane];
+            wgrad_fold(sFold, lane, acc0, acc1);
+            if (itile == 0 && lane < 16) bg = wgrad_bias_fold(sFold, lane);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = 4 * (lane >> 4) + r;
@@ -374,13 +280,13 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
             __syncthreads();
             const bool mine = tid < 128 || (itile == 0 && tid < 132);
             const long off = (long)b * kTailTileFloats + 4 * tid;
-            tail_f32x4 own = {0.f, 0.f, 0.f, 0.f};
+            f32x4 own = {0.f, 0.f, 0.f, 0.f};
             if (mine) {
-                own = *reinterpret_cast<const tail_f32x4*>(sTile + 4 * tid);
+                own = *reinterpret_cast<const f32x4*>(sTile + 4 * tid);
                 tail_xchg_store4(*xc, off, own);
             }
             tail_xchg_publish_wait(*xc, (unsigned)b);
-            if (mine) *reinterpret_cast<tail_f32x4*>(sTile + 4 * tid) = tail_xchg_sum4(*xc, off, own);
+            if (mine) *reinterpret_cast<f32x4*>(sTile + 4 * tid) = tail_xchg_sum4(*xc, off, own);
             __syncthreads();
             if (wave == 0) {
 #pragma unroll
@@ -404,7 +310,7 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
             // block_sum(q) of the chain's wgrad launch: only this wave contributes, and its wave sum + three zeros is exact
             q = tail_wave_sum(q);
             TAIL_STAMP(td, 4);
-            tail_sync_wave0(u, td, b, which, got, q, s_coef);
+            tail_sync_wave0(td, b, got, u.beta1, u.beta2, u.max_norm, u.grad_scale, which, nullptr, q, s_coef);
         }
         __syncthreads();                                      // s_coef and sTile are visible
         TAIL_STAMP(td, 5);
@@ -421,10 +327,10 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
         TAIL_STAMP(td, 6);
     } else {
         // output layer (+ log_std): row-block partials -> gradient in block order; a thread keeps its elements
-        const long seg_off = offW(depth), seg_len = nd.size - seg_off;
+        const long seg_off = split_off_w<H>(nd, nd.depth), seg_len = nd.size - seg_off;
         const float* outpart = u.sp.outpart[which];
         const int n_hb = (B + 15) >> 4;
-        TailPmv se[kTailMaxE];
+        Pmv se[kTailMaxE];
         float ge[kTailMaxE];
 #pragma unroll
         for (int k = 0; k < kTailMaxE; ++k) {
@@ -439,17 +345,7 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
 #pragma unroll
         for (int k = 0; k < kTailMaxE; ++k) {
             const long idx = tid + (long)kWgradThreads * k;
-            if (idx < seg_len) {
-                float acc = 0.f;
-                for (int g0 = 0; g0 < n_hb; g0 += 8) {
-                    float pv[8];
-#pragma unroll
-                    for (int kk = 0; kk < 8; ++kk) pv[kk] = outpart[(long)(g0 + kk < n_hb ? g0 + kk : 0) * seg_len + idx];
-#pragma unroll
-                    for (int kk = 0; kk < 8; ++kk) if (g0 + kk < n_hb) acc += pv[kk];
-                }
-                ge[k] = acc;
-            }
+            if (idx < seg_len) ge[k] = split_out_fold(outpart, n_hb, seg_len, idx);
         }
         if (XCHG) {
 #pragma unroll
@@ -479,7 +375,7 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
         const TailPre got = ONE_TRIP ? tail_pre_use(pre) : pre;   // every wave: see tail_pre_use
         if (wave == 0) {
             q = tail_wave_sum(lane < 4 ? s_red[lane] : 0.0);
-            tail_sync_wave0(u, td, b, which, got, q, s_coef);
+            tail_sync_wave0(td, b, got, u.beta1, u.beta2, u.max_norm, u.grad_scale, which, nullptr, q, s_coef);
         }
         __syncthreads();
         const TailCoef cf = {s_coef[0], s_coef[1], s_coef[2]};
@@ -494,7 +390,7 @@ __device__ __forceinline__ void tail_job(const UpdateDev& u, const TailDev& td, 
 template <int HA, int HC, bool XCHG>
 __global__ __launch_bounds__(kWgradThreads) void ppo_update_wgrad_adam_kernel(UpdateDev u, TailDev td, TailXchg xc) {
     __shared__ double s_red[17];
-    __shared__ __attribute__((aligned(16))) float s_fold[6 * 256 + 64];
+    __shared__ __attribute__((aligned(16))) float s_fold[kWgradFoldFloats];
     __shared__ float s_tile[16 * 32 + 16];
     __shared__ float s_coef[4];
     constexpr bool ONE_TRIP = kTailOneTrip(HA, HC);

@@ -12,7 +12,6 @@
 namespace ppoaf {
 
 typedef unsigned tail_u32x4 __attribute__((ext_vector_type(4)));
-typedef float tail_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTailRecOff = 256;              // byte offset of the records inside the control block
 constexpr int kTailMaxRounds = 8;             // a polling lane holds up to 8 records: <= 512 workgroups
@@ -50,8 +49,6 @@ struct TailDev {
     long long budget;                         // wall_clock64 ticks (100 MHz)
     int nblk, jobs_a, jobs_c, per_xcd;
 };
-
-struct TailCoef { float gs, step_size, bc2_sqrt; };
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tail_rsrc(const TailDev& td) {
     return __builtin_amdgcn_make_buffer_rsrc(td.ctl, 0, 0xFFFFFFFF, 0x00020000);
@@ -128,6 +125,44 @@ __device__ __forceinline__ bool tail_gather_n(const TailDev& td, const unsigned 
 __device__ __forceinline__ bool tail_gather(const TailDev& td, const unsigned tag, double& sq0, double& sq1) {
     if (td.nblk <= 192) return tail_gather_n<3>(td, tag, sq0, sq1);          // uniform: a lane holds ceil(nblk / 64) records
     return tail_gather_n<kTailMaxRounds>(td, tag, sq0, sq1);
+}
+
+// What a workgroup reads, BEFORE it publishes, of the words the bookkeeping workgroup rewrites once every record carries
+// the launch's tag: the launch tag's source, the Adam step taken so far, the learning rate, and the bias corrections the
+// previous launch's bookkeeping workgroup left in the control block while it waited (two double pow: ~2 us of one wave).
+struct TailBc { long long t; double bc1, bc2s; };             // the Adam step the corrections were computed for
+struct TailPre { unsigned long long seq; long long t; float lr; TailBc bc; };
+__device__ __forceinline__ unsigned tail_tag(const unsigned long long seq) {
+    return ((unsigned)seq & 0x7fffffffu) + 1u;                 // never 0: a zero-initialised record is never current
+}
+
+// Wave 0 of workgroup b (all 64 lanes), q = the workgroup's squared-norm partial: publish, wait for everybody's, and
+// leave the step's clip / Adam coefficients (clip_adam_kernel's, expression for expression) in s_coef.  The bias
+// corrections are recomputed only when the control block holds another step's (first launch, restored state).
+// which: the network whose norm clips this workgroup's elements; grad_norm_out (may be null): workgroup 0 reports the norm.
+__device__ __forceinline__ void tail_sync_wave0(const TailDev& td, const int b, const TailPre& pre, const float beta1, const float beta2,
+                                                const float max_norm, const float grad_scale, const int which, float* grad_norm_out,
+                                                const double q, float* s_coef) {
+    const unsigned tag = tail_tag(pre.seq);
+    const long long t_next = pre.t + 1;
+    const float lr = pre.lr;
+    if (threadIdx.x == 0) tail_publish(td, tag, b, q);
+    double bc1 = pre.bc.bc1, bc2s = pre.bc.bc2s;
+    if (pre.bc.t != t_next) {                                 // uniform
+        bc1 = 1.0 - pow((double)beta1, (double)t_next);
+        bc2s = sqrt(1.0 - pow((double)beta2, (double)t_next));
+    }
+    double sq0, sq1;
+    tail_gather(td, tag, sq0, sq1);
+    if (threadIdx.x == 0) {
+        const float total_norm = (float)sqrt(which ? sq1 : sq0);
+        float coef = 1.0f;
+        if (max_norm > 0.f) coef = fminf(max_norm / (total_norm + 1e-6f), 1.0f);
+        s_coef[0] = grad_scale * coef;
+        s_coef[1] = (float)((double)lr / bc1);
+        s_coef[2] = (float)bc2s;
+        if (b == 0 && grad_norm_out) grad_norm_out[0] = total_norm;
+    }
 }
 
 }  // namespace ppoaf

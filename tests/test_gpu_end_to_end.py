@@ -506,6 +506,92 @@ def test_mat_policy_rollout_and_update_match_cpu_port(update_mode, B):
     np.testing.assert_allclose(w, w_ref, rtol=2e-4, atol=3e-5)
 
 
+def test_mat_update_with_more_row_tiles_than_one_operand_batch(monkeypatch):
+    """
+    K15 with 66 row tiles per mini-batch (5 agents: 3 sequences per 16-row tile, B = 196; N = 400: two full mini-batches
+    and a tail of 8): the wgrad tile's operand loop (wgrad_tile.hpp: 16 chunks per wave and trip) takes a SECOND trip on
+    waves 0 and 1, which no other shape of the suite reaches.  One epoch, graphs off:
+      (a) the fused path against this package's torch path on identical rollouts (the bounds of
+          test_fused_mat_and_icm_paths_fuzz_against_the_torch_paths);
+      (b) the fused tail against the three-launch chain: parameters, moments and the gradient bucket bitwise;
+      (c) the slab form against the chain (the bounds of test_c5_mat_split_wgrad_chain_matches_the_slab_form_at_full_size).
+    """
+    import ctypes as C
+    from ppo_and_friends_amd import _lib
+    from ppo_and_friends_amd import kernels as K
+    from ppo_and_friends_amd.ppo import PPO, PermutationLoader
+    from ppo_and_friends_amd.policies.mat_policy import MATPolicy
+    from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
+    from ppo_and_friends_amd.spaces import Box, Discrete
+    dev = torch.device("cuda", 0)
+    A, O, NA, B, E, T, seed = 5, 7, 4, 196, 25, 16, 11
+    n_mb = (E * T + B - 1) // B
+
+    def make(mode):
+        env_gen = lambda: SyntheticFixedLengthEnv(E, O, Discrete(NA), T, dev, reward="uniform", seed=41, num_agents=A)
+        sp = Box(-np.inf, np.inf, (O,), np.float32)
+        ppo = PPO(env_gen, {"mat": (MATPolicy, sp, sp, Discrete(NA), {})}, device=dev, random_seed=seed, normalize_obs=False,
+                  normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=B, epochs_per_iter=1,
+                  update_mode=mode, use_graphs=False)
+        ppo.policies["mat"].fused_step_unsupported_reason = lambda: "torch rollout forced by the test"   # identical rollouts
+        return ppo
+
+    def first_minibatch(split):
+        """the first mini-batch's gradient bucket and loss totals on their own (no optimiser step)"""
+        monkeypatch.setenv("PPOAF_SPLIT_WGRAD", split)
+        ppo = make("fused")
+        pol = ppo.policies["mat"]
+        ppo.rollout()
+        pol.train()
+        fused = ppo._fused_updater("mat", B)
+        assert fused.split == (split == "1") and fused.n_wg == 66
+        perm = torch.randperm(len(pol.dataset), device=dev, generator=torch.Generator(device=dev).manual_seed(3))
+        fused.begin_epoch(perm)
+        args, lib, st = fused._args_for(B), _lib.load(), K.stream()
+        _lib.check(lib.ppoaf_mat_update_fwd_bwd(C.byref(args), st), "mat fwd_bwd")
+        _lib.check(lib.ppoaf_mat_update_reduce(C.byref(args), st), "mat reduce")
+        torch.cuda.synchronize()
+        return pol.actor_critic.flat_grads.clone(), fused.totals.clone(), pol.buffer.actions.clone()
+
+    def epoch(mode, split="1", tail="1"):
+        monkeypatch.setenv("PPOAF_SPLIT_WGRAD", split)
+        monkeypatch.setenv("PPOAF_FUSED_TAIL", tail)
+        ppo = make(mode)
+        pol = ppo.policies["mat"]
+        ppo.rollout()
+        loader = PermutationLoader(pol.dataset, B, ppo.loader_generator)
+        pol.train()
+        ppo._ppo_batch_train(loader, "mat")
+        sd = ppo.status_dict["mat"]
+        opt = pol.actor_critic_optim
+        fused = ppo._fused_updater("mat", B)
+        assert (fused is not None) == (mode == "fused")
+        if fused is not None:
+            assert int(opt.step_count.item()) == n_mb and fused.n_wg == 66
+            assert fused.split == (split == "1") and (fused.tail_reason() == "") == (split == "1" and tail == "1"), fused.tail_reason()
+        return dict(w=pol.actor_critic.flat_params.detach().clone(), m=opt.exp_avg.clone(), v=opt.exp_avg_sq.clone(),
+                    g=pol.actor_critic.flat_grads.clone(), actions=pol.buffer.actions.clone(),
+                    status=[sd[k] for k in ("actor loss", "critic loss", "kl avg", "weighted entropy")])
+
+    chain, torch_path = epoch("fused"), epoch("torch")
+    three, slabs = epoch("fused", tail="0"), epoch("fused", split="0", tail="0")
+    for r in (torch_path, three, slabs):
+        assert torch.equal(r["actions"], chain["actions"])
+    # (a)
+    np.testing.assert_allclose(chain["status"], torch_path["status"], rtol=1e-4, atol=1e-5)
+    np.testing.assert_allclose(chain["w"].cpu().numpy(), torch_path["w"].cpu().numpy(), rtol=2e-4, atol=3e-5)
+    # (b)
+    for k, what in (("w", "parameters"), ("m", "exp_avg"), ("v", "exp_avg_sq"), ("g", "gradient bucket of the last mini-batch")):
+        assert torch.equal(chain[k], three[k]), f"{what} differ, max |d| {float((chain[k] - three[k]).abs().max()):.3e}"
+    # (c)
+    (g1, t1, a1), (g0, t0, a0) = first_minibatch("1"), first_minibatch("0")
+    assert torch.equal(a1, a0)
+    scale, d = float(g0.abs().max()), float((g1 - g0).abs().max())
+    assert d <= 1e-5 * scale, f"max |dg| {d:.3e} against max |g| {scale:.3e}"
+    np.testing.assert_allclose(t1.cpu().numpy(), t0.cpu().numpy(), rtol=1e-6, atol=1e-9)
+    np.testing.assert_allclose(chain["status"], slabs["status"], rtol=2e-4, atol=1e-4)
+
+
 @pytest.mark.parametrize("shared", [False, True])
 @pytest.mark.parametrize("update_mode", ["fused", "torch"])
 def test_mat_policy_with_icm_matches_cpu_port(update_mode, shared, tmp_path):
@@ -621,6 +707,9 @@ def test_filter_stack_in_the_loop(update_mode):
     dict(kind="c", NA=6, O=17, H=128, E=12, T=16, B=64),
     dict(kind="d", NA=5, O=18, H=64, E=8, T=12, B=32, d_inv=3, d_fwd=1),
     dict(kind="c", NA=2, O=3, H=64, E=16, T=64, B=16, graphs=True),          # 64 mini-batches: two graph chunks
+    # 33 row tiles: the wgrad tile's operand loop (wgrad_tile.hpp, 8 chunks per wave and trip) takes a third trip on waves
+    # 0 and 1 of the encoder jobs (66 chunks over both streams) and a second on wave 0 of the model jobs; tail of 32
+    dict(kind="d", NA=3, O=6, H=64, E=34, T=32, B=528),
 ])
 @pytest.mark.parametrize("form", ["split", "slabs"])
 def test_fused_icm_update_matches_oracle(case, form, monkeypatch):
