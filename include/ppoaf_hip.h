@@ -928,6 +928,63 @@ int ppoaf_lstm_backward(const ppoaf_lstm_desc_t* desc, const float* c0, const fl
 int ppoaf_lstm_wgrad(const ppoaf_lstm_desc_t* desc, const float* x, const float* h0, ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * K21  one env step of an LSTM actor / critic pair for all E rows in one launch
+ * replaces PPOPolicy.get_rollout_actions            policies/ppo_policy.py:729-794
+ *          PPO.get_policy_values + denormalisation  ppo.py:1030-1075, utils/misc.py:113-128
+ *          the hidden-state rows of add_episode_info policies/ppo_policy.py:593-627
+ *          the critic's extra step at a cut         ppo.py:1863-1881
+ *          LSTMNetwork.forward                      networks/ppo_networks/lstm.py:103-127
+ *          PPOPolicy.get_inference_actions          policies/ppo_policy.py:796-889
+ * The networks are K18's (same descriptors, coverage and bucket layout; steps = 1, `rows` is not read: E rules), both
+ * with ONE LSTM hidden size (one block size per launch; ff_hidden / ff_depth may differ); the recurrence, LayerNorm
+ * and head are K18's forward code at one step, the action heads K6's / K19's (categorical and Gaussian only).
+ * obs [E, actor.in_dim], critic_obs [E, critic.in_dim]; actor_h / actor_c / critic_h / critic_c [E, hidden] are the
+ * networks' states, stepped IN PLACE.  mode:
+ *   PPOAF_LSTM_STEP         2 * ceil(E/16) workgroups (actor / critic halves grouped per XCD as K6's).  Writes row t of
+ *                           the rollout buffer as K6 does (raw action, action, log-prob, value -- denormalised when
+ *                           normalize_values --, optional observation copies; Philox counter offset + row;
+ *                           forced_raw_action as K6's) and the states AFTER the step into the four *_hidden_out /
+ *                           *_cell_out rows [E, hidden].
+ *   PPOAF_LSTM_CRITIC_NEXT  critic only, ceil(E/16) workgroups: V(critic_obs) (denormalised) -> boot_value_out [E]; the
+ *                           critic's (h, c) are replaced only when the device byte *commit != 0.  With `terminated`
+ *                           (device bytes [E], 0 / 1) the four stored rows of the terminated envs are zeroed; the
+ *                           networks' own state is never reset.
+ *   PPOAF_LSTM_INFER        actor only: steps (actor_h, actor_c) and writes the ENVIRONMENT action to action_out in
+ *                           K19's layouts ([E] int64 / [E, D] float32); infer_mode = PPOAF_INFER_SAMPLE (K6's draw with
+ *                           counter offset + row) or PPOAF_INFER_DETERMINISTIC (argmax, lowest index on a tie /
+ *                           tanh(mean) scaled to the bounds).
+ *   PPOAF_LSTM_MASK         the zeroing of CRITIC_NEXT alone, for a step without a CRITIC_NEXT launch.
+ * ppoaf_lstm_policy_step_check validates the arguments on the host (pointers are only compared with NULL) and
+ * launches nothing; E = 0 is accepted by both and launches nothing.
+ * ------------------------------------------------------------------------ */
+#define PPOAF_LSTM_STEP        0
+#define PPOAF_LSTM_CRITIC_NEXT 1
+#define PPOAF_LSTM_INFER       2
+#define PPOAF_LSTM_MASK        3
+
+typedef struct {
+    ppoaf_lstm_desc_t actor, critic;
+    const float* obs; const float* critic_obs; int64_t E;
+    float* actor_h; float* actor_c; float* critic_h; float* critic_c;
+    int32_t head_kind; float min_std;           /* PPOAF_HEAD_CATEGORICAL or PPOAF_HEAD_GAUSSIAN */
+    const float* log_std;                       /* Gaussian head: device float32[actor.out_dim] */
+    const float* act_lo; const float* act_hi;   /* Gaussian head: bounds per action dimension; both NULL = [-1,1] */
+    const void* forced_raw_action;              /* STEP: NULL = sample, else the raw actions to log (as K6) */
+    uint64_t seed, offset;
+    int32_t normalize_values; int32_t mode;
+    const float* vn_mean; const float* vn_var;
+    void* raw_action_out; void* action_out; float* logp_out; float* value_out;
+    float* obs_copy_out; float* critic_obs_copy_out;
+    float* actor_hidden_out; float* actor_cell_out; float* critic_hidden_out; float* critic_cell_out;
+    int32_t infer_mode; int32_t _pad;
+    const uint8_t* commit; const uint8_t* terminated;
+    float* boot_value_out;
+} ppoaf_lstm_policy_step_args_t;
+
+int ppoaf_lstm_policy_step(const ppoaf_lstm_policy_step_args_t* args, ppoaf_stream_t stream);
+int ppoaf_lstm_policy_step_check(const ppoaf_lstm_policy_step_args_t* args);
+
+/* ------------------------------------------------------------------------ *
  * K17  gradient exchange between the ranks of one node over peer mappings (xGMI)
  * replaces, inside the per-mini-batch update chain, the comm.Allreduce of
  *          mpi_avg_gradients                       utils/mpi_utils.py:65-86  (called from ppo.py:2443-2448,

@@ -97,6 +97,22 @@ class PolicyInferArgs(C.Structure):
                 ("seed", C.c_uint64), ("offset", C.c_uint64), ("action_out", C.c_void_p)]
 
 
+class LstmPolicyStepArgs(C.Structure):
+    """ppoaf_lstm_policy_step_args_t (include/ppoaf_hip.h)."""
+    _fields_ = [("actor", LstmDesc), ("critic", LstmDesc), ("obs", C.c_void_p), ("critic_obs", C.c_void_p),
+                ("E", C.c_int64), ("actor_h", C.c_void_p), ("actor_c", C.c_void_p), ("critic_h", C.c_void_p),
+                ("critic_c", C.c_void_p), ("head_kind", C.c_int32), ("min_std", C.c_float),
+                ("log_std", C.c_void_p), ("act_lo", C.c_void_p), ("act_hi", C.c_void_p),
+                ("forced_raw_action", C.c_void_p), ("seed", C.c_uint64), ("offset", C.c_uint64),
+                ("normalize_values", C.c_int32), ("mode", C.c_int32), ("vn_mean", C.c_void_p), ("vn_var", C.c_void_p),
+                ("raw_action_out", C.c_void_p), ("action_out", C.c_void_p), ("logp_out", C.c_void_p),
+                ("value_out", C.c_void_p), ("obs_copy_out", C.c_void_p), ("critic_obs_copy_out", C.c_void_p),
+                ("actor_hidden_out", C.c_void_p), ("actor_cell_out", C.c_void_p),
+                ("critic_hidden_out", C.c_void_p), ("critic_cell_out", C.c_void_p),
+                ("infer_mode", C.c_int32), ("_pad", C.c_int32), ("commit", C.c_void_p), ("terminated", C.c_void_p),
+                ("boot_value_out", C.c_void_p)]
+
+
 class EvalScoresArgs(C.Structure):
     """ppoaf_eval_scores_args_t (include/ppoaf_hip.h)."""
     _fields_ = [("score", C.c_void_p), ("done", C.c_void_p), ("quota", C.c_void_p), ("E", C.c_int64),
@@ -281,6 +297,8 @@ SIGNATURES = {
     "ppoaf_lstm_forward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int32, _ptr]),
     "ppoaf_lstm_backward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),
     "ppoaf_lstm_wgrad": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),
+    "ppoaf_lstm_policy_step": (C.c_int, [C.POINTER(LstmPolicyStepArgs), _ptr]),
+    "ppoaf_lstm_policy_step_check": (C.c_int, [C.POINTER(LstmPolicyStepArgs)]),
     "ppoaf_peer_exchange_create": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "ppoaf_peer_exchange_export": (C.c_int, [_ptr, _ptr]),
     "ppoaf_peer_exchange_connect": (C.c_int, [_ptr, C.c_char_p]),

@@ -1,4 +1,6 @@
-// MultiDiscrete and MultiBinary heads on <= 8 actor outputs, one lane per row: shared by the rollout step (K6+K7,
+// Action heads on <= 8 actor outputs, one lane per row.  The Categorical and tanh-Gaussian rows of a rollout step and of
+// an evaluation step: one copy for the MLP kernels (K6, K19) and the LSTM kernel (K21).  The MultiDiscrete and
+// MultiBinary heads: shared by the rollout step (K6+K7,
 // policy_step.hip) and the fused update (K12, ppo_update_dev.hpp: ppo_head_loss).  Both take a row's log-prob from the
 // same functions here, on output values formed by the same output-layer code, so the log-prob logged for a row and the
 // one its first mini-batch recomputes are bitwise equal.
@@ -87,6 +89,103 @@ __device__ __forceinline__ void gauss_normals4(const unsigned long long seed, co
 }
 // a squashed action in [-1, 1] -> [lo, hi]                                          distributions.py:580-581
 __device__ __forceinline__ float unit_to_bounds(float a, float lo, float hi) { return ((a + 1.0f) / 2.0f) * (hi - lo) + lo; }
+// ---- one row of the Categorical / tanh-Gaussian head, one lane per row: the rollout step (K6, policy_step.hip, and K21,
+// lstm_policy_step.hip, share the *_step_row pair) and the evaluation step (K19, policy_infer.hip, and K21's INFER mode
+// share the *_infer_row pair).  z / mean: the row's outputs; the row's Philox counter is offset + e.
+// Discrete: sample (or the forced raw action, clamped into the classes) -> raw action, action, log-prob
+__device__ __forceinline__ void cat_step_row(const float* z, const int out_dim, const void* forced_raw_action, const long e,
+                                             const unsigned long long seed, const unsigned long long offset,
+                                             void* raw_action_out, void* action_out, float* logp_out) {
+    float p[8];
+    const float s2 = cat_probs(z, out_dim, p);
+    int a;
+    float pa = p[0];
+    if (forced_raw_action) {
+        const long fa = reinterpret_cast<const int64_t*>(forced_raw_action)[e];
+        a = fa < 0 ? 0 : (fa >= out_dim ? out_dim - 1 : (int)fa);
+    } else {
+        a = cat_sample(p, s2, out_dim, seed, offset + (unsigned long long)e);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (k == a) pa = p[k];
+    reinterpret_cast<int64_t*>(raw_action_out)[e] = a;
+    reinterpret_cast<int64_t*>(action_out)[e] = a;
+    logp_out[e] = logf(clamp_prob_u(pa / s2));
+}
+// Box: x = mean + sd * normal (or the forced raw action) -> raw action, tanh(x) scaled to the bounds (act_lo NULL: the
+// unit box), log-prob of the squashed Gaussian
+__device__ __forceinline__ void gauss_step_row(const float* mean_row, const int out_dim, const float* log_std,
+                                               const float min_std, const float* act_lo, const float* act_hi,
+                                               const void* forced_raw_action, const long e, const unsigned long long seed,
+                                               const unsigned long long offset, void* raw_action_out, void* action_out,
+                                               float* logp_out) {
+    float* raw = reinterpret_cast<float*>(raw_action_out) + e * out_dim;
+    float* ac = reinterpret_cast<float*>(action_out) + e * out_dim;
+    const bool rescale = act_lo != nullptr;
+    const float* forced = reinterpret_cast<const float*>(forced_raw_action);
+    float lp = 0.f, slog = 0.f;
+    for (int d0 = 0; d0 < out_dim; d0 += 4) {
+        float z[4];
+        gauss_normals4(seed, offset + (unsigned long long)e, (uint32_t)(d0 >> 2), z);
+        for (int j = 0; j < 4 && d0 + j < out_dim; ++j) {
+            const int d = d0 + j;
+            const float sd = fmaxf(softplus_u(log_std[d]), min_std);
+            const float mean = mean_row[d];
+            const float x = forced ? forced[e * out_dim + d] : mean + sd * z[j];
+            raw[d] = x;
+            float a = tanhf(x);
+            slog += logf(fmaxf(1.0f - a * a, 1e-6f));
+            if (rescale) a = unit_to_bounds(a, act_lo[d], act_hi[d]);
+            ac[d] = a;
+            const float zz = x - mean;
+            float l = -(zz * zz) / (2.0f * sd * sd) - logf(sd) - 0.91893853320467274178f;
+            lp += fminf(fmaxf(l, -100.f), 100.f);
+        }
+    }
+    logp_out[e] = lp - slog;
+}
+// Discrete, evaluation: the argmax, the lowest index on an exact tie (torch.argmax on the reference's CPU tensors), or a
+// sample -> the env action
+__device__ __forceinline__ void cat_infer_row(const float* zr, const int out_dim, const bool greedy, const long e,
+                                              const unsigned long long seed, const unsigned long long offset,
+                                              void* action_out) {
+    int a = 0;
+    if (greedy) {
+        float best = zr[0];
+#pragma unroll
+        for (int k = 1; k < 8; ++k)
+            if (k < out_dim && zr[k] > best) { best = zr[k]; a = k; }
+    } else {
+        float p[8];
+        const float s2 = cat_probs(zr, out_dim, p);
+        a = cat_sample(p, s2, out_dim, seed, offset + (unsigned long long)e);
+    }
+    reinterpret_cast<int64_t*>(action_out)[e] = a;
+}
+// Box, evaluation: tanh(mean), or tanh of a sample, scaled to the bounds -> the env action
+__device__ __forceinline__ void gauss_infer_row(const float* zr, const int out_dim, const bool greedy, const float* log_std,
+                                                const float min_std, const float* act_lo, const float* act_hi, const long e,
+                                                const unsigned long long seed, const unsigned long long offset,
+                                                void* action_out) {
+    float* ac = reinterpret_cast<float*>(action_out) + e * out_dim;
+    const bool rescale = act_lo != nullptr;
+    for (int d0 = 0; d0 < out_dim; d0 += 4) {
+        float z[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!greedy) gauss_normals4(seed, offset + (unsigned long long)e, (uint32_t)(d0 >> 2), z);
+        for (int j = 0; j < 4 && d0 + j < out_dim; ++j) {
+            const int d = d0 + j;
+            const float mean = zr[d];
+            float x = mean;
+            if (!greedy) {
+                const float sd = fmaxf(softplus_u(log_std[d]), min_std);
+                x = mean + sd * z[j];
+            }
+            float a = tanhf(x);
+            if (rescale) a = unit_to_bounds(a, act_lo[d], act_hi[d]);
+            ac[d] = a;
+        }
+    }
+}
 // MultiBinary: the uniform of bit d = component d % 4 of Philox (seed, ctr, d / 4); r carries the block from bit to bit
 __device__ __forceinline__ float bern_uniform(const unsigned long long seed, const unsigned long long ctr, const int d,
                                               Philox4& r) {

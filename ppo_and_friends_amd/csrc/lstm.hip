@@ -9,224 +9,15 @@
 // runs the same step structure in reverse: dgates of a step go through LDS and the MFMA forms dh_{t-1}.  The weight
 // gradients are a separate launch of 16 x 16 output tiles, each reduced over (row, step) samples by four waves in a
 // fixed order and summed in a fixed order: bitwise reproducible, no atomics.
-#include "common.hpp"
-#include "mlp_device.hpp"
+#include "lstm_device.hpp"
 
 namespace ppoaf {
 namespace {
 
-constexpr int kLRows = 16;                // rows per workgroup
-constexpr int kLMaxIn = 256;
-constexpr int kLMaxF = 128;
-constexpr int kLFS = kLMaxF + 4;          // LDS row stride of the head's buffers
-constexpr int kLMaxJobs = 12;
-
-inline long pad4(long n) { return (n + 3) / 4 * 4; }
-
-struct LstmLayout {
-    // parameters, float offsets into the network's bucket (module order, each tensor padded to 4 floats)
-    long w_ih, w_hh, b_ih, b_hh, ln_w, ln_b, fw[3], fb[3], size;
-    // workspace, float offsets
-    long gates, cst, hst, stats, acts[3], dG, dy, xhat, dz[3], total;
-};
-
-LstmLayout layout_of(const ppoaf_lstm_desc_t& d) {
-    LstmLayout L{};
-    const long I = d.in_dim, H = d.hidden, F = d.ff_hidden, O = d.out_dim, D = d.ff_depth;
-    long o = 0;
-    L.w_ih = o; o += pad4(4 * H * I);
-    L.w_hh = o; o += pad4(4 * H * H);
-    L.b_ih = o; o += pad4(4 * H);
-    L.b_hh = o; o += pad4(4 * H);
-    L.ln_w = o; o += pad4(H);
-    L.ln_b = o; o += pad4(H);
-    for (long l = 0; l <= D; ++l) {
-        const long in = l == 0 ? H : F, out = l == D ? O : F;
-        L.fw[l] = o; o += pad4(out * in);
-        L.fb[l] = o; o += pad4(out);
-    }
-    L.size = o;
-    const long R = d.rows, S = d.steps;
-    long w = 0;
-    L.gates = w; w += R * S * 4 * H;      // activated i, f, g, o per (row, step)
-    L.cst = w; w += R * S * H;            // c_t
-    L.hst = w; w += R * S * H;            // h_t
-    L.stats = w; w += R * 2;              // LayerNorm mean, 1 / std
-    L.acts[0] = w; w += R * H;            // activation(LayerNorm(h_S))
-    for (long l = 1; l <= D; ++l) { L.acts[l] = w; w += R * F; }    // hidden layer outputs (post-activation)
-    L.dG = w; w += R * S * 4 * H;         // d pre-activation gates
-    L.dy = w; w += R * H;                 // d LayerNorm output
-    L.xhat = w; w += R * H;               // normalised h_S
-    for (long l = 0; l <= D; ++l) { L.dz[l] = w; w += R * (l == D ? O : F); }   // d pre-activation output of layer l
-    L.total = w;
-    return L;
-}
-
-struct LstmArgs {
-    const float* P;
-    float* ws;
-    const float* x;
-    const float* h0;
-    const float* c0;
-    float* out;
-    float* hn;
-    float* cn;
-    const float* dout;
-    long N;
-    int S, I, F, D, O, act, stash;
-    LstmLayout L;
-};
-
-__device__ __forceinline__ float sigm(float z) { return 1.f / (1.f + expf(-z)); }
-
+// the forward body lives in lstm_device.hpp (K21, lstm_policy_step.hip, instantiates it as well)
 template <int H>
 __global__ __launch_bounds__(H / 16 * 64) void lstm_fwd_kernel(const LstmArgs a) {
-    constexpr int HT = H / 16, NT = HT * 64, HS = H + 4, XS = kLMaxIn + 4;
-    static_assert(2 * kLRows * XS >= kLRows * HS + 2 * kLRows * kLFS, "head buffers reuse the x buffers");
-    __shared__ float xs[2 * kLRows * XS];
-    __shared__ float hs[2][kLRows * HS];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const long r0 = (long)blockIdx.x * kLRows;
-    const long N = a.N;
-    const int S = a.S, I = a.I, Ip = (a.I + 15) & ~15;
-    const int j = 16 * w + (lane & 15);
-    const float* Wih = a.P + a.L.w_ih;
-    const float* Whh = a.P + a.L.w_hh;
-
-    // H <= 64: the four gate blocks stay in VGPRs for the window; H = 128 (128 VGPRs of them, more than the 256-register
-    // budget of 8 waves per CU leaves beside the rest) re-reads one gate block at a time from the L1 / L2 every step
-    constexpr bool kResident = H <= 64;
-    float4 fr[kResident ? 4 : 1][HT];
-    if constexpr (kResident) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) load_fwd_frags<HT>(Whh, q * H + 16 * w, lane, fr[q]);
-    }
-    float bias[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) bias[q] = a.P[a.L.b_ih + q * H + j] + a.P[a.L.b_hh + q * H + j];
-
-    auto load_x = [&](int t, float* dst) {
-        for (int e = tid; e < kLRows * Ip; e += NT) {
-            const int r = e / Ip, k = e - r * Ip;
-            const long n = r0 + r;
-            dst[r * XS + k] = (n < N && k < I) ? a.x[(n * S + t) * I + k] : 0.f;
-        }
-    };
-    for (int e = tid; e < kLRows * H; e += NT) {
-        const int r = e / H, k = e - r * H;
-        const long n = r0 + r;
-        hs[0][r * HS + k] = n < N ? a.h0[n * H + k] : 0.f;
-    }
-    float cr[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const long n = r0 + 4 * (lane >> 4) + g;
-        cr[g] = n < N ? a.c0[n * H + j] : 0.f;
-    }
-    load_x(0, xs);
-    __syncthreads();
-
-    for (int t = 0; t < S; ++t) {
-        const float* xb = xs + (t & 1) * kLRows * XS;
-        const float* hb = hs[t & 1];
-        f32x4 z[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if constexpr (!kResident) load_fwd_frags<HT>(Whh, q * H + 16 * w, lane, fr[0]);
-            f32x4 acc = {bias[q], bias[q], bias[q], bias[q]};
-            const float* wr = Wih + (long)(q * H + j) * I;
-#pragma unroll 1
-            for (int c = 0; c < Ip / 16; ++c) {
-                const int k0 = 16 * c + 4 * (lane >> 4);
-                const float4 x4 = *reinterpret_cast<const float4*>(xb + (lane & 15) * XS + k0);
-                const float b0 = k0 < I ? wr[k0] : 0.f, b1 = k0 + 1 < I ? wr[k0 + 1] : 0.f;
-                const float b2 = k0 + 2 < I ? wr[k0 + 2] : 0.f, b3 = k0 + 3 < I ? wr[k0 + 3] : 0.f;
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x4.x, b0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x4.y, b1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x4.z, b2, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x4.w, b3, acc, 0, 0, 0);
-            }
-            z[q] = acc + mfma_rows_x_frags<HT>(hb, HS, lane, fr[kResident ? q : 0], 0.f);
-        }
-        float* hnext = hs[(t + 1) & 1];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int rr = 4 * (lane >> 4) + g;
-            const long n = r0 + rr;
-            const float ig = sigm(z[0][g]), fg = sigm(z[1][g]), gg = tanhf(z[2][g]), og = sigm(z[3][g]);
-            const float c = fg * cr[g] + ig * gg;
-            const float h = og * tanhf(c);
-            cr[g] = c;
-            hnext[rr * HS + j] = h;
-            if (a.stash && n < N) {
-                float* gp = a.ws + a.L.gates + (n * S + t) * 4 * H + j;
-                gp[0] = ig; gp[H] = fg; gp[2 * H] = gg; gp[3 * H] = og;
-                a.ws[a.L.cst + (n * S + t) * H + j] = c;
-                a.ws[a.L.hst + (n * S + t) * H + j] = h;
-            }
-        }
-        if (t + 1 < S) load_x(t + 1, xs + ((t + 1) & 1) * kLRows * XS);
-        __syncthreads();
-    }
-    const float* hfin = hs[S & 1];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const int rr = 4 * (lane >> 4) + g;
-        const long n = r0 + rr;
-        if (n < N) {
-            if (a.hn) a.hn[n * H + j] = hfin[rr * HS + j];
-            if (a.cn) a.cn[n * H + j] = cr[g];
-        }
-    }
-
-    // ---- head: LayerNorm(H) -> activation -> Linear layers (the x buffers are free now)
-    float* A0 = xs;
-    float* A1 = xs + kLRows * HS;
-    float* A2 = A1 + kLRows * kLFS;
-    for (int r = w; r < kLRows; r += HT) {
-        const long n = r0 + r;
-        float s = 0.f;
-        for (int k = lane; k < H; k += 64) s += hfin[r * HS + k];
-        const float mean = wave_sum(s) / (float)H;
-        float v = 0.f;
-        for (int k = lane; k < H; k += 64) { const float d = hfin[r * HS + k] - mean; v += d * d; }
-        const float rstd = 1.f / sqrtf(wave_sum(v) / (float)H + 1e-5f);
-        for (int k = lane; k < H; k += 64) {
-            const float y = (hfin[r * HS + k] - mean) * rstd * a.P[a.L.ln_w + k] + a.P[a.L.ln_b + k];
-            const float y2 = act_fwd(y, a.act);
-            A0[r * HS + k] = y2;
-            if (a.stash && n < N) a.ws[a.L.acts[0] + n * H + k] = y2;
-        }
-        if (a.stash && n < N && lane == 0) { a.ws[a.L.stats + 2 * n] = mean; a.ws[a.L.stats + 2 * n + 1] = rstd; }
-    }
-    __syncthreads();
-    const float* in = A0;
-    int IS = HS, K = H;
-    for (int l = 0; l <= a.D; ++l) {
-        const bool last = l == a.D;
-        const int M = last ? a.O : a.F;
-        float* ob = (l & 1) ? A2 : A1;
-        const float* W = a.P + a.L.fw[l];
-        const float* b = a.P + a.L.fb[l];
-        for (int e = tid; e < kLRows * M; e += NT) {
-            const int r = e / M, m = e - r * M;
-            const long n = r0 + r;
-            const float* ir = in + r * IS;
-            const float* wr = W + (long)m * K;
-            float s = 0.f;
-            for (int k = 0; k < K; ++k) s += ir[k] * wr[k];
-            s += b[m];
-            if (last) {
-                if (n < N) a.out[n * M + m] = s;
-            } else {
-                s = act_fwd(s, a.act);
-                ob[r * kLFS + m] = s;
-                if (a.stash && n < N) a.ws[a.L.acts[l + 1] + n * M + m] = s;
-            }
-        }
-        __syncthreads();
-        in = ob; IS = kLFS; K = M;
-    }
+    lstm_rows_forward<H, false>(a, blockIdx.x);
 }
 
 template <int H>
@@ -426,41 +217,6 @@ __global__ __launch_bounds__(256) void lstm_wgrad_kernel(const WJobs J) {
     }
 }
 
-int check_desc(const ppoaf_lstm_desc_t* d, bool need_ws, const char* what) {
-    PPOAF_REQUIRE(d != nullptr && d->params != nullptr, "%s: desc / params is NULL", what);
-    PPOAF_REQUIRE(d->hidden == 32 || d->hidden == 64 || d->hidden == 128, "%s: hidden %d not in {32, 64, 128}", what, d->hidden);
-    PPOAF_REQUIRE(d->ff_hidden == 16 || d->ff_hidden == 32 || d->ff_hidden == 64 || d->ff_hidden == 128,
-                  "%s: ff_hidden %d not in {16, 32, 64, 128}", what, d->ff_hidden);
-    PPOAF_REQUIRE(d->ff_depth == 1 || d->ff_depth == 2, "%s: ff_depth %d not in {1, 2}", what, d->ff_depth);
-    PPOAF_REQUIRE(d->in_dim >= 1 && d->in_dim <= kLMaxIn, "%s: in_dim %d not in [1, %d]", what, d->in_dim, kLMaxIn);
-    PPOAF_REQUIRE(d->out_dim >= 1 && d->out_dim <= 8, "%s: out_dim %d not in [1, 8]", what, d->out_dim);
-    PPOAF_REQUIRE(d->steps >= 1 && d->steps <= 16, "%s: steps %lld not in [1, 16]", what, (long long)d->steps);
-    PPOAF_REQUIRE(d->rows >= 1, "%s: rows must be >= 1", what);
-    PPOAF_REQUIRE(d->activation == PPOAF_ACT_RELU || d->activation == PPOAF_ACT_LEAKY_RELU || d->activation == PPOAF_ACT_TANH,
-                  "%s: unknown activation %d", what, d->activation);
-    if (need_ws) {
-        const LstmLayout L = layout_of(*d);
-        PPOAF_REQUIRE(d->workspace != nullptr && d->workspace_floats >= L.total,
-                      "%s: workspace holds %lld floats, %ld needed", what, (long long)d->workspace_floats, L.total);
-    }
-    return PPOAF_OK;
-}
-
-LstmArgs args_of(const ppoaf_lstm_desc_t* d) {
-    LstmArgs a{};
-    a.P = d->params;
-    a.ws = d->workspace;
-    a.N = d->rows;
-    a.S = (int)d->steps;
-    a.I = d->in_dim;
-    a.F = d->ff_hidden;
-    a.D = d->ff_depth;
-    a.O = d->out_dim;
-    a.act = d->activation;
-    a.L = layout_of(*d);
-    return a;
-}
-
 template <template <int> class Launch, typename... T>
 int dispatch_h(int H, T... args) {
     if (H == 32) return Launch<32>::run(args...);
@@ -489,7 +245,7 @@ template <int H> struct BwdLaunch {
 using namespace ppoaf;
 
 extern "C" int ppoaf_lstm_workspace_floats(const ppoaf_lstm_desc_t* d, int64_t* floats_out) {
-    if (int rc = check_desc(d, false, "ppoaf_lstm_workspace_floats")) return rc;
+    if (int rc = check_lstm_desc(d, false, "ppoaf_lstm_workspace_floats")) return rc;
     PPOAF_REQUIRE(floats_out != nullptr, "ppoaf_lstm_workspace_floats: floats_out is NULL");
     const LstmLayout L = layout_of(*d);
     floats_out[0] = L.total;
@@ -499,23 +255,23 @@ extern "C" int ppoaf_lstm_workspace_floats(const ppoaf_lstm_desc_t* d, int64_t* 
 
 extern "C" int ppoaf_lstm_forward(const ppoaf_lstm_desc_t* d, const float* x, const float* h0, const float* c0,
                                   float* out, float* hn, float* cn, int32_t stash, ppoaf_stream_t stream) {
-    if (int rc = check_desc(d, stash != 0, "ppoaf_lstm_forward")) return rc;
+    if (int rc = check_lstm_desc(d, stash != 0, "ppoaf_lstm_forward")) return rc;
     PPOAF_REQUIRE(x && h0 && c0 && out, "ppoaf_lstm_forward: x / h0 / c0 / out is NULL");
-    LstmArgs a = args_of(d);
+    LstmArgs a = lstm_args_of(d);
     a.x = x; a.h0 = h0; a.c0 = c0; a.out = out; a.hn = hn; a.cn = cn; a.stash = stash != 0;
     return dispatch_h<FwdLaunch>(d->hidden, a, (hipStream_t)stream);
 }
 
 extern "C" int ppoaf_lstm_backward(const ppoaf_lstm_desc_t* d, const float* c0, const float* dout, ppoaf_stream_t stream) {
-    if (int rc = check_desc(d, true, "ppoaf_lstm_backward")) return rc;
+    if (int rc = check_lstm_desc(d, true, "ppoaf_lstm_backward")) return rc;
     PPOAF_REQUIRE(c0 && dout, "ppoaf_lstm_backward: c0 / dout is NULL");
-    LstmArgs a = args_of(d);
+    LstmArgs a = lstm_args_of(d);
     a.c0 = c0; a.dout = dout;
     return dispatch_h<BwdLaunch>(d->hidden, a, (hipStream_t)stream);
 }
 
 extern "C" int ppoaf_lstm_wgrad(const ppoaf_lstm_desc_t* d, const float* x, const float* h0, ppoaf_stream_t stream) {
-    if (int rc = check_desc(d, true, "ppoaf_lstm_wgrad")) return rc;
+    if (int rc = check_lstm_desc(d, true, "ppoaf_lstm_wgrad")) return rc;
     PPOAF_REQUIRE(x && h0 && d->grads, "ppoaf_lstm_wgrad: x / h0 / grads is NULL");
     const LstmLayout L = layout_of(*d);
     const long N = d->rows, S = d->steps, NS = N * S;

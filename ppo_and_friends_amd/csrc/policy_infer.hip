@@ -41,19 +41,7 @@ __global__ __launch_bounds__(kThreadsU) void policy_infer_kernel(InferDev u) {
     const long e = e0 + tid;
     const bool greedy = u.mode == PPOAF_INFER_DETERMINISTIC;
     if (u.head_kind == PPOAF_HEAD_CATEGORICAL) {
-        int a = 0;
-        if (greedy) {
-            // argmax, the lowest index on an exact tie (torch.argmax on the reference's CPU tensors)
-            float best = zr[0];
-#pragma unroll
-            for (int k = 1; k < 8; ++k)
-                if (k < out_dim && zr[k] > best) { best = zr[k]; a = k; }
-        } else {
-            float p[8];
-            const float s2 = cat_probs(zr, out_dim, p);
-            a = cat_sample(p, s2, out_dim, u.seed, u.offset + (unsigned long long)e);
-        }
-        reinterpret_cast<int64_t*>(u.action_out)[e] = a;
+        cat_infer_row(zr, out_dim, greedy, e, u.seed, u.offset, u.action_out);
     } else if (XH) {
         float z[8];
 #pragma unroll
@@ -102,25 +90,8 @@ __global__ __launch_bounds__(kThreadsU) void policy_infer_kernel(InferDev u) {
             }
         }
     } else {
-        const float* log_std = u.params + nd.offset + nd.log_std_off;
-        float* ac = reinterpret_cast<float*>(u.action_out) + e * out_dim;
-        const bool rescale = u.act_lo != nullptr;
-        for (int d0 = 0; d0 < out_dim; d0 += 4) {
-            float z[4] = {0.f, 0.f, 0.f, 0.f};
-            if (!greedy) gauss_normals4(u.seed, u.offset + (unsigned long long)e, (uint32_t)(d0 >> 2), z);
-            for (int j = 0; j < 4 && d0 + j < out_dim; ++j) {
-                const int d = d0 + j;
-                const float mean = zr[d];
-                float x = mean;
-                if (!greedy) {
-                    const float sd = fmaxf(softplus_u(log_std[d]), u.min_std);
-                    x = mean + sd * z[j];
-                }
-                float a = tanhf(x);
-                if (rescale) a = unit_to_bounds(a, u.act_lo[d], u.act_hi[d]);
-                ac[d] = a;
-            }
-        }
+        gauss_infer_row(zr, out_dim, greedy, u.params + nd.offset + nd.log_std_off, u.min_std, u.act_lo, u.act_hi, e,
+                        u.seed, u.offset, u.action_out);
     }
 }
 

@@ -55,21 +55,8 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
             if (u.normalize_values) v = u.vn_mean[0] + v * sqrtf(u.vn_var[0] + 1e-8f);   // misc.py:124-128
             u.value_out[e] = v;
         } else if (u.head_kind == PPOAF_HEAD_CATEGORICAL) {
-            float p[8];
-            const float s2 = cat_probs(sOut + s * kMaxOut, out_dim, p);
-            int a;
-            float pa = p[0];
-            if (u.forced_raw_action) {
-                const long fa = reinterpret_cast<const int64_t*>(u.forced_raw_action)[e];
-                a = fa < 0 ? 0 : (fa >= out_dim ? out_dim - 1 : (int)fa);
-            } else {
-                a = cat_sample(p, s2, out_dim, u.seed, u.offset + (unsigned long long)e);
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) if (k == a) pa = p[k];
-            reinterpret_cast<int64_t*>(u.raw_action_out)[e] = a;
-            reinterpret_cast<int64_t*>(u.action_out)[e] = a;
-            u.logp_out[e] = logf(clamp_prob_u(pa / s2));
+            cat_step_row(sOut + s * kMaxOut, out_dim, u.forced_raw_action, e, u.seed, u.offset, u.raw_action_out,
+                         u.action_out, u.logp_out);
         } else if (XH) {
             // MultiDiscrete / MultiBinary: the log-prob by the functions K12 recomputes it with (action_heads.hpp)
             float z[8];
@@ -117,31 +104,8 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
                 u.logp_out[e] = bern_logp(z, a, out_dim);
             }
         } else {
-            const float* log_std = P + nd.log_std_off;
-            float* raw = reinterpret_cast<float*>(u.raw_action_out) + e * out_dim;
-            float* ac = reinterpret_cast<float*>(u.action_out) + e * out_dim;
-            const bool rescale = u.act_lo != nullptr;
-            const float* forced = reinterpret_cast<const float*>(u.forced_raw_action);
-            float lp = 0.f, slog = 0.f;
-            for (int d0 = 0; d0 < out_dim; d0 += 4) {
-                float z[4];
-                gauss_normals4(u.seed, u.offset + (unsigned long long)e, (uint32_t)(d0 >> 2), z);
-                for (int j = 0; j < 4 && d0 + j < out_dim; ++j) {
-                    const int d = d0 + j;
-                    const float sd = fmaxf(softplus_u(log_std[d]), u.min_std);
-                    const float mean = sOut[s * kMaxOut + d];
-                    const float x = forced ? forced[e * out_dim + d] : mean + sd * z[j];
-                    raw[d] = x;
-                    float a = tanhf(x);
-                    slog += logf(fmaxf(1.0f - a * a, 1e-6f));
-                    if (rescale) a = unit_to_bounds(a, u.act_lo[d], u.act_hi[d]);
-                    ac[d] = a;
-                    const float zz = x - mean;
-                    float l = -(zz * zz) / (2.0f * sd * sd) - logf(sd) - 0.91893853320467274178f;
-                    lp += fminf(fmaxf(l, -100.f), 100.f);
-                }
-            }
-            u.logp_out[e] = lp - slog;
+            gauss_step_row(sOut + s * kMaxOut, out_dim, P + nd.log_std_off, u.min_std, u.act_lo, u.act_hi,
+                           u.forced_raw_action, e, u.seed, u.offset, u.raw_action_out, u.action_out, u.logp_out);
         }
     }
 }

@@ -756,3 +756,105 @@ def lstm_backward(desc, x, h0, c0, dout):
     lib = _lib.load()
     check(lib.ppoaf_lstm_backward(C.byref(desc), ptr(c0), ptr(dout), stream()), "lstm_backward")
     check(lib.ppoaf_lstm_wgrad(C.byref(desc), ptr(x), ptr(h0), stream()), "lstm_wgrad")
+
+
+# --------------------------------------------------------------------------
+# K21: one env step of an LSTM actor / critic pair (csrc/lstm_policy_step.hip)
+# --------------------------------------------------------------------------
+LSTM_STEP, LSTM_CRITIC_NEXT, LSTM_INFER, LSTM_MASK = 0, 1, 2, 3
+
+
+def lstm_policy_step_refusal(args):
+    """'' when ppoaf_lstm_policy_step_check accepts the filled _lib.LstmPolicyStepArgs (host only: nothing is launched,
+    pointers are only compared with NULL), else the library's reason."""
+    lib = _lib.load()
+    if lib.ppoaf_lstm_policy_step_check(C.byref(args)) == 0:
+        return ""
+    return lib.ppoaf_last_error().decode("utf-8", "replace")
+
+
+def _lstm_rows(t, E, width, name, dtype=torch.float32):
+    _req(t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == E * width,
+         f"{name} must be a contiguous {dtype} device tensor of {E} x {width} values")
+    return t.data_ptr()
+
+
+def _lstm_flags(t, n, name):
+    _req(t.is_cuda and t.dtype in (torch.bool, torch.uint8) and t.is_contiguous() and t.numel() == n,
+         f"{name} must be a contiguous bool / uint8 device tensor of {n} values")
+    return t.data_ptr()
+
+
+def _lstm_states(args, which, h, c):
+    H = getattr(args, which).hidden
+    setattr(args, which + "_h", _lstm_rows(h, args.E, H, which + " h"))
+    setattr(args, which + "_c", _lstm_rows(c, args.E, H, which + " c"))
+
+
+def _lstm_stored(args, stored):
+    """stored: the step's rows (actor_hidden, actor_cell, critic_hidden, critic_cell), each [E, H]."""
+    for f, t in zip(("actor_hidden_out", "actor_cell_out", "critic_hidden_out", "critic_cell_out"), stored):
+        setattr(args, f, _lstm_rows(t, args.E, args.actor.hidden, f))
+
+
+def _lstm_launch(args, mode):
+    args.mode = mode
+    check(_lib.load().ppoaf_lstm_policy_step(C.byref(args), stream()), "lstm_policy_step")
+
+
+def lstm_policy_step(args, obs, critic_obs, actor_state, critic_state, raw_action_out, action_out, logp_out, value_out,
+                     stored, obs_copy_out=None, critic_obs_copy_out=None, forced_raw_action=None):
+    """STEP: one launch steps both networks' (h, c) in place and writes the step's rows (see include/ppoaf_hip.h).
+    args: a _lib.LstmPolicyStepArgs whose descriptors, E, head fields, seed / offset and normaliser fields are set."""
+    E = args.E
+    args.obs = _lstm_rows(obs, E, args.actor.in_dim, "obs")
+    args.critic_obs = _lstm_rows(critic_obs, E, args.critic.in_dim, "critic_obs")
+    _lstm_states(args, "actor", *actor_state)
+    _lstm_states(args, "critic", *critic_state)
+    gauss = args.head_kind == HEAD_GAUSSIAN
+    width, adt = (args.actor.out_dim, torch.float32) if gauss else (1, torch.int64)
+    args.raw_action_out = _lstm_rows(raw_action_out, E, width, "raw_action_out", adt)
+    args.action_out = _lstm_rows(action_out, E, width, "action_out", adt)
+    args.logp_out = _lstm_rows(logp_out, E, 1, "logp_out")
+    args.value_out = _lstm_rows(value_out, E, 1, "value_out")
+    _lstm_stored(args, stored)
+    args.obs_copy_out = None if obs_copy_out is None else _lstm_rows(obs_copy_out, E, args.actor.in_dim, "obs_copy_out")
+    args.critic_obs_copy_out = None if critic_obs_copy_out is None else \
+        _lstm_rows(critic_obs_copy_out, E, args.critic.in_dim, "critic_obs_copy_out")
+    args.forced_raw_action = None if forced_raw_action is None else \
+        _lstm_rows(forced_raw_action, E, width, "forced_raw_action", adt)
+    _lstm_launch(args, LSTM_STEP)
+
+
+def lstm_critic_next(args, critic_obs, critic_state, boot_value_out, commit, terminated=None, stored=None):
+    """CRITIC_NEXT: V(critic_obs) -> boot_value_out [E]; the critic's (h, c) are replaced only where the device byte
+    `commit` is set; with `terminated` [E] the four `stored` rows of those envs are zeroed."""
+    E = args.E
+    args.critic_obs = _lstm_rows(critic_obs, E, args.critic.in_dim, "critic_obs")
+    _lstm_states(args, "critic", *critic_state)
+    args.boot_value_out = _lstm_rows(boot_value_out, E, 1, "boot_value_out")
+    args.commit = _lstm_flags(commit, 1, "commit")
+    args.terminated = None
+    if terminated is not None:
+        args.terminated = _lstm_flags(terminated, E, "terminated")
+        _lstm_stored(args, stored)
+    _lstm_launch(args, LSTM_CRITIC_NEXT)
+
+
+def lstm_mask_stored(args, terminated, stored):
+    """MASK: the four `stored` rows of the terminated envs are zeroed (a step without a CRITIC_NEXT launch)."""
+    args.terminated = _lstm_flags(terminated, args.E, "terminated")
+    _lstm_stored(args, stored)
+    _lstm_launch(args, LSTM_MASK)
+
+
+def lstm_policy_infer(args, obs, actor_state, action_out, deterministic):
+    """INFER: steps the actor's (h, c) in place and writes the env action ([E] int64 / [E, D] float32)."""
+    E = args.E
+    args.obs = _lstm_rows(obs, E, args.actor.in_dim, "obs")
+    _lstm_states(args, "actor", *actor_state)
+    gauss = args.head_kind == HEAD_GAUSSIAN
+    args.action_out = _lstm_rows(action_out, E, args.actor.out_dim if gauss else 1, "action_out",
+                                 torch.float32 if gauss else torch.int64)
+    args.infer_mode = INFER_DETERMINISTIC if deterministic else INFER_SAMPLE
+    _lstm_launch(args, LSTM_INFER)

@@ -134,6 +134,7 @@ class PPOPolicy:
         self.use_huber_loss = use_huber_loss
         self.frozen = False
         self.fused_action_heads = False      # MultiDiscrete / MultiBinary heads on K6 / K12 (set by PPO(update_mode="fused"))
+        self.fused_lstm_step = True          # K21 for the rollout / evaluation step of a covered LSTM policy
         self.random_seed = random_seed
         self.lr = _callable(lr)
         self.icm_lr = _callable(icm_lr)
@@ -415,6 +416,165 @@ class PPOPolicy:
         K.policy_step(a)
         return buf.actions[t]
 
+    # ---- K21: the rollout / evaluation step of an LSTM policy in one launch (csrc/lstm_policy_step.hip)
+    def lstm_step_unsupported_reason(self):
+        """'' when K21 (ppoaf_lstm_policy_step) covers this policy: a device LSTM policy that PPO has not put on the
+        torch path, both networks on K18 (`use_hip`) with one LSTM hidden size, and the library's own check accepting;
+        else why today's route (forward_logits + torch ops) is taken.  `fused_lstm_step = False` switches K21 off."""
+        if not self.using_lstm:
+            return "not an LSTM policy"
+        if not getattr(self, "fused_lstm_step", True):
+            return "fused_lstm_step is switched off on this policy"
+        if self.device.type != "cuda":
+            return f"the policy lives on {self.device}: K21 needs a HIP device"
+        if getattr(self, "update_mode", "auto") == "torch":
+            return "update_mode='torch' keeps the policy on the torch-ROCm path"
+        key = (self.policy_params.data_ptr(), bool(self.actor.use_hip), bool(self.critic.use_hip), bool(self.enable_icm))
+        if getattr(self, "_lstm_step_reason", (None, ""))[0] != key:
+            self._lstm_step_reason = (key, self._lstm_step_scope())
+        return self._lstm_step_reason[1]
+
+    def _lstm_step_scope(self):
+        from ..fused_update import FusedLstm
+        why = FusedLstm.unsupported_reason(self)
+        if why:
+            return why
+        if not (self.actor.use_hip and self.critic.use_hip):
+            return "the networks run nn.LSTM (use_hip is not set: update_mode='auto' keeps today's route)"
+        ha, hc = self.actor.lstm_hidden_size, self.critic.lstm_hidden_size
+        if ha != hc:
+            return f"LSTM hidden sizes differ (actor {ha}, critic {hc}): one K21 launch has one block size"
+        if self.enable_icm:
+            return "ICM policies keep today's route (K21 does not keep the next-observation rows)"
+        # what the library itself refuses: host only, nothing is launched and no pointer is followed
+        a = self._new_lstm_step_args(1)
+        a.mode, a.infer_mode = K.LSTM_INFER, K.INFER_DETERMINISTIC
+        a.obs = a.actor_h = a.actor_c = a.action_out = self.policy_params.data_ptr()
+        return K.lstm_policy_step_refusal(a)
+
+    def _new_lstm_step_args(self, E):
+        """_lib.LstmPolicyStepArgs with everything that stays from step to step, for E rows."""
+        from .. import _lib
+        from ..fused_update import _activation_code
+        from ..networks.distributions import GaussianDistribution
+        a = _lib.LstmPolicyStepArgs()
+        for tag, net in (("actor", self.actor), ("critic", self.critic)):
+            d = getattr(a, tag)
+            dims = net.ff_layers.layer_dims()
+            d.in_dim, d.hidden, d.ff_hidden, d.ff_depth = net.in_size, net.lstm_hidden_size, dims[0][1], len(dims) - 1
+            d.out_dim, d.activation = net.out_size, _activation_code(net.activation)
+            d.rows, d.steps = E, 1
+            d.params = net.flat_params.data_ptr()
+        a.E = E
+        dist = self.actor.distribution
+        gauss = isinstance(dist, GaussianDistribution)
+        a.head_kind = K.HEAD_GAUSSIAN if gauss else K.HEAD_CATEGORICAL
+        a.min_std = float(getattr(dist, "min_std", 0.01))
+        if gauss:
+            a.log_std = dist.log_std.data_ptr()
+            lo, hi = dist.bound_tensors()
+            a.act_lo = None if lo is None else lo.data_ptr()
+            a.act_hi = None if hi is None else hi.data_ptr()
+        return a
+
+    def _lstm_step_args(self, E):
+        """The K21 arguments for E rows, and both networks' (h, c) as its in / out buffers: reset by the networks' own
+        rule (lstm.py:109-113: when the batch size changes), then stepped in place."""
+        st = getattr(self, "_lstm_step_state", None)
+        key = (E, self.policy_params.data_ptr())
+        if st is None or st["key"] != key:
+            st = self._lstm_step_state = dict(key=key, args=self._new_lstm_step_args(E),
+                                              one=torch.ones(1, dtype=torch.uint8, device=self.device))
+        for net in (self.actor, self.critic):
+            hs = net.hidden_state
+            if hs is None or hs[0].shape[1] != E:
+                net.reset_hidden_state(batch_size=E, device=self.device)
+            elif not (hs[0].is_contiguous() and hs[1].is_contiguous()):
+                net.hidden_state = (hs[0].contiguous(), hs[1].contiguous())
+        return st
+
+    def _lstm_stored_rows(self, t):
+        h = self.buffer.hidden
+        return h["actor_hidden"][t], h["actor_cell"][t], h["critic_hidden"][t], h["critic_cell"][t]
+
+    def lstm_rollout_step(self, t, obs, critic_obs, value_normalizer=None, forced_raw_action=None):
+        """
+        rollout_step for an LSTM policy (K21, STEP): both networks' forward passes, sampling (or the forced raw action),
+        log-prob, value (+ denormalisation) and row t of the buffer -- actions, log-probs, values, observation copies and
+        the four hidden-state rows -- in ONE launch that steps the networks' `hidden_state` tensors in place.  Returns
+        the action row for env.step; `lstm_finish_step` takes the environment's answer.
+        """
+        buf = self.buffer
+        E = buf.C
+        a = self._lstm_step_args(E)["args"]
+        a.seed, a.offset = self.actor.distribution.rng.take(E)
+        self._lstm_normalizer(a, value_normalizer)
+        K.lstm_policy_step(a, obs, critic_obs, self.actor.hidden_state, self.critic.hidden_state, buf.raw_actions[t],
+                           buf.actions[t], buf.log_probs[t], buf.values[t], self._lstm_stored_rows(t),
+                           buf.observations[t], buf.critic_observations[t], forced_raw_action)
+        return buf.actions[t]
+
+    @staticmethod
+    def _lstm_normalizer(a, value_normalizer):
+        a.normalize_values = 0
+        if value_normalizer is not None:
+            a.normalize_values = 1
+            a.vn_mean = value_normalizer.running_stats.mean_t.data_ptr()
+            a.vn_var = value_normalizer.running_stats.var_t.data_ptr()
+
+    def lstm_finish_step(self, t, rewards, terminated, next_critic_obs=None, cut=None, value_normalizer=None):
+        """
+        The environment's answer for step t of an LSTM policy: rewards, and the stored hidden rows of the envs that
+        terminated zeroed (ppo_policy.py:593-627).  With `next_critic_obs` the same launch (K21, CRITIC_NEXT) writes
+        V(next critic observation) to boot_value[t] and keeps the critic's stepped state only where the device flag
+        `cut` (one bool / byte, never read by the host) is set (ppo.py:1863-1881); without it the zeroing is a launch of
+        its own (MASK).
+        """
+        buf = self.buffer
+        buf.rewards[t].copy_(rewards.reshape(-1))
+        buf.steps_written = max(buf.steps_written, t + 1)
+        self._t = t + 1
+        a = self._lstm_step_args(buf.C)["args"]
+        terminated = terminated.reshape(-1).contiguous()
+        if next_critic_obs is None:
+            K.lstm_mask_stored(a, terminated, self._lstm_stored_rows(t))
+            return
+        self._lstm_normalizer(a, value_normalizer)
+        K.lstm_critic_next(a, next_critic_obs, self.critic.hidden_state, buf.boot_value[t], cut.reshape(1), terminated,
+                           self._lstm_stored_rows(t))
+
+    def lstm_last_value(self, t, critic_obs, value_normalizer=None):
+        """V(critic_obs) after the last step of a rollout -> boot_value[t] (K21, CRITIC_NEXT with the flag set: the critic
+        is stepped, as get_critic_values steps it).  Returns that row."""
+        buf = self.buffer
+        st = self._lstm_step_args(buf.C)
+        self._lstm_normalizer(st["args"], value_normalizer)
+        K.lstm_critic_next(st["args"], critic_obs, self.critic.hidden_state, buf.boot_value[t], st["one"])
+        return buf.boot_value[t]
+
+    def _lstm_infer_step(self, t_obs, deterministic):
+        """K21, INFER: one launch steps the actor's hidden state in place and writes the env action into a reusable
+        tensor (K19's shapes and dtypes)."""
+        E = t_obs.shape[0]
+        hs = self.actor.hidden_state
+        if hs is None or hs[0].shape[1] != E:
+            self.actor.reset_hidden_state(batch_size=E, device=self.device)
+        elif not (hs[0].is_contiguous() and hs[1].is_contiguous()):
+            self.actor.hidden_state = (hs[0].contiguous(), hs[1].contiguous())
+        st = getattr(self, "_lstm_infer_state", None)
+        key = (E, self.policy_params.data_ptr())
+        if st is None or st["key"] != key:
+            a = self._new_lstm_step_args(E)
+            gauss = a.head_kind == K.HEAD_GAUSSIAN
+            out = torch.zeros((E, a.actor.out_dim) if gauss else (E,), dtype=torch.float32 if gauss else torch.int64,
+                              device=self.device)
+            st = self._lstm_infer_state = dict(key=key, args=a, out=out)
+        a = st["args"]
+        if not deterministic:
+            a.seed, a.offset = self.eval_rng().take(E)
+        K.lstm_policy_infer(a, t_obs.reshape(E, -1).contiguous(), self.actor.hidden_state, st["out"], deterministic)
+        return st["out"]
+
     def finish_step(self, t, rewards, next_obs=None):
         """The environment's answer for step t: rewards (and next observations when ICM keeps them)."""
         buf = self.buffer
@@ -481,7 +641,7 @@ class PPOPolicy:
         if getattr(self, "update_mode", "auto") == "torch":
             return "update_mode='torch' keeps the policy on the torch-ROCm path"
         if self.using_lstm:
-            return "LSTM policies go through forward_logits (K18 under update_mode='fused')"
+            return "LSTM policies are not K19's: K21 or forward_logits (see lstm_step_unsupported_reason)"
         # (asked once per evaluation step: the answer is kept for as long as what it depends on stays)
         key = (self.policy_params.data_ptr(), bool(self.fused_action_heads))
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
@@ -537,7 +697,8 @@ class PPOPolicy:
         """
         ppo_policy.py:796-889 -> the environment action of every row: the distribution's refined prediction when
         `deterministic`, else a sample.  numpy in -> numpy out, device tensor in -> device tensor out.  On K19 (see
-        inference_unsupported_reason) the result is a reusable tensor that the next call overwrites.
+        inference_unsupported_reason) and on K21 (an LSTM policy, see lstm_step_unsupported_reason; the actor's hidden
+        state is stepped in place) the result is a reusable tensor that the next call overwrites.
         """
         if len(obs.shape) < 2:
             raise ValueError(f"get_inference_actions expects a batch of observations, got shape {obs.shape}")
@@ -545,6 +706,8 @@ class PPOPolicy:
         t_obs = self._to_device(obs)
         if self.inference_unsupported_reason() == "":
             action = self._infer_step(t_obs, deterministic)
+        elif self.using_lstm and self.lstm_step_unsupported_reason() == "":
+            action = self._lstm_infer_step(t_obs, deterministic)
         else:
             dist = self.actor.distribution
             with torch.no_grad():

@@ -342,6 +342,8 @@ class PPO:
         may_end_early = getattr(env, "term_table", True) is not None or self.max_ts_per_ep < T
         fused_step = (self.update_mode != "torch" and self.device.type == "cuda"
                       and pol.fused_step_unsupported_reason() == "")
+        # K21: an LSTM policy's step in one launch (STEP), its answer in a second (CRITIC_NEXT or MASK)
+        lstm_step = pol.using_lstm and self.device.type == "cuda" and pol.lstm_step_unsupported_reason() == ""
         vn = self.value_normalizers[policy_id] if self.normalize_values else None
         grouped = pol.agent_grouping
         if grouped:
@@ -399,6 +401,14 @@ class PPO:
                     intr_buf[t] = pol.get_intrinsic_reward(obs, nxt_obs, action)   # ppo.py:1719-1723: the post-step observation
                     reward = reward + intr_buf[t]
                 pol.finish_step(t, reward, term_obs)
+            elif lstm_step:
+                action = pol.lstm_rollout_step(t, obs.contiguous(), critic_obs.contiguous(), vn, forced_raw_action=replay(t))
+                nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(action))
+                nat_buf[t].copy_(self._natural_reward(env, reward))
+                if self.ext_reward_weight != 1.0:
+                    reward = reward * self.ext_reward_weight
+                if not (may_end_early and t < T - 1):      # no critic step on the next observation: the zeroing alone
+                    pol.lstm_finish_step(t, reward, terminated)
             elif grouped:
                 g_obs, g_cobs = group(obs), group(critic_obs)
                 raw_action, action, log_prob = pol.get_rollout_actions(g_cobs if pol.expanded_actor_space else g_obs, forced_raw_action=replay(t))
@@ -442,10 +452,14 @@ class PPO:
                     # stateful LSTM critic once more.  Branch-free here: the extra step is computed every
                     # time and kept only if the reference would have taken it.
                     cut = (((ep_ts == self.max_ts_per_ep) & ~terminated).any() | truncated.any())   # ep_ts of terminated envs is 0 by then (:1851)
-                    h_old = tuple(x.clone() for x in pol.critic.hidden_state)
-                    v_next = self.get_policy_values(policy_id, nxt_cobs)
-                    pol.critic.hidden_state = tuple(torch.where(cut, n, o) for n, o in zip(pol.critic.hidden_state, h_old))
-                    buf.boot_value[t].copy_(v_next)
+                    if lstm_step:
+                        # the flag stays on the device: the launch keeps the critic's stepped state only where it is set
+                        pol.lstm_finish_step(t, reward, terminated, nxt_cobs.contiguous(), cut, vn)
+                    else:
+                        h_old = tuple(x.clone() for x in pol.critic.hidden_state)
+                        v_next = self.get_policy_values(policy_id, nxt_cobs)
+                        pol.critic.hidden_state = tuple(torch.where(cut, n, o) for n, o in zip(pol.critic.hidden_state, h_old))
+                        buf.boot_value[t].copy_(v_next)
                 buf.end_kind[t] = torch.where(terminated, 1, torch.where(boot, 2, 0)).to(torch.int8)
                 ep_ts = torch.where(terminated | boot, torch.zeros_like(ep_ts), ep_ts)
                 buf.fixed_length = False        # (also at the last row: an env may TERMINATE there -- ts_per_rollout = 1 made it visible)
@@ -453,11 +467,15 @@ class PPO:
         # bootstrap values: V(next obs).  For ends before the last row the next
         # observation's value is the value logged at t+1 (same critic, same
         # normaliser state during a rollout); the last row needs one more pass.
-        next_value = self.get_policy_values(policy_id, group(critic_obs) if grouped else critic_obs)
+        if lstm_step:
+            next_value = pol.lstm_last_value(T - 1, critic_obs.contiguous(), vn)      # (lands in boot_value[T - 1])
+        else:
+            next_value = self.get_policy_values(policy_id, group(critic_obs) if grouped else critic_obs)
         if may_end_early:
             if not pol.using_lstm:           # stateless critics: V(next obs) is the value logged at t + 1
                 buf.boot_value[:-1].copy_(buf.values[1:])
-            buf.boot_value[T - 1].copy_(next_value)
+            if not lstm_step:
+                buf.boot_value[T - 1].copy_(next_value)
             buf.boot_reward.copy_(buf.boot_value)
             buf.boot_stats = None
             if pol.enable_icm:
@@ -475,7 +493,8 @@ class PPO:
         else:
             buf.boot_stats = None
             buf.end_kind[T - 1].fill_(2)
-            buf.boot_value[T - 1].copy_(next_value)
+            if not lstm_step:
+                buf.boot_value[T - 1].copy_(next_value)
             buf.boot_reward[T - 1].copy_(next_value)
         self._obs = (obs, critic_obs)
         pol.finalize_dataset()

@@ -5,6 +5,9 @@ Evaluation env-steps/s of `ppo_and_friends_amd.testing.test_policy` at three sha
           c3  SyntheticFixedLengthEnv, E = 4096, actor 17 -> 256^3 -> 6 (Box(6), C3's actor shape), no filters
           c5  SyntheticFixedLengthEnv, E = 4096, O = 18, Discrete(5), 3 agents, MATPolicy defaults (C5's shape), no
               filters; only with --shape c5 ("both" stays c2 + c3)
+          lstm  BatchedCartPoleEnv, E = 4096, LSTM actor / critic of the reference's cart_pole_lstm baseline (4
+              observations, Discrete(2), LSTM 32, feed-forward 16, LeakyReLU), update_mode="fused"; only with --shape
+              lstm.  Also times PPO.rollout (T = --rollout-steps per env) with the K21 step on and off.
   legs    a   this package: test_policy (K19 `ppoaf_policy_infer` + `ppoaf_eval_scores_step` per step, one host read
               of `remaining` every check_every steps)
           b   the baseline: the same loop written only with what the package had before K19 -- the torch forward of
@@ -13,12 +16,15 @@ Evaluation env-steps/s of `ppo_and_friends_amd.testing.test_policy` at three sha
               c5: the path evaluation took before K20 on the same object -- `inference_unsupported_reason` forced
               non-empty, so PPO.get_inference_actions regroups and the network modules decode, and one
               `ppoaf_eval_scores_step` launch per agent and one more per agent for the policy's book
+              lstm: leg a is K21 (`ppoaf_lstm_policy_step`, INFER), leg b the same test_policy with
+              `pol.fused_lstm_step = False`: forward_logits on K18 + torch ops, the route before K21
 
 Both legs play the same number of test runs from the same env seed; env-steps/s = E x loop steps / wall time, printed as
 median and spread (min .. max) over `--repeats`, then one JSON line.  `--leg a|b --shape c2|c3 --repeats 1` under
 `rocprofv3 --kernel-trace --stats` gives the launches per evaluation step of one leg (the loop steps are printed).
 
-    python tools/eval_bench.py [--shape both|c2|c3|c5] [--leg both|a|b] [--envs 4096] [--runs-per-env 2] [--repeats 5]
+    python tools/eval_bench.py [--shape both|c2|c3|c5|lstm] [--leg both|a|b] [--envs 4096] [--runs-per-env 2] [--repeats 5]
+                               [--rollout-steps 128]
 """
 import argparse
 import json
@@ -50,7 +56,7 @@ def count_steps(ppo):
     raw.step = step
 
 
-def make(shape, E):
+def make(shape, E, T=32):
     from ppo_and_friends_amd.ppo import PPO
     from ppo_and_friends_amd.environments.cartpole import BatchedCartPoleEnv
     from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
@@ -62,6 +68,15 @@ def make(shape, E):
         settings = {"p": (None, probe.observation_space, probe.observation_space, Discrete(2),
                           dict(actor_kw_args=dict(net), critic_kw_args=dict(net)))}
         ppo = PPO(env_gen, settings, device=DEV, random_seed=1, envs_per_proc=E, ts_per_rollout=32, save_state=False)
+    elif shape == "lstm":
+        from ppo_and_friends_amd.networks.lstm import LSTMNetwork
+        env_gen = lambda: BatchedCartPoleEnv(E, DEV, seed=0, max_episode_steps=200)
+        probe = BatchedCartPoleEnv(1, DEV)
+        net = dict(lstm_hidden_size=32, ff_hidden_size=16, activation=nn.LeakyReLU())
+        settings = {"p": (None, probe.observation_space, probe.observation_space, Discrete(2),
+                          dict(ac_network=LSTMNetwork, actor_kw_args=dict(net), critic_kw_args=dict(net)))}
+        ppo = PPO(env_gen, settings, device=DEV, random_seed=1, envs_per_proc=E, ts_per_rollout=T, max_ts_per_ep=200,
+                  save_state=False, update_mode="fused")
     elif shape == "c5":
         from ppo_and_friends_amd.policies.mat_policy import MATPolicy
 
@@ -177,6 +192,51 @@ def leg_b_mat(ppo, N, check_every):
             "p": {"low_score": lo, "high_score": hi, "avg_score": avg}}
 
 
+def leg_b_lstm(ppo, N, check_every):
+    """test_policy with the K21 step switched off: the route an LSTM policy's evaluation took before K21."""
+    pol = ppo.policies["p"]
+    pol.fused_lstm_step = False
+    try:
+        return leg_a(ppo, N, check_every)
+    finally:
+        pol.fused_lstm_step = True
+
+
+def rollout_seconds(ppo, fused):
+    """Wall time of one PPO.rollout with the K21 step on or off (synchronised before and after)."""
+    pol = ppo.policies["p"]
+    pol.fused_lstm_step = fused
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ppo.rollout()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    finally:
+        pol.fused_lstm_step = True
+        pol.clear_dataset()
+
+
+def time_rollouts(ppo, result, legs, repeats, warmup):
+    """Rollout seconds per leg (a: K21, b: the attribute off), alternated; median and min .. max."""
+    for name in legs:
+        for _ in range(warmup):
+            rollout_seconds(ppo, name == "a")
+    times = {k: [] for k in legs}
+    for _ in range(repeats):
+        for name in legs:
+            times[name].append(rollout_seconds(ppo, name == "a"))
+    T = ppo.ts_per_rollout // ppo.envs_per_proc
+    for name in legs:
+        t = np.array(times[name])
+        result[f"lstm_rollout_{name}_seconds"] = float(np.median(t))
+        result[f"lstm_rollout_{name}_spread"] = [float(t.min()), float(t.max())]
+        print(f"lstm rollout leg {name}: seconds median {np.median(t):.4f}  spread {t.min():.4f} .. {t.max():.4f}"
+              f"  (T {T} x E {ppo.envs_per_proc})", flush=True)
+    if len(legs) == 2:
+        result["lstm_rollout_b_over_a"] = result["lstm_rollout_b_seconds"] / result["lstm_rollout_a_seconds"]
+
+
 def timed(fn, ppo, N, check_every):
     ppo.loop_steps[0] = 0
     torch.cuda.synchronize()
@@ -188,12 +248,13 @@ def timed(fn, ppo, N, check_every):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", default="both", choices=["both", "c2", "c3", "c5"])
+    ap.add_argument("--shape", default="both", choices=["both", "c2", "c3", "c5", "lstm"])
     ap.add_argument("--leg", default="both", choices=["both", "a", "b"])
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--runs-per-env", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--rollout-steps", type=int, default=128, help="--shape lstm: env steps per env of the timed rollouts (0: skip them)")
     args = ap.parse_args()
     from ppo_and_friends_amd import testing
     testing.rank_print = lambda *a, **k: None        # the score report is not what is timed
@@ -203,9 +264,15 @@ def main():
     E, N = args.envs, args.envs * args.runs_per_env
     result = {"envs": E, "num_test_runs": N}
     for shape in shapes:
-        ppo = make(shape, E)
-        check_every = 50 if shape == "c2" else 64
-        if "a" in legs:
+        ppo = make(shape, E, max(1, args.rollout_steps) if shape == "lstm" else 32)
+        check_every = 50 if shape in ("c2", "lstm") else 64
+        if shape == "lstm":
+            assert ppo.policies["p"].lstm_step_unsupported_reason() == "", ppo.policies["p"].lstm_step_unsupported_reason()
+            if "b" in legs:
+                legs = dict(legs, b=leg_b_lstm)
+            if args.rollout_steps > 0:
+                time_rollouts(ppo, result, legs, args.repeats, args.warmup)
+        elif "a" in legs:
             assert ppo.policies["p"].inference_unsupported_reason() == "", ppo.policies["p"].inference_unsupported_reason()
         if shape == "c5" and "b" in legs:
             legs = dict(legs, b=leg_b_mat)
