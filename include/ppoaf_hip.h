@@ -754,6 +754,63 @@ int ppoaf_icm_intrinsic_reward(const ppoaf_icm_update_args_t* args, float scale,
                                ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * K14, general shapes: the same mini-batch update and rollout-time reward for ICMs whose
+ * encoder, encoding and models have widths of their own
+ * replaces one iteration of PPO._icm_batch_train   ppo.py:2487-2567
+ *          ICM.__init__ / ICM.forward              networks/ppo_networks/icm.py:227-430
+ *          LinearObservationEncoder                networks/encoders.py:9-56
+ *          PPOPolicy.get_intrinsic_reward          policies/ppo_policy.py:954-1007
+ * With pad16(x) = 16 ceil(x / 16):
+ *   encoder  O -> E -> E -> E -> D (last layer linear)     E in {32, 64, 128}, 1 <= D <= 128, 1 <= O <= 1024
+ *   inverse  2D -> Mi (x depth_inv hidden layers) -> A     Mi, Mf in {32, 64, 128}, depths 1..3, A, A_in <= 8
+ *   forward  D + A_in -> Mf (x depth_fwd hidden layers) -> D
+ * Losses, activations and the bucket (module order, each parameter padded to 4 floats) are
+ * those of ppoaf_icm_update_args_t.  Weight rows of 2D and D + A_in floats are not 16-byte
+ * aligned in general: every layer with a run-time width reads its weights with bound-checked
+ * scalar loads; the ExE and MxM layers have compile-time widths.
+ *
+ * Only the split-wgrad form exists.  `fwd_bwd` enqueues three launches, none of which waits
+ * inside a kernel: encoder forward (2 ceil(B/16) workgroups: row tile x obs | next_obs),
+ * the two models (row tile x inverse | forward: forward, losses, backward; each model's
+ * share of d(enc) to a scratch of its own; ONE launch when inv_hidden == fwd_hidden, else one
+ * launch per model), encoder backward (adds the shares as inverse + forward).  `wgrad` is
+ * K14's weight-gradient launch over a block table of at most 14 blocks (per-network plane
+ * widths; the inverse layer 0 as an enc_1 and an enc_2 block, the forward layer 0 as an enc_1
+ * and an action block) [+ Adam with fused_adam], the loss into totals, cursor + 1.  Sums run
+ * in a fixed order, no float atomics: bitwise reproducible.
+ *   act_scratch   [2][3][Bpad][E] encoder hidden planes, then [2][Bpad][pad16(D)] encodings
+ *   denc_scratch  [2 models][2 streams][Bpad][pad16(D)]                 (Bpad = 16 ceil(B/16))
+ *   workspace     ppoaf_icm_shapes_workspace_bytes() bytes, 256-byte aligned (update only)
+ * `check` validates topology and bucket layout on the host and launches nothing.
+ * `intrinsic_reward`: as ppoaf_icm_intrinsic_reward (perm NULL, fused_adam 0; params, topology
+ * and act_scratch only), two launches: the encoder, then the forward model alone.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t obs_dim, enc_hidden, enc_dim, inv_hidden, fwd_hidden, action_dim, fwd_action_dim, depth_inv, depth_fwd;
+    int32_t activation, discrete, xcd_half;           /* xcd_half: as ppoaf_icm_update_args_t                */
+    int64_t enc_offset, inv_offset, fwd_offset, bucket_total;
+    const float* params; float* grads; float* exp_avg; float* exp_avg_sq;
+    int64_t* step_count; const float* lr;
+    float beta1, beta2, adam_eps, grad_scale;
+    const float* obs; const float* next_obs; const void* actions;
+    const int64_t* perm; const int32_t* row_map; int64_t n_rows;
+    int64_t* cursor; int64_t B, batch_stride;
+    float icm_beta; int32_t fused_adam;
+    float* act_scratch; float* denc_scratch;
+    float* loss_partials;            /* [ceil(B/16) + 1, 2] (last row: this step's Adam constants)*/
+    double* totals;                  /* [2]                                                     */
+    int32_t inputs_in_batch_order, _pad;
+    void* workspace; int64_t workspace_bytes;
+} ppoaf_icm_shapes_args_t;
+
+int ppoaf_icm_shapes_check(const ppoaf_icm_shapes_args_t* args);
+int ppoaf_icm_shapes_workspace_bytes(const ppoaf_icm_shapes_args_t* args, int64_t* bytes_out);
+int ppoaf_icm_shapes_fwd_bwd(const ppoaf_icm_shapes_args_t* args, ppoaf_stream_t stream);
+int ppoaf_icm_shapes_wgrad(const ppoaf_icm_shapes_args_t* args, ppoaf_stream_t stream);
+int ppoaf_icm_shapes_intrinsic_reward(const ppoaf_icm_shapes_args_t* args, float scale, float* intr_out,
+                                      ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * K15  fused multi-agent-transformer mini-batch update
  * replaces one iteration of PPO._ppo_batch_train for a MATPolicy  ppo.py:2292-2469
  *          MATPolicy.evaluate (token block, teacher forcing)      policies/mat_policy.py:378-439,628-658

@@ -151,6 +151,27 @@ class IcmUpdateArgs(C.Structure):
                 ("xcd_half", C.c_int32), ("fuse_kernels", C.c_int32)]
 
 
+class IcmShapesArgs(C.Structure):
+    """ppoaf_icm_shapes_args_t (include/ppoaf_hip.h) -- field order must match the header; 280 bytes, as
+    csrc/icm_update_shapes.hip asserts."""
+    _fields_ = [("obs_dim", C.c_int32), ("enc_hidden", C.c_int32), ("enc_dim", C.c_int32), ("inv_hidden", C.c_int32),
+                ("fwd_hidden", C.c_int32), ("action_dim", C.c_int32), ("fwd_action_dim", C.c_int32),
+                ("depth_inv", C.c_int32), ("depth_fwd", C.c_int32),
+                ("activation", C.c_int32), ("discrete", C.c_int32), ("xcd_half", C.c_int32),
+                ("enc_offset", C.c_int64), ("inv_offset", C.c_int64), ("fwd_offset", C.c_int64),
+                ("bucket_total", C.c_int64),
+                ("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("step_count", C.c_void_p), ("lr", C.c_void_p),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("grad_scale", C.c_float),
+                ("obs", C.c_void_p), ("next_obs", C.c_void_p), ("actions", C.c_void_p),
+                ("perm", C.c_void_p), ("row_map", C.c_void_p), ("n_rows", C.c_int64),
+                ("cursor", C.c_void_p), ("B", C.c_int64), ("batch_stride", C.c_int64),
+                ("icm_beta", C.c_float), ("fused_adam", C.c_int32),
+                ("act_scratch", C.c_void_p), ("denc_scratch", C.c_void_p), ("loss_partials", C.c_void_p),
+                ("totals", C.c_void_p), ("inputs_in_batch_order", C.c_int32), ("_pad", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class MatUpdateArgs(C.Structure):
     """ppoaf_mat_update_args_t (include/ppoaf_hip.h) -- field order must match the header."""
     _fields_ = [("obs_dim", C.c_int32), ("num_agents", C.c_int32), ("num_actions", C.c_int32), ("embedding", C.c_int32),
@@ -281,6 +302,11 @@ SIGNATURES = {
     "ppoaf_icm_update_split_workspace_bytes": (C.c_int, [C.POINTER(IcmUpdateArgs), C.POINTER(C.c_int64)]),
     "ppoaf_icm_update_fuses_kernels": (C.c_int, [C.POINTER(IcmUpdateArgs)]),
     "ppoaf_icm_intrinsic_reward": (C.c_int, [C.POINTER(IcmUpdateArgs), C.c_float, _ptr, _ptr]),
+    "ppoaf_icm_shapes_check": (C.c_int, [C.POINTER(IcmShapesArgs)]),
+    "ppoaf_icm_shapes_workspace_bytes": (C.c_int, [C.POINTER(IcmShapesArgs), C.POINTER(C.c_int64)]),
+    "ppoaf_icm_shapes_fwd_bwd": (C.c_int, [C.POINTER(IcmShapesArgs), _ptr]),
+    "ppoaf_icm_shapes_wgrad": (C.c_int, [C.POINTER(IcmShapesArgs), _ptr]),
+    "ppoaf_icm_shapes_intrinsic_reward": (C.c_int, [C.POINTER(IcmShapesArgs), C.c_float, _ptr, _ptr]),
     "ppoaf_adam_step_prenormed": (C.c_int, [_ptr, _ptr, _ptr, _ptr, C.c_int64, _ptr, _ptr, C.c_float, C.c_float,
                                             C.c_float, C.c_float, C.c_float, _ptr, C.c_int32, _ptr, _ptr]),
     "ppoaf_mat_update_fwd_bwd": (C.c_int, [C.POINTER(MatUpdateArgs), _ptr]),

@@ -13,48 +13,13 @@
 // and each phase runs on 2 * B/16 workgroups: (obs, next_obs) for the encoder phases,
 // (inverse, forward model) for the heads.  float32 MFMA (v_mfma_f32_16x16x4_f32) keeps fmaf
 // chains exact, weight gradients are written to private slabs and summed in a fixed order.
+#include "icm_update_dev.hpp"
 #include "ppo_update_rowpair.hpp"
 #include "wgrad_tile.hpp"
 #include <algorithm>
 #include <cstdlib>
 
 namespace ppoaf {
-
-struct IcmDev {
-    int O, H, A, Ain, d_inv, d_fwd, act, discrete;
-    long enc_off, inv_off, fwd_off, enc_size, total;
-    const float* params; float* grads; float* exp_avg; float* exp_avg_sq; float* slabs;
-    int64_t* step_count; const float* lr;
-    float beta1, beta2, adam_eps, grad_scale;
-    const float* obs; const float* next_obs; const void* actions;
-    const int64_t* perm; const int32_t* row_map; long n_rows;
-    int64_t* cursor; long B, batch_stride, Bpad;
-    float icm_beta; int fused_adam, pregathered;
-    float* actE; float* dEnc; float* loss_partials; double* totals;
-    int nT, confine;
-    // split-wgrad chain (args->split_workspace): the three fwd_bwd kernels form NO weight gradient; they publish every
-    // layer's dLoss/dz (and the inputs that are not in scratch already) as [rows][width] panels and the reduce launch
-    // becomes icm_wgrad_kernel.  Panels (plane = Bpad * H floats):
-    int split;
-    float* xO;      // [2][Bpad][XO]   gathered observation rows of the two streams, zero padded to XO = 16 ceil(O / 16)
-    float* dE;      // [2][4][plane]   encoder dz, stream-major
-    float* hI;      // [d_inv][plane]  inverse model hidden activations     dI: [d_inv][plane] its dz
-    float* dI;
-    float* oI;      // [Bpad][16]      d(inverse model output), zero padded
-    float* hF;      // [d_fwd][plane]  forward model hidden activations     dF: [d_fwd + 1][plane] its dz (last: the output layer)
-    float* dF;
-    float* aF;      // [Bpad][16]      the forward model's action columns (one-hot / action values), zero padded
-    int XO;
-};
-
-// one [n_o x n_i] block of some weight matrix = D^T X over all rows (and both observation streams for the encoder)
-struct IcmBlk {
-    const float* D; const float* X;     // [rows][ldd] / [rows][ldx] panels; segment s adds s * seg_d / s * seg_x floats
-    long seg_d, seg_x, w, b;            // w: bucket offset of the block's first weight; b: of its bias (-1: none from this block)
-    int n_seg, ldd, ldx, n_o, n_i, ldw, job0, n_ip;
-};
-constexpr int kIcmMaxBlk = 16;
-struct IcmWg { IcmBlk blk[kIcmMaxBlk]; int n_blk, n_jobs; int xcd_job0[9]; };   // XCD x works on jobs [xcd_job0[x], xcd_job0[x + 1])
 
 // 16 rows x H floats of LDS (row stride HS) -> rows [16 g, +16) of a [Bpad][H] panel
 template <int H>
@@ -67,33 +32,6 @@ __device__ __forceinline__ void icm_publish(const float* __restrict__ src, int H
 }
 
 extern __shared__ __attribute__((aligned(16))) unsigned char icm_smem[];
-
-// args->xcd_half = 1 / 2: the fwd_bwd kernels' workgroups on XCDs 0-3 / 4-7 only (workgroup b is dispatched to XCD b % 8;
-// the launch is twice as wide, the other half's workgroups return at once) -> the block index the kernel works on, or -1
-__device__ __forceinline__ int icm_block(const IcmDev& u) {
-    const int b = blockIdx.x;
-    if (!u.confine) return b;
-    const int x = b & 7;
-    return (x >> 2) != u.confine - 1 ? -1 : ((b >> 3) << 2) | (x & 3);
-}
-
-__device__ __forceinline__ void icm_rows(const IcmDev& u, int g, int tid, int* sRow) {
-    if (tid < kRows) {
-        const long s = (long)g * kRows + tid;
-        int row = -1;
-        if (s < u.B) {
-            if (u.pregathered) {
-                row = (int)(u.cursor[0] * u.batch_stride + s);   // tables in shuffled order: no index chain
-            } else if (u.perm) {
-                const long p = u.perm[u.cursor[0] * u.batch_stride + s];
-                if (p >= 0 && p < u.n_rows) row = u.row_map ? u.row_map[p] : (int)p;
-            } else {
-                row = (int)s;                         // rollout-time reward: the batch is the env batch itself
-            }
-        }
-        sRow[tid] = row;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // encoder forward: blockIdx.x = 2 * g + which (0: obs, 1: next_obs)
@@ -962,6 +900,38 @@ __global__ __launch_bounds__(256) void icm_wgrad_kernel(IcmDev u, IcmWg w, int p
 }
 
 static int jobs_of(const IcmBlk* blk, int i, int n, int jobs) { return (i + 1 < n ? blk[i + 1].job0 : jobs) - blk[i].job0; }
+void icm_add_block(IcmWg* w, const float* D, int ldd, long seg_d, const float* X, int ldx, long seg_x, int n_seg, int n_o, int n_i,
+                   long wo, int ldw, long bo) {
+    IcmBlk& k = w->blk[w->n_blk++];
+    k.D = D; k.X = X; k.seg_d = seg_d; k.seg_x = seg_x; k.w = wo; k.b = bo;
+    k.n_seg = n_seg; k.ldd = ldd; k.ldx = ldx; k.n_o = n_o; k.n_i = n_i; k.ldw = ldw; k.job0 = w->n_jobs;
+    k.n_ip = (n_i + 31) / 32;
+    w->n_jobs += ((n_o + 15) / 16) * k.n_ip;
+}
+// deal the block-major job list to the 8 XCDs in runs of equal COST (a job's cost = its K: the encoder's jobs run over
+// both observation streams), so that no XCD is left with twice the work of the others
+void icm_deal_jobs(IcmWg* w) {
+    const int n = w->n_blk, jobs = w->n_jobs;
+    long total = 0;
+    for (int i = 0; i < n; ++i) total += (long)(jobs_of(w->blk, i, n, jobs)) * w->blk[i].n_seg;
+    long acc = 0;
+    int x = 0;
+    w->xcd_job0[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        const int nj = jobs_of(w->blk, i, n, jobs);
+        for (int j = 0; j < nj; ++j) {
+            while (x < 7 && acc * 8 >= total * (x + 1)) w->xcd_job0[++x] = w->blk[i].job0 + j;
+            acc += w->blk[i].n_seg;
+        }
+    }
+    while (x < 8) w->xcd_job0[++x] = jobs;
+}
+int icm_launch_wgrad(const IcmDev& u, const IcmWg& w, hipStream_t stream) {
+    int per_xcd = 1;
+    for (int x = 0; x < 8; ++x) per_xcd = std::max(per_xcd, w.xcd_job0[x + 1] - w.xcd_job0[x]);
+    hipLaunchKernelGGL(icm_wgrad_kernel, dim3((unsigned)(8 * per_xcd + 1)), dim3(256), 0, stream, u, w, per_xcd);
+    return check_launch("icm_update_reduce (wgrad)");
+}
 // panel layout of the split workspace and the block table of the wgrad launch -> bytes
 static size_t icm_split_layout(IcmDev& u, char* base, IcmWg* w) {
     const long H = u.H, plane = u.Bpad * H;
@@ -973,15 +943,9 @@ static size_t icm_split_layout(IcmDev& u, char* base, IcmWg* w) {
     u.hI = take((size_t)u.d_inv * plane); u.dI = take((size_t)u.d_inv * plane); u.oI = take((size_t)u.Bpad * 16);
     u.hF = take((size_t)u.d_fwd * plane); u.dF = take((size_t)(u.d_fwd + 1) * plane); u.aF = take((size_t)u.Bpad * 16);
     if (!w) return off;
-    int n = 0, jobs = 0;
+    w->n_blk = w->n_jobs = 0;
     auto add = [&](const float* D, int ldd, long seg_d, const float* X, int ldx, long seg_x, int n_seg, int n_o, int n_i,
-                   long wo, int ldw, long bo) {
-        IcmBlk& k = w->blk[n++];
-        k.D = D; k.X = X; k.seg_d = seg_d; k.seg_x = seg_x; k.w = wo; k.b = bo;
-        k.n_seg = n_seg; k.ldd = ldd; k.ldx = ldx; k.n_o = n_o; k.n_i = n_i; k.ldw = ldw; k.job0 = jobs;
-        k.n_ip = (n_i + 31) / 32;
-        jobs += ((n_o + 15) / 16) * k.n_ip;
-    };
+                   long wo, int ldw, long bo) { icm_add_block(w, D, ldd, seg_d, X, ldx, seg_x, n_seg, n_o, n_i, wo, ldw, bo); };
     const int Hi = (int)H;
     // encoder (both observation streams: two segments): layer 0 from the gathered rows, layers 1..3 from the scratch
     long e = u.enc_off;
@@ -1011,22 +975,7 @@ static size_t icm_split_layout(IcmDev& u, char* base, IcmWg* w) {
         add(u.dF + l * plane, Hi, 0, u.hF + (l - 1) * plane, Hi, 0, 1, Hi, Hi, f, Hi, f + H * H);
         f += H * H + H;
     }
-    w->n_blk = n; w->n_jobs = jobs;
-    // deal the block-major job list to the 8 XCDs in runs of equal COST (a job's cost = its K: the encoder's jobs run over
-    // both observation streams), so that no XCD is left with twice the work of the others
-    long total = 0;
-    for (int i = 0; i < n; ++i) total += (long)(jobs_of(w->blk, i, n, jobs)) * w->blk[i].n_seg;
-    long acc = 0;
-    int x = 0;
-    w->xcd_job0[0] = 0;
-    for (int i = 0; i < n; ++i) {
-        const int nj = jobs_of(w->blk, i, n, jobs);
-        for (int j = 0; j < nj; ++j) {
-            while (x < 7 && acc * 8 >= total * (x + 1)) w->xcd_job0[++x] = w->blk[i].job0 + j;
-            acc += w->blk[i].n_seg;
-        }
-    }
-    while (x < 8) w->xcd_job0[++x] = jobs;
+    icm_deal_jobs(w);
     return off;
 }
 
@@ -1099,8 +1048,7 @@ static int make_icm(const ppoaf_icm_update_args_t* a, IcmDev& u, bool training =
     return PPOAF_OK;
 }
 
-// gfx950 has 160 KB of LDS per CU; launches above the 64 KB default need the attribute set once per kernel
-static int allow_large_lds(const void* kernel, size_t bytes, bool& done, const char* what) {
+int allow_large_lds(const void* kernel, size_t bytes, bool& done, const char* what) {
     if (bytes <= 64 * 1024 || done) return PPOAF_OK;
     hipFuncAttributes fa;
     hipError_t e = hipFuncGetAttributes(&fa, kernel);          // static __shared__ counts against the same 160 KB
@@ -1187,10 +1135,7 @@ extern "C" int ppoaf_icm_update_reduce(const ppoaf_icm_update_args_t* args, ppoa
     if (u.split) {
         IcmWg w;
         icm_split_layout(u, icm_panels_base(args), &w);
-        int per_xcd = 1;
-        for (int x = 0; x < 8; ++x) per_xcd = std::max(per_xcd, w.xcd_job0[x + 1] - w.xcd_job0[x]);
-        hipLaunchKernelGGL(icm_wgrad_kernel, dim3((unsigned)(8 * per_xcd + 1)), dim3(256), 0, (hipStream_t)stream, u, w, per_xcd);
-        return check_launch("icm_update_reduce (wgrad)");
+        return icm_launch_wgrad(u, w, (hipStream_t)stream);
     }
     const long n4 = u.total >> 2;
     hipLaunchKernelGGL(icm_reduce_kernel, dim3((unsigned)((n4 + kIcmRedThreads - 1) / kIcmRedThreads) + 1u),

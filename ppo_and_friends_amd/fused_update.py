@@ -1,6 +1,6 @@
 """
 Host drivers of the fused mini-batch update kernels: K12 (MLP policies, csrc/ppo_update.hip), K14 (ICM,
-csrc/icm_update.hip) and K15 (MAT policies, csrc/mat_update.hip).  All three run one epoch protocol (FusedEpoch):
+csrc/icm_update.hip, csrc/icm_update_shapes.hip) and K15 (MAT policies, csrc/mat_update.hip).  All three run one epoch protocol (FusedEpoch):
   begin_epoch : the epoch's inputs gathered in shuffled order (one launch), the driver's own records (value-normaliser
                 records of every mini-batch: one launch, one all-gather across ranks), cursor / totals reset
   run_epoch   : per mini-batch  fwd_bwd -> reduce -> [all-reduce] -> adam;
@@ -850,6 +850,108 @@ class FusedPolicyUpdate(FusedEpoch):
 # K14: fused ICM update
 # ======================================================================================
 def _describe_icm(icm, action_dtype):
+    """
+    Topology fields of an ICM living in one flat bucket, or (None, reason): IcmUpdateArgs' for the one-width topology
+    (csrc/icm_update.hip), else IcmShapesArgs' plus `general=True` for an ICM whose encoder, encoding and models have
+    widths of their own (csrc/icm_update_shapes.hip).
+    """
+    topo, _ = _describe_icm_one_width(icm, action_dtype)
+    if topo is not None:
+        return topo, ""
+    return _describe_icm_shapes(icm, action_dtype)
+
+
+def _icm_bucket_marks(icm, groups):
+    """Bucket offsets of the layer groups when the bucket is the groups' parameters in order, each padded to 4 floats:
+    (marks, total), or (None, reason)."""
+    base = icm.flat_params.data_ptr()
+    off, marks = 0, []
+    for group in groups:
+        marks.append(off)
+        for m in group:
+            for p in (m.weight, m.bias):
+                if (p.data_ptr() - base) // 4 != off:
+                    return None, "parameter layout differs from the kernel's layer table"
+                off += (p.numel() + 3) // 4 * 4
+    if off != icm.flat_params.numel():
+        return None, "the ICM holds parameters the fused kernel does not know about"
+    return marks, off
+
+
+def _describe_icm_shapes(icm, action_dtype):
+    """IcmShapesArgs topology fields (+ general=True) of an ICM, or (None, reason).  Covered: encoder O -> E -> E -> E -> D,
+    inverse 2D -> Mi (x 1..3) -> A, forward D + Ain -> Mf (x 1..3) -> D; E, Mi, Mf in (32, 64, 128), 1 <= D <= 128."""
+    from .networks.icm import ICM, LinearObservationEncoder
+    if not isinstance(icm, ICM):
+        return None, "not an ICM"
+    if not isinstance(icm.obs_encoder, LinearObservationEncoder):
+        return None, ("the identity encoder (encoded_obs_dim = 0) is not covered: the fused kernels need a "
+                      "LinearObservationEncoder")
+    if action_dtype == "multi-discrete":
+        return None, "multi-discrete actions are not covered by the fused ICM update"
+    if action_dtype not in ("discrete", "continuous"):
+        return None, "unsupported action space for the fused ICM update"
+    enc = [icm.obs_encoder.enc_1, icm.obs_encoder.enc_2, icm.obs_encoder.enc_3, icm.obs_encoder.enc_4]
+    inv = [m for m in icm.inv_model.sequential_net.modules() if isinstance(m, nn.Linear)]
+    fwd = [m for m in icm.forward_model.sequential_net.modules() if isinstance(m, nn.Linear)]
+    widths = (32, 64, 128)
+    E, O, D = enc[0].out_features, enc[0].in_features, enc[3].out_features
+    if E not in widths:
+        return None, f"encoder width {E} is not an instantiated width {widths}"
+    if [(m.in_features, m.out_features) for m in enc] != [(O, E), (E, E), (E, E), (E, D)]:
+        return None, "encoder layers must be O -> E -> E -> E -> D"
+    if not 1 <= D <= 128:
+        return None, f"encoded dim {D} must be in [1, 128]"
+    if not 1 <= O <= 1024:
+        return None, f"observation size {O} must be in [1, 1024]"
+    if len(inv) < 2 or len(fwd) < 2 or len(inv) > 4 or len(fwd) > 4:
+        return None, "inverse / forward model need 1..3 hidden layers"
+    Mi, Mf = inv[0].out_features, fwd[0].out_features
+    if Mi not in widths or Mf not in widths:
+        return None, f"inverse / forward model widths ({Mi}, {Mf}) are not instantiated widths {widths}"
+    A, Ain = inv[-1].out_features, fwd[0].in_features - D
+    want_inv = [(2 * D, Mi)] + [(Mi, Mi)] * (len(inv) - 2) + [(Mi, A)]
+    want_fwd = [(D + Ain, Mf)] + [(Mf, Mf)] * (len(fwd) - 2) + [(Mf, D)]
+    if [(m.in_features, m.out_features) for m in inv] != want_inv or \
+            [(m.in_features, m.out_features) for m in fwd] != want_fwd:
+        return None, "inverse / forward model layers do not follow 2D -> Mi .. -> A / D + Ain -> Mf .. -> D"
+    if not (1 <= A <= 8 and 1 <= Ain <= 8):
+        return None, f"action widths ({A}, {Ain}) must be in [1, 8]"
+    if action_dtype == "discrete" and Ain != A:
+        return None, "unsupported action space for the fused ICM update"
+    acts = {_activation_code(a) for a in (icm.activation, icm.obs_encoder.activation, icm.inv_model.activation,
+                                           icm.forward_model.activation)}
+    if len(acts) != 1 or None in acts:
+        return None, "activation is not one shared ReLU / LeakyReLU(0.01) / Tanh"
+    if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
+        return None, "PPOAF_SPLIT_WGRAD=0: the chain for these ICM shapes has no slab form"
+    marks, total = _icm_bucket_marks(icm, (enc, inv, fwd))
+    if marks is None:
+        return None, total
+    return dict(general=True, obs_dim=O, enc_hidden=E, enc_dim=D, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A, fwd_action_dim=Ain,
+                depth_inv=len(inv) - 1, depth_fwd=len(fwd) - 1, activation=acts.pop(), discrete=int(action_dtype == "discrete"),
+                enc_offset=marks[0], inv_offset=marks[1], fwd_offset=marks[2], bucket_total=total), ""
+
+
+def icm_scratch_floats(topo, rows):
+    """(act_scratch, denc_scratch) floats of either K14 chain for `rows` rows (include/ppoaf_hip.h)."""
+    bpad = (rows + 15) // 16 * 16
+    if topo.get("general"):
+        dp = (topo["enc_dim"] + 15) // 16 * 16
+        return 2 * bpad * (3 * topo["enc_hidden"] + dp), 4 * bpad * dp
+    return 8 * bpad * topo["hidden"], 4 * bpad * topo["hidden"]
+
+
+def icm_topology_args(topo):
+    """The args struct of the chain `topo` selects, topology fields set."""
+    a = _lib.IcmShapesArgs() if topo.get("general") else _lib.IcmUpdateArgs()
+    for k, v in topo.items():
+        if k != "general":
+            setattr(a, k, v)
+    return a
+
+
+def _describe_icm_one_width(icm, action_dtype):
     """IcmUpdateArgs topology fields of an ICM living in one flat bucket, or (None, reason)."""
     from .networks.icm import ICM, LinearObservationEncoder
     if not isinstance(icm, ICM) or not isinstance(icm.obs_encoder, LinearObservationEncoder):
@@ -878,17 +980,9 @@ def _describe_icm(icm, action_dtype):
                                            icm.forward_model.activation)}
     if len(acts) != 1 or None in acts:
         return None, "activation is not one shared ReLU / LeakyReLU(0.01) / Tanh"
-    base = icm.flat_params.data_ptr()
-    off, marks = 0, []
-    for group in (enc, inv, fwd):
-        marks.append(off)
-        for m in group:
-            for p in (m.weight, m.bias):
-                if (p.data_ptr() - base) // 4 != off:
-                    return None, "parameter layout differs from the kernel's layer table"
-                off += (p.numel() + 3) // 4 * 4
-    if off != icm.flat_params.numel():
-        return None, "the ICM holds parameters the fused kernel does not know about"
+    marks, off = _icm_bucket_marks(icm, (enc, inv, fwd))
+    if marks is None:
+        return None, off
     return dict(obs_dim=O, hidden=H, action_dim=A, fwd_action_dim=Ain, depth_inv=len(inv) - 1,
                 depth_fwd=len(fwd) - 1, activation=acts.pop(), discrete=int(action_dtype == "discrete"),
                 enc_offset=marks[0], inv_offset=marks[1], fwd_offset=marks[2], bucket_total=off), ""
@@ -899,7 +993,8 @@ class FusedIcmUpdate(FusedEpoch):
     Host driver of K14 (csrc/icm_update.hip): one epoch of PPO._icm_batch_train (ppo.py:2487-2567).
     Per mini-batch: fwd_bwd (3 launches) -> reduce [+ Adam]; with more ranks reduce -> all-reduce ->
     K11 Adam.  On a single rank `graph_chunk` mini-batches are captured into a hipGraph and replayed
-    (all launches read the device cursor).
+    (all launches read the device cursor).  An ICM with widths of its own (`topo["general"]`) runs the same protocol on
+    csrc/icm_update_shapes.hip: ppoaf_icm_shapes_fwd_bwd -> ppoaf_icm_shapes_wgrad, split-wgrad form only.
     """
 
     n_totals = 2
@@ -919,11 +1014,13 @@ class FusedIcmUpdate(FusedEpoch):
         pol = self.pol
         dev = pol.device
         self.topo, _ = _describe_icm(pol.icm_model, pol.action_dtype)
+        self.general = bool(self.topo.get("general"))      # csrc/icm_update_shapes.hip: split-wgrad form only, no in-kernel waits
         nT = (self.B + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
-        H, total = self.topo["hidden"], self.topo["bucket_total"]
-        self.slabs = torch.zeros(2 * nT, total, dtype=torch.float32, device=dev)
-        self.act_scratch = torch.zeros(2, 4, 16 * nT, H, dtype=torch.float32, device=dev)
-        self.denc_scratch = torch.zeros(2, 2, 16 * nT, H, dtype=torch.float32, device=dev)
+        total = self.topo["bucket_total"]
+        self.slabs = None if self.general else torch.zeros(2 * nT, total, dtype=torch.float32, device=dev)
+        n_act, n_denc = icm_scratch_floats(self.topo, self.B)
+        self.act_scratch = torch.zeros(n_act, dtype=torch.float32, device=dev)
+        self.denc_scratch = torch.zeros(n_denc, dtype=torch.float32, device=dev)
         self.loss_partials = torch.zeros(nT + 1, 2, dtype=torch.float32, device=dev)    # + the step's Adam constants
         self._open_exchange(pol.icm_model.flat_grads.numel())
         # split-wgrad chain (csrc/icm_update.hip: icm_wgrad_kernel): PPOAF_SPLIT_WGRAD = auto (= 1) | 1 | 0.  The reduce entry
@@ -937,13 +1034,12 @@ class FusedIcmUpdate(FusedEpoch):
 
     def _make_args(self, B):
         pol, buf, opt = self.pol, self.pol.buffer, self.pol.icm_optim
-        a = _lib.IcmUpdateArgs()
-        for k, v in self.topo.items():
-            setattr(a, k, v)
+        a = icm_topology_args(self.topo)
         icm = pol.icm_model
         a.params, a.grads = icm.flat_params.data_ptr(), icm.flat_grads.data_ptr()
         a.exp_avg, a.exp_avg_sq = opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr()
-        a.slabs = self.slabs.data_ptr()
+        if not self.general:
+            a.slabs = self.slabs.data_ptr()
         a.step_count, a.lr = opt.step_count.data_ptr(), opt.lr.data_ptr()
         a.beta1, a.beta2, a.adam_eps = opt.betas[0], opt.betas[1], opt.eps
         a.grad_scale = 1.0 / self.world
@@ -957,6 +1053,13 @@ class FusedIcmUpdate(FusedEpoch):
         a.act_scratch, a.denc_scratch = self.act_scratch.data_ptr(), self.denc_scratch.data_ptr()
         a.loss_partials, a.totals = self.loss_partials.data_ptr(), self.totals.data_ptr()
         a.xcd_half = getattr(self, "xcd_half", 0)
+        if self.general:
+            if self._split_space is None:                # sized once, for the full batch size (a tail mini-batch needs less)
+                need = C.c_int64(0)
+                _lib.check(self._lib.ppoaf_icm_shapes_workspace_bytes(C.byref(a), C.byref(need)), "icm_shapes_workspace_bytes")
+                self._split_space = torch.zeros(int(need.value), dtype=torch.uint8, device=pol.device)
+            a.workspace, a.workspace_bytes = self._split_space.data_ptr(), self._split_space.numel()
+            return a
         a.split_workspace, a.split_workspace_bytes = None, 0
         a.fuse_kernels = 0
         if self.split:
@@ -983,6 +1086,8 @@ class FusedIcmUpdate(FusedEpoch):
 
     def fuse_reason(self):
         """'' when a mini-batch's encoder / model / encoder-backward kernels run as one launch, else why not."""
+        if self.general:
+            return "the chain for ICMs with widths of their own has no single-launch form (and no bounded waits)"
         if not self.fuse_kernels:
             return "off (fuse_kernels = False)"
         if getattr(self, "_fuse_disabled", ""):
@@ -1006,12 +1111,17 @@ class FusedIcmUpdate(FusedEpoch):
 
     def _one(self, args):
         lib, st, ref = self._lib, K.stream(), C.byref(args)
-        rc = lib.ppoaf_icm_update_fwd_bwd(ref, st)
-        if args.fuse_kernels and getattr(self, "_fuses", False):
-            self._fused_used = True
-            FusedIcmUpdate.fused_launches += 1
-        if rc == 0:
-            rc = lib.ppoaf_icm_update_reduce(ref, st)
+        if self.general:
+            rc = lib.ppoaf_icm_shapes_fwd_bwd(ref, st)
+            if rc == 0:
+                rc = lib.ppoaf_icm_shapes_wgrad(ref, st)
+        else:
+            rc = lib.ppoaf_icm_update_fwd_bwd(ref, st)
+            if args.fuse_kernels and getattr(self, "_fuses", False):
+                self._fused_used = True
+                FusedIcmUpdate.fused_launches += 1
+            if rc == 0:
+                rc = lib.ppoaf_icm_update_reduce(ref, st)
         if rc != 0:
             _lib.check(rc, "icm_update")
         if self.multi:
@@ -1021,6 +1131,10 @@ class FusedIcmUpdate(FusedEpoch):
             else:
                 mpi_utils.allreduce_sum_(g)
             self.pol.icm_optim.step(grad_scale=1.0 / self.world, max_norm=None)
+
+    def _c_loop(self, args, n):
+        # (the C-level RCCL loop is the one-width chain's: these shapes take _one's all-reduce branch)
+        return False if self.general else super()._c_loop(args, n)
 
     def _chain_allreduce(self, ref, comm, k, st):
         opt = self.pol.icm_optim

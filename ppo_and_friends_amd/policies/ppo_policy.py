@@ -95,6 +95,8 @@ class FlatAdam:
 
 class PPOPolicy:
 
+    fused_icm_reward_calls = 0         # intrinsic-reward calls answered by K14's two launches in this process (tests: the path ran)
+
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
                  actor_kw_args={}, critic_kw_args={}, icm_kw_args={}, target_kl=100.,
@@ -610,27 +612,26 @@ class PPOPolicy:
         st = getattr(self, "_icm_reward_state", None)
         n = obs_1.shape[0]
         if st is None or st["n"] != n:
-            from ..fused_update import _describe_icm
+            from ..fused_update import _describe_icm, icm_scratch_floats, icm_topology_args
             topo, why = _describe_icm(self.icm_model, self.action_dtype)
             if topo is None:
                 self.fused_icm_reward = False
                 return None
-            a = _lib.IcmUpdateArgs()
-            for k, v in topo.items():
-                setattr(a, k, v)
-            nT = (n + 15) // 16
-            scratch = torch.zeros(2, 4, 16 * nT, topo["hidden"], dtype=torch.float32, device=self.device)
+            a = icm_topology_args(topo)
+            scratch = torch.zeros(icm_scratch_floats(topo, n)[0], dtype=torch.float32, device=self.device)
             a.params = self.icm_model.flat_params.data_ptr()
             a.act_scratch = scratch.data_ptr()
             a.B, a.batch_stride, a.n_rows, a.fused_adam = n, n, n, 0
-            st = self._icm_reward_state = dict(n=n, args=a, scratch=scratch)
+            # an ICM with widths of its own (csrc/icm_update_shapes.hip) has entry points of its own
+            entry = "ppoaf_icm_shapes_intrinsic_reward" if topo.get("general") else "ppoaf_icm_intrinsic_reward"
+            st = self._icm_reward_state = dict(n=n, args=a, scratch=scratch, entry=entry)
         a = st["args"]
         obs_1, obs_2, act = obs_1.reshape(n, -1).contiguous(), obs_2.reshape(n, -1).contiguous(), act.contiguous()
         a.obs, a.next_obs, a.actions = obs_1.data_ptr(), obs_2.data_ptr(), act.data_ptr()
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         scale = float(self.intr_reward_weight()) * float(self.icm_model.reward_scale) / 2.0
-        _lib.check(_lib.load().ppoaf_icm_intrinsic_reward(C.byref(a), scale, out.data_ptr(), K.stream()),
-                   "icm_intrinsic_reward")
+        _lib.check(getattr(_lib.load(), st["entry"])(C.byref(a), scale, out.data_ptr(), K.stream()), st["entry"][6:])
+        PPOPolicy.fused_icm_reward_calls += 1
         return out
 
     def inference_unsupported_reason(self):

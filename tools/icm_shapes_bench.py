@@ -1,0 +1,114 @@
+"""
+One ICM epoch and the per-env-step intrinsic reward at the reference baselines' ICM shape -- encoder 17 -> 128^3 -> 9,
+inverse / forward model width 32, Box(6) actions, 4096 envs x 128 steps, mini-batches of 256 -- on K14's chain for ICMs with
+widths of their own (csrc/icm_update_shapes.hip, update_mode="fused") against update_mode="torch", which is what ran this
+shape before that chain existed.
+
+Both legs live in one process on the same rollout shape; after a warm-up pass of each they are ALTERNATED `--repeats`
+times and timed with device events: the epoch = PPO._icm_batch_train over 2048 mini-batches (shuffle draw included), the
+reward = PPOPolicy.get_intrinsic_reward on the 4096-row env batch (mean of `--reward-calls` back-to-back calls).  Prints the
+median and the spread (min .. max) of both, the launches per mini-batch of the fused chain, and one JSON line.
+
+    python tools/icm_shapes_bench.py [--envs 4096] [--steps 128] [--batch 256] [--repeats 5] [--reward-calls 50]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+DEV = torch.device("cuda", 0)
+O, NA = 17, 6
+ICM_KW = dict(encoded_obs_dim=9, encoder_hidden_size=128, inverse_hidden_size=32, forward_hidden_size=32)
+
+
+def make(mode, E, T, B):
+    from ppo_and_friends_amd.ppo import PPO
+    from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
+    from ppo_and_friends_amd.spaces import Box
+    space = Box(-1.0, 1.0, (NA,), np.float32)
+    env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, DEV, reward="uniform", seed=5, term_prob=0.05)
+    sp = Box(-np.inf, np.inf, (O,), np.float32)
+    ppo = PPO(env_gen, {"p": (None, sp, sp, space, dict(enable_icm=True, icm_kw_args=ICM_KW))}, device=DEV, random_seed=4,
+              normalize_obs=False, normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=B, epochs_per_iter=1,
+              update_mode=mode)
+    ppo.rollout()
+    return ppo
+
+
+def timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=128)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--reward-calls", type=int, default=50)
+    args = ap.parse_args()
+    from ppo_and_friends_amd.ppo import PermutationLoader
+    from ppo_and_friends_amd.fused_update import FusedIcmUpdate
+    from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
+    legs = {}
+    for mode in ("fused", "torch"):
+        ppo = make(mode, args.envs, args.steps, args.batch)
+        pol = ppo.policies["p"]
+        upd = ppo._fused_icm_updater("p")
+        if mode == "fused":
+            assert upd is not None and upd.topo.get("general"), FusedIcmUpdate.unsupported_reason(pol)
+        else:
+            assert upd is None
+        loader = PermutationLoader(pol.dataset, args.batch, ppo.loader_generator)
+        buf = pol.buffer
+        o1, o2, act = buf.observations[0], buf.next_observations[0], buf.actions[0]
+
+        def epoch(ppo=ppo, loader=loader):
+            ppo._icm_batch_train(loader, "p")
+
+        def reward(pol=pol, o1=o1, o2=o2, act=act, n=args.reward_calls):
+            for _ in range(n):
+                pol.get_intrinsic_reward(o1, o2, act)
+        legs[mode] = dict(epoch=epoch, reward=reward, ms=[], us=[])
+    n_mb = -(-args.envs * args.steps // args.batch)
+    for leg in legs.values():                                  # warm-up pass: graph capture, allocations, autotuning
+        leg["epoch"](); leg["reward"]()
+    calls = PPOPolicy.fused_icm_reward_calls
+    for _ in range(max(5, args.repeats)):
+        for mode in ("fused", "torch"):
+            leg = legs[mode]
+            leg["ms"].append(timed(leg["epoch"]))
+            leg["us"].append(1e3 * timed(leg["reward"]) / args.reward_calls)
+    assert PPOPolicy.fused_icm_reward_calls - calls == max(5, args.repeats) * args.reward_calls, "the fused leg's rewards took the torch path"
+    out = dict(shape=dict(O=O, actions=NA, envs=args.envs, steps=args.steps, batch=args.batch, minibatches=n_mb, **ICM_KW),
+               fused_launches_per_minibatch=4 if ICM_KW["inverse_hidden_size"] == ICM_KW["forward_hidden_size"] else 5)
+    for mode, leg in legs.items():
+        ms, us = leg["ms"], leg["us"]
+        out[mode] = dict(epoch_ms_median=statistics.median(ms), epoch_ms_min=min(ms), epoch_ms_max=max(ms),
+                         us_per_minibatch=1e3 * statistics.median(ms) / n_mb,
+                         reward_us_median=statistics.median(us), reward_us_min=min(us), reward_us_max=max(us))
+        print(f"{mode:5s}: ICM epoch {statistics.median(ms):9.2f} ms ({min(ms):.2f} .. {max(ms):.2f}) = "
+              f"{1e3 * statistics.median(ms) / n_mb:7.2f} us per mini-batch; reward call {statistics.median(us):8.1f} us "
+              f"({min(us):.1f} .. {max(us):.1f})")
+    out["epoch_speedup"] = out["torch"]["epoch_ms_median"] / out["fused"]["epoch_ms_median"]
+    out["reward_speedup"] = out["torch"]["reward_us_median"] / out["fused"]["reward_us_median"]
+    print(f"fused chain: {out['fused_launches_per_minibatch']} launches per mini-batch; epoch x{out['epoch_speedup']:.2f}, "
+          f"reward x{out['reward_speedup']:.2f} against the torch path")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
