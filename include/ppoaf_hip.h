@@ -784,6 +784,17 @@ int ppoaf_icm_intrinsic_reward(const ppoaf_icm_update_args_t* args, float scale,
  * `check` validates topology and bucket layout on the host and launches nothing.
  * `intrinsic_reward`: as ppoaf_icm_intrinsic_reward (perm NULL, fused_adam 0; params, topology
  * and act_scratch only), two launches: the encoder, then the forward model alone.
+ *
+ * Identity encoder (ICM(encoded_obs_dim = 0): obs_encoder = nn.Identity(), icm.py:227-430):
+ * enc_hidden == 0 with enc_dim == obs_dim (1 <= O <= 128) and enc_offset == inv_offset (an
+ * encoder of size 0; the bucket is the inverse model's parameters, then the forward model's).
+ * The encodings are the observation rows: no encoder launch, and no d(enc) -- observations
+ * take no gradient.  `fwd_bwd` is the models launch alone (one per model when the widths
+ * differ), whose tiles are loaded straight from obs / next_obs (dead rows and columns
+ * O .. pad16(O) as zeros); the inverse model's workgroups publish them as the layer-0 panels
+ * of `wgrad`, whose table has at most 10 blocks.  `intrinsic_reward` is one launch.
+ *   act_scratch   [2][Bpad][pad16(O)]       denc_scratch  unused, may be NULL
+ * `check` refuses enc_hidden == 0 with enc_dim != obs_dim or obs_dim > 128.
  * ------------------------------------------------------------------------ */
 typedef struct {
     int32_t obs_dim, enc_hidden, enc_dim, inv_hidden, fwd_hidden, action_dim, fwd_action_dim, depth_inv, depth_fwd;

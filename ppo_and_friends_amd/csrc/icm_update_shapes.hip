@@ -10,6 +10,9 @@
 // has run-time sizes and reads its weights with bound-checked scalar loads (rows of 18 or 12 floats at the baseline
 // shapes are not 16-byte aligned), as the encoder's layer 0 (K = O) always has.  Columns D .. pad16(D) of every
 // D-wide panel are written as zeros.
+// Identity encoder (enc_hidden = 0, D = O <= 128): the encodings ARE the observation rows.  No encoder kernel runs; the
+// models kernel and the reward kernel fill their two encoding tiles from the observation tables (sh_load_obs), the
+// inverse model's workgroup publishes them as the layer-0 panels of the wgrad launch, and no d(enc) is formed.
 #include "icm_update_dev.hpp"
 #include "wgrad_tile.hpp"
 #include <cstddef>
@@ -19,6 +22,7 @@ namespace ppoaf {
 struct IcmSh {
     IcmDev d;                  // d.H = D (the forward loss's mean and the bookkeeping run over B x D); d.actE: hidden planes
     int E, D, DP, Mi, Mf;      // DP = pad16(D)
+    int ident;                 // identity encoder: E = 0, D = O; enc is filled by the models kernel, gI / gF / dEh / dEo unused
     float* enc;                // [2][Bpad][DP]     encodings of the two streams
     float* gI;                 // [2][Bpad][DP]     the inverse model's share of d(enc_1), d(enc_2)
     float* gF;                 // [2][Bpad][DP]     the forward model's
@@ -111,6 +115,16 @@ __device__ __forceinline__ void sh_fetch(const float* __restrict__ panel, int n,
     for (int i = tid; i < kRows * n4; i += kThreadsU) {
         const int r = i / n4, c4 = i - r * n4;
         *reinterpret_cast<float4*>(dst + r * ls + 4 * c4) = *reinterpret_cast<const float4*>(src + (long)r * n + 4 * c4);
+    }
+}
+// identity encoder: the tile's 16 observation rows (stride O floats: not 16-byte aligned in general, so one dword per
+// lane, consecutive lanes on consecutive columns) -> dst [16][ls]; dead rows and columns O .. DP are written as zeros
+__device__ __forceinline__ void sh_load_obs(const float* __restrict__ src, int O, int DP, const int* sRow, float* __restrict__ dst,
+                                            int ls, int tid) {
+    for (int idx = tid; idx < kRows * DP; idx += kThreadsU) {
+        const int s = idx / DP, i = idx - s * DP;
+        const int row = sRow[s];
+        dst[s * ls + i] = (row >= 0 && i < O) ? src[(long)row * O + i] : 0.f;
     }
 }
 
@@ -252,13 +266,30 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
     float* sDOut = sOut + kRows * kMaxOut;                    // [16, 16]
     __shared__ float red[17];
 
+    if (q.ident && vb == 0 && which == 0 && tid == 0 && u.fused_adam) {
+        // (no encoder launch ahead of this one: the Adam constants of icm_sh_encoder_fwd_kernel are computed here)
+        const int64_t t = u.step_count[0] + 1;
+        u.step_count[0] = t;
+        u.loss_partials[2 * u.nT] = (float)((double)u.lr[0] / (1.0 - pow((double)u.beta1, (double)t)));
+        u.loss_partials[2 * u.nT + 1] = (float)sqrt(1.0 - pow((double)u.beta2, (double)t));
+    }
     icm_rows(u, g, tid, sRow);
     for (int i = tid; i < kRows * kShXS; i += kThreadsU) sXa[i] = 0.f;
-    sh_fetch(q.enc, DP, g, sE1, DS, tid);
-    sh_fetch(q.enc + u.Bpad * DP, DP, g, sE2, DS, tid);
+    if (q.ident) {
+        __syncthreads();
+        sh_load_obs(u.obs, u.O, DP, sRow, sE1, DS, tid);
+        sh_load_obs(u.next_obs, u.O, DP, sRow, sE2, DS, tid);
+    } else {
+        sh_fetch(q.enc, DP, g, sE1, DS, tid);
+        sh_fetch(q.enc + u.Bpad * DP, DP, g, sE2, DS, tid);
+    }
     __syncthreads();
     sh_actions(u, sRow, sAct, sXa, tid);
     __syncthreads();
+    if (q.ident && which == 0) {        // the layer-0 inputs of the wgrad launch
+        sh_publish(sE1, DS, q.enc, DP, g, tid);
+        sh_publish(sE2, DS, q.enc + u.Bpad * DP, DP, g, tid);
+    }
 
     if (which == 0) {
         // =================================== inverse model ===================================
@@ -391,6 +422,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         }
         // layer 0: two K halves; the shares of the encodings' gradients leave through scratch
         sh_publish(Dc, MS, u.dI, M, g, tid);
+        if (q.ident) return;            // observations take no gradient
         sh_layer_dgrad(P, ld0, M, D, Dc, MS, nullptr, 0, act, nullptr, q.gI + (long)g * kRows * DP, DP, wave, lane);
         sh_layer_dgrad(P + D, ld0, M, D, Dc, MS, nullptr, 0, act, nullptr, q.gI + (u.Bpad + (long)g * kRows) * DP, DP, wave, lane);
     } else {
@@ -408,7 +440,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         {
             const float sc = (1.0f - u.icm_beta) / ((float)B * (float)D);
             float part = 0.f;
-            float* dE2 = q.gF + (u.Bpad + (long)g * kRows) * DP;
+            float* dE2 = q.ident ? nullptr : q.gF + (u.Bpad + (long)g * kRows) * DP;
             for (int idx = tid; idx < kRows * DP; idx += kThreadsU) {
                 const int s = idx / DP, i = idx - s * DP;
                 float dv = 0.f;
@@ -418,7 +450,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
                     dv = sc * diff;
                 }
                 sP[s * DS + i] = dv;
-                dE2[(long)s * DP + i] = -dv;
+                if (dE2) dE2[(long)s * DP + i] = -dv;
             }
             part = block_sum(part, red);
             if (tid == 0) u.loss_partials[g * 2 + 1] = 0.5f * part;
@@ -438,12 +470,14 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
             float* t = Dc; Dc = Dn; Dn = t;
         }
         sh_publish(Dc, MS, u.dF, M, g, tid);
+        if (q.ident) return;
         sh_layer_dgrad(P, ld0, M, D, Dc, MS, nullptr, 0, act, nullptr, q.gF + (long)g * kRows * DP, DP, wave, lane);
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// rollout-time intrinsic reward: the forward model alone on the encodings icm_sh_encoder_fwd_kernel left;
+// rollout-time intrinsic reward: the forward model alone on the encodings icm_sh_encoder_fwd_kernel left (identity
+// encoder: on the observation rows themselves, the only launch of the call);
 // intr[row] = scale * sum_d (pred - enc_2)^2.  One workgroup per 16 rows.
 // ------------------------------------------------------------------------------------------------
 template <int MT>
@@ -463,8 +497,14 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_reward_kernel(IcmSh q, float
     float* sH = sP + kRows * DS;                              // d_fwd x [16, MS]
     icm_rows(u, g, tid, sRow);
     for (int i = tid; i < kRows * kShXS; i += kThreadsU) sXa[i] = 0.f;
-    sh_fetch(q.enc, DP, g, sE1, DS, tid);
-    sh_fetch(q.enc + u.Bpad * DP, DP, g, sE2, DS, tid);
+    if (q.ident) {
+        __syncthreads();
+        sh_load_obs(u.obs, u.O, DP, sRow, sE1, DS, tid);
+        sh_load_obs(u.next_obs, u.O, DP, sRow, sE2, DS, tid);
+    } else {
+        sh_fetch(q.enc, DP, g, sE1, DS, tid);
+        sh_fetch(q.enc + u.Bpad * DP, DP, g, sE2, DS, tid);
+    }
     __syncthreads();
     sh_actions(u, sRow, sAct, sXa, tid);
     __syncthreads();
@@ -540,7 +580,14 @@ static bool sh_width(int w) { return w == 32 || w == 64 || w == 128; }
 // topology and bucket layout only: what ppoaf_icm_shapes_check answers without a device
 static int sh_check(const ppoaf_icm_shapes_args_t* a) {
     PPOAF_REQUIRE(a, "icm_shapes: null args");
-    PPOAF_REQUIRE(sh_width(a->enc_hidden), "icm_shapes: enc_hidden=%d is not an instantiated width (32, 64, 128)", a->enc_hidden);
+    const bool ident = a->enc_hidden == 0;          // identity encoder: the encoding is the observation
+    PPOAF_REQUIRE(ident || sh_width(a->enc_hidden), "icm_shapes: enc_hidden=%d is not an instantiated width (32, 64, 128)", a->enc_hidden);
+    if (ident) {
+        PPOAF_REQUIRE(a->enc_dim == a->obs_dim, "icm_shapes: enc_hidden=0 (identity encoder) needs enc_dim=%d to equal obs_dim=%d",
+                      a->enc_dim, a->obs_dim);
+        PPOAF_REQUIRE(a->obs_dim >= 1 && a->obs_dim <= 128, "icm_shapes: enc_hidden=0 (identity encoder): obs_dim=%d must be in [1,128]",
+                      a->obs_dim);
+    }
     PPOAF_REQUIRE(sh_width(a->inv_hidden) && sh_width(a->fwd_hidden),
                   "icm_shapes: inv_hidden=%d / fwd_hidden=%d are not instantiated widths (32, 64, 128)", a->inv_hidden, a->fwd_hidden);
     PPOAF_REQUIRE(a->enc_dim >= 1 && a->enc_dim <= 128, "icm_shapes: enc_dim=%d must be in [1,128]", a->enc_dim);
@@ -553,7 +600,7 @@ static int sh_check(const ppoaf_icm_shapes_args_t* a) {
     PPOAF_REQUIRE(a->xcd_half >= 0 && a->xcd_half <= 2, "icm_shapes: xcd_half=%d (0, 1 or 2)", a->xcd_half);
     const long E = a->enc_hidden, D = a->enc_dim, Mi = a->inv_hidden, Mf = a->fwd_hidden, O = a->obs_dim, A = a->action_dim,
                Ain = a->fwd_action_dim;
-    const long enc_size = E * O + E + 2 * (E * E + E) + D * E + pad4l(D);
+    const long enc_size = ident ? 0 : E * O + E + 2 * (E * E + E) + D * E + pad4l(D);
     const long inv_size = Mi * 2 * D + Mi + (long)(a->depth_inv - 1) * (Mi * Mi + Mi) + A * Mi + pad4l(A);
     const long fwd_size = Mf * (D + Ain) + Mf + (long)(a->depth_fwd - 1) * (Mf * Mf + Mf) + D * Mf + pad4l(D);
     PPOAF_REQUIRE(a->enc_offset >= 0 && a->enc_offset % 4 == 0 && a->inv_offset == a->enc_offset + enc_size &&
@@ -572,8 +619,10 @@ static size_t sh_layout(IcmSh& q, char* base, IcmWg* w) {
     size_t off = 0;
     auto take = [&](size_t floats) { float* p = reinterpret_cast<float*>(base + off); off += (floats * 4 + 255) & ~(size_t)255; return p; };
     u.XO = 16 * ((u.O + 15) / 16);
-    u.xO = take((size_t)2 * Bp * u.XO);
-    q.dEh = take((size_t)6 * planeE); q.dEo = take((size_t)2 * planeD);
+    if (!q.ident) {
+        u.xO = take((size_t)2 * Bp * u.XO);
+        q.dEh = take((size_t)6 * planeE); q.dEo = take((size_t)2 * planeD);
+    }
     u.hI = take((size_t)u.d_inv * planeI); u.dI = take((size_t)u.d_inv * planeI); u.oI = take((size_t)Bp * 16);
     u.hF = take((size_t)u.d_fwd * planeF); u.dF = take((size_t)u.d_fwd * planeF); q.dFo = take((size_t)planeD);
     u.aF = take((size_t)Bp * 16);
@@ -582,14 +631,17 @@ static size_t sh_layout(IcmSh& q, char* base, IcmWg* w) {
     const int Ei = (int)E, Di = q.D, DPi = (int)DP, Mii = (int)Mi, Mfi = (int)Mf;
     const long D = q.D;
     // encoder (both observation streams: two segments): layer 0 from the gathered rows, 1..2 from the hidden planes, 3 -> D
-    long e = u.enc_off;
-    icm_add_block(w, q.dEh, Ei, 3 * planeE, u.xO, u.XO, Bp * u.XO, 2, Ei, u.O, e, u.O, e + E * u.O);
-    e += E * u.O + E;
-    for (int l = 1; l < 3; ++l) {
-        icm_add_block(w, q.dEh + l * planeE, Ei, 3 * planeE, u.actE + (l - 1) * planeE, Ei, 3 * planeE, 2, Ei, Ei, e, Ei, e + E * E);
-        e += E * E + E;
+    // (identity encoder: no encoder blocks, 10 blocks at most)
+    if (!q.ident) {
+        long e = u.enc_off;
+        icm_add_block(w, q.dEh, Ei, 3 * planeE, u.xO, u.XO, Bp * u.XO, 2, Ei, u.O, e, u.O, e + E * u.O);
+        e += E * u.O + E;
+        for (int l = 1; l < 3; ++l) {
+            icm_add_block(w, q.dEh + l * planeE, Ei, 3 * planeE, u.actE + (l - 1) * planeE, Ei, 3 * planeE, 2, Ei, Ei, e, Ei, e + E * E);
+            e += E * E + E;
+        }
+        icm_add_block(w, q.dEo, DPi, planeD, u.actE + 2 * planeE, Ei, 3 * planeE, 2, Di, Ei, e, Ei, e + D * E);
     }
-    icm_add_block(w, q.dEo, DPi, planeD, u.actE + 2 * planeE, Ei, 3 * planeE, 2, Di, Ei, e, Ei, e + D * E);
     // inverse model: layer 0 as an enc_1 and an enc_2 block (columns 0 and D of rows of 2D), hidden layers, output layer
     long p = u.inv_off;
     icm_add_block(w, u.dI, Mii, 0, q.enc, DPi, 0, 1, Mii, Di, p, 2 * Di, p + Mi * 2 * D);
@@ -626,7 +678,7 @@ static int make_sh(const ppoaf_icm_shapes_args_t* a, IcmSh& q, bool training) {
                   "icm_shapes: buckets and scratch must be 16-byte aligned");
     if (training) {
         PPOAF_REQUIRE(a->grads && a->exp_avg && a->exp_avg_sq && a->step_count && a->lr && (a->perm || a->inputs_in_batch_order) &&
-                          a->cursor && a->denc_scratch && a->loss_partials && a->totals && a->workspace,
+                          a->cursor && (a->denc_scratch || a->enc_hidden == 0) && a->loss_partials && a->totals && a->workspace,
                       "icm_shapes: null pointer (the workspace is mandatory: there is no slab form)");
         PPOAF_REQUIRE(((uintptr_t)a->grads & 15) == 0 && ((uintptr_t)a->exp_avg & 15) == 0 && ((uintptr_t)a->exp_avg_sq & 15) == 0 &&
                           ((uintptr_t)a->denc_scratch & 15) == 0 && ((uintptr_t)a->workspace & 255) == 0,
@@ -635,6 +687,7 @@ static int make_sh(const ppoaf_icm_shapes_args_t* a, IcmSh& q, bool training) {
     IcmDev& u = q.d;
     u = IcmDev();
     q.E = a->enc_hidden; q.D = a->enc_dim; q.DP = 16 * ((a->enc_dim + 15) / 16); q.Mi = a->inv_hidden; q.Mf = a->fwd_hidden;
+    q.ident = a->enc_hidden == 0;
     u.O = a->obs_dim; u.H = a->enc_dim; u.A = a->action_dim; u.Ain = a->fwd_action_dim;
     u.d_inv = a->depth_inv; u.d_fwd = a->depth_fwd; u.act = a->activation; u.discrete = a->discrete != 0;
     u.enc_off = a->enc_offset; u.inv_off = a->inv_offset; u.fwd_off = a->fwd_offset; u.enc_size = a->inv_offset - a->enc_offset;
@@ -650,11 +703,13 @@ static int make_sh(const ppoaf_icm_shapes_args_t* a, IcmSh& q, bool training) {
     u.actE = a->act_scratch; u.loss_partials = a->loss_partials; u.totals = a->totals;
     u.confine = training ? a->xcd_half : 0;
     u.split = training ? 1 : 0;
-    q.enc = a->act_scratch + 6 * u.Bpad * q.E;
+    q.enc = a->act_scratch + 6 * u.Bpad * q.E;      // (identity encoder: E = 0, the encodings are all of act_scratch)
     q.gI = q.gF = q.dEh = q.dEo = q.dFo = nullptr;
     if (training) {
-        q.gI = a->denc_scratch;
-        q.gF = a->denc_scratch + 2 * u.Bpad * q.DP;
+        if (!q.ident) {
+            q.gI = a->denc_scratch;
+            q.gF = a->denc_scratch + 2 * u.Bpad * q.DP;
+        }
         const size_t need = sh_layout(q, reinterpret_cast<char*>(a->workspace), nullptr);
         PPOAF_REQUIRE((size_t)a->workspace_bytes >= need, "icm_shapes: workspace of %ld B, %zu needed", (long)a->workspace_bytes, need);
     }
@@ -762,6 +817,7 @@ extern "C" int ppoaf_icm_shapes_workspace_bytes(const ppoaf_icm_shapes_args_t* a
     IcmSh q;
     q.d = IcmDev();
     q.E = args->enc_hidden; q.D = args->enc_dim; q.DP = 16 * ((args->enc_dim + 15) / 16); q.Mi = args->inv_hidden; q.Mf = args->fwd_hidden;
+    q.ident = args->enc_hidden == 0;
     q.d.O = args->obs_dim; q.d.d_inv = args->depth_inv; q.d.d_fwd = args->depth_fwd;
     q.d.Bpad = (args->B + kRows - 1) / kRows * kRows;
     *bytes_out = (int64_t)sh_layout(q, nullptr, nullptr);
@@ -773,15 +829,17 @@ extern "C" int ppoaf_icm_shapes_fwd_bwd(const ppoaf_icm_shapes_args_t* args, ppo
     int rc = make_sh(args, q, true);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    PPOAF_REQUIRE(sh_lds_enc_fwd(q) <= 160 * 1024, "icm_shapes: the encoder needs %zu B of LDS (> 160 KiB)", sh_lds_enc_fwd(q));
-    rc = launch_sh_encoder(q, false, s);
-    if (rc) return rc;
+    if (!q.ident) {
+        PPOAF_REQUIRE(sh_lds_enc_fwd(q) <= 160 * 1024, "icm_shapes: the encoder needs %zu B of LDS (> 160 KiB)", sh_lds_enc_fwd(q));
+        rc = launch_sh_encoder(q, false, s);
+        if (rc) return rc;
+    }
     if (q.Mi == q.Mf) rc = launch_sh_models(q, q.Mi, -1, s);
     else {
         rc = launch_sh_models(q, q.Mi, 0, s);
         if (!rc) rc = launch_sh_models(q, q.Mf, 1, s);
     }
-    if (rc) return rc;
+    if (rc || q.ident) return rc;
     return launch_sh_encoder(q, true, s);
 }
 
@@ -802,10 +860,12 @@ extern "C" int ppoaf_icm_shapes_intrinsic_reward(const ppoaf_icm_shapes_args_t* 
     PPOAF_REQUIRE(intr_out, "icm_shapes_intrinsic_reward: null output");
     PPOAF_REQUIRE(args->perm == nullptr && args->fused_adam == 0 && args->inputs_in_batch_order == 0,
                   "icm_shapes_intrinsic_reward: rows are the batch itself (perm NULL, fused_adam 0, inputs_in_batch_order 0)");
-    PPOAF_REQUIRE(sh_lds_enc_fwd(q) <= 160 * 1024, "icm_shapes: the encoder needs %zu B of LDS (> 160 KiB)", sh_lds_enc_fwd(q));
     hipStream_t s = (hipStream_t)stream;
-    rc = launch_sh_encoder(q, false, s);
-    if (rc) return rc;
+    if (!q.ident) {
+        PPOAF_REQUIRE(sh_lds_enc_fwd(q) <= 160 * 1024, "icm_shapes: the encoder needs %zu B of LDS (> 160 KiB)", sh_lds_enc_fwd(q));
+        rc = launch_sh_encoder(q, false, s);
+        if (rc) return rc;
+    }
     if (q.Mf == 32) return launch_sh_reward<2>(q, scale, intr_out, s);
     if (q.Mf == 64) return launch_sh_reward<4>(q, scale, intr_out, s);
     return launch_sh_reward<8>(q, scale, intr_out, s);

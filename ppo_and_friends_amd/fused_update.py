@@ -933,9 +933,71 @@ def _describe_icm_shapes(icm, action_dtype):
                 enc_offset=marks[0], inv_offset=marks[1], fwd_offset=marks[2], bucket_total=total), ""
 
 
+def _describe_icm_identity(icm, action_dtype):
+    """IcmShapesArgs topology fields (+ general=True, identity=True) of an ICM whose encoder is nn.Identity()
+    (encoded_obs_dim = 0), or (None, reason).  The kernels read it as enc_hidden = 0, enc_dim = obs_dim = O and an encoder
+    of size 0 (enc_offset == inv_offset).  Covered: 1 <= O <= 128, inverse 2 O -> Mi (x 1..3) -> A, forward O + Ain -> Mf
+    (x 1..3) -> O; Mi, Mf in (32, 64, 128)."""
+    from .networks.icm import ICM
+    if not isinstance(icm, ICM):
+        return None, "not an ICM"
+    if not isinstance(icm.obs_encoder, nn.Identity):
+        return None, "not an identity encoder (encoded_obs_dim > 0)"
+    if action_dtype == "multi-discrete":
+        return None, "multi-discrete actions are not covered by the fused ICM update"
+    if action_dtype not in ("discrete", "continuous"):
+        return None, "unsupported action space for the fused ICM update"
+    inv = [m for m in icm.inv_model.sequential_net.modules() if isinstance(m, nn.Linear)]
+    fwd = [m for m in icm.forward_model.sequential_net.modules() if isinstance(m, nn.Linear)]
+    widths = (32, 64, 128)
+    if len(inv) < 2 or len(fwd) < 2 or len(inv) > 4 or len(fwd) > 4:
+        return None, "inverse / forward model need 1..3 hidden layers"
+    O = fwd[-1].out_features
+    if not 1 <= O <= 128:
+        return None, f"identity encoder: observation size O = {O} is above the fused kernels' limit of 128"
+    Mi, Mf = inv[0].out_features, fwd[0].out_features
+    if Mi not in widths or Mf not in widths:
+        return None, f"inverse / forward model widths ({Mi}, {Mf}) are not instantiated widths {widths}"
+    A, Ain = inv[-1].out_features, fwd[0].in_features - O
+    want_inv = [(2 * O, Mi)] + [(Mi, Mi)] * (len(inv) - 2) + [(Mi, A)]
+    want_fwd = [(O + Ain, Mf)] + [(Mf, Mf)] * (len(fwd) - 2) + [(Mf, O)]
+    if [(m.in_features, m.out_features) for m in inv] != want_inv or \
+            [(m.in_features, m.out_features) for m in fwd] != want_fwd:
+        return None, "inverse / forward model layers do not follow 2 O -> Mi .. -> A / O + Ain -> Mf .. -> O"
+    if not (1 <= A <= 8 and 1 <= Ain <= 8):
+        return None, f"action widths ({A}, {Ain}) must be in [1, 8]"
+    if action_dtype == "discrete" and Ain != A:
+        return None, "unsupported action space for the fused ICM update"
+    acts = {_activation_code(a) for a in (icm.activation, icm.inv_model.activation, icm.forward_model.activation)}
+    if len(acts) != 1 or None in acts:
+        return None, "activation is not one shared ReLU / LeakyReLU(0.01) / Tanh"
+    if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
+        return None, "PPOAF_SPLIT_WGRAD=0: the chain for these ICM shapes has no slab form"
+    marks, total = _icm_bucket_marks(icm, (inv, fwd))
+    if marks is None:
+        return None, total
+    return dict(general=True, identity=True, obs_dim=O, enc_hidden=0, enc_dim=O, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A,
+                fwd_action_dim=Ain, depth_inv=len(inv) - 1, depth_fwd=len(fwd) - 1, activation=acts.pop(),
+                discrete=int(action_dtype == "discrete"), enc_offset=marks[0], inv_offset=marks[0], fwd_offset=marks[1],
+                bucket_total=total), ""
+
+
+def describe_icm_chain(icm, action_dtype):
+    """Which K14 chain trains `icm`: the one-width description, else the one for widths of their own, else the identity
+    encoder's; (topology, "") or (None, reason of the describer that matches the ICM's encoder type)."""
+    topo, why = _describe_icm(icm, action_dtype)
+    if topo is not None:
+        return topo, ""
+    if isinstance(getattr(icm, "obs_encoder", None), nn.Identity):
+        return _describe_icm_identity(icm, action_dtype)
+    return None, why
+
+
 def icm_scratch_floats(topo, rows):
     """(act_scratch, denc_scratch) floats of either K14 chain for `rows` rows (include/ppoaf_hip.h)."""
     bpad = (rows + 15) // 16 * 16
+    if topo.get("identity"):                     # the two observation panels; no d(enc) (a token allocation)
+        return 2 * bpad * ((topo["obs_dim"] + 15) // 16 * 16), 4
     if topo.get("general"):
         dp = (topo["enc_dim"] + 15) // 16 * 16
         return 2 * bpad * (3 * topo["enc_hidden"] + dp), 4 * bpad * dp
@@ -946,7 +1008,7 @@ def icm_topology_args(topo):
     """The args struct of the chain `topo` selects, topology fields set."""
     a = _lib.IcmShapesArgs() if topo.get("general") else _lib.IcmUpdateArgs()
     for k, v in topo.items():
-        if k != "general":
+        if k not in ("general", "identity"):
             setattr(a, k, v)
     return a
 
@@ -994,31 +1056,51 @@ class FusedIcmUpdate(FusedEpoch):
     Per mini-batch: fwd_bwd (3 launches) -> reduce [+ Adam]; with more ranks reduce -> all-reduce ->
     K11 Adam.  On a single rank `graph_chunk` mini-batches are captured into a hipGraph and replayed
     (all launches read the device cursor).  An ICM with widths of its own (`topo["general"]`) runs the same protocol on
-    csrc/icm_update_shapes.hip: ppoaf_icm_shapes_fwd_bwd -> ppoaf_icm_shapes_wgrad, split-wgrad form only.
+    csrc/icm_update_shapes.hip: ppoaf_icm_shapes_fwd_bwd -> ppoaf_icm_shapes_wgrad, split-wgrad form only; so does an ICM
+    with an identity encoder (`topo["identity"]`), whose fwd_bwd is the models launch alone.
+
+    Agent-grouped (MAT) policies without agent_shared_icm (ppo.py:2540-2545, "case 3"): the ICM samples of a mini-batch of
+    n grouped rows are its n A (row, agent) pairs in row-major order.  The epoch's tables are [N, A, .] in shuffled order,
+    which read as [N A, .] are those samples in mini-batch order, so the kernels run with inputs_in_batch_order = 1,
+    B = n A and batch_stride = batch_size A: icm_rows (csrc/icm_update_dev.hpp) then takes row cursor * batch_stride + s of
+    the tables and reads neither `perm` nor `row_map` (they index the buffer's grouped rows, not the samples: NULL here),
+    and n_rows = N A only bounds the tables.  `self.B`, the tail and the cursor keep counting grouped rows / mini-batches.
     """
 
     n_totals = 2
     min_tail_rows = 1
 
     @staticmethod
-    def unsupported_reason(pol):
+    def unsupported_reason(pol, batch_size=None):
         if not pol.enable_icm:
             return "no ICM"
-        if pol.agent_grouping:
-            return "agent-grouped policy: the ICM rows are regrouped per mini-batch (ppo.py:2509-2545), torch path"
-        _, why = _describe_icm(pol.icm_model, pol.action_dtype)
+        if pol.agent_grouping and pol.agent_shared_icm:
+            return ("agent_shared_icm: one ICM over the MultiDiscrete action space of the whole group (ppo.py:2520-2538) "
+                    "is not covered, torch path")
+        _, why = describe_icm_chain(pol.icm_model, pol.action_dtype)
+        if not why and pol.agent_grouping and batch_size is not None:
+            A = FusedIcmUpdate._agents(pol)
+            if batch_size * A > 65536:
+                return f"agent-grouped policy: batch_size x agents = {batch_size} x {A} ICM rows per mini-batch exceed 65536"
         return why
+
+    @staticmethod
+    def _agents(pol):
+        """ICM samples per buffer row: the group's agents for an agent-grouped policy, else 1."""
+        return int(getattr(pol, "num_agents", 0) or len(pol.agent_ids)) if getattr(pol, "agent_grouping", False) else 1
 
     def __init__(self, ppo, policy_id):
         super().__init__(ppo, policy_id)
         pol = self.pol
         dev = pol.device
-        self.topo, _ = _describe_icm(pol.icm_model, pol.action_dtype)
+        self.topo, _ = describe_icm_chain(pol.icm_model, pol.action_dtype)
         self.general = bool(self.topo.get("general"))      # csrc/icm_update_shapes.hip: split-wgrad form only, no in-kernel waits
-        nT = (self.B + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
+        self.A = self._agents(pol)                         # ICM samples per buffer row (agent-grouped policies: the agents)
+        rows = self.B * self.A                             # everything below is sized for a full mini-batch's samples
+        nT = (rows + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
         total = self.topo["bucket_total"]
         self.slabs = None if self.general else torch.zeros(2 * nT, total, dtype=torch.float32, device=dev)
-        n_act, n_denc = icm_scratch_floats(self.topo, self.B)
+        n_act, n_denc = icm_scratch_floats(self.topo, rows)
         self.act_scratch = torch.zeros(n_act, dtype=torch.float32, device=dev)
         self.denc_scratch = torch.zeros(n_denc, dtype=torch.float32, device=dev)
         self.loss_partials = torch.zeros(nT + 1, 2, dtype=torch.float32, device=dev)    # + the step's Adam constants
@@ -1046,8 +1128,12 @@ class FusedIcmUpdate(FusedEpoch):
         t = self.tables                        # per-epoch inputs in shuffled order (begin_epoch)
         a.obs, a.next_obs, a.actions = t["obs"].data_ptr(), t["next_obs"].data_ptr(), t["actions"].data_ptr()
         a.inputs_in_batch_order = 1
-        a.perm, a.row_map, a.n_rows = self.perm.data_ptr(), buf.row_map.data_ptr(), buf.num_transitions
-        a.cursor, a.B, a.batch_stride = self.cursor.data_ptr(), B, self.B
+        if self.A > 1:
+            # (row, agent) samples: the tables read as [N A, .]; perm / row_map are not the samples' (class comment)
+            a.perm, a.row_map, a.n_rows = None, None, self.perm.numel() * self.A
+        else:
+            a.perm, a.row_map, a.n_rows = self.perm.data_ptr(), buf.row_map.data_ptr(), buf.num_transitions
+        a.cursor, a.B, a.batch_stride = self.cursor.data_ptr(), B * self.A, self.B * self.A
         a.icm_beta = float(pol.icm_beta)
         a.fused_adam = int(not self.multi)
         a.act_scratch, a.denc_scratch = self.act_scratch.data_ptr(), self.denc_scratch.data_ptr()

@@ -605,15 +605,16 @@ class PPOPolicy:
         return intr.reshape(-1) * float(self.intr_reward_weight())
 
     def _fused_intrinsic_reward(self, obs_1, obs_2, act):
-        """K14's encoder + forward-model kernels on the env batch (two launches); None when not covered."""
+        """K14's encoder + forward-model kernels on the env batch (two launches; one for an identity encoder); None when not
+        covered."""
         import ctypes as C
         from .. import _lib
         from .. import kernels as K
         st = getattr(self, "_icm_reward_state", None)
         n = obs_1.shape[0]
         if st is None or st["n"] != n:
-            from ..fused_update import _describe_icm, icm_scratch_floats, icm_topology_args
-            topo, why = _describe_icm(self.icm_model, self.action_dtype)
+            from ..fused_update import describe_icm_chain, icm_scratch_floats, icm_topology_args
+            topo, why = describe_icm_chain(self.icm_model, self.action_dtype)
             if topo is None:
                 self.fused_icm_reward = False
                 return None

@@ -72,6 +72,16 @@ class PermutationLoader:
         self.generator = generator
         # {"n": N, "perm": tensor}: the NEXT draw of `generator`, made early (see prefetch())
         self.prefetch_cache = prefetch_cache if prefetch_cache is not None else {}
+        self._own_cache = prefetch_cache is None
+
+    def __del__(self):
+        # a draw made ahead into a cache that goes away with this loader would be lost, and the generator left one draw
+        # ahead of the reference's stream: put it back, so that the next loader on this generator receives that draw
+        try:
+            if self._own_cache:
+                self._discard_prefetch()
+        except Exception:                     # interpreter shutdown
+            pass
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
@@ -1013,6 +1023,23 @@ class PPO:
                 f.drop_peer_exchange(why)
         self.status_dict["global status"]["peer exchange disabled"] = True
 
+    def _overlapped_epochs(self, policy_id, batch_size=None):
+        """Whether a policy's PPO epoch and ICM epoch run side by side (_ppo_icm_epoch_overlapped) or in turn."""
+        pol = self.policies[policy_id]
+        if not pol.enable_icm or not getattr(self, "overlap_icm", True) or self.device.type != "cuda" \
+                or os.environ.get("PPOAF_OVERLAP_ICM", "1") == "0":            # (measurement switch: the two epochs in turn)
+            return False
+        if pol.agent_grouping:
+            # K14 beside K15 on XCD halves has not been run or measured: the two epochs go in turn
+            return False
+        fused = self._fused_updater(policy_id, self.batch_size if batch_size is None else batch_size)
+        fused_icm = self._fused_icm_updater(policy_id)
+        if fused is None or fused_icm is None:
+            return False
+        if mpi_utils.distributed_path() and (fused.xchg is None or fused_icm.xchg is None):
+            return False
+        return True
+
     def _ppo_icm_epoch_overlapped(self, loader, policy_id):
         """
         One PPO epoch and the ICM epoch that follows it (ppo.py:2208-2216) on two HIP streams at once.
@@ -1025,16 +1052,10 @@ class PPO:
         object, nothing orders the two against each other) -- host-side collectives stay on one stream, so the RCCL /
         gloo paths run the two epochs one after the other as the reference does.
         """
-        pol = self.policies[policy_id]
-        if not pol.enable_icm or not getattr(self, "overlap_icm", True) or self.device.type != "cuda" \
-                or os.environ.get("PPOAF_OVERLAP_ICM", "1") == "0":            # (measurement switch: the two epochs in turn)
+        if not self._overlapped_epochs(policy_id, loader.batch_size):
             return False
         fused = self._fused_updater(policy_id, loader.batch_size)
         fused_icm = self._fused_icm_updater(policy_id)
-        if fused is None or fused_icm is None:
-            return False
-        if mpi_utils.distributed_path() and (fused.xchg is None or fused_icm.xchg is None):
-            return False
         # each chain's fwd_bwd launches on its own half of the XCDs: weights and panels of one chain stay out of the other's
         # four L2s (C3: +2 % env-steps/s; PPO.xcd_halves = False: both use every XCD)
         halves = getattr(self, "xcd_halves", True)
@@ -1230,7 +1251,7 @@ class PPO:
         key = ("icm", policy_id)
         if key not in self._fused:
             from .fused_update import FusedIcmUpdate
-            why = FusedIcmUpdate.unsupported_reason(self.policies[policy_id])
+            why = FusedIcmUpdate.unsupported_reason(self.policies[policy_id], self.batch_size)
             if why and self.verbose:
                 rank_print(f"policy {policy_id}: torch ICM update path ({why})")
             self._fused[key] = None if why else FusedIcmUpdate(self, policy_id)

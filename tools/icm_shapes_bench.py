@@ -2,14 +2,24 @@
 One ICM epoch and the per-env-step intrinsic reward at the reference baselines' ICM shape -- encoder 17 -> 128^3 -> 9,
 inverse / forward model width 32, Box(6) actions, 4096 envs x 128 steps, mini-batches of 256 -- on K14's chain for ICMs with
 widths of their own (csrc/icm_update_shapes.hip, update_mode="fused") against update_mode="torch", which is what ran this
-shape before that chain existed.
+shape before that chain existed.  Two more cases, each against the torch path that ran them until K14 covered them:
+
+  --identity   the abmarl_blind_large_maze form: identity encoder (encoded_obs_dim = 0) on the agent's position (O 2),
+               inverse / forward model width 128, Discrete(5) actions (csrc/icm_update_shapes.hip with enc_hidden = 0)
+  --agents A   an agent-grouped MATPolicy of A agents (O 18, Discrete(5): the C5 dims of bench.py at A = 3) with the default
+               ICM (one width, 128): one ICM sample per (row, agent) pair, so a mini-batch of `--batch` grouped rows is
+               `--batch` x A ICM rows; `--envs` defaults to 1024 here, as C5's.  Combine with --identity for the identity ICM.
 
 Both legs live in one process on the same rollout shape; after a warm-up pass of each they are ALTERNATED `--repeats`
 times and timed with device events: the epoch = PPO._icm_batch_train over 2048 mini-batches (shuffle draw included), the
 reward = PPOPolicy.get_intrinsic_reward on the 4096-row env batch (mean of `--reward-calls` back-to-back calls).  Prints the
 median and the spread (min .. max) of both, the launches per mini-batch of the fused chain, and one JSON line.
 
-    python tools/icm_shapes_bench.py [--envs 4096] [--steps 128] [--batch 256] [--repeats 5] [--reward-calls 50]
+    python tools/icm_shapes_bench.py [--identity] [--agents A] [--envs 4096] [--steps 128] [--batch 256] [--repeats 5]
+                                     [--reward-calls 50] [--allow-torch-path]
+
+--allow-torch-path: do not insist that the "fused" leg has a fused updater -- for running this tool on a commit whose K14
+does not cover the case yet (both legs then time the torch path, which is what that commit runs).
 """
 import argparse
 import json
@@ -24,18 +34,34 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 DEV = torch.device("cuda", 0)
-O, NA = 17, 6
-ICM_KW = dict(encoded_obs_dim=9, encoder_hidden_size=128, inverse_hidden_size=32, forward_hidden_size=32)
+BASELINE_KW = dict(encoded_obs_dim=9, encoder_hidden_size=128, inverse_hidden_size=32, forward_hidden_size=32)
+IDENTITY_KW = dict(encoded_obs_dim=0, inverse_hidden_size=128, forward_hidden_size=128)
 
 
-def make(mode, E, T, B):
+def case_of(args):
+    """-> (O, action space, agents, ICM keyword arguments) of the case the flags select."""
+    from ppo_and_friends_amd.spaces import Box, Discrete
+    if args.agents > 1:
+        return 18, Discrete(5), args.agents, (dict(IDENTITY_KW) if args.identity else {})
+    if args.identity:
+        return 2, Discrete(5), 1, dict(IDENTITY_KW)
+    return 17, Box(-1.0, 1.0, (6,), np.float32), 1, dict(BASELINE_KW)
+
+
+def make(mode, E, T, B, case):
     from ppo_and_friends_amd.ppo import PPO
     from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
     from ppo_and_friends_amd.spaces import Box
-    space = Box(-1.0, 1.0, (NA,), np.float32)
-    env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, DEV, reward="uniform", seed=5, term_prob=0.05)
+    O, space, A, icm_kw = case
+    cls = None
+    if A > 1:
+        from ppo_and_friends_amd.policies.mat_policy import MATPolicy
+        cls = MATPolicy
+        env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, DEV, reward="uniform", seed=5, num_agents=A)
+    else:
+        env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, DEV, reward="uniform", seed=5, term_prob=0.05)
     sp = Box(-np.inf, np.inf, (O,), np.float32)
-    ppo = PPO(env_gen, {"p": (None, sp, sp, space, dict(enable_icm=True, icm_kw_args=ICM_KW))}, device=DEV, random_seed=4,
+    ppo = PPO(env_gen, {"p": (cls, sp, sp, space, dict(enable_icm=True, icm_kw_args=icm_kw))}, device=DEV, random_seed=4,
               normalize_obs=False, normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=B, epochs_per_iter=1,
               update_mode=mode)
     ppo.rollout()
@@ -54,27 +80,38 @@ def timed(fn):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--identity", action="store_true")
+    ap.add_argument("--agents", type=int, default=1)
+    ap.add_argument("--allow-torch-path", action="store_true")
+    ap.add_argument("--envs", type=int, default=None)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--reward-calls", type=int, default=50)
     args = ap.parse_args()
+    if args.envs is None:
+        args.envs = 1024 if args.agents > 1 else 4096
     from ppo_and_friends_amd.ppo import PermutationLoader
     from ppo_and_friends_amd.fused_update import FusedIcmUpdate
     from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
-    legs = {}
+    case = case_of(args)
+    O, space, A, icm_kw = case
+    legs, path = {}, {}
     for mode in ("fused", "torch"):
-        ppo = make(mode, args.envs, args.steps, args.batch)
+        ppo = make(mode, args.envs, args.steps, args.batch, case)
         pol = ppo.policies["p"]
         upd = ppo._fused_icm_updater("p")
-        if mode == "fused":
-            assert upd is not None and upd.topo.get("general"), FusedIcmUpdate.unsupported_reason(pol)
-        else:
+        path[mode] = "torch" if upd is None else "K14"
+        if mode == "fused" and not args.allow_torch_path:
+            assert upd is not None, FusedIcmUpdate.unsupported_reason(pol)
+            assert bool(upd.topo.get("identity")) == args.identity, upd.topo
+        elif mode == "torch":
             assert upd is None
         loader = PermutationLoader(pol.dataset, args.batch, ppo.loader_generator)
         buf = pol.buffer
-        o1, o2, act = buf.observations[0], buf.next_observations[0], buf.actions[0]
+        rows = args.envs * A                                     # the env batch of one step: one row per (env, agent)
+        o1, o2 = buf.observations[0].reshape(rows, -1), buf.next_observations[0].reshape(rows, -1)
+        act = buf.actions[0].reshape(rows, -1)
 
         def epoch(ppo=ppo, loader=loader):
             ppo._icm_batch_train(loader, "p")
@@ -82,25 +119,36 @@ def main():
         def reward(pol=pol, o1=o1, o2=o2, act=act, n=args.reward_calls):
             for _ in range(n):
                 pol.get_intrinsic_reward(o1, o2, act)
-        legs[mode] = dict(epoch=epoch, reward=reward, ms=[], us=[])
+        legs[mode] = dict(epoch=epoch, reward=reward, ms=[], us=[], upd=upd)
     n_mb = -(-args.envs * args.steps // args.batch)
     for leg in legs.values():                                  # warm-up pass: graph capture, allocations, autotuning
         leg["epoch"](); leg["reward"]()
     calls = PPOPolicy.fused_icm_reward_calls
+    topo = {} if legs["fused"]["upd"] is None else legs["fused"]["upd"].topo
     for _ in range(max(5, args.repeats)):
         for mode in ("fused", "torch"):
             leg = legs[mode]
             leg["ms"].append(timed(leg["epoch"]))
             leg["us"].append(1e3 * timed(leg["reward"]) / args.reward_calls)
-    assert PPOPolicy.fused_icm_reward_calls - calls == max(5, args.repeats) * args.reward_calls, "the fused leg's rewards took the torch path"
-    out = dict(shape=dict(O=O, actions=NA, envs=args.envs, steps=args.steps, batch=args.batch, minibatches=n_mb, **ICM_KW),
-               fused_launches_per_minibatch=4 if ICM_KW["inverse_hidden_size"] == ICM_KW["forward_hidden_size"] else 5)
+    if not args.allow_torch_path:
+        assert PPOPolicy.fused_icm_reward_calls - calls == max(5, args.repeats) * args.reward_calls, "the fused leg's rewards took the torch path"
+    # launches per mini-batch: [encoder forward,] the models (one launch per model when their widths differ) [, encoder
+    # backward], weight gradients; the one-width chain fuses its first three into one launch where it can
+    if not topo:
+        launches = None
+    elif topo.get("general"):
+        launches = (1 if topo["inv_hidden"] == topo["fwd_hidden"] else 2) + (1 if topo.get("identity") else 3)
+    else:
+        launches = 2 if legs["fused"]["upd"].fuse_reason() == "" else 4
+    out = dict(shape=dict(O=O, actions=f"Discrete({space.n})" if hasattr(space, "n") else f"Box({space.shape[0]})", agents=A, envs=args.envs, steps=args.steps, batch=args.batch,
+                          icm_rows_per_minibatch=args.batch * A, minibatches=n_mb, **icm_kw),
+               path=path, fused_launches_per_minibatch=launches)
     for mode, leg in legs.items():
         ms, us = leg["ms"], leg["us"]
         out[mode] = dict(epoch_ms_median=statistics.median(ms), epoch_ms_min=min(ms), epoch_ms_max=max(ms),
                          us_per_minibatch=1e3 * statistics.median(ms) / n_mb,
                          reward_us_median=statistics.median(us), reward_us_min=min(us), reward_us_max=max(us))
-        print(f"{mode:5s}: ICM epoch {statistics.median(ms):9.2f} ms ({min(ms):.2f} .. {max(ms):.2f}) = "
+        print(f"{mode:5s} ({path[mode]}): ICM epoch {statistics.median(ms):9.2f} ms ({min(ms):.2f} .. {max(ms):.2f}) = "
               f"{1e3 * statistics.median(ms) / n_mb:7.2f} us per mini-batch; reward call {statistics.median(us):8.1f} us "
               f"({min(us):.1f} .. {max(us):.1f})")
     out["epoch_speedup"] = out["torch"]["epoch_ms_median"] / out["fused"]["epoch_ms_median"]
