@@ -1053,6 +1053,69 @@ int ppoaf_lstm_policy_step(const ppoaf_lstm_policy_step_args_t* args, ppoaf_stre
 int ppoaf_lstm_policy_step_check(const ppoaf_lstm_policy_step_args_t* args);
 
 /* ------------------------------------------------------------------------ *
+ * K22  one mini-batch of the PPO update of an LSTM actor / critic pair as three launches
+ * replaces, per mini-batch of PPO._ppo_batch_train    ppo.py:2292-2469
+ *          the window gather of the dataset           utils/episode_info.py:775-809,940-987
+ *          the hidden-state hand-over and write-back  ppo.py:2312-2319,2450-2466
+ *          PPOPolicy.evaluate + the losses            policies/ppo_policy.py:891-952, ppo.py:2325-2438
+ *          loss.backward                              ppo.py:2408-2441
+ *          clip_grad_norm_ + Adam per network         policies/ppo_policy.py:1037-1042
+ * The networks are K18's (same descriptors, coverage and bucket layout; `steps` is the window length S, `rows`,
+ * `workspace` and `workspace_floats` of the descriptors are not read), both with ONE LSTM hidden size; actor.params /
+ * actor.grads and critic.params / critic.grads point into the policy's flat buckets `params` / `grads` (actor first,
+ * critic at actor_size), which also hold a Gaussian head's log_std at log_std_offset floats inside the actor's part.
+ * Every launch reads the device cursor: mini-batch mb = *cursor covers entries [mb * batch_stride, mb * batch_stride + B)
+ * of `perm` (the epoch's shuffled item indices) and of the per-epoch tables raw_actions / advantages / old_log_probs /
+ * rewards_to_go, which hold the items' LAST position (item + S - 1) in shuffled order.
+ *   ppoaf_lstm_update_fwd_bwd  2 * ceil(B/16) workgroups (the actor's 16-row tiles, then the critic's) of hidden/16
+ *       waves.  A workgroup forms its items' windows -- buffer rows row_map[item + s], s < S, of obs / critic_obs
+ *       [n_rows, in_dim]; actor observations zeroed strictly after a terminal position (`terminal`: one byte per
+ *       dataset position, NULL when S = 1) --, takes (h0, c0) from the hidden tables [n_rows, hidden] at the last
+ *       position's row, stages both into the workspace, runs K18's forward, writes the final (h, c) back to the same
+ *       rows, evaluates the head and the loss of its rows (K12's terms; the critic's values are scattered into `values`
+ *       at the last position's row; advantage and value normalisation from the per-mini-batch records adv_records
+ *       [n_batches, 3] / vn_records [n_batches, n_ranks, 3] of (n, mean, M2) and the double-buffered normaliser slots
+ *       vn_mean / vn_var / vn_count [2]), leaves its loss partial sums in loss_partials [2, ceil(B/16), 8] and runs
+ *       K18's backward (head, LayerNorm, BPTT) into the workspace.
+ *   ppoaf_lstm_update_wgrad    the weight gradients of both networks (K18's tiles: fixed reduction order, no
+ *       atomics), STORED into `grads` -- nothing has to clear the bucket --, one pair of squared-norm partials of the
+ *       scaled gradient per workgroup in norm_scratch[2 ..]; its last workgroup advances both Adam step counters.
+ *   ppoaf_lstm_update_adam     clip norm per network (max_norm <= 0: no clipping) + Adam on exp_avg / exp_avg_sq /
+ *       step_counts [2] with the gradient scale grad_scale (1 / ranks); its last workgroup folds loss_partials into the
+ *       nine totals, integrates the mini-batch's normaliser record into the other slot and advances the cursor.
+ *       norm_mode 0: the partials of ppoaf_lstm_update_wgrad; 1: a norm pass over `grads` first (a fourth launch: after
+ *       an all-reduce of the bucket); 2: norm_scratch[0..1] hold the squared norms (ppoaf_peer_exchange_allreduce).
+ * ppoaf_lstm_update_check validates on the host only (no launch, no pointer followed; with `pointers` == 0 the shapes
+ * alone) and names the offending field; ppoaf_lstm_update_workspace_floats: out[0] = floats of `workspace` for B rows,
+ * out[1] = doubles of norm_scratch, out[2] = LDS bytes of a fwd_bwd workgroup.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    ppoaf_lstm_desc_t actor, critic;
+    float* params; float* grads; float* exp_avg; float* exp_avg_sq;
+    int64_t bucket_total, actor_size, log_std_offset;     /* log_std_offset: -1 without a Gaussian head */
+    int64_t* step_counts; const float* lr; double* norm_scratch; int64_t norm_scratch_doubles;
+    float beta1, beta2, adam_eps, grad_scale, max_norm; int32_t head_kind;
+    const float* obs; const float* critic_obs; const uint8_t* terminal;
+    const int64_t* perm; const int32_t* row_map; int64_t n_rows, n_items;
+    const void* raw_actions; const float* advantages; const float* old_log_probs; const float* rewards_to_go;
+    float* values;
+    float* actor_hidden; float* actor_cell; float* critic_hidden; float* critic_cell;
+    int64_t* cursor; int64_t B, batch_stride;
+    int32_t normalize_values, n_ranks;
+    float* vn_mean; float* vn_var; double* vn_count; const double* vn_records; const double* adv_records;
+    int32_t normalize_adv, use_huber;
+    float surr_clip, entropy_weight, kl_loss_weight, huber_delta, min_std; int32_t _pad;
+    float* loss_partials; double* totals;
+    float* workspace; int64_t workspace_floats;
+} ppoaf_lstm_update_args_t;
+
+int ppoaf_lstm_update_check(const ppoaf_lstm_update_args_t* args, int32_t pointers);
+int ppoaf_lstm_update_workspace_floats(const ppoaf_lstm_update_args_t* args, int64_t* out /* host [3] */);
+int ppoaf_lstm_update_fwd_bwd(const ppoaf_lstm_update_args_t* args, ppoaf_stream_t stream);
+int ppoaf_lstm_update_wgrad(const ppoaf_lstm_update_args_t* args, ppoaf_stream_t stream);
+int ppoaf_lstm_update_adam(const ppoaf_lstm_update_args_t* args, int32_t norm_mode, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * K17  gradient exchange between the ranks of one node over peer mappings (xGMI)
  * replaces, inside the per-mini-batch update chain, the comm.Allreduce of
  *          mpi_avg_gradients                       utils/mpi_utils.py:65-86  (called from ppo.py:2443-2448,

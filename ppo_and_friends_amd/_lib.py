@@ -113,6 +113,32 @@ class LstmPolicyStepArgs(C.Structure):
                 ("boot_value_out", C.c_void_p)]
 
 
+class LstmUpdateArgs(C.Structure):
+    """ppoaf_lstm_update_args_t (include/ppoaf_hip.h) -- field order must match the header."""
+    _fields_ = [("actor", LstmDesc), ("critic", LstmDesc),
+                ("params", C.c_void_p), ("grads", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("bucket_total", C.c_int64), ("actor_size", C.c_int64), ("log_std_offset", C.c_int64),
+                ("step_counts", C.c_void_p), ("lr", C.c_void_p), ("norm_scratch", C.c_void_p),
+                ("norm_scratch_doubles", C.c_int64),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("grad_scale", C.c_float),
+                ("max_norm", C.c_float), ("head_kind", C.c_int32),
+                ("obs", C.c_void_p), ("critic_obs", C.c_void_p), ("terminal", C.c_void_p),
+                ("perm", C.c_void_p), ("row_map", C.c_void_p), ("n_rows", C.c_int64), ("n_items", C.c_int64),
+                ("raw_actions", C.c_void_p), ("advantages", C.c_void_p), ("old_log_probs", C.c_void_p),
+                ("rewards_to_go", C.c_void_p), ("values", C.c_void_p),
+                ("actor_hidden", C.c_void_p), ("actor_cell", C.c_void_p), ("critic_hidden", C.c_void_p),
+                ("critic_cell", C.c_void_p),
+                ("cursor", C.c_void_p), ("B", C.c_int64), ("batch_stride", C.c_int64),
+                ("normalize_values", C.c_int32), ("n_ranks", C.c_int32),
+                ("vn_mean", C.c_void_p), ("vn_var", C.c_void_p), ("vn_count", C.c_void_p),
+                ("vn_records", C.c_void_p), ("adv_records", C.c_void_p),
+                ("normalize_adv", C.c_int32), ("use_huber", C.c_int32),
+                ("surr_clip", C.c_float), ("entropy_weight", C.c_float), ("kl_loss_weight", C.c_float),
+                ("huber_delta", C.c_float), ("min_std", C.c_float), ("_pad", C.c_int32),
+                ("loss_partials", C.c_void_p), ("totals", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_floats", C.c_int64)]
+
+
 class EvalScoresArgs(C.Structure):
     """ppoaf_eval_scores_args_t (include/ppoaf_hip.h)."""
     _fields_ = [("score", C.c_void_p), ("done", C.c_void_p), ("quota", C.c_void_p), ("E", C.c_int64),
@@ -325,6 +351,11 @@ SIGNATURES = {
     "ppoaf_lstm_wgrad": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),
     "ppoaf_lstm_policy_step": (C.c_int, [C.POINTER(LstmPolicyStepArgs), _ptr]),
     "ppoaf_lstm_policy_step_check": (C.c_int, [C.POINTER(LstmPolicyStepArgs)]),
+    "ppoaf_lstm_update_check": (C.c_int, [C.POINTER(LstmUpdateArgs), C.c_int32]),
+    "ppoaf_lstm_update_workspace_floats": (C.c_int, [C.POINTER(LstmUpdateArgs), C.POINTER(C.c_int64)]),
+    "ppoaf_lstm_update_fwd_bwd": (C.c_int, [C.POINTER(LstmUpdateArgs), _ptr]),
+    "ppoaf_lstm_update_wgrad": (C.c_int, [C.POINTER(LstmUpdateArgs), _ptr]),
+    "ppoaf_lstm_update_adam": (C.c_int, [C.POINTER(LstmUpdateArgs), C.c_int32, _ptr]),
     "ppoaf_peer_exchange_create": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "ppoaf_peer_exchange_export": (C.c_int, [_ptr, _ptr]),
     "ppoaf_peer_exchange_connect": (C.c_int, [_ptr, C.c_char_p]),

@@ -3,6 +3,9 @@
 // rollout / evaluation step, always S = 1): descriptor checks, bucket and workspace layout, kernel arguments and the
 // workgroup body.  Both kernels instantiate lstm_rows_forward, so a step of K21 and a one-step call of K18 form the
 // same sums in the same order.
+// K22 (lstm_update.hip: the fused update mini-batch) instantiates the forward body too, and with it the backward body
+// (lstm_rows_backward) and the weight-gradient tile body and job list (lstm_wgrad_tile, lstm_wgrad_add_jobs) that K18's
+// own kernels run: one copy of each, so K18 and K22 form the same sums in the same order.
 #pragma once
 #include "common.hpp"
 #include "mlp_device.hpp"
@@ -276,5 +279,247 @@ __device__ __forceinline__ const float* lstm_rows_forward(const LstmArgs& a, con
     }
     return in;
 }
+
+// The backward of rows [16 g, 16 g + 16) through the head, LayerNorm and time (dgrad / BPTT): d out (a.dout) -> the
+// pre-activation gradients of every Linear, of the LayerNorm output and of every (row, step)'s gates, into the
+// workspace the forward stashed into.  K18's kernel (lstm.hip) and K22's fwd_bwd launch (lstm_update.hip) both
+// instantiate it, so both form the same sums in the same order.
+template <int H>
+__device__ __forceinline__ void lstm_rows_backward(const LstmArgs& a, const int g_tile) {
+    constexpr int HT = H / 16, NT = HT * 64, HS = H + 4, GS = 4 * H + 4;
+    constexpr int kLds = 2 * kLRows * GS > 2 * kLRows * kLFS + kLRows * HS ? 2 * kLRows * GS : 2 * kLRows * kLFS + kLRows * HS;
+    __shared__ float lds[kLds];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long r0 = (long)g_tile * kLRows;
+    const long N = a.N;
+    const int S = a.S, F = a.F, D = a.D, O = a.O;
+    const int j = 16 * w + (lane & 15);
+    float* ws = a.ws;
+
+    // ---- head: d logits -> d pre-activation of every Linear -> d LayerNorm output -> d h_S
+    float* Bc = lds;
+    float* Bn = lds + kLRows * kLFS;
+    float* DH = lds + 2 * kLRows * kLFS;
+    for (int e = tid; e < kLRows * O; e += NT) {
+        const int r = e / O, o = e - r * O;
+        const long n = r0 + r;
+        const float v = n < N ? a.dout[n * O + o] : 0.f;
+        Bc[r * kLFS + o] = v;
+        if (n < N) ws[a.L.dz[D] + n * O + o] = v;
+    }
+    __syncthreads();
+    for (int l = D; l >= 0; --l) {
+        const int M = l == D ? O : F, K = l == 0 ? H : F;
+        const float* W = a.P + a.L.fw[l];
+        for (int e = tid; e < kLRows * K; e += NT) {
+            const int r = e / K, k = e - r * K;
+            const long n = r0 + r;
+            float s = 0.f;
+            for (int m = 0; m < M; ++m) s += Bc[r * kLFS + m] * W[(long)m * K + k];
+            const float av = n < N ? ws[a.L.acts[l] + n * K + k] : 0.f;
+            const float g = n < N ? s * act_bwd(av, a.act) : 0.f;
+            if (l > 0) {
+                Bn[r * kLFS + k] = g;
+                if (n < N) ws[a.L.dz[l - 1] + n * F + k] = g;
+            } else {
+                DH[r * HS + k] = g;
+                if (n < N) ws[a.L.dy + n * H + k] = g;
+            }
+        }
+        __syncthreads();
+        float* t = Bc; Bc = Bn; Bn = t;
+    }
+    for (int r = w; r < kLRows; r += HT) {
+        const long n = r0 + r;
+        if (n >= N) {
+            for (int k = lane; k < H; k += 64) DH[r * HS + k] = 0.f;
+            continue;
+        }
+        const float mean = ws[a.L.stats + 2 * n], rstd = ws[a.L.stats + 2 * n + 1];
+        const float* hS = ws + a.L.hst + (n * S + S - 1) * H;
+        float xh[2] = {0.f, 0.f}, gy[2] = {0.f, 0.f};
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int k = lane + 64 * u;
+            if (k < H) {
+                xh[u] = (hS[k] - mean) * rstd;
+                gy[u] = DH[r * HS + k] * a.P[a.L.ln_w + k];
+                s1 += gy[u];
+                s2 += gy[u] * xh[u];
+                ws[a.L.xhat + n * H + k] = xh[u];
+            }
+        }
+        s1 = wave_sum(s1) / (float)H;
+        s2 = wave_sum(s2) / (float)H;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int k = lane + 64 * u;
+            if (k < H) DH[r * HS + k] = rstd * (gy[u] - s1 - xh[u] * s2);
+        }
+    }
+    __syncthreads();
+    float dh[4], dc[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) { dh[g] = DH[(4 * (lane >> 4) + g) * HS + j]; dc[g] = 0.f; }
+    // W_hh^T slice of this wave: B[k][col] = W_hh[k][16 w + col], k over the 4H gate rows
+    float4 fr[4 * HT];
+    {
+        const float* Whh = a.P + a.L.w_hh + (long)(4 * (lane >> 4)) * H + j;
+#pragma unroll
+        for (int c = 0; c < 4 * HT; ++c) {
+            const float* wp = Whh + (long)(16 * c) * H;
+            fr[c] = make_float4(wp[0], wp[H], wp[2 * H], wp[3 * H]);
+        }
+    }
+    __syncthreads();                                          // DH shares the LDS with the dgates buffers
+
+    for (int t = S - 1; t >= 0; --t) {
+        float* gb = lds + (t & 1) * kLRows * GS;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int rr = 4 * (lane >> 4) + g;
+            const long n = r0 + rr;
+            float dai = 0.f, daf = 0.f, dag = 0.f, dao = 0.f;
+            if (n < N) {
+                const float* gp = ws + a.L.gates + (n * S + t) * 4 * H + j;
+                const float ig = gp[0], fg = gp[H], gg = gp[2 * H], og = gp[3 * H];
+                const float ct = ws[a.L.cst + (n * S + t) * H + j];
+                const float cp = t > 0 ? ws[a.L.cst + (n * S + t - 1) * H + j] : a.c0[n * H + j];
+                const float tc = tanhf(ct);
+                const float dcv = dc[g] + dh[g] * og * (1.f - tc * tc);
+                dai = dcv * gg * (ig * (1.f - ig));
+                daf = dcv * cp * (fg * (1.f - fg));
+                dag = dcv * ig * (1.f - gg * gg);
+                dao = dh[g] * tc * (og * (1.f - og));
+                dc[g] = dcv * fg;
+                float* dp = ws + a.L.dG + (n * S + t) * 4 * H + j;
+                dp[0] = dai; dp[H] = daf; dp[2 * H] = dag; dp[3 * H] = dao;
+            }
+            gb[rr * GS + j] = dai; gb[rr * GS + H + j] = daf; gb[rr * GS + 2 * H + j] = dag; gb[rr * GS + 3 * H + j] = dao;
+        }
+        __syncthreads();
+        if (t > 0) {
+            const f32x4 acc = mfma_rows_x_frags<4 * HT>(gb, GS, lane, fr, 0.f);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) dh[g] = acc[g];
+        }
+    }
+}
+
+// ---- weight gradients: out[i][j] (+)= sum over samples s of A[s][i] * B(s, j)
+enum { kBDense = 0, kBOnes = 1, kBHPrev = 2, kBDiag = 3 };
+struct WJob {
+    const float* A;
+    const float* B;
+    const float* B0;          // kBHPrev: h0 [N, ldb] (the previous state of step 0)
+    float* out;
+    float* out2;              // second destination (b_ih and b_hh receive the same gradient)
+    long K;                   // samples
+    int lda, ldb, M, Nc, ldo, mode, S, tiles_n, tile_begin;
+};
+struct WJobs {
+    WJob j[kLMaxJobs];
+    int n;
+};
+
+// One 16 x 16 output tile of a job, by a workgroup of 256 threads: four waves reduce over the samples in a fixed order
+// and are added in wave order.  ADD (K18): the tile is added to the gradient bucket; otherwise (K22) it is stored, so
+// that nothing has to clear the bucket first.  Returns the element this thread wrote (0 for a thread that wrote none):
+// K22 forms the clip norm from it.
+template <bool ADD>
+__device__ __forceinline__ float lstm_wgrad_tile(const WJob& jb, const int tile, float (*part)[64][4]) {
+    const int i0 = (tile / jb.tiles_n) * 16, j0 = (tile % jb.tiles_n) * 16;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const long K = jb.K;
+    if (jb.mode == kBDiag) {
+        const int jc = j0 + (lane & 15), s4 = lane >> 4;
+        float p = 0.f;
+        if (jc < jb.Nc)
+            for (long s = 4 * w + s4; s < K; s += 16) p += jb.A[s * jb.lda + jc] * (jb.B ? jb.B[s * jb.ldb + jc] : 1.f);
+        part[w][lane][0] = p;
+        __syncthreads();
+        if (tid < 16 && j0 + tid < jb.Nc) {
+            float v = 0.f;
+            for (int ww = 0; ww < 4; ++ww)
+                for (int q = 0; q < 4; ++q) v += part[ww][16 * q + tid][0];
+            if constexpr (ADD) jb.out[j0 + tid] += v; else jb.out[j0 + tid] = v;
+            return v;
+        }
+        return 0.f;
+    }
+    const int i = i0 + (lane & 15), jc = j0 + (lane & 15), s4 = lane >> 4;
+    const bool iok = i < jb.M, jok = jc < jb.Nc;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (long base = 16 * w; base < K; base += 64) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long s = base + 4 * s4 + u;
+            float av = 0.f, bv = 0.f;
+            if (s < K) {
+                if (iok) av = jb.A[s * jb.lda + i];
+                if (jb.mode == kBDense) {
+                    if (jok) bv = jb.B[s * jb.ldb + jc];
+                } else if (jb.mode == kBOnes) {
+                    bv = jc == 0 ? 1.f : 0.f;
+                } else if (jok) {                                   // kBHPrev
+                    const long t = s % jb.S;
+                    bv = t > 0 ? jb.B[(s - 1) * jb.ldb + jc] : jb.B0[(s / jb.S) * jb.ldb + jc];
+                }
+            }
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) part[w][lane][g] = acc[g];
+    __syncthreads();
+    const int ln = tid >> 2, g = tid & 3;
+    const float v = part[0][ln][g] + part[1][ln][g] + part[2][ln][g] + part[3][ln][g];
+    const int row = i0 + 4 * (ln >> 4) + g, col = j0 + (ln & 15);
+    if (row < jb.M && col < jb.Nc) {
+        if constexpr (ADD) {
+            jb.out[(long)row * jb.ldo + col] += v;
+            if (jb.out2) jb.out2[(long)row * jb.ldo + col] += v;
+        } else {
+            jb.out[(long)row * jb.ldo + col] = v;
+            if (jb.out2) jb.out2[(long)row * jb.ldo + col] = v;
+        }
+        return v;
+    }
+    return 0.f;
+}
+
+
+// host: the weight-gradient jobs of one network (a.N rows of a.S steps; x [N, S, I] and h0 [N, H] are what its forward
+// read, G its gradient bucket) appended to jobs[n..]; tiles are numbered from tile_begin.  Returns the tile count after them.
+inline int lstm_wgrad_add_jobs(WJob* jobs, int& n, int tile_begin, const LstmArgs& a, const int H, const float* x, const float* h0,
+                               float* G) {
+    const LstmLayout& L = a.L;
+    const long N = a.N, S = a.S, NS = N * S;
+    const int I = a.I, F = a.F, D = a.D, O = a.O;
+    const float* ws = a.ws;
+    int nt = tile_begin;
+    auto add = [&](const float* A, int lda, const float* B, int ldb, const float* B0, int M, int Nc, int mode,
+                   long K, float* out, float* out2, int ldo) {
+        WJob& jb = jobs[n++];
+        jb.A = A; jb.lda = lda; jb.B = B; jb.ldb = ldb; jb.B0 = B0; jb.M = M; jb.Nc = Nc; jb.mode = mode;
+        jb.K = K; jb.out = out; jb.out2 = out2; jb.ldo = ldo; jb.S = (int)S;
+        jb.tiles_n = (Nc + 15) / 16;
+        jb.tile_begin = nt;
+        nt += (mode == kBDiag ? 1 : (M + 15) / 16) * jb.tiles_n;
+    };
+    add(ws + L.dG, 4 * H, x, I, nullptr, 4 * H, I, kBDense, NS, G + L.w_ih, nullptr, I);
+    add(ws + L.dG, 4 * H, ws + L.hst, H, h0, 4 * H, H, kBHPrev, NS, G + L.w_hh, nullptr, H);
+    add(ws + L.dG, 4 * H, nullptr, 0, nullptr, 4 * H, 1, kBOnes, NS, G + L.b_ih, G + L.b_hh, 1);
+    add(ws + L.dy, H, ws + L.xhat, H, nullptr, 1, H, kBDiag, N, G + L.ln_w, nullptr, 1);
+    add(ws + L.dy, H, nullptr, H, nullptr, 1, H, kBDiag, N, G + L.ln_b, nullptr, 1);
+    for (int l = 0; l <= D; ++l) {
+        const int M = l == D ? O : F, K = l == 0 ? H : F;
+        add(ws + L.dz[l], M, ws + L.acts[l], K, nullptr, M, K, kBDense, N, G + L.fw[l], nullptr, K);
+        add(ws + L.dz[l], M, nullptr, 0, nullptr, M, 1, kBOnes, N, G + L.fb[l], nullptr, 1);
+    }
+    return nt;
+}
+
 
 }  // namespace ppoaf

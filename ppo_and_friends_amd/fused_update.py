@@ -1,6 +1,7 @@
 """
 Host drivers of the fused mini-batch update kernels: K12 (MLP policies, csrc/ppo_update.hip), K14 (ICM,
-csrc/icm_update.hip, csrc/icm_update_shapes.hip) and K15 (MAT policies, csrc/mat_update.hip).  All three run one epoch protocol (FusedEpoch):
+csrc/icm_update.hip, csrc/icm_update_shapes.hip), K15 (MAT policies, csrc/mat_update.hip) and K22 (LSTM policies,
+csrc/lstm_update.hip).  All of them run one epoch protocol (FusedEpoch):
   begin_epoch : the epoch's inputs gathered in shuffled order (one launch), the driver's own records (value-normaliser
                 records of every mini-batch: one launch, one all-gather across ranks), cursor / totals reset
   run_epoch   : per mini-batch  fwd_bwd -> reduce -> [all-reduce] -> adam;
@@ -522,6 +523,193 @@ class FusedLstm:
         if pol.critic.out_size != 1:
             return "critic must have one output"
         return ""
+
+
+def _describe_lstm_update(pol, B):
+    """_lib.LstmUpdateArgs with the shapes of an LSTM policy's two networks (no pointer set), for a mini-batch of B rows."""
+    a = _lib.LstmUpdateArgs()
+    for tag, net in (("actor", pol.actor), ("critic", pol.critic)):
+        d = getattr(a, tag)
+        dims = net.ff_layers.layer_dims()
+        d.in_dim, d.hidden, d.ff_hidden, d.ff_depth = net.in_size, net.lstm_hidden_size, dims[0][1], len(dims) - 1
+        d.out_dim, d.activation = net.out_size, _activation_code(net.activation)
+        d.rows, d.steps = B, net.sequence_length
+    a.head_kind = K.HEAD_GAUSSIAN if isinstance(pol.actor.distribution, GaussianDistribution) else K.HEAD_CATEGORICAL
+    a.B = a.batch_stride = B
+    return a
+
+
+class FusedLstmUpdate(FusedEpoch):
+    """
+    Host driver of K22 (csrc/lstm_update.hip): one epoch of PPO._ppo_batch_train for an LSTM actor / critic pair, three
+    launches per mini-batch (fwd_bwd -> wgrad -> adam) that read the device cursor.  The windows and the stored hidden
+    states are read through `perm` / `row_map` inside fwd_bwd (windows overlap and the states change during the epoch,
+    so neither can be tabled); the fields of the windows' LAST position are gathered once per epoch in shuffled order.
+    The optimiser state is the policy's own (FlatAdam's tensors), so `pol.fused_lstm_update = False` -- today's
+    mini-batch loop -- and checkpoints continue from the same state.
+    """
+
+    launches = 0                       # launches issued in this process (tests: the path really ran; graph replays not counted)
+
+    @staticmethod
+    def unsupported_reason(pol, batch_size):
+        """'' when K22 covers this policy at this batch size, else why the mini-batch loop runs."""
+        why = FusedLstm.unsupported_reason(pol)
+        if why:
+            return why
+        ha, hc = pol.actor.lstm_hidden_size, pol.critic.lstm_hidden_size
+        if ha != hc:
+            return f"LSTM hidden sizes differ (actor {ha}, critic {hc}): one K22 launch has one block size"
+        if pol.actor.sequence_length != pol.critic.sequence_length:
+            return f"sequence lengths differ (actor {pol.actor.sequence_length}, critic {pol.critic.sequence_length})"
+        if batch_size < 2:
+            return "batch size < 2"
+        return K.lstm_update_refusal(_describe_lstm_update(pol, batch_size))     # host only: nothing is launched
+
+    def __init__(self, ppo, policy_id):
+        super().__init__(ppo, policy_id)
+        pol, dev = self.pol, self.pol.device
+        self.n_wg = (self.B + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
+        _init_normaliser(self)
+        self.loss_partials = torch.zeros(2, self.n_wg, 8, dtype=torch.float32, device=dev)
+        self.S = pol.actor.sequence_length
+        self.actor_size = pol.actor.bucket_size()
+        self.gauss = isinstance(pol.actor.distribution, GaussianDistribution)
+        self.log_std_offset = -1
+        if self.gauss:
+            self.log_std_offset = (pol.actor.distribution.log_std.data_ptr() - pol.policy_params.data_ptr()) // 4
+        q = _describe_lstm_update(pol, self.B)
+        q.bucket_total, q.actor_size = pol.policy_params.numel(), self.actor_size
+        floats, doubles, self.lds_bytes = K.lstm_update_sizes(q)
+        self.workspace = torch.zeros(floats, dtype=torch.float32, device=dev)
+        self.norm_scratch = torch.zeros(doubles, dtype=torch.float64, device=dev)
+        self.perm_last = None
+        self._open_exchange(pol.policy_params.numel())
+
+    # ------------------------------------------------------------------ args
+    def _make_args(self, B):
+        pol, ppo, buf, ds, t = self.pol, self.ppo, self.pol.buffer, self.pol.dataset, self.tables
+        a = _describe_lstm_update(pol, B)
+        a.batch_stride = self.B
+        na = self.actor_size
+        a.params, a.grads = pol.policy_params.data_ptr(), pol.policy_grads.data_ptr()
+        a.exp_avg, a.exp_avg_sq = pol.policy_exp_avg.data_ptr(), pol.policy_exp_avg_sq.data_ptr()
+        a.actor.params, a.actor.grads = a.params, a.grads
+        a.critic.params, a.critic.grads = a.params + 4 * na, a.grads + 4 * na
+        a.bucket_total, a.actor_size, a.log_std_offset = pol.policy_params.numel(), na, self.log_std_offset
+        a.step_counts, a.lr = pol.policy_step_counts.data_ptr(), pol.policy_lr.data_ptr()
+        a.norm_scratch, a.norm_scratch_doubles = self.norm_scratch.data_ptr(), self.norm_scratch.numel()
+        a.beta1, a.beta2, a.adam_eps = 0.9, 0.999, 1e-5
+        a.grad_scale = 1.0 / self.world
+        a.max_norm = float(pol.gradient_clip) if pol.gradient_clip is not None else 0.0
+        a.obs, a.critic_obs = buf.observations.data_ptr(), buf.critic_observations.data_ptr()
+        a.terminal = ds.terminal_positions.data_ptr() if self.S > 1 else None
+        a.perm, a.row_map = self.perm.data_ptr(), ds.row_map.data_ptr()
+        a.n_rows, a.n_items = buf.num_transitions, self.perm.numel()
+        a.raw_actions, a.advantages = t["raw_actions"].data_ptr(), t["advantages"].data_ptr()
+        a.old_log_probs, a.rewards_to_go = t["log_probs"].data_ptr(), t["rewards_to_go"].data_ptr()
+        a.values = buf.values.data_ptr()
+        h = buf.hidden
+        a.actor_hidden, a.actor_cell = h["actor_hidden"].data_ptr(), h["actor_cell"].data_ptr()
+        a.critic_hidden, a.critic_cell = h["critic_hidden"].data_ptr(), h["critic_cell"].data_ptr()
+        a.cursor = self.cursor.data_ptr()
+        a.normalize_values, a.n_ranks = int(bool(ppo.normalize_values)), self.world
+        a.normalize_adv, a.use_huber = int(bool(ppo.normalize_adv)), int(bool(pol.use_huber_loss))
+        a.vn_mean, a.vn_var, a.vn_count = self.vn_mean.data_ptr(), self.vn_var.data_ptr(), self.vn_count.data_ptr()
+        a.vn_records = self.records.data_ptr() if self.records is not None else None
+        a.adv_records = self.adv_records.data_ptr() if self.adv_records is not None else None
+        a.surr_clip, a.entropy_weight = float(pol.surr_clip), float(pol.entropy_weight())
+        a.kl_loss_weight, a.huber_delta = float(pol.kl_loss_weight), 10.0
+        a.min_std = float(getattr(pol.actor.distribution, "min_std", 0.01))
+        a.loss_partials, a.totals = self.loss_partials.data_ptr(), self.totals.data_ptr()
+        a.workspace, a.workspace_floats = self.workspace.data_ptr(), self.workspace.numel()
+        why = K.lstm_update_refusal(a, pointers=True)
+        if why:
+            raise _lib.PpoafError(why)
+        return a
+
+    def _signature(self):
+        """Everything baked into captured launches; a change re-captures."""
+        pol, buf, ds = self.pol, self.pol.buffer, self.pol.dataset
+        return (buf.observations.data_ptr(), buf.critic_observations.data_ptr(), buf.values.data_ptr(), buf.num_transitions,
+                ds.row_map.data_ptr(), ds.terminal_positions.data_ptr() if self.S > 1 else 0, self.perm.data_ptr(),
+                self.perm.numel(), tuple(v.data_ptr() for v in self.tables.values()),
+                tuple(v.data_ptr() for v in buf.hidden.values()), pol.policy_params.data_ptr(), float(pol.lr()),
+                self.world) + _loss_signature(self)
+
+    # ----------------------------------------------------------------- epoch
+    def _epoch_inputs(self, N):
+        pol, ppo = self.pol, self.ppo
+        buf = pol.buffer
+        if self.perm_last is None or self.perm_last.numel() != N:
+            self.perm_last = torch.empty(N, dtype=torch.int64, device=pol.device)
+        torch.add(self.perm, self.S - 1, out=self.perm_last)          # every non-observation field: the window's last position
+        fields = dict(raw_actions=buf.raw_actions, advantages=buf.advantages, log_probs=buf.log_probs,
+                      rewards_to_go=buf.rewards_to_go)
+        flat = lambda x: x.view((buf.num_transitions,) + tuple(x.shape[2:]))
+        t = self.tables
+        if t is None or next(iter(t.values())).shape[0] != N:
+            t = self.tables = {k: torch.empty((N,) + tuple(v.shape[2:]), dtype=v.dtype, device=v.device) for k, v in fields.items()}
+            self._graphs.clear()
+            self._args = {}
+        K.minibatch_gather([(flat(v), t[k]) for k, v in fields.items()], self.perm_last, buf.row_map)
+        nb = (N + self.B - 1) // self.B
+        if ppo.normalize_values:
+            local = K.minibatch_moments(buf.rewards_to_go.view(-1), self.perm_last, buf.row_map, self.B)
+            if self.multi:
+                rec = mpi_utils.allgather_records(local.reshape(-1)).view(self.world, nb, 3).permute(1, 0, 2).contiguous()
+            else:
+                rec = local.view(nb, 1, 3)
+            if self.records is None or self.records.shape != rec.shape:
+                self.records = torch.empty_like(rec)
+                self._graphs.clear()
+            self.records.copy_(rec)
+            _seed_normaliser(self)
+        if ppo.normalize_adv:
+            if self.adv_records is None or self.adv_records.shape[0] != nb:
+                self.adv_records = torch.empty(nb, 3, dtype=torch.float64, device=pol.device)
+                self._graphs.clear()
+            K.minibatch_moments(buf.advantages.view(-1), self.perm_last, buf.row_map, self.B, out=self.adv_records)
+
+    def _epoch_state(self):
+        pol = self.pol
+        return [pol.policy_params, pol.policy_exp_avg, pol.policy_exp_avg_sq, pol.policy_step_counts, self.vn_mean, self.vn_var,
+                self.vn_count, pol.buffer.values] + list(pol.buffer.hidden.values())
+
+    _publish = _publish_normaliser
+
+    def gradient_only(self, args):
+        """fwd_bwd + wgrad of ONE mini-batch, no optimiser step: the gradient bucket tests compare.  (The wgrad launch
+        advances the Adam step counters as usual; the cursor stays.)"""
+        lib, st, ref = self._lib, K.stream(), C.byref(args)
+        _lib.check(lib.ppoaf_lstm_update_fwd_bwd(ref, st), "lstm_update_fwd_bwd")
+        _lib.check(lib.ppoaf_lstm_update_wgrad(ref, st), "lstm_update_wgrad")
+        FusedLstmUpdate.launches += 2
+
+    def _one(self, args):
+        """One mini-batch: 3 launches; on N > 1 the gradient exchange sits between wgrad and adam (K17: one launch that
+        also leaves both clip norms; else an all-reduce and a norm pass)."""
+        lib, st, ref = self._lib, K.stream(), C.byref(args)
+        rc = lib.ppoaf_lstm_update_fwd_bwd(ref, st) or lib.ppoaf_lstm_update_wgrad(ref, st)
+        n = 3
+        if rc == 0 and not self.multi:
+            rc = lib.ppoaf_lstm_update_adam(ref, 0, st)
+        elif rc == 0 and self.xchg is not None:
+            g = self.pol.policy_grads
+            self.xchg.allreduce(g, g, split_floats=self.actor_size, norm_scale=args.grad_scale, norm_out=self.norm_scratch,
+                                stream=st)
+            rc = lib.ppoaf_lstm_update_adam(ref, 2, st)
+            n = 4
+        elif rc == 0:
+            mpi_utils.allreduce_sum_(self.pol.policy_grads)
+            rc = lib.ppoaf_lstm_update_adam(ref, 1, st)
+            n = 4
+        FusedLstmUpdate.launches += n
+        if rc != 0:
+            _lib.check(rc, "lstm_update")
+
+    def _c_loop(self, args, n):
+        return False                   # (no C chain for this driver: the all-reduce fallback is the eager loop)
 
 
 class FusedPolicyUpdate(FusedEpoch):

@@ -858,3 +858,34 @@ def lstm_policy_infer(args, obs, actor_state, action_out, deterministic):
                                  torch.float32 if gauss else torch.int64)
     args.infer_mode = INFER_DETERMINISTIC if deterministic else INFER_SAMPLE
     _lstm_launch(args, LSTM_INFER)
+
+
+# --------------------------------------------------------------------------
+# K22: one mini-batch of an LSTM policy's PPO update (csrc/lstm_update.hip)
+# --------------------------------------------------------------------------
+def lstm_update_refusal(args, pointers=False):
+    """'' when ppoaf_lstm_update_check accepts the _lib.LstmUpdateArgs (host only: nothing is launched, no pointer is
+    followed; pointers=False: the shapes alone), else the library's reason."""
+    lib = _lib.load()
+    if lib.ppoaf_lstm_update_check(C.byref(args), 1 if pointers else 0) == 0:
+        return ""
+    return lib.ppoaf_last_error().decode("utf-8", "replace")
+
+
+def lstm_update_sizes(args):
+    """(workspace floats for args.B rows, norm_scratch doubles, LDS bytes of a fwd_bwd workgroup)."""
+    out = (C.c_int64 * 3)()
+    check(_lib.load().ppoaf_lstm_update_workspace_floats(C.byref(args), out), "lstm_update_workspace_floats")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def lstm_update_fwd_bwd(args):
+    check(_lib.load().ppoaf_lstm_update_fwd_bwd(C.byref(args), stream()), "lstm_update_fwd_bwd")
+
+
+def lstm_update_wgrad(args):
+    check(_lib.load().ppoaf_lstm_update_wgrad(C.byref(args), stream()), "lstm_update_wgrad")
+
+
+def lstm_update_adam(args, norm_mode=0):
+    check(_lib.load().ppoaf_lstm_update_adam(C.byref(args), int(norm_mode), stream()), "lstm_update_adam")

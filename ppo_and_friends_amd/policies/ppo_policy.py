@@ -137,6 +137,7 @@ class PPOPolicy:
         self.frozen = False
         self.fused_action_heads = False      # MultiDiscrete / MultiBinary heads on K6 / K12 (set by PPO(update_mode="fused"))
         self.fused_lstm_step = True          # K21 for the rollout / evaluation step of a covered LSTM policy
+        self.fused_lstm_update = True        # K22 for the update epoch of a covered LSTM policy (False: the mini-batch loop)
         self.random_seed = random_seed
         self.lr = _callable(lr)
         self.icm_lr = _callable(icm_lr)

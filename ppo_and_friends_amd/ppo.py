@@ -1032,6 +1032,8 @@ class PPO:
         if pol.agent_grouping:
             # K14 beside K15 on XCD halves has not been run or measured: the two epochs go in turn
             return False
+        if pol.using_lstm:
+            return False                                   # (K22 beside K14 likewise: an LSTM policy's ICM epoch stays as it was)
         fused = self._fused_updater(policy_id, self.batch_size if batch_size is None else batch_size)
         fused_icm = self._fused_icm_updater(policy_id)
         if fused is None or fused_icm is None:
@@ -1261,15 +1263,25 @@ class PPO:
         if self.update_mode == "torch" or self.device.type != "cuda":
             return None
         key = (policy_id, B)
-        if key not in self._fused and self.update_mode == "fused" and self.policies[policy_id].using_lstm \
-                and not self.policies[policy_id].agent_grouping:
-            # LSTM policies: the mini-batch loop drives them, every compute launch of it ours (K18 networks, distribution
-            # and loss kernels, FlatAdam); coverage was checked when the networks were switched to K18
-            from .fused_update import FusedLstm
-            why = FusedLstm.unsupported_reason(self.policies[policy_id])
-            if why:
-                raise NotImplementedError(f"update_mode='fused' but {why}")
-            self._fused[key] = None
+        pol = self.policies[policy_id]
+        if self.update_mode == "fused" and pol.using_lstm and not pol.agent_grouping:
+            # LSTM policies: K22 (FusedLstmUpdate) runs the epoch; `pol.fused_lstm_update = False` -- read at every epoch --
+            # or a shape K22 does not cover keeps the mini-batch loop, every compute launch of which is ours as well (K18
+            # networks, distribution and loss kernels, FlatAdam).  K18's coverage was checked when the networks were switched to it.
+            from .fused_update import FusedLstm, FusedLstmUpdate
+            if not getattr(pol, "fused_lstm_update", True):
+                self._say_lstm_update_path(policy_id, "the mini-batch loop (fused_lstm_update is switched off on this policy)")
+                return None
+            if key not in self._fused:
+                why = FusedLstm.unsupported_reason(pol)
+                if why:
+                    raise NotImplementedError(f"update_mode='fused' but {why}")
+                why = FusedLstmUpdate.unsupported_reason(pol, B)
+                self._fused[key] = None if why else FusedLstmUpdate(self, policy_id)
+            if self.verbose:
+                self._say_lstm_update_path(policy_id, "K22 (FusedLstmUpdate)" if self._fused[key] is not None else
+                                           f"the mini-batch loop ({FusedLstmUpdate.unsupported_reason(pol, B)})")
+            return self._fused[key]
         if key not in self._fused:
             from .fused_update import FusedMatUpdate, FusedPolicyUpdate
             driver = FusedMatUpdate if self.policies[policy_id].agent_grouping else FusedPolicyUpdate    # K15 / K12
@@ -1283,6 +1295,13 @@ class PPO:
             else:
                 self._fused[key] = driver(self, policy_id)
         return self._fused[key]
+
+    def _say_lstm_update_path(self, policy_id, path):
+        """verbose: which path an LSTM policy's update takes (once per change)."""
+        said = self.__dict__.setdefault("_lstm_update_said", {})
+        if self.verbose and said.get(policy_id) != path:
+            said[policy_id] = path
+            rank_print(f"policy {policy_id}: LSTM update on {path}")
 
     def _publish_epoch_stats(self, policy_id, t):
         """ppo.py:2471-2485: counters and sums across ranks, then per-mini-batch averages."""
