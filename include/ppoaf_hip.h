@@ -829,7 +829,8 @@ int ppoaf_icm_shapes_intrinsic_reward(const ppoaf_icm_shapes_args_t* args, float
  *          SelfAttention / Encoding / Decoding blocks             networks/attention.py:13-257
  *          the loss, backward and (through K11) the one clip + Adam over the shared bucket  mat_policy.py:677-699
  * for the default topology: embedding 64, one block, one head, GELU, Discrete actions (<= 8),
- * obs_dim <= 64, num_agents <= 16.  `offsets` are the 63 parameter tensors of MATActorCritic in
+ * obs_dim <= 128 (rows up to 32 wide are staged whole in LDS; wider ones stream through it in chunks of
+ * 32 columns, read from critic_obs again by the backward), num_agents <= 16.  `offsets` are the 63 parameter tensors of MATActorCritic in
  * module order (each padded to 4 floats) relative to `params`.  Dataset rows are envs carrying
  * num_agents tokens: critic_obs [n_rows, A, O], raw_actions int64 [n_rows, A], advantages /
  * old_log_probs / rewards_to_go / values [n_rows, A].  adv_records / vn_records are (n, mean, M2)
@@ -908,7 +909,7 @@ int ppoaf_mat_update_norm_partials(const ppoaf_mat_update_args_t* args);
  * encoder runs once, the decoder A times (agent i's sampled action is agent i+1's token).
  * Outputs are the step's row of the rollout buffer: actions int64 [E, A], log-probs and
  * (denormalised) values [E, A]; *_copy_out receive the observation rows (actor_obs [E, A,
- * actor_obs_dim], or critic_obs again when NULL).  offsets / limits as K15.
+ * actor_obs_dim], or critic_obs again when NULL).  offsets / limits as K15 (obs_dim <= 128).
  * ------------------------------------------------------------------------ */
 typedef struct {
     int32_t obs_dim, num_agents, num_actions, embedding, actor_obs_dim, normalize_values;
@@ -931,7 +932,7 @@ int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* args, ppoaf_stream_t stre
  *          _get_autoregressive_actions (sampled)                        mat_policy.py:441-519
  *          (the step of the evaluation loop                             testing.py:8-175)
  * The encoder runs once (up to rep_enc: no value), the decoder A times (agent i's env action is agent i+1's token);
- * only the int64 env actions are stored.  Shapes as K16; offsets as K15 (checked).  mode:
+ * only the int64 env actions are stored.  Shapes as K16, but obs_dim <= 64; offsets as K15 (checked).  mode:
  *   PPOAF_INFER_SAMPLE         K16's categorical draw with K16's Philox counter (offset + env * A + slot): for equal
  *                              (obs, params, seed, offset) in grouped layout the actions are bitwise
  *                              ppoaf_mat_policy_step's action_out

@@ -361,37 +361,47 @@ __device__ __forceinline__ void att_bwd(const float* Q, const float* K, const fl
 // ------------------------------------------------------------------------------------------------
 // narrow first layers (observation encoder K = O, action encoder K = Ain): weights [64, K] row-major
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void narrow_fwd(const float* __restrict__ W, int Kdim, const float* __restrict__ bias,
-                                           const float* __restrict__ X, int ldx, float* __restrict__ out, int wave, int lane) {
+// acc += X[:, 0 .. kend) . W[o, c0 .. c0 + kend)^T for the wave's 16 outputs o: X is a tile (stride ldx) whose column 0 is
+// input column c0 of W's rows (stride Kdim, zero beyond it); k ascends, so chunks called in order are the unchunked chain
+__device__ __forceinline__ void narrow_fwd_acc(const float* __restrict__ W, int Kdim, int c0, int kend,
+                                               const float* __restrict__ X, int ldx, f32x4& acc, int wave, int lane) {
     const int o = wave * 16 + (lane & 15);
-    const float bv = bias ? bias[o] : 0.f;
-    f32x4 acc = {bv, bv, bv, bv};
-    const float* w = W + (long)o * Kdim;
+    const float* w = W + (long)o * Kdim + c0;
     const float* arow = X + (lane & 15) * ldx;
-    for (int k0 = 0; k0 < Kdim; k0 += 16) {
+    for (int k0 = 0; k0 < kend; k0 += 16) {
         float bq[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { const int k = k0 + 4 * j + (lane >> 4); bq[j] = k < Kdim ? w[k] : 0.f; }
+        for (int j = 0; j < 4; ++j) { const int k = k0 + 4 * j + (lane >> 4); bq[j] = c0 + k < Kdim ? w[k] : 0.f; }
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[k0 + 4 * j + (lane >> 4)], bq[j], acc, 0, 0, 0);
     }
+}
+__device__ __forceinline__ void narrow_store(const f32x4& acc, float* __restrict__ out, int wave, int lane) {
+    const int o = wave * 16 + (lane & 15);
 #pragma unroll
     for (int r = 0; r < 4; ++r) out[(4 * (lane >> 4) + r) * kMHS + o] = acc[r];
 }
-// dX[16, Kdim] = D[16,64] . W[64, Kdim]  (tile stride ldx; columns >= Kdim untouched)
-__device__ __forceinline__ void narrow_dgrad(const float* __restrict__ W, int Kdim, const float* __restrict__ Dt,
+__device__ __forceinline__ void narrow_fwd(const float* __restrict__ W, int Kdim, const float* __restrict__ bias,
+                                           const float* __restrict__ X, int ldx, float* __restrict__ out, int wave, int lane) {
+    const float bv = bias ? bias[wave * 16 + (lane & 15)] : 0.f;
+    f32x4 acc = {bv, bv, bv, bv};
+    narrow_fwd_acc(W, Kdim, 0, Kdim, X, ldx, acc, wave, lane);
+    narrow_store(acc, out, wave, lane);
+}
+// dX[16, n] = D[16,64] . W[64, 0 .. n) for rows of W of stride ldw (tile stride ldx; columns >= n untouched)
+__device__ __forceinline__ void narrow_dgrad(const float* __restrict__ W, int ldw, int n, const float* __restrict__ Dt,
                                              float* __restrict__ dX, int ldx, int wave, int lane) {
-    for (int nt = wave; nt * 16 < Kdim; nt += kMNW) {
+    for (int nt = wave; nt * 16 < n; nt += kMNW) {
         const int i = nt * 16 + (lane & 15);
         float4 fr[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const float* wp = W + (long)(16 * c + 4 * (lane >> 4)) * Kdim + i;
-            fr[c] = i < Kdim ? make_float4(wp[0], wp[Kdim], wp[2 * Kdim], wp[3 * Kdim]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float* wp = W + (long)(16 * c + 4 * (lane >> 4)) * ldw + i;
+            fr[c] = i < n ? make_float4(wp[0], wp[ldw], wp[2 * ldw], wp[3 * ldw]) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
         const f32x4 acc = mfma_rows_x_frags<4>(Dt, kMHS, lane, fr, 0.f);
-        if (i < Kdim) {
+        if (i < n) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) dX[(4 * (lane >> 4) + r) * ldx + i] = acc[r];
         }
@@ -471,18 +481,26 @@ constexpr int mat_fwd_tile(int k) {
          : 9;                                                // y, x-hat; S4 / DENC exist only in the backward
 }
 
+// Observation widths: up to kMONarrow the rows are staged whole in LDS; wider ones (WIDE, up to kMOWide) stream through two
+// [16][kMOCS] chunk tiles of kMOC columns (mat_obs_encoder_wide), so the carve is that of a kMONarrow-wide launch plus the
+// [16] row means -- two whole [16][pad16(O) + 4] tiles beside the 34 activation tiles pass the CU's 160 KiB at O = 49.
+constexpr int kMONarrow = 32, kMOWide = 128;
+constexpr int kMOC = 32;           // columns of a chunk
+constexpr int kMOCS = kMOC + 4;    // row stride of a chunk tile
+
 // LDS carve shared by the update kernel (K15), the rollout step kernel (K16) and, with FWD, the evaluation step (K20)
-template <bool FWD>
+template <bool FWD, bool WIDE = false>
 struct MatCtxT {
+    static constexpr bool kWide = WIDE;
     const float* P; const long* off;
     int O, L, NA, Ain, OS, n_rows;
-    int* sRow; int* sAct; float* sMisc; float* sRowF; float* sRstd;
+    int* sRow; int* sAct; float* sMisc; float* sRowF; float* sRstd; float* sMean;
     float *sOutC, *sOutA, *sDOutC, *sDOutA, *sP0, *sP1, *sP2, *sS, *sXA, *sXO, *sYO, *T;
     __device__ __forceinline__ float* tile(int k) const { return T + (long)(FWD ? mat_fwd_tile(k) : k) * kMTile; }
     __device__ __forceinline__ float* rstd(int k) const { return sRstd + 16 * k; }
     __device__ __forceinline__ const float* W(int k) const { return P + off[k]; }
     __device__ __forceinline__ void carve(float* sm, int O_) {
-        O = O_; OS = 16 * ((O_ + 15) >> 4) + 4;
+        O = O_; OS = WIDE ? kMOCS : 16 * ((O_ + 15) >> 4) + 4;
         sRow = reinterpret_cast<int*>(sm);                 // [16] buffer row of the token's env (-1: padding)
         sAct = reinterpret_cast<int*>(sm) + 16;            // [16] action of the token
         sMisc = sm + 32;                                   // [8] adv mean/std, vn mean/var
@@ -495,8 +513,10 @@ struct MatCtxT {
             sP0 = sP1 = sP2 = sS = sOutA + 128;            // one probability tile [16][17]: the attentions run one at a time
             sXA = sP0 + 272;                               // [16][kMXS] action tokens
             sYO = sXA + kRows * kMXS;                      // [16][OS] observations, then the observation LayerNorm's output
-            T = sYO + kRows * OS;
-            sXO = tile(cY_);                               // its x-hat: unread (OS <= kMHS, so it fits the tile)
+            sMean = sYO + kRows * OS;                      // WIDE: [16] row means
+            T = sMean + (WIDE ? kRows : 0);
+            sXO = tile(cY_);                               // its x-hat: unread (OS <= kMHS, so it fits the tile); WIDE: the
+                                                           // second chunk tile
         } else {
             sDOutC = sOutA + 128;
             sDOutA = sDOutC + 128;
@@ -507,7 +527,8 @@ struct MatCtxT {
             sXA = sS + 272;                                // [16][kMXS] action tokens
             sXO = sXA + kRows * kMXS;                      // [16][OS] xhat of the observation LayerNorm
             sYO = sXO + kRows * OS;                        // [16][OS] its output (input of the encoder linear)
-            T = sYO + kRows * OS;                          // [16][68] tiles from here on
+            sMean = sYO + kRows * OS;                      // WIDE (sXO / sYO are the two chunk tiles): [16] row means
+            T = sMean + (WIDE ? kRows : 0);                // [16][68] tiles from here on
         }
     }
 };
@@ -544,21 +565,68 @@ struct MatPanelPub {
     __device__ __forceinline__ void operator()(int xid, const float* T) const { publish_tile(T, xpanel + (long)xid * plane, g, tid); }
 };
 
-// critic (encoder): observations in sYO -> rep_enc in cENC, value in sOutC[:, 0]; ends WITHOUT a barrier
+// obs_encoder.0 + obs_encoder.1 of a WIDE carve: LayerNorm(O) -> Linear(O, 64) pre-GELU values -> `out`, no barrier after.
+// Thread (row = tid >> 4, l = tid & 15) holds columns l + 16 j of its row, read from global memory (orow: the token's
+// observation row, nullptr for a padding row -- read as zeros, as the staged form's zeroed tile); mean and rstd by
+// tile_ln_fwd's two-pass arithmetic, both kept for the backward.  Then per chunk of kMOC columns: y = xhat g + b into one of
+// the two chunk tiles (alternating: one barrier per chunk), accumulated into the wave's MFMA chain with k ascending.
+template <typename Ctx>
+__device__ __forceinline__ void mat_obs_encoder_wide(const Ctx& c, const float* __restrict__ orow, float* __restrict__ out,
+                                                     int tid, int wave, int lane) {
+    const int O = c.O, row = tid >> 4, l = tid & 15;
+    const float* __restrict__ g = c.W(C_OLN_G);
+    const float* __restrict__ b = c.W(C_OLN_B);
+    constexpr int NJ = kMOWide / 16;
+    float x[NJ], s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { const int col = l + 16 * j; x[j] = (orow && col < O) ? orow[col] : 0.f; s += x[j]; }
+    const float mean = group16_sum(s) / (float)O;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { const int col = l + 16 * j; x[j] = col < O ? x[j] - mean : 0.f; q += x[j] * x[j]; }
+    const float rs = 1.0f / sqrtf(group16_sum(q) / (float)O + 1e-5f);
+    if (l == 0) { c.rstd(0)[row] = rs; c.sMean[row] = mean; }
+    const float bv = c.W(C_ENC_B)[wave * 16 + (lane & 15)];
+    f32x4 acc = {bv, bv, bv, bv};
+#pragma unroll
+    for (int ci = 0; ci < kMOWide / kMOC; ++ci) {
+        const int c0 = kMOC * ci;
+        if (c0 < O) {                                                  // uniform: every thread meets the barrier
+            float* Y = (ci & 1) ? c.sXO : c.sYO;
+#pragma unroll
+            for (int jj = 0; jj < kMOC / 16; ++jj) {
+                const int col = c0 + l + 16 * jj;
+                Y[row * kMOCS + l + 16 * jj] = col < O ? x[(kMOC / 16) * ci + jj] * rs * g[col] + b[col] : 0.f;
+            }
+            MAT_SYNC();
+            const int cw = O - c0 < kMOC ? O - c0 : kMOC;
+            narrow_fwd_acc(c.W(C_ENC_W), O, c0, 16 * ((cw + 15) >> 4), Y, kMOCS, acc, wave, lane);
+        }
+    }
+    narrow_store(acc, out, wave, lane);
+}
+
+// critic (encoder): observations in sYO (a WIDE carve: read through orow) -> rep_enc in cENC, value in sOutC[:, 0]; ends
+// WITHOUT a barrier
 // PF (K15): the fragments of linear `n` are requested one phase ahead -- MAT_NEXT(n) at the start of the phase before;
 // else (K16: its registers are spoken for) at the point of use
 #define MAT_LIN(r, Wk, Bk, A, out) do { if (!PF) pf_fwd(W(Wk), W(Bk), wave, lane, r); lin_fwd_r(r, A, out, wave, lane); } while (0)
 #define MAT_NEXT(r, Wk, Bk) do { if (PF) pf_fwd(W(Wk), W(Bk), wave, lane, r); } while (0)
 // VALUE = false (K20): stops at rep_enc, after a barrier -- the three phases of the value head are not run
 template <bool PF, typename Pub = MatNoPub, bool VALUE = true, typename Ctx = MatCtx>
-__device__ __forceinline__ void mat_encoder_forward(const Ctx& c, int tid, int wave, int lane, const Pub pub = Pub()) {
+__device__ __forceinline__ void mat_encoder_forward(const Ctx& c, int tid, int wave, int lane, const Pub pub = Pub(),
+                                                    const float* orow = nullptr) {
     MAT_TILES(c);
     MatFr rq, rk, rv, rp, rm1, rm2, rh1;
     MAT_NEXT(rq, C_Q_W, C_Q_B); MAT_NEXT(rk, C_K_W, C_K_B); MAT_NEXT(rv, C_V_W, C_V_B);       // two phases ahead of their use
-    tile_ln_fwd(sYO, OS, O, W(C_OLN_G), W(C_OLN_B), sXO, rstd(0), sYO, tid);                 // obs_encoder.0
-    MAT_SYNC();
-    MAT_STAMP(16);
-    narrow_fwd(W(C_ENC_W), O, W(C_ENC_B), sYO, OS, cZ1, wave, lane);                          // obs_encoder.1
+    if constexpr (Ctx::kWide) {
+        mat_obs_encoder_wide(c, orow, cZ1, tid, wave, lane);                                  // obs_encoder.0 and .1
+    } else {
+        tile_ln_fwd(sYO, OS, O, W(C_OLN_G), W(C_OLN_B), sXO, rstd(0), sYO, tid);              // obs_encoder.0
+        MAT_SYNC();
+        MAT_STAMP(16);
+        narrow_fwd(W(C_ENC_W), O, W(C_ENC_B), sYO, OS, cZ1, wave, lane);                      // obs_encoder.1
+    }
     MAT_SYNC();
     MAT_STAMP(17);
     tile_gelu(cZ1, S0, tid);
@@ -690,11 +758,11 @@ __device__ __forceinline__ void mat_decoder_forward(const Ctx& c, int tid, int w
     } while (0)
 // slab form only: an input tile rebuilt for a weight gradient (and the barrier that settles it)
 #define MAT_SLAB_ONLY(stmt) do { if constexpr (!SPLIT) { stmt; } } while (0)
-template <bool SPLIT>
-__global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_kernel(MatDev u) {
+// WIDE: the chunked observation front end (33 <= O <= kMOWide); the kernels of the two forms keep names of their own
+template <bool SPLIT, bool WIDE>
+__device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = blockIdx.x;
-    const int NT0 = (u.O + 15) >> 4;
     const float* P = u.params;
     float* slab = u.slabs + (long)g * u.slab_stride;
     const long mb = u.cursor[0] + u.mb_offset;
@@ -705,13 +773,19 @@ __global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_kernel(MatDev u) {
 
     MAT_STAMP(0);
     // ---- LDS carve
-    MatCtx c;
+    MatCtxT<false, WIDE> c;
     c.P = P; c.off = u.off; c.L = u.L; c.NA = u.NA; c.Ain = u.Ain; c.n_rows = n_seq * u.L;
     c.carve(reinterpret_cast<float*>(mat_smem), u.O);
     MAT_TILES(c);
     int* sRow = c.sRow; int* sAct = c.sAct; float* sMisc = c.sMisc; float* sRowF = c.sRowF;
     float* sDOutC = c.sDOutC; float* sDOutA = c.sDOutA;
     auto G = [&](int k) -> float* { return slab + u.goff[k]; };
+    // the observation row of token row s (once sRow is settled; nullptr: padding), in both addressing forms
+    auto obs_row = [&](int s) -> const float* {
+        if (s >= n_rows || sRow[s] < 0) return nullptr;
+        const long orow = u.pregathered ? mb * u.batch_stride + seq0 + s / L : (long)sRow[s];
+        return u.obs + (orow * L + (s % L)) * O;
+    };
 
     // ---- rows, per-token scalars, mini-batch statistics
     if (tid < kRows) {
@@ -781,11 +855,14 @@ __global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_kernel(MatDev u) {
         sMisc[2] = m; sMisc[3] = v;
         if (g == 0) { u.vn_mean[slot ^ 1] = m; u.vn_var[slot ^ 1] = v; u.vn_count[slot ^ 1] = cnt; }
     }
-    for (int i = tid; i < kRows * OS; i += kMT) { sXO[i] = 0.f; sYO[i] = 0.f; }
+    if constexpr (!WIDE)
+        for (int i = tid; i < kRows * OS; i += kMT) { sXO[i] = 0.f; sYO[i] = 0.f; }
     for (int i = tid; i < kRows * kMXS; i += kMT) sXA[i] = 0.f;
     MAT_SYNC();
     MAT_STAMP(1);
-    // observations of the tile's tokens; the shifted one-hot token block (mat_policy.py:308-344,378-416)
+    // observations of the tile's tokens (WIDE: the encoder reads them from global memory); the shifted one-hot token
+    // block (mat_policy.py:308-344,378-416)
+    if constexpr (!WIDE)
     for (int idx = tid; idx < n_rows * O; idx += kMT) {
         const int s = idx / O, i = idx - s * O;
         const int row = sRow[s];
@@ -800,13 +877,14 @@ __global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_kernel(MatDev u) {
     MAT_SYNC();
     MAT_STAMP(2);
 
+    const float* orow0 = WIDE ? obs_row(tid >> 4) : nullptr;
     if constexpr (SPLIT) {
         const MatPanelPub pub{u.xpanel, (long)u.R * kMD, g, tid};
-        mat_encoder_forward<true>(c, tid, wave, lane, pub);
+        mat_encoder_forward<true>(c, tid, wave, lane, pub, orow0);
         MAT_STAMP(3);
         mat_decoder_forward<true>(c, tid, wave, lane, pub);
     } else {
-        mat_encoder_forward<true>(c, tid, wave, lane);
+        mat_encoder_forward<true>(c, tid, wave, lane, MatNoPub(), orow0);
         MAT_STAMP(3);
         mat_decoder_forward<true>(c, tid, wave, lane);
     }
@@ -1017,28 +1095,54 @@ __global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_kernel(MatDev u) {
     tile_ln_bwd(S0, kMHS, kMD, cN0, rstd(1), W(C_LN_G), S1, G(C_LN_G), G(C_LN_B), tid);
     tile_gelu_bwd(S1, cZ1, tid);
     MAT_SYNC();
-    layer_wgrad<4, kMNW>(S1, sYO, OS, NT0, O, G(C_ENC_W), O, G(C_ENC_B), wave, lane, tid);
-    narrow_dgrad(W(C_ENC_W), O, S1, S2, kMHS, wave, lane);                                     // d (obs LayerNorm output) in S2[:, :O]
-    MAT_SYNC();
-    MAT_STAMP(9);
-    // observation LayerNorm: only its affine parameters receive gradient
-    if (tid < 64) {
-        if (tid < O) {
-            float a = 0.f;
+    // obs_encoder.1's weight gradient, then the observation LayerNorm, of which only the affine parameters receive
+    // gradient: columns [c0, c0 + cw) at a time.  The staged form has y in sYO and x-hat in sXO and takes all O at once;
+    // WIDE rebuilds both for a chunk from the (L2-resident) observation row and the saved mean / rstd.
+    const float* orow = WIDE ? obs_row(tid >> 4) : nullptr;
+    for (int c0 = 0; c0 < O; c0 += kMOC) {
+        const int cw = !WIDE ? O : (O - c0 < kMOC ? O - c0 : kMOC);
+        if constexpr (WIDE) {
+            const int row = tid >> 4, l = tid & 15;
+            const float mean = c.sMean[row], rs = rstd(0)[row];
 #pragma unroll
-            for (int s = 0; s < kRows; ++s) a = fmaf(S2[s * kMHS + tid], sXO[s * OS + tid], a);
-            G(C_OLN_G)[tid] = a;
+            for (int jj = 0; jj < kMOC / 16; ++jj) {
+                const int col = c0 + l + 16 * jj;
+                const float xv = (orow && col < O) ? orow[col] : 0.f;
+                const float xh = col < O ? (xv - mean) * rs : 0.f;
+                sXO[row * OS + l + 16 * jj] = xh;
+                sYO[row * OS + l + 16 * jj] = col < O ? xh * W(C_OLN_G)[col] + W(C_OLN_B)[col] : 0.f;
+            }
+            MAT_SYNC();
         }
-    } else if (tid < 128) {
-        const int c = tid - 64;
-        if (c < O) {
-            float a = 0.f;
+        layer_wgrad<4, kMNW>(S1, sYO, OS, (cw + 15) >> 4, cw, G(C_ENC_W) + c0, O, c0 == 0 ? G(C_ENC_B) : nullptr, wave, lane, tid);
+        narrow_dgrad(W(C_ENC_W) + c0, O, cw, S1, S2, kMHS, wave, lane);                        // d (obs LayerNorm output) in S2[:, :cw]
+        MAT_SYNC();
+        MAT_STAMP(9);
+        if (tid < 64) {
+            if (tid < cw) {
+                float a = 0.f;
 #pragma unroll
-            for (int s = 0; s < kRows; ++s) a += S2[s * kMHS + c];
-            G(C_OLN_B)[c] = a;
+                for (int s = 0; s < kRows; ++s) a = fmaf(S2[s * kMHS + tid], sXO[s * OS + tid], a);
+                G(C_OLN_G)[c0 + tid] = a;
+            }
+        } else if (tid < 128) {
+            const int cc = tid - 64;
+            if (cc < cw) {
+                float a = 0.f;
+#pragma unroll
+                for (int s = 0; s < kRows; ++s) a += S2[s * kMHS + cc];
+                G(C_OLN_B)[c0 + cc] = a;
+            }
         }
+        if constexpr (!WIDE) break;
+        MAT_SYNC();                                                    // the chunk tiles and S2 are rewritten
     }
 }
+
+template <bool SPLIT>
+__global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_kernel(MatDev u) { mat_update_fwd_bwd_body<SPLIT, false>(u); }
+template <bool SPLIT>
+__global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_wide_kernel(MatDev u) { mat_update_fwd_bwd_body<SPLIT, true>(u); }
 
 // ------------------------------------------------------------------------------------------------
 // K16: one rollout step of a MATPolicy for all envs of the rank (mat_policy.py:441-519,587-626,660-675):
@@ -1058,24 +1162,26 @@ struct MatStepDev {
     const int64_t* forced_action;                  // NULL: sample; else [E, L] actions to log (replay)
 };
 
-__global__ __launch_bounds__(kMT) void mat_policy_step_kernel(MatStepDev u) {
+template <bool WIDE>
+__device__ __forceinline__ void mat_policy_step_body(const MatStepDev u) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long seq0 = (long)blockIdx.x * u.per_tile;
     const long rem = u.E - seq0;
     const int n_seq = (int)(rem < u.per_tile ? (rem < 0 ? 0 : rem) : u.per_tile);
-    MatCtx c;
+    MatCtxT<false, WIDE> c;
     c.P = u.params; c.off = u.off; c.L = u.L; c.NA = u.NA; c.Ain = u.Ain; c.n_rows = n_seq * u.L;
     c.carve(reinterpret_cast<float*>(mat_smem), u.O);
     MAT_TILES(c);
     int* sAct = c.sAct;
-    for (int i = tid; i < kRows * OS; i += kMT) { sXO[i] = 0.f; sYO[i] = 0.f; }
+    if constexpr (!WIDE)
+        for (int i = tid; i < kRows * OS; i += kMT) { sXO[i] = 0.f; sYO[i] = 0.f; }
     for (int i = tid; i < kRows * kMXS; i += kMT) sXA[i] = 0.f;
     MAT_SYNC();
     const long tok0 = seq0 * L;                                  // first token (env-major, agents inside)
     for (int idx = tid; idx < n_rows * O; idx += kMT) {
         const int s = idx / O, i = idx - s * O;
         const float v = u.obs[(tok0 + s) * O + i];
-        sYO[s * OS + i] = v;
+        if constexpr (!WIDE) sYO[s * OS + i] = v;                 // (WIDE: the encoder reads the rows from global memory)
         if (u.critic_obs_out) u.critic_obs_out[(tok0 + s) * O + i] = v;
     }
     if (u.obs_out) {
@@ -1084,7 +1190,8 @@ __global__ __launch_bounds__(kMT) void mat_policy_step_kernel(MatStepDev u) {
     }
     if (tid < n_rows && tid % L == 0) sXA[tid * kMXS] = 1.0f;     // start token of agent 0 (mat_policy.py:325-333)
     MAT_SYNC();
-    mat_encoder_forward<false>(c, tid, wave, lane);
+    mat_encoder_forward<false>(c, tid, wave, lane, MatNoPub(),
+                               (WIDE && (tid >> 4) < n_rows) ? u.obs + (tok0 + (tid >> 4)) * O : nullptr);
     MAT_SYNC();
     if (tid < n_rows) {
         float v = sOutC[tid * 8];
@@ -1134,6 +1241,9 @@ __global__ __launch_bounds__(kMT) void mat_policy_step_kernel(MatStepDev u) {
     }
 }
 
+__global__ __launch_bounds__(kMT) void mat_policy_step_kernel(MatStepDev u) { mat_policy_step_body<false>(u); }
+__global__ __launch_bounds__(kMT) void mat_policy_step_wide_kernel(MatStepDev u) { mat_policy_step_body<true>(u); }
+
 // ------------------------------------------------------------------------------------------------
 // K20: one evaluation step of a MATPolicy for all envs in one launch (mat_policy.py:701-790 over :521-585 greedy and
 // :441-519 sampled): the encoder up to rep_enc, then L decoder passes -- agent i's env action, the argmax of pass i's
@@ -1162,28 +1272,34 @@ struct MatInferDev {
 constexpr bool kInferCompact = !(PPOAF_MAT_INFER_VARIANT & 1);
 constexpr bool kInferValue = (PPOAF_MAT_INFER_VARIANT & 2) != 0;
 
-template <bool COMPACT, bool VALUE>
-__global__ __launch_bounds__(kMT) void mat_policy_infer_kernel(MatInferDev u) {
+template <bool COMPACT, bool VALUE, bool WIDE>
+__device__ __forceinline__ void mat_policy_infer_body(const MatInferDev u) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long seq0 = (long)blockIdx.x * u.per_tile;
     const long rem = u.E - seq0;
     const int n_seq = (int)(rem < u.per_tile ? (rem < 0 ? 0 : rem) : u.per_tile);
-    MatCtxT<COMPACT> c;
+    MatCtxT<COMPACT, WIDE> c;
     c.P = u.params; c.off = u.off; c.L = u.L; c.NA = u.NA; c.Ain = u.Ain; c.n_rows = n_seq * u.L;
     c.carve(reinterpret_cast<float*>(mat_smem), u.O);
     MAT_TILES(c);
-    for (int i = tid; i < kRows * OS; i += kMT) sYO[i] = 0.f;
-    for (int i = tid; i < kRows * kMXS; i += kMT) sXA[i] = 0.f;
-    MAT_SYNC();
-    for (int idx = tid; idx < n_rows * O; idx += kMT) {
-        const int s = idx / O, i = idx - s * O;
+    auto obs_row = [&](int s) -> const float* {
         const int q = s / L;
         const long row = (long)u.slot_agent[s - q * L] * u.obs_agent_stride + (seq0 + q) * u.obs_env_stride;
-        sYO[s * OS + i] = u.obs[row * O + i];
+        return u.obs + row * O;
+    };
+    if constexpr (!WIDE)
+        for (int i = tid; i < kRows * OS; i += kMT) sYO[i] = 0.f;
+    for (int i = tid; i < kRows * kMXS; i += kMT) sXA[i] = 0.f;
+    MAT_SYNC();
+    if constexpr (!WIDE)
+    for (int idx = tid; idx < n_rows * O; idx += kMT) {
+        const int s = idx / O, i = idx - s * O;
+        sYO[s * OS + i] = obs_row(s)[i];
     }
     if (tid < n_rows && tid % L == 0) sXA[tid * kMXS] = 1.0f;     // start token of agent 0 (mat_policy.py:325-333)
     MAT_SYNC();
-    mat_encoder_forward<false, MatNoPub, VALUE>(c, tid, wave, lane);
+    mat_encoder_forward<false, MatNoPub, VALUE>(c, tid, wave, lane, MatNoPub(),
+                                                (WIDE && (tid >> 4) < n_rows) ? obs_row(tid >> 4) : nullptr);
     MAT_SYNC();
     const long tok0 = seq0 * L;                                  // K16's Philox counter: offset + env * L + slot
     for (int i = 0; i < L; ++i) {
@@ -1228,6 +1344,11 @@ __global__ __launch_bounds__(kMT) void mat_policy_infer_kernel(MatInferDev u) {
         MAT_SYNC();
     }
 }
+
+template <bool COMPACT, bool VALUE>
+__global__ __launch_bounds__(kMT) void mat_policy_infer_kernel(MatInferDev u) { mat_policy_infer_body<COMPACT, VALUE, false>(u); }
+template <bool COMPACT, bool VALUE>
+__global__ __launch_bounds__(kMT) void mat_policy_infer_wide_kernel(MatInferDev u) { mat_policy_infer_body<COMPACT, VALUE, true>(u); }
 
 // slabs -> gradient bucket in a fixed order (each thread owns a float4 column, 8 slab loads in flight at a
 // time, no LDS staging); the last workgroup folds the loss partials and advances the cursor
@@ -1489,9 +1610,14 @@ __global__ __launch_bounds__(256) void mat_update_wgrad_adam_kernel(MatDev u, in
     mat_wgrad_body<true>(u, n_small_blocks, ad, td, s_red, s_fold, s_tile, s_coef);
 }
 
+// the observation part of a carve: two (K20's compact carve: one) [16][OS] tiles; a wide launch has OS = kMOCS and [16] means
+static bool mat_is_wide(int O) { return O > kMONarrow; }
+static size_t mat_obs_lds_floats(int O, int n_tiles) {
+    const size_t OS = mat_is_wide(O) ? kMOCS : 16 * ((O + 15) / 16) + 4;
+    return n_tiles * kRows * OS + (mat_is_wide(O) ? kRows : 0);
+}
 static size_t mat_lds_bytes(int O) {
-    const size_t OS = 16 * ((O + 15) / 16) + 4;
-    return (256 + 4 * 128 + 4 * 272 + kRows * kMXS + 2 * kRows * OS + 34 * (size_t)kMTile) * 4;
+    return (256 + 4 * 128 + 4 * 272 + kRows * kMXS + mat_obs_lds_floats(O, 2) + 34 * (size_t)kMTile) * 4;
 }
 
 // the offset table of MATActorCritic's parameters in module order, every tensor padded to 4 floats -> want[]; returns the
@@ -1518,15 +1644,14 @@ static long mat_offset_table(long O, long NA, long* want) {
 }
 
 static size_t mat_fwd_lds_bytes(int O) {
-    const size_t OS = 16 * ((O + 15) / 16) + 4;
-    return (256 + 2 * 128 + 272 + kRows * kMXS + kRows * OS + kMatFwdTiles * (size_t)kMTile) * 4;
+    return (256 + 2 * 128 + 272 + kRows * kMXS + mat_obs_lds_floats(O, 1) + kMatFwdTiles * (size_t)kMTile) * 4;
 }
 
 static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u) {
     PPOAF_REQUIRE(a, "mat_update: null args");
     PPOAF_REQUIRE(a->embedding == kMD, "mat_update: embedding=%d (the fused kernel is built for 64)", a->embedding);
     PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16, "mat_update: num_agents=%d out of [1,16]", a->num_agents);
-    PPOAF_REQUIRE(a->obs_dim >= 1 && a->obs_dim <= 64, "mat_update: obs_dim=%d out of [1,64]", a->obs_dim);
+    PPOAF_REQUIRE(a->obs_dim >= 1 && a->obs_dim <= kMOWide, "mat_update: obs_dim=%d out of [1,%d]", a->obs_dim, kMOWide);
     PPOAF_REQUIRE(a->num_actions >= 1 && a->num_actions <= 8, "mat_update: num_actions=%d out of [1,8]", a->num_actions);
     PPOAF_REQUIRE(a->B >= 1 && a->batch_stride >= a->B, "mat_update: B=%ld stride=%ld", (long)a->B, (long)a->batch_stride);
     PPOAF_REQUIRE(a->params && a->grads && a->slabs && a->critic_obs && a->raw_actions && a->advantages &&
@@ -1618,25 +1743,23 @@ extern "C" int ppoaf_mat_update_fwd_bwd_timed(const ppoaf_mat_update_args_t* arg
     if (rc) return rc;
     const size_t lds = mat_lds_bytes(u.O);
     PPOAF_REQUIRE(lds <= 160 * 1024, "mat_update: needs %zu B of LDS (> 160 KiB)", lds);
+    // [split][wide]
+    static void (*const kern[2][2])(MatDev) = {{mat_update_fwd_bwd_kernel<false>, mat_update_fwd_bwd_wide_kernel<false>},
+                                               {mat_update_fwd_bwd_kernel<true>, mat_update_fwd_bwd_wide_kernel<true>}};
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mat_update_fwd_bwd_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(mat_update_fwd_bwd_kernel<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+        for (int i = 0; i < 4; ++i) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern[i >> 1][i & 1]),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+        }
         attr_set = true;
     }
     const dim3 grid((unsigned)u.nT), block(kMT);
     hipStream_t st = (hipStream_t)stream;
-    if (u.split) {
-        if (e0 || e1) hipExtLaunchKernelGGL(mat_update_fwd_bwd_kernel<true>, grid, block, lds, st, e0, e1, 0, u);
-        else hipLaunchKernelGGL(mat_update_fwd_bwd_kernel<true>, grid, block, lds, st, u);
-    } else {
-        if (e0 || e1) hipExtLaunchKernelGGL(mat_update_fwd_bwd_kernel<false>, grid, block, lds, st, e0, e1, 0, u);
-        else hipLaunchKernelGGL(mat_update_fwd_bwd_kernel<false>, grid, block, lds, st, u);
-    }
+    const auto fn = kern[u.split ? 1 : 0][mat_is_wide(u.O) ? 1 : 0];
+    if (e0 || e1) hipExtLaunchKernelGGL(fn, grid, block, lds, st, e0, e1, 0, u);
+    else hipLaunchKernelGGL(fn, grid, block, lds, st, u);
     return check_launch("mat_update_fwd_bwd");
 }
 
@@ -1714,9 +1837,10 @@ extern "C" int ppoaf_mat_update_norm_partials(const ppoaf_mat_update_args_t* arg
 extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_stream_t stream) {
     PPOAF_REQUIRE(a, "mat_policy_step: null args");
     PPOAF_REQUIRE(a->embedding == kMD, "mat_policy_step: embedding=%d (built for 64)", a->embedding);
-    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= 64 &&
+    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= kMOWide &&
                       a->num_actions >= 1 && a->num_actions <= 8 && a->actor_obs_dim >= 1,
-                  "mat_policy_step: sizes (agents %d, obs %d, actions %d)", a->num_agents, a->obs_dim, a->num_actions);
+                  "mat_policy_step: sizes (agents %d, obs %d, actions %d) outside the kernel's limits (16, %d, 8)", a->num_agents,
+                  a->obs_dim, a->num_actions, kMOWide);
     PPOAF_REQUIRE(a->E >= 1, "mat_policy_step: E=%ld", (long)a->E);
     PPOAF_REQUIRE(a->params && a->critic_obs && a->action_out && a->logp_out && a->value_out, "mat_policy_step: null pointer");
     PPOAF_REQUIRE(!a->normalize_values || (a->vn_mean && a->vn_var), "mat_policy_step: value normaliser statistics missing");
@@ -1733,16 +1857,19 @@ extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_strea
     u.forced_action = a->forced_action;
     const size_t lds = mat_lds_bytes(u.O);
     PPOAF_REQUIRE(lds <= 160 * 1024, "mat_policy_step: needs %zu B of LDS (> 160 KiB)", lds);
+    static void (*const kern[2])(MatStepDev) = {mat_policy_step_kernel, mat_policy_step_wide_kernel};
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mat_policy_step_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+        for (int i = 0; i < 2; ++i) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern[i]),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+        }
         attr_set = true;
     }
     const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
     PPOAF_REQUIRE(n_wg <= 0x7fffffffL, "mat_policy_step: too many envs");
-    hipLaunchKernelGGL(mat_policy_step_kernel, dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
+    hipLaunchKernelGGL(kern[mat_is_wide(u.O) ? 1 : 0], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
     return check_launch("mat_policy_step");
 }
 
@@ -1806,16 +1933,19 @@ extern "C" int ppoaf_mat_policy_infer(const ppoaf_mat_infer_args_t* a, ppoaf_str
     for (int i = 0; i < 16; ++i) u.slot_agent[i] = (unsigned char)(i < u.L ? a->slot_agent[i] : 0);
     const size_t lds = kInferCompact ? mat_fwd_lds_bytes(u.O) : mat_lds_bytes(u.O);
     PPOAF_REQUIRE(lds <= 160 * 1024, "mat_policy_infer: needs %zu B of LDS (> 160 KiB)", lds);
-    const void* fn = reinterpret_cast<const void*>(mat_policy_infer_kernel<kInferCompact, kInferValue>);
-    static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    // 33 <= obs_dim <= 64 takes K16's chunked front end, so the sampled actions stay operation for operation K16's
+    static void (*const kern[2])(MatInferDev) = {mat_policy_infer_kernel<kInferCompact, kInferValue>,
+                                                 mat_policy_infer_wide_kernel<kInferCompact, kInferValue>};
+    const int wide = mat_is_wide(u.O) ? 1 : 0;
+    static bool attr_set[2] = {false, false};
+    if (!attr_set[wide] && lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern[wide]),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
+        attr_set[wide] = true;
     }
     const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
-    hipLaunchKernelGGL((mat_policy_infer_kernel<kInferCompact, kInferValue>), dim3((unsigned)n_wg), dim3(kMT), lds,
-                       (hipStream_t)stream, u);
+    hipLaunchKernelGGL(kern[wide], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
     return check_launch("mat_policy_infer");
 }
 

@@ -1438,6 +1438,12 @@ _MAT_PARAM_NAMES = (
     + [f"critic.head.{i}.{p}" for i in (0, 2, 3) for p in ("weight", "bias")])
 
 
+# per-agent observation widths of the MAT kernels (csrc/mat_update.hip): K15 and K16 stream rows wider than 32 through LDS in
+# column chunks, up to 128; K20's entry point stops at 64
+MAT_MAX_OBS = 128
+MAT_INFER_MAX_OBS = 64
+
+
 def _describe_mat(pol):
     """Topology + offset table of a MATPolicy's actor_critic for K15, or (None, reason)."""
     from .networks.multi_agent_transformer import MATActorCritic
@@ -1462,8 +1468,8 @@ def _describe_mat(pol):
     if [n for n, _ in named] != _MAT_PARAM_NAMES:
         return None, "parameter list differs from the default MATActorCritic"
     NA, O, A = ac.actor.action_pred_size, ac.critic.in_size, ac.actor.num_agents
-    if not (1 <= NA <= 8 and 1 <= O <= 32 and 1 <= A <= 16):
-        return None, f"sizes (actions {NA}, obs {O}, agents {A}) outside the fused kernel's limits (8, 32, 16)"
+    if not (1 <= NA <= 8 and 1 <= O <= MAT_MAX_OBS and 1 <= A <= 16):
+        return None, f"sizes (actions {NA}, obs {O}, agents {A}) outside the fused kernel's limits (8, {MAT_MAX_OBS}, 16)"
     if ac.actor.action_encoder[0].in_features != NA + 1 or ac.actor.action_encoder[0].bias is not None:
         return None, "action encoder is not the Discrete (start token + one-hot, no bias) form"
     base = ac.flat_params.data_ptr()

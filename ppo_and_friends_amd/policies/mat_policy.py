@@ -299,7 +299,11 @@ class MATPolicy(PPOPolicy):
         # (asked once per evaluation step: the answer is kept for as long as the parameter bucket stays)
         key = self.policy_params.data_ptr()
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
-            self._infer_reason = (key, self.fused_step_unsupported_reason())
+            from ..fused_update import MAT_INFER_MAX_OBS
+            why, O = self.fused_step_unsupported_reason(), self.critic.in_size
+            if not why and O > MAT_INFER_MAX_OBS:
+                why = f"observations {O} wide: the K20 evaluation step takes up to {MAT_INFER_MAX_OBS} (K15 and K16 take these)"
+            self._infer_reason = (key, why)
         return self._infer_reason[1]
 
     def _infer_step(self, t_obs, deterministic, agent_major=False):

@@ -155,6 +155,12 @@ def test_policy(ppo, num_test_runs, deterministic=False, save_test_scores=False,
         policy_scores = {p: make() for p in shared}
         never = torch.zeros(E, dtype=torch.bool, device=device)
 
+    if verbose:
+        for p, pol in ppo.policies.items():
+            why = pol.inference_unsupported_reason() if policy_agents[p] and hasattr(pol, "inference_unsupported_reason") else ""
+            if why:
+                rank_print("Policy {}: the network modules decode its actions, not the one-launch step: {}".format(p, why))
+
     # ---- state to put back
     stack = list(ppo._filter_stack(env))
     switches = [(w, w._cfg["update"], w.update_stats) for w in stack if hasattr(w, "update_stats")]
