@@ -43,25 +43,35 @@ def _pair(I, O, H, F, depth, act, S, seed):
     return gpu, cpu
 
 
-# H, F, depth, activation, out (2 categorical logits / 6 Gaussian means / 1 value), S, rows
+# H, F, depth, activation, out (2 categorical logits / 6 Gaussian means / 1 value), S, rows, in_dim (K18 instantiates
+# lstm_rows_forward<H, false>, K22 the <H, true> form: both pad the input to 16-column chunks, limit 256)
 GRID = [
-    (32, 16, 1, "leaky", 2, 5, 256),
-    (32, 32, 2, "tanh", 1, 1, 2),
-    (32, 128, 1, "relu", 6, 16, 2),
-    (64, 64, 1, "relu", 6, 3, 256),
-    (64, 16, 2, "leaky", 1, 10, 2),
-    (64, 32, 1, "tanh", 2, 1, 4096),
-    (128, 128, 1, "relu", 6, 10, 256),
-    (128, 64, 2, "tanh", 2, 16, 256),
-    (128, 16, 1, "leaky", 1, 5, 4096),
-    (128, 128, 2, "relu", 8, 1, 256),
-    (32, 64, 1, "relu", 3, 3, 4096),
+    (32, 16, 1, "leaky", 2, 5, 256, 17),
+    (32, 32, 2, "tanh", 1, 1, 2, 4),
+    (32, 128, 1, "relu", 6, 16, 2, 4),
+    (64, 64, 1, "relu", 6, 3, 256, 17),
+    (64, 16, 2, "leaky", 1, 10, 2, 4),
+    (64, 32, 1, "tanh", 2, 1, 4096, 17),
+    (128, 128, 1, "relu", 6, 10, 256, 17),
+    (128, 64, 2, "tanh", 2, 16, 256, 17),
+    (128, 16, 1, "leaky", 1, 5, 4096, 17),
+    (128, 128, 2, "relu", 8, 1, 256, 17),
+    (32, 64, 1, "relu", 3, 3, 4096, 17),
+    (32, 16, 1, "relu", 2, 4, 2, 1),
+    (128, 32, 2, "tanh", 3, 3, 256, 1),
+    (32, 32, 1, "leaky", 6, 5, 256, 16),
+    (128, 16, 1, "relu", 1, 2, 2, 16),
+    (32, 16, 2, "tanh", 2, 3, 256, 255),
+    (128, 128, 2, "relu", 8, 16, 2, 255),
+    (32, 64, 1, "leaky", 1, 4, 2, 256),
+    (128, 128, 1, "tanh", 6, 6, 256, 256),
 ]
 
 
-@pytest.mark.parametrize("H,F,depth,act,O,S,N", GRID)
-def test_network_matches_torch_cpu(H, F, depth, act, O, S, N):
-    I = 17 if N != 2 else 4
+# (the rows with in_dim 17 / 4 keep the test ids they had before the grid had that column)
+@pytest.mark.parametrize("H,F,depth,act,O,S,N,I", [
+    pytest.param(*r, id="-".join(map(str, r[:7] if r[7] == (17 if r[6] != 2 else 4) else r))) for r in GRID])
+def test_network_matches_torch_cpu(H, F, depth, act, O, S, N, I):
     gpu, cpu = _pair(I, O, H, F, depth, act, S, seed=H + F + S + N)
     g = torch.Generator().manual_seed(7)
     x = torch.randn(N, S, I, generator=g)
