@@ -762,7 +762,7 @@ int ppoaf_icm_intrinsic_reward(const ppoaf_icm_update_args_t* args, float scale,
  *          PPOPolicy.get_intrinsic_reward          policies/ppo_policy.py:954-1007
  * With pad16(x) = 16 ceil(x / 16):
  *   encoder  O -> E -> E -> E -> D (last layer linear)     E in {32, 64, 128}, 1 <= D <= 128, 1 <= O <= 1024
- *   inverse  2D -> Mi (x depth_inv hidden layers) -> A     Mi, Mf in {32, 64, 128}, depths 1..3, A, A_in <= 8
+ *   inverse  2D -> Mi (x depth_inv hidden layers) -> A     Mi, Mf in {32, 64, 128}, depths 1..3, A, A_in <= 8, or <= 16 with n_action_slices
  *   forward  D + A_in -> Mf (x depth_fwd hidden layers) -> D
  * Losses, activations and the bucket (module order, each parameter padded to 4 floats) are
  * those of ppoaf_icm_update_args_t.  Weight rows of 2D and D + A_in floats are not 16-byte
@@ -795,6 +795,21 @@ int ppoaf_icm_intrinsic_reward(const ppoaf_icm_update_args_t* args, float scale,
  * of `wgrad`, whose table has at most 10 blocks.  `intrinsic_reward` is one launch.
  *   act_scratch   [2][Bpad][pad16(O)]       denc_scratch  unused, may be NULL
  * `check` refuses enc_hidden == 0 with enc_dim != obs_dim or obs_dim > 128.
+ *
+ * MultiDiscrete actions with equal class counts (n_action_slices = k >= 2): the agent-shared ICM
+ * of an agent-grouped policy, one ICM per env over the concatenation of the group's observations
+ * with the action space MultiDiscrete([n] * k)          ppo.py:2520-2538, mat_policy.py:1012-1090
+ *   discrete = 1, action_dim == fwd_action_dim == k n, n >= 2, k <= 8, action_dim <= 16
+ *   actions  int64 [n_rows, k]: slice j of row r at r * k + j (with inputs_in_batch_order the
+ *            rows are read as those of the other tables); a class outside [0, n) is clamped into it
+ *   forward model input: column j n + a_j of the row's action block is 1 for every slice j -- what
+ *            the loop of icm.py:198-211 yields for equal class counts
+ *   inverse head: ONE softmax p over the whole action_dim-wide row (icm.py:76-77), then per slice
+ *            CrossEntropyLoss on p[slice] (a second log-softmax over the slice), summed over the
+ *            slices, mean over B (icm.py:400-412)
+ * n_action_slices 0 or 1: Discrete / Box as above, action widths <= 8.  `check` refuses, for
+ * k >= 2, discrete == 0, action_dim != fwd_action_dim, k > 8, action_dim > 16, action_dim % k != 0
+ * and action_dim / k < 2.
  * ------------------------------------------------------------------------ */
 typedef struct {
     int32_t obs_dim, enc_hidden, enc_dim, inv_hidden, fwd_hidden, action_dim, fwd_action_dim, depth_inv, depth_fwd;
@@ -810,7 +825,8 @@ typedef struct {
     float* act_scratch; float* denc_scratch;
     float* loss_partials;            /* [ceil(B/16) + 1, 2] (last row: this step's Adam constants)*/
     double* totals;                  /* [2]                                                     */
-    int32_t inputs_in_batch_order, _pad;
+    int32_t inputs_in_batch_order;
+    int32_t n_action_slices;         /* 0 | 1: Discrete / Box; k >= 2: MultiDiscrete, k equal slices (above) */
     void* workspace; int64_t workspace_bytes;
 } ppoaf_icm_shapes_args_t;
 

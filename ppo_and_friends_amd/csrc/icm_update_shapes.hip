@@ -10,6 +10,9 @@
 // has run-time sizes and reads its weights with bound-checked scalar loads (rows of 18 or 12 floats at the baseline
 // shapes are not 16-byte aligned), as the encoder's layer 0 (K = O) always has.  Columns D .. pad16(D) of every
 // D-wide panel are written as zeros.
+// MultiDiscrete actions (n_action_slices = k >= 2, the agent-shared ICM of a MAT group): A = A_in = k n <= 16, `actions`
+// int64 [rows][k]; the forward model's input carries k one-hots side by side, the inverse head takes one softmax over
+// the row and a cross entropy per slice (icm.py:76-77, 198-211, 400-412) in icm_sh_models_kernel<., 16>.
 // Identity encoder (enc_hidden = 0, D = O <= 128): the encodings ARE the observation rows.  No encoder kernel runs; the
 // models kernel and the reward kernel fill their two encoding tiles from the observation tables (sh_load_obs), the
 // inverse model's workgroup publishes them as the layer-0 panels of the wgrad launch, and no d(enc) is formed.
@@ -23,6 +26,7 @@ struct IcmSh {
     IcmDev d;                  // d.H = D (the forward loss's mean and the bookkeeping run over B x D); d.actE: hidden planes
     int E, D, DP, Mi, Mf;      // DP = pad16(D)
     int ident;                 // identity encoder: E = 0, D = O; enc is filled by the models kernel, gI / gF / dEh / dEo unused
+    int n_sl;                  // MultiDiscrete: k >= 2 equal action slices of A / k classes (args->n_action_slices); else 0
     float* enc;                // [2][Bpad][DP]     encodings of the two streams
     float* gI;                 // [2][Bpad][DP]     the inverse model's share of d(enc_1), d(enc_2)
     float* gF;                 // [2][Bpad][DP]     the forward model's
@@ -215,12 +219,21 @@ __device__ __forceinline__ void sh_forward_model(const IcmSh& q, const float* __
     __syncthreads();
 }
 
-// the action columns of a row tile: one-hot (icm.py:198-204) or the action values, zero padded; sAct keeps the class /
-// the values for the inverse model's loss
-__device__ __forceinline__ void sh_actions(const IcmDev& u, const int* sRow, float* sAct, float* sXa, int tid) {
+// the action columns of a row tile: one-hot (icm.py:198-204), one one-hot per slice side by side (MultiDiscrete with equal
+// class counts, icm.py:198-211) or the action values, zero padded; sAct keeps the class(es) / the values for the inverse
+// model's loss.  A class outside its slice is clamped into it: nothing is read or set beyond the slice.
+__device__ __forceinline__ void sh_actions(const IcmDev& u, int n_sl, const int* sRow, float* sAct, float* sXa, int tid) {
     if (tid < kRows) {
         const int row = sRow[tid], A = u.A;
-        if (u.discrete) {
+        if (n_sl >= 2) {
+            const int n = A / n_sl;
+            for (int j = 0; j < n_sl; ++j) {
+                int a = row >= 0 ? (int)reinterpret_cast<const int64_t*>(u.actions)[(long)row * n_sl + j] : 0;
+                a = a < 0 ? 0 : (a >= n ? n - 1 : a);
+                reinterpret_cast<int*>(sAct)[tid * 8 + j] = a;
+                if (row >= 0) sXa[tid * kShXS + j * n + a] = 1.0f;
+            }
+        } else if (u.discrete) {
             int a = row >= 0 ? (int)reinterpret_cast<const int64_t*>(u.actions)[row] : 0;
             a = a < 0 ? 0 : (a >= A ? A - 1 : a);
             reinterpret_cast<int*>(sAct)[tid * 8] = a;
@@ -237,9 +250,11 @@ __device__ __forceinline__ void sh_actions(const IcmDev& u, const int* sRow, flo
 
 // ------------------------------------------------------------------------------------------------
 // models: block 2 * g + which (0: inverse model, 1: forward model); only >= 0: every block runs that model on tile
-// blockIdx (the launch per model when the two widths differ)
+// blockIdx (the launch per model when the two widths differ).  AW: the columns the inverse model's head is written for.
+// 8 is the Discrete / Box head (A <= 8); 16 the MultiDiscrete one (n_action_slices >= 2, A <= 16), an instantiation of its
+// own so that the A <= 8 shapes keep their head's arithmetic and their 8-wide tiles (sh_actions is shared by both).
 // ------------------------------------------------------------------------------------------------
-template <int MT>
+template <int MT, int AW>
 __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int only) {
     constexpr int M = 16 * MT, MS = M + 4;
     const IcmDev& u = q.d;
@@ -254,8 +269,8 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
     int* sRow = reinterpret_cast<int*>(smem);                 // [16]
     float* sAct = smem + 16;                                  // [16][8] actions (float, or int bits)
     float* sBout = smem + 144;                                // [16]
-    float* sWout = smem + 160;                                // [8, M]
-    float* sXa = sWout + 8 * M;                               // [16, kShXS]
+    float* sWout = smem + 160;                                // [AW, M]
+    float* sXa = sWout + AW * M;                              // [16, kShXS]
     float* sE1 = sXa + kRows * kShXS;                         // [16, DS]
     float* sE2 = sE1 + kRows * DS;
     float* sP = sE2 + kRows * DS;                             // [16, DS]  forward model: prediction, then its dz
@@ -284,7 +299,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         sh_fetch(q.enc + u.Bpad * DP, DP, g, sE2, DS, tid);
     }
     __syncthreads();
-    sh_actions(u, sRow, sAct, sXa, tid);
+    sh_actions(u, q.n_sl, sRow, sAct, sXa, tid);
     __syncthreads();
     if (q.ident && which == 0) {        // the layer-0 inputs of the wgrad launch
         sh_publish(sE1, DS, q.enc, DP, g, tid);
@@ -316,7 +331,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         }
         const float* Hlast = sH + (long)(depth - 1) * kRows * MS;
         for (int l = 0; l < depth; ++l) sh_publish(sH + (long)l * kRows * MS, MS, u.hI + (long)l * u.Bpad * M, M, g, tid);
-        // output layer (A <= 8): VALU from LDS + 16-lane reductions
+        // output layer (A <= AW): VALU from LDS + 16-lane reductions
         if (tid < 256) {
             const int s = tid >> 4, part = tid & 15;
             for (int k = 0; k < A; ++k) {
@@ -333,7 +348,51 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
             const int s = lane;
             const bool live = s < kRows && sRow[s] >= 0;
             float part = 0.f;
-            if (live && u.discrete) {
+            if constexpr (AW == 16) {
+                if (live) {
+                    // icm.py:76-77, 400-412: ONE softmax p over the whole row, then per slice CrossEntropyLoss on p[slice]
+                    // (a second log-softmax over the slice, with its own max); the row's loss is the sum over the slices
+                    const int nsl = q.n_sl, n = A / nsl;
+                    float p[16];
+                    float m = -INFINITY;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) if (k < A) m = fmaxf(m, sOut[s * kMaxOut + k]);
+                    float ssum = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) { p[k] = k < A ? expf(sOut[s * kMaxOut + k] - m) : 0.f; ssum += p[k]; }
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) p[k] /= ssum;
+                    const float sc = u.icm_beta / (float)B;
+                    float dq[16];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) dq[k] = 0.f;
+#pragma unroll 1
+                    for (int j = 0; j < nsl; ++j) {
+                        const int lo = j * n, hi = lo + n;
+                        const int a = lo + reinterpret_cast<const int*>(sAct)[s * 8 + j];
+                        float m2 = -INFINITY;
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) if (k >= lo && k < hi) m2 = fmaxf(m2, p[k]);
+                        float e2[16], s2 = 0.f;
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) { e2[k] = (k >= lo && k < hi) ? expf(p[k] - m2) : 0.f; s2 += e2[k]; }
+                        float pa = 0.f;
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) if (k == a) pa = p[k];
+                        part += -(pa - m2 - logf(s2));
+#pragma unroll
+                        for (int k = 0; k < 16; ++k) if (k >= lo && k < hi) dq[k] = sc * (e2[k] / s2 - (k == a ? 1.f : 0.f));
+                    }
+                    float dot = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) dot += dq[k] * p[k];
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) sDOut[s * kMaxOut + k] = p[k] * (dq[k] - dot);
+                } else if (s < kRows) {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) sDOut[s * kMaxOut + k] = 0.f;
+                }
+            } else if (live && u.discrete) {
                 // icm.py:404-409: softmax output fed to CrossEntropyLoss (a second log-softmax)
                 float p[8];
                 float m = -INFINITY;
@@ -389,19 +448,19 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         // output layer backward
         if (tid < kRows * 16) {                                 // d(out) rows, zero padded to 16 columns
             const int s = tid >> 4, k = tid & 15;
-            u.oI[((long)g * kRows + s) * 16 + k] = k < 8 ? sDOut[s * kMaxOut + k] : 0.f;
+            u.oI[((long)g * kRows + s) * 16 + k] = k < AW ? sDOut[s * kMaxOut + k] : 0.f;
         }
         if (tid >= 256) {
             const int t2 = tid - 256;
             const int s = t2 >> 4, ig = t2 & 15;
-            float d[8];
+            float d[AW];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) d[k] = sDOut[s * kMaxOut + k];
+            for (int k = 0; k < AW; ++k) d[k] = sDOut[s * kMaxOut + k];
             float hv[MT], acc[MT];
 #pragma unroll
             for (int ii = 0; ii < MT; ++ii) { hv[ii] = Hlast[s * MS + ig + 16 * ii]; acc[ii] = 0.f; }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
+            for (int k = 0; k < AW; ++k) {
                 if (k < A) {
 #pragma unroll
                     for (int ii = 0; ii < MT; ++ii) acc[ii] = fmaf(d[k], sWout[k * M + ig + 16 * ii], acc[ii]);
@@ -506,7 +565,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_reward_kernel(IcmSh q, float
         sh_fetch(q.enc + u.Bpad * DP, DP, g, sE2, DS, tid);
     }
     __syncthreads();
-    sh_actions(u, sRow, sAct, sXa, tid);
+    sh_actions(u, q.n_sl, sRow, sAct, sXa, tid);
     __syncthreads();
     sh_forward_model<MT>(q, u.params + u.fwd_off, sE1, sXa, sH, sP, wave, lane);
     // row sums of (pred - enc_2)^2: 16 lanes per row (columns D .. DP are zero on both sides)
@@ -592,8 +651,22 @@ static int sh_check(const ppoaf_icm_shapes_args_t* a) {
                   "icm_shapes: inv_hidden=%d / fwd_hidden=%d are not instantiated widths (32, 64, 128)", a->inv_hidden, a->fwd_hidden);
     PPOAF_REQUIRE(a->enc_dim >= 1 && a->enc_dim <= 128, "icm_shapes: enc_dim=%d must be in [1,128]", a->enc_dim);
     PPOAF_REQUIRE(a->obs_dim >= 1 && a->obs_dim <= 1024, "icm_shapes: obs_dim=%d must be in [1,1024]", a->obs_dim);
-    PPOAF_REQUIRE(a->action_dim >= 1 && a->action_dim <= 8 && a->fwd_action_dim >= 1 && a->fwd_action_dim <= 8,
-                  "icm_shapes: action_dim=%d fwd_action_dim=%d must be in [1,8]", a->action_dim, a->fwd_action_dim);
+    if (a->n_action_slices >= 2) {
+        // MultiDiscrete over k equal slices (the agent-shared ICM of a MAT group): one class per slice in `actions`
+        const int k = a->n_action_slices;
+        PPOAF_REQUIRE(a->discrete != 0, "icm_shapes: n_action_slices=%d needs discrete=1 (discrete=%d)", k, a->discrete);
+        PPOAF_REQUIRE(a->action_dim == a->fwd_action_dim, "icm_shapes: n_action_slices=%d needs action_dim=%d to equal fwd_action_dim=%d",
+                      k, a->action_dim, a->fwd_action_dim);
+        PPOAF_REQUIRE(k <= 8, "icm_shapes: n_action_slices=%d must be at most 8", k);
+        PPOAF_REQUIRE(a->action_dim >= 1 && a->action_dim <= 16, "icm_shapes: action_dim=%d must be in [1,16] with n_action_slices=%d",
+                      a->action_dim, k);
+        PPOAF_REQUIRE(a->action_dim % k == 0, "icm_shapes: action_dim=%d is not a multiple of n_action_slices=%d", a->action_dim, k);
+        PPOAF_REQUIRE(a->action_dim / k >= 2, "icm_shapes: action_dim=%d / n_action_slices=%d leaves fewer than 2 classes per slice",
+                      a->action_dim, k);
+    } else {
+        PPOAF_REQUIRE(a->action_dim >= 1 && a->action_dim <= 8 && a->fwd_action_dim >= 1 && a->fwd_action_dim <= 8,
+                      "icm_shapes: action_dim=%d fwd_action_dim=%d must be in [1,8]", a->action_dim, a->fwd_action_dim);
+    }
     PPOAF_REQUIRE(a->depth_inv >= 1 && a->depth_inv <= 3 && a->depth_fwd >= 1 && a->depth_fwd <= 3,
                   "icm_shapes: hidden depths (%d, %d) out of [1,3]", a->depth_inv, a->depth_fwd);
     PPOAF_REQUIRE(a->activation >= 0 && a->activation <= 2, "icm_shapes: activation=%d", a->activation);
@@ -688,6 +761,7 @@ static int make_sh(const ppoaf_icm_shapes_args_t* a, IcmSh& q, bool training) {
     u = IcmDev();
     q.E = a->enc_hidden; q.D = a->enc_dim; q.DP = 16 * ((a->enc_dim + 15) / 16); q.Mi = a->inv_hidden; q.Mf = a->fwd_hidden;
     q.ident = a->enc_hidden == 0;
+    q.n_sl = a->n_action_slices >= 2 ? a->n_action_slices : 0;
     u.O = a->obs_dim; u.H = a->enc_dim; u.A = a->action_dim; u.Ain = a->fwd_action_dim;
     u.d_inv = a->depth_inv; u.d_fwd = a->depth_fwd; u.act = a->activation; u.discrete = a->discrete != 0;
     u.enc_off = a->enc_offset; u.inv_off = a->inv_offset; u.fwd_off = a->fwd_offset; u.enc_size = a->inv_offset - a->enc_offset;
@@ -716,6 +790,7 @@ static int make_sh(const ppoaf_icm_shapes_args_t* a, IcmSh& q, bool training) {
     return PPOAF_OK;
 }
 
+constexpr size_t kShMaxLds = 160 * 1024;      // gfx950: LDS per CU
 static size_t sh_lds_enc_fwd(const IcmSh& q) {
     const size_t ES = q.E + 4, INP = 16 * ((q.d.O + 15) / 16) + 4, DS = q.DP + 4;
     return (16 + kRows * INP + 3 * kRows * ES + kRows * DS) * 4;
@@ -724,9 +799,9 @@ static size_t sh_lds_enc_bwd(const IcmSh& q) {
     const size_t ES = q.E + 4, DS = q.DP + 4;
     return (5 * kRows * ES + kRows * DS) * 4;
 }
-static size_t sh_lds_models(const IcmSh& q, int M, int depth) {
+static size_t sh_lds_models(const IcmSh& q, int M, int depth, int AW) {
     const size_t MS = M + 4, DS = q.DP + 4;
-    return (160 + 8 * (size_t)M + kRows * kShXS + 3 * kRows * DS + (size_t)(depth + 2) * kRows * MS + 2 * kRows * kMaxOut) * 4;
+    return (160 + (size_t)AW * M + kRows * kShXS + 3 * kRows * DS + (size_t)(depth + 2) * kRows * MS + 2 * kRows * kMaxOut) * 4;
 }
 static size_t sh_lds_reward(const IcmSh& q) {
     const size_t MS = q.Mf + 4, DS = q.DP + 4;
@@ -753,18 +828,24 @@ static int launch_sh_encoder(const IcmSh& q, bool backward, hipStream_t s) {
 }
 
 // only < 0: both models in one launch (the widths agree); else the launch of model `only`
-template <int MT>
+template <int MT, int AW>
 static int launch_sh_models(const IcmSh& q, int only, hipStream_t s) {
     const IcmDev& u = q.d;
     static bool big = false;
     const int dmax = only < 0 ? (u.d_inv > u.d_fwd ? u.d_inv : u.d_fwd) : (only == 0 ? u.d_inv : u.d_fwd);
-    const size_t lds = sh_lds_models(q, 16 * MT, dmax);
-    const int rc = allow_large_lds(reinterpret_cast<const void*>(icm_sh_models_kernel<MT>), lds, big, "icm_sh_models");
+    // widest case (M 128, D 128, depth 3, AW 16): 19936 floats = 79744 B
+    const size_t lds = sh_lds_models(q, 16 * MT, dmax, AW);
+    PPOAF_REQUIRE(lds <= kShMaxLds, "icm_shapes: the models kernel needs %zu B of LDS (> 160 KiB)", lds);      // (sh_check: A <= AW)
+    const int rc = allow_large_lds(reinterpret_cast<const void*>(icm_sh_models_kernel<MT, AW>), lds, big, "icm_sh_models");
     if (rc) return rc;
     const int n = only < 0 ? 2 * u.nT : u.nT;
     const unsigned grid = u.confine ? 8u * (unsigned)((n + 3) / 4) : (unsigned)n;
-    hipLaunchKernelGGL(icm_sh_models_kernel<MT>, dim3(grid), dim3(kThreadsU), lds, s, q, only);
+    hipLaunchKernelGGL((icm_sh_models_kernel<MT, AW>), dim3(grid), dim3(kThreadsU), lds, s, q, only);
     return check_launch("icm_sh_models");
+}
+template <int MT>
+static int launch_sh_models(const IcmSh& q, int only, hipStream_t s) {
+    return q.n_sl >= 2 ? launch_sh_models<MT, 16>(q, only, s) : launch_sh_models<MT, 8>(q, only, s);
 }
 static int launch_sh_models(const IcmSh& q, int M, int only, hipStream_t s) {
     if (M == 32) return launch_sh_models<2>(q, only, s);
@@ -775,7 +856,8 @@ static int launch_sh_models(const IcmSh& q, int M, int only, hipStream_t s) {
 template <int MT>
 static int launch_sh_reward(const IcmSh& q, float scale, float* intr_out, hipStream_t s) {
     static bool big = false;
-    const size_t lds = sh_lds_reward(q);
+    const size_t lds = sh_lds_reward(q);      // widest case (Mf 128, D 128, depth 3): 13136 floats = 52544 B
+    PPOAF_REQUIRE(lds <= kShMaxLds, "icm_shapes: the reward kernel needs %zu B of LDS (> 160 KiB)", lds);
     const int rc = allow_large_lds(reinterpret_cast<const void*>(icm_sh_reward_kernel<MT>), lds, big, "icm_sh_reward");
     if (rc) return rc;
     hipLaunchKernelGGL(icm_sh_reward_kernel<MT>, dim3((unsigned)q.d.nT), dim3(kThreadsU), lds, s, q, scale, intr_out);
@@ -799,6 +881,7 @@ PPOAF_LAYOUT(ppoaf_icm_shapes_args_t, icm_beta, 216);
 PPOAF_LAYOUT(ppoaf_icm_shapes_args_t, act_scratch, 224);
 PPOAF_LAYOUT(ppoaf_icm_shapes_args_t, loss_partials, 240);
 PPOAF_LAYOUT(ppoaf_icm_shapes_args_t, inputs_in_batch_order, 256);
+PPOAF_LAYOUT(ppoaf_icm_shapes_args_t, n_action_slices, 260);
 PPOAF_LAYOUT(ppoaf_icm_shapes_args_t, workspace, 264);
 PPOAF_LAYOUT(ppoaf_icm_shapes_args_t, workspace_bytes, 272);
 static_assert(sizeof(ppoaf_icm_shapes_args_t) == 280, "ppoaf_icm_shapes_args_t");

@@ -16,6 +16,7 @@ import os
 import sys
 from typing import Callable, NamedTuple
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -290,17 +291,24 @@ class FusedEpoch:
             self._graphs.clear()
         self.n_full, self.tail = N // self.B, N % self.B
 
-    def _gather_tables(self, fields):
-        """K4 over the whole epoch: every input field of the update in shuffled order (one launch)."""
-        buf, N = self.pol.buffer, self.perm.numel()
-        flat = lambda x: x.view((buf.num_transitions,) + tuple(x.shape[2:]))
-        t = self.tables
+    def _epoch_tables(self, attr, N, shapes):
+        """The epoch's tables kept in `self.<attr>`: {name: (row shape, dtype, device)} -> tensors of N rows each, allocated
+        anew (captured graphs and args dropped: they hold the addresses) only when N changes."""
+        t = getattr(self, attr, None)
         if t is None or next(iter(t.values())).shape[0] != N:
-            t = self.tables = {k: torch.empty((N,) + tuple(v.shape[2:]), dtype=v.dtype, device=v.device)
-                               for k, v in fields.items()}
+            t = {k: torch.empty((N,) + tuple(shape), dtype=dtype, device=device) for k, (shape, dtype, device) in shapes.items()}
+            setattr(self, attr, t)
             self._graphs.clear()
             self._args = {}
+        return t
+
+    def _gather_tables(self, fields, into="tables"):
+        """K4 over the whole epoch: every input field of the update in shuffled order (one launch), into `self.<into>`."""
+        buf, N = self.pol.buffer, self.perm.numel()
+        flat = lambda x: x.view((buf.num_transitions,) + tuple(x.shape[2:]))
+        t = self._epoch_tables(into, N, {k: (v.shape[2:], v.dtype, v.device) for k, v in fields.items()})
         K.minibatch_gather([(flat(v), t[k]) for k, v in fields.items()], self.perm, buf.row_map)
+        return t
 
     def _restart_epoch(self):
         """The cursor starts over: totals, mini-batch count and every record region tagged with the cursor back to zero."""
@@ -1066,18 +1074,42 @@ def _icm_bucket_marks(icm, groups):
     return marks, off
 
 
-def _describe_icm_shapes(icm, action_dtype):
+def _icm_action_slices(icm):
+    """MultiDiscrete ICM actions on the shapes chain (csrc/icm_update_shapes.hip, n_action_slices): (slices, total classes,
+    "") or (0, 0, reason).  The kernels take k <= 8 equal slices of n >= 2 classes, k n <= 16."""
+    nvec = [int(n) for n in (getattr(icm, "action_nvec", None) or [])]
+    if not nvec:
+        return 0, 0, "multi-discrete actions without class counts (nvec)"
+    if len(set(nvec)) != 1:
+        return 0, 0, (f"multi-discrete class counts {nvec} differ: the reference's forward-model one-hot (icm.py:198-211) is "
+                      "only well-formed for equal class counts")
+    if nvec[0] < 2:
+        return 0, 0, f"multi-discrete class count of {nvec[0]}: every slice needs at least 2 classes"
+    if len(nvec) > 8:
+        return 0, 0, f"multi-discrete actions of {len(nvec)} slices: the fused ICM kernels take at most 8"
+    if sum(nvec) > 16:
+        return 0, 0, f"multi-discrete actions of {sum(nvec)} classes in all: the fused ICM kernels take at most 16"
+    return len(nvec), sum(nvec), ""
+
+
+def _describe_icm_shapes(icm, action_dtype, multi_discrete=False):
     """IcmShapesArgs topology fields (+ general=True) of an ICM, or (None, reason).  Covered: encoder O -> E -> E -> E -> D,
-    inverse 2D -> Mi (x 1..3) -> A, forward D + Ain -> Mf (x 1..3) -> D; E, Mi, Mf in (32, 64, 128), 1 <= D <= 128."""
+    inverse 2D -> Mi (x 1..3) -> A, forward D + Ain -> Mf (x 1..3) -> D; E, Mi, Mf in (32, 64, 128), 1 <= D <= 128.
+    multi_discrete: MultiDiscrete actions are described as well (n_action_slices; _icm_action_slices has the limits)."""
     from .networks.icm import ICM, LinearObservationEncoder
     if not isinstance(icm, ICM):
         return None, "not an ICM"
     if not isinstance(icm.obs_encoder, LinearObservationEncoder):
         return None, ("the identity encoder (encoded_obs_dim = 0) is not covered: the fused kernels need a "
                       "LinearObservationEncoder")
+    slices = 0
     if action_dtype == "multi-discrete":
-        return None, "multi-discrete actions are not covered by the fused ICM update"
-    if action_dtype not in ("discrete", "continuous"):
+        if not multi_discrete:
+            return None, "multi-discrete actions are not covered by the fused ICM update"
+        slices, classes, why = _icm_action_slices(icm)
+        if why:
+            return None, why
+    elif action_dtype not in ("discrete", "continuous"):
         return None, "unsupported action space for the fused ICM update"
     enc = [icm.obs_encoder.enc_1, icm.obs_encoder.enc_2, icm.obs_encoder.enc_3, icm.obs_encoder.enc_4]
     inv = [m for m in icm.inv_model.sequential_net.modules() if isinstance(m, nn.Linear)]
@@ -1103,7 +1135,10 @@ def _describe_icm_shapes(icm, action_dtype):
     if [(m.in_features, m.out_features) for m in inv] != want_inv or \
             [(m.in_features, m.out_features) for m in fwd] != want_fwd:
         return None, "inverse / forward model layers do not follow 2D -> Mi .. -> A / D + Ain -> Mf .. -> D"
-    if not (1 <= A <= 8 and 1 <= Ain <= 8):
+    if slices:
+        if (A, Ain) != (classes, classes):
+            return None, f"action widths ({A}, {Ain}) are not the {classes} classes of the multi-discrete action space"
+    elif not (1 <= A <= 8 and 1 <= Ain <= 8):
         return None, f"action widths ({A}, {Ain}) must be in [1, 8]"
     if action_dtype == "discrete" and Ain != A:
         return None, "unsupported action space for the fused ICM update"
@@ -1116,12 +1151,15 @@ def _describe_icm_shapes(icm, action_dtype):
     marks, total = _icm_bucket_marks(icm, (enc, inv, fwd))
     if marks is None:
         return None, total
-    return dict(general=True, obs_dim=O, enc_hidden=E, enc_dim=D, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A, fwd_action_dim=Ain,
+    topo = dict(general=True, obs_dim=O, enc_hidden=E, enc_dim=D, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A, fwd_action_dim=Ain,
                 depth_inv=len(inv) - 1, depth_fwd=len(fwd) - 1, activation=acts.pop(), discrete=int(action_dtype == "discrete"),
-                enc_offset=marks[0], inv_offset=marks[1], fwd_offset=marks[2], bucket_total=total), ""
+                enc_offset=marks[0], inv_offset=marks[1], fwd_offset=marks[2], bucket_total=total)
+    if slices:
+        topo.update(discrete=1, n_action_slices=slices)
+    return topo, ""
 
 
-def _describe_icm_identity(icm, action_dtype):
+def _describe_icm_identity(icm, action_dtype, multi_discrete=False):
     """IcmShapesArgs topology fields (+ general=True, identity=True) of an ICM whose encoder is nn.Identity()
     (encoded_obs_dim = 0), or (None, reason).  The kernels read it as enc_hidden = 0, enc_dim = obs_dim = O and an encoder
     of size 0 (enc_offset == inv_offset).  Covered: 1 <= O <= 128, inverse 2 O -> Mi (x 1..3) -> A, forward O + Ain -> Mf
@@ -1131,9 +1169,14 @@ def _describe_icm_identity(icm, action_dtype):
         return None, "not an ICM"
     if not isinstance(icm.obs_encoder, nn.Identity):
         return None, "not an identity encoder (encoded_obs_dim > 0)"
+    slices = 0
     if action_dtype == "multi-discrete":
-        return None, "multi-discrete actions are not covered by the fused ICM update"
-    if action_dtype not in ("discrete", "continuous"):
+        if not multi_discrete:
+            return None, "multi-discrete actions are not covered by the fused ICM update"
+        slices, classes, why = _icm_action_slices(icm)
+        if why:
+            return None, why
+    elif action_dtype not in ("discrete", "continuous"):
         return None, "unsupported action space for the fused ICM update"
     inv = [m for m in icm.inv_model.sequential_net.modules() if isinstance(m, nn.Linear)]
     fwd = [m for m in icm.forward_model.sequential_net.modules() if isinstance(m, nn.Linear)]
@@ -1152,7 +1195,10 @@ def _describe_icm_identity(icm, action_dtype):
     if [(m.in_features, m.out_features) for m in inv] != want_inv or \
             [(m.in_features, m.out_features) for m in fwd] != want_fwd:
         return None, "inverse / forward model layers do not follow 2 O -> Mi .. -> A / O + Ain -> Mf .. -> O"
-    if not (1 <= A <= 8 and 1 <= Ain <= 8):
+    if slices:
+        if (A, Ain) != (classes, classes):
+            return None, f"action widths ({A}, {Ain}) are not the {classes} classes of the multi-discrete action space"
+    elif not (1 <= A <= 8 and 1 <= Ain <= 8):
         return None, f"action widths ({A}, {Ain}) must be in [1, 8]"
     if action_dtype == "discrete" and Ain != A:
         return None, "unsupported action space for the fused ICM update"
@@ -1164,15 +1210,25 @@ def _describe_icm_identity(icm, action_dtype):
     marks, total = _icm_bucket_marks(icm, (inv, fwd))
     if marks is None:
         return None, total
-    return dict(general=True, identity=True, obs_dim=O, enc_hidden=0, enc_dim=O, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A,
+    topo = dict(general=True, identity=True, obs_dim=O, enc_hidden=0, enc_dim=O, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A,
                 fwd_action_dim=Ain, depth_inv=len(inv) - 1, depth_fwd=len(fwd) - 1, activation=acts.pop(),
                 discrete=int(action_dtype == "discrete"), enc_offset=marks[0], inv_offset=marks[0], fwd_offset=marks[1],
-                bucket_total=total), ""
+                bucket_total=total)
+    if slices:
+        topo.update(discrete=1, n_action_slices=slices)
+    return topo, ""
 
 
-def describe_icm_chain(icm, action_dtype):
+def describe_icm_chain(icm, action_dtype, multi_discrete=False):
     """Which K14 chain trains `icm`: the one-width description, else the one for widths of their own, else the identity
-    encoder's; (topology, "") or (None, reason of the describer that matches the ICM's encoder type)."""
+    encoder's; (topology, "") or (None, reason of the describer that matches the ICM's encoder type).
+    multi_discrete (the opt-in PPOPolicy.fused_shared_icm): an ICM over MultiDiscrete actions of equal class counts is
+    described too -- always on the shapes chain or the identity form, whose kernels have the multi-categorical head; the
+    one-width chain is not asked.  Without it such an ICM is refused as before."""
+    if multi_discrete and action_dtype == "multi-discrete":
+        if isinstance(getattr(icm, "obs_encoder", None), nn.Identity):
+            return _describe_icm_identity(icm, action_dtype, True)
+        return _describe_icm_shapes(icm, action_dtype, True)
     topo, why = _describe_icm(icm, action_dtype)
     if topo is not None:
         return topo, ""
@@ -1253,6 +1309,13 @@ class FusedIcmUpdate(FusedEpoch):
     B = n A and batch_stride = batch_size A: icm_rows (csrc/icm_update_dev.hpp) then takes row cursor * batch_stride + s of
     the tables and reads neither `perm` nor `row_map` (they index the buffer's grouped rows, not the samples: NULL here),
     and n_rows = N A only bounds the tables.  `self.B`, the tail and the cursor keep counting grouped rows / mini-batches.
+
+    Agent-grouped policies with agent_shared_icm (ppo.py:2520-2538, "case 2"), behind the opt-in `pol.fused_shared_icm`: one
+    ICM sample per grouped row, its observation the group's observations side by side in the order of the policy's current
+    agent_idxs, its action the group's classes in that order -- MultiDiscrete([n] * A), topo["n_action_slices"] = A.  The
+    epoch's gathered tables [N, A, .] are re-ordered along the agent axis by agent_idxs (taken at begin_epoch: the policy
+    reshuffles it at every rollout) and read as [N, A O], [N, A O] and int64 [N, A]; self.A = 1, so B and batch_stride
+    count grouped rows, inputs_in_batch_order = 1, perm / row_map NULL and n_rows = N.
     """
 
     n_totals = 2
@@ -1262,6 +1325,9 @@ class FusedIcmUpdate(FusedEpoch):
     def unsupported_reason(pol, batch_size=None):
         if not pol.enable_icm:
             return "no ICM"
+        if FusedIcmUpdate._shared(pol):
+            # (the policy's own action_dtype is the agents' "discrete": the ICM's is what it trains on)
+            return describe_icm_chain(pol.icm_model, pol.icm_model.action_dtype, multi_discrete=True)[1]
         if pol.agent_grouping and pol.agent_shared_icm:
             return ("agent_shared_icm: one ICM over the MultiDiscrete action space of the whole group (ppo.py:2520-2538) "
                     "is not covered, torch path")
@@ -1273,15 +1339,26 @@ class FusedIcmUpdate(FusedEpoch):
         return why
 
     @staticmethod
+    def _shared(pol):
+        """The agent-shared ICM of an agent-grouped policy on the fused kernels (opt-in: PPOPolicy.fused_shared_icm)."""
+        return bool(getattr(pol, "agent_grouping", False) and pol.agent_shared_icm and getattr(pol, "fused_shared_icm", False))
+
+    @staticmethod
     def _agents(pol):
-        """ICM samples per buffer row: the group's agents for an agent-grouped policy, else 1."""
+        """ICM samples per buffer row: the group's agents for an agent-grouped policy (1 when they share one ICM), else 1."""
+        if FusedIcmUpdate._shared(pol):
+            return 1
         return int(getattr(pol, "num_agents", 0) or len(pol.agent_ids)) if getattr(pol, "agent_grouping", False) else 1
 
     def __init__(self, ppo, policy_id):
         super().__init__(ppo, policy_id)
         pol = self.pol
         dev = pol.device
-        self.topo, _ = describe_icm_chain(pol.icm_model, pol.action_dtype)
+        self.shared = self._shared(pol)                    # read once, as the refusal was: the opt-in is set before the first epoch
+        if self.shared:
+            self.topo, _ = describe_icm_chain(pol.icm_model, pol.icm_model.action_dtype, multi_discrete=True)
+        else:
+            self.topo, _ = describe_icm_chain(pol.icm_model, pol.action_dtype)
         self.general = bool(self.topo.get("general"))      # csrc/icm_update_shapes.hip: split-wgrad form only, no in-kernel waits
         self.A = self._agents(pol)                         # ICM samples per buffer row (agent-grouped policies: the agents)
         rows = self.B * self.A                             # everything below is sized for a full mini-batch's samples
@@ -1316,8 +1393,9 @@ class FusedIcmUpdate(FusedEpoch):
         t = self.tables                        # per-epoch inputs in shuffled order (begin_epoch)
         a.obs, a.next_obs, a.actions = t["obs"].data_ptr(), t["next_obs"].data_ptr(), t["actions"].data_ptr()
         a.inputs_in_batch_order = 1
-        if self.A > 1:
-            # (row, agent) samples: the tables read as [N A, .]; perm / row_map are not the samples' (class comment)
+        if self.A > 1 or self.shared:
+            # (row, agent) samples: the tables read as [N A, .]; perm / row_map are not the samples' (class comment).
+            # Shared ICM: A = 1, the tables' rows are the N joined grouped rows
             a.perm, a.row_map, a.n_rows = None, None, self.perm.numel() * self.A
         else:
             a.perm, a.row_map, a.n_rows = self.perm.data_ptr(), buf.row_map.data_ptr(), buf.num_transitions
@@ -1381,7 +1459,19 @@ class FusedIcmUpdate(FusedEpoch):
 
     def _epoch_inputs(self, N):
         buf = self.pol.buffer
-        self._gather_tables(dict(obs=buf.observations, next_obs=buf.next_observations, actions=buf.actions))
+        if not self.shared:
+            self._gather_tables(dict(obs=buf.observations, next_obs=buf.next_observations, actions=buf.actions))
+            return
+        # case 2 (ppo.py:2520-2538; the torch path: PPO._icm_batch_train): gather [N, A, .] in shuffled order, then the agents
+        # in the order of the policy's current agent_idxs, side by side in one row -- once per epoch, into tables that keep
+        # their addresses (the captured launches read them)
+        grouped = self._gather_tables(dict(obs=buf.observations, next_obs=buf.next_observations, actions=buf.actions),
+                                      into="_grouped_tables")
+        joined = self._epoch_tables("tables", N, {k: ((v[0].numel(),), v.dtype, v.device) for k, v in grouped.items()})
+        order = self.ppo._scratch(f"icm_agent_order_{self.policy_id}", len(self.pol.agent_idxs), torch.int64)
+        order.copy_(torch.as_tensor(np.asarray(self.pol.agent_idxs), dtype=torch.int64))
+        for k, v in grouped.items():
+            torch.index_select(v.reshape(N, buf.A, -1), 1, order, out=joined[k].view(N, buf.A, -1))
 
     def _one(self, args):
         lib, st, ref = self._lib, K.stream(), C.byref(args)

@@ -472,6 +472,11 @@ class MATPolicy(PPOPolicy):
         obs_1, obs_2 = join(obs_1), join(self._to_device(obs))
         adt = torch.int64 if self.action_dtype in ("discrete", "multi-discrete") else torch.float32
         act = join(self._to_device(actions, adt))
+        if self.fused_shared_icm and obs_1.is_cuda and getattr(self, "fused_icm_reward", True):
+            # K14 on the joined rows [E, A O] / int64 [E, A] (opt-in; counted in PPOPolicy.fused_icm_reward_calls)
+            fused = self._fused_intrinsic_reward(obs_1, obs_2, act, shared=True)
+            if fused is not None:
+                return fused
         with torch.no_grad():
             intr, _, _ = self.icm_model(obs_1, obs_2, act)
         return intr.reshape(-1) * float(self.intr_reward_weight())

@@ -96,6 +96,10 @@ class FlatAdam:
 class PPOPolicy:
 
     fused_icm_reward_calls = 0         # intrinsic-reward calls answered by K14's two launches in this process (tests: the path ran)
+    # Opt-in: the agent-shared ICM of an agent-grouped policy (MultiDiscrete over the group, ppo.py:2520-2538) on K14's
+    # kernels, update epoch and rollout-time reward.  Set on the policy before its first rollout: it is read when the ICM
+    # updater and the reward state are first built.  False: the torch path, with today's messages.
+    fused_shared_icm = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -605,9 +609,10 @@ class PPOPolicy:
             intr, _, _ = self.icm_model(obs_1, obs_2, act)
         return intr.reshape(-1) * float(self.intr_reward_weight())
 
-    def _fused_intrinsic_reward(self, obs_1, obs_2, act):
+    def _fused_intrinsic_reward(self, obs_1, obs_2, act, shared=False):
         """K14's encoder + forward-model kernels on the env batch (two launches; one for an identity encoder); None when not
-        covered."""
+        covered.  shared: the rows are an agent-shared ICM's (one per env, MultiDiscrete classes [n, agents]): described
+        with the ICM's own action dtype."""
         import ctypes as C
         from .. import _lib
         from .. import kernels as K
@@ -615,7 +620,10 @@ class PPOPolicy:
         n = obs_1.shape[0]
         if st is None or st["n"] != n:
             from ..fused_update import describe_icm_chain, icm_scratch_floats, icm_topology_args
-            topo, why = describe_icm_chain(self.icm_model, self.action_dtype)
+            if shared:
+                topo, why = describe_icm_chain(self.icm_model, self.icm_model.action_dtype, multi_discrete=True)
+            else:
+                topo, why = describe_icm_chain(self.icm_model, self.action_dtype)
             if topo is None:
                 self.fused_icm_reward = False
                 return None

@@ -9,13 +9,18 @@ shape before that chain existed.  Two more cases, each against the torch path th
   --agents A   an agent-grouped MATPolicy of A agents (O 18, Discrete(5): the C5 dims of bench.py at A = 3) with the default
                ICM (one width, 128): one ICM sample per (row, agent) pair, so a mini-batch of `--batch` grouped rows is
                `--batch` x A ICM rows; `--envs` defaults to 1024 here, as C5's.  Combine with --identity for the identity ICM.
+  --agents A --shared   the same policy with agent_shared_icm: ONE ICM per env over the group's A x 18 observation columns,
+               actions MultiDiscrete([5] * A), one ICM row per grouped row.  Both legs run update_mode="fused"; the "fused" leg
+               sets the opt-in PPOPolicy.fused_shared_icm (K14's shapes chain, n_action_slices = A), the "torch" leg leaves it
+               off, which keeps the ICM epoch and MATPolicy.get_agent_shared_intrinsic_rewards on the torch path.  Combines
+               with --identity.
 
 Both legs live in one process on the same rollout shape; after a warm-up pass of each they are ALTERNATED `--repeats`
 times and timed with device events: the epoch = PPO._icm_batch_train over 2048 mini-batches (shuffle draw included), the
 reward = PPOPolicy.get_intrinsic_reward on the 4096-row env batch (mean of `--reward-calls` back-to-back calls).  Prints the
 median and the spread (min .. max) of both, the launches per mini-batch of the fused chain, and one JSON line.
 
-    python tools/icm_shapes_bench.py [--identity] [--agents A] [--envs 4096] [--steps 128] [--batch 256] [--repeats 5]
+    python tools/icm_shapes_bench.py [--identity] [--agents A [--shared]] [--envs 4096] [--steps 128] [--batch 256] [--repeats 5]
                                      [--reward-calls 50] [--allow-torch-path]
 
 --allow-torch-path: do not insist that the "fused" leg has a fused updater -- for running this tool on a commit whose K14
@@ -48,7 +53,7 @@ def case_of(args):
     return 17, Box(-1.0, 1.0, (6,), np.float32), 1, dict(BASELINE_KW)
 
 
-def make(mode, E, T, B, case):
+def make(mode, E, T, B, case, shared=False):
     from ppo_and_friends_amd.ppo import PPO
     from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
     from ppo_and_friends_amd.spaces import Box
@@ -61,9 +66,14 @@ def make(mode, E, T, B, case):
     else:
         env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, DEV, reward="uniform", seed=5, term_prob=0.05)
     sp = Box(-np.inf, np.inf, (O,), np.float32)
-    ppo = PPO(env_gen, {"p": (cls, sp, sp, space, dict(enable_icm=True, icm_kw_args=icm_kw))}, device=DEV, random_seed=4,
+    kw = dict(enable_icm=True, icm_kw_args=icm_kw)
+    if shared:
+        kw["agent_shared_icm"] = True
+    ppo = PPO(env_gen, {"p": (cls, sp, sp, space, kw)}, device=DEV, random_seed=4,
               normalize_obs=False, normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=B, epochs_per_iter=1,
-              update_mode=mode)
+              update_mode="fused" if shared else mode)
+    if shared and mode == "fused":
+        ppo.policies["p"].fused_shared_icm = True              # the opt-in, before the first rollout
     ppo.rollout()
     return ppo
 
@@ -82,6 +92,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--identity", action="store_true")
     ap.add_argument("--agents", type=int, default=1)
+    ap.add_argument("--shared", action="store_true")
     ap.add_argument("--allow-torch-path", action="store_true")
     ap.add_argument("--envs", type=int, default=None)
     ap.add_argument("--steps", type=int, default=128)
@@ -89,6 +100,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--reward-calls", type=int, default=50)
     args = ap.parse_args()
+    if args.shared and args.agents < 2:
+        ap.error("--shared needs --agents A with A >= 2")
     if args.envs is None:
         args.envs = 1024 if args.agents > 1 else 4096
     from ppo_and_friends_amd.ppo import PermutationLoader
@@ -98,13 +111,14 @@ def main():
     O, space, A, icm_kw = case
     legs, path = {}, {}
     for mode in ("fused", "torch"):
-        ppo = make(mode, args.envs, args.steps, args.batch, case)
+        ppo = make(mode, args.envs, args.steps, args.batch, case, args.shared)
         pol = ppo.policies["p"]
         upd = ppo._fused_icm_updater("p")
         path[mode] = "torch" if upd is None else "K14"
         if mode == "fused" and not args.allow_torch_path:
             assert upd is not None, FusedIcmUpdate.unsupported_reason(pol)
             assert bool(upd.topo.get("identity")) == args.identity, upd.topo
+            assert not args.shared or upd.topo.get("n_action_slices") == A, upd.topo
         elif mode == "torch":
             assert upd is None
         loader = PermutationLoader(pol.dataset, args.batch, ppo.loader_generator)
@@ -112,13 +126,17 @@ def main():
         rows = args.envs * A                                     # the env batch of one step: one row per (env, agent)
         o1, o2 = buf.observations[0].reshape(rows, -1), buf.next_observations[0].reshape(rows, -1)
         act = buf.actions[0].reshape(rows, -1)
+        if args.shared:                                          # the environment's agent-major batches [A E, .]
+            major = lambda x: x.reshape(args.envs, A, -1).transpose(0, 1).reshape(rows, -1).contiguous()
+            o1, o2, act = major(o1), major(o2), major(act)
 
         def epoch(ppo=ppo, loader=loader):
             ppo._icm_batch_train(loader, "p")
 
         def reward(pol=pol, o1=o1, o2=o2, act=act, n=args.reward_calls):
+            call = pol.get_agent_shared_intrinsic_rewards if args.shared else pol.get_intrinsic_reward
             for _ in range(n):
-                pol.get_intrinsic_reward(o1, o2, act)
+                call(o1, o2, act)
         legs[mode] = dict(epoch=epoch, reward=reward, ms=[], us=[], upd=upd)
     n_mb = -(-args.envs * args.steps // args.batch)
     for leg in legs.values():                                  # warm-up pass: graph capture, allocations, autotuning
@@ -141,7 +159,8 @@ def main():
     else:
         launches = 2 if legs["fused"]["upd"].fuse_reason() == "" else 4
     out = dict(shape=dict(O=O, actions=f"Discrete({space.n})" if hasattr(space, "n") else f"Box({space.shape[0]})", agents=A, envs=args.envs, steps=args.steps, batch=args.batch,
-                          icm_rows_per_minibatch=args.batch * A, minibatches=n_mb, **icm_kw),
+                          shared_icm=args.shared, icm_rows_per_minibatch=args.batch * (1 if args.shared else A), minibatches=n_mb,
+                          **icm_kw),
                path=path, fused_launches_per_minibatch=launches)
     for mode, leg in legs.items():
         ms, us = leg["ms"], leg["us"]
