@@ -23,35 +23,44 @@ def _lin(i, o, gain=np.sqrt(2)):
     return layer
 
 
+def activation_module(name):
+    """"relu" (the reference's default), "leaky_relu" (slope 0.01) or "tanh": the one activation an ICM shares between its
+    encoder and both models (icm.py:228-240 hands `activation` to all three)."""
+    return {"relu": nn.ReLU, "leaky_relu": lambda: nn.LeakyReLU(0.01), "tanh": nn.Tanh}[name]()
+
+
 class ObsEncoder(nn.Module):
-    def __init__(self, obs_size, encoded_dim=128, out_init=1.0, hidden=128):
+    def __init__(self, obs_size, encoded_dim=128, out_init=1.0, hidden=128, activation="relu"):
         super().__init__()
+        self.act = activation_module(activation)
         self.enc_1 = _lin(obs_size, hidden); self.enc_2 = _lin(hidden, hidden)
         self.enc_3 = _lin(hidden, hidden); self.enc_4 = _lin(hidden, encoded_dim, out_init)
 
     def forward(self, obs):
-        x = torch.relu(self.enc_1(obs.flatten(start_dim=1)))
-        x = torch.relu(self.enc_2(x))
-        x = torch.relu(self.enc_3(x))
+        x = self.act(self.enc_1(obs.flatten(start_dim=1)))
+        x = self.act(self.enc_2(x))
+        x = self.act(self.enc_3(x))
         return self.enc_4(x)
 
 
 class ICM(nn.Module):
     def __init__(self, obs_size, act_size, discrete, reward_scale=0.01, out_init=1.0, enc=128, hidden=128, depth=2,
-                 nvec=None, enc_hidden=None, inv_depth=None, fwd_depth=None):
+                 nvec=None, enc_hidden=None, inv_depth=None, fwd_depth=None, activation="relu"):
         """nvec: the MultiDiscrete class counts of an agent-shared ICM (act_size = sum(nvec)); icm.py:322-324.
         enc_hidden / inv_depth / fwd_depth: encoder_hidden_size, inverse_hidden_depth, forward_hidden_depth when they
-        differ from `hidden` / `depth` (icm.py:228-240)."""
+        differ from `hidden` / `depth` (icm.py:228-240).  activation: "relu" | "leaky_relu" | "tanh", in the encoder and both
+        models."""
         super().__init__()
         self.discrete, self.act_size, self.reward_scale = discrete, act_size, reward_scale
         self.nvec = None if nvec is None else [int(n) for n in nvec]
-        self.obs_encoder = ObsEncoder(obs_size, enc, out_init, hidden if enc_hidden is None else enc_hidden)
+        self.activation = activation
+        self.obs_encoder = ObsEncoder(obs_size, enc, out_init, hidden if enc_hidden is None else enc_hidden, activation)
         self.inv_model = nn.Module()
         self.inv_model.sequential_net = make_mlp(2 * enc, act_size, hidden, depth if inv_depth is None else inv_depth,
-                                                 out_gain=out_init)
+                                                 out_gain=out_init, activation=activation_module(activation))
         self.forward_model = nn.Module()
         self.forward_model.sequential_net = make_mlp(enc + act_size, enc, hidden, depth if fwd_depth is None else fwd_depth,
-                                                     out_gain=out_init)
+                                                     out_gain=out_init, activation=activation_module(activation))
 
     def forward(self, obs_1, obs_2, actions):
         e1, e2 = self.obs_encoder(obs_1), self.obs_encoder(obs_2)
