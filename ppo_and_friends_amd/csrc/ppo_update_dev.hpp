@@ -9,6 +9,30 @@
 
 namespace ppoaf {
 
+// Diagnostic build only (-DPPOAF_STAMPS): s_memtime per phase of workgroup (0, which), wave 0,
+// into a buffer nothing else reads.  The shipped library executes no stamp.
+// PPOAF_STAMP_W(k, w): the same clock read by lane 0 of wave w, into the buffer's second row (tools/phase_stamps.py:
+// inside the head and the output backward, where the waves of a workgroup do different things).
+#ifdef PPOAF_STAMPS
+#ifndef PPOAF_STAMP_BLOCK
+#define PPOAF_STAMP_BLOCK 0        /* 0..3: an actor workgroup, 4..7: a critic workgroup */
+#endif
+static __device__ unsigned long long g_ppo_update_stamps[2][16];
+#define PPOAF_STAMP_AT(row, k, t0)                                                       \
+    do {                                                                                 \
+        if (blockIdx.x == PPOAF_STAMP_BLOCK && threadIdx.x == (t0)) {                    \
+            unsigned long long t_;                                                       \
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");    \
+            g_ppo_update_stamps[row][k] = t_;                                            \
+        }                                                                                \
+    } while (0)
+#define PPOAF_STAMP(k) PPOAF_STAMP_AT(0, k, 0)
+#define PPOAF_STAMP_W(k, w) PPOAF_STAMP_AT(1, k, 64 * (w))
+#else
+#define PPOAF_STAMP(k) do {} while (0)
+#define PPOAF_STAMP_W(k, w) do {} while (0)
+#endif
+
 // Per-mini-batch panels shared by the layered mode of the two-XCD persistent kernel and by the split-wgrad chain
 // (fwd_bwd publishes them, the wgrad launch consumes them): workspace memory, 256-byte aligned pieces.
 struct WsDev {
@@ -241,8 +265,15 @@ __device__ __forceinline__ unsigned hw_xcc_id() {
 // d / d log_std parked in sOut[.][8..]), the block's loss partials -> u.loss_partials, critic values written back.
 //   sRow16[16] dataset row of each block row (-1: dead), sRowF[3][16] adv / old log-prob / rewards-to-go,
 //   sMisc[4] adv mean / std, value-normaliser mean / var, sActF[16][8] raw actions, log_std_p the actor's log_std.
+// In three parts, so that a caller can take everything the backward pass does not wait for off its path:
+//   ppo_head_rows    the row part: everything up to sDOut (and sOut[.][8..]).  Touches no global memory but the Gaussian
+//                    head's log_std.  It leaves each row's loss terms (part[0, 2, 3, 4, 7]; dead rows: zeros) in the row's
+//                    8 words of sActF, which is dead once the row's actions have been read.
+//   ppo_head_values  the critic's u.values[row] = v (ppo.py:2340), from sOut alone.
+//   ppo_head_block   the block part: the parked terms, read in row order, -> the same eight 16-lane sums -> u.loss_partials.
+// The last two may run on any wave, any time after a barrier behind the row part, while sRow / sOut / sActF are intact.
 template <bool NT, typename U>
-__device__ __forceinline__ void ppo_head_loss(const U& u, const int which, const int g, const int out_dim,
+__device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const int out_dim,
                                               const float* __restrict__ log_std_p, const int* sRow,
                                               const float* sRowF, const float* sMisc, float* sActF, float* sOut,
                                               float* sDOut, const int lane, const long B) {
@@ -314,11 +345,8 @@ __device__ __forceinline__ void ppo_head_loss(const U& u, const int which, const
                 sDOut[s4 * kMaxOut + k0] = 0.f; sDOut[s4 * kMaxOut + k1] = 0.f;
                 if (q == 0) for (int k2 = 8; k2 < kMaxOut; ++k2) sDOut[s4 * kMaxOut + k2] = 0.f;
             }
-            // row results -> lane s (= row s) for the partial sums below
-            const int src = (lane & 15) * 4;
-            const float r_surr = __shfl(-fminf(surr1, surr2), src, 64), r_ent = __shfl(ent4, src, 64);
-            const float r_kl = __shfl(lpo4 - logp4, src, 64), r_bad = __shfl(bad4, src, 64);
-            if (live) { part[0] = r_surr; part[3] = r_ent; part[4] = r_kl; part[7] = r_bad; }
+            // row results: lane (s4, 0) holds them; it parks them below
+            if (live4) { part[0] = -fminf(surr1, surr2); part[3] = ent4; part[4] = lpo4 - logp4; part[7] = bad4; }
         } else if (u.head_kind >= PPOAF_HEAD_MULTI_CATEGORICAL) {
             // MultiDiscrete / MultiBinary (action_heads.hpp): one lane per row
             if (live) {
@@ -427,24 +455,57 @@ __device__ __forceinline__ void ppo_head_loss(const U& u, const int which, const
             part[2] = l;
             sDOut[s * kMaxOut] = dl * inv_B;
             for (int k2 = 1; k2 < 8; ++k2) sDOut[s * kMaxOut + k2] = 0.f;
-            u.values[row] = v;                                   // ppo.py:2340
         } else if (s < kRows) {
             for (int k2 = 0; k2 < 8; ++k2) sDOut[s * kMaxOut + k2] = 0.f;
         }
     }
+    // park the row's terms where its actions were.  (The actions were read above through pointers of another type: the
+    // compiler may not take these stores ahead of those reads.)
+    asm volatile("" ::: "memory");
+    const bool cat = which == 0 && u.head_kind == PPOAF_HEAD_CATEGORICAL;
+    const int prow = cat ? (lane >> 2) : s;
+    if (cat ? (lane & 3) == 0 : s < kRows) {
+        float* pk = sActF + prow * 8;
+        pk[0] = part[0]; pk[2] = part[2]; pk[3] = part[3]; pk[4] = part[4]; pk[7] = part[7];
+    }
+}
+
+template <typename U>
+__device__ __forceinline__ void ppo_head_values(const U& u, const int* sRow, const float* sOut, const int lane) {
+    if (lane < kRows) {
+        const int row = sRow[lane];
+        if (row >= 0) u.values[row] = sOut[lane * kMaxOut];      // ppo.py:2340
+    }
+}
+
+template <typename U>
+__device__ __forceinline__ void ppo_head_block(const U& u, const int which, const int g, const float* sMisc,
+                                               const float* sActF, const int lane) {
+    float part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (lane < kRows) {
+        const float* pk = sActF + lane * 8;
+        part[0] = pk[0]; part[2] = pk[2]; part[3] = pk[3]; part[4] = pk[4]; part[7] = pk[7];
+    }
     // per-workgroup partial sums (lanes >= 16 contribute zeros)
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        float v = (lane < kRows) ? part[k] : 0.f;
-        v = group16_sum(v);
-        part[k] = v;
-    }
+    for (int k = 0; k < 8; ++k) part[k] = group16_sum(part[k]);
     if (lane == 0) {
         if (which == 0 && g == 0) { part[5] = sMisc[0]; part[6] = sMisc[1]; }
         float* lp = u.loss_partials + ((long)which * u.n_wg + g) * 8;
 #pragma unroll
         for (int k = 0; k < 8; ++k) lp[k] = part[k];
     }
+}
+
+// the three parts back to back on one wave (the pair body, ppo_update_rowpair.hpp; K22, lstm_update.hip)
+template <bool NT, typename U>
+__device__ __forceinline__ void ppo_head_loss(const U& u, const int which, const int g, const int out_dim,
+                                              const float* __restrict__ log_std_p, const int* sRow,
+                                              const float* sRowF, const float* sMisc, float* sActF, float* sOut,
+                                              float* sDOut, const int lane, const long B) {
+    ppo_head_rows<NT>(u, which, out_dim, log_std_p, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
+    if (which != 0) ppo_head_values(u, sRow, sOut, lane);
+    ppo_head_block(u, which, g, sMisc, sActF, lane);
 }
 
 }  // namespace ppoaf

@@ -6,25 +6,6 @@ namespace ppoaf {
 
 extern __shared__ __attribute__((aligned(16))) unsigned char ppo_update_smem[];
 
-// Diagnostic build only (-DPPOAF_STAMPS): s_memtime per phase of workgroup (0, which), wave 0,
-// into a buffer nothing else reads.  The shipped library executes no stamp.
-#ifdef PPOAF_STAMPS
-#ifndef PPOAF_STAMP_BLOCK
-#define PPOAF_STAMP_BLOCK 0        /* 0..3: an actor workgroup, 4..7: a critic workgroup */
-#endif
-static __device__ unsigned long long g_ppo_update_stamps[2][16];
-#define PPOAF_STAMP(k)                                                                   \
-    do {                                                                                 \
-        if (blockIdx.x == PPOAF_STAMP_BLOCK && threadIdx.x == 0) {                       \
-            unsigned long long t_;                                                       \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");    \
-            g_ppo_update_stamps[0][k] = t_;                                              \
-        }                                                                                \
-    } while (0)
-#else
-#define PPOAF_STAMP(k) do {} while (0)
-#endif
-
 
 // SPLIT = true (split-wgrad chain): the body keeps forward, losses and dgrad, but computes NO weight gradient of a hidden
 // layer.  It publishes what a complete-K wgrad launch needs instead -- its 16 rows of the input x, of every hidden
@@ -84,6 +65,29 @@ __device__ __forceinline__ int rowtile_request_args(const UpdateDev& u, int b) {
     return b;
 }
 
+// CP adjacent floats of LDS <-> registers; 16-byte accesses where CP allows (the callers' addresses are multiples of CP floats)
+template <int CP> __device__ __forceinline__ void lds_read_adjacent(const float* p, float (&v)[CP]) {
+    if constexpr (CP % 4 == 0) {
+#pragma unroll
+        for (int q = 0; q < CP / 4; ++q) {
+            const float4 t = *reinterpret_cast<const float4*>(p + 4 * q);
+            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < CP; ++q) v[q] = p[q];
+    }
+}
+template <int CP> __device__ __forceinline__ void lds_write_adjacent(float* p, const float (&v)[CP]) {
+    if constexpr (CP % 4 == 0) {
+#pragma unroll
+        for (int q = 0; q < CP / 4; ++q) *reinterpret_cast<float4*>(p + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < CP; ++q) p[q] = v[q];
+    }
+}
+
 // TABLES is the flavour the epoch driver of fused_update.py runs at three hidden layers: the deep prefetch below (one
 // output tile per wave) over per-epoch tables in shuffled order that hold row numbers (u.pregathered, no u.row_map).  It is
 // a compile-time flavour, chosen by ppo_update_fwd_bwd_body from the arguments.  As run-time conditions of one body, "are
@@ -122,13 +126,36 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     // produced here) its row of the output-layer partials, addressed with the same bucket offsets
     float* slab = SPLIT ? u.sp.outpart[which] + (long)g * (nd.size - offW(depth)) - offW(depth)
                         : u.slabs + (long)g * u.bucket_total + nd.offset;
-    // 16 rows x H floats of LDS (row stride HS) -> rows [16 g, +16) of a [Bp][H] panel: one float4 per thread at H = 128
-    auto publish_rows = [&](const float* src, float* panel) {
-        float* dst = panel + (long)g * kRows * H;
-        for (int i = tid; i < kRows * (H / 4); i += kThreadsU) {
-            const int r = i / (H / 4), c4 = i - r * (H / 4);
-            *reinterpret_cast<float4*>(dst + (long)r * H + 4 * c4) = *reinterpret_cast<const float4*>(src + r * HS + 4 * c4);
+    // 16 rows x H floats of LDS (row stride HS) -> rows [16 g, +16) of a [Bp][H] panel: one float4 per thread at H = 128.
+    // In two halves: the LDS read where the rows are complete, the stores behind the MFMAs of the layer that consumes the
+    // same rows.  Nothing reads the panel before the next launch, and a wave issues in order: a store ahead of the layer
+    // would put the LDS round trip of its data in front of the layer's first MFMA.
+    // (256-wide tiles keep the store at the read: their register file is full, two more float4 across the MFMAs spill)
+    constexpr int kPub = (kRows * (H / 4) + kThreadsU - 1) / kThreadsU;
+    constexpr bool kPubLate = HT <= kNW;
+    float4 pub[kPub];
+    auto publish_read = [&](const float* src) {
+#pragma unroll
+        for (int q = 0; q < kPub; ++q) {
+            const int i = tid + q * kThreadsU, r = i / (H / 4), c4 = i - r * (H / 4);
+            if (i < kRows * (H / 4)) pub[q] = *reinterpret_cast<const float4*>(src + r * HS + 4 * c4);
         }
+    };
+    auto publish_store = [&](float* panel) {
+        float* dst = panel + (long)g * kRows * H;
+#pragma unroll
+        for (int q = 0; q < kPub; ++q) {
+            const int i = tid + q * kThreadsU, r = i / (H / 4), c4 = i - r * (H / 4);
+            if (i < kRows * (H / 4)) *reinterpret_cast<float4*>(dst + (long)r * H + 4 * c4) = pub[q];
+        }
+    };
+    // ahead of a layer's MFMAs / behind them (the scheduling barrier keeps the compiler from taking the stores back up)
+    auto publish_begin = [&](const float* src, float* panel) {
+        publish_read(src);
+        if constexpr (!kPubLate) publish_store(panel);
+    };
+    auto publish_end = [&](float* panel) {
+        if constexpr (kPubLate) { __builtin_amdgcn_sched_barrier(0); publish_store(panel); }
     };
     const long sp_plane = SPLIT ? (long)u.sp.Bp * H : 0;
 
@@ -465,7 +492,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     for (int l = 1; l < depth; ++l) {
         const float* Hp = sH + (long)(l - 1) * kRows * HS;
         float* Hc = sH + (long)l * kRows * HS;
-        if (SPLIT) publish_rows(Hp, u.sp.hbuf[which] + (long)(l - 1) * sp_plane);      // h_{l-1}: the K-panel of dW_l
+        if (SPLIT) publish_begin(Hp, u.sp.hbuf[which] + (long)(l - 1) * sp_plane);     // h_{l-1}: the K-panel of dW_l
         for (int nt = wave; nt < HT; nt += kNW) {
             const int o = nt * 16 + (lane & 15);
             f32x4 acc;
@@ -487,10 +514,9 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
-            
         }
+        if (SPLIT) publish_end(u.sp.hbuf[which] + (long)(l - 1) * sp_plane);
         __syncthreads();
-        
     }
     PPOAF_STAMP(4);
     const float* Hlast = sH + (long)(depth - 1) * kRows * HS;
@@ -509,74 +535,47 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     __syncthreads();
     PPOAF_STAMP(5);
 
-    // ---- distribution head + loss terms for this workgroup's rows (K6 + K3)
+    // ---- distribution head + loss terms for this workgroup's rows (K6 + K3): the row part only -- d loss / d out is what
+    //      the backward pass waits for.  The block's loss partials and the critic's values leave at the end of the body.
     if (wave == 0) {
-        ppo_head_loss<NT>(u, which, g, out_dim, P + nd.log_std_off, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
+        if constexpr (TABLES) asm volatile("; ppoaf_rowtile_head_rows_begin");
+        ppo_head_rows<NT>(u, which, out_dim, P + nd.log_std_off, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
+        if constexpr (TABLES) asm volatile("; ppoaf_rowtile_head_rows_end");
+        PPOAF_STAMP_W(0, 0);
     }
     __syncthreads();
+    if constexpr (TABLES) asm volatile("; ppoaf_rowtile_middle_begin");
     PPOAF_STAMP(6);
 
-    // ---- output layer backward (weights from LDS).  Operands are pulled into registers with
-    //      independent LDS reads first; a read-per-FMA loop is LDS-latency bound (~64 cycles each).
+    // ---- output layer backward, the part the hidden backward waits for: dz_last = (dOut . W_out) * act'(Hlast), on all
+    //      eight waves -- 16 rows x 32 lane groups of H / 32 adjacent columns (weights from LDS; every element adds its
+    //      out_dim products in the order k = 0, 1, ...).  Nothing between the two barriers touches global memory.
     {
-        if (tid < H) {
-            const int i = tid;
-            float h[kRows];
+        constexpr int CP = H / 32;
+        static_assert(kThreadsU == 32 * kRows && H % 32 == 0, "dz_last: 32 lane groups per row");
+        const int s = tid >> 5, c0 = (tid & 31) * CP;
+        float d[8];
+        const float4 d0 = *reinterpret_cast<const float4*>(sDOut + s * kMaxOut);
+        const float4 d1 = *reinterpret_cast<const float4*>(sDOut + s * kMaxOut + 4);
+        d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
+        float hv[CP], acc[CP], wv[CP];
+        lds_read_adjacent<CP>(Hlast + s * HS + c0, hv);
 #pragma unroll
-            for (int s = 0; s < kRows; ++s) h[s] = Hlast[s * HS + i];
-            for (int k = 0; k < out_dim; ++k) {
-                float d[kRows];
+        for (int ii = 0; ii < CP; ++ii) acc[ii] = 0.f;
 #pragma unroll
-                for (int s = 0; s < kRows; ++s) d[s] = sDOut[s * kMaxOut + k];
-                float acc = 0.f;
-#pragma unroll
-                for (int s = 0; s < kRows; ++s) acc = fmaf(d[s], h[s], acc);
-                slab[offW(depth) + (long)k * H + i] = acc;
-            }
-        }
-        // (SPLIT: the padding slots of the segment are written too, as zeros -- the partials row lives in a workspace whose
-        //  layout changes with the mini-batch size, so nothing in it may be assumed to be zero; a slab's padding is never touched)
-        const int out_pad = SPLIT ? ((out_dim + 3) & ~3) : out_dim;
-        if (tid >= 256 && tid < 256 + out_pad) {
-            const int k = tid - 256;
-            float acc = 0.f;
+        for (int k = 0; k < 8; ++k) {
             if (k < out_dim) {
+                lds_read_adjacent<CP>(sWout + k * H + c0, wv);
 #pragma unroll
-                for (int s = 0; s < kRows; ++s) acc += sDOut[s * kMaxOut + k];
+                for (int ii = 0; ii < CP; ++ii) acc[ii] = fmaf(d[k], wv[ii], acc[ii]);
             }
-            slab[offB(depth) + k] = acc;
         }
-        if (which == 0 && u.head_kind == PPOAF_HEAD_GAUSSIAN && tid >= 320 && tid < 320 + out_pad) {
-            const int d = tid - 320;
-            float acc = 0.f;
-            if (d < out_dim) {
 #pragma unroll
-                for (int s = 0; s < kRows; ++s) acc += sOut[s * kMaxOut + 8 + d];
-            }
-            slab[nd.log_std_off + d] = acc;
-        }
-        // dz_last = (dOut . W_out) * act'(Hlast): waves 4..7 (the others store dW_out above)
-        if (tid >= 256) {
-            const int t2 = tid - 256;
-            const int s = t2 >> 4, ig = t2 & 15;
-            float d[8];
-            const float4 d0 = *reinterpret_cast<const float4*>(sDOut + s * kMaxOut);
-            const float4 d1 = *reinterpret_cast<const float4*>(sDOut + s * kMaxOut + 4);
-            d[0] = d0.x; d[1] = d0.y; d[2] = d0.z; d[3] = d0.w; d[4] = d1.x; d[5] = d1.y; d[6] = d1.z; d[7] = d1.w;
-            float hv[HT], acc[HT];
-#pragma unroll
-            for (int ii = 0; ii < HT; ++ii) { hv[ii] = Hlast[s * HS + ig + 16 * ii]; acc[ii] = 0.f; }
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                if (k < out_dim) {
-#pragma unroll
-                    for (int ii = 0; ii < HT; ++ii) acc[ii] = fmaf(d[k], sWout[k * H + ig + 16 * ii], acc[ii]);
-                }
-            }
-#pragma unroll
-            for (int ii = 0; ii < HT; ++ii) sD0[s * HS + ig + 16 * ii] = acc[ii] * act_bwd(hv[ii], act);
-        }
+        for (int ii = 0; ii < CP; ++ii) acc[ii] = acc[ii] * act_bwd(hv[ii], act);
+        lds_write_adjacent<CP>(sD0 + s * HS + c0, acc);
     }
+    PPOAF_STAMP_W(2, 0); PPOAF_STAMP_W(3, 4); PPOAF_STAMP_W(4, 5);
+    if constexpr (TABLES) asm volatile("; ppoaf_rowtile_middle_end");
     __syncthreads();
     PPOAF_STAMP(7);
 
@@ -585,7 +584,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     float* Dn = sD1;
     for (int l = depth - 1; l >= 1; --l) {
         const float* Hin = sH + (long)(l - 1) * kRows * HS;
-        if (SPLIT) publish_rows(Dc, u.sp.dbuf[which] + (long)l * sp_plane);            // dz_l: the other panel of dW_l, db_l
+        if (SPLIT) publish_begin(Dc, u.sp.dbuf[which] + (long)l * sp_plane);           // dz_l: the other panel of dW_l, db_l
         // dgrad first (its operands were prefetched): dh[s][i] = sum_o dz[s][o] * W[o][i]
         for (int nt = wave; nt < HT; nt += kNW) {
             f32x4 acc;
@@ -602,6 +601,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
                 Dn[s * HS + i] = acc[r] * act_bwd(Hin[s * HS + i], act);
             }
         }
+        if (SPLIT) publish_end(u.sp.dbuf[which] + (long)l * sp_plane);
         if (l == depth - 1) PPOAF_STAMP(10);
         // wgrad: dW[o][i] = sum_s dz[s][o] * Hin[s][i]   (SPLIT: left to the wgrad launch, over all rows at once)
         if (!SPLIT) {
@@ -626,7 +626,8 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
 
     // ---- first layer backward: dW0[o][i] = sum_s dz0[s][o] * x[s][i] on MFMA against the padded sX
     if (SPLIT) {
-        publish_rows(Dc, u.sp.dbuf[which]);                   // dz_0 (its K-panel is x, published after the gather)
+        publish_read(Dc);                                     // dz_0 (its K-panel is x, published after the gather)
+        publish_store(u.sp.dbuf[which]);
     } else {
         for (int mt = wave; mt < HT; mt += kNW)
             wgrad_mtile(Dc, HS, sX, INP, mt * 16, NT0, in_dim, lane, slab + offW(0), in_dim);
@@ -636,6 +637,56 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             for (int s = 0; s < kRows; ++s) acc += Dc[s * HS + o];
             slab[offB(0) + o] = acc;
         }
+    }
+    PPOAF_STAMP_W(6, 0);
+
+    // ---- what nothing inside this launch consumes, last: the output layer's weight / bias gradients and the Gaussian
+    //      head's d / d log_std column sums (-> the slab, or the block's row of the output partials), the block's loss
+    //      partials and the critic's values.  Hlast, sDOut, sOut, sRow and the terms parked in sActF are as the middle of
+    //      the body left them.  (Measured against running it behind the dgrad MFMAs of the first hidden-backward layer,
+    //      where it delays that layer's barrier: profiles/middle_phase_stamps_C2.txt.)
+    //      Operands are pulled into registers with independent LDS reads first; a read-per-FMA loop is LDS-latency bound
+    //      (~64 cycles each).  (dW_out as one element per thread over all eight waves measured slower: same file.)
+    if (tid < H) {
+        const int i = tid;
+        float h[kRows];
+#pragma unroll
+        for (int s = 0; s < kRows; ++s) h[s] = Hlast[s * HS + i];
+        for (int k = 0; k < out_dim; ++k) {
+            float d[kRows];
+#pragma unroll
+            for (int s = 0; s < kRows; ++s) d[s] = sDOut[s * kMaxOut + k];
+            float acc = 0.f;
+#pragma unroll
+            for (int s = 0; s < kRows; ++s) acc = fmaf(d[s], h[s], acc);
+            slab[offW(depth) + (long)k * H + i] = acc;
+        }
+    }
+    {
+        // (SPLIT: the padding slots of the segment are written too, as zeros -- the partials row lives in a workspace whose
+        //  layout changes with the mini-batch size, so nothing in it may be assumed to be zero; a slab's padding is never touched)
+        const int out_pad = SPLIT ? ((out_dim + 3) & ~3) : out_dim;
+        if (tid >= 256 && tid < 256 + out_pad) {
+            const int k = tid - 256;
+            float acc = 0.f;
+            if (k < out_dim) {
+#pragma unroll
+                for (int s = 0; s < kRows; ++s) acc += sDOut[s * kMaxOut + k];
+            }
+            slab[offB(depth) + k] = acc;
+        }
+        if (which == 0 && u.head_kind == PPOAF_HEAD_GAUSSIAN && tid >= 320 && tid < 320 + out_pad) {
+            const int d = tid - 320;
+            float acc = 0.f;
+            if (d < out_dim) {
+#pragma unroll
+                for (int s = 0; s < kRows; ++s) acc += sOut[s * kMaxOut + 8 + d];
+            }
+            slab[nd.log_std_off + d] = acc;
+        }
+        if (which != 0 && wave == 6) ppo_head_values(u, sRow, sOut, lane);
+        if (wave == 7) ppo_head_block(u, which, g, sMisc, sActF, lane);
+        PPOAF_STAMP_W(5, 0); PPOAF_STAMP_W(1, 7);
     }
     if (l2_touch == 1.2345e38f) u.loss_partials[0] = l2_touch;   // keeps the early line touches alive
     PPOAF_STAMP(9);

@@ -24,7 +24,12 @@ torch.cuda.synchronize()
 lib=_lib.load(); buf=(C.c_ulonglong*32)(); lib.ppoaf_debug_read_stamps.argtypes=[C.c_void_p]; print(lib.ppoaf_debug_read_stamps(buf))
 st=np.array(list(buf),dtype=np.int64).reshape(2,16)
 names=["P0 idx/stats","P1 gatherX","P2 layer0","P3 hidden fwd","P4 out","P5 head","P6 out bwd","P7 hidden bwd","P8 layer0 bwd"]
-for w in (0,1):
-    d=np.diff(st[w,:10]); print("net",w,"total cycles",st[w,9]-st[w,0])
-    for n,x in zip(names,d): print("   %-16s %7d"%(n,x))
-    print("   first bwd layer: dgrad %d, wgrad %d, bias sums %d, barrier %d"%(st[w,10]-st[w,7], st[w,11]-st[w,10], st[w,12]-st[w,11], st[w,13]-st[w,12]))
+d=np.diff(st[0,:10]); print("net",int(os.environ.get('STAMP_NET','0')),"total cycles",st[0,9]-st[0,0])
+for n,x in zip(names,d): print("   %-16s %7d"%(n,x))
+print("   first bwd layer: dgrad %d, wgrad %d, bias sums %d, barrier %d"%(st[0,10]-st[0,7], st[0,11]-st[0,10], st[0,12]-st[0,11], st[0,13]-st[0,12]))
+# per-wave stamps (PPOAF_STAMP_W, second row): inside the head (from P5's start) and the output backward (from P6's start);
+# side work = the output layer's gradients (wave 0) and the loss partials (wave 7), from the barrier that releases P7
+w=st[1]; rel=lambda a,b: int(a-b) if a else -1
+print("   P5: sDOut written %d, partials stored %d (of %d)"%(rel(w[0],st[0,5]), rel(w[1],st[0,5]), st[0,6]-st[0,5]))
+print("   P6: at the barrier: wave 0 (dW_out) %d, wave 4 (db_out) %d, wave 5 %d (of %d)"%(rel(w[2],st[0,6]), rel(w[3],st[0,6]), rel(w[4],st[0,6]), st[0,7]-st[0,6]))
+print("   end of the body (from the last panel copy): dW_out stored %d, partials stored %d"%(rel(w[5],w[6]) if w[6] else -1, rel(w[1],w[6]) if w[6] else -1))

@@ -253,6 +253,63 @@ def fwd_bwd_report(ins):
             "set_loads_at_barrier": sorted(reached), "draining": [w for w in waits if w[0] < w[1]]}
 
 
+# ---- the middle of the row-tile body (tests/test_k12_middle_isa.py): the head's row part, and the window between the barrier
+#      that ends the head phase and the barrier that releases the hidden backward.  The TABLES flavour marks both.
+MARK_HEAD_ROWS = ("ppoaf_rowtile_head_rows_begin", "ppoaf_rowtile_head_rows_end")
+MARK_MIDDLE = ("ppoaf_rowtile_middle_begin", "ppoaf_rowtile_middle_end")
+_GSTORE = re.compile(r"^(global|buffer|flat|scratch)_(store|atomic)")
+
+
+def marked_windows(ins, marks):
+    """Every instruction some path executes between a `marks[0]` line and the first `marks[1]` line behind it, one entry per
+    begin marker: {"ins": [(op, args)], "closed": every path from the marker ends at an end marker (none runs into
+    s_endpgm or into another begin marker first)}.  Branches are followed (class Cfg), so a block the compiler has laid out
+    somewhere else in the text still counts."""
+    cfg = Cfg(ins)
+    begin, end = marks
+    out = []
+    for b0, i0 in cfg.find_all(lambda op, args: op == "marker" and args == begin):
+        seen_ins, closed, visited = [], True, set()
+        todo = [(b0, i0 + 1)]
+        while todo:
+            b, pos = todo.pop()
+            if (b, pos) in visited:
+                continue
+            visited.add((b, pos))
+            ended = False
+            for op, args in cfg.blocks[b][pos:]:
+                if op == "marker":
+                    if args == end:
+                        ended = True
+                        break
+                    if args == begin:
+                        closed, ended = False, True
+                        break
+                    continue
+                if op == "s_endpgm":
+                    closed = False
+                seen_ins.append((op, args))
+            if not ended:
+                todo.extend((s, 0) for s in cfg.succ[b])
+        out.append({"ins": seen_ins, "closed": closed})
+    return out
+
+
+def middle_report(ins):
+    """fwd_bwd, TABLES flavour: what the head's row part and the window behind the head's barrier contain that does not
+    belong on the path to the hidden backward -- stores to global memory, cross-lane round trips through the LDS crossbar
+    (`ds_bpermute` / `ds_permute`), and, for the window, barriers (it lies between two of them)."""
+    def scan(marks):
+        w = marked_windows(ins, marks)
+        flat = [x for e in w for x in e["ins"]]
+        return {"windows": len(w), "closed": all(e["closed"] for e in w), "instructions": len(flat),
+                "global_stores": [f"{op} {args}" for op, args in flat if _GSTORE.match(op)],
+                "permutes": [f"{op} {args}" for op, args in flat if op.startswith(("ds_bpermute", "ds_permute"))],
+                "barriers": sum(op == "s_barrier" for op, _ in flat),
+                "lds_writes": sum(op.startswith("ds_write") or op.startswith("ds_store") for op, _ in flat)}
+    return {"head_rows": scan(MARK_HEAD_ROWS), "middle": scan(MARK_MIDDLE)}
+
+
 def describe(kernel, ins):
     print(f"{kernel}: {sum(op not in ('label', 'marker') for op, _ in ins)} instructions")
     n, _ = scalar_waits_before_vmem(ins)
@@ -273,6 +330,9 @@ def describe(kernel, ins):
         print(f"  vmcnt waits behind the first hidden-set load, up to the S0 barrier, as (N, set loads issued): "
               f"{r['waits_after_first_set']}")
         print(f"  of these, waits for a hidden set (N < set loads issued): {r['draining']}")
+        for name, m in middle_report(ins).items():
+            print(f"  {name}: {m['windows']} windows (closed: {m['closed']}), {m['instructions']} instructions, "
+                  f"{len(m['global_stores'])} global stores, {len(m['permutes'])} ds_(b)permute, {m['barriers']} barriers")
 
 
 def main(argv):
