@@ -326,7 +326,10 @@ int ppoaf_adam_step_prenormed(float* params, const float* grads,
  * Network parameters are the flat bucket of nn.Linear tensors in module order
  * (weight [out,in] row-major then bias, each padded to 4 floats), hidden
  * layers of equal width H per network; instantiated (actor, critic) widths:
- * (32,32) (64,64) (128,128) (256,256) (128,256) (64,128); depth >= 1.
+ * (32,32) (64,64) (128,128) (256,256) (128,256) (64,128) (64,256) (32,256)
+ * (32,64); depth >= 1.  One list names them for every launch of K6+K7 and K12
+ * (csrc/ppo_update_dev.hpp: PPOAF_WIDTH_PAIRS); a critic narrower than its
+ * actor and 512-wide networks are refused.
  * ------------------------------------------------------------------------ */
 #define PPOAF_ACT_RELU        0
 #define PPOAF_ACT_LEAKY_RELU  1      /* negative slope 0.01 (nn.LeakyReLU default) */
@@ -403,7 +406,8 @@ typedef struct {
      * confinement costs 1 % (C2).  Placement only changes speed. */
     int32_t xcd_half;
     /* ABI 6.  1 (split-wgrad chain only; ignored otherwise): the 16-row tiles of a 256-wide network of depth 2 .. 4 run on
-     * PAIRS of workgroups that split every hidden layer pass by output columns and exchange the halves through tagged
+     * PAIRS of workgroups (a 32-, 64- or 128-wide actor beside such a critic keeps one workgroup per tile; a 256-wide actor
+     * beside it must be of depth 2 .. 4 itself, else neither network runs in pairs) that split every hidden layer pass by output columns and exchange the halves through tagged
      * records behind the panels of split_workspace (csrc/ppo_update_rowpair.hpp) -- ppoaf_ppo_update_split_workspace_bytes()
      * then includes the record region.  Results are BITWISE those of row_pairs = 0.  The tag is the mini-batch index + 1:
      * the caller zeroes split_workspace before the first launch and whenever mini-batch indices restart (every epoch).
@@ -422,7 +426,8 @@ int ppoaf_ppo_update_fwd_bwd_timed(const ppoaf_ppo_update_args_t* args, void* st
                                    ppoaf_stream_t stream);
 /* Host-only query (added within ABI 7: no field or call changed), nothing is launched and no pointer of args is read:
  * PPOAF_OK when fwd_bwd accepts these shapes (layer tables, bucket, head, batch size, the row-tile body's LDS, the
- * instantiated width pairs), else PPOAF_E_INVALID with the launch's own message in ppoaf_last_error().  The host
+ * instantiated width pairs: the nine listed above ppoaf_mlp_desc_t, for every depth and in_dim whose row tile fits the LDS
+ * of the wider network), else PPOAF_E_INVALID with the launch's own message in ppoaf_last_error().  The host
  * driver's scope test (fused_update.py: FusedPolicyUpdate.unsupported_reason) asks it. */
 int ppoaf_ppo_update_check(const ppoaf_ppo_update_args_t* args);
 int ppoaf_ppo_update_reduce(const ppoaf_ppo_update_args_t* args, int compute_norms, ppoaf_stream_t stream);

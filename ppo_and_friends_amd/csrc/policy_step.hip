@@ -9,7 +9,7 @@
 // grid = 2 * ceil(E/16) workgroups (XCD-grouped like the update kernel: blocks 0-3 mod 8 actor, 4-7
 // critic), 512 threads: 16 env rows per workgroup, hidden layers on v_mfma_f32_16x16x4_f32 with the same
 // tile code as the update's forward, so a row's log-prob here and in the first mini-batch agree bit for bit.
-#include "action_heads.hpp"
+#include "ppo_update_dev.hpp"        // the list of instantiated width pairs (and action_heads.hpp)
 
 namespace ppoaf {
 
@@ -147,12 +147,9 @@ static int launch_step(const StepDev& u, size_t lds, hipStream_t s) {
 template <bool XH>
 static int launch_widths(const StepDev& u, size_t lds, hipStream_t s) {
     const int ha = u.net[0].H, hc = u.net[1].H;
-    if (ha == 32 && hc == 32) return launch_step<2, 2, XH>(u, lds, s);
-    if (ha == 64 && hc == 64) return launch_step<4, 4, XH>(u, lds, s);
-    if (ha == 128 && hc == 128) return launch_step<8, 8, XH>(u, lds, s);
-    if (ha == 256 && hc == 256) return launch_step<16, 16, XH>(u, lds, s);
-    if (ha == 128 && hc == 256) return launch_step<8, 16, XH>(u, lds, s);
-    if (ha == 64 && hc == 128) return launch_step<4, 8, XH>(u, lds, s);
+#define PPOAF_WIDTH_PAIR_CALL_(A, C) launch_step<A / 16, C / 16, XH>(u, lds, s)
+    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+#undef PPOAF_WIDTH_PAIR_CALL_
     set_error("policy_step: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_E_INVALID;
 }

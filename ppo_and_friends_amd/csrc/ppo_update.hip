@@ -1,6 +1,7 @@
 // K12: fused PPO mini-batch update for MLP actor / critic networks.
 // One iteration of PPO._ppo_batch_train (ppo.py:2292-2469) =
-//   ppo_update_fwd_bwd_kernel  (gather + normalisers + forward + head/loss + backward -> slabs)
+//   ppo_update_fwd_bwd_kernel  (gather + normalisers + forward + head/loss + backward -> slabs; ppo_update_fwd_bwd.hpp:
+//                               instantiated here and, for the narrow-actor width pairs, in ppo_update_narrow.hip)
 //   ppo_update_reduce_kernel   (slabs -> gradient bucket, loss partials -> totals [, norms])
 //   ppo_update_adam_kernel     (clip + Adam for both networks, advance the cursor)
 //
@@ -12,60 +13,11 @@
 // writes its weight-gradient partial to a private slab with plain coalesced stores; the slabs
 // are summed in a fixed order by the reduce kernel, so results are bitwise reproducible (float
 // atomics would not be) and nothing needs zeroing.
-#include "ppo_update_rowpair.hpp"
-#include <hip/hip_ext.h>
+#include "ppo_update_fwd_bwd.hpp"
 #include "peer_exchange_device.hpp"
 #include <cstdlib>
 
 namespace ppoaf {
-
-
-// 1-D grid of 2 * n_wg workgroups.  Every workgroup of a network streams that network's whole
-// weight set, so workgroups of one network are placed on the same XCDs (blocks b and b + 8 share
-// an XCD under the observed round-robin dispatch): XCDs 0-3 take the actor, 4-7 the critic, and
-// each weight line is then fetched into an XCD's L2 once for its 4 consumers instead of once per
-// pair.  Placement only changes speed; nothing depends on it.
-template <int HTA, int HTC, bool SPLIT>
-__global__ __launch_bounds__(kThreadsU) void ppo_update_fwd_bwd_kernel(UpdateDev u) {
-    const int b = rowtile_request_args(u, blockIdx.x);     // one round trip for the argument block, then the cursor's
-    int which = (b >> 2) & 1;                              // b % 8 in {0..3} -> actor, {4..7} -> critic
-    int g = ((b >> 3) << 2) | (b & 3);
-    if (u.confine) {                                // one half of the XCDs left to another chain (args->xcd_half)
-        const int x = b & 7;
-        if ((x >> 2) != u.confine - 1) return;
-        which = (x & 3) >> 1;                              // the half's first two XCDs: actor, the other two: critic
-        g = ((b >> 3) << 1) | (x & 1);
-    }
-    if (g >= u.n_wg) return;                               // uniform per workgroup, before any barrier
-    if (which == 0) ppo_update_fwd_bwd_body<HTA, SPLIT>(u, 0, g);
-    else ppo_update_fwd_bwd_body<HTC, SPLIT>(u, 1, g);
-}
-
-// args->row_pairs (split-wgrad chain): a 256-wide network's row tiles on pairs of workgroups (ppo_update_rowpair.hpp); the
-// other network's tiles as above.  Workgroup b runs on XCD b % 8; slot j = b / 8 of an XCD holds tile pair member j & 1.
-template <int HTA, int HTC>
-__global__ __launch_bounds__(kThreadsU) void ppo_update_fwd_bwd_pair_kernel(UpdateDev u, PairDev pd) {
-    const int b = blockIdx.x, x = b & 7, j = b >> 3;
-    int which, g, hf = 0;
-    if (u.confine) {
-        if ((x >> 2) != u.confine - 1) return;
-        which = (x & 3) >> 1;
-        if (which == 0 ? HTA == 16 : HTC == 16) { hf = j & 1; g = ((j >> 1) << 1) | (x & 1); }
-        else g = (j << 1) | (x & 1);
-    } else {
-        which = x >> 2;
-        if (which == 0 ? HTA == 16 : HTC == 16) { hf = j & 1; g = ((j >> 1) << 2) | (x & 3); }
-        else g = (j << 2) | (x & 3);
-    }
-    if (g >= u.n_wg) return;                               // uniform per workgroup, before any barrier
-    if (which == 0) {
-        if constexpr (HTA == 16) ppo_update_fwd_bwd_pair_body<16>(u, 0, g, hf, pd);
-        else ppo_update_fwd_bwd_body_as<HTA, true, false>(u, 0, g);     // (the 256-wide partner's pairs set this launch's time)
-    } else {
-        if constexpr (HTC == 16) ppo_update_fwd_bwd_pair_body<16>(u, 1, g, hf, pd);
-        else ppo_update_fwd_bwd_body_as<HTC, true, false>(u, 1, g);
-    }
-}
 
 // slabs -> gradient bucket in a fixed order.  The slabs were just written by other CUs, so every
 // read is a cold miss: each thread owns one float4 column and puts the loads of 8 slabs in flight
@@ -384,52 +336,9 @@ static int fwd_bwd_fits(const UpdateDev& u) {
     const size_t lds = fwd_bwd_lds_bytes(u);
     PPOAF_REQUIRE(lds <= 160 * 1024, "ppo_update_fwd_bwd: needs %zu B of LDS (> 160 KiB)", lds);
     const int ha = u.net[0].H, hc = u.net[1].H;
-    PPOAF_REQUIRE((ha == 32 && hc == 32) || (ha == 64 && hc == 64) || (ha == 128 && hc == 128) || (ha == 256 && hc == 256) ||
-                      (ha == 128 && hc == 256) || (ha == 64 && hc == 128),
+    PPOAF_REQUIRE(width_pair_instantiated(ha, hc),
                   "ppo_update_fwd_bwd: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_OK;
-}
-
-template <int HTA, int HTC, bool SPLIT>
-static int launch_fwd_bwd_as(const UpdateDev& u, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_update_fwd_bwd_kernel<HTA, HTC, SPLIT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
-    const unsigned grid = u.confine ? 8u * (unsigned)((u.n_wg + 1) / 2) : 8u * (unsigned)((u.n_wg + 3) / 4);     // groups of 4 actor + 4 critic blocks
-    if (e0 || e1)        // the kernel's own begin / end stamped into the events (bench.py: roofline_update)
-        hipExtLaunchKernelGGL((ppo_update_fwd_bwd_kernel<HTA, HTC, SPLIT>), dim3(grid), dim3(kThreadsU), lds, s, e0, e1, 0, u);
-    else
-        hipLaunchKernelGGL((ppo_update_fwd_bwd_kernel<HTA, HTC, SPLIT>), dim3(grid), dim3(kThreadsU), lds, s, u);
-    return check_launch("ppo_update_fwd_bwd");
-}
-
-// split-wgrad chain with args->row_pairs: the 256-wide networks' tiles on workgroup pairs
-template <int HTA, int HTC>
-static int launch_fwd_bwd_pairs(const UpdateDev& u, const PairDev& pd, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-    static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_update_fwd_bwd_pair_kernel<HTA, HTC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
-    // slots per XCD: two per tile of a paired network (both networks share the grid: the wider need decides)
-    const unsigned per_slot = u.confine ? 2u : 4u;
-    const unsigned grid = 8u * 2u * (unsigned)((u.n_wg + per_slot - 1) / per_slot);
-    if (e0 || e1)
-        hipExtLaunchKernelGGL((ppo_update_fwd_bwd_pair_kernel<HTA, HTC>), dim3(grid), dim3(kThreadsU), lds, s, e0, e1, 0, u, pd);
-    else
-        hipLaunchKernelGGL((ppo_update_fwd_bwd_pair_kernel<HTA, HTC>), dim3(grid), dim3(kThreadsU), lds, s, u, pd);
-    return check_launch("ppo_update_fwd_bwd(row pairs)");
-}
-
-template <int HTA, int HTC>
-static int launch_fwd_bwd(const UpdateDev& u, size_t lds, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-    return u.split ? launch_fwd_bwd_as<HTA, HTC, true>(u, lds, s, e0, e1) : launch_fwd_bwd_as<HTA, HTC, false>(u, lds, s, e0, e1);
 }
 
 }  // namespace ppoaf
@@ -449,24 +358,13 @@ extern "C" int ppoaf_ppo_update_fwd_bwd_timed(const ppoaf_ppo_update_args_t* arg
     if (rc) return rc;
     const size_t lds = fwd_bwd_lds_bytes(u);
     hipStream_t s = (hipStream_t)stream;
-    // instantiated (actor width, critic width) pairs; the host falls back to the torch path otherwise
-    const int ha = u.net[0].H, hc = u.net[1].H;
-    if (u.split && args->row_pairs && (pair_eligible(u.net[0]) || pair_eligible(u.net[1]))) {
-        PairDev pd;
-        const size_t lds_pairs = lds;
-        pair_region_layout(u, &pd, reinterpret_cast<char*>(args->split_workspace) + pair_region_offset(u));
-        if (ha == 128 && hc == 256 && pd.net_off[1]) return launch_fwd_bwd_pairs<8, 16>(u, pd, lds_pairs, s, e0, e1);
-        if (ha == 256 && hc == 256 && pd.net_off[0] && pd.net_off[1]) return launch_fwd_bwd_pairs<16, 16>(u, pd, lds_pairs, s, e0, e1);
-        // other shapes (a 256-wide network of depth 1 or > 4, a 256-wide actor beside a narrower critic): one workgroup per tile
-    }
-    if (ha == 32 && hc == 32) return launch_fwd_bwd<2, 2>(u, lds, s, e0, e1);
-    if (ha == 64 && hc == 64) return launch_fwd_bwd<4, 4>(u, lds, s, e0, e1);
-    if (ha == 128 && hc == 128) return launch_fwd_bwd<8, 8>(u, lds, s, e0, e1);
-    if (ha == 256 && hc == 256) return launch_fwd_bwd<16, 16>(u, lds, s, e0, e1);
-    if (ha == 128 && hc == 256) return launch_fwd_bwd<8, 16>(u, lds, s, e0, e1);
-    if (ha == 64 && hc == 128) return launch_fwd_bwd<4, 8>(u, lds, s, e0, e1);
-    set_error("ppo_update_fwd_bwd: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
-    return PPOAF_E_INVALID;
+    // the instantiated (actor width, critic width) pairs (ppo_update_dev.hpp: PPOAF_WIDTH_PAIRS; the host falls back to the
+    // torch path otherwise): this translation unit's share of the list, then ppo_update_narrow.hip's
+    const FwdBwdLaunch L = {u, args, lds, s, e0, e1};
+#define PPOAF_WIDTH_PAIR_CALL_(A, C) fwd_bwd_launch_pair<A, C>(L)
+    PPOAF_WIDTH_PAIR_LADDER_OF(PPOAF_WIDTH_PAIRS_IN_UPDATE, u.net[0].H, u.net[1].H)
+#undef PPOAF_WIDTH_PAIR_CALL_
+    return fwd_bwd_launch_narrow(L);
 }
 
 extern "C" int ppoaf_ppo_update_check(const ppoaf_ppo_update_args_t* args) {

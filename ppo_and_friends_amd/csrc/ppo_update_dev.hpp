@@ -33,6 +33,28 @@ static __device__ unsigned long long g_ppo_update_stamps[2][16];
 #define PPOAF_STAMP_W(k, w) do {} while (0)
 #endif
 
+// The instantiated (actor width, critic width) pairs of K6+K7 (policy_step.hip) and K12 (fwd_bwd, the wgrad launch, the
+// fused tail): the ONE list.  Every dispatcher expands it into its `if` ladder and fwd_bwd_fits / the ladders' last line
+// refuse what it does not name, so no launch can accept a pair that another one refuses.  A critic is never narrower than
+// its actor here; 512-wide networks need a tile width, LDS budgets and a weight-gradient grid of their own.
+// (two sub-lists: fwd_bwd's kernels are spread over ppo_update.hip and ppo_update_narrow.hip, ppo_update_fwd_bwd.hpp)
+#define PPOAF_WIDTH_PAIRS_IN_UPDATE(X) X(32, 32) X(64, 64) X(128, 128) X(256, 256) X(128, 256) X(64, 128)
+#define PPOAF_WIDTH_PAIRS_IN_NARROW(X) X(64, 256) X(32, 256) X(32, 64)
+#define PPOAF_WIDTH_PAIRS(X) PPOAF_WIDTH_PAIRS_IN_UPDATE(X) PPOAF_WIDTH_PAIRS_IN_NARROW(X)
+// one rung per pair: with PPOAF_WIDTH_PAIR_CALL_(A, C) defined as the expression that launches pair <A, C>,
+// PPOAF_WIDTH_PAIR_LADDER(ha, hc) returns its value for the pair (ha, hc) and falls through for a pair not in the list
+// (PPOAF_WIDTH_PAIR_LADDER_OF: over one of the sub-lists)
+#define PPOAF_WIDTH_PAIR_RUNG_(A, C) if (ppoaf_ha_ == A && ppoaf_hc_ == C) return PPOAF_WIDTH_PAIR_CALL_(A, C);
+#define PPOAF_WIDTH_PAIR_LADDER_OF(LIST, ha, hc) \
+    { const int ppoaf_ha_ = (ha), ppoaf_hc_ = (hc); LIST(PPOAF_WIDTH_PAIR_RUNG_) }
+#define PPOAF_WIDTH_PAIR_LADDER(ha, hc) PPOAF_WIDTH_PAIR_LADDER_OF(PPOAF_WIDTH_PAIRS, ha, hc)
+inline bool width_pair_instantiated(const int ha, const int hc) {
+#define PPOAF_WIDTH_PAIR_CALL_(A, C) true
+    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+#undef PPOAF_WIDTH_PAIR_CALL_
+    return false;
+}
+
 // Per-mini-batch panels shared by the layered mode of the two-XCD persistent kernel and by the split-wgrad chain
 // (fwd_bwd publishes them, the wgrad launch consumes them): workspace memory, 256-byte aligned pieces.
 struct WsDev {
@@ -121,6 +143,12 @@ struct PairDev {
 
 inline bool pair_eligible(const NetDev& n) { return n.H == 256 && n.depth >= 2 && n.depth <= 4; }
 inline int pair_phases(const NetDev& n) { return 2 * n.depth - 3; }
+// args->row_pairs takes effect (fwd_bwd's dispatch and ppoaf_ppo_update_row_pairs_error_offset both ask here): an eligible
+// critic beside a narrower actor, whose tiles keep one workgroup each, or two eligible networks.  Other shapes (a 256-wide
+// network of depth 1 or > 4, a 256-wide actor that is not eligible itself): one workgroup per tile.
+inline bool pairs_run(const NetDev& a, const NetDev& c) {
+    return width_pair_instantiated(a.H, c.H) && pair_eligible(c) && (a.H < 256 || pair_eligible(a));
+}
 // the region's place does not move with the mini-batch size (a tail mini-batch's panels are laid out differently, and
 // nothing but records may ever be stored where records are polled): behind the panels of the FULL batch size
 inline size_t pair_region_offset(const UpdateDev& u) {

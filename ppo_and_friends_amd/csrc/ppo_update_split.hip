@@ -144,9 +144,7 @@ extern "C" int ppoaf_ppo_update_row_pairs_error_offset(const ppoaf_ppo_update_ar
     UpdateDev u;
     int rc = make_update_dev(&a, u);
     if (rc) return rc;
-    const int ha = u.net[0].H, hc = u.net[1].H;
-    const bool pairs = a.row_pairs && ((ha == 128 && hc == 256 && pair_eligible(u.net[1])) ||
-                                       (ha == 256 && hc == 256 && pair_eligible(u.net[0]) && pair_eligible(u.net[1])));
+    const bool pairs = a.row_pairs && pairs_run(u.net[0], u.net[1]);      // the condition of fwd_bwd's dispatch
     *offset_out = pairs ? (int64_t)pair_region_offset(u) : -1;
     return PPOAF_OK;
 }
@@ -168,12 +166,9 @@ extern "C" int ppoaf_ppo_update_wgrad(const ppoaf_ppo_update_args_t* args, ppoaf
     PPOAF_REQUIRE(u.split, "ppo_update_wgrad: args->split_workspace is not set (the slab chain uses ppoaf_ppo_update_reduce)");
     hipStream_t s = (hipStream_t)stream;
     const int ha = u.net[0].H, hc = u.net[1].H;
-    if (ha == 32 && hc == 32) return wgrad_launch<32, 32>(u, s);
-    if (ha == 64 && hc == 64) return wgrad_launch<64, 64>(u, s);
-    if (ha == 128 && hc == 128) return wgrad_launch<128, 128>(u, s);
-    if (ha == 256 && hc == 256) return wgrad_launch<256, 256>(u, s);
-    if (ha == 128 && hc == 256) return wgrad_launch<128, 256>(u, s);
-    if (ha == 64 && hc == 128) return wgrad_launch<64, 128>(u, s);
+#define PPOAF_WIDTH_PAIR_CALL_(A, C) wgrad_launch<A, C>(u, s)
+    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+#undef PPOAF_WIDTH_PAIR_CALL_
     set_error("ppo_update_wgrad: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_E_INVALID;
 }

@@ -460,12 +460,9 @@ static int tail_launch(const UpdateDev& u, const TailDev& td, const TailXchg* xc
 
 static int tail_dispatch(const UpdateDev& u, const TailDev& td, const TailXchg* xc, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     const int ha = u.net[0].H, hc = u.net[1].H;
-    if (ha == 32 && hc == 32) return tail_launch<32, 32>(u, td, xc, s, e0, e1);
-    if (ha == 64 && hc == 64) return tail_launch<64, 64>(u, td, xc, s, e0, e1);
-    if (ha == 128 && hc == 128) return tail_launch<128, 128>(u, td, xc, s, e0, e1);
-    if (ha == 256 && hc == 256) return tail_launch<256, 256>(u, td, xc, s, e0, e1);
-    if (ha == 128 && hc == 256) return tail_launch<128, 256>(u, td, xc, s, e0, e1);
-    if (ha == 64 && hc == 128) return tail_launch<64, 128>(u, td, xc, s, e0, e1);
+#define PPOAF_WIDTH_PAIR_CALL_(A, C) tail_launch<A, C>(u, td, xc, s, e0, e1)
+    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+#undef PPOAF_WIDTH_PAIR_CALL_
     set_error("ppo_update_wgrad_adam: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_E_INVALID;
 }

@@ -720,6 +720,10 @@ class FusedLstmUpdate(FusedEpoch):
         return False                   # (no C chain for this driver: the all-reduce fallback is the eager loop)
 
 
+# the (actor width, critic width) pairs K6+K7 and K12 are instantiated for (csrc/ppo_update_dev.hpp: PPOAF_WIDTH_PAIRS)
+WIDTH_PAIRS = ((32, 32), (64, 64), (128, 128), (256, 256), (128, 256), (64, 128), (64, 256), (32, 256), (32, 64))
+
+
 class FusedPolicyUpdate(FusedEpoch):
     """Host driver of K12 (csrc/ppo_update.hip): one epoch of PPO._ppo_batch_train (ppo.py:2274-2485) for an MLP
     actor/critic."""
@@ -742,7 +746,7 @@ class FusedPolicyUpdate(FusedEpoch):
             return "critic must have one output"
         if a.offset != 0 or c.offset != a.size:
             return "actor and critic buckets are not adjacent"
-        if (a.hidden, c.hidden) not in ((32, 32), (64, 64), (128, 128), (256, 256), (128, 256), (64, 128)):
+        if (a.hidden, c.hidden) not in WIDTH_PAIRS:
             return f"hidden widths (actor {a.hidden}, critic {c.hidden}) are not an instantiated pair"
         if batch_size < 2:
             return "batch size < 2"
@@ -843,7 +847,8 @@ class FusedPolicyUpdate(FusedEpoch):
     pair_launches = 0                  # fwd_bwd launches issued with row pairs in this process (graph replays not counted)
 
     def pairs_reason(self):
-        """'' when fwd_bwd runs the 256-wide networks' row tiles on workgroup pairs, else why not."""
+        """'' when fwd_bwd runs the 256-wide networks' row tiles on workgroup pairs, else why not (a narrower actor beside
+        such a critic keeps one workgroup per tile)."""
         if not self.row_pairs:
             return "off (row_pairs = False)"
         if getattr(self, "_pairs_disabled", ""):
@@ -852,8 +857,8 @@ class FusedPolicyUpdate(FusedEpoch):
             return "the slab chain runs (" + self.split_reason + ")"
         a, c = self.actor_desc, self.critic_desc
         ok = lambda d: d.hidden == 256 and 2 <= d.depth <= 4
-        if not ((a.hidden == 128 and ok(c)) or (ok(a) and ok(c))):
-            return "no 256-wide network of depth 2 .. 4 (beside a 128- or 256-wide actor)"
+        if not (ok(c) and (a.hidden < 256 or ok(a))):          # (csrc/ppo_update_dev.hpp: pairs_run)
+            return "no 256-wide critic of depth 2 .. 4 beside a 32-, 64- or 128-wide actor or a 256-wide actor of depth 2 .. 4"
         return ""
 
     # ---- fused tail of the split-wgrad chain: fwd_bwd -> wgrad + clip norms + Adam in one launch (two launches per mini-batch)

@@ -1,0 +1,100 @@
+"""
+One rollout and one update epoch of an MLP policy at `lunar_lander`'s dimensions -- 8 observations, Discrete(4), 64-wide
+actor and 256-wide critic of depth 3, 4096 envs x 128 steps, batch 256 (2048 mini-batches per epoch, hipGraph replay) -- on
+the fused kernels (update_mode="fused": K6+K7 rollout steps, K12 update on the pair <64, 256>: the critic's row tiles on
+workgroup pairs, the fused tail) against the torch-ROCm path (update_mode="torch": what "auto" ran for this width pair
+before the pair was instantiated).  A 128 / 256 policy at the same dimensions runs on the fused path beside them: the
+critic's row pairs set fwd_bwd's time in both, so the narrower actor should cost nothing.
+
+All legs are warmed up, then timed alternately `--repeats` times each in this one process, each timing between two device
+synchronisations; seconds are printed as median and spread (min .. max) per leg, then one JSON line.
+
+    python tools/width_pairs_bench.py [--repeats 5] [--envs 4096] [--steps 128]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LEGS = {"64x256_fused": ((64, 256), "fused"), "64x256_torch": ((64, 256), "torch"), "128x256_fused": ((128, 256), "fused")}
+BATCH = 256
+
+
+def make_ppo(widths, mode, E, T, seed=1):
+    from ppo_and_friends_amd.ppo import PPO
+    from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
+    from ppo_and_friends_amd.spaces import Box, Discrete
+    dev = torch.device("cuda", 0)
+    env_gen = lambda: SyntheticFixedLengthEnv(E, 8, Discrete(4), T, dev, reward="ones", seed=1234)
+    sp = Box(-np.inf, np.inf, (8,), np.float32)
+    pargs = dict(actor_kw_args=dict(hidden_size=widths[0], hidden_depth=3), critic_kw_args=dict(hidden_size=widths[1], hidden_depth=3))
+    return PPO(env_gen, {"p": (None, sp, sp, Discrete(4), pargs)}, device=dev, random_seed=seed, normalize_obs=False,
+               normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=BATCH, epochs_per_iter=1,
+               save_state=False, update_mode=mode)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def rollout_and_epoch(ppo):
+    """(seconds of one rollout, seconds of one update epoch on it)."""
+    from ppo_and_friends_amd.ppo import PermutationLoader
+    pol = ppo.policies["p"]
+    t_roll = timed(ppo.rollout)
+    pol.train()
+    loader = PermutationLoader(pol.dataset, BATCH, ppo.loader_generator)
+    t_epoch = timed(lambda: ppo._ppo_batch_train(loader, "p"))
+    return t_roll, t_epoch
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=128, help="env steps per rollout (E x T transitions)")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    args = ap.parse_args()
+    n = args.envs * args.steps
+    result = {"transitions": n, "batch_size": BATCH, "minibatches_per_epoch": (n + BATCH - 1) // BATCH, "repeats": args.repeats}
+    ppos = {k: make_ppo(w, m, args.envs, args.steps) for k, (w, m) in LEGS.items()}
+    for k, ppo in ppos.items():                      # the path each leg takes, as the JSON line reports it
+        pol = ppo.policies["p"]
+        fused = ppo._fused_updater("p", BATCH)
+        step_on = ppo.update_mode != "torch" and pol.fused_step_unsupported_reason() == ""
+        result[f"{k}_rollout_path"] = "K6+K7" if step_on else "torch"
+        result[f"{k}_update_path"] = "torch" if fused is None else \
+            "K12" + (", row pairs" if fused.pairs_reason() == "" else "") + (", fused tail" if fused.tail_reason() == "" else "")
+        for _ in range(args.warmup):
+            rollout_and_epoch(ppo)
+    times = {k: [] for k in ppos}
+    for _ in range(args.repeats):
+        for k, ppo in ppos.items():                  # alternating: drifts of clock / neighbours hit all legs alike
+            times[k].append(rollout_and_epoch(ppo))
+    for k in ppos:
+        for j, what in enumerate(("rollout", "epoch")):
+            t = np.array([x[j] for x in times[k]])
+            path = result[k + ("_rollout_path" if what == "rollout" else "_update_path")]
+            print(f"{k:14s} {what:8s} median {np.median(t) * 1e3:9.2f} ms  spread {t.min() * 1e3:9.2f} .. {t.max() * 1e3:9.2f} ms"
+                  f"   ({path})", flush=True)
+            result[f"{k}_{what}_s"] = float(np.median(t))
+            result[f"{k}_{what}_spread_s"] = [float(t.min()), float(t.max())]
+    for what in ("rollout", "epoch"):
+        result[f"64x256_{what}_torch_over_fused"] = result[f"64x256_torch_{what}_s"] / result[f"64x256_fused_{what}_s"]
+    result["epoch_64x256_over_128x256"] = result["64x256_fused_epoch_s"] / result["128x256_fused_epoch_s"]
+    print(json.dumps(result), flush=True)
+
+
+if __name__ == "__main__":
+    main()
