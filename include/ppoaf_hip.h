@@ -947,6 +947,102 @@ typedef struct {
 int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* args, ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * K23  the bookkeeping of one env step of a multi-policy rollout, one launch for all members
+ * replaces, after env.step, per member: the reward / natural-reward rows of its agents,
+ *          `reward * ext_reward_weight`, `+ intrinsic reward`, buffer.rewards[t], end_kind[t];
+ *          and once: the ep_ts arithmetic of the episode ends                 ppo.py:1795-1983
+ * The env's rewards arrive as a ROW-BLOCK TABLE per member, passed by value (no device-side table): block b is the
+ * float32 [E] row of the member's b-th agent in env order, wherever it lies -- `base + agent * E` of the env's
+ * agent-major tensor, or one tensor of a dict keyed by agent id.  1 <= n_blocks <= PPOAF_ROW_BLOCKS_MAX.
+ * Per member, in its buffer layout:
+ *   grouped == 0 (PPOPolicy)   row  b * E + e  <- block b, env e                      (agent-major [n * E])
+ *   grouped == 1 (MATPolicy)   row  e * n + s  <- block slot_agent[s], env e          ([E, n] in slot order);
+ *                              slot_agent is a permutation of 0..n-1 (an entry outside the table is refused)
+ *   reward_out[row]  = reward (* ext_reward_weight when it is not 1) (+ intrinsic[row] when intrinsic != NULL):
+ *                      two float32 roundings, never one fma -- bitwise the torch statements
+ *   natural_out      (NULL: not kept) ALWAYS agent-major, [b * E + e] <- natural[b][e] (reward[b][e] when
+ *                      natural[b] == NULL): the layout the rollout statistics sum over
+ *   end_kind_out     int8 [n * E] (grouped == 0: the env's kind for each of its agents) or [E] (grouped == 1)
+ * write_ends != 0: ts = ep_ts[e] + 1; boot = !terminated[e] && (ts >= max_ts_per_ep || truncated[e] || last_step);
+ *   kind = terminated ? 1 : boot ? 2 : 0; ep_ts[e] = (terminated || boot) ? 0 : ts -- ep_ts int32 [E] advances ONCE,
+ *   in place; terminated / truncated are byte flags [E] (truncated may be NULL).  write_ends == 0: neither ep_ts nor
+ *   end_kind_out is touched (fixed-length rollouts).
+ * Alignment: a deliberate exception to the other block tables (ppoaf_policy_step_blocks and
+ * ppoaf_mat_policy_step_blocks ask for 16-byte aligned bases).  Here every row is an [E] float32 vector read and written
+ * with scalar accesses, and the rows an env hands over lie E * 4 bytes apart (40 bytes at E = 10), so only float32
+ * alignment is asked for.  E == 0: PPOAF_OK without a launch.  Plain vector stores; one thread per env.
+ * ------------------------------------------------------------------------ */
+/* rows of a launch that lie in several tensors are described by a table of this many row-block pointers at most
+ * (K23 below, and the block forms of K6+K7 and K16 after it) */
+#define PPOAF_ROW_BLOCKS_MAX 16
+#define PPOAF_FINISH_MAX_MEMBERS 8
+typedef struct {
+    int32_t n_blocks, grouped;
+    int32_t slot_agent[PPOAF_ROW_BLOCKS_MAX];
+    const float* reward[PPOAF_ROW_BLOCKS_MAX];
+    const float* natural[PPOAF_ROW_BLOCKS_MAX];
+    const float* intrinsic;
+    float* reward_out; float* natural_out; int8_t* end_kind_out;
+} ppoaf_finish_member_t;
+
+typedef struct {
+    int32_t n_members, write_ends, last_step, max_ts_per_ep;
+    float ext_reward_weight;
+    int64_t E;
+    const uint8_t* terminated; const uint8_t* truncated;
+    int32_t* ep_ts;
+    ppoaf_finish_member_t members[PPOAF_FINISH_MAX_MEMBERS];
+} ppoaf_rollout_finish_args_t;
+
+int ppoaf_rollout_finish_rows(const ppoaf_rollout_finish_args_t* args, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * K6+K7, block form: ppoaf_policy_step reading the env's tensors where they lie
+ * `args` as for ppoaf_policy_step, except that args->obs / args->critic_obs are not read: row r of the launch
+ * (0 <= r < args->E = n_blocks * rows_per_block) is row r % rows_per_block of block r / rows_per_block of `obs` and of
+ * `critic_obs` -- block a of an agent-major env tensor [A * E, width] is `base + a * E * width`, of a dict env the
+ * tensor of the member's a-th agent.  The buffer row (raw actions, actions, log-probs, values, observation copies) is
+ * written exactly as by ppoaf_policy_step; the env action of row r ALSO goes to row r % rows_per_block of
+ * env_action[r / rows_per_block] (int64 [rows_per_block, 1 or n_action_slices] for the categorical heads, float32
+ * [rows_per_block, out_dim] for the Gaussian and Bernoulli ones): the env's combined action tensor or its per-agent
+ * tensors, so env.step needs no index_put.  Philox counters, head code and tile code are ppoaf_policy_step's, so for
+ * equal inputs, seed and offset every output is bitwise its output on the gathered rows.  A 16-row tile may straddle two
+ * blocks: row addresses are computed per row.  Refused: n_blocks outside [1, PPOAF_ROW_BLOCKS_MAX], a base that is null or
+ * not 16-byte aligned, args->E != n_blocks * rows_per_block; rows_per_block == 0: PPOAF_OK without a launch.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n_blocks;
+    int64_t rows_per_block;
+    const float* obs[PPOAF_ROW_BLOCKS_MAX];
+    const float* critic_obs[PPOAF_ROW_BLOCKS_MAX];
+    void* env_action[PPOAF_ROW_BLOCKS_MAX];
+} ppoaf_step_blocks_t;
+
+int ppoaf_policy_step_blocks(const ppoaf_policy_step_args_t* args, const ppoaf_step_blocks_t* blocks, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * K16, block form: ppoaf_mat_policy_step reading the env's tensors where they lie
+ * `args` as for ppoaf_mat_policy_step, except that args->critic_obs / args->actor_obs are not read.  The table holds one
+ * block per agent of the team in env order (n_blocks == args->num_agents), each [E, width] rows; slot s of env e reads
+ * row e of block slot_agent[s] of `critic_obs` and of `actor_obs` (all NULL: the actor sees the critic's observation) --
+ * K20's slot_agent, but over a table, so a team whose agents are not adjacent in the env works -- on the narrow
+ * (obs_dim <= 32) and the wide-chunk path alike.  The buffer row stays grouped [E, A] and is written exactly as by
+ * ppoaf_mat_policy_step; the env action of slot s ALSO goes to element e of int64 block env_action[slot_agent[s]].
+ * For equal inputs, seed and offset every output is bitwise ppoaf_mat_policy_step's on the regrouped rows.  Refused:
+ * n_blocks outside [1, PPOAF_ROW_BLOCKS_MAX] or != num_agents, a base that is null or not 16-byte aligned, a slot_agent
+ * entry outside the table or named twice; E == 0: PPOAF_OK without a launch.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n_blocks;
+    int32_t slot_agent[PPOAF_ROW_BLOCKS_MAX];
+    const float* critic_obs[PPOAF_ROW_BLOCKS_MAX];
+    const float* actor_obs[PPOAF_ROW_BLOCKS_MAX];
+    int64_t* env_action[PPOAF_ROW_BLOCKS_MAX];
+} ppoaf_mat_step_blocks_t;
+
+int ppoaf_mat_policy_step_blocks(const ppoaf_mat_step_args_t* args, const ppoaf_mat_step_blocks_t* blocks, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * K20  one evaluation step of a MATPolicy for all E envs in one launch
  * replaces MATPolicy.get_inference_actions                              policies/mat_policy.py:701-790
  *          _get_autoregressive_actions_without_exploration (greedy)     mat_policy.py:521-585

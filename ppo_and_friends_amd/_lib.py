@@ -245,6 +245,37 @@ class MatInferArgs(C.Structure):
                 ("action_out", C.c_void_p), ("act_env_stride", C.c_int64), ("act_agent_stride", C.c_int64)]
 
 
+ROW_BLOCKS_MAX, FINISH_MAX_MEMBERS = 16, 8
+
+
+class FinishMember(C.Structure):
+    """ppoaf_finish_member_t (include/ppoaf_hip.h)."""
+    _fields_ = [("n_blocks", C.c_int32), ("grouped", C.c_int32), ("slot_agent", C.c_int32 * ROW_BLOCKS_MAX),
+                ("reward", C.c_void_p * ROW_BLOCKS_MAX), ("natural", C.c_void_p * ROW_BLOCKS_MAX),
+                ("intrinsic", C.c_void_p), ("reward_out", C.c_void_p), ("natural_out", C.c_void_p),
+                ("end_kind_out", C.c_void_p)]
+
+
+class StepBlocks(C.Structure):
+    """ppoaf_step_blocks_t (include/ppoaf_hip.h)."""
+    _fields_ = [("n_blocks", C.c_int32), ("rows_per_block", C.c_int64), ("obs", C.c_void_p * ROW_BLOCKS_MAX),
+                ("critic_obs", C.c_void_p * ROW_BLOCKS_MAX), ("env_action", C.c_void_p * ROW_BLOCKS_MAX)]
+
+
+class MatStepBlocks(C.Structure):
+    """ppoaf_mat_step_blocks_t (include/ppoaf_hip.h)."""
+    _fields_ = [("n_blocks", C.c_int32), ("slot_agent", C.c_int32 * ROW_BLOCKS_MAX), ("critic_obs", C.c_void_p * ROW_BLOCKS_MAX),
+                ("actor_obs", C.c_void_p * ROW_BLOCKS_MAX), ("env_action", C.c_void_p * ROW_BLOCKS_MAX)]
+
+
+class RolloutFinishArgs(C.Structure):
+    """ppoaf_rollout_finish_args_t (include/ppoaf_hip.h)."""
+    _fields_ = [("n_members", C.c_int32), ("write_ends", C.c_int32), ("last_step", C.c_int32), ("max_ts_per_ep", C.c_int32),
+                ("ext_reward_weight", C.c_float), ("E", C.c_int64),
+                ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("ep_ts", C.c_void_p),
+                ("members", FinishMember * FINISH_MAX_MEMBERS)]
+
+
 class ObsFilter(C.Structure):
     """ppoaf_obs_filter_t (include/ppoaf_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
@@ -345,6 +376,9 @@ SIGNATURES = {
     "ppoaf_mat_update_norm_partials": (C.c_int, [C.POINTER(MatUpdateArgs)]),
     "ppoaf_mat_policy_step": (C.c_int, [C.POINTER(MatStepArgs), _ptr]),
     "ppoaf_mat_policy_infer": (C.c_int, [C.POINTER(MatInferArgs), _ptr]),
+    "ppoaf_rollout_finish_rows": (C.c_int, [C.POINTER(RolloutFinishArgs), _ptr]),
+    "ppoaf_policy_step_blocks": (C.c_int, [C.POINTER(PolicyStepArgs), C.POINTER(StepBlocks), _ptr]),
+    "ppoaf_mat_policy_step_blocks": (C.c_int, [C.POINTER(MatStepArgs), C.POINTER(MatStepBlocks), _ptr]),
     "ppoaf_lstm_workspace_floats": (C.c_int, [C.POINTER(LstmDesc), C.POINTER(C.c_int64)]),
     "ppoaf_lstm_forward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int32, _ptr]),
     "ppoaf_lstm_backward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),

@@ -1162,8 +1162,36 @@ struct MatStepDev {
     const int64_t* forced_action;                  // NULL: sample; else [E, L] actions to log (replay)
 };
 
-template <bool WIDE>
-__device__ __forceinline__ void mat_policy_step_body(const MatStepDev u) {
+// The block form (ppoaf_mat_policy_step_blocks): slot s of env e reads row e of block slot_agent[s] of `critic_obs` (and of
+// `actor_obs`), and its env action goes to element e of action block slot_agent[s]; the buffer row stays grouped [E, A].
+struct MatStepBlocks {
+    const float* critic_obs[PPOAF_ROW_BLOCKS_MAX];
+    const float* actor_obs[PPOAF_ROW_BLOCKS_MAX];   // all NULL: the actor sees the critic's observation
+    int64_t* env_action[PPOAF_ROW_BLOCKS_MAX];
+    unsigned long long slots[2];                    // slot_agent, one byte per slot
+};
+// The table stays in the kernel arguments: entries are read with compile-time indices (scalar loads) and chosen with
+// selects, never through an address -- a runtime-indexed copy would put the table into every thread's scratch memory.
+__device__ __forceinline__ int mat_slot_agent(const MatStepBlocks& tb, const int s) {
+    return (int)(((s < 8 ? tb.slots[0] : tb.slots[1]) >> (8 * (s & 7))) & 0xffull);
+}
+template <class T>
+__device__ __forceinline__ T* mat_opaque(T* p) {
+    // keeps each entry a scalar load of its own: the optimiser otherwise folds the selects back into one indexed load
+    asm volatile("" : "+s"(p));
+    return p;
+}
+#define MAT_BLOCK_(a, b, k) (b) == k ? mat_opaque((a)[k])
+#define mat_block(a, b)                                                                                                   \
+    (MAT_BLOCK_(a, b, 1) : MAT_BLOCK_(a, b, 2) : MAT_BLOCK_(a, b, 3) : MAT_BLOCK_(a, b, 4) : MAT_BLOCK_(a, b, 5)           \
+     : MAT_BLOCK_(a, b, 6) : MAT_BLOCK_(a, b, 7) : MAT_BLOCK_(a, b, 8) : MAT_BLOCK_(a, b, 9) : MAT_BLOCK_(a, b, 10)        \
+     : MAT_BLOCK_(a, b, 11) : MAT_BLOCK_(a, b, 12) : MAT_BLOCK_(a, b, 13) : MAT_BLOCK_(a, b, 14) : MAT_BLOCK_(a, b, 15)    \
+     : mat_opaque((a)[0]))
+static_assert(PPOAF_ROW_BLOCKS_MAX == 16, "mat_block spells out 16 entries");
+
+template <bool WIDE, bool BLK = false>
+__device__ __forceinline__ void mat_policy_step_body(const MatStepDev u, const MatStepBlocks* tbp = nullptr) {
+    [[maybe_unused]] const MatStepBlocks& tb = *tbp;          // (the block form only)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long seq0 = (long)blockIdx.x * u.per_tile;
     const long rem = u.E - seq0;
@@ -1180,18 +1208,36 @@ __device__ __forceinline__ void mat_policy_step_body(const MatStepDev u) {
     const long tok0 = seq0 * L;                                  // first token (env-major, agents inside)
     for (int idx = tid; idx < n_rows * O; idx += kMT) {
         const int s = idx / O, i = idx - s * O;
-        const float v = u.obs[(tok0 + s) * O + i];
+        float v;
+        if constexpr (BLK) v = mat_block(tb.critic_obs, mat_slot_agent(tb, (int)((tok0 + s) % L)))[(tok0 + s) / L * O + i];
+        else v = u.obs[(tok0 + s) * O + i];
         if constexpr (!WIDE) sYO[s * OS + i] = v;                 // (WIDE: the encoder reads the rows from global memory)
         if (u.critic_obs_out) u.critic_obs_out[(tok0 + s) * O + i] = v;
     }
-    if (u.obs_out) {
+    if constexpr (BLK) {
+        if (u.obs_out) {
+            const bool own = tb.actor_obs[0] != nullptr;
+            for (long idx = tid; idx < (long)n_rows * u.Oa; idx += kMT) {
+                const long tok = tok0 + idx / u.Oa;
+                const int b = mat_slot_agent(tb, (int)(tok % L));
+                const float* src = own ? mat_block(tb.actor_obs, b) : mat_block(tb.critic_obs, b);
+                u.obs_out[tok0 * u.Oa + idx] = src[tok / L * u.Oa + idx % u.Oa];
+            }
+        }
+    } else if (u.obs_out) {
         const float* src = u.actor_obs ? u.actor_obs : u.obs;
         for (long idx = tid; idx < (long)n_rows * u.Oa; idx += kMT) u.obs_out[tok0 * u.Oa + idx] = src[tok0 * u.Oa + idx];
     }
     if (tid < n_rows && tid % L == 0) sXA[tid * kMXS] = 1.0f;     // start token of agent 0 (mat_policy.py:325-333)
     MAT_SYNC();
-    mat_encoder_forward<false>(c, tid, wave, lane, MatNoPub(),
-                               (WIDE && (tid >> 4) < n_rows) ? u.obs + (tok0 + (tid >> 4)) * O : nullptr);
+    if constexpr (BLK) {
+        const long tok = tok0 + (tid >> 4);
+        mat_encoder_forward<false>(c, tid, wave, lane, MatNoPub(),
+                                   (WIDE && (tid >> 4) < n_rows) ? mat_block(tb.critic_obs, mat_slot_agent(tb, (int)(tok % L))) + tok / L * O : nullptr);
+    } else {
+        mat_encoder_forward<false>(c, tid, wave, lane, MatNoPub(),
+                                   (WIDE && (tid >> 4) < n_rows) ? u.obs + (tok0 + (tid >> 4)) * O : nullptr);
+    }
     MAT_SYNC();
     if (tid < n_rows) {
         float v = sOutC[tid * 8];
@@ -1233,6 +1279,7 @@ __device__ __forceinline__ void mat_policy_step_body(const MatStepDev u) {
             for (int k = 0; k < 8; ++k) if (k == a) pa = p[k];
             sAct[tid] = a;
             u.action_out[tok0 + tid] = a;
+            if constexpr (BLK) mat_block(tb.env_action, mat_slot_agent(tb, i))[(tok0 + tid) / L] = a;
             if (u.raw_action_out) u.raw_action_out[tok0 + tid] = a;
             u.logp_out[tok0 + tid] = logf(clamp_prob_u(pa / s2));
             if (i + 1 < L) sXA[(tid + 1) * kMXS + 1 + a] = 1.0f;  // agent i+1 sees agent i's action
@@ -1243,6 +1290,12 @@ __device__ __forceinline__ void mat_policy_step_body(const MatStepDev u) {
 
 __global__ __launch_bounds__(kMT) void mat_policy_step_kernel(MatStepDev u) { mat_policy_step_body<false>(u); }
 __global__ __launch_bounds__(kMT) void mat_policy_step_wide_kernel(MatStepDev u) { mat_policy_step_body<true>(u); }
+__global__ __launch_bounds__(kMT) void mat_policy_step_blocks_kernel(MatStepDev u, MatStepBlocks tb) {
+    mat_policy_step_body<false, true>(u, &tb);
+}
+__global__ __launch_bounds__(kMT) void mat_policy_step_blocks_wide_kernel(MatStepDev u, MatStepBlocks tb) {
+    mat_policy_step_body<true, true>(u, &tb);
+}
 
 // ------------------------------------------------------------------------------------------------
 // K20: one evaluation step of a MATPolicy for all envs in one launch (mat_policy.py:701-790 over :521-585 greedy and
@@ -1834,15 +1887,15 @@ extern "C" int ppoaf_mat_update_norm_partials(const ppoaf_mat_update_args_t* arg
     return (int)(((u.total >> 2) + kMatRedThreads - 1) / kMatRedThreads);
 }
 
-extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a, "mat_policy_step: null args");
+// validates `a`, fills the device view, launches the plain form (tb == NULL) or the block form
+static int mat_policy_step_launch(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb, ppoaf_stream_t stream) {
     PPOAF_REQUIRE(a->embedding == kMD, "mat_policy_step: embedding=%d (built for 64)", a->embedding);
     PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= kMOWide &&
                       a->num_actions >= 1 && a->num_actions <= 8 && a->actor_obs_dim >= 1,
                   "mat_policy_step: sizes (agents %d, obs %d, actions %d) outside the kernel's limits (16, %d, 8)", a->num_agents,
                   a->obs_dim, a->num_actions, kMOWide);
     PPOAF_REQUIRE(a->E >= 1, "mat_policy_step: E=%ld", (long)a->E);
-    PPOAF_REQUIRE(a->params && a->critic_obs && a->action_out && a->logp_out && a->value_out, "mat_policy_step: null pointer");
+    PPOAF_REQUIRE(a->params && (tb || a->critic_obs) && a->action_out && a->logp_out && a->value_out, "mat_policy_step: null pointer");
     PPOAF_REQUIRE(!a->normalize_values || (a->vn_mean && a->vn_var), "mat_policy_step: value normaliser statistics missing");
     PPOAF_REQUIRE(((uintptr_t)a->params & 15) == 0, "mat_policy_step: params must be 16-byte aligned");
     MatStepDev u;
@@ -1869,11 +1922,69 @@ extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_strea
     }
     const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
     PPOAF_REQUIRE(n_wg <= 0x7fffffffL, "mat_policy_step: too many envs");
+    if (tb) {
+        static void (*const kern_b[2])(MatStepDev, MatStepBlocks) = {mat_policy_step_blocks_kernel, mat_policy_step_blocks_wide_kernel};
+        static bool attr_b = false;
+        if (!attr_b) {
+            for (int i = 0; i < 2; ++i) {
+                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_b[i]),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+            }
+            attr_b = true;
+        }
+        u.obs = nullptr; u.actor_obs = nullptr;
+        hipLaunchKernelGGL(kern_b[mat_is_wide(u.O) ? 1 : 0], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u, *tb);
+        return check_launch("mat_policy_step_blocks");
+    }
     hipLaunchKernelGGL(kern[mat_is_wide(u.O) ? 1 : 0], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
     return check_launch("mat_policy_step");
 }
 
+extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_policy_step: null args");
+    return mat_policy_step_launch(a, nullptr, stream);
+}
+
+extern "C" int ppoaf_mat_policy_step_blocks(const ppoaf_mat_step_args_t* a, const ppoaf_mat_step_blocks_t* t,
+                                            ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a && t, "mat_policy_step_blocks: null args");
+    PPOAF_REQUIRE(t->n_blocks >= 1 && t->n_blocks <= PPOAF_ROW_BLOCKS_MAX, "mat_policy_step_blocks: n_blocks=%d not in [1, %d]",
+                  t->n_blocks, PPOAF_ROW_BLOCKS_MAX);
+    PPOAF_REQUIRE(t->n_blocks == a->num_agents, "mat_policy_step_blocks: n_blocks=%d, the policy has %d agents", t->n_blocks,
+                  a->num_agents);
+    PPOAF_REQUIRE(a->E >= 0, "mat_policy_step_blocks: E=%ld must be >= 0", (long)a->E);
+    MatStepBlocks tb;
+    tb.slots[0] = tb.slots[1] = 0;
+    unsigned seen = 0;
+    for (int b = 0; b < PPOAF_ROW_BLOCKS_MAX; ++b) {
+        const bool in = b < t->n_blocks;
+        if (in) {
+            const int v = t->slot_agent[b];
+            PPOAF_REQUIRE(v >= 0 && v < t->n_blocks, "mat_policy_step_blocks: slot_agent[%d]=%d is outside the table of %d blocks", b, v,
+                          t->n_blocks);
+            PPOAF_REQUIRE(!(seen & (1u << v)), "mat_policy_step_blocks: slot_agent names block %d twice", v);
+            seen |= 1u << v;
+            PPOAF_REQUIRE(t->critic_obs[b] && t->env_action[b] && ((uintptr_t)t->critic_obs[b] & 15) == 0 &&
+                              ((uintptr_t)t->actor_obs[b] & 15) == 0 && ((uintptr_t)t->env_action[b] & 15) == 0 &&
+                              (t->actor_obs[b] != nullptr) == (t->actor_obs[0] != nullptr),
+                          "mat_policy_step_blocks: block %d: a base is null or not 16-byte aligned", b);
+        }
+        tb.critic_obs[b] = in ? t->critic_obs[b] : nullptr;
+        tb.actor_obs[b] = in ? t->actor_obs[b] : nullptr;
+        tb.env_action[b] = in ? t->env_action[b] : nullptr;
+        if (in) tb.slots[b >> 3] |= (unsigned long long)t->slot_agent[b] << (8 * (b & 7));
+    }
+    if (a->E == 0) return PPOAF_OK;
+    return mat_policy_step_launch(a, &tb, stream);
+}
+
 #define PPOAF_LAYOUT(T, f, off) static_assert(offsetof(T, f) == off, #T "." #f)
+PPOAF_LAYOUT(ppoaf_mat_step_blocks_t, slot_agent, 4);
+PPOAF_LAYOUT(ppoaf_mat_step_blocks_t, critic_obs, 72);
+PPOAF_LAYOUT(ppoaf_mat_step_blocks_t, actor_obs, 200);
+PPOAF_LAYOUT(ppoaf_mat_step_blocks_t, env_action, 328);
+static_assert(sizeof(ppoaf_mat_step_blocks_t) == 456, "ppoaf_mat_step_blocks_t");
 PPOAF_LAYOUT(ppoaf_mat_infer_args_t, obs_dim, 0);
 PPOAF_LAYOUT(ppoaf_mat_infer_args_t, num_agents, 4);
 PPOAF_LAYOUT(ppoaf_mat_infer_args_t, num_actions, 8);

@@ -1,6 +1,7 @@
 // Device building blocks shared by the fused update (ppo_update.hip) and the rollout step
 // (policy_step.hip): network descriptors, activations, f32-MFMA forward tiles.
 #pragma once
+#include <type_traits>
 #include "common.hpp"
 #include <cfloat>
 
@@ -451,10 +452,23 @@ __device__ __forceinline__ void layer_wgrad(const float* __restrict__ D, const f
 // sOut[16][kMaxOut], valid after the function's last barrier.  Both kernels instantiate THIS code, so a row's outputs
 // are bitwise the same in both.  `cpy` (may be NULL): the observation rows are copied there on the way in.
 // smem: mlp_rows_forward_lds_floats(nd) floats of dynamic LDS, 16-byte aligned.
-template <int HT>
+// BlockRows (the block form of K6+K7, `rows` != NULL and `src` unused): the rows lie in a table of up to 16 row blocks of
+// `rows_per_block` rows each, row r being row r % rows_per_block of block r / rows_per_block -- a 16-row tile may straddle
+// two blocks, so the address is computed per row.
+struct BlockRows {
+    const float* const* blocks;      // (points into the kernel arguments)
+    long rows_per_block;
+    __device__ __forceinline__ float load(const long r, const int i, const int in_dim) const {
+        const long b = r / rows_per_block;
+        return blocks[b][(r - b * rows_per_block) * in_dim + i];
+    }
+};
+
+template <int HT, class Rows = void>
 __device__ __forceinline__ const float* mlp_rows_forward(const NetDev& nd, const float* __restrict__ params,
                                                          const float* __restrict__ src, float* __restrict__ cpy,
-                                                         const long E, const long e0, float* smem) {
+                                                         const long E, const long e0, float* smem,
+                                                         const Rows* rows = nullptr) {
     constexpr int H = 16 * HT, HS = H + 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int in_dim = nd.in_dim, depth = nd.depth, out_dim = nd.out_dim, act = nd.act;
@@ -483,7 +497,8 @@ __device__ __forceinline__ const float* mlp_rows_forward(const NetDev& nd, const
         const int s = idx / INP, i = idx - s * INP;
         float x = 0.f;
         if (i < in_dim && e0 + s < E) {
-            x = src[(e0 + s) * in_dim + i];
+            if constexpr (std::is_void<Rows>::value) x = src[(e0 + s) * in_dim + i];
+            else x = rows->load(e0 + s, i, in_dim);
             if (cpy) cpy[(e0 + s) * in_dim + i] = x;
         }
         sX[idx] = x;

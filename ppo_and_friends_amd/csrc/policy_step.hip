@@ -9,6 +9,7 @@
 // grid = 2 * ceil(E/16) workgroups (XCD-grouped like the update kernel: blocks 0-3 mod 8 actor, 4-7
 // critic), 512 threads: 16 env rows per workgroup, hidden layers on v_mfma_f32_16x16x4_f32 with the same
 // tile code as the update's forward, so a row's log-prob here and in the first mini-batch agree bit for bit.
+#include <cstddef>
 #include "ppo_update_dev.hpp"        // the list of instantiated width pairs (and action_heads.hpp)
 
 namespace ppoaf {
@@ -30,21 +31,39 @@ struct StepDev {
     int n_slices; int slices[8];               // multi-categorical head: classes per action dimension
 };
 
+// The block form (ppoaf_policy_step_blocks): row r of the launch is row r % rows_per_block of block r / rows_per_block
+// of `obs` / `critic_obs`, and its env action also goes to that row of `env_action`.  The pointers travel in the kernel
+// arguments.
+struct StepBlocks {
+    const float* obs[PPOAF_ROW_BLOCKS_MAX];
+    const float* critic_obs[PPOAF_ROW_BLOCKS_MAX];
+    void* env_action[PPOAF_ROW_BLOCKS_MAX];
+    long rows_per_block;
+    int action_elems, action_is_float;         // elements of one row's env action; float32 (Box, MultiBinary) or int64
+};
+
 extern __shared__ __attribute__((aligned(16))) unsigned char policy_step_smem[];
 
 // XH: the MultiDiscrete / MultiBinary heads are compiled in (instantiations of their own, so that the categorical and
 // Gaussian ones keep their registers)
-template <int HT, bool XH>
-__device__ __forceinline__ void policy_step_body(const StepDev& u, const int which, const int g) {
+template <int HT, bool XH, bool BLK = false>
+__device__ __forceinline__ void policy_step_body(const StepDev& u, const int which, const int g,
+                                                 const StepBlocks* tb = nullptr) {
     const int tid = threadIdx.x;
     const NetDev& nd = u.net[which];
     const int out_dim = nd.out_dim;
     const float* P = u.params + nd.offset;
     const long e0 = (long)g * kRows;
     // the forward K19 runs as well (mlp_device.hpp)
-    const float* sOut = mlp_rows_forward<HT>(nd, u.params, which == 0 ? u.obs : u.critic_obs,
-                                             which == 0 ? u.obs_out : u.critic_obs_out, u.E, e0,
-                                             reinterpret_cast<float*>(policy_step_smem));
+    float* smem = reinterpret_cast<float*>(policy_step_smem);
+    float* cpy = which == 0 ? u.obs_out : u.critic_obs_out;
+    const float* sOut;
+    if constexpr (BLK) {
+        const BlockRows rows{which == 0 ? tb->obs : tb->critic_obs, tb->rows_per_block};
+        sOut = mlp_rows_forward<HT, BlockRows>(nd, u.params, nullptr, cpy, u.E, e0, smem, &rows);
+    } else {
+        sOut = mlp_rows_forward<HT>(nd, u.params, which == 0 ? u.obs : u.critic_obs, cpy, u.E, e0, smem);
+    }
 
     // heads: one lane per env row
     if (tid < kRows && e0 + tid < u.E) {
@@ -107,6 +126,20 @@ __device__ __forceinline__ void policy_step_body(const StepDev& u, const int whi
             gauss_step_row(sOut + s * kMaxOut, out_dim, P + nd.log_std_off, u.min_std, u.act_lo, u.act_hi,
                            u.forced_raw_action, e, u.seed, u.offset, u.raw_action_out, u.action_out, u.logp_out);
         }
+        if (BLK && which == 0) {
+            // the row's env action, as this lane has just stored it in the buffer row, into the env's action tensor
+            const long b = e / tb->rows_per_block, r = e - b * tb->rows_per_block;
+            const int n = tb->action_elems;
+            if (tb->action_is_float) {
+                const float* src = reinterpret_cast<const float*>(u.action_out) + e * n;
+                float* dst = reinterpret_cast<float*>(tb->env_action[b]) + r * n;
+                for (int k = 0; k < n; ++k) dst[k] = src[k];
+            } else {
+                const int64_t* src = reinterpret_cast<const int64_t*>(u.action_out) + e * n;
+                int64_t* dst = reinterpret_cast<int64_t*>(tb->env_action[b]) + r * n;
+                for (int k = 0; k < n; ++k) dst[k] = src[k];
+            }
+        }
     }
 }
 
@@ -118,6 +151,16 @@ __global__ __launch_bounds__(kThreadsS) void policy_step_kernel(StepDev u) {
     if (g >= u.n_wg) return;
     if (which == 0) policy_step_body<HTA, XH>(u, 0, g);
     else policy_step_body<HTC, XH>(u, 1, g);
+}
+
+template <int HTA, int HTC, bool XH>
+__global__ __launch_bounds__(kThreadsS) void policy_step_blocks_kernel(StepDev u, StepBlocks tb) {
+    const int b = blockIdx.x;
+    const int which = (b >> 2) & 1;
+    const int g = ((b >> 3) << 2) | (b & 3);
+    if (g >= u.n_wg) return;
+    if (which == 0) policy_step_body<HTA, XH, true>(u, 0, g, &tb);
+    else policy_step_body<HTC, XH, true>(u, 1, g, &tb);
 }
 
 static size_t step_lds_bytes(const StepDev& u) {
@@ -144,6 +187,30 @@ static int launch_step(const StepDev& u, size_t lds, hipStream_t s) {
     return check_launch("policy_step");
 }
 
+template <int HTA, int HTC, bool XH>
+static int launch_step_blocks(const StepDev& u, const StepBlocks& tb, size_t lds, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set && lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_step_blocks_kernel<HTA, HTC, XH>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+        attr_set = true;
+    }
+    const unsigned grid = 8u * (unsigned)((u.n_wg + 3) / 4);
+    hipLaunchKernelGGL((policy_step_blocks_kernel<HTA, HTC, XH>), dim3(grid), dim3(kThreadsS), lds, s, u, tb);
+    return check_launch("policy_step_blocks");
+}
+
+template <bool XH>
+static int launch_widths_blocks(const StepDev& u, const StepBlocks& tb, size_t lds, hipStream_t s) {
+    const int ha = u.net[0].H, hc = u.net[1].H;
+#define PPOAF_WIDTH_PAIR_CALL_(A, C) launch_step_blocks<A / 16, C / 16, XH>(u, tb, lds, s)
+    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+#undef PPOAF_WIDTH_PAIR_CALL_
+    set_error("policy_step_blocks: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
+    return PPOAF_E_INVALID;
+}
+
 template <bool XH>
 static int launch_widths(const StepDev& u, size_t lds, hipStream_t s) {
     const int ha = u.net[0].H, hc = u.net[1].H;
@@ -158,17 +225,17 @@ static int launch_widths(const StepDev& u, size_t lds, hipStream_t s) {
 
 using namespace ppoaf;
 
-extern "C" int ppoaf_policy_step(const ppoaf_policy_step_args_t* a, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a, "policy_step: null args");
-    StepDev u;
+// validates `a` and fills the device view; *empty: E == 0, nothing to launch.  with_obs: obs / critic_obs are read from `a`
+static int fill_step(const ppoaf_policy_step_args_t* a, StepDev& u, bool with_obs, bool* empty, size_t* lds_out) {
+    *empty = false;
     int rc = fill_net(a->actor, u.net[0], "actor");
     if (rc) return rc;
     rc = fill_net(a->critic, u.net[1], "critic");
     if (rc) return rc;
     PPOAF_REQUIRE(a->E >= 0, "policy_step: negative E");
-    if (a->E == 0) return PPOAF_OK;
+    if (a->E == 0) { *empty = true; return PPOAF_OK; }
     PPOAF_REQUIRE(a->E <= (1L << 27), "policy_step: E too large");
-    PPOAF_REQUIRE(a->params && a->obs && a->critic_obs && a->raw_action_out && a->action_out &&
+    PPOAF_REQUIRE(a->params && (!with_obs || (a->obs && a->critic_obs)) && a->raw_action_out && a->action_out &&
                       a->logp_out && a->value_out,
                   "policy_step: null pointer");
     PPOAF_REQUIRE(a->critic.out_dim == 1, "policy_step: critic out_dim must be 1");
@@ -189,6 +256,56 @@ extern "C" int ppoaf_policy_step(const ppoaf_policy_step_args_t* a, ppoaf_stream
     for (int j = 0; j < 8; ++j) u.slices[j] = j < u.n_slices ? a->action_slices[j] : 0;
     const size_t lds = step_lds_bytes(u);
     PPOAF_REQUIRE(lds <= 160 * 1024, "policy_step: needs %zu B of LDS", lds);
+    *lds_out = lds;
+    return PPOAF_OK;
+}
+
+extern "C" int ppoaf_policy_step(const ppoaf_policy_step_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "policy_step: null args");
+    StepDev u;
+    bool empty;
+    size_t lds = 0;
+    const int rc = fill_step(a, u, true, &empty, &lds);
+    if (rc || empty) return rc;
     hipStream_t s = (hipStream_t)stream;
     return u.head_kind >= PPOAF_HEAD_MULTI_CATEGORICAL ? launch_widths<true>(u, lds, s) : launch_widths<false>(u, lds, s);
 }
+
+extern "C" int ppoaf_policy_step_blocks(const ppoaf_policy_step_args_t* a, const ppoaf_step_blocks_t* t,
+                                        ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a && t, "policy_step_blocks: null args");
+    PPOAF_REQUIRE(t->n_blocks >= 1 && t->n_blocks <= PPOAF_ROW_BLOCKS_MAX, "policy_step_blocks: n_blocks=%d not in [1, %d]",
+                  t->n_blocks, PPOAF_ROW_BLOCKS_MAX);
+    PPOAF_REQUIRE(t->rows_per_block >= 0, "policy_step_blocks: rows_per_block=%ld must be >= 0", (long)t->rows_per_block);
+    PPOAF_REQUIRE(a->E == t->rows_per_block * t->n_blocks, "policy_step_blocks: E=%ld is not n_blocks=%d x rows_per_block=%ld",
+                  (long)a->E, t->n_blocks, (long)t->rows_per_block);
+    for (int b = 0; b < t->n_blocks; ++b)
+        PPOAF_REQUIRE(t->obs[b] && t->critic_obs[b] && t->env_action[b] && ((uintptr_t)t->obs[b] & 15) == 0 &&
+                          ((uintptr_t)t->critic_obs[b] & 15) == 0 && ((uintptr_t)t->env_action[b] & 15) == 0,
+                      "policy_step_blocks: block %d: a base is null or not 16-byte aligned", b);
+    if (a->E == 0) return PPOAF_OK;                 // no env: nothing is read, nothing launched
+    StepDev u;
+    bool empty;
+    size_t lds = 0;
+    const int rc = fill_step(a, u, false, &empty, &lds);
+    if (rc || empty) return rc;
+    StepBlocks tb;
+    for (int b = 0; b < PPOAF_ROW_BLOCKS_MAX; ++b) {
+        const bool in = b < t->n_blocks;
+        tb.obs[b] = in ? t->obs[b] : nullptr;
+        tb.critic_obs[b] = in ? t->critic_obs[b] : nullptr;
+        tb.env_action[b] = in ? t->env_action[b] : nullptr;
+    }
+    tb.rows_per_block = t->rows_per_block;
+    tb.action_is_float = u.head_kind == PPOAF_HEAD_GAUSSIAN || u.head_kind == PPOAF_HEAD_BERNOULLI;
+    tb.action_elems = u.head_kind == PPOAF_HEAD_CATEGORICAL ? 1
+                      : u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? u.n_slices : u.net[0].out_dim;
+    u.obs = nullptr; u.critic_obs = nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    return u.head_kind >= PPOAF_HEAD_MULTI_CATEGORICAL ? launch_widths_blocks<true>(u, tb, lds, s)
+                                                       : launch_widths_blocks<false>(u, tb, lds, s);
+}
+
+static_assert(offsetof(ppoaf_step_blocks_t, rows_per_block) == 8 && offsetof(ppoaf_step_blocks_t, obs) == 16 &&
+                  offsetof(ppoaf_step_blocks_t, critic_obs) == 144 && offsetof(ppoaf_step_blocks_t, env_action) == 272 &&
+                  sizeof(ppoaf_step_blocks_t) == 400, "ppoaf_step_blocks_t");

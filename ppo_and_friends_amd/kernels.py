@@ -422,6 +422,11 @@ def policy_step(args):
     check(_lib.load().ppoaf_policy_step(C.byref(args), stream()), "policy_step")
 
 
+def policy_step_blocks(args, blocks):
+    """ppoaf_policy_step_blocks: K6+K7 on rows that lie in a table of row blocks (_lib.StepBlocks)."""
+    check(_lib.load().ppoaf_policy_step_blocks(C.byref(args), C.byref(blocks), stream()), "policy_step_blocks")
+
+
 # --------------------------------------------------------------------------
 # K19: evaluation step (actor forward -> env action) and the score bookkeeping
 # --------------------------------------------------------------------------
@@ -551,6 +556,101 @@ class EvalScoreBooks:
 def mat_policy_infer(args):
     """ppoaf_mat_policy_infer on a filled _lib.MatInferArgs (policies/mat_policy.py fills it once per policy)."""
     check(_lib.load().ppoaf_mat_policy_infer(C.byref(args), stream()), "mat_policy_infer")
+
+
+# --------------------------------------------------------------------------
+# K23: the rows that follow env.step in a multi-policy rollout, all members in one launch
+# --------------------------------------------------------------------------
+def rollout_finish_rows(args):
+    """ppoaf_rollout_finish_rows on a filled _lib.RolloutFinishArgs."""
+    check(_lib.load().ppoaf_rollout_finish_rows(C.byref(args), stream()), "rollout_finish_rows")
+
+
+class RolloutFinish:
+    """
+    One rollout's K23 launches.  members: per policy a dict with `agents` (its agent ids in env order), `index` (their
+    positions among the env's agents), `slot_order` (None, or MATPolicy.agent_slot_order(): rows are [E, n] in that order),
+    and the [T, .] tensors the launch writes row t of: `rewards`, `natural`, `end_kind`, and `intrinsic` (None, or the
+    rows it reads).  ep_ts: int32 [E], advanced in place.  The env's rewards are handed to step() as they come: one
+    agent-major tensor [A * E] or a dict keyed by agent id -- the launch reads the members' rows where they lie.
+    """
+
+    @staticmethod
+    def unsupported_reason(team_sizes):
+        if len(team_sizes) > _lib.FINISH_MAX_MEMBERS:
+            return f"{len(team_sizes)} policies, one launch takes {_lib.FINISH_MAX_MEMBERS}"
+        if max(team_sizes) > _lib.ROW_BLOCKS_MAX:
+            return f"a policy of {max(team_sizes)} agents, a row-block table holds {_lib.ROW_BLOCKS_MAX}"
+        return ""
+
+    def __init__(self, members, num_env_agents, E, max_ts_per_ep, ext_reward_weight, ep_ts):
+        _req(ep_ts.is_cuda and ep_ts.dtype == torch.int32 and ep_ts.numel() == E and ep_ts.is_contiguous(), "ep_ts: int32 [E]")
+        self.members, self.E, self.A, self.ep_ts = members, int(E), int(num_env_agents), ep_ts
+        a = self.args = _lib.RolloutFinishArgs()
+        a.n_members, a.E, a.max_ts_per_ep = len(members), self.E, int(max_ts_per_ep)
+        a.ext_reward_weight = float(ext_reward_weight)
+        a.ep_ts = ep_ts.data_ptr()
+        for m, mem in zip(a.members, members):
+            m.n_blocks, m.grouped = len(mem["agents"]), int(mem["slot_order"] is not None)
+            for s, b in enumerate(mem["slot_order"] if m.grouped else ()):
+                m.slot_agent[s] = int(b)
+            for k in ("rewards", "natural"):
+                _req(mem[k].is_cuda and mem[k].dtype == torch.float32 and mem[k][0].is_contiguous()
+                     and mem[k][0].numel() == m.n_blocks * self.E, f"{k}: float32 [T, n * E]")
+            _req(mem["end_kind"].dtype == torch.int8 and mem["end_kind"][0].is_contiguous()
+                 and mem["end_kind"][0].numel() == (self.E if m.grouped else m.n_blocks * self.E), "end_kind: int8 [T, E] / [T, n * E]")
+            _req(mem["intrinsic"] is None or (mem["intrinsic"].dtype == torch.float32 and mem["intrinsic"][0].is_contiguous()
+                                              and mem["intrinsic"][0].numel() == m.n_blocks * self.E), "intrinsic: float32 [T, n * E]")
+
+    def _blocks(self, x, mem, what):
+        """Device pointers of the member's [E] rows of an env quantity (a dict keyed by agent id, or agent-major [A * E])."""
+        if isinstance(x, dict):
+            rows = [x[a] for a in mem["agents"]]
+            for r in rows:
+                _req(r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() == self.E, f"{what}: float32 [E] per agent")
+            return [r.data_ptr() for r in rows]
+        _req(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == self.A * self.E, f"{what}: float32 [A * E]")
+        return [x.data_ptr() + 4 * self.E * int(i) for i in mem["index"]]
+
+    @staticmethod
+    def _flags(x, E, what):
+        if x is None:
+            return None
+        _req(x.is_cuda and x.dtype in (torch.bool, torch.uint8) and x.is_contiguous() and x.numel() == E, f"{what}: bool [E]")
+        return x.data_ptr()
+
+    def inputs_unsupported_reason(self, reward, natural, terminated, truncated):
+        """'' when step() takes what this env step handed over; else why not (the caller then keeps the torch statements
+        for the rest of the rollout: ep_ts is advanced in place, so the two paths can follow one another)."""
+        for what, x in (("reward", reward), ("natural reward", natural)):
+            if x is None:
+                continue
+            rows = [x.get(a) for m in self.members for a in m["agents"]] if isinstance(x, dict) else [x]
+            n = self.E if isinstance(x, dict) else self.A * self.E
+            for r in rows:
+                if not (torch.is_tensor(r) and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() == n):
+                    return f"the env's {what} is not a contiguous float32 device tensor of {n} elements" + (" per agent" if isinstance(x, dict) else "")
+        for what, x in (("terminated", terminated), ("truncated", truncated)):
+            if x is not None and not (torch.is_tensor(x) and x.is_cuda and x.dtype in (torch.bool, torch.uint8) and x.is_contiguous()
+                                      and x.numel() == self.E):
+                return f"the env's `{what}` is not a contiguous bool device tensor [{self.E}]"
+        return ""
+
+    def step(self, t, reward, natural, terminated, truncated, last_step):
+        """Row t of every member.  natural None: the env's reward is the natural reward.  terminated None: a
+        fixed-length rollout, no ends are written and ep_ts stays."""
+        a = self.args
+        a.write_ends, a.last_step = int(terminated is not None), int(bool(last_step))
+        a.terminated, a.truncated = self._flags(terminated, self.E, "terminated"), self._flags(truncated, self.E, "truncated")
+        for m, mem in zip(a.members, self.members):
+            for b, p in enumerate(self._blocks(reward, mem, "reward")):
+                m.reward[b] = p
+            for b, p in enumerate(self._blocks(natural, mem, "natural reward") if natural is not None else [None] * m.n_blocks):
+                m.natural[b] = p
+            m.reward_out, m.natural_out = mem["rewards"][t].data_ptr(), mem["natural"][t].data_ptr()
+            m.end_kind_out = mem["end_kind"][t].data_ptr()
+            m.intrinsic = None if mem["intrinsic"] is None else mem["intrinsic"][t].data_ptr()
+        rollout_finish_rows(a)
 
 
 # --------------------------------------------------------------------------

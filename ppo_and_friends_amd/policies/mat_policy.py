@@ -158,8 +158,12 @@ class MATPolicy(PPOPolicy):
         from ..fused_update import _describe_mat
         return _describe_mat(self)[1]
 
-    def rollout_step(self, t, critic_obs, actor_obs, value_normalizer=None, forced_raw_action=None):
+    def rollout_step(self, t, critic_obs, actor_obs, value_normalizer=None, forced_raw_action=None, blocks=None):
         """
+        blocks (optional, then critic_obs / actor_obs are None): (critic_obs_blocks, actor_obs_blocks or None,
+        env_action_blocks), one device tensor per agent of the policy in env order -- the [E, .] rows of the env's tensors
+        where they lie and its int64 action tensors [E] / [E, 1], which the launch fills beside the grouped buffer row
+        (ppoaf_mat_policy_step_blocks reads them in the policy's slot order); `step_blocks_unsupported_reason` says when not.
         forced_raw_action (optional int64 device tensor [E, A] / [E, A, 1]): log these actions instead of sampling
         (replay of a recorded rollout).
         One env step of get_rollout_actions (encoder + A autoregressive decoder passes + sampling) and
@@ -186,11 +190,26 @@ class MATPolicy(PPOPolicy):
             a.E = E
             a.actor_obs_dim = int(buf.observations.shape[-1])
             self._step_args = a
-        if critic_obs.shape != (E, A, a.obs_dim) or not critic_obs.is_cuda:
-            raise _lib.PpoafError(f"mat rollout_step: critic_obs must be a device tensor [{E}, {A}, {a.obs_dim}]")
-        critic_obs = critic_obs.contiguous()
-        actor_obs = actor_obs.contiguous()
-        a.critic_obs, a.actor_obs = critic_obs.data_ptr(), actor_obs.data_ptr()
+        if blocks is not None:
+            why = self.step_blocks_unsupported_reason(*blocks)
+            if why:
+                raise _lib.PpoafError(f"mat rollout_step: {why}")
+            tb = getattr(self, "_step_blocks", None)
+            if tb is None:
+                tb = self._step_blocks = _lib.MatStepBlocks()
+            tb.n_blocks = A
+            for s_, b in enumerate(self.agent_slot_order()):
+                tb.slot_agent[s_] = int(b)
+            for b in range(A):
+                tb.critic_obs[b], tb.env_action[b] = blocks[0][b].data_ptr(), blocks[2][b].data_ptr()
+                tb.actor_obs[b] = None if blocks[1] is None else blocks[1][b].data_ptr()
+            a.critic_obs = a.actor_obs = None
+        else:
+            if critic_obs.shape != (E, A, a.obs_dim) or not critic_obs.is_cuda:
+                raise _lib.PpoafError(f"mat rollout_step: critic_obs must be a device tensor [{E}, {A}, {a.obs_dim}]")
+            critic_obs = critic_obs.contiguous()
+            actor_obs = actor_obs.contiguous()
+            a.critic_obs, a.actor_obs = critic_obs.data_ptr(), actor_obs.data_ptr()
         a.seed, a.offset = self.actor.distribution.rng.take(E * A)
         a.forced_action = None
         if forced_raw_action is not None:
@@ -205,12 +224,37 @@ class MATPolicy(PPOPolicy):
         a.action_out, a.raw_action_out = buf.actions[t].data_ptr(), buf.raw_actions[t].data_ptr()
         a.logp_out, a.value_out = buf.log_probs[t].data_ptr(), buf.values[t].data_ptr()
         a.critic_obs_copy_out, a.obs_copy_out = buf.critic_observations[t].data_ptr(), buf.observations[t].data_ptr()
-        _lib.check(_lib.load().ppoaf_mat_policy_step(C.byref(a), K.stream()), "mat_policy_step")
+        if blocks is not None:
+            _lib.check(_lib.load().ppoaf_mat_policy_step_blocks(C.byref(a), C.byref(tb), K.stream()), "mat_policy_step_blocks")
+        else:
+            _lib.check(_lib.load().ppoaf_mat_policy_step(C.byref(a), K.stream()), "mat_policy_step")
         return buf.actions[t]
+
+    def step_blocks_unsupported_reason(self, critic_obs_blocks, actor_obs_blocks, env_action_blocks):
+        """'' when ppoaf_mat_policy_step_blocks takes these per-agent blocks (the library checks the same before it launches)."""
+        from .. import _lib
+        buf = self.buffer
+        E, A = buf.C, buf.A
+        if not 1 <= A <= _lib.ROW_BLOCKS_MAX:
+            return f"{A} agents, a row-block table holds {_lib.ROW_BLOCKS_MAX}"
+        sets = [("critic observation", critic_obs_blocks, torch.float32, buf.critic_observations.shape[-1]),
+                ("env action", env_action_blocks, torch.int64, 1)]
+        if actor_obs_blocks is not None:
+            sets.append(("observation", actor_obs_blocks, torch.float32, buf.observations.shape[-1]))
+        for what, blks, dt, width in sets:
+            if len(blks) != A:
+                return f"{len(blks)} {what} blocks for {A} agents"
+            for b, x in enumerate(blks):
+                if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == E * width):
+                    return f"{what} block {b} is not a contiguous {dt} device tensor of {E} x {width}"
+                if x.data_ptr() % 16:
+                    return f"{what} block {b} does not start on a 16-byte boundary"
+        return ""
 
     def finish_step(self, t, rewards, next_obs=None):
         buf = self.buffer
-        buf.rewards[t].copy_(rewards.reshape(buf.rewards[t].shape))
+        if rewards is not None:           # None: K23 has written the row already
+            buf.rewards[t].copy_(rewards.reshape(buf.rewards[t].shape))
         if buf.next_observations is not None and next_obs is not None:
             buf.next_observations[t].copy_(next_obs.reshape(buf.next_observations[t].shape))
         buf.steps_written = max(buf.steps_written, t + 1)

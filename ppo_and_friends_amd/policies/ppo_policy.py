@@ -361,8 +361,12 @@ class PPOPolicy:
         from ..fused_update import FusedPolicyUpdate
         return FusedPolicyUpdate.unsupported_reason(self, 2)
 
-    def rollout_step(self, t, obs, critic_obs, value_normalizer=None, forced_raw_action=None):
+    def rollout_step(self, t, obs, critic_obs, value_normalizer=None, forced_raw_action=None, blocks=None):
         """
+        blocks (optional, then obs / critic_obs are None): (obs_blocks, critic_obs_blocks, env_action_blocks), one
+        device tensor per agent of the policy in env order -- [E_env, .] float32 rows of the env's observation tensors
+        where they lie (slices of an agent-major tensor or a dict env's entries) and the env's action tensors, which the
+        launch fills beside the buffer row (ppoaf_policy_step_blocks); `step_blocks_unsupported_reason` says when not.
         forced_raw_action (optional contiguous device tensor shaped like the step's raw actions: [E] / [E,1] int64
         (Discrete), [E,D] int64 (MultiDiscrete, one class per slice), [E,D] float32 (Box) or [E,n] float32 of 0 / 1
         (MultiBinary)): log these raw actions instead of sampling -- replay of a recorded rollout (log-probs, refined actions and values are computed
@@ -393,12 +397,24 @@ class PPOPolicy:
             a.act_lo = None if lo is None else lo.data_ptr()
             a.act_hi = None if hi is None else hi.data_ptr()
             self._step_args = a
-        K._req(obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous() and obs.numel() == E * a.actor.in_dim,
-               "rollout_step: obs must be a contiguous float32 device tensor [E, obs_dim]")
-        K._req(critic_obs.is_cuda and critic_obs.dtype == torch.float32 and critic_obs.is_contiguous()
-               and critic_obs.numel() == E * a.critic.in_dim,
-               "rollout_step: critic_obs must be a contiguous float32 device tensor [E, critic_obs_dim]")
-        a.obs = obs.data_ptr(); a.critic_obs = critic_obs.data_ptr()
+        if blocks is None:
+            K._req(obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous() and obs.numel() == E * a.actor.in_dim,
+                   "rollout_step: obs must be a contiguous float32 device tensor [E, obs_dim]")
+            K._req(critic_obs.is_cuda and critic_obs.dtype == torch.float32 and critic_obs.is_contiguous()
+                   and critic_obs.numel() == E * a.critic.in_dim,
+                   "rollout_step: critic_obs must be a contiguous float32 device tensor [E, critic_obs_dim]")
+            a.obs = obs.data_ptr(); a.critic_obs = critic_obs.data_ptr()
+        else:
+            why = self.step_blocks_unsupported_reason(*blocks)
+            if why:
+                raise _lib.PpoafError(f"rollout_step: {why}")
+            tb = getattr(self, "_step_blocks", None)
+            if tb is None:
+                tb = self._step_blocks = _lib.StepBlocks()
+            tb.n_blocks, tb.rows_per_block = len(blocks[0]), E // len(blocks[0])
+            for b, (o, co, ea) in enumerate(zip(*blocks)):
+                tb.obs[b], tb.critic_obs[b], tb.env_action[b] = o.data_ptr(), co.data_ptr(), ea.data_ptr()
+            a.obs = a.critic_obs = None
         a.forced_raw_action = None
         if forced_raw_action is not None:
             want = torch.float32 if a.head_kind in (K.HEAD_GAUSSIAN, K.HEAD_BERNOULLI) else torch.int64
@@ -420,8 +436,32 @@ class PPOPolicy:
         a.logp_out = buf.log_probs[t].data_ptr(); a.value_out = buf.values[t].data_ptr()
         a.obs_copy_out = buf.observations[t].data_ptr()
         a.critic_obs_copy_out = buf.critic_observations[t].data_ptr()
-        K.policy_step(a)
+        if blocks is None:
+            K.policy_step(a)
+        else:
+            K.policy_step_blocks(a, tb)
         return buf.actions[t]
+
+    def step_blocks_unsupported_reason(self, obs_blocks, critic_obs_blocks, env_action_blocks):
+        """'' when ppoaf_policy_step_blocks takes these row blocks (the library checks the same before it launches)."""
+        from .. import _lib
+        buf = self.buffer
+        n = len(obs_blocks)
+        if not 1 <= n <= _lib.ROW_BLOCKS_MAX:
+            return f"{n} row blocks, a table holds 1 .. {_lib.ROW_BLOCKS_MAX}"
+        if len(critic_obs_blocks) != n or len(env_action_blocks) != n or buf.C % n:
+            return f"{n} observation blocks, {len(critic_obs_blocks)} critic and {len(env_action_blocks)} action blocks for {buf.C} rows"
+        rows = buf.C // n
+        adt, per_row = buf.actions.dtype, buf.actions[0].numel() // buf.C
+        for what, blks, dt, width in (("observation", obs_blocks, torch.float32, buf.observations.shape[-1]),
+                                      ("critic observation", critic_obs_blocks, torch.float32, buf.critic_observations.shape[-1]),
+                                      ("env action", env_action_blocks, adt, per_row)):
+            for b, x in enumerate(blks):
+                if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == rows * width):
+                    return f"{what} block {b} is not a contiguous {dt} device tensor of {rows} x {width}"
+                if x.data_ptr() % 16:
+                    return f"{what} block {b} does not start on a 16-byte boundary"
+        return ""
 
     # ---- K21: the rollout / evaluation step of an LSTM policy in one launch (csrc/lstm_policy_step.hip)
     def lstm_step_unsupported_reason(self):
@@ -583,9 +623,11 @@ class PPOPolicy:
         return st["out"]
 
     def finish_step(self, t, rewards, next_obs=None):
-        """The environment's answer for step t: rewards (and next observations when ICM keeps them)."""
+        """The environment's answer for step t: rewards (None: K23 has written the row already) and next observations
+        when ICM keeps them."""
         buf = self.buffer
-        buf.rewards[t].copy_(rewards.reshape(-1))
+        if rewards is not None:
+            buf.rewards[t].copy_(rewards.reshape(-1))
         if buf.next_observations is not None and next_obs is not None:
             buf.next_observations[t].copy_(next_obs.reshape(buf.next_observations[t].shape))
         buf.steps_written = max(buf.steps_written, t + 1)

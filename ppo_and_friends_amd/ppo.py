@@ -167,6 +167,13 @@ class PermutationLoader:
 
 class PPO:
 
+    # K23 writes the reward / natural-reward / end_kind rows of every member of a multi-policy rollout and advances ep_ts
+    # in one launch per env step; False keeps the torch operators (the two are bitwise equal), for comparison
+    finish_rows = True
+    # K6+K7's block form for the feed-forward members of a multi-policy rollout (ppoaf_policy_step_blocks: observations
+    # read from the env's tensors through a row-block table, env actions written in place); False keeps the gathers
+    step_row_blocks = True
+
     def __init__(self, env_generator, policy_settings, policy_mapping_fn=None, device="cuda",
                  random_seed=None, envs_per_proc=1, max_ts_per_ep=200, batch_size=256,
                  ts_per_rollout=1024, gamma=0.99, epochs_per_iter=10, ext_reward_weight=1.0,
@@ -368,13 +375,7 @@ class PPO:
         intr_buf = torch.zeros(T, E * (pol.num_agents if grouped else 1), dtype=torch.float32,
                                device=self.device) if pol.enable_icm else None
 
-        def grouped_intrinsic(prev_obs, prev_cobs, nxt_obs, nxt_cobs, act_env):
-            """ppo.py:1219-1288 for an agent-grouped policy: agent-major [A*E] intrinsic rewards (one shared value
-            per env repeated for its agents, or one per (agent, env) row); observations = the actor's view."""
-            o1, o2 = (prev_cobs, nxt_cobs) if pol.expanded_actor_space else (prev_obs, nxt_obs)
-            if pol.agent_shared_icm:
-                return pol.get_agent_shared_intrinsic_rewards(o1, o2, act_env).repeat(n_ag)
-            return pol.get_intrinsic_reward(o1, o2, act_env)
+        grouped_intrinsic = lambda *step: self._grouped_intrinsic(pol, *step)
 
         if pol.enable_icm:
             may_end_early = True          # bootstrap rewards carry the "surprise" term: dense end table
@@ -382,16 +383,64 @@ class PPO:
         # layout, or None) makes every step log the recorded raw action instead of sampling one
         rec = getattr(self, "replay_raw_actions", None)
         replay = (lambda t: None) if rec is None else (lambda t: rec[t].contiguous())
+        mat_blocks = bool(self.step_row_blocks and fused_step and grouped)
+        if mat_blocks:
+            mat_act_env = torch.zeros((n_ag * n_envs,) + tuple(buf.actions.shape[3:]), dtype=buf.actions.dtype, device=self.device)
         nat_buf = self._scratch(f"nat_buf_{T}_{env.num_agents if hasattr(env, 'num_agents') else 1}_{n_envs}",
                                 T * (E if not grouped else E * pol.num_agents), torch.float32).view(T, -1)
+        mat_finish = None
+        if mat_blocks and self.finish_rows:
+            from .kernels import RolloutFinish
+            if RolloutFinish.unsupported_reason([n_ag]) == "":
+                mat_finish = RolloutFinish([dict(agents=list(range(n_ag)), index=list(range(n_ag)), rewards=buf.rewards,
+                                                 natural=nat_buf, end_kind=buf.end_kind, intrinsic=intr_buf,
+                                                 slot_order=pol.agent_slot_order())], n_ag, n_envs, self.max_ts_per_ep,
+                                           self.ext_reward_weight, ep_ts)
         for t in range(T):
             if fused_step and grouped:
                 # K16: encoder + autoregressive decoder passes + sampling + values + the buffer row in one launch
-                g_obs, g_cobs = group(obs), group(critic_obs)
-                action = pol.rollout_step(t, g_cobs, g_cobs if pol.expanded_actor_space else g_obs, vn, forced_raw_action=replay(t))
-                act_env = ungroup(action)
+                tb = None
+                if mat_blocks:
+                    # the block form reads the env's agent-major rows in the policy's slot order and writes the env's
+                    # action tensor itself: no group() / ungroup()
+                    cut = lambda x: list(x.reshape((n_ag, n_envs) + tuple(x.shape[1:])).unbind(0))
+                    tb = (cut(critic_obs), None if pol.expanded_actor_space else cut(obs), cut(mat_act_env))
+                    why = pol.step_blocks_unsupported_reason(*tb)
+                    if why:
+                        mat_blocks, tb = False, None
+                        if self.verbose:
+                            rank_print(f"rollout: policy {policy_id} regroups its rows with torch operators ({why})")
+                if tb is not None:
+                    pol.rollout_step(t, None, None, vn, forced_raw_action=replay(t), blocks=tb)
+                    act_env = mat_act_env
+                else:
+                    g_obs, g_cobs = group(obs), group(critic_obs)
+                    action = pol.rollout_step(t, g_cobs, g_cobs if pol.expanded_actor_space else g_obs, vn, forced_raw_action=replay(t))
+                    act_env = ungroup(action)
                 nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(act_env))
-                nat_buf[t].copy_(self._natural_reward(env, reward))
+                nat = self._natural_reward(env, reward)
+                terminated, truncated = terminated[:n_envs], truncated[:n_envs]   # agents of an env end together
+                if mat_finish is not None:
+                    why = "the step was regrouped" if tb is None else mat_finish.inputs_unsupported_reason(
+                        reward, None if nat is reward else nat, terminated if may_end_early else None,
+                        truncated if may_end_early else None)
+                    if why:               # the torch statements from here on (ep_ts has been advanced in place)
+                        mat_finish = None
+                        if self.verbose:
+                            rank_print(f"rollout: policy {policy_id}: the per-step rows stay on torch operators ({why})")
+                if mat_finish is not None:
+                    # K23 with one grouped member: reward (weighted, + intrinsic), natural reward, end_kind and ep_ts in one
+                    # launch, in the buffer's [E, A] slot order -- no group() of the reward either
+                    if pol.enable_icm:
+                        intr_buf[t] = group(grouped_intrinsic(obs, critic_obs, nxt_obs, nxt_cobs, act_env)).reshape(-1)
+                    mat_finish.step(t, reward, None if nat is reward else nat, terminated if may_end_early else None,
+                                    truncated if may_end_early else None, t == T - 1)
+                    pol.finish_step(t, None, group(nxt_cobs if pol.expanded_actor_space else term_obs) if pol.enable_icm else None)
+                    if may_end_early:
+                        buf.fixed_length = False
+                    obs, critic_obs = nxt_obs, nxt_cobs
+                    continue
+                nat_buf[t].copy_(nat)
                 if self.ext_reward_weight != 1.0:
                     reward = reward * self.ext_reward_weight
                 if pol.enable_icm:
@@ -399,7 +448,6 @@ class PPO:
                     intr_buf[t] = group(intr).reshape(-1)
                     reward = reward + intr
                 pol.finish_step(t, group(reward), group(nxt_cobs if pol.expanded_actor_space else term_obs) if pol.enable_icm else None)
-                terminated, truncated = terminated[:n_envs], truncated[:n_envs]   # agents of an env end together
             elif fused_step:
                 # K6+K7: inference, sampling, log-probs, values and the buffer row in one launch
                 action = pol.rollout_step(t, obs.contiguous(), critic_obs.contiguous(), vn, forced_raw_action=replay(t))
@@ -481,11 +529,36 @@ class PPO:
             next_value = pol.lstm_last_value(T - 1, critic_obs.contiguous(), vn)      # (lands in boot_value[T - 1])
         else:
             next_value = self.get_policy_values(policy_id, group(critic_obs) if grouped else critic_obs)
+        self._close_rollout_buffer(policy_id, pol, next_value, intr_buf, may_end_early, lstm_step)
+        self._obs = (obs, critic_obs)
+        pol.finalize_dataset()
+        self._publish_rollout_statistics(policy_id, buf, nat_buf, intr_buf, n_envs, T, obs, grouped)
+        gs = self.status_dict["global status"]
+        gs["timesteps"] += self.ts_per_rollout * mpi_utils.get_num_procs()     # env steps (ppo.py:1653), not agent steps
+        torch.cuda.synchronize() if self.device.type == "cuda" else None
+        gs["rollout time"] = time.time() - start
+        return pol.dataset
+
+    @staticmethod
+    def _grouped_intrinsic(pol, prev_obs, prev_cobs, nxt_obs, nxt_cobs, act_env):
+        """ppo.py:1219-1288 for an agent-grouped policy: agent-major [A*E] intrinsic rewards over the policy's own agents
+        (one shared value per env repeated for its agents, or one per (agent, env) row); observations = the actor's view."""
+        o1, o2 = (prev_cobs, nxt_cobs) if pol.expanded_actor_space else (prev_obs, nxt_obs)
+        if pol.agent_shared_icm:
+            return pol.get_agent_shared_intrinsic_rewards(o1, o2, act_env).repeat(pol.num_agents)
+        return pol.get_intrinsic_reward(o1, o2, act_env)
+
+    def _close_rollout_buffer(self, policy_id, pol, next_value, intr_buf, may_end_early, lstm_step=False):
+        """
+        The end of a rollout for one policy's buffer (ppo.py:1863-1930): bootstrap values and rewards of every episode end,
+        the statistics' view of them, and an ICM policy's "surprise".  next_value: V(observation after the last step).
+        """
+        buf = pol.buffer
         if may_end_early:
             if not pol.using_lstm:           # stateless critics: V(next obs) is the value logged at t + 1
                 buf.boot_value[:-1].copy_(buf.values[1:])
             if not lstm_step:
-                buf.boot_value[T - 1].copy_(next_value)
+                buf.boot_value[buf.T - 1].copy_(next_value)
             buf.boot_reward.copy_(buf.boot_value)
             buf.boot_stats = None
             if pol.enable_icm:
@@ -502,29 +575,25 @@ class PPO:
                     buf.boot_value.copy_(buf.boot_reward)
         else:
             buf.boot_stats = None
-            buf.end_kind[T - 1].fill_(2)
+            buf.end_kind[buf.T - 1].fill_(2)
             if not lstm_step:
-                buf.boot_value[T - 1].copy_(next_value)
-            buf.boot_reward[T - 1].copy_(next_value)
-        self._obs = (obs, critic_obs)
-        pol.finalize_dataset()
-        self._publish_rollout_statistics(policy_id, buf, nat_buf, intr_buf, n_envs, T, obs, grouped)
-        gs = self.status_dict["global status"]
-        gs["timesteps"] += self.ts_per_rollout * mpi_utils.get_num_procs()     # env steps (ppo.py:1653), not agent steps
-        torch.cuda.synchronize() if self.device.type == "cuda" else None
-        gs["rollout time"] = time.time() - start
-        return pol.dataset
+                buf.boot_value[buf.T - 1].copy_(next_value)
+            buf.boot_reward[buf.T - 1].copy_(next_value)
 
     def _rollout_multi_policy(self):
         """
         ppo.py:1534-2110 with several policies (`policy_mapping_fn` partitions the env's agents, ppo.py:329-345,
         710-858): every policy acts on its own agents' rows of the agent-major env tensors and logs into its own
         rollout buffer; the env is stepped once with the combined actions; episode ends are shared (the agents of an
-        env end together).  Covers feed-forward PPOPolicy instances (independent or team-wise PPO).  The env hands over
-        either agent-major tensors [A*E, .] (all agents share shapes) or, as the reference's multi-agent wrappers do,
-        dicts keyed by agent id (agents of different policies may then differ in observation / action space; the
-        agents of ONE policy share them, as in the reference).  Grouped (MAT), LSTM and ICM policies are
-        single-policy features here.
+        env end together).  Members are feed-forward PPOPolicy instances (independent or team-wise PPO) and MATPolicy
+        teams, each with or without an ICM; every member behaves as it does alone in `rollout` on an env restricted to
+        its agents.  The env hands over either agent-major tensors [A*E, .] (all agents share shapes) or, as the
+        reference's multi-agent wrappers do, dicts keyed by agent id (agents of different policies may then differ in
+        observation / action space; the agents of ONE policy share them, as in the reference).  A grouped member's
+        buffer rows are [E, A, .] in its own slot order and its `end_kind` is per env; an ICM member adds its
+        intrinsic reward after `ext_reward_weight`, keeps the next observations and turns the dense end table on for
+        the whole run (episode ends are shared).  `replay_raw_actions` may be a dict {policy_id: [T, rows, .]} in each
+        member's buffer layout.  LSTM policies stay a single-policy feature.
         """
         start = time.time()
         env = self.env
@@ -534,20 +603,36 @@ class PPO:
         A = len(agent_ids)
         ctxs = []
         for policy_id, pol in self.policies.items():
-            if pol.agent_grouping or pol.using_lstm or pol.enable_icm:
-                raise NotImplementedError("several policies in one run: feed-forward PPOPolicy without ICM only")
+            if pol.using_lstm:
+                raise NotImplementedError(f"several policies in one run: LSTM policies are not supported (policy {policy_id})")
+        for policy_id, pol in self.policies.items():
             pol.initialize_dataset()
             pol.eval()
             pol.initialize_episodes(n_envs, self.status_dict, ts_per_rollout=self.ts_per_rollout)
             idx = torch.as_tensor(sorted(agent_ids.index(a) for a in pol.agent_ids), device=self.device)
+            n = int(idx.numel())
             fused = (self.update_mode != "torch" and self.device.type == "cuda"
                      and pol.fused_step_unsupported_reason() == "")
-            ctxs.append(dict(id=policy_id, pol=pol, buf=pol.buffer, idx=idx, n=int(idx.numel()), fused=fused,
-                             agents=[agent_ids[int(i)] for i in idx],          # the policy's agents in env order
-                             vn=self.value_normalizers[policy_id] if self.normalize_values else None,
-                             nat=torch.zeros(T, int(idx.numel()) * n_envs, dtype=torch.float32, device=self.device)))
+            c = dict(id=policy_id, pol=pol, buf=pol.buffer, idx=idx, n=n, fused=fused, grouped=bool(pol.agent_grouping),
+                     agents=[agent_ids[int(i)] for i in idx],          # the policy's agents in env order
+                     vn=self.value_normalizers[policy_id] if self.normalize_values else None,
+                     nat=torch.zeros(T, n * n_envs, dtype=torch.float32, device=self.device),
+                     # per-step intrinsic rewards in the buffer's own layout (agents side by side when grouped)
+                     intr=torch.zeros(T, n * n_envs, dtype=torch.float32, device=self.device) if pol.enable_icm else None)
+            if c["grouped"]:
+                # MAT: [n*E, .] agent-major rows of the member's agents <-> [E, n, .] in its (shuffled) slot order
+                pol.shuffle_agent_ids()
+                c["order"] = torch.as_tensor(pol.agent_slot_order(), device=self.device)
+                c["inverse"] = torch.argsort(c["order"])
+            ctxs.append(c)
         if sorted(int(i) for c in ctxs for i in c["idx"]) != list(range(A)):
             raise ValueError("policy_mapping_fn must assign every agent of the env to exactly one policy")
+        group = lambda x, c: x.reshape((c["n"], n_envs) + tuple(x.shape[1:]))[c["order"]].transpose(0, 1).contiguous()
+        ungroup = lambda x, c: x.transpose(0, 1)[c["inverse"]].reshape((c["n"] * n_envs,) + tuple(x.shape[2:]))
+        rec = getattr(self, "replay_raw_actions", None)
+        if rec is not None and not isinstance(rec, dict):
+            raise ValueError("replay_raw_actions with several policies: a dict {policy_id: [T, rows, .]}")
+        replay = lambda t, c: None if rec is None or c["id"] not in rec else rec[c["id"]][t].contiguous()
         if self._obs is None or not self.soft_resets():
             obs, critic_obs = self.apply_policy_reset_constraints(*env.reset())
         else:
@@ -564,15 +649,85 @@ class PPO:
         per_env = lambda x: (x[agent_ids[0]] if isinstance(x, dict) else x[:n_envs])   # agents of an env end together
         ep_ts = torch.zeros(n_envs, dtype=torch.int32, device=self.device)
         may_end_early = getattr(env, "term_table", True) is not None or self.max_ts_per_ep < T
+        if any(c["pol"].enable_icm for c in ctxs):
+            may_end_early = True          # bootstrap rewards carry the "surprise" term: dense end table, shared by all
         actions = None
+        # K23 (kernels.RolloutFinish): the rows that follow env.step, for all members in one launch
+        finish, why = None, "the rollout is not on a HIP device or update_mode='torch'"
+        if self.finish_rows and self.device.type == "cuda" and self.update_mode != "torch":
+            from .kernels import RolloutFinish
+            why = RolloutFinish.unsupported_reason([c["n"] for c in ctxs])
+            if why == "":
+                finish = RolloutFinish(
+                    [dict(agents=c["agents"], index=c["idx"].tolist(), rewards=c["buf"].rewards, natural=c["nat"],
+                          end_kind=c["buf"].end_kind, intrinsic=c["intr"],
+                          slot_order=c["pol"].agent_slot_order() if c["grouped"] else None) for c in ctxs],
+                    A, n_envs, self.max_ts_per_ep, self.ext_reward_weight, ep_ts)
+        if finish is None and self.finish_rows and self.verbose:
+            rank_print(f"multi-policy rollout: the per-step rows stay on torch operators ({why})")
+        blocks_of = lambda x, c: ([x[a] for a in c["agents"]] if isinstance(x, dict) else
+                                  [x.reshape((A, n_envs) + tuple(x.shape[1:]))[i] for i in c["index"]])
+        for c in ctxs:
+            # the block forms of K6+K7 and K16: the member reads its agents' rows of the env's tensors where they lie and
+            # writes the env's action tensors itself (a MAT team in its slot order, without group() / ungroup())
+            c["index"] = c["idx"].tolist()
+            c["blocks"] = bool(self.step_row_blocks and c["fused"])
+            if c["blocks"] and dict_env:
+                row = c["buf"].actions[0]
+                per_agent = tuple(row.shape[2:] if c["grouped"] else row.shape[1:])
+                c["env_act"] = [torch.zeros((n_envs,) + per_agent, dtype=row.dtype, device=self.device) for _ in c["agents"]]
         for t in range(T):
             for c in ctxs:
-                pol, o, co = c["pol"], rows(obs, c).contiguous(), rows(critic_obs, c).contiguous()
-                if c["fused"]:
-                    a = pol.rollout_step(t, o, co, c["vn"])
+                pol = c["pol"]
+                if c["blocks"]:
+                    row = pol.buffer.actions[t]
+                    per_agent = tuple(row.shape[2:] if c["grouped"] else row.shape[1:])     # one agent's action in one env
+                    if not dict_env:
+                        if actions is None:
+                            actions = torch.zeros((A, n_envs) + per_agent, dtype=row.dtype, device=self.device)
+                        c["env_act"] = [actions[i] for i in c["index"]]
+                    if c["grouped"]:
+                        tb = (blocks_of(critic_obs, c), None if pol.expanded_actor_space else blocks_of(obs, c), c["env_act"])
+                    else:
+                        tb = (blocks_of(obs, c), blocks_of(critic_obs, c), c["env_act"])
+                    why = "the env's action tensor has another dtype or shape" if not dict_env and (
+                        actions.dtype != row.dtype or tuple(actions.shape[2:]) != per_agent) else \
+                        pol.step_blocks_unsupported_reason(*tb)
+                    if why:
+                        c["blocks"] = False
+                        if self.verbose:
+                            rank_print(f"multi-policy rollout: policy {c['id']} gathers its rows with torch operators ({why})")
+                    else:
+                        if c["grouped"]:
+                            pol.rollout_step(t, None, None, c["vn"], forced_raw_action=replay(t, c), blocks=tb)
+                            a = torch.cat(c["env_act"], 0) if pol.enable_icm else None        # agent-major, as ungroup() gives it
+                        else:
+                            a = pol.rollout_step(t, None, None, c["vn"], forced_raw_action=replay(t, c), blocks=tb)
+                        if pol.enable_icm:        # the ICM's view of the step: the critic's rows only where its actor sees them
+                            c["step"] = (rows(obs, c), rows(critic_obs, c) if c["grouped"] and pol.expanded_actor_space else None, a)
+                        else:
+                            c["step"] = (None, None, a)
+                        if dict_env:
+                            if actions is None:
+                                actions = {}
+                            actions.update(zip(c["agents"], c["env_act"]))
+                        continue
+                o, co = rows(obs, c).contiguous(), rows(critic_obs, c).contiguous()
+                if c["grouped"]:
+                    g_obs, g_cobs = group(o, c), group(co, c)
+                    a_obs = g_cobs if pol.expanded_actor_space else g_obs
+                    if c["fused"]:
+                        g_a = pol.rollout_step(t, g_cobs, a_obs, c["vn"], forced_raw_action=replay(t, c))
+                    else:
+                        raw, g_a, lp = pol.get_rollout_actions(a_obs, forced_raw_action=replay(t, c))
+                        c["pending"] = (g_cobs, a_obs, raw, g_a, self.get_policy_values(c["id"], g_cobs), lp)
+                    a = ungroup(g_a, c)
+                elif c["fused"]:
+                    a = pol.rollout_step(t, o, co, c["vn"], forced_raw_action=replay(t, c))
                 else:
-                    raw, a, lp = pol.get_rollout_actions(o)
+                    raw, a, lp = pol.get_rollout_actions(o, forced_raw_action=replay(t, c))
                     c["pending"] = (co, o, raw, a, self.get_policy_values(c["id"], co), lp)
+                c["step"] = (o, co, a)
                 if dict_env:
                     if actions is None:
                         actions = {}
@@ -591,28 +746,63 @@ class PPO:
             env_action = actions if dict_env else actions.reshape((A * n_envs,) + tuple(actions.shape[2:]))
             nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(env_action))
             nat = self._natural_reward(env, reward)
-            if self.ext_reward_weight != 1.0 and not dict_env:
+            env_reward = reward
+            if finish is not None:
+                why = finish.inputs_unsupported_reason(reward, None if nat is reward else nat,
+                                                       per_env(terminated) if may_end_early else None,
+                                                       per_env(truncated) if may_end_early else None)
+                if why:                   # the torch statements from here on (ep_ts has been advanced in place)
+                    finish = None
+                    if self.verbose:
+                        rank_print(f"multi-policy rollout: the per-step rows stay on torch operators ({why})")
+            if self.ext_reward_weight != 1.0 and not dict_env and finish is None:
                 reward = reward * self.ext_reward_weight
             for c in ctxs:
-                c["nat"][t].copy_(rows(nat, c))
-                r = rows(reward, c)
-                if self.ext_reward_weight != 1.0 and dict_env:
-                    r = r * self.ext_reward_weight
+                pol, nxt, intr = c["pol"], None, None
+                prev_o, prev_co, act = c.pop("step")
+                if pol.enable_icm and c["grouped"]:
+                    n_o, n_co = rows(nxt_obs, c), rows(nxt_cobs, c) if pol.expanded_actor_space else None
+                    intr = self._grouped_intrinsic(pol, prev_o, prev_co, n_o, n_co, act)
+                    c["intr"][t] = group(intr, c).reshape(-1)
+                    nxt = group(n_co if pol.expanded_actor_space else rows(term_obs, c), c)
+                elif pol.enable_icm:              # ppo.py:1719-1723: the post-step observation
+                    c["intr"][t] = intr = pol.get_intrinsic_reward(prev_o, rows(nxt_obs, c), act)
+                    nxt = rows(term_obs, c)
+                if finish is not None:
+                    r = c["buf"].rewards[t]       # K23 below writes the row: the torch path's write_step copies it onto itself
+                else:
+                    c["nat"][t].copy_(rows(nat, c))
+                    r = rows(reward, c)
+                    if self.ext_reward_weight != 1.0 and dict_env:
+                        r = r * self.ext_reward_weight
+                    if intr is not None:
+                        r = r + intr
+                    if c["grouped"]:
+                        r = group(r, c)
+                c["answer"] = (r, nxt)
+            if finish is not None:
+                # K23: every member's reward, natural-reward and end_kind rows and the shared ep_ts, in one launch
+                finish.step(t, env_reward, None if nat is env_reward else nat,
+                            per_env(terminated) if may_end_early else None, per_env(truncated) if may_end_early else None,
+                            t == T - 1)
+            for c in ctxs:
+                r, nxt = c.pop("answer")
                 if c["fused"]:
-                    c["pol"].finish_step(t, r, None)
+                    c["pol"].finish_step(t, None if finish is not None else r, nxt)
                 else:
                     co, o, raw, a, v, lp = c.pop("pending")
-                    c["buf"].write_step(t, slice(0, c["buf"].C), co, o, None, raw, a, v, lp, r)
+                    c["buf"].write_step(t, slice(0, c["buf"].C), co, o, nxt, raw, a, v, lp, r)
                     c["pol"]._t = t + 1
-            if may_end_early:
+                if may_end_early:
+                    c["buf"].fixed_length = False
+            if may_end_early and finish is None:
                 term_e, trunc_e = per_env(terminated), per_env(truncated)
                 ep_ts += 1
                 last = t == T - 1
                 boot = (~term_e) & ((ep_ts >= self.max_ts_per_ep) | trunc_e | last)
                 kind = torch.where(term_e, 1, torch.where(boot, 2, 0)).to(torch.int8)
                 for c in ctxs:
-                    c["buf"].end_kind[t] = kind.repeat(c["n"])
-                    c["buf"].fixed_length = False
+                    c["buf"].end_kind[t] = kind if c["grouped"] else kind.repeat(c["n"])
                 ep_ts = torch.where(term_e | boot, torch.zeros_like(ep_ts), ep_ts)
             obs, critic_obs = nxt_obs, nxt_cobs
         self._obs = (obs, critic_obs)
@@ -620,17 +810,11 @@ class PPO:
         episodes_before = gs["total episodes"]
         for c in ctxs:
             buf = c["buf"]
-            next_value = self.get_policy_values(c["id"], rows(critic_obs, c).contiguous())
-            if may_end_early:
-                buf.boot_value[:-1].copy_(buf.values[1:])
-                buf.boot_value[T - 1].copy_(next_value)
-                buf.boot_reward.copy_(buf.boot_value)
-            else:
-                buf.end_kind[T - 1].fill_(2)
-                buf.boot_value[T - 1].copy_(next_value)
-                buf.boot_reward[T - 1].copy_(next_value)
+            last_cobs = rows(critic_obs, c).contiguous()
+            next_value = self.get_policy_values(c["id"], group(last_cobs, c) if c["grouped"] else last_cobs)
+            self._close_rollout_buffer(c["id"], c["pol"], next_value, c["intr"], may_end_early)
             c["pol"].finalize_dataset()
-            self._publish_rollout_statistics(c["id"], buf, c["nat"], None, n_envs, T, rows(obs, c), False)
+            self._publish_rollout_statistics(c["id"], buf, c["nat"], c["intr"], n_envs, T, rows(obs, c), c["grouped"])
         # every policy's statistics pass added the (shared, per-env) episode count: keep it once (ppo.py:2089)
         gs["total episodes"] = episodes_before + (gs["total episodes"] - episodes_before) / len(ctxs)
         gs["timesteps"] += self.ts_per_rollout * mpi_utils.get_num_procs()
@@ -741,6 +925,22 @@ class PPO:
             out.append((policy_id, pol, [agent_ids[i] for i in idx], idx))
         return out
 
+    @staticmethod
+    def _member_inference_actions(pol, obs, critic_obs, n_envs, deterministic):
+        """One policy of a multi-policy env: its agents' agent-major rows [n*E, .] in, its agent-major actions out.  An
+        agent-grouped policy (MAT) decodes [E, n, .] in its slot order, on the critic's observation when its actor sees it."""
+        if not pol.agent_grouping:
+            return pol.get_inference_actions(obs.contiguous(), deterministic)
+        if pol.expanded_actor_space:
+            if critic_obs is None:
+                raise ValueError("this policy's actor sees the critic's observation: pass critic_obs")
+            obs = critic_obs
+        n = obs.shape[0] // n_envs
+        order = torch.as_tensor(pol.agent_slot_order(), device=obs.device)
+        g = obs.reshape((n, n_envs) + tuple(obs.shape[1:]))[order].transpose(0, 1).contiguous()
+        a = pol.get_inference_actions(g, deterministic)                     # [E, n, .]
+        return a.transpose(0, 1)[torch.argsort(order)].reshape((n * n_envs,) + tuple(a.shape[2:]))
+
     def get_inference_actions(self, obs, deterministic, critic_obs=None, env=None):
         """
         ppo.py:896-1028 for this package's batched contract: `obs` is what the env hands over (agent-major rows
@@ -755,7 +955,8 @@ class PPO:
         if isinstance(obs, dict):
             actions = {}
             for _, pol, agents, _ in groups:
-                a = pol.get_inference_actions(torch.cat([obs[k] for k in agents], 0).contiguous(), deterministic)
+                co = None if critic_obs is None else torch.cat([critic_obs[k] for k in agents], 0)
+                a = self._member_inference_actions(pol, torch.cat([obs[k] for k in agents], 0), co, n_envs, deterministic)
                 per_agent = a.reshape((len(agents), n_envs) + tuple(a.shape[1:]))
                 for i, agent_id in enumerate(agents):
                     actions[agent_id] = per_agent[i]
@@ -779,8 +980,9 @@ class PPO:
         actions = None
         for _, pol, agents, idx in groups:
             ix = torch.as_tensor(idx, device=obs.device)
-            o = obs.reshape((A, n_envs) + tuple(obs.shape[1:]))[ix].reshape((len(idx) * n_envs,) + tuple(obs.shape[1:]))
-            a = pol.get_inference_actions(o.contiguous(), deterministic)
+            take = lambda x: x.reshape((A, n_envs) + tuple(x.shape[1:]))[ix].reshape((len(idx) * n_envs,) + tuple(x.shape[1:]))
+            a = self._member_inference_actions(pol, take(obs), None if critic_obs is None else take(critic_obs), n_envs,
+                                               deterministic)
             if a.dim() == 1:
                 a = a.unsqueeze(-1)
             if actions is None:
