@@ -45,7 +45,60 @@ WORST = {}                     # case -> (worst fraction of the bound, where)
 # terms that cancel)
 TOTALS = [("", "totals", 0, (8,))]
 
-MEASURED = """(not measured yet)"""
+MEASURED = """
+worst deviation / bound per case (one run of the whole GPU suite)
+  B15                  0.255  clip step: actor.w_ih
+  B16                  0.257  clip step: actor.w_hh
+  B17                  0.258  second step: critic.b_ih
+  B2                   0.256  clip step: critic.ln_b
+  B257                 0.258  clip step: actor.ff0.weight
+  B31                  0.262  no clip step: actor.b_hh
+  B33                  0.269  no clip step: critic.ff0.bias
+  B5                   0.271  gradient: actor.ff2.bias
+  B80                  0.303  gradient: actor.w_ih
+  S1                   0.408  gradient: actor.ff2.weight
+  S15                  0.267  no clip step: actor.ff2.bias
+  S16                  0.262  clip step: critic.ff0.bias
+  S2                   0.261  no clip step: actor.w_hh
+  cat2                 0.260  clip step: actor.b_hh
+  cat8                 0.261  no clip step: actor.b_hh
+  fuzz 0               0.262  no clip step: actor.b_ih
+  fuzz 1               0.272  no clip step: critic.b_ih
+  fuzz 2               0.537  second gradient: critic.ff2.bias
+  fuzz 3               0.255  no clip m: actor.ff0.bias
+  fuzz 4               0.268  no clip step: actor.w_hh
+  fuzz 5               0.269  gradient: actor.ff0.bias
+  fuzz 6               0.257  second step: critic.b_hh
+  fuzz 7               0.269  second step: critic.b_ih
+  fuzz 8               0.255  no clip step: critic.ff0.weight
+  fuzz 9               0.290  no clip step: actor.w_ih
+  gau1                 0.335  gradient: actor.b_ih
+  gau2                 0.266  gradient: actor.w_hh
+  gau8                 0.270  no clip m: actor.ln_b
+  h128_f128            0.440  gradient: actor.ff0.bias
+  h128_f16             0.255  clip step: actor.ln_b
+  h128_f64             0.263  no clip m: actor.log_std
+  h32_f128             0.257  no clip step: critic.w_hh
+  h32_f16              0.280  gradient: actor.w_hh
+  h64_f128             0.346  no clip m: actor.w_ih
+  h64_f16              0.256  no clip step: actor.b_hh
+  h64_f32              0.260  clip step: critic.b_hh
+  in1                  0.253  clip step: critic.w_hh
+  in15                 0.272  clip step: actor.b_ih
+  in16                 0.261  clip step: critic.w_hh
+  in17                 0.257  clip step: critic.b_ih
+  in255                0.849  no clip step: actor.ff1.bias
+  in255_max            0.264  no clip step: critic.w_ih
+  in256                0.271  clip step: actor.w_ih
+  in256_max            0.435  no clip step: actor.ff2.weight
+  in3                  0.276  no clip step: actor.ff1.bias
+  ln_small_variance    0.263  clip step: actor.ff0.bias
+  mse_kl_no_entropy    0.268  no clip step: critic.ff0.bias
+  no_gradient_clip     0.253  no clip step: critic.b_ih
+  no_norm_adv          0.271  gradient: actor.ln_b
+  no_norm_values       0.261  no clip step: actor.b_ih
+  unequal_in           0.260  clip step: actor.w_hh
+"""
 
 
 @pytest.fixture(scope="module", autouse=True)

@@ -128,7 +128,9 @@ def test_first_minibatch_gradient_matches_the_oracle(shape):
     read the encoder's output, so the critic's tensors, the observation encoder's among them, also receive the actor
     loss.  The actor's tensors are compared with the trace as it is.  For the critic's, the same mini-batch is taken
     through the oracle's own evaluate and loss once more on a copy: its critic-loss share must be the trace's, and its
-    total is the reference.
+    total is the reference.  The atol here is on the BUCKET's scale, and at the default initialisation half of the tensors
+    lie orders of magnitude below it: tests/test_gpu_mat_update_float64.py judges every tensor of one K15 mini-batch on its
+    own scale, against float64, with the weights overwritten.
     """
     from torch.utils.data import DataLoader
     from oracle import ppo_loss_oracle as lo
