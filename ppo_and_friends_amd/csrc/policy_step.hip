@@ -205,7 +205,7 @@ template <bool XH>
 static int launch_widths_blocks(const StepDev& u, const StepBlocks& tb, size_t lds, hipStream_t s) {
     const int ha = u.net[0].H, hc = u.net[1].H;
 #define PPOAF_WIDTH_PAIR_CALL_(A, C) launch_step_blocks<A / 16, C / 16, XH>(u, tb, lds, s)
-    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+    PPOAF_WIDTH_PAIR_LADDER_ALL(ha, hc)
 #undef PPOAF_WIDTH_PAIR_CALL_
     set_error("policy_step_blocks: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_E_INVALID;
@@ -215,7 +215,7 @@ template <bool XH>
 static int launch_widths(const StepDev& u, size_t lds, hipStream_t s) {
     const int ha = u.net[0].H, hc = u.net[1].H;
 #define PPOAF_WIDTH_PAIR_CALL_(A, C) launch_step<A / 16, C / 16, XH>(u, lds, s)
-    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+    PPOAF_WIDTH_PAIR_LADDER_ALL(ha, hc)
 #undef PPOAF_WIDTH_PAIR_CALL_
     set_error("policy_step: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_E_INVALID;

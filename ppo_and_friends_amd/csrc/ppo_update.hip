@@ -227,8 +227,8 @@ __global__ __launch_bounds__(256) void minibatch_moments_kernel(const float* __r
 }
 
 int fill_net(const ppoaf_mlp_desc_t& d, NetDev& n, const char* what) {
-    PPOAF_REQUIRE(d.hidden >= 16 && d.hidden <= 256 && d.hidden % 16 == 0,
-                  "%s: hidden=%d must be a multiple of 16 in [16,256]", what, d.hidden);
+    PPOAF_REQUIRE(d.hidden >= 16 && d.hidden <= 512 && d.hidden % 16 == 0,
+                  "%s: hidden=%d must be a multiple of 16 in [16,512]", what, d.hidden);
     PPOAF_REQUIRE(d.depth >= 1 && d.depth + 1 <= kMaxLayers, "%s: depth=%d out of [1,%d]", what, d.depth, kMaxLayers - 1);
     PPOAF_REQUIRE(d.in_dim >= 1 && d.in_dim <= 1024, "%s: in_dim=%d", what, d.in_dim);
     PPOAF_REQUIRE(d.out_dim >= 1 && d.out_dim <= 8, "%s: out_dim=%d out of [1,8]", what, d.out_dim);
@@ -271,6 +271,11 @@ static int update_shapes(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
     if (rc) return rc;
     PPOAF_REQUIRE(a->B >= 2 && a->batch_stride >= a->B, "ppo_update: B=%ld stride=%ld", (long)a->B,
                   (long)a->batch_stride);
+    // a wide pair (512-wide critic) has no slab form: the limits of the split-wgrad chain are the pair's own
+    if (width_pair_is_wide(u.net[0].H, u.net[1].H))
+        PPOAF_REQUIRE(u.net[0].in_dim <= 64 && u.net[1].in_dim <= 64 && a->B <= 512,
+                      "ppo_update: the wide pair (actor %d, critic %d) runs the split-wgrad chain only: in_dim <= 64 and B <= 512 "
+                      "(got in_dim %d / %d, B %ld)", u.net[0].H, u.net[1].H, u.net[0].in_dim, u.net[1].in_dim, (long)a->B);
     return PPOAF_OK;
 }
 
@@ -327,15 +332,23 @@ int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
 }
 
 static size_t fwd_bwd_lds_bytes(const UpdateDev& u) {
+    if (width_pair_is_wide(u.net[0].H, u.net[1].H)) {       // the critic's body has a carve of its own, without line slots
+        const size_t a = (rowtile_lds_floats(u.net[0]) * 4 + 15) / 16 * 16 + kRowtileLineFloats * 4;
+        const size_t c = (rowtile_wide_lds_floats(u.net[1]) * 4 + 15) / 16 * 16;
+        return a > c ? a : c;
+    }
     const size_t a = rowtile_lds_floats(u.net[0]), c = rowtile_lds_floats(u.net[1]);
     return ((a > c ? a : c) * 4 + 15) / 16 * 16 + kRowtileLineFloats * 4;
 }
 
 // what fwd_bwd refuses beyond make_update_dev: the row-tile body's LDS and the instantiated width pairs
 static int fwd_bwd_fits(const UpdateDev& u) {
+    const int ha = u.net[0].H, hc = u.net[1].H;
+    // (a 512-wide network outside the list: refused by its widths, whatever the narrower bodies' LDS formula makes of it)
+    PPOAF_REQUIRE((ha <= 256 && hc <= 256) || width_pair_instantiated(ha, hc),
+                  "ppo_update_fwd_bwd: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     const size_t lds = fwd_bwd_lds_bytes(u);
     PPOAF_REQUIRE(lds <= 160 * 1024, "ppo_update_fwd_bwd: needs %zu B of LDS (> 160 KiB)", lds);
-    const int ha = u.net[0].H, hc = u.net[1].H;
     PPOAF_REQUIRE(width_pair_instantiated(ha, hc),
                   "ppo_update_fwd_bwd: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_OK;
@@ -359,11 +372,12 @@ extern "C" int ppoaf_ppo_update_fwd_bwd_timed(const ppoaf_ppo_update_args_t* arg
     const size_t lds = fwd_bwd_lds_bytes(u);
     hipStream_t s = (hipStream_t)stream;
     // the instantiated (actor width, critic width) pairs (ppo_update_dev.hpp: PPOAF_WIDTH_PAIRS; the host falls back to the
-    // torch path otherwise): this translation unit's share of the list, then ppo_update_narrow.hip's
+    // torch path otherwise): this translation unit's share of the list, then ppo_update_wide.hip's and ppo_update_narrow.hip's
     const FwdBwdLaunch L = {u, args, lds, s, e0, e1};
 #define PPOAF_WIDTH_PAIR_CALL_(A, C) fwd_bwd_launch_pair<A, C>(L)
     PPOAF_WIDTH_PAIR_LADDER_OF(PPOAF_WIDTH_PAIRS_IN_UPDATE, u.net[0].H, u.net[1].H)
 #undef PPOAF_WIDTH_PAIR_CALL_
+    if (width_pair_is_wide(u.net[0].H, u.net[1].H)) return fwd_bwd_launch_wide(L);
     return fwd_bwd_launch_narrow(L);
 }
 

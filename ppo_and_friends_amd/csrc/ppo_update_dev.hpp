@@ -36,23 +36,46 @@ static __device__ unsigned long long g_ppo_update_stamps[2][16];
 // The instantiated (actor width, critic width) pairs of K6+K7 (policy_step.hip) and K12 (fwd_bwd, the wgrad launch, the
 // fused tail): the ONE list.  Every dispatcher expands it into its `if` ladder and fwd_bwd_fits / the ladders' last line
 // refuse what it does not name, so no launch can accept a pair that another one refuses.  A critic is never narrower than
-// its actor here; 512-wide networks need a tile width, LDS budgets and a weight-gradient grid of their own.
-// (two sub-lists: fwd_bwd's kernels are spread over ppo_update.hip and ppo_update_narrow.hip, ppo_update_fwd_bwd.hpp)
+// its actor here; a 512-wide network has a row-tile body of its own (ppo_update_rowtile_wide.hpp) and exists as a critic
+// beside a 256-wide actor only.
+// (three sub-lists: fwd_bwd's kernels are spread over ppo_update.hip, ppo_update_narrow.hip and ppo_update_wide.hip,
+//  ppo_update_fwd_bwd.hpp)
+// The WIDE sub-list is the one place where a launch refuses what the list names: its pair runs the three-launch form of the
+// split-wgrad chain only (fwd_bwd -> ppoaf_ppo_update_wgrad -> ppoaf_ppo_update_adam(3)).  The fused tail
+// (ppo_update_tail.hip) and the row-pair kernel have no instantiation for it -- the tail's ladder, PPOAF_WIDTH_PAIR_LADDER,
+// runs over the pairs that have every launch form and answers "not instantiated" with the widths; pairs_run() needs a
+// 256-wide critic -- and the host never asks for either (fused_update.py: tail_reason, pairs_reason).
 #define PPOAF_WIDTH_PAIRS_IN_UPDATE(X) X(32, 32) X(64, 64) X(128, 128) X(256, 256) X(128, 256) X(64, 128)
 #define PPOAF_WIDTH_PAIRS_IN_NARROW(X) X(64, 256) X(32, 256) X(32, 64)
-#define PPOAF_WIDTH_PAIRS(X) PPOAF_WIDTH_PAIRS_IN_UPDATE(X) PPOAF_WIDTH_PAIRS_IN_NARROW(X)
+#define PPOAF_WIDTH_PAIRS_WIDE(X) X(256, 512)
+#define PPOAF_WIDTH_PAIRS_EVERY_FORM(X) PPOAF_WIDTH_PAIRS_IN_UPDATE(X) PPOAF_WIDTH_PAIRS_IN_NARROW(X)
+#define PPOAF_WIDTH_PAIRS(X) PPOAF_WIDTH_PAIRS_EVERY_FORM(X) PPOAF_WIDTH_PAIRS_WIDE(X)
 // one rung per pair: with PPOAF_WIDTH_PAIR_CALL_(A, C) defined as the expression that launches pair <A, C>,
-// PPOAF_WIDTH_PAIR_LADDER(ha, hc) returns its value for the pair (ha, hc) and falls through for a pair not in the list
-// (PPOAF_WIDTH_PAIR_LADDER_OF: over one of the sub-lists)
+// PPOAF_WIDTH_PAIR_LADDER_ALL(ha, hc) returns its value for the pair (ha, hc) and falls through for a pair not in the list
+// (PPOAF_WIDTH_PAIR_LADDER_OF: over one of the sub-lists; PPOAF_WIDTH_PAIR_LADDER: the pairs with every launch form)
 #define PPOAF_WIDTH_PAIR_RUNG_(A, C) if (ppoaf_ha_ == A && ppoaf_hc_ == C) return PPOAF_WIDTH_PAIR_CALL_(A, C);
 #define PPOAF_WIDTH_PAIR_LADDER_OF(LIST, ha, hc) \
     { const int ppoaf_ha_ = (ha), ppoaf_hc_ = (hc); LIST(PPOAF_WIDTH_PAIR_RUNG_) }
-#define PPOAF_WIDTH_PAIR_LADDER(ha, hc) PPOAF_WIDTH_PAIR_LADDER_OF(PPOAF_WIDTH_PAIRS, ha, hc)
+#define PPOAF_WIDTH_PAIR_LADDER(ha, hc) PPOAF_WIDTH_PAIR_LADDER_OF(PPOAF_WIDTH_PAIRS_EVERY_FORM, ha, hc)
+#define PPOAF_WIDTH_PAIR_LADDER_ALL(ha, hc) PPOAF_WIDTH_PAIR_LADDER_OF(PPOAF_WIDTH_PAIRS, ha, hc)
 inline bool width_pair_instantiated(const int ha, const int hc) {
 #define PPOAF_WIDTH_PAIR_CALL_(A, C) true
-    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+    PPOAF_WIDTH_PAIR_LADDER_ALL(ha, hc)
 #undef PPOAF_WIDTH_PAIR_CALL_
     return false;
+}
+inline bool width_pair_is_wide(const int ha, const int hc) {
+#define PPOAF_WIDTH_PAIR_CALL_(A, C) true
+    PPOAF_WIDTH_PAIR_LADDER_OF(PPOAF_WIDTH_PAIRS_WIDE, ha, hc)
+#undef PPOAF_WIDTH_PAIR_CALL_
+    return false;
+}
+// dynamic LDS of the wide critic's row-tile body (the carve of ppo_update_rowtile_wide.hpp): the row tables, biases, ONE
+// output row of weights, the input rows, three activation-sized planes and the output / d output tiles.  No line slots:
+// 124.7 KB at depth 7 and in_dim 64.
+inline size_t rowtile_wide_lds_floats(const NetDev& n) {
+    const size_t HS = n.H + 4, INP = 16 * ((n.in_dim + 15) / 16) + 4;
+    return 208 + (size_t)(n.depth + 1) * n.H + (size_t)n.H + kRows * INP + 3 * kRows * HS + 2 * kRows * kMaxOut;
 }
 
 // Per-mini-batch panels shared by the layered mode of the two-XCD persistent kernel and by the split-wgrad chain

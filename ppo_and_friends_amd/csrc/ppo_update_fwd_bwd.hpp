@@ -1,7 +1,7 @@
 // K12's fwd_bwd launch: the two kernels (one workgroup per 16-row tile; 256-wide networks' tiles on workgroup pairs) and
 // their launchers, shared by the translation units that instantiate them -- ppo_update.hip (pairs of equal widths, 128/256,
-// 64/128) and ppo_update_narrow.hip (the narrow-actor pairs 64/256, 32/256, 32/64): one hipcc process each, so that neither
-// is the build's long pole alone.  Which unit holds which pair: PPOAF_WIDTH_PAIRS, ppo_update_dev.hpp.
+// 64/128), ppo_update_narrow.hip (the narrow-actor pairs 64/256, 32/256, 32/64) and ppo_update_wide.hip (256/512, whose
+// critic runs the body of ppo_update_rowtile_wide.hpp): one hipcc process each, so that none is the build's long pole alone.  Which unit holds which pair: PPOAF_WIDTH_PAIRS, ppo_update_dev.hpp.
 #pragma once
 #include "ppo_update_rowpair.hpp"
 #include <hip/hip_ext.h>
@@ -122,5 +122,7 @@ inline int fwd_bwd_launch_pair(const FwdBwdLaunch& L) {
 }
 // the narrow-actor pairs' rungs, then the refusal of a pair the list does not name (ppo_update_narrow.hip)
 int fwd_bwd_launch_narrow(const FwdBwdLaunch& L);
+// the wide pairs' rungs (ppo_update_wide.hip): the split-wgrad chain only, one workgroup per tile
+int fwd_bwd_launch_wide(const FwdBwdLaunch& L);
 
 }  // namespace ppoaf

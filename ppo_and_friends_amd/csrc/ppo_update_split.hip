@@ -167,7 +167,7 @@ extern "C" int ppoaf_ppo_update_wgrad(const ppoaf_ppo_update_args_t* args, ppoaf
     hipStream_t s = (hipStream_t)stream;
     const int ha = u.net[0].H, hc = u.net[1].H;
 #define PPOAF_WIDTH_PAIR_CALL_(A, C) wgrad_launch<A, C>(u, s)
-    PPOAF_WIDTH_PAIR_LADDER(ha, hc)
+    PPOAF_WIDTH_PAIR_LADDER_ALL(ha, hc)
 #undef PPOAF_WIDTH_PAIR_CALL_
     set_error("ppo_update_wgrad: hidden widths (actor %d, critic %d) not instantiated", ha, hc);
     return PPOAF_E_INVALID;

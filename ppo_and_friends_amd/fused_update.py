@@ -72,8 +72,9 @@ def set_action_slices(args, slices):
         args.action_slices[j] = slices[j] if j < len(slices) else 0
 
 
-def _describe(net, bucket, with_log_std):
-    """MlpDesc of a FeedForwardNetwork living in `bucket`, or (None, reason)."""
+def _describe(net, bucket, with_log_std, wide=False):
+    """MlpDesc of a FeedForwardNetwork living in `bucket`, or (None, reason).  wide: a 512-wide network is described too
+    (the critic of a policy with `fused_wide_critic`: WIDE_WIDTH_PAIRS)."""
     if not isinstance(net, FeedForwardNetwork) or net.is_embedded:
         return None, "network is not a plain FeedForwardNetwork"
     dims = net.layer_dims()
@@ -82,7 +83,7 @@ def _describe(net, bucket, with_log_std):
     H = dims[0][1]
     if any(o != H for (_, o) in dims[:-1]) or any(i != H for (i, _) in dims[1:]):
         return None, "hidden layers must share one width"
-    if H not in (32, 64, 128, 256):
+    if H not in (32, 64, 128, 256) and not (wide and H == 512):
         return None, f"hidden width {H} is not one of the instantiated widths (32, 64, 128, 256)"
     act = _activation_code(net.activation)
     if act is None:
@@ -722,6 +723,15 @@ class FusedLstmUpdate(FusedEpoch):
 
 # the (actor width, critic width) pairs K6+K7 and K12 are instantiated for (csrc/ppo_update_dev.hpp: PPOAF_WIDTH_PAIRS)
 WIDTH_PAIRS = ((32, 32), (64, 64), (128, 128), (256, 256), (128, 256), (64, 128), (64, 256), (32, 256), (32, 64))
+# ... and the pairs with a 512-wide critic (PPOAF_WIDTH_PAIRS_WIDE; csrc/ppo_update_rowtile_wide.hpp), taken only for a policy
+# whose `fused_wide_critic` is true (PPO sets it under update_mode="fused"; "auto" keeps the torch-ROCm path for them): the
+# split-wgrad chain in its three-launch form, single rank, in_dim <= 64, batch sizes <= 512.
+WIDE_WIDTH_PAIRS = ((256, 512),)
+
+
+def wide_critic(pol):
+    """The policy's 512-wide critic may run on the fused kernels (PPOPolicy.fused_wide_critic)."""
+    return bool(getattr(pol, "fused_wide_critic", False))
 
 
 class FusedPolicyUpdate(FusedEpoch):
@@ -739,17 +749,28 @@ class FusedPolicyUpdate(FusedEpoch):
         a, why = _describe(pol.actor, pol.policy_params, head == K.HEAD_GAUSSIAN)
         if a is None:
             return "actor: " + why
-        c, why = _describe(pol.critic, pol.policy_params, False)
+        c, why = _describe(pol.critic, pol.policy_params, False, wide_critic(pol))
         if c is None:
             return "critic: " + why
         if c.out_dim != 1:
             return "critic must have one output"
         if a.offset != 0 or c.offset != a.size:
             return "actor and critic buckets are not adjacent"
-        if (a.hidden, c.hidden) not in WIDTH_PAIRS:
+        wide = (a.hidden, c.hidden) in WIDE_WIDTH_PAIRS          # (a 512-wide critic is described for wide_critic(pol) only)
+        if (a.hidden, c.hidden) not in WIDTH_PAIRS and not wide:
             return f"hidden widths (actor {a.hidden}, critic {c.hidden}) are not an instantiated pair"
         if batch_size < 2:
             return "batch size < 2"
+        if wide:
+            pair = f"wide pair (actor {a.hidden}, critic {c.hidden})"
+            if max(a.in_dim, c.in_dim) > 64:
+                return f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 64 (the split-wgrad chain's panels cover in_dim <= 64)"
+            if batch_size > 512:
+                return f"{pair}: batch size {batch_size} > 512 (the split-wgrad chain covers batch sizes <= 512)"
+            if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
+                return f"{pair}: PPOAF_SPLIT_WGRAD=0, and the wide pair has no slab form"
+            if mpi_utils.get_num_procs() > 1:
+                return f"{pair}: single rank only for now ({mpi_utils.get_num_procs()} ranks)"
         # what the library itself refuses (depth, in_dim, the row-tile body's LDS): host-only, nothing is launched
         q = _lib.PpoUpdateArgs()
         q.actor, q.critic, q.bucket_total = a, c, a.size + c.size
@@ -759,16 +780,29 @@ class FusedPolicyUpdate(FusedEpoch):
             return _lib.load().ppoaf_last_error().decode("utf-8", "replace")
         return ""
 
+    @staticmethod
+    def fused_mode_would_take(pol, batch_size):
+        """True for a policy that is refused only because `fused_wide_critic` is off (what "auto" says under verbose)."""
+        if wide_critic(pol) or pol.using_lstm or pol.agent_grouping:
+            return False
+        pol.fused_wide_critic = True
+        try:
+            return FusedPolicyUpdate.unsupported_reason(pol, batch_size) == ""
+        finally:
+            pol.fused_wide_critic = False
+
     def __init__(self, ppo, policy_id):
         super().__init__(ppo, policy_id)
         pol = self.pol
         dev = pol.device
         self.head, self.action_slices, _ = action_head(pol)
         self.actor_desc, _ = _describe(pol.actor, pol.policy_params, self.head == K.HEAD_GAUSSIAN)
-        self.critic_desc, _ = _describe(pol.critic, pol.policy_params, False)
+        self.critic_desc, _ = _describe(pol.critic, pol.policy_params, False, wide_critic(pol))
+        self.wide = (self.actor_desc.hidden, self.critic_desc.hidden) in WIDE_WIDTH_PAIRS
         self.n_wg = (self.B + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
         total = pol.policy_params.numel()
-        self.slabs = torch.zeros(self.n_wg, total, dtype=torch.float32, device=dev)
+        # (a wide pair has no slab form: a placeholder for the args' pointer instead of n_wg x 0.75 M floats nothing reads)
+        self.slabs = torch.zeros((1, 4) if self.wide else (self.n_wg, total), dtype=torch.float32, device=dev)
         _init_normaliser(self)
         self.loss_partials = torch.zeros(2, self.n_wg, 8, dtype=torch.float32, device=dev)
         self.rows = None
@@ -817,6 +851,8 @@ class FusedPolicyUpdate(FusedEpoch):
         where the split saves more than a launch costs (<8,16>: 46.5 + 6.9 against 59 us; <8,8>: 17.8 + 5.1 against 21.4).
         """
         mode = _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1"))
+        if self.wide:
+            return True, ""            # (the only form a wide pair has: unsupported_reason has refused everything else)
         if mode == "0":
             return False, "off (PPOAF_SPLIT_WGRAD=0)"
         if max(self.actor_desc.in_dim, self.critic_desc.in_dim) > 64 or self.B > 512:
@@ -867,6 +903,8 @@ class FusedPolicyUpdate(FusedEpoch):
     def tail_reason(self):
         """'' when a mini-batch of the split-wgrad chain ends in ppoaf_ppo_update_wgrad_adam, else why it takes the
         wgrad and Adam launches.  PPOAF_FUSED_TAIL = 1 (default) | 0."""
+        if self.wide:                  # (at every depth: the fused tail is not instantiated for a 512-wide critic)
+            return "wide pair: the mini-batch ends in the wgrad and Adam launches"
         if _switch("PPOAF_FUSED_TAIL", "1") == "0":
             return "off (PPOAF_FUSED_TAIL=0)"
         if getattr(self, "_tail_disabled", ""):

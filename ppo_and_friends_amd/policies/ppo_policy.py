@@ -140,6 +140,9 @@ class PPOPolicy:
         self.use_huber_loss = use_huber_loss
         self.frozen = False
         self.fused_action_heads = False      # MultiDiscrete / MultiBinary heads on K6 / K12 (set by PPO(update_mode="fused"))
+        # a 512-wide critic beside a 256-wide actor on K6+K7 / K12 (fused_update.WIDE_WIDTH_PAIRS): set by
+        # PPO(update_mode="fused"), or by hand before the first rollout.  False: the torch path, with today's messages.
+        self.fused_wide_critic = False
         self.fused_lstm_step = True          # K21 for the rollout / evaluation step of a covered LSTM policy
         self.fused_lstm_update = True        # K22 for the update epoch of a covered LSTM policy (False: the mini-batch loop)
         self.random_seed = random_seed
@@ -387,7 +390,7 @@ class PPOPolicy:
             head, slices, _ = action_head(self)
             gauss = head == K.HEAD_GAUSSIAN
             a.actor, _ = _describe(self.actor, self.policy_params, gauss)
-            a.critic, _ = _describe(self.critic, self.policy_params, False)
+            a.critic, _ = _describe(self.critic, self.policy_params, False, self.fused_wide_critic)
             a.params = self.policy_params.data_ptr()
             a.E = E
             a.head_kind = head
@@ -696,7 +699,7 @@ class PPOPolicy:
         if self.using_lstm:
             return "LSTM policies are not K19's: K21 or forward_logits (see lstm_step_unsupported_reason)"
         # (asked once per evaluation step: the answer is kept for as long as what it depends on stays)
-        key = (self.policy_params.data_ptr(), bool(self.fused_action_heads))
+        key = (self.policy_params.data_ptr(), bool(self.fused_action_heads), bool(self.fused_wide_critic))
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
             self._infer_reason = (key, self.fused_step_unsupported_reason())
         return self._infer_reason[1]

@@ -278,6 +278,8 @@ class PPO:
             pol.fused_icm_reward = update_mode != "torch"       # K14's kernels for the rollout-time intrinsic reward
             # the MultiDiscrete / MultiBinary heads of K6 / K12 (csrc/action_heads.hpp); "auto" keeps them on torch-ROCm for now
             pol.fused_action_heads = update_mode == "fused"
+            # ... and so does a 512-wide critic beside a 256-wide actor (fused_update.WIDE_WIDTH_PAIRS)
+            pol.fused_wide_critic = update_mode == "fused"
             if update_mode == "fused" and pol.using_lstm and self.device.type == "cuda":
                 # K18 for both recurrent networks, in the rollout and in the update ("auto" keeps nn.LSTM for now)
                 from .fused_update import FusedLstm
@@ -1492,7 +1494,10 @@ class PPO:
                 if self.update_mode == "fused":
                     raise NotImplementedError(f"update_mode='fused' but {why}")
                 if self.verbose:
-                    rank_print(f"policy {policy_id}: torch update path ({why})")
+                    hint = ""
+                    if driver is FusedPolicyUpdate and FusedPolicyUpdate.fused_mode_would_take(self.policies[policy_id], B):
+                        hint = "; update_mode='fused' would take it on the fused kernels"
+                    rank_print(f"policy {policy_id}: torch update path ({why}){hint}")
                 self._fused[key] = None
             else:
                 self._fused[key] = driver(self, policy_id)
