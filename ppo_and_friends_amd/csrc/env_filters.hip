@@ -16,6 +16,7 @@
 //     count' = count + n*n_all,  mean' = m + S1/count',  var' = (count*var + S2 - S1^2/count')/count'
 // (n_all = rows of all ranks: each of the n updates gathers every rank's vector, stats.py:47-50).
 #include "common.hpp"
+#include "running_stats_device.hpp"
 
 namespace ppoaf {
 
@@ -99,23 +100,12 @@ __device__ __forceinline__ void obs_column_apply(const ObsF& f, int col, long n,
                     const double* rec = recs + (long)r * rec_len;
                     const double nr = rec[0];
                     if (nr <= 0.0) continue;
-                    const double d = rec[f.off_mean + col] - mb, nn = nb + nr;
-                    mb += d * (nr / nn);
-                    M2 += rec[f.off_m2 + col] + d * d * nb * nr / nn;
-                    nb = nn;
+                    chan_merge(nb, mb, M2, nr, rec[f.off_mean + col], rec[f.off_m2 + col]);
                 }
                 if (nb > 0.0) {
-                    // stats.py:73-94, expression order of moments.hip (float32 state, float64 count)
-                    const float batch_mean = (float)mb, batch_var = (float)(M2 / nb);
-                    const double old_count = f.count[col];
-                    const float delta = batch_mean - mean;
-                    const double new_count = old_count + nb;
-                    const float new_mean = (float)((double)mean + (double)delta * (nb / new_count));
-                    const double m_2 = (double)var * old_count + (double)batch_var * nb +
-                                       (double)(delta * delta) * old_count * nb / new_count;
-                    mean = new_mean;
-                    var = (float)(m_2 / new_count);
-                    f.mean[col] = mean; f.var[col] = var; f.count[col] = new_count;
+                    double count = f.count[col];
+                    running_integrate(mean, var, count, nb, mb, M2);
+                    f.mean[col] = mean; f.var[col] = var; f.count[col] = count;
                 }
             }
             sh[0] = mean;

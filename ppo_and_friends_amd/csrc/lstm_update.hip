@@ -16,6 +16,7 @@
 
 #include "lstm_device.hpp"
 #include "ppo_update_dev.hpp"
+#include "running_stats_device.hpp"
 
 namespace ppoaf {
 namespace {
@@ -91,32 +92,6 @@ inline long upd_lds_bytes(const int H) {
     return 4 * (fwd + (b1 > b2 ? b1 : b2) + own);
 }
 
-// the mini-batch's value-normaliser state: Chan merge of the ranks' records, then the reference's integrate
-// (utils/stats.py:73-94), as K12 and K15
-__device__ __forceinline__ void upd_vn_state(const LstmUpdDev& u, const long mb, float& m, float& v, double& cnt) {
-    const int slot = (int)(mb & 1);
-    m = u.vn_mean[slot]; v = u.vn_var[slot]; cnt = u.vn_count[slot];
-    if (!u.normalize_values) return;
-    double n = 0.0, bm = 0.0, M2 = 0.0;
-    for (int r = 0; r < u.n_ranks; ++r) {
-        const double* rec = u.vn_records + (mb * u.n_ranks + r) * 3;
-        const double nb = rec[0];
-        if (nb <= 0.0) continue;
-        const double d = rec[1] - bm, nn = n + nb;
-        bm += d * (nb / nn);
-        M2 += rec[2] + d * d * n * nb / nn;
-        n = nn;
-    }
-    if (n > 0.0) {
-        const float batch_mean = (float)bm, batch_var = (float)(M2 / n);
-        const float delta = batch_mean - m;
-        const double new_count = cnt + n;
-        const float new_mean = (float)((double)m + (double)delta * (n / new_count));
-        const double m_2 = (double)v * cnt + (double)batch_var * n + (double)(delta * delta) * cnt * n / (cnt + n);
-        m = new_mean; v = (float)(m_2 / (cnt + n)); cnt = new_count;
-    }
-}
-
 template <int H>
 __global__ __launch_bounds__(H / 16 * 64) void lstm_update_fwd_bwd_kernel(const LstmUpdDev u) {
     constexpr int NT = H / 16 * 64;
@@ -177,17 +152,13 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_update_fwd_bwd_kernel(const 
     }
     if (tid == 64) {
         float mean_f = 0.f, std_f = 1.f;
-        if (which == 0 && u.normalize_adv) {
-            const double* rec = u.adv_records + mb * 3;
-            mean_f = (float)rec[1];
-            std_f = (float)sqrt(rec[2] / (rec[0] - 1.0));
-        }
+        if (which == 0 && u.normalize_adv) adv_mean_std(u.adv_records + mb * 3, mean_f, std_f);
         sMisc[0] = mean_f; sMisc[1] = std_f;
     }
     if (tid == 96) {
         float m = 0.f, v = 1.f;
         double cnt = 0.0;
-        if (which == 1) upd_vn_state(u, mb, m, v, cnt);
+        if (which == 1) minibatch_vn_state(u, mb, m, v, cnt);
         sMisc[2] = m; sMisc[3] = v;
     }
     __syncthreads();
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_update_fwd_bwd_kernel(const 
     __syncthreads();
 
     // ---- head + loss of the 16 rows by one wave (K12's), d loss / d out -> sDOut
-    if (tid < 64) ppo_head_loss<false>(u, which, g, O, u.log_std, sRow, sRowF, sMisc, sActF, sOut, sDOut, tid, B);
+    if (tid < 64) ppo_head_loss(u, which, g, O, u.log_std, sRow, sRowF, sMisc, sActF, sOut, sDOut, tid, B);
     __syncthreads();
     for (int e = tid; e < kLRows * O; e += NT) {
         const int r = e / O, o = e - r * O;
@@ -319,7 +290,7 @@ __device__ __forceinline__ void lstm_update_bookkeeping(const LstmUpdDev& u) {
         const long mb = u.cursor[0];
         float m, v;
         double cnt;
-        upd_vn_state(u, mb, m, v, cnt);
+        minibatch_vn_state(u, mb, m, v, cnt);
         const int slot = (int)(mb & 1) ^ 1;
         u.vn_mean[slot] = m; u.vn_var[slot] = v; u.vn_count[slot] = cnt;
         u.cursor[0] = mb + 1;

@@ -16,6 +16,7 @@
 // A mini-batch of 256 envs is 52 workgroups; the ~80 dependent phases are barrier + LDS latency
 // bound, not MFMA bound -- the point is that they replace ~270 separate kernel launches.
 #include "mlp_device.hpp"
+#include "running_stats_device.hpp"
 #include "tail_sync.hpp"
 #include "wgrad_tile.hpp"
 #include <hip/hip_ext.h>
@@ -819,39 +820,14 @@ __device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
     }
     if (tid == 64) {
         float mean_f = 0.f, std_f = 1.f;
-        if (u.normalize_adv) {
-            const double* rec = u.adv_records + mb * 3;
-            mean_f = (float)rec[1];
-            std_f = (float)sqrt(rec[2] / (rec[0] - 1.0));
-        }
+        if (u.normalize_adv) adv_mean_std(u.adv_records + mb * 3, mean_f, std_f);
         sMisc[0] = mean_f; sMisc[1] = std_f;
     }
-    if (tid == 128) {
-        // value normaliser: Chan merge of the rank records of this mini-batch + the reference's integrate
-        // (utils/stats.py:73-94), as in K12
+    if (tid == 128) {                                       // the value normaliser of this mini-batch
         const int slot = (int)(mb & 1);
-        float m = u.vn_mean[slot], v = u.vn_var[slot];
-        double cnt = u.vn_count[slot];
-        if (u.normalize_values) {
-            double n = 0.0, bm = 0.0, M2 = 0.0;
-            for (int r = 0; r < u.n_ranks; ++r) {
-                const double* rec = u.vn_records + (mb * u.n_ranks + r) * 3;
-                const double nb = rec[0];
-                if (nb <= 0.0) continue;
-                const double d = rec[1] - bm, nn = n + nb;
-                bm += d * (nb / nn);
-                M2 += rec[2] + d * d * n * nb / nn;
-                n = nn;
-            }
-            if (n > 0.0) {
-                const float batch_mean = (float)bm, batch_var = (float)(M2 / n);
-                const float delta = batch_mean - m;
-                const double new_count = cnt + n;
-                const float new_mean = (float)((double)m + (double)delta * (n / new_count));
-                const double m_2 = (double)v * cnt + (double)batch_var * n + (double)(delta * delta) * cnt * n / (cnt + n);
-                m = new_mean; v = (float)(m_2 / (cnt + n)); cnt = new_count;
-            }
-        }
+        float m, v;
+        double cnt;
+        minibatch_vn_state(u, mb, m, v, cnt);
         sMisc[2] = m; sMisc[3] = v;
         if (g == 0) { u.vn_mean[slot ^ 1] = m; u.vn_var[slot ^ 1] = v; u.vn_count[slot ^ 1] = cnt; }
     }

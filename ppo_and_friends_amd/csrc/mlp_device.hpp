@@ -66,64 +66,29 @@ __device__ __forceinline__ float softplus_u(float x) { return x > 20.f ? x : log
 //      C/D col = lane&15, row = 4*(lane>>4)+reg).  The k order inside a 16-chunk is permuted the
 //      same way on both operands (lane slot s carries k = 4s+j at step j), which leaves the sum intact.
 
-// B fragments of one forward tile: fr[c] = W[o][16c + 4*slot .. +3], o = n0 + (lane&15); W row-major [*, H]
-// Loads of data that ANOTHER CU of the same launch may have rewritten (the persistent update kernels: weights after
-// the Adam phase, slabs, activations, the gradient bucket, statistics).  A CU's vector L1 is never refreshed by
-// another CU's stores, so these loads must not be served by it.  NT = true: AGENT-SCOPE loads (`sc1`), the form the
-// AMDGPU memory model defines for reading other CUs' data -- 4-byte values as relaxed agent-scope atomic loads, 16-byte
-// values as two 8-byte ones (MI355X_MICROARCH.md, inter-workgroup visibility, "8-B agent atomics" / `sc1` loads): they
-// miss in the L1 by definition and are served by the L2 all workers of a network share (one XCD), whatever other loads
-// have touched the same lines before.  (Rounds 1-2 used non-temporal loads here: a cache-policy HINT that happened to
-// bypass the L1 as long as every access to those lines was non-temporal; measured the same speed)  The producers' side is `s_waitcnt vmcnt(0)` + workgroup barrier before the flag store: their write-through
-// stores have been acknowledged by that same L2.  NT = false: plain loads (separate launches: the kernel boundary does
-// the invalidation).
-template <bool NT> __device__ __forceinline__ float ld1(const float* p) {
-    if (NT) return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    return *p;
-}
-template <bool NT> __device__ __forceinline__ double ld1(const double* p) {
-    if (NT) return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
-                                                                     __HIP_MEMORY_SCOPE_AGENT));
-    return *p;
-}
-// 16 bytes in ONE instruction: `buffer_load_dwordx4 ... sc1` (two 8-byte agent-scope loads measured 8-10 % slower per
-// mini-batch at C4).  A buffer resource needs a wave-uniform base: the first active lane's address minus 2 GiB, each lane
-// then carries its own 32-bit byte offset (the lanes of a wave read one array: far less than 2 GiB apart).  The compiler
-// tracks it with vmcnt like any other load.
-typedef unsigned ppoaf_u32x4 __attribute__((ext_vector_type(4)));
-template <bool NT> __device__ __forceinline__ float4 ld4(const float* p) {
-    if (NT) {
-        const unsigned long long a = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo0 = __builtin_amdgcn_readfirstlane((unsigned)a), hi0 = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        const unsigned long long base = (((unsigned long long)hi0 << 32) | lo0) - 0x80000000ull;
-        __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(base), 0, 0xFFFFFFFF, 0x00020000);
-        const ppoaf_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (unsigned)(a - base), 0, 16 /* sc1 */);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    }
-    return *reinterpret_cast<const float4*>(p);
-}
-
-template <int HT, bool NT = false>
+// B fragments of one forward tile: fr[c] = W[o][16c + 4*slot .. +3], o = n0 + (lane&15); W row-major [*, H].  Plain loads:
+// every kernel here reads what an EARLIER launch wrote (the kernel boundary invalidates a CU's vector L1).
+template <int HT>
 __device__ __forceinline__ void load_fwd_frags(const float* __restrict__ W, int n0, int lane, float4 (&fr)[HT]) {
     const float* w = W + (long)(n0 + (lane & 15)) * (16 * HT) + 4 * (lane >> 4);
     // chunks c and c + 1 lie in one 128-byte line of every row: even chunks first -- a load that asks for a line whose fill is
     // still pending stalls the CU's L1 (round 4, stamps of the 256-wide row pairs: a 128 KB set arrived in 18 k cycles instead of
     // 32 k; C2 +0.7 %)
 #pragma unroll
-    for (int c = 0; c < HT; c += 2) fr[c] = ld4<NT>(w + 16 * c);
+    for (int c = 0; c < HT; c += 2) fr[c] = *reinterpret_cast<const float4*>(w + 16 * c);
     __builtin_amdgcn_sched_barrier(0);                    // (the scheduler would sort the loads by offset again)
 #pragma unroll
-    for (int c = 1; c < HT; c += 2) fr[c] = ld4<NT>(w + 16 * c);
+    for (int c = 1; c < HT; c += 2) fr[c] = *reinterpret_cast<const float4*>(w + 16 * c);
 }
 // B fragments of one dgrad tile: fr[c] = { W[16c+4*slot+j][n0 + (lane&15)] }_j
-template <int HT, bool NT = false>
+template <int HT>
 __device__ __forceinline__ void load_dgrad_frags(const float* __restrict__ W, int n0, int lane, float4 (&fr)[HT]) {
     constexpr int H = 16 * HT;
     const float* w = W + (long)(4 * (lane >> 4)) * H + n0 + (lane & 15);
 #pragma unroll
     for (int c = 0; c < HT; ++c) {
         const float* wp = w + (long)(16 * c) * H;
-        fr[c] = make_float4(ld1<NT>(wp), ld1<NT>(wp + H), ld1<NT>(wp + 2 * H), ld1<NT>(wp + 3 * H));
+        fr[c] = make_float4(wp[0], wp[H], wp[2 * H], wp[3 * H]);
     }
 }
 // The same fragments through a buffer resource on the (wave-uniform) weight matrix: every load of a set shares ONE
@@ -132,6 +97,7 @@ __device__ __forceinline__ void load_dgrad_frags(const float* __restrict__ W, in
 // two sets cannot be in flight at once).  Forward chunks c and c + 1 share a 128-byte line of every row: even chunks
 // first -- a load that asks for a line whose fill is still pending stalls the CU's L1 (stamps: a 128 KB set arrived in
 // 18 k cycles instead of 32 k).
+typedef unsigned ppoaf_u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t frag_rsrc(const float* W) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, 0x7FFFFFFF, 0x00020000);
 }

@@ -42,7 +42,9 @@ __global__ __launch_bounds__(256) void running_moments_integrate_kernel(
     double n_tot = 0.0;
     for (int r = 0; r < R; ++r) n_tot += moments[(long)r * stride];
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < W; c += gridDim.x * blockDim.x) {
-        // Chan merge of the R records -> batch (n, mean, M2)
+        // Chan merge of the R records -> batch (n, mean, M2), then the integrate step: chan_merge and running_integrate of
+        // running_stats_device.hpp, written out (through the helpers this kernel comes out with other register numbers
+        // and another instruction order, and no tool of the project times it)
         double n = 0.0, m = 0.0, M2 = 0.0;
         for (int r = 0; r < R; ++r) {
             const double nb = moments[(long)r * stride];

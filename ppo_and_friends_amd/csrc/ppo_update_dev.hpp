@@ -3,6 +3,7 @@
 // list of the split-wgrad launches and the distribution head + loss terms of one 16-row block.
 #pragma once
 #include "action_heads.hpp"
+#include "running_stats_device.hpp"
 #include "wgrad_tile.hpp"
 #include <cstddef>
 #include <cstring>
@@ -323,7 +324,7 @@ __device__ __forceinline__ unsigned hw_xcc_id() {
 //   ppo_head_values  the critic's u.values[row] = v (ppo.py:2340), from sOut alone.
 //   ppo_head_block   the block part: the parked terms, read in row order, -> the same eight 16-lane sums -> u.loss_partials.
 // The last two may run on any wave, any time after a barrier behind the row part, while sRow / sOut / sActF are intact.
-template <bool NT, typename U>
+template <typename U>
 __device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const int out_dim,
                                               const float* __restrict__ log_std_p, const int* sRow,
                                               const float* sRowF, const float* sMisc, float* sActF, float* sOut,
@@ -442,7 +443,7 @@ __device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const
             float lp = 0.f, slog = 0.f;
             ent = 0.f;
             for (int d = 0; d < out_dim; ++d) {
-                const float sd = fmaxf(softplus_u(ld1<NT>(log_std + d)), u.min_std);
+                const float sd = fmaxf(softplus_u(log_std[d]), u.min_std);
                 const float mu = sOut[s * kMaxOut + d];
                 const float zz = x[d] - mu;
                 const float l0 = -logf(sd) - 0.91893853320467274178f;
@@ -469,7 +470,7 @@ __device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const
             glp *= inv_B;
             const float gH = (u.entropy_weight != 0.0f) ? -u.entropy_weight * inv_B : 0.f;
             for (int d = 0; d < out_dim; ++d) {
-                const float ls = ld1<NT>(log_std + d);
+                const float ls = log_std[d];
                 const float sp = softplus_u(ls), sd = fmaxf(sp, u.min_std);
                 const float mu = sOut[s * kMaxOut + d];
                 const float zz = x[d] - mu;
@@ -549,12 +550,12 @@ __device__ __forceinline__ void ppo_head_block(const U& u, const int which, cons
 }
 
 // the three parts back to back on one wave (the pair body, ppo_update_rowpair.hpp; K22, lstm_update.hip)
-template <bool NT, typename U>
+template <typename U>
 __device__ __forceinline__ void ppo_head_loss(const U& u, const int which, const int g, const int out_dim,
                                               const float* __restrict__ log_std_p, const int* sRow,
                                               const float* sRowF, const float* sMisc, float* sActF, float* sOut,
                                               float* sDOut, const int lane, const long B) {
-    ppo_head_rows<NT>(u, which, out_dim, log_std_p, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
+    ppo_head_rows(u, which, out_dim, log_std_p, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
     if (which != 0) ppo_head_values(u, sRow, sOut, lane);
     ppo_head_block(u, which, g, sMisc, sActF, lane);
 }

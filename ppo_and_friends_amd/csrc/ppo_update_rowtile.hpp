@@ -12,20 +12,9 @@ extern __shared__ __attribute__((aligned(16))) unsigned char ppo_update_smem[];
 // activation h_l and of every dLoss/dz_l (u.sp: hbuf / dbuf / xbuf planes, 16 KB per layer per workgroup at H = 128
 // against a 135 KB slab) -- and the output layer's partials go to u.sp.outpart (folded in block order by that launch).
 
-// A forward weight set of one output tile: requested as whole lines and turned into fragment order through the wave's LDS
-// slots when consumed (mlp_device.hpp: mfma_rows_x_lines; one CU's L1 delivers the fragment pattern itself at a third of
-// that rate).  (NT = true: agent-scope loads in fragment order -- the removed persistent forms.)
-template <int HT, bool NT>
-__device__ __forceinline__ void load_fwd_set(const float* __restrict__ W, int n0, int lane, float4 (&fr)[HT]) {
-    if constexpr (NT) load_fwd_frags<HT, true>(W, n0, lane, fr);
-    else load_fwd_lines_buf<HT>(W, n0, lane, fr);
-}
-template <int HT, bool NT>
-__device__ __forceinline__ f32x4 mfma_fwd_set(const float* __restrict__ A, int HS, int lane, const float4 (&fr)[HT], float init,
-                                              float* __restrict__ scratch) {
-    if constexpr (NT) return mfma_rows_x_frags<HT>(A, HS, lane, fr, init);
-    else return mfma_rows_x_lines<HT>(A, HS, lane, fr, init, scratch);
-}
+// (A forward weight set of one output tile is requested as whole lines, load_fwd_lines_buf, and turned into fragment order
+//  through the wave's LDS slots when consumed, mfma_rows_x_lines: one CU's L1 delivers the fragment pattern itself at a
+//  third of that rate.)
 
 // The kernel arguments the prologue of a row-tile workgroup needs, asked for in ONE batch at the kernel's entry.  Left to
 // itself the compiler fetches the 1176-byte argument block field group by field group as the code reaches each use, every
@@ -96,24 +85,15 @@ template <int CP> __device__ __forceinline__ void lds_write_adjacent(float* p, c
 // then waited for the sets as well.  Every other case runs the body as it was (TABLES = false: both decided at run time).
 template <int HT, bool SPLIT, bool TABLES>
 __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, const int which, const int g) {
-    // (NT, mb_extra: what the persistent forms of rounds 2-3 set -- loads at agent scope, the mini-batch's position inside a
-    //  launch; the forms are gone, the constants keep the body's text as it was measured)
-    constexpr bool NT = false;
-    constexpr long mb_extra = 0;
     constexpr int H = 16 * HT, HS = H + 4;                 // which: 0 actor, 1 critic; g: 16-row block
-    int tid_ = threadIdx.x;
-    if (NT) {     // persistent form: nothing derived from the lane id may be hoisted out of the caller's mini-batch loop
-        asm volatile("" : "+v"(tid_));
-        __builtin_assume(tid_ >= 0 && tid_ < kThreadsU);
-    }
-    const int tid = tid_, lane = tid & 63, wave = NT ? __builtin_amdgcn_readfirstlane(tid >> 6) : (tid >> 6);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const auto& nd = u.net[which];
     const int in_dim = nd.in_dim, depth = nd.depth, out_dim = nd.out_dim, act = nd.act;
     const int NT0 = (in_dim + 15) >> 4;                    // 16-column tiles of the input
     const int INP = 16 * NT0 + 4;
     const float* P = u.params + nd.offset;
     const long B = u.B;
-    const long mb = u.cursor[0] + u.mb_offset + mb_extra;
+    const long mb = u.cursor[0] + u.mb_offset;
     const long base = mb * u.batch_stride;
     // Layer offsets inside the bucket, by arithmetic: indexing a table in the kernel arguments with a
     // loop variable compiles to a vector load of kernarg memory plus a full vmcnt drain (~6k cycles).
@@ -161,11 +141,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
 
     PPOAF_STAMP(0);
     // ---- LDS carve (all offsets multiples of 16 B)
-    // persistent form: an opaque zero in the LDS base keeps the per-lane LDS addresses of the body from being hoisted
-    // out of the caller's mini-batch loop (hoisted, all of them are live at once)
-    int zl = 0;
-    if (NT) asm volatile("" : "+s"(zl));
-    float* smem = reinterpret_cast<float*>(ppo_update_smem + zl);
+    float* smem = reinterpret_cast<float*>(ppo_update_smem);
     int* sRow = reinterpret_cast<int*>(smem);                 // [16]
     float* sMisc = smem + 16;                                 // [16]: adv mean/std, vn mean/var
     float* sRowF = smem + 32;                                 // [3][16]: adv, old log-prob, rewards-to-go
@@ -178,9 +154,9 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     float* sD1 = sD0 + kRows * HS;                            // [16, HS]
     float* sOut = sD1 + kRows * HS;                           // [16, 16]
     float* sDOut = sOut + kRows * kMaxOut;                    // [16, 16]
-    float* sScr = sDOut + kRows * kMaxOut + wave * 2 * kLineSlot;   // this wave's two line slots (separate launches only)
+    float* sScr = sDOut + kRows * kMaxOut + wave * 2 * kLineSlot;   // this wave's two line slots
 
-    if (!NT && g == 0 && which == 0 && tid == 0) { u.norm_scratch[0] = 0.0; u.norm_scratch[1] = 0.0; }
+    if (g == 0 && which == 0 && tid == 0) { u.norm_scratch[0] = 0.0; u.norm_scratch[1] = 0.0; }
 
     // Deep prefetch (three hidden layers, one output tile per wave): the weights depend on nothing, so the
     // fragments of BOTH hidden-to-hidden layers are requested before anything else; as each set is consumed
@@ -203,17 +179,16 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     const int n_bias = (depth + 1) * H, n_wout = out_dim * H;
     const bool copy_fits = n_bias <= kCopyRegs * kThreadsU && n_wout <= kCopyRegs * kThreadsU;
     auto request_weights = [&]() {
-        // separate launches: request order = arrival order (a wave's loads return in order) -- layer 0's operands, biases and
-        // output weights go out BEFORE the 2 x 8 KB per wave of hidden-layer sets, so the first layer starts after one
-        // memory round trip instead of behind the whole stream (round 4)
-        if (NT && deep && has_tile) {
-            load_fwd_set<HT, NT>(P + offW(1), wave * 16, lane, fr);
-            load_fwd_set<HT, NT>(P + offW(2), wave * 16, lane, fr2);
-        }
+        // (fr, fr2 stay captured here though only request_hidden_sets fills them: without the two captures six fwd_bwd
+        //  kernels, <8,8,*> among them, come out with other register numbers and one more SGPR spill)
+        (void)fr; (void)fr2;
+        // request order = arrival order (a wave's loads return in order) -- layer 0's operands, biases and output weights
+        // go out BEFORE the 2 x 8 KB per wave of hidden-layer sets, so the first layer starts after one memory round trip
+        // instead of behind the whole stream (round 4)
         if (l0_pre) {
             const float* w = P + offW(0) + (long)(wave * 16 + (lane & 15)) * in_dim;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { const int k = 4 * j + (lane >> 4); if (k < in_dim) l0w[j] = ld1<NT>(w + k); }
+            for (int j = 0; j < 4; ++j) { const int k = 4 * j + (lane >> 4); if (k < in_dim) l0w[j] = w[k]; }
         }
         // The weights were rewritten by the Adam kernel a moment ago, so this XCD's L2 does not hold them:
         // the first touch of every 128-B line of the network is requested here, before anything else, so
@@ -224,30 +199,29 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
 #ifndef PPOAF_L2_TOUCH_MAX_HT
 #define PPOAF_L2_TOUCH_MAX_HT 8
 #endif
-        if (!deep && !NT && HT <= PPOAF_L2_TOUCH_MAX_HT) for (long i = (long)tid * 32; i < nd.size; i += (long)kThreadsU * 32) l2_touch += P[i];
+        if (!deep && HT <= PPOAF_L2_TOUCH_MAX_HT) for (long i = (long)tid * 32; i < nd.size; i += (long)kThreadsU * 32) l2_touch += P[i];
         if (copy_fits) {
 #pragma unroll
             for (int r = 0; r < kCopyRegs; ++r) {
                 const int i = tid + r * kThreadsU;
                 bias_reg[r] = 0.f; wout_reg[r] = 0.f;
-                if (i < n_bias) { const int l = i / H, j = i - l * H; if (l < depth || j < out_dim) bias_reg[r] = ld1<NT>(P + offB(l) + j); }
-                if (i < n_wout) wout_reg[r] = ld1<NT>(P + offW(depth) + i);
+                if (i < n_bias) { const int l = i / H, j = i - l * H; if (l < depth || j < out_dim) bias_reg[r] = P[offB(l) + j]; }
+                if (i < n_wout) wout_reg[r] = P[offW(depth) + i];
             }
         }
     };
     // ... and the hidden sets, LAST of the prologue's requests: whatever a wave asks for behind them arrives behind 16 KB
     auto request_hidden_sets = [&]() {
-        if (!NT && deep && has_tile) {
-            load_fwd_set<HT, NT>(P + offW(1), wave * 16, lane, fr);
-            load_fwd_set<HT, NT>(P + offW(2), wave * 16, lane, fr2);
+        if (deep && has_tile) {
+            load_fwd_lines_buf<HT>(P + offW(1), wave * 16, lane, fr);
+            load_fwd_lines_buf<HT>(P + offW(2), wave * 16, lane, fr2);
         }
     };
-    // three-launch chain: the weights first (cold misses, nothing to wait for).  Persistent forms: the row loads
-    // first, then the hook (the wait for the previous Adam phase), then the weights (L2 hits).
+    // the weights first (cold misses, nothing to wait for)
     // per-epoch tables in shuffled order: an input row's address depends on the cursor only -- requested now (16 x in_dim <=
     // 1024 values: two per thread), dropped below where the row turns out to be padding
     const float* x_src = which == 0 ? u.obs : u.critic_obs;
-    const bool x_pre = !NT && (TABLES || u.pregathered) && kRows * in_dim <= 2 * kThreadsU;
+    const bool x_pre = (TABLES || u.pregathered) && kRows * in_dim <= 2 * kThreadsU;
     float xr[2] = {0.f, 0.f};
     if (x_pre) {
 #pragma unroll
@@ -258,7 +232,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     }
     // (a line of text in the assembly: tools/prologue_isa.py reads the TABLES flavour's prologue from here)
     if constexpr (TABLES) asm volatile("; ppoaf_rowtile_tables_prologue");
-    if (!NT) request_weights();
+    request_weights();
 
     // Wave 0's row lanes and the statistics lane, in arrival order as well (a wave's loads retire in order): with the
     // per-epoch tables in shuffled order (u.pregathered) the address of a row's scalars -- like the index itself -- depends
@@ -268,7 +242,6 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     constexpr int kActRegs = 8;                            // sActF holds 8 action words per row
     constexpr int kVnPre = 2;                              // per-rank value-normaliser records requested ahead of the sets
     const bool row_lane = tid < kRows && (long)g * kRows + tid < B;      // rows >= B: no address is formed
-    static_assert(!TABLES || !NT, "per-epoch tables: separate launches only");
     constexpr bool early = TABLES;                         // (every other case: behind the index, as it was)
     const int n_act = which != 0 ? 0 : u.head_kind == PPOAF_HEAD_CATEGORICAL ? 1
                     : u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? u.n_slices : out_dim;
@@ -316,8 +289,8 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             }
         } else {
             const int slot = (int)(mb & 1);
-            vn_m = ld1<NT>(u.vn_mean + slot); vn_v = ld1<NT>(u.vn_var + slot);
-            vn_cnt = ld1<NT>(u.vn_count + slot);
+            vn_m = u.vn_mean[slot]; vn_v = u.vn_var[slot];
+            vn_cnt = u.vn_count[slot];
             if (u.normalize_values) {
 #pragma unroll
                 for (int r = 0; r < kVnPre; ++r) {
@@ -330,6 +303,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
         }
     }
     // Chan merge of the per-rank records of this mini-batch (one step; the reference's order: rank 0 first)
+    // (chan_merge of running_stats_device.hpp, written out: calling it here renumbers registers in these kernels)
     double vn_n = 0.0, vn_bm = 0.0, vn_M2 = 0.0;
     auto vn_merge = [&](const double nb, const double mean, const double m2) {
         if (nb <= 0.0) return;
@@ -349,7 +323,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             vn_merge(rec[0], rec[1], rec[2]);
         }
     }
-    if (!NT) request_hidden_sets();
+    request_hidden_sets();
 
     if (tid < kRows) {
         auto store_row = [&](const int row, const bool have) {
@@ -384,18 +358,15 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     if (stat_lane) {                                        // a lane of wave 1: mini-batch statistics
         if (which == 0) {
             float mean_f = 0.f, std_f = 1.f;
-            if (u.normalize_adv) {                           // ppo.py:2326-2333, from the per-epoch table
-                mean_f = (float)adv_rec[1];
-                std_f = (float)sqrt(adv_rec[2] / (adv_rec[0] - 1.0));
-            }
+            if (u.normalize_adv) adv_mean_std(adv_rec, mean_f, std_f);     // from the per-epoch table
             sMisc[0] = mean_f; sMisc[1] = std_f;
         } else {
             const int slot = (int)(mb & 1);
             float m = vn_m, v = vn_v;
             double cnt = vn_cnt;
             if (u.normalize_values) {
-                // Chan merge of the R per-rank records of this mini-batch, then the reference's
-                // integrate (utils/stats.py:73-94) -- same arithmetic as running_moments_integrate_kernel.
+                // the records requested ahead of the sets (unless the dependent trip above has merged them already), then
+                // the reference's integrate (running_integrate, written out for the same reason as the merge above)
                 if (u.n_ranks <= kVnPre) {
 #pragma unroll
                     for (int r = 0; r < kVnPre; ++r)
@@ -427,9 +398,9 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
         for (int l = 0; l <= depth; ++l) {
             const int n = (l == depth) ? out_dim : H;
             const float* bb = P + offB(l);
-            for (int i = tid; i < n; i += kThreadsU) sBias[l * H + i] = ld1<NT>(bb + i);
+            for (int i = tid; i < n; i += kThreadsU) sBias[l * H + i] = bb[i];
         }
-        for (int i = tid; i < out_dim * H; i += kThreadsU) sWout[i] = ld1<NT>(P + offW(depth) + i);
+        for (int i = tid; i < out_dim * H; i += kThreadsU) sWout[i] = P[offW(depth) + i];
     }
     for (int i = tid; i < kRows * INP; i += kThreadsU) sX[i] = 0.f;
     __syncthreads();
@@ -453,7 +424,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
         }
     }
     // prefetch: fragments of the first hidden-to-hidden layer (or nothing if depth == 1)
-    if (!deep && depth > 1 && has_tile) load_fwd_set<HT, NT>(P + offW(1), wave * 16, lane, fr);
+    if (!deep && depth > 1 && has_tile) load_fwd_lines_buf<HT>(P + offW(1), wave * 16, lane, fr);
     __syncthreads();
     PPOAF_STAMP(2);
     if (SPLIT) {            // the block's input rows, zero padded to 64 columns: the layer-0 wgrad's K-panel
@@ -476,7 +447,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int k = k0 + 4 * j + (lane >> 4);
-                bq[j] = l0_pre ? l0w[j] : (k < in_dim ? ld1<NT>(w + k) : 0.f);
+                bq[j] = l0_pre ? l0w[j] : (k < in_dim ? w[k] : 0.f);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -498,18 +469,18 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             f32x4 acc;
             if (deep) {
                 if (l == 1) {
-                    acc = mfma_fwd_set<HT, NT>(Hp, HS, lane, fr, sBias[l * H + o], sScr);
-                    load_dgrad_frags<HT, NT>(P + offW(2), wave * 16, lane, fr);  // first backward phase, two phases early
+                    acc = mfma_rows_x_lines<HT>(Hp, HS, lane, fr, sBias[l * H + o], sScr);
+                    load_dgrad_frags<HT>(P + offW(2), wave * 16, lane, fr);  // first backward phase, two phases early
                 } else {
-                    acc = mfma_fwd_set<HT, NT>(Hp, HS, lane, fr2, sBias[l * H + o], sScr);
-                    load_dgrad_frags<HT, NT>(P + offW(1), wave * 16, lane, fr2); // second backward phase
+                    acc = mfma_rows_x_lines<HT>(Hp, HS, lane, fr2, sBias[l * H + o], sScr);
+                    load_dgrad_frags<HT>(P + offW(1), wave * 16, lane, fr2); // second backward phase
                 }
             } else {
-            if (nt != wave) load_fwd_set<HT, NT>(P + offW(l), nt * 16, lane, fr);
-            acc = mfma_fwd_set<HT, NT>(Hp, HS, lane, fr, sBias[l * H + o], sScr);
+            if (nt != wave) load_fwd_lines_buf<HT>(P + offW(l), nt * 16, lane, fr);
+            acc = mfma_rows_x_lines<HT>(Hp, HS, lane, fr, sBias[l * H + o], sScr);
             if (nt + kNW >= HT) {                           // last tile of this wave in this layer
-                if (l + 1 < depth) load_fwd_set<HT, NT>(P + offW(l + 1), wave * 16, lane, fr);
-                else load_dgrad_frags<HT, NT>(P + offW(l), wave * 16, lane, fr);   // first backward phase
+                if (l + 1 < depth) load_fwd_lines_buf<HT>(P + offW(l + 1), wave * 16, lane, fr);
+                else load_dgrad_frags<HT>(P + offW(l), wave * 16, lane, fr);   // first backward phase
             }
             }
 #pragma unroll
@@ -539,7 +510,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     //      the backward pass waits for.  The block's loss partials and the critic's values leave at the end of the body.
     if (wave == 0) {
         if constexpr (TABLES) asm volatile("; ppoaf_rowtile_head_rows_begin");
-        ppo_head_rows<NT>(u, which, out_dim, P + nd.log_std_off, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
+        ppo_head_rows(u, which, out_dim, P + nd.log_std_off, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
         if constexpr (TABLES) asm volatile("; ppoaf_rowtile_head_rows_end");
         PPOAF_STAMP_W(0, 0);
     }
@@ -591,9 +562,9 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             if (deep) {
                 acc = l == 2 ? mfma_rows_x_frags<HT>(Dc, HS, lane, fr, 0.f) : mfma_rows_x_frags<HT>(Dc, HS, lane, fr2, 0.f);
             } else {
-            if (nt != wave) load_dgrad_frags<HT, NT>(P + offW(l), nt * 16, lane, fr);
+            if (nt != wave) load_dgrad_frags<HT>(P + offW(l), nt * 16, lane, fr);
             acc = mfma_rows_x_frags<HT>(Dc, HS, lane, fr, 0.f);
-            if (nt + kNW >= HT && l - 1 >= 1) load_dgrad_frags<HT, NT>(P + offW(l - 1), wave * 16, lane, fr);
+            if (nt + kNW >= HT && l - 1 >= 1) load_dgrad_frags<HT>(P + offW(l - 1), wave * 16, lane, fr);
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

@@ -93,31 +93,9 @@ __device__ __forceinline__ void ppo_update_wide_critic_body(const UpdateDev& u, 
     }
     if (tid == 64) {                                        // a lane of wave 1: the value normaliser of this mini-batch
         const int slot = (int)(mb & 1);
-        float m = u.vn_mean[slot], v = u.vn_var[slot];
-        double cnt = u.vn_count[slot];
-        if (u.normalize_values) {
-            // Chan merge of the per-rank records of this mini-batch (rank 0 first), then the reference's integrate
-            // (utils/stats.py:73-94) -- the arithmetic of the other body, expression for expression
-            double vn_n = 0.0, vn_bm = 0.0, vn_M2 = 0.0;
-            for (int r = 0; r < u.n_ranks; ++r) {
-                const double* rec = u.vn_records + (mb * u.n_ranks + r) * 3;
-                const double nb = rec[0], mean = rec[1], m2 = rec[2];
-                if (nb <= 0.0) continue;
-                const double d = mean - vn_bm, nn = vn_n + nb;
-                vn_bm += d * (nb / nn);
-                vn_M2 += m2 + d * d * vn_n * nb / nn;
-                vn_n = nn;
-            }
-            const double n = vn_n, bm = vn_bm, M2 = vn_M2;
-            if (n > 0.0) {
-                const float batch_mean = (float)bm, batch_var = (float)(M2 / n);
-                const float delta = batch_mean - m;
-                const double new_count = cnt + n;
-                const float new_mean = (float)((double)m + (double)delta * (n / new_count));
-                const double m_2 = (double)v * cnt + (double)batch_var * n + (double)(delta * delta) * cnt * n / (cnt + n);
-                m = new_mean; v = (float)(m_2 / (cnt + n)); cnt = new_count;
-            }
-        }
+        float m, v;
+        double cnt;
+        minibatch_vn_state(u, mb, m, v, cnt);
         sMisc[2] = m; sMisc[3] = v;
         if (g == 0) { u.vn_mean[slot ^ 1] = m; u.vn_var[slot ^ 1] = v; u.vn_count[slot ^ 1] = cnt; }
     }
@@ -223,7 +201,7 @@ __device__ __forceinline__ void ppo_update_wide_critic_body(const UpdateDev& u, 
 
     // ---- value loss terms of this workgroup's rows: d loss / d out -> sDOut, the rows' terms parked in sActF
     if (wave == 0)
-        ppo_head_rows<false>(u, which, 1, P, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
+        ppo_head_rows(u, which, 1, P, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
     __syncthreads();
 
     // ---- output layer backward: dz_last = dOut . W_out * act'(Hlast) -> X2 (16 rows x 32 lane groups of 16 adjacent
