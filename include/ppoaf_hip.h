@@ -397,7 +397,9 @@ typedef struct {
     /* split-wgrad chain (NULL: weight-gradient slabs + ppoaf_ppo_update_reduce).  With a workspace of
      * ppoaf_ppo_update_split_workspace_bytes() bytes (256-byte aligned) fwd_bwd computes no hidden-layer weight gradient:
      * every workgroup publishes its 16 rows of the inputs, hidden activations and dLoss/dz of the mini-batch there, and
-     * ppoaf_ppo_update_wgrad forms the complete gradients from those panels (then ppoaf_ppo_update_adam, compute_norms 3). */
+     * ppoaf_ppo_update_wgrad forms the complete gradients from those panels (then ppoaf_ppo_update_adam, compute_norms 3).
+     * Per network: hidden activations and dLoss/dz [depth][Bp][hidden], the output layer's partials and the gathered input
+     * rows [Bp][64 | 128] (Bp = B rounded up to 64; 128: a wide pair's network with more than 64 inputs, PPOAF_SPLIT_WIDE_INPUTS). */
     void* split_workspace; int64_t split_workspace_bytes;
     /* 0: fwd_bwd's workgroups use every XCD (actor on 0-3, critic on 4-7; default).  1 / 2: they sit on XCDs 0-3 / 4-7 only
      * (actor on the half's first two XCDs, critic on the other two; the launch is twice as wide and the workgroups
@@ -405,14 +407,23 @@ typedef struct {
      * runs on a second stream, each keeps its weights and panels in its own four L2s -- C3: +2 % env-steps/s; alone the
      * confinement costs 1 % (C2).  Placement only changes speed. */
     int32_t xcd_half;
-    /* ABI 6.  1 (split-wgrad chain only; ignored otherwise): the 16-row tiles of a 256-wide network of depth 2 .. 4 run on
+    /* ABI 6.  Options of the split-wgrad chain, a bit set (the field keeps the name of its first option; 0: none).
+     * PPOAF_SPLIT_ROW_PAIRS (1; with split_workspace only, ignored otherwise): the 16-row tiles of a 256-wide network of depth 2 .. 4 run on
      * PAIRS of workgroups (a 32-, 64- or 128-wide actor beside such a critic keeps one workgroup per tile; a 256-wide actor
      * beside it must be of depth 2 .. 4 itself, else neither network runs in pairs) that split every hidden layer pass by output columns and exchange the halves through tagged
      * records behind the panels of split_workspace (csrc/ppo_update_rowpair.hpp) -- ppoaf_ppo_update_split_workspace_bytes()
      * then includes the record region.  Results are BITWISE those of row_pairs = 0.  The tag is the mini-batch index + 1:
      * the caller zeroes split_workspace before the first launch and whenever mini-batch indices restart (every epoch).
      * The region's first 32-bit word (byte offset ppoaf_ppo_update_row_pairs_error_offset()) is non-zero after a launch in
-     * which a partner did not answer within 2 s; that launch's results are invalid. */
+     * which a partner did not answer within 2 s; that launch's results are invalid.
+     * PPOAF_SPLIT_WIDE_INPUTS (2; added within ABI 7, read by every entry point, ppoaf_ppo_update_check included): an opt-in
+     * for the wide pair (actor 256, critic 512), which runs the split-wgrad chain only.  Without it every check, message and
+     * workspace size is what it was (in_dim <= 64).  With it the pair takes in_dim <= 128 per network: the layer-0 panel of
+     * a network with 64 < in_dim <= 128 has a row stride of 128 floats instead of 64 (ppoaf_ppo_update_split_workspace_bytes()
+     * counts it); a network with in_dim <= 64 keeps the stride of 64, and its results are bitwise those without the bit.
+     * Every other pair ignores the bit: with a split workspace it keeps in_dim <= 64 (wider inputs run its slab chain). */
+#define PPOAF_SPLIT_ROW_PAIRS   1
+#define PPOAF_SPLIT_WIDE_INPUTS 2
     int32_t row_pairs;
     /* the slice table of PPOAF_HEAD_MULTI_CATEGORICAL: classes per action dimension, in order, summing to actor.out_dim.
      * Read only for that head kind (appended: every field above keeps its offset). */

@@ -70,6 +70,10 @@ class PpoUpdateArgs(C.Structure):
                 ("n_action_slices", C.c_int32), ("action_slices", C.c_int32 * 8)]
 
 
+# ppoaf_ppo_update_args_t.row_pairs is a bit set (include/ppoaf_hip.h: PPOAF_SPLIT_ROW_PAIRS, PPOAF_SPLIT_WIDE_INPUTS)
+SPLIT_ROW_PAIRS = 1
+SPLIT_WIDE_INPUTS = 2
+
 ABI_VERSION = 7
 
 

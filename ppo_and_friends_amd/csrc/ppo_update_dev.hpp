@@ -85,9 +85,12 @@ struct WsDev {
     float* hbuf[2];                       // [depth][Bp][H]   hidden activations of the mini-batch
     float* dbuf[2];                       // [depth][Bp][H]   dLoss / dz
     float* outpart[2];                    // [ceil(B/16)][seg] output-layer (+ log_std) gradient partials per row block
-    float* xbuf[2];                       // [Bp][64]         the mini-batch's gathered input rows, zero padded (layer-0 wgrad)
+    float* xbuf[2];                       // [Bp][xld]        the mini-batch's gathered input rows, zero padded (layer-0 wgrad)
     int W;                                // workers per network (persistent kernel)
-    int xcc[2];                           // XCD of the actor / critic workers (persistent kernel)
+    // row stride of xbuf per network (split_xld): 64, or 128 for a wide pair's network with 64 < in_dim <= 128
+    // (PPOAF_SPLIT_WIDE_INPUTS).  Only the wide pair's kernels read it; every other kernel's stride is the constant 64.
+    // (in the place of the persistent kernel's XCD numbers, which nothing read: the argument block keeps its layout)
+    int xld[2];
     int Bp;                               // B rounded up to 64
 };
 
@@ -133,7 +136,15 @@ inline int split_wgrad_jobs(const NetDev& n) {
 inline int split_wgrad_per_xcd(const UpdateDev& u) { return (split_wgrad_jobs(u.net[0]) + split_wgrad_jobs(u.net[1]) + 7) / 8; }
 inline int split_wgrad_blocks(const UpdateDev& u) { return 8 * split_wgrad_per_xcd(u); }      // some run no job (partials 0)
 
-// workspace layout: per network hbuf, dbuf ([depth][Bp][H] each), outpart ([ceil(B/16)][seg]) and xbuf ([Bp][64])
+// args->row_pairs is a bit set (ppoaf_hip.h): the row pairs of 256-wide networks, the wide pair's 65 .. 128 inputs
+inline bool args_row_pairs(const ppoaf_ppo_update_args_t* a) { return (a->row_pairs & PPOAF_SPLIT_ROW_PAIRS) != 0; }
+inline bool args_wide_inputs(const ppoaf_ppo_update_args_t* a) { return (a->row_pairs & PPOAF_SPLIT_WIDE_INPUTS) != 0; }
+
+// row stride of a network's layer-0 panel: the host admits in_dim > 64 for a wide pair with PPOAF_SPLIT_WIDE_INPUTS only
+// (update_shapes, make_update_dev), so every other pair's panels are [Bp][64] as they always were
+inline int split_xld(const NetDev& n) { return n.in_dim <= 64 ? 64 : 128; }
+
+// workspace layout: per network hbuf, dbuf ([depth][Bp][H] each), outpart ([ceil(B/16)][seg]) and xbuf ([Bp][64 | 128])
 inline size_t ws_layout(const UpdateDev& u, WsDev* ws, char* base) {
     const long Bp = (u.B + 63) & ~63L;
     size_t off = 0;
@@ -142,12 +153,13 @@ inline size_t ws_layout(const UpdateDev& u, WsDev* ws, char* base) {
         const NetDev& n = u.net[w];
         const size_t plane = (size_t)n.depth * Bp * n.H;
         const size_t oh = take(plane), od = take(plane), oo = take((size_t)((u.B + 15) / 16) * ws_seg_len(n));
-        const size_t ox = take((size_t)Bp * 64);
+        const size_t ox = take((size_t)Bp * split_xld(n));
         if (ws) {
             ws->hbuf[w] = reinterpret_cast<float*>(base + oh);
             ws->dbuf[w] = reinterpret_cast<float*>(base + od);
             ws->outpart[w] = reinterpret_cast<float*>(base + oo);
             ws->xbuf[w] = reinterpret_cast<float*>(base + ox);
+            ws->xld[w] = split_xld(n);
         }
     }
     if (ws) ws->Bp = (int)Bp;

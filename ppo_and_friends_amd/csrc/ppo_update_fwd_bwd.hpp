@@ -25,8 +25,10 @@ __global__ __launch_bounds__(kThreadsU) void ppo_update_fwd_bwd_kernel(UpdateDev
         g = ((b >> 3) << 1) | (x & 1);
     }
     if (g >= u.n_wg) return;                               // uniform per workgroup, before any barrier
-    if (which == 0) ppo_update_fwd_bwd_body<HTA, SPLIT>(u, 0, g);
-    else ppo_update_fwd_bwd_body<HTC, SPLIT>(u, 1, g);
+    // (a wide pair's kernel alone reads the layer-0 panel's row stride from its arguments: u.sp.xld, PPOAF_SPLIT_WIDE_INPUTS)
+    constexpr bool XLD = SPLIT && HTC > 16;
+    if (which == 0) ppo_update_fwd_bwd_body<HTA, SPLIT, XLD>(u, 0, g);
+    else ppo_update_fwd_bwd_body<HTC, SPLIT, XLD>(u, 1, g);
 }
 
 // args->row_pairs (split-wgrad chain): a 256-wide network's row tiles on pairs of workgroups (ppo_update_rowpair.hpp); the
@@ -112,7 +114,7 @@ struct FwdBwdLaunch {
 template <int HA, int HC>
 inline int fwd_bwd_launch_pair(const FwdBwdLaunch& L) {
     const UpdateDev& u = L.u;
-    if (u.split && L.args->row_pairs && pairs_run(u.net[0], u.net[1])) {
+    if (u.split && args_row_pairs(L.args) && pairs_run(u.net[0], u.net[1])) {
         PairDev pd;
         pair_region_layout(u, &pd, reinterpret_cast<char*>(L.args->split_workspace) + pair_region_offset(u));
         return launch_fwd_bwd_pairs_of<HA, HC>(u, pd, L.lds, L.s, L.e0, L.e1);

@@ -48,7 +48,7 @@ __device__ __forceinline__ int rowtile_request_args(const UpdateDev& u, int b) {
     asm("" : "+s"(b)
         : "s"(cur), "s"(u.entropy_weight), "s"(u.kl_loss_weight), "s"(u.huber_delta), "s"(u.min_std), "s"(u.loss_partials),
           "s"(u.sp.hbuf[0]), "s"(u.sp.hbuf[1]), "s"(u.sp.dbuf[0]), "s"(u.sp.dbuf[1]), "s"(u.sp.outpart[0]), "s"(u.sp.outpart[1]),
-          "s"(u.sp.xbuf[0]), "s"(u.sp.xbuf[1]), "s"(u.sp.W), "s"(u.sp.xcc[0]), "s"(u.sp.xcc[1]), "s"(u.sp.Bp), "s"(u.n_slices),
+          "s"(u.sp.xbuf[0]), "s"(u.sp.xbuf[1]), "s"(u.sp.W), "s"(u.sp.xld[0]), "s"(u.sp.xld[1]), "s"(u.sp.Bp), "s"(u.n_slices),
           "s"(u.slices[0]), "s"(u.slices[1]), "s"(u.slices[2]), "s"(u.slices[3]), "s"(u.slices[4]), "s"(u.slices[5]),
           "s"(u.slices[6]), "s"(u.slices[7]));
     return b;
@@ -83,7 +83,9 @@ template <int CP> __device__ __forceinline__ void lds_write_adjacent(float* p, c
 // the hidden sets requested" and "do a row's scalars follow the sets as dependent loads" left the compiler several
 // histories to reconcile at every later wait of the prologue, and its safe answer to that is vmcnt(0): each of those waits
 // then waited for the sets as well.  Every other case runs the body as it was (TABLES = false: both decided at run time).
-template <int HT, bool SPLIT, bool TABLES>
+// XLD (the wide pair's kernel only, ppo_update_fwd_bwd.hpp): the SPLIT publish of the input rows takes the panel's row stride
+// from u.sp.xld[which] (64 | 128, PPOAF_SPLIT_WIDE_INPUTS).  Every other kernel keeps the constant and the loop written for it.
+template <int HT, bool SPLIT, bool TABLES, bool XLD = false>
 __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, const int which, const int g) {
     constexpr int H = 16 * HT, HS = H + 4;                 // which: 0 actor, 1 critic; g: 16-row block
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -427,7 +429,14 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     if (!deep && depth > 1 && has_tile) load_fwd_lines_buf<HT>(P + offW(1), wave * 16, lane, fr);
     __syncthreads();
     PPOAF_STAMP(2);
-    if (SPLIT) {            // the block's input rows, zero padded to 64 columns: the layer-0 wgrad's K-panel
+    if constexpr (SPLIT && XLD) {      // ... zero padded to the panel's stride, 64 or 128 columns (uniform per network)
+        const int xld = u.sp.xld[which], sh = xld == 64 ? 6 : 7;
+        float* xb = u.sp.xbuf[which] + (long)g * kRows * xld;
+        for (int i = tid; i < kRows * xld; i += kThreadsU) {
+            const int r = i >> sh, c = i & (xld - 1);
+            xb[i] = c < 16 * NT0 ? sX[r * INP + c] : 0.f;
+        }
+    } else if (SPLIT) {     // the block's input rows, zero padded to 64 columns: the layer-0 wgrad's K-panel
         float* xb = u.sp.xbuf[which] + (long)g * kRows * 64;
         for (int i = tid; i < kRows * 64; i += kThreadsU) {
             const int r = i >> 6, c = i & 63;
@@ -663,15 +672,15 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     PPOAF_STAMP(9);
 }
 
-template <int HT, bool SPLIT = false>
+template <int HT, bool SPLIT = false, bool XLD = false>
 __device__ __forceinline__ void ppo_update_fwd_bwd_body(const UpdateDev& u, const int which, const int g) {
     if constexpr (HT <= kNW) {
         if (u.net[which].depth == 3 && u.pregathered && !u.row_map) {        // uniform
-            ppo_update_fwd_bwd_body_as<HT, SPLIT, true>(u, which, g);
+            ppo_update_fwd_bwd_body_as<HT, SPLIT, true, XLD>(u, which, g);
             return;
         }
     }
-    ppo_update_fwd_bwd_body_as<HT, SPLIT, false>(u, which, g);
+    ppo_update_fwd_bwd_body_as<HT, SPLIT, false, XLD>(u, which, g);
 }
 
 // dynamic LDS the body needs for one network

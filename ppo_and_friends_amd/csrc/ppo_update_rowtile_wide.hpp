@@ -130,10 +130,11 @@ __device__ __forceinline__ void ppo_update_wide_critic_body(const UpdateDev& u, 
     };
     if (depth > 1) request_fwd(1, 0, fr[0]);
     __syncthreads();
-    {           // the block's input rows, zero padded to 64 columns: the layer-0 wgrad's K-panel
-        float* xb = u.sp.xbuf[which] + (long)g * kRows * 64;
-        for (int i = tid; i < kRows * 64; i += kThreadsU) {
-            const int r = i >> 6, c = i & 63;
+    {           // the block's input rows, zero padded to the panel's stride (64 | 128 columns): the layer-0 wgrad's K-panel
+        const int xld = u.sp.xld[which], sh = xld == 64 ? 6 : 7;
+        float* xb = u.sp.xbuf[which] + (long)g * kRows * xld;
+        for (int i = tid; i < kRows * xld; i += kThreadsU) {
+            const int r = i >> sh, c = i & (xld - 1);
             xb[i] = c < 16 * NT0 ? sX[r * INP + c] : 0.f;
         }
     }
@@ -290,7 +291,7 @@ __device__ __forceinline__ void ppo_update_wide_critic_body(const UpdateDev& u, 
 
 // the critic's tiles of ppo_update_fwd_bwd_kernel<16, 32, true> (ppo_update_fwd_bwd.hpp) run the body above
 template <>
-__device__ __forceinline__ void ppo_update_fwd_bwd_body<kWideHT, true>(const UpdateDev& u, const int which, const int g) {
+__device__ __forceinline__ void ppo_update_fwd_bwd_body<kWideHT, true, true>(const UpdateDev& u, const int which, const int g) {
     (void)which;                                          // (the kernel hands a 32-tile network to its critic branch only)
     ppo_update_wide_critic_body(u, g);
 }

@@ -21,7 +21,9 @@ namespace ppoaf {
 // fwd_bwd's dependent chain.
 // ------------------------------------------------------------------------------------------------------------
 // MAXC = chunks of 16 rows a wave may own (B <= 512: 32 chunks over 4 waves)
-template <int H>
+// XLD (the wide pair's launch only): the layer-0 panel's row stride is the network's u.sp.xld (64 | 128: PPOAF_SPLIT_WIDE_INPUTS);
+// every other pair's launch keeps the constant.
+template <int H, bool XLD>
 __device__ __forceinline__ double split_wgrad_job(const UpdateDev& u, const int which, const int job, float* sFold /* wgrad_tile.hpp */) {
     constexpr int MAXC = 8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -38,7 +40,7 @@ __device__ __forceinline__ double split_wgrad_job(const UpdateDev& u, const int 
         // buffer loads: resource = the layer's panel, scalar offset = chunk + row quad, vector offset = the lane's constant
         // byte offset.  Rows of the last chunk beyond B are dead rows of their tile: their dz is zero and their activations
         // finite, exactly as the slab form sums them.
-        const long ldx = sj.l >= 1 ? H : 64;                  // row stride of the input panel (layer 0: the gathered input rows)
+        const long ldx = sj.l >= 1 ? H : (XLD ? u.sp.xld[which] : 64);       // row stride of the input panel (layer 0: the gathered input rows)
         const __amdgpu_buffer_rsrc_t rd = split_panel_d<H>(u, which, sj.l), rx = split_panel_x<H>(u, which, sj.l);
         const unsigned dl = 4u * (unsigned)((lane >> 4) * H + ot * 16 + (lane & 15));
         const unsigned xl = 4u * (unsigned)((lane >> 4) * (int)ldx + itile * 16 + (lane & 15));
@@ -100,8 +102,9 @@ __global__ __launch_bounds__(kWgradThreads) void ppo_update_wgrad_kernel(UpdateD
     if (b == 8 * per_xcd) { ppo_update_bookkeeping_split(u); return; }           // uniform per workgroup
     const int job = (b & 7) * per_xcd + (b >> 3);             // XCD b % 8 works on one run of the layer-major job list
     double q = 0.0;
-    if (job < jobs_a) q = split_wgrad_job<HA>(u, 0, job, s_fold);
-    else if (job < jobs_a + jobs_c) q = split_wgrad_job<HC>(u, 1, job - jobs_a, s_fold);
+    constexpr bool XLD = HC > 256;                            // a wide pair (PPOAF_WIDTH_PAIRS_WIDE)
+    if (job < jobs_a) q = split_wgrad_job<HA, XLD>(u, 0, job, s_fold);
+    else if (job < jobs_a + jobs_c) q = split_wgrad_job<HC, XLD>(u, 1, job - jobs_a, s_fold);
     const bool actor = job < jobs_a;
     q = block_sum(q, s_red);
     if (threadIdx.x == 0) {
@@ -128,11 +131,12 @@ extern "C" int ppoaf_ppo_update_split_workspace_bytes(const ppoaf_ppo_update_arg
     UpdateDev u;
     int rc = make_update_dev(&a, u);
     if (rc) return rc;
-    PPOAF_REQUIRE(u.net[0].in_dim <= 64 && u.net[1].in_dim <= 64 && u.B <= 512,
-                  "ppo_update_split_workspace_bytes: the split-wgrad chain covers in_dim <= 64 and B <= 512 (got %d / %d, %ld)",
-                  u.net[0].in_dim, u.net[1].in_dim, u.B);
+    if (!(args_wide_inputs(&a) && width_pair_is_wide(u.net[0].H, u.net[1].H)))      // (else: update_shapes' in_dim <= 128, B <= 512)
+        PPOAF_REQUIRE(u.net[0].in_dim <= 64 && u.net[1].in_dim <= 64 && u.B <= 512,
+                      "ppo_update_split_workspace_bytes: the split-wgrad chain covers in_dim <= 64 and B <= 512 (got %d / %d, %ld)",
+                      u.net[0].in_dim, u.net[1].in_dim, u.B);
     size_t need = ws_layout(u, nullptr, nullptr);
-    if (a.row_pairs) need = pair_region_offset(u) + pair_region_layout(u, nullptr, nullptr);
+    if (args_row_pairs(&a)) need = pair_region_offset(u) + pair_region_layout(u, nullptr, nullptr);
     *bytes_out = (int64_t)need;
     return PPOAF_OK;
 }
@@ -144,7 +148,7 @@ extern "C" int ppoaf_ppo_update_row_pairs_error_offset(const ppoaf_ppo_update_ar
     UpdateDev u;
     int rc = make_update_dev(&a, u);
     if (rc) return rc;
-    const bool pairs = a.row_pairs && pairs_run(u.net[0], u.net[1]);      // the condition of fwd_bwd's dispatch
+    const bool pairs = args_row_pairs(&a) && pairs_run(u.net[0], u.net[1]);      // the condition of fwd_bwd's dispatch
     *offset_out = pairs ? (int64_t)pair_region_offset(u) : -1;
     return PPOAF_OK;
 }

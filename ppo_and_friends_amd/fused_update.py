@@ -725,13 +725,25 @@ class FusedLstmUpdate(FusedEpoch):
 WIDTH_PAIRS = ((32, 32), (64, 64), (128, 128), (256, 256), (128, 256), (64, 128), (64, 256), (32, 256), (32, 64))
 # ... and the pairs with a 512-wide critic (PPOAF_WIDTH_PAIRS_WIDE; csrc/ppo_update_rowtile_wide.hpp), taken only for a policy
 # whose `fused_wide_critic` is true (PPO sets it under update_mode="fused"; "auto" keeps the torch-ROCm path for them): the
-# split-wgrad chain in its three-launch form, single rank, in_dim <= 64, batch sizes <= 512.
+# split-wgrad chain in its three-launch form, single rank, in_dim <= 64, batch sizes <= 512.  With the opt-in
+# `PPOPolicy.fused_wide_inputs` in_dim <= 128: the layer-0 panel of a network with more than 64 inputs takes a row stride of
+# 128 floats (the bit PPOAF_SPLIT_WIDE_INPUTS of ppoaf_ppo_update_args_t.row_pairs; csrc/ppo_update_dev.hpp: split_xld).
 WIDE_WIDTH_PAIRS = ((256, 512),)
 
 
 def wide_critic(pol):
     """The policy's 512-wide critic may run on the fused kernels (PPOPolicy.fused_wide_critic)."""
     return bool(getattr(pol, "fused_wide_critic", False))
+
+
+def wide_inputs(pol):
+    """The policy's wide pair may take 65 .. 128 inputs per network (PPOPolicy.fused_wide_inputs, set by hand)."""
+    return bool(getattr(pol, "fused_wide_inputs", False))
+
+
+def panel_stride(in_dim):
+    """Row stride (floats) of a network's layer-0 panel in the split workspace (csrc/ppo_update_dev.hpp: split_xld)."""
+    return 64 if in_dim <= 64 else 128
 
 
 class FusedPolicyUpdate(FusedEpoch):
@@ -763,8 +775,12 @@ class FusedPolicyUpdate(FusedEpoch):
             return "batch size < 2"
         if wide:
             pair = f"wide pair (actor {a.hidden}, critic {c.hidden})"
-            if max(a.in_dim, c.in_dim) > 64:
-                return f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 64 (the split-wgrad chain's panels cover in_dim <= 64)"
+            if max(a.in_dim, c.in_dim) > 64 and not wide_inputs(pol):
+                hint = "; PPOPolicy.fused_wide_inputs = True takes in_dim <= 128" if max(a.in_dim, c.in_dim) <= 128 else ""
+                return f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 64 (the split-wgrad chain's panels cover in_dim <= 64){hint}"
+            if max(a.in_dim, c.in_dim) > 128:
+                return (f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 128 (with fused_wide_inputs the split-wgrad chain's panels "
+                        "cover in_dim <= 128)")
             if batch_size > 512:
                 return f"{pair}: batch size {batch_size} > 512 (the split-wgrad chain covers batch sizes <= 512)"
             if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
@@ -775,6 +791,7 @@ class FusedPolicyUpdate(FusedEpoch):
         q = _lib.PpoUpdateArgs()
         q.actor, q.critic, q.bucket_total = a, c, a.size + c.size
         q.head_kind, q.B, q.batch_stride = head, batch_size, batch_size
+        q.row_pairs = _lib.SPLIT_WIDE_INPUTS if wide and wide_inputs(pol) else 0
         set_action_slices(q, action_head(pol)[1])
         if _lib.load().ppoaf_ppo_update_check(C.byref(q)) != 0:
             return _lib.load().ppoaf_last_error().decode("utf-8", "replace")
@@ -799,6 +816,7 @@ class FusedPolicyUpdate(FusedEpoch):
         self.actor_desc, _ = _describe(pol.actor, pol.policy_params, self.head == K.HEAD_GAUSSIAN)
         self.critic_desc, _ = _describe(pol.critic, pol.policy_params, False, wide_critic(pol))
         self.wide = (self.actor_desc.hidden, self.critic_desc.hidden) in WIDE_WIDTH_PAIRS
+        self.wide_inputs = self.wide and wide_inputs(pol)      # (read here, once: the args and the workspace are built from it)
         self.n_wg = (self.B + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
         total = pol.policy_params.numel()
         # (a wide pair has no slab form: a placeholder for the args' pointer instead of n_wg x 0.75 M floats nothing reads)
@@ -863,6 +881,18 @@ class FusedPolicyUpdate(FusedEpoch):
             if self.xchg_sp is None and mode != "1" and max(self.actor_desc.hidden, self.critic_desc.hidden) < 256:   # (no fused-tail exchange)
                 return False, "N > 1, no exchange for the wgrad launch and no 256-wide network: the slab reduce launch carries K17"
         return True, ""
+
+    def description(self):
+        """One line for `verbose`: the chain a mini-batch runs and, on the split-wgrad chain, the row stride of each
+        network's layer-0 panel."""
+        a, c = self.actor_desc, self.critic_desc
+        line = f"K12 for (actor {a.hidden}, critic {c.hidden}), in_dim {a.in_dim} / {c.in_dim}: "
+        if not self.split:
+            return line + f"slab chain ({self.split_reason})"
+        tail = self.tail_reason()
+        line += "split-wgrad chain, " + ("fused tail" if tail == "" else f"wgrad and Adam launches ({tail})")
+        return line + (f"; layer-0 panel stride {panel_stride(a.in_dim)} (actor) / {panel_stride(c.in_dim)} (critic) floats"
+                       f"{', fused_wide_inputs' if self.wide_inputs else ''}")
 
     def gradient_only(self, args, timing_events=(None, None)):
         """fwd_bwd + the launch that completes the gradient bucket (wgrad / slab reduce) of ONE mini-batch, no optimiser step:
@@ -954,19 +984,20 @@ class FusedPolicyUpdate(FusedEpoch):
         _loss_args(self, a, B)
         a.xcd_half = getattr(self, "xcd_half", 0)        # 1 / 2: beside the ICM chain (ppo.py: _ppo_icm_epoch_overlapped)
         a.split_workspace, a.split_workspace_bytes = None, 0
-        a.row_pairs = 0
+        # (args.row_pairs is a bit set: the row pairs, and a wide pair's 65 .. 128 inputs -- never both, a wide pair runs no pairs)
+        a.row_pairs = wide_bit = _lib.SPLIT_WIDE_INPUTS if self.wide_inputs else 0
         if self.split:
-            a.row_pairs = int(self.pairs_reason() == "")
+            a.row_pairs = wide_bit | int(self.pairs_reason() == "")
             if self._split_space is None:            # sized once for the full batch size; a tail mini-batch needs less
                 need = C.c_int64(0)
-                a.row_pairs = int(self.row_pairs)    # (room for the pairs' records whether or not they stay switched on)
+                a.row_pairs = wide_bit | int(self.row_pairs)    # (room for the pairs' records whether or not they stay switched on)
                 _lib.check(self._lib.ppoaf_ppo_update_split_workspace_bytes(C.byref(a), C.byref(need)), "split_workspace_bytes")
                 self._split_space = torch.zeros(int(need.value), dtype=torch.uint8, device=pol.device)
                 off = C.c_int64(-1)
                 _lib.check(self._lib.ppoaf_ppo_update_row_pairs_error_offset(C.byref(a), C.byref(off)), "row_pairs_error_offset")
                 self._pair_region = int(off.value)   # -1: these shapes run no pairs
                 assert self._pair_region >= 0 or self.pairs_reason() != "", "the library runs no pairs for shapes pairs_reason() accepts"
-                a.row_pairs = int(self.pairs_reason() == "")
+                a.row_pairs = wide_bit | int(self.pairs_reason() == "")
                 blocks = int(self._lib.ppoaf_ppo_update_split_blocks(C.byref(a)))
                 if pol.policy_norm_scratch.numel() < 6 + 2 * blocks:      # one pair of norm partials per wgrad workgroup
                     pol.policy_norm_scratch = torch.zeros(6 + 2 * blocks, dtype=torch.float64, device=pol.device)
@@ -1037,7 +1068,7 @@ class FusedPolicyUpdate(FusedEpoch):
         ref = C.byref(args)
         single = not self.multi
         rc = lib.ppoaf_ppo_update_fwd_bwd(ref, st)
-        if args.row_pairs:
+        if args.row_pairs & _lib.SPLIT_ROW_PAIRS:
             self._pairs_used = True
             FusedPolicyUpdate.pair_launches += 1
         if rc == 0 and args.split_workspace:

@@ -100,6 +100,11 @@ class PPOPolicy:
     # kernels, update epoch and rollout-time reward.  Set on the policy before its first rollout: it is read when the ICM
     # updater and the reward state are first built.  False: the torch path, with today's messages.
     fused_shared_icm = False
+    # Opt-in: a wide pair (256-wide actor, 512-wide critic; `fused_wide_critic`) with 65 .. 128 inputs to either network on
+    # K6+K7 and K12: the layer-0 panel of such a network takes a row stride of 128 instead of 64 (the library's
+    # PPOAF_SPLIT_WIDE_INPUTS).  Set by hand, on the class or on the policy, before the first rollout -- no update_mode sets it.  False:
+    # the torch path for those shapes, with today's messages; at in_dim <= 64 the flag changes nothing, bitwise.
+    fused_wide_inputs = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -699,7 +704,8 @@ class PPOPolicy:
         if self.using_lstm:
             return "LSTM policies are not K19's: K21 or forward_logits (see lstm_step_unsupported_reason)"
         # (asked once per evaluation step: the answer is kept for as long as what it depends on stays)
-        key = (self.policy_params.data_ptr(), bool(self.fused_action_heads), bool(self.fused_wide_critic))
+        key = (self.policy_params.data_ptr(), bool(self.fused_action_heads), bool(self.fused_wide_critic),
+               bool(self.fused_wide_inputs))
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
             self._infer_reason = (key, self.fused_step_unsupported_reason())
         return self._infer_reason[1]

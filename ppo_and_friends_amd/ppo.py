@@ -1501,6 +1501,8 @@ class PPO:
                 self._fused[key] = None
             else:
                 self._fused[key] = driver(self, policy_id)
+                if self.verbose and getattr(self._fused[key], "wide", False):
+                    rank_print(f"policy {policy_id}: {self._fused[key].description()}")
         return self._fused[key]
 
     def _say_lstm_update_path(self, policy_id, path):

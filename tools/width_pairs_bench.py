@@ -14,6 +14,13 @@ synchronisations; seconds are printed as median and spread (min .. max) per leg,
 --widths A C times another pair instead, at `bipedal_walker_hardcore`'s dimensions (24 observations, Box(4), depth 3): the
 policy under update_mode="fused" against the same policy under update_mode="torch", by the same protocol.  `--widths 256 512`
 is the wide pair (K12 ends in the wgrad and Adam launches there: profiles/wide_critic.txt).
+
+--obs-dim N (with --widths) times the pair at the RAM baselines' dimensions instead: N observations, Discrete(4), depth 3.
+--wide-inputs sets PPOPolicy.fused_wide_inputs, which a wide pair needs above 64 inputs, and --batch the mini-batch size:
+
+    python tools/width_pairs_bench.py --widths 256 512 --obs-dim 128 --wide-inputs --batch 128
+
+is `breakout_ram` / `mario_bros_ram` (128 RAM bytes, batch 128: 4096 mini-batches per epoch; profiles/wide_inputs.txt).
 """
 import argparse
 import json
@@ -31,12 +38,14 @@ LEGS = {"64x256_fused": ((64, 256), "fused"), "64x256_torch": ((64, 256), "torch
 BATCH = 256
 
 
-def make_ppo(widths, mode, E, T, seed=1, walker=False):
+def make_ppo(widths, mode, E, T, seed=1, walker=False, obs_dim=None):
     from ppo_and_friends_amd.ppo import PPO
     from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
     from ppo_and_friends_amd.spaces import Box, Discrete
     dev = torch.device("cuda", 0)
     O, space = (24, Box(-1.0, 1.0, (4,), np.float32)) if walker else (8, Discrete(4))
+    if obs_dim is not None:
+        O, space = obs_dim, Discrete(4)
     env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, dev, reward="ones", seed=1234)
     sp = Box(-np.inf, np.inf, (O,), np.float32)
     pargs = dict(actor_kw_args=dict(hidden_size=widths[0], hidden_depth=3), critic_kw_args=dict(hidden_size=widths[1], hidden_depth=3))
@@ -65,6 +74,7 @@ def rollout_and_epoch(ppo):
 
 
 def main():
+    global BATCH
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=128, help="env steps per rollout (E x T transitions)")
@@ -72,14 +82,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--widths", type=int, nargs=2, metavar=("ACTOR", "CRITIC"), default=None,
                     help="this pair, fused against torch, at bipedal_walker_hardcore's dimensions (default: the 64 / 256 legs)")
+    ap.add_argument("--obs-dim", type=int, default=None, help="with --widths: this many observations and Discrete(4) actions")
+    ap.add_argument("--wide-inputs", action="store_true", help="PPOPolicy.fused_wide_inputs = True (a wide pair above 64 inputs)")
+    ap.add_argument("--batch", type=int, default=BATCH, help="mini-batch size")
     args = ap.parse_args()
+    if args.obs_dim is not None and not args.widths:
+        ap.error("--obs-dim goes with --widths")
+    BATCH = args.batch
+    if args.wide_inputs:
+        from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
+        PPOPolicy.fused_wide_inputs = True
     legs, pair = LEGS, "64x256"
     if args.widths:
         pair = f"{args.widths[0]}x{args.widths[1]}"
         legs = {f"{pair}_{m}": (tuple(args.widths), m) for m in ("fused", "torch")}
     n = args.envs * args.steps
     result = {"transitions": n, "batch_size": BATCH, "minibatches_per_epoch": (n + BATCH - 1) // BATCH, "repeats": args.repeats}
-    ppos = {k: make_ppo(w, m, args.envs, args.steps, walker=bool(args.widths)) for k, (w, m) in legs.items()}
+    if args.obs_dim is not None:
+        result.update(obs_dim=args.obs_dim, wide_inputs=bool(args.wide_inputs))
+    ppos = {k: make_ppo(w, m, args.envs, args.steps, walker=bool(args.widths), obs_dim=args.obs_dim) for k, (w, m) in legs.items()}
     for k, ppo in ppos.items():                      # the path each leg takes, as the JSON line reports it
         pol = ppo.policies["p"]
         fused = ppo._fused_updater("p", BATCH)
@@ -110,6 +131,10 @@ def main():
         # the pair's reason to exist: the fused epoch's median below the fastest of the torch path's runs
         result[f"{pair}_fused_median_below_fastest_torch"] = bool(
             result[f"{pair}_fused_epoch_s"] < result[f"{pair}_torch_epoch_spread_s"][0])
+        # ... and leg against leg inside each alternation
+        for j, what in enumerate(("rollout", "epoch")):
+            result[f"{pair}_fused_{what}_faster_in_every_alternation"] = bool(
+                all(f[j] < t[j] for f, t in zip(times[f"{pair}_fused"], times[f"{pair}_torch"])))
     else:
         result["epoch_64x256_over_128x256"] = result["64x256_fused_epoch_s"] / result["128x256_fused_epoch_s"]
     print(json.dumps(result), flush=True)
