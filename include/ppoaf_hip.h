@@ -958,7 +958,7 @@ typedef struct {
 int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* args, ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
- * K23  the bookkeeping of one env step of a multi-policy rollout, one launch for all members
+ * K23  the bookkeeping of one env step of a rollout (PPO.rollout), one launch for all of its members
  * replaces, after env.step, per member: the reward / natural-reward rows of its agents,
  *          `reward * ext_reward_weight`, `+ intrinsic reward`, buffer.rewards[t], end_kind[t];
  *          and once: the ep_ts arithmetic of the episode ends                 ppo.py:1795-1983

@@ -1,5 +1,5 @@
-// K23: the per-step bookkeeping of a multi-policy rollout, one launch for all members.
-// Replaces, per env step and per member, the torch statements of PPO._rollout_multi_policy that follow env.step:
+// K23: the per-step bookkeeping of a rollout, one launch for all members (the policies of a multi-policy run, or a MAT
+// team alone).  Replaces, per env step and per member, the torch statements of PPO.rollout that follow env.step:
 // the gathers of the member's reward / natural-reward rows, `reward * ext_reward_weight`, `+ intrinsic`, the copies
 // into buffer.rewards[t] and the natural-reward row, `end_kind[t]`, and -- once -- the shared ep_ts arithmetic
 // (ppo.py:1795-1983 of the reference: terminated -> terminal end; ep_ts == max_ts_per_ep, truncated or the last step

@@ -559,7 +559,7 @@ def mat_policy_infer(args):
 
 
 # --------------------------------------------------------------------------
-# K23: the rows that follow env.step in a multi-policy rollout, all members in one launch
+# K23: the rows that follow env.step in PPO.rollout, all members in one launch
 # --------------------------------------------------------------------------
 def rollout_finish_rows(args):
     """ppoaf_rollout_finish_rows on a filled _lib.RolloutFinishArgs."""

@@ -165,13 +165,221 @@ class PermutationLoader:
             yield perm[o:o + self.batch_size]
 
 
+def _group(x, n, E, order):
+    """MAT: [n * E, .] agent-major rows -> [E, n, .], agents side by side in the slot order `order` (a device tensor)."""
+    return x.reshape((n, E) + tuple(x.shape[1:]))[order].transpose(0, 1).contiguous()
+
+
+def _ungroup(x, n, E, inverse):
+    """[E, n, .] in slot order -> [n * E, .] agent-major; inverse = argsort(order)."""
+    return x.transpose(0, 1)[inverse].reshape((n * E,) + tuple(x.shape[2:]))
+
+
+class _RolloutMember:
+    """
+    One policy's part of one rollout (PPO.rollout): the policy with its buffer and value normaliser, its agents in env
+    order (`agents`, their positions `index` among the env's A agents), how it steps (`grouped`: MAT rows [E, n, .] in
+    the policy's shuffled slot order; `fused`: K6+K7 / K16; `lstm_kernel`: K21; `blocks`: the block forms, which read the
+    agents' rows of the env's tensors where they lie and write the env's action tensors themselves) and its per-step
+    natural (`nat`) and intrinsic (`intr`) reward rows, [T, n * E].  `whole`: the member owns every agent of a tensor
+    env, so the env's tensors ARE its agent-major rows [n * E, .] -- no gather, no block table for a non-grouped
+    policy, and its actions are the env's.
+    """
+
+    def __init__(self, ppo, policy_id, agents, index, A, n_envs, T, whole):
+        pol = ppo.policies[policy_id]
+        pol.initialize_dataset()
+        pol.eval()
+        pol.initialize_episodes(n_envs, ppo.status_dict, ts_per_rollout=ppo.ts_per_rollout)
+        dev = ppo.device
+        self.ppo, self.id, self.pol, self.buf = ppo, policy_id, pol, pol.buffer
+        self.vn = ppo.value_normalizers[policy_id] if ppo.normalize_values else None
+        self.agents, self.index, self.n, self.A, self.E, self.whole = agents, index, len(index), A, n_envs, whole
+        self.idx = None if whole else torch.as_tensor(index, device=dev)
+        self.grouped = bool(pol.agent_grouping)
+        self.fused = ppo.update_mode != "torch" and dev.type == "cuda" and pol.fused_step_unsupported_reason() == ""
+        # K21: an LSTM policy's step in one launch (STEP), its answer in a second (CRITIC_NEXT or MASK)
+        self.lstm_kernel = pol.using_lstm and dev.type == "cuda" and pol.lstm_step_unsupported_reason() == ""
+        if self.grouped:
+            # MAT: rows are envs, agents side by side in the policy's (shuffled) slot order (ppo.py:1643-1644, 753-770)
+            pol.shuffle_agent_ids()
+            self.order, self.inverse = torch.as_tensor(pol.agent_slot_order(), device=dev), None
+        self.blocks = bool(ppo.step_row_blocks and self.fused and (self.grouped or not whole))
+        self.env_act = None
+        self.nat = ppo._scratch(f"nat_buf_{policy_id}_{T}_{self.n}_{n_envs}", T * self.n * n_envs, torch.float32).view(T, -1)
+        # per-step intrinsic rewards in the buffer's own layout (agents side by side when grouped)
+        self.intr = torch.zeros(T, self.n * n_envs, dtype=torch.float32, device=dev) if pol.enable_icm else None
+
+    def rows(self, x):
+        """The member's rows of an env quantity, agent-major: [n * E, .]."""
+        if self.whole:
+            return x
+        if isinstance(x, dict):
+            return torch.cat([x[a] for a in self.agents], 0)
+        return x.reshape((self.A, self.E) + tuple(x.shape[1:]))[self.idx].reshape((self.n * self.E,) + tuple(x.shape[1:]))
+
+    def row_blocks(self, x):
+        """The same rows where they lie: one [E, .] tensor per agent of the member."""
+        if isinstance(x, dict):
+            return [x[a] for a in self.agents]
+        per_agent = x.reshape((self.A, self.E) + tuple(x.shape[1:])).unbind(0)
+        return [per_agent[i] for i in self.index]
+
+    def group(self, x):
+        return _group(x, self.n, self.E, self.order)
+
+    def ungroup(self, x):
+        if self.inverse is None:
+            self.inverse = torch.argsort(self.order)
+        return _ungroup(x, self.n, self.E, self.inverse)
+
+    def agent_action_shape(self):
+        """One agent's action in one env, as the buffer keeps it."""
+        return tuple(self.buf.actions.shape[3 if self.grouped else 2:])
+
+    def act(self, t, obs, critic_obs, actions):
+        """
+        Step t of the policy on what the env handed over (with `recorded` raw actions, [T, rows, .] in the buffer's row
+        layout, every step logs the recorded one instead of sampling).  Returns the member's env actions, agent-major
+        [n * E, .] -- or None when a block form has written them: into the member's blocks of `actions` (the combined
+        [A, E, .] tensor), or for a dict env into `env_act`, one tensor per agent.
+        """
+        ppo, pol = self.ppo, self.pol
+        forced = None if self.recorded is None else self.recorded[t].contiguous()
+        if self.blocks:
+            why = ""
+            if isinstance(actions, dict):
+                if self.env_act is None:
+                    self.env_act = [torch.zeros((self.E,) + self.agent_action_shape(), dtype=self.buf.actions.dtype,
+                                                device=ppo.device) for _ in self.agents]
+            elif actions.dtype != self.buf.actions.dtype or tuple(actions.shape[2:]) != self.agent_action_shape():
+                why = "the env's action tensor has another dtype or shape"
+            else:
+                per_agent = actions.unbind(0)
+                self.env_act = [per_agent[i] for i in self.index]
+            if not why:
+                if self.grouped:
+                    tb = (self.row_blocks(critic_obs), None if pol.expanded_actor_space else self.row_blocks(obs), self.env_act)
+                else:
+                    tb = (self.row_blocks(obs), self.row_blocks(critic_obs), self.env_act)
+                why = pol.step_blocks_unsupported_reason(*tb)          # the tables are checked before every launch
+            if why:
+                self.blocks = False
+                if ppo.verbose:
+                    rank_print(f"rollout: policy {self.id} gathers its rows with torch operators ({why})")
+            else:
+                # K6+K7 / K16 with the buffer row in one launch; a MAT team in its slot order, without group() / ungroup()
+                a = pol.rollout_step(t, None, None, self.vn, forced_raw_action=forced, blocks=tb)
+                if pol.enable_icm:        # the ICM's view of the step: the critic's rows only where its actor sees them
+                    if self.grouped:      # agent-major, as ungroup() gives it
+                        a = actions.reshape((self.n * self.E,) + tuple(actions.shape[2:])) if self.whole else torch.cat(self.env_act, 0)
+                    self.step = (self.rows(obs), self.rows(critic_obs) if self.grouped and pol.expanded_actor_space else None, a)
+                return None
+        o, co = self.rows(obs).contiguous(), self.rows(critic_obs).contiguous()
+        if self.grouped:
+            g_obs, g_cobs = self.group(o), self.group(co)
+            a_obs = g_cobs if pol.expanded_actor_space else g_obs
+            if self.fused:
+                # K16: encoder + autoregressive decoder passes + sampling + values + the buffer row in one launch
+                g_a = pol.rollout_step(t, g_cobs, a_obs, self.vn, forced_raw_action=forced)
+            else:
+                raw, g_a, lp = pol.get_rollout_actions(a_obs, forced_raw_action=forced)
+                self.pending = (g_cobs, a_obs, raw, g_a, ppo.get_policy_values(self.id, g_cobs), lp)
+            a = self.ungroup(g_a)
+        elif self.fused:
+            # K6+K7: inference, sampling, log-probs, values and the buffer row in one launch
+            a = pol.rollout_step(t, o, co, self.vn, forced_raw_action=forced)
+        elif self.lstm_kernel:
+            a = pol.lstm_rollout_step(t, o, co, self.vn, forced_raw_action=forced)
+        else:
+            raw, a, lp = pol.get_rollout_actions(o, forced_raw_action=forced)
+            self.pending = (co, o, raw, a, ppo.get_policy_values(self.id, co), lp)
+        self.step = (o, co, a)
+        return a
+
+    def answer(self, t, reward, nat, nxt_obs, nxt_cobs, term_obs, finish_rows):
+        """
+        The env's answer to step t: the intrinsic reward (ppo.py:1719-1723 -> apply_intrinsic_rewards :1219-1288, on the
+        post-step observation) into `intr[t]` and, unless K23 writes them (finish_rows), the natural reward into `nat[t]`
+        and the reward row: `ext_reward_weight`, then the intrinsic reward, then the buffer's layout.
+        Kept for write(): the reward row and the next observations an ICM keeps.
+        """
+        ppo, pol = self.ppo, self.pol
+        nxt = intr = None
+        if pol.enable_icm:
+            prev_o, prev_co, act = self.step
+            if self.grouped:
+                n_o, n_co = self.rows(nxt_obs), self.rows(nxt_cobs) if pol.expanded_actor_space else None
+                intr = ppo._grouped_intrinsic(pol, prev_o, prev_co, n_o, n_co, act)
+                self.intr[t] = self.group(intr).reshape(-1)
+                nxt = self.group(n_co if pol.expanded_actor_space else self.rows(term_obs))
+            else:
+                self.intr[t] = intr = pol.get_intrinsic_reward(prev_o, self.rows(nxt_obs), act)
+                nxt = self.rows(term_obs)
+        if finish_rows:       # K23 writes the row: write_step copies it onto itself
+            self.answered = (None if self.fused else self.buf.rewards[t]), nxt
+            return
+        self.nat[t].copy_(self.rows(nat))
+        r = self.rows(reward)
+        if ppo.ext_reward_weight != 1.0 and isinstance(reward, dict):
+            r = r * ppo.ext_reward_weight
+        if intr is not None:
+            r = r + intr
+        self.answered = (self.group(r) if self.grouped else r), nxt
+
+    def write(self, t, terminated, critic_next):
+        """Row t of the buffer takes the answer.  critic_next: lstm_critic_next() follows for an LSTM policy."""
+        pol, (r, nxt) = self.pol, self.answered
+        if self.fused:
+            pol.finish_step(t, r, nxt)
+        elif self.lstm_kernel:
+            self.reward = r
+            if not critic_next:           # no critic step on the next observation: the zeroing alone
+                pol.lstm_finish_step(t, r, terminated)
+        else:
+            co, o, raw, a, v, lp = self.pending
+            self.buf.write_step(t, slice(0, self.buf.C), co, o, nxt, raw, a, v, lp, r)
+            pol._t = t + 1
+            if pol.using_lstm:
+                pol.store_hidden_states(t, terminated)
+
+    def lstm_critic_next(self, t, terminated, nxt_cobs, cut):
+        """The LSTM critic's step on the next observation, kept only where the device flag `cut` is set; its value goes
+        to boot_value[t]."""
+        pol, nxt_cobs = self.pol, self.rows(nxt_cobs)
+        if self.lstm_kernel:
+            # the flag stays on the device: the launch keeps the critic's stepped state only where it is set
+            pol.lstm_finish_step(t, self.reward, terminated, nxt_cobs.contiguous(), cut, self.vn)
+        else:
+            h_old = tuple(x.clone() for x in pol.critic.hidden_state)
+            v_next = self.ppo.get_policy_values(self.id, nxt_cobs)
+            pol.critic.hidden_state = tuple(torch.where(cut, n, o) for n, o in zip(pol.critic.hidden_state, h_old))
+            self.buf.boot_value[t].copy_(v_next)
+
+    def close(self, T, obs, critic_obs, may_end_early):
+        """The end of the rollout: bootstrap values, the dataset and the statistics.  Bootstrap values are V(next obs): for
+        ends before the last row the value logged at t + 1 (same critic, same normaliser state during a rollout); the last
+        row needs one more pass."""
+        ppo, pol = self.ppo, self.pol
+        last_cobs = self.rows(critic_obs).contiguous()
+        if self.lstm_kernel:
+            next_value = pol.lstm_last_value(T - 1, last_cobs, self.vn)      # (lands in boot_value[T - 1])
+        else:
+            next_value = ppo.get_policy_values(self.id, self.group(last_cobs) if self.grouped else last_cobs)
+        ppo._close_rollout_buffer(self.id, pol, next_value, self.intr, may_end_early, self.lstm_kernel)
+        pol.finalize_dataset()
+        ppo._publish_rollout_statistics(self.id, self.buf, self.nat, self.intr, self.E, T, self.rows(obs), self.grouped)
+
+
 class PPO:
 
-    # K23 writes the reward / natural-reward / end_kind rows of every member of a multi-policy rollout and advances ep_ts
-    # in one launch per env step; False keeps the torch operators (the two are bitwise equal), for comparison
+    # K23 writes the reward / natural-reward / end_kind rows of every member of a rollout and advances ep_ts in one launch
+    # per env step (multi-policy runs, and a MAT team alone on its block form); False keeps the torch operators (the two
+    # are bitwise equal), for comparison
     finish_rows = True
-    # K6+K7's block form for the feed-forward members of a multi-policy rollout (ppoaf_policy_step_blocks: observations
-    # read from the env's tensors through a row-block table, env actions written in place); False keeps the gathers
+    # the block forms of K6+K7 and K16 for the members that would gather or regroup their rows (ppoaf_policy_step_blocks,
+    # ppoaf_mat_policy_step_blocks: observations read from the env's tensors through a row-block table, env actions
+    # written in place); False keeps the gathers
     step_row_blocks = True
 
     def __init__(self, env_generator, policy_settings, policy_mapping_fn=None, device="cuda",
@@ -329,27 +537,32 @@ class PPO:
 
     def rollout(self):
         """
-        ppo.py:1534-2110 for a batched device environment and one policy.
-        Per step: actions / log-probs (actor + sampling kernel), values (critic,
-        denormalised), env.step, buffer row write, episode-end flags -- all
-        enqueued without a host read.  Episode-end cases (ppo.py:1795-1983):
-        terminated -> terminal end; ep_ts == max_ts_per_ep, truncated, or the
-        last step of the rollout -> bootstrapped end with the critic's value of
-        the next observation.
+        ppo.py:1534-2110 for a batched device environment and one policy or several (`policy_mapping_fn` partitions the
+        env's agents, ppo.py:329-345, 710-858).  Every policy is one member of the rollout (_RolloutMember): it acts on
+        its own agents' rows of what the env hands over and logs into its own rollout buffer; the env is stepped once
+        with the combined actions.  The env hands over either agent-major tensors [A*E, .] (all agents share shapes) or, as
+        the reference's multi-agent wrappers do, dicts keyed by agent id (agents of different policies may then differ in
+        observation / action space; the agents of ONE policy share them, as in the reference).  A member that owns every
+        agent takes the env's tensors as they are, so a member of a mixed run behaves as it does alone on an env
+        restricted to its agents.  Members are feed-forward PPOPolicy instances (independent or team-wise PPO) and
+        MATPolicy teams, each with or without an ICM; an LSTM policy runs as the only member.
+        Per step: actions / log-probs (actor + sampling kernel), values (critic, denormalised), env.step, buffer row
+        write, episode-end flags -- all enqueued without a host read.  Episode-end cases (ppo.py:1795-1983): terminated
+        -> terminal end; ep_ts == max_ts_per_ep, truncated, or the last step of the rollout -> bootstrapped end with the
+        critic's value of the next observation.  The agents of an env end together, so one `ep_ts` and one end table
+        serve all members, and an ICM member turns the dense end table on for the whole run.
+        `replay_raw_actions` (None, a [T, rows, .] device tensor in the only member's buffer layout, or a dict of them by
+        policy id) makes every step log the recorded raw action instead of sampling one.
+        Returns the policy's dataset, or {policy_id: dataset} for several policies.
         """
-        if len(self.policies) > 1:
-            return self._rollout_multi_policy()
         start = time.time()
-        policy_id = next(iter(self.policies))
-        pol = self.policies[policy_id]
-        pol.initialize_dataset()
-        pol.eval()
         env = self.env
         n_envs = env.get_batch_size()
         T = self.ts_per_rollout // n_envs
-        pol.initialize_episodes(n_envs, self.status_dict, ts_per_rollout=self.ts_per_rollout)
-        buf = pol.buffer
-        E = buf.C                      # rows per step: agents x envs, agent-major (ppo.py:710-795)
+        if len(self.policies) > 1:
+            for policy_id, pol in self.policies.items():
+                if pol.using_lstm:
+                    raise NotImplementedError(f"several policies in one run: LSTM policies are not supported (policy {policy_id})")
         # ppo.py:1580-1586: a hard reset per rollout unless soft_resets (then the env carries on, and
         # a filter stack counts the carried observation once more, ppo_env_wrappers.py:149-199)
         if self._obs is None or not self.soft_resets():
@@ -357,189 +570,125 @@ class PPO:
         else:
             soft = getattr(env, "soft_reset", None)
             obs, critic_obs = soft() if callable(soft) else self._obs
-        ep_ts = torch.zeros(E, dtype=torch.int32, device=self.device)
-        may_end_early = getattr(env, "term_table", True) is not None or self.max_ts_per_ep < T
-        fused_step = (self.update_mode != "torch" and self.device.type == "cuda"
-                      and pol.fused_step_unsupported_reason() == "")
-        # K21: an LSTM policy's step in one launch (STEP), its answer in a second (CRITIC_NEXT or MASK)
-        lstm_step = pol.using_lstm and self.device.type == "cuda" and pol.lstm_step_unsupported_reason() == ""
-        vn = self.value_normalizers[policy_id] if self.normalize_values else None
-        grouped = pol.agent_grouping
-        if grouped:
-            # MAT: rows are envs, agents side by side in the policy's (shuffled) slot order
-            # (ppo.py:1643-1644, 753-770): [A*E, .] agent-major env tensors -> [E, A, .]
-            pol.shuffle_agent_ids()
-            order = torch.as_tensor(pol.agent_slot_order(), device=self.device)
-            n_ag = order.numel()
-            group = lambda x: x.reshape((n_ag, n_envs) + tuple(x.shape[1:]))[order].transpose(0, 1).contiguous()
-            ungroup = lambda x: x.transpose(0, 1)[torch.argsort(order)].reshape((n_ag * n_envs,) + tuple(x.shape[2:]))
-        # per-step intrinsic rewards in the buffer's own layout ([T, E*A] rows of agents side by side when grouped)
-        intr_buf = torch.zeros(T, E * (pol.num_agents if grouped else 1), dtype=torch.float32,
-                               device=self.device) if pol.enable_icm else None
-
-        grouped_intrinsic = lambda *step: self._grouped_intrinsic(pol, *step)
-
-        if pol.enable_icm:
-            may_end_early = True          # bootstrap rewards carry the "surprise" term: dense end table
-        # replay of a recorded rollout: `self.replay_raw_actions` ([T, rows, .] device tensor in the buffer's row
-        # layout, or None) makes every step log the recorded raw action instead of sampling one
+        dict_env = isinstance(obs, dict)
+        agent_rows = self._policy_agent_rows(env)
+        env_agents = list(getattr(env, "agent_ids", ["agent0"]))
+        A = len(env_agents)
+        if sorted(i for *_, index in agent_rows for i in index) != list(range(A)):
+            raise ValueError("policy_mapping_fn must assign every agent of the env to exactly one policy")
+        members = [_RolloutMember(self, policy_id, agents, index, A, n_envs, T, not dict_env and len(index) == A)
+                   for policy_id, _, agents, index in agent_rows]
         rec = getattr(self, "replay_raw_actions", None)
-        replay = (lambda t: None) if rec is None else (lambda t: rec[t].contiguous())
-        mat_blocks = bool(self.step_row_blocks and fused_step and grouped)
-        if mat_blocks:
-            mat_act_env = torch.zeros((n_ag * n_envs,) + tuple(buf.actions.shape[3:]), dtype=buf.actions.dtype, device=self.device)
-        nat_buf = self._scratch(f"nat_buf_{T}_{env.num_agents if hasattr(env, 'num_agents') else 1}_{n_envs}",
-                                T * (E if not grouped else E * pol.num_agents), torch.float32).view(T, -1)
-        mat_finish = None
-        if mat_blocks and self.finish_rows:
-            from .kernels import RolloutFinish
-            if RolloutFinish.unsupported_reason([n_ag]) == "":
-                mat_finish = RolloutFinish([dict(agents=list(range(n_ag)), index=list(range(n_ag)), rewards=buf.rewards,
-                                                 natural=nat_buf, end_kind=buf.end_kind, intrinsic=intr_buf,
-                                                 slot_order=pol.agent_slot_order())], n_ag, n_envs, self.max_ts_per_ep,
-                                           self.ext_reward_weight, ep_ts)
+        if rec is not None and not isinstance(rec, dict):
+            if len(members) > 1:
+                raise ValueError("replay_raw_actions with several policies: a dict {policy_id: [T, rows, .]}")
+            rec = {members[0].id: rec}
+        for m in members:
+            m.recorded = None if rec is None else rec.get(m.id)
+        # The agents of an env end together (every env of environments/), so the end flags and ep_ts are kept per env;
+        # a non-grouped member that owns every row takes the flags as handed, per buffer row.
+        row_ends = members[0].whole and not members[0].grouped
+        per_env = (lambda x: x) if row_ends else (lambda x: x[env_agents[0]] if isinstance(x, dict) else x[:n_envs])
+        ep_ts = torch.zeros(A * n_envs if row_ends else n_envs, dtype=torch.int32, device=self.device)
+        may_end_early = getattr(env, "term_table", True) is not None or self.max_ts_per_ep < T
+        if any(m.pol.enable_icm for m in members):
+            may_end_early = True          # bootstrap rewards carry the "surprise" term: dense end table, shared by all
+        # K23 (kernels.RolloutFinish): the rows that follow env.step, for all members in one launch.  It reads the env's
+        # rows through block tables, so a member that takes the env's tensors as they are keeps the torch statements.
+        as_handed = lambda: any(m.whole and not m.blocks for m in members)
+        finish, why = None, ""
+        if self.finish_rows and not as_handed():
+            why = "the rollout is not on a HIP device or update_mode='torch'"
+            if self.device.type == "cuda" and self.update_mode != "torch":
+                from .kernels import RolloutFinish
+                why = RolloutFinish.unsupported_reason([m.n for m in members])
+                if why == "":
+                    finish = RolloutFinish(
+                        [dict(agents=m.agents, index=m.index, rewards=m.buf.rewards, natural=m.nat, end_kind=m.buf.end_kind,
+                              intrinsic=m.intr, slot_order=m.pol.agent_slot_order() if m.grouped else None) for m in members],
+                        A, n_envs, self.max_ts_per_ep, self.ext_reward_weight, ep_ts)
+        if why and self.verbose:
+            rank_print(f"rollout: the per-step rows stay on torch operators ({why})")
+        lstm_members = [m for m in members if m.pol.using_lstm]
+        # what env.step takes: a dict by agent id, or the combined tensor [A, E, .] once a member needs one
+        actions = {} if dict_env else None
         for t in range(T):
-            if fused_step and grouped:
-                # K16: encoder + autoregressive decoder passes + sampling + values + the buffer row in one launch
-                tb = None
-                if mat_blocks:
-                    # the block form reads the env's agent-major rows in the policy's slot order and writes the env's
-                    # action tensor itself: no group() / ungroup()
-                    cut = lambda x: list(x.reshape((n_ag, n_envs) + tuple(x.shape[1:])).unbind(0))
-                    tb = (cut(critic_obs), None if pol.expanded_actor_space else cut(obs), cut(mat_act_env))
-                    why = pol.step_blocks_unsupported_reason(*tb)
-                    if why:
-                        mat_blocks, tb = False, None
-                        if self.verbose:
-                            rank_print(f"rollout: policy {policy_id} regroups its rows with torch operators ({why})")
-                if tb is not None:
-                    pol.rollout_step(t, None, None, vn, forced_raw_action=replay(t), blocks=tb)
-                    act_env = mat_act_env
+            last, env_action = t == T - 1, None
+            for m in members:
+                if m.blocks and actions is None:
+                    actions = torch.zeros((A, n_envs) + m.agent_action_shape(), dtype=m.buf.actions.dtype, device=self.device)
+                a = m.act(t, obs, critic_obs, actions)
+                if a is None:                     # the block form has written the member's blocks of `actions`
+                    if dict_env:
+                        actions.update(zip(m.agents, m.env_act))
+                elif m.whole:
+                    env_action = a
+                elif dict_env:
+                    per_agent = a.reshape((m.n, n_envs) + tuple(a.shape[1:]))
+                    for i, agent_id in enumerate(m.agents):
+                        actions[agent_id] = per_agent[i]
                 else:
-                    g_obs, g_cobs = group(obs), group(critic_obs)
-                    action = pol.rollout_step(t, g_cobs, g_cobs if pol.expanded_actor_space else g_obs, vn, forced_raw_action=replay(t))
-                    act_env = ungroup(action)
-                nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(act_env))
-                nat = self._natural_reward(env, reward)
-                terminated, truncated = terminated[:n_envs], truncated[:n_envs]   # agents of an env end together
-                if mat_finish is not None:
-                    why = "the step was regrouped" if tb is None else mat_finish.inputs_unsupported_reason(
-                        reward, None if nat is reward else nat, terminated if may_end_early else None,
-                        truncated if may_end_early else None)
-                    if why:               # the torch statements from here on (ep_ts has been advanced in place)
-                        mat_finish = None
-                        if self.verbose:
-                            rank_print(f"rollout: policy {policy_id}: the per-step rows stay on torch operators ({why})")
-                if mat_finish is not None:
-                    # K23 with one grouped member: reward (weighted, + intrinsic), natural reward, end_kind and ep_ts in one
-                    # launch, in the buffer's [E, A] slot order -- no group() of the reward either
-                    if pol.enable_icm:
-                        intr_buf[t] = group(grouped_intrinsic(obs, critic_obs, nxt_obs, nxt_cobs, act_env)).reshape(-1)
-                    mat_finish.step(t, reward, None if nat is reward else nat, terminated if may_end_early else None,
-                                    truncated if may_end_early else None, t == T - 1)
-                    pol.finish_step(t, None, group(nxt_cobs if pol.expanded_actor_space else term_obs) if pol.enable_icm else None)
-                    if may_end_early:
-                        buf.fixed_length = False
-                    obs, critic_obs = nxt_obs, nxt_cobs
-                    continue
-                nat_buf[t].copy_(nat)
-                if self.ext_reward_weight != 1.0:
-                    reward = reward * self.ext_reward_weight
-                if pol.enable_icm:
-                    intr = grouped_intrinsic(obs, critic_obs, nxt_obs, nxt_cobs, act_env)
-                    intr_buf[t] = group(intr).reshape(-1)
-                    reward = reward + intr
-                pol.finish_step(t, group(reward), group(nxt_cobs if pol.expanded_actor_space else term_obs) if pol.enable_icm else None)
-            elif fused_step:
-                # K6+K7: inference, sampling, log-probs, values and the buffer row in one launch
-                action = pol.rollout_step(t, obs.contiguous(), critic_obs.contiguous(), vn, forced_raw_action=replay(t))
-                nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(action))
-                nat_buf[t].copy_(self._natural_reward(env, reward))
-                if self.ext_reward_weight != 1.0:
-                    reward = reward * self.ext_reward_weight
-                if pol.enable_icm:            # ppo.py:1719-1723 -> apply_intrinsic_rewards :1219-1288
-                    intr_buf[t] = pol.get_intrinsic_reward(obs, nxt_obs, action)   # ppo.py:1719-1723: the post-step observation
-                    reward = reward + intr_buf[t]
-                pol.finish_step(t, reward, term_obs)
-            elif lstm_step:
-                action = pol.lstm_rollout_step(t, obs.contiguous(), critic_obs.contiguous(), vn, forced_raw_action=replay(t))
-                nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(action))
-                nat_buf[t].copy_(self._natural_reward(env, reward))
-                if self.ext_reward_weight != 1.0:
-                    reward = reward * self.ext_reward_weight
-                if not (may_end_early and t < T - 1):      # no critic step on the next observation: the zeroing alone
-                    pol.lstm_finish_step(t, reward, terminated)
-            elif grouped:
-                g_obs, g_cobs = group(obs), group(critic_obs)
-                raw_action, action, log_prob = pol.get_rollout_actions(g_cobs if pol.expanded_actor_space else g_obs, forced_raw_action=replay(t))
-                value = self.get_policy_values(policy_id, g_cobs)
-                act_env = ungroup(action)
-                nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(act_env))
-                nat_buf[t].copy_(self._natural_reward(env, reward))
-                if self.ext_reward_weight != 1.0:
-                    reward = reward * self.ext_reward_weight
-                if pol.enable_icm:
-                    intr = grouped_intrinsic(obs, critic_obs, nxt_obs, nxt_cobs, act_env)
-                    intr_buf[t] = group(intr).reshape(-1)
-                    reward = reward + intr
-                buf.write_step(t, slice(0, E), g_cobs, g_cobs if pol.expanded_actor_space else g_obs,
-                               group(nxt_cobs if pol.expanded_actor_space else term_obs) if pol.enable_icm else None,
-                               raw_action, action, value, log_prob, group(reward))
-                pol._t = t + 1
-                terminated, truncated = terminated[:n_envs], truncated[:n_envs]   # agents of an env end together
-            else:
-                raw_action, action, log_prob = pol.get_rollout_actions(obs, forced_raw_action=replay(t))
-                value = self.get_policy_values(policy_id, critic_obs)
-                nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(action))
-                nat_buf[t].copy_(self._natural_reward(env, reward))
-                if self.ext_reward_weight != 1.0:
-                    reward = reward * self.ext_reward_weight
-                if pol.enable_icm:
-                    intr_buf[t] = pol.get_intrinsic_reward(obs, nxt_obs, action)   # ppo.py:1719-1723: the post-step observation
-                    reward = reward + intr_buf[t]
-                buf.write_step(t, slice(0, E), critic_obs, obs, term_obs, raw_action, action, value,
-                               log_prob, reward)
-                pol._t = t + 1
-                if pol.using_lstm:
-                    pol.store_hidden_states(t, terminated)
-            if may_end_early:
+                    if actions is None:
+                        actions = torch.zeros((A, n_envs) + tuple(a.shape[1:]), dtype=a.dtype, device=self.device)
+                    elif a.dtype != actions.dtype or tuple(a.shape[1:]) != tuple(actions.shape[2:]):
+                        raise ValueError(
+                            f"policy {m.id} produces actions {a.dtype}{tuple(a.shape[1:])} but the env's combined action tensor "
+                            f"holds {actions.dtype}{tuple(actions.shape[2:])}: policies with different action spaces need an env "
+                            "that exchanges dicts keyed by agent id (environments/synthetic.py:SyntheticMixedAgentsEnv)")
+                    actions[m.idx] = a.reshape((m.n, n_envs) + tuple(a.shape[1:]))
+            if env_action is None:
+                env_action = actions if dict_env else actions.reshape((A * n_envs,) + tuple(actions.shape[2:]))
+            nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(env_action))
+            nat = self._natural_reward(env, reward)
+            term_e, trunc_e = per_env(terminated), per_env(truncated)
+            if finish is not None:
+                finish_in = (reward, None if nat is reward else nat, term_e if may_end_early else None,
+                             trunc_e if may_end_early else None)
+                why = "a policy regrouped its rows" if as_handed() else finish.inputs_unsupported_reason(*finish_in)
+                if why:                   # the torch statements from here on (ep_ts has been advanced in place)
+                    finish = None
+                    if self.verbose:
+                        rank_print(f"rollout: the per-step rows stay on torch operators ({why})")
+            # ext_reward_weight: on the whole tensor here, per member for a dict env, inside the launch when K23 runs
+            if self.ext_reward_weight != 1.0 and not dict_env and finish is None:
+                reward = reward * self.ext_reward_weight
+            for m in members:
+                m.answer(t, reward, nat, nxt_obs, nxt_cobs, term_obs, finish is not None)
+            if finish is not None:
+                # K23: every member's reward, natural-reward and end_kind rows and the shared ep_ts, in one launch
+                finish.step(t, *finish_in, last)
+            for m in members:
+                m.write(t, terminated, may_end_early and not last)
+                if may_end_early:
+                    m.buf.fixed_length = False        # (also at the last row: an env may TERMINATE there -- ts_per_rollout = 1 made it visible)
+            if may_end_early and finish is None:
                 ep_ts += 1
-                last = t == T - 1
-                boot = (~terminated) & ((ep_ts >= self.max_ts_per_ep) | truncated | last)
-                if pol.using_lstm and not last:
-                    # ppo.py:1863-1881: whenever an episode is cut (max length / truncation) the reference
-                    # evaluates the critic on the NEXT observation for the whole batch, which also steps the
-                    # stateful LSTM critic once more.  Branch-free here: the extra step is computed every
-                    # time and kept only if the reference would have taken it.
-                    cut = (((ep_ts == self.max_ts_per_ep) & ~terminated).any() | truncated.any())   # ep_ts of terminated envs is 0 by then (:1851)
-                    if lstm_step:
-                        # the flag stays on the device: the launch keeps the critic's stepped state only where it is set
-                        pol.lstm_finish_step(t, reward, terminated, nxt_cobs.contiguous(), cut, vn)
-                    else:
-                        h_old = tuple(x.clone() for x in pol.critic.hidden_state)
-                        v_next = self.get_policy_values(policy_id, nxt_cobs)
-                        pol.critic.hidden_state = tuple(torch.where(cut, n, o) for n, o in zip(pol.critic.hidden_state, h_old))
-                        buf.boot_value[t].copy_(v_next)
-                buf.end_kind[t] = torch.where(terminated, 1, torch.where(boot, 2, 0)).to(torch.int8)
-                ep_ts = torch.where(terminated | boot, torch.zeros_like(ep_ts), ep_ts)
-                buf.fixed_length = False        # (also at the last row: an env may TERMINATE there -- ts_per_rollout = 1 made it visible)
+                boot = (~term_e) & ((ep_ts >= self.max_ts_per_ep) | trunc_e | last)
+                for m in lstm_members:
+                    if not last:
+                        # ppo.py:1863-1881: whenever an episode is cut (max length / truncation) the reference
+                        # evaluates the critic on the NEXT observation for the whole batch, which also steps the
+                        # stateful LSTM critic once more.  Branch-free here: the extra step is computed every
+                        # time and kept only if the reference would have taken it.
+                        cut = (((ep_ts == self.max_ts_per_ep) & ~term_e).any() | trunc_e.any())   # ep_ts of terminated envs is 0 by then (:1851)
+                        m.lstm_critic_next(t, terminated, nxt_cobs, cut)
+                kind = torch.where(term_e, 1, torch.where(boot, 2, 0)).to(torch.int8)
+                for m in members:
+                    m.buf.end_kind[t] = kind if m.grouped or row_ends else kind.repeat(m.n)
+                ep_ts = torch.where(term_e | boot, torch.zeros_like(ep_ts), ep_ts)
             obs, critic_obs = nxt_obs, nxt_cobs
-        # bootstrap values: V(next obs).  For ends before the last row the next
-        # observation's value is the value logged at t+1 (same critic, same
-        # normaliser state during a rollout); the last row needs one more pass.
-        if lstm_step:
-            next_value = pol.lstm_last_value(T - 1, critic_obs.contiguous(), vn)      # (lands in boot_value[T - 1])
-        else:
-            next_value = self.get_policy_values(policy_id, group(critic_obs) if grouped else critic_obs)
-        self._close_rollout_buffer(policy_id, pol, next_value, intr_buf, may_end_early, lstm_step)
         self._obs = (obs, critic_obs)
-        pol.finalize_dataset()
-        self._publish_rollout_statistics(policy_id, buf, nat_buf, intr_buf, n_envs, T, obs, grouped)
         gs = self.status_dict["global status"]
+        episodes_before = gs["total episodes"]
+        for m in members:
+            m.close(T, obs, critic_obs, may_end_early)
+        if len(members) > 1:
+            # every policy's statistics pass added the (shared, per-env) episode count: keep it once (ppo.py:2089)
+            gs["total episodes"] = episodes_before + (gs["total episodes"] - episodes_before) / len(members)
         gs["timesteps"] += self.ts_per_rollout * mpi_utils.get_num_procs()     # env steps (ppo.py:1653), not agent steps
         torch.cuda.synchronize() if self.device.type == "cuda" else None
         gs["rollout time"] = time.time() - start
-        return pol.dataset
+        return members[0].pol.dataset if len(members) == 1 else {m.id: m.pol.dataset for m in members}
 
     @staticmethod
     def _grouped_intrinsic(pol, prev_obs, prev_cobs, nxt_obs, nxt_cobs, act_env):
@@ -581,248 +730,6 @@ class PPO:
             if not lstm_step:
                 buf.boot_value[buf.T - 1].copy_(next_value)
             buf.boot_reward[buf.T - 1].copy_(next_value)
-
-    def _rollout_multi_policy(self):
-        """
-        ppo.py:1534-2110 with several policies (`policy_mapping_fn` partitions the env's agents, ppo.py:329-345,
-        710-858): every policy acts on its own agents' rows of the agent-major env tensors and logs into its own
-        rollout buffer; the env is stepped once with the combined actions; episode ends are shared (the agents of an
-        env end together).  Members are feed-forward PPOPolicy instances (independent or team-wise PPO) and MATPolicy
-        teams, each with or without an ICM; every member behaves as it does alone in `rollout` on an env restricted to
-        its agents.  The env hands over either agent-major tensors [A*E, .] (all agents share shapes) or, as the
-        reference's multi-agent wrappers do, dicts keyed by agent id (agents of different policies may then differ in
-        observation / action space; the agents of ONE policy share them, as in the reference).  A grouped member's
-        buffer rows are [E, A, .] in its own slot order and its `end_kind` is per env; an ICM member adds its
-        intrinsic reward after `ext_reward_weight`, keeps the next observations and turns the dense end table on for
-        the whole run (episode ends are shared).  `replay_raw_actions` may be a dict {policy_id: [T, rows, .]} in each
-        member's buffer layout.  LSTM policies stay a single-policy feature.
-        """
-        start = time.time()
-        env = self.env
-        n_envs = env.get_batch_size()
-        T = self.ts_per_rollout // n_envs
-        agent_ids = list(env.agent_ids)
-        A = len(agent_ids)
-        ctxs = []
-        for policy_id, pol in self.policies.items():
-            if pol.using_lstm:
-                raise NotImplementedError(f"several policies in one run: LSTM policies are not supported (policy {policy_id})")
-        for policy_id, pol in self.policies.items():
-            pol.initialize_dataset()
-            pol.eval()
-            pol.initialize_episodes(n_envs, self.status_dict, ts_per_rollout=self.ts_per_rollout)
-            idx = torch.as_tensor(sorted(agent_ids.index(a) for a in pol.agent_ids), device=self.device)
-            n = int(idx.numel())
-            fused = (self.update_mode != "torch" and self.device.type == "cuda"
-                     and pol.fused_step_unsupported_reason() == "")
-            c = dict(id=policy_id, pol=pol, buf=pol.buffer, idx=idx, n=n, fused=fused, grouped=bool(pol.agent_grouping),
-                     agents=[agent_ids[int(i)] for i in idx],          # the policy's agents in env order
-                     vn=self.value_normalizers[policy_id] if self.normalize_values else None,
-                     nat=torch.zeros(T, n * n_envs, dtype=torch.float32, device=self.device),
-                     # per-step intrinsic rewards in the buffer's own layout (agents side by side when grouped)
-                     intr=torch.zeros(T, n * n_envs, dtype=torch.float32, device=self.device) if pol.enable_icm else None)
-            if c["grouped"]:
-                # MAT: [n*E, .] agent-major rows of the member's agents <-> [E, n, .] in its (shuffled) slot order
-                pol.shuffle_agent_ids()
-                c["order"] = torch.as_tensor(pol.agent_slot_order(), device=self.device)
-                c["inverse"] = torch.argsort(c["order"])
-            ctxs.append(c)
-        if sorted(int(i) for c in ctxs for i in c["idx"]) != list(range(A)):
-            raise ValueError("policy_mapping_fn must assign every agent of the env to exactly one policy")
-        group = lambda x, c: x.reshape((c["n"], n_envs) + tuple(x.shape[1:]))[c["order"]].transpose(0, 1).contiguous()
-        ungroup = lambda x, c: x.transpose(0, 1)[c["inverse"]].reshape((c["n"] * n_envs,) + tuple(x.shape[2:]))
-        rec = getattr(self, "replay_raw_actions", None)
-        if rec is not None and not isinstance(rec, dict):
-            raise ValueError("replay_raw_actions with several policies: a dict {policy_id: [T, rows, .]}")
-        replay = lambda t, c: None if rec is None or c["id"] not in rec else rec[c["id"]][t].contiguous()
-        if self._obs is None or not self.soft_resets():
-            obs, critic_obs = self.apply_policy_reset_constraints(*env.reset())
-        else:
-            soft = getattr(env, "soft_reset", None)
-            obs, critic_obs = soft() if callable(soft) else self._obs
-        dict_env = isinstance(obs, dict)
-
-        def rows(x, c):
-            """The policy's rows of an env quantity, agent-major: [n * E, .]."""
-            if isinstance(x, dict):
-                return torch.cat([x[a] for a in c["agents"]], 0)
-            return x.reshape((A, n_envs) + tuple(x.shape[1:]))[c["idx"]].reshape((c["n"] * n_envs,) + tuple(x.shape[1:]))
-
-        per_env = lambda x: (x[agent_ids[0]] if isinstance(x, dict) else x[:n_envs])   # agents of an env end together
-        ep_ts = torch.zeros(n_envs, dtype=torch.int32, device=self.device)
-        may_end_early = getattr(env, "term_table", True) is not None or self.max_ts_per_ep < T
-        if any(c["pol"].enable_icm for c in ctxs):
-            may_end_early = True          # bootstrap rewards carry the "surprise" term: dense end table, shared by all
-        actions = None
-        # K23 (kernels.RolloutFinish): the rows that follow env.step, for all members in one launch
-        finish, why = None, "the rollout is not on a HIP device or update_mode='torch'"
-        if self.finish_rows and self.device.type == "cuda" and self.update_mode != "torch":
-            from .kernels import RolloutFinish
-            why = RolloutFinish.unsupported_reason([c["n"] for c in ctxs])
-            if why == "":
-                finish = RolloutFinish(
-                    [dict(agents=c["agents"], index=c["idx"].tolist(), rewards=c["buf"].rewards, natural=c["nat"],
-                          end_kind=c["buf"].end_kind, intrinsic=c["intr"],
-                          slot_order=c["pol"].agent_slot_order() if c["grouped"] else None) for c in ctxs],
-                    A, n_envs, self.max_ts_per_ep, self.ext_reward_weight, ep_ts)
-        if finish is None and self.finish_rows and self.verbose:
-            rank_print(f"multi-policy rollout: the per-step rows stay on torch operators ({why})")
-        blocks_of = lambda x, c: ([x[a] for a in c["agents"]] if isinstance(x, dict) else
-                                  [x.reshape((A, n_envs) + tuple(x.shape[1:]))[i] for i in c["index"]])
-        for c in ctxs:
-            # the block forms of K6+K7 and K16: the member reads its agents' rows of the env's tensors where they lie and
-            # writes the env's action tensors itself (a MAT team in its slot order, without group() / ungroup())
-            c["index"] = c["idx"].tolist()
-            c["blocks"] = bool(self.step_row_blocks and c["fused"])
-            if c["blocks"] and dict_env:
-                row = c["buf"].actions[0]
-                per_agent = tuple(row.shape[2:] if c["grouped"] else row.shape[1:])
-                c["env_act"] = [torch.zeros((n_envs,) + per_agent, dtype=row.dtype, device=self.device) for _ in c["agents"]]
-        for t in range(T):
-            for c in ctxs:
-                pol = c["pol"]
-                if c["blocks"]:
-                    row = pol.buffer.actions[t]
-                    per_agent = tuple(row.shape[2:] if c["grouped"] else row.shape[1:])     # one agent's action in one env
-                    if not dict_env:
-                        if actions is None:
-                            actions = torch.zeros((A, n_envs) + per_agent, dtype=row.dtype, device=self.device)
-                        c["env_act"] = [actions[i] for i in c["index"]]
-                    if c["grouped"]:
-                        tb = (blocks_of(critic_obs, c), None if pol.expanded_actor_space else blocks_of(obs, c), c["env_act"])
-                    else:
-                        tb = (blocks_of(obs, c), blocks_of(critic_obs, c), c["env_act"])
-                    why = "the env's action tensor has another dtype or shape" if not dict_env and (
-                        actions.dtype != row.dtype or tuple(actions.shape[2:]) != per_agent) else \
-                        pol.step_blocks_unsupported_reason(*tb)
-                    if why:
-                        c["blocks"] = False
-                        if self.verbose:
-                            rank_print(f"multi-policy rollout: policy {c['id']} gathers its rows with torch operators ({why})")
-                    else:
-                        if c["grouped"]:
-                            pol.rollout_step(t, None, None, c["vn"], forced_raw_action=replay(t, c), blocks=tb)
-                            a = torch.cat(c["env_act"], 0) if pol.enable_icm else None        # agent-major, as ungroup() gives it
-                        else:
-                            a = pol.rollout_step(t, None, None, c["vn"], forced_raw_action=replay(t, c), blocks=tb)
-                        if pol.enable_icm:        # the ICM's view of the step: the critic's rows only where its actor sees them
-                            c["step"] = (rows(obs, c), rows(critic_obs, c) if c["grouped"] and pol.expanded_actor_space else None, a)
-                        else:
-                            c["step"] = (None, None, a)
-                        if dict_env:
-                            if actions is None:
-                                actions = {}
-                            actions.update(zip(c["agents"], c["env_act"]))
-                        continue
-                o, co = rows(obs, c).contiguous(), rows(critic_obs, c).contiguous()
-                if c["grouped"]:
-                    g_obs, g_cobs = group(o, c), group(co, c)
-                    a_obs = g_cobs if pol.expanded_actor_space else g_obs
-                    if c["fused"]:
-                        g_a = pol.rollout_step(t, g_cobs, a_obs, c["vn"], forced_raw_action=replay(t, c))
-                    else:
-                        raw, g_a, lp = pol.get_rollout_actions(a_obs, forced_raw_action=replay(t, c))
-                        c["pending"] = (g_cobs, a_obs, raw, g_a, self.get_policy_values(c["id"], g_cobs), lp)
-                    a = ungroup(g_a, c)
-                elif c["fused"]:
-                    a = pol.rollout_step(t, o, co, c["vn"], forced_raw_action=replay(t, c))
-                else:
-                    raw, a, lp = pol.get_rollout_actions(o, forced_raw_action=replay(t, c))
-                    c["pending"] = (co, o, raw, a, self.get_policy_values(c["id"], co), lp)
-                c["step"] = (o, co, a)
-                if dict_env:
-                    if actions is None:
-                        actions = {}
-                    per_agent = a.reshape((c["n"], n_envs) + tuple(a.shape[1:]))
-                    for i, agent_id in enumerate(c["agents"]):
-                        actions[agent_id] = per_agent[i]
-                    continue
-                if actions is None:
-                    actions = torch.zeros((A, n_envs) + tuple(a.shape[1:]), dtype=a.dtype, device=self.device)
-                elif a.dtype != actions.dtype or tuple(a.shape[1:]) != tuple(actions.shape[2:]):
-                    raise ValueError(
-                        f"policy {c['id']} produces actions {a.dtype}{tuple(a.shape[1:])} but the env's combined action tensor "
-                        f"holds {actions.dtype}{tuple(actions.shape[2:])}: policies with different action spaces need an env "
-                        "that exchanges dicts keyed by agent id (environments/synthetic.py:SyntheticMixedAgentsEnv)")
-                actions[c["idx"]] = a.reshape((c["n"], n_envs) + tuple(a.shape[1:]))
-            env_action = actions if dict_env else actions.reshape((A * n_envs,) + tuple(actions.shape[2:]))
-            nxt_obs, nxt_cobs, reward, terminated, truncated, term_obs = self.apply_policy_step_constraints(*env.step(env_action))
-            nat = self._natural_reward(env, reward)
-            env_reward = reward
-            if finish is not None:
-                why = finish.inputs_unsupported_reason(reward, None if nat is reward else nat,
-                                                       per_env(terminated) if may_end_early else None,
-                                                       per_env(truncated) if may_end_early else None)
-                if why:                   # the torch statements from here on (ep_ts has been advanced in place)
-                    finish = None
-                    if self.verbose:
-                        rank_print(f"multi-policy rollout: the per-step rows stay on torch operators ({why})")
-            if self.ext_reward_weight != 1.0 and not dict_env and finish is None:
-                reward = reward * self.ext_reward_weight
-            for c in ctxs:
-                pol, nxt, intr = c["pol"], None, None
-                prev_o, prev_co, act = c.pop("step")
-                if pol.enable_icm and c["grouped"]:
-                    n_o, n_co = rows(nxt_obs, c), rows(nxt_cobs, c) if pol.expanded_actor_space else None
-                    intr = self._grouped_intrinsic(pol, prev_o, prev_co, n_o, n_co, act)
-                    c["intr"][t] = group(intr, c).reshape(-1)
-                    nxt = group(n_co if pol.expanded_actor_space else rows(term_obs, c), c)
-                elif pol.enable_icm:              # ppo.py:1719-1723: the post-step observation
-                    c["intr"][t] = intr = pol.get_intrinsic_reward(prev_o, rows(nxt_obs, c), act)
-                    nxt = rows(term_obs, c)
-                if finish is not None:
-                    r = c["buf"].rewards[t]       # K23 below writes the row: the torch path's write_step copies it onto itself
-                else:
-                    c["nat"][t].copy_(rows(nat, c))
-                    r = rows(reward, c)
-                    if self.ext_reward_weight != 1.0 and dict_env:
-                        r = r * self.ext_reward_weight
-                    if intr is not None:
-                        r = r + intr
-                    if c["grouped"]:
-                        r = group(r, c)
-                c["answer"] = (r, nxt)
-            if finish is not None:
-                # K23: every member's reward, natural-reward and end_kind rows and the shared ep_ts, in one launch
-                finish.step(t, env_reward, None if nat is env_reward else nat,
-                            per_env(terminated) if may_end_early else None, per_env(truncated) if may_end_early else None,
-                            t == T - 1)
-            for c in ctxs:
-                r, nxt = c.pop("answer")
-                if c["fused"]:
-                    c["pol"].finish_step(t, None if finish is not None else r, nxt)
-                else:
-                    co, o, raw, a, v, lp = c.pop("pending")
-                    c["buf"].write_step(t, slice(0, c["buf"].C), co, o, nxt, raw, a, v, lp, r)
-                    c["pol"]._t = t + 1
-                if may_end_early:
-                    c["buf"].fixed_length = False
-            if may_end_early and finish is None:
-                term_e, trunc_e = per_env(terminated), per_env(truncated)
-                ep_ts += 1
-                last = t == T - 1
-                boot = (~term_e) & ((ep_ts >= self.max_ts_per_ep) | trunc_e | last)
-                kind = torch.where(term_e, 1, torch.where(boot, 2, 0)).to(torch.int8)
-                for c in ctxs:
-                    c["buf"].end_kind[t] = kind if c["grouped"] else kind.repeat(c["n"])
-                ep_ts = torch.where(term_e | boot, torch.zeros_like(ep_ts), ep_ts)
-            obs, critic_obs = nxt_obs, nxt_cobs
-        self._obs = (obs, critic_obs)
-        gs = self.status_dict["global status"]
-        episodes_before = gs["total episodes"]
-        for c in ctxs:
-            buf = c["buf"]
-            last_cobs = rows(critic_obs, c).contiguous()
-            next_value = self.get_policy_values(c["id"], group(last_cobs, c) if c["grouped"] else last_cobs)
-            self._close_rollout_buffer(c["id"], c["pol"], next_value, c["intr"], may_end_early)
-            c["pol"].finalize_dataset()
-            self._publish_rollout_statistics(c["id"], buf, c["nat"], c["intr"], n_envs, T, rows(obs, c), c["grouped"])
-        # every policy's statistics pass added the (shared, per-env) episode count: keep it once (ppo.py:2089)
-        gs["total episodes"] = episodes_before + (gs["total episodes"] - episodes_before) / len(ctxs)
-        gs["timesteps"] += self.ts_per_rollout * mpi_utils.get_num_procs()
-        torch.cuda.synchronize() if self.device.type == "cuda" else None
-        gs["rollout time"] = time.time() - start
-        return {c["id"]: c["pol"].dataset for c in ctxs}
 
     @staticmethod
     def _natural_reward(env, reward):
@@ -919,7 +826,7 @@ class PPO:
         return env
 
     def _policy_agent_rows(self, env):
-        """[(policy_id, policy, its agents in env order, their indices)] -- the index sets _rollout_multi_policy builds."""
+        """[(policy_id, policy, its agents in env order, their indices)] -- the index sets of a rollout's members."""
         agent_ids = list(getattr(env, "agent_ids", ["agent0"]))
         out = []
         for policy_id, pol in self.policies.items():
@@ -939,9 +846,8 @@ class PPO:
             obs = critic_obs
         n = obs.shape[0] // n_envs
         order = torch.as_tensor(pol.agent_slot_order(), device=obs.device)
-        g = obs.reshape((n, n_envs) + tuple(obs.shape[1:]))[order].transpose(0, 1).contiguous()
-        a = pol.get_inference_actions(g, deterministic)                     # [E, n, .]
-        return a.transpose(0, 1)[torch.argsort(order)].reshape((n * n_envs,) + tuple(a.shape[2:]))
+        a = pol.get_inference_actions(_group(obs, n, n_envs, order), deterministic)                     # [E, n, .]
+        return _ungroup(a, n, n_envs, torch.argsort(order))
 
     def get_inference_actions(self, obs, deterministic, critic_obs=None, env=None):
         """
@@ -975,9 +881,8 @@ class PPO:
                     # argument of the launch
                     return pol.get_inference_actions_agent_major(obs, deterministic)
                 order = torch.as_tensor(pol.agent_slot_order(), device=obs.device)
-                g = obs.reshape((A, n_envs) + tuple(obs.shape[1:]))[order].transpose(0, 1).contiguous()
-                a = pol.get_inference_actions(g, deterministic)                     # [E, A, .]
-                return a.transpose(0, 1)[torch.argsort(order)].reshape((A * n_envs,) + tuple(a.shape[2:]))
+                a = pol.get_inference_actions(_group(obs, A, n_envs, order), deterministic)                     # [E, A, .]
+                return _ungroup(a, A, n_envs, torch.argsort(order))
             return pol.get_inference_actions(obs, deterministic)
         actions = None
         for _, pol, agents, idx in groups:

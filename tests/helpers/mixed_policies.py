@@ -81,9 +81,9 @@ def settings_of(specs, members):
     return out
 
 
-def mixed_run(name, dev, mode, prepare=None, **kw):
+def mixed_run(name, dev, mode, prepare=None, term_prob=0.05, **kw):
     specs, members = member_sets()[name]
-    env_gen = lambda: SyntheticMixedAgentsEnv(E, specs, T, dev, reward="uniform", seed=33, term_prob=0.05)
+    env_gen = lambda: SyntheticMixedAgentsEnv(E, specs, T, dev, reward="uniform", seed=33, term_prob=term_prob)
     mapping = lambda a: next(pid for pid, (_, prefix, _) in members.items() if a.startswith(prefix))
     ppo = make_ppo(env_gen, settings_of(specs, members), mapping, dev, mode, **kw)
     if prepare is not None:

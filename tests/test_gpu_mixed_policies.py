@@ -159,14 +159,17 @@ def test_library_calls_per_env_step_of_a_fused_mixed_rollout(name, monkeypatch):
     assert calls == ["ppoaf_policy_step", "ppoaf_mat_policy_step", "env.step"] * M.T
 
 
-@pytest.mark.parametrize("name", ["ppo+mat_icm", "ppo_icm+mat"])
+@pytest.mark.parametrize("name", ["ppo+mat_icm", "ppo_icm+mat", "ppo+mat fixed-length"])
 def test_the_block_routes_against_the_torch_operators_they_replace(name):
     """The attributes that keep the gather path: the same fused mixed rollout with `finish_rows` and `step_row_blocks` on
-    and off, bitwise."""
+    and off, bitwise.  `fixed-length`: no terminations and episodes longer than the rollout, so no end is written before
+    the last row (K23 without end tables against the torch statements that skip theirs)."""
     import mixed_policies as M
+    name, _, fixed_length = name.partition(" fixed-length")
+    kw = dict(term_prob=0.0, max_ts_per_ep=200) if fixed_length else {}
     snaps = []
     for on in (True, False):
-        ppo, specs, _ = M.mixed_run(name, DEV, "fused", _prepare)
+        ppo, specs, _ = M.mixed_run(name, DEV, "fused", _prepare, **kw)
         ppo.finish_rows = ppo.step_row_blocks = on
         ppo.replay_raw_actions = M.replay_actions(ppo, specs)
         np.random.seed(11)

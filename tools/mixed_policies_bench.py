@@ -1,5 +1,5 @@
 """
-Rollout cost of multi-policy runs on one GPU (profiles/mixed_policies.txt):
+Rollout cost of multi-policy and single-policy runs on one GPU (profiles/mixed_policies.txt, profiles/one_rollout_loop.txt):
 
   mixed      mpe_simple_adversary's dims -- an adversary (O 8) on a PPOPolicy, two agents (O 10) on a MATPolicy team,
              Discrete(5), E = 4096, T = 128, update_mode="fused" -- with the block routes on (PPO.finish_rows: K23, one
@@ -8,15 +8,24 @@ Rollout cost of multi-policy runs on one GPU (profiles/mixed_policies.txt):
   two_ppo    the same env with both groups on PPOPolicy (the rollout of
              tests/test_gpu_end_to_end.py::test_two_policies_with_different_spaces_match_two_cpu_ports)
   c5         the single-policy MATPolicy rollout at bench.py's C5 dims (3 agents, O 18, Discrete(5), E = 1024, T = 128)
+  c2         one PPOPolicy alone at bench.py's C2 dims (O 4, Discrete(2), actor / critic 128^3)
+  c4         one PPOPolicy shared by three agents at bench.py's C4 dims (O 18, O_c 54, Discrete(5), actor 128^3, critic
+             256^3, E = 1024): the sole member owns every row and takes the env's tensors as they are
+  lstm       one LSTM policy alone on K21 (tools/lstm_bench.py's cart_pole_lstm shape, update_mode="fused", E = 1024)
+
+All of them run the one loop of PPO.rollout.
 
 Per variant: median rollout milliseconds of --repeats rollouts (after one warm-up) with the spread (min .. max), and
 what the package issues per env step besides the env's own work: library calls and torch operators on device tensors,
-views included (a TorchDispatchMode, suspended inside env.step).  A tree without multi-policy MAT members prints `n/a`
-for `mixed`, so the same file measures a parent commit for two_ppo and c5.
+views included (a TorchDispatchMode, suspended inside env.step; both are the rollout's totals over T, set-up and
+closing included), and the operators between two env.step calls that launch or copy, with a digest of their names.
+A tree without multi-policy MAT members prints `n/a` for `mixed`, so the same file measures a parent commit for the
+other variants.
 
     python tools/mixed_policies_bench.py [--envs 4096] [--ts 128] [--repeats 5] [--label this]
 """
 import argparse
+import hashlib
 import os
 import statistics
 import sys
@@ -37,18 +46,24 @@ DEV = torch.device("cuda", 0)
 box = lambda n: Box(-np.inf, np.inf, (n,), np.float32)
 
 
+# operators that only make another view of a tensor's memory: no launch, no copy
+PURE_VIEWS = ("aten.select.int", "aten.view.default", "aten._unsafe_view.default", "aten.reshape.default", "aten.unbind.int",
+              "aten.alias.default", "aten.slice.Tensor", "aten.detach.default")
+
+
 class _DeviceOps(TorchDispatchMode):
-    """Counts the torch operators that touch a device tensor."""
+    """Counts the torch operators that touch a device tensor, and keeps their names."""
 
     def __init__(self):
         super().__init__()
-        self.n = 0
+        self.n, self.names = 0, []
 
     def __torch_dispatch__(self, func, types, args=(), kwargs=None):
         out = func(*args, **(kwargs or {}))
         flat = list(args) + list((kwargs or {}).values()) + (list(out) if isinstance(out, (tuple, list)) else [out])
         if any(torch.is_tensor(x) and x.is_cuda for x in flat):
             self.n += 1
+            self.names.append(str(func))
         return out
 
 
@@ -68,8 +83,29 @@ def make_c5(E, T):
                save_state=False)
 
 
+def make_single(E, T, O, n_actions, agents=1, critic_hidden=128):
+    env_gen = lambda: SyntheticFixedLengthEnv(E, O, Discrete(n_actions), T, DEV, reward="uniform", seed=1234, num_agents=agents,
+                                              critic_view="policy" if agents > 1 else "local")
+    pargs = dict(actor_kw_args=dict(hidden_size=128), critic_kw_args=dict(hidden_size=critic_hidden))
+    return PPO(env_gen, {"p": (None, box(O), box(O * agents), Discrete(n_actions), pargs)}, device=DEV, random_seed=1,
+               normalize_obs=False, normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=256, save_state=False)
+
+
+def make_lstm(E, T):
+    from ppo_and_friends_amd.networks.lstm import LSTMNetwork
+    kw = dict(sequence_length=5, lstm_hidden_size=32, ff_hidden_size=16, activation=torch.nn.LeakyReLU())
+    env_gen = lambda: SyntheticFixedLengthEnv(E, 4, Discrete(2), T, DEV, reward="uniform", seed=11, term_prob=0.02)
+    pargs = dict(ac_network=LSTMNetwork, actor_kw_args=dict(kw), critic_kw_args=dict(kw))
+    return PPO(env_gen, {"p": (None, box(4), box(4), Discrete(2), pargs)}, device=DEV, random_seed=0, normalize_obs=False,
+               normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=256, max_ts_per_ep=64, save_state=False,
+               update_mode="fused")
+
+
 def per_step_counts(ppo, T):
-    """(library calls, torch operators on device tensors) per env step of one rollout, env.step's own work left out."""
+    """(library calls, torch operators on device tensors) per env step of one rollout, env.step's own work left out; and
+    what lies between two consecutive env.step calls: how many of those operators launch or copy (pure views left out,
+    lowest .. highest over the steps) and a digest of their names in order -- equal digests: the same launching
+    operators in the same order after every step."""
     lib, calls = _lib.load(), [0]
 
     class Counting:
@@ -85,6 +121,7 @@ def per_step_counts(ppo, T):
     mode = _DeviceOps()
 
     def step(action):
+        mode.names.append("env.step")
         with torch.utils._python_dispatch._disable_current_modes():
             return inner_step(action)
     env.step, _lib.load = step, (lambda: Counting())
@@ -93,7 +130,10 @@ def per_step_counts(ppo, T):
             ppo.rollout()
     finally:
         env.step, _lib.load = inner_step, load
-    return calls[0] / T, mode.n / T
+    marks = [i for i, x in enumerate(mode.names) if x == "env.step"]
+    between = [[o for o in mode.names[a + 1:b] if o not in PURE_VIEWS] for a, b in zip(marks[:-1], marks[1:])]
+    digest = hashlib.sha1("\n".join("|".join(seg) for seg in between).encode()).hexdigest()[:10]
+    return calls[0] / T, mode.n / T, min(map(len, between)), max(map(len, between)), digest
 
 
 def timed(variants, repeats):
@@ -109,7 +149,8 @@ def timed(variants, repeats):
 
 def report(label, name, ms, counts):
     med = statistics.median(ms)
-    c = "n/a" if counts is None else f"{counts[0]:.2f} library calls + {counts[1]:.2f} torch operators (views included) per env step"
+    c = "n/a" if counts is None else (f"{counts[0]:.2f} library calls + {counts[1]:.2f} torch operators (views included) per env step; "
+                                      f"between env steps {counts[2]} .. {counts[3]} launching operators, digest {counts[4]}")
     print(f"{label:8s} {name:22s} rollout {med:8.2f} ms  (min {min(ms):.2f} .. max {max(ms):.2f}, {len(ms)} runs)  {c}", flush=True)
 
 
@@ -150,9 +191,13 @@ def main():
     report(a.label, "two_ppo", ms["two_ppo"], per_step_counts(ppo, T))
     del ppo
     E5 = 1024 if E == 4096 else E
-    ppo = make_c5(E5, T)
-    ms = timed({"c5": rollout_ms(ppo)}, a.repeats)
-    report(a.label, f"c5 (E={E5})", ms["c5"], per_step_counts(ppo, T))
+    singles = (("c5", E5, lambda: make_c5(E5, T)), ("c2", E, lambda: make_single(E, T, 4, 2)),
+               ("c4", E5, lambda: make_single(E5, T, 18, 5, agents=3, critic_hidden=256)), ("lstm", E5, lambda: make_lstm(E5, T)))
+    for name, envs, make in singles:
+        ppo = make()
+        ms = timed({name: rollout_ms(ppo)}, a.repeats)
+        report(a.label, f"{name} (E={envs})", ms[name], per_step_counts(ppo, T))
+        del ppo
 
 
 if __name__ == "__main__":
