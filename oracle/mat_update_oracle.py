@@ -52,6 +52,13 @@ class Planted(NamedTuple):
     tanh_gelu: bool = False
     adv_std_ddof: int = 1                # 0: the biased advantage std
     tile_mean: bool = False              # the loss mean over 16-row tiles (dead rows counted) instead of B A tokens
+    # the rollout step K16 only (tests/helpers/mat_step_cases.py, tests/test_mat_step_oracle.py)
+    counter_slot_major: bool = False     # the Philox counter as offset + slot E + env
+    counter_no_slot: bool = False        # the Philox counter as offset + env: one draw shared by an env's agents
+    philox_word_y: bool = False          # the draw from word y of the block
+    stale_logits: bool = False           # every agent's draw taken from pass 0's logits
+    denorm_var: bool = False             # values denormalised with var instead of sqrt(var + 1e-8)
+    logp_no_clamp: bool = False          # the log-prob without the clamp to [eps, 1 - eps]
 
 
 def _pad4(n):

@@ -101,8 +101,8 @@ class Policy:
         if self.bounds is not None:
             a.act_lo, a.act_hi = self.bounds[0].data_ptr(), self.bounds[1].data_ptr()
 
-    def step_k6(self, obs, seed, offset):
-        """ppoaf_policy_step -> action_out."""
+    def step_k6(self, obs, seed, offset, full=False):
+        """ppoaf_policy_step -> action_out; full: (raw_action_out, action_out, logp_out, value_out)."""
         from ppo_and_friends_amd import kernels as K
         E = obs.shape[0]
         a = self._lib.PolicyStepArgs()
@@ -115,7 +115,7 @@ class Policy:
         logp, val = torch.zeros(E, device=self.device), torch.zeros(E, device=self.device)
         a.raw_action_out, a.action_out, a.logp_out, a.value_out = raw.data_ptr(), act.data_ptr(), logp.data_ptr(), val.data_ptr()
         K.policy_step(a)
-        return act
+        return (raw, act, logp, val) if full else act
 
     def infer_args(self, obs, mode, seed=0, offset=0, out=None):
         E = obs.shape[0]

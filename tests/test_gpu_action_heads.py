@@ -19,6 +19,8 @@ import torch.nn as nn
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+from philox import philox4x32_10 as _philox4x32_10  # noqa: E402
 K12_FORMS = {"chain": {}, "three_launches": {"PPOAF_FUSED_TAIL": "0"}, "slabs": {"PPOAF_SPLIT_WGRAD": "0"}}
 ACTS = {"relu": nn.ReLU, "leaky": nn.LeakyReLU, "tanh": nn.Tanh}
 
@@ -251,20 +253,6 @@ def test_torch_heads_match_reference_golden_g16(golden, tag):
     np.testing.assert_allclose(glp.cpu().numpy(), g[f"{tag}_dlogp_dlogits"], rtol=1e-4, atol=1e-6)
     np.testing.assert_allclose(gent.cpu().numpy(), g[f"{tag}_dent_dlogits"], rtol=1e-4, atol=1e-6)
     np.testing.assert_array_equal(d.refine_prediction(logits.detach()).cpu().numpy(), g[f"{tag}_refined"])
-
-
-def _philox4x32_10(seed, counters, stream):
-    """Philox4x32-10 as csrc/common.hpp forms it, for an array of 64-bit counters -> its four 32-bit words."""
-    M = np.uint64(0xFFFFFFFF)
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
-    counters = np.asarray(counters, dtype=np.uint64)
-    c0, c1 = counters & M, counters >> np.uint64(32)
-    c2, c3 = np.full_like(counters, stream), np.zeros_like(counters)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & M, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & M
-        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
-    return c0, c1, c2, c3
 
 
 def test_fused_bernoulli_sampler_draws_its_bits():

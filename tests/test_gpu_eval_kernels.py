@@ -5,7 +5,12 @@
     by the bound rule tests/test_gpu_k12_gradients.py states for K12, the discrete heads by their argmax with the
     near-tie rule below --, against planted exact ties, and against the `*_refined` arrays fixture g16 recorded from the
     reference's distribution classes;
-  * ppoaf_eval_scores_step against the numpy restatement (tests/helpers/eval_restatement.py), bit for bit.
+  * ppoaf_eval_scores_step against the numpy restatement (tests/helpers/eval_restatement.py), bit for bit;
+  * K6's own Categorical and Gaussian draws (cat_step_row / gauss_step_row of csrc/action_heads.hpp, which K21 and K19's
+    sample mode share) against the Philox restatement of tests/helpers/philox.py on the float64 forward (section 9).
+    Measured on the MI355X, worst deviation / bound: Categorical, no row left out in any of the four cases, logp <= 0.007,
+    value <= 0.011; Gaussian (out_dim 1, 4, 5, 6, with and without bounds) raw <= 0.024, action <= 0.027, logp <= 0.100,
+    value <= 0.013 -- the device's logf and sincosf stay well inside the rule at these arguments.
 
 Near-tie rule (discrete heads): a logit's bound is 1e-5 |z| + 1e-5 max|z| over the case's float64 logits, so two logits
 are told apart when their float64 gap is at least the sum of their bounds (at most 4e-5 max|z|).  A row may be left out
@@ -293,3 +298,118 @@ def test_scores_kernel_is_the_restatement_bit_for_bit(case):
     assert got["remaining"] == want["remaining"]
     if "never" in c:
         assert got["remaining"] > 0
+
+
+# ------------------------------------------------------------------- 9: K6's draws against the restated Philox block
+def _k6(pol, obs, seed, offset):
+    raw, act, logp, val = pol.step_k6(obs, seed, offset, full=True)
+    torch.cuda.synchronize()
+    return raw.cpu().numpy(), act.cpu().numpy(), logp.double().cpu().numpy(), val.double().cpu().numpy()
+
+
+def _judge(what, got, x64, x32, mask=None):
+    from eval_kernels import k12_bound
+    got, x64, x32 = (np.asarray(t, np.float64) for t in (got, x64, x32))
+    if mask is not None:
+        got, x64, x32 = got[mask], x64[mask], x32[mask]
+    frac = (np.abs(got - x64) / k12_bound(x64, x32)).max()
+    print(f"  {what}: worst deviation / bound = {frac:.3f}")
+    assert np.isfinite(got).all() and frac <= 1.0, (what, frac)
+
+
+@pytest.mark.parametrize("E", [15, 33])
+@pytest.mark.parametrize("out_dim", [2, 8])
+def test_k6_categorical_draw_against_the_restated_philox(out_dim, E):
+    """Row e draws word x of Philox(seed, offset + e, stream 0); the action is the first k with u s < cum_k over the
+    softmax of the float64 logits (s its sum), the log-prob log(clip(p_a / s, eps32, 1 - eps32)).  Near-tie rule: a
+    logit's bound is 1e-5 |z| + 1e-5 max|z|; a row whose u s lies within 2 max_k bound + 1e-6 of a CDF edge is left out
+    (at most 2 rows per case, asserted).  The counter's low word wraps inside the launch."""
+    import philox
+    from eval_kernels import Policy
+    O = 18
+    pol = Policy(40 + out_dim + E, O, 64, 2, out_dim, "categorical", act="tanh", out_gain=1.0, critic_hidden=64)
+    obs = _obs(out_dim * 100 + E, E, O)
+    x = obs.cpu().numpy()
+    seed, offset = 0x1234ABCD5678 + E, 2 ** 32 - 7
+    words = philox.philox4x32_10(seed, philox.counters_u64(offset, np.arange(E)), 0)
+    eps = np.finfo(np.float32).eps
+
+    def restate(dt):
+        z = pol.actor.forward(x.astype(dt), dt)
+        p = np.exp(z - z.max(1, keepdims=True))
+        p = p / p.sum(1, keepdims=True)
+        s, cum = p.sum(1), np.cumsum(p, 1)
+        us = philox.u32_to_unit(words[0]).astype(dt) * s
+        a = np.minimum((us[:, None] >= cum).sum(1), out_dim - 1)
+        gap = np.abs(us[:, None] - cum).min(1)
+        return z, a, gap, p, s
+
+    z64, a64, gap, _, _ = restate(np.float64)
+    _, a32, _, p32, s32 = restate(np.float32)
+    near = gap < 2.0 * _logit_bound(z64).max(1) + 1e-6
+    assert near.sum() <= 2, f"{near.sum()} rows of {E} near a CDF edge"
+    raw, act, logp, val = _k6(pol, obs, seed, offset)
+    print(f"\ncategorical out_dim {out_dim} E {E}: {near.sum()} rows left out, classes drawn {np.unique(act).tolist()}")
+    assert np.array_equal(raw, act)
+    assert np.array_equal(a32[~near], a64[~near]), "the float32 restatement decodes a kept row differently"
+    np.testing.assert_array_equal(act[~near], a64[~near])
+    assert len(np.unique(a64)) > 1
+    lp = lambda dt, p, s, a: np.log(np.clip(p[np.arange(E), a] / s, dt(eps), dt(1.0) - dt(eps)))
+    p64 = np.exp(z64 - z64.max(1, keepdims=True))
+    p64 = p64 / p64.sum(1, keepdims=True)
+    _judge("logp", logp, lp(np.float64, p64, p64.sum(1), a64), lp(np.float32, p32, s32, a64), ~near)
+    _judge("value", val, pol.critic.forward(x)[:, 0], pol.critic.forward(x.astype(np.float32), np.float32)[:, 0])
+
+
+def _gauss_normals(philox, seed, counters, out_dim, dt):
+    """gauss_normals4 of csrc/action_heads.hpp in `dt`: dimensions 4 q .. 4 q + 3 from the block (seed, counter, q) --
+    x an open-0 word and y an angle word give the cos and the sin output, z and w the second pair."""
+    z = np.zeros((len(counters), 4 * ((out_dim + 3) // 4)), dt)
+    two_pi = dt(6.28318530717958647692)
+    for q in range((out_dim + 3) // 4):
+        w = philox.philox4x32_10(seed, counters, q)
+        for pair in (0, 1):
+            r = np.sqrt(dt(-2.0) * np.log(philox.u32_to_unit_open0(w[2 * pair]).astype(dt)))
+            ang = two_pi * philox.u32_to_unit(w[2 * pair + 1]).astype(dt)
+            z[:, 4 * q + 2 * pair], z[:, 4 * q + 2 * pair + 1] = r * np.cos(ang), r * np.sin(ang)
+    return z[:, :out_dim]
+
+
+@pytest.mark.parametrize("bounded", [False, True])
+@pytest.mark.parametrize("out_dim", [1, 4, 5, 6])
+def test_k6_gaussian_draw_against_the_restated_philox(out_dim, bounded):
+    """raw = mean + sd z with z the Box-Muller pairs of the row's Philox blocks (seed, offset + e, q = d / 4), sd =
+    max(softplus(log_std), min_std); action tanh(raw) (scaled to the bounds); the squashed Gaussian's log-prob.  raw,
+    action, log-prob and value by the bound rule, in float64 with the float32 restatement as the floor; no row is left
+    out (the map is continuous)."""
+    import philox
+    from eval_kernels import Policy
+    O, E = 17, 33
+    pol = Policy(60 + out_dim, O, 64, 2, out_dim, "gaussian", act="tanh", bounds=_bounds(out_dim) if bounded else None,
+                 out_gain=1.0, critic_hidden=64)
+    obs = _obs(7 + out_dim, E, O)
+    x = obs.cpu().numpy()
+    seed, offset = 0x1234ABCD5678 + out_dim, 2 ** 32 - 9 if bounded else 977 * out_dim
+    counters = philox.counters_u64(offset, np.arange(E))
+
+    def restate(dt):
+        mean = pol.actor.forward(x.astype(dt), dt)
+        sd = np.maximum(np.log1p(np.exp(pol.actor.log_std.astype(dt))), dt(pol.min_std))
+        raw = mean + sd * _gauss_normals(philox, seed, counters, out_dim, dt)
+        a = np.tanh(raw)
+        slog = np.log(np.maximum(dt(1.0) - a * a, dt(1e-6))).sum(1)
+        act = a
+        if bounded:
+            lo, hi = (v.astype(dt) for v in _bounds(out_dim))
+            act = ((a + dt(1.0)) / dt(2.0)) * (hi - lo) + lo
+        zz = raw - mean
+        l = -(zz * zz) / (dt(2.0) * sd * sd) - np.log(sd) - dt(0.91893853320467274178)
+        return raw, act, np.clip(l, dt(-100.0), dt(100.0)).sum(1) - slog
+
+    r64, r32 = restate(np.float64), restate(np.float32)
+    assert r32[0].dtype == np.float32 and r32[2].dtype == np.float32
+    raw, act, logp, val = _k6(pol, obs, seed, offset)
+    print(f"\ngaussian out_dim {out_dim} bounded {bounded}: max |raw| {np.abs(r64[0]).max():.3g}")
+    for what, got, x64, x32 in (("raw", raw, r64[0], r32[0]), ("action", act, r64[1], r32[1]), ("logp", logp, r64[2], r32[2])):
+        _judge(what, got, x64, x32)
+    _judge("value", val, pol.critic.forward(x)[:, 0], pol.critic.forward(x.astype(np.float32), np.float32)[:, 0])
