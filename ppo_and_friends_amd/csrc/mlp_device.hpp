@@ -221,6 +221,66 @@ __device__ __forceinline__ f32x4 mfma_rows_x_lines(const float* __restrict__ A, 
     }
     return acc0 + acc1;
 }
+// mfma_rows_x_lines (its operands, its MFMAs, their order: the same bits) that also REQUESTS the dgrad set of the tile
+// (n0, Wd) into `raw` as it goes (load_dgrad_frags' loads and layout): chunks 2 q and 2 q + 1 -- eight loads -- ahead of
+// the MFMAs of line q, behind the LDS reads those wait for.  raw[0 .. 2 q + 3] have gone to the line slots when line q
+// begins, so the two chunks are free there; nothing is requested behind the last MFMA.  For a wave that loads alone: eight
+// waves doing this ask for more than the CU's L1 delivers in a layer, and the issue of the loads backs up into the loop.
+// The scheduling barriers hold the loads where they are written.
+template <int HT>
+__device__ __forceinline__ f32x4 mfma_rows_x_lines_paced(const float* __restrict__ A, int HS, int lane, float4 (&raw)[HT],
+                                                         float init, float* __restrict__ scratch, const float* __restrict__ Wd,
+                                                         int n0) {
+    constexpr int NL = HT / 2, H = 16 * HT;
+    const float* arow = A + (lane & 15) * HS + 4 * (lane >> 4);
+    float* wr = scratch + (lane >> 3) * kLineRow + 4 * (lane & 7);
+    const float* rd = scratch + (lane & 15) * kLineRow + 4 * (lane >> 4);
+    const float* wd = Wd + (long)(4 * (lane >> 4)) * H + n0 + (lane & 15);
+    f32x4 acc0 = {init, init, init, init};
+    f32x4 acc1 = {0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<float4*>(wr) = raw[0];
+    *reinterpret_cast<float4*>(wr + 8 * kLineRow) = raw[1];
+    if (NL > 1) {
+        *reinterpret_cast<float4*>(wr + kLineSlot) = raw[2];
+        *reinterpret_cast<float4*>(wr + kLineSlot + 8 * kLineRow) = raw[3];
+    }
+    __builtin_amdgcn_wave_barrier();
+    float4 f0 = *reinterpret_cast<const float4*>(rd);
+    float4 f1 = *reinterpret_cast<const float4*>(rd + 16);
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+        const int slot = (q & 1) * kLineSlot;
+        float4 g0 = f0, g1 = f1;
+        if (q + 1 < NL) {
+            g0 = *reinterpret_cast<const float4*>(rd + (kLineSlot - slot));
+            g1 = *reinterpret_cast<const float4*>(rd + (kLineSlot - slot) + 16);
+        }
+        const float4 a0 = *reinterpret_cast<const float4*>(arow + 32 * q);
+        const float4 a1 = *reinterpret_cast<const float4*>(arow + 32 * q + 16);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const float* wp = wd + (long)(16 * (2 * q + p)) * H;
+            raw[2 * q + p] = make_float4(wp[0], wp[H], wp[2 * H], wp[3 * H]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, f0.x, acc0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, f0.y, acc0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, f0.z, acc0, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, f0.w, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.x, f1.x, acc1, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.y, f1.y, acc1, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.z, f1.z, acc1, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1.w, f1.w, acc1, 0, 0, 0);
+        __builtin_amdgcn_wave_barrier();
+        if (q + 2 < NL) {                                 // this line's slot is free: its fragments were read an iteration ago
+            *reinterpret_cast<float4*>(wr + slot) = raw[2 * q + 4];
+            *reinterpret_cast<float4*>(wr + slot + 8 * kLineRow) = raw[2 * q + 5];
+        }
+        f0 = g0; f1 = g1;
+    }
+    return acc0 + acc1;
+}
 
 // Weight gradient of one 16-row block of outputs: dW[m0+.., i] = sum_s D[s][m0+..] * Bsrc[s][i] for
 // i < n_valid (n tiles of 16 columns), K = the 16 rows of the workgroup.  Both operands come from LDS.

@@ -498,6 +498,9 @@ extern "C" int ppoaf_ppo_update_adam_exchanged(const ppoaf_ppo_update_args_t* ar
 extern "C" int ppoaf_debug_read_stamps(unsigned long long* out /* host [32] */) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ppo_update_stamps), sizeof(unsigned long long) * 32) == hipSuccess ? 0 : -2;
 }
+extern "C" int ppoaf_debug_read_hidden_stamps(unsigned long long* out /* host [2][8][8] */) {
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ppo_hidden_stamps), sizeof(unsigned long long) * 128) == hipSuccess ? 0 : -2;
+}
 #endif
 
 extern "C" int ppoaf_minibatch_moments(const float* data, const int64_t* perm, const int32_t* row_map,

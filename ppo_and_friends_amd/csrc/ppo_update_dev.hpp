@@ -29,9 +29,29 @@ static __device__ unsigned long long g_ppo_update_stamps[2][16];
     } while (0)
 #define PPOAF_STAMP(k) PPOAF_STAMP_AT(0, k, 0)
 #define PPOAF_STAMP_W(k, w) PPOAF_STAMP_AT(1, k, 64 * (w))
+// The hidden forward layers of the row tile, every wave of the stamped workgroup (tools/phase_stamps.py): the clock is read
+// into a register where the event is (PPOAF_HSTAMP, held in place by scheduling barriers) and stored behind the layer's
+// barrier (PPOAF_HSTAMP_FLUSH) -- a store between the layer's own loads would queue with them.
+static __device__ unsigned long long g_ppo_hidden_stamps[2][8][8];       // [layer][wave][event]
+#define PPOAF_HSTAMP_DECL unsigned long long hstamp_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define PPOAF_HSTAMP(k)                                                                  \
+    do {                                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                               \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(hstamp_[k])::"memory"); \
+        __builtin_amdgcn_sched_barrier(0);                                               \
+    } while (0)
+#define PPOAF_HSTAMP_FLUSH(layer)                                                        \
+    do {                                                                                 \
+        if (blockIdx.x == PPOAF_STAMP_BLOCK && (threadIdx.x & 63) == 0) {                \
+            for (int k_ = 0; k_ < 8; ++k_) g_ppo_hidden_stamps[layer][threadIdx.x >> 6][k_] = hstamp_[k_]; \
+        }                                                                                \
+    } while (0)
 #else
 #define PPOAF_STAMP(k) do {} while (0)
 #define PPOAF_STAMP_W(k, w) do {} while (0)
+#define PPOAF_HSTAMP_DECL do {} while (0)
+#define PPOAF_HSTAMP(k) do {} while (0)
+#define PPOAF_HSTAMP_FLUSH(layer) do {} while (0)
 #endif
 
 // The instantiated (actor width, critic width) pairs of K6+K7 (policy_step.hip) and K12 (fwd_bwd, the wgrad launch, the

@@ -142,6 +142,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     const long sp_plane = SPLIT ? (long)u.sp.Bp * H : 0;
 
     PPOAF_STAMP(0);
+    PPOAF_HSTAMP_DECL;
     // ---- LDS carve (all offsets multiples of 16 B)
     float* smem = reinterpret_cast<float*>(ppo_update_smem);
     int* sRow = reinterpret_cast<int*>(smem);                 // [16]
@@ -165,6 +166,8 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     // its registers are refilled with the dgrad fragments of the backward pass (W2 first, then W1).  Every
     // weight load is then in flight for at least two phases -- including the cold first touch after the
     // Adam kernel rewrote the bucket -- instead of one barrier.
+    // (TABLES: the dgrad sets are not requested behind the forward MFMAs but where the wave's issue holds nobody up; see
+    //  the hidden forward layers below.)
     const bool has_tile = HT >= kNW || wave < HT;          // waves beyond the tile count idle in MFMA phases (H < 128)
     static_assert(!TABLES || HT <= kNW, "deep prefetch: one output tile per wave");
     const bool deep = TABLES || (depth == 3 && HT <= kNW);   // (TABLES: the caller has checked depth == 3)
@@ -469,10 +472,38 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     PPOAF_STAMP(3);
 
     // ---- hidden layers forward; the next phase's fragments are requested before each barrier
+    // (lines of text in the assembly: tools/prologue_isa.py reads the TABLES flavour's hidden layers between them)
+    if constexpr (TABLES) asm volatile("; ppoaf_rowtile_hidden_fwd_begin" ::: "memory");
     for (int l = 1; l < depth; ++l) {
+        if constexpr (TABLES) asm volatile("; ppoaf_rowtile_hidden_layer_begin" ::: "memory");
         const float* Hp = sH + (long)(l - 1) * kRows * HS;
         float* Hc = sH + (long)l * kRows * HS;
         if (SPLIT) publish_begin(Hp, u.sp.hbuf[which] + (long)(l - 1) * sp_plane);     // h_{l-1}: the K-panel of dW_l
+        PPOAF_HSTAMP(0);
+        if constexpr (TABLES) {
+            // One output tile per wave, and no request for a dgrad set behind the layer's MFMAs: a wave issues in order, and
+            // 32 value-by-value loads per wave between the MFMAs and the epilogue stood in front of the layer's barrier.
+            // Waves 1-7 ask where they are parked anyway (below: the output layer, the head); wave 0 runs the head, so it
+            // asks through its own MFMA loops, where nobody else is loading.
+            if (has_tile) {
+                const int o = wave * 16 + (lane & 15);
+                const float bv = sBias[l * H + o];
+                f32x4 acc;
+                if (wave == 0) {
+                    if (l == 1) acc = mfma_rows_x_lines_paced<HT>(Hp, HS, lane, fr, bv, sScr, P + offW(2), wave * 16);
+                    else acc = mfma_rows_x_lines_paced<HT>(Hp, HS, lane, fr2, bv, sScr, P + offW(1), wave * 16);
+                } else {
+                    acc = l == 1 ? mfma_rows_x_lines<HT>(Hp, HS, lane, fr, bv, sScr) : mfma_rows_x_lines<HT>(Hp, HS, lane, fr2, bv, sScr);
+                }
+                PPOAF_HSTAMP(1);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
+                asm volatile("; ppoaf_rowtile_hidden_epilogue_end" ::: "memory");
+            }
+            if (SPLIT) publish_end(u.sp.hbuf[which] + (long)(l - 1) * sp_plane);
+            PPOAF_HSTAMP(3);
+            PPOAF_HSTAMP(2);
+        } else {
         for (int nt = wave; nt < HT; nt += kNW) {
             const int o = nt * 16 + (lane & 15);
             f32x4 acc;
@@ -496,12 +527,21 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
         }
         if (SPLIT) publish_end(u.sp.hbuf[which] + (long)(l - 1) * sp_plane);
+        }
         __syncthreads();
+        PPOAF_HSTAMP(4);
+        PPOAF_HSTAMP_FLUSH(l - 1);
     }
     PPOAF_STAMP(4);
     const float* Hlast = sH + (long)(depth - 1) * kRows * HS;
 
     // ---- output layer (out_dim <= 8): VALU from LDS + 16-lane reductions
+    if constexpr (TABLES) {                            // waves 4-7 have nothing to do in this phase: both their dgrad sets
+        if (has_tile && wave >= 4) {
+            load_dgrad_frags<HT>(P + offW(2), wave * 16, lane, fr);
+            load_dgrad_frags<HT>(P + offW(1), wave * 16, lane, fr2);
+        }
+    }
     if (tid < 256) {
         const int s = tid >> 4, part = tid & 15;
         for (int k = 0; k < out_dim; ++k) {
@@ -522,6 +562,12 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
         ppo_head_rows(u, which, out_dim, P + nd.log_std_off, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
         if constexpr (TABLES) asm volatile("; ppoaf_rowtile_head_rows_end");
         PPOAF_STAMP_W(0, 0);
+    }
+    if constexpr (TABLES) {                            // waves 1-3 are parked at the barrier below while wave 0 runs the head
+        if (has_tile && wave >= 1 && wave < 4) {
+            load_dgrad_frags<HT>(P + offW(2), wave * 16, lane, fr);
+            load_dgrad_frags<HT>(P + offW(1), wave * 16, lane, fr2);
+        }
     }
     __syncthreads();
     if constexpr (TABLES) asm volatile("; ppoaf_rowtile_middle_begin");
@@ -558,6 +604,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     if constexpr (TABLES) asm volatile("; ppoaf_rowtile_middle_end");
     __syncthreads();
     PPOAF_STAMP(7);
+    if constexpr (TABLES) asm volatile("; ppoaf_rowtile_hidden_bwd_begin" ::: "memory");
 
     // ---- hidden layers backward: wgrad + bias grad + dgrad; `fr` holds this wave's dgrad fragments
     float* Dc = sD0;

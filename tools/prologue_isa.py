@@ -310,6 +310,93 @@ def middle_report(ins):
     return {"head_rows": scan(MARK_HEAD_ROWS), "middle": scan(MARK_MIDDLE)}
 
 
+# ---- the hidden forward layers of the row-tile body (tests/test_k12_hidden_isa.py).  The TABLES flavour marks the start of
+#      the hidden forward, of each of its layers, the end of a layer's epilogue writes and the start of the hidden backward.
+MARK_HIDDEN = ("ppoaf_rowtile_hidden_fwd_begin", "ppoaf_rowtile_hidden_bwd_begin")
+MARK_LAYER = ("ppoaf_rowtile_hidden_layer_begin", "ppoaf_rowtile_hidden_epilogue_end")
+_LDS_WRITE = re.compile(r"^ds_(write|store)")
+
+
+def _reachable(cfg, start, stop):
+    """Every (block, position) some path executes from `start` on, up to (not including) the first instruction on that
+    path that `stop` accepts."""
+    seen, todo = set(), [start]
+    while todo:
+        b, pos = todo.pop()
+        while pos < len(cfg.blocks[b]) and (b, pos) not in seen and not stop(*cfg.blocks[b][pos]):
+            seen.add((b, pos))
+            pos += 1
+        if pos == len(cfg.blocks[b]):
+            todo.extend((s, 0) for s in cfg.succ[b] if (s, 0) not in seen)
+    return seen
+
+
+def _phase_of(cfg, start, stop):
+    """{(block, position): barriers passed} for everything some path executes from `start` up to the first instruction
+    `stop` accepts: which barrier-delimited phase an instruction belongs to (the fewest barriers, should paths disagree)."""
+    phase, todo = {}, [(start[0], start[1], 0)]
+    while todo:
+        b, pos, n = todo.pop()
+        while pos < len(cfg.blocks[b]) and phase.get((b, pos), 1 << 30) > n and not stop(*cfg.blocks[b][pos]):
+            phase[(b, pos)] = n
+            n += cfg.blocks[b][pos][0] == "s_barrier"
+            pos += 1
+        if pos == len(cfg.blocks[b]):
+            todo.extend((s, 0, n) for s in cfg.succ[b])
+    return phase
+
+
+def kernel_scratch_bytes(asm_path, kernel):
+    """`; ScratchSize: N` of the kernel's resource comment (bytes of scratch memory per lane)."""
+    tagm, inside = mangled(kernel), False
+    with open(asm_path) as fh:
+        for line in fh:
+            if not inside:
+                inside = line.startswith("_ZN5ppoaf") and tagm in line.split(":")[0]
+            elif line.startswith("; ScratchSize:"):
+                return int(line.split(":")[1])
+    raise KeyError(f"{kernel}: no ScratchSize line in {asm_path}")
+
+
+def hidden_report(ins):
+    """fwd_bwd, TABLES flavour, one entry per network:
+      "late_loads": per hidden forward layer (in text order), the vector-memory loads that some path executes behind the
+          layer's last MFMA and ahead of an LDS write of its epilogue -- a load from which an LDS write of the layer can be
+          reached without passing an MFMA;
+      "layer_mfmas": the MFMAs of each layer (a layer without any would make the line above empty for nothing);
+      "dgrad_loads": the single-dword vector loads between the start of the hidden forward and the start of the hidden
+          backward, the head's row part left out (its own loads are not weight requests), per barrier-delimited phase
+          [hidden layer 1, hidden layer 2, output layer, head, output backward]: the two dgrad sets, which are the only
+          weights this kernel fetches value by value."""
+    cfg = Cfg(ins)
+    is_mark = lambda name: (lambda op, args: op == "marker" and args == name)
+    begins = cfg.find_all(is_mark(MARK_HIDDEN[0]))
+    out = []
+    for b0 in begins:
+        window = _reachable(cfg, (b0[0], b0[1] + 1), is_mark(MARK_HIDDEN[1]))
+        at = lambda p: cfg.blocks[p[0]][p[1]]
+        head = set()
+        for h in (p for p in window if is_mark(MARK_HEAD_ROWS[0])(*at(p))):
+            head |= _reachable(cfg, (h[0], h[1] + 1), is_mark(MARK_HEAD_ROWS[1]))
+        phase = _phase_of(cfg, (b0[0], b0[1] + 1), is_mark(MARK_HIDDEN[1]))
+        by_phase = [0] * (max(phase.values()) + 1)
+        for p in window - head:
+            if re.match(r"^(global|buffer|flat)_load_dword$", at(p)[0]):
+                by_phase[phase[p]] += 1
+        late, mfmas = [], []
+        for lb in sorted(p for p in window if is_mark(MARK_LAYER[0])(*at(p))):
+            layer = _reachable(cfg, (lb[0], lb[1] + 1), is_mark(MARK_LAYER[1]))
+            mfmas.append(sum(at(p)[0].startswith("v_mfma") for p in layer))
+            bad = []
+            for p in sorted(q for q in layer if _VLOAD.match(at(q)[0])):
+                tail = _reachable(cfg, (p[0], p[1] + 1), lambda op, args: op.startswith("v_mfma") or is_mark(MARK_LAYER[1])(op, args))
+                if any(_LDS_WRITE.match(at(q)[0]) for q in tail):
+                    bad.append(" ".join(at(p)))
+            late.append(bad)
+        out.append({"layers": len(late), "late_loads": late, "layer_mfmas": mfmas, "dgrad_loads": by_phase})
+    return out
+
+
 def describe(kernel, ins):
     print(f"{kernel}: {sum(op not in ('label', 'marker') for op, _ in ins)} instructions")
     n, _ = scalar_waits_before_vmem(ins)
@@ -333,6 +420,10 @@ def describe(kernel, ins):
         for name, m in middle_report(ins).items():
             print(f"  {name}: {m['windows']} windows (closed: {m['closed']}), {m['instructions']} instructions, "
                   f"{len(m['global_stores'])} global stores, {len(m['permutes'])} ds_(b)permute, {m['barriers']} barriers")
+        for i, h in enumerate(hidden_report(ins)):
+            print(f"  hidden forward, network {i}: {h['layers']} layers of {h['layer_mfmas']} MFMAs, vector loads between a "
+                  f"layer's last MFMA and its epilogue's LDS writes: {[len(x) for x in h['late_loads']]}; dgrad dword loads up "
+                  f"to the hidden backward: {h['dgrad_loads']}")
 
 
 def main(argv):
