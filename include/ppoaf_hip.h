@@ -1182,6 +1182,45 @@ int ppoaf_lstm_policy_step(const ppoaf_lstm_policy_step_args_t* args, ppoaf_stre
 int ppoaf_lstm_policy_step_check(const ppoaf_lstm_policy_step_args_t* args);
 
 /* ------------------------------------------------------------------------ *
+ * K21, block form: ppoaf_lstm_policy_step reading the env's tensors where they lie
+ * `args` as for ppoaf_lstm_policy_step, modes PPOAF_LSTM_STEP and PPOAF_LSTM_CRITIC_NEXT only (MASK reads no observation
+ * and INFER runs on gathered rows), except that args->obs / args->critic_obs are not read: row r of the launch
+ * (0 <= r < args->E = n_blocks * rows_per_block) is row r % rows_per_block of block r / rows_per_block of `obs` and of
+ * `critic_obs` -- block a of an agent-major env tensor [A * E, width] is `base + a * E * width`, of a dict env the
+ * tensor of the member's a-th agent.  Everything else stays indexed by the launch row r: the networks' (h, c), the
+ * buffer row and the four hidden rows.
+ *   STEP         the buffer row (raw actions, actions, log-probs, values, both observation copies, the four hidden rows)
+ *                and the stepped (h, c) are written exactly as by ppoaf_lstm_policy_step; the env action of row r ALSO
+ *                goes to row r % rows_per_block of env_action[r / rows_per_block] (int64 [rows_per_block] for the
+ *                categorical head, float32 [rows_per_block, actor.out_dim] for the Gaussian one): the env's combined
+ *                action tensor or its per-agent tensors, so env.step needs no index_put.
+ *   CRITIC_NEXT  only `critic_obs` of the table is read (obs / env_action may be NULL); commit and boot_value_out as in
+ *                the tensor form.  args->terminated, when given, holds the PER-ENV bytes [rows_per_block] -- the agents
+ *                of an env end together -- and row r is zeroed where terminated[r % rows_per_block] is set: the env's
+ *                flags are taken as handed, without a copy per agent.
+ * Philox counters, head code and tile code are ppoaf_lstm_policy_step's, so for equal inputs, seed and offset every
+ * output is bitwise its output on the gathered rows.  A 16-row tile may straddle two blocks (three and more for
+ * rows_per_block < 8): row addresses are computed per row.  Loads and stores through the table are scalar, so a base
+ * needs its element's alignment only (float32: 4 bytes, int64 actions: 8) -- an env's [E, width] blocks lie
+ * E * width * 4 bytes apart, which 16 need not divide.  Refused, before any launch: n_blocks outside
+ * [1, PPOAF_ROW_BLOCKS_MAX], args->E != n_blocks * rows_per_block, a base the mode reads or writes that is null or not
+ * aligned to its element, a mode other than the two, and whatever ppoaf_lstm_policy_step_check refuses;
+ * rows_per_block == 0: PPOAF_OK without a launch.  ppoaf_lstm_policy_step_blocks_check runs the same checks on the host
+ * and launches nothing.  Plain vector stores; one lane per row for the heads; no workgroup waits on another.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t n_blocks;
+    int64_t rows_per_block;
+    const float* obs[PPOAF_ROW_BLOCKS_MAX];
+    const float* critic_obs[PPOAF_ROW_BLOCKS_MAX];
+    void* env_action[PPOAF_ROW_BLOCKS_MAX];
+} ppoaf_lstm_step_blocks_t;
+
+int ppoaf_lstm_policy_step_blocks(const ppoaf_lstm_policy_step_args_t* args, const ppoaf_lstm_step_blocks_t* blocks,
+                                  ppoaf_stream_t stream);
+int ppoaf_lstm_policy_step_blocks_check(const ppoaf_lstm_policy_step_args_t* args, const ppoaf_lstm_step_blocks_t* blocks);
+
+/* ------------------------------------------------------------------------ *
  * K22  one mini-batch of the PPO update of an LSTM actor / critic pair as three launches
  * replaces, per mini-batch of PPO._ppo_batch_train    ppo.py:2292-2469
  *          the window gather of the dataset           utils/episode_info.py:775-809,940-987

@@ -266,6 +266,12 @@ class StepBlocks(C.Structure):
                 ("critic_obs", C.c_void_p * ROW_BLOCKS_MAX), ("env_action", C.c_void_p * ROW_BLOCKS_MAX)]
 
 
+class LstmStepBlocks(C.Structure):
+    """ppoaf_lstm_step_blocks_t (include/ppoaf_hip.h)."""
+    _fields_ = [("n_blocks", C.c_int32), ("rows_per_block", C.c_int64), ("obs", C.c_void_p * ROW_BLOCKS_MAX),
+                ("critic_obs", C.c_void_p * ROW_BLOCKS_MAX), ("env_action", C.c_void_p * ROW_BLOCKS_MAX)]
+
+
 class MatStepBlocks(C.Structure):
     """ppoaf_mat_step_blocks_t (include/ppoaf_hip.h)."""
     _fields_ = [("n_blocks", C.c_int32), ("slot_agent", C.c_int32 * ROW_BLOCKS_MAX), ("critic_obs", C.c_void_p * ROW_BLOCKS_MAX),
@@ -389,6 +395,8 @@ SIGNATURES = {
     "ppoaf_lstm_wgrad": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),
     "ppoaf_lstm_policy_step": (C.c_int, [C.POINTER(LstmPolicyStepArgs), _ptr]),
     "ppoaf_lstm_policy_step_check": (C.c_int, [C.POINTER(LstmPolicyStepArgs)]),
+    "ppoaf_lstm_policy_step_blocks": (C.c_int, [C.POINTER(LstmPolicyStepArgs), C.POINTER(LstmStepBlocks), _ptr]),
+    "ppoaf_lstm_policy_step_blocks_check": (C.c_int, [C.POINTER(LstmPolicyStepArgs), C.POINTER(LstmStepBlocks)]),
     "ppoaf_lstm_update_check": (C.c_int, [C.POINTER(LstmUpdateArgs), C.c_int32]),
     "ppoaf_lstm_update_workspace_floats": (C.c_int, [C.POINTER(LstmUpdateArgs), C.POINTER(C.c_int64)]),
     "ppoaf_lstm_update_fwd_bwd": (C.c_int, [C.POINTER(LstmUpdateArgs), _ptr]),

@@ -116,14 +116,36 @@ inline LstmArgs lstm_args_of(const ppoaf_lstm_desc_t* d) {
 
 __device__ __forceinline__ float sigm(float z) { return 1.f / (1.f + expf(-z)); }
 
+// Where lstm_rows_forward finds element k of step t of row n of its input.  LstmXDense: a.x [N, S, I], the form K18, K22
+// and the tensor form of K21 instantiate -- an empty object whose load() is the expression the staging loop has always
+// held, so those instantiations keep their code.  LstmXBlocks (the block form of K21, always S = 1): the rows lie in a
+// table of up to PPOAF_ROW_BLOCKS_MAX row blocks of `rows_per_block` rows each, row n being row n % rows_per_block of
+// block n / rows_per_block; a 16-row tile may straddle blocks, so the address is formed per row.  N <= 2^27 (checked by
+// the entry point), so the division is a 32-bit one.
+struct LstmXDense {
+    __device__ __forceinline__ float load(const LstmArgs& a, long n, int S, int t, int I, int k) const {
+        return a.x[(n * S + t) * I + k];
+    }
+};
+struct LstmXBlocks {
+    const float* const* blocks;      // (points into the kernel arguments)
+    unsigned rows_per_block;
+    __device__ __forceinline__ const float* row(const long n, const int I) const {
+        const unsigned b = (unsigned)n / rows_per_block;
+        return blocks[b] + (long)((unsigned)n - b * rows_per_block) * I;
+    }
+    __device__ __forceinline__ float load(const LstmArgs&, long n, int, int, int I, int k) const { return row(n, I)[k]; }
+};
+
 // Rows [16 g, 16 g + 16) of the network: S recurrent steps, LayerNorm, activation, feed-forward head.  The workgroup has
 // H / 16 waves and wave w owns the hidden slice [16 w, 16 w + 16) of all four gates (see lstm.hip).  STEP = false (K18):
 // the outputs go to a.out.  STEP = true (K21): they stay in LDS -- the returned pointer, row stride kLFS, valid after
 // the call for every thread -- for the one-lane-per-row heads; the final (h, c) also go to a.hn_row / a.cn_row, and
 // a.hn / a.cn (which may be a.h0 / a.c0: a workgroup reads only its own 16 rows, all of them before its first barrier,
-// and writes them after its last recurrent step) are written only when *a.commit says so.
-template <int H, bool STEP>
-__device__ __forceinline__ const float* lstm_rows_forward(const LstmArgs& a, const int g_tile) {
+// and writes them after its last recurrent step) are written only when *a.commit says so.  XRows: where the input rows
+// lie (LstmXDense / LstmXBlocks above).
+template <int H, bool STEP, class XRows = LstmXDense>
+__device__ __forceinline__ const float* lstm_rows_forward(const LstmArgs& a, const int g_tile, const XRows xrows = XRows()) {
     constexpr int HT = H / 16, NT = HT * 64, HS = H + 4, XS = kLMaxIn + 4;
     static_assert(2 * kLRows * XS >= kLRows * HS + 2 * kLRows * kLFS, "head buffers reuse the x buffers");
     __shared__ float xs[2 * kLRows * XS];
@@ -152,7 +174,7 @@ __device__ __forceinline__ const float* lstm_rows_forward(const LstmArgs& a, con
         for (int e = tid; e < kLRows * Ip; e += NT) {
             const int r = e / Ip, k = e - r * Ip;
             const long n = r0 + r;
-            dst[r * XS + k] = (n < N && k < I) ? a.x[(n * S + t) * I + k] : 0.f;
+            dst[r * XS + k] = (n < N && k < I) ? xrows.load(a, n, S, t, I, k) : 0.f;
         }
     };
     for (int e = tid; e < kLRows * H; e += NT) {

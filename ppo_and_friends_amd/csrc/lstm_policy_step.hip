@@ -15,6 +15,10 @@
 // and feed-forward head are K18's forward at S = 1 (lstm_device.hpp: lstm_rows_forward), the heads run one lane per row
 // on K6's / K19's functions (action_heads.hpp).  The networks' (h, c) are stepped IN PLACE: a workgroup reads only its
 // own 16 rows, all before its first barrier, and writes them after the recurrent step.
+//
+// Block form (ppoaf_lstm_policy_step_blocks, STEP and CRITIC_NEXT): the observations are read where the env left them,
+// through a table of row blocks in the kernel arguments, and STEP also writes the env's action blocks -- a member of a
+// multi-policy run then needs no gather and no index_put (PPO.rollout, DESIGN.md "LSTM members").
 #include <cstddef>
 
 #include "action_heads.hpp"
@@ -37,6 +41,17 @@ struct LstmStepDev {
     float* obs_out; float* critic_obs_out;
     const unsigned char* terminated;
     float* stored[4];                              // the step's hidden rows, for the zeroing
+};
+
+// The block form (ppoaf_lstm_policy_step_blocks): row r of the launch is row r % rows_per_block of block
+// r / rows_per_block of `obs` / `critic_obs`, its env action (STEP) also goes to that row of `env_action`, and
+// `terminated` (CRITIC_NEXT) holds one byte per row of a block.  The pointers travel in the kernel arguments.
+struct LstmStepBlocks {
+    const float* obs[PPOAF_ROW_BLOCKS_MAX];
+    const float* critic_obs[PPOAF_ROW_BLOCKS_MAX];
+    void* env_action[PPOAF_ROW_BLOCKS_MAX];
+    unsigned rows_per_block;
+    int action_elems;                              // float32 elements of a Gaussian row's env action; int64: 1
 };
 
 template <int H>
@@ -102,6 +117,74 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_policy_step_kernel(const Lst
     }
 }
 
+// The block form of lstm_policy_step_kernel, STEP and CRITIC_NEXT only (the entry point refuses the other modes).  The
+// tensor form keeps its own text and with it its code; both instantiate lstm_rows_forward and call the same head
+// functions with the same row number, so for equal inputs they store equal bits.
+template <int H>
+__global__ __launch_bounds__(H / 16 * 64) void lstm_policy_step_blocks_kernel(const LstmStepDev u, const LstmStepBlocks tb) {
+    constexpr int NT = H / 16 * 64;
+    const int tid = threadIdx.x;
+    int which = 1, g = blockIdx.x;
+    if (u.mode == PPOAF_LSTM_STEP) {
+        const int b = blockIdx.x;
+        which = (b >> 2) & 1;
+        g = ((b >> 3) << 2) | (b & 3);
+    }
+    if (g >= u.n_wg) return;
+    const long e0 = (long)g * kLRows;
+    const LstmArgs& a = u.net[which];
+    const LstmXBlocks xr{which == 0 ? tb.obs : tb.critic_obs, tb.rows_per_block};
+    float* oc = which == 0 ? u.obs_out : u.critic_obs_out;
+    if (oc) {
+        const int I = a.I;
+        for (int i = tid; i < kLRows * I; i += NT) {
+            const int r = i / I, k = i - r * I;
+            if (e0 + r < u.E) oc[(e0 + r) * I + k] = xr.row(e0 + r, I)[k];
+        }
+    }
+    const float* sOut = lstm_rows_forward<H, true, LstmXBlocks>(a, g, xr);
+
+    // heads: one lane per env row
+    if (tid < kLRows && e0 + tid < u.E) {
+        const float* zr = sOut + tid * kLFS;
+        const long e = e0 + tid;
+        if (which == 1) {
+            float v = zr[0];
+            if (u.normalize_values) v = u.vn_mean[0] + v * sqrtf(u.vn_var[0] + 1e-8f);   // misc.py:124-128
+            u.value_out[e] = v;
+        } else {
+            // the row's env action, as this lane stores it in the buffer row, also into the env's action tensor
+            const unsigned b = (unsigned)e / tb.rows_per_block;
+            const long r = (long)((unsigned)e - b * tb.rows_per_block);
+            if (u.head_kind == PPOAF_HEAD_CATEGORICAL) {
+                cat_step_row(zr, a.O, u.forced_raw_action, e, u.seed, u.offset, u.raw_action_out, u.action_out, u.logp_out);
+                reinterpret_cast<int64_t*>(tb.env_action[b])[r] = reinterpret_cast<const int64_t*>(u.action_out)[e];
+            } else {
+                gauss_step_row(zr, a.O, u.log_std, u.min_std, u.act_lo, u.act_hi, u.forced_raw_action, e, u.seed, u.offset,
+                               u.raw_action_out, u.action_out, u.logp_out);
+                const int n = tb.action_elems;
+                const float* src = reinterpret_cast<const float*>(u.action_out) + e * n;
+                float* dst = reinterpret_cast<float*>(tb.env_action[b]) + r * n;
+                for (int k = 0; k < n; ++k) dst[k] = src[k];
+            }
+        }
+    }
+
+    // CRITIC_NEXT: the rows the step stored for the envs that terminated at it are zeroed; the env's byte serves each of
+    // its agents' rows
+    if (u.terminated && u.mode == PPOAF_LSTM_CRITIC_NEXT) {
+        for (int i = tid; i < kLRows * H; i += NT) {
+            const int r = i / H;
+            const long n = e0 + r;
+            if (n < u.E && u.terminated[(unsigned)n % tb.rows_per_block]) {
+                const long at = n * H + (i - r * H);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) u.stored[q][at] = 0.f;
+            }
+        }
+    }
+}
+
 template <int H>
 static int launch_lstm_step(const LstmStepDev& u, hipStream_t s) {
     const unsigned grid = u.mode == PPOAF_LSTM_STEP ? 8u * (unsigned)((u.n_wg + 3) / 4) : (unsigned)u.n_wg;
@@ -109,7 +192,15 @@ static int launch_lstm_step(const LstmStepDev& u, hipStream_t s) {
     return check_launch("lstm_policy_step");
 }
 
-static int check_step_args(const ppoaf_lstm_policy_step_args_t* a) {
+template <int H>
+static int launch_lstm_step_blocks(const LstmStepDev& u, const LstmStepBlocks& tb, hipStream_t s) {
+    const unsigned grid = u.mode == PPOAF_LSTM_STEP ? 8u * (unsigned)((u.n_wg + 3) / 4) : (unsigned)u.n_wg;
+    hipLaunchKernelGGL(lstm_policy_step_blocks_kernel<H>, dim3(grid), dim3(H / 16 * 64), 0, s, u, tb);
+    return check_launch("lstm_policy_step_blocks");
+}
+
+// with_obs: obs / critic_obs are read from `a` (the block form reads them through its table)
+static int check_step_args(const ppoaf_lstm_policy_step_args_t* a, const bool with_obs = true) {
     PPOAF_REQUIRE(a, "lstm_policy_step: null args");
     PPOAF_REQUIRE(a->mode >= PPOAF_LSTM_STEP && a->mode <= PPOAF_LSTM_MASK,
                   "lstm_policy_step: mode=%d (0 step, 1 critic next, 2 infer, 3 mask)", a->mode);
@@ -128,12 +219,12 @@ static int check_step_args(const ppoaf_lstm_policy_step_args_t* a) {
     PPOAF_REQUIRE((a->act_lo == nullptr) == (a->act_hi == nullptr), "lstm_policy_step: give both action bounds or neither");
     const bool rows = a->actor_hidden_out && a->actor_cell_out && a->critic_hidden_out && a->critic_cell_out;
     if (a->mode == PPOAF_LSTM_STEP) {
-        PPOAF_REQUIRE(a->obs && a->critic_obs && a->actor_h && a->actor_c && a->critic_h && a->critic_c,
+        PPOAF_REQUIRE((!with_obs || (a->obs && a->critic_obs)) && a->actor_h && a->actor_c && a->critic_h && a->critic_c,
                       "lstm_policy_step: STEP: null observation / state pointer");
         PPOAF_REQUIRE(a->raw_action_out && a->action_out && a->logp_out && a->value_out && rows,
                       "lstm_policy_step: STEP needs the row-t outputs (actions, log-probs, values, four hidden rows)");
     } else if (a->mode == PPOAF_LSTM_CRITIC_NEXT) {
-        PPOAF_REQUIRE(a->critic_obs && a->critic_h && a->critic_c && a->boot_value_out && a->commit,
+        PPOAF_REQUIRE((!with_obs || a->critic_obs) && a->critic_h && a->critic_c && a->boot_value_out && a->commit,
                       "lstm_policy_step: CRITIC_NEXT: null critic_obs / critic state / boot_value_out / commit");
         PPOAF_REQUIRE(!a->terminated || rows, "lstm_policy_step: terminated given without the four hidden rows");
     } else if (a->mode == PPOAF_LSTM_INFER) {
@@ -147,6 +238,30 @@ static int check_step_args(const ppoaf_lstm_policy_step_args_t* a) {
     if (a->mode == PPOAF_LSTM_STEP || a->mode == PPOAF_LSTM_CRITIC_NEXT)
         PPOAF_REQUIRE(!a->normalize_values || (a->vn_mean && a->vn_var), "lstm_policy_step: normaliser state missing");
     return PPOAF_OK;
+}
+
+static int check_step_blocks(const ppoaf_lstm_policy_step_args_t* a, const ppoaf_lstm_step_blocks_t* t) {
+    PPOAF_REQUIRE(a && t, "lstm_policy_step_blocks: null args");
+    PPOAF_REQUIRE(a->mode == PPOAF_LSTM_STEP || a->mode == PPOAF_LSTM_CRITIC_NEXT,
+                  "lstm_policy_step_blocks: mode=%d (0 step, 1 critic next; INFER and MASK have no block form)", a->mode);
+    PPOAF_REQUIRE(t->n_blocks >= 1 && t->n_blocks <= PPOAF_ROW_BLOCKS_MAX, "lstm_policy_step_blocks: n_blocks=%d not in [1, %d]",
+                  t->n_blocks, PPOAF_ROW_BLOCKS_MAX);
+    PPOAF_REQUIRE(t->rows_per_block >= 0, "lstm_policy_step_blocks: rows_per_block=%ld must be >= 0", (long)t->rows_per_block);
+    PPOAF_REQUIRE(a->E == t->rows_per_block * t->n_blocks,
+                  "lstm_policy_step_blocks: E=%ld is not n_blocks=%d x rows_per_block=%ld", (long)a->E, t->n_blocks,
+                  (long)t->rows_per_block);
+    // scalar loads and stores: the element's own alignment is all that is asked for
+    const uintptr_t act_mask = a->head_kind == PPOAF_HEAD_GAUSSIAN ? 3 : 7;
+    for (int b = 0; b < t->n_blocks; ++b) {
+        PPOAF_REQUIRE(t->critic_obs[b] && ((uintptr_t)t->critic_obs[b] & 3) == 0,
+                      "lstm_policy_step_blocks: block %d: the critic_obs base is null or not aligned to 4 bytes", b);
+        if (a->mode == PPOAF_LSTM_STEP)
+            PPOAF_REQUIRE(t->obs[b] && t->env_action[b] && ((uintptr_t)t->obs[b] & 3) == 0 &&
+                              ((uintptr_t)t->env_action[b] & act_mask) == 0,
+                          "lstm_policy_step_blocks: block %d: the obs / env_action base is null or not aligned to its element "
+                          "(float32 4 bytes, int64 8)", b);
+    }
+    return check_step_args(a, false);
 }
 
 }  // namespace ppoaf
@@ -195,9 +310,8 @@ static_assert(sizeof(ppoaf_lstm_policy_step_args_t) == 392, "ppoaf_lstm_policy_s
 
 extern "C" int ppoaf_lstm_policy_step_check(const ppoaf_lstm_policy_step_args_t* a) { return check_step_args(a); }
 
-extern "C" int ppoaf_lstm_policy_step(const ppoaf_lstm_policy_step_args_t* a, ppoaf_stream_t stream) {
-    if (int rc = check_step_args(a)) return rc;
-    if (a->E == 0) return PPOAF_OK;
+// the device view of checked arguments
+static LstmStepDev step_dev_of(const ppoaf_lstm_policy_step_args_t* a) {
     LstmStepDev u{};
     // (the descriptors' own `rows` is not read: E rules)
     u.net[0] = lstm_args_of(&a->actor);
@@ -227,10 +341,51 @@ extern "C" int ppoaf_lstm_policy_step(const ppoaf_lstm_policy_step_args_t* a, pp
     u.terminated = (a->mode == PPOAF_LSTM_CRITIC_NEXT || a->mode == PPOAF_LSTM_MASK) ? a->terminated : nullptr;
     u.stored[0] = a->actor_hidden_out; u.stored[1] = a->actor_cell_out;
     u.stored[2] = a->critic_hidden_out; u.stored[3] = a->critic_cell_out;
+    return u;
+}
+
+extern "C" int ppoaf_lstm_policy_step(const ppoaf_lstm_policy_step_args_t* a, ppoaf_stream_t stream) {
+    if (int rc = check_step_args(a)) return rc;
+    if (a->E == 0) return PPOAF_OK;
+    const LstmStepDev u = step_dev_of(a);
     hipStream_t s = (hipStream_t)stream;
     switch (a->actor.hidden) {
         case 32: return launch_lstm_step<32>(u, s);
         case 64: return launch_lstm_step<64>(u, s);
     }
     return launch_lstm_step<128>(u, s);
+}
+
+PPOAF_LAYOUT(ppoaf_lstm_step_blocks_t, n_blocks, 0);
+PPOAF_LAYOUT(ppoaf_lstm_step_blocks_t, rows_per_block, 8);
+PPOAF_LAYOUT(ppoaf_lstm_step_blocks_t, obs, 16);
+PPOAF_LAYOUT(ppoaf_lstm_step_blocks_t, critic_obs, 144);
+PPOAF_LAYOUT(ppoaf_lstm_step_blocks_t, env_action, 272);
+static_assert(sizeof(ppoaf_lstm_step_blocks_t) == 400, "ppoaf_lstm_step_blocks_t");
+
+extern "C" int ppoaf_lstm_policy_step_blocks_check(const ppoaf_lstm_policy_step_args_t* a, const ppoaf_lstm_step_blocks_t* t) {
+    return check_step_blocks(a, t);
+}
+
+extern "C" int ppoaf_lstm_policy_step_blocks(const ppoaf_lstm_policy_step_args_t* a, const ppoaf_lstm_step_blocks_t* t,
+                                             ppoaf_stream_t stream) {
+    if (int rc = check_step_blocks(a, t)) return rc;
+    if (a->E == 0) return PPOAF_OK;                 // no row: nothing is read, nothing launched
+    LstmStepDev u = step_dev_of(a);
+    u.net[0].x = u.net[1].x = nullptr;
+    LstmStepBlocks tb;
+    for (int b = 0; b < PPOAF_ROW_BLOCKS_MAX; ++b) {
+        const bool in = b < t->n_blocks;
+        tb.obs[b] = in && a->mode == PPOAF_LSTM_STEP ? t->obs[b] : nullptr;
+        tb.critic_obs[b] = in ? t->critic_obs[b] : nullptr;
+        tb.env_action[b] = in && a->mode == PPOAF_LSTM_STEP ? t->env_action[b] : nullptr;
+    }
+    tb.rows_per_block = (unsigned)t->rows_per_block;
+    tb.action_elems = a->head_kind == PPOAF_HEAD_GAUSSIAN ? a->actor.out_dim : 1;
+    hipStream_t s = (hipStream_t)stream;
+    switch (a->actor.hidden) {
+        case 32: return launch_lstm_step_blocks<32>(u, tb, s);
+        case 64: return launch_lstm_step_blocks<64>(u, tb, s);
+    }
+    return launch_lstm_step_blocks<128>(u, tb, s);
 }

@@ -897,18 +897,32 @@ def _lstm_stored(args, stored):
         setattr(args, f, _lstm_rows(t, args.E, args.actor.hidden, f))
 
 
-def _lstm_launch(args, mode):
+def _lstm_launch(args, mode, blocks=None):
     args.mode = mode
-    check(_lib.load().ppoaf_lstm_policy_step(C.byref(args), stream()), "lstm_policy_step")
+    if blocks is None:
+        check(_lib.load().ppoaf_lstm_policy_step(C.byref(args), stream()), "lstm_policy_step")
+    else:
+        check(_lib.load().ppoaf_lstm_policy_step_blocks(C.byref(args), C.byref(blocks), stream()), "lstm_policy_step_blocks")
+
+
+def lstm_policy_step_blocks_refusal(args, blocks):
+    """'' when ppoaf_lstm_policy_step_blocks_check accepts the filled arguments and the _lib.LstmStepBlocks table (host
+    only: nothing is launched, pointers are compared with NULL and looked at for their alignment), else the reason."""
+    lib = _lib.load()
+    if lib.ppoaf_lstm_policy_step_blocks_check(C.byref(args), C.byref(blocks)) == 0:
+        return ""
+    return lib.ppoaf_last_error().decode("utf-8", "replace")
 
 
 def lstm_policy_step(args, obs, critic_obs, actor_state, critic_state, raw_action_out, action_out, logp_out, value_out,
-                     stored, obs_copy_out=None, critic_obs_copy_out=None, forced_raw_action=None):
+                     stored, obs_copy_out=None, critic_obs_copy_out=None, forced_raw_action=None, blocks=None):
     """STEP: one launch steps both networks' (h, c) in place and writes the step's rows (see include/ppoaf_hip.h).
-    args: a _lib.LstmPolicyStepArgs whose descriptors, E, head fields, seed / offset and normaliser fields are set."""
+    args: a _lib.LstmPolicyStepArgs whose descriptors, E, head fields, seed / offset and normaliser fields are set.
+    blocks: a filled _lib.LstmStepBlocks -- the observations are read through it (obs / critic_obs are None then) and
+    the env actions also go to its env_action blocks (ppoaf_lstm_policy_step_blocks)."""
     E = args.E
-    args.obs = _lstm_rows(obs, E, args.actor.in_dim, "obs")
-    args.critic_obs = _lstm_rows(critic_obs, E, args.critic.in_dim, "critic_obs")
+    args.obs = None if blocks is not None else _lstm_rows(obs, E, args.actor.in_dim, "obs")
+    args.critic_obs = None if blocks is not None else _lstm_rows(critic_obs, E, args.critic.in_dim, "critic_obs")
     _lstm_states(args, "actor", *actor_state)
     _lstm_states(args, "critic", *critic_state)
     gauss = args.head_kind == HEAD_GAUSSIAN
@@ -923,22 +937,24 @@ def lstm_policy_step(args, obs, critic_obs, actor_state, critic_state, raw_actio
         _lstm_rows(critic_obs_copy_out, E, args.critic.in_dim, "critic_obs_copy_out")
     args.forced_raw_action = None if forced_raw_action is None else \
         _lstm_rows(forced_raw_action, E, width, "forced_raw_action", adt)
-    _lstm_launch(args, LSTM_STEP)
+    _lstm_launch(args, LSTM_STEP, blocks)
 
 
-def lstm_critic_next(args, critic_obs, critic_state, boot_value_out, commit, terminated=None, stored=None):
+def lstm_critic_next(args, critic_obs, critic_state, boot_value_out, commit, terminated=None, stored=None, blocks=None):
     """CRITIC_NEXT: V(critic_obs) -> boot_value_out [E]; the critic's (h, c) are replaced only where the device byte
-    `commit` is set; with `terminated` [E] the four `stored` rows of those envs are zeroed."""
+    `commit` is set; with `terminated` [E] the four `stored` rows of those envs are zeroed.  blocks: a _lib.LstmStepBlocks
+    whose critic_obs blocks are read instead (critic_obs is None); `terminated` then holds the per-env bytes
+    [rows_per_block]."""
     E = args.E
-    args.critic_obs = _lstm_rows(critic_obs, E, args.critic.in_dim, "critic_obs")
+    args.critic_obs = None if blocks is not None else _lstm_rows(critic_obs, E, args.critic.in_dim, "critic_obs")
     _lstm_states(args, "critic", *critic_state)
     args.boot_value_out = _lstm_rows(boot_value_out, E, 1, "boot_value_out")
     args.commit = _lstm_flags(commit, 1, "commit")
     args.terminated = None
     if terminated is not None:
-        args.terminated = _lstm_flags(terminated, E, "terminated")
+        args.terminated = _lstm_flags(terminated, E if blocks is None else blocks.rows_per_block, "terminated")
         _lstm_stored(args, stored)
-    _lstm_launch(args, LSTM_CRITIC_NEXT)
+    _lstm_launch(args, LSTM_CRITIC_NEXT, blocks)
 
 
 def lstm_mask_stored(args, terminated, stored):

@@ -552,21 +552,66 @@ class PPOPolicy:
         h = self.buffer.hidden
         return h["actor_hidden"][t], h["actor_cell"][t], h["critic_hidden"][t], h["critic_cell"][t]
 
-    def lstm_rollout_step(self, t, obs, critic_obs, value_normalizer=None, forced_raw_action=None):
+    def lstm_step_blocks_unsupported_reason(self, obs_blocks, critic_obs_blocks, env_action_blocks):
+        """'' when ppoaf_lstm_policy_step_blocks takes these row blocks: one device tensor per agent of the policy in env
+        order, [E_env, .] rows of the env's tensors where they lie.  obs_blocks and env_action_blocks are None for the
+        critic's step on the next observation (CRITIC_NEXT reads the critic's blocks only).  The loads are scalar, so a
+        block needs its element's alignment only; the library checks the same before it launches."""
+        from .. import _lib
+        buf = self.buffer
+        n = len(critic_obs_blocks)
+        if not 1 <= n <= _lib.ROW_BLOCKS_MAX:
+            return f"{n} row blocks, a table holds 1 .. {_lib.ROW_BLOCKS_MAX}"
+        if buf.C % n or any(b is not None and len(b) != n for b in (obs_blocks, env_action_blocks)):
+            return f"{n} critic observation blocks do not pair with the other blocks or with {buf.C} rows"
+        rows = buf.C // n
+        adt, per_row = buf.actions.dtype, buf.actions[0].numel() // buf.C
+        for what, blks, dt, width in (("observation", obs_blocks, torch.float32, buf.observations.shape[-1]),
+                                      ("critic observation", critic_obs_blocks, torch.float32, buf.critic_observations.shape[-1]),
+                                      ("env action", env_action_blocks, adt, per_row)):
+            for b, x in enumerate(blks or ()):
+                if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dt and x.is_contiguous() and x.numel() == rows * width):
+                    return f"{what} block {b} is not a contiguous {dt} device tensor of {rows} x {width}"
+                if x.data_ptr() % x.element_size():
+                    return f"{what} block {b} does not start on a {x.element_size()}-byte boundary"
+        return ""
+
+    def _lstm_step_blocks(self, obs_blocks, critic_obs_blocks, env_action_blocks):
+        """The checked blocks as the table of ppoaf_lstm_policy_step_blocks (one reusable _lib.LstmStepBlocks)."""
+        from .. import _lib
+        why = self.lstm_step_blocks_unsupported_reason(obs_blocks, critic_obs_blocks, env_action_blocks)
+        if why:
+            raise _lib.PpoafError(f"lstm_policy_step_blocks: {why}")
+        tb = getattr(self, "_lstm_blocks_table", None)
+        if tb is None:
+            tb = self._lstm_blocks_table = _lib.LstmStepBlocks()
+        n = len(critic_obs_blocks)
+        tb.n_blocks, tb.rows_per_block = n, self.buffer.C // n
+        for b in range(n):
+            tb.critic_obs[b] = critic_obs_blocks[b].data_ptr()
+            tb.obs[b] = None if obs_blocks is None else obs_blocks[b].data_ptr()
+            tb.env_action[b] = None if env_action_blocks is None else env_action_blocks[b].data_ptr()
+        return tb
+
+    def lstm_rollout_step(self, t, obs, critic_obs, value_normalizer=None, forced_raw_action=None, blocks=None):
         """
         rollout_step for an LSTM policy (K21, STEP): both networks' forward passes, sampling (or the forced raw action),
         log-prob, value (+ denormalisation) and row t of the buffer -- actions, log-probs, values, observation copies and
         the four hidden-state rows -- in ONE launch that steps the networks' `hidden_state` tensors in place.  Returns
         the action row for env.step; `lstm_finish_step` takes the environment's answer.
+        blocks (optional, then obs / critic_obs are None): (obs_blocks, critic_obs_blocks, env_action_blocks) as for
+        `rollout_step` -- the launch reads the env's tensors where they lie and fills the env's action tensors beside
+        the buffer row (ppoaf_lstm_policy_step_blocks); `lstm_step_blocks_unsupported_reason` says when not.
         """
         buf = self.buffer
         E = buf.C
         a = self._lstm_step_args(E)["args"]
+        tb = None if blocks is None else self._lstm_step_blocks(*blocks)
         a.seed, a.offset = self.actor.distribution.rng.take(E)
         self._lstm_normalizer(a, value_normalizer)
         K.lstm_policy_step(a, obs, critic_obs, self.actor.hidden_state, self.critic.hidden_state, buf.raw_actions[t],
                            buf.actions[t], buf.log_probs[t], buf.values[t], self._lstm_stored_rows(t),
-                           buf.observations[t], buf.critic_observations[t], forced_raw_action)
+                           buf.observations[t], buf.critic_observations[t], forced_raw_action, blocks=tb)
         return buf.actions[t]
 
     @staticmethod
@@ -577,34 +622,41 @@ class PPOPolicy:
             a.vn_mean = value_normalizer.running_stats.mean_t.data_ptr()
             a.vn_var = value_normalizer.running_stats.var_t.data_ptr()
 
-    def lstm_finish_step(self, t, rewards, terminated, next_critic_obs=None, cut=None, value_normalizer=None):
+    def lstm_finish_step(self, t, rewards, terminated, next_critic_obs=None, cut=None, value_normalizer=None,
+                         next_critic_blocks=None):
         """
-        The environment's answer for step t of an LSTM policy: rewards, and the stored hidden rows of the envs that
-        terminated zeroed (ppo_policy.py:593-627).  With `next_critic_obs` the same launch (K21, CRITIC_NEXT) writes
-        V(next critic observation) to boot_value[t] and keeps the critic's stepped state only where the device flag
-        `cut` (one bool / byte, never read by the host) is set (ppo.py:1863-1881); without it the zeroing is a launch of
-        its own (MASK).
+        The environment's answer for step t of an LSTM policy: rewards (None: K23 has written the row already), and the
+        stored hidden rows of the envs that terminated zeroed (ppo_policy.py:593-627).  With `next_critic_obs` the same
+        launch (K21, CRITIC_NEXT) writes V(next critic observation) to boot_value[t] and keeps the critic's stepped state
+        only where the device flag `cut` (one bool / byte, never read by the host) is set (ppo.py:1863-1881); without it
+        the zeroing is a launch of its own (MASK).  `terminated`: one flag per buffer row.  next_critic_blocks instead of
+        next_critic_obs: the next critic observation as row blocks (see lstm_rollout_step), and then `terminated` holds
+        the per-env flags, one per row of a block.
         """
         buf = self.buffer
-        buf.rewards[t].copy_(rewards.reshape(-1))
+        if rewards is not None:
+            buf.rewards[t].copy_(rewards.reshape(-1))
         buf.steps_written = max(buf.steps_written, t + 1)
         self._t = t + 1
         a = self._lstm_step_args(buf.C)["args"]
         terminated = terminated.reshape(-1).contiguous()
-        if next_critic_obs is None:
+        if next_critic_obs is None and next_critic_blocks is None:
             K.lstm_mask_stored(a, terminated, self._lstm_stored_rows(t))
             return
+        tb = None if next_critic_blocks is None else self._lstm_step_blocks(None, next_critic_blocks, None)
         self._lstm_normalizer(a, value_normalizer)
         K.lstm_critic_next(a, next_critic_obs, self.critic.hidden_state, buf.boot_value[t], cut.reshape(1), terminated,
-                           self._lstm_stored_rows(t))
+                           self._lstm_stored_rows(t), blocks=tb)
 
-    def lstm_last_value(self, t, critic_obs, value_normalizer=None):
+    def lstm_last_value(self, t, critic_obs, value_normalizer=None, critic_blocks=None):
         """V(critic_obs) after the last step of a rollout -> boot_value[t] (K21, CRITIC_NEXT with the flag set: the critic
-        is stepped, as get_critic_values steps it).  Returns that row."""
+        is stepped, as get_critic_values steps it).  Returns that row.  critic_blocks instead of critic_obs: the
+        observation as row blocks."""
         buf = self.buffer
         st = self._lstm_step_args(buf.C)
+        tb = None if critic_blocks is None else self._lstm_step_blocks(None, critic_blocks, None)
         self._lstm_normalizer(st["args"], value_normalizer)
-        K.lstm_critic_next(st["args"], critic_obs, self.critic.hidden_state, buf.boot_value[t], st["one"])
+        K.lstm_critic_next(st["args"], critic_obs, self.critic.hidden_state, buf.boot_value[t], st["one"], blocks=tb)
         return buf.boot_value[t]
 
     def _lstm_infer_step(self, t_obs, deterministic):

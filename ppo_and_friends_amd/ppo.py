@@ -204,7 +204,16 @@ class _RolloutMember:
             # MAT: rows are envs, agents side by side in the policy's (shuffled) slot order (ppo.py:1643-1644, 753-770)
             pol.shuffle_agent_ids()
             self.order, self.inverse = torch.as_tensor(pol.agent_slot_order(), device=dev), None
-        self.blocks = bool(ppo.step_row_blocks and self.fused and (self.grouped or not whole))
+        self.blocks = bool(ppo.step_row_blocks and (self.fused or self.lstm_kernel) and (self.grouped or not whole))
+        if pol.using_lstm and ppo.verbose and not whole:
+            # which step form an LSTM member takes, and why (a block form that a table refuses later says so in act())
+            if not self.lstm_kernel:
+                form = f"the torch route ({pol.lstm_step_unsupported_reason()})"
+            elif self.blocks:
+                form = "K21 on the env's row blocks (ppoaf_lstm_policy_step_blocks)"
+            else:
+                form = "K21 on gathered rows (step_row_blocks is switched off)"
+            rank_print(f"rollout: LSTM policy {policy_id} steps on {form}")
         self.env_act = None
         self.nat = ppo._scratch(f"nat_buf_{policy_id}_{T}_{self.n}_{n_envs}", T * self.n * n_envs, torch.float32).view(T, -1)
         # per-step intrinsic rewards in the buffer's own layout (agents side by side when grouped)
@@ -217,6 +226,13 @@ class _RolloutMember:
         if isinstance(x, dict):
             return torch.cat([x[a] for a in self.agents], 0)
         return x.reshape((self.A, self.E) + tuple(x.shape[1:]))[self.idx].reshape((self.n * self.E,) + tuple(x.shape[1:]))
+
+    def term_rows(self, terminated, term_e):
+        """The member's rows of the env's `terminated`, agent-major [n * E]: the agents of an env end together, so the
+        per-env flags `term_e` serve each of its agents."""
+        if self.whole:
+            return terminated
+        return term_e if self.n == 1 else term_e.repeat(self.n)
 
     def row_blocks(self, x):
         """The same rows where they lie: one [E, .] tensor per agent of the member."""
@@ -262,11 +278,16 @@ class _RolloutMember:
                     tb = (self.row_blocks(critic_obs), None if pol.expanded_actor_space else self.row_blocks(obs), self.env_act)
                 else:
                     tb = (self.row_blocks(obs), self.row_blocks(critic_obs), self.env_act)
-                why = pol.step_blocks_unsupported_reason(*tb)          # the tables are checked before every launch
+                # the tables are checked before every launch
+                why = pol.lstm_step_blocks_unsupported_reason(*tb) if self.lstm_kernel else pol.step_blocks_unsupported_reason(*tb)
             if why:
                 self.blocks = False
                 if ppo.verbose:
                     rank_print(f"rollout: policy {self.id} gathers its rows with torch operators ({why})")
+            elif self.lstm_kernel:
+                # K21 with the buffer row and the env's action blocks in one launch
+                pol.lstm_rollout_step(t, None, None, self.vn, forced_raw_action=forced, blocks=tb)
+                return None
             else:
                 # K6+K7 / K16 with the buffer row in one launch; a MAT team in its slot order, without group() / ungroup()
                 a = pol.rollout_step(t, None, None, self.vn, forced_raw_action=forced, blocks=tb)
@@ -317,7 +338,7 @@ class _RolloutMember:
                 self.intr[t] = intr = pol.get_intrinsic_reward(prev_o, self.rows(nxt_obs), act)
                 nxt = self.rows(term_obs)
         if finish_rows:       # K23 writes the row: write_step copies it onto itself
-            self.answered = (None if self.fused else self.buf.rewards[t]), nxt
+            self.answered = (None if self.fused or self.lstm_kernel else self.buf.rewards[t]), nxt
             return
         self.nat[t].copy_(self.rows(nat))
         r = self.rows(reward)
@@ -327,29 +348,49 @@ class _RolloutMember:
             r = r + intr
         self.answered = (self.group(r) if self.grouped else r), nxt
 
-    def write(self, t, terminated, critic_next):
-        """Row t of the buffer takes the answer.  critic_next: lstm_critic_next() follows for an LSTM policy."""
+    def write(self, t, terminated, term_e, critic_next):
+        """Row t of the buffer takes the answer.  terminated / term_e: the env's flags as handed and per env (an LSTM
+        policy takes its own rows of them, term_rows); critic_next: lstm_critic_next() follows for an LSTM policy."""
         pol, (r, nxt) = self.pol, self.answered
         if self.fused:
             pol.finish_step(t, r, nxt)
         elif self.lstm_kernel:
             self.reward = r
             if not critic_next:           # no critic step on the next observation: the zeroing alone
-                pol.lstm_finish_step(t, r, terminated)
+                pol.lstm_finish_step(t, r, self.term_rows(terminated, term_e))
         else:
             co, o, raw, a, v, lp = self.pending
             self.buf.write_step(t, slice(0, self.buf.C), co, o, nxt, raw, a, v, lp, r)
             pol._t = t + 1
             if pol.using_lstm:
-                pol.store_hidden_states(t, terminated)
+                pol.store_hidden_states(t, self.term_rows(terminated, term_e))
 
-    def lstm_critic_next(self, t, terminated, nxt_cobs, cut):
+    def critic_blocks(self, critic_obs):
+        """The member's critic observation as the row blocks of K21's block form, or None: gathered rows.  The table is
+        checked before every launch; a refusal ends the block form for the rest of the run."""
+        if not (self.blocks and self.lstm_kernel):
+            return None
+        blocks = self.row_blocks(critic_obs)
+        why = self.pol.lstm_step_blocks_unsupported_reason(None, blocks, None)
+        if why:
+            self.blocks = False
+            if self.ppo.verbose:
+                rank_print(f"rollout: policy {self.id} gathers its rows with torch operators ({why})")
+            return None
+        return blocks
+
+    def lstm_critic_next(self, t, terminated, term_e, nxt_cobs, cut):
         """The LSTM critic's step on the next observation, kept only where the device flag `cut` is set; its value goes
-        to boot_value[t]."""
-        pol, nxt_cobs = self.pol, self.rows(nxt_cobs)
+        to boot_value[t].  terminated / term_e: the env's flags as handed and per env."""
+        pol, blocks = self.pol, self.critic_blocks(nxt_cobs)
+        if blocks is not None:
+            # the block form takes the env's flags as handed: one byte per env serves each of its agents' rows
+            pol.lstm_finish_step(t, self.reward, term_e, None, cut, self.vn, next_critic_blocks=blocks)
+            return
+        nxt_cobs = self.rows(nxt_cobs)
         if self.lstm_kernel:
             # the flag stays on the device: the launch keeps the critic's stepped state only where it is set
-            pol.lstm_finish_step(t, self.reward, terminated, nxt_cobs.contiguous(), cut, self.vn)
+            pol.lstm_finish_step(t, self.reward, self.term_rows(terminated, term_e), nxt_cobs.contiguous(), cut, self.vn)
         else:
             h_old = tuple(x.clone() for x in pol.critic.hidden_state)
             v_next = self.ppo.get_policy_values(self.id, nxt_cobs)
@@ -361,9 +402,10 @@ class _RolloutMember:
         ends before the last row the value logged at t + 1 (same critic, same normaliser state during a rollout); the last
         row needs one more pass."""
         ppo, pol = self.ppo, self.pol
-        last_cobs = self.rows(critic_obs).contiguous()
+        blocks = self.critic_blocks(critic_obs)
+        last_cobs = None if blocks is not None else self.rows(critic_obs).contiguous()
         if self.lstm_kernel:
-            next_value = pol.lstm_last_value(T - 1, last_cobs, self.vn)      # (lands in boot_value[T - 1])
+            next_value = pol.lstm_last_value(T - 1, last_cobs, self.vn, critic_blocks=blocks)   # (lands in boot_value[T - 1])
         else:
             next_value = ppo.get_policy_values(self.id, self.group(last_cobs) if self.grouped else last_cobs)
         ppo._close_rollout_buffer(self.id, pol, next_value, self.intr, may_end_early, self.lstm_kernel)
@@ -381,6 +423,9 @@ class PPO:
     # ppoaf_mat_policy_step_blocks: observations read from the env's tensors through a row-block table, env actions
     # written in place); False keeps the gathers
     step_row_blocks = True
+    # LSTM PPOPolicy instances as members of a run with several policies (beside feed-forward members, MAT teams and
+    # other LSTM members): opt-in, set on the class or on an instance before the first rollout; False refuses them
+    lstm_members = False
 
     def __init__(self, env_generator, policy_settings, policy_mapping_fn=None, device="cuda",
                  random_seed=None, envs_per_proc=1, max_ts_per_ep=200, batch_size=256,
@@ -545,7 +590,8 @@ class PPO:
         observation / action space; the agents of ONE policy share them, as in the reference).  A member that owns every
         agent takes the env's tensors as they are, so a member of a mixed run behaves as it does alone on an env
         restricted to its agents.  Members are feed-forward PPOPolicy instances (independent or team-wise PPO) and
-        MATPolicy teams, each with or without an ICM; an LSTM policy runs as the only member.
+        MATPolicy teams, each with or without an ICM; an LSTM policy runs as the only member, or with `lstm_members`
+        switched on beside any of the others (K21 on the env's row blocks, on gathered rows, or the torch route).
         Per step: actions / log-probs (actor + sampling kernel), values (critic, denormalised), env.step, buffer row
         write, episode-end flags -- all enqueued without a host read.  Episode-end cases (ppo.py:1795-1983): terminated
         -> terminal end; ep_ts == max_ts_per_ep, truncated, or the last step of the rollout -> bootstrapped end with the
@@ -561,7 +607,7 @@ class PPO:
         T = self.ts_per_rollout // n_envs
         if len(self.policies) > 1:
             for policy_id, pol in self.policies.items():
-                if pol.using_lstm:
+                if pol.using_lstm and not self.lstm_members:
                     raise NotImplementedError(f"several policies in one run: LSTM policies are not supported (policy {policy_id})")
         # ppo.py:1580-1586: a hard reset per rollout unless soft_resets (then the env carries on, and
         # a filter stack counts the carried observation once more, ppo_env_wrappers.py:149-199)
@@ -658,7 +704,7 @@ class PPO:
                 # K23: every member's reward, natural-reward and end_kind rows and the shared ep_ts, in one launch
                 finish.step(t, *finish_in, last)
             for m in members:
-                m.write(t, terminated, may_end_early and not last)
+                m.write(t, terminated, term_e, may_end_early and not last)
                 if may_end_early:
                     m.buf.fixed_length = False        # (also at the last row: an env may TERMINATE there -- ts_per_rollout = 1 made it visible)
             if may_end_early and finish is None:
@@ -671,11 +717,19 @@ class PPO:
                         # stateful LSTM critic once more.  Branch-free here: the extra step is computed every
                         # time and kept only if the reference would have taken it.
                         cut = (((ep_ts == self.max_ts_per_ep) & ~term_e).any() | trunc_e.any())   # ep_ts of terminated envs is 0 by then (:1851)
-                        m.lstm_critic_next(t, terminated, nxt_cobs, cut)
+                        m.lstm_critic_next(t, terminated, term_e, nxt_cobs, cut)
                 kind = torch.where(term_e, 1, torch.where(boot, 2, 0)).to(torch.int8)
                 for m in members:
                     m.buf.end_kind[t] = kind if m.grouped or row_ends else kind.repeat(m.n)
                 ep_ts = torch.where(term_e | boot, torch.zeros_like(ep_ts), ep_ts)
+            elif may_end_early and lstm_members and not last:
+                # K23 has advanced ep_ts and written end_kind[t]: the same flag from that row, still on the device.  Before
+                # the last step kind 2 is "not terminated, and at max_ts_per_ep or truncated" (K23 resets ep_ts at the
+                # maximum, so >= and == agree), and `| trunc_e.any()` restores the statement above for an env that is
+                # terminated and truncated at once.
+                cut = (lstm_members[0].buf.end_kind[t] == 2).any() | trunc_e.any()
+                for m in lstm_members:
+                    m.lstm_critic_next(t, terminated, term_e, nxt_cobs, cut)
             obs, critic_obs = nxt_obs, nxt_cobs
         self._obs = (obs, critic_obs)
         gs = self.status_dict["global status"]
