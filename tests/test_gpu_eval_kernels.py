@@ -7,7 +7,8 @@
     reference's distribution classes;
   * ppoaf_eval_scores_step against the numpy restatement (tests/helpers/eval_restatement.py), bit for bit;
   * K6's own Categorical and Gaussian draws (cat_step_row / gauss_step_row of csrc/action_heads.hpp, which K21 and K19's
-    sample mode share) against the Philox restatement of tests/helpers/philox.py on the float64 forward (section 9).
+    sample mode share) against the restated heads of tests/helpers/head_draws.py (on the Philox of tests/helpers/philox.py)
+    fed with the float64 forward (section 9).
     Measured on the MI355X, worst deviation / bound: Categorical, no row left out in any of the four cases, logp <= 0.007,
     value <= 0.011; Gaussian (out_dim 1, 4, 5, 6, with and without bounds) raw <= 0.024, action <= 0.027, logp <= 0.100,
     value <= 0.013 -- the device's logf and sincosf stay well inside the rule at these arguments.
@@ -25,6 +26,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import head_draws as hd  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -143,29 +145,6 @@ SHAPES = {"c2": (4, 128, 3, 2), "c4": (18, 128, 3, 5), "c3w": (17, 256, 3, 8), "
 SLICES = {2: (2,), 5: (3, 2), 8: (2, 2, 2, 2), 6: (1, 2, 3)}
 
 
-def _logit_bound(z64):
-    return 1e-5 * np.abs(z64) + 1e-5 * np.abs(z64).max()
-
-
-def _greedy64(head, z64, slices):
-    """(float64 greedy action, rows that may be left out by the near-tie rule)."""
-    tol = _logit_bound(z64)
-    if head == "bernoulli":
-        return (z64 >= 0).astype(np.float32), (np.abs(z64) < tol).any(1)
-    acts, near, o = [], np.zeros(len(z64), bool), 0
-    for n in (slices or (z64.shape[1],)):
-        z, t = z64[:, o:o + n], tol[:, o:o + n]
-        order = np.argsort(-z, axis=1, kind="stable")
-        acts.append(np.argmax(z, axis=1))
-        if n > 1:
-            r = np.arange(len(z))
-            i0, i1 = order[:, 0], order[:, 1]
-            near |= (z[r, i0] - z[r, i1]) < (t[r, i0] + t[r, i1])
-        o += n
-    a = np.stack(acts, 1)
-    return (a if slices else a[:, 0]), near
-
-
 @pytest.mark.parametrize("gain", [0.01, 1.0])
 @pytest.mark.parametrize("shape", sorted(SHAPES))
 @pytest.mark.parametrize("head", ["categorical", "multi_categorical", "bernoulli"])
@@ -176,7 +155,7 @@ def test_deterministic_discrete_against_float64(head, shape, gain):
     slices = SLICES[out_dim] if head == "multi_categorical" else ()
     pol = Policy(21, O, hidden, depth, out_dim, head, act="relu", slices=slices, out_gain=gain)
     obs = _obs(9, E, O)
-    want, near = _greedy64(head, pol.actor.forward(obs.cpu().numpy()), slices)
+    want, near = hd.greedy(head, pol.actor.forward(obs.cpu().numpy()), slices)
     got = pol.infer(obs, GREEDY).cpu().numpy()
     share = near.mean()
     print(f"\n{head} {shape} gain {gain}: {near.sum()} of {E} rows near a tie ({100 * share:.3f} %)")
@@ -331,22 +310,16 @@ def test_k6_categorical_draw_against_the_restated_philox(out_dim, E):
     obs = _obs(out_dim * 100 + E, E, O)
     x = obs.cpu().numpy()
     seed, offset = 0x1234ABCD5678 + E, 2 ** 32 - 7
-    words = philox.philox4x32_10(seed, philox.counters_u64(offset, np.arange(E)), 0)
-    eps = np.finfo(np.float32).eps
+    counters = philox.counters_u64(offset, np.arange(E))
 
     def restate(dt):
         z = pol.actor.forward(x.astype(dt), dt)
-        p = np.exp(z - z.max(1, keepdims=True))
-        p = p / p.sum(1, keepdims=True)
-        s, cum = p.sum(1), np.cumsum(p, 1)
-        us = philox.u32_to_unit(words[0]).astype(dt) * s
-        a = np.minimum((us[:, None] >= cum).sum(1), out_dim - 1)
-        gap = np.abs(us[:, None] - cum).min(1)
+        a, gap, p, s = hd.categorical_draw(z, seed, counters, dt)
         return z, a, gap, p, s
 
-    z64, a64, gap, _, _ = restate(np.float64)
+    z64, a64, gap, p64, s64 = restate(np.float64)
     _, a32, _, p32, s32 = restate(np.float32)
-    near = gap < 2.0 * _logit_bound(z64).max(1) + 1e-6
+    near = hd.near_cdf_edge(z64, gap)
     assert near.sum() <= 2, f"{near.sum()} rows of {E} near a CDF edge"
     raw, act, logp, val = _k6(pol, obs, seed, offset)
     print(f"\ncategorical out_dim {out_dim} E {E}: {near.sum()} rows left out, classes drawn {np.unique(act).tolist()}")
@@ -354,25 +327,8 @@ def test_k6_categorical_draw_against_the_restated_philox(out_dim, E):
     assert np.array_equal(a32[~near], a64[~near]), "the float32 restatement decodes a kept row differently"
     np.testing.assert_array_equal(act[~near], a64[~near])
     assert len(np.unique(a64)) > 1
-    lp = lambda dt, p, s, a: np.log(np.clip(p[np.arange(E), a] / s, dt(eps), dt(1.0) - dt(eps)))
-    p64 = np.exp(z64 - z64.max(1, keepdims=True))
-    p64 = p64 / p64.sum(1, keepdims=True)
-    _judge("logp", logp, lp(np.float64, p64, p64.sum(1), a64), lp(np.float32, p32, s32, a64), ~near)
+    _judge("logp", logp, hd.categorical_logp(p64, s64, a64, np.float64), hd.categorical_logp(p32, s32, a64, np.float32), ~near)
     _judge("value", val, pol.critic.forward(x)[:, 0], pol.critic.forward(x.astype(np.float32), np.float32)[:, 0])
-
-
-def _gauss_normals(philox, seed, counters, out_dim, dt):
-    """gauss_normals4 of csrc/action_heads.hpp in `dt`: dimensions 4 q .. 4 q + 3 from the block (seed, counter, q) --
-    x an open-0 word and y an angle word give the cos and the sin output, z and w the second pair."""
-    z = np.zeros((len(counters), 4 * ((out_dim + 3) // 4)), dt)
-    two_pi = dt(6.28318530717958647692)
-    for q in range((out_dim + 3) // 4):
-        w = philox.philox4x32_10(seed, counters, q)
-        for pair in (0, 1):
-            r = np.sqrt(dt(-2.0) * np.log(philox.u32_to_unit_open0(w[2 * pair]).astype(dt)))
-            ang = two_pi * philox.u32_to_unit(w[2 * pair + 1]).astype(dt)
-            z[:, 4 * q + 2 * pair], z[:, 4 * q + 2 * pair + 1] = r * np.cos(ang), r * np.sin(ang)
-    return z[:, :out_dim]
 
 
 @pytest.mark.parametrize("bounded", [False, True])
@@ -394,17 +350,10 @@ def test_k6_gaussian_draw_against_the_restated_philox(out_dim, bounded):
 
     def restate(dt):
         mean = pol.actor.forward(x.astype(dt), dt)
-        sd = np.maximum(np.log1p(np.exp(pol.actor.log_std.astype(dt))), dt(pol.min_std))
-        raw = mean + sd * _gauss_normals(philox, seed, counters, out_dim, dt)
-        a = np.tanh(raw)
-        slog = np.log(np.maximum(dt(1.0) - a * a, dt(1e-6))).sum(1)
-        act = a
-        if bounded:
-            lo, hi = (v.astype(dt) for v in _bounds(out_dim))
-            act = ((a + dt(1.0)) / dt(2.0)) * (hi - lo) + lo
-        zz = raw - mean
-        l = -(zz * zz) / (dt(2.0) * sd * sd) - np.log(sd) - dt(0.91893853320467274178)
-        return raw, act, np.clip(l, dt(-100.0), dt(100.0)).sum(1) - slog
+        sd = hd.gauss_std(pol.actor.log_std, pol.min_std, dt)
+        raw = mean + sd * hd.gauss_normals(seed, counters, out_dim, dt)
+        act, logp = hd.squashed_gaussian(mean, sd, raw, _bounds(out_dim) if bounded else None, dt)
+        return raw, act, logp
 
     r64, r32 = restate(np.float64), restate(np.float32)
     assert r32[0].dtype == np.float32 and r32[2].dtype == np.float32
