@@ -1,8 +1,8 @@
 """
-Kernel-level drivers for the K19 tests: an MLP actor (+ a critic for K6) laid out in one bucket the way the kernels'
-layer tables expect it (per Linear: weight [out, in] row-major padded to 4 floats, bias padded to 4 floats; log_std
-after the actor's layers for the Gaussian head), the ctypes argument blocks of ppoaf_policy_step / ppoaf_policy_infer,
-and the same forward in float64 / float32 on the CPU.
+Kernel-level drivers for the K19 and K6 tests: an MLP actor (+ a critic for K6, with an in_dim, a width and a depth of its
+own where asked) laid out in one bucket the way the kernels' layer tables expect it (per Linear: weight [out, in]
+row-major padded to 4 floats, bias padded to 4 floats; log_std after the actor's layers for the Gaussian head), the
+ctypes argument blocks of ppoaf_policy_step / ppoaf_policy_infer, and the same forward in float64 / float32 on the CPU.
 """
 import numpy as np
 import torch
@@ -65,13 +65,18 @@ class Policy:
     """Actor + critic in one device bucket, with the argument blocks of K6 and K19."""
 
     def __init__(self, seed, in_dim, hidden, depth, out_dim, head, act="relu", slices=(), bounds=None, out_gain=1.0,
-                 device="cuda", critic_hidden=None):
+                 device="cuda", critic_hidden=None, critic_in_dim=None, critic_depth=None, nets=None):
+        """critic_in_dim / critic_depth: a critic with observations and a depth of its own (default: the actor's).
+        nets: (actor, critic) already drawn -- the seed and the shape arguments are then unused."""
         from ppo_and_friends_amd import _lib
         self._lib = _lib
         rng = np.random.default_rng(seed)
         self.head, self.slices, self.device = head, tuple(slices), torch.device(device)
-        self.actor = Net(rng, in_dim, hidden, depth, out_dim, act, out_gain, log_std=head == "gaussian")
-        self.critic = Net(rng, in_dim, critic_hidden or hidden, depth, 1, act)
+        if nets is not None:
+            self.actor, self.critic = nets
+        else:
+            self.actor = Net(rng, in_dim, hidden, depth, out_dim, act, out_gain, log_std=head == "gaussian")
+            self.critic = Net(rng, critic_in_dim or in_dim, critic_hidden or hidden, critic_depth or depth, 1, act)
         self.params = torch.from_numpy(np.concatenate([self.actor.flat(), self.critic.flat()])).to(self.device)
         self.bounds = None
         if bounds is not None:
@@ -101,15 +106,20 @@ class Policy:
         if self.bounds is not None:
             a.act_lo, a.act_hi = self.bounds[0].data_ptr(), self.bounds[1].data_ptr()
 
-    def step_k6(self, obs, seed, offset, full=False):
-        """ppoaf_policy_step -> action_out; full: (raw_action_out, action_out, logp_out, value_out)."""
-        from ppo_and_friends_amd import kernels as K
-        E = obs.shape[0]
+    def step_args(self, obs, seed, offset, critic_obs=None):
+        """ppoaf_policy_step's argument block, the outputs left to the caller (critic_obs None: the actor's rows)."""
         a = self._lib.PolicyStepArgs()
         a.actor, a.critic = self.actor.desc(self._lib, 0), self.critic.desc(self._lib, self.actor.size())
         self._common(a, obs)
-        a.critic_obs = obs.data_ptr()
+        a.critic_obs = (obs if critic_obs is None else critic_obs).data_ptr()
         a.seed, a.offset = seed, offset
+        return a
+
+    def step_k6(self, obs, seed, offset, full=False, critic_obs=None):
+        """ppoaf_policy_step -> action_out; full: (raw_action_out, action_out, logp_out, value_out)."""
+        from ppo_and_friends_amd import kernels as K
+        E = obs.shape[0]
+        a = self.step_args(obs, seed, offset, critic_obs)
         shape, dt = self.action_shape(E)
         raw, act = torch.zeros(shape, dtype=dt, device=self.device), torch.zeros(shape, dtype=dt, device=self.device)
         logp, val = torch.zeros(E, device=self.device), torch.zeros(E, device=self.device)
