@@ -399,7 +399,8 @@ typedef struct {
      * every workgroup publishes its 16 rows of the inputs, hidden activations and dLoss/dz of the mini-batch there, and
      * ppoaf_ppo_update_wgrad forms the complete gradients from those panels (then ppoaf_ppo_update_adam, compute_norms 3).
      * Per network: hidden activations and dLoss/dz [depth][Bp][hidden], the output layer's partials and the gathered input
-     * rows [Bp][64 | 128] (Bp = B rounded up to 64; 128: a wide pair's network with more than 64 inputs, PPOAF_SPLIT_WIDE_INPUTS). */
+     * rows [Bp][64 | 128] (Bp = B rounded up to 64; 128: a wide pair's network with more than 64 inputs, PPOAF_SPLIT_WIDE_INPUTS;
+     * [Bp][256 | 512] for one with more than 128 | 256 inputs, PPOAF_SPLIT_WIDE_SHAPES). */
     void* split_workspace; int64_t split_workspace_bytes;
     /* 0: fwd_bwd's workgroups use every XCD (actor on 0-3, critic on 4-7; default).  1 / 2: they sit on XCDs 0-3 / 4-7 only
      * (actor on the half's first two XCDs, critic on the other two; the launch is twice as wide and the workgroups
@@ -421,9 +422,18 @@ typedef struct {
      * workspace size is what it was (in_dim <= 64).  With it the pair takes in_dim <= 128 per network: the layer-0 panel of
      * a network with 64 < in_dim <= 128 has a row stride of 128 floats instead of 64 (ppoaf_ppo_update_split_workspace_bytes()
      * counts it); a network with in_dim <= 64 keeps the stride of 64, and its results are bitwise those without the bit.
-     * Every other pair ignores the bit: with a split workspace it keeps in_dim <= 64 (wider inputs run its slab chain). */
+     * Every other pair ignores the bit: with a split workspace it keeps in_dim <= 64 (wider inputs run its slab chain).
+     * PPOAF_SPLIT_WIDE_SHAPES (4; added within ABI 7, read by every entry point; implies PPOAF_SPLIT_WIDE_INPUTS): a second
+     * opt-in for the wide pair.  With it the pair takes in_dim <= 512 per network, as far as each row-tile body's LDS goes
+     * (the 256-wide actor: 512 inputs at depth 1 and 2, 432 at depth 3, 160 at depth 4, none deeper; the 512-wide critic:
+     * 512 at every depth 1 .. 7; a refusal for LDS names LDS), and B <= 1024.  The layer-0 panel's row stride is the
+     * smallest of 64, 128, 256, 512 floats that holds the network's in_dim; Bp goes up to 1024.  ppoaf_ppo_update_wgrad takes
+     * a mini-batch of more than 512 rows in two passes of 32 chunks of 16 rows over the same accumulators.  Inside the
+     * limits of PPOAF_SPLIT_WIDE_INPUTS every size and result is bitwise what that bit alone gives.  Every other pair
+     * ignores the bit, as it ignores the other.  Bits from 8 up are refused. */
 #define PPOAF_SPLIT_ROW_PAIRS   1
 #define PPOAF_SPLIT_WIDE_INPUTS 2
+#define PPOAF_SPLIT_WIDE_SHAPES 4
     int32_t row_pairs;
     /* the slice table of PPOAF_HEAD_MULTI_CATEGORICAL: classes per action dimension, in order, summing to actor.out_dim.
      * Read only for that head kind (appended: every field above keeps its offset). */

@@ -70,9 +70,11 @@ class PpoUpdateArgs(C.Structure):
                 ("n_action_slices", C.c_int32), ("action_slices", C.c_int32 * 8)]
 
 
-# ppoaf_ppo_update_args_t.row_pairs is a bit set (include/ppoaf_hip.h: PPOAF_SPLIT_ROW_PAIRS, PPOAF_SPLIT_WIDE_INPUTS)
+# ppoaf_ppo_update_args_t.row_pairs is a bit set (include/ppoaf_hip.h: PPOAF_SPLIT_ROW_PAIRS, PPOAF_SPLIT_WIDE_INPUTS,
+# PPOAF_SPLIT_WIDE_SHAPES)
 SPLIT_ROW_PAIRS = 1
 SPLIT_WIDE_INPUTS = 2
+SPLIT_WIDE_SHAPES = 4
 
 ABI_VERSION = 7
 

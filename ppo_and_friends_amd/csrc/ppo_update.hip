@@ -272,9 +272,16 @@ static int update_shapes(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
     PPOAF_REQUIRE(a->B >= 2 && a->batch_stride >= a->B, "ppo_update: B=%ld stride=%ld", (long)a->B,
                   (long)a->batch_stride);
     // a wide pair (512-wide critic) has no slab form: the limits of the split-wgrad chain are the pair's own
-    // (PPOAF_SPLIT_WIDE_INPUTS: its layer-0 panels take a row stride of 128 -- split_xld, ppo_update_dev.hpp)
+    // (PPOAF_SPLIT_WIDE_INPUTS: its layer-0 panels take a row stride of 128 -- split_xld, ppo_update_dev.hpp;
+    //  PPOAF_SPLIT_WIDE_SHAPES: of 256 or 512, and the wgrad launch takes more than 32 chunks of 16 rows in passes.  What
+    //  each body's LDS holds of in_dim <= 512 is fwd_bwd_fits' to say, as for every pair.)
     if (width_pair_is_wide(u.net[0].H, u.net[1].H)) {
-        if (args_wide_inputs(a))
+        if (args_wide_shapes(a))
+            PPOAF_REQUIRE(u.net[0].in_dim <= 512 && u.net[1].in_dim <= 512 && a->B <= 1024,
+                          "ppo_update: the wide pair (actor %d, critic %d) runs the split-wgrad chain only: with "
+                          "PPOAF_SPLIT_WIDE_SHAPES in_dim <= 512 and B <= 1024 (got in_dim %d / %d, B %ld)", u.net[0].H, u.net[1].H, u.net[0].in_dim,
+                          u.net[1].in_dim, (long)a->B);
+        else if (args_wide_inputs(a))
             PPOAF_REQUIRE(u.net[0].in_dim <= 128 && u.net[1].in_dim <= 128 && a->B <= 512,
                           "ppo_update: the wide pair (actor %d, critic %d) runs the split-wgrad chain only: with "
                           "PPOAF_SPLIT_WIDE_INPUTS in_dim <= 128 and B <= 512 (got in_dim %d / %d, B %ld)", u.net[0].H, u.net[1].H, u.net[0].in_dim,
@@ -326,14 +333,15 @@ int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
     u.sp = WsDev();
     if (a->split_workspace) {
         PPOAF_REQUIRE((((uintptr_t)a->split_workspace) & 255) == 0, "ppo_update: split_workspace must be 256-byte aligned");
-        // (a wide pair with PPOAF_SPLIT_WIDE_INPUTS: update_shapes has checked its own limits, in_dim <= 128 and B <= 512)
+        // (a wide pair with PPOAF_SPLIT_WIDE_INPUTS: update_shapes has checked its own limits, in_dim <= 128 and B <= 512;
+        //  with PPOAF_SPLIT_WIDE_SHAPES in_dim <= 512 and B <= 1024)
         if (!(args_wide_inputs(a) && width_pair_is_wide(u.net[0].H, u.net[1].H)))
             PPOAF_REQUIRE(u.net[0].in_dim <= 64 && u.net[1].in_dim <= 64 && u.B <= 512,
                           "ppo_update: the split-wgrad chain covers in_dim <= 64 and B <= 512 (got %d / %d, %ld)", u.net[0].in_dim,
                           u.net[1].in_dim, u.B);
         size_t need = ws_layout(u, &u.sp, reinterpret_cast<char*>(a->split_workspace));
-        PPOAF_REQUIRE((a->row_pairs & ~(PPOAF_SPLIT_ROW_PAIRS | PPOAF_SPLIT_WIDE_INPUTS)) == 0,
-                      "ppo_update: row_pairs=%d (a bit set: 1 row pairs, 2 wide inputs)", a->row_pairs);
+        PPOAF_REQUIRE((a->row_pairs & ~(PPOAF_SPLIT_ROW_PAIRS | PPOAF_SPLIT_WIDE_INPUTS | PPOAF_SPLIT_WIDE_SHAPES)) == 0,
+                      "ppo_update: row_pairs=%d (a bit set: 1 row pairs, 2 wide inputs, 4 wide shapes)", a->row_pairs);
         if (args_row_pairs(a)) need = pair_region_offset(u) + pair_region_layout(u, nullptr, nullptr);      // the record region comes last
         PPOAF_REQUIRE((size_t)a->split_workspace_bytes >= need, "ppo_update: split_workspace of %ld B, %zu needed",
                       (long)a->split_workspace_bytes, need);

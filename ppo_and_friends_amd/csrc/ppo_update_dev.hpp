@@ -108,7 +108,7 @@ struct WsDev {
     float* xbuf[2];                       // [Bp][xld]        the mini-batch's gathered input rows, zero padded (layer-0 wgrad)
     int W;                                // workers per network (persistent kernel)
     // row stride of xbuf per network (split_xld): 64, or 128 for a wide pair's network with 64 < in_dim <= 128
-    // (PPOAF_SPLIT_WIDE_INPUTS).  Only the wide pair's kernels read it; every other kernel's stride is the constant 64.
+    // (PPOAF_SPLIT_WIDE_INPUTS), 256 | 512 for one with in_dim <= 256 | 512 (PPOAF_SPLIT_WIDE_SHAPES).  Only the wide pair's kernels read it; every other kernel's stride is the constant 64.
     // (in the place of the persistent kernel's XCD numbers, which nothing read: the argument block keeps its layout)
     int xld[2];
     int Bp;                               // B rounded up to 64
@@ -156,15 +156,20 @@ inline int split_wgrad_jobs(const NetDev& n) {
 inline int split_wgrad_per_xcd(const UpdateDev& u) { return (split_wgrad_jobs(u.net[0]) + split_wgrad_jobs(u.net[1]) + 7) / 8; }
 inline int split_wgrad_blocks(const UpdateDev& u) { return 8 * split_wgrad_per_xcd(u); }      // some run no job (partials 0)
 
-// args->row_pairs is a bit set (ppoaf_hip.h): the row pairs of 256-wide networks, the wide pair's 65 .. 128 inputs
+// args->row_pairs is a bit set (ppoaf_hip.h): the row pairs of 256-wide networks, the wide pair's 65 .. 128 inputs, the
+// wide pair's in_dim <= 512 and B <= 1024 (which implies the second)
 inline bool args_row_pairs(const ppoaf_ppo_update_args_t* a) { return (a->row_pairs & PPOAF_SPLIT_ROW_PAIRS) != 0; }
-inline bool args_wide_inputs(const ppoaf_ppo_update_args_t* a) { return (a->row_pairs & PPOAF_SPLIT_WIDE_INPUTS) != 0; }
+inline bool args_wide_shapes(const ppoaf_ppo_update_args_t* a) { return (a->row_pairs & PPOAF_SPLIT_WIDE_SHAPES) != 0; }
+inline bool args_wide_inputs(const ppoaf_ppo_update_args_t* a) {
+    return (a->row_pairs & (PPOAF_SPLIT_WIDE_INPUTS | PPOAF_SPLIT_WIDE_SHAPES)) != 0;
+}
 
-// row stride of a network's layer-0 panel: the host admits in_dim > 64 for a wide pair with PPOAF_SPLIT_WIDE_INPUTS only
-// (update_shapes, make_update_dev), so every other pair's panels are [Bp][64] as they always were
-inline int split_xld(const NetDev& n) { return n.in_dim <= 64 ? 64 : 128; }
+// row stride of a network's layer-0 panel, the smallest of 64, 128, 256, 512 that holds in_dim: the host admits in_dim > 64
+// for a wide pair with PPOAF_SPLIT_WIDE_INPUTS (<= 128) or PPOAF_SPLIT_WIDE_SHAPES (<= 512) only (update_shapes,
+// make_update_dev), so every other pair's panels are [Bp][64] as they always were
+inline int split_xld(const NetDev& n) { return n.in_dim <= 64 ? 64 : n.in_dim <= 128 ? 128 : n.in_dim <= 256 ? 256 : 512; }
 
-// workspace layout: per network hbuf, dbuf ([depth][Bp][H] each), outpart ([ceil(B/16)][seg]) and xbuf ([Bp][64 | 128])
+// workspace layout: per network hbuf, dbuf ([depth][Bp][H] each), outpart ([ceil(B/16)][seg]) and xbuf ([Bp][xld])
 inline size_t ws_layout(const UpdateDev& u, WsDev* ws, char* base) {
     const long Bp = (u.B + 63) & ~63L;
     size_t off = 0;

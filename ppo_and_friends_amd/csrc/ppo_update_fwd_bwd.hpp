@@ -25,7 +25,7 @@ __global__ __launch_bounds__(kThreadsU) void ppo_update_fwd_bwd_kernel(UpdateDev
         g = ((b >> 3) << 1) | (x & 1);
     }
     if (g >= u.n_wg) return;                               // uniform per workgroup, before any barrier
-    // (a wide pair's kernel alone reads the layer-0 panel's row stride from its arguments: u.sp.xld, PPOAF_SPLIT_WIDE_INPUTS)
+    // (a wide pair's kernel alone reads the layer-0 panel's row stride from its arguments: u.sp.xld, PPOAF_SPLIT_WIDE_INPUTS / _SHAPES)
     constexpr bool XLD = SPLIT && HTC > 16;
     if (which == 0) ppo_update_fwd_bwd_body<HTA, SPLIT, XLD>(u, 0, g);
     else ppo_update_fwd_bwd_body<HTC, SPLIT, XLD>(u, 1, g);

@@ -84,7 +84,7 @@ template <int CP> __device__ __forceinline__ void lds_write_adjacent(float* p, c
 // histories to reconcile at every later wait of the prologue, and its safe answer to that is vmcnt(0): each of those waits
 // then waited for the sets as well.  Every other case runs the body as it was (TABLES = false: both decided at run time).
 // XLD (the wide pair's kernel only, ppo_update_fwd_bwd.hpp): the SPLIT publish of the input rows takes the panel's row stride
-// from u.sp.xld[which] (64 | 128, PPOAF_SPLIT_WIDE_INPUTS).  Every other kernel keeps the constant and the loop written for it.
+// from u.sp.xld[which] (64 | 128: PPOAF_SPLIT_WIDE_INPUTS; 256 | 512: PPOAF_SPLIT_WIDE_SHAPES).  Every other kernel keeps the constant and the loop written for it.
 template <int HT, bool SPLIT, bool TABLES, bool XLD = false>
 __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, const int which, const int g) {
     constexpr int H = 16 * HT, HS = H + 4;                 // which: 0 actor, 1 critic; g: 16-row block
@@ -432,8 +432,8 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     if (!deep && depth > 1 && has_tile) load_fwd_lines_buf<HT>(P + offW(1), wave * 16, lane, fr);
     __syncthreads();
     PPOAF_STAMP(2);
-    if constexpr (SPLIT && XLD) {      // ... zero padded to the panel's stride, 64 or 128 columns (uniform per network)
-        const int xld = u.sp.xld[which], sh = xld == 64 ? 6 : 7;
+    if constexpr (SPLIT && XLD) {      // ... zero padded to the panel's stride, 64 .. 512 columns (a power of two, uniform per network)
+        const int xld = u.sp.xld[which], sh = __builtin_ctz((unsigned)xld);
         float* xb = u.sp.xbuf[which] + (long)g * kRows * xld;
         for (int i = tid; i < kRows * xld; i += kThreadsU) {
             const int r = i >> sh, c = i & (xld - 1);

@@ -130,8 +130,8 @@ __device__ __forceinline__ void ppo_update_wide_critic_body(const UpdateDev& u, 
     };
     if (depth > 1) request_fwd(1, 0, fr[0]);
     __syncthreads();
-    {           // the block's input rows, zero padded to the panel's stride (64 | 128 columns): the layer-0 wgrad's K-panel
-        const int xld = u.sp.xld[which], sh = xld == 64 ? 6 : 7;
+    {           // the block's input rows, zero padded to the panel's stride (64 .. 512 columns, a power of two): the layer-0 wgrad's K-panel
+        const int xld = u.sp.xld[which], sh = __builtin_ctz((unsigned)xld);
         float* xb = u.sp.xbuf[which] + (long)g * kRows * xld;
         for (int i = tid; i < kRows * xld; i += kThreadsU) {
             const int r = i >> sh, c = i & (xld - 1);

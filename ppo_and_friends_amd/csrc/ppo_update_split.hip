@@ -20,10 +20,15 @@ namespace ppoaf {
 // 8.7 MB of slab round trip per mini-batch at C2 become 1.6 MB of panels, and the hidden-layer wgrad MFMAs leave
 // fwd_bwd's dependent chain.
 // ------------------------------------------------------------------------------------------------------------
-// MAXC = chunks of 16 rows a wave may own (B <= 512: 32 chunks over 4 waves)
-// XLD (the wide pair's launch only): the layer-0 panel's row stride is the network's u.sp.xld (64 | 128: PPOAF_SPLIT_WIDE_INPUTS);
-// every other pair's launch keeps the constant.
-template <int H, bool XLD>
+// MAXC = chunks of 16 rows a wave keeps in registers at a time (B <= 512: 32 chunks over 4 waves, one pass)
+// XLD (the wide pair's launch only): the layer-0 panel's row stride is the network's u.sp.xld (64 | 128: PPOAF_SPLIT_WIDE_INPUTS;
+// 256 | 512: PPOAF_SPLIT_WIDE_SHAPES); every other pair's launch keeps the constant.
+// PASSES (the wide pair's launch for a mini-batch of more than 32 chunks, B > 512: PPOAF_SPLIT_WIDE_SHAPES admits B <= 1024):
+// the request / MFMA sequence runs in passes of 4 MAXC = 32 chunks -- pass p covers chunks 32 p .. 32 p + 31, wave w keeps
+// chunks w, w + 4, ... of them -- into the same accumulators, so a wave adds its chunks in ascending order, and parks and
+// folds once.  (16 chunks per wave at once would be 192 VGPRs of operands.)  A kernel of its own (wgrad_launch): up to 32
+// chunks every pair, the wide one included, runs the one-pass kernel, whose text this leaves alone.
+template <int H, bool XLD, bool PASSES = false>
 __device__ __forceinline__ double split_wgrad_job(const UpdateDev& u, const int which, const int job, float* sFold /* wgrad_tile.hpp */) {
     constexpr int MAXC = 8;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -45,23 +50,47 @@ __device__ __forceinline__ double split_wgrad_job(const UpdateDev& u, const int 
         const unsigned dl = 4u * (unsigned)((lane >> 4) * H + ot * 16 + (lane & 15));
         const unsigned xl = 4u * (unsigned)((lane >> 4) * (int)ldx + itile * 16 + (lane & 15));
         const int nc = (B + 15) >> 4;                         // 16-row chunks of the mini-batch: one batch
-        float a[MAXC][4], x0[MAXC][4], x1[MAXC][4];
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-            const int ch = wave + 4 * c;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { a[c][j] = 0.f; x0[c][j] = 0.f; x1[c][j] = 0.f; }
-            if (ch < nc) {                                    // wave-uniform
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const WgradOff so = {4u * (unsigned)((16 * ch + 4 * j) * H), 4u * (unsigned)((16 * ch + 4 * j) * (int)ldx)};
-                    wgrad_request_quad(rd, rx, dl, xl, xl + 64u, two, so, a[c][j], x0[c][j], x1[c][j]);
-                }
-            }
-        }
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         float bsum = 0.f;
-        wgrad_mfma<MAXC>(a, x0, x1, two, wave, nc, acc0, acc1, bsum);
+        {
+            float a[MAXC][4], x0[MAXC][4], x1[MAXC][4];
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c) {
+                const int ch = wave + 4 * c;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { a[c][j] = 0.f; x0[c][j] = 0.f; x1[c][j] = 0.f; }
+                if (ch < nc) {                                // wave-uniform
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const WgradOff so = {4u * (unsigned)((16 * ch + 4 * j) * H), 4u * (unsigned)((16 * ch + 4 * j) * (int)ldx)};
+                        wgrad_request_quad(rd, rx, dl, xl, xl + 64u, two, so, a[c][j], x0[c][j], x1[c][j]);
+                    }
+                }
+            }
+            wgrad_mfma<MAXC>(a, x0, x1, two, wave, nc, acc0, acc1, bsum);
+        }
+        if constexpr (PASSES) {
+            // the same sequence again per further pass of 4 MAXC chunks, for a wave that has a chunk in it.  (A copy of the
+            // block above and not a loop around it: the first pass stays textually what every other pair's kernel compiles,
+            // so that those kernels keep their machine code.)
+            for (int c0 = wave + 4 * MAXC; c0 < nc; c0 += 4 * MAXC) {            // c0 = the wave's first chunk of the pass (scalar)
+                float a[MAXC][4], x0[MAXC][4], x1[MAXC][4];
+#pragma unroll
+                for (int c = 0; c < MAXC; ++c) {
+                    const int ch = c0 + 4 * c;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { a[c][j] = 0.f; x0[c][j] = 0.f; x1[c][j] = 0.f; }
+                    if (ch < nc) {                            // wave-uniform
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const WgradOff so = {4u * (unsigned)((16 * ch + 4 * j) * H), 4u * (unsigned)((16 * ch + 4 * j) * (int)ldx)};
+                            wgrad_request_quad(rd, rx, dl, xl, xl + 64u, two, so, a[c][j], x0[c][j], x1[c][j]);
+                        }
+                    }
+                }
+                wgrad_mfma<MAXC>(a, x0, x1, two, c0, nc, acc0, acc1, bsum);
+            }
+        }
         wgrad_park(sFold, wave, lane, acc0, acc1, bsum);
         if (wave == 0) wgrad_fold(sFold, lane, acc0, acc1);
         const long ldw = sj.ldw;
@@ -113,9 +142,34 @@ __global__ __launch_bounds__(kWgradThreads) void ppo_update_wgrad_kernel(UpdateD
     }
 }
 
+// ppo_update_wgrad_kernel for a mini-batch of more than 32 chunks (the wide pair with PPOAF_SPLIT_WIDE_SHAPES, B > 512)
+template <int HA, int HC>
+__global__ __launch_bounds__(kWgradThreads) void ppo_update_wgrad_passes_kernel(UpdateDev u, int jobs_a, int jobs_c, int per_xcd) {
+    __shared__ double s_red[17];
+    __shared__ __attribute__((aligned(16))) float s_fold[kWgradFoldFloats];
+    const int b = blockIdx.x;
+    if (b == 8 * per_xcd) { ppo_update_bookkeeping_split(u); return; }           // uniform per workgroup
+    const int job = (b & 7) * per_xcd + (b >> 3);
+    double q = 0.0;
+    if (job < jobs_a) q = split_wgrad_job<HA, true, true>(u, 0, job, s_fold);
+    else if (job < jobs_a + jobs_c) q = split_wgrad_job<HC, true, true>(u, 1, job - jobs_a, s_fold);
+    const bool actor = job < jobs_a;
+    q = block_sum(q, s_red);
+    if (threadIdx.x == 0) {
+        u.norm_scratch[6 + 2 * b] = actor ? q : 0.0;
+        u.norm_scratch[7 + 2 * b] = actor ? 0.0 : q;
+    }
+}
+
 template <int HA, int HC>
 static int wgrad_launch(const UpdateDev& u, hipStream_t s) {
     const int ja = split_wgrad_jobs(u.net[0]), jc = split_wgrad_jobs(u.net[1]), px = split_wgrad_per_xcd(u);
+    if constexpr (HC > 256) {                                 // a wide pair (the host admits B > 512 for no other)
+        if (u.B > 512) {
+            hipLaunchKernelGGL((ppo_update_wgrad_passes_kernel<HA, HC>), dim3((unsigned)(8 * px + 1)), dim3(kWgradThreads), 0, s, u, ja, jc, px);
+            return check_launch("ppo_update_wgrad");
+        }
+    }
     hipLaunchKernelGGL((ppo_update_wgrad_kernel<HA, HC>), dim3((unsigned)(8 * px + 1)), dim3(kWgradThreads), 0, s, u, ja, jc, px);
     return check_launch("ppo_update_wgrad");
 }
@@ -131,7 +185,8 @@ extern "C" int ppoaf_ppo_update_split_workspace_bytes(const ppoaf_ppo_update_arg
     UpdateDev u;
     int rc = make_update_dev(&a, u);
     if (rc) return rc;
-    if (!(args_wide_inputs(&a) && width_pair_is_wide(u.net[0].H, u.net[1].H)))      // (else: update_shapes' in_dim <= 128, B <= 512)
+    // (else: update_shapes' in_dim <= 128, B <= 512, or in_dim <= 512, B <= 1024 with PPOAF_SPLIT_WIDE_SHAPES)
+    if (!(args_wide_inputs(&a) && width_pair_is_wide(u.net[0].H, u.net[1].H)))
         PPOAF_REQUIRE(u.net[0].in_dim <= 64 && u.net[1].in_dim <= 64 && u.B <= 512,
                       "ppo_update_split_workspace_bytes: the split-wgrad chain covers in_dim <= 64 and B <= 512 (got %d / %d, %ld)",
                       u.net[0].in_dim, u.net[1].in_dim, u.B);

@@ -728,6 +728,9 @@ WIDTH_PAIRS = ((32, 32), (64, 64), (128, 128), (256, 256), (128, 256), (64, 128)
 # split-wgrad chain in its three-launch form, single rank, in_dim <= 64, batch sizes <= 512.  With the opt-in
 # `PPOPolicy.fused_wide_inputs` in_dim <= 128: the layer-0 panel of a network with more than 64 inputs takes a row stride of
 # 128 floats (the bit PPOAF_SPLIT_WIDE_INPUTS of ppoaf_ppo_update_args_t.row_pairs; csrc/ppo_update_dev.hpp: split_xld).
+# With the opt-in `PPOPolicy.fused_wide_shapes` (which implies the other; PPOAF_SPLIT_WIDE_SHAPES) in_dim <= 512, as far as
+# each row-tile body's LDS goes, on panels of stride 256 or 512, and batch sizes <= 1024: the weight-gradient launch then
+# runs a mini-batch of more than 32 chunks of 16 rows in passes of 32 (csrc/ppo_update_split.hip).
 WIDE_WIDTH_PAIRS = ((256, 512),)
 
 
@@ -736,14 +739,26 @@ def wide_critic(pol):
     return bool(getattr(pol, "fused_wide_critic", False))
 
 
+def wide_shapes(pol):
+    """The policy's wide pair may take in_dim <= 512 per network and batch sizes <= 1024 (PPOPolicy.fused_wide_shapes, set by
+    hand)."""
+    return bool(getattr(pol, "fused_wide_shapes", False))
+
+
 def wide_inputs(pol):
-    """The policy's wide pair may take 65 .. 128 inputs per network (PPOPolicy.fused_wide_inputs, set by hand)."""
-    return bool(getattr(pol, "fused_wide_inputs", False))
+    """The policy's wide pair may take 65 .. 128 inputs per network (PPOPolicy.fused_wide_inputs, set by hand, or implied by
+    PPOPolicy.fused_wide_shapes)."""
+    return bool(getattr(pol, "fused_wide_inputs", False)) or wide_shapes(pol)
+
+
+def wide_bits(pol):
+    """The option bits of ppoaf_ppo_update_args_t.row_pairs a wide pair of this policy sets."""
+    return _lib.SPLIT_WIDE_SHAPES if wide_shapes(pol) else _lib.SPLIT_WIDE_INPUTS if wide_inputs(pol) else 0
 
 
 def panel_stride(in_dim):
     """Row stride (floats) of a network's layer-0 panel in the split workspace (csrc/ppo_update_dev.hpp: split_xld)."""
-    return 64 if in_dim <= 64 else 128
+    return next((s for s in (64, 128, 256) if in_dim <= s), 512)
 
 
 class FusedPolicyUpdate(FusedEpoch):
@@ -778,11 +793,19 @@ class FusedPolicyUpdate(FusedEpoch):
             if max(a.in_dim, c.in_dim) > 64 and not wide_inputs(pol):
                 hint = "; PPOPolicy.fused_wide_inputs = True takes in_dim <= 128" if max(a.in_dim, c.in_dim) <= 128 else ""
                 return f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 64 (the split-wgrad chain's panels cover in_dim <= 64){hint}"
-            if max(a.in_dim, c.in_dim) > 128:
-                return (f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 128 (with fused_wide_inputs the split-wgrad chain's panels "
-                        "cover in_dim <= 128)")
-            if batch_size > 512:
-                return f"{pair}: batch size {batch_size} > 512 (the split-wgrad chain covers batch sizes <= 512)"
+            if wide_shapes(pol):
+                if max(a.in_dim, c.in_dim) > 512:
+                    return (f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 512 (with fused_wide_shapes the split-wgrad chain's panels "
+                            "cover in_dim <= 512)")
+                if batch_size > 1024:
+                    return (f"{pair}: batch size {batch_size} > 1024 (with fused_wide_shapes the split-wgrad chain covers batch "
+                            "sizes <= 1024)")
+            else:
+                if max(a.in_dim, c.in_dim) > 128:
+                    return (f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 128 (with fused_wide_inputs the split-wgrad chain's panels "
+                            "cover in_dim <= 128)")
+                if batch_size > 512:
+                    return f"{pair}: batch size {batch_size} > 512 (the split-wgrad chain covers batch sizes <= 512)"
             if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
                 return f"{pair}: PPOAF_SPLIT_WGRAD=0, and the wide pair has no slab form"
             if mpi_utils.get_num_procs() > 1:
@@ -791,7 +814,7 @@ class FusedPolicyUpdate(FusedEpoch):
         q = _lib.PpoUpdateArgs()
         q.actor, q.critic, q.bucket_total = a, c, a.size + c.size
         q.head_kind, q.B, q.batch_stride = head, batch_size, batch_size
-        q.row_pairs = _lib.SPLIT_WIDE_INPUTS if wide and wide_inputs(pol) else 0
+        q.row_pairs = wide_bits(pol) if wide else 0
         set_action_slices(q, action_head(pol)[1])
         if _lib.load().ppoaf_ppo_update_check(C.byref(q)) != 0:
             return _lib.load().ppoaf_last_error().decode("utf-8", "replace")
@@ -816,7 +839,8 @@ class FusedPolicyUpdate(FusedEpoch):
         self.actor_desc, _ = _describe(pol.actor, pol.policy_params, self.head == K.HEAD_GAUSSIAN)
         self.critic_desc, _ = _describe(pol.critic, pol.policy_params, False, wide_critic(pol))
         self.wide = (self.actor_desc.hidden, self.critic_desc.hidden) in WIDE_WIDTH_PAIRS
-        self.wide_inputs = self.wide and wide_inputs(pol)      # (read here, once: the args and the workspace are built from it)
+        # the wide pair's option bits (read here, once: the args and the workspace are built from them)
+        self.wide_bits = wide_bits(pol) if self.wide else 0
         self.n_wg = (self.B + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
         total = pol.policy_params.numel()
         # (a wide pair has no slab form: a placeholder for the args' pointer instead of n_wg x 0.75 M floats nothing reads)
@@ -892,7 +916,7 @@ class FusedPolicyUpdate(FusedEpoch):
         tail = self.tail_reason()
         line += "split-wgrad chain, " + ("fused tail" if tail == "" else f"wgrad and Adam launches ({tail})")
         return line + (f"; layer-0 panel stride {panel_stride(a.in_dim)} (actor) / {panel_stride(c.in_dim)} (critic) floats"
-                       f"{', fused_wide_inputs' if self.wide_inputs else ''}")
+                       f"{', fused_wide_shapes' if self.wide_bits & _lib.SPLIT_WIDE_SHAPES else ', fused_wide_inputs' if self.wide_bits else ''}")
 
     def gradient_only(self, args, timing_events=(None, None)):
         """fwd_bwd + the launch that completes the gradient bucket (wgrad / slab reduce) of ONE mini-batch, no optimiser step:
@@ -984,8 +1008,9 @@ class FusedPolicyUpdate(FusedEpoch):
         _loss_args(self, a, B)
         a.xcd_half = getattr(self, "xcd_half", 0)        # 1 / 2: beside the ICM chain (ppo.py: _ppo_icm_epoch_overlapped)
         a.split_workspace, a.split_workspace_bytes = None, 0
-        # (args.row_pairs is a bit set: the row pairs, and a wide pair's 65 .. 128 inputs -- never both, a wide pair runs no pairs)
-        a.row_pairs = wide_bit = _lib.SPLIT_WIDE_INPUTS if self.wide_inputs else 0
+        # (args.row_pairs is a bit set: the row pairs, and a wide pair's wider inputs and larger batches -- never both, a wide
+        #  pair runs no pairs)
+        a.row_pairs = wide_bit = self.wide_bits
         if self.split:
             a.row_pairs = wide_bit | int(self.pairs_reason() == "")
             if self._split_space is None:            # sized once for the full batch size; a tail mini-batch needs less

@@ -105,6 +105,12 @@ class PPOPolicy:
     # PPOAF_SPLIT_WIDE_INPUTS).  Set by hand, on the class or on the policy, before the first rollout -- no update_mode sets it.  False:
     # the torch path for those shapes, with today's messages; at in_dim <= 64 the flag changes nothing, bitwise.
     fused_wide_inputs = False
+    # Opt-in, implies `fused_wide_inputs`: the wide pair at in_dim <= 512 per network (as far as each row-tile body's LDS goes:
+    # a 256-wide actor of depth 1 / 2 holds 512 inputs, of depth 3 432, of depth 4 160) and batch sizes <= 1024 on K6+K7 and
+    # K12 (the library's PPOAF_SPLIT_WIDE_SHAPES: layer-0 panels of stride 256 or 512, the weight-gradient launch in passes of
+    # 32 chunks of 16 rows).  Set by hand, on the class or on the policy, before the first rollout -- no update_mode sets it.
+    # False: the torch path for those shapes, with today's messages; inside the other opt-in's limits the flag changes nothing, bitwise.
+    fused_wide_shapes = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -757,7 +763,7 @@ class PPOPolicy:
             return "LSTM policies are not K19's: K21 or forward_logits (see lstm_step_unsupported_reason)"
         # (asked once per evaluation step: the answer is kept for as long as what it depends on stays)
         key = (self.policy_params.data_ptr(), bool(self.fused_action_heads), bool(self.fused_wide_critic),
-               bool(self.fused_wide_inputs))
+               bool(self.fused_wide_inputs), bool(self.fused_wide_shapes))
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
             self._infer_reason = (key, self.fused_step_unsupported_reason())
         return self._infer_reason[1]

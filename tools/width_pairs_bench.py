@@ -20,7 +20,14 @@ is the wide pair (K12 ends in the wgrad and Adam launches there: profiles/wide_c
 
     python tools/width_pairs_bench.py --widths 256 512 --obs-dim 128 --wide-inputs --batch 128
 
-is `breakout_ram` / `mario_bros_ram` (128 RAM bytes, batch 128: 4096 mini-batches per epoch; profiles/wide_inputs.txt).
+is `breakout_ram` / `mario_bros_ram` at --hist_size 1 (128 RAM bytes, batch 128: 4096 mini-batches per epoch;
+profiles/wide_inputs.txt).  --wide-shapes sets PPOPolicy.fused_wide_shapes instead (in_dim <= 512, mini-batches <= 1024):
+
+    python tools/width_pairs_bench.py --widths 256 512 --obs-dim 256 --wide-shapes --batch 128
+    python tools/width_pairs_bench.py --widths 256 512 --obs-dim 142 --wide-shapes --batch 1000
+
+are `breakout_ram` at the reference's default --hist_size 2 and the critic of `robot_warehouse`'s MAPPO members at their
+default batch (profiles/wide_shapes.txt).
 """
 import argparse
 import json
@@ -84,6 +91,8 @@ def main():
                     help="this pair, fused against torch, at bipedal_walker_hardcore's dimensions (default: the 64 / 256 legs)")
     ap.add_argument("--obs-dim", type=int, default=None, help="with --widths: this many observations and Discrete(4) actions")
     ap.add_argument("--wide-inputs", action="store_true", help="PPOPolicy.fused_wide_inputs = True (a wide pair above 64 inputs)")
+    ap.add_argument("--wide-shapes", action="store_true",
+                    help="PPOPolicy.fused_wide_shapes = True (a wide pair above 128 inputs or above 512 rows per mini-batch)")
     ap.add_argument("--batch", type=int, default=BATCH, help="mini-batch size")
     args = ap.parse_args()
     if args.obs_dim is not None and not args.widths:
@@ -92,6 +101,9 @@ def main():
     if args.wide_inputs:
         from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
         PPOPolicy.fused_wide_inputs = True
+    if args.wide_shapes:
+        from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
+        PPOPolicy.fused_wide_shapes = True
     legs, pair = LEGS, "64x256"
     if args.widths:
         pair = f"{args.widths[0]}x{args.widths[1]}"
@@ -100,6 +112,8 @@ def main():
     result = {"transitions": n, "batch_size": BATCH, "minibatches_per_epoch": (n + BATCH - 1) // BATCH, "repeats": args.repeats}
     if args.obs_dim is not None:
         result.update(obs_dim=args.obs_dim, wide_inputs=bool(args.wide_inputs))
+        if args.wide_shapes:
+            result.update(wide_shapes=True)
     ppos = {k: make_ppo(w, m, args.envs, args.steps, walker=bool(args.widths), obs_dim=args.obs_dim) for k, (w, m) in legs.items()}
     for k, ppo in ppos.items():                      # the path each leg takes, as the JSON line reports it
         pol = ppo.policies["p"]
