@@ -330,6 +330,13 @@ int ppoaf_adam_step_prenormed(float* params, const float* grads,
  * (32,64); depth >= 1.  One list names them for every launch of K6+K7 and K12
  * (csrc/ppo_update_dev.hpp: PPOAF_WIDTH_PAIRS); a critic narrower than its
  * actor and 512-wide networks are refused.
+ * out_dim: 1 .. 8.  The 256-wide actor of the wide pair (256, 512) takes
+ * 9 .. 24 outputs under PPOAF_HEAD_CATEGORICAL and PPOAF_HEAD_GAUSSIAN (the
+ * wide heads: Discrete(18), Box(17)) in ppoaf_policy_step, its block form and
+ * ppoaf_ppo_update_*, on kernels of their own that the library picks from
+ * out_dim (csrc/policy_wide_heads.hip, csrc/ppo_update_wide_heads.hip); a
+ * launch with out_dim <= 8 runs the kernel it always ran.  The two other
+ * heads, every other pair and out_dim > 24 are refused by name.
  * ------------------------------------------------------------------------ */
 #define PPOAF_ACT_RELU        0
 #define PPOAF_ACT_LEAKY_RELU  1      /* negative slope 0.01 (nn.LeakyReLU default) */
@@ -535,7 +542,9 @@ int ppoaf_policy_step(const ppoaf_policy_step_args_t* args, ppoaf_stream_t strea
  *                              action is bitwise ppoaf_policy_step's action_out
  *   PPOAF_INFER_DETERMINISTIC  argmax (lowest index on an exact tie), argmax per slice, z >= 0 per bit, tanh(mean)
  *                              rescaled into [act_lo, act_hi]; seed / offset are not read
- * No log-prob, no value, no observation copies.  Shapes as K6: hidden width 32 / 64 / 128 / 256, out_dim <= 8.
+ * No log-prob, no value, no observation copies.  Shapes as K6: hidden width 32 / 64 / 128 / 256, out_dim <= 8; a
+ * 256-wide actor takes out_dim 9 .. 24 under the categorical and the Gaussian head (the wide heads, a kernel of their
+ * own: csrc/policy_wide_heads.hip; no critic here, so no pair is asked for).
  * ------------------------------------------------------------------------ */
 #define PPOAF_INFER_SAMPLE        0
 #define PPOAF_INFER_DETERMINISTIC 1

@@ -1,4 +1,5 @@
-// Action heads on <= 8 actor outputs, one lane per row.  The Categorical and tanh-Gaussian rows of a rollout step and of
+// Action heads on <= 8 actor outputs (Categorical and tanh-Gaussian: <= 24 for the wide heads of the 256/512 pair), one lane
+// per row.  The Categorical and tanh-Gaussian rows of a rollout step and of
 // an evaluation step: one copy for the MLP kernels (K6, K19) and the LSTM kernel (K21).  The MultiDiscrete and
 // MultiBinary heads: shared by the rollout step (K6+K7,
 // policy_step.hip) and the fused update (K12, ppo_update_dev.hpp: ppo_head_loss).  Both take a row's log-prob from the
@@ -43,22 +44,25 @@ inline int check_action_head(const char* what, int head_kind, const ppoaf_mlp_de
 
 // ---- sampling pieces shared by the rollout step (K6) and the evaluation step (K19, policy_infer.hip): one copy, so
 // that a sampled evaluation action is bitwise the rollout's for the same (outputs, seed, counter)
-// Discrete: softmax of the row's <= 8 outputs -> p (padding classes 0); returns the sum of p (Categorical's own
-// renormaliser, ~1)
+// Discrete: softmax of the row's <= K outputs -> p (padding classes 0); returns the sum of p (Categorical's own
+// renormaliser, ~1).  K = 8, or 24 for the wide heads of the 256/512 pair (instantiations of their own): classes 0 .. 7 take
+// the same operations in the same order under both.
+template <int K = 8>
 __device__ __forceinline__ float cat_probs(const float* z, const int out_dim, float* p) {
     float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) if (k < out_dim) m = fmaxf(m, z[k]);
+    for (int k = 0; k < K; ++k) if (k < out_dim) m = fmaxf(m, z[k]);
     float ssum = 0.f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { p[k] = k < out_dim ? expf(z[k] - m) : 0.f; ssum += p[k]; }
+    for (int k = 0; k < K; ++k) { p[k] = k < out_dim ? expf(z[k] - m) : 0.f; ssum += p[k]; }
     const float inv = 1.0f / ssum;
     float s2 = 0.f;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { p[k] *= inv; s2 += p[k]; }
+    for (int k = 0; k < K; ++k) { p[k] *= inv; s2 += p[k]; }
     return s2;
 }
 // the row with Philox counter `ctr` draws (seed, ctr, 0).x and takes the inverse CDF over the unnormalised mass
+template <int K = 8>
 __device__ __forceinline__ int cat_sample(const float* p, const float s2, const int out_dim,
                                           const unsigned long long seed, const unsigned long long ctr) {
     int a = out_dim - 1;
@@ -67,7 +71,7 @@ __device__ __forceinline__ int cat_sample(const float* p, const float s2, const 
     const float uu = u32_to_unit(rnd.x) * s2;
     bool found = false;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < K; ++k) {
         if (k < out_dim) {
             c += p[k];
             if (!found && uu < c) { a = k; found = true; }
@@ -93,21 +97,22 @@ __device__ __forceinline__ float unit_to_bounds(float a, float lo, float hi) { r
 // lstm_policy_step.hip, share the *_step_row pair) and the evaluation step (K19, policy_infer.hip, and K21's INFER mode
 // share the *_infer_row pair).  z / mean: the row's outputs; the row's Philox counter is offset + e.
 // Discrete: sample (or the forced raw action, clamped into the classes) -> raw action, action, log-prob
+template <int K = 8>
 __device__ __forceinline__ void cat_step_row(const float* z, const int out_dim, const void* forced_raw_action, const long e,
                                              const unsigned long long seed, const unsigned long long offset,
                                              void* raw_action_out, void* action_out, float* logp_out) {
-    float p[8];
-    const float s2 = cat_probs(z, out_dim, p);
+    float p[K];
+    const float s2 = cat_probs<K>(z, out_dim, p);
     int a;
     float pa = p[0];
     if (forced_raw_action) {
         const long fa = reinterpret_cast<const int64_t*>(forced_raw_action)[e];
         a = fa < 0 ? 0 : (fa >= out_dim ? out_dim - 1 : (int)fa);
     } else {
-        a = cat_sample(p, s2, out_dim, seed, offset + (unsigned long long)e);
+        a = cat_sample<K>(p, s2, out_dim, seed, offset + (unsigned long long)e);
     }
 #pragma unroll
-    for (int k = 0; k < 8; ++k) if (k == a) pa = p[k];
+    for (int k = 0; k < K; ++k) if (k == a) pa = p[k];
     reinterpret_cast<int64_t*>(raw_action_out)[e] = a;
     reinterpret_cast<int64_t*>(action_out)[e] = a;
     logp_out[e] = logf(clamp_prob_u(pa / s2));
@@ -146,6 +151,7 @@ __device__ __forceinline__ void gauss_step_row(const float* mean_row, const int 
 }
 // Discrete, evaluation: the argmax, the lowest index on an exact tie (torch.argmax on the reference's CPU tensors), or a
 // sample -> the env action
+template <int K = 8>
 __device__ __forceinline__ void cat_infer_row(const float* zr, const int out_dim, const bool greedy, const long e,
                                               const unsigned long long seed, const unsigned long long offset,
                                               void* action_out) {
@@ -153,12 +159,12 @@ __device__ __forceinline__ void cat_infer_row(const float* zr, const int out_dim
     if (greedy) {
         float best = zr[0];
 #pragma unroll
-        for (int k = 1; k < 8; ++k)
+        for (int k = 1; k < K; ++k)
             if (k < out_dim && zr[k] > best) { best = zr[k]; a = k; }
     } else {
-        float p[8];
-        const float s2 = cat_probs(zr, out_dim, p);
-        a = cat_sample(p, s2, out_dim, seed, offset + (unsigned long long)e);
+        float p[K];
+        const float s2 = cat_probs<K>(zr, out_dim, p);
+        a = cat_sample<K>(p, s2, out_dim, seed, offset + (unsigned long long)e);
     }
     reinterpret_cast<int64_t*>(action_out)[e] = a;
 }

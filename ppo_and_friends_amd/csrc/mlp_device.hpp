@@ -474,7 +474,7 @@ __device__ __forceinline__ void layer_wgrad(const float* __restrict__ D, const f
 // ---- the 16-row MLP forward of the rollout step (K6, policy_step.hip) and of the evaluation step (K19,
 // policy_infer.hip): one workgroup of kThreadsU threads takes rows [e0, e0 + 16) of `src` ([E, in_dim]) through the
 // network `nd` of the bucket `params` -- first layer (K = in_dim, zero padded) / hidden layers (same tile code as the
-// update's forward) / output layer (<= 8 outputs, 16 lanes per row) -- and leaves the outputs in LDS: returns
+// update's forward) / output layer (<= KO outputs, 16 lanes per row) -- and leaves the outputs in LDS: returns
 // sOut[16][kMaxOut], valid after the function's last barrier.  Both kernels instantiate THIS code, so a row's outputs
 // are bitwise the same in both.  `cpy` (may be NULL): the observation rows are copied there on the way in.
 // smem: mlp_rows_forward_lds_floats(nd) floats of dynamic LDS, 16-byte aligned.
@@ -490,7 +490,11 @@ struct BlockRows {
     }
 };
 
-template <int HT, class Rows = void>
+// KO: the output rows the carve holds, 8, or 24 for the wide heads of the 256/512 pair (kernels of their own:
+// policy_wide_heads.hip) -- sWout [KO, H], and sOut rows mlp_rows_out_stride(KO) floats apart.
+constexpr int kWideOut = 24;                      // the most outputs of a wide actor head
+constexpr int mlp_rows_out_stride(const int KO) { return KO <= 8 ? kMaxOut : KO; }
+template <int HT, class Rows = void, int KO = 8>
 __device__ __forceinline__ const float* mlp_rows_forward(const NetDev& nd, const float* __restrict__ params,
                                                          const float* __restrict__ src, float* __restrict__ cpy,
                                                          const long E, const long e0, float* smem,
@@ -507,11 +511,12 @@ __device__ __forceinline__ const float* mlp_rows_forward(const NetDev& nd, const
     };
 
     float* sBias = smem;                                   // [(depth+1), H]
-    float* sWout = sBias + (depth + 1) * H;                // [8, H]
-    float* sX = sWout + 8 * H;                             // [16, INP]
+    constexpr int OS = mlp_rows_out_stride(KO);
+    float* sWout = sBias + (depth + 1) * H;                // [KO, H]
+    float* sX = sWout + KO * H;                            // [16, INP]
     float* sH0 = sX + kRows * INP;                         // [16, HS] ping
     float* sH1 = sH0 + kRows * HS;                         // [16, HS] pong
-    float* sOut = sH1 + kRows * HS;                        // [16, 16]
+    float* sOut = sH1 + kRows * HS;                        // [16, OS]
 
     for (int l = 0; l <= depth; ++l) {
         const int n = (l == depth) ? out_dim : H;
@@ -577,19 +582,23 @@ __device__ __forceinline__ const float* mlp_rows_forward(const NetDev& nd, const
 #pragma unroll
             for (int i = 0; i < HT; ++i) acc = fmaf(Hp[s * HS + part + 16 * i], sWout[k * H + part + 16 * i], acc);
             acc = group16_sum(acc);
-            if (part == 0) sOut[s * kMaxOut + k] = acc + sBias[depth * H + k];
+            if (part == 0) sOut[s * OS + k] = acc + sBias[depth * H + k];
         }
     }
     __syncthreads();
     return sOut;
 }
-// host: the floats of LDS mlp_rows_forward takes for this network
+// host: the floats of LDS mlp_rows_forward takes for this network (more than 8 outputs: the KO = 24 carve of the wide heads)
 inline size_t mlp_rows_forward_lds_floats(const NetDev& n) {
     const size_t HS = n.H + 4, INP = 16 * ((n.in_dim + 15) / 16) + 4;
-    return (size_t)(n.depth + 1) * n.H + 8 * (size_t)n.H + kRows * INP + 2 * kRows * HS + kRows * kMaxOut;
+    const size_t KO = n.out_dim > 8 ? kWideOut : 8;
+    return (size_t)(n.depth + 1) * n.H + KO * (size_t)n.H + kRows * INP + 2 * kRows * HS + kRows * mlp_rows_out_stride((int)KO);
 }
 
-// host: validate a network descriptor and fill the device view
+// host: validate a network descriptor and fill the device view.  out_dim: 1 .. 8, and 9 .. kWideOut for ANY 256-wide
+// descriptor -- that such a network is the actor of the wide pair under a head that has wide kernels is the CALLER's to
+// check (check_wide_head, ppo_update_dev.hpp, as ppoaf_policy_step, ppoaf_policy_infer and ppoaf_ppo_update_* do, beside
+// their "critic out_dim must be 1"): every kernel but the wide heads' keeps 8 values per row in registers.
 int fill_net(const ppoaf_mlp_desc_t& d, NetDev& n, const char* what);
 
 }  // namespace ppoaf

@@ -8,24 +8,10 @@
 // K6 (policy_step.hip) instantiates for its actor half, and sampling goes through K6's own pieces (action_heads.hpp) with
 // K6's Philox counters: for equal (obs, params, seed, offset) a sampled action is bitwise K6's action_out.  No critic,
 // no log-prob, no buffer rows: half of K6's workgroups and all but one of its stores are not there.
-#include <cstddef>
-
-#include "action_heads.hpp"
+// Actor outputs: <= 8; a 256-wide actor with 9 .. 24 outputs (Categorical, Gaussian) runs policy_wide_heads.hip's kernel.
+#include "policy_rows.hpp"          // InferDev (shared with policy_wide_heads.hip)
 
 namespace ppoaf {
-
-struct InferDev {
-    NetDev net;
-    const float* params;
-    const float* obs; long E;
-    int head_kind, mode; float min_std;
-    const float* act_lo; const float* act_hi;
-    unsigned long long seed, offset;
-    void* action_out;
-    int n_slices; int slices[8];
-};
-
-extern __shared__ __attribute__((aligned(16))) unsigned char policy_infer_smem[];
 
 template <int HT, bool XH>
 __global__ __launch_bounds__(kThreadsU) void policy_infer_kernel(InferDev u) {
@@ -252,6 +238,8 @@ extern "C" int ppoaf_policy_infer(const ppoaf_policy_infer_args_t* a, ppoaf_stre
     rc = check_action_head("policy_infer", a->head_kind, a->actor,
                            a->head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? a->n_action_slices : 0, a->action_slices);
     if (rc) return rc;
+    rc = check_wide_head("policy_infer", a->actor, a->head_kind, 0);
+    if (rc) return rc;
     PPOAF_REQUIRE(a->params && a->obs && a->action_out, "policy_infer: null pointer");
     PPOAF_REQUIRE((a->act_lo == nullptr) == (a->act_hi == nullptr), "policy_infer: give both action bounds or neither");
     if (a->E == 0) return PPOAF_OK;
@@ -264,6 +252,7 @@ extern "C" int ppoaf_policy_infer(const ppoaf_policy_infer_args_t* a, ppoaf_stre
     const size_t lds = (mlp_rows_forward_lds_floats(u.net) * 4 + 15) / 16 * 16;
     PPOAF_REQUIRE(lds <= 160 * 1024, "policy_infer: needs %zu B of LDS", lds);
     hipStream_t s = (hipStream_t)stream;
+    if (u.net.out_dim > 8) return launch_infer_wide_heads(u, lds, s);         // (a 256-wide actor, Categorical or Gaussian: checked above)
     return u.head_kind >= PPOAF_HEAD_MULTI_CATEGORICAL ? launch_infer_width<true>(u, lds, s) : launch_infer_width<false>(u, lds, s);
 }
 

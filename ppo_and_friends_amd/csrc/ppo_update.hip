@@ -231,7 +231,13 @@ int fill_net(const ppoaf_mlp_desc_t& d, NetDev& n, const char* what) {
                   "%s: hidden=%d must be a multiple of 16 in [16,512]", what, d.hidden);
     PPOAF_REQUIRE(d.depth >= 1 && d.depth + 1 <= kMaxLayers, "%s: depth=%d out of [1,%d]", what, d.depth, kMaxLayers - 1);
     PPOAF_REQUIRE(d.in_dim >= 1 && d.in_dim <= 1024, "%s: in_dim=%d", what, d.in_dim);
-    PPOAF_REQUIRE(d.out_dim >= 1 && d.out_dim <= 8, "%s: out_dim=%d out of [1,8]", what, d.out_dim);
+    // (a 256-wide network may be the actor of the wide pair, whose heads take 9 .. kWideOut outputs: the entry points check the
+    //  pair and the head kind, check_wide_head)
+    if (d.hidden == 256 && d.out_dim > 8)
+        PPOAF_REQUIRE(d.out_dim <= kWideOut, "%s: out_dim=%d out of [1,%d] (a 256-wide actor's wide heads, beside a 512-wide critic, "
+                      "take 9 .. %d outputs; every other network [1,8])", what, d.out_dim, kWideOut, kWideOut);
+    else
+        PPOAF_REQUIRE(d.out_dim >= 1 && d.out_dim <= 8, "%s: out_dim=%d out of [1,8]", what, d.out_dim);
     PPOAF_REQUIRE(d.activation >= 0 && d.activation <= 2, "%s: activation=%d", what, d.activation);
     PPOAF_REQUIRE(d.offset % 4 == 0, "%s: bucket offset must be 16-byte aligned", what);
     n.in_dim = d.in_dim; n.H = d.hidden; n.depth = d.depth; n.out_dim = d.out_dim; n.act = d.activation;
@@ -268,6 +274,8 @@ static int update_shapes(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
     PPOAF_REQUIRE(a->critic.out_dim == 1 && a->critic.log_std_offset < 0, "ppo_update: critic out_dim must be 1");
     rc = check_action_head("ppo_update", a->head_kind, a->actor,
                            a->head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? a->n_action_slices : 0, a->action_slices);
+    if (rc) return rc;
+    rc = check_wide_head("ppo_update", a->actor, a->head_kind, a->critic.hidden);
     if (rc) return rc;
     PPOAF_REQUIRE(a->B >= 2 && a->batch_stride >= a->B, "ppo_update: B=%ld stride=%ld", (long)a->B,
                   (long)a->batch_stride);
@@ -352,7 +360,9 @@ int make_update_dev(const ppoaf_ppo_update_args_t* a, UpdateDev& u) {
 
 static size_t fwd_bwd_lds_bytes(const UpdateDev& u) {
     if (width_pair_is_wide(u.net[0].H, u.net[1].H)) {       // the critic's body has a carve of its own, without line slots
-        const size_t a = (rowtile_lds_floats(u.net[0]) * 4 + 15) / 16 * 16 + kRowtileLineFloats * 4;
+        // (more than 8 actor outputs: the wide-head body's carve, ppo_update_rowtile_heads.hpp)
+        const size_t af = u.net[0].out_dim > 8 ? rowtile_heads_lds_floats(u.net[0]) : rowtile_lds_floats(u.net[0]);
+        const size_t a = (af * 4 + 15) / 16 * 16 + kRowtileLineFloats * 4;
         const size_t c = (rowtile_wide_lds_floats(u.net[1]) * 4 + 15) / 16 * 16;
         return a > c ? a : c;
     }
@@ -396,7 +406,8 @@ extern "C" int ppoaf_ppo_update_fwd_bwd_timed(const ppoaf_ppo_update_args_t* arg
 #define PPOAF_WIDTH_PAIR_CALL_(A, C) fwd_bwd_launch_pair<A, C>(L)
     PPOAF_WIDTH_PAIR_LADDER_OF(PPOAF_WIDTH_PAIRS_IN_UPDATE, u.net[0].H, u.net[1].H)
 #undef PPOAF_WIDTH_PAIR_CALL_
-    if (width_pair_is_wide(u.net[0].H, u.net[1].H)) return fwd_bwd_launch_wide(L);
+    if (width_pair_is_wide(u.net[0].H, u.net[1].H))
+        return u.net[0].out_dim > 8 ? fwd_bwd_launch_wide_heads(L) : fwd_bwd_launch_wide(L);
     return fwd_bwd_launch_narrow(L);
 }
 

@@ -91,12 +91,38 @@ inline bool width_pair_is_wide(const int ha, const int hc) {
 #undef PPOAF_WIDTH_PAIR_CALL_
     return false;
 }
+// host: more than 8 actor outputs -- the wide heads' scope (fill_net has admitted 9 .. kWideOut at a 256-wide network): the head
+// kinds that have them and, for the entry points with a critic, the width pair.  `what`: the entry point's name;
+// critic_hidden: 0 where there is no critic (K19).
+inline int check_wide_head(const char* what, const ppoaf_mlp_desc_t& actor, int head_kind, int critic_hidden) {
+    if (actor.out_dim <= 8) return PPOAF_OK;
+    PPOAF_REQUIRE(head_kind == PPOAF_HEAD_CATEGORICAL || head_kind == PPOAF_HEAD_GAUSSIAN,
+                  "%s: actor out_dim=%d with head_kind=%d: the wide heads (out_dim 9 .. %d) are Categorical (0) and Gaussian (1); a "
+                  "multi-categorical or Bernoulli head covers out_dim in [1,8]", what, actor.out_dim, head_kind, kWideOut);
+    PPOAF_REQUIRE(critic_hidden == 0 || width_pair_is_wide(actor.hidden, critic_hidden),
+                  "%s: actor out_dim=%d at hidden widths (actor %d, critic %d): the wide heads (out_dim 9 .. %d) exist for the wide "
+                  "pair (actor 256, critic 512) only; this pair covers out_dim in [1,8]", what, actor.out_dim, actor.hidden,
+                  critic_hidden, kWideOut);
+    return PPOAF_OK;
+}
+
 // dynamic LDS of the wide critic's row-tile body (the carve of ppo_update_rowtile_wide.hpp): the row tables, biases, ONE
 // output row of weights, the input rows, three activation-sized planes and the output / d output tiles.  No line slots:
 // 124.7 KB at depth 7 and in_dim 64.
 inline size_t rowtile_wide_lds_floats(const NetDev& n) {
     const size_t HS = n.H + 4, INP = 16 * ((n.in_dim + 15) / 16) + 4;
     return 208 + (size_t)(n.depth + 1) * n.H + (size_t)n.H + kRows * INP + 3 * kRows * HS + 2 * kRows * kMaxOut;
+}
+// dynamic LDS of the wide-head actor's row-tile body (the carve of ppo_update_rowtile_heads.hpp), without the line slots:
+// rowtile_lds_floats' terms (ppo_update_rowtile.hpp) but for a floor under the input rows, whose region holds d loss / d out
+// and the per-row d / d log_std, [16][24] each, once layer 0 has run -- more than the rows themselves below 33 inputs only.
+constexpr int kHeadStride = kWideOut;                     // floats between the rows of the output tiles and the action words
+constexpr int kHeadXFloats = 2 * kRows * kHeadStride;
+inline size_t rowtile_heads_lds_floats(const NetDev& n) {
+    const size_t HS = n.H + 4, INP = 16 * ((n.in_dim + 15) / 16) + 4;
+    const size_t x = kRows * INP > (size_t)kHeadXFloats ? kRows * INP : (size_t)kHeadXFloats;
+    return 208 + (size_t)(n.depth + 1) * n.H + 8 * (size_t)n.H + x + (size_t)n.depth * kRows * HS + 2 * kRows * HS +
+           2 * kRows * kMaxOut;
 }
 
 // Per-mini-batch panels shared by the layered mode of the two-XCD persistent kernel and by the split-wgrad chain

@@ -126,5 +126,7 @@ inline int fwd_bwd_launch_pair(const FwdBwdLaunch& L) {
 int fwd_bwd_launch_narrow(const FwdBwdLaunch& L);
 // the wide pairs' rungs (ppo_update_wide.hip): the split-wgrad chain only, one workgroup per tile
 int fwd_bwd_launch_wide(const FwdBwdLaunch& L);
+// ... with more than 8 actor outputs (ppo_update_wide_heads.hip: the wide heads, a kernel of their own)
+int fwd_bwd_launch_wide_heads(const FwdBwdLaunch& L);
 
 }  // namespace ppoaf

@@ -72,9 +72,10 @@ def set_action_slices(args, slices):
         args.action_slices[j] = slices[j] if j < len(slices) else 0
 
 
-def _describe(net, bucket, with_log_std, wide=False):
+def _describe(net, bucket, with_log_std, wide=False, max_out=8):
     """MlpDesc of a FeedForwardNetwork living in `bucket`, or (None, reason).  wide: a 512-wide network is described too
-    (the critic of a policy with `fused_wide_critic`: WIDE_WIDTH_PAIRS)."""
+    (the critic of a policy with `fused_wide_critic`: WIDE_WIDTH_PAIRS).  max_out: the widest output layer taken (8, or
+    WIDE_HEAD_MAX for the actor of a policy with `fused_wide_heads`: actor_out_limit)."""
     if not isinstance(net, FeedForwardNetwork) or net.is_embedded:
         return None, "network is not a plain FeedForwardNetwork"
     dims = net.layer_dims()
@@ -89,8 +90,8 @@ def _describe(net, bucket, with_log_std, wide=False):
     if act is None:
         return None, f"activation {net.activation} is not one of ReLU / LeakyReLU(0.01) / Tanh"
     out_dim = dims[-1][1]
-    if out_dim > 8:
-        return None, f"output width {out_dim} > 8"
+    if out_dim > max_out:
+        return None, f"output width {out_dim} > {max_out}"
     d = _lib.MlpDesc()
     d.in_dim, d.hidden, d.depth, d.out_dim, d.activation = dims[0][0], H, len(dims) - 1, out_dim, act
     base = bucket.data_ptr()
@@ -751,6 +752,34 @@ def wide_inputs(pol):
     return bool(getattr(pol, "fused_wide_inputs", False)) or wide_shapes(pol)
 
 
+# With the opt-in `PPOPolicy.fused_wide_heads` the wide pair's actor takes 9 .. WIDE_HEAD_MAX outputs under a Categorical or a
+# tanh-Gaussian head (Discrete(18), Box(17)): kernels of their own for K6+K7, K12's fwd_bwd and K19 (csrc/policy_wide_heads.hip,
+# csrc/ppo_update_wide_heads.hip), chosen by the library from out_dim.  Every other pair and head keeps 8.
+WIDE_HEAD_MAX = 24
+
+
+def wide_heads(pol):
+    """The policy's wide pair may take an actor head of 9 .. WIDE_HEAD_MAX outputs (PPOPolicy.fused_wide_heads, set by hand)."""
+    return bool(getattr(pol, "fused_wide_heads", False))
+
+
+def actor_out_limit(pol, head):
+    """The widest actor output layer `_describe` takes for this policy: WIDE_HEAD_MAX for a Categorical or Gaussian head of a
+    policy with `fused_wide_heads` and `fused_wide_critic` (that the pair is the wide one is checked where both networks are
+    known: wide_head_reason), else 8."""
+    ok = wide_heads(pol) and wide_critic(pol) and head in (K.HEAD_CATEGORICAL, K.HEAD_GAUSSIAN)
+    return WIDE_HEAD_MAX if ok else 8
+
+
+def wide_head_reason(a, c):
+    """'' for described networks whose actor head the kernels take, else the limit: more than 8 outputs exist at the wide pair
+    only."""
+    if a.out_dim <= 8 or (a.hidden, c.hidden) in WIDE_WIDTH_PAIRS:
+        return ""
+    return (f"hidden widths (actor {a.hidden}, critic {c.hidden}): actor output width {a.out_dim} > 8 (fused_wide_heads takes "
+            f"9 .. {WIDE_HEAD_MAX} outputs at the wide pair {WIDE_WIDTH_PAIRS[0]} only)")
+
+
 def wide_bits(pol):
     """The option bits of ppoaf_ppo_update_args_t.row_pairs a wide pair of this policy sets."""
     return _lib.SPLIT_WIDE_SHAPES if wide_shapes(pol) else _lib.SPLIT_WIDE_INPUTS if wide_inputs(pol) else 0
@@ -773,7 +802,7 @@ class FusedPolicyUpdate(FusedEpoch):
         head, _, why = action_head(pol)
         if head is None:
             return why
-        a, why = _describe(pol.actor, pol.policy_params, head == K.HEAD_GAUSSIAN)
+        a, why = _describe(pol.actor, pol.policy_params, head == K.HEAD_GAUSSIAN, False, actor_out_limit(pol, head))
         if a is None:
             return "actor: " + why
         c, why = _describe(pol.critic, pol.policy_params, False, wide_critic(pol))
@@ -786,6 +815,8 @@ class FusedPolicyUpdate(FusedEpoch):
         wide = (a.hidden, c.hidden) in WIDE_WIDTH_PAIRS          # (a 512-wide critic is described for wide_critic(pol) only)
         if (a.hidden, c.hidden) not in WIDTH_PAIRS and not wide:
             return f"hidden widths (actor {a.hidden}, critic {c.hidden}) are not an instantiated pair"
+        if wide_head_reason(a, c):
+            return wide_head_reason(a, c)
         if batch_size < 2:
             return "batch size < 2"
         if wide:
@@ -831,12 +862,31 @@ class FusedPolicyUpdate(FusedEpoch):
         finally:
             pol.fused_wide_critic = False
 
+    @staticmethod
+    def wide_heads_would_take(pol, batch_size):
+        """True for a policy that is refused only because `fused_wide_heads` is off -- under "auto", together with
+        `fused_wide_critic` (what `verbose` adds to the refusal)."""
+        if wide_heads(pol) or pol.using_lstm or pol.agent_grouping:
+            return False
+        missing = object()
+        was, own = pol.fused_wide_critic, vars(pol).get("fused_wide_heads", missing)
+        pol.fused_wide_heads = pol.fused_wide_critic = True
+        try:
+            return FusedPolicyUpdate.unsupported_reason(pol, batch_size) == ""
+        finally:
+            pol.fused_wide_critic = was
+            if own is missing:
+                del pol.fused_wide_heads       # (the instance had none: the class attribute is read again)
+            else:
+                pol.fused_wide_heads = own     # (a False set by hand on the instance, under a class attribute of True)
+
     def __init__(self, ppo, policy_id):
         super().__init__(ppo, policy_id)
         pol = self.pol
         dev = pol.device
         self.head, self.action_slices, _ = action_head(pol)
-        self.actor_desc, _ = _describe(pol.actor, pol.policy_params, self.head == K.HEAD_GAUSSIAN)
+        self.actor_desc, _ = _describe(pol.actor, pol.policy_params, self.head == K.HEAD_GAUSSIAN, False,
+                                       actor_out_limit(pol, self.head))
         self.critic_desc, _ = _describe(pol.critic, pol.policy_params, False, wide_critic(pol))
         self.wide = (self.actor_desc.hidden, self.critic_desc.hidden) in WIDE_WIDTH_PAIRS
         # the wide pair's option bits (read here, once: the args and the workspace are built from them)
@@ -910,7 +960,8 @@ class FusedPolicyUpdate(FusedEpoch):
         """One line for `verbose`: the chain a mini-batch runs and, on the split-wgrad chain, the row stride of each
         network's layer-0 panel."""
         a, c = self.actor_desc, self.critic_desc
-        line = f"K12 for (actor {a.hidden}, critic {c.hidden}), in_dim {a.in_dim} / {c.in_dim}: "
+        line = f"K12 for (actor {a.hidden}, critic {c.hidden}), in_dim {a.in_dim} / {c.in_dim}"
+        line += f", {a.out_dim} actor outputs (fused_wide_heads): " if a.out_dim > 8 else ": "
         if not self.split:
             return line + f"slab chain ({self.split_reason})"
         tail = self.tail_reason()

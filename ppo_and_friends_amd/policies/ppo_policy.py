@@ -111,6 +111,13 @@ class PPOPolicy:
     # 32 chunks of 16 rows).  Set by hand, on the class or on the policy, before the first rollout -- no update_mode sets it.
     # False: the torch path for those shapes, with today's messages; inside the other opt-in's limits the flag changes nothing, bitwise.
     fused_wide_shapes = False
+    # Opt-in: the wide pair's actor with 9 .. 24 outputs under a Categorical or tanh-Gaussian head (Discrete(18), Box(17)) on
+    # K6+K7, K12 and K19: kernels of their own, which the library picks from out_dim (fused_update.WIDE_HEAD_MAX).  Set by hand,
+    # on the class or on the policy, before the first rollout -- no update_mode sets it; it combines with the two flags above
+    # (376 inputs need `fused_wide_shapes`).  False: the torch path for those heads, with today's messages ("output width 17 >
+    # 8"); a policy with out_dim <= 8 computes bitwise the same, flag on or off.  MultiDiscrete / MultiBinary heads, LSTM and
+    # MAT policies, ICMs and every other width pair keep 8.
+    fused_wide_heads = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -392,7 +399,7 @@ class PPOPolicy:
         `finish_step` once the environment has answered.
         """
         from .. import _lib
-        from ..fused_update import _describe, action_head, set_action_slices
+        from ..fused_update import _describe, action_head, actor_out_limit, set_action_slices
         buf = self.buffer
         E = buf.C                       # agents x envs rows, agent-major
         a = getattr(self, "_step_args", None)
@@ -400,7 +407,7 @@ class PPOPolicy:
             a = _lib.PolicyStepArgs()
             head, slices, _ = action_head(self)
             gauss = head == K.HEAD_GAUSSIAN
-            a.actor, _ = _describe(self.actor, self.policy_params, gauss)
+            a.actor, _ = _describe(self.actor, self.policy_params, gauss, False, actor_out_limit(self, head))
             a.critic, _ = _describe(self.critic, self.policy_params, False, self.fused_wide_critic)
             a.params = self.policy_params.data_ptr()
             a.E = E
@@ -763,7 +770,7 @@ class PPOPolicy:
             return "LSTM policies are not K19's: K21 or forward_logits (see lstm_step_unsupported_reason)"
         # (asked once per evaluation step: the answer is kept for as long as what it depends on stays)
         key = (self.policy_params.data_ptr(), bool(self.fused_action_heads), bool(self.fused_wide_critic),
-               bool(self.fused_wide_inputs), bool(self.fused_wide_shapes))
+               bool(self.fused_wide_inputs), bool(self.fused_wide_shapes), bool(self.fused_wide_heads))
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
             self._infer_reason = (key, self.fused_step_unsupported_reason())
         return self._infer_reason[1]
@@ -780,14 +787,14 @@ class PPOPolicy:
     def _infer_step(self, t_obs, deterministic):
         """K19: one launch, actor forward -> head -> env action, into a reusable output tensor."""
         from .. import _lib
-        from ..fused_update import _describe, action_head, set_action_slices
+        from ..fused_update import _describe, action_head, actor_out_limit, set_action_slices
         E = t_obs.shape[0]
         st = getattr(self, "_infer_state", None)
         if st is None or st["E"] != E or st["params"] != self.policy_params.data_ptr():
             a = _lib.PolicyInferArgs()
             head, slices, _ = action_head(self)
             gauss = head == K.HEAD_GAUSSIAN
-            a.actor, _ = _describe(self.actor, self.policy_params, gauss)
+            a.actor, _ = _describe(self.actor, self.policy_params, gauss, False, actor_out_limit(self, head))
             a.params = self.policy_params.data_ptr()
             a.E = E
             a.head_kind = head

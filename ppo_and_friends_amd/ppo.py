@@ -545,6 +545,8 @@ class PPO:
                 from .fused_update import FusedPolicyUpdate
                 why = FusedPolicyUpdate.unsupported_reason(pol, self.batch_size)
                 if why:
+                    if verbose and FusedPolicyUpdate.wide_heads_would_take(pol, self.batch_size):
+                        why += "; PPOPolicy.fused_wide_heads = True would take it on the fused kernels"
                     raise NotImplementedError(f"update_mode='fused' but policy {policy_id}: {why}")
         # ppo.py:663-678: freeze cycling over policy groups (utils/schedulers.py:FreezeCyclingScheduler)
         from .utils.schedulers import FreezeCyclingScheduler
@@ -1456,6 +1458,8 @@ class PPO:
                     hint = ""
                     if driver is FusedPolicyUpdate and FusedPolicyUpdate.fused_mode_would_take(self.policies[policy_id], B):
                         hint = "; update_mode='fused' would take it on the fused kernels"
+                    elif driver is FusedPolicyUpdate and FusedPolicyUpdate.wide_heads_would_take(self.policies[policy_id], B):
+                        hint = "; update_mode='fused' with PPOPolicy.fused_wide_heads = True would take it on the fused kernels"
                     rank_print(f"policy {policy_id}: torch update path ({why}){hint}")
                 self._fused[key] = None
             else:

@@ -15,7 +15,9 @@ synchronisations; seconds are printed as median and spread (min .. max) per leg,
 policy under update_mode="fused" against the same policy under update_mode="torch", by the same protocol.  `--widths 256 512`
 is the wide pair (K12 ends in the wgrad and Adam launches there: profiles/wide_critic.txt).
 
---obs-dim N (with --widths) times the pair at the RAM baselines' dimensions instead: N observations, Discrete(4), depth 3.
+--obs-dim N (with --widths) times the pair at the RAM baselines' dimensions instead: N observations, Discrete(4), depth 3
+(--action discrete:N | box:N and --activation relu | leaky_relu | tanh for another head and activation; --wide-heads sets
+PPOPolicy.fused_wide_heads, which the pair needs above 8 actor outputs: profiles/wide_heads.txt).
 --wide-inputs sets PPOPolicy.fused_wide_inputs, which a wide pair needs above 64 inputs, and --batch the mini-batch size:
 
     python tools/width_pairs_bench.py --widths 256 512 --obs-dim 128 --wide-inputs --batch 128
@@ -45,17 +47,31 @@ LEGS = {"64x256_fused": ((64, 256), "fused"), "64x256_torch": ((64, 256), "torch
 BATCH = 256
 
 
-def make_ppo(widths, mode, E, T, seed=1, walker=False, obs_dim=None):
+ACTIVATIONS = {"relu": "ReLU", "leaky_relu": "LeakyReLU", "tanh": "Tanh"}
+
+
+def action_space(spec):
+    """--action discrete:N | box:N -> the space (Box bounds -0.4 .. 0.4 on every dimension, humanoid's)."""
+    from ppo_and_friends_amd.spaces import Box, Discrete
+    kind, _, n = spec.partition(":")
+    if kind not in ("discrete", "box") or not n.isdigit() or int(n) < 1:
+        raise ValueError(f"--action {spec!r}: expected discrete:N or box:N")
+    return Discrete(int(n)) if kind == "discrete" else Box(-0.4, 0.4, (int(n),), np.float32)
+
+
+def make_ppo(widths, mode, E, T, seed=1, walker=False, obs_dim=None, action="discrete:4", activation="relu"):
     from ppo_and_friends_amd.ppo import PPO
     from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
     from ppo_and_friends_amd.spaces import Box, Discrete
     dev = torch.device("cuda", 0)
     O, space = (24, Box(-1.0, 1.0, (4,), np.float32)) if walker else (8, Discrete(4))
     if obs_dim is not None:
-        O, space = obs_dim, Discrete(4)
+        O, space = obs_dim, action_space(action)
     env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, dev, reward="ones", seed=1234)
     sp = Box(-np.inf, np.inf, (O,), np.float32)
-    pargs = dict(actor_kw_args=dict(hidden_size=widths[0], hidden_depth=3), critic_kw_args=dict(hidden_size=widths[1], hidden_depth=3))
+    act = lambda: getattr(torch.nn, ACTIVATIONS[activation])()
+    pargs = dict(actor_kw_args=dict(hidden_size=widths[0], hidden_depth=3, activation=act()),
+                 critic_kw_args=dict(hidden_size=widths[1], hidden_depth=3, activation=act()))
     return PPO(env_gen, {"p": (None, sp, sp, space, pargs)}, device=dev, random_seed=seed, normalize_obs=False,
                normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=BATCH, epochs_per_iter=1,
                save_state=False, update_mode=mode)
@@ -93,6 +109,10 @@ def main():
     ap.add_argument("--wide-inputs", action="store_true", help="PPOPolicy.fused_wide_inputs = True (a wide pair above 64 inputs)")
     ap.add_argument("--wide-shapes", action="store_true",
                     help="PPOPolicy.fused_wide_shapes = True (a wide pair above 128 inputs or above 512 rows per mini-batch)")
+    ap.add_argument("--wide-heads", action="store_true",
+                    help="PPOPolicy.fused_wide_heads = True (a wide pair's actor with 9 .. 24 outputs, Discrete or Box)")
+    ap.add_argument("--action", default="discrete:4", help="with --obs-dim: discrete:N or box:N (default discrete:4)")
+    ap.add_argument("--activation", choices=sorted(ACTIVATIONS), default="relu")
     ap.add_argument("--batch", type=int, default=BATCH, help="mini-batch size")
     args = ap.parse_args()
     if args.obs_dim is not None and not args.widths:
@@ -104,6 +124,9 @@ def main():
     if args.wide_shapes:
         from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
         PPOPolicy.fused_wide_shapes = True
+    if args.wide_heads:
+        from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
+        PPOPolicy.fused_wide_heads = True
     legs, pair = LEGS, "64x256"
     if args.widths:
         pair = f"{args.widths[0]}x{args.widths[1]}"
@@ -114,7 +137,10 @@ def main():
         result.update(obs_dim=args.obs_dim, wide_inputs=bool(args.wide_inputs))
         if args.wide_shapes:
             result.update(wide_shapes=True)
-    ppos = {k: make_ppo(w, m, args.envs, args.steps, walker=bool(args.widths), obs_dim=args.obs_dim) for k, (w, m) in legs.items()}
+        if args.wide_heads or args.action != "discrete:4" or args.activation != "relu":
+            result.update(wide_heads=bool(args.wide_heads), action=args.action, activation=args.activation)
+    ppos = {k: make_ppo(w, m, args.envs, args.steps, walker=bool(args.widths), obs_dim=args.obs_dim, action=args.action,
+                        activation=args.activation) for k, (w, m) in legs.items()}
     for k, ppo in ppos.items():                      # the path each leg takes, as the JSON line reports it
         pol = ppo.policies["p"]
         fused = ppo._fused_updater("p", BATCH)
