@@ -471,6 +471,13 @@ int ppoaf_ppo_update_split_workspace_bytes(const ppoaf_ppo_update_args_t* args, 
 int ppoaf_ppo_update_split_blocks(const ppoaf_ppo_update_args_t* args);
 /* byte offset of the row-pair error word inside split_workspace; -1 in *offset_out when args (row_pairs, shapes) select no pairs */
 int ppoaf_ppo_update_row_pairs_error_offset(const ppoaf_ppo_update_args_t* args, int64_t* offset_out);
+/* Which form of the fwd_bwd kernel ppoaf_ppo_update_fwd_bwd launches for these args (added within ABI 7; pure host, no pointer
+ * of args is followed): *form_out = 1 for the lean kernel (csrc/ppo_update_lean.hip: the row-tile body compiled for one
+ * activation and one head), 0 for the general one.  Lean needs ALL of: split_workspace set and no row pairs selected, both
+ * networks of depth 3, inputs_in_batch_order, no row_map, actor.activation == critic.activation, head_kind Categorical or
+ * Gaussian, hidden widths 32/32, 64/64, 128/128 or 64/128.  Results are BITWISE the general kernel's (the same expressions in
+ * the same order: the forward and backward of PPO._ppo_batch_train, ppo.py:2292-2469). */
+int ppoaf_ppo_update_fwd_bwd_form(const ppoaf_ppo_update_args_t* args, int32_t* form_out);
 int ppoaf_ppo_update_wgrad(const ppoaf_ppo_update_args_t* args, ppoaf_stream_t stream);
 /* Fused tail of the split-wgrad chain (ABI 5; csrc/ppo_update_tail.hip): fwd_bwd (args->split_workspace set) ->
  * ppoaf_ppo_update_wgrad_adam -- TWO launches per mini-batch.  Everything from loss.backward()'s weight gradients to

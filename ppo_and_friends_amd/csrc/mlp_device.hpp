@@ -32,6 +32,20 @@ __device__ __forceinline__ float act_bwd(float h, int act) {
     if (act == PPOAF_ACT_LEAKY_RELU) return h > 0.f ? 1.f : 0.01f;
     return 1.f - h * h;
 }
+// The same two with the activation as a compile-time constant: only that activation's expression is in the text.  ACT = -1:
+// the run-time form above, on `act`.
+template <int ACT> __device__ __forceinline__ float act_fwd_as(float z, int act) {
+    if constexpr (ACT == PPOAF_ACT_RELU) return fmaxf(z, 0.f);
+    else if constexpr (ACT == PPOAF_ACT_LEAKY_RELU) return z > 0.f ? z : 0.01f * z;
+    else if constexpr (ACT >= 0) return tanhf(z);
+    else return act_fwd(z, act);
+}
+template <int ACT> __device__ __forceinline__ float act_bwd_as(float h, int act) {
+    if constexpr (ACT == PPOAF_ACT_RELU) return h > 0.f ? 1.f : 0.f;
+    else if constexpr (ACT == PPOAF_ACT_LEAKY_RELU) return h > 0.f ? 1.f : 0.01f;
+    else if constexpr (ACT >= 0) return 1.f - h * h;
+    else return act_bwd(h, act);
+}
 
 // ---- 16-lane (DPP "row") reductions.  `__shfl_xor` compiles to ds_bpermute_b32 -- a round trip through the LDS
 //      hardware, ~100+ cycles, four of them dependent per sum (K15 carried 324 of them: a fifth of its wave cycles).  The

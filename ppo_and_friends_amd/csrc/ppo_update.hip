@@ -2,6 +2,8 @@
 // One iteration of PPO._ppo_batch_train (ppo.py:2292-2469) =
 //   ppo_update_fwd_bwd_kernel  (gather + normalisers + forward + head/loss + backward -> slabs; ppo_update_fwd_bwd.hpp:
 //                               instantiated here and, for the narrow-actor width pairs, in ppo_update_narrow.hip)
+//                              (or ppo_update_fwd_bwd_lean_kernel, ppo_update_lean.hip: the same body compiled for one
+//                               activation and one head, where the host finds the epoch driver's case)
 //   ppo_update_reduce_kernel   (slabs -> gradient bucket, loss partials -> totals [, norms])
 //   ppo_update_adam_kernel     (clip + Adam for both networks, advance the cursor)
 //
@@ -416,6 +418,20 @@ extern "C" int ppoaf_ppo_update_check(const ppoaf_ppo_update_args_t* args) {
     int rc = update_shapes(args, u);
     if (rc == PPOAF_OK) rc = fwd_bwd_fits(u);
     return rc;
+}
+
+extern "C" int ppoaf_ppo_update_fwd_bwd_form(const ppoaf_ppo_update_args_t* args, int32_t* form_out) {
+    PPOAF_REQUIRE(args && form_out, "ppo_update_fwd_bwd_form: null argument");
+    UpdateDev u;
+    int rc = update_shapes(args, u);
+    if (rc == PPOAF_OK) rc = fwd_bwd_fits(u);
+    if (rc) return rc;
+    // what the dispatch reads beyond the shapes, as make_update_dev sets it (no pointer is followed)
+    u.head_kind = args->head_kind; u.pregathered = args->inputs_in_batch_order != 0; u.row_map = args->row_map;
+    u.split = args->split_workspace != nullptr;
+    const bool pairs = u.split && args_row_pairs(args) && pairs_run(u.net[0], u.net[1]);     // the rung ahead of the lean one
+    *form_out = !pairs && fwd_bwd_lean_form(u) ? 1 : 0;
+    return PPOAF_OK;
 }
 
 extern "C" int ppoaf_ppo_update_reduce(const ppoaf_ppo_update_args_t* args, int compute_norms,

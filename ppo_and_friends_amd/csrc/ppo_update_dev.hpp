@@ -387,7 +387,14 @@ __device__ __forceinline__ unsigned hw_xcc_id() {
 //   ppo_head_values  the critic's u.values[row] = v (ppo.py:2340), from sOut alone.
 //   ppo_head_block   the block part: the parked terms, read in row order, -> the same eight 16-lane sums -> u.loss_partials.
 // The last two may run on any wave, any time after a barrier behind the row part, while sRow / sOut / sActF are intact.
-template <typename U>
+// HEAD: the actor's head kind as a compile-time constant (ppo_update_lean.hip: the arms of the other heads leave the text),
+// or -1: read from u.head_kind where each arm asks, as every other caller does.
+template <int HEAD, typename U>
+__device__ __forceinline__ int head_kind_as(const U& u) {
+    if constexpr (HEAD >= 0) return HEAD;
+    else return u.head_kind;
+}
+template <int HEAD = -1, typename U>
 __device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const int out_dim,
                                               const float* __restrict__ log_std_p, const int* sRow,
                                               const float* sRowF, const float* sMisc, float* sActF, float* sOut,
@@ -404,7 +411,7 @@ __device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const
             av = sRowF[s]; lpo = sRowF[16 + s];
             if (u.normalize_adv) av = (av - sMisc[0]) / (sMisc[1] + 1e-8f);
         }
-        if (u.head_kind == PPOAF_HEAD_CATEGORICAL) {
+        if (head_kind_as<HEAD>(u) == PPOAF_HEAD_CATEGORICAL) {
             // lane-parallel: 4 lanes per row, lane (s4, q) owns classes q and q + 4; the class
             // reductions are two xor-shuffles inside the 4-lane group, so the transcendental chain
             // is 2 values long instead of 8.  Row results are handed to lane s4 at the end.
@@ -462,13 +469,13 @@ __device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const
             }
             // row results: lane (s4, 0) holds them; it parks them below
             if (live4) { part[0] = -fminf(surr1, surr2); part[3] = ent4; part[4] = lpo4 - logp4; part[7] = bad4; }
-        } else if (u.head_kind >= PPOAF_HEAD_MULTI_CATEGORICAL) {
+        } else if (head_kind_as<HEAD>(u) >= PPOAF_HEAD_MULTI_CATEGORICAL) {
             // MultiDiscrete / MultiBinary (action_heads.hpp): one lane per row
             if (live) {
                 float z[8], dz[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) z[k] = k < out_dim ? sOut[s * kMaxOut + k] : 0.f;
-                const bool mcat = u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL;
+                const bool mcat = head_kind_as<HEAD>(u) == PPOAF_HEAD_MULTI_CATEGORICAL;
                 const float* x = sActF + s * 8;
                 float p[8], sm[8];
                 unsigned first = 0u, pick = 0u;
@@ -552,7 +559,7 @@ __device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const
             }
         } else if (s < kRows) {
             for (int k = 0; k < kMaxOut; ++k) sDOut[s * kMaxOut + k] = 0.f;
-            if (u.head_kind == PPOAF_HEAD_GAUSSIAN)
+            if (head_kind_as<HEAD>(u) == PPOAF_HEAD_GAUSSIAN)
                 for (int d = 0; d < 8; ++d) sOut[s * kMaxOut + 8 + d] = 0.f;
         }
     } else {
@@ -577,7 +584,7 @@ __device__ __forceinline__ void ppo_head_rows(const U& u, const int which, const
     // park the row's terms where its actions were.  (The actions were read above through pointers of another type: the
     // compiler may not take these stores ahead of those reads.)
     asm volatile("" ::: "memory");
-    const bool cat = which == 0 && u.head_kind == PPOAF_HEAD_CATEGORICAL;
+    const bool cat = which == 0 && head_kind_as<HEAD>(u) == PPOAF_HEAD_CATEGORICAL;
     const int prow = cat ? (lane >> 2) : s;
     if (cat ? (lane & 3) == 0 : s < kRows) {
         float* pk = sActF + prow * 8;

@@ -1,6 +1,6 @@
 // K12's fwd_bwd launch: the two kernels (one workgroup per 16-row tile; 256-wide networks' tiles on workgroup pairs) and
 // their launchers, shared by the translation units that instantiate them -- ppo_update.hip (pairs of equal widths, 128/256,
-// 64/128), ppo_update_narrow.hip (the narrow-actor pairs 64/256, 32/256, 32/64) and ppo_update_wide.hip (256/512, whose
+// 64/128), ppo_update_lean.hip (the lean kernel of the epoch driver's case, below), ppo_update_narrow.hip (the narrow-actor pairs 64/256, 32/256, 32/64) and ppo_update_wide.hip (256/512, whose
 // critic runs the body of ppo_update_rowtile_wide.hpp): one hipcc process each, so that none is the build's long pole alone.  Which unit holds which pair: PPOAF_WIDTH_PAIRS, ppo_update_dev.hpp.
 #pragma once
 #include "ppo_update_rowpair.hpp"
@@ -111,6 +111,13 @@ inline int launch_fwd_bwd(const UpdateDev& u, size_t lds, hipStream_t s, hipEven
 struct FwdBwdLaunch {
     const UpdateDev& u; const ppoaf_ppo_update_args_t* args; size_t lds; hipStream_t s; hipEvent_t e0, e1;
 };
+// The lean kernel (ppo_update_lean.hip): the row-tile body compiled for one (activation, head), split-wgrad chain and
+// per-epoch-tables flavour only.  fwd_bwd_lean_form evaluates ONCE per launch, on the host, what ppo_update_fwd_bwd_body asks in
+// every workgroup (depth 3 on both networks, tables in batch order, no row_map), and: the split-wgrad chain, one activation code
+// for both networks, a Categorical or Gaussian head, a width pair with an instantiation (32/32, 64/64, 128/128, 64/128).
+bool fwd_bwd_lean_form(const UpdateDev& u);
+int fwd_bwd_launch_lean(const FwdBwdLaunch& L);
+
 template <int HA, int HC>
 inline int fwd_bwd_launch_pair(const FwdBwdLaunch& L) {
     const UpdateDev& u = L.u;
@@ -119,6 +126,7 @@ inline int fwd_bwd_launch_pair(const FwdBwdLaunch& L) {
         pair_region_layout(u, &pd, reinterpret_cast<char*>(L.args->split_workspace) + pair_region_offset(u));
         return launch_fwd_bwd_pairs_of<HA, HC>(u, pd, L.lds, L.s, L.e0, L.e1);
     }
+    if (fwd_bwd_lean_form(u)) return fwd_bwd_launch_lean(L);
     // other shapes (a 256-wide network of depth 1 or > 4): one workgroup per tile
     return launch_fwd_bwd<HA / 16, HC / 16>(u, L.lds, L.s, L.e0, L.e1);
 }

@@ -85,12 +85,15 @@ template <int CP> __device__ __forceinline__ void lds_write_adjacent(float* p, c
 // then waited for the sets as well.  Every other case runs the body as it was (TABLES = false: both decided at run time).
 // XLD (the wide pair's kernel only, ppo_update_fwd_bwd.hpp): the SPLIT publish of the input rows takes the panel's row stride
 // from u.sp.xld[which] (64 | 128: PPOAF_SPLIT_WIDE_INPUTS; 256 | 512: PPOAF_SPLIT_WIDE_SHAPES).  Every other kernel keeps the constant and the loop written for it.
-template <int HT, bool SPLIT, bool TABLES, bool XLD = false>
+// ACT / HEAD (ppo_update_lean.hip): the network's activation code and the actor's head kind as compile-time constants -- what a
+// training run never changes is then not decided in every workgroup of every launch, and the other activations' and heads'
+// arms leave the text.  -1 (every other caller): read from the arguments.
+template <int HT, bool SPLIT, bool TABLES, bool XLD = false, int ACT = -1, int HEAD = -1>
 __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, const int which, const int g) {
     constexpr int H = 16 * HT, HS = H + 4;                 // which: 0 actor, 1 critic; g: 16-row block
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const auto& nd = u.net[which];
-    const int in_dim = nd.in_dim, depth = nd.depth, out_dim = nd.out_dim, act = nd.act;
+    const int in_dim = nd.in_dim, depth = nd.depth, out_dim = nd.out_dim, act = ACT >= 0 ? ACT : nd.act;
     const int NT0 = (in_dim + 15) >> 4;                    // 16-column tiles of the input
     const int INP = 16 * NT0 + 4;
     const float* P = u.params + nd.offset;
@@ -248,8 +251,8 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     constexpr int kVnPre = 2;                              // per-rank value-normaliser records requested ahead of the sets
     const bool row_lane = tid < kRows && (long)g * kRows + tid < B;      // rows >= B: no address is formed
     constexpr bool early = TABLES;                         // (every other case: behind the index, as it was)
-    const int n_act = which != 0 ? 0 : u.head_kind == PPOAF_HEAD_CATEGORICAL ? 1
-                    : u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL ? u.n_slices : out_dim;
+    const int n_act = which != 0 ? 0 : head_kind_as<HEAD>(u) == PPOAF_HEAD_CATEGORICAL ? 1
+                    : head_kind_as<HEAD>(u) == PPOAF_HEAD_MULTI_CATEGORICAL ? u.n_slices : out_dim;
     long perm_v = -1;
     float av = 0.f, lpo = 0.f, rt = 0.f;
     int act_bits[kActRegs];                                // raw actions as sActF keeps them: class indices, or float bits
@@ -258,9 +261,9 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     auto request_row_scalars = [&](const long di) {
         if (which == 0) {
             av = u.adv[di]; lpo = u.old_lp[di];
-            if (u.head_kind == PPOAF_HEAD_CATEGORICAL) {
+            if (head_kind_as<HEAD>(u) == PPOAF_HEAD_CATEGORICAL) {
                 act_bits[0] = (int)reinterpret_cast<const int64_t*>(u.raw_actions)[di];
-            } else if (u.head_kind == PPOAF_HEAD_MULTI_CATEGORICAL) {
+            } else if (head_kind_as<HEAD>(u) == PPOAF_HEAD_MULTI_CATEGORICAL) {
 #pragma unroll
                 for (int j = 0; j < kActRegs; ++j)
                     if (j < n_act) act_bits[j] = (int)reinterpret_cast<const int64_t*>(u.raw_actions)[(long)di * u.n_slices + j];
@@ -466,7 +469,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[k0 + 4 * j + (lane >> 4)], bq[j], acc, 0, 0, 0);
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sH[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
+        for (int r = 0; r < 4; ++r) sH[(4 * (lane >> 4) + r) * HS + o] = act_fwd_as<ACT>(acc[r], act);
     }
     __syncthreads();
     PPOAF_STAMP(3);
@@ -497,7 +500,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
                 }
                 PPOAF_HSTAMP(1);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
+                for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd_as<ACT>(acc[r], act);
                 asm volatile("; ppoaf_rowtile_hidden_epilogue_end" ::: "memory");
             }
             if (SPLIT) publish_end(u.sp.hbuf[which] + (long)(l - 1) * sp_plane);
@@ -524,7 +527,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             }
             }
 #pragma unroll
-            for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd(acc[r], act);
+            for (int r = 0; r < 4; ++r) Hc[(4 * (lane >> 4) + r) * HS + o] = act_fwd_as<ACT>(acc[r], act);
         }
         if (SPLIT) publish_end(u.sp.hbuf[which] + (long)(l - 1) * sp_plane);
         }
@@ -559,7 +562,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
     //      the backward pass waits for.  The block's loss partials and the critic's values leave at the end of the body.
     if (wave == 0) {
         if constexpr (TABLES) asm volatile("; ppoaf_rowtile_head_rows_begin");
-        ppo_head_rows(u, which, out_dim, P + nd.log_std_off, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
+        ppo_head_rows<HEAD>(u, which, out_dim, P + nd.log_std_off, sRow, sRowF, sMisc, sActF, sOut, sDOut, lane, B);
         if constexpr (TABLES) asm volatile("; ppoaf_rowtile_head_rows_end");
         PPOAF_STAMP_W(0, 0);
     }
@@ -597,7 +600,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             }
         }
 #pragma unroll
-        for (int ii = 0; ii < CP; ++ii) acc[ii] = acc[ii] * act_bwd(hv[ii], act);
+        for (int ii = 0; ii < CP; ++ii) acc[ii] = acc[ii] * act_bwd_as<ACT>(hv[ii], act);
         lds_write_adjacent<CP>(sD0 + s * HS + c0, acc);
     }
     PPOAF_STAMP_W(2, 0); PPOAF_STAMP_W(3, 4); PPOAF_STAMP_W(4, 5);
@@ -625,7 +628,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int s = 4 * (lane >> 4) + r, i = nt * 16 + (lane & 15);
-                Dn[s * HS + i] = acc[r] * act_bwd(Hin[s * HS + i], act);
+                Dn[s * HS + i] = acc[r] * act_bwd_as<ACT>(Hin[s * HS + i], act);
             }
         }
         if (SPLIT) publish_end(u.sp.dbuf[which] + (long)l * sp_plane);
@@ -702,7 +705,7 @@ __device__ __forceinline__ void ppo_update_fwd_bwd_body_as(const UpdateDev& u, c
             }
             slab[offB(depth) + k] = acc;
         }
-        if (which == 0 && u.head_kind == PPOAF_HEAD_GAUSSIAN && tid >= 320 && tid < 320 + out_pad) {
+        if (which == 0 && head_kind_as<HEAD>(u) == PPOAF_HEAD_GAUSSIAN && tid >= 320 && tid < 320 + out_pad) {
             const int d = tid - 320;
             float acc = 0.f;
             if (d < out_dim) {

@@ -22,6 +22,11 @@ args=f._args_for(256)
 for _ in range(50): f._one(args)
 torch.cuda.synchronize()
 lib=_lib.load(); buf=(C.c_ulonglong*32)(); lib.ppoaf_debug_read_stamps.argtypes=[C.c_void_p]; print(lib.ppoaf_debug_read_stamps(buf))
+# the lean kernel (csrc/ppo_update_lean.hip) stamps into its own translation unit's buffers: read those where it ran
+form=C.c_int32(0)
+lean=hasattr(lib,'ppoaf_debug_read_lean_stamps') and lib.ppoaf_ppo_update_fwd_bwd_form(C.byref(args),C.byref(form))==0 and form.value==1
+print("fwd_bwd form:", "lean" if lean else "general")
+if lean: lib.ppoaf_debug_read_lean_stamps.argtypes=[C.c_void_p]; lib.ppoaf_debug_read_lean_stamps(buf)
 st=np.array(list(buf),dtype=np.int64).reshape(2,16)
 names=["P0 idx/stats","P1 gatherX","P2 layer0","P3 hidden fwd","P4 out","P5 head","P6 out bwd","P7 hidden bwd","P8 layer0 bwd"]
 d=np.diff(st[0,:10]); print("net",int(os.environ.get('STAMP_NET','0')),"total cycles",st[0,9]-st[0,0])
@@ -40,7 +45,8 @@ print("   end of the body (from the last panel copy): dW_out stored %d, partials
 # the last epilogue ds_write / panel store issued, the barrier passed.  "burst" = first to last load issued where the set is
 # one burst; "late" = the wave's arrival at the barrier after the first wave's.  HIDDEN_WAVES picks the waves (default 0,3,7).
 if hasattr(lib,'ppoaf_debug_read_hidden_stamps'):
-    hb=(C.c_ulonglong*128)(); lib.ppoaf_debug_read_hidden_stamps.argtypes=[C.c_void_p]; lib.ppoaf_debug_read_hidden_stamps(hb)
+    rd=lib.ppoaf_debug_read_lean_hidden_stamps if lean else lib.ppoaf_debug_read_hidden_stamps
+    hb=(C.c_ulonglong*128)(); rd.argtypes=[C.c_void_p]; rd(hb)
     hs=np.array(list(hb),dtype=np.int64).reshape(2,8,8)
     waves=[int(x) for x in os.environ.get('HIDDEN_WAVES','0,3,7').split(',')]
     for l in range(2):

@@ -2,8 +2,9 @@
 
     python tools/prologue_isa.py                      # the C2 kernels: tail <128,128,false|true>, fwd_bwd <8,8,true>
     python tools/prologue_isa.py 'fwd_bwd_kernel<16,16,true>' 'wgrad_adam_kernel<256,256,false>'
+    python tools/prologue_isa.py 'fwd_bwd_lean_kernel<8,8,0,0>'      # the lean kernel <HTA, HTC, activation, head> (csrc/ppo_update_lean.hip)
 
-Compiles csrc/ppo_update.hip and csrc/ppo_update_tail.hip to gfx950 assembly in a temporary directory with csrc/build.py's
+Compiles csrc/ppo_update.hip, csrc/ppo_update_lean.hip and csrc/ppo_update_tail.hip (the units the named kernels live in) to gfx950 assembly in a temporary directory with csrc/build.py's
 FLAGS (device side only) and, for every named kernel, prints
   (i)  the number of `s_waitcnt lgkmcnt(0)` before the first vector-memory instruction (kernel-argument and cursor
        round trips that nothing overlaps), and
@@ -26,7 +27,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from ppo_and_friends_amd.csrc import build as hip_build  # noqa: E402
 
-UNITS = {"fwd_bwd": "ppo_update.hip", "wgrad_adam": "ppo_update_tail.hip"}
+# (first match wins: the lean kernel's name contains the general kernel's key)
+UNITS = {"fwd_bwd_lean": "ppo_update_lean.hip", "fwd_bwd": "ppo_update.hip", "wgrad_adam": "ppo_update_tail.hip"}
 DEFAULT_KERNELS = ("wgrad_adam_kernel<128,128,false>", "wgrad_adam_kernel<128,128,true>", "fwd_bwd_kernel<8,8,true>")
 
 _VMEM = re.compile(r"^(global|buffer|flat|scratch)_(load|store|atomic)")
@@ -63,7 +65,7 @@ def unit_of(kernel):
     for key, src in UNITS.items():
         if key in kernel:
             return src
-    raise ValueError(f"kernel name {kernel!r}: not one of K12's fwd_bwd / wgrad_adam kernels")
+    raise ValueError(f"kernel name {kernel!r}: not one of K12's fwd_bwd / fwd_bwd_lean / wgrad_adam kernels")
 
 
 def kernel_text(asm_path, kernel):
@@ -358,6 +360,22 @@ def kernel_scratch_bytes(asm_path, kernel):
     raise KeyError(f"{kernel}: no ScratchSize line in {asm_path}")
 
 
+def kernel_resource(asm_path, kernel, key):
+    """`; <key>: N` of the kernel's resource comment, e.g. "NumVgprs", "TotalNumVgprs", "ScratchSize"."""
+    tagm, inside = mangled(kernel), False
+    with open(asm_path) as fh:
+        for line in fh:
+            if not inside:
+                inside = line.startswith("_ZN5ppoaf") and tagm in line.split(":")[0]
+            elif line.startswith(f"; {key}:"):
+                return int(line.split(":")[1])
+    raise KeyError(f"{kernel}: no {key} line in {asm_path}")
+
+
+def instruction_count(ins):
+    return sum(op not in ("label", "marker") for op, _ in ins)
+
+
 def hidden_report(ins):
     """fwd_bwd, TABLES flavour, one entry per network:
       "late_loads": per hidden forward layer (in text order), the vector-memory loads that some path executes behind the
@@ -398,7 +416,7 @@ def hidden_report(ins):
 
 
 def describe(kernel, ins):
-    print(f"{kernel}: {sum(op not in ('label', 'marker') for op, _ in ins)} instructions")
+    print(f"{kernel}: {instruction_count(ins)} instructions")
     n, _ = scalar_waits_before_vmem(ins)
     print(f"  (i)  s_waitcnt lgkmcnt(0) before the first vector-memory instruction (no path avoids them): {n}")
     waits = vmcnt_waits_before_barrier(ins)
@@ -410,7 +428,7 @@ def describe(kernel, ins):
     if "wgrad_adam" in kernel:
         n, which = tail_waits_before_operands(ins)
         print(f"  vmcnt waits before the first operand load of a tile job: {n} {which}")
-    if "fwd_bwd_kernel" in kernel:
+    if "fwd_bwd_kernel" in kernel or "fwd_bwd_lean_kernel" in kernel:
         r = fwd_bwd_report(ins)
         print(f"  row-tile bodies of the per-epoch-tables flavour: {r['bodies']}")
         print(f"  hidden-set loads in flight at the S0 barrier, by path: {r['set_loads_at_barrier']}")
