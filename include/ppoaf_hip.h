@@ -804,7 +804,7 @@ int ppoaf_icm_intrinsic_reward(const ppoaf_icm_update_args_t* args, float scale,
  *          PPOPolicy.get_intrinsic_reward          policies/ppo_policy.py:954-1007
  * With pad16(x) = 16 ceil(x / 16):
  *   encoder  O -> E -> E -> E -> D (last layer linear)     E in {32, 64, 128}, 1 <= D <= 128, 1 <= O <= 1024
- *   inverse  2D -> Mi (x depth_inv hidden layers) -> A     Mi, Mf in {32, 64, 128}, depths 1..3, A, A_in <= 8, or <= 16 with n_action_slices
+ *   inverse  2D -> Mi (x depth_inv hidden layers) -> A     Mi, Mf in {32, 64, 128}, depths 1..3, A, A_in <= 8, or <= 16 with n_action_slices, or <= 24 with PPOAF_ICM_WIDE_ACTIONS
  *   forward  D + A_in -> Mf (x depth_fwd hidden layers) -> D
  * Losses, activations and the bucket (module order, each parameter padded to 4 floats) are
  * those of ppoaf_icm_update_args_t.  Weight rows of 2D and D + A_in floats are not 16-byte
@@ -852,7 +852,19 @@ int ppoaf_icm_intrinsic_reward(const ppoaf_icm_update_args_t* args, float scale,
  * n_action_slices 0 or 1: Discrete / Box as above, action widths <= 8.  `check` refuses, for
  * k >= 2, discrete == 0, action_dim != fwd_action_dim, k > 8, action_dim > 16, action_dim % k != 0
  * and action_dim / k < 2.
+ *
+ * Wide actions (opt-in): n_action_slices carries option bits above its low byte, which stays the
+ * slice count.  PPOAF_ICM_WIDE_ACTIONS with a slice count of 0 or 1: Discrete / Box with
+ * action_dim and fwd_action_dim in [1,24] (discrete needs them equal).  A launch with either
+ * above 8 runs the 32-column form of the models and reward kernels (one softmax over the row and
+ * CrossEntropyLoss on it, or the MSE over B x A, as at <= 8; the action panels of `wgrad` are
+ * [Bpad][32], and the workspace grows by them); with both <= 8 it runs the kernels and needs
+ * the workspace it does without the bit.  With a slice count k >= 2 the bit changes nothing:
+ * MultiDiscrete keeps k <= 8 and 16 classes.  `check` names the field, its value and [1,24].
+ * With the bit, any other bit above the low byte is refused.
+ * Without the bit every answer, message and byte count is what it was.
  * ------------------------------------------------------------------------ */
+#define PPOAF_ICM_WIDE_ACTIONS 0x100   /* in ppoaf_icm_shapes_args_t.n_action_slices */
 typedef struct {
     int32_t obs_dim, enc_hidden, enc_dim, inv_hidden, fwd_hidden, action_dim, fwd_action_dim, depth_inv, depth_fwd;
     int32_t activation, discrete, xcd_half;           /* xcd_half: as ppoaf_icm_update_args_t                */
@@ -868,7 +880,7 @@ typedef struct {
     float* loss_partials;            /* [ceil(B/16) + 1, 2] (last row: this step's Adam constants)*/
     double* totals;                  /* [2]                                                     */
     int32_t inputs_in_batch_order;
-    int32_t n_action_slices;         /* 0 | 1: Discrete / Box; k >= 2: MultiDiscrete, k equal slices (above) */
+    int32_t n_action_slices;         /* 0 | 1: Discrete / Box; k >= 2: MultiDiscrete, k equal slices; | PPOAF_ICM_WIDE_ACTIONS (above) */
     void* workspace; int64_t workspace_bytes;
 } ppoaf_icm_shapes_args_t;
 

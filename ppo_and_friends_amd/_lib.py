@@ -75,6 +75,8 @@ class PpoUpdateArgs(C.Structure):
 SPLIT_ROW_PAIRS = 1
 SPLIT_WIDE_INPUTS = 2
 SPLIT_WIDE_SHAPES = 4
+# ppoaf_icm_shapes_args_t.n_action_slices: the slice count in the low byte, option bits above it (PPOAF_ICM_WIDE_ACTIONS)
+ICM_WIDE_ACTIONS = 0x100
 
 ABI_VERSION = 7
 

@@ -16,6 +16,9 @@
 // Identity encoder (enc_hidden = 0, D = O <= 128): the encodings ARE the observation rows.  No encoder kernel runs; the
 // models kernel and the reward kernel fill their two encoding tiles from the observation tables (sh_load_obs), the
 // inverse model's workgroup publishes them as the layer-0 panels of the wgrad launch, and no d(enc) is formed.
+// Wide actions (PPOAF_ICM_WIDE_ACTIONS in n_action_slices, Discrete / Box with 9 <= max(A, A_in) <= 24): a third form of the
+// models kernel, icm_sh_models_kernel<., 32>, and a second of the reward kernel, over a 32-column action tile (ShForm); the
+// panels oI / aF of the wgrad launch are [Bpad][32].  A launch with A, A_in <= 8 or with slices runs the kernel it ran before.
 #include "icm_update_dev.hpp"
 #include "wgrad_tile.hpp"
 #include <cstddef>
@@ -27,6 +30,7 @@ struct IcmSh {
     int E, D, DP, Mi, Mf;      // DP = pad16(D)
     int ident;                 // identity encoder: E = 0, D = O; enc is filled by the models kernel, gI / gF / dEh / dEo unused
     int n_sl;                  // MultiDiscrete: k >= 2 equal action slices of A / k classes (args->n_action_slices); else 0
+    int wide;                  // host only: the 32-column action form (ShForm<32>) runs; fills the padding ahead of `enc`
     float* enc;                // [2][Bpad][DP]     encodings of the two streams
     float* gI;                 // [2][Bpad][DP]     the inverse model's share of d(enc_1), d(enc_2)
     float* gF;                 // [2][Bpad][DP]     the forward model's
@@ -35,11 +39,32 @@ struct IcmSh {
     float* dEo;                // [2][Bpad][DP]     dz of encoder layer 3 = d(enc)
     float* dFo;                // [Bpad][DP]        dz of the forward model's output layer
     // d.xO [2][Bpad][XO]; d.hI / d.dI [d_inv][planeI]; d.oI [Bpad][16]; d.hF / d.dF [d_fwd][planeF]; d.aF [Bpad][16]
+    // (wide: d.oI and d.aF [Bpad][32])
 };
+
+static_assert(offsetof(IcmSh, enc) == sizeof(IcmDev) + 32, "IcmSh: `wide` sits in what was padding, the kernel arguments keep their layout");
 
 extern __shared__ __attribute__((aligned(16))) unsigned char icm_sh_smem[];
 
 constexpr int kShXS = 20;      // row stride of the padded action tile [16, 16 + 4]
+constexpr int kShWideA = 24;   // classes / dimensions the 32-column form's head is written for (fused_update.WIDE_HEAD_MAX)
+
+// The action-tile form of a models / reward kernel, from AW = the columns the inverse head is instantiated with.  8 and 16
+// share the 16-column tile; 32 is the wide form: every size below is a compile-time constant of the instantiation.
+template <int AW>
+struct ShForm {
+    static constexpr bool wide = AW == 32;
+    static constexpr int XW = wide ? 32 : 16;               // columns of the action tile and of the panels oI / aF
+    static constexpr int XSH = wide ? 5 : 4;                // log2(XW)
+    static constexpr int XS = wide ? 36 : kShXS;            // row stride of the action tile [16][XW + 4]
+    static constexpr int AS = wide ? 32 : 8;                // row stride of sAct
+    static constexpr int OS = wide ? 32 : kMaxOut;          // row stride of sOut / sDOut
+    static constexpr int HEAD = wide ? kShWideA : AW;       // columns the head and the output layer's backward run over
+    static constexpr int kBout = 16 + kRows * AS;           // carve (floats): sRow [16] | sAct [16][AS] | sBout | sWout
+    static constexpr int kWout = kBout + (wide ? 32 : 16);
+};
+static_assert(ShForm<8>::kBout == 144 && ShForm<8>::kWout == 160 && ShForm<16>::kWout == 160, "the narrow carve stays");
+static_assert(ShForm<32>::kBout == 528 && ShForm<32>::kWout == 560, "the wide carve");
 
 // ---- run-time sized MFMA tiles: weights by bound-checked scalar loads -------------------------------------------
 // acc += A[16][K] . w[0..K) for this lane's output column; A in LDS (stride lda, readable and finite up to pad16(K))
@@ -190,9 +215,9 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_encoder_fwd_kernel(IcmSh q) 
 
 // ------------------------------------------------------------------------------------------------
 // the forward model's forward pass on one row tile, shared by the update and the reward kernel: sE1 [16][DS] and
-// sXa [16][kShXS] in, hidden planes in sH (depth x [16][MS]), the prediction of enc_2 in sPred [16][DS].  Ends with a barrier.
+// sXa [16][XS] in, hidden planes in sH (depth x [16][MS]), the prediction of enc_2 in sPred [16][DS].  Ends with a barrier.
 // ------------------------------------------------------------------------------------------------
-template <int MT>
+template <int MT, int XS>
 __device__ __forceinline__ void sh_forward_model(const IcmSh& q, const float* __restrict__ P, const float* sE1, const float* sXa,
                                                  float* sH, float* sPred, int wave, int lane) {
     constexpr int M = 16 * MT, MS = M + 4;
@@ -205,7 +230,7 @@ __device__ __forceinline__ void sh_forward_model(const IcmSh& q, const float* __
         const float bv = P[offB(0) + o];
         f32x4 acc = {bv, bv, bv, bv};
         acc = sh_tile_fwd(acc, sE1, DS, P + (long)o * ld0, D, true, lane);
-        acc = sh_tile_fwd(acc, sXa, kShXS, P + (long)o * ld0 + D, Ain, true, lane);
+        acc = sh_tile_fwd(acc, sXa, XS, P + (long)o * ld0 + D, Ain, true, lane);
 #pragma unroll
         for (int r = 0; r < 4; ++r) sH[(4 * (lane >> 4) + r) * MS + o] = act_fwd(acc[r], u.act);
     }
@@ -222,6 +247,8 @@ __device__ __forceinline__ void sh_forward_model(const IcmSh& q, const float* __
 // the action columns of a row tile: one-hot (icm.py:198-204), one one-hot per slice side by side (MultiDiscrete with equal
 // class counts, icm.py:198-211) or the action values, zero padded; sAct keeps the class(es) / the values for the inverse
 // model's loss.  A class outside its slice is clamped into it: nothing is read or set beyond the slice.
+// XS / AS: row strides of sXa / sAct (ShForm).
+template <int XS, int AS>
 __device__ __forceinline__ void sh_actions(const IcmDev& u, int n_sl, const int* sRow, float* sAct, float* sXa, int tid) {
     if (tid < kRows) {
         const int row = sRow[tid], A = u.A;
@@ -230,19 +257,19 @@ __device__ __forceinline__ void sh_actions(const IcmDev& u, int n_sl, const int*
             for (int j = 0; j < n_sl; ++j) {
                 int a = row >= 0 ? (int)reinterpret_cast<const int64_t*>(u.actions)[(long)row * n_sl + j] : 0;
                 a = a < 0 ? 0 : (a >= n ? n - 1 : a);
-                reinterpret_cast<int*>(sAct)[tid * 8 + j] = a;
-                if (row >= 0) sXa[tid * kShXS + j * n + a] = 1.0f;
+                reinterpret_cast<int*>(sAct)[tid * AS + j] = a;
+                if (row >= 0) sXa[tid * XS + j * n + a] = 1.0f;
             }
         } else if (u.discrete) {
             int a = row >= 0 ? (int)reinterpret_cast<const int64_t*>(u.actions)[row] : 0;
             a = a < 0 ? 0 : (a >= A ? A - 1 : a);
-            reinterpret_cast<int*>(sAct)[tid * 8] = a;
-            if (row >= 0) sXa[tid * kShXS + a] = 1.0f;
+            reinterpret_cast<int*>(sAct)[tid * AS] = a;
+            if (row >= 0) sXa[tid * XS + a] = 1.0f;
         } else {
             for (int d = 0; d < A; ++d) {
                 const float v = row >= 0 ? reinterpret_cast<const float*>(u.actions)[(long)row * A + d] : 0.f;
-                sAct[tid * 8 + d] = v;
-                sXa[tid * kShXS + d] = v;
+                sAct[tid * AS + d] = v;
+                sXa[tid * XS + d] = v;
             }
         }
     }
@@ -252,7 +279,8 @@ __device__ __forceinline__ void sh_actions(const IcmDev& u, int n_sl, const int*
 // models: block 2 * g + which (0: inverse model, 1: forward model); only >= 0: every block runs that model on tile
 // blockIdx (the launch per model when the two widths differ).  AW: the columns the inverse model's head is written for.
 // 8 is the Discrete / Box head (A <= 8); 16 the MultiDiscrete one (n_action_slices >= 2, A <= 16), an instantiation of its
-// own so that the A <= 8 shapes keep their head's arithmetic and their 8-wide tiles (sh_actions is shared by both).
+// own so that the A <= 8 shapes keep their head's arithmetic and their 8-wide tiles (sh_actions is shared by both);
+// 32 the wide Discrete / Box one (9 <= max(A, A_in) <= kShWideA) over the 32-column tile of ShForm<32>.
 // ------------------------------------------------------------------------------------------------
 template <int MT, int AW>
 __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int only) {
@@ -265,20 +293,22 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
     const int act = u.act, A = u.A, D = q.D, DP = q.DP, DS = DP + 4;
     const int depth = which == 0 ? u.d_inv : u.d_fwd;
     const long B = u.B;
+    using F = ShForm<AW>;
+    constexpr int XS = F::XS, AS = F::AS, OS = F::OS;
     float* smem = reinterpret_cast<float*>(icm_sh_smem);
     int* sRow = reinterpret_cast<int*>(smem);                 // [16]
-    float* sAct = smem + 16;                                  // [16][8] actions (float, or int bits)
-    float* sBout = smem + 144;                                // [16]
-    float* sWout = smem + 160;                                // [AW, M]
-    float* sXa = sWout + AW * M;                              // [16, kShXS]
-    float* sE1 = sXa + kRows * kShXS;                         // [16, DS]
+    float* sAct = smem + 16;                                  // [16][AS] actions (float, or int bits)
+    float* sBout = smem + F::kBout;                           // [16] (wide: [32])
+    float* sWout = smem + F::kWout;                           // [AW, M]
+    float* sXa = sWout + AW * M;                              // [16, XS]
+    float* sE1 = sXa + kRows * XS;                            // [16, DS]
     float* sE2 = sE1 + kRows * DS;
     float* sP = sE2 + kRows * DS;                             // [16, DS]  forward model: prediction, then its dz
     float* sH = sP + kRows * DS;                              // depth x [16, MS]
     float* sD0 = sH + (long)depth * kRows * MS;
     float* sD1 = sD0 + kRows * MS;
-    float* sOut = sD1 + kRows * MS;                           // [16, 16]
-    float* sDOut = sOut + kRows * kMaxOut;                    // [16, 16]
+    float* sOut = sD1 + kRows * MS;                           // [16, OS]
+    float* sDOut = sOut + kRows * OS;                         // [16, OS]
     __shared__ float red[17];
 
     if (q.ident && vb == 0 && which == 0 && tid == 0 && u.fused_adam) {
@@ -289,7 +319,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         u.loss_partials[2 * u.nT + 1] = (float)sqrt(1.0 - pow((double)u.beta2, (double)t));
     }
     icm_rows(u, g, tid, sRow);
-    for (int i = tid; i < kRows * kShXS; i += kThreadsU) sXa[i] = 0.f;
+    for (int i = tid; i < kRows * XS; i += kThreadsU) sXa[i] = 0.f;
     if (q.ident) {
         __syncthreads();
         sh_load_obs(u.obs, u.O, DP, sRow, sE1, DS, tid);
@@ -299,7 +329,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         sh_fetch(q.enc + u.Bpad * DP, DP, g, sE2, DS, tid);
     }
     __syncthreads();
-    sh_actions(u, q.n_sl, sRow, sAct, sXa, tid);
+    sh_actions<XS, AS>(u, q.n_sl, sRow, sAct, sXa, tid);
     __syncthreads();
     if (q.ident && which == 0) {        // the layer-0 inputs of the wgrad launch
         sh_publish(sE1, DS, q.enc, DP, g, tid);
@@ -339,7 +369,7 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
 #pragma unroll
                 for (int i = 0; i < MT; ++i) acc = fmaf(Hlast[s * MS + part + 16 * i], sWout[k * M + part + 16 * i], acc);
                 acc = group16_sum(acc);
-                if (part == 0) sOut[s * kMaxOut + k] = acc + sBout[k];
+                if (part == 0) sOut[s * OS + k] = acc + sBout[k];
             }
         }
         __syncthreads();
@@ -348,7 +378,59 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
             const int s = lane;
             const bool live = s < kRows && sRow[s] >= 0;
             float part = 0.f;
-            if constexpr (AW == 16) {
+            if constexpr (AW == 32) {
+                // the wide Discrete / Box head: the 8-wide head's arithmetic over NH = 24 columns, one lane per row, classes in
+                // ascending order; every per-class array has compile-time indices only (registers, no private segment)
+                constexpr int NH = F::HEAD;
+                if (live && u.discrete) {
+                    // icm.py:76-77, 404-415: softmax output fed to CrossEntropyLoss (a second log-softmax with its own max)
+                    float p[NH];
+                    float m = -INFINITY;
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) if (k < A) m = fmaxf(m, sOut[s * OS + k]);
+                    float ssum = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) { p[k] = k < A ? expf(sOut[s * OS + k] - m) : 0.f; ssum += p[k]; }
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) p[k] /= ssum;
+                    float m2 = -INFINITY;
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) if (k < A) m2 = fmaxf(m2, p[k]);
+                    float e2[NH], s2 = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) { e2[k] = k < A ? expf(p[k] - m2) : 0.f; s2 += e2[k]; }
+                    const int a = reinterpret_cast<const int*>(sAct)[s * AS];
+                    float pa = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) if (k == a) pa = p[k];
+                    part = -(pa - m2 - logf(s2));
+                    const float sc = u.icm_beta / (float)B;
+                    float dq[NH], dot = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) {
+                        dq[k] = k < A ? sc * (e2[k] / s2 - (k == a ? 1.f : 0.f)) : 0.f;
+                        dot += dq[k] * p[k];
+                    }
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) sDOut[s * OS + k] = p[k] * (dq[k] - dot);
+                } else if (live) {
+                    // icm.py:417-419: mean squared error over B x A
+                    const float sc = u.icm_beta * 2.0f / ((float)B * (float)A);
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) {
+                        float dv = 0.f;
+                        if (k < A) {
+                            const float diff = sOut[s * OS + k] - sAct[s * AS + k];
+                            part += diff * diff;
+                            dv = sc * diff;
+                        }
+                        sDOut[s * OS + k] = dv;
+                    }
+                } else if (s < kRows) {
+#pragma unroll
+                    for (int k = 0; k < NH; ++k) sDOut[s * OS + k] = 0.f;
+                }
+            } else if constexpr (AW == 16) {
                 if (live) {
                     // icm.py:76-77, 400-412: ONE softmax p over the whole row, then per slice CrossEntropyLoss on p[slice]
                     // (a second log-softmax over the slice, with its own max); the row's loss is the sum over the slices
@@ -446,21 +528,21 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         }
         __syncthreads();
         // output layer backward
-        if (tid < kRows * 16) {                                 // d(out) rows, zero padded to 16 columns
-            const int s = tid >> 4, k = tid & 15;
-            u.oI[((long)g * kRows + s) * 16 + k] = k < AW ? sDOut[s * kMaxOut + k] : 0.f;
+        if (tid < kRows * F::XW) {                              // d(out) rows, zero padded to XW columns
+            const int s = tid >> F::XSH, k = tid & (F::XW - 1);
+            u.oI[((long)g * kRows + s) * F::XW + k] = k < F::HEAD ? sDOut[s * OS + k] : 0.f;
         }
         if (tid >= 256) {
             const int t2 = tid - 256;
             const int s = t2 >> 4, ig = t2 & 15;
-            float d[AW];
+            float d[F::HEAD];
 #pragma unroll
-            for (int k = 0; k < AW; ++k) d[k] = sDOut[s * kMaxOut + k];
+            for (int k = 0; k < F::HEAD; ++k) d[k] = sDOut[s * OS + k];
             float hv[MT], acc[MT];
 #pragma unroll
             for (int ii = 0; ii < MT; ++ii) { hv[ii] = Hlast[s * MS + ig + 16 * ii]; acc[ii] = 0.f; }
 #pragma unroll
-            for (int k = 0; k < AW; ++k) {
+            for (int k = 0; k < F::HEAD; ++k) {
                 if (k < A) {
 #pragma unroll
                     for (int ii = 0; ii < MT; ++ii) acc[ii] = fmaf(d[k], sWout[k * M + ig + 16 * ii], acc[ii]);
@@ -489,11 +571,11 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
         const float* P = u.params + u.fwd_off;
         const int ld0 = D + u.Ain;
         auto offW = [&](int l) -> long { return l == 0 ? 0 : (long)M * ld0 + M + (long)(l - 1) * (M * M + M); };
-        sh_forward_model<MT>(q, P, sE1, sXa, sH, sP, wave, lane);
+        sh_forward_model<MT, XS>(q, P, sE1, sXa, sH, sP, wave, lane);
         for (int l = 0; l < depth; ++l) sh_publish(sH + (long)l * kRows * MS, MS, u.hF + (long)l * u.Bpad * M, M, g, tid);
-        if (tid < kRows * 16) {                                 // the action columns of layer 0's input
-            const int s = tid >> 4, k = tid & 15;
-            u.aF[((long)g * kRows + s) * 16 + k] = sXa[s * kShXS + k];
+        if (tid < kRows * F::XW) {                              // the action columns of layer 0's input
+            const int s = tid >> F::XSH, k = tid & (F::XW - 1);
+            u.aF[((long)g * kRows + s) * F::XW + k] = sXa[s * XS + k];
         }
         // K8: f_loss = 0.5 mean((pred - enc_2)^2); d pred = (1 - beta) (pred - enc_2) / (B D); d enc_2 = -d pred
         {
@@ -537,25 +619,27 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_models_kernel(IcmSh q, int o
 // ------------------------------------------------------------------------------------------------
 // rollout-time intrinsic reward: the forward model alone on the encodings icm_sh_encoder_fwd_kernel left (identity
 // encoder: on the observation rows themselves, the only launch of the call);
-// intr[row] = scale * sum_d (pred - enc_2)^2.  One workgroup per 16 rows.
+// intr[row] = scale * sum_d (pred - enc_2)^2.  One workgroup per 16 rows.  AW: the action-tile form (ShForm; 8 or 32).
 // ------------------------------------------------------------------------------------------------
-template <int MT>
+template <int MT, int AW>
 __global__ __launch_bounds__(kThreadsU) void icm_sh_reward_kernel(IcmSh q, float scale, float* __restrict__ intr_out) {
     const IcmDev& u = q.d;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = blockIdx.x;
     if (g >= u.nT) return;
     const int DP = q.DP, DS = DP + 4;
+    using F = ShForm<AW>;
+    constexpr int XS = F::XS, AS = F::AS;
     float* smem = reinterpret_cast<float*>(icm_sh_smem);
     int* sRow = reinterpret_cast<int*>(smem);                 // [16]
-    float* sAct = smem + 16;                                  // [16][8]
-    float* sXa = smem + 144;                                  // [16, kShXS]
-    float* sE1 = sXa + kRows * kShXS;                         // [16, DS]
+    float* sAct = smem + 16;                                  // [16][AS]
+    float* sXa = smem + F::kBout;                             // [16, XS]
+    float* sE1 = sXa + kRows * XS;                            // [16, DS]
     float* sE2 = sE1 + kRows * DS;
     float* sP = sE2 + kRows * DS;
     float* sH = sP + kRows * DS;                              // d_fwd x [16, MS]
     icm_rows(u, g, tid, sRow);
-    for (int i = tid; i < kRows * kShXS; i += kThreadsU) sXa[i] = 0.f;
+    for (int i = tid; i < kRows * XS; i += kThreadsU) sXa[i] = 0.f;
     if (q.ident) {
         __syncthreads();
         sh_load_obs(u.obs, u.O, DP, sRow, sE1, DS, tid);
@@ -565,9 +649,9 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_reward_kernel(IcmSh q, float
         sh_fetch(q.enc + u.Bpad * DP, DP, g, sE2, DS, tid);
     }
     __syncthreads();
-    sh_actions(u, q.n_sl, sRow, sAct, sXa, tid);
+    sh_actions<XS, AS>(u, q.n_sl, sRow, sAct, sXa, tid);
     __syncthreads();
-    sh_forward_model<MT>(q, u.params + u.fwd_off, sE1, sXa, sH, sP, wave, lane);
+    sh_forward_model<MT, XS>(q, u.params + u.fwd_off, sE1, sXa, sH, sP, wave, lane);
     // row sums of (pred - enc_2)^2: 16 lanes per row (columns D .. DP are zero on both sides)
     if (tid < 256) {
         const int s = tid >> 4, part = tid & 15;
@@ -635,6 +719,13 @@ __global__ __launch_bounds__(kThreadsU) void icm_sh_encoder_bwd_kernel(IcmSh q) 
 // ------------------------------------------------------------------------------------------------
 static long pad4l(long x) { return (x + 3) / 4 * 4; }
 static bool sh_width(int w) { return w == 32 || w == 64 || w == 128; }
+// n_action_slices = option bits above the slice count in the low byte (include/ppoaf_hip.h)
+static bool sh_wide_bit(const ppoaf_icm_shapes_args_t* a) { return a->n_action_slices > 0 && (a->n_action_slices & PPOAF_ICM_WIDE_ACTIONS) != 0; }
+static int sh_slices(const ppoaf_icm_shapes_args_t* a) { return sh_wide_bit(a) ? (a->n_action_slices & 0xff) : a->n_action_slices; }
+// the 32-column action form runs: asked for, Discrete / Box, and a width the 16-column tile's head (A <= 8) does not take
+static bool sh_wide(const ppoaf_icm_shapes_args_t* a) {
+    return sh_wide_bit(a) && sh_slices(a) < 2 && (a->action_dim > 8 || a->fwd_action_dim > 8);
+}
 
 // topology and bucket layout only: what ppoaf_icm_shapes_check answers without a device
 static int sh_check(const ppoaf_icm_shapes_args_t* a) {
@@ -651,9 +742,14 @@ static int sh_check(const ppoaf_icm_shapes_args_t* a) {
                   "icm_shapes: inv_hidden=%d / fwd_hidden=%d are not instantiated widths (32, 64, 128)", a->inv_hidden, a->fwd_hidden);
     PPOAF_REQUIRE(a->enc_dim >= 1 && a->enc_dim <= 128, "icm_shapes: enc_dim=%d must be in [1,128]", a->enc_dim);
     PPOAF_REQUIRE(a->obs_dim >= 1 && a->obs_dim <= 1024, "icm_shapes: obs_dim=%d must be in [1,1024]", a->obs_dim);
-    if (a->n_action_slices >= 2) {
+    // (without the bit the word is a slice count, refused above 8 below: an option bit this library does not know is never
+    // half-honoured)
+    PPOAF_REQUIRE(!sh_wide_bit(a) || (a->n_action_slices & ~(PPOAF_ICM_WIDE_ACTIONS | 0xff)) == 0,
+                  "icm_shapes: n_action_slices=0x%x carries option bits other than PPOAF_ICM_WIDE_ACTIONS (0x%x)", a->n_action_slices,
+                  PPOAF_ICM_WIDE_ACTIONS);
+    if (sh_slices(a) >= 2) {
         // MultiDiscrete over k equal slices (the agent-shared ICM of a MAT group): one class per slice in `actions`
-        const int k = a->n_action_slices;
+        const int k = sh_slices(a);
         PPOAF_REQUIRE(a->discrete != 0, "icm_shapes: n_action_slices=%d needs discrete=1 (discrete=%d)", k, a->discrete);
         PPOAF_REQUIRE(a->action_dim == a->fwd_action_dim, "icm_shapes: n_action_slices=%d needs action_dim=%d to equal fwd_action_dim=%d",
                       k, a->action_dim, a->fwd_action_dim);
@@ -663,6 +759,15 @@ static int sh_check(const ppoaf_icm_shapes_args_t* a) {
         PPOAF_REQUIRE(a->action_dim % k == 0, "icm_shapes: action_dim=%d is not a multiple of n_action_slices=%d", a->action_dim, k);
         PPOAF_REQUIRE(a->action_dim / k >= 2, "icm_shapes: action_dim=%d / n_action_slices=%d leaves fewer than 2 classes per slice",
                       a->action_dim, k);
+    } else if (sh_wide_bit(a)) {
+        // PPOAF_ICM_WIDE_ACTIONS: Discrete / Box up to kShWideA classes or dimensions
+        PPOAF_REQUIRE(a->action_dim >= 1 && a->action_dim <= kShWideA, "icm_shapes: action_dim=%d must be in [1,%d] with PPOAF_ICM_WIDE_ACTIONS",
+                      a->action_dim, kShWideA);
+        PPOAF_REQUIRE(a->fwd_action_dim >= 1 && a->fwd_action_dim <= kShWideA,
+                      "icm_shapes: fwd_action_dim=%d must be in [1,%d] with PPOAF_ICM_WIDE_ACTIONS", a->fwd_action_dim, kShWideA);
+        PPOAF_REQUIRE(!a->discrete || a->action_dim == a->fwd_action_dim,
+                      "icm_shapes: discrete=%d needs action_dim=%d to equal fwd_action_dim=%d with PPOAF_ICM_WIDE_ACTIONS", a->discrete,
+                      a->action_dim, a->fwd_action_dim);
     } else {
         PPOAF_REQUIRE(a->action_dim >= 1 && a->action_dim <= 8 && a->fwd_action_dim >= 1 && a->fwd_action_dim <= 8,
                       "icm_shapes: action_dim=%d fwd_action_dim=%d must be in [1,8]", a->action_dim, a->fwd_action_dim);
@@ -692,13 +797,14 @@ static size_t sh_layout(IcmSh& q, char* base, IcmWg* w) {
     size_t off = 0;
     auto take = [&](size_t floats) { float* p = reinterpret_cast<float*>(base + off); off += (floats * 4 + 255) & ~(size_t)255; return p; };
     u.XO = 16 * ((u.O + 15) / 16);
+    const int pw = q.wide ? 32 : 16;          // columns of the action panels oI / aF (ShForm::XW)
     if (!q.ident) {
         u.xO = take((size_t)2 * Bp * u.XO);
         q.dEh = take((size_t)6 * planeE); q.dEo = take((size_t)2 * planeD);
     }
-    u.hI = take((size_t)u.d_inv * planeI); u.dI = take((size_t)u.d_inv * planeI); u.oI = take((size_t)Bp * 16);
+    u.hI = take((size_t)u.d_inv * planeI); u.dI = take((size_t)u.d_inv * planeI); u.oI = take((size_t)Bp * pw);
     u.hF = take((size_t)u.d_fwd * planeF); u.dF = take((size_t)u.d_fwd * planeF); q.dFo = take((size_t)planeD);
-    u.aF = take((size_t)Bp * 16);
+    u.aF = take((size_t)Bp * pw);
     if (!w) return off;
     w->n_blk = w->n_jobs = 0;
     const int Ei = (int)E, Di = q.D, DPi = (int)DP, Mii = (int)Mi, Mfi = (int)Mf;
@@ -724,12 +830,12 @@ static size_t sh_layout(IcmSh& q, char* base, IcmWg* w) {
         icm_add_block(w, u.dI + l * planeI, Mii, 0, u.hI + (l - 1) * planeI, Mii, 0, 1, Mii, Mii, p, Mii, p + Mi * Mi);
         p += Mi * Mi + Mi;
     }
-    icm_add_block(w, u.oI, 16, 0, u.hI + (u.d_inv - 1) * planeI, Mii, 0, 1, u.A, Mii, p, Mii, p + (long)u.A * Mi);
+    icm_add_block(w, u.oI, pw, 0, u.hI + (u.d_inv - 1) * planeI, Mii, 0, 1, u.A, Mii, p, Mii, p + (long)u.A * Mi);
     // forward model: layer 0 as an enc_1 and an action block, hidden layers, output layer (D rows)
     long f = u.fwd_off;
     const int ld0 = Di + u.Ain;
     icm_add_block(w, u.dF, Mfi, 0, q.enc, DPi, 0, 1, Mfi, Di, f, ld0, f + Mf * ld0);
-    icm_add_block(w, u.dF, Mfi, 0, u.aF, 16, 0, 1, Mfi, u.Ain, f + D, ld0, -1);
+    icm_add_block(w, u.dF, Mfi, 0, u.aF, pw, 0, 1, Mfi, u.Ain, f + D, ld0, -1);
     f += Mf * ld0 + Mf;
     for (int l = 1; l < u.d_fwd; ++l) {
         icm_add_block(w, u.dF + l * planeF, Mfi, 0, u.hF + (l - 1) * planeF, Mfi, 0, 1, Mfi, Mfi, f, Mfi, f + Mf * Mf);
@@ -761,7 +867,8 @@ static int make_sh(const ppoaf_icm_shapes_args_t* a, IcmSh& q, bool training) {
     u = IcmDev();
     q.E = a->enc_hidden; q.D = a->enc_dim; q.DP = 16 * ((a->enc_dim + 15) / 16); q.Mi = a->inv_hidden; q.Mf = a->fwd_hidden;
     q.ident = a->enc_hidden == 0;
-    q.n_sl = a->n_action_slices >= 2 ? a->n_action_slices : 0;
+    q.n_sl = sh_slices(a) >= 2 ? sh_slices(a) : 0;
+    q.wide = sh_wide(a);
     u.O = a->obs_dim; u.H = a->enc_dim; u.A = a->action_dim; u.Ain = a->fwd_action_dim;
     u.d_inv = a->depth_inv; u.d_fwd = a->depth_fwd; u.act = a->activation; u.discrete = a->discrete != 0;
     u.enc_off = a->enc_offset; u.inv_off = a->inv_offset; u.fwd_off = a->fwd_offset; u.enc_size = a->inv_offset - a->enc_offset;
@@ -799,13 +906,17 @@ static size_t sh_lds_enc_bwd(const IcmSh& q) {
     const size_t ES = q.E + 4, DS = q.DP + 4;
     return (5 * kRows * ES + kRows * DS) * 4;
 }
-static size_t sh_lds_models(const IcmSh& q, int M, int depth, int AW) {
+template <int AW>
+static size_t sh_lds_models(const IcmSh& q, int M, int depth) {
+    using F = ShForm<AW>;
     const size_t MS = M + 4, DS = q.DP + 4;
-    return (160 + (size_t)AW * M + kRows * kShXS + 3 * kRows * DS + (size_t)(depth + 2) * kRows * MS + 2 * kRows * kMaxOut) * 4;
+    return (F::kWout + (size_t)AW * M + kRows * F::XS + 3 * kRows * DS + (size_t)(depth + 2) * kRows * MS + 2 * kRows * F::OS) * 4;
 }
+template <int AW>
 static size_t sh_lds_reward(const IcmSh& q) {
+    using F = ShForm<AW>;
     const size_t MS = q.Mf + 4, DS = q.DP + 4;
-    return (144 + kRows * kShXS + 3 * kRows * DS + (size_t)q.d.d_fwd * kRows * MS) * 4;
+    return (F::kBout + kRows * F::XS + 3 * kRows * DS + (size_t)q.d.d_fwd * kRows * MS) * 4;
 }
 
 template <int ET>
@@ -833,8 +944,8 @@ static int launch_sh_models(const IcmSh& q, int only, hipStream_t s) {
     const IcmDev& u = q.d;
     static bool big = false;
     const int dmax = only < 0 ? (u.d_inv > u.d_fwd ? u.d_inv : u.d_fwd) : (only == 0 ? u.d_inv : u.d_fwd);
-    // widest case (M 128, D 128, depth 3, AW 16): 19936 floats = 79744 B
-    const size_t lds = sh_lds_models(q, 16 * MT, dmax, AW);
+    // widest case (M 128, D 128, depth 3): AW 16 19936 floats = 79744 B; AW 32 23152 floats = 92608 B
+    const size_t lds = sh_lds_models<AW>(q, 16 * MT, dmax);
     PPOAF_REQUIRE(lds <= kShMaxLds, "icm_shapes: the models kernel needs %zu B of LDS (> 160 KiB)", lds);      // (sh_check: A <= AW)
     const int rc = allow_large_lds(reinterpret_cast<const void*>(icm_sh_models_kernel<MT, AW>), lds, big, "icm_sh_models");
     if (rc) return rc;
@@ -845,6 +956,7 @@ static int launch_sh_models(const IcmSh& q, int only, hipStream_t s) {
 }
 template <int MT>
 static int launch_sh_models(const IcmSh& q, int only, hipStream_t s) {
+    if (q.wide) return launch_sh_models<MT, 32>(q, only, s);
     return q.n_sl >= 2 ? launch_sh_models<MT, 16>(q, only, s) : launch_sh_models<MT, 8>(q, only, s);
 }
 static int launch_sh_models(const IcmSh& q, int M, int only, hipStream_t s) {
@@ -853,15 +965,20 @@ static int launch_sh_models(const IcmSh& q, int M, int only, hipStream_t s) {
     return launch_sh_models<8>(q, only, s);
 }
 
-template <int MT>
+template <int MT, int AW>
 static int launch_sh_reward(const IcmSh& q, float scale, float* intr_out, hipStream_t s) {
     static bool big = false;
-    const size_t lds = sh_lds_reward(q);      // widest case (Mf 128, D 128, depth 3): 13136 floats = 52544 B
+    // widest case (Mf 128, D 128, depth 3): 13136 floats = 52544 B; wide tile 13776 floats = 55104 B
+    const size_t lds = sh_lds_reward<AW>(q);
     PPOAF_REQUIRE(lds <= kShMaxLds, "icm_shapes: the reward kernel needs %zu B of LDS (> 160 KiB)", lds);
-    const int rc = allow_large_lds(reinterpret_cast<const void*>(icm_sh_reward_kernel<MT>), lds, big, "icm_sh_reward");
+    const int rc = allow_large_lds(reinterpret_cast<const void*>(icm_sh_reward_kernel<MT, AW>), lds, big, "icm_sh_reward");
     if (rc) return rc;
-    hipLaunchKernelGGL(icm_sh_reward_kernel<MT>, dim3((unsigned)q.d.nT), dim3(kThreadsU), lds, s, q, scale, intr_out);
+    hipLaunchKernelGGL((icm_sh_reward_kernel<MT, AW>), dim3((unsigned)q.d.nT), dim3(kThreadsU), lds, s, q, scale, intr_out);
     return check_launch("icm_sh_reward");
+}
+template <int MT>
+static int launch_sh_reward(const IcmSh& q, float scale, float* intr_out, hipStream_t s) {
+    return q.wide ? launch_sh_reward<MT, 32>(q, scale, intr_out, s) : launch_sh_reward<MT, 8>(q, scale, intr_out, s);
 }
 
 // the layouts the ctypes structure of _lib.py restates (tests/test_icm_shapes_scope.py reads this list)
@@ -901,6 +1018,7 @@ extern "C" int ppoaf_icm_shapes_workspace_bytes(const ppoaf_icm_shapes_args_t* a
     q.d = IcmDev();
     q.E = args->enc_hidden; q.D = args->enc_dim; q.DP = 16 * ((args->enc_dim + 15) / 16); q.Mi = args->inv_hidden; q.Mf = args->fwd_hidden;
     q.ident = args->enc_hidden == 0;
+    q.wide = sh_wide(args);
     q.d.O = args->obs_dim; q.d.d_inv = args->depth_inv; q.d.d_fwd = args->depth_fwd;
     q.d.Bpad = (args->B + kRows - 1) / kRows * kRows;
     *bytes_out = (int64_t)sh_layout(q, nullptr, nullptr);

@@ -1242,10 +1242,18 @@ def _icm_action_slices(icm):
     return len(nvec), sum(nvec), ""
 
 
-def _describe_icm_shapes(icm, action_dtype, multi_discrete=False):
+def _icm_action_widths_reason(A, Ain, wide_actions):
+    """'' when Discrete / Box action widths are the kernels': [1, 8], or [1, WIDE_HEAD_MAX] with wide_actions."""
+    top = WIDE_HEAD_MAX if wide_actions else 8
+    return "" if 1 <= A <= top and 1 <= Ain <= top else f"action widths ({A}, {Ain}) must be in [1, {top}]"
+
+
+def _describe_icm_shapes(icm, action_dtype, multi_discrete=False, wide_actions=False):
     """IcmShapesArgs topology fields (+ general=True) of an ICM, or (None, reason).  Covered: encoder O -> E -> E -> E -> D,
     inverse 2D -> Mi (x 1..3) -> A, forward D + Ain -> Mf (x 1..3) -> D; E, Mi, Mf in (32, 64, 128), 1 <= D <= 128.
-    multi_discrete: MultiDiscrete actions are described as well (n_action_slices; _icm_action_slices has the limits)."""
+    multi_discrete: MultiDiscrete actions are described as well (n_action_slices; _icm_action_slices has the limits).
+    wide_actions (the opt-in PPOPolicy.fused_wide_icm_actions): Discrete / Box widths of 9 .. WIDE_HEAD_MAX are described too;
+    the topology carries _lib.ICM_WIDE_ACTIONS only when a width is above 8."""
     from .networks.icm import ICM, LinearObservationEncoder
     if not isinstance(icm, ICM):
         return None, "not an ICM"
@@ -1288,8 +1296,8 @@ def _describe_icm_shapes(icm, action_dtype, multi_discrete=False):
     if slices:
         if (A, Ain) != (classes, classes):
             return None, f"action widths ({A}, {Ain}) are not the {classes} classes of the multi-discrete action space"
-    elif not (1 <= A <= 8 and 1 <= Ain <= 8):
-        return None, f"action widths ({A}, {Ain}) must be in [1, 8]"
+    elif _icm_action_widths_reason(A, Ain, wide_actions):
+        return None, _icm_action_widths_reason(A, Ain, wide_actions)
     if action_dtype == "discrete" and Ain != A:
         return None, "unsupported action space for the fused ICM update"
     acts = {_activation_code(a) for a in (icm.activation, icm.obs_encoder.activation, icm.inv_model.activation,
@@ -1306,14 +1314,16 @@ def _describe_icm_shapes(icm, action_dtype, multi_discrete=False):
                 enc_offset=marks[0], inv_offset=marks[1], fwd_offset=marks[2], bucket_total=total)
     if slices:
         topo.update(discrete=1, n_action_slices=slices)
+    elif max(A, Ain) > 8:
+        topo.update(n_action_slices=_lib.ICM_WIDE_ACTIONS)
     return topo, ""
 
 
-def _describe_icm_identity(icm, action_dtype, multi_discrete=False):
+def _describe_icm_identity(icm, action_dtype, multi_discrete=False, wide_actions=False):
     """IcmShapesArgs topology fields (+ general=True, identity=True) of an ICM whose encoder is nn.Identity()
     (encoded_obs_dim = 0), or (None, reason).  The kernels read it as enc_hidden = 0, enc_dim = obs_dim = O and an encoder
     of size 0 (enc_offset == inv_offset).  Covered: 1 <= O <= 128, inverse 2 O -> Mi (x 1..3) -> A, forward O + Ain -> Mf
-    (x 1..3) -> O; Mi, Mf in (32, 64, 128)."""
+    (x 1..3) -> O; Mi, Mf in (32, 64, 128).  multi_discrete / wide_actions: as _describe_icm_shapes."""
     from .networks.icm import ICM
     if not isinstance(icm, ICM):
         return None, "not an ICM"
@@ -1348,8 +1358,8 @@ def _describe_icm_identity(icm, action_dtype, multi_discrete=False):
     if slices:
         if (A, Ain) != (classes, classes):
             return None, f"action widths ({A}, {Ain}) are not the {classes} classes of the multi-discrete action space"
-    elif not (1 <= A <= 8 and 1 <= Ain <= 8):
-        return None, f"action widths ({A}, {Ain}) must be in [1, 8]"
+    elif _icm_action_widths_reason(A, Ain, wide_actions):
+        return None, _icm_action_widths_reason(A, Ain, wide_actions)
     if action_dtype == "discrete" and Ain != A:
         return None, "unsupported action space for the fused ICM update"
     acts = {_activation_code(a) for a in (icm.activation, icm.inv_model.activation, icm.forward_model.activation)}
@@ -1366,15 +1376,26 @@ def _describe_icm_identity(icm, action_dtype, multi_discrete=False):
                 bucket_total=total)
     if slices:
         topo.update(discrete=1, n_action_slices=slices)
+    elif max(A, Ain) > 8:
+        topo.update(n_action_slices=_lib.ICM_WIDE_ACTIONS)
     return topo, ""
 
 
-def describe_icm_chain(icm, action_dtype, multi_discrete=False):
+def icm_wide_actions(pol):
+    """The policy's ICM may take Discrete / Box actions of 9 .. WIDE_HEAD_MAX classes or dimensions on the shapes chain
+    (PPOPolicy.fused_wide_icm_actions, set by hand)."""
+    return bool(getattr(pol, "fused_wide_icm_actions", False))
+
+
+def describe_icm_chain(icm, action_dtype, multi_discrete=False, wide_actions=False):
     """Which K14 chain trains `icm`: the one-width description, else the one for widths of their own, else the identity
     encoder's; (topology, "") or (None, reason of the describer that matches the ICM's encoder type).
     multi_discrete (the opt-in PPOPolicy.fused_shared_icm): an ICM over MultiDiscrete actions of equal class counts is
     described too -- always on the shapes chain or the identity form, whose kernels have the multi-categorical head; the
-    one-width chain is not asked.  Without it such an ICM is refused as before."""
+    one-width chain is not asked.  Without it such an ICM is refused as before.
+    wide_actions (the opt-in PPOPolicy.fused_wide_icm_actions): an ICM that the describers refuse is asked again with
+    Discrete / Box widths up to WIDE_HEAD_MAX on the shapes chain or the identity form -- a one-width ICM (128/128/128) with
+    such actions too: the one-width kernels keep 8.  Whatever is described without it is described exactly so with it."""
     if multi_discrete and action_dtype == "multi-discrete":
         if isinstance(getattr(icm, "obs_encoder", None), nn.Identity):
             return _describe_icm_identity(icm, action_dtype, True)
@@ -1383,7 +1404,9 @@ def describe_icm_chain(icm, action_dtype, multi_discrete=False):
     if topo is not None:
         return topo, ""
     if isinstance(getattr(icm, "obs_encoder", None), nn.Identity):
-        return _describe_icm_identity(icm, action_dtype)
+        return _describe_icm_identity(icm, action_dtype, wide_actions=wide_actions)
+    if wide_actions and action_dtype in ("discrete", "continuous"):
+        return _describe_icm_shapes(icm, action_dtype, wide_actions=True)
     return None, why
 
 
@@ -1472,7 +1495,10 @@ class FusedIcmUpdate(FusedEpoch):
     min_tail_rows = 1
 
     @staticmethod
-    def unsupported_reason(pol, batch_size=None):
+    def unsupported_reason(pol, batch_size=None, wide_actions=None):
+        """'' or why the torch path trains the policy's ICM.  wide_actions: None reads the policy's opt-in."""
+        if wide_actions is None:
+            wide_actions = icm_wide_actions(pol)
         if not pol.enable_icm:
             return "no ICM"
         if FusedIcmUpdate._shared(pol):
@@ -1481,12 +1507,18 @@ class FusedIcmUpdate(FusedEpoch):
         if pol.agent_grouping and pol.agent_shared_icm:
             return ("agent_shared_icm: one ICM over the MultiDiscrete action space of the whole group (ppo.py:2520-2538) "
                     "is not covered, torch path")
-        _, why = describe_icm_chain(pol.icm_model, pol.action_dtype)
+        _, why = describe_icm_chain(pol.icm_model, pol.action_dtype, wide_actions=wide_actions)
         if not why and pol.agent_grouping and batch_size is not None:
             A = FusedIcmUpdate._agents(pol)
             if batch_size * A > 65536:
                 return f"agent-grouped policy: batch_size x agents = {batch_size} x {A} ICM rows per mini-batch exceed 65536"
         return why
+
+    @staticmethod
+    def wide_actions_would_take(pol, batch_size=None):
+        """True for an ICM that is refused only because `fused_wide_icm_actions` is off (what `verbose` adds to the refusal)."""
+        return bool(not icm_wide_actions(pol) and FusedIcmUpdate.unsupported_reason(pol, batch_size, wide_actions=False)
+                    and not FusedIcmUpdate.unsupported_reason(pol, batch_size, wide_actions=True))
 
     @staticmethod
     def _shared(pol):
@@ -1508,7 +1540,7 @@ class FusedIcmUpdate(FusedEpoch):
         if self.shared:
             self.topo, _ = describe_icm_chain(pol.icm_model, pol.icm_model.action_dtype, multi_discrete=True)
         else:
-            self.topo, _ = describe_icm_chain(pol.icm_model, pol.action_dtype)
+            self.topo, _ = describe_icm_chain(pol.icm_model, pol.action_dtype, wide_actions=icm_wide_actions(pol))
         self.general = bool(self.topo.get("general"))      # csrc/icm_update_shapes.hip: split-wgrad form only, no in-kernel waits
         self.A = self._agents(pol)                         # ICM samples per buffer row (agent-grouped policies: the agents)
         rows = self.B * self.A                             # everything below is sized for a full mini-batch's samples

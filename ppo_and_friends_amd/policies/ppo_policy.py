@@ -118,6 +118,13 @@ class PPOPolicy:
     # 8"); a policy with out_dim <= 8 computes bitwise the same, flag on or off.  MultiDiscrete / MultiBinary heads, LSTM and
     # MAT policies, ICMs and every other width pair keep 8.
     fused_wide_heads = False
+    # Opt-in: an ICM over Discrete / Box actions of 9 .. 24 classes or dimensions (Discrete(18), Box(17)) on K14's shapes chain
+    # and its identity form, update epoch and rollout-time reward: the 32-column action form, which the library runs when
+    # the topology carries PPOAF_ICM_WIDE_ACTIONS; a one-width ICM (128/128/128) with such actions goes to the shapes chain too.
+    # Set by hand, on the class or on the policy, before the first rollout -- no update_mode sets it.  False: the torch path for
+    # those ICMs, with today's messages ("action widths (18, 18) must be in [1, 8]"); an ICM with action widths <= 8 computes
+    # bitwise the same, flag on or off.  MultiDiscrete ICMs keep 16 classes in all.
+    fused_wide_icm_actions = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -734,11 +741,11 @@ class PPOPolicy:
         st = getattr(self, "_icm_reward_state", None)
         n = obs_1.shape[0]
         if st is None or st["n"] != n:
-            from ..fused_update import describe_icm_chain, icm_scratch_floats, icm_topology_args
+            from ..fused_update import describe_icm_chain, icm_scratch_floats, icm_topology_args, icm_wide_actions
             if shared:
                 topo, why = describe_icm_chain(self.icm_model, self.icm_model.action_dtype, multi_discrete=True)
             else:
-                topo, why = describe_icm_chain(self.icm_model, self.action_dtype)
+                topo, why = describe_icm_chain(self.icm_model, self.action_dtype, wide_actions=icm_wide_actions(self))
             if topo is None:
                 self.fused_icm_reward = False
                 return None

@@ -1420,7 +1420,10 @@ class PPO:
             from .fused_update import FusedIcmUpdate
             why = FusedIcmUpdate.unsupported_reason(self.policies[policy_id], self.batch_size)
             if why and self.verbose:
-                rank_print(f"policy {policy_id}: torch ICM update path ({why})")
+                hint = ""
+                if FusedIcmUpdate.wide_actions_would_take(self.policies[policy_id], self.batch_size):
+                    hint = "; PPOPolicy.fused_wide_icm_actions = True would take it on the fused kernels"
+                rank_print(f"policy {policy_id}: torch ICM update path ({why}){hint}")
             self._fused[key] = None if why else FusedIcmUpdate(self, policy_id)
         return self._fused[key]
 

@@ -14,14 +14,21 @@ shape before that chain existed.  Two more cases, each against the torch path th
                sets the opt-in PPOPolicy.fused_shared_icm (K14's shapes chain, n_action_slices = A), the "torch" leg leaves it
                off, which keeps the ICM epoch and MATPolicy.get_agent_shared_intrinsic_rewards on the torch path.  Combines
                with --identity.
+  --action discrete:N | box:N   another action space for the single-agent cases (the syntax of tools/width_pairs_bench.py;
+               Box bounds -1 .. 1), --obs-dim O another observation width.  Above 8 classes or dimensions the ICM needs
+  --wide-actions   both legs run update_mode="auto" (the policy's own 18-output actor is not the subject and stays where it
+               is); the "fused" leg sets the opt-in PPOPolicy.fused_wide_icm_actions (K14's shapes chain, the 32-column
+               action form), the "torch" leg leaves it off, which keeps the ICM epoch and the reward on the torch path.
+               mario_bros_ram's ICM: --wide-actions --action discrete:18 --obs-dim 256 --batch 128.
 
 Both legs live in one process on the same rollout shape; after a warm-up pass of each they are ALTERNATED `--repeats`
 times and timed with device events: the epoch = PPO._icm_batch_train over 2048 mini-batches (shuffle draw included), the
 reward = PPOPolicy.get_intrinsic_reward on the 4096-row env batch (mean of `--reward-calls` back-to-back calls).  Prints the
 median and the spread (min .. max) of both, the launches per mini-batch of the fused chain, and one JSON line.
 
-    python tools/icm_shapes_bench.py [--identity] [--agents A [--shared]] [--envs 4096] [--steps 128] [--batch 256] [--repeats 5]
-                                     [--reward-calls 50] [--allow-torch-path]
+    python tools/icm_shapes_bench.py [--identity] [--agents A [--shared]] [--action discrete:N|box:N] [--obs-dim O] [--wide-actions]
+                                     [--envs 4096] [--steps 128] [--batch 256] [--repeats 5] [--reward-calls 50]
+                                     [--allow-torch-path]
 
 --allow-torch-path: do not insist that the "fused" leg has a fused updater -- for running this tool on a commit whose K14
 does not cover the case yet (both legs then time the torch path, which is what that commit runs).
@@ -43,17 +50,25 @@ BASELINE_KW = dict(encoded_obs_dim=9, encoder_hidden_size=128, inverse_hidden_si
 IDENTITY_KW = dict(encoded_obs_dim=0, inverse_hidden_size=128, forward_hidden_size=128)
 
 
+def action_space(spec):
+    """--action discrete:N | box:N -> the space (Box bounds -1 .. 1 on every dimension)."""
+    from ppo_and_friends_amd.spaces import Box, Discrete
+    kind, _, n = spec.partition(":")
+    if kind not in ("discrete", "box") or not n.isdigit() or int(n) < 1:
+        raise ValueError(f"--action {spec!r}: expected discrete:N or box:N")
+    return Discrete(int(n)) if kind == "discrete" else Box(-1.0, 1.0, (int(n),), np.float32)
+
+
 def case_of(args):
     """-> (O, action space, agents, ICM keyword arguments) of the case the flags select."""
     from ppo_and_friends_amd.spaces import Box, Discrete
     if args.agents > 1:
         return 18, Discrete(5), args.agents, (dict(IDENTITY_KW) if args.identity else {})
-    if args.identity:
-        return 2, Discrete(5), 1, dict(IDENTITY_KW)
-    return 17, Box(-1.0, 1.0, (6,), np.float32), 1, dict(BASELINE_KW)
+    O, space, kw = (2, Discrete(5), IDENTITY_KW) if args.identity else (17, Box(-1.0, 1.0, (6,), np.float32), BASELINE_KW)
+    return args.obs_dim or O, action_space(args.action) if args.action else space, 1, dict(kw)
 
 
-def make(mode, E, T, B, case, shared=False):
+def make(mode, E, T, B, case, shared=False, wide_actions=False):
     from ppo_and_friends_amd.ppo import PPO
     from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
     from ppo_and_friends_amd.spaces import Box
@@ -71,9 +86,11 @@ def make(mode, E, T, B, case, shared=False):
         kw["agent_shared_icm"] = True
     ppo = PPO(env_gen, {"p": (cls, sp, sp, space, kw)}, device=DEV, random_seed=4,
               normalize_obs=False, normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=B, epochs_per_iter=1,
-              update_mode="fused" if shared else mode)
+              update_mode="fused" if shared else "auto" if wide_actions else mode)
     if shared and mode == "fused":
         ppo.policies["p"].fused_shared_icm = True              # the opt-in, before the first rollout
+    if wide_actions and mode == "fused":
+        ppo.policies["p"].fused_wide_icm_actions = True        # likewise
     ppo.rollout()
     return ppo
 
@@ -94,6 +111,9 @@ def main():
     ap.add_argument("--agents", type=int, default=1)
     ap.add_argument("--shared", action="store_true")
     ap.add_argument("--allow-torch-path", action="store_true")
+    ap.add_argument("--action", default=None, help="discrete:N or box:N (single-agent cases)")
+    ap.add_argument("--obs-dim", type=int, default=None, help="observation width (single-agent cases)")
+    ap.add_argument("--wide-actions", action="store_true", help="the fused leg sets PPOPolicy.fused_wide_icm_actions")
     ap.add_argument("--envs", type=int, default=None)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--batch", type=int, default=256)
@@ -102,6 +122,17 @@ def main():
     args = ap.parse_args()
     if args.shared and args.agents < 2:
         ap.error("--shared needs --agents A with A >= 2")
+    if args.agents > 1 and (args.action or args.obs_dim or args.wide_actions):
+        ap.error("--action, --obs-dim and --wide-actions are for the single-agent cases")
+    if args.wide_actions:
+        # (at 8 or fewer the opt-in changes nothing: both legs would run the fused chain and there is nothing to compare)
+        try:
+            width = action_space(args.action or "")
+        except ValueError:
+            ap.error("--wide-actions needs --action discrete:N or box:N with N in 9..24")
+        width = width.n if hasattr(width, "n") else width.shape[0]
+        if not 9 <= width <= 24:
+            ap.error(f"--wide-actions needs an action width in 9..24 (--action {args.action}: {width})")
     if args.envs is None:
         args.envs = 1024 if args.agents > 1 else 4096
     from ppo_and_friends_amd.ppo import PermutationLoader
@@ -111,7 +142,7 @@ def main():
     O, space, A, icm_kw = case
     legs, path = {}, {}
     for mode in ("fused", "torch"):
-        ppo = make(mode, args.envs, args.steps, args.batch, case, args.shared)
+        ppo = make(mode, args.envs, args.steps, args.batch, case, args.shared, args.wide_actions)
         pol = ppo.policies["p"]
         upd = ppo._fused_icm_updater("p")
         path[mode] = "torch" if upd is None else "K14"
@@ -119,8 +150,9 @@ def main():
             assert upd is not None, FusedIcmUpdate.unsupported_reason(pol)
             assert bool(upd.topo.get("identity")) == args.identity, upd.topo
             assert not args.shared or upd.topo.get("n_action_slices") == A, upd.topo
+            assert not args.wide_actions or upd.topo.get("general"), upd.topo
         elif mode == "torch":
-            assert upd is None
+            assert upd is None, "the torch leg got a fused ICM updater: there is no torch path to compare against at this shape"
         loader = PermutationLoader(pol.dataset, args.batch, ppo.loader_generator)
         buf = pol.buffer
         rows = args.envs * A                                     # the env batch of one step: one row per (env, agent)
@@ -159,7 +191,7 @@ def main():
     else:
         launches = 2 if legs["fused"]["upd"].fuse_reason() == "" else 4
     out = dict(shape=dict(O=O, actions=f"Discrete({space.n})" if hasattr(space, "n") else f"Box({space.shape[0]})", agents=A, envs=args.envs, steps=args.steps, batch=args.batch,
-                          shared_icm=args.shared, icm_rows_per_minibatch=args.batch * (1 if args.shared else A), minibatches=n_mb,
+                          shared_icm=args.shared, wide_actions=args.wide_actions, icm_rows_per_minibatch=args.batch * (1 if args.shared else A), minibatches=n_mb,
                           **icm_kw),
                path=path, fused_launches_per_minibatch=launches)
     for mode, leg in legs.items():
