@@ -7,9 +7,11 @@ PINNED by the g12_* fixtures: float64 reproduces the first mini-batch's losses a
 fixture (tests/test_k12_oracle.py).  Built from the pinned pieces:
 
   networks                <- cpu_ppo_loop.make_mlp                     networks/utils.py:120-191
-  categorical / tanh-Gaussian heads <- ppo_loss_oracle                 networks/distributions.py:199-269, :441-694
-  MultiDiscrete / MultiBinary heads  (torch.distributions, like the product's networks/distributions.py; fixture g16)
-                                                                       networks/distributions.py:134-196, :272-438
+  tanh-Gaussian head      <- ppo_loss_oracle                           networks/distributions.py:441-694
+  Categorical / MultiDiscrete / MultiBinary heads: torch.distributions' text written out, probs_to_logits' clamp at
+                          float32's eps in EVERY dtype -- the constant of the reference (a float32 program) and of the
+                          kernels; held to torch.distributions in float32 by tests/test_head_gates_oracle.py (fixture g16)
+                                                                       networks/distributions.py:134-269, :272-438
   value normaliser        <- running_stats_oracle.RunningMeanStd       utils/stats.py:73-94, misc.py:106-111
   surrogate / entropy / KL / critic loss                               ppo.py:2325-2419
   clip + Adam             <- clip_grad_norm_ + torch.optim.Adam         policies/ppo_policy.py:1032-1055
@@ -18,6 +20,7 @@ Layouts are K12's (include/ppoaf_hip.h ppoaf_mlp_desc_t, csrc/ppo_update.hip fil
 [out, in] row-major, then the bias, each padded to 4 floats; the Gaussian head's log_std follows the actor's last
 bias (padded to 4); the critic's segment follows the actor's.  Padding stays zero in the gradient bucket.
 """
+import math
 from typing import NamedTuple
 
 import numpy as np
@@ -97,25 +100,127 @@ def pre_activations(net, seg, x, dtype=torch.float64):
     return out
 
 
-def _head_terms(head, out, log_std, actions, slices, min_std, entropy_slice_scale):
-    """(log-prob, entropy) per row of the actor output."""
+EPS32 = float(np.finfo(np.float32).eps)   # probs_to_logits' clamp in the reference (a float32 program) and in the kernels
+
+
+class GatePlants(NamedTuple):
+    """Errors planted in the heads' gradient gates by the sharpness tests (tests/test_head_gates_oracle.py), never set
+    otherwise.  Each leaves the forward values alone and lets gradient through where the clean text passes none."""
+    gate_open: bool = False                # the discrete clamp to [eps32, 1 - eps32] passes gradient everywhere
+    gate_on_chosen_only: bool = False      # the entropy term's gate is dropped, the chosen class's gate is kept
+    density_clamp_open: bool = False       # clamp(Normal.log_prob, -100, 100) passes gradient outside
+    tanh_clamp_open: bool = False          # the entropy's clamp(1 - tanh(mean)^2, 1e-6) passes gradient below
+    floor_open: bool = False               # max(softplus(log_std), min_std) passes gradient to log_std below the floor
+    softplus_no_identity: bool = False     # d softplus = sigmoid(log_std) above 20 in place of 1
+
+
+class _Through(torch.autograd.Function):
+    """forward: `y` (the clamped / floored value of x); backward: the gradient handed to x as it is (an open gate)."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        return y.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+class _SoftplusSigmoid(torch.autograd.Function):
+    """softplus whose derivative is sigmoid(x) on the identity branch (x > 20) as well."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return nn.functional.softplus(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g * torch.sigmoid(ctx.saved_tensors[0])
+
+
+def _clamp(x, lo, hi, through=False):
+    y = torch.clamp(x, lo, hi)
+    return _Through.apply(x, y.detach()) if through else y
+
+
+def _categorical_terms(z, a, plants, note):
+    """Categorical(probs=softmax(z)) written out (torch.distributions: probs / probs.sum, probs_to_logits' clamp, log)
+    with the clamp at float32's eps in every dtype -> (log-prob [rows], entropy [rows])."""
+    p = torch.softmax(z, dim=-1)
+    n = p / p.sum(-1, keepdim=True)
+    note(n)
+    l = torch.log(_clamp(n, EPS32, 1.0 - EPS32, plants.gate_open))
+    le = torch.log(_clamp(n, EPS32, 1.0 - EPS32, True)) if plants.gate_on_chosen_only else l
+    return l.gather(-1, a.reshape(-1, 1)).squeeze(-1), -(n * le).sum(-1)
+
+
+def _bernoulli_terms(z, a, plants, note):
+    """Bernoulli(probs=sigmoid(z)) written out (probs_to_logits(is_binary=True), log_prob and entropy as binary cross
+    entropies with logits; the entropy's target p carries gradient) with the clamp at float32's eps in every dtype."""
+    bce = nn.functional.binary_cross_entropy_with_logits
+    p = torch.sigmoid(z)
+    note(p)
+    q = _clamp(p, EPS32, 1.0 - EPS32, plants.gate_open)
+    l = torch.log(q) - torch.log1p(-q)
+    le = l
+    if plants.gate_on_chosen_only:
+        qe = _clamp(p, EPS32, 1.0 - EPS32, True)
+        le = torch.log(qe) - torch.log1p(-qe)
+    return -bce(l, a, reduction="none").sum(-1), bce(le, p, reduction="none").sum(-1)
+
+
+def _gaussian_planted(mean, log_std, x, min_std, plants, tanh_open):
+    """ppo_loss_oracle.gaussian_tanh_logp with a place for each planted gate error."""
+    sp = _SoftplusSigmoid.apply(log_std) if plants.softplus_no_identity else nn.functional.softplus(log_std)
+    std = torch.max(sp, torch.tensor([min_std], dtype=torch.float32))
+    if plants.floor_open:
+        std = _Through.apply(sp, std.detach())
+    nlp = torch.distributions.Normal(mean, std).log_prob(x)
+    nlp = _clamp(nlp, -100, 100, plants.density_clamp_open).sum(dim=-1)
+    s_log = torch.log(torch.clamp(1.0 - torch.pow(torch.tanh(x), 2), 1e-6, None))
+    if tanh_open:       # the clamped value with the gradient of log(1 - tanh(x)^2) = 2 (log 2 - x - softplus(-2 x)): -2 tanh(x)
+        f = 2.0 * (math.log(2.0) - x - nn.functional.softplus(-2.0 * x))
+        s_log = s_log.detach() + (f - f.detach())
+    return nlp - s_log.sum(dim=-1)
+
+
+def _head_terms(head, out, log_std, actions, slices, min_std, entropy_slice_scale, plants=GatePlants(), gate_args=None):
+    """(log-prob, entropy) per row of the actor output.  The discrete heads are torch.distributions' text written out, so
+    that the clamp of probs_to_logits stands at float32's eps in every dtype (tests/test_head_gates_oracle.py holds the
+    text to torch.distributions).  gate_args: a dict that receives the arguments of the heads' gradient gates, in the run's
+    dtype -- n [rows, classes] (renormalised probabilities; MultiBinary: p), or density / tanh_prime [rows, D] and
+    softplus / log_std [D]."""
+    args = {} if gate_args is None else gate_args
+    note = lambda n: args.setdefault("n", []).append(n.detach())
     if head == "categorical":
-        logp, ent, _ = lo.categorical_logp_entropy(out, actions.long().reshape(-1))
-        return logp, ent
-    if head == "gaussian":                                 # entropy := -log_prob of the mean (distributions.py:694)
-        return (lo.gaussian_tanh_logp(out, log_std, actions, min_std),
-                -lo.gaussian_tanh_logp(out, log_std, out, min_std))
-    if head == "multi_categorical":                        # one Categorical per slice, summed (:272-438)
+        logp, ent = _categorical_terms(out, actions.long().reshape(-1), plants, note)
+    elif head == "gaussian":                               # entropy := -log_prob of the mean (distributions.py:694)
+        if any(plants):
+            logp = _gaussian_planted(out, log_std, actions, min_std, plants, False)
+            ent = -_gaussian_planted(out, log_std, out, min_std, plants, plants.tanh_clamp_open)
+        else:
+            logp = lo.gaussian_tanh_logp(out, log_std, actions, min_std)
+            ent = -lo.gaussian_tanh_logp(out, log_std, out, min_std)
+        with torch.no_grad():
+            sp = nn.functional.softplus(log_std)
+            args["softplus"], args["log_std"] = sp, log_std.detach()
+            args["density"] = lo.gaussian_dist(out, log_std, min_std).log_prob(actions)
+            args["tanh_prime"] = 1.0 - torch.pow(torch.tanh(out), 2)
+    elif head == "multi_categorical":                      # one Categorical per slice, summed (:272-438)
         lps, ents, start = [], [], 0
         a = actions.long().reshape(out.shape[0], -1)
         for d, n in enumerate(slices):
-            dist = torch.distributions.Categorical(probs=torch.softmax(out[:, start:start + n], dim=-1))
-            lps.append(dist.log_prob(a[:, d]))
-            ents.append(dist.entropy() * entropy_slice_scale.get(d, 1.0))
+            lp, en = _categorical_terms(out[:, start:start + n], a[:, d], plants, note)
+            lps.append(lp)
+            ents.append(en * entropy_slice_scale.get(d, 1.0))
             start += n
-        return torch.stack(lps, -1).sum(-1), torch.stack(ents, -1).sum(-1)
-    dist = torch.distributions.Bernoulli(probs=torch.sigmoid(out), validate_args=False)     # (:134-196)
-    return dist.log_prob(actions.reshape(out.shape).to(out.dtype)).sum(-1), dist.entropy().sum(-1)
+        logp, ent = torch.stack(lps, -1).sum(-1), torch.stack(ents, -1).sum(-1)
+    else:                                                  # MultiBinary: independent Bernoullis (:134-196)
+        logp, ent = _bernoulli_terms(out, actions.reshape(out.shape).to(out.dtype), plants, note)
+    if "n" in args:
+        args["n"] = torch.cat(args["n"], dim=-1)
+    return logp, ent
 
 
 def normalised_rtg(rtg, vn_state, records, dtype=torch.float64):
@@ -190,12 +295,13 @@ class Consts(NamedTuple):
 
 
 def minibatch(params, actor, critic, head, slices, mb, consts, vn_state=(0.0, 1.0, 1e-4), records=None,
-              dtype=torch.float64, adv_std_ddof=1, clip_wrong_side=False, entropy_slice_scale=None):
+              dtype=torch.float64, adv_std_ddof=1, clip_wrong_side=False, entropy_slice_scale=None, *,
+              gate_plants=GatePlants()):
     """
     One K12 mini-batch from the flat parameter bucket `params` -> dict(totals [8], grads [bucket size] in K12's layout,
-    padding zero; values [B] (critic outputs); vn (the normaliser state after the records)).  `records`: this
-    mini-batch's (n, mean, M2) per rank (default: the mini-batch's own rewards-to-go).  The remaining keywords plant
-    errors for the sharpness tests only.
+    padding zero; values [B] (critic outputs); vn (the normaliser state after the records); gate_args: the arguments of
+    the head's gradient gates in the run's dtype, see _head_terms).  `records`: this mini-batch's (n, mean, M2) per rank
+    (default: the mini-batch's own rewards-to-go).  The remaining keywords plant errors for the sharpness tests only.
     """
     params = np.asarray(params, dtype=np.float64)
     _, na = tensor_table(actor, head == "gaussian")
@@ -212,7 +318,9 @@ def minibatch(params, actor, critic, head, slices, mb, consts, vn_state=(0.0, 1.
     T = lambda x: torch.as_tensor(np.asarray(x), dtype=dtype)
     out = am(T(mb.obs))
     values = cm(T(mb.critic_obs)).reshape(-1)
-    logp, ent = _head_terms(head, out, log_std, T(mb.raw_actions), slices, consts.min_std, entropy_slice_scale or {})
+    gate_args = {}
+    logp, ent = _head_terms(head, out, log_std, T(mb.raw_actions), slices, consts.min_std, entropy_slice_scale or {},
+                            gate_plants, gate_args)
     rtg = T(mb.rewards_to_go).reshape(-1)
     vn = None
     if consts.normalize_values:
@@ -232,7 +340,8 @@ def minibatch(params, actor, critic, head, slices, mb, consts, vn_state=(0.0, 1.
     for (tag, name, off, shape), g in zip(tables, list(ga) + list(gc)):
         grads[off:off + g.numel()] = g.detach().double().numpy().reshape(-1)
     return dict(totals=totals, grads=grads, values=values.detach().double().numpy(), rtg=rtg.detach().double().numpy(),
-                logp=logp.detach().double().numpy().reshape(-1), vn=vn)
+                logp=logp.detach().double().numpy().reshape(-1), vn=vn,
+                gate_args={k: v.double().numpy() for k, v in gate_args.items()})
 
 
 def kinked_rows(net, seg, x, rel=1e-4):

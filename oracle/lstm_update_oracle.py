@@ -138,14 +138,16 @@ def _inputs(mb, dtype, mask_from_terminal, mask_critic, states_from_first):
 
 def minibatch(params, actor, critic, head, mb, consts, vn_state=(0.0, 1.0, 1e-4), records=None, dtype=torch.float64,
               mask_from_terminal=False, mask_critic=False, states_from_first=False, drop_b_hh_grad=False, ln_eps=1e-5,
-              adv_std_ddof=1):
+              adv_std_ddof=1, *, gate_plants=ko.GatePlants()):
     """
     One K22 mini-batch from the flat parameter bucket `params` -> dict(totals [8] (ko.SC_NAMES), grads [bucket size] in
     K18's layout, padding zero; values [B] (critic outputs), rtg [B] (normalised), logp [B]; actor_h / actor_c / critic_h /
-    critic_c [B, H]: the final states, written back at the last position; vn: the normaliser state after the records).
+    critic_c [B, H]: the final states, written back at the last position; vn: the normaliser state after the records;
+    gate_args: the arguments of the head's gradient gates, ko._head_terms).
     `records`: this mini-batch's (n, mean, M2) per rank (default: the mini-batch's own rewards-to-go).
     mask_from_terminal, mask_critic, states_from_first, drop_b_hh_grad, ln_eps, adv_std_ddof: planted errors of the
-    sharpness tests (tests/test_lstm_update_oracle.py), never set otherwise.
+    sharpness tests (tests/test_lstm_update_oracle.py), never set otherwise; gate_plants: those of
+    tests/test_head_gates_oracle.py.
     """
     params = np.asarray(params, dtype=np.float64)
     ta, na = tensor_table(actor, head == "gaussian")
@@ -162,7 +164,8 @@ def minibatch(params, actor, critic, head, mb, consts, vn_state=(0.0, 1.0, 1e-4)
     out, ah, ac, _ = am(obs, ah0, ac0)
     val, ch, cc, _ = cm(cobs, ch0, cc0)
     values = val.reshape(-1)
-    logp, ent = ko._head_terms(head, out, log_std, T(mb.raw_actions), (), consts.min_std, {})
+    gate_args = {}
+    logp, ent = ko._head_terms(head, out, log_std, T(mb.raw_actions), (), consts.min_std, {}, gate_plants, gate_args)
     rtg = T(mb.rewards_to_go).reshape(-1)
     vn = None
     if consts.normalize_values:
@@ -184,7 +187,8 @@ def minibatch(params, actor, critic, head, mb, consts, vn_state=(0.0, 1.0, 1e-4)
             grads[off:off + g.numel()] = g.detach().double().numpy().reshape(-1)
     n64 = lambda t: t.detach().double().numpy()
     return dict(totals=totals, grads=grads, values=n64(values), rtg=n64(rtg), logp=n64(logp).reshape(-1),
-                actor_h=n64(ah), actor_c=n64(ac), critic_h=n64(ch), critic_c=n64(cc), vn=vn)
+                actor_h=n64(ah), actor_c=n64(ac), critic_h=n64(ch), critic_c=n64(cc), vn=vn,
+                gate_args={k: n64(v) for k, v in gate_args.items()})
 
 
 def pre_activations(net, seg, x, h0, c0, dtype=torch.float64):

@@ -59,6 +59,9 @@ class Planted(NamedTuple):
     stale_logits: bool = False           # every agent's draw taken from pass 0's logits
     denorm_var: bool = False             # values denormalised with var instead of sqrt(var + 1e-8)
     logp_no_clamp: bool = False          # the log-prob without the clamp to [eps, 1 - eps]
+    # the clamp's gradient gate in K15's backward (tests/test_head_gates_oracle.py)
+    gate_open: bool = False              # the clamp passes gradient everywhere
+    gate_on_chosen_only: bool = False    # the entropy term's gate is dropped, the chosen class's gate is kept
 
 
 def _pad4(n):
@@ -174,9 +177,10 @@ def minibatch(params, A, O, NA, mb, consts, vn_state=(0.0, 1.0, 1e-4), records=N
     actions = torch.as_tensor(np.asarray(mb.raw_actions)).long().reshape(B, A)
     values, probs = net(T(mb.obs).reshape(B, A, O), action_block(actions, A, NA, dtype, planted))
     n = probs / probs.sum(-1, keepdim=True)               # Categorical(probs=...): renormalised, clamped, log
-    l = torch.log(n.clamp(EPS32, 1.0 - EPS32))
+    l = torch.log(ko._clamp(n, EPS32, 1.0 - EPS32, planted.gate_open))
+    le = torch.log(ko._clamp(n, EPS32, 1.0 - EPS32, True)) if planted.gate_on_chosen_only else l
     logp = l.gather(-1, actions.unsqueeze(-1)).squeeze(-1)
-    ent = -(n * l).sum(-1)
+    ent = -(n * le).sum(-1)
     values = values.squeeze(-1)
     rtg, vn = T(mb.rewards_to_go).reshape(B, A), None
     if consts.normalize_values:

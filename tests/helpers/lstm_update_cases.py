@@ -29,6 +29,8 @@ import torch
 from oracle import k12_oracle as ko
 from oracle import lstm_update_oracle as lo
 
+import head_gates as hg
+
 E = 4                           # envs of every case
 VN = (0.3, 0.25, 5000.0)
 STEPS0 = (6, 9)
@@ -37,12 +39,14 @@ KINDS = ("first byte at step 0", "first byte at step S-2", "only byte at step S-
 
 
 def case(I=5, H=32, F=16, depth=1, S=4, B=16, head=("categorical", 3), act="relu", agents=1, norm_adv=True,
-         norm_values=True, huber=True, kl=0.0, ent=0.01, clip=True, second=False, small_h=False, seed=0):
+         norm_values=True, huber=True, kl=0.0, ent=0.01, clip=True, second=False, small_h=False, seed=0, gates=False):
     """agents = 2: two agents per env, the critic sees both observations (in_dim 2 I).  clip = False: gradient_clip None.
     second: mini-batch 1 is run and checked as well.  small_h: output-gate biases of -2.5 + -2.5, so that the LayerNorm
-    sees rows of variance ~1e-4 (its eps matters there)."""
+    sees rows of variance ~1e-4 (its eps matters there).  gates: the head's gradient gates are closed in part of the
+    mini-batch (Steering._steer_gates, tests/helpers/head_gates.py)."""
     return dict(I=I, H=H, F=F, depth=depth, S=S, B=B, head=head, act=act, agents=agents, norm_adv=norm_adv,
-                norm_values=norm_values, huber=huber, kl=kl, ent=ent, clip=clip, second=second, small_h=small_h, seed=seed)
+                norm_values=norm_values, huber=huber, kl=kl, ent=ent, clip=clip, second=second, small_h=small_h, seed=seed,
+                gates=gates)
 
 
 CAT, GAU = "categorical", "gaussian"
@@ -87,6 +91,13 @@ CASES = {
     # a LayerNorm row of small variance
     "ln_small_variance": case(small_h=True, head=(CAT, 3), H=32, F=16, depth=1, S=3, B=24, seed=95),
 }
+# tests/test_gpu_head_gates.py: ppo_head_loss inside K22 with gates closed
+GATES_CASES = {
+    "k22_cat8": case(I=5, H=32, F=16, depth=1, S=4, B=20, head=(CAT, 8), act="relu", seed=921, gates=True),
+    "k22_gau4": case(I=5, H=32, F=16, depth=1, S=4, B=20, head=(GAU, 4), act="tanh", seed=922, gates=True),
+}
+GATES_RMS = 10.0               # of the steered logits: unconfident rows (kind a) and confident ones among the candidates
+GATES_CANDIDATES = 1024
 
 
 def geometry(c):
@@ -201,7 +212,10 @@ class Steering:
             raise AssertionError(f"kink budget: {len(order)} un-kinked items of {items}, {B} needed")
         chosen = np.asarray(chosen, dtype=np.int64)[rng.permutation(B)]
         self.chosen, last = chosen, chosen + S - 1
-        if self.head == "gaussian":
+        self.forced = np.zeros(0, dtype=np.int64)
+        if c["gates"]:
+            self._steer_gates(rng)
+        elif self.head == "gaussian":
             k = max(1, B // 8)
             a = self.raw_actions[last[:k]]
             self.raw_actions[last[:k]] = f32(np.where(a < 0, -1.0, 1.0) * rng.uniform(3.8, 4.2, a.shape))
@@ -212,9 +226,16 @@ class Steering:
         # (small B: the last two rows on either side of the clip for certain, with advantages of either sign)
         self.log_probs[last[-2:]] = np.float32(logp[-2:] - np.log([0.65, 1.45]))
         self.advantages[last[-2:]] = np.abs(self.advantages[last[-2:]]) * np.float32([1.0, -1.0])
+        if len(self.forced):                  # the tuned rows' surrogate inside the clip
+            self.log_probs[last], self.advantages[last] = hg.force_surrogate(self.log_probs[last], self.advantages[last], logp,
+                                                                              self.forced)
         self.mb =self.minibatch_of(chosen)
         self.r64 = self.reference(torch.float64)
         self.r32 = self.reference(torch.float32)
+        self.gates_failures = None
+        if c["gates"]:
+            self.gates_failures = hg.census_failures(self.head, (), O, self.r64, self.r32, self.mb.raw_actions)
+            self.census = hg.describe(self.head, (), self.r64, self.mb.raw_actions)
         # ---- preset optimiser state on the gradient's scale, the two clip thresholds
         g = self.r64["grads"]
         self.pad = np.ones(self.size, dtype=bool)
@@ -257,6 +278,59 @@ class Steering:
     def reference(self, dtype, mb=None, params=None, vn=None, **planted):
         return lo.minibatch(self.params if params is None else params, self.actor, self.critic, self.head,
                             self.mb if mb is None else mb, self.consts, self.vn if vn is None else vn, dtype=dtype, **planted)
+
+    def _steer_gates(self, rng):
+        """The gates steering of tests/helpers/head_gates.py on the chosen items.  A LayerNorm stands before the head, so a
+        row's confidence cannot be tuned by scaling its inputs: each item's (h, c) at its last position -- read by that item
+        alone -- is picked among GATES_CANDIDATES draws (h = 0.9 tanh N(0, 1), c = 1.5 N(0, 1): wider than the other rows', so
+        that the logits move) of generator (seed, 3000 + row) as the first un-kinked one, not near
+        a gate, of the kind the row's index asks for (row % 4: a top class above 1 - eps32; a second class at 0.05 .. 0.45
+        eps32, the tuned row; no class out of range; any)."""
+        c, S, H, seed, head = self.c, self.c["S"], self.c["H"], self.c["seed"], self.head
+        table, na = lo.tensor_table(self.actor, head == "gaussian")
+        spans = {name: (off, shape) for name, off, shape in table}
+        weight, bias = spans[f"ff{self.actor.ff_depth}.weight"], spans[f"ff{self.actor.ff_depth}.bias"]
+        f32 = lambda x: np.asarray(x, dtype=np.float32)
+        T = lambda x: torch.as_tensor(np.asarray(x), dtype=torch.float64)
+        chosen, last = self.chosen, self.chosen + S - 1
+        obs, _, term, _, _ = self.windows(chosen)
+        masked = np.where(lo.window_mask(term)[:, :, None], np.float32(0.0), obs)
+
+        def forward(params, inputs):
+            with torch.no_grad():
+                return lo._Module(self.actor, params[:na], torch.float64)(T(inputs["obs"]), T(inputs["h"]), T(inputs["c"]))[0].numpy()
+
+        inputs = dict(obs=masked, h=self.hidden["actor_hidden"][last], c=self.hidden["actor_cell"][last])
+        self.params, tanh_dim = hg.steer_last_layer(self.params, weight, bias, spans["log_std"][0] if head == "gaussian" else None,
+                                                    self.actor.out_dim, head, lambda p: forward(p, inputs), GATES_RMS)
+        K = GATES_CANDIDATES
+        outs = np.zeros((len(chosen), self.actor.out_dim))
+        for i in range(len(chosen)):
+            g = np.random.default_rng((seed, 3000 + i))
+            cand = dict(obs=np.repeat(masked[i:i + 1], K, axis=0), h=f32(0.9 * np.tanh(g.normal(0, 1, (K, H)))), c=f32(1.5 * g.normal(0, 1, (K, H))))
+            out = forward(self.params, cand)
+            ok = ~lo.kinked_items(self.actor, self.params[:na], cand["obs"], cand["h"], cand["c"])
+            if head == "gaussian":
+                tp = (1.0 - np.tanh(out) ** 2) / 1e-6
+                ok &= ~((tp >= 0.5) & (tp <= 2.0)).any(axis=1)
+                want = ok
+            else:
+                n = hg.probabilities(head, (), out)
+                ok &= ~hg.near_discrete(n)
+                srt = np.sort(n, axis=1)
+                gap = (1.0 - srt[:, -1]) / hg.EPS32
+                want = ok & [gap < 0.5, (srt[:, -2] / hg.EPS32 > 0.05) & (srt[:, -2] / hg.EPS32 < 0.45) & (gap < 0.5),
+                             (srt[:, 0] > hg.EPS32) & (gap > 2.0), ok][i % 4]
+            k = int(np.argmax(want)) if want.any() else int(np.argmax(ok))
+            assert ok[k], "no candidate state without a kink and away from the gates"
+            self.hidden["actor_hidden"][last[i]], self.hidden["actor_cell"][last[i]] = cand["h"][k], cand["c"][k]
+            outs[i] = out[k]
+        if head == "gaussian":
+            ls = spans["log_std"][0]
+            self.raw_actions[last] = hg.plant_gaussian(outs, self.params[ls:ls + self.actor.out_dim], self.consts.min_std, rng, tanh_dim)
+        else:
+            self.raw_actions[last] = hg.plant_discrete(head, (), outs, hg.probabilities(head, (), outs), rng).reshape(-1, 1)
+            self.forced = np.arange(len(chosen))[1::4]
 
     def _steer_second(self, rng):
         """Mini-batch 1 = perm[B : B + L], L = min(items - B, B): three items of mini-batch 0 again, then unused ones;

@@ -42,6 +42,8 @@ import torch
 from oracle import k12_oracle as ko
 from oracle import mat_update_oracle as mu
 
+import head_gates as hg
+
 VN = (0.3, 0.25, 5000.0)
 STEP0 = 6
 LR = float(np.float32(3e-4))
@@ -51,11 +53,14 @@ KEY_BIAS = {f"{a}.key_net.bias": f"{a}.query_net.bias" for a in ATTENTIONS}
 ROW_MODES = ("map", "order", "offset", "tail")
 
 
-def case(A, O, NA, B, seed, norm_values=True, n_ranks=1, norm_adv=True, huber=True, kl=0.0, ent=0.01, rows="map", second=False):
+def case(A, O, NA, B, seed, norm_values=True, n_ranks=1, norm_adv=True, huber=True, kl=0.0, ent=0.01, rows="map", second=False,
+         saturate=0.0):
     """rows: how the GPU test addresses the mini-batch (perm o row_map on buffer rows; per-epoch tables from cursor 1; the
-    same by mb_offset 1; a tail mini-batch behind two full ones).  second: mini-batch 1 is launched right after."""
+    same by mb_offset 1; a tail mini-batch behind two full ones).  second: mini-batch 1 is launched right after.
+    saturate: the head's last linear multiplied by it (tests/helpers/mat_step_cases.py) and actions planted so that the
+    clamp's gradient gate is closed in part of the tokens (Steering._gates, tests/helpers/head_gates.py)."""
     return dict(A=A, O=O, NA=NA, B=B, seed=seed, norm_values=norm_values, n_ranks=n_ranks, norm_adv=norm_adv, huber=huber,
-                kl=kl, ent=ent, rows=rows, second=second)
+                kl=kl, ent=ent, rows=rows, second=second, saturate=saturate)
 
 
 def _drawn():
@@ -84,6 +89,13 @@ CASES = {
     "tiles64_16_7_4_64": case(16, 7, 4, 64, 11, rows="offset"),                      # the last count in one trip of the wgrad tile
     "tiles65_16_7_4_65": case(16, 7, 4, 65, 12, rows="tail", n_ranks=2),             # the first that takes a second trip
     **_drawn(),
+}
+
+
+# tests/test_gpu_head_gates.py: K15's own head with the clamp's gate closed
+GATES_CASES = {
+    "k15_3_18_8_11": case(3, 18, 8, 11, 961, saturate=8.0),
+    "k15_16_7_5_3": case(16, 7, 5, 3, 942, saturate=8.0, rows="order"),
 }
 
 
@@ -133,8 +145,11 @@ class Steering:
             self.pad[off:off + int(np.prod(shape))] = False
         rng = np.random.default_rng(c["seed"])
         self.params = draw_params(A, O, NA, rng)
+        self.gated = None
         self.consts = ko.Consts(c["norm_adv"], c["norm_values"], c["huber"], 10.0, 0.2, c["ent"], c["kl"], 0.01)
         self.vn = VN if c["norm_values"] else (0.0, 1.0, 1e-4)
+        if c["saturate"]:
+            self._gates()
         self.mb = self.draw(B, rng, self.params, self.vn)
         self.records = self.records_of(self.mb)
         self.r64 = self.reference(torch.float64)
@@ -160,6 +175,8 @@ class Steering:
         n = B * A
         obs = f32(rng.normal(0, 1, (B, A, O)))
         act = rng.integers(0, NA, (B, A)).astype(np.int64)
+        if self.gated is not None:
+            obs, act = self.gated
         adv = f32(rng.normal(0.2, 1.0, n))
         sd = 0.5 if c["norm_values"] else 1.0
         rtg = 0.3 + sd * np.clip(rng.normal(0, 1, n), -3.0, 3.0)
@@ -172,7 +189,77 @@ class Steering:
         logp = mu.minibatch(params, A, O, NA, mb, self.consts, vn, self.records_of(mb))["logp"].reshape(-1)
         old = ko.steered_old_log_probs(logp, rng, self.consts.surr_clip)
         old[:k] = f32(logp[:k] - np.log([r for r, _ in FORCED[:k]]))
+        if self.gated is not None:             # tokens whose closed gate would carry a visible surrogate gradient: inside the clip
+            chosen = np.take_along_axis(self.probs_of(params, obs, act), act[..., None], -1).reshape(-1) / hg.EPS32
+            self.visible = np.array([i for i in np.flatnonzero((chosen > 0.01) & (chosen < 0.9)) if i >= k], dtype=np.int64)
+            old, adv = hg.force_surrogate(old, adv, logp, self.visible)
+            mb = mb._replace(advantages=adv.reshape(B, A))
         return mb._replace(old_log_probs=old.reshape(B, A))
+
+    def probs_of(self, params, obs, act):
+        """float64 renormalised probabilities [B, A, NA] of the tokens under the given actions."""
+        A, O, NA, _ = self.shape
+        net = mu.network(A, O, NA, params)
+        with torch.no_grad():
+            _, p = net(torch.as_tensor(obs, dtype=torch.float64), mu.action_block(act, A, NA))
+        return (p / p.sum(-1, keepdim=True)).numpy()
+
+    def logits_of(self, params, obs, act):
+        """float64 outputs of the head's last linear [B, A, NA]."""
+        A, O, NA, _ = self.shape
+        net = mu.network(A, O, NA, params)
+        got = []
+        hook = net.actor.head[3].register_forward_hook(lambda m, i, o: got.append(o.detach().numpy()))
+        with torch.no_grad():
+            net(torch.as_tensor(obs, dtype=torch.float64), mu.action_block(act, A, NA))
+        hook.remove()
+        return got[0]
+
+    def _gates(self):
+        """The gates steering on the B A tokens.  A LayerNorm stands before everything, so a token's confidence cannot be
+        tuned by scaling its observation, and one factor on the head's last linear leaves every token equally confident.
+        Its rows are therefore scaled apart: classes 1 .. to a root mean square of saturate / 4 over the tokens (among
+        themselves in range), class 0 to a standard deviation of 2 saturate against them, its bias set so that it is centred on them -- far above them in some tokens
+        (kind d), far below in others (b, c), among them in the rest (a).  Observations come from generator
+        (seed, 500 + round) and actions are planted agent by agent (an agent's probabilities depend on the agents before
+        it) by hg's row rule, until the tokens hold every kind, none is near a gate, and two chosen classes lie at
+        0.01 .. 0.9 eps32 (their surrogate gradient is what an open gate would let through)."""
+        c, (A, O, NA, B) = self.c, self.shape
+        spans = {name: (off, shape) for _, name, off, shape in self.table}
+        (wo, (_, width)), (bo, _) = spans["actor.head.3.weight"], spans["actor.head.3.bias"]
+        g = np.random.default_rng((c["seed"], 499))
+        z = self.logits_of(self.params, np.asarray(g.normal(0, 1, (64, A, O)), dtype=np.float32), g.integers(0, NA, (64, A)))
+        z = z.reshape(-1, NA)
+        rest = z[:, 1:].mean(axis=1)
+        f = np.full(NA, 0.25 * c["saturate"] / np.sqrt(((z[:, 1:] - rest[:, None]) ** 2).mean()))
+        f[0] = 2.0 * c["saturate"] / (z[:, 0] - rest).std()
+        for k in range(NA):
+            self.params[wo + k * width:wo + (k + 1) * width] *= f[k]
+            self.params[bo + k] *= f[k]
+        self.params[bo] -= (f[0] * z[:, 0] - f[1] * rest).mean()          # class 0 centred on the others over the tokens
+        self.params = self.params.astype(np.float32).astype(np.float64)
+        for r in range(200):
+            g = np.random.default_rng((c["seed"], 500 + r))
+            obs = np.asarray(g.normal(0, 1, (B, A, O)), dtype=np.float32)
+            act = np.zeros((B, A), dtype=np.int64)
+            for i in range(A):
+                n = self.probs_of(self.params, obs, act)
+                for b in range(B):
+                    act[b, i] = hg._plant_classes(n[b, i], (b * A + i) % 4, g)
+            n = self.probs_of(self.params, obs, act).reshape(-1, NA)
+            kinds = hg.counts(hg.census("categorical", (), dict(n=n), act.reshape(-1)))[1]
+            chosen = n[np.arange(B * A), act.reshape(-1)] / hg.EPS32
+            if not hg.near_discrete(n).any() and all(kinds.get(k, 0) >= hg.MIN_ENTRIES for k in "abcd") \
+                    and ((chosen > 0.01) & (chosen < 0.9))[4:].sum() >= 2:
+                self.gated, self.rounds = (obs, act), r
+                return
+        raise AssertionError("no draw of the observations holds every kind of token away from the gates")
+
+    def gates_failures(self):
+        """hg.census_failures of the steered tokens (rows = tokens) on the two references."""
+        NA = self.shape[2]
+        as_args = lambda r: dict(gate_args=dict(n=r["probs"].reshape(-1, NA)))
+        return hg.census_failures("categorical", (), NA, as_args(self.r64), as_args(self.r32), self.mb.raw_actions.reshape(-1))
 
     def records_of(self, mb):
         """The mini-batch's (n, mean, M2) per rank."""

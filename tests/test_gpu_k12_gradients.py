@@ -18,6 +18,7 @@ the CPU) where float32 itself cannot do better (ko.deviations).
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -25,6 +26,9 @@ import torch
 import torch.nn as nn
 
 from oracle import k12_oracle as ko
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import head_gates as hg  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -49,9 +53,11 @@ def _report():
 
 
 def case(O=8, ha=64, hc=None, depth=2, B=64, head=("categorical", 3), act="relu", wide_critic=False, norm_adv=True,
-         norm_values=True, huber=True, kl=0.0, ent=0.01, seed=0):
+         norm_values=True, huber=True, kl=0.0, ent=0.01, seed=0, gates=None):
+    """gates: the head's gradient gates are closed in part of the mini-batch (tests/helpers/head_gates.py: the actor's last
+    layer / log_std steered in the policy's bucket, observations and actions planted, the census asserted)."""
     return dict(O=O, ha=ha, hc=hc or ha, depth=depth, B=B, head=head, act=act, wide_critic=wide_critic,
-                norm_adv=norm_adv, norm_values=norm_values, huber=huber, kl=kl, ent=ent, seed=seed)
+                norm_adv=norm_adv, norm_values=norm_values, huber=huber, kl=kl, ent=ent, seed=seed, gates=gates)
 
 
 CASES = {
@@ -145,22 +151,33 @@ class Steered:
         self.na = upd.actor_desc.size
         assert size == pol.policy_params.numel()
         self.params = pol.policy_params.detach().double().cpu().numpy()
-        # ---- observations: N(0, 1), kinked rows drawn again
-        obs = rng.normal(0, 1, (B, self.actor.in_dim)).astype(np.float32)
-        cobs = rng.normal(0, 1, (B, self.critic.in_dim)).astype(np.float32)
-        for r in range(50):
-            ka = ko.kinked_rows(self.actor, self.params[:self.na], obs)
-            kc = ko.kinked_rows(self.critic, self.params[self.na:], cobs)
-            if not (ka.any() or kc.any()):
-                break
-            g = np.random.default_rng((seed, r))
-            obs[ka] = g.normal(0, 1, (int(ka.sum()), obs.shape[1]))
-            cobs[kc] = g.normal(0, 1, (int(kc.sum()), cobs.shape[1]))
+        min_std = float(getattr(pol.actor.distribution, "min_std", 0.01))
+        gated = None
+        if c.get("gates"):
+            # ---- the gates steering: the bucket's last actor layer / log_std, observations without kinks, planted actions
+            gated = hg.steer(self.params, self.actor, self.critic, head, self.slices, B, rng, seed, min_std=min_std)
+            self.params = gated.params
+            pol.policy_params.copy_(torch.from_numpy(gated.params.astype(np.float32)))
+            obs, cobs = gated.inputs["obs"], gated.inputs["cobs"]
         else:
-            pytest.fail("kinked rows left after 50 redraws")
+            # ---- observations: N(0, 1), kinked rows drawn again
+            obs = rng.normal(0, 1, (B, self.actor.in_dim)).astype(np.float32)
+            cobs = rng.normal(0, 1, (B, self.critic.in_dim)).astype(np.float32)
+            for r in range(50):
+                ka = ko.kinked_rows(self.actor, self.params[:self.na], obs)
+                kc = ko.kinked_rows(self.critic, self.params[self.na:], cobs)
+                if not (ka.any() or kc.any()):
+                    break
+                g = np.random.default_rng((seed, r))
+                obs[ka] = g.normal(0, 1, (int(ka.sum()), obs.shape[1]))
+                cobs[kc] = g.normal(0, 1, (int(kc.sum()), cobs.shape[1]))
+            else:
+                pytest.fail("kinked rows left after 50 redraws")
         self._put("observations", obs)
         self._put("critic_observations", cobs)
-        if head == "gaussian":
+        if gated is not None:
+            self._put("raw_actions", gated.actions)
+        elif head == "gaussian":
             acts = rng.normal(0, 1.5, (B, self.actor.out_dim)).astype(np.float32)
             k = max(1, B // 8)
             acts[:k] = np.sign(acts[:k]) * rng.uniform(3.8, 4.2, acts[:k].shape)
@@ -179,13 +196,21 @@ class Steered:
         self._put("advantages", rng.normal(0.2, 1.0, B).astype(np.float32))
         self.consts = ko.Consts(c["norm_adv"], c["norm_values"], c["huber"], 10.0, float(pol.surr_clip),
                                 float(pol.entropy_weight()), float(pol.kl_loss_weight),
-                                float(getattr(pol.actor.distribution, "min_std", 0.01)))
+                                min_std)
         mb = self._mb(raw, np.zeros(B, np.float32))
         logp = ko.minibatch(self.params, self.actor, self.critic, head, self.slices, mb, self.consts, self.vn)["logp"]
-        self._put("log_probs", ko.steered_old_log_probs(logp, rng, self.consts.surr_clip))
+        old = ko.steered_old_log_probs(logp, rng, self.consts.surr_clip)
+        if gated is not None:                  # the tuned rows' surrogate inside the clip
+            old, adv = hg.force_surrogate(old, mb.advantages, logp, gated.forced)
+            self._put("advantages", adv)
+        self._put("log_probs", old)
         self.mb = self._mb(raw, self._get("log_probs").reshape(-1))
         self.r64 = self._ref(torch.float64)
         self.r32 = self._ref(torch.float32)
+        if gated is not None:
+            bad = hg.census_failures(head, self.slices, self.actor.out_dim, self.r64, self.r32, raw, min_std)
+            assert not bad, "gates steering: " + "; ".join(bad)
+            self.census = hg.describe(head, self.slices, self.r64, raw, min_std)
         if c["huber"]:
             d = np.abs(self.r64["values"] - self.r64["rtg"])
             assert (d > 10.0).any() and np.abs(d - 10.0).min() > 1e-3, "Huber branch steering"

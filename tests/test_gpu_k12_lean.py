@@ -99,7 +99,11 @@ def _setup(c):
 
 @pytest.mark.parametrize("name", sorted(LEAN))
 def test_lean_kernel(name):
-    c = LEAN[name]
+    run_lean(name, LEAN[name])
+
+
+def run_lean(name, c):
+    """Checks (i) .. (v) of the module docstring on one lean case -> the worst deviation / bound against float64."""
     s, upd, identity = _setup(c)
     B = c["B"]
     lean = [_launch(s, upd, B, None, 1) for _ in range(5)]              # (i) inside: the export says "lean"
@@ -117,11 +121,13 @@ def test_lean_kernel(name):
     rows = s.rows.cpu().numpy()
     vals = values.reshape(-1)[rows]
     one = lambda what, n: [("", what, 0, (n,))]
+    worst_of_all = (0.0, "")
     for what, got, key, tab in (("gradient", grads, "grads", s.tables), ("totals", totals, "totals", g12.TOTALS),
                                 ("values", vals, "values", one("values", B))):
         w64, w32 = np.asarray(s.r64[key]).reshape(-1), np.asarray(s.r32[key]).reshape(-1)
         worst = max(ko.deviations(got, w64, w32, tab), key=lambda d: d[1])
         print(f"{name}: {what}: worst {worst[1]:.3f} x bound at {worst[0]}")
+        worst_of_all = max(worst_of_all, (worst[1], f"{what}: {worst[0]}"))
         bad = ko.failures(got, w64, w32, tab)
         assert not bad, f"{name} / {what}: " + "; ".join(bad[:6])
     # (v) the other rows' values
@@ -129,6 +135,7 @@ def test_lean_kernel(name):
     other[rows] = False
     assert np.array_equal(values.reshape(-1)[other], s.values0.double().cpu().numpy().reshape(-1)[other]), \
         f"{name}: values outside the mini-batch's rows changed"
+    return worst_of_all
 
 
 @pytest.mark.parametrize("name", sorted(GENERAL))

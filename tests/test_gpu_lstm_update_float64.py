@@ -183,6 +183,8 @@ class Steered:
             assert (d > 10.0).any() and np.abs(d - 10.0).min() > 1e-3, "Huber branch steering"
         if S > 1 and B >= 5 * s.need:
             assert (s.kinds[s.chosen].sum(0) >= s.need).all(), "every kind of terminal window"
+        if c["gates"]:
+            assert s.gates_failures == [], "gates steering: " + "; ".join(s.gates_failures)
 
     def _flat(self, t):
         return t.view((self.s.N,) + tuple(t.shape[2:]))

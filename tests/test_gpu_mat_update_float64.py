@@ -136,7 +136,7 @@ def _report():
 @functools.lru_cache(maxsize=None)
 def steering(name):
     """The case's tables and its float64 / float32 references: built once per case, not once per form."""
-    return cases.Steering(cases.CASES[name])
+    return cases.Steering({**cases.CASES, **cases.GATES_CASES}[name])
 
 
 def _note(key, what, devs):
@@ -195,6 +195,8 @@ class Device:
         self.name, self.s = name, steering(name)
         s, c = self.s, self.s.c
         A, O, NA, B = s.shape
+        if c["saturate"]:
+            assert s.gates_failures() == [], "gates steering: " + "; ".join(s.gates_failures())
         self.lib, self.K, self._lib = _lib.load(), K, _lib
         dev = self.dev = torch.device("cuda", 0)
         n_wg = (B + 16 // A - 1) // (16 // A)

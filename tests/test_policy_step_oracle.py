@@ -46,7 +46,7 @@ def _words(seed, counter, stream):
 @pytest.mark.parametrize("name", list(cases.CASES))
 def test_forced_launch_is_the_k12_oracle(name):
     s = cases.steering(name)
-    f64 = s.reference("forced", np.float64, eps=EPS64)
+    f64 = s.reference("forced", np.float64)              # (the clamp at eps32, as the K12 oracle holds it in every dtype)
     T = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float64)
     with torch.no_grad():
         out = ko._module(cases.ko_net(s.actor), s.actor.flat().astype(np.float64), torch.float64)[0](T(s.obs))
@@ -64,14 +64,14 @@ def test_forced_launch_is_the_k12_oracle(name):
     rows = np.ones(s.c["E"], bool)
     mine = f64["logp"]
     if s.head == CAT:
-        # the clamp at eps32 is the kernel's alone: the oracle's is log q wherever q >= eps64, and the restatement's
-        # clamp moves exactly the classes outside [eps32, 1 - eps32] -- to log(eps32) / log(1 - eps32)
+        # the K12 oracle clamps at eps32 in every dtype, as the kernel and this restatement do: every row compares below, the
+        # clamped ones included.  The restatement's clamp moves exactly the classes outside [eps32, 1 - eps32] -- to
+        # log(eps32) / log(1 - eps32)
         q = f64["probs"][np.arange(s.c["E"]), f64["action"]] / f64["probs"].sum(1)
-        rows = q >= EPS64
-        mine = s.reference("forced", np.float64, logp_no_clamp=True)["logp"]
+        unclamped = s.reference("forced", np.float64, logp_no_clamp=True)["logp"]
         inside = (q >= EPS32) & (q <= 1.0 - EPS32)
-        assert rows.sum() >= max(1, s.c["E"] // 2) and inside.any()
-        np.testing.assert_array_equal(f64["logp"][inside], mine[inside])
+        assert (q >= EPS64).sum() >= max(1, s.c["E"] // 2) and inside.any()
+        np.testing.assert_array_equal(f64["logp"][inside], unclamped[inside])
         np.testing.assert_allclose(f64["logp"][q < EPS32], np.log(EPS32), rtol=1e-12)
         np.testing.assert_allclose(f64["logp"][q > 1.0 - EPS32], np.log1p(-EPS32), rtol=1e-12)
     np.testing.assert_allclose(mine[rows], logp.numpy().reshape(-1)[rows], rtol=1e-12, atol=1e-12)
