@@ -490,20 +490,23 @@ extern "C" int ppoaf_ppo_update_adam(const ppoaf_ppo_update_args_t* args, int co
 }
 
 // The N > 1 fallback chain in one call: fwd_bwd -> reduce -> RCCL sum all-reduce of the gradient bucket -> norms +
-// Adam, for n consecutive mini-batches.  What `fused_update._eager_multi_rank` does from Python (4 launches + one
+// Adam, for n consecutive mini-batches.  What `FusedPolicyUpdate._one` does from Python (4 launches + one
 // torch.distributed call per mini-batch: ~42 us of host time, more than the kernels take) issued from C: the host cost
-// per mini-batch drops below the GPU's.
+// per mini-batch drops below the GPU's.  Args with a split workspace (the wide pair, which has no slab form) run the
+// split-wgrad chain instead: ppoaf_ppo_update_wgrad completes the bucket in place of the slab reduce; the norms it
+// leaves are this rank's alone and are not read -- Adam's norm pass (compute_norms = 1) follows the all-reduce as ever.
 extern "C" int ppoaf_ppo_update_chain_allreduce(const ppoaf_ppo_update_args_t* args, ppoaf_comm_t* comm, int64_t n_minibatches,
                                                 ppoaf_stream_t stream) {
     PPOAF_REQUIRE(args && comm, "ppo_update_chain_allreduce: null argument");
     PPOAF_REQUIRE(n_minibatches >= 1 && n_minibatches <= (1 << 20), "ppo_update_chain_allreduce: n_minibatches=%ld", (long)n_minibatches);
     PPOAF_REQUIRE(args->mb_offset == 0, "ppo_update_chain_allreduce: mb_offset must be 0");
     ppoaf_ppo_update_args_t a = copy_update_args(args);
+    const bool split = a.split_workspace != nullptr;
     for (int64_t j = 0; j < n_minibatches; ++j) {
         a.mb_offset = j;
         a.cursor_advance = (j == n_minibatches - 1) ? n_minibatches : 0;
         int rc = ppoaf_ppo_update_fwd_bwd(&a, stream);
-        if (rc == PPOAF_OK) rc = ppoaf_ppo_update_reduce(&a, 0, stream);
+        if (rc == PPOAF_OK) rc = split ? ppoaf_ppo_update_wgrad(&a, stream) : ppoaf_ppo_update_reduce(&a, 0, stream);
         if (rc == PPOAF_OK) rc = ppoaf_allreduce_sum_f32(comm, a.grads, a.bucket_total, stream);
         if (rc == PPOAF_OK) rc = ppoaf_ppo_update_adam(&a, 1, stream);
         if (rc != PPOAF_OK) return rc;
@@ -520,8 +523,9 @@ extern "C" int ppoaf_ppo_update_adam_exchanged(const ppoaf_ppo_update_args_t* ar
     const long n4 = u.bucket_total >> 2;
     PPOAF_REQUIRE(xchg->dev.n4 == n4, "ppo_update_adam_exchanged: exchange made for %ld float4, bucket has %ld",
                   xchg->dev.n4, n4);
-    // one pair of norm partials per exchange group: the workgroups of ppoaf_ppo_update_reduce_exchange, or (split-wgrad
-    // chain) of ppoaf_ppo_update_wgrad_exchange
+    // one pair of norm partials per exchange group: the workgroups of ppoaf_ppo_update_reduce_exchange.  (With a split
+    // workspace the count is the wgrad launch's workgroups; no launch of the split-wgrad chain fills the exchange's partials
+    // today -- its N > 1 forms are ppoaf_ppo_update_wgrad_adam_exchange, or wgrad -> K17 -> ppoaf_ppo_update_adam(2).)
     const unsigned groups = u.split ? (unsigned)split_wgrad_blocks(u) : (unsigned)((n4 + kRedThreads - 1) / kRedThreads);
     PPOAF_REQUIRE(groups <= (unsigned)kXchgMaxGrid, "ppo_update_adam_exchanged: bucket too large for the fused exchange");
     hipLaunchKernelGGL(ppo_update_adam_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u,

@@ -732,6 +732,8 @@ WIDTH_PAIRS = ((32, 32), (64, 64), (128, 128), (256, 256), (128, 256), (64, 128)
 # With the opt-in `PPOPolicy.fused_wide_shapes` (which implies the other; PPOAF_SPLIT_WIDE_SHAPES) in_dim <= 512, as far as
 # each row-tile body's LDS goes, on panels of stride 256 or 512, and batch sizes <= 1024: the weight-gradient launch then
 # runs a mini-batch of more than 32 chunks of 16 rows in passes of 32 (csrc/ppo_update_split.hip).
+# With the opt-in `PPOPolicy.fused_wide_ranks` N > 1 ranks: the same three launches with the gradient all-reduce between wgrad
+# and Adam (Adam mode 1; from C: ppoaf_ppo_update_chain_allreduce's split form).  No K17 route: FusedPolicyUpdate.__init__.
 WIDE_WIDTH_PAIRS = ((256, 512),)
 
 
@@ -761,6 +763,12 @@ WIDE_HEAD_MAX = 24
 def wide_heads(pol):
     """The policy's wide pair may take an actor head of 9 .. WIDE_HEAD_MAX outputs (PPOPolicy.fused_wide_heads, set by hand)."""
     return bool(getattr(pol, "fused_wide_heads", False))
+
+
+def wide_ranks(pol):
+    """The policy's wide pair may train on N > 1 ranks (PPOPolicy.fused_wide_ranks, set by hand): the split-wgrad chain with
+    the gradient all-reduce between its wgrad and Adam launches."""
+    return bool(getattr(pol, "fused_wide_ranks", False))
 
 
 def actor_out_limit(pol, head):
@@ -839,7 +847,7 @@ class FusedPolicyUpdate(FusedEpoch):
                     return f"{pair}: batch size {batch_size} > 512 (the split-wgrad chain covers batch sizes <= 512)"
             if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
                 return f"{pair}: PPOAF_SPLIT_WGRAD=0, and the wide pair has no slab form"
-            if mpi_utils.get_num_procs() > 1:
+            if mpi_utils.get_num_procs() > 1 and not wide_ranks(pol):
                 return f"{pair}: single rank only for now ({mpi_utils.get_num_procs()} ranks)"
         # what the library itself refuses (depth, in_dim, the row-tile body's LDS): host-only, nothing is launched
         q = _lib.PpoUpdateArgs()
@@ -880,6 +888,24 @@ class FusedPolicyUpdate(FusedEpoch):
             else:
                 pol.fused_wide_heads = own     # (a False set by hand on the instance, under a class attribute of True)
 
+    @staticmethod
+    def wide_ranks_would_take(pol, batch_size):
+        """True for a policy that is refused only because `fused_wide_ranks` is off: a wide pair on N > 1 ranks -- under
+        "auto", together with `fused_wide_critic` (what `verbose` adds to the refusal)."""
+        if wide_ranks(pol) or pol.using_lstm or pol.agent_grouping or mpi_utils.get_num_procs() == 1:
+            return False
+        missing = object()
+        was, own = pol.fused_wide_critic, vars(pol).get("fused_wide_ranks", missing)
+        pol.fused_wide_ranks = pol.fused_wide_critic = True
+        try:
+            return FusedPolicyUpdate.unsupported_reason(pol, batch_size) == ""
+        finally:
+            pol.fused_wide_critic = was
+            if own is missing:
+                del pol.fused_wide_ranks       # (the instance had none: the class attribute is read again)
+            else:
+                pol.fused_wide_ranks = own     # (a False set by hand on the instance, under a class attribute of True)
+
     def __init__(self, ppo, policy_id):
         super().__init__(ppo, policy_id)
         pol = self.pol
@@ -898,7 +924,13 @@ class FusedPolicyUpdate(FusedEpoch):
         _init_normaliser(self)
         self.loss_partials = torch.zeros(2, self.n_wg, 8, dtype=torch.float32, device=dev)
         self.rows = None
-        self._open_exchange(total)
+        if self.wide and self.world > 1:
+            # No K17 route for a wide pair: with a K17 launch between its wgrad and Adam launches, ranks that shared one GPU
+            # ran K17's bounded wait out; the cause is not known.  The all-reduce route runs whatever
+            # PPOAF_GRAD_EXCHANGE asks for.  (One rank rehearsing the N > 1 path waits for nobody and keeps its exchange.)
+            self.xchg, self.xchg_reason = None, "a wide pair's gradients go through the all-reduce: no K17 route for it"
+        else:
+            self._open_exchange(total)
         # the fused tail launch of the split-wgrad chain (csrc/ppo_update_tail.hip) carries the exchange as a phase of
         # every weight-gradient job (one exchange group per workgroup, job-major tiles in the slots: an object of its own
         # again; at most 512 workgroups = the flag words of one exchange object): two launches per mini-batch on N > 1 ranks too.
@@ -916,7 +948,9 @@ class FusedPolicyUpdate(FusedEpoch):
 
     def drop_peer_exchange(self, why):
         super().drop_peer_exchange(why)
-        self.split, self.split_reason = self._split_wanted()     # the all-reduce loops run the slab chain
+        # the all-reduce loops run the slab chain -- but for a wide pair, which has none: its split-wgrad chain goes on with
+        # the all-reduce between wgrad and Adam (_split_wanted)
+        self.split, self.split_reason = self._split_wanted()
         self._split_space = None
 
     def _split_blocks(self):
@@ -966,8 +1000,19 @@ class FusedPolicyUpdate(FusedEpoch):
             return line + f"slab chain ({self.split_reason})"
         tail = self.tail_reason()
         line += "split-wgrad chain, " + ("fused tail" if tail == "" else f"wgrad and Adam launches ({tail})")
+        if self.wide and self.multi and (self.world > 1 or wide_ranks(self.pol)):
+            # (one rank rehearsing the N > 1 path without the opt-in: the line it always had)
+            line += "; " + self.exchange_route()
         return line + (f"; layer-0 panel stride {panel_stride(a.in_dim)} (actor) / {panel_stride(c.in_dim)} (critic) floats"
                        f"{', fused_wide_shapes' if self.wide_bits & _lib.SPLIT_WIDE_SHAPES else ', fused_wide_inputs' if self.wide_bits else ''}")
+
+    def exchange_route(self):
+        """N > 1, a wide pair: the route its mini-batch takes between the wgrad and the Adam launch (description())."""
+        if self.xchg is not None:        # (only one rank rehearsing the N > 1 path holds an exchange: __init__)
+            return "N > 1 rehearsed on one rank: fwd_bwd, wgrad, a K17 launch with no peer, Adam on its clip norms"
+        # (which loop issues it is settled at the first epoch, by a vote of the ranks: rccl_comm -- not asked here)
+        return (f"N > 1 ({self.world} ranks): all-reduce route -- fwd_bwd, wgrad, all-reduce, Adam with its norm pass: four "
+                f"launches and a collective, eager ({self.xchg_reason})")
 
     def gradient_only(self, args, timing_events=(None, None)):
         """fwd_bwd + the launch that completes the gradient bucket (wgrad / slab reduce) of ONE mini-batch, no optimiser step:
@@ -1177,7 +1222,7 @@ class FusedPolicyUpdate(FusedEpoch):
             self.xchg.allreduce(g, g, split_floats=self.actor_desc.size, norm_scale=args.grad_scale,
                                 norm_out=self.pol.policy_norm_scratch, stream=st)
             rc = lib.ppoaf_ppo_update_adam(ref, 2, st)
-        elif rc == 0 and args.split_workspace:
+        elif rc == 0 and args.split_workspace and single:
             rc = lib.ppoaf_ppo_update_adam(ref, 3, st)       # (the wgrad launch left both clip norms)
         else:
             if rc == 0 and not single:

@@ -118,6 +118,12 @@ class PPOPolicy:
     # 8"); a policy with out_dim <= 8 computes bitwise the same, flag on or off.  MultiDiscrete / MultiBinary heads, LSTM and
     # MAT policies, ICMs and every other width pair keep 8.
     fused_wide_heads = False
+    # Opt-in: the wide pair on N > 1 ranks (DD-PPO), at every shape it takes on one rank with the flags above: the three-launch
+    # split-wgrad chain with the gradient all-reduce between its wgrad and Adam launches (Adam then runs its own norm pass); from
+    # C where the library holds an RCCL communicator (ppoaf_ppo_update_chain_allreduce).  No K17 route yet.  Set by hand, on the class or on the policy,
+    # before the first rollout -- no update_mode sets it.  False: on N > 1 ranks the pair is refused with today's message
+    # ("single rank only for now"); on one rank the flag changes nothing.
+    fused_wide_ranks = False
     # Opt-in: an ICM over Discrete / Box actions of 9 .. 24 classes or dimensions (Discrete(18), Box(17)) on K14's shapes chain
     # and its identity form, update epoch and rollout-time reward: the 32-column action form, which the library runs when
     # the topology carries PPOAF_ICM_WIDE_ACTIONS; a one-width ICM (128/128/128) with such actions goes to the shapes chain too.
@@ -777,7 +783,7 @@ class PPOPolicy:
             return "LSTM policies are not K19's: K21 or forward_logits (see lstm_step_unsupported_reason)"
         # (asked once per evaluation step: the answer is kept for as long as what it depends on stays)
         key = (self.policy_params.data_ptr(), bool(self.fused_action_heads), bool(self.fused_wide_critic),
-               bool(self.fused_wide_inputs), bool(self.fused_wide_shapes), bool(self.fused_wide_heads))
+               bool(self.fused_wide_inputs), bool(self.fused_wide_shapes), bool(self.fused_wide_heads), bool(self.fused_wide_ranks))
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
             self._infer_reason = (key, self.fused_step_unsupported_reason())
         return self._infer_reason[1]

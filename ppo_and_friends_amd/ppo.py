@@ -547,6 +547,8 @@ class PPO:
                 if why:
                     if verbose and FusedPolicyUpdate.wide_heads_would_take(pol, self.batch_size):
                         why += "; PPOPolicy.fused_wide_heads = True would take it on the fused kernels"
+                    elif verbose and FusedPolicyUpdate.wide_ranks_would_take(pol, self.batch_size):
+                        why += "; PPOPolicy.fused_wide_ranks = True would take it on the fused kernels"
                     raise NotImplementedError(f"update_mode='fused' but policy {policy_id}: {why}")
         # ppo.py:663-678: freeze cycling over policy groups (utils/schedulers.py:FreezeCyclingScheduler)
         from .utils.schedulers import FreezeCyclingScheduler
@@ -1463,6 +1465,8 @@ class PPO:
                         hint = "; update_mode='fused' would take it on the fused kernels"
                     elif driver is FusedPolicyUpdate and FusedPolicyUpdate.wide_heads_would_take(self.policies[policy_id], B):
                         hint = "; update_mode='fused' with PPOPolicy.fused_wide_heads = True would take it on the fused kernels"
+                    elif driver is FusedPolicyUpdate and FusedPolicyUpdate.wide_ranks_would_take(self.policies[policy_id], B):
+                        hint = "; update_mode='fused' with PPOPolicy.fused_wide_ranks = True would take it on the fused kernels"
                     rank_print(f"policy {policy_id}: torch update path ({why}){hint}")
                 self._fused[key] = None
             else:

@@ -111,6 +111,8 @@ def main():
                     help="PPOPolicy.fused_wide_shapes = True (a wide pair above 128 inputs or above 512 rows per mini-batch)")
     ap.add_argument("--wide-heads", action="store_true",
                     help="PPOPolicy.fused_wide_heads = True (a wide pair's actor with 9 .. 24 outputs, Discrete or Box)")
+    ap.add_argument("--wide-ranks", action="store_true",
+                    help="PPOPolicy.fused_wide_ranks = True (a wide pair on N > 1 ranks, under a launcher: profiles/wide_ranks.txt)")
     ap.add_argument("--action", default="discrete:4", help="with --obs-dim: discrete:N or box:N (default discrete:4)")
     ap.add_argument("--activation", choices=sorted(ACTIVATIONS), default="relu")
     ap.add_argument("--batch", type=int, default=BATCH, help="mini-batch size")
@@ -127,6 +129,12 @@ def main():
     if args.wide_heads:
         from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
         PPOPolicy.fused_wide_heads = True
+    if args.wide_ranks:
+        from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
+        PPOPolicy.fused_wide_ranks = True
+    # under a launcher, or PPOAF_REHEARSE_MULTI_RANK=1 (one rank on the N > 1 path): the process group (no-op otherwise)
+    from ppo_and_friends_amd.utils import mpi_utils
+    mpi_utils.init_process_group_from_env()
     legs, pair = LEGS, "64x256"
     if args.widths:
         pair = f"{args.widths[0]}x{args.widths[1]}"
@@ -147,7 +155,8 @@ def main():
         step_on = ppo.update_mode != "torch" and pol.fused_step_unsupported_reason() == ""
         result[f"{k}_rollout_path"] = "K6+K7" if step_on else "torch"
         result[f"{k}_update_path"] = "torch" if fused is None else \
-            "K12" + (", row pairs" if fused.pairs_reason() == "" else "") + (", fused tail" if fused.tail_reason() == "" else "")
+            "K12" + (", row pairs" if fused.pairs_reason() == "" else "") + (", fused tail" if fused.tail_reason() == "" else "") \
+            + (", N > 1 path" if fused.multi else "")
         for _ in range(args.warmup):
             rollout_and_epoch(ppo)
     times = {k: [] for k in ppos}
