@@ -38,11 +38,47 @@ def _activation_code(act):
     return None
 
 
-def action_head(pol):
+class FusedOptIns(NamedTuple):
+    """
+    The opt-ins of a policy to the fused path, as one immutable value: field `x` is the policy's attribute `fused_x`
+    (PPOPolicy's class attributes and their comments say what each switches on; PPO sets `fused_action_heads` and
+    `fused_wide_critic` under update_mode="fused", the others are set by hand).  Every scope question takes one, so a
+    hypothetical ("would this policy be taken with fused_wide_heads on?") is `opt._replace(...)`, never a write to the policy.
+    """
+    action_heads: bool = False         # MultiDiscrete / MultiBinary heads on K6 / K12
+    wide_critic: bool = False          # a 512-wide critic beside a 256-wide actor (WIDE_WIDTH_PAIRS)
+    wide_inputs: bool = False          # the wide pair with 65 .. 128 inputs per network (implied by wide_shapes: of())
+    wide_shapes: bool = False          # the wide pair with in_dim <= 512 per network and batch sizes <= 1024
+    wide_heads: bool = False           # the wide pair's actor with a head of 9 .. WIDE_HEAD_MAX outputs
+    wide_ranks: bool = False           # the wide pair on N > 1 ranks
+    shared_icm: bool = False           # the agent-shared ICM of an agent-grouped policy on K14
+    wide_icm_actions: bool = False     # ICM Discrete / Box actions of 9 .. WIDE_HEAD_MAX classes or dimensions
+
+    @classmethod
+    def of(cls, pol):
+        """The policy's opt-ins as they are now: a policy without an attribute (MAT, test doubles) has it off."""
+        on = {f: bool(getattr(pol, "fused_" + f, False)) for f in cls._fields}
+        on["wide_inputs"] |= on["wide_shapes"]
+        return cls(**on)
+
+    @property
+    def wide_bits(self):
+        """The option bits of ppoaf_ppo_update_args_t.row_pairs a wide pair sets."""
+        return _lib.SPLIT_WIDE_SHAPES if self.wide_shapes else _lib.SPLIT_WIDE_INPUTS if self.wide_inputs else 0
+
+    def actor_out_limit(self, head):
+        """The widest actor output layer `_describe` takes: WIDE_HEAD_MAX for a Categorical or Gaussian head with
+        `wide_heads` and `wide_critic` (that the pair is the wide one is checked where both networks are known:
+        wide_head_reason), else 8."""
+        ok = self.wide_heads and self.wide_critic and head in (K.HEAD_CATEGORICAL, K.HEAD_GAUSSIAN)
+        return WIDE_HEAD_MAX if ok else 8
+
+
+def action_head(pol, opt=None):
     """
     (head kind, slice table, '') of the policy's action distribution on K6 / K12, or (None, None, why not).  The
     MultiDiscrete and MultiBinary heads (csrc/action_heads.hpp) are taken only for a policy built with
-    update_mode="fused" (PPO sets pol.fused_action_heads); "auto" keeps the torch-ROCm path for them.
+    update_mode="fused" (PPO sets pol.fused_action_heads: opt.action_heads); "auto" keeps the torch-ROCm path for them.
     """
     dist = pol.actor.distribution
     if isinstance(dist, CategoricalDistribution):
@@ -51,7 +87,7 @@ def action_head(pol):
         return K.HEAD_GAUSSIAN, (), ""
     if not isinstance(dist, (MultiCategoricalDistribution, BernoulliDistribution)):
         return None, None, "unknown action distribution"
-    if not getattr(pol, "fused_action_heads", False):
+    if not (opt or FusedOptIns.of(pol)).action_heads:
         return None, None, "MultiDiscrete / MultiBinary heads run on the fused kernels under update_mode='fused' only"
     if isinstance(dist, BernoulliDistribution):
         n = int(pol.action_pred_size)
@@ -75,7 +111,8 @@ def set_action_slices(args, slices):
 def _describe(net, bucket, with_log_std, wide=False, max_out=8):
     """MlpDesc of a FeedForwardNetwork living in `bucket`, or (None, reason).  wide: a 512-wide network is described too
     (the critic of a policy with `fused_wide_critic`: WIDE_WIDTH_PAIRS).  max_out: the widest output layer taken (8, or
-    WIDE_HEAD_MAX for the actor of a policy with `fused_wide_heads`: actor_out_limit)."""
+    WIDE_HEAD_MAX for the actor of a policy with `fused_wide_heads`: FusedOptIns.actor_out_limit).  Called by describe_policy
+    alone: every consumer of a policy's descriptors takes them from there."""
     if not isinstance(net, FeedForwardNetwork) or net.is_embedded:
         return None, "network is not a plain FeedForwardNetwork"
     dims = net.layer_dims()
@@ -147,6 +184,11 @@ def _switch(name, default, values=("0", "1")):
     if v not in values:
         raise ValueError(f"{name}={v!r}: expected {', '.join(values[:-1])} or {values[-1]}")
     return v
+
+
+def split_wgrad_mode():
+    """PPOAF_SPLIT_WGRAD = auto | 0 | 1: the split-wgrad chain of K12, K14 and K15 against their slab forms."""
+    return _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1"))
 
 
 def rccl_comm(dev):
@@ -737,46 +779,10 @@ WIDTH_PAIRS = ((32, 32), (64, 64), (128, 128), (256, 256), (128, 256), (64, 128)
 WIDE_WIDTH_PAIRS = ((256, 512),)
 
 
-def wide_critic(pol):
-    """The policy's 512-wide critic may run on the fused kernels (PPOPolicy.fused_wide_critic)."""
-    return bool(getattr(pol, "fused_wide_critic", False))
-
-
-def wide_shapes(pol):
-    """The policy's wide pair may take in_dim <= 512 per network and batch sizes <= 1024 (PPOPolicy.fused_wide_shapes, set by
-    hand)."""
-    return bool(getattr(pol, "fused_wide_shapes", False))
-
-
-def wide_inputs(pol):
-    """The policy's wide pair may take 65 .. 128 inputs per network (PPOPolicy.fused_wide_inputs, set by hand, or implied by
-    PPOPolicy.fused_wide_shapes)."""
-    return bool(getattr(pol, "fused_wide_inputs", False)) or wide_shapes(pol)
-
-
 # With the opt-in `PPOPolicy.fused_wide_heads` the wide pair's actor takes 9 .. WIDE_HEAD_MAX outputs under a Categorical or a
 # tanh-Gaussian head (Discrete(18), Box(17)): kernels of their own for K6+K7, K12's fwd_bwd and K19 (csrc/policy_wide_heads.hip,
 # csrc/ppo_update_wide_heads.hip), chosen by the library from out_dim.  Every other pair and head keeps 8.
 WIDE_HEAD_MAX = 24
-
-
-def wide_heads(pol):
-    """The policy's wide pair may take an actor head of 9 .. WIDE_HEAD_MAX outputs (PPOPolicy.fused_wide_heads, set by hand)."""
-    return bool(getattr(pol, "fused_wide_heads", False))
-
-
-def wide_ranks(pol):
-    """The policy's wide pair may train on N > 1 ranks (PPOPolicy.fused_wide_ranks, set by hand): the split-wgrad chain with
-    the gradient all-reduce between its wgrad and Adam launches."""
-    return bool(getattr(pol, "fused_wide_ranks", False))
-
-
-def actor_out_limit(pol, head):
-    """The widest actor output layer `_describe` takes for this policy: WIDE_HEAD_MAX for a Categorical or Gaussian head of a
-    policy with `fused_wide_heads` and `fused_wide_critic` (that the pair is the wide one is checked where both networks are
-    known: wide_head_reason), else 8."""
-    ok = wide_heads(pol) and wide_critic(pol) and head in (K.HEAD_CATEGORICAL, K.HEAD_GAUSSIAN)
-    return WIDE_HEAD_MAX if ok else 8
 
 
 def wide_head_reason(a, c):
@@ -788,14 +794,88 @@ def wide_head_reason(a, c):
             f"9 .. {WIDE_HEAD_MAX} outputs at the wide pair {WIDE_WIDTH_PAIRS[0]} only)")
 
 
-def wide_bits(pol):
-    """The option bits of ppoaf_ppo_update_args_t.row_pairs a wide pair of this policy sets."""
-    return _lib.SPLIT_WIDE_SHAPES if wide_shapes(pol) else _lib.SPLIT_WIDE_INPUTS if wide_inputs(pol) else 0
-
-
 def panel_stride(in_dim):
     """Row stride (floats) of a network's layer-0 panel in the split workspace (csrc/ppo_update_dev.hpp: split_xld)."""
     return next((s for s in (64, 128, 256) if in_dim <= s), 512)
+
+
+class PolicyDesc(NamedTuple):
+    """What K6+K7, K12 and K19 are told about an MLP policy (describe_policy)."""
+    head: int                          # K.HEAD_*
+    slices: tuple                      # the multi-categorical head's slice table (empty for the other heads)
+    actor: "_lib.MlpDesc"
+    critic: "_lib.MlpDesc"
+    wide: bool                         # the pair is one of WIDE_WIDTH_PAIRS
+
+
+def describe_policy(pol, opt=None):
+    """(PolicyDesc, '') of an MLP actor / critic the fused kernels are instantiated for, under the opt-ins `opt` (None: the
+    policy's own), or (None, why not).  The one description that the update's scope check and driver, the rollout step and
+    the inference step take their descriptors from; what depends on the batch size, the ranks, the environment or the
+    library is FusedPolicyUpdate.unsupported_reason's."""
+    if opt is None:
+        opt = FusedOptIns.of(pol)
+    head, slices, why = action_head(pol, opt)
+    if head is None:
+        return None, why
+    nets = []
+    for name, net, log_std, wide, max_out in (("actor", pol.actor, head == K.HEAD_GAUSSIAN, False, opt.actor_out_limit(head)),
+                                              ("critic", pol.critic, False, opt.wide_critic, 8)):
+        d, why = _describe(net, pol.policy_params, log_std, wide, max_out)
+        if d is None:
+            return None, f"{name}: {why}"
+        nets.append(d)
+    a, c = nets
+    if c.out_dim != 1:
+        return None, "critic must have one output"
+    if a.offset != 0 or c.offset != a.size:
+        return None, "actor and critic buckets are not adjacent"
+    wide = (a.hidden, c.hidden) in WIDE_WIDTH_PAIRS              # (a 512-wide critic is described for opt.wide_critic only)
+    if (a.hidden, c.hidden) not in WIDTH_PAIRS and not wide:
+        return None, f"hidden widths (actor {a.hidden}, critic {c.hidden}) are not an instantiated pair"
+    if wide_head_reason(a, c):
+        return None, wide_head_reason(a, c)
+    return PolicyDesc(head, slices, a, c, wide), ""
+
+
+def set_head_args(args, desc, dist):
+    """The action head of a described policy into K6's / K19's args: kind, slice table, and the Gaussian head's min_std and
+    action bounds (dist: the actor's distribution)."""
+    args.head_kind = desc.head
+    set_action_slices(args, desc.slices)
+    args.min_std = float(getattr(dist, "min_std", 0.01))
+    lo, hi = dist.bound_tensors() if desc.head == K.HEAD_GAUSSIAN else (None, None)
+    args.act_lo = None if lo is None else lo.data_ptr()
+    args.act_hi = None if hi is None else hi.data_ptr()
+
+
+def _would_take(driver, pol, batch_size, flag, *also):
+    """True when the opt-in `flag` is off and `driver` takes the policy with it (and the opt-ins `also`) switched on: the
+    hypothetical is asked of a changed FusedOptIns, the policy is only read."""
+    opt = FusedOptIns.of(pol)
+    if getattr(opt, flag):
+        return False
+    return driver.unsupported_reason(pol, batch_size, opt._replace(**dict.fromkeys((flag,) + also, True))) == ""
+
+
+def opt_in_hint(pol, batch_size, update_mode):
+    """The clause `verbose` appends to a refusal of FusedPolicyUpdate: the one switch that would take the policy -- under
+    "auto" update_mode="fused" itself, then with fused_wide_heads, then with fused_wide_ranks; under "fused" the latter two --
+    or '' (a policy that misses two opt-ins at once gets none)."""
+    F = FusedPolicyUpdate
+    if update_mode == "fused":
+        if F.wide_heads_would_take(pol, batch_size):
+            return "; PPOPolicy.fused_wide_heads = True would take it on the fused kernels"
+        if F.wide_ranks_would_take(pol, batch_size):
+            return "; PPOPolicy.fused_wide_ranks = True would take it on the fused kernels"
+        return ""
+    if F.fused_mode_would_take(pol, batch_size):
+        return "; update_mode='fused' would take it on the fused kernels"
+    if F.wide_heads_would_take(pol, batch_size):
+        return "; update_mode='fused' with PPOPolicy.fused_wide_heads = True would take it on the fused kernels"
+    if F.wide_ranks_would_take(pol, batch_size):
+        return "; update_mode='fused' with PPOPolicy.fused_wide_ranks = True would take it on the fused kernels"
+    return ""
 
 
 class FusedPolicyUpdate(FusedEpoch):
@@ -803,36 +883,25 @@ class FusedPolicyUpdate(FusedEpoch):
     actor/critic."""
 
     @staticmethod
-    def unsupported_reason(pol, batch_size):
-        """'' when the fused kernels cover this policy, else why not (the torch path is used then)."""
+    def unsupported_reason(pol, batch_size, opt=None):
+        """'' when the fused kernels cover this policy, else why not (the torch path is used then).  opt: the opt-ins the
+        question is asked under (None: the policy's own, FusedOptIns.of)."""
         if pol.using_lstm or pol.agent_grouping:
             return "LSTM / grouped (MAT) policies are not covered by the fused MLP update"
-        head, _, why = action_head(pol)
-        if head is None:
+        if opt is None:
+            opt = FusedOptIns.of(pol)
+        desc, why = describe_policy(pol, opt)
+        if desc is None:
             return why
-        a, why = _describe(pol.actor, pol.policy_params, head == K.HEAD_GAUSSIAN, False, actor_out_limit(pol, head))
-        if a is None:
-            return "actor: " + why
-        c, why = _describe(pol.critic, pol.policy_params, False, wide_critic(pol))
-        if c is None:
-            return "critic: " + why
-        if c.out_dim != 1:
-            return "critic must have one output"
-        if a.offset != 0 or c.offset != a.size:
-            return "actor and critic buckets are not adjacent"
-        wide = (a.hidden, c.hidden) in WIDE_WIDTH_PAIRS          # (a 512-wide critic is described for wide_critic(pol) only)
-        if (a.hidden, c.hidden) not in WIDTH_PAIRS and not wide:
-            return f"hidden widths (actor {a.hidden}, critic {c.hidden}) are not an instantiated pair"
-        if wide_head_reason(a, c):
-            return wide_head_reason(a, c)
+        a, c = desc.actor, desc.critic
         if batch_size < 2:
             return "batch size < 2"
-        if wide:
+        if desc.wide:
             pair = f"wide pair (actor {a.hidden}, critic {c.hidden})"
-            if max(a.in_dim, c.in_dim) > 64 and not wide_inputs(pol):
+            if max(a.in_dim, c.in_dim) > 64 and not opt.wide_inputs:
                 hint = "; PPOPolicy.fused_wide_inputs = True takes in_dim <= 128" if max(a.in_dim, c.in_dim) <= 128 else ""
                 return f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 64 (the split-wgrad chain's panels cover in_dim <= 64){hint}"
-            if wide_shapes(pol):
+            if opt.wide_shapes:
                 if max(a.in_dim, c.in_dim) > 512:
                     return (f"{pair}: in_dim {a.in_dim} / {c.in_dim} > 512 (with fused_wide_shapes the split-wgrad chain's panels "
                             "cover in_dim <= 512)")
@@ -845,16 +914,16 @@ class FusedPolicyUpdate(FusedEpoch):
                             "cover in_dim <= 128)")
                 if batch_size > 512:
                     return f"{pair}: batch size {batch_size} > 512 (the split-wgrad chain covers batch sizes <= 512)"
-            if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
+            if split_wgrad_mode() == "0":
                 return f"{pair}: PPOAF_SPLIT_WGRAD=0, and the wide pair has no slab form"
-            if mpi_utils.get_num_procs() > 1 and not wide_ranks(pol):
+            if mpi_utils.get_num_procs() > 1 and not opt.wide_ranks:
                 return f"{pair}: single rank only for now ({mpi_utils.get_num_procs()} ranks)"
         # what the library itself refuses (depth, in_dim, the row-tile body's LDS): host-only, nothing is launched
         q = _lib.PpoUpdateArgs()
         q.actor, q.critic, q.bucket_total = a, c, a.size + c.size
-        q.head_kind, q.B, q.batch_stride = head, batch_size, batch_size
-        q.row_pairs = wide_bits(pol) if wide else 0
-        set_action_slices(q, action_head(pol)[1])
+        q.head_kind, q.B, q.batch_stride = desc.head, batch_size, batch_size
+        q.row_pairs = opt.wide_bits if desc.wide else 0
+        set_action_slices(q, desc.slices)
         if _lib.load().ppoaf_ppo_update_check(C.byref(q)) != 0:
             return _lib.load().ppoaf_last_error().decode("utf-8", "replace")
         return ""
@@ -862,61 +931,29 @@ class FusedPolicyUpdate(FusedEpoch):
     @staticmethod
     def fused_mode_would_take(pol, batch_size):
         """True for a policy that is refused only because `fused_wide_critic` is off (what "auto" says under verbose)."""
-        if wide_critic(pol) or pol.using_lstm or pol.agent_grouping:
-            return False
-        pol.fused_wide_critic = True
-        try:
-            return FusedPolicyUpdate.unsupported_reason(pol, batch_size) == ""
-        finally:
-            pol.fused_wide_critic = False
+        return _would_take(FusedPolicyUpdate, pol, batch_size, "wide_critic")
 
     @staticmethod
     def wide_heads_would_take(pol, batch_size):
         """True for a policy that is refused only because `fused_wide_heads` is off -- under "auto", together with
         `fused_wide_critic` (what `verbose` adds to the refusal)."""
-        if wide_heads(pol) or pol.using_lstm or pol.agent_grouping:
-            return False
-        missing = object()
-        was, own = pol.fused_wide_critic, vars(pol).get("fused_wide_heads", missing)
-        pol.fused_wide_heads = pol.fused_wide_critic = True
-        try:
-            return FusedPolicyUpdate.unsupported_reason(pol, batch_size) == ""
-        finally:
-            pol.fused_wide_critic = was
-            if own is missing:
-                del pol.fused_wide_heads       # (the instance had none: the class attribute is read again)
-            else:
-                pol.fused_wide_heads = own     # (a False set by hand on the instance, under a class attribute of True)
+        return _would_take(FusedPolicyUpdate, pol, batch_size, "wide_heads", "wide_critic")
 
     @staticmethod
     def wide_ranks_would_take(pol, batch_size):
         """True for a policy that is refused only because `fused_wide_ranks` is off: a wide pair on N > 1 ranks -- under
         "auto", together with `fused_wide_critic` (what `verbose` adds to the refusal)."""
-        if wide_ranks(pol) or pol.using_lstm or pol.agent_grouping or mpi_utils.get_num_procs() == 1:
-            return False
-        missing = object()
-        was, own = pol.fused_wide_critic, vars(pol).get("fused_wide_ranks", missing)
-        pol.fused_wide_ranks = pol.fused_wide_critic = True
-        try:
-            return FusedPolicyUpdate.unsupported_reason(pol, batch_size) == ""
-        finally:
-            pol.fused_wide_critic = was
-            if own is missing:
-                del pol.fused_wide_ranks       # (the instance had none: the class attribute is read again)
-            else:
-                pol.fused_wide_ranks = own     # (a False set by hand on the instance, under a class attribute of True)
+        return mpi_utils.get_num_procs() > 1 and _would_take(FusedPolicyUpdate, pol, batch_size, "wide_ranks", "wide_critic")
 
     def __init__(self, ppo, policy_id):
         super().__init__(ppo, policy_id)
         pol = self.pol
         dev = pol.device
-        self.head, self.action_slices, _ = action_head(pol)
-        self.actor_desc, _ = _describe(pol.actor, pol.policy_params, self.head == K.HEAD_GAUSSIAN, False,
-                                       actor_out_limit(pol, self.head))
-        self.critic_desc, _ = _describe(pol.critic, pol.policy_params, False, wide_critic(pol))
-        self.wide = (self.actor_desc.hidden, self.critic_desc.hidden) in WIDE_WIDTH_PAIRS
+        split_wgrad_mode()             # (a value that is none of the switch's is an error before anything is described or opened)
+        opt = FusedOptIns.of(pol)
+        self.head, self.action_slices, self.actor_desc, self.critic_desc, self.wide = describe_policy(pol, opt)[0]
         # the wide pair's option bits (read here, once: the args and the workspace are built from them)
-        self.wide_bits = wide_bits(pol) if self.wide else 0
+        self.wide_bits = opt.wide_bits if self.wide else 0
         self.n_wg = (self.B + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
         total = pol.policy_params.numel()
         # (a wide pair has no slab form: a placeholder for the args' pointer instead of n_wg x 0.75 M floats nothing reads)
@@ -936,7 +973,7 @@ class FusedPolicyUpdate(FusedEpoch):
         # again; at most 512 workgroups = the flag words of one exchange object): two launches per mini-batch on N > 1 ranks too.
         self.xchg_sp = None
         if self.xchg is not None and _switch("PPOAF_FUSED_TAIL", "1") != "0" \
-                and _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) != "0" and self._split_blocks() <= 512 \
+                and split_wgrad_mode() != "0" and self._split_blocks() <= 512 \
                 and max(self.actor_desc.in_dim, self.critic_desc.in_dim) <= 64 and self.B <= 512:
             self.xchg_sp, why = peer_exchange.open_exchange(self._tail_exchange_floats(), dev)
             if self.xchg_sp is not None and self.xchg_sp.status()[2] == 3:      # (the same kind on every rank: a collective choice)
@@ -976,7 +1013,7 @@ class FusedPolicyUpdate(FusedEpoch):
         of its own between wgrad and Adam (four launches), which beats the slab chain's fused reduce + exchange launch only
         where the split saves more than a launch costs (<8,16>: 46.5 + 6.9 against 59 us; <8,8>: 17.8 + 5.1 against 21.4).
         """
-        mode = _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1"))
+        mode = split_wgrad_mode()
         if self.wide:
             return True, ""            # (the only form a wide pair has: unsupported_reason has refused everything else)
         if mode == "0":
@@ -1000,7 +1037,7 @@ class FusedPolicyUpdate(FusedEpoch):
             return line + f"slab chain ({self.split_reason})"
         tail = self.tail_reason()
         line += "split-wgrad chain, " + ("fused tail" if tail == "" else f"wgrad and Adam launches ({tail})")
-        if self.wide and self.multi and (self.world > 1 or wide_ranks(self.pol)):
+        if self.wide and self.multi and (self.world > 1 or FusedOptIns.of(self.pol).wide_ranks):
             # (one rank rehearsing the N > 1 path without the opt-in: the line it always had)
             line += "; " + self.exchange_route()
         return line + (f"; layer-0 panel stride {panel_stride(a.in_dim)} (actor) / {panel_stride(c.in_dim)} (critic) floats"
@@ -1293,6 +1330,76 @@ def _icm_action_widths_reason(A, Ain, wide_actions):
     return "" if 1 <= A <= top and 1 <= Ain <= top else f"action widths ({A}, {Ain}) must be in [1, {top}]"
 
 
+def _describe_icm_general(icm, action_dtype, enc, multi_discrete, wide_actions):
+    """The body of _describe_icm_shapes (enc: the encoder's four Linear layers) and of _describe_icm_identity (enc: ()).
+    Without an encoder the models work on the observation itself: D = O, and the texts say O."""
+    slices = 0
+    if action_dtype == "multi-discrete":
+        if not multi_discrete:
+            return None, "multi-discrete actions are not covered by the fused ICM update"
+        slices, classes, why = _icm_action_slices(icm)
+        if why:
+            return None, why
+    elif action_dtype not in ("discrete", "continuous"):
+        return None, "unsupported action space for the fused ICM update"
+    inv = [m for m in icm.inv_model.sequential_net.modules() if isinstance(m, nn.Linear)]
+    fwd = [m for m in icm.forward_model.sequential_net.modules() if isinstance(m, nn.Linear)]
+    widths = (32, 64, 128)
+    E = 0
+    if enc:
+        E, O, D = enc[0].out_features, enc[0].in_features, enc[3].out_features
+        if E not in widths:
+            return None, f"encoder width {E} is not an instantiated width {widths}"
+        if [(m.in_features, m.out_features) for m in enc] != [(O, E), (E, E), (E, E), (E, D)]:
+            return None, "encoder layers must be O -> E -> E -> E -> D"
+        if not 1 <= D <= 128:
+            return None, f"encoded dim {D} must be in [1, 128]"
+        if not 1 <= O <= 1024:
+            return None, f"observation size {O} must be in [1, 1024]"
+    if len(inv) < 2 or len(fwd) < 2 or len(inv) > 4 or len(fwd) > 4:
+        return None, "inverse / forward model need 1..3 hidden layers"
+    if not enc:
+        O = D = fwd[-1].out_features
+        if not 1 <= O <= 128:
+            return None, f"identity encoder: observation size O = {O} is above the fused kernels' limit of 128"
+    Mi, Mf = inv[0].out_features, fwd[0].out_features
+    if Mi not in widths or Mf not in widths:
+        return None, f"inverse / forward model widths ({Mi}, {Mf}) are not instantiated widths {widths}"
+    A, Ain = inv[-1].out_features, fwd[0].in_features - D
+    want_inv = [(2 * D, Mi)] + [(Mi, Mi)] * (len(inv) - 2) + [(Mi, A)]
+    want_fwd = [(D + Ain, Mf)] + [(Mf, Mf)] * (len(fwd) - 2) + [(Mf, D)]
+    if [(m.in_features, m.out_features) for m in inv] != want_inv or \
+            [(m.in_features, m.out_features) for m in fwd] != want_fwd:
+        return None, ("inverse / forward model layers do not follow 2D -> Mi .. -> A / D + Ain -> Mf .. -> D" if enc else
+                      "inverse / forward model layers do not follow 2 O -> Mi .. -> A / O + Ain -> Mf .. -> O")
+    if slices:
+        if (A, Ain) != (classes, classes):
+            return None, f"action widths ({A}, {Ain}) are not the {classes} classes of the multi-discrete action space"
+    elif _icm_action_widths_reason(A, Ain, wide_actions):
+        return None, _icm_action_widths_reason(A, Ain, wide_actions)
+    if action_dtype == "discrete" and Ain != A:
+        return None, "unsupported action space for the fused ICM update"
+    acts = {_activation_code(a) for a in (icm.activation, *([icm.obs_encoder.activation] if enc else []),
+                                           icm.inv_model.activation, icm.forward_model.activation)}
+    if len(acts) != 1 or None in acts:
+        return None, "activation is not one shared ReLU / LeakyReLU(0.01) / Tanh"
+    if split_wgrad_mode() == "0":
+        return None, "PPOAF_SPLIT_WGRAD=0: the chain for these ICM shapes has no slab form"
+    marks, total = _icm_bucket_marks(icm, (enc, inv, fwd))       # (an encoder of size 0: enc_offset == inv_offset)
+    if marks is None:
+        return None, total
+    topo = dict(general=True, obs_dim=O, enc_hidden=E, enc_dim=D, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A, fwd_action_dim=Ain,
+                depth_inv=len(inv) - 1, depth_fwd=len(fwd) - 1, activation=acts.pop(), discrete=int(action_dtype == "discrete"),
+                enc_offset=marks[0], inv_offset=marks[1], fwd_offset=marks[2], bucket_total=total)
+    if not enc:
+        topo.update(identity=True)
+    if slices:
+        topo.update(discrete=1, n_action_slices=slices)
+    elif max(A, Ain) > 8:
+        topo.update(n_action_slices=_lib.ICM_WIDE_ACTIONS)
+    return topo, ""
+
+
 def _describe_icm_shapes(icm, action_dtype, multi_discrete=False, wide_actions=False):
     """IcmShapesArgs topology fields (+ general=True) of an ICM, or (None, reason).  Covered: encoder O -> E -> E -> E -> D,
     inverse 2D -> Mi (x 1..3) -> A, forward D + Ain -> Mf (x 1..3) -> D; E, Mi, Mf in (32, 64, 128), 1 <= D <= 128.
@@ -1305,63 +1412,8 @@ def _describe_icm_shapes(icm, action_dtype, multi_discrete=False, wide_actions=F
     if not isinstance(icm.obs_encoder, LinearObservationEncoder):
         return None, ("the identity encoder (encoded_obs_dim = 0) is not covered: the fused kernels need a "
                       "LinearObservationEncoder")
-    slices = 0
-    if action_dtype == "multi-discrete":
-        if not multi_discrete:
-            return None, "multi-discrete actions are not covered by the fused ICM update"
-        slices, classes, why = _icm_action_slices(icm)
-        if why:
-            return None, why
-    elif action_dtype not in ("discrete", "continuous"):
-        return None, "unsupported action space for the fused ICM update"
-    enc = [icm.obs_encoder.enc_1, icm.obs_encoder.enc_2, icm.obs_encoder.enc_3, icm.obs_encoder.enc_4]
-    inv = [m for m in icm.inv_model.sequential_net.modules() if isinstance(m, nn.Linear)]
-    fwd = [m for m in icm.forward_model.sequential_net.modules() if isinstance(m, nn.Linear)]
-    widths = (32, 64, 128)
-    E, O, D = enc[0].out_features, enc[0].in_features, enc[3].out_features
-    if E not in widths:
-        return None, f"encoder width {E} is not an instantiated width {widths}"
-    if [(m.in_features, m.out_features) for m in enc] != [(O, E), (E, E), (E, E), (E, D)]:
-        return None, "encoder layers must be O -> E -> E -> E -> D"
-    if not 1 <= D <= 128:
-        return None, f"encoded dim {D} must be in [1, 128]"
-    if not 1 <= O <= 1024:
-        return None, f"observation size {O} must be in [1, 1024]"
-    if len(inv) < 2 or len(fwd) < 2 or len(inv) > 4 or len(fwd) > 4:
-        return None, "inverse / forward model need 1..3 hidden layers"
-    Mi, Mf = inv[0].out_features, fwd[0].out_features
-    if Mi not in widths or Mf not in widths:
-        return None, f"inverse / forward model widths ({Mi}, {Mf}) are not instantiated widths {widths}"
-    A, Ain = inv[-1].out_features, fwd[0].in_features - D
-    want_inv = [(2 * D, Mi)] + [(Mi, Mi)] * (len(inv) - 2) + [(Mi, A)]
-    want_fwd = [(D + Ain, Mf)] + [(Mf, Mf)] * (len(fwd) - 2) + [(Mf, D)]
-    if [(m.in_features, m.out_features) for m in inv] != want_inv or \
-            [(m.in_features, m.out_features) for m in fwd] != want_fwd:
-        return None, "inverse / forward model layers do not follow 2D -> Mi .. -> A / D + Ain -> Mf .. -> D"
-    if slices:
-        if (A, Ain) != (classes, classes):
-            return None, f"action widths ({A}, {Ain}) are not the {classes} classes of the multi-discrete action space"
-    elif _icm_action_widths_reason(A, Ain, wide_actions):
-        return None, _icm_action_widths_reason(A, Ain, wide_actions)
-    if action_dtype == "discrete" and Ain != A:
-        return None, "unsupported action space for the fused ICM update"
-    acts = {_activation_code(a) for a in (icm.activation, icm.obs_encoder.activation, icm.inv_model.activation,
-                                           icm.forward_model.activation)}
-    if len(acts) != 1 or None in acts:
-        return None, "activation is not one shared ReLU / LeakyReLU(0.01) / Tanh"
-    if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
-        return None, "PPOAF_SPLIT_WGRAD=0: the chain for these ICM shapes has no slab form"
-    marks, total = _icm_bucket_marks(icm, (enc, inv, fwd))
-    if marks is None:
-        return None, total
-    topo = dict(general=True, obs_dim=O, enc_hidden=E, enc_dim=D, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A, fwd_action_dim=Ain,
-                depth_inv=len(inv) - 1, depth_fwd=len(fwd) - 1, activation=acts.pop(), discrete=int(action_dtype == "discrete"),
-                enc_offset=marks[0], inv_offset=marks[1], fwd_offset=marks[2], bucket_total=total)
-    if slices:
-        topo.update(discrete=1, n_action_slices=slices)
-    elif max(A, Ain) > 8:
-        topo.update(n_action_slices=_lib.ICM_WIDE_ACTIONS)
-    return topo, ""
+    e = icm.obs_encoder
+    return _describe_icm_general(icm, action_dtype, [e.enc_1, e.enc_2, e.enc_3, e.enc_4], multi_discrete, wide_actions)
 
 
 def _describe_icm_identity(icm, action_dtype, multi_discrete=False, wide_actions=False):
@@ -1374,62 +1426,7 @@ def _describe_icm_identity(icm, action_dtype, multi_discrete=False, wide_actions
         return None, "not an ICM"
     if not isinstance(icm.obs_encoder, nn.Identity):
         return None, "not an identity encoder (encoded_obs_dim > 0)"
-    slices = 0
-    if action_dtype == "multi-discrete":
-        if not multi_discrete:
-            return None, "multi-discrete actions are not covered by the fused ICM update"
-        slices, classes, why = _icm_action_slices(icm)
-        if why:
-            return None, why
-    elif action_dtype not in ("discrete", "continuous"):
-        return None, "unsupported action space for the fused ICM update"
-    inv = [m for m in icm.inv_model.sequential_net.modules() if isinstance(m, nn.Linear)]
-    fwd = [m for m in icm.forward_model.sequential_net.modules() if isinstance(m, nn.Linear)]
-    widths = (32, 64, 128)
-    if len(inv) < 2 or len(fwd) < 2 or len(inv) > 4 or len(fwd) > 4:
-        return None, "inverse / forward model need 1..3 hidden layers"
-    O = fwd[-1].out_features
-    if not 1 <= O <= 128:
-        return None, f"identity encoder: observation size O = {O} is above the fused kernels' limit of 128"
-    Mi, Mf = inv[0].out_features, fwd[0].out_features
-    if Mi not in widths or Mf not in widths:
-        return None, f"inverse / forward model widths ({Mi}, {Mf}) are not instantiated widths {widths}"
-    A, Ain = inv[-1].out_features, fwd[0].in_features - O
-    want_inv = [(2 * O, Mi)] + [(Mi, Mi)] * (len(inv) - 2) + [(Mi, A)]
-    want_fwd = [(O + Ain, Mf)] + [(Mf, Mf)] * (len(fwd) - 2) + [(Mf, O)]
-    if [(m.in_features, m.out_features) for m in inv] != want_inv or \
-            [(m.in_features, m.out_features) for m in fwd] != want_fwd:
-        return None, "inverse / forward model layers do not follow 2 O -> Mi .. -> A / O + Ain -> Mf .. -> O"
-    if slices:
-        if (A, Ain) != (classes, classes):
-            return None, f"action widths ({A}, {Ain}) are not the {classes} classes of the multi-discrete action space"
-    elif _icm_action_widths_reason(A, Ain, wide_actions):
-        return None, _icm_action_widths_reason(A, Ain, wide_actions)
-    if action_dtype == "discrete" and Ain != A:
-        return None, "unsupported action space for the fused ICM update"
-    acts = {_activation_code(a) for a in (icm.activation, icm.inv_model.activation, icm.forward_model.activation)}
-    if len(acts) != 1 or None in acts:
-        return None, "activation is not one shared ReLU / LeakyReLU(0.01) / Tanh"
-    if _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) == "0":
-        return None, "PPOAF_SPLIT_WGRAD=0: the chain for these ICM shapes has no slab form"
-    marks, total = _icm_bucket_marks(icm, (inv, fwd))
-    if marks is None:
-        return None, total
-    topo = dict(general=True, identity=True, obs_dim=O, enc_hidden=0, enc_dim=O, inv_hidden=Mi, fwd_hidden=Mf, action_dim=A,
-                fwd_action_dim=Ain, depth_inv=len(inv) - 1, depth_fwd=len(fwd) - 1, activation=acts.pop(),
-                discrete=int(action_dtype == "discrete"), enc_offset=marks[0], inv_offset=marks[0], fwd_offset=marks[1],
-                bucket_total=total)
-    if slices:
-        topo.update(discrete=1, n_action_slices=slices)
-    elif max(A, Ain) > 8:
-        topo.update(n_action_slices=_lib.ICM_WIDE_ACTIONS)
-    return topo, ""
-
-
-def icm_wide_actions(pol):
-    """The policy's ICM may take Discrete / Box actions of 9 .. WIDE_HEAD_MAX classes or dimensions on the shapes chain
-    (PPOPolicy.fused_wide_icm_actions, set by hand)."""
-    return bool(getattr(pol, "fused_wide_icm_actions", False))
+    return _describe_icm_general(icm, action_dtype, (), multi_discrete, wide_actions)
 
 
 def describe_icm_chain(icm, action_dtype, multi_discrete=False, wide_actions=False):
@@ -1453,6 +1450,17 @@ def describe_icm_chain(icm, action_dtype, multi_discrete=False, wide_actions=Fal
     if wide_actions and action_dtype in ("discrete", "continuous"):
         return _describe_icm_shapes(icm, action_dtype, wide_actions=True)
     return None, why
+
+
+def describe_policy_icm(pol, opt=None):
+    """Which K14 chain trains the policy's ICM under the opt-ins `opt` (None: the policy's own): describe_icm_chain's
+    (topology, "") or (None, reason).  An agent-shared ICM (FusedIcmUpdate._shared) is described with its own action dtype
+    -- the policy's is the agents' "discrete", the ICM's is what it trains on -- and its multi-categorical head."""
+    if opt is None:
+        opt = FusedOptIns.of(pol)
+    if FusedIcmUpdate._shared(pol, opt):
+        return describe_icm_chain(pol.icm_model, pol.icm_model.action_dtype, multi_discrete=True)
+    return describe_icm_chain(pol.icm_model, pol.action_dtype, wide_actions=opt.wide_icm_actions)
 
 
 def icm_scratch_floats(topo, rows):
@@ -1540,21 +1548,20 @@ class FusedIcmUpdate(FusedEpoch):
     min_tail_rows = 1
 
     @staticmethod
-    def unsupported_reason(pol, batch_size=None, wide_actions=None):
-        """'' or why the torch path trains the policy's ICM.  wide_actions: None reads the policy's opt-in."""
-        if wide_actions is None:
-            wide_actions = icm_wide_actions(pol)
+    def unsupported_reason(pol, batch_size=None, opt=None):
+        """'' or why the torch path trains the policy's ICM.  opt: the opt-ins the question is asked under (None: the
+        policy's own)."""
+        if opt is None:
+            opt = FusedOptIns.of(pol)
         if not pol.enable_icm:
             return "no ICM"
-        if FusedIcmUpdate._shared(pol):
-            # (the policy's own action_dtype is the agents' "discrete": the ICM's is what it trains on)
-            return describe_icm_chain(pol.icm_model, pol.icm_model.action_dtype, multi_discrete=True)[1]
-        if pol.agent_grouping and pol.agent_shared_icm:
+        shared = FusedIcmUpdate._shared(pol, opt)
+        if pol.agent_grouping and pol.agent_shared_icm and not shared:
             return ("agent_shared_icm: one ICM over the MultiDiscrete action space of the whole group (ppo.py:2520-2538) "
                     "is not covered, torch path")
-        _, why = describe_icm_chain(pol.icm_model, pol.action_dtype, wide_actions=wide_actions)
-        if not why and pol.agent_grouping and batch_size is not None:
-            A = FusedIcmUpdate._agents(pol)
+        _, why = describe_policy_icm(pol, opt)
+        if not why and pol.agent_grouping and not shared and batch_size is not None:
+            A = FusedIcmUpdate._agents(pol, opt)
             if batch_size * A > 65536:
                 return f"agent-grouped policy: batch_size x agents = {batch_size} x {A} ICM rows per mini-batch exceed 65536"
         return why
@@ -1562,18 +1569,18 @@ class FusedIcmUpdate(FusedEpoch):
     @staticmethod
     def wide_actions_would_take(pol, batch_size=None):
         """True for an ICM that is refused only because `fused_wide_icm_actions` is off (what `verbose` adds to the refusal)."""
-        return bool(not icm_wide_actions(pol) and FusedIcmUpdate.unsupported_reason(pol, batch_size, wide_actions=False)
-                    and not FusedIcmUpdate.unsupported_reason(pol, batch_size, wide_actions=True))
+        refused = FusedIcmUpdate.unsupported_reason(pol, batch_size) != ""
+        return refused and _would_take(FusedIcmUpdate, pol, batch_size, "wide_icm_actions")
 
     @staticmethod
-    def _shared(pol):
+    def _shared(pol, opt=None):
         """The agent-shared ICM of an agent-grouped policy on the fused kernels (opt-in: PPOPolicy.fused_shared_icm)."""
-        return bool(getattr(pol, "agent_grouping", False) and pol.agent_shared_icm and getattr(pol, "fused_shared_icm", False))
+        return bool(getattr(pol, "agent_grouping", False) and pol.agent_shared_icm and (opt or FusedOptIns.of(pol)).shared_icm)
 
     @staticmethod
-    def _agents(pol):
+    def _agents(pol, opt=None):
         """ICM samples per buffer row: the group's agents for an agent-grouped policy (1 when they share one ICM), else 1."""
-        if FusedIcmUpdate._shared(pol):
+        if FusedIcmUpdate._shared(pol, opt):
             return 1
         return int(getattr(pol, "num_agents", 0) or len(pol.agent_ids)) if getattr(pol, "agent_grouping", False) else 1
 
@@ -1581,13 +1588,11 @@ class FusedIcmUpdate(FusedEpoch):
         super().__init__(ppo, policy_id)
         pol = self.pol
         dev = pol.device
-        self.shared = self._shared(pol)                    # read once, as the refusal was: the opt-in is set before the first epoch
-        if self.shared:
-            self.topo, _ = describe_icm_chain(pol.icm_model, pol.icm_model.action_dtype, multi_discrete=True)
-        else:
-            self.topo, _ = describe_icm_chain(pol.icm_model, pol.action_dtype, wide_actions=icm_wide_actions(pol))
+        opt = FusedOptIns.of(pol)                          # read once, as the refusal was: the opt-ins are set before the first epoch
+        self.shared = self._shared(pol, opt)
+        self.topo, _ = describe_policy_icm(pol, opt)
         self.general = bool(self.topo.get("general"))      # csrc/icm_update_shapes.hip: split-wgrad form only, no in-kernel waits
-        self.A = self._agents(pol)                         # ICM samples per buffer row (agent-grouped policies: the agents)
+        self.A = self._agents(pol, opt)                    # ICM samples per buffer row (agent-grouped policies: the agents)
         rows = self.B * self.A                             # everything below is sized for a full mini-batch's samples
         nT = (rows + K.UPDATE_ROWS_PER_WG - 1) // K.UPDATE_ROWS_PER_WG
         total = self.topo["bucket_total"]
@@ -1599,7 +1604,7 @@ class FusedIcmUpdate(FusedEpoch):
         self._open_exchange(pol.icm_model.flat_grads.numel())
         # split-wgrad chain (csrc/icm_update.hip: icm_wgrad_kernel): PPOAF_SPLIT_WGRAD = auto (= 1) | 1 | 0.  The reduce entry
         # point keeps its contract, so graphs, K17 and the RCCL loop are the same with either form.
-        self.split = _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) != "0"
+        self.split = split_wgrad_mode() != "0"
 
     def drop_peer_exchange(self, why):
         super().drop_peer_exchange(why)
@@ -1832,7 +1837,7 @@ class FusedMatUpdate(FusedEpoch):
         # split-wgrad chain (csrc/mat_update.hip: mat_update_wgrad_kernel): PPOAF_SPLIT_WGRAD = auto (= 1) | 1 | 0.  The reduce
         # entry point keeps its contract (slabs / panels -> gradient bucket), so every path above it -- graphs, K17, the
         # RCCL loops -- is the same with either form.
-        self.split = _switch("PPOAF_SPLIT_WGRAD", "auto", ("auto", "0", "1")) != "0"
+        self.split = split_wgrad_mode() != "0"
         self._norm_partials = {}
 
     def _make_args(self, B):

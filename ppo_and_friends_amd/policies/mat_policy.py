@@ -518,7 +518,7 @@ class MATPolicy(PPOPolicy):
         act = join(self._to_device(actions, adt))
         if self.fused_shared_icm and obs_1.is_cuda and getattr(self, "fused_icm_reward", True):
             # K14 on the joined rows [E, A O] / int64 [E, A] (opt-in; counted in PPOPolicy.fused_icm_reward_calls)
-            fused = self._fused_intrinsic_reward(obs_1, obs_2, act, shared=True)
+            fused = self._fused_intrinsic_reward(obs_1, obs_2, act)
             if fused is not None:
                 return fused
         with torch.no_grad():

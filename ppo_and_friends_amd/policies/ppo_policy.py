@@ -412,24 +412,17 @@ class PPOPolicy:
         `finish_step` once the environment has answered.
         """
         from .. import _lib
-        from ..fused_update import _describe, action_head, actor_out_limit, set_action_slices
+        from ..fused_update import describe_policy, set_head_args
         buf = self.buffer
         E = buf.C                       # agents x envs rows, agent-major
         a = getattr(self, "_step_args", None)
         if a is None:
             a = _lib.PolicyStepArgs()
-            head, slices, _ = action_head(self)
-            gauss = head == K.HEAD_GAUSSIAN
-            a.actor, _ = _describe(self.actor, self.policy_params, gauss, False, actor_out_limit(self, head))
-            a.critic, _ = _describe(self.critic, self.policy_params, False, self.fused_wide_critic)
+            desc, _ = describe_policy(self)     # (a covered policy: the callers have asked fused_step_unsupported_reason)
+            a.actor, a.critic = desc.actor, desc.critic
             a.params = self.policy_params.data_ptr()
             a.E = E
-            a.head_kind = head
-            set_action_slices(a, slices)
-            a.min_std = float(getattr(self.actor.distribution, "min_std", 0.01))
-            lo, hi = self.actor.distribution.bound_tensors() if gauss else (None, None)
-            a.act_lo = None if lo is None else lo.data_ptr()
-            a.act_hi = None if hi is None else hi.data_ptr()
+            set_head_args(a, desc, self.actor.distribution)
             self._step_args = a
         if blocks is None:
             K._req(obs.is_cuda and obs.dtype == torch.float32 and obs.is_contiguous() and obs.numel() == E * a.actor.in_dim,
@@ -737,21 +730,18 @@ class PPOPolicy:
             intr, _, _ = self.icm_model(obs_1, obs_2, act)
         return intr.reshape(-1) * float(self.intr_reward_weight())
 
-    def _fused_intrinsic_reward(self, obs_1, obs_2, act, shared=False):
+    def _fused_intrinsic_reward(self, obs_1, obs_2, act):
         """K14's encoder + forward-model kernels on the env batch (two launches; one for an identity encoder); None when not
-        covered.  shared: the rows are an agent-shared ICM's (one per env, MultiDiscrete classes [n, agents]): described
-        with the ICM's own action dtype."""
+        covered.  The rows of an agent-shared ICM (one per env, MultiDiscrete classes [n, agents]; MATPolicy) are described
+        with the ICM's own action dtype: fused_update.describe_policy_icm."""
         import ctypes as C
         from .. import _lib
         from .. import kernels as K
         st = getattr(self, "_icm_reward_state", None)
         n = obs_1.shape[0]
         if st is None or st["n"] != n:
-            from ..fused_update import describe_icm_chain, icm_scratch_floats, icm_topology_args, icm_wide_actions
-            if shared:
-                topo, why = describe_icm_chain(self.icm_model, self.icm_model.action_dtype, multi_discrete=True)
-            else:
-                topo, why = describe_icm_chain(self.icm_model, self.action_dtype, wide_actions=icm_wide_actions(self))
+            from ..fused_update import describe_policy_icm, icm_scratch_floats, icm_topology_args
+            topo, why = describe_policy_icm(self)
             if topo is None:
                 self.fused_icm_reward = False
                 return None
@@ -782,8 +772,8 @@ class PPOPolicy:
         if self.using_lstm:
             return "LSTM policies are not K19's: K21 or forward_logits (see lstm_step_unsupported_reason)"
         # (asked once per evaluation step: the answer is kept for as long as what it depends on stays)
-        key = (self.policy_params.data_ptr(), bool(self.fused_action_heads), bool(self.fused_wide_critic),
-               bool(self.fused_wide_inputs), bool(self.fused_wide_shapes), bool(self.fused_wide_heads), bool(self.fused_wide_ranks))
+        from ..fused_update import FusedOptIns
+        key = (self.policy_params.data_ptr(), FusedOptIns.of(self))
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
             self._infer_reason = (key, self.fused_step_unsupported_reason())
         return self._infer_reason[1]
@@ -800,23 +790,17 @@ class PPOPolicy:
     def _infer_step(self, t_obs, deterministic):
         """K19: one launch, actor forward -> head -> env action, into a reusable output tensor."""
         from .. import _lib
-        from ..fused_update import _describe, action_head, actor_out_limit, set_action_slices
+        from ..fused_update import describe_policy, set_head_args
         E = t_obs.shape[0]
         st = getattr(self, "_infer_state", None)
         if st is None or st["E"] != E or st["params"] != self.policy_params.data_ptr():
             a = _lib.PolicyInferArgs()
-            head, slices, _ = action_head(self)
-            gauss = head == K.HEAD_GAUSSIAN
-            a.actor, _ = _describe(self.actor, self.policy_params, gauss, False, actor_out_limit(self, head))
+            desc, _ = describe_policy(self)     # (a covered policy: get_inference_actions has asked inference_unsupported_reason)
+            head, a.actor = desc.head, desc.actor
             a.params = self.policy_params.data_ptr()
             a.E = E
-            a.head_kind = head
-            set_action_slices(a, slices)
-            a.min_std = float(getattr(self.actor.distribution, "min_std", 0.01))
-            lo, hi = self.actor.distribution.bound_tensors() if gauss else (None, None)
-            a.act_lo = None if lo is None else lo.data_ptr()
-            a.act_hi = None if hi is None else hi.data_ptr()
-            shape = {K.HEAD_CATEGORICAL: (E,), K.HEAD_MULTI_CATEGORICAL: (E, len(slices))}.get(head, (E, a.actor.out_dim))
+            set_head_args(a, desc, self.actor.distribution)
+            shape = {K.HEAD_CATEGORICAL: (E,), K.HEAD_MULTI_CATEGORICAL: (E, len(desc.slices))}.get(head, (E, a.actor.out_dim))
             out = torch.zeros(shape, dtype=torch.float32 if head in (K.HEAD_GAUSSIAN, K.HEAD_BERNOULLI) else torch.int64,
                               device=self.device)
             a.action_out = out.data_ptr()

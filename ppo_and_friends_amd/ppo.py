@@ -542,13 +542,10 @@ class PPO:
                 pol.actor.use_hip = pol.critic.use_hip = True
             elif update_mode == "fused" and not pol.agent_grouping and self.device.type == "cuda":
                 # K12's scope is known before the first rollout: refuse here, not in the middle of the first epoch
-                from .fused_update import FusedPolicyUpdate
+                from .fused_update import FusedPolicyUpdate, opt_in_hint
                 why = FusedPolicyUpdate.unsupported_reason(pol, self.batch_size)
                 if why:
-                    if verbose and FusedPolicyUpdate.wide_heads_would_take(pol, self.batch_size):
-                        why += "; PPOPolicy.fused_wide_heads = True would take it on the fused kernels"
-                    elif verbose and FusedPolicyUpdate.wide_ranks_would_take(pol, self.batch_size):
-                        why += "; PPOPolicy.fused_wide_ranks = True would take it on the fused kernels"
+                    why += opt_in_hint(pol, self.batch_size, update_mode) if verbose else ""
                     raise NotImplementedError(f"update_mode='fused' but policy {policy_id}: {why}")
         # ppo.py:663-678: freeze cycling over policy groups (utils/schedulers.py:FreezeCyclingScheduler)
         from .utils.schedulers import FreezeCyclingScheduler
@@ -1453,20 +1450,14 @@ class PPO:
                                            f"the mini-batch loop ({FusedLstmUpdate.unsupported_reason(pol, B)})")
             return self._fused[key]
         if key not in self._fused:
-            from .fused_update import FusedMatUpdate, FusedPolicyUpdate
+            from .fused_update import FusedMatUpdate, FusedPolicyUpdate, opt_in_hint
             driver = FusedMatUpdate if self.policies[policy_id].agent_grouping else FusedPolicyUpdate    # K15 / K12
             why = driver.unsupported_reason(self.policies[policy_id], B)
             if why:
                 if self.update_mode == "fused":
                     raise NotImplementedError(f"update_mode='fused' but {why}")
                 if self.verbose:
-                    hint = ""
-                    if driver is FusedPolicyUpdate and FusedPolicyUpdate.fused_mode_would_take(self.policies[policy_id], B):
-                        hint = "; update_mode='fused' would take it on the fused kernels"
-                    elif driver is FusedPolicyUpdate and FusedPolicyUpdate.wide_heads_would_take(self.policies[policy_id], B):
-                        hint = "; update_mode='fused' with PPOPolicy.fused_wide_heads = True would take it on the fused kernels"
-                    elif driver is FusedPolicyUpdate and FusedPolicyUpdate.wide_ranks_would_take(self.policies[policy_id], B):
-                        hint = "; update_mode='fused' with PPOPolicy.fused_wide_ranks = True would take it on the fused kernels"
+                    hint = opt_in_hint(pol, B, self.update_mode) if driver is FusedPolicyUpdate else ""
                     rank_print(f"policy {policy_id}: torch update path ({why}){hint}")
                 self._fused[key] = None
             else:

@@ -214,7 +214,7 @@ def test_update_mode_leaves_the_attribute_alone():
 
 
 def test_unsupported_reason_follows_the_attribute(monkeypatch):
-    from ppo_and_friends_amd.fused_update import FusedPolicyUpdate, panel_stride, wide_inputs, wide_shapes
+    from ppo_and_friends_amd.fused_update import FusedOptIns, FusedPolicyUpdate, panel_stride
     from ppo_and_friends_amd.policies.ppo_policy import PPOPolicy
     reason = FusedPolicyUpdate.unsupported_reason
     pols = {O: _ppo("fused", O=O).policies["p"] for O in (128, 129, 256, 433, 513)}
@@ -228,7 +228,7 @@ def test_unsupported_reason_follows_the_attribute(monkeypatch):
         assert reason(small, B) == batch_today(B), B
     with monkeypatch.context() as mp:
         mp.setattr(PPOPolicy, "fused_wide_inputs", True)
-        assert wide_inputs(small) and not wide_shapes(small)
+        assert FusedOptIns.of(small).wide_inputs and not FusedOptIns.of(small).wide_shapes
         for O, pol in pols.items():
             assert reason(pol, 64) == _todays_in_dim_reason(O, True), O
         for B in (513, 1000, 1024, 1025):
@@ -236,7 +236,7 @@ def test_unsupported_reason_follows_the_attribute(monkeypatch):
     # the new attribute, alone: it implies the other
     with monkeypatch.context() as mp:
         mp.setattr(PPOPolicy, "fused_wide_shapes", True)
-        assert wide_shapes(small) and wide_inputs(small) and PPOPolicy.fused_wide_inputs is False
+        assert FusedOptIns.of(small).wide_shapes and FusedOptIns.of(small).wide_inputs and PPOPolicy.fused_wide_inputs is False
         for O in (128, 129, 256):
             assert reason(pols[O], 64) == "", (O, reason(pols[O], 64))
             assert reason(pols[O], 1024) == "", O
