@@ -1092,6 +1092,68 @@ typedef struct {
 int ppoaf_mat_policy_step_blocks(const ppoaf_mat_step_args_t* args, const ppoaf_mat_step_blocks_t* blocks, ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * K15 / K16, Box form: a MATPolicy over continuous (tanh-Gaussian) actions
+ * replaces the same interfaces as K15 and K16 for MATActor's continuous form   networks/actor_critic/multi_agent_transformer.py:22-156
+ *          the zero-start action block of previous agents' actions            policies/mat_policy.py:308-344,378-439,441-519
+ *          GaussianDistribution: sample, refine, log-prob, entropy            networks/distributions.py:441-694
+ * The action encoder is Linear(NA, 64) WITH a bias over the previous agents' actions themselves, the head's last linear
+ * gives the means, std = max(softplus(log_std), min_std).  `mat` is read as by the Discrete entry points, except:
+ *   num_actions = NA, the action dimensions (1 .. 8);
+ *   offsets[0 .. 62] = the 63 tensors both forms share, where they sit in the Box bucket, which is in module order
+ *     distribution.log_std [NA], action_encoder.0.weight [64, NA], action_encoder.0.bias [64], then the Discrete list
+ *     from actor.ln on (each tensor padded to 4 floats); log_std_offset and enc_bias_offset place the two tensors only
+ *     this form has.  The whole table is checked against the topology;
+ *   the int64 action pointers (update: raw_actions; step: action_out, raw_action_out, forced_action) must be NULL: the
+ *     float tables of this struct take their place.
+ * Update (split-wgrad chain only: mat.split_workspace must be set): the token block is evaluate's -- slot i sees the
+ * STORED raw action of slot i - 1, slot 0 zeros -- and log-prob / entropy are K12's Gaussian head, clamps and gradient
+ * gates included.  fwd_bwd leaves d log_std as one partial per workgroup in its compact slab; `reduce` / `wgrad_adam`
+ * are the Discrete launches over a bucket that holds the two extra tensors.  Same call sequence and outputs as K15.
+ * Step: pass i draws raw = mean + std * n with the Philox counter offset + env * A + slot, block q of it giving the
+ * normals of dimensions 4 q .. 4 q + 3 (K6's Gaussian sampler), or with forced_action evaluates the recorded raw
+ * action; the action refined through tanh into [act_lo, act_hi] is agent i + 1's token.  Buffer rows, value output and
+ * observation copies are K16's; the block form's env_action blocks are float32 [E, NA].
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    ppoaf_mat_update_args_t mat;
+    const float* raw_actions;        /* [n_rows, A, NA] (or the per-epoch table, as mat.inputs_in_batch_order says) */
+    int64_t enc_bias_offset, log_std_offset;
+    float min_std;
+    int32_t reserved;
+} ppoaf_mat_box_update_args_t;
+
+int ppoaf_mat_box_update_fwd_bwd(const ppoaf_mat_box_update_args_t* args, ppoaf_stream_t stream);
+int ppoaf_mat_box_update_reduce(const ppoaf_mat_box_update_args_t* args, ppoaf_stream_t stream);
+int ppoaf_mat_box_update_split_workspace_bytes(const ppoaf_mat_box_update_args_t* args, int64_t* bytes_out);
+int ppoaf_mat_box_update_tail_ctl_bytes(const ppoaf_mat_box_update_args_t* args, int64_t* bytes_out);
+int ppoaf_mat_box_update_wgrad_adam(const ppoaf_mat_box_update_args_t* args, void* ctl, float* exp_avg, float* exp_avg_sq,
+                                    const float* lr, float beta1, float beta2, float eps, float grad_scale, float max_norm,
+                                    float* grad_norm_out, double wait_seconds, ppoaf_stream_t stream);
+int ppoaf_mat_box_update_norm_partials(const ppoaf_mat_box_update_args_t* args);
+
+typedef struct {
+    ppoaf_mat_step_args_t mat;
+    int64_t enc_bias_offset, log_std_offset;
+    float min_std;
+    int32_t reserved;
+    const float* act_lo; const float* act_hi;    /* [NA] device bounds, or both NULL: the unit box */
+    float* action_out; float* raw_action_out;    /* [E, A, NA] */
+    const float* forced_action;                  /* NULL: sample.  Else [E, A, NA] raw actions to evaluate (replay) */
+} ppoaf_mat_box_step_args_t;
+
+typedef struct {
+    int32_t n_blocks;
+    int32_t slot_agent[PPOAF_ROW_BLOCKS_MAX];
+    const float* critic_obs[PPOAF_ROW_BLOCKS_MAX];
+    const float* actor_obs[PPOAF_ROW_BLOCKS_MAX];
+    float* env_action[PPOAF_ROW_BLOCKS_MAX];     /* [E, NA] each */
+} ppoaf_mat_box_step_blocks_t;
+
+int ppoaf_mat_box_policy_step(const ppoaf_mat_box_step_args_t* args, ppoaf_stream_t stream);
+int ppoaf_mat_box_policy_step_blocks(const ppoaf_mat_box_step_args_t* args, const ppoaf_mat_box_step_blocks_t* blocks,
+                                     ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * K20  one evaluation step of a MATPolicy for all E envs in one launch
  * replaces MATPolicy.get_inference_actions                              policies/mat_policy.py:701-790
  *          _get_autoregressive_actions_without_exploration (greedy)     mat_policy.py:521-585

@@ -242,6 +242,19 @@ class MatStepArgs(C.Structure):
                 ("forced_action", C.c_void_p)]
 
 
+class MatBoxUpdateArgs(C.Structure):
+    """ppoaf_mat_box_update_args_t (include/ppoaf_hip.h): K15's args and what the Box form adds."""
+    _fields_ = [("mat", MatUpdateArgs), ("raw_actions", C.c_void_p), ("enc_bias_offset", C.c_int64),
+                ("log_std_offset", C.c_int64), ("min_std", C.c_float), ("reserved", C.c_int32)]
+
+
+class MatBoxStepArgs(C.Structure):
+    """ppoaf_mat_box_step_args_t (include/ppoaf_hip.h): K16's args and what the Box form adds."""
+    _fields_ = [("mat", MatStepArgs), ("enc_bias_offset", C.c_int64), ("log_std_offset", C.c_int64),
+                ("min_std", C.c_float), ("reserved", C.c_int32), ("act_lo", C.c_void_p), ("act_hi", C.c_void_p),
+                ("action_out", C.c_void_p), ("raw_action_out", C.c_void_p), ("forced_action", C.c_void_p)]
+
+
 class MatInferArgs(C.Structure):
     """ppoaf_mat_infer_args_t (include/ppoaf_hip.h)."""
     _fields_ = [("obs_dim", C.c_int32), ("num_agents", C.c_int32), ("num_actions", C.c_int32), ("embedding", C.c_int32),
@@ -280,6 +293,10 @@ class MatStepBlocks(C.Structure):
     """ppoaf_mat_step_blocks_t (include/ppoaf_hip.h)."""
     _fields_ = [("n_blocks", C.c_int32), ("slot_agent", C.c_int32 * ROW_BLOCKS_MAX), ("critic_obs", C.c_void_p * ROW_BLOCKS_MAX),
                 ("actor_obs", C.c_void_p * ROW_BLOCKS_MAX), ("env_action", C.c_void_p * ROW_BLOCKS_MAX)]
+
+
+class MatBoxStepBlocks(MatStepBlocks):
+    """ppoaf_mat_box_step_blocks_t (include/ppoaf_hip.h): the same layout, env_action blocks are float32 [E, NA]."""
 
 
 class RolloutFinishArgs(C.Structure):
@@ -394,6 +411,15 @@ SIGNATURES = {
     "ppoaf_rollout_finish_rows": (C.c_int, [C.POINTER(RolloutFinishArgs), _ptr]),
     "ppoaf_policy_step_blocks": (C.c_int, [C.POINTER(PolicyStepArgs), C.POINTER(StepBlocks), _ptr]),
     "ppoaf_mat_policy_step_blocks": (C.c_int, [C.POINTER(MatStepArgs), C.POINTER(MatStepBlocks), _ptr]),
+    "ppoaf_mat_box_update_fwd_bwd": (C.c_int, [C.POINTER(MatBoxUpdateArgs), _ptr]),
+    "ppoaf_mat_box_update_reduce": (C.c_int, [C.POINTER(MatBoxUpdateArgs), _ptr]),
+    "ppoaf_mat_box_update_split_workspace_bytes": (C.c_int, [C.POINTER(MatBoxUpdateArgs), C.POINTER(C.c_int64)]),
+    "ppoaf_mat_box_update_tail_ctl_bytes": (C.c_int, [C.POINTER(MatBoxUpdateArgs), C.POINTER(C.c_int64)]),
+    "ppoaf_mat_box_update_wgrad_adam": (C.c_int, [C.POINTER(MatBoxUpdateArgs), _ptr, _ptr, _ptr, _ptr, C.c_float, C.c_float,
+                                                  C.c_float, C.c_float, C.c_float, _ptr, C.c_double, _ptr]),
+    "ppoaf_mat_box_update_norm_partials": (C.c_int, [C.POINTER(MatBoxUpdateArgs)]),
+    "ppoaf_mat_box_policy_step": (C.c_int, [C.POINTER(MatBoxStepArgs), _ptr]),
+    "ppoaf_mat_box_policy_step_blocks": (C.c_int, [C.POINTER(MatBoxStepArgs), C.POINTER(MatBoxStepBlocks), _ptr]),
     "ppoaf_lstm_workspace_floats": (C.c_int, [C.POINTER(LstmDesc), C.POINTER(C.c_int64)]),
     "ppoaf_lstm_forward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int32, _ptr]),
     "ppoaf_lstm_backward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),

@@ -149,6 +149,39 @@ __device__ __forceinline__ void gauss_step_row(const float* mean_row, const int 
     }
     logp_out[e] = lp - slog;
 }
+// Box, update: ONE dimension of the tanh-Gaussian head as K12 evaluates it (ppo_update_dev.hpp: ppo_head_loss), for heads
+// that spread a row's dimensions over lanes (K15's Box form: mat_box.hpp).  Terms: l += the clamped Normal log-density of
+// x, slog += the tanh log-det of x, ent += the entropy term (the corrected log-density of the MEAN, negated)
+__device__ __forceinline__ void gauss_dim_terms(const float mu, const float x, const float ls, const float min_std,
+                                                float& l_sum, float& slog, float& ent) {
+    const float sd = fmaxf(softplus_u(ls), min_std);
+    const float zz = x - mu;
+    const float l0 = -logf(sd) - 0.91893853320467274178f;
+    const float l = -(zz * zz) / (2.0f * sd * sd) + l0;
+    l_sum += fminf(fmaxf(l, -100.f), 100.f);
+    const float th = tanhf(x);
+    slog += logf(fmaxf(1.0f - th * th, 1e-6f));
+    const float thm = tanhf(mu);
+    ent += logf(fmaxf(1.0f - thm * thm, 1e-6f)) - fminf(fmaxf(l0, -100.f), 100.f);
+}
+// ... and its gradients for d loss / d log-prob = glp, d loss / d entropy = gH, with K12's gates: the +-100 clamps pass
+// gradient inside their bounds (bounds included), the entropy's tanh clamp where 1 - tanh(mu)^2 >= 1e-6, max(softplus,
+// min_std) to the softplus where it is the larger (halved on a tie)
+__device__ __forceinline__ void gauss_dim_grads(const float mu, const float x, const float ls, const float min_std,
+                                                const float glp, const float gH, float& d_mean, float& d_log_std) {
+    const float sp = softplus_u(ls), sd = fmaxf(sp, min_std);
+    const float zz = x - mu;
+    const float l0 = -logf(sd) - 0.91893853320467274178f;
+    const float l = -(zz * zz) / (2.0f * sd * sd) + l0;
+    const float pass = (l >= -100.f && l <= 100.f) ? 1.f : 0.f;
+    const float pass0 = (l0 >= -100.f && l0 <= 100.f) ? 1.f : 0.f;
+    const float thm = tanhf(mu);
+    const float pass_t = (1.0f - thm * thm >= 1e-6f) ? 1.f : 0.f;
+    d_mean = glp * pass * zz / (sd * sd) - gH * pass_t * 2.0f * thm;
+    const float dmax = sp > min_std ? 1.f : (sp == min_std ? 0.5f : 0.f);
+    const float dsp = ls > 20.f ? 1.f : 1.0f / (1.0f + expf(-ls));
+    d_log_std = (glp * pass * (zz * zz / (sd * sd * sd) - 1.0f / sd) + gH * pass0 / sd) * dmax * dsp;
+}
 // Discrete, evaluation: the argmax, the lowest index on an exact tie (torch.argmax on the reference's CPU tensors), or a
 // sample -> the env action
 template <int K = 8>

@@ -19,6 +19,8 @@
 #include "running_stats_device.hpp"
 #include "tail_sync.hpp"
 #include "wgrad_tile.hpp"
+#include "mat_box.hpp"
+#include <type_traits>
 #include <hip/hip_ext.h>
 #include <cstdlib>
 
@@ -69,6 +71,15 @@ struct MatDev {
     long slab_stride;    // floats per workgroup slab (split: n_small4 * 4; else total)
     int n_small4;        // float4 columns of the compact slab
     int n_seg, seg_start[4], seg_dst[4];   // runs of small tensors: compact float offset -> bucket float offset
+};
+
+// The Box form (mat_box.hpp) carries the Discrete form's view -- off[] / goff[] hold the 63 shared tensors where they sit in
+// the Box bucket, NA = Ain = the action dimensions, `actions` unused -- and, beside it, the two tensors only it has
+struct MatBoxDev : MatDev {
+    const float* actions_f;          // [tokens][NA] stored raw actions
+    long off_enc_b, off_log_std;     // action_encoder.0.bias, distribution.log_std in the bucket
+    int goff_enc_b, goff_log_std;    // ... and in a workgroup's compact slab
+    float min_std;
 };
 
 // the 18 linears whose weight gradients the wgrad launch forms, in the order the backward meets them, and the panel that
@@ -685,11 +696,12 @@ __device__ __forceinline__ void mat_encoder_forward(const Ctx& c, int tid, int w
 
 // actor (decoder): token block in sXA + rep_enc in cENC -> logits in sOutA; starts and ends with the tiles settled
 template <bool PF, typename Pub = MatNoPub, typename Ctx = MatCtx>
-__device__ __forceinline__ void mat_decoder_forward(const Ctx& c, int tid, int wave, int lane, const Pub pub = Pub()) {
+__device__ __forceinline__ void mat_decoder_forward(const Ctx& c, int tid, int wave, int lane, const Pub pub = Pub(),
+                                                    const float* enc_bias = nullptr) {
     MAT_TILES(c);
     MatFr rk1, rq1, rv1, rp1, rk2, rv2, rq2, rp2, rm1, rm2, rh1;
     MAT_NEXT(rk1, A_K1_W, A_K1_B); MAT_NEXT(rq1, A_Q1_W, A_Q1_B); MAT_NEXT(rv1, A_V1_W, A_V1_B);
-    narrow_fwd(W(A_ENC_W), Ain, nullptr, sXA, kMXS, aZ, wave, lane);                          // action_encoder.0 (no bias)
+    narrow_fwd(W(A_ENC_W), Ain, enc_bias, sXA, kMXS, aZ, wave, lane);                         // action_encoder.0 (Box: a bias)
     MAT_SYNC();
     tile_gelu(aZ, S0, tid);
     tile_ln_fwd(S0, kMHS, kMD, W(A_LN_G), W(A_LN_B), aN0, rstd(5), S1, tid);                  // x0 in S1
@@ -760,8 +772,10 @@ __device__ __forceinline__ void mat_decoder_forward(const Ctx& c, int tid, int w
 // slab form only: an input tile rebuilt for a weight gradient (and the barrier that settles it)
 #define MAT_SLAB_ONLY(stmt) do { if constexpr (!SPLIT) { stmt; } } while (0)
 // WIDE: the chunked observation front end (33 <= O <= kMOWide); the kernels of the two forms keep names of their own
-template <bool SPLIT, bool WIDE>
-__device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
+// U = MatBoxDev: the Box form (its branches are discarded from the Discrete kernels)
+template <bool SPLIT, bool WIDE, class U = MatDev>
+__device__ __forceinline__ void mat_update_fwd_bwd_body(const U u) {
+    constexpr bool BOX = std::is_same<U, MatBoxDev>::value;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = blockIdx.x;
     const float* P = u.params;
@@ -800,7 +814,7 @@ __device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
                 // per-epoch tables in shuffled order: entry `pos` belongs to perm[pos], so these loads depend on the cursor
                 // only and go out together with the perm load (instead of behind perm -> row_map: two cold round trips)
                 const long tok = pos * L + a;
-                const int a_raw = (int)u.actions[tok];
+                const int a_raw = BOX ? 0 : (int)u.actions[tok];
                 const float av_ = u.adv[tok], lpo_ = u.old_lp[tok], rt_ = u.rtg[tok];
                 if (p >= 0 && p < u.n_rows) {
                     row = u.row_map ? u.row_map[p] : (int)p;
@@ -810,7 +824,7 @@ __device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
             } else if (p >= 0 && p < u.n_rows) {
                 row = u.row_map ? u.row_map[p] : (int)p;
                 const long tok = (long)row * L + a;
-                act = (int)u.actions[tok];
+                act = BOX ? 0 : (int)u.actions[tok];
                 act = act < 0 ? 0 : (act >= NA ? NA - 1 : act);
                 av = u.adv[tok]; lpo = u.old_lp[tok]; rt = u.rtg[tok];
             }
@@ -845,6 +859,15 @@ __device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
         const long orow = u.pregathered ? mb * u.batch_stride + seq0 + s / L : (long)row;
         if (row >= 0) sYO[s * OS + i] = u.obs[(orow * L + (s % L)) * O + i];
     }
+    // Box: slot i sees the stored raw action of slot i - 1, slot 0 zeros; the rows' own actions behind the tiles
+    [[maybe_unused]] float* sRaw = c.T + (long)MAT_NUM_TILES * kMTile;
+    [[maybe_unused]] const float* enc_b = nullptr;
+    if constexpr (BOX) {
+        enc_b = P + u.off_enc_b;
+        mat_box_action_tiles(u.actions_f, [&](int s) -> long {
+            return (u.pregathered ? mb * u.batch_stride + seq0 + s / L : (long)sRow[s]) * L + s % L; },
+            sRow, n_rows, L, NA, kMXS, sXA, sRaw, tid);
+    } else
     if (tid < n_rows && sRow[tid] >= 0) {
         const int a = tid % L;
         if (a == 0) sXA[tid * kMXS] = 1.0f;
@@ -858,11 +881,11 @@ __device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
         const MatPanelPub pub{u.xpanel, (long)u.R * kMD, g, tid};
         mat_encoder_forward<true>(c, tid, wave, lane, pub, orow0);
         MAT_STAMP(3);
-        mat_decoder_forward<true>(c, tid, wave, lane, pub);
+        mat_decoder_forward<true>(c, tid, wave, lane, pub, enc_b);
     } else {
         mat_encoder_forward<true>(c, tid, wave, lane, MatNoPub(), orow0);
         MAT_STAMP(3);
-        mat_decoder_forward<true>(c, tid, wave, lane);
+        mat_decoder_forward<true>(c, tid, wave, lane, MatNoPub(), enc_b);
     }
     MAT_STAMP(4);
     // input-gradient (dgrad) fragment sets of the backward: each requested at the start of the phase before its use
@@ -873,7 +896,21 @@ __device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
     // wave 0: the categorical head of the 16 token rows, 4 lanes per row (lane (s4, q) owns classes q and q + 4: the
     // transcendental chain is 2 values long instead of 8, class reductions are quad permutes -- as K12's head);
     // wave 1: the value loss of the rows, at the same time.
-    if (wave == 0) {
+    if constexpr (BOX) {
+        if (wave == 0) {
+            const int s4 = lane >> 2;
+            const bool live4 = s4 < n_rows && sRow[s4] >= 0;
+            float av4 = 0.f, lpo4 = 0.f;
+            if (live4) {
+                av4 = sRowF[s4]; lpo4 = sRowF[16 + s4];
+                if (u.normalize_adv) av4 = (av4 - sMisc[0]) / (sMisc[1] + 1e-8f);
+            }
+            mat_box_head_wave0(sOutA, sRaw, P + u.off_log_std, u.min_std, NA, live4, av4, lpo4, u.surr_clip, u.entropy_weight,
+                               inv_n, sDOutA, slab + u.goff_log_std, u.loss_partials + (long)g * 8,
+                               g == 0 ? sMisc[0] : 0.f, g == 0 ? sMisc[1] : 0.f, lane);
+        }
+    }
+    if (!BOX && wave == 0) {
         const int s4 = lane >> 2, q = lane & 3;
         const bool live4 = s4 < n_rows && sRow[s4] >= 0;
         float av4 = 0.f, lpo4 = 0.f;
@@ -1023,7 +1060,11 @@ __device__ __forceinline__ void mat_update_fwd_bwd_body(const MatDev u) {
     tile_ln_bwd(S0, kMHS, kMD, aN0, rstd(5), W(A_LN_G), S1, G(A_LN_G), G(A_LN_B), tid);        // d gelu out -> S1
     tile_gelu_bwd(S1, aZ, tid);
     MAT_SYNC();
-    layer_wgrad<4, kMNW>(S1, sXA, kMXS, 1, Ain, G(A_ENC_W), Ain, nullptr, wave, lane, tid);
+    {
+        float* enc_gb = nullptr;                                        // Box: action_encoder.0.bias
+        if constexpr (BOX) enc_gb = slab + u.goff_enc_b;
+        layer_wgrad<4, kMNW>(S1, sXA, kMXS, 1, Ain, G(A_ENC_W), Ain, enc_gb, wave, lane, tid);
+    }
 
     MAT_STAMP(8);
     // =========================================== critic backward ===========================================
@@ -1119,6 +1160,11 @@ template <bool SPLIT>
 __global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_kernel(MatDev u) { mat_update_fwd_bwd_body<SPLIT, false>(u); }
 template <bool SPLIT>
 __global__ __launch_bounds__(kMT) void mat_update_fwd_bwd_wide_kernel(MatDev u) { mat_update_fwd_bwd_body<SPLIT, true>(u); }
+// the Box form runs on the split-wgrad chain only.  The Box kernels are compiled without the packed-float32 VALU forms
+// (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32); the attribute covers everything inlined into them
+#define PPOAF_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+__global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_update_fwd_bwd_kernel(MatBoxDev u) { mat_update_fwd_bwd_body<true, false>(u); }
+__global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_update_fwd_bwd_wide_kernel(MatBoxDev u) { mat_update_fwd_bwd_body<true, true>(u); }
 
 // ------------------------------------------------------------------------------------------------
 // K16: one rollout step of a MATPolicy for all envs of the rank (mat_policy.py:441-519,587-626,660-675):
@@ -1136,6 +1182,16 @@ struct MatStepDev {
     int64_t* action_out; int64_t* raw_action_out; float* logp_out; float* value_out;
     float* critic_obs_out; float* obs_out;
     const int64_t* forced_action;                  // NULL: sample; else [E, L] actions to log (replay)
+};
+
+// The Box form (mat_box.hpp): off[] holds the 63 shared tensors of the Box bucket, NA = Ain = the action dimensions, the
+// int64 action pointers are unused
+struct MatBoxStepDev : MatStepDev {
+    long off_enc_b, off_log_std;
+    float min_std;
+    const float* act_lo; const float* act_hi;      // [NA], or both NULL: the unit box
+    float* action_f; float* raw_action_f;          // [E, L, NA]
+    const float* forced_f;                         // NULL: sample; else [E, L, NA] raw actions to evaluate (replay)
 };
 
 // The block form (ppoaf_mat_policy_step_blocks): slot s of env e reads row e of block slot_agent[s] of `critic_obs` (and of
@@ -1165,8 +1221,11 @@ __device__ __forceinline__ T* mat_opaque(T* p) {
      : mat_opaque((a)[0]))
 static_assert(PPOAF_ROW_BLOCKS_MAX == 16, "mat_block spells out 16 entries");
 
-template <bool WIDE, bool BLK = false>
-__device__ __forceinline__ void mat_policy_step_body(const MatStepDev u, const MatStepBlocks* tbp = nullptr) {
+template <bool WIDE, bool BLK = false, class U = MatStepDev>
+__device__ __forceinline__ void mat_policy_step_body(const U u, const MatStepBlocks* tbp = nullptr) {
+    constexpr bool BOX = std::is_same<U, MatBoxStepDev>::value;
+    [[maybe_unused]] const float* enc_b = nullptr;
+    if constexpr (BOX) enc_b = u.params + u.off_enc_b;
     [[maybe_unused]] const MatStepBlocks& tb = *tbp;          // (the block form only)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long seq0 = (long)blockIdx.x * u.per_tile;
@@ -1204,7 +1263,7 @@ __device__ __forceinline__ void mat_policy_step_body(const MatStepDev u, const M
         const float* src = u.actor_obs ? u.actor_obs : u.obs;
         for (long idx = tid; idx < (long)n_rows * u.Oa; idx += kMT) u.obs_out[tok0 * u.Oa + idx] = src[tok0 * u.Oa + idx];
     }
-    if (tid < n_rows && tid % L == 0) sXA[tid * kMXS] = 1.0f;     // start token of agent 0 (mat_policy.py:325-333)
+    if (!BOX && tid < n_rows && tid % L == 0) sXA[tid * kMXS] = 1.0f;     // start token of agent 0 (mat_policy.py:325-333)
     MAT_SYNC();
     if constexpr (BLK) {
         const long tok = tok0 + (tid >> 4);
@@ -1221,7 +1280,17 @@ __device__ __forceinline__ void mat_policy_step_body(const MatStepDev u, const M
         u.value_out[tok0 + tid] = v;
     }
     for (int i = 0; i < L; ++i) {
-        mat_decoder_forward<false>(c, tid, wave, lane);           // ends with a barrier
+        mat_decoder_forward<false>(c, tid, wave, lane, MatNoPub(), enc_b);           // ends with a barrier
+        if constexpr (BOX) {
+            if (tid < n_rows && tid % L == i) {
+                float* env_row = nullptr;
+                if constexpr (BLK)
+                    env_row = reinterpret_cast<float*>(mat_block(tb.env_action, mat_slot_agent(tb, i))) + (tok0 + tid) / L * NA;
+                mat_box_step_row(sOutA + tid * 8, NA, u.params + u.off_log_std, u.min_std, u.act_lo, u.act_hi, u.forced_f,
+                                 tok0 + tid, u.seed, u.offset, u.raw_action_f, u.action_f, u.logp_out,
+                                 i + 1 < L ? sXA + (tid + 1) * kMXS : nullptr, env_row);
+            }
+        } else
         if (tid < n_rows && tid % L == i) {
             float p[8];
             float m = -INFINITY;
@@ -1270,6 +1339,14 @@ __global__ __launch_bounds__(kMT) void mat_policy_step_blocks_kernel(MatStepDev 
     mat_policy_step_body<false, true>(u, &tb);
 }
 __global__ __launch_bounds__(kMT) void mat_policy_step_blocks_wide_kernel(MatStepDev u, MatStepBlocks tb) {
+    mat_policy_step_body<true, true>(u, &tb);
+}
+__global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_policy_step_kernel(MatBoxStepDev u) { mat_policy_step_body<false>(u); }
+__global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_policy_step_wide_kernel(MatBoxStepDev u) { mat_policy_step_body<true>(u); }
+__global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_policy_step_blocks_kernel(MatBoxStepDev u, MatStepBlocks tb) {
+    mat_policy_step_body<false, true>(u, &tb);
+}
+__global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_policy_step_blocks_wide_kernel(MatBoxStepDev u, MatStepBlocks tb) {
     mat_policy_step_body<true, true>(u, &tb);
 }
 
@@ -1676,14 +1753,27 @@ static size_t mat_fwd_lds_bytes(int O) {
     return (256 + 2 * 128 + 272 + kRows * kMXS + mat_obs_lds_floats(O, 1) + kMatFwdTiles * (size_t)kMTile) * 4;
 }
 
-static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u) {
+// The Box bucket (mat_box.hpp): distribution.log_std [NA] first, then the Discrete list with the action encoder's
+// [64, NA + 1] weight read as weight [64, NA] + bias [64] -- the same floats, so every shared tensor sits pad4(NA) floats
+// behind its Discrete place.  want[]: the 63 shared tensors; returns the bucket's size
+static long mat_box_offset_table(long O, long NA, long* want, long* enc_bias, long* log_std) {
+    const long shift = (NA + 3) / 4 * 4;
+    const long total = mat_offset_table(O, NA, want) + shift;
+    for (int i = 0; i < MAT_NUM_PARAMS; ++i) want[i] += shift;
+    *log_std = 0;
+    *enc_bias = shift + kMD * NA;
+    return total;
+}
+
+// box: the Box form's args around `a` (NULL: the Discrete form)
+static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u, const ppoaf_mat_box_update_args_t* box = nullptr) {
     PPOAF_REQUIRE(a, "mat_update: null args");
     PPOAF_REQUIRE(a->embedding == kMD, "mat_update: embedding=%d (the fused kernel is built for 64)", a->embedding);
     PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16, "mat_update: num_agents=%d out of [1,16]", a->num_agents);
     PPOAF_REQUIRE(a->obs_dim >= 1 && a->obs_dim <= kMOWide, "mat_update: obs_dim=%d out of [1,%d]", a->obs_dim, kMOWide);
     PPOAF_REQUIRE(a->num_actions >= 1 && a->num_actions <= 8, "mat_update: num_actions=%d out of [1,8]", a->num_actions);
     PPOAF_REQUIRE(a->B >= 1 && a->batch_stride >= a->B, "mat_update: B=%ld stride=%ld", (long)a->B, (long)a->batch_stride);
-    PPOAF_REQUIRE(a->params && a->grads && a->slabs && a->critic_obs && a->raw_actions && a->advantages &&
+    PPOAF_REQUIRE(a->params && a->grads && a->slabs && a->critic_obs && (box ? box->raw_actions && !a->raw_actions : a->raw_actions != nullptr) && a->advantages &&
                       a->old_log_probs && a->rewards_to_go && a->values && a->perm && a->cursor && a->vn_mean &&
                       a->vn_var && a->vn_count && a->loss_partials && a->totals,
                   "mat_update: null pointer");
@@ -1691,11 +1781,19 @@ static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u) {
     PPOAF_REQUIRE(!a->normalize_adv || a->adv_records, "mat_update: adv_records missing");
     PPOAF_REQUIRE(a->bucket_total % 4 == 0 && ((uintptr_t)a->params & 15) == 0 && ((uintptr_t)a->grads & 15) == 0 &&
                       ((uintptr_t)a->slabs & 15) == 0, "mat_update: buckets must be 16-byte aligned");
-    const long Ain = a->num_actions + 1;
+    const long Ain = box ? a->num_actions : a->num_actions + 1;
     long want[MAT_NUM_PARAMS];
     {
-        const long off = mat_offset_table(a->obs_dim, a->num_actions, want);
+        long want_eb = 0, want_ls = 0;
+        const long off = box ? mat_box_offset_table(a->obs_dim, a->num_actions, want, &want_eb, &want_ls)
+                             : mat_offset_table(a->obs_dim, a->num_actions, want);
         PPOAF_REQUIRE(off == a->bucket_total, "mat_update: bucket_total=%ld, the topology needs %ld", (long)a->bucket_total, off);
+        if (box) {
+            PPOAF_REQUIRE(box->enc_bias_offset == want_eb && box->log_std_offset == want_ls,
+                          "mat_box_update: action encoder bias / log_std sit at %ld / %ld, expected %ld / %ld",
+                          (long)box->enc_bias_offset, (long)box->log_std_offset, want_eb, want_ls);
+            PPOAF_REQUIRE(box->min_std >= 0.f, "mat_box_update: min_std=%g", (double)box->min_std);
+        }
     }
     for (int i = 0; i < MAT_NUM_PARAMS; ++i) {
         PPOAF_REQUIRE(a->offsets[i] == want[i], "mat_update: parameter %d sits at %ld, expected %ld", i,
@@ -1738,8 +1836,10 @@ static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u) {
         u.dpanel = u.xpanel + (size_t)MAT_NUM_XPANELS * u.R * kMD;
         bool big[MAT_NUM_PARAMS] = {};
         for (int k = 0; k < kMatLin; ++k) { big[kMatLinW_host[k]] = true; big[kMatLinW_host[k] + 1] = true; }
-        long compact = 0;
-        bool in_run = false;
+        // (Box: the bucket opens with log_std, a small tensor ahead of the first run)
+        long compact = u.off[0];
+        bool in_run = compact > 0;
+        if (in_run) { u.seg_start[0] = 0; u.seg_dst[0] = 0; u.n_seg = 1; }
         for (int i = 0; i < MAT_NUM_PARAMS; ++i) {
             if (big[i]) { u.goff[i] = -1; in_run = false; continue; }
             if (!in_run) {
@@ -1817,12 +1917,10 @@ extern "C" int ppoaf_mat_update_tail_ctl_bytes(const ppoaf_mat_update_args_t* ar
     return PPOAF_OK;
 }
 
-extern "C" int ppoaf_mat_update_wgrad_adam(const ppoaf_mat_update_args_t* args, void* ctl, float* exp_avg, float* exp_avg_sq,
-                                           const float* lr, float beta1, float beta2, float eps, float grad_scale, float max_norm,
-                                           float* grad_norm_out, double wait_seconds, ppoaf_stream_t stream) {
-    MatDev u;
-    const int rc = make_mat(args, u);
-    if (rc) return rc;
+// the fused tail over a validated view (the Discrete form's, or the Box form's base)
+static int mat_wgrad_adam_launch(const MatDev& u, void* ctl, float* exp_avg, float* exp_avg_sq, const float* lr, float beta1,
+                                 float beta2, float eps, float grad_scale, float max_norm, float* grad_norm_out,
+                                 double wait_seconds, ppoaf_stream_t stream) {
     PPOAF_REQUIRE(u.split, "mat_update_wgrad_adam: args->split_workspace is not set (the tail of the split-wgrad chain)");
     PPOAF_REQUIRE(u.fuse_norm, "mat_update_wgrad_adam: args->fuse_norm must be set (the launch owns the step counter)");
     PPOAF_REQUIRE(ctl && (((uintptr_t)ctl) & 63) == 0, "mat_update_wgrad_adam: control block missing or not 64-byte aligned");
@@ -1845,6 +1943,16 @@ extern "C" int ppoaf_mat_update_wgrad_adam(const ppoaf_mat_update_args_t* args, 
     return check_launch("mat_update_wgrad_adam");
 }
 
+extern "C" int ppoaf_mat_update_wgrad_adam(const ppoaf_mat_update_args_t* args, void* ctl, float* exp_avg, float* exp_avg_sq,
+                                           const float* lr, float beta1, float beta2, float eps, float grad_scale, float max_norm,
+                                           float* grad_norm_out, double wait_seconds, ppoaf_stream_t stream) {
+    MatDev u;
+    const int rc = make_mat(args, u);
+    if (rc) return rc;
+    return mat_wgrad_adam_launch(u, ctl, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, grad_scale, max_norm, grad_norm_out,
+                                 wait_seconds, stream);
+}
+
 extern "C" int ppoaf_mat_update_split_workspace_bytes(const ppoaf_mat_update_args_t* args, int64_t* bytes_out) {
     PPOAF_REQUIRE(args && bytes_out, "mat_update_split_workspace_bytes: null argument");
     ppoaf_mat_update_args_t a = *args;
@@ -1863,20 +1971,34 @@ extern "C" int ppoaf_mat_update_norm_partials(const ppoaf_mat_update_args_t* arg
     return (int)(((u.total >> 2) + kMatRedThreads - 1) / kMatRedThreads);
 }
 
-// validates `a`, fills the device view, launches the plain form (tb == NULL) or the block form
-static int mat_policy_step_launch(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb, ppoaf_stream_t stream) {
+// validates `a` and fills the device view (tb: the block form; box: the Box form's args around `a`, NULL for Discrete)
+static int mat_step_dev(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb, const ppoaf_mat_box_step_args_t* box, MatStepDev& u) {
     PPOAF_REQUIRE(a->embedding == kMD, "mat_policy_step: embedding=%d (built for 64)", a->embedding);
     PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= kMOWide &&
                       a->num_actions >= 1 && a->num_actions <= 8 && a->actor_obs_dim >= 1,
                   "mat_policy_step: sizes (agents %d, obs %d, actions %d) outside the kernel's limits (16, %d, 8)", a->num_agents,
                   a->obs_dim, a->num_actions, kMOWide);
     PPOAF_REQUIRE(a->E >= 1, "mat_policy_step: E=%ld", (long)a->E);
-    PPOAF_REQUIRE(a->params && (tb || a->critic_obs) && a->action_out && a->logp_out && a->value_out, "mat_policy_step: null pointer");
+    PPOAF_REQUIRE(a->params && (tb || a->critic_obs) && (box ? box->action_out && box->raw_action_out : a->action_out != nullptr) &&
+                      a->logp_out && a->value_out, "mat_policy_step: null pointer");
+    if (box) {
+        PPOAF_REQUIRE(!a->action_out && !a->raw_action_out && !a->forced_action,
+                      "mat_box_policy_step: the int64 action pointers must be NULL (the float tables take their place)");
+        PPOAF_REQUIRE((box->act_lo == nullptr) == (box->act_hi == nullptr), "mat_box_policy_step: give both bounds or neither");
+        PPOAF_REQUIRE(box->min_std >= 0.f, "mat_box_policy_step: min_std=%g", (double)box->min_std);
+        long want[MAT_NUM_PARAMS], want_eb = 0, want_ls = 0;
+        mat_box_offset_table(a->obs_dim, a->num_actions, want, &want_eb, &want_ls);
+        for (int i = 0; i < MAT_NUM_PARAMS; ++i)
+            PPOAF_REQUIRE(a->offsets[i] == want[i], "mat_box_policy_step: parameter %d sits at %ld, expected %ld", i,
+                          (long)a->offsets[i], want[i]);
+        PPOAF_REQUIRE(box->enc_bias_offset == want_eb && box->log_std_offset == want_ls,
+                      "mat_box_policy_step: action encoder bias / log_std sit at %ld / %ld, expected %ld / %ld",
+                      (long)box->enc_bias_offset, (long)box->log_std_offset, want_eb, want_ls);
+    }
     PPOAF_REQUIRE(!a->normalize_values || (a->vn_mean && a->vn_var), "mat_policy_step: value normaliser statistics missing");
     PPOAF_REQUIRE(((uintptr_t)a->params & 15) == 0, "mat_policy_step: params must be 16-byte aligned");
-    MatStepDev u;
     for (int i = 0; i < 64; ++i) u.off[i] = a->offsets[i];
-    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = a->num_actions + 1;
+    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = box ? a->num_actions : a->num_actions + 1;
     u.per_tile = 16 / u.L; u.Oa = a->actor_obs_dim;
     u.params = a->params; u.obs = a->critic_obs; u.actor_obs = a->actor_obs; u.E = a->E;
     u.seed = a->seed; u.offset = a->offset;
@@ -1884,8 +2006,18 @@ static int mat_policy_step_launch(const ppoaf_mat_step_args_t* a, const MatStepB
     u.action_out = a->action_out; u.raw_action_out = a->raw_action_out; u.logp_out = a->logp_out;
     u.value_out = a->value_out; u.critic_obs_out = a->critic_obs_copy_out; u.obs_out = a->obs_copy_out;
     u.forced_action = a->forced_action;
+    if (tb) { u.obs = nullptr; u.actor_obs = nullptr; }
+    PPOAF_REQUIRE(mat_lds_bytes(u.O) <= 160 * 1024, "mat_policy_step: needs %zu B of LDS (> 160 KiB)", mat_lds_bytes(u.O));
+    PPOAF_REQUIRE((a->E + u.per_tile - 1) / u.per_tile <= 0x7fffffffL, "mat_policy_step: too many envs");
+    return PPOAF_OK;
+}
+
+// launches the plain form (tb == NULL) or the block form
+static int mat_policy_step_launch(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb, ppoaf_stream_t stream) {
+    MatStepDev u;
+    const int rc = mat_step_dev(a, tb, nullptr, u);
+    if (rc) return rc;
     const size_t lds = mat_lds_bytes(u.O);
-    PPOAF_REQUIRE(lds <= 160 * 1024, "mat_policy_step: needs %zu B of LDS (> 160 KiB)", lds);
     static void (*const kern[2])(MatStepDev) = {mat_policy_step_kernel, mat_policy_step_wide_kernel};
     static bool attr_set = false;
     if (!attr_set) {
@@ -1897,7 +2029,6 @@ static int mat_policy_step_launch(const ppoaf_mat_step_args_t* a, const MatStepB
         attr_set = true;
     }
     const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
-    PPOAF_REQUIRE(n_wg <= 0x7fffffffL, "mat_policy_step: too many envs");
     if (tb) {
         static void (*const kern_b[2])(MatStepDev, MatStepBlocks) = {mat_policy_step_blocks_kernel, mat_policy_step_blocks_wide_kernel};
         static bool attr_b = false;
@@ -1909,7 +2040,6 @@ static int mat_policy_step_launch(const ppoaf_mat_step_args_t* a, const MatStepB
             }
             attr_b = true;
         }
-        u.obs = nullptr; u.actor_obs = nullptr;
         hipLaunchKernelGGL(kern_b[mat_is_wide(u.O) ? 1 : 0], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u, *tb);
         return check_launch("mat_policy_step_blocks");
     }
@@ -1922,15 +2052,14 @@ extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_strea
     return mat_policy_step_launch(a, nullptr, stream);
 }
 
-extern "C" int ppoaf_mat_policy_step_blocks(const ppoaf_mat_step_args_t* a, const ppoaf_mat_step_blocks_t* t,
-                                            ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a && t, "mat_policy_step_blocks: null args");
+// the block table of either form (they differ in the element type of env_action) -> the kernels' table
+template <class Table>
+static int mat_step_blocks_dev(const ppoaf_mat_step_args_t* a, const Table* t, MatStepBlocks& tb) {
     PPOAF_REQUIRE(t->n_blocks >= 1 && t->n_blocks <= PPOAF_ROW_BLOCKS_MAX, "mat_policy_step_blocks: n_blocks=%d not in [1, %d]",
                   t->n_blocks, PPOAF_ROW_BLOCKS_MAX);
     PPOAF_REQUIRE(t->n_blocks == a->num_agents, "mat_policy_step_blocks: n_blocks=%d, the policy has %d agents", t->n_blocks,
                   a->num_agents);
     PPOAF_REQUIRE(a->E >= 0, "mat_policy_step_blocks: E=%ld must be >= 0", (long)a->E);
-    MatStepBlocks tb;
     tb.slots[0] = tb.slots[1] = 0;
     unsigned seen = 0;
     for (int b = 0; b < PPOAF_ROW_BLOCKS_MAX; ++b) {
@@ -1948,9 +2077,18 @@ extern "C" int ppoaf_mat_policy_step_blocks(const ppoaf_mat_step_args_t* a, cons
         }
         tb.critic_obs[b] = in ? t->critic_obs[b] : nullptr;
         tb.actor_obs[b] = in ? t->actor_obs[b] : nullptr;
-        tb.env_action[b] = in ? t->env_action[b] : nullptr;
+        tb.env_action[b] = in ? reinterpret_cast<int64_t*>(t->env_action[b]) : nullptr;
         if (in) tb.slots[b >> 3] |= (unsigned long long)t->slot_agent[b] << (8 * (b & 7));
     }
+    return PPOAF_OK;
+}
+
+extern "C" int ppoaf_mat_policy_step_blocks(const ppoaf_mat_step_args_t* a, const ppoaf_mat_step_blocks_t* t,
+                                            ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a && t, "mat_policy_step_blocks: null args");
+    MatStepBlocks tb;
+    const int rc = mat_step_blocks_dev(a, t, tb);
+    if (rc) return rc;
     if (a->E == 0) return PPOAF_OK;
     return mat_policy_step_launch(a, &tb, stream);
 }
@@ -2059,6 +2197,155 @@ extern "C" int ppoaf_mat_update_chain_allreduce(const ppoaf_mat_update_args_t* a
     }
     return PPOAF_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Box form: entry points (the kernels are the bodies above with U = MatBoxDev / MatBoxStepDev; the reduce and tail
+// launches are the Discrete kernels over the Box bucket's offset table and compact-slab layout)
+// ------------------------------------------------------------------------------------------------
+namespace ppoaf {
+// the rows' own raw actions [16][8] sit behind the 34 activation tiles
+static size_t mat_box_lds_bytes(int O) { return mat_lds_bytes(O) + kRows * 8 * 4; }
+
+static int make_mat_box(const ppoaf_mat_box_update_args_t* a, MatBoxDev& u, bool need_split = true) {
+    PPOAF_REQUIRE(a, "mat_box_update: null args");
+    const int rc = make_mat(&a->mat, u, a);
+    if (rc) return rc;
+    PPOAF_REQUIRE(!need_split || u.split, "mat_box_update: the Box form runs on the split-wgrad chain only (split_workspace is not set)");
+    u.actions = nullptr;
+    u.actions_f = a->raw_actions;
+    u.off_enc_b = a->enc_bias_offset; u.off_log_std = a->log_std_offset;
+    u.goff_enc_b = (int)a->enc_bias_offset; u.goff_log_std = (int)a->log_std_offset;   // the first run of the compact slab is the bucket's head
+    u.min_std = a->min_std;
+    return PPOAF_OK;
+}
+}  // namespace ppoaf
+
+extern "C" int ppoaf_mat_box_update_fwd_bwd(const ppoaf_mat_box_update_args_t* args, ppoaf_stream_t stream) {
+    MatBoxDev u;
+    const int rc = make_mat_box(args, u);
+    if (rc) return rc;
+    const size_t lds = mat_box_lds_bytes(u.O);
+    PPOAF_REQUIRE(lds <= 160 * 1024, "mat_box_update: needs %zu B of LDS (> 160 KiB)", lds);
+    static void (*const kern[2])(MatBoxDev) = {mat_box_update_fwd_bwd_kernel, mat_box_update_fwd_bwd_wide_kernel};
+    static bool attr_set = false;
+    if (!attr_set) {
+        for (int i = 0; i < 2; ++i) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern[i]),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+        }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kern[mat_is_wide(u.O) ? 1 : 0], dim3((unsigned)u.nT), dim3(kMT), lds, (hipStream_t)stream, u);
+    return check_launch("mat_box_update_fwd_bwd");
+}
+
+extern "C" int ppoaf_mat_box_update_reduce(const ppoaf_mat_box_update_args_t* args, ppoaf_stream_t stream) {
+    MatBoxDev u;
+    const int rc = make_mat_box(args, u);
+    if (rc) return rc;
+    const int nsb = (4 * u.n_small4 + 255) / 256;
+    hipLaunchKernelGGL(mat_update_wgrad_kernel, dim3((unsigned)(kMatWgJobs + nsb + 1)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const MatDev&>(u), nsb);
+    return check_launch("mat_box_update_reduce (wgrad)");
+}
+
+extern "C" int ppoaf_mat_box_update_split_workspace_bytes(const ppoaf_mat_box_update_args_t* args, int64_t* bytes_out) {
+    PPOAF_REQUIRE(args && bytes_out, "mat_box_update_split_workspace_bytes: null argument");
+    ppoaf_mat_box_update_args_t a = *args;
+    a.mat.split_workspace = nullptr; a.mat.split_workspace_bytes = 0;
+    MatBoxDev u;
+    const int rc = make_mat_box(&a, u, false);
+    if (rc) return rc;
+    *bytes_out = (int64_t)((size_t)(MAT_NUM_XPANELS + kMatLin) * u.R * kMD * 4);
+    return PPOAF_OK;
+}
+
+extern "C" int ppoaf_mat_box_update_tail_ctl_bytes(const ppoaf_mat_box_update_args_t* args, int64_t* bytes_out) {
+    PPOAF_REQUIRE(args && bytes_out, "mat_box_update_tail_ctl_bytes: null argument");
+    MatBoxDev u;
+    const int rc = make_mat_box(args, u);
+    if (rc) return rc;
+    *bytes_out = (int64_t)kTailRecOff + 16 * (int64_t)(kMatWgJobs + (4 * u.n_small4 + 255) / 256);
+    return PPOAF_OK;
+}
+
+extern "C" int ppoaf_mat_box_update_norm_partials(const ppoaf_mat_box_update_args_t* args) {
+    MatBoxDev u;
+    if (make_mat_box(args, u)) return -1;
+    return kMatWgJobs + (4 * u.n_small4 + 255) / 256;
+}
+
+extern "C" int ppoaf_mat_box_update_wgrad_adam(const ppoaf_mat_box_update_args_t* args, void* ctl, float* exp_avg, float* exp_avg_sq,
+                                               const float* lr, float beta1, float beta2, float eps, float grad_scale,
+                                               float max_norm, float* grad_norm_out, double wait_seconds, ppoaf_stream_t stream) {
+    MatBoxDev u;
+    const int rc = make_mat_box(args, u);
+    if (rc) return rc;
+    return mat_wgrad_adam_launch(u, ctl, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, grad_scale, max_norm, grad_norm_out,
+                                 wait_seconds, stream);
+}
+
+static int mat_box_policy_step_launch(const ppoaf_mat_box_step_args_t* a, const MatStepBlocks* tb, ppoaf_stream_t stream) {
+    MatBoxStepDev u;
+    const int rc = mat_step_dev(&a->mat, tb, a, u);
+    if (rc) return rc;
+    u.action_out = nullptr; u.raw_action_out = nullptr; u.forced_action = nullptr;
+    u.off_enc_b = a->enc_bias_offset; u.off_log_std = a->log_std_offset; u.min_std = a->min_std;
+    u.act_lo = a->act_lo; u.act_hi = a->act_hi;
+    u.action_f = a->action_out; u.raw_action_f = a->raw_action_out; u.forced_f = a->forced_action;
+    const size_t lds = mat_lds_bytes(u.O);
+    static void (*const kern[2])(MatBoxStepDev) = {mat_box_policy_step_kernel, mat_box_policy_step_wide_kernel};
+    static void (*const kern_b[2])(MatBoxStepDev, MatStepBlocks) = {mat_box_policy_step_blocks_kernel, mat_box_policy_step_blocks_wide_kernel};
+    static bool attr_set = false;
+    if (!attr_set) {
+        for (int i = 0; i < 4; ++i) {
+            const void* fn = i < 2 ? reinterpret_cast<const void*>(kern[i]) : reinterpret_cast<const void*>(kern_b[i - 2]);
+            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+        }
+        attr_set = true;
+    }
+    const unsigned n_wg = (unsigned)((a->mat.E + u.per_tile - 1) / u.per_tile);
+    const int wide = mat_is_wide(u.O) ? 1 : 0;
+    if (tb) hipLaunchKernelGGL(kern_b[wide], dim3(n_wg), dim3(kMT), lds, (hipStream_t)stream, u, *tb);
+    else hipLaunchKernelGGL(kern[wide], dim3(n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
+    return check_launch(tb ? "mat_box_policy_step_blocks" : "mat_box_policy_step");
+}
+
+extern "C" int ppoaf_mat_box_policy_step(const ppoaf_mat_box_step_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_box_policy_step: null args");
+    return mat_box_policy_step_launch(a, nullptr, stream);
+}
+
+extern "C" int ppoaf_mat_box_policy_step_blocks(const ppoaf_mat_box_step_args_t* a, const ppoaf_mat_box_step_blocks_t* t,
+                                                ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a && t, "mat_box_policy_step_blocks: null args");
+    MatStepBlocks tb;
+    const int rc = mat_step_blocks_dev(&a->mat, t, tb);
+    if (rc) return rc;
+    if (a->mat.E == 0) return PPOAF_OK;
+    return mat_box_policy_step_launch(a, &tb, stream);
+}
+
+PPOAF_LAYOUT(ppoaf_mat_box_update_args_t, mat, 0);
+PPOAF_LAYOUT(ppoaf_mat_box_update_args_t, raw_actions, sizeof(ppoaf_mat_update_args_t));
+PPOAF_LAYOUT(ppoaf_mat_box_update_args_t, enc_bias_offset, sizeof(ppoaf_mat_update_args_t) + 8);
+PPOAF_LAYOUT(ppoaf_mat_box_update_args_t, log_std_offset, sizeof(ppoaf_mat_update_args_t) + 16);
+PPOAF_LAYOUT(ppoaf_mat_box_update_args_t, min_std, sizeof(ppoaf_mat_update_args_t) + 24);
+static_assert(sizeof(ppoaf_mat_box_update_args_t) == sizeof(ppoaf_mat_update_args_t) + 32, "ppoaf_mat_box_update_args_t");
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, mat, 0);
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, enc_bias_offset, sizeof(ppoaf_mat_step_args_t));
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, log_std_offset, sizeof(ppoaf_mat_step_args_t) + 8);
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, min_std, sizeof(ppoaf_mat_step_args_t) + 16);
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, act_lo, sizeof(ppoaf_mat_step_args_t) + 24);
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, act_hi, sizeof(ppoaf_mat_step_args_t) + 32);
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, action_out, sizeof(ppoaf_mat_step_args_t) + 40);
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, raw_action_out, sizeof(ppoaf_mat_step_args_t) + 48);
+PPOAF_LAYOUT(ppoaf_mat_box_step_args_t, forced_action, sizeof(ppoaf_mat_step_args_t) + 56);
+static_assert(sizeof(ppoaf_mat_box_step_args_t) == sizeof(ppoaf_mat_step_args_t) + 64, "ppoaf_mat_box_step_args_t");
+PPOAF_LAYOUT(ppoaf_mat_box_step_blocks_t, env_action, 328);
+static_assert(sizeof(ppoaf_mat_box_step_blocks_t) == 456, "ppoaf_mat_box_step_blocks_t");
 
 #ifdef PPOAF_MAT_STAMPS
 extern "C" int ppoaf_debug_read_mat_stamps(unsigned long long* out /* host [64] */) {

@@ -530,13 +530,14 @@ def _loss_signature(upd):
 
 def _chunk_with_offsets(upd, args, n):
     """n consecutive mini-batches with their index baked in: one cursor update for the whole chain."""
+    inner = getattr(args, "mat", args)                  # (K15's Box form wraps the args that carry the cursor fields)
     try:
         for j in range(n):
-            args.mb_offset = j
-            args.cursor_advance = n if j == n - 1 else 0
+            inner.mb_offset = j
+            inner.cursor_advance = n if j == n - 1 else 0
             upd._one(args)
     finally:
-        args.mb_offset, args.cursor_advance = 0, 1
+        inner.mb_offset, inner.cursor_advance = 0, 1
 
 
 # the fused tail launch of K12 and K15 (the same control-block layout: csrc/tail_sync.hpp TailCtl)
@@ -1766,13 +1767,23 @@ MAT_MAX_OBS = 128
 MAT_INFER_MAX_OBS = 64
 
 
-def _describe_mat(pol):
-    """Topology + offset table of a MATPolicy's actor_critic for K15, or (None, reason)."""
+# the Box form's bucket (csrc/mat_box.hpp): the distribution's log_std leads, the action encoder has a bias
+_MAT_BOX_PARAM_NAMES = (["actor.distribution.log_std", "actor.action_encoder.0.weight", "actor.action_encoder.0.bias"]
+                        + _MAT_PARAM_NAMES[1:])
+
+
+def _describe_mat(pol, box_actions=None):
+    """Topology + offset table of a MATPolicy's actor_critic for K15, or (None, reason).  A Box policy is described
+    (topo["box"]: the Box entry points take it) only with the opt-in `fused_mat_box_actions` -- MATPolicy's own attribute,
+    read here and nowhere else; box_actions: the answer to ask under instead (a hypothetical never writes to the policy)."""
     from .networks.multi_agent_transformer import MATActorCritic
     ac = getattr(pol, "actor_critic", None)
     if not isinstance(ac, MATActorCritic):
         return None, "not a MATActorCritic"
-    if pol.action_dtype != "discrete":
+    if box_actions is None:
+        box_actions = bool(getattr(pol, "fused_mat_box_actions", False))
+    box = pol.action_dtype == "continuous" and box_actions
+    if pol.action_dtype != "discrete" and not box:
         return None, "the fused MAT update covers Discrete actions"
     D = ac.actor.embedding_size
     if D != 64 or ac.critic.embedding_size != 64:
@@ -1787,23 +1798,42 @@ def _describe_mat(pol):
     if others or any(getattr(m, "approximate", "none") != "none" for m in gelus):
         return None, "activations other than exact GELU"
     named = list(ac.named_parameters())
-    if [n for n, _ in named] != _MAT_PARAM_NAMES:
+    if [n for n, _ in named] != (_MAT_BOX_PARAM_NAMES if box else _MAT_PARAM_NAMES):
         return None, "parameter list differs from the default MATActorCritic"
     NA, O, A = ac.actor.action_pred_size, ac.critic.in_size, ac.actor.num_agents
     if not (1 <= NA <= 8 and 1 <= O <= MAT_MAX_OBS and 1 <= A <= 16):
         return None, f"sizes (actions {NA}, obs {O}, agents {A}) outside the fused kernel's limits (8, {MAT_MAX_OBS}, 16)"
-    if ac.actor.action_encoder[0].in_features != NA + 1 or ac.actor.action_encoder[0].bias is not None:
+    enc = ac.actor.action_encoder[0]
+    if box:
+        if enc.in_features != NA or enc.bias is None or not isinstance(ac.actor.distribution, GaussianDistribution):
+            return None, "action encoder / distribution are not the Box (previous actions, bias, tanh-Gaussian) form"
+        if mpi_utils.get_num_procs() > 1:
+            return None, "N > 1 ranks: the Box form of the fused MAT kernels runs on a single rank"
+    elif enc.in_features != NA + 1 or enc.bias is not None:
         return None, "action encoder is not the Discrete (start token + one-hot, no bias) form"
     base = ac.flat_params.data_ptr()
-    offs, off = [], 0
-    for _, p in named:
+    offs, off = {}, 0
+    for n, p in named:
         if (p.data_ptr() - base) // 4 != off:
             return None, "parameter layout differs from the kernel's table"
-        offs.append(off)
+        offs[n] = off
         off += (p.numel() + 3) // 4 * 4
     if off != ac.flat_params.numel():
         return None, "bucket holds parameters the fused kernel does not know about"
-    return dict(obs_dim=O, num_agents=A, num_actions=NA, embedding=64, offsets=offs, bucket_total=off), ""
+    topo = dict(obs_dim=O, num_agents=A, num_actions=NA, embedding=64, offsets=[offs[n] for n in _MAT_PARAM_NAMES],
+                bucket_total=off, box=box)
+    if box:       # the two tensors only the Box form has, and the head's constants
+        dist = ac.actor.distribution
+        topo.update(enc_bias_offset=offs["actor.action_encoder.0.bias"], log_std_offset=offs["actor.distribution.log_std"],
+                    min_std=dist.min_std)
+    return topo, ""
+
+
+def mat_box_hint(pol):
+    """What `verbose` adds to the refusal of a MAT policy that `fused_mat_box_actions` alone would take."""
+    if _describe_mat(pol)[0] is None and _describe_mat(pol, box_actions=True)[0] is not None:
+        return "; MATPolicy.fused_mat_box_actions = True would take it on the fused kernels"
+    return ""
 
 
 class FusedMatUpdate(FusedEpoch):
@@ -1827,6 +1857,10 @@ class FusedMatUpdate(FusedEpoch):
         pol = self.pol
         dev = pol.device
         self.topo, _ = _describe_mat(pol)
+        self.box = bool(self.topo.get("box"))
+        self._fn = "ppoaf_mat_box_update_" if self.box else "ppoaf_mat_update_"       # the entry points of the form
+        if self.box:
+            self._tail_ctl_bytes = "mat_box_update_tail_ctl_bytes"
         self.per_tile = 16 // self.topo["num_agents"]
         self.n_wg = (self.B + self.per_tile - 1) // self.per_tile
         total = self.topo["bucket_total"]
@@ -1838,11 +1872,21 @@ class FusedMatUpdate(FusedEpoch):
         # entry point keeps its contract (slabs / panels -> gradient bucket), so every path above it -- graphs, K17, the
         # RCCL loops -- is the same with either form.
         self.split = split_wgrad_mode() != "0"
+        if self.box and not self.split:
+            raise _lib.PpoafError("PPOAF_SPLIT_WGRAD=0: the Box form of K15 runs on the split-wgrad chain only")
         self._norm_partials = {}
+
+    def description(self):
+        """One line for `verbose`: the form and the chain a mini-batch runs."""
+        t = self.topo
+        form = f"Box({t['num_actions']}) tanh-Gaussian form (fused_mat_box_actions)" if self.box else f"Discrete({t['num_actions']}) form"
+        chain = "fwd_bwd -> wgrad_adam" if self.tail_reason() == "" else "fwd_bwd -> reduce -> adam_step_prenormed"
+        return f"K15 (FusedMatUpdate), {form}, {t['num_agents']} agents, obs {t['obs_dim']}: {chain}"
 
     def _make_args(self, B):
         pol, ppo, buf = self.pol, self.ppo, self.pol.buffer
-        a = _lib.MatUpdateArgs()
+        full = _lib.MatBoxUpdateArgs() if self.box else _lib.MatUpdateArgs()
+        a = full.mat if self.box else full             # (a view: writes land in `full`)
         t = self.topo
         a.obs_dim, a.num_agents, a.num_actions, a.embedding = t["obs_dim"], t["num_agents"], t["num_actions"], 64
         for i, o in enumerate(t["offsets"]):
@@ -1852,6 +1896,9 @@ class FusedMatUpdate(FusedEpoch):
         a.params, a.grads, a.slabs = ac.flat_params.data_ptr(), ac.flat_grads.data_ptr(), self.slabs.data_ptr()
         a.perm, a.row_map = self.perm.data_ptr(), buf.row_map.data_ptr()
         _loss_args(self, a, B)
+        if self.box:                                   # the float action table takes the int64 one's place
+            full.raw_actions, a.raw_actions = a.raw_actions, None
+            full.enc_bias_offset, full.log_std_offset, full.min_std = t["enc_bias_offset"], t["log_std_offset"], t["min_std"]
         opt = pol.actor_critic_optim
         a.norm_scratch, a.step_count = opt.norm_scratch.data_ptr(), opt.step_count.data_ptr()
         # the reduce launch also advances the step count and yields the local ||g||^2 (replaced by K17's norm of the
@@ -1861,17 +1908,17 @@ class FusedMatUpdate(FusedEpoch):
         if self.split:
             if self._split_space is None:                # sized once, for the full batch size (a tail mini-batch needs less)
                 need = C.c_int64(0)
-                _lib.check(self._lib.ppoaf_mat_update_split_workspace_bytes(C.byref(a), C.byref(need)), "mat_update_split_workspace_bytes")
+                _lib.check(getattr(self._lib, self._fn + "split_workspace_bytes")(C.byref(full), C.byref(need)), "mat_update_split_workspace_bytes")
                 self._split_space = torch.zeros(int(need.value), dtype=torch.uint8, device=pol.device)
             a.split_workspace, a.split_workspace_bytes = self._split_space.data_ptr(), self._split_space.numel()
-        n = int(self._lib.ppoaf_mat_update_norm_partials(C.byref(a)))
+        n = int(getattr(self._lib, self._fn + "norm_partials")(C.byref(full)))
         if n < 0:
             _lib.check(n, "mat_update_norm_partials")
         self._norm_partials[B] = n
         if opt.norm_scratch.numel() < 2 + n:             # one squared-norm partial per workgroup of the reduce launch
             opt.norm_scratch = torch.zeros(2 + n, dtype=torch.float64, device=pol.device)
             a.norm_scratch = opt.norm_scratch.data_ptr()
-        return a
+        return full
 
     def _signature(self):
         buf = self.pol.buffer
@@ -1942,10 +1989,10 @@ class FusedMatUpdate(FusedEpoch):
 
     def _one(self, args):
         lib, st, ref = self._lib, K.stream(), C.byref(args)
-        rc = lib.ppoaf_mat_update_fwd_bwd(ref, st)
+        rc = getattr(lib, self._fn + "fwd_bwd")(ref, st)
         if rc == 0 and self.tail_reason() == "":
             opt, clip = self.pol.actor_critic_optim, self.pol.gradient_clip
-            rc = lib.ppoaf_mat_update_wgrad_adam(
+            rc = getattr(lib, self._fn + "wgrad_adam")(
                 ref, self._tail_ctl_ptr(args), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr(), opt.lr.data_ptr(), opt.betas[0],
                 opt.betas[1], opt.eps, 1.0, float(clip) if clip is not None else 0.0, opt.grad_norm.data_ptr(),
                 self.tail_wait_seconds, st)
@@ -1954,7 +2001,7 @@ class FusedMatUpdate(FusedEpoch):
                 _lib.check(rc, "mat_update_wgrad_adam")
             return
         if rc == 0:
-            rc = lib.ppoaf_mat_update_reduce(ref, st)
+            rc = getattr(lib, self._fn + "reduce")(ref, st)
         if rc != 0:
             _lib.check(rc, "mat_update")
         if self.multi and self.xchg is None:

@@ -26,6 +26,12 @@ from .ppo_policy import FlatAdam, PPOPolicy
 
 class MATPolicy(PPOPolicy):
 
+    # Opt-in: a team over Box (tanh-Gaussian) actions on the fused rollout step K16 and update K15 (csrc/mat_box.hpp), single
+    # rank.  Set by hand, on the class or on the policy, before the first rollout -- no update_mode sets it.  False: such a
+    # team keeps the torch path.  Evaluation (K20) keeps the module decode either way.  (MATPolicy's own switch, read by
+    # fused_update._describe_mat: the FusedOptIns value holds the opt-ins of the feed-forward and ICM describers.)
+    fused_mat_box_actions = False
+
     def __init__(self, ac_network=MATActorCritic, mat_kw_args={}, use_huber_loss=True, **kw_args):
         super().__init__(ac_network=ac_network, mat_kw_args=mat_kw_args, use_huber_loss=use_huber_loss, **kw_args)
         self.agent_grouping = True
@@ -153,6 +159,8 @@ class MATPolicy(PPOPolicy):
         self._t = 0
         self.dataset.attach(self.buffer, self.gamma, self.lambd, self.get_bs_clip_range(None), self.use_gae)
 
+    box_step_launches = 0      # K16 launches of the Box form, over all policies (tests, verbose)
+
     def fused_step_unsupported_reason(self):
         """'' when the K16 rollout-step kernel covers this policy (same coverage as the fused update K15)."""
         from ..fused_update import _describe_mat
@@ -182,7 +190,12 @@ class MATPolicy(PPOPolicy):
             topo, why = _describe_mat(self)
             if topo is None:
                 raise _lib.PpoafError(f"mat rollout_step: {why}")
-            a = _lib.MatStepArgs()
+            self._step_box = box = _lib.MatBoxStepArgs() if topo["box"] else None
+            a = box.mat if box is not None else _lib.MatStepArgs()         # (a view: writes land in `box`)
+            if box is not None:
+                box.enc_bias_offset, box.log_std_offset, box.min_std = topo["enc_bias_offset"], topo["log_std_offset"], topo["min_std"]
+                lo, hi = self.actor.distribution.bound_tensors()
+                box.act_lo, box.act_hi = (None, None) if lo is None else (lo.data_ptr(), hi.data_ptr())
             a.obs_dim, a.num_agents, a.num_actions, a.embedding = topo["obs_dim"], topo["num_agents"], topo["num_actions"], 64
             for i, o in enumerate(topo["offsets"]):
                 a.offsets[i] = o
@@ -190,13 +203,14 @@ class MATPolicy(PPOPolicy):
             a.E = E
             a.actor_obs_dim = int(buf.observations.shape[-1])
             self._step_args = a
+        box = self._step_box
         if blocks is not None:
             why = self.step_blocks_unsupported_reason(*blocks)
             if why:
                 raise _lib.PpoafError(f"mat rollout_step: {why}")
             tb = getattr(self, "_step_blocks", None)
             if tb is None:
-                tb = self._step_blocks = _lib.MatStepBlocks()
+                tb = self._step_blocks = _lib.MatStepBlocks() if box is None else _lib.MatBoxStepBlocks()
             tb.n_blocks = A
             for s_, b in enumerate(self.agent_slot_order()):
                 tb.slot_agent[s_] = int(b)
@@ -212,7 +226,16 @@ class MATPolicy(PPOPolicy):
             a.critic_obs, a.actor_obs = critic_obs.data_ptr(), actor_obs.data_ptr()
         a.seed, a.offset = self.actor.distribution.rng.take(E * A)
         a.forced_action = None
-        if forced_raw_action is not None:
+        if box is not None:
+            # the Box form (K16 over tanh-Gaussian actions): float tables [E, A, NA], recorded RAW actions on replay
+            NA = a.num_actions
+            box.forced_action = None
+            if forced_raw_action is not None:
+                if not (forced_raw_action.is_cuda and forced_raw_action.dtype == torch.float32 and forced_raw_action.is_contiguous()
+                        and forced_raw_action.numel() == E * A * NA):
+                    raise _lib.PpoafError(f"mat rollout_step: forced_raw_action must be a contiguous float32 device tensor [{E}, {A}, {NA}]")
+                box.forced_action = forced_raw_action.data_ptr()
+        elif forced_raw_action is not None:
             if not (forced_raw_action.is_cuda and forced_raw_action.dtype == torch.int64 and forced_raw_action.is_contiguous()
                     and forced_raw_action.numel() == E * A):
                 raise _lib.PpoafError(f"mat rollout_step: forced_raw_action must be a contiguous int64 device tensor [{E}, {A}]")
@@ -221,10 +244,19 @@ class MATPolicy(PPOPolicy):
         if value_normalizer is not None:
             a.vn_mean = value_normalizer.running_stats.mean_t.data_ptr()
             a.vn_var = value_normalizer.running_stats.var_t.data_ptr()
-        a.action_out, a.raw_action_out = buf.actions[t].data_ptr(), buf.raw_actions[t].data_ptr()
+        if box is not None:
+            box.action_out, box.raw_action_out = buf.actions[t].data_ptr(), buf.raw_actions[t].data_ptr()
+        else:
+            a.action_out, a.raw_action_out = buf.actions[t].data_ptr(), buf.raw_actions[t].data_ptr()
         a.logp_out, a.value_out = buf.log_probs[t].data_ptr(), buf.values[t].data_ptr()
         a.critic_obs_copy_out, a.obs_copy_out = buf.critic_observations[t].data_ptr(), buf.observations[t].data_ptr()
-        if blocks is not None:
+        if box is not None:
+            MATPolicy.box_step_launches += 1
+            if blocks is not None:
+                _lib.check(_lib.load().ppoaf_mat_box_policy_step_blocks(C.byref(box), C.byref(tb), K.stream()), "mat_box_policy_step_blocks")
+            else:
+                _lib.check(_lib.load().ppoaf_mat_box_policy_step(C.byref(box), K.stream()), "mat_box_policy_step")
+        elif blocks is not None:
             _lib.check(_lib.load().ppoaf_mat_policy_step_blocks(C.byref(a), C.byref(tb), K.stream()), "mat_policy_step_blocks")
         else:
             _lib.check(_lib.load().ppoaf_mat_policy_step(C.byref(a), K.stream()), "mat_policy_step")
@@ -238,7 +270,7 @@ class MATPolicy(PPOPolicy):
         if not 1 <= A <= _lib.ROW_BLOCKS_MAX:
             return f"{A} agents, a row-block table holds {_lib.ROW_BLOCKS_MAX}"
         sets = [("critic observation", critic_obs_blocks, torch.float32, buf.critic_observations.shape[-1]),
-                ("env action", env_action_blocks, torch.int64, 1)]
+                ("env action", env_action_blocks, buf.actions.dtype, buf.actions.shape[-1])]
         if actor_obs_blocks is not None:
             sets.append(("observation", actor_obs_blocks, torch.float32, buf.observations.shape[-1]))
         for what, blks, dt, width in sets:
@@ -345,6 +377,8 @@ class MATPolicy(PPOPolicy):
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
             from ..fused_update import MAT_INFER_MAX_OBS
             why, O = self.fused_step_unsupported_reason(), self.critic.in_size
+            if not why and self.action_dtype != "discrete":
+                why = "K20 covers Discrete actions: the evaluation of a Box team keeps the module decode"
             if not why and O > MAT_INFER_MAX_OBS:
                 why = f"observations {O} wide: the K20 evaluation step takes up to {MAT_INFER_MAX_OBS} (K15 and K16 take these)"
             self._infer_reason = (key, why)

@@ -1450,19 +1450,19 @@ class PPO:
                                            f"the mini-batch loop ({FusedLstmUpdate.unsupported_reason(pol, B)})")
             return self._fused[key]
         if key not in self._fused:
-            from .fused_update import FusedMatUpdate, FusedPolicyUpdate, opt_in_hint
+            from .fused_update import FusedMatUpdate, FusedPolicyUpdate, mat_box_hint, opt_in_hint
             driver = FusedMatUpdate if self.policies[policy_id].agent_grouping else FusedPolicyUpdate    # K15 / K12
             why = driver.unsupported_reason(self.policies[policy_id], B)
             if why:
                 if self.update_mode == "fused":
                     raise NotImplementedError(f"update_mode='fused' but {why}")
                 if self.verbose:
-                    hint = opt_in_hint(pol, B, self.update_mode) if driver is FusedPolicyUpdate else ""
+                    hint = opt_in_hint(pol, B, self.update_mode) if driver is FusedPolicyUpdate else mat_box_hint(pol)
                     rank_print(f"policy {policy_id}: torch update path ({why}){hint}")
                 self._fused[key] = None
             else:
                 self._fused[key] = driver(self, policy_id)
-                if self.verbose and getattr(self._fused[key], "wide", False):
+                if self.verbose and (getattr(self._fused[key], "wide", False) or getattr(self._fused[key], "box", False)):
                     rank_print(f"policy {policy_id}: {self._fused[key].description()}")
         return self._fused[key]
 

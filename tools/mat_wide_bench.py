@@ -12,7 +12,11 @@ range (min .. max) of rollout ms, epoch ms and us per mini-batch of both legs, e
 not the faster one, the device launches per env step of one more rollout of each leg (torch.profiler; "n/a" where the
 profiler gives no device events), and one JSON line.
 
-    python tools/mat_wide_bench.py [--obs 71 128] [--envs 1024] [--steps 128] [--batch 256] [--repeats 5]
+--action box:N: the team acts in Box(N) instead (tanh-Gaussian; csrc/mat_box.hpp).  Both legs then run update_mode="auto" on
+the same policy class and differ in the opt-in MATPolicy.fused_mat_box_actions alone: on = K16 / K15, off = the torch path.
+
+    python tools/mat_wide_bench.py [--obs 71 128] [--action discrete:5 | box:N] [--envs 1024] [--steps 128] [--batch 256]
+                                   [--repeats 5]
 """
 import argparse
 import json
@@ -31,16 +35,25 @@ DEV = torch.device("cuda", 0)
 A, NA = 3, 5
 
 
-def make(mode, O, E, T, B):
+def action_space(spec):
+    from ppo_and_friends_amd.spaces import Box, Discrete
+    kind, n = spec.split(":")
+    return Box(-1.0, 1.0, (int(n),), np.float32) if kind == "box" else Discrete(int(n))
+
+
+def make(mode, O, E, T, B, spec=f"discrete:{NA}"):
     from ppo_and_friends_amd.ppo import PPO
     from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
     from ppo_and_friends_amd.policies.mat_policy import MATPolicy
-    from ppo_and_friends_amd.spaces import Box, Discrete
-    env_gen = lambda: SyntheticFixedLengthEnv(E, O, Discrete(NA), T, DEV, reward="uniform", seed=5, num_agents=A)
+    from ppo_and_friends_amd.spaces import Box
+    space, box = action_space(spec), spec.startswith("box")
+    env_gen = lambda: SyntheticFixedLengthEnv(E, O, space, T, DEV, reward="uniform", seed=5, num_agents=A)
     sp = Box(-np.inf, np.inf, (O,), np.float32)
-    return PPO(env_gen, {"mat": (MATPolicy, sp, sp, Discrete(NA), {})}, device=DEV, random_seed=4, normalize_obs=False,
-               normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=B, epochs_per_iter=1, update_mode=mode,
-               save_state=False)
+    ppo = PPO(env_gen, {"mat": (MATPolicy, sp, sp, space, {})}, device=DEV, random_seed=4, normalize_obs=False,
+              normalize_rewards=False, envs_per_proc=E, ts_per_rollout=T, batch_size=B, epochs_per_iter=1,
+              update_mode="auto" if box else mode, save_state=False)
+    ppo.policies["mat"].fused_mat_box_actions = box and mode == "fused"       # (a Box team: the legs differ in the opt-in alone)
+    return ppo
 
 
 def wall_ms(fn):
@@ -84,7 +97,7 @@ def run_width(O, args):
     from ppo_and_friends_amd.ppo import PermutationLoader
     legs = {}
     for mode in ("fused", "torch"):
-        ppo = make(mode, O, args.envs, args.steps, args.batch)
+        ppo = make(mode, O, args.envs, args.steps, args.batch, args.action)
         pol = ppo.policies["mat"]
         upd = ppo._fused_updater("mat", args.batch)
         if mode == "fused":
@@ -103,9 +116,9 @@ def run_width(O, args):
             leg["rollout"].append(wall_ms(leg["ppo"].rollout))
             leg["pol"].train()
             leg["epoch"].append(event_ms(lambda leg=leg: leg["ppo"]._ppo_batch_train(leg["loader"], "mat")))
-    out = dict(shape=dict(agents=A, O=O, actions=f"Discrete({NA})", envs=args.envs, steps=args.steps, batch=args.batch,
+    out = dict(shape=dict(agents=A, O=O, actions=args.action, envs=args.envs, steps=args.steps, batch=args.batch,
                           minibatches=n_mb))
-    print(f"--- O = {O}: {A} agents, Discrete({NA}), {args.envs} envs x {args.steps} steps, batch {args.batch} ({n_mb} mini-batches), "
+    print(f"--- O = {O}: {A} agents, {args.action}, {args.envs} envs x {args.steps} steps, batch {args.batch} ({n_mb} mini-batches), "
           f"{args.repeats} alternations")
     for mode, leg in legs.items():
         launches = device_launches(leg["ppo"].rollout)
@@ -130,6 +143,7 @@ def run_width(O, args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--obs", type=int, nargs="+", default=[71, 128])
+    ap.add_argument("--action", default=f"discrete:{NA}", help="discrete:N or box:N (N <= 8)")
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--batch", type=int, default=256)
