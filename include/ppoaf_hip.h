@@ -1185,6 +1185,40 @@ typedef struct {
 
 int ppoaf_mat_policy_infer(const ppoaf_mat_infer_args_t* args, ppoaf_stream_t stream);
 
+/* K20 for observations up to 128 wide: the same struct, checks, kernels and results as ppoaf_mat_policy_infer, which keeps
+ * its limit of 64 (and its refusal of 65).  Rows wider than 32 stream through K16's chunked front end, as many chunks
+ * of 32 columns as the row has, so the bitwise link to ppoaf_mat_policy_step's action_out holds up to 128. */
+int ppoaf_mat_policy_infer_wide(const ppoaf_mat_infer_args_t* args, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
+ * K20, Box form: one evaluation step of a MATPolicy over continuous (tanh-Gaussian) actions
+ * replaces MATPolicy.get_inference_actions for MATActor's continuous form   policies/mat_policy.py:701-790
+ *          the greedy decode over refine_prediction                         mat_policy.py:521-585
+ *          the sampled decode                                               mat_policy.py:441-519
+ *          GaussianDistribution: sample, refine_prediction                  networks/distributions.py:441-694
+ * `mat` is read as by ppoaf_mat_policy_infer (obs_dim <= 128), except: num_actions = NA, the action dimensions (1 .. 8);
+ * offsets / enc_bias_offset / log_std_offset place the Box bucket's tensors as for ppoaf_mat_box_policy_step (checked
+ * against the topology); mat.action_out is not read.  The refined actions are float32, NA per (env, agent): slot s of
+ * env e writes the NA floats of ROW slot_agent[s] * act_agent_stride + e * act_env_stride of action_out.
+ * The token block has no start-token column (slot 0 sees zeros), the action encoder is Linear(NA, 64) with its bias; the
+ * value head is not run.  mode:
+ *   PPOAF_INFER_DETERMINISTIC  tanh(mean) scaled into [act_lo, act_hi] (both NULL: the unit box); seed / offset are not read
+ *   PPOAF_INFER_SAMPLE         tanh(mean + sd * n), sd = max(softplus(log_std), min_std), n from Philox block d / 4 of the
+ *                              counter offset + env * A + slot: for equal (obs, params, seed, offset) in grouped layout the
+ *                              actions are bitwise ppoaf_mat_box_policy_step's action_out
+ * No log-prob, no raw action.  E == 0: nothing to do.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    ppoaf_mat_infer_args_t mat;
+    int64_t enc_bias_offset, log_std_offset;
+    float min_std;
+    int32_t reserved;
+    const float* act_lo; const float* act_hi;    /* [NA] device bounds, or both NULL: the unit box */
+    float* action_out;                           /* NA floats per (env, agent) row */
+} ppoaf_mat_box_infer_args_t;
+
+int ppoaf_mat_box_policy_infer(const ppoaf_mat_box_infer_args_t* args, ppoaf_stream_t stream);
+
 /* ------------------------------------------------------------------------ *
  * K18  one-layer LSTM network: LSTMNetwork.forward_logits and its gradients
  * replaces nn.LSTM -> LayerNorm -> activation -> ff_layers of

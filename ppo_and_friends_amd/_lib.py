@@ -266,6 +266,13 @@ class MatInferArgs(C.Structure):
                 ("action_out", C.c_void_p), ("act_env_stride", C.c_int64), ("act_agent_stride", C.c_int64)]
 
 
+class MatBoxInferArgs(C.Structure):
+    """ppoaf_mat_box_infer_args_t (include/ppoaf_hip.h): K20's args and what the Box form adds."""
+    _fields_ = [("mat", MatInferArgs), ("enc_bias_offset", C.c_int64), ("log_std_offset", C.c_int64),
+                ("min_std", C.c_float), ("reserved", C.c_int32), ("act_lo", C.c_void_p), ("act_hi", C.c_void_p),
+                ("action_out", C.c_void_p)]
+
+
 ROW_BLOCKS_MAX, FINISH_MAX_MEMBERS = 16, 8
 
 
@@ -408,6 +415,8 @@ SIGNATURES = {
     "ppoaf_mat_update_norm_partials": (C.c_int, [C.POINTER(MatUpdateArgs)]),
     "ppoaf_mat_policy_step": (C.c_int, [C.POINTER(MatStepArgs), _ptr]),
     "ppoaf_mat_policy_infer": (C.c_int, [C.POINTER(MatInferArgs), _ptr]),
+    "ppoaf_mat_policy_infer_wide": (C.c_int, [C.POINTER(MatInferArgs), _ptr]),
+    "ppoaf_mat_box_policy_infer": (C.c_int, [C.POINTER(MatBoxInferArgs), _ptr]),
     "ppoaf_rollout_finish_rows": (C.c_int, [C.POINTER(RolloutFinishArgs), _ptr]),
     "ppoaf_policy_step_blocks": (C.c_int, [C.POINTER(PolicyStepArgs), C.POINTER(StepBlocks), _ptr]),
     "ppoaf_mat_policy_step_blocks": (C.c_int, [C.POINTER(MatStepArgs), C.POINTER(MatStepBlocks), _ptr]),

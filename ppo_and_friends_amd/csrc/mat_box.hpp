@@ -1,4 +1,4 @@
-// Box (tanh-Gaussian) form of the MAT kernels K15 and K16 (mat_update.hip): what differs from the Discrete form.
+// Box (tanh-Gaussian) form of the MAT kernels K15, K16 and K20 (mat_update.hip): what differs from the Discrete form.
 //   MATActor with continuous actions (networks/actor_critic/multi_agent_transformer.py:22-156): the action encoder is
 //   Linear(NA, 64) WITH a bias over the previous agents' actions themselves (no start-token column: slot 0 sees zeros,
 //   mat_policy.py:308-344), the head's last linear gives the means of a GaussianDistribution (networks/distributions.py:
@@ -14,6 +14,8 @@
 //   K16: one lane per token row draws with K6's gauss_step_row (action_heads.hpp): the row's Philox counter is
 //        offset + env * A + slot, block q of it gives the normals of dimensions 4 q .. 4 q + 3; the REFINED action is
 //        agent i + 1's token (mat_policy.py:441-519).
+//   K20: a lane pair per token row, lane (row, q) drawing and refining dimensions 4 q .. 4 q + 3 from Philox block q
+//        (mat_box_infer_lane); only the refined env actions leave the kernel (mat_policy.py:521-585,701-790).
 #pragma once
 #include "action_heads.hpp"
 
@@ -111,6 +113,38 @@ __device__ __forceinline__ void mat_box_step_row(const float* __restrict__ mean_
         const float a = action_out[tok * NA + d];
         if (next_token) next_token[d] = a;
         if (env_row) env_row[d] = a;
+    }
+}
+
+// K20, pass i: a LANE PAIR per token row.  Lane (row, q) owns dimensions 4 q .. 4 q + 3 -- exactly Philox block q of the
+// row's counter `ctr` (= offset + env * A + slot, K16's), so with NA <= 8 a row is two lanes with one Box-Muller block
+// each, side by side.  The per-dimension arithmetic is gauss_step_row's, operation for operation (the sampled actions
+// are bitwise K16's action_out); greedy: tanh(mean) scaled to the bounds, the counter is not read.  The refined action
+// goes to the env's row and, with next_token (NULL for the last agent), into agent i + 1's row of the LDS action tile --
+// before the barrier that pass i + 1's decoder reads behind.  No log-prob, no raw action.
+__device__ __forceinline__ void mat_box_infer_lane(const float* __restrict__ mean_row, const int NA, const int q,
+                                                   const bool greedy, const float* __restrict__ log_std, const float min_std,
+                                                   const float* __restrict__ act_lo, const float* __restrict__ act_hi,
+                                                   const unsigned long long seed, const unsigned long long ctr,
+                                                   float* __restrict__ env_row, float* __restrict__ next_token) {
+    const bool rescale = act_lo != nullptr;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!greedy) gauss_normals4(seed, ctr, (uint32_t)q, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int d = 4 * q + j;
+        if (d < NA) {
+            const float mean = mean_row[d];
+            float x = mean;
+            if (!greedy) {
+                const float sd = fmaxf(softplus_u(log_std[d]), min_std);
+                x = mean + sd * z[j];
+            }
+            float a = tanhf(x);
+            if (rescale) a = unit_to_bounds(a, act_lo[d], act_hi[d]);
+            env_row[d] = a;
+            if (next_token) next_token[d] = a;
+        }
     }
 }
 

@@ -1358,6 +1358,10 @@ __global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_policy_step_block
 // (env seq0 + s / L, slot s % L); the slot's observation row and action element are found through slot_agent and the
 // strides, so grouped [E, A, .] and the env's agent-major [A * E, .] tensors are both read and written in place.
 // COMPACT: the forward-only carve (MatCtxT<true>, 10 tiles instead of 34: three workgroups per CU instead of one).
+// WIDE: K16's chunked front end, as many chunks of 32 columns as the row has (up to 128 wide).
+// X = MatBoxInferDev: the Box form (mat_box.hpp) -- no start-token column, the action encoder's bias, and a head that
+// gives each token row a lane pair; float32 actions, NA per (env, agent) row.  Its branches are discarded from the
+// Discrete kernels.
 // ------------------------------------------------------------------------------------------------
 struct MatInferDev {
     long off[64];
@@ -1370,6 +1374,18 @@ struct MatInferDev {
     unsigned char slot_agent[16];
 };
 
+// The Box form (mat_box.hpp): off[] holds the 63 shared tensors of the Box bucket, NA = Ain = the action dimensions; the
+// refined actions go to action_f, NA floats per (env, agent) ROW -- rows addressed as action_out's elements are.  The
+// int64 pointer is unused.  A second kernel argument beside MatInferDev, so that the Discrete kernels' argument stays as it
+// is (one struct holding both is copied to scratch memory for its runtime-indexed slot_agent).
+struct MatNoBox {};
+struct MatBoxInferDev {
+    long off_enc_b, off_log_std;
+    float min_std;
+    const float* act_lo; const float* act_hi;      // [NA], or both NULL: the unit box
+    float* action_f;
+};
+
 // Diagnostic builds only (-DPPOAF_MAT_INFER_VARIANT=bits, the A/B legs of profiles/eval_bench.txt): 1 = K16's full carve,
 // 2 = run the value head as K16 does.  The shipped library is variant 0.
 #ifndef PPOAF_MAT_INFER_VARIANT
@@ -1378,8 +1394,11 @@ struct MatInferDev {
 constexpr bool kInferCompact = !(PPOAF_MAT_INFER_VARIANT & 1);
 constexpr bool kInferValue = (PPOAF_MAT_INFER_VARIANT & 2) != 0;
 
-template <bool COMPACT, bool VALUE, bool WIDE>
-__device__ __forceinline__ void mat_policy_infer_body(const MatInferDev u) {
+template <bool COMPACT, bool VALUE, bool WIDE, class X = MatNoBox>
+__device__ __forceinline__ void mat_policy_infer_body(const MatInferDev u, [[maybe_unused]] const X x = X()) {
+    constexpr bool BOX = std::is_same<X, MatBoxInferDev>::value;
+    [[maybe_unused]] const float* enc_b = nullptr;
+    if constexpr (BOX) enc_b = u.params + x.off_enc_b;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long seq0 = (long)blockIdx.x * u.per_tile;
     const long rem = u.E - seq0;
@@ -1402,14 +1421,24 @@ __device__ __forceinline__ void mat_policy_infer_body(const MatInferDev u) {
         const int s = idx / O, i = idx - s * O;
         sYO[s * OS + i] = obs_row(s)[i];
     }
-    if (tid < n_rows && tid % L == 0) sXA[tid * kMXS] = 1.0f;     // start token of agent 0 (mat_policy.py:325-333)
+    if (!BOX && tid < n_rows && tid % L == 0) sXA[tid * kMXS] = 1.0f;     // start token of agent 0 (mat_policy.py:325-333)
     MAT_SYNC();
     mat_encoder_forward<false, MatNoPub, VALUE>(c, tid, wave, lane, MatNoPub(),
                                                 (WIDE && (tid >> 4) < n_rows) ? obs_row(tid >> 4) : nullptr);
     MAT_SYNC();
     const long tok0 = seq0 * L;                                  // K16's Philox counter: offset + env * L + slot
     for (int i = 0; i < L; ++i) {
-        mat_decoder_forward<false>(c, tid, wave, lane);           // ends with a barrier
+        mat_decoder_forward<false>(c, tid, wave, lane, MatNoPub(), enc_b);           // ends with a barrier
+        if constexpr (BOX) {
+            // a lane pair per token row (mat_box_infer_lane): 2 x 16 lanes of wave 0, one Philox block each
+            const int row = tid >> 1, q = tid & 1;
+            if (row < n_rows && row % L == i && 4 * q < NA) {
+                const long arow = (long)u.slot_agent[i] * u.act_agent_stride + (seq0 + row / L) * u.act_env_stride;
+                mat_box_infer_lane(sOutA + row * 8, NA, q, u.mode == PPOAF_INFER_DETERMINISTIC, u.params + x.off_log_std,
+                                   x.min_std, x.act_lo, x.act_hi, u.seed, u.offset + (unsigned long long)(tok0 + row),
+                                   x.action_f + arow * NA, i + 1 < L ? sXA + (row + 1) * kMXS : nullptr);
+            }
+        } else
         if (tid < n_rows && tid % L == i) {
             int a = 0;
             if (u.mode == PPOAF_INFER_DETERMINISTIC) {
@@ -1455,6 +1484,9 @@ template <bool COMPACT, bool VALUE>
 __global__ __launch_bounds__(kMT) void mat_policy_infer_kernel(MatInferDev u) { mat_policy_infer_body<COMPACT, VALUE, false>(u); }
 template <bool COMPACT, bool VALUE>
 __global__ __launch_bounds__(kMT) void mat_policy_infer_wide_kernel(MatInferDev u) { mat_policy_infer_body<COMPACT, VALUE, true>(u); }
+// the Box form: the forward-only carve, no value head
+__global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_policy_infer_kernel(MatInferDev u, MatBoxInferDev x) { mat_policy_infer_body<true, false, false>(u, x); }
+__global__ __launch_bounds__(kMT) PPOAF_NO_PK_F32 void mat_box_policy_infer_wide_kernel(MatInferDev u, MatBoxInferDev x) { mat_policy_infer_body<true, false, true>(u, x); }
 
 // slabs -> gradient bucket in a fixed order (each thread owns a float4 column, 8 slab loads in flight at a
 // time, no LDS staging); the last workgroup folds the loss partials and advances the cursor
@@ -2118,61 +2150,103 @@ PPOAF_LAYOUT(ppoaf_mat_infer_args_t, act_env_stride, 664);
 PPOAF_LAYOUT(ppoaf_mat_infer_args_t, act_agent_stride, 672);
 static_assert(sizeof(ppoaf_mat_infer_args_t) == 680, "ppoaf_mat_infer_args_t");
 
-extern "C" int ppoaf_mat_policy_infer(const ppoaf_mat_infer_args_t* a, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a, "mat_policy_infer: null args");
-    PPOAF_REQUIRE(a->embedding == kMD, "mat_policy_infer: embedding=%d (built for 64)", a->embedding);
-    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= 64 &&
+// The one launcher of K20's entry points.  who: the entry point's name in its messages; max_obs: the widest observation it
+// answers for (ppoaf_mat_policy_infer keeps 64, and its refusal of 65); box: the Box form's args around `a`, NULL for the
+// Discrete form.
+static int mat_policy_infer_launch(const ppoaf_mat_infer_args_t* a, const ppoaf_mat_box_infer_args_t* box, const char* who,
+                                   int max_obs, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a->embedding == kMD, "%s: embedding=%d (built for 64)", who, a->embedding);
+    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= max_obs &&
                       a->num_actions >= 1 && a->num_actions <= 8,
-                  "mat_policy_infer: sizes (agents %d, obs %d, actions %d) outside K16's limits (16, 64, 8)", a->num_agents,
-                  a->obs_dim, a->num_actions);
+                  "%s: sizes (agents %d, obs %d, actions %d) outside K16's limits (16, %d, 8)", who, a->num_agents, a->obs_dim,
+                  a->num_actions, max_obs);
     PPOAF_REQUIRE(a->mode == PPOAF_INFER_SAMPLE || a->mode == PPOAF_INFER_DETERMINISTIC,
-                  "mat_policy_infer: mode=%d (0 sample, 1 deterministic)", a->mode);
-    PPOAF_REQUIRE(a->E >= 0, "mat_policy_infer: negative E");
-    PPOAF_REQUIRE(a->E <= (1L << 27), "mat_policy_infer: E too large");
-    PPOAF_REQUIRE(a->params && a->obs && a->action_out, "mat_policy_infer: null pointer");
-    PPOAF_REQUIRE(((uintptr_t)a->params & 15) == 0, "mat_policy_infer: params must be 16-byte aligned");
+                  "%s: mode=%d (0 sample, 1 deterministic)", who, a->mode);
+    PPOAF_REQUIRE(a->E >= 0, "%s: negative E", who);
+    PPOAF_REQUIRE(a->E <= (1L << 27), "%s: E too large", who);
+    PPOAF_REQUIRE(a->params && a->obs && (box ? (void*)box->action_out : (void*)a->action_out), "%s: null pointer", who);
+    PPOAF_REQUIRE(((uintptr_t)a->params & 15) == 0, "%s: params must be 16-byte aligned", who);
     PPOAF_REQUIRE(a->obs_env_stride >= 1 && a->obs_agent_stride >= 1 && a->act_env_stride >= 1 && a->act_agent_stride >= 1,
-                  "mat_policy_infer: strides must be >= 1 (obs %ld / %ld, action %ld / %ld)", (long)a->obs_env_stride,
+                  "%s: strides must be >= 1 (obs %ld / %ld, action %ld / %ld)", who, (long)a->obs_env_stride,
                   (long)a->obs_agent_stride, (long)a->act_env_stride, (long)a->act_agent_stride);
     unsigned seen = 0;
     for (int i = 0; i < a->num_agents; ++i) {
         const int v = a->slot_agent[i];
         PPOAF_REQUIRE(v >= 0 && v < a->num_agents && !((seen >> v) & 1u),
-                      "mat_policy_infer: slot_agent is not a permutation of 0..%d (slot %d holds %d)", a->num_agents - 1, i, v);
+                      "%s: slot_agent is not a permutation of 0..%d (slot %d holds %d)", who, a->num_agents - 1, i, v);
         seen |= 1u << v;
     }
-    long want[MAT_NUM_PARAMS];
-    mat_offset_table(a->obs_dim, a->num_actions, want);
+    long want[MAT_NUM_PARAMS], want_eb = 0, want_ls = 0;
+    if (box) mat_box_offset_table(a->obs_dim, a->num_actions, want, &want_eb, &want_ls);
+    else mat_offset_table(a->obs_dim, a->num_actions, want);
     for (int i = 0; i < MAT_NUM_PARAMS; ++i)
-        PPOAF_REQUIRE(a->offsets[i] == want[i], "mat_policy_infer: parameter %d sits at %ld, expected %ld", i, (long)a->offsets[i],
-                      want[i]);
+        PPOAF_REQUIRE(a->offsets[i] == want[i], "%s: parameter %d sits at %ld, expected %ld", who, i, (long)a->offsets[i], want[i]);
+    if (box) {
+        PPOAF_REQUIRE((box->act_lo == nullptr) == (box->act_hi == nullptr), "%s: give both bounds or neither", who);
+        PPOAF_REQUIRE(box->min_std >= 0.f, "%s: min_std=%g", who, (double)box->min_std);
+        PPOAF_REQUIRE(box->enc_bias_offset == want_eb && box->log_std_offset == want_ls,
+                      "%s: action encoder bias / log_std sit at %ld / %ld, expected %ld / %ld", who, (long)box->enc_bias_offset,
+                      (long)box->log_std_offset, want_eb, want_ls);
+    }
     if (a->E == 0) return PPOAF_OK;
     MatInferDev u;
     for (int i = 0; i < 64; ++i) u.off[i] = i < MAT_NUM_PARAMS ? a->offsets[i] : 0;
-    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = a->num_actions + 1;
+    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = box ? a->num_actions : a->num_actions + 1;
     u.per_tile = 16 / u.L; u.mode = a->mode;
     u.params = a->params; u.obs = a->obs; u.E = a->E;
     u.obs_env_stride = a->obs_env_stride; u.obs_agent_stride = a->obs_agent_stride;
     u.act_env_stride = a->act_env_stride; u.act_agent_stride = a->act_agent_stride;
     u.seed = a->seed; u.offset = a->offset; u.action_out = a->action_out;
     for (int i = 0; i < 16; ++i) u.slot_agent[i] = (unsigned char)(i < u.L ? a->slot_agent[i] : 0);
-    const size_t lds = kInferCompact ? mat_fwd_lds_bytes(u.O) : mat_lds_bytes(u.O);
-    PPOAF_REQUIRE(lds <= 160 * 1024, "mat_policy_infer: needs %zu B of LDS (> 160 KiB)", lds);
-    // 33 <= obs_dim <= 64 takes K16's chunked front end, so the sampled actions stay operation for operation K16's
+    const size_t lds = (box || kInferCompact) ? mat_fwd_lds_bytes(u.O) : mat_lds_bytes(u.O);
+    PPOAF_REQUIRE(lds <= 160 * 1024, "%s: needs %zu B of LDS (> 160 KiB)", who, lds);
+    // obs_dim >= 33 takes K16's chunked front end, so the sampled actions stay operation for operation K16's
     static void (*const kern[2])(MatInferDev) = {mat_policy_infer_kernel<kInferCompact, kInferValue>,
                                                  mat_policy_infer_wide_kernel<kInferCompact, kInferValue>};
-    const int wide = mat_is_wide(u.O) ? 1 : 0;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[wide] && lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern[wide]),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    static void (*const kern_box[2])(MatInferDev, MatBoxInferDev) = {mat_box_policy_infer_kernel, mat_box_policy_infer_wide_kernel};
+    const int wide = mat_is_wide(u.O) ? 1 : 0, k = (box ? 2 : 0) + wide;
+    static bool attr_set[4] = {false, false, false, false};
+    if (!attr_set[k] && lds > 64 * 1024) {
+        const void* fn = box ? reinterpret_cast<const void*>(kern_box[wide]) : reinterpret_cast<const void*>(kern[wide]);
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set[wide] = true;
+        attr_set[k] = true;
     }
     const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
-    hipLaunchKernelGGL(kern[wide], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
-    return check_launch("mat_policy_infer");
+    if (box) {
+        u.action_out = nullptr;
+        const MatBoxInferDev x{box->enc_bias_offset, box->log_std_offset, box->min_std, box->act_lo, box->act_hi, box->action_out};
+        hipLaunchKernelGGL(kern_box[wide], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u, x);
+    } else {
+        hipLaunchKernelGGL(kern[wide], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
+    }
+    return check_launch(who);
 }
+
+extern "C" int ppoaf_mat_policy_infer(const ppoaf_mat_infer_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_policy_infer: null args");
+    return mat_policy_infer_launch(a, nullptr, "mat_policy_infer", 64, stream);
+}
+
+// the same launch for observations up to kMOWide (the chunked front end walks as many chunks as the row has)
+extern "C" int ppoaf_mat_policy_infer_wide(const ppoaf_mat_infer_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_policy_infer_wide: null args");
+    return mat_policy_infer_launch(a, nullptr, "mat_policy_infer_wide", kMOWide, stream);
+}
+
+extern "C" int ppoaf_mat_box_policy_infer(const ppoaf_mat_box_infer_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_box_policy_infer: null args");
+    return mat_policy_infer_launch(&a->mat, a, "mat_box_policy_infer", kMOWide, stream);
+}
+
+PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, mat, 0);
+PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, enc_bias_offset, sizeof(ppoaf_mat_infer_args_t));
+PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, log_std_offset, sizeof(ppoaf_mat_infer_args_t) + 8);
+PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, min_std, sizeof(ppoaf_mat_infer_args_t) + 16);
+PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, act_lo, sizeof(ppoaf_mat_infer_args_t) + 24);
+PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, act_hi, sizeof(ppoaf_mat_infer_args_t) + 32);
+PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, action_out, sizeof(ppoaf_mat_infer_args_t) + 40);
+static_assert(sizeof(ppoaf_mat_box_infer_args_t) == sizeof(ppoaf_mat_infer_args_t) + 48, "ppoaf_mat_box_infer_args_t");
 
 // mpi_avg_gradients at the MAT update's per-mini-batch call site (mat_policy.py:692) when the K17 peer exchange is not
 // available: fwd_bwd -> reduce -> RCCL sum all-reduce of the shared bucket -> K11 clip + Adam (mat_policy.py:694-699),

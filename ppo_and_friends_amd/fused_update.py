@@ -1762,7 +1762,7 @@ _MAT_PARAM_NAMES = (
 
 
 # per-agent observation widths of the MAT kernels (csrc/mat_update.hip): K15 and K16 stream rows wider than 32 through LDS in
-# column chunks, up to 128; K20's entry point stops at 64
+# column chunks, up to 128; K20's first entry point stops at 64, its wide and Box entry points (opt-in) take 128
 MAT_MAX_OBS = 128
 MAT_INFER_MAX_OBS = 64
 
@@ -1833,6 +1833,36 @@ def mat_box_hint(pol):
     """What `verbose` adds to the refusal of a MAT policy that `fused_mat_box_actions` alone would take."""
     if _describe_mat(pol)[0] is None and _describe_mat(pol, box_actions=True)[0] is not None:
         return "; MATPolicy.fused_mat_box_actions = True would take it on the fused kernels"
+    return ""
+
+
+def mat_eval_forms(pol):
+    """The opt-in `fused_mat_eval_forms` -- MATPolicy's own attribute, read here and nowhere else."""
+    return bool(getattr(pol, "fused_mat_eval_forms", False))
+
+
+def mat_infer_reason(pol, eval_forms=None):
+    """'' when K20 evaluates a MAT policy in one launch, else why the network modules decode.  What K16 / K15 refuse,
+    K20 refuses in their words.  Of what they take, the Box form and observations above MAT_INFER_MAX_OBS run only with
+    the opt-in `fused_mat_eval_forms` (ppoaf_mat_box_policy_infer / ppoaf_mat_policy_infer_wide); eval_forms: the answer
+    to ask under instead (a hypothetical never writes to the policy)."""
+    if eval_forms is None:
+        eval_forms = mat_eval_forms(pol)
+    topo, why = _describe_mat(pol)
+    if why or eval_forms:
+        return why
+    if topo["box"]:
+        return "K20 covers Discrete actions: the evaluation of a Box team keeps the module decode"
+    if topo["obs_dim"] > MAT_INFER_MAX_OBS:
+        return (f"observations {topo['obs_dim']} wide: the K20 evaluation step takes up to {MAT_INFER_MAX_OBS} "
+                "(K15 and K16 take these)")
+    return ""
+
+
+def mat_eval_hint(pol, why):
+    """What `verbose` adds to the refusal `why` of a MAT policy's evaluation that `fused_mat_eval_forms` alone would take."""
+    if why and why == mat_infer_reason(pol, eval_forms=False) and mat_infer_reason(pol, eval_forms=True) == "":
+        return "; MATPolicy.fused_mat_eval_forms = True would take it on the one-launch step"
     return ""
 
 

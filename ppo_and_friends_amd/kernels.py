@@ -558,6 +558,16 @@ def mat_policy_infer(args):
     check(_lib.load().ppoaf_mat_policy_infer(C.byref(args), stream()), "mat_policy_infer")
 
 
+def mat_policy_infer_wide(args):
+    """ppoaf_mat_policy_infer_wide: the same launch on the same struct, observations up to 128 wide."""
+    check(_lib.load().ppoaf_mat_policy_infer_wide(C.byref(args), stream()), "mat_policy_infer_wide")
+
+
+def mat_box_policy_infer(args):
+    """ppoaf_mat_box_policy_infer on a filled _lib.MatBoxInferArgs: K20 over a Box team, float32 actions."""
+    check(_lib.load().ppoaf_mat_box_policy_infer(C.byref(args), stream()), "mat_box_policy_infer")
+
+
 # --------------------------------------------------------------------------
 # K23: the rows that follow env.step in PPO.rollout, all members in one launch
 # --------------------------------------------------------------------------

@@ -28,9 +28,16 @@ class MATPolicy(PPOPolicy):
 
     # Opt-in: a team over Box (tanh-Gaussian) actions on the fused rollout step K16 and update K15 (csrc/mat_box.hpp), single
     # rank.  Set by hand, on the class or on the policy, before the first rollout -- no update_mode sets it.  False: such a
-    # team keeps the torch path.  Evaluation (K20) keeps the module decode either way.  (MATPolicy's own switch, read by
-    # fused_update._describe_mat: the FusedOptIns value holds the opt-ins of the feed-forward and ICM describers.)
+    # team keeps the torch path.  Evaluation (K20) takes such a team only with the next opt-in.  (MATPolicy's own switch, read
+    # by fused_update._describe_mat: the FusedOptIns value holds the opt-ins of the feed-forward and ICM describers.)
     fused_mat_box_actions = False
+
+    # Opt-in: the evaluation step K20 for every MAT policy that K16 / K15 take -- a Box team (ppoaf_mat_box_policy_infer) and
+    # Discrete teams with observations 65 .. 128 wide (ppoaf_mat_policy_infer_wide).  Set by hand, on the class or on the
+    # policy, before the first evaluation -- no update_mode sets it.  False: those two keep the module decode, with the
+    # refusals they always had; a policy inside K20's first limits runs the same launch either way.  (Read by
+    # fused_update.mat_eval_forms, beside the other MAT opt-in.)
+    fused_mat_eval_forms = False
 
     def __init__(self, ac_network=MATActorCritic, mat_kw_args={}, use_huber_loss=True, **kw_args):
         super().__init__(ac_network=ac_network, mat_kw_args=mat_kw_args, use_huber_loss=use_huber_loss, **kw_args)
@@ -373,15 +380,10 @@ class MATPolicy(PPOPolicy):
         if getattr(self, "update_mode", "auto") == "torch":
             return "update_mode='torch' keeps the policy on the torch-ROCm path"
         # (asked once per evaluation step: the answer is kept for as long as the parameter bucket stays)
-        key = self.policy_params.data_ptr()
+        from ..fused_update import mat_eval_forms, mat_infer_reason
+        key = (self.policy_params.data_ptr(), mat_eval_forms(self))
         if getattr(self, "_infer_reason", (None, ""))[0] != key:
-            from ..fused_update import MAT_INFER_MAX_OBS
-            why, O = self.fused_step_unsupported_reason(), self.critic.in_size
-            if not why and self.action_dtype != "discrete":
-                why = "K20 covers Discrete actions: the evaluation of a Box team keeps the module decode"
-            if not why and O > MAT_INFER_MAX_OBS:
-                why = f"observations {O} wide: the K20 evaluation step takes up to {MAT_INFER_MAX_OBS} (K15 and K16 take these)"
-            self._infer_reason = (key, why)
+            self._infer_reason = (key, mat_infer_reason(self))
         return self._infer_reason[1]
 
     def _infer_step(self, t_obs, deterministic, agent_major=False):
@@ -392,26 +394,38 @@ class MATPolicy(PPOPolicy):
         """
         from .. import _lib
         from .. import kernels as K
-        from ..fused_update import _describe_mat
+        from ..fused_update import MAT_INFER_MAX_OBS, _describe_mat, mat_eval_forms
         A = len(self.agent_ids)
         st = getattr(self, "_infer_state", None)
-        if st is None or st["params"] != self.policy_params.data_ptr():
+        forms = mat_eval_forms(self)
+        if st is None or st["params"] != self.policy_params.data_ptr() or st["forms"] != forms:
             topo, why = _describe_mat(self)
             if topo is None:
                 raise _lib.PpoafError(f"mat inference step: {why}")
-            a = _lib.MatInferArgs()
+            # the forms behind `fused_mat_eval_forms`: a Box team (float32 actions, NA per agent) and observations above
+            # MAT_INFER_MAX_OBS (the wide entry point); everything else is the launch it always was
+            box = _lib.MatBoxInferArgs() if topo["box"] else None
+            wide = box is None and topo["obs_dim"] > MAT_INFER_MAX_OBS
+            if (box is not None or wide) and not forms:
+                raise _lib.PpoafError(f"mat inference step: {self.inference_unsupported_reason()}")
+            a = box.mat if box is not None else _lib.MatInferArgs()        # (a view: writes land in `box`)
+            if box is not None:
+                box.enc_bias_offset, box.log_std_offset, box.min_std = topo["enc_bias_offset"], topo["log_std_offset"], topo["min_std"]
+                lo, hi = self.actor.distribution.bound_tensors()
+                box.act_lo, box.act_hi = (None, None) if lo is None else (lo.data_ptr(), hi.data_ptr())
             a.obs_dim, a.num_agents, a.num_actions, a.embedding = topo["obs_dim"], topo["num_agents"], topo["num_actions"], 64
             for i, o in enumerate(topo["offsets"]):
                 a.offsets[i] = o
             a.params = self.policy_params.data_ptr()
-            st = self._infer_state = dict(params=a.params, args=a, out={}, order=None)
-        a = st["args"]
+            st = self._infer_state = dict(params=a.params, forms=forms, args=a, box=box, wide=wide, out={}, order=None)
+        a, box = st["args"], st["box"]
         K._req(t_obs.is_cuda and t_obs.dtype == torch.float32 and t_obs.numel() % (A * a.obs_dim) == 0,
                f"get_inference_actions: obs must hold [E, {A}, {a.obs_dim}] float32 values on the device")
         E = t_obs.numel() // (A * a.obs_dim)
         out = st["out"].get((E, agent_major))
         if out is None:
-            out = st["out"][(E, agent_major)] = torch.zeros((A * E, 1) if agent_major else (E, A, 1), dtype=torch.int64,
+            width, dt = (1, torch.int64) if box is None else (a.num_actions, torch.float32)
+            out = st["out"][(E, agent_major)] = torch.zeros((A * E, width) if agent_major else (E, A, width), dtype=dt,
                                                             device=self.device)
         order = tuple(self.agent_ids) if agent_major else None
         if st["order"] != (agent_major, order):
@@ -422,11 +436,20 @@ class MATPolicy(PPOPolicy):
         a.obs_env_stride, a.obs_agent_stride = (1, E) if agent_major else (A, 1)
         a.act_env_stride, a.act_agent_stride = a.obs_env_stride, a.obs_agent_stride
         t_obs = t_obs.contiguous()
-        a.obs, a.action_out = t_obs.data_ptr(), out.data_ptr()
+        a.obs = t_obs.data_ptr()
+        if box is None:
+            a.action_out = out.data_ptr()
+        else:
+            box.action_out = out.data_ptr()
         a.mode = K.INFER_DETERMINISTIC if deterministic else K.INFER_SAMPLE
         if not deterministic:
             a.seed, a.offset = self.eval_rng().take(E * A)
-        K.mat_policy_infer(a)
+        if box is not None:
+            K.mat_box_policy_infer(box)
+        elif st["wide"]:
+            K.mat_policy_infer_wide(a)
+        else:
+            K.mat_policy_infer(a)
         return out
 
     def get_inference_actions(self, obs, deterministic):

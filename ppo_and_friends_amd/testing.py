@@ -159,7 +159,9 @@ def test_policy(ppo, num_test_runs, deterministic=False, save_test_scores=False,
         for p, pol in ppo.policies.items():
             why = pol.inference_unsupported_reason() if policy_agents[p] and hasattr(pol, "inference_unsupported_reason") else ""
             if why:
-                rank_print("Policy {}: the network modules decode its actions, not the one-launch step: {}".format(p, why))
+                from .fused_update import mat_eval_hint
+                rank_print("Policy {}: the network modules decode its actions, not the one-launch step: {}{}".format(
+                    p, why, mat_eval_hint(pol, why)))
 
     # ---- state to put back
     stack = list(ppo._filter_stack(env))

@@ -4,7 +4,11 @@ Evaluation env-steps/s of `ppo_and_friends_amd.testing.test_policy` at three sha
   shapes  c2  BatchedCartPoleEnv, E = 4096, actor 4 -> 128^3 -> 2 (Discrete(2)), observation / reward normalisers
           c3  SyntheticFixedLengthEnv, E = 4096, actor 17 -> 256^3 -> 6 (Box(6), C3's actor shape), no filters
           c5  SyntheticFixedLengthEnv, E = 4096, O = 18, Discrete(5), 3 agents, MATPolicy defaults (C5's shape), no
-              filters; only with --shape c5 ("both" stays c2 + c3)
+              filters; only with --shape c5 ("both" stays c2 + c3).  --action box:N makes the team's action space
+              Box(-0.5, 2.0, (N,)) and --obs W its observations W wide: a Box team or W > 64 evaluates on K20 only behind
+              `MATPolicy.fused_mat_eval_forms`, and then leg b is the SAME test_policy with that attribute off (the
+              module decode of this build, the behaviour before these forms).  Also prints the K20 launch's own time
+              (HIP events around 200 back-to-back launches on a fixed observation batch).
           lstm  BatchedCartPoleEnv, E = 4096, LSTM actor / critic of the reference's cart_pole_lstm baseline (4
               observations, Discrete(2), LSTM 32, feed-forward 16, LeakyReLU), update_mode="fused"; only with --shape
               lstm.  Also times PPO.rollout (T = --rollout-steps per env) with the K21 step on and off.
@@ -24,7 +28,7 @@ median and spread (min .. max) over `--repeats`, then one JSON line.  `--leg a|b
 `rocprofv3 --kernel-trace --stats` gives the launches per evaluation step of one leg (the loop steps are printed).
 
     python tools/eval_bench.py [--shape both|c2|c3|c5|lstm] [--leg both|a|b] [--envs 4096] [--runs-per-env 2] [--repeats 5]
-                               [--rollout-steps 128]
+                               [--rollout-steps 128] [--action discrete:5|box:N] [--obs 18]
 """
 import argparse
 import json
@@ -56,7 +60,7 @@ def count_steps(ppo):
     raw.step = step
 
 
-def make(shape, E, T=32):
+def make(shape, E, T=32, obs=18, action="discrete:5"):
     from ppo_and_friends_amd.ppo import PPO
     from ppo_and_friends_amd.environments.cartpole import BatchedCartPoleEnv
     from ppo_and_friends_amd.environments.synthetic import SyntheticFixedLengthEnv
@@ -80,13 +84,18 @@ def make(shape, E, T=32):
     elif shape == "c5":
         from ppo_and_friends_amd.policies.mat_policy import MATPolicy
 
+        kind, n = action.split(":")
+        space = Box(-0.5, 2.0, (int(n),), np.float32) if kind == "box" else Discrete(int(n))
+
         def env_gen():
-            env = SyntheticFixedLengthEnv(E, 18, Discrete(5), 64, DEV, reward="uniform", seed=1234, term_prob=0.02, num_agents=3)
+            env = SyntheticFixedLengthEnv(E, obs, space, 64, DEV, reward="uniform", seed=1234, term_prob=0.02, num_agents=3)
             env.term_table[-1] = True                 # every row finishes at least once per 64 steps
             return env
-        sp = Box(-np.inf, np.inf, (18,), np.float32)
-        ppo = PPO(env_gen, {"p": (MATPolicy, sp, sp, Discrete(5), {})}, device=DEV, random_seed=1, envs_per_proc=E,
+        sp = Box(-np.inf, np.inf, (obs,), np.float32)
+        ppo = PPO(env_gen, {"p": (MATPolicy, sp, sp, space, {})}, device=DEV, random_seed=1, envs_per_proc=E,
                   ts_per_rollout=32, normalize_obs=False, normalize_rewards=False, save_state=False)
+        # the opt-ins, set before the first rollout: a Box team on K16, and the evaluation forms of K20
+        ppo.policies["p"].fused_mat_box_actions = ppo.policies["p"].fused_mat_eval_forms = kind == "box" or obs > 64
     else:
         space = Box(-1.0, 1.0, (6,), np.float32)
 
@@ -192,6 +201,32 @@ def leg_b_mat(ppo, N, check_every):
             "p": {"low_score": lo, "high_score": hi, "avg_score": avg}}
 
 
+def leg_b_forms(ppo, N, check_every):
+    """test_policy with `fused_mat_eval_forms` off: the module decode a Box team or a team with observations above 64 took."""
+    pol = ppo.policies["p"]
+    pol.fused_mat_eval_forms = False
+    try:
+        assert pol.inference_unsupported_reason() != ""
+        return leg_a(ppo, N, check_every)
+    finally:
+        pol.fused_mat_eval_forms = True
+
+
+def k20_launch_us(ppo, E, n=200):
+    """Microseconds per K20 launch: HIP events around n back-to-back launches on one observation batch (deterministic mode)."""
+    pol = ppo.policies["p"]
+    obs = torch.randn(E, len(pol.agent_ids), pol.critic.in_size, device=DEV)
+    for _ in range(10):
+        pol._infer_step(obs, True)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(n):
+        pol._infer_step(obs, True)
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) * 1e3 / n
+
+
 def leg_b_lstm(ppo, N, check_every):
     """test_policy with the K21 step switched off: the route an LSTM policy's evaluation took before K21."""
     pol = ppo.policies["p"]
@@ -254,6 +289,8 @@ def main():
     ap.add_argument("--runs-per-env", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--action", default="discrete:5", help="--shape c5: the team's action space, discrete:N or box:N")
+    ap.add_argument("--obs", type=int, default=18, help="--shape c5: observation width per agent")
     ap.add_argument("--rollout-steps", type=int, default=128, help="--shape lstm: env steps per env of the timed rollouts (0: skip them)")
     args = ap.parse_args()
     from ppo_and_friends_amd import testing
@@ -264,7 +301,7 @@ def main():
     E, N = args.envs, args.envs * args.runs_per_env
     result = {"envs": E, "num_test_runs": N}
     for shape in shapes:
-        ppo = make(shape, E, max(1, args.rollout_steps) if shape == "lstm" else 32)
+        ppo = make(shape, E, max(1, args.rollout_steps) if shape == "lstm" else 32, args.obs, args.action)
         check_every = 50 if shape in ("c2", "lstm") else 64
         if shape == "lstm":
             assert ppo.policies["p"].lstm_step_unsupported_reason() == "", ppo.policies["p"].lstm_step_unsupported_reason()
@@ -275,7 +312,7 @@ def main():
         elif "a" in legs:
             assert ppo.policies["p"].inference_unsupported_reason() == "", ppo.policies["p"].inference_unsupported_reason()
         if shape == "c5" and "b" in legs:
-            legs = dict(legs, b=leg_b_mat)
+            legs = dict(legs, b=leg_b_forms if ppo.policies["p"].fused_mat_eval_forms else leg_b_mat)
         for name, fn in legs.items():
             for _ in range(args.warmup):
                 timed(fn, ppo, N, check_every)
@@ -294,6 +331,11 @@ def main():
                   f"  (loop steps {times[name][0][1]}, {np.median([dt for dt, _ in times[name]]) * 1e3:.1f} ms)", flush=True)
         if len(legs) == 2:
             result[f"{shape}_a_over_b"] = result[f"{shape}_a_env_steps_per_s"] / result[f"{shape}_b_env_steps_per_s"]
+            result[f"{shape}_a_faster_in_every_alternation"] = all(
+                sa / ta > sb / tb for (ta, sa), (tb, sb) in zip(times["a"], times["b"]))
+        if shape == "c5" and "a" in legs:
+            result["c5_k20_us_per_launch"] = k20_launch_us(ppo, E)
+            print(f"c5 K20 ({args.action}, O = {args.obs}): {result['c5_k20_us_per_launch']:.1f} us per launch", flush=True)
         del ppo
     print(json.dumps(result), flush=True)
 
