@@ -34,6 +34,27 @@ inline int check_launch(const char* what) {
         }                                            \
     } while (0)
 
+// A launch of `kernel` with more than 64 KiB of dynamic LDS needs the kernel's limit raised first, once: `done` is the call
+// site's flag for this one kernel, `what` its name in messages.  The kernel's static __shared__ counts against the same
+// 160 KiB, so the limit becomes what is left beside it, and a launch that asks for more is refused here.
+inline int allow_large_lds(const void* kernel, size_t bytes, bool& done, const char* what) {
+    if (bytes <= 64 * 1024 || done) return PPOAF_OK;
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, kernel);
+    if (e != hipSuccess) { set_error("%s: hipFuncGetAttributes: %s", what, hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+    const size_t room = 160 * 1024 - fa.sharedSizeBytes;
+    PPOAF_REQUIRE(bytes <= room, "%s: needs %zu B of dynamic LDS, %zu available beside %zu B of static LDS", what, bytes,
+                  room, (size_t)fa.sharedSizeBytes);
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room);
+    if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
+    done = true;
+    return PPOAF_OK;
+}
+template <class Kernel>
+inline int allow_large_lds(Kernel kernel, size_t bytes, bool& done, const char* what) {
+    return allow_large_lds(reinterpret_cast<const void*>(kernel), bytes, done, what);
+}
+
 // Launches whose workgroups all wait for each other need every workgroup resident at once: PPOAF_OK when `blocks`
 // workgroups of `kernel` (`threads` each, no dynamic LDS) fit on the current device together.  The occupancy is queried
 // once per kernel and device (on the first, eager, launch: nothing but the launch inside a stream capture) and cached

@@ -1048,20 +1048,6 @@ static int make_icm(const ppoaf_icm_update_args_t* a, IcmDev& u, bool training =
     return PPOAF_OK;
 }
 
-int allow_large_lds(const void* kernel, size_t bytes, bool& done, const char* what) {
-    if (bytes <= 64 * 1024 || done) return PPOAF_OK;
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, kernel);          // static __shared__ counts against the same 160 KB
-    if (e != hipSuccess) { set_error("%s: hipFuncGetAttributes: %s", what, hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-    const size_t room = 160 * 1024 - fa.sharedSizeBytes;
-    PPOAF_REQUIRE(bytes <= room, "%s: needs %zu B of dynamic LDS, %zu available beside %zu B of static LDS", what, bytes,
-                  room, (size_t)fa.sharedSizeBytes);
-    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room);
-    if (e != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-    done = true;
-    return PPOAF_OK;
-}
-
 template <int HT>
 static int launch_icm_fwd_bwd(const IcmDev& u, hipStream_t s) {
     const size_t HS = 16 * HT + 4, H = 16 * HT;

@@ -77,7 +77,5 @@ void icm_add_block(IcmWg* w, const float* D, int ldd, long seg_d, const float* X
                    long wo, int ldw, long bo);
 void icm_deal_jobs(IcmWg* w);
 int icm_launch_wgrad(const IcmDev& u, const IcmWg& w, hipStream_t stream);
-// gfx950 has 160 KB of LDS per CU; launches above the 64 KB default need the attribute set once per kernel
-int allow_large_lds(const void* kernel, size_t bytes, bool& done, const char* what);
 
 }  // namespace ppoaf

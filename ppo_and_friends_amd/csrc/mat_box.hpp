@@ -3,7 +3,7 @@
 //   Linear(NA, 64) WITH a bias over the previous agents' actions themselves (no start-token column: slot 0 sees zeros,
 //   mat_policy.py:308-344), the head's last linear gives the means of a GaussianDistribution (networks/distributions.py:
 //   441-694) whose log_std is a parameter of the bucket.
-// Everything between the encoder and the head is the Discrete kernels' code: the pieces here are called from
+// Everything between the encoder and the head is the Discrete kernels' code (mat_device.hpp): the pieces here are called from
 // `if constexpr (BOX)` branches of the same kernel bodies.
 //   K15: the token block of evaluate (mat_policy.py:378-439: slot i sees the STORED raw action of slot i - 1) and the
 //        token's own raw action [16][8] (the 512 bytes behind the 34 activation tiles); the head on wave 0, four lanes per

@@ -15,7 +15,7 @@
 // (normalised activations, pre-GELU values, q/k/v, probabilities) stays in LDS: ~147 KB of the 160 KB.
 // A mini-batch of 256 envs is 52 workgroups; the ~80 dependent phases are barrier + LDS latency
 // bound, not MFMA bound -- the point is that they replace ~270 separate kernel launches.
-#include "mlp_device.hpp"
+#include "mat_device.hpp"
 #include "running_stats_device.hpp"
 #include "tail_sync.hpp"
 #include "wgrad_tile.hpp"
@@ -25,26 +25,6 @@
 #include <cstdlib>
 
 namespace ppoaf {
-
-constexpr int kMD = 64;            // embedding width
-constexpr int kMHS = kMD + 4;      // LDS row stride of a [16, 64] tile
-constexpr int kMNW = 4;            // waves per workgroup
-constexpr int kMT = 64 * kMNW;
-constexpr int kMXS = 20;           // row stride of the action-token tile [16, 16 + 4]
-constexpr int kMTile = kRows * kMHS;
-
-// parameter tensors of MATActorCritic in module order (== bucket order); offsets in floats
-enum MatP {
-    A_ENC_W, A_LN_G, A_LN_B, A_LN1_G, A_LN1_B, A_LN2_G, A_LN2_B, A_LN3_G, A_LN3_B,
-    A_K1_W, A_K1_B, A_Q1_W, A_Q1_B, A_V1_W, A_V1_B, A_P1_W, A_P1_B,
-    A_K2_W, A_K2_B, A_Q2_W, A_Q2_B, A_V2_W, A_V2_B, A_P2_W, A_P2_B,
-    A_M1_W, A_M1_B, A_M2_W, A_M2_B, A_H1_W, A_H1_B, A_HLN_G, A_HLN_B, A_H2_W, A_H2_B,
-    C_OLN_G, C_OLN_B, C_ENC_W, C_ENC_B, C_LN_G, C_LN_B, C_LN1_G, C_LN1_B, C_LN2_G, C_LN2_B,
-    C_K_W, C_K_B, C_Q_W, C_Q_B, C_V_W, C_V_B, C_P_W, C_P_B,
-    C_M1_W, C_M1_B, C_M2_W, C_M2_B, C_H1_W, C_H1_B, C_HLN_G, C_HLN_B, C_H2_W, C_H2_B,
-    MAT_NUM_PARAMS
-};
-static_assert(MAT_NUM_PARAMS == 63, "offset table layout");
 
 struct MatDev {
     long off[64];
@@ -84,7 +64,6 @@ struct MatBoxDev : MatDev {
 
 // the 18 linears whose weight gradients the wgrad launch forms, in the order the backward meets them, and the panel that
 // holds each one's input (x1 feeds K2 / V2, x0 feeds Q1 / K1 / V1, H0 feeds Q / K / V, rep_enc feeds Q2 and the critic head)
-enum MatX { X_X3, X_GAM, X_X2, X_AY2, X_ENC, X_X1, X_AY1, X_X0, X_GCM, X_H1, X_CY, X_H0, MAT_NUM_XPANELS };
 constexpr int kMatLin = 18;
 #define PPOAF_MAT_LIN_W { A_H1_W, A_M2_W, A_M1_W, A_P2_W, A_Q2_W, A_K2_W, A_V2_W, A_P1_W, A_Q1_W, A_K1_W, A_V1_W, \
                           C_H1_W, C_M2_W, C_M1_W, C_P_W, C_Q_W, C_K_W, C_V_W }
@@ -98,667 +77,6 @@ enum MatLinId { L_A_H1, L_A_M2, L_A_M1, L_A_P2, L_A_Q2, L_A_K2, L_A_V2, L_A_P1, 
                 L_C_H1, L_C_M2, L_C_M1, L_C_P, L_C_Q, L_C_K, L_C_V };
 
 extern __shared__ __attribute__((aligned(16))) unsigned char mat_smem[];
-
-// Diagnostic build only (-DPPOAF_MAT_STAMPS, tools/mat_stamps.py): s_memtime of workgroup 0 / thread 0 at the marked points
-// of the update kernel, into a buffer nothing else reads.  The shipped library executes no stamp.
-#ifdef PPOAF_MAT_STAMPS
-static __device__ unsigned long long g_mat_stamps[64];
-#define MAT_STAMP(k)                                                                     \
-    do {                                                                                 \
-        if (blockIdx.x == 0 && threadIdx.x == 0) {                                       \
-            unsigned long long t_;                                                       \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");    \
-            g_mat_stamps[k] = t_;                                                        \
-        }                                                                                \
-    } while (0)
-#else
-#define MAT_STAMP(k) do {} while (0)
-#endif
-
-// ------------------------------------------------------------------------------------------------
-// element-wise passes over a [16, 64] tile: thread = (row = tid >> 4, lane16 = tid & 15), 4 columns each
-// ------------------------------------------------------------------------------------------------
-// Exact (erf) GELU, nn.GELU's default (multi_agent_transformer.py:51-60).  erf by Abramowitz & Stegun 7.1.26 --
-// erf(x) = 1 - (a1 t + .. + a5 t^5) exp(-x^2), t = 1 / (1 + p x), |error| <= 1.5e-7 -- instead of the library erff:
-// one exponential (the SAME exp(-z^2 / 2) the derivative's density term needs), one reciprocal and five FMAs against
-// ~85 instructions per element; a GELU pass over a tile was 1400 of a phase's 1500 cycles (tools/mat_stamps.py) and 16 of
-// the kernel's 71 phases contain one.  1.5e-7 absolute on erf is 25 x below the 1e-5 parity tolerance of every output.
-__device__ __forceinline__ void gelu_parts(float z, float& cdf, float& pdf) {
-    const float x = fabsf(z) * 0.70710678118654752440f;
-    const float e = __expf(-x * x);                            // = exp(-z^2 / 2)
-    const float t = __frcp_rn(fmaf(0.3275911f, x, 1.0f));
-    float poly = fmaf(1.061405429f, t, -1.453152027f);
-    poly = fmaf(poly, t, 1.421413741f);
-    poly = fmaf(poly, t, -0.284496736f);
-    poly = fmaf(poly, t, 0.254829592f);
-    const float erf_abs = 1.0f - poly * t * e;
-    cdf = 0.5f * (1.0f + copysignf(erf_abs, z));
-    pdf = e * 0.39894228040143267794f;
-}
-__device__ __forceinline__ float gelu_f(float z) { float cdf, pdf; gelu_parts(z, cdf, pdf); return z * cdf; }
-__device__ __forceinline__ float gelu_d(float z) { float cdf, pdf; gelu_parts(z, cdf, pdf); return cdf + z * pdf; }
-
-// out = gelu(Z)
-__device__ __forceinline__ void tile_gelu(const float* __restrict__ Z, float* __restrict__ out, int tid) {
-    const int row = tid >> 4, l = tid & 15;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) out[row * kMHS + l + 16 * j] = gelu_f(Z[row * kMHS + l + 16 * j]);
-}
-// D *= gelu'(Z)
-__device__ __forceinline__ void tile_gelu_bwd(float* __restrict__ D, const float* __restrict__ Z, int tid) {
-    const int row = tid >> 4, l = tid & 15;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) D[row * kMHS + l + 16 * j] *= gelu_d(Z[row * kMHS + l + 16 * j]);
-}
-// out = A + B
-__device__ __forceinline__ void tile_add(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ out, int tid) {
-    const int row = tid >> 4, l = tid & 15;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) out[row * kMHS + l + 16 * j] = A[row * kMHS + l + 16 * j] + B[row * kMHS + l + 16 * j];
-}
-// Y = Xhat * g + b   (LayerNorm output re-materialised for the backward)
-__device__ __forceinline__ void tile_affine(const float* __restrict__ Xhat, const float* __restrict__ g,
-                                            const float* __restrict__ b, float* __restrict__ Y, int tid) {
-    const int row = tid >> 4, l = tid & 15;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const int c = l + 16 * j; Y[row * kMHS + c] = Xhat[row * kMHS + c] * g[c] + b[c]; }
-}
-
-// LayerNorm over W <= 64 columns (tile stride `ld`): Xhat, rstd[16], Y = Xhat * g + b.  X may alias Y.
-__device__ __forceinline__ void tile_ln_fwd(const float* X, int ld, int W, const float* __restrict__ g,
-                                            const float* __restrict__ b, float* __restrict__ Xhat,
-                                            float* __restrict__ rstd, float* Y, int tid) {
-    const int row = tid >> 4, l = tid & 15;
-    float x[4], s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const int c = l + 16 * j; x[j] = c < W ? X[row * ld + c] : 0.f; s += x[j]; }
-    const float mean = group16_sum(s) / (float)W;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const int c = l + 16 * j; x[j] = c < W ? x[j] - mean : 0.f; q += x[j] * x[j]; }
-    const float rs = 1.0f / sqrtf(group16_sum(q) / (float)W + 1e-5f);
-    if (l == 0) rstd[row] = rs;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = l + 16 * j;
-        if (c < W) {
-            const float xh = x[j] * rs;
-            Xhat[row * ld + c] = xh;
-            Y[row * ld + c] = xh * g[c] + b[c];
-        }
-    }
-}
-// LayerNorm backward: DX = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)); d gamma / d beta column sums -> slab.
-// DX must not alias DY (the column sums read DY while the rows are being written).  DX == nullptr: no input gradient.
-__device__ __forceinline__ void tile_ln_bwd(const float* __restrict__ DY, int ld, int W, const float* __restrict__ Xhat,
-                                            const float* __restrict__ rstd, const float* __restrict__ g,
-                                            float* __restrict__ DX, float* __restrict__ slab_g, float* __restrict__ slab_b,
-                                            int tid) {
-    const int row = tid >> 4, l = tid & 15;
-    if (DX) {
-        float dxh[4], xh[4], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = l + 16 * j;
-            xh[j] = c < W ? Xhat[row * ld + c] : 0.f;
-            dxh[j] = c < W ? DY[row * ld + c] * g[c] : 0.f;
-            s1 += dxh[j]; s2 += dxh[j] * xh[j];
-        }
-        const float m1 = group16_sum(s1) / (float)W, m2 = group16_sum(s2) / (float)W, rs = rstd[row];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int c = l + 16 * j; if (c < W) DX[row * ld + c] = (dxh[j] - m1 - xh[j] * m2) * rs; }
-    }
-    if (tid < 64) {
-        if (tid < W) {
-            float a = 0.f;
-#pragma unroll
-            for (int s = 0; s < kRows; ++s) a = fmaf(DY[s * ld + tid], Xhat[s * ld + tid], a);
-            slab_g[tid] = a;
-        }
-    } else if (tid < 128) {
-        const int c = tid - 64;
-        if (c < W) {
-            float a = 0.f;
-#pragma unroll
-            for (int s = 0; s < kRows; ++s) a += DY[s * ld + c];
-            slab_b[c] = a;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// linears on [16, 64] tiles (one output tile of 16 columns per wave)
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lin_fwd(const float* __restrict__ W, const float* __restrict__ bias,
-                                        const float* __restrict__ A, float* __restrict__ out, int wave, int lane) {
-    layer_fwd<4, true, kMNW>(W, kMD, bias, A, out, -1, wave, lane);
-}
-__device__ __forceinline__ void lin_wgrad(const float* __restrict__ Dt, const float* __restrict__ In,
-                                          float* __restrict__ dW, float* __restrict__ dB, int wave, int lane, int tid) {
-    layer_wgrad<4, kMNW>(Dt, In, kMHS, 4, kMD, dW, kMD, dB, wave, lane, tid);
-}
-// out (+)= Dt . W   (out must not alias Dt)
-template <bool ACCUM>
-__device__ __forceinline__ void lin_dgrad(const float* __restrict__ W, const float* __restrict__ Dt,
-                                          float* __restrict__ out, int wave, int lane) {
-    float4 fr[4];
-    load_dgrad_frags_ld<4>(W, kMD, wave * 16, lane, fr);
-    const f32x4 acc = mfma_rows_x_frags<4>(Dt, kMHS, lane, fr, 0.f);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int idx = (4 * (lane >> 4) + r) * kMHS + wave * 16 + (lane & 15);
-        out[idx] = ACCUM ? out[idx] + acc[r] : acc[r];
-    }
-}
-
-// split-wgrad chain: a settled [16, 64] LDS tile -> rows [16 g, +16) of a [R][64] panel (one float4 per thread)
-__device__ __forceinline__ void publish_tile(const float* __restrict__ T, float* __restrict__ panel, int g, int tid) {
-    const int r = tid >> 4, c4 = tid & 15;
-    *reinterpret_cast<float4*>(panel + ((long)g * kRows + r) * kMD + 4 * c4) =
-        *reinterpret_cast<const float4*>(T + r * kMHS + 4 * c4);
-}
-
-// The same linears with their weight fragments REQUESTED AHEAD: a wave's share of a 64x64 linear is 4 float4 per lane (+ its
-// bias element).  A phase of this kernel is a dependent chain -- barrier, weight fragments from the L2 (~400 cycles), A
-// from LDS, 16 MFMAs (32 cycles each), LDS stores, barrier: ~1800 cycles by in-kernel stamps, tools/mat_stamps.py -- and
-// the 400 cycles of fragment latency sit at the head of 45 of the 71 phases.  The update kernel therefore requests the
-// fragments of the NEXT linear at the start of the phase that runs the current one (they land behind its MFMAs and the
-// barrier).  Not deeper: vmcnt retires in order, so with a whole pass's fragments in flight every small load issued
-// after them (LayerNorm gains, biases) waited for all of them -- measured slower than no prefetch at all.
-struct MatFr { float4 f[4]; float b; };
-__device__ __forceinline__ void pf_fwd(const float* __restrict__ W, const float* __restrict__ bias, int wave, int lane, MatFr& r) {
-    load_fwd_frags_ld<4, true>(W, kMD, wave * 16, lane, r.f);
-    r.b = bias[wave * 16 + (lane & 15)];
-}
-__device__ __forceinline__ void pf_dgrad(const float* __restrict__ W, int wave, int lane, MatFr& r) {
-    load_dgrad_frags_ld<4>(W, kMD, wave * 16, lane, r.f);
-    r.b = 0.f;
-}
-__device__ __forceinline__ void lin_fwd_r(const MatFr& r, const float* __restrict__ A, float* __restrict__ out, int wave, int lane) {
-    const int o = wave * 16 + (lane & 15);
-    const f32x4 acc = mfma_rows_x_frags<4>(A, kMHS, lane, r.f, r.b);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[(4 * (lane >> 4) + q) * kMHS + o] = acc[q];
-}
-template <bool ACCUM>
-__device__ __forceinline__ void lin_dgrad_r(const MatFr& r, const float* __restrict__ Dt, float* __restrict__ out, int wave, int lane) {
-    const f32x4 acc = mfma_rows_x_frags<4>(Dt, kMHS, lane, r.f, 0.f);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int idx = (4 * (lane >> 4) + q) * kMHS + wave * 16 + (lane & 15);
-        out[idx] = ACCUM ? out[idx] + acc[q] : acc[q];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// attention core on LDS tiles (K9's block-diagonal packing).  Q, K, V, Y, dY ... are [16, 64] tiles.
-// ------------------------------------------------------------------------------------------------
-// out[:, 16 nt ..] = A[16,16] . Z[:, 16 nt ..]; A from the 17-stride tile T, as is or transposed
-__device__ __forceinline__ void att_a_times(const float* __restrict__ T, bool transposed, const float* __restrict__ Z,
-                                            float* __restrict__ out, int nt, int lane) {
-    const int i = lane & 15, slot = lane >> 4;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int kk = 4 * slot + j;
-        const float a = transposed ? T[kk * 17 + i] : T[i * 17 + kk];
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Z[kk * kMHS + 16 * nt + i], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[(4 * slot + r) * kMHS + 16 * nt + i] = acc[r];
-}
-// One 16-wide K chunk of X Y^T (X, Y: [16, 64] tiles): the wave's share of a score tile
-__device__ __forceinline__ f32x4 att_xyT_chunk(const float* __restrict__ X, const float* __restrict__ Y, int chunk, int lane) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const float4 a = *reinterpret_cast<const float4*>(X + (lane & 15) * kMHS + 16 * chunk + 4 * (lane >> 4));
-    const float4 b = *reinterpret_cast<const float4*>(Y + (lane & 15) * kMHS + 16 * chunk + 4 * (lane >> 4));
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-    return acc;
-}
-// forward: probabilities -> sP (kept for the backward), Y = P V.  Three barriers inside, none after.
-// The 16 x 16 score tile is ONE MFMA output tile: instead of one wave running its 16 dependent MFMAs and the softmax of all
-// 16 rows while three waves wait (stamps: 3.6 k cycles per attention), every wave takes one 16-wide K chunk (4 MFMAs), the
-// four partial tiles meet in LDS (the Y tile is free until the last phase), and every wave runs the softmax of 4 rows, one
-// row per 16 lanes.
-__device__ __forceinline__ void att_fwd(const float* Q, const float* K, const float* V, float* Y, float* sP,
-                                        int L, int n_rows, bool masked, int wave, int lane) {
-    {
-        const f32x4 s = att_xyT_chunk(Q, K, wave, lane);
-        const int col = lane & 15;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Y[wave * 272 + (4 * (lane >> 4) + r) * 17 + col] = s[r];
-    }
-    __syncthreads();
-    {
-        const int row = 4 * wave + (lane >> 4), col = lane & 15;
-        const float sc = (Y[row * 17 + col] + Y[272 + row * 17 + col]) + (Y[544 + row * 17 + col] + Y[816 + row * 17 + col]);
-        bool ok = row < n_rows && col < n_rows && (row / L) == (col / L);
-        if (masked) ok = ok && (col % L) <= (row % L);
-        const float x = ok ? sc * 0.125f : -INFINITY;                       // 1 / sqrt(64)
-        const float m = group16_max(x);
-        const float e = ok ? expf(x - m) : 0.f;
-        const float den = group16_sum(e);
-        sP[row * 17 + col] = den > 0.f ? e / den : 0.f;
-    }
-    __syncthreads();
-    att_a_times(sP, false, V, Y, wave, lane);
-}
-// backward from dY: dQ, dK, dV (three distinct output tiles); sS is a 17-stride scratch tile; the partial tiles of
-// dP = dY V^T meet in the dQ tile (written only in the last phase)
-__device__ __forceinline__ void att_bwd(const float* Q, const float* K, const float* V, const float* sP, const float* dY,
-                                        float* dQ, float* dK, float* dV, float* sS, int wave, int lane) {
-    {
-        const f32x4 dp = att_xyT_chunk(dY, V, wave, lane);
-        const int col = lane & 15;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dQ[wave * 272 + (4 * (lane >> 4) + r) * 17 + col] = dp[r];
-    }
-    __syncthreads();
-    {
-        const int row = 4 * wave + (lane >> 4), col = lane & 15;
-        const float dp = (dQ[row * 17 + col] + dQ[272 + row * 17 + col]) + (dQ[544 + row * 17 + col] + dQ[816 + row * 17 + col]);
-        const float p = sP[row * 17 + col];
-        const float dot = group16_sum(dp * p);
-        sS[row * 17 + col] = p * (dp - dot) * 0.125f;
-    }
-    __syncthreads();
-    att_a_times(sP, true, dY, dV, wave, lane);      // dV = P^T dY
-    att_a_times(sS, false, K, dQ, wave, lane);      // dQ = dS K
-    att_a_times(sS, true, Q, dK, wave, lane);       // dK = dS^T Q
-}
-
-// ------------------------------------------------------------------------------------------------
-// narrow first layers (observation encoder K = O, action encoder K = Ain): weights [64, K] row-major
-// ------------------------------------------------------------------------------------------------
-// acc += X[:, 0 .. kend) . W[o, c0 .. c0 + kend)^T for the wave's 16 outputs o: X is a tile (stride ldx) whose column 0 is
-// input column c0 of W's rows (stride Kdim, zero beyond it); k ascends, so chunks called in order are the unchunked chain
-__device__ __forceinline__ void narrow_fwd_acc(const float* __restrict__ W, int Kdim, int c0, int kend,
-                                               const float* __restrict__ X, int ldx, f32x4& acc, int wave, int lane) {
-    const int o = wave * 16 + (lane & 15);
-    const float* w = W + (long)o * Kdim + c0;
-    const float* arow = X + (lane & 15) * ldx;
-    for (int k0 = 0; k0 < kend; k0 += 16) {
-        float bq[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { const int k = k0 + 4 * j + (lane >> 4); bq[j] = c0 + k < Kdim ? w[k] : 0.f; }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(arow[k0 + 4 * j + (lane >> 4)], bq[j], acc, 0, 0, 0);
-    }
-}
-__device__ __forceinline__ void narrow_store(const f32x4& acc, float* __restrict__ out, int wave, int lane) {
-    const int o = wave * 16 + (lane & 15);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[(4 * (lane >> 4) + r) * kMHS + o] = acc[r];
-}
-__device__ __forceinline__ void narrow_fwd(const float* __restrict__ W, int Kdim, const float* __restrict__ bias,
-                                           const float* __restrict__ X, int ldx, float* __restrict__ out, int wave, int lane) {
-    const float bv = bias ? bias[wave * 16 + (lane & 15)] : 0.f;
-    f32x4 acc = {bv, bv, bv, bv};
-    narrow_fwd_acc(W, Kdim, 0, Kdim, X, ldx, acc, wave, lane);
-    narrow_store(acc, out, wave, lane);
-}
-// dX[16, n] = D[16,64] . W[64, 0 .. n) for rows of W of stride ldw (tile stride ldx; columns >= n untouched)
-__device__ __forceinline__ void narrow_dgrad(const float* __restrict__ W, int ldw, int n, const float* __restrict__ Dt,
-                                             float* __restrict__ dX, int ldx, int wave, int lane) {
-    for (int nt = wave; nt * 16 < n; nt += kMNW) {
-        const int i = nt * 16 + (lane & 15);
-        float4 fr[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float* wp = W + (long)(16 * c + 4 * (lane >> 4)) * ldw + i;
-            fr[c] = i < n ? make_float4(wp[0], wp[ldw], wp[2 * ldw], wp[3 * ldw]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        const f32x4 acc = mfma_rows_x_frags<4>(Dt, kMHS, lane, fr, 0.f);
-        if (i < n) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dX[(4 * (lane >> 4) + r) * ldx + i] = acc[r];
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// narrow output layers (64 -> n_out <= 8) on the VALU
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void head_out_fwd(const float* __restrict__ W, const float* __restrict__ bias, int n_out,
-                                             const float* __restrict__ Hh, float* __restrict__ sOut, int tid) {
-    const int s = tid >> 4, part = tid & 15;
-    for (int k = 0; k < n_out; ++k) {
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc = fmaf(Hh[s * kMHS + part + 16 * i], W[k * kMD + part + 16 * i], acc);
-        acc = group16_sum(acc);
-        if (part == 0) sOut[s * 8 + k] = acc + bias[k];
-    }
-}
-// dW[k][i], db[k] -> slab; dH[s][i] = sum_k dOut[s][k] W[k][i]
-__device__ __forceinline__ void head_out_bwd(const float* __restrict__ W, int n_out, const float* __restrict__ Hh,
-                                             const float* __restrict__ sDOut, float* __restrict__ dH,
-                                             float* __restrict__ slabW, float* __restrict__ slabB, int tid) {
-    if (tid < kMD) {
-        float h[kRows];
-#pragma unroll
-        for (int s = 0; s < kRows; ++s) h[s] = Hh[s * kMHS + tid];
-        for (int k = 0; k < n_out; ++k) {
-            float acc = 0.f;
-#pragma unroll
-            for (int s = 0; s < kRows; ++s) acc = fmaf(sDOut[s * 8 + k], h[s], acc);
-            slabW[k * kMD + tid] = acc;
-        }
-    } else if (tid < kMD + 8) {
-        const int k = tid - kMD;
-        float acc = 0.f;
-        if (k < n_out)
-#pragma unroll
-            for (int s = 0; s < kRows; ++s) acc += sDOut[s * 8 + k];
-        if (k < ((n_out + 3) & ~3)) slabB[k] = acc;
-    }
-    const int s = tid >> 4, part = tid & 15;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < n_out; ++k) {
-        const float d = sDOut[s * 8 + k];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i] = fmaf(d, W[k * kMD + part + 16 * i], acc[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dH[s * kMHS + part + 16 * i] = acc[i];
-}
-
-// Barriers separate phases whose readers use a different thread <-> element mapping than the writers (MFMA
-// tiles vs the 16-lanes-per-row passes).  Row-pass -> row-pass sequences (add -> LayerNorm, GELU -> LayerNorm,
-// LayerNorm backward -> GELU backward) and accumulating dgrads into one tile touch only a thread's own elements
-// and run without one.
-#define MAT_SYNC() __syncthreads()
-
-// tile indices: saved activations of the critic (0-11) and the actor (12-27), scratch (28-33)
-enum { cZ1_ = 0, cN0_, cQ_, cK_, cV_, cY_, cN1_, cZM_, cN2_, cENC_, cZH_, cNH_,
-       aZ_, aN0_, aQ1_, aK1_, aV1_, aY1_, aN1_, aK2_, aV2_, aQ2_, aY2_, aN2_, aZM_, aN3_, aZH_, aNH_,
-       S0_, S1_, S2_, S3_, S4_, DENC_, MAT_NUM_TILES };
-
-// Forward-only carve (K20): nothing is read back by a backward pass, so tiles whose lives never overlap share storage.
-//   0 rep_enc (live through every decoder pass)   1-4 S0..S3   5 every pre-GELU tile (written by a linear, read by the
-//   next phase's GELU)   6 / 7 / 8 q / k / v of the attention in flight   9 its y -- and every saved x-hat: a LayerNorm
-//   writes it and nobody reads it, and no LayerNorm runs between an attention and the projection that consumes y
-constexpr int kMatFwdTiles = 10;
-constexpr int mat_fwd_tile(int k) {
-    return k == cENC_ ? 0
-         : (k >= S0_ && k <= S3_) ? 1 + (k - S0_)
-         : (k == cZ1_ || k == cZM_ || k == cZH_ || k == aZ_ || k == aZM_ || k == aZH_) ? 5
-         : (k == cQ_ || k == aQ1_ || k == aQ2_) ? 6
-         : (k == cK_ || k == aK1_ || k == aK2_) ? 7
-         : (k == cV_ || k == aV1_ || k == aV2_) ? 8
-         : 9;                                                // y, x-hat; S4 / DENC exist only in the backward
-}
-
-// Observation widths: up to kMONarrow the rows are staged whole in LDS; wider ones (WIDE, up to kMOWide) stream through two
-// [16][kMOCS] chunk tiles of kMOC columns (mat_obs_encoder_wide), so the carve is that of a kMONarrow-wide launch plus the
-// [16] row means -- two whole [16][pad16(O) + 4] tiles beside the 34 activation tiles pass the CU's 160 KiB at O = 49.
-constexpr int kMONarrow = 32, kMOWide = 128;
-constexpr int kMOC = 32;           // columns of a chunk
-constexpr int kMOCS = kMOC + 4;    // row stride of a chunk tile
-
-// LDS carve shared by the update kernel (K15), the rollout step kernel (K16) and, with FWD, the evaluation step (K20)
-template <bool FWD, bool WIDE = false>
-struct MatCtxT {
-    static constexpr bool kWide = WIDE;
-    const float* P; const long* off;
-    int O, L, NA, Ain, OS, n_rows;
-    int* sRow; int* sAct; float* sMisc; float* sRowF; float* sRstd; float* sMean;
-    float *sOutC, *sOutA, *sDOutC, *sDOutA, *sP0, *sP1, *sP2, *sS, *sXA, *sXO, *sYO, *T;
-    __device__ __forceinline__ float* tile(int k) const { return T + (long)(FWD ? mat_fwd_tile(k) : k) * kMTile; }
-    __device__ __forceinline__ float* rstd(int k) const { return sRstd + 16 * k; }
-    __device__ __forceinline__ const float* W(int k) const { return P + off[k]; }
-    __device__ __forceinline__ void carve(float* sm, int O_) {
-        O = O_; OS = WIDE ? kMOCS : 16 * ((O_ + 15) >> 4) + 4;
-        sRow = reinterpret_cast<int*>(sm);                 // [16] buffer row of the token's env (-1: padding)
-        sAct = reinterpret_cast<int*>(sm) + 16;            // [16] action of the token
-        sMisc = sm + 32;                                   // [8] adv mean/std, vn mean/var
-        sRowF = sm + 48;                                   // [3][16] adv, old log-prob, rewards-to-go
-        sRstd = sm + 96;                                   // [10][16]
-        sOutC = sm + 256;                                  // [16][8] critic output (col 0)
-        sOutA = sOutC + 128;                               // [16][8] logits
-        if constexpr (FWD) {
-            sDOutC = sDOutA = nullptr;
-            sP0 = sP1 = sP2 = sS = sOutA + 128;            // one probability tile [16][17]: the attentions run one at a time
-            sXA = sP0 + 272;                               // [16][kMXS] action tokens
-            sYO = sXA + kRows * kMXS;                      // [16][OS] observations, then the observation LayerNorm's output
-            sMean = sYO + kRows * OS;                      // WIDE: [16] row means
-            T = sMean + (WIDE ? kRows : 0);
-            sXO = tile(cY_);                               // its x-hat: unread (OS <= kMHS, so it fits the tile); WIDE: the
-                                                           // second chunk tile
-        } else {
-            sDOutC = sOutA + 128;
-            sDOutA = sDOutC + 128;
-            sP0 = sDOutA + 128;                            // 3 probability tiles + 1 dS scratch, [16][17] each
-            sP1 = sP0 + 272;
-            sP2 = sP1 + 272;
-            sS = sP2 + 272;
-            sXA = sS + 272;                                // [16][kMXS] action tokens
-            sXO = sXA + kRows * kMXS;                      // [16][OS] xhat of the observation LayerNorm
-            sYO = sXO + kRows * OS;                        // [16][OS] its output (input of the encoder linear)
-            sMean = sYO + kRows * OS;                      // WIDE (sXO / sYO are the two chunk tiles): [16] row means
-            T = sMean + (WIDE ? kRows : 0);                // [16][68] tiles from here on
-        }
-    }
-};
-using MatCtx = MatCtxT<false>;
-
-#define MAT_TILES(c)                                                                                              \
-    float *cZ1 = c.tile(cZ1_), *cN0 = c.tile(cN0_), *cQ = c.tile(cQ_), *cK = c.tile(cK_), *cV = c.tile(cV_),       \
-          *cY = c.tile(cY_), *cN1 = c.tile(cN1_), *cZM = c.tile(cZM_), *cN2 = c.tile(cN2_), *cENC = c.tile(cENC_), \
-          *cZH = c.tile(cZH_), *cNH = c.tile(cNH_);                                                               \
-    float *aZ = c.tile(aZ_), *aN0 = c.tile(aN0_), *aQ1 = c.tile(aQ1_), *aK1 = c.tile(aK1_), *aV1 = c.tile(aV1_),   \
-          *aY1 = c.tile(aY1_), *aN1 = c.tile(aN1_), *aK2 = c.tile(aK2_), *aV2 = c.tile(aV2_), *aQ2 = c.tile(aQ2_), \
-          *aY2 = c.tile(aY2_), *aN2 = c.tile(aN2_), *aZM = c.tile(aZM_), *aN3 = c.tile(aN3_), *aZH = c.tile(aZH_), \
-          *aNH = c.tile(aNH_);                                                                                    \
-    float *S0 = c.tile(S0_), *S1 = c.tile(S1_), *S2 = c.tile(S2_), *S3 = c.tile(S3_), *S4 = c.tile(S4_),           \
-          *DENC = c.tile(DENC_);                                                                                  \
-    (void)cZ1; (void)cN0; (void)cQ; (void)cK; (void)cV; (void)cY; (void)cN1; (void)cZM; (void)cN2; (void)cENC;     \
-    (void)cZH; (void)cNH; (void)aZ; (void)aN0; (void)aQ1; (void)aK1; (void)aV1; (void)aY1; (void)aN1; (void)aK2;   \
-    (void)aV2; (void)aQ2; (void)aY2; (void)aN2; (void)aZM; (void)aN3; (void)aZH; (void)aNH; (void)S0; (void)S1;   \
-    (void)S2; (void)S3; (void)S4; (void)DENC;                                                                     \
-    float *sXA = c.sXA, *sXO = c.sXO, *sYO = c.sYO, *sP0 = c.sP0, *sP1 = c.sP1, *sP2 = c.sP2, *sS = c.sS,          \
-          *sOutC = c.sOutC, *sOutA = c.sOutA;                                                                     \
-    (void)sXA; (void)sXO; (void)sYO; (void)sP0; (void)sP1; (void)sP2; (void)sS; (void)sOutC; (void)sOutA;          \
-    const int O = c.O, L = c.L, NA = c.NA, Ain = c.Ain, OS = c.OS, n_rows = c.n_rows;                              \
-    (void)O; (void)L; (void)NA; (void)Ain; (void)OS; (void)n_rows;                                                \
-    auto W = [&](int k) -> const float* { return c.W(k); };                                                       \
-    auto rstd = [&](int k) -> float* { return c.rstd(k); };                                                       \
-    (void)W; (void)rstd
-
-// split-wgrad chain: the forward publishes every linear's input tile the moment it is settled (the backward then has
-// no reason to rebuild it from the saved normalised activations); K16 and the slab form publish nothing
-struct MatNoPub { __device__ __forceinline__ void operator()(int, const float*) const {} };
-struct MatPanelPub {
-    float* xpanel; long plane; int g, tid;
-    __device__ __forceinline__ void operator()(int xid, const float* T) const { publish_tile(T, xpanel + (long)xid * plane, g, tid); }
-};
-
-// obs_encoder.0 + obs_encoder.1 of a WIDE carve: LayerNorm(O) -> Linear(O, 64) pre-GELU values -> `out`, no barrier after.
-// Thread (row = tid >> 4, l = tid & 15) holds columns l + 16 j of its row, read from global memory (orow: the token's
-// observation row, nullptr for a padding row -- read as zeros, as the staged form's zeroed tile); mean and rstd by
-// tile_ln_fwd's two-pass arithmetic, both kept for the backward.  Then per chunk of kMOC columns: y = xhat g + b into one of
-// the two chunk tiles (alternating: one barrier per chunk), accumulated into the wave's MFMA chain with k ascending.
-template <typename Ctx>
-__device__ __forceinline__ void mat_obs_encoder_wide(const Ctx& c, const float* __restrict__ orow, float* __restrict__ out,
-                                                     int tid, int wave, int lane) {
-    const int O = c.O, row = tid >> 4, l = tid & 15;
-    const float* __restrict__ g = c.W(C_OLN_G);
-    const float* __restrict__ b = c.W(C_OLN_B);
-    constexpr int NJ = kMOWide / 16;
-    float x[NJ], s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { const int col = l + 16 * j; x[j] = (orow && col < O) ? orow[col] : 0.f; s += x[j]; }
-    const float mean = group16_sum(s) / (float)O;
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { const int col = l + 16 * j; x[j] = col < O ? x[j] - mean : 0.f; q += x[j] * x[j]; }
-    const float rs = 1.0f / sqrtf(group16_sum(q) / (float)O + 1e-5f);
-    if (l == 0) { c.rstd(0)[row] = rs; c.sMean[row] = mean; }
-    const float bv = c.W(C_ENC_B)[wave * 16 + (lane & 15)];
-    f32x4 acc = {bv, bv, bv, bv};
-#pragma unroll
-    for (int ci = 0; ci < kMOWide / kMOC; ++ci) {
-        const int c0 = kMOC * ci;
-        if (c0 < O) {                                                  // uniform: every thread meets the barrier
-            float* Y = (ci & 1) ? c.sXO : c.sYO;
-#pragma unroll
-            for (int jj = 0; jj < kMOC / 16; ++jj) {
-                const int col = c0 + l + 16 * jj;
-                Y[row * kMOCS + l + 16 * jj] = col < O ? x[(kMOC / 16) * ci + jj] * rs * g[col] + b[col] : 0.f;
-            }
-            MAT_SYNC();
-            const int cw = O - c0 < kMOC ? O - c0 : kMOC;
-            narrow_fwd_acc(c.W(C_ENC_W), O, c0, 16 * ((cw + 15) >> 4), Y, kMOCS, acc, wave, lane);
-        }
-    }
-    narrow_store(acc, out, wave, lane);
-}
-
-// critic (encoder): observations in sYO (a WIDE carve: read through orow) -> rep_enc in cENC, value in sOutC[:, 0]; ends
-// WITHOUT a barrier
-// PF (K15): the fragments of linear `n` are requested one phase ahead -- MAT_NEXT(n) at the start of the phase before;
-// else (K16: its registers are spoken for) at the point of use
-#define MAT_LIN(r, Wk, Bk, A, out) do { if (!PF) pf_fwd(W(Wk), W(Bk), wave, lane, r); lin_fwd_r(r, A, out, wave, lane); } while (0)
-#define MAT_NEXT(r, Wk, Bk) do { if (PF) pf_fwd(W(Wk), W(Bk), wave, lane, r); } while (0)
-// VALUE = false (K20): stops at rep_enc, after a barrier -- the three phases of the value head are not run
-template <bool PF, typename Pub = MatNoPub, bool VALUE = true, typename Ctx = MatCtx>
-__device__ __forceinline__ void mat_encoder_forward(const Ctx& c, int tid, int wave, int lane, const Pub pub = Pub(),
-                                                    const float* orow = nullptr) {
-    MAT_TILES(c);
-    MatFr rq, rk, rv, rp, rm1, rm2, rh1;
-    MAT_NEXT(rq, C_Q_W, C_Q_B); MAT_NEXT(rk, C_K_W, C_K_B); MAT_NEXT(rv, C_V_W, C_V_B);       // two phases ahead of their use
-    if constexpr (Ctx::kWide) {
-        mat_obs_encoder_wide(c, orow, cZ1, tid, wave, lane);                                  // obs_encoder.0 and .1
-    } else {
-        tile_ln_fwd(sYO, OS, O, W(C_OLN_G), W(C_OLN_B), sXO, rstd(0), sYO, tid);              // obs_encoder.0
-        MAT_SYNC();
-        MAT_STAMP(16);
-        narrow_fwd(W(C_ENC_W), O, W(C_ENC_B), sYO, OS, cZ1, wave, lane);                      // obs_encoder.1
-    }
-    MAT_SYNC();
-    MAT_STAMP(17);
-    tile_gelu(cZ1, S0, tid);
-    tile_ln_fwd(S0, kMHS, kMD, W(C_LN_G), W(C_LN_B), cN0, rstd(1), S1, tid);                  // critic.ln -> H0 in S1
-    MAT_SYNC();
-    MAT_STAMP(18);
-    pub(X_H0, S1);
-    MAT_NEXT(rp, C_P_W, C_P_B);
-    MAT_LIN(rq, C_Q_W, C_Q_B, S1, cQ);
-    MAT_LIN(rk, C_K_W, C_K_B, S1, cK);
-    MAT_LIN(rv, C_V_W, C_V_B, S1, cV);
-    MAT_SYNC();
-    MAT_STAMP(19);
-    att_fwd(cQ, cK, cV, cY, sP0, L, n_rows, false, wave, lane);
-    MAT_SYNC();
-    MAT_STAMP(20);
-    pub(X_CY, cY);
-    MAT_NEXT(rm1, C_M1_W, C_M1_B);
-    MAT_LIN(rp, C_P_W, C_P_B, cY, S2);
-    MAT_SYNC();
-    MAT_STAMP(21);
-    tile_add(S1, S2, S2, tid);
-    tile_ln_fwd(S2, kMHS, kMD, W(C_LN1_G), W(C_LN1_B), cN1, rstd(2), S0, tid);                // H1 in S0
-    MAT_SYNC();
-    MAT_STAMP(22);
-    pub(X_H1, S0);
-    MAT_NEXT(rm2, C_M2_W, C_M2_B);
-    MAT_LIN(rm1, C_M1_W, C_M1_B, S0, cZM);
-    MAT_SYNC();
-    MAT_STAMP(23);
-    tile_gelu(cZM, S2, tid);
-    MAT_SYNC();
-    MAT_STAMP(24);
-    pub(X_GCM, S2);
-    MAT_NEXT(rh1, C_H1_W, C_H1_B);
-    MAT_LIN(rm2, C_M2_W, C_M2_B, S2, S3);
-    MAT_SYNC();
-    MAT_STAMP(25);
-    tile_add(S0, S3, S3, tid);
-    tile_ln_fwd(S3, kMHS, kMD, W(C_LN2_G), W(C_LN2_B), cN2, rstd(3), cENC, tid);              // rep_enc
-    MAT_SYNC();
-    MAT_STAMP(26);
-    pub(X_ENC, cENC);
-    if constexpr (!VALUE) return;
-    MAT_LIN(rh1, C_H1_W, C_H1_B, cENC, cZH);
-    MAT_SYNC();
-    MAT_STAMP(27);
-    tile_gelu(cZH, S0, tid);
-    tile_ln_fwd(S0, kMHS, kMD, W(C_HLN_G), W(C_HLN_B), cNH, rstd(4), S1, tid);
-    MAT_SYNC();
-    MAT_STAMP(28);
-    head_out_fwd(W(C_H2_W), W(C_H2_B), 1, S1, sOutC, tid);
-
-}
-
-// actor (decoder): token block in sXA + rep_enc in cENC -> logits in sOutA; starts and ends with the tiles settled
-template <bool PF, typename Pub = MatNoPub, typename Ctx = MatCtx>
-__device__ __forceinline__ void mat_decoder_forward(const Ctx& c, int tid, int wave, int lane, const Pub pub = Pub(),
-                                                    const float* enc_bias = nullptr) {
-    MAT_TILES(c);
-    MatFr rk1, rq1, rv1, rp1, rk2, rv2, rq2, rp2, rm1, rm2, rh1;
-    MAT_NEXT(rk1, A_K1_W, A_K1_B); MAT_NEXT(rq1, A_Q1_W, A_Q1_B); MAT_NEXT(rv1, A_V1_W, A_V1_B);
-    narrow_fwd(W(A_ENC_W), Ain, enc_bias, sXA, kMXS, aZ, wave, lane);                         // action_encoder.0 (Box: a bias)
-    MAT_SYNC();
-    tile_gelu(aZ, S0, tid);
-    tile_ln_fwd(S0, kMHS, kMD, W(A_LN_G), W(A_LN_B), aN0, rstd(5), S1, tid);                  // x0 in S1
-    MAT_SYNC();
-    pub(X_X0, S1);
-    MAT_NEXT(rp1, A_P1_W, A_P1_B);
-    MAT_LIN(rk1, A_K1_W, A_K1_B, S1, aK1);
-    MAT_LIN(rq1, A_Q1_W, A_Q1_B, S1, aQ1);
-    MAT_LIN(rv1, A_V1_W, A_V1_B, S1, aV1);
-    MAT_SYNC();
-    att_fwd(aQ1, aK1, aV1, aY1, sP1, L, n_rows, true, wave, lane);
-    MAT_SYNC();
-    pub(X_AY1, aY1);
-    MAT_NEXT(rk2, A_K2_W, A_K2_B); MAT_NEXT(rv2, A_V2_W, A_V2_B); MAT_NEXT(rq2, A_Q2_W, A_Q2_B);
-    MAT_LIN(rp1, A_P1_W, A_P1_B, aY1, S2);
-    MAT_SYNC();
-    tile_add(S1, S2, S2, tid);
-    tile_ln_fwd(S2, kMHS, kMD, W(A_LN1_G), W(A_LN1_B), aN1, rstd(6), S0, tid);                // x1 in S0
-    MAT_SYNC();
-    pub(X_X1, S0);
-    MAT_NEXT(rp2, A_P2_W, A_P2_B);
-    MAT_LIN(rk2, A_K2_W, A_K2_B, S0, aK2);                                       // key = value = x1
-    MAT_LIN(rv2, A_V2_W, A_V2_B, S0, aV2);
-    MAT_LIN(rq2, A_Q2_W, A_Q2_B, cENC, aQ2);                                     // query = rep_enc
-    MAT_SYNC();
-    att_fwd(aQ2, aK2, aV2, aY2, sP2, L, n_rows, true, wave, lane);
-    MAT_SYNC();
-    pub(X_AY2, aY2);
-    MAT_NEXT(rm1, A_M1_W, A_M1_B);
-    MAT_LIN(rp2, A_P2_W, A_P2_B, aY2, S2);
-    MAT_SYNC();
-    tile_add(cENC, S2, S2, tid);
-    tile_ln_fwd(S2, kMHS, kMD, W(A_LN2_G), W(A_LN2_B), aN2, rstd(7), S1, tid);                // x2 in S1
-    MAT_SYNC();
-    pub(X_X2, S1);
-    MAT_NEXT(rm2, A_M2_W, A_M2_B);
-    MAT_LIN(rm1, A_M1_W, A_M1_B, S1, aZM);
-    MAT_SYNC();
-    tile_gelu(aZM, S2, tid);
-    MAT_SYNC();
-    pub(X_GAM, S2);
-    MAT_NEXT(rh1, A_H1_W, A_H1_B);
-    MAT_LIN(rm2, A_M2_W, A_M2_B, S2, S3);
-    MAT_SYNC();
-    tile_add(S1, S3, S3, tid);
-    tile_ln_fwd(S3, kMHS, kMD, W(A_LN3_G), W(A_LN3_B), aN3, rstd(8), S0, tid);                // x3 in S0
-    MAT_SYNC();
-    pub(X_X3, S0);
-    MAT_LIN(rh1, A_H1_W, A_H1_B, S0, aZH);
-    MAT_SYNC();
-    tile_gelu(aZH, S2, tid);
-    tile_ln_fwd(S2, kMHS, kMD, W(A_HLN_G), W(A_HLN_B), aNH, rstd(9), S1, tid);                // head LayerNorm output in S1
-    MAT_SYNC();
-    head_out_fwd(W(A_H2_W), W(A_H2_B), NA, S1, sOutA, tid);
-    MAT_SYNC();
-
-}
 
 
 // SPLIT: the weight gradients of the 18 64x64 linears are NOT formed here (a third of the kernel's MFMA work, on the
@@ -1757,6 +1075,9 @@ static size_t mat_obs_lds_floats(int O, int n_tiles) {
 static size_t mat_lds_bytes(int O) {
     return (256 + 4 * 128 + 4 * 272 + kRows * kMXS + mat_obs_lds_floats(O, 2) + 34 * (size_t)kMTile) * 4;
 }
+static size_t mat_fwd_lds_bytes(int O) {
+    return (256 + 2 * 128 + 272 + kRows * kMXS + mat_obs_lds_floats(O, 1) + kMatFwdTiles * (size_t)kMTile) * 4;
+}
 
 // the offset table of MATActorCritic's parameters in module order, every tensor padded to 4 floats -> want[]; returns the
 // bucket's size in floats
@@ -1781,10 +1102,6 @@ static long mat_offset_table(long O, long NA, long* want) {
     return off;
 }
 
-static size_t mat_fwd_lds_bytes(int O) {
-    return (256 + 2 * 128 + 272 + kRows * kMXS + mat_obs_lds_floats(O, 1) + kMatFwdTiles * (size_t)kMTile) * 4;
-}
-
 // The Box bucket (mat_box.hpp): distribution.log_std [NA] first, then the Discrete list with the action encoder's
 // [64, NA + 1] weight read as weight [64, NA] + bias [64] -- the same floats, so every shared tensor sits pad4(NA) floats
 // behind its Discrete place.  want[]: the 63 shared tensors; returns the bucket's size
@@ -1797,13 +1114,51 @@ static long mat_box_offset_table(long O, long NA, long* want, long* enc_bias, lo
     return total;
 }
 
+// what the Box form of an entry point adds to the topology (act_lo / act_hi: the bounds of K16 and K20; K15 has none)
+struct MatBoxTopo { int64_t enc_bias_offset, log_std_offset; float min_std; const float* act_lo; const float* act_hi; };
+
+// The one description of a topology the MAT kernels take, for the args `a` of K15, K16 or K20.  who: the entry point's
+// name in its messages; max_obs: the widest observation it answers for; box: the Box form's fields (NULL: the Discrete
+// form); total: the bucket's size in floats.
+template <class A>
+static int mat_check_topology(const char* who, const A* a, int max_obs, bool compare_offsets, const MatBoxTopo* box,
+                              long* total = nullptr) {
+    PPOAF_REQUIRE(a->embedding == kMD, "%s: embedding=%d (built for 64)", who, a->embedding);
+    const struct { const char* name; int v, hi; } dims[3] = {
+        {"num_agents", a->num_agents, 16}, {"obs_dim", a->obs_dim, max_obs}, {"num_actions", a->num_actions, 8}};
+    for (const auto& d : dims)
+        PPOAF_REQUIRE(d.v >= 1 && d.v <= d.hi, "%s: %s=%d out of [1,%d] (sizes: agents %d, obs %d, actions %d)", who, d.name, d.v,
+                      d.hi, a->num_agents, a->obs_dim, a->num_actions);
+    PPOAF_REQUIRE(((uintptr_t)a->params & 15) == 0, "%s: params must be 16-byte aligned", who);
+    long want[MAT_NUM_PARAMS], want_eb = 0, want_ls = 0;
+    const long size = box ? mat_box_offset_table(a->obs_dim, a->num_actions, want, &want_eb, &want_ls)
+                          : mat_offset_table(a->obs_dim, a->num_actions, want);
+    if (total) *total = size;
+    for (int i = 0; compare_offsets && i < MAT_NUM_PARAMS; ++i)
+        PPOAF_REQUIRE(a->offsets[i] == want[i], "%s: parameter %d sits at %ld, expected %ld", who, i, (long)a->offsets[i], want[i]);
+    if (box) {
+        PPOAF_REQUIRE(box->enc_bias_offset == want_eb && box->log_std_offset == want_ls,
+                      "%s: action encoder bias / log_std sit at %ld / %ld, expected %ld / %ld", who, (long)box->enc_bias_offset,
+                      (long)box->log_std_offset, want_eb, want_ls);
+        PPOAF_REQUIRE(box->min_std >= 0.f, "%s: min_std=%g", who, (double)box->min_std);
+        PPOAF_REQUIRE((box->act_lo == nullptr) == (box->act_hi == nullptr), "%s: give both bounds or neither", who);
+    }
+    return PPOAF_OK;
+}
+
+// workgroups of the wgrad launch ahead of its bookkeeping one: the 18 linears' jobs and the small tensors' blocks
+static int mat_small_blocks(const MatDev& u) { return (4 * u.n_small4 + 255) / 256; }
+static int mat_wgrad_blocks(const MatDev& u) { return kMatWgJobs + mat_small_blocks(u); }
+// the panels of the split-wgrad chain: [MAT_NUM_XPANELS + kMatLin][R][64] floats
+static size_t mat_split_workspace_bytes(const MatDev& u) { return (size_t)(MAT_NUM_XPANELS + kMatLin) * u.R * kMD * 4; }
+
 // box: the Box form's args around `a` (NULL: the Discrete form)
 static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u, const ppoaf_mat_box_update_args_t* box = nullptr) {
     PPOAF_REQUIRE(a, "mat_update: null args");
-    PPOAF_REQUIRE(a->embedding == kMD, "mat_update: embedding=%d (the fused kernel is built for 64)", a->embedding);
-    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16, "mat_update: num_agents=%d out of [1,16]", a->num_agents);
-    PPOAF_REQUIRE(a->obs_dim >= 1 && a->obs_dim <= kMOWide, "mat_update: obs_dim=%d out of [1,%d]", a->obs_dim, kMOWide);
-    PPOAF_REQUIRE(a->num_actions >= 1 && a->num_actions <= 8, "mat_update: num_actions=%d out of [1,8]", a->num_actions);
+    const MatBoxTopo bt = box ? MatBoxTopo{box->enc_bias_offset, box->log_std_offset, box->min_std, nullptr, nullptr} : MatBoxTopo{};
+    long total = 0;
+    if (const int rc = mat_check_topology(box ? "mat_box_update" : "mat_update", a, kMOWide, true, box ? &bt : nullptr, &total))
+        return rc;
     PPOAF_REQUIRE(a->B >= 1 && a->batch_stride >= a->B, "mat_update: B=%ld stride=%ld", (long)a->B, (long)a->batch_stride);
     PPOAF_REQUIRE(a->params && a->grads && a->slabs && a->critic_obs && (box ? box->raw_actions && !a->raw_actions : a->raw_actions != nullptr) && a->advantages &&
                       a->old_log_probs && a->rewards_to_go && a->values && a->perm && a->cursor && a->vn_mean &&
@@ -1811,29 +1166,12 @@ static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u, const ppoaf_mat
                   "mat_update: null pointer");
     PPOAF_REQUIRE(!a->normalize_values || (a->vn_records && a->n_ranks >= 1), "mat_update: vn_records missing");
     PPOAF_REQUIRE(!a->normalize_adv || a->adv_records, "mat_update: adv_records missing");
-    PPOAF_REQUIRE(a->bucket_total % 4 == 0 && ((uintptr_t)a->params & 15) == 0 && ((uintptr_t)a->grads & 15) == 0 &&
-                      ((uintptr_t)a->slabs & 15) == 0, "mat_update: buckets must be 16-byte aligned");
-    const long Ain = box ? a->num_actions : a->num_actions + 1;
-    long want[MAT_NUM_PARAMS];
-    {
-        long want_eb = 0, want_ls = 0;
-        const long off = box ? mat_box_offset_table(a->obs_dim, a->num_actions, want, &want_eb, &want_ls)
-                             : mat_offset_table(a->obs_dim, a->num_actions, want);
-        PPOAF_REQUIRE(off == a->bucket_total, "mat_update: bucket_total=%ld, the topology needs %ld", (long)a->bucket_total, off);
-        if (box) {
-            PPOAF_REQUIRE(box->enc_bias_offset == want_eb && box->log_std_offset == want_ls,
-                          "mat_box_update: action encoder bias / log_std sit at %ld / %ld, expected %ld / %ld",
-                          (long)box->enc_bias_offset, (long)box->log_std_offset, want_eb, want_ls);
-            PPOAF_REQUIRE(box->min_std >= 0.f, "mat_box_update: min_std=%g", (double)box->min_std);
-        }
-    }
-    for (int i = 0; i < MAT_NUM_PARAMS; ++i) {
-        PPOAF_REQUIRE(a->offsets[i] == want[i], "mat_update: parameter %d sits at %ld, expected %ld", i,
-                      (long)a->offsets[i], want[i]);
-        u.off[i] = a->offsets[i];
-    }
+    PPOAF_REQUIRE(a->bucket_total % 4 == 0 && ((uintptr_t)a->grads & 15) == 0 && ((uintptr_t)a->slabs & 15) == 0,
+                  "mat_update: buckets must be 16-byte aligned");
+    PPOAF_REQUIRE(total == a->bucket_total, "mat_update: bucket_total=%ld, the topology needs %ld", (long)a->bucket_total, total);
+    for (int i = 0; i < MAT_NUM_PARAMS; ++i) u.off[i] = a->offsets[i];
     u.off[63] = 0;
-    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = (int)Ain;
+    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = box ? a->num_actions : a->num_actions + 1;
     u.per_tile = 16 / u.L;
     u.nT = (int)((a->B + u.per_tile - 1) / u.per_tile);
     u.total = a->bucket_total;
@@ -1859,8 +1197,7 @@ static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u, const ppoaf_mat
     for (int i = 0; i < 64; ++i) u.goff[i] = i < MAT_NUM_PARAMS ? (int)u.off[i] : 0;
     if (a->split_workspace) {
         PPOAF_REQUIRE((((uintptr_t)a->split_workspace) & 255) == 0, "mat_update: split_workspace must be 256-byte aligned");
-        const size_t plane = (size_t)u.R * kMD * 4;
-        const size_t need = (size_t)(MAT_NUM_XPANELS + kMatLin) * plane;
+        const size_t need = mat_split_workspace_bytes(u);
         PPOAF_REQUIRE((size_t)a->split_workspace_bytes >= need, "mat_update: split_workspace of %ld B, %zu needed",
                       (long)a->split_workspace_bytes, need);
         u.split = 1;
@@ -1888,65 +1225,72 @@ static int make_mat(const ppoaf_mat_update_args_t* a, MatDev& u, const ppoaf_mat
     return PPOAF_OK;
 }
 
-}  // namespace ppoaf
-
-using namespace ppoaf;
-
-extern "C" int ppoaf_mat_update_fwd_bwd(const ppoaf_mat_update_args_t* args, ppoaf_stream_t stream) {
-    return ppoaf_mat_update_fwd_bwd_timed(args, nullptr, nullptr, stream);
+// the Box form's view: its base is the view the shared launches (wgrad, wgrad_adam) take
+static int make_mat_box(const ppoaf_mat_box_update_args_t* a, MatBoxDev& u) {
+    PPOAF_REQUIRE(a, "mat_box_update: null args");
+    if (const int rc = make_mat(&a->mat, u, a)) return rc;
+    PPOAF_REQUIRE(u.split, "mat_box_update: the Box form runs on the split-wgrad chain only (split_workspace is not set)");
+    u.actions = nullptr;
+    u.actions_f = a->raw_actions;
+    u.off_enc_b = a->enc_bias_offset; u.off_log_std = a->log_std_offset;
+    u.goff_enc_b = (int)a->enc_bias_offset; u.goff_log_std = (int)a->log_std_offset;   // the first run of the compact slab is the bucket's head
+    u.min_std = a->min_std;
+    return PPOAF_OK;
 }
 
-extern "C" int ppoaf_mat_update_fwd_bwd_timed(const ppoaf_mat_update_args_t* args, void* start_event, void* stop_event,
-                                              ppoaf_stream_t stream) {
-    hipEvent_t e0 = (hipEvent_t)start_event, e1 = (hipEvent_t)stop_event;
-    MatDev u;
-    const int rc = make_mat(args, u);
-    if (rc) return rc;
-    const size_t lds = mat_lds_bytes(u.O);
-    PPOAF_REQUIRE(lds <= 160 * 1024, "mat_update: needs %zu B of LDS (> 160 KiB)", lds);
-    // [split][wide]
-    static void (*const kern[2][2])(MatDev) = {{mat_update_fwd_bwd_kernel<false>, mat_update_fwd_bwd_wide_kernel<false>},
-                                               {mat_update_fwd_bwd_kernel<true>, mat_update_fwd_bwd_wide_kernel<true>}};
-    static bool attr_set = false;
-    if (!attr_set) {
-        for (int i = 0; i < 4; ++i) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern[i >> 1][i & 1]),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        }
-        attr_set = true;
+// K15's first launch over a validated view of either form
+template <class U>
+static int mat_fwd_bwd_launch(const U& u, const char* who, hipEvent_t e0, hipEvent_t e1, ppoaf_stream_t stream) {
+    constexpr bool BOX = std::is_same<U, MatBoxDev>::value;
+    // (Box: the rows' own raw actions [16][8] sit behind the 34 activation tiles)
+    const size_t lds = mat_lds_bytes(u.O) + (BOX ? kRows * 8 * 4 : 0);
+    PPOAF_REQUIRE(lds <= 160 * 1024, "%s: needs %zu B of LDS (> 160 KiB)", who, lds);
+    const int wide = mat_is_wide(u.O) ? 1 : 0, k = 2 * (u.split ? 1 : 0) + wide;
+    void (*fn)(U);
+    if constexpr (BOX) {
+        fn = wide ? mat_box_update_fwd_bwd_wide_kernel : mat_box_update_fwd_bwd_kernel;
+    } else {
+        static void (*const kern[4])(MatDev) = {mat_update_fwd_bwd_kernel<false>, mat_update_fwd_bwd_wide_kernel<false>,
+                                                mat_update_fwd_bwd_kernel<true>, mat_update_fwd_bwd_wide_kernel<true>};
+        fn = kern[k];
     }
+    static bool attr_set[4] = {false, false, false, false};
+    if (const int rc = allow_large_lds(fn, lds, attr_set[k], who)) return rc;
     const dim3 grid((unsigned)u.nT), block(kMT);
-    hipStream_t st = (hipStream_t)stream;
-    const auto fn = kern[u.split ? 1 : 0][mat_is_wide(u.O) ? 1 : 0];
-    if (e0 || e1) hipExtLaunchKernelGGL(fn, grid, block, lds, st, e0, e1, 0, u);
-    else hipLaunchKernelGGL(fn, grid, block, lds, st, u);
-    return check_launch("mat_update_fwd_bwd");
+    if (e0 || e1) hipExtLaunchKernelGGL(fn, grid, block, lds, (hipStream_t)stream, e0, e1, 0, u);
+    else hipLaunchKernelGGL(fn, grid, block, lds, (hipStream_t)stream, u);
+    return check_launch(who);
 }
 
-extern "C" int ppoaf_mat_update_reduce(const ppoaf_mat_update_args_t* args, ppoaf_stream_t stream) {
-    MatDev u;
-    const int rc = make_mat(args, u);
-    if (rc) return rc;
+static int mat_reduce_launch(const MatDev& u, const char* who, ppoaf_stream_t stream) {
     if (u.split) {
-        const int nsb = (4 * u.n_small4 + 255) / 256;
+        const int nsb = mat_small_blocks(u);
         hipLaunchKernelGGL(mat_update_wgrad_kernel, dim3((unsigned)(kMatWgJobs + nsb + 1)), dim3(256), 0, (hipStream_t)stream, u, nsb);
-        return check_launch("mat_update_reduce (wgrad)");
+        return check_launch(who);
     }
     const long n4 = u.total >> 2;
     hipLaunchKernelGGL(mat_update_reduce_kernel, dim3((unsigned)((n4 + kMatRedThreads - 1) / kMatRedThreads) + 1u),
                        dim3(kMatRedThreads), 0, (hipStream_t)stream, u);
-    return check_launch("mat_update_reduce");
+    return check_launch(who);
 }
 
-extern "C" int ppoaf_mat_update_tail_ctl_bytes(const ppoaf_mat_update_args_t* args, int64_t* bytes_out) {
-    PPOAF_REQUIRE(args && bytes_out, "mat_update_tail_ctl_bytes: null argument");
-    MatDev u;
-    const int rc = make_mat(args, u);
-    if (rc) return rc;
+static int mat_tail_ctl_bytes(const MatDev& u, int64_t* bytes_out) {
     PPOAF_REQUIRE(u.split, "mat_update_tail_ctl_bytes: args->split_workspace is not set");
-    *bytes_out = (int64_t)kTailRecOff + 16 * (int64_t)(kMatWgJobs + (4 * u.n_small4 + 255) / 256);
+    *bytes_out = (int64_t)kTailRecOff + 16 * (int64_t)mat_wgrad_blocks(u);
     return PPOAF_OK;
+}
+
+// the bytes of panels a split-wgrad chain over these args needs (the args' own workspace does not count)
+static int mat_split_workspace_query(ppoaf_mat_update_args_t a, const ppoaf_mat_box_update_args_t* box, int64_t* bytes_out) {
+    a.split_workspace = nullptr; a.split_workspace_bytes = 0;
+    MatDev u;
+    if (const int rc = make_mat(&a, u, box)) return rc;
+    *bytes_out = (int64_t)mat_split_workspace_bytes(u);
+    return PPOAF_OK;
+}
+
+static int mat_norm_partials(const MatDev& u) {
+    return u.split ? mat_wgrad_blocks(u) : (int)(((u.total >> 2) + kMatRedThreads - 1) / kMatRedThreads);
 }
 
 // the fused tail over a validated view (the Discrete form's, or the Box form's base)
@@ -1958,11 +1302,10 @@ static int mat_wgrad_adam_launch(const MatDev& u, void* ctl, float* exp_avg, flo
     PPOAF_REQUIRE(ctl && (((uintptr_t)ctl) & 63) == 0, "mat_update_wgrad_adam: control block missing or not 64-byte aligned");
     PPOAF_REQUIRE(exp_avg && exp_avg_sq && lr, "mat_update_wgrad_adam: null optimiser state");
     PPOAF_REQUIRE(wait_seconds > 0.0 && wait_seconds <= 600.0, "mat_update_wgrad_adam: wait_seconds=%g", wait_seconds);
-    const int nsb = (4 * u.n_small4 + 255) / 256;
     TailDev td;
     td.ctl = reinterpret_cast<TailCtl*>(ctl);
     td.budget = (long long)(wait_seconds * 1.0e8);
-    td.nblk = kMatWgJobs + nsb;
+    td.nblk = mat_wgrad_blocks(u);
     td.jobs_a = 1 << 30; td.jobs_c = 0; td.per_xcd = 1;       // one optimiser: every record belongs to the one norm
     PPOAF_REQUIRE(td.nblk <= 64 * kTailMaxRounds, "mat_update_wgrad_adam: %d workgroups, a polling wave holds %d records", td.nblk,
                   64 * kTailMaxRounds);
@@ -1971,64 +1314,25 @@ static int mat_wgrad_adam_launch(const MatDev& u, void* ctl, float* exp_avg, flo
                                          "mat_update_wgrad_adam");
     if (fit) return fit;
     MatAdam ad{exp_avg, exp_avg_sq, lr, beta1, beta2, eps, grad_scale, max_norm, grad_norm_out};
-    hipLaunchKernelGGL(mat_update_wgrad_adam_kernel, dim3((unsigned)(td.nblk + 1)), dim3(256), 0, (hipStream_t)stream, u, nsb, ad, td);
+    hipLaunchKernelGGL(mat_update_wgrad_adam_kernel, dim3((unsigned)(td.nblk + 1)), dim3(256), 0, (hipStream_t)stream, u,
+                       mat_small_blocks(u), ad, td);
     return check_launch("mat_update_wgrad_adam");
 }
 
-extern "C" int ppoaf_mat_update_wgrad_adam(const ppoaf_mat_update_args_t* args, void* ctl, float* exp_avg, float* exp_avg_sq,
-                                           const float* lr, float beta1, float beta2, float eps, float grad_scale, float max_norm,
-                                           float* grad_norm_out, double wait_seconds, ppoaf_stream_t stream) {
-    MatDev u;
-    const int rc = make_mat(args, u);
-    if (rc) return rc;
-    return mat_wgrad_adam_launch(u, ctl, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, grad_scale, max_norm, grad_norm_out,
-                                 wait_seconds, stream);
-}
-
-extern "C" int ppoaf_mat_update_split_workspace_bytes(const ppoaf_mat_update_args_t* args, int64_t* bytes_out) {
-    PPOAF_REQUIRE(args && bytes_out, "mat_update_split_workspace_bytes: null argument");
-    ppoaf_mat_update_args_t a = *args;
-    a.split_workspace = nullptr; a.split_workspace_bytes = 0;
-    MatDev u;
-    const int rc = make_mat(&a, u);
-    if (rc) return rc;
-    *bytes_out = (int64_t)((size_t)(MAT_NUM_XPANELS + kMatLin) * u.R * kMD * 4);
-    return PPOAF_OK;
-}
-
-extern "C" int ppoaf_mat_update_norm_partials(const ppoaf_mat_update_args_t* args) {
-    MatDev u;
-    if (make_mat(args, u)) return -1;
-    if (u.split) return kMatWgJobs + (4 * u.n_small4 + 255) / 256;
-    return (int)(((u.total >> 2) + kMatRedThreads - 1) / kMatRedThreads);
-}
-
 // validates `a` and fills the device view (tb: the block form; box: the Box form's args around `a`, NULL for Discrete)
-static int mat_step_dev(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb, const ppoaf_mat_box_step_args_t* box, MatStepDev& u) {
-    PPOAF_REQUIRE(a->embedding == kMD, "mat_policy_step: embedding=%d (built for 64)", a->embedding);
-    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= kMOWide &&
-                      a->num_actions >= 1 && a->num_actions <= 8 && a->actor_obs_dim >= 1,
-                  "mat_policy_step: sizes (agents %d, obs %d, actions %d) outside the kernel's limits (16, %d, 8)", a->num_agents,
-                  a->obs_dim, a->num_actions, kMOWide);
-    PPOAF_REQUIRE(a->E >= 1, "mat_policy_step: E=%ld", (long)a->E);
+static int mat_step_dev(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb, const ppoaf_mat_box_step_args_t* box, const char* who,
+                        MatStepDev& u) {
+    const MatBoxTopo bt = box ? MatBoxTopo{box->enc_bias_offset, box->log_std_offset, box->min_std, box->act_lo, box->act_hi} : MatBoxTopo{};
+    // (the Discrete step has never compared the offsets with the table, and does not start to here)
+    if (const int rc = mat_check_topology(who, a, kMOWide, box != nullptr, box ? &bt : nullptr)) return rc;
+    PPOAF_REQUIRE(a->actor_obs_dim >= 1, "%s: actor_obs_dim=%d (sizes: agents %d, obs %d, actions %d)", who, a->actor_obs_dim,
+                  a->num_agents, a->obs_dim, a->num_actions);
+    PPOAF_REQUIRE(a->E >= 1, "%s: E=%ld", who, (long)a->E);
     PPOAF_REQUIRE(a->params && (tb || a->critic_obs) && (box ? box->action_out && box->raw_action_out : a->action_out != nullptr) &&
-                      a->logp_out && a->value_out, "mat_policy_step: null pointer");
-    if (box) {
-        PPOAF_REQUIRE(!a->action_out && !a->raw_action_out && !a->forced_action,
-                      "mat_box_policy_step: the int64 action pointers must be NULL (the float tables take their place)");
-        PPOAF_REQUIRE((box->act_lo == nullptr) == (box->act_hi == nullptr), "mat_box_policy_step: give both bounds or neither");
-        PPOAF_REQUIRE(box->min_std >= 0.f, "mat_box_policy_step: min_std=%g", (double)box->min_std);
-        long want[MAT_NUM_PARAMS], want_eb = 0, want_ls = 0;
-        mat_box_offset_table(a->obs_dim, a->num_actions, want, &want_eb, &want_ls);
-        for (int i = 0; i < MAT_NUM_PARAMS; ++i)
-            PPOAF_REQUIRE(a->offsets[i] == want[i], "mat_box_policy_step: parameter %d sits at %ld, expected %ld", i,
-                          (long)a->offsets[i], want[i]);
-        PPOAF_REQUIRE(box->enc_bias_offset == want_eb && box->log_std_offset == want_ls,
-                      "mat_box_policy_step: action encoder bias / log_std sit at %ld / %ld, expected %ld / %ld",
-                      (long)box->enc_bias_offset, (long)box->log_std_offset, want_eb, want_ls);
-    }
-    PPOAF_REQUIRE(!a->normalize_values || (a->vn_mean && a->vn_var), "mat_policy_step: value normaliser statistics missing");
-    PPOAF_REQUIRE(((uintptr_t)a->params & 15) == 0, "mat_policy_step: params must be 16-byte aligned");
+                      a->logp_out && a->value_out, "%s: null pointer", who);
+    PPOAF_REQUIRE(!box || (!a->action_out && !a->raw_action_out && !a->forced_action),
+                  "%s: the int64 action pointers must be NULL (the float tables take their place)", who);
+    PPOAF_REQUIRE(!a->normalize_values || (a->vn_mean && a->vn_var), "%s: value normaliser statistics missing", who);
     for (int i = 0; i < 64; ++i) u.off[i] = a->offsets[i];
     u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = box ? a->num_actions : a->num_actions + 1;
     u.per_tile = 16 / u.L; u.Oa = a->actor_obs_dim;
@@ -2039,49 +1343,50 @@ static int mat_step_dev(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb,
     u.value_out = a->value_out; u.critic_obs_out = a->critic_obs_copy_out; u.obs_out = a->obs_copy_out;
     u.forced_action = a->forced_action;
     if (tb) { u.obs = nullptr; u.actor_obs = nullptr; }
-    PPOAF_REQUIRE(mat_lds_bytes(u.O) <= 160 * 1024, "mat_policy_step: needs %zu B of LDS (> 160 KiB)", mat_lds_bytes(u.O));
-    PPOAF_REQUIRE((a->E + u.per_tile - 1) / u.per_tile <= 0x7fffffffL, "mat_policy_step: too many envs");
+    PPOAF_REQUIRE(mat_lds_bytes(u.O) <= 160 * 1024, "%s: needs %zu B of LDS (> 160 KiB)", who, mat_lds_bytes(u.O));
+    PPOAF_REQUIRE((a->E + u.per_tile - 1) / u.per_tile <= 0x7fffffffL, "%s: too many envs", who);
     return PPOAF_OK;
 }
 
-// launches the plain form (tb == NULL) or the block form
-static int mat_policy_step_launch(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb, ppoaf_stream_t stream) {
-    MatStepDev u;
-    const int rc = mat_step_dev(a, tb, nullptr, u);
-    if (rc) return rc;
+// K16 over a validated view of either form: the plain launch (tb == NULL) or the block form
+template <class U>
+static int mat_step_launch(const U& u, const MatStepBlocks* tb, const char* who, ppoaf_stream_t stream) {
+    constexpr bool BOX = std::is_same<U, MatBoxStepDev>::value;
     const size_t lds = mat_lds_bytes(u.O);
-    static void (*const kern[2])(MatStepDev) = {mat_policy_step_kernel, mat_policy_step_wide_kernel};
-    static bool attr_set = false;
-    if (!attr_set) {
-        for (int i = 0; i < 2; ++i) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern[i]),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        }
-        attr_set = true;
-    }
-    const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
+    const bool wide = mat_is_wide(u.O);
+    const dim3 grid((unsigned)((u.E + u.per_tile - 1) / u.per_tile)), block(kMT);
+    static bool attr_set[4] = {false, false, false, false};
+    bool& done = attr_set[(tb ? 2 : 0) + (wide ? 1 : 0)];
     if (tb) {
-        static void (*const kern_b[2])(MatStepDev, MatStepBlocks) = {mat_policy_step_blocks_kernel, mat_policy_step_blocks_wide_kernel};
-        static bool attr_b = false;
-        if (!attr_b) {
-            for (int i = 0; i < 2; ++i) {
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern_b[i]),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-            }
-            attr_b = true;
-        }
-        hipLaunchKernelGGL(kern_b[mat_is_wide(u.O) ? 1 : 0], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u, *tb);
-        return check_launch("mat_policy_step_blocks");
+        void (*fn)(U, MatStepBlocks);
+        if constexpr (BOX) fn = wide ? mat_box_policy_step_blocks_wide_kernel : mat_box_policy_step_blocks_kernel;
+        else fn = wide ? mat_policy_step_blocks_wide_kernel : mat_policy_step_blocks_kernel;
+        if (const int rc = allow_large_lds(fn, lds, done, who)) return rc;
+        hipLaunchKernelGGL(fn, grid, block, lds, (hipStream_t)stream, u, *tb);
+    } else {
+        void (*fn)(U);
+        if constexpr (BOX) fn = wide ? mat_box_policy_step_wide_kernel : mat_box_policy_step_kernel;
+        else fn = wide ? mat_policy_step_wide_kernel : mat_policy_step_kernel;
+        if (const int rc = allow_large_lds(fn, lds, done, who)) return rc;
+        hipLaunchKernelGGL(fn, grid, block, lds, (hipStream_t)stream, u);
     }
-    hipLaunchKernelGGL(kern[mat_is_wide(u.O) ? 1 : 0], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
-    return check_launch("mat_policy_step");
+    return check_launch(who);
 }
 
-extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a, "mat_policy_step: null args");
-    return mat_policy_step_launch(a, nullptr, stream);
+static int mat_policy_step(const ppoaf_mat_step_args_t* a, const MatStepBlocks* tb, const char* who, ppoaf_stream_t stream) {
+    MatStepDev u;
+    if (const int rc = mat_step_dev(a, tb, nullptr, who, u)) return rc;
+    return mat_step_launch(u, tb, who, stream);
+}
+
+static int mat_box_policy_step(const ppoaf_mat_box_step_args_t* a, const MatStepBlocks* tb, const char* who, ppoaf_stream_t stream) {
+    MatBoxStepDev u;
+    if (const int rc = mat_step_dev(&a->mat, tb, a, who, u)) return rc;
+    u.action_out = nullptr; u.raw_action_out = nullptr; u.forced_action = nullptr;
+    u.off_enc_b = a->enc_bias_offset; u.off_log_std = a->log_std_offset; u.min_std = a->min_std;
+    u.act_lo = a->act_lo; u.act_hi = a->act_hi;
+    u.action_f = a->action_out; u.raw_action_f = a->raw_action_out; u.forced_f = a->forced_action;
+    return mat_step_launch(u, tb, who, stream);
 }
 
 // the block table of either form (they differ in the element type of env_action) -> the kernels' table
@@ -2115,14 +1420,199 @@ static int mat_step_blocks_dev(const ppoaf_mat_step_args_t* a, const Table* t, M
     return PPOAF_OK;
 }
 
+// The one launcher of K20's entry points.  who: the entry point's name in its messages; max_obs: the widest observation it
+// answers for (ppoaf_mat_policy_infer keeps 64, and its refusal of 65); box: the Box form's args around `a`, NULL for the
+// Discrete form.
+static int mat_policy_infer_launch(const ppoaf_mat_infer_args_t* a, const ppoaf_mat_box_infer_args_t* box, const char* who,
+                                   int max_obs, ppoaf_stream_t stream) {
+    const MatBoxTopo bt = box ? MatBoxTopo{box->enc_bias_offset, box->log_std_offset, box->min_std, box->act_lo, box->act_hi} : MatBoxTopo{};
+    if (const int rc = mat_check_topology(who, a, max_obs, true, box ? &bt : nullptr)) return rc;
+    PPOAF_REQUIRE(a->mode == PPOAF_INFER_SAMPLE || a->mode == PPOAF_INFER_DETERMINISTIC,
+                  "%s: mode=%d (0 sample, 1 deterministic)", who, a->mode);
+    PPOAF_REQUIRE(a->E >= 0, "%s: negative E", who);
+    PPOAF_REQUIRE(a->E <= (1L << 27), "%s: E too large", who);
+    PPOAF_REQUIRE(a->params && a->obs && (box ? (void*)box->action_out : (void*)a->action_out), "%s: null pointer", who);
+    PPOAF_REQUIRE(a->obs_env_stride >= 1 && a->obs_agent_stride >= 1 && a->act_env_stride >= 1 && a->act_agent_stride >= 1,
+                  "%s: strides must be >= 1 (obs %ld / %ld, action %ld / %ld)", who, (long)a->obs_env_stride,
+                  (long)a->obs_agent_stride, (long)a->act_env_stride, (long)a->act_agent_stride);
+    unsigned seen = 0;
+    for (int i = 0; i < a->num_agents; ++i) {
+        const int v = a->slot_agent[i];
+        PPOAF_REQUIRE(v >= 0 && v < a->num_agents && !((seen >> v) & 1u),
+                      "%s: slot_agent is not a permutation of 0..%d (slot %d holds %d)", who, a->num_agents - 1, i, v);
+        seen |= 1u << v;
+    }
+    if (a->E == 0) return PPOAF_OK;
+    MatInferDev u;
+    for (int i = 0; i < 64; ++i) u.off[i] = i < MAT_NUM_PARAMS ? a->offsets[i] : 0;
+    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = box ? a->num_actions : a->num_actions + 1;
+    u.per_tile = 16 / u.L; u.mode = a->mode;
+    u.params = a->params; u.obs = a->obs; u.E = a->E;
+    u.obs_env_stride = a->obs_env_stride; u.obs_agent_stride = a->obs_agent_stride;
+    u.act_env_stride = a->act_env_stride; u.act_agent_stride = a->act_agent_stride;
+    u.seed = a->seed; u.offset = a->offset; u.action_out = a->action_out;
+    for (int i = 0; i < 16; ++i) u.slot_agent[i] = (unsigned char)(i < u.L ? a->slot_agent[i] : 0);
+    const size_t lds = (box || kInferCompact) ? mat_fwd_lds_bytes(u.O) : mat_lds_bytes(u.O);
+    PPOAF_REQUIRE(lds <= 160 * 1024, "%s: needs %zu B of LDS (> 160 KiB)", who, lds);
+    // obs_dim >= 33 takes K16's chunked front end, so the sampled actions stay operation for operation K16's
+    static void (*const kern[2])(MatInferDev) = {mat_policy_infer_kernel<kInferCompact, kInferValue>,
+                                                 mat_policy_infer_wide_kernel<kInferCompact, kInferValue>};
+    static void (*const kern_box[2])(MatInferDev, MatBoxInferDev) = {mat_box_policy_infer_kernel, mat_box_policy_infer_wide_kernel};
+    const int wide = mat_is_wide(u.O) ? 1 : 0;
+    static bool attr_set[4] = {false, false, false, false};
+    bool& done = attr_set[(box ? 2 : 0) + wide];
+    if (const int rc = box ? allow_large_lds(kern_box[wide], lds, done, who) : allow_large_lds(kern[wide], lds, done, who)) return rc;
+    const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
+    if (box) {
+        u.action_out = nullptr;
+        const MatBoxInferDev x{box->enc_bias_offset, box->log_std_offset, box->min_std, box->act_lo, box->act_hi, box->action_out};
+        hipLaunchKernelGGL(kern_box[wide], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u, x);
+    } else {
+        hipLaunchKernelGGL(kern[wide], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
+    }
+    return check_launch(who);
+}
+
+}  // namespace ppoaf
+
+using namespace ppoaf;
+
+extern "C" int ppoaf_mat_update_fwd_bwd_timed(const ppoaf_mat_update_args_t* args, void* start_event, void* stop_event,
+                                              ppoaf_stream_t stream) {
+    MatDev u;
+    if (const int rc = make_mat(args, u)) return rc;
+    return mat_fwd_bwd_launch(u, "mat_update_fwd_bwd", (hipEvent_t)start_event, (hipEvent_t)stop_event, stream);
+}
+extern "C" int ppoaf_mat_update_fwd_bwd(const ppoaf_mat_update_args_t* args, ppoaf_stream_t stream) {
+    return ppoaf_mat_update_fwd_bwd_timed(args, nullptr, nullptr, stream);
+}
+extern "C" int ppoaf_mat_box_update_fwd_bwd(const ppoaf_mat_box_update_args_t* args, ppoaf_stream_t stream) {
+    MatBoxDev u;
+    if (const int rc = make_mat_box(args, u)) return rc;
+    return mat_fwd_bwd_launch(u, "mat_box_update_fwd_bwd", nullptr, nullptr, stream);
+}
+
+extern "C" int ppoaf_mat_update_reduce(const ppoaf_mat_update_args_t* args, ppoaf_stream_t stream) {
+    MatDev u;
+    if (const int rc = make_mat(args, u)) return rc;
+    return mat_reduce_launch(u, u.split ? "mat_update_reduce (wgrad)" : "mat_update_reduce", stream);
+}
+extern "C" int ppoaf_mat_box_update_reduce(const ppoaf_mat_box_update_args_t* args, ppoaf_stream_t stream) {
+    MatBoxDev u;
+    if (const int rc = make_mat_box(args, u)) return rc;
+    return mat_reduce_launch(u, "mat_box_update_reduce (wgrad)", stream);
+}
+
+extern "C" int ppoaf_mat_update_tail_ctl_bytes(const ppoaf_mat_update_args_t* args, int64_t* bytes_out) {
+    PPOAF_REQUIRE(args && bytes_out, "mat_update_tail_ctl_bytes: null argument");
+    MatDev u;
+    if (const int rc = make_mat(args, u)) return rc;
+    return mat_tail_ctl_bytes(u, bytes_out);
+}
+extern "C" int ppoaf_mat_box_update_tail_ctl_bytes(const ppoaf_mat_box_update_args_t* args, int64_t* bytes_out) {
+    PPOAF_REQUIRE(args && bytes_out, "mat_box_update_tail_ctl_bytes: null argument");
+    MatBoxDev u;
+    if (const int rc = make_mat_box(args, u)) return rc;
+    return mat_tail_ctl_bytes(u, bytes_out);
+}
+
+extern "C" int ppoaf_mat_update_split_workspace_bytes(const ppoaf_mat_update_args_t* args, int64_t* bytes_out) {
+    PPOAF_REQUIRE(args && bytes_out, "mat_update_split_workspace_bytes: null argument");
+    return mat_split_workspace_query(*args, nullptr, bytes_out);
+}
+extern "C" int ppoaf_mat_box_update_split_workspace_bytes(const ppoaf_mat_box_update_args_t* args, int64_t* bytes_out) {
+    PPOAF_REQUIRE(args && bytes_out, "mat_box_update_split_workspace_bytes: null argument");
+    return mat_split_workspace_query(args->mat, args, bytes_out);
+}
+
+extern "C" int ppoaf_mat_update_norm_partials(const ppoaf_mat_update_args_t* args) {
+    MatDev u;
+    return make_mat(args, u) ? -1 : mat_norm_partials(u);
+}
+extern "C" int ppoaf_mat_box_update_norm_partials(const ppoaf_mat_box_update_args_t* args) {
+    MatBoxDev u;
+    return make_mat_box(args, u) ? -1 : mat_norm_partials(u);
+}
+
+extern "C" int ppoaf_mat_update_wgrad_adam(const ppoaf_mat_update_args_t* args, void* ctl, float* exp_avg, float* exp_avg_sq,
+                                           const float* lr, float beta1, float beta2, float eps, float grad_scale, float max_norm,
+                                           float* grad_norm_out, double wait_seconds, ppoaf_stream_t stream) {
+    MatDev u;
+    if (const int rc = make_mat(args, u)) return rc;
+    return mat_wgrad_adam_launch(u, ctl, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, grad_scale, max_norm, grad_norm_out,
+                                 wait_seconds, stream);
+}
+extern "C" int ppoaf_mat_box_update_wgrad_adam(const ppoaf_mat_box_update_args_t* args, void* ctl, float* exp_avg, float* exp_avg_sq,
+                                               const float* lr, float beta1, float beta2, float eps, float grad_scale,
+                                               float max_norm, float* grad_norm_out, double wait_seconds, ppoaf_stream_t stream) {
+    MatBoxDev u;
+    if (const int rc = make_mat_box(args, u)) return rc;
+    return mat_wgrad_adam_launch(u, ctl, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, grad_scale, max_norm, grad_norm_out,
+                                 wait_seconds, stream);
+}
+
+extern "C" int ppoaf_mat_policy_step(const ppoaf_mat_step_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_policy_step: null args");
+    return mat_policy_step(a, nullptr, "mat_policy_step", stream);
+}
+extern "C" int ppoaf_mat_box_policy_step(const ppoaf_mat_box_step_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_box_policy_step: null args");
+    return mat_box_policy_step(a, nullptr, "mat_box_policy_step", stream);
+}
+
 extern "C" int ppoaf_mat_policy_step_blocks(const ppoaf_mat_step_args_t* a, const ppoaf_mat_step_blocks_t* t,
                                             ppoaf_stream_t stream) {
     PPOAF_REQUIRE(a && t, "mat_policy_step_blocks: null args");
     MatStepBlocks tb;
-    const int rc = mat_step_blocks_dev(a, t, tb);
-    if (rc) return rc;
+    if (const int rc = mat_step_blocks_dev(a, t, tb)) return rc;
     if (a->E == 0) return PPOAF_OK;
-    return mat_policy_step_launch(a, &tb, stream);
+    return mat_policy_step(a, &tb, "mat_policy_step_blocks", stream);
+}
+extern "C" int ppoaf_mat_box_policy_step_blocks(const ppoaf_mat_box_step_args_t* a, const ppoaf_mat_box_step_blocks_t* t,
+                                                ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a && t, "mat_box_policy_step_blocks: null args");
+    MatStepBlocks tb;
+    if (const int rc = mat_step_blocks_dev(&a->mat, t, tb)) return rc;
+    if (a->mat.E == 0) return PPOAF_OK;
+    return mat_box_policy_step(a, &tb, "mat_box_policy_step_blocks", stream);
+}
+
+extern "C" int ppoaf_mat_policy_infer(const ppoaf_mat_infer_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_policy_infer: null args");
+    return mat_policy_infer_launch(a, nullptr, "mat_policy_infer", 64, stream);
+}
+// the same launch for observations up to kMOWide (the chunked front end walks as many chunks as the row has)
+extern "C" int ppoaf_mat_policy_infer_wide(const ppoaf_mat_infer_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_policy_infer_wide: null args");
+    return mat_policy_infer_launch(a, nullptr, "mat_policy_infer_wide", kMOWide, stream);
+}
+extern "C" int ppoaf_mat_box_policy_infer(const ppoaf_mat_box_infer_args_t* a, ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(a, "mat_box_policy_infer: null args");
+    return mat_policy_infer_launch(&a->mat, a, "mat_box_policy_infer", kMOWide, stream);
+}
+
+// mpi_avg_gradients at the MAT update's per-mini-batch call site (mat_policy.py:692) when the K17 peer exchange is not
+// available: fwd_bwd -> reduce -> RCCL sum all-reduce of the shared bucket -> K11 clip + Adam (mat_policy.py:694-699),
+// for n consecutive mini-batches issued from this one call.
+extern "C" int ppoaf_mat_update_chain_allreduce(const ppoaf_mat_update_args_t* args, ppoaf_comm_t* comm, int64_t n_minibatches,
+                                                float* exp_avg, float* exp_avg_sq, const float* lr, float beta1, float beta2,
+                                                float eps, float grad_scale, float max_norm, float* grad_norm_out,
+                                                ppoaf_stream_t stream) {
+    PPOAF_REQUIRE(args && comm && exp_avg && exp_avg_sq && lr, "mat_update_chain_allreduce: null argument");
+    PPOAF_REQUIRE(n_minibatches >= 1 && n_minibatches <= (1 << 20), "mat_update_chain_allreduce: n_minibatches=%ld", (long)n_minibatches);
+    PPOAF_REQUIRE(args->fuse_norm == 0 && args->norm_scratch && args->step_count,
+                  "mat_update_chain_allreduce: fuse_norm must be 0 (the norm is that of the all-reduced gradient)");
+    for (int64_t j = 0; j < n_minibatches; ++j) {
+        int rc = ppoaf_mat_update_fwd_bwd(args, stream);
+        if (rc == PPOAF_OK) rc = ppoaf_mat_update_reduce(args, stream);
+        if (rc == PPOAF_OK) rc = ppoaf_allreduce_sum_f32(comm, args->grads, args->bucket_total, stream);
+        if (rc == PPOAF_OK)
+            rc = ppoaf_clip_adam_step(const_cast<float*>(args->params), args->grads, exp_avg, exp_avg_sq, args->bucket_total,
+                                      args->step_count, lr, beta1, beta2, eps, grad_scale, max_norm, args->norm_scratch,
+                                      grad_norm_out, stream);
+        if (rc != PPOAF_OK) return rc;
+    }
+    return PPOAF_OK;
 }
 
 #define PPOAF_LAYOUT(T, f, off) static_assert(offsetof(T, f) == off, #T "." #f)
@@ -2149,96 +1639,6 @@ PPOAF_LAYOUT(ppoaf_mat_infer_args_t, action_out, 656);
 PPOAF_LAYOUT(ppoaf_mat_infer_args_t, act_env_stride, 664);
 PPOAF_LAYOUT(ppoaf_mat_infer_args_t, act_agent_stride, 672);
 static_assert(sizeof(ppoaf_mat_infer_args_t) == 680, "ppoaf_mat_infer_args_t");
-
-// The one launcher of K20's entry points.  who: the entry point's name in its messages; max_obs: the widest observation it
-// answers for (ppoaf_mat_policy_infer keeps 64, and its refusal of 65); box: the Box form's args around `a`, NULL for the
-// Discrete form.
-static int mat_policy_infer_launch(const ppoaf_mat_infer_args_t* a, const ppoaf_mat_box_infer_args_t* box, const char* who,
-                                   int max_obs, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a->embedding == kMD, "%s: embedding=%d (built for 64)", who, a->embedding);
-    PPOAF_REQUIRE(a->num_agents >= 1 && a->num_agents <= 16 && a->obs_dim >= 1 && a->obs_dim <= max_obs &&
-                      a->num_actions >= 1 && a->num_actions <= 8,
-                  "%s: sizes (agents %d, obs %d, actions %d) outside K16's limits (16, %d, 8)", who, a->num_agents, a->obs_dim,
-                  a->num_actions, max_obs);
-    PPOAF_REQUIRE(a->mode == PPOAF_INFER_SAMPLE || a->mode == PPOAF_INFER_DETERMINISTIC,
-                  "%s: mode=%d (0 sample, 1 deterministic)", who, a->mode);
-    PPOAF_REQUIRE(a->E >= 0, "%s: negative E", who);
-    PPOAF_REQUIRE(a->E <= (1L << 27), "%s: E too large", who);
-    PPOAF_REQUIRE(a->params && a->obs && (box ? (void*)box->action_out : (void*)a->action_out), "%s: null pointer", who);
-    PPOAF_REQUIRE(((uintptr_t)a->params & 15) == 0, "%s: params must be 16-byte aligned", who);
-    PPOAF_REQUIRE(a->obs_env_stride >= 1 && a->obs_agent_stride >= 1 && a->act_env_stride >= 1 && a->act_agent_stride >= 1,
-                  "%s: strides must be >= 1 (obs %ld / %ld, action %ld / %ld)", who, (long)a->obs_env_stride,
-                  (long)a->obs_agent_stride, (long)a->act_env_stride, (long)a->act_agent_stride);
-    unsigned seen = 0;
-    for (int i = 0; i < a->num_agents; ++i) {
-        const int v = a->slot_agent[i];
-        PPOAF_REQUIRE(v >= 0 && v < a->num_agents && !((seen >> v) & 1u),
-                      "%s: slot_agent is not a permutation of 0..%d (slot %d holds %d)", who, a->num_agents - 1, i, v);
-        seen |= 1u << v;
-    }
-    long want[MAT_NUM_PARAMS], want_eb = 0, want_ls = 0;
-    if (box) mat_box_offset_table(a->obs_dim, a->num_actions, want, &want_eb, &want_ls);
-    else mat_offset_table(a->obs_dim, a->num_actions, want);
-    for (int i = 0; i < MAT_NUM_PARAMS; ++i)
-        PPOAF_REQUIRE(a->offsets[i] == want[i], "%s: parameter %d sits at %ld, expected %ld", who, i, (long)a->offsets[i], want[i]);
-    if (box) {
-        PPOAF_REQUIRE((box->act_lo == nullptr) == (box->act_hi == nullptr), "%s: give both bounds or neither", who);
-        PPOAF_REQUIRE(box->min_std >= 0.f, "%s: min_std=%g", who, (double)box->min_std);
-        PPOAF_REQUIRE(box->enc_bias_offset == want_eb && box->log_std_offset == want_ls,
-                      "%s: action encoder bias / log_std sit at %ld / %ld, expected %ld / %ld", who, (long)box->enc_bias_offset,
-                      (long)box->log_std_offset, want_eb, want_ls);
-    }
-    if (a->E == 0) return PPOAF_OK;
-    MatInferDev u;
-    for (int i = 0; i < 64; ++i) u.off[i] = i < MAT_NUM_PARAMS ? a->offsets[i] : 0;
-    u.O = a->obs_dim; u.L = a->num_agents; u.NA = a->num_actions; u.Ain = box ? a->num_actions : a->num_actions + 1;
-    u.per_tile = 16 / u.L; u.mode = a->mode;
-    u.params = a->params; u.obs = a->obs; u.E = a->E;
-    u.obs_env_stride = a->obs_env_stride; u.obs_agent_stride = a->obs_agent_stride;
-    u.act_env_stride = a->act_env_stride; u.act_agent_stride = a->act_agent_stride;
-    u.seed = a->seed; u.offset = a->offset; u.action_out = a->action_out;
-    for (int i = 0; i < 16; ++i) u.slot_agent[i] = (unsigned char)(i < u.L ? a->slot_agent[i] : 0);
-    const size_t lds = (box || kInferCompact) ? mat_fwd_lds_bytes(u.O) : mat_lds_bytes(u.O);
-    PPOAF_REQUIRE(lds <= 160 * 1024, "%s: needs %zu B of LDS (> 160 KiB)", who, lds);
-    // obs_dim >= 33 takes K16's chunked front end, so the sampled actions stay operation for operation K16's
-    static void (*const kern[2])(MatInferDev) = {mat_policy_infer_kernel<kInferCompact, kInferValue>,
-                                                 mat_policy_infer_wide_kernel<kInferCompact, kInferValue>};
-    static void (*const kern_box[2])(MatInferDev, MatBoxInferDev) = {mat_box_policy_infer_kernel, mat_box_policy_infer_wide_kernel};
-    const int wide = mat_is_wide(u.O) ? 1 : 0, k = (box ? 2 : 0) + wide;
-    static bool attr_set[4] = {false, false, false, false};
-    if (!attr_set[k] && lds > 64 * 1024) {
-        const void* fn = box ? reinterpret_cast<const void*>(kern_box[wide]) : reinterpret_cast<const void*>(kern[wide]);
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set[k] = true;
-    }
-    const long n_wg = (a->E + u.per_tile - 1) / u.per_tile;
-    if (box) {
-        u.action_out = nullptr;
-        const MatBoxInferDev x{box->enc_bias_offset, box->log_std_offset, box->min_std, box->act_lo, box->act_hi, box->action_out};
-        hipLaunchKernelGGL(kern_box[wide], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u, x);
-    } else {
-        hipLaunchKernelGGL(kern[wide], dim3((unsigned)n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
-    }
-    return check_launch(who);
-}
-
-extern "C" int ppoaf_mat_policy_infer(const ppoaf_mat_infer_args_t* a, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a, "mat_policy_infer: null args");
-    return mat_policy_infer_launch(a, nullptr, "mat_policy_infer", 64, stream);
-}
-
-// the same launch for observations up to kMOWide (the chunked front end walks as many chunks as the row has)
-extern "C" int ppoaf_mat_policy_infer_wide(const ppoaf_mat_infer_args_t* a, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a, "mat_policy_infer_wide: null args");
-    return mat_policy_infer_launch(a, nullptr, "mat_policy_infer_wide", kMOWide, stream);
-}
-
-extern "C" int ppoaf_mat_box_policy_infer(const ppoaf_mat_box_infer_args_t* a, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a, "mat_box_policy_infer: null args");
-    return mat_policy_infer_launch(&a->mat, a, "mat_box_policy_infer", kMOWide, stream);
-}
-
 PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, mat, 0);
 PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, enc_bias_offset, sizeof(ppoaf_mat_infer_args_t));
 PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, log_std_offset, sizeof(ppoaf_mat_infer_args_t) + 8);
@@ -2247,161 +1647,6 @@ PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, act_lo, sizeof(ppoaf_mat_infer_args_t) 
 PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, act_hi, sizeof(ppoaf_mat_infer_args_t) + 32);
 PPOAF_LAYOUT(ppoaf_mat_box_infer_args_t, action_out, sizeof(ppoaf_mat_infer_args_t) + 40);
 static_assert(sizeof(ppoaf_mat_box_infer_args_t) == sizeof(ppoaf_mat_infer_args_t) + 48, "ppoaf_mat_box_infer_args_t");
-
-// mpi_avg_gradients at the MAT update's per-mini-batch call site (mat_policy.py:692) when the K17 peer exchange is not
-// available: fwd_bwd -> reduce -> RCCL sum all-reduce of the shared bucket -> K11 clip + Adam (mat_policy.py:694-699),
-// for n consecutive mini-batches issued from this one call.
-extern "C" int ppoaf_mat_update_chain_allreduce(const ppoaf_mat_update_args_t* args, ppoaf_comm_t* comm, int64_t n_minibatches,
-                                                float* exp_avg, float* exp_avg_sq, const float* lr, float beta1, float beta2,
-                                                float eps, float grad_scale, float max_norm, float* grad_norm_out,
-                                                ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(args && comm && exp_avg && exp_avg_sq && lr, "mat_update_chain_allreduce: null argument");
-    PPOAF_REQUIRE(n_minibatches >= 1 && n_minibatches <= (1 << 20), "mat_update_chain_allreduce: n_minibatches=%ld", (long)n_minibatches);
-    PPOAF_REQUIRE(args->fuse_norm == 0 && args->norm_scratch && args->step_count,
-                  "mat_update_chain_allreduce: fuse_norm must be 0 (the norm is that of the all-reduced gradient)");
-    for (int64_t j = 0; j < n_minibatches; ++j) {
-        int rc = ppoaf_mat_update_fwd_bwd(args, stream);
-        if (rc == PPOAF_OK) rc = ppoaf_mat_update_reduce(args, stream);
-        if (rc == PPOAF_OK) rc = ppoaf_allreduce_sum_f32(comm, args->grads, args->bucket_total, stream);
-        if (rc == PPOAF_OK)
-            rc = ppoaf_clip_adam_step(const_cast<float*>(args->params), args->grads, exp_avg, exp_avg_sq, args->bucket_total,
-                                      args->step_count, lr, beta1, beta2, eps, grad_scale, max_norm, args->norm_scratch,
-                                      grad_norm_out, stream);
-        if (rc != PPOAF_OK) return rc;
-    }
-    return PPOAF_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Box form: entry points (the kernels are the bodies above with U = MatBoxDev / MatBoxStepDev; the reduce and tail
-// launches are the Discrete kernels over the Box bucket's offset table and compact-slab layout)
-// ------------------------------------------------------------------------------------------------
-namespace ppoaf {
-// the rows' own raw actions [16][8] sit behind the 34 activation tiles
-static size_t mat_box_lds_bytes(int O) { return mat_lds_bytes(O) + kRows * 8 * 4; }
-
-static int make_mat_box(const ppoaf_mat_box_update_args_t* a, MatBoxDev& u, bool need_split = true) {
-    PPOAF_REQUIRE(a, "mat_box_update: null args");
-    const int rc = make_mat(&a->mat, u, a);
-    if (rc) return rc;
-    PPOAF_REQUIRE(!need_split || u.split, "mat_box_update: the Box form runs on the split-wgrad chain only (split_workspace is not set)");
-    u.actions = nullptr;
-    u.actions_f = a->raw_actions;
-    u.off_enc_b = a->enc_bias_offset; u.off_log_std = a->log_std_offset;
-    u.goff_enc_b = (int)a->enc_bias_offset; u.goff_log_std = (int)a->log_std_offset;   // the first run of the compact slab is the bucket's head
-    u.min_std = a->min_std;
-    return PPOAF_OK;
-}
-}  // namespace ppoaf
-
-extern "C" int ppoaf_mat_box_update_fwd_bwd(const ppoaf_mat_box_update_args_t* args, ppoaf_stream_t stream) {
-    MatBoxDev u;
-    const int rc = make_mat_box(args, u);
-    if (rc) return rc;
-    const size_t lds = mat_box_lds_bytes(u.O);
-    PPOAF_REQUIRE(lds <= 160 * 1024, "mat_box_update: needs %zu B of LDS (> 160 KiB)", lds);
-    static void (*const kern[2])(MatBoxDev) = {mat_box_update_fwd_bwd_kernel, mat_box_update_fwd_bwd_wide_kernel};
-    static bool attr_set = false;
-    if (!attr_set) {
-        for (int i = 0; i < 2; ++i) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern[i]),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern[mat_is_wide(u.O) ? 1 : 0], dim3((unsigned)u.nT), dim3(kMT), lds, (hipStream_t)stream, u);
-    return check_launch("mat_box_update_fwd_bwd");
-}
-
-extern "C" int ppoaf_mat_box_update_reduce(const ppoaf_mat_box_update_args_t* args, ppoaf_stream_t stream) {
-    MatBoxDev u;
-    const int rc = make_mat_box(args, u);
-    if (rc) return rc;
-    const int nsb = (4 * u.n_small4 + 255) / 256;
-    hipLaunchKernelGGL(mat_update_wgrad_kernel, dim3((unsigned)(kMatWgJobs + nsb + 1)), dim3(256), 0, (hipStream_t)stream,
-                       static_cast<const MatDev&>(u), nsb);
-    return check_launch("mat_box_update_reduce (wgrad)");
-}
-
-extern "C" int ppoaf_mat_box_update_split_workspace_bytes(const ppoaf_mat_box_update_args_t* args, int64_t* bytes_out) {
-    PPOAF_REQUIRE(args && bytes_out, "mat_box_update_split_workspace_bytes: null argument");
-    ppoaf_mat_box_update_args_t a = *args;
-    a.mat.split_workspace = nullptr; a.mat.split_workspace_bytes = 0;
-    MatBoxDev u;
-    const int rc = make_mat_box(&a, u, false);
-    if (rc) return rc;
-    *bytes_out = (int64_t)((size_t)(MAT_NUM_XPANELS + kMatLin) * u.R * kMD * 4);
-    return PPOAF_OK;
-}
-
-extern "C" int ppoaf_mat_box_update_tail_ctl_bytes(const ppoaf_mat_box_update_args_t* args, int64_t* bytes_out) {
-    PPOAF_REQUIRE(args && bytes_out, "mat_box_update_tail_ctl_bytes: null argument");
-    MatBoxDev u;
-    const int rc = make_mat_box(args, u);
-    if (rc) return rc;
-    *bytes_out = (int64_t)kTailRecOff + 16 * (int64_t)(kMatWgJobs + (4 * u.n_small4 + 255) / 256);
-    return PPOAF_OK;
-}
-
-extern "C" int ppoaf_mat_box_update_norm_partials(const ppoaf_mat_box_update_args_t* args) {
-    MatBoxDev u;
-    if (make_mat_box(args, u)) return -1;
-    return kMatWgJobs + (4 * u.n_small4 + 255) / 256;
-}
-
-extern "C" int ppoaf_mat_box_update_wgrad_adam(const ppoaf_mat_box_update_args_t* args, void* ctl, float* exp_avg, float* exp_avg_sq,
-                                               const float* lr, float beta1, float beta2, float eps, float grad_scale,
-                                               float max_norm, float* grad_norm_out, double wait_seconds, ppoaf_stream_t stream) {
-    MatBoxDev u;
-    const int rc = make_mat_box(args, u);
-    if (rc) return rc;
-    return mat_wgrad_adam_launch(u, ctl, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, grad_scale, max_norm, grad_norm_out,
-                                 wait_seconds, stream);
-}
-
-static int mat_box_policy_step_launch(const ppoaf_mat_box_step_args_t* a, const MatStepBlocks* tb, ppoaf_stream_t stream) {
-    MatBoxStepDev u;
-    const int rc = mat_step_dev(&a->mat, tb, a, u);
-    if (rc) return rc;
-    u.action_out = nullptr; u.raw_action_out = nullptr; u.forced_action = nullptr;
-    u.off_enc_b = a->enc_bias_offset; u.off_log_std = a->log_std_offset; u.min_std = a->min_std;
-    u.act_lo = a->act_lo; u.act_hi = a->act_hi;
-    u.action_f = a->action_out; u.raw_action_f = a->raw_action_out; u.forced_f = a->forced_action;
-    const size_t lds = mat_lds_bytes(u.O);
-    static void (*const kern[2])(MatBoxStepDev) = {mat_box_policy_step_kernel, mat_box_policy_step_wide_kernel};
-    static void (*const kern_b[2])(MatBoxStepDev, MatStepBlocks) = {mat_box_policy_step_blocks_kernel, mat_box_policy_step_blocks_wide_kernel};
-    static bool attr_set = false;
-    if (!attr_set) {
-        for (int i = 0; i < 4; ++i) {
-            const void* fn = i < 2 ? reinterpret_cast<const void*>(kern[i]) : reinterpret_cast<const void*>(kern_b[i - 2]);
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        }
-        attr_set = true;
-    }
-    const unsigned n_wg = (unsigned)((a->mat.E + u.per_tile - 1) / u.per_tile);
-    const int wide = mat_is_wide(u.O) ? 1 : 0;
-    if (tb) hipLaunchKernelGGL(kern_b[wide], dim3(n_wg), dim3(kMT), lds, (hipStream_t)stream, u, *tb);
-    else hipLaunchKernelGGL(kern[wide], dim3(n_wg), dim3(kMT), lds, (hipStream_t)stream, u);
-    return check_launch(tb ? "mat_box_policy_step_blocks" : "mat_box_policy_step");
-}
-
-extern "C" int ppoaf_mat_box_policy_step(const ppoaf_mat_box_step_args_t* a, ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a, "mat_box_policy_step: null args");
-    return mat_box_policy_step_launch(a, nullptr, stream);
-}
-
-extern "C" int ppoaf_mat_box_policy_step_blocks(const ppoaf_mat_box_step_args_t* a, const ppoaf_mat_box_step_blocks_t* t,
-                                                ppoaf_stream_t stream) {
-    PPOAF_REQUIRE(a && t, "mat_box_policy_step_blocks: null args");
-    MatStepBlocks tb;
-    const int rc = mat_step_blocks_dev(&a->mat, t, tb);
-    if (rc) return rc;
-    if (a->mat.E == 0) return PPOAF_OK;
-    return mat_box_policy_step_launch(a, &tb, stream);
-}
-
 PPOAF_LAYOUT(ppoaf_mat_box_update_args_t, mat, 0);
 PPOAF_LAYOUT(ppoaf_mat_box_update_args_t, raw_actions, sizeof(ppoaf_mat_update_args_t));
 PPOAF_LAYOUT(ppoaf_mat_box_update_args_t, enc_bias_offset, sizeof(ppoaf_mat_update_args_t) + 8);

@@ -84,12 +84,7 @@ __global__ __launch_bounds__(kThreadsU) void policy_infer_kernel(InferDev u) {
 template <int HT, bool XH>
 static int launch_infer(const InferDev& u, size_t lds, hipStream_t s) {
     static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_infer_kernel<HT, XH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
+    if (const int rc = allow_large_lds(policy_infer_kernel<HT, XH>, lds, attr_set, "policy_infer")) return rc;
     const unsigned grid = (unsigned)((u.E + kRows - 1) / kRows);
     hipLaunchKernelGGL((policy_infer_kernel<HT, XH>), dim3(grid), dim3(kThreadsU), lds, s, u);
     return check_launch("policy_infer");

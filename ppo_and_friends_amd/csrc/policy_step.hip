@@ -48,12 +48,7 @@ static size_t step_lds_bytes(const StepDev& u) {
 template <int HTA, int HTC, bool XH>
 static int launch_step(const StepDev& u, size_t lds, hipStream_t s) {
     static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_step_kernel<HTA, HTC, XH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
+    if (const int rc = allow_large_lds(policy_step_kernel<HTA, HTC, XH>, lds, attr_set, "policy_step")) return rc;
     const unsigned grid = 8u * (unsigned)((u.n_wg + 3) / 4);
     hipLaunchKernelGGL((policy_step_kernel<HTA, HTC, XH>), dim3(grid), dim3(kThreadsS), lds, s, u);
     return check_launch("policy_step");
@@ -62,12 +57,7 @@ static int launch_step(const StepDev& u, size_t lds, hipStream_t s) {
 template <int HTA, int HTC, bool XH>
 static int launch_step_blocks(const StepDev& u, const StepBlocks& tb, size_t lds, hipStream_t s) {
     static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_step_blocks_kernel<HTA, HTC, XH>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
+    if (const int rc = allow_large_lds(policy_step_blocks_kernel<HTA, HTC, XH>, lds, attr_set, "policy_step_blocks")) return rc;
     const unsigned grid = 8u * (unsigned)((u.n_wg + 3) / 4);
     hipLaunchKernelGGL((policy_step_blocks_kernel<HTA, HTC, XH>), dim3(grid), dim3(kThreadsS), lds, s, u, tb);
     return check_launch("policy_step_blocks");

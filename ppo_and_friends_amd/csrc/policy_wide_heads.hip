@@ -51,22 +51,10 @@ __global__ __launch_bounds__(kThreadsU) void policy_infer_wide_heads_kernel(Infe
                         u.seed, u.offset, u.action_out);
 }
 
-// dynamic LDS beyond 64 KB is asked for once per kernel
-template <class Kernel>
-static int allow_lds(Kernel k, bool& done, size_t lds) {
-    if (!done && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        done = true;
-    }
-    return PPOAF_OK;
-}
-
 template <int HA, int HC>
 static int launch_step_pair(const StepDev& u, size_t lds, hipStream_t s) {
     static bool attr_set = false;
-    const int rc = allow_lds(policy_step_wide_heads_kernel<HA / 16, HC / 16>, attr_set, lds);
-    if (rc) return rc;
+    if (const int rc = allow_large_lds(policy_step_wide_heads_kernel<HA / 16, HC / 16>, lds, attr_set, "policy_step")) return rc;
     const unsigned grid = 8u * (unsigned)((u.n_wg + 3) / 4);
     hipLaunchKernelGGL((policy_step_wide_heads_kernel<HA / 16, HC / 16>), dim3(grid), dim3(kThreadsS), lds, s, u);
     return check_launch("policy_step");
@@ -75,8 +63,7 @@ static int launch_step_pair(const StepDev& u, size_t lds, hipStream_t s) {
 template <int HA, int HC>
 static int launch_step_blocks_pair(const StepDev& u, const StepBlocks& tb, size_t lds, hipStream_t s) {
     static bool attr_set = false;
-    const int rc = allow_lds(policy_step_blocks_wide_heads_kernel<HA / 16, HC / 16>, attr_set, lds);
-    if (rc) return rc;
+    if (const int rc = allow_large_lds(policy_step_blocks_wide_heads_kernel<HA / 16, HC / 16>, lds, attr_set, "policy_step_blocks")) return rc;
     const unsigned grid = 8u * (unsigned)((u.n_wg + 3) / 4);
     hipLaunchKernelGGL((policy_step_blocks_wide_heads_kernel<HA / 16, HC / 16>), dim3(grid), dim3(kThreadsS), lds, s, u, tb);
     return check_launch("policy_step_blocks");
@@ -106,8 +93,7 @@ int launch_infer_wide_heads(const InferDev& u, size_t lds, hipStream_t s) {
         return PPOAF_E_INVALID;
     }
     static bool attr_set = false;
-    const int rc = allow_lds(policy_infer_wide_heads_kernel<16>, attr_set, lds);
-    if (rc) return rc;
+    if (const int rc = allow_large_lds(policy_infer_wide_heads_kernel<16>, lds, attr_set, "policy_infer")) return rc;
     const unsigned grid = (unsigned)((u.E + kRows - 1) / kRows);
     hipLaunchKernelGGL((policy_infer_wide_heads_kernel<16>), dim3(grid), dim3(kThreadsU), lds, s, u);
     return check_launch("policy_infer");

@@ -60,12 +60,7 @@ __global__ __launch_bounds__(kThreadsU) void ppo_update_fwd_bwd_pair_kernel(Upda
 template <int HTA, int HTC, bool SPLIT>
 inline int launch_fwd_bwd_as(const UpdateDev& u, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_update_fwd_bwd_kernel<HTA, HTC, SPLIT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
+    if (const int rc = allow_large_lds(ppo_update_fwd_bwd_kernel<HTA, HTC, SPLIT>, lds, attr_set, "ppo_update_fwd_bwd")) return rc;
     const unsigned grid = u.confine ? 8u * (unsigned)((u.n_wg + 1) / 2) : 8u * (unsigned)((u.n_wg + 3) / 4);     // groups of 4 actor + 4 critic blocks
     if (e0 || e1)        // the kernel's own begin / end stamped into the events (bench.py: roofline_update)
         hipExtLaunchKernelGGL((ppo_update_fwd_bwd_kernel<HTA, HTC, SPLIT>), dim3(grid), dim3(kThreadsU), lds, s, e0, e1, 0, u);
@@ -78,12 +73,7 @@ inline int launch_fwd_bwd_as(const UpdateDev& u, size_t lds, hipStream_t s, hipE
 template <int HTA, int HTC>
 inline int launch_fwd_bwd_pairs(const UpdateDev& u, const PairDev& pd, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
     static bool attr_set = false;
-    if (!attr_set && lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_update_fwd_bwd_pair_kernel<HTA, HTC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
+    if (const int rc = allow_large_lds(ppo_update_fwd_bwd_pair_kernel<HTA, HTC>, lds, attr_set, "ppo_update_fwd_bwd(row pairs)")) return rc;
     // slots per XCD: two per tile of a paired network (both networks share the grid: the wider need decides)
     const unsigned per_slot = u.confine ? 2u : 4u;
     const unsigned grid = 8u * 2u * (unsigned)((u.n_wg + per_slot - 1) / per_slot);

@@ -53,12 +53,7 @@ template <int HTA, int HTC, int ACT, int HEAD>
 static int launch_lean_as(const FwdBwdLaunch& L) {
     const UpdateDev& u = L.u;
     static bool attr_set = false;
-    if (!attr_set && L.lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_update_fwd_bwd_lean_kernel<HTA, HTC, ACT, HEAD>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
+    if (const int rc = allow_large_lds(ppo_update_fwd_bwd_lean_kernel<HTA, HTC, ACT, HEAD>, L.lds, attr_set, "ppo_update_fwd_bwd(lean)")) return rc;
     const unsigned grid = u.confine ? 8u * (unsigned)((u.n_wg + 1) / 2) : 8u * (unsigned)((u.n_wg + 3) / 4);     // launch_fwd_bwd_as's
     if (L.e0 || L.e1)
         hipExtLaunchKernelGGL((ppo_update_fwd_bwd_lean_kernel<HTA, HTC, ACT, HEAD>), dim3(grid), dim3(kThreadsU), L.lds, L.s, L.e0, L.e1, 0, u);

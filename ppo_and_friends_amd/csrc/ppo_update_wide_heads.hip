@@ -31,12 +31,7 @@ static int fwd_bwd_launch_wide_heads_pair(const FwdBwdLaunch& L) {
     static_assert(HC / 16 == kWideHT, "the wide body is the 512-wide critic's");
     const UpdateDev& u = L.u;
     static bool attr_set = false;
-    if (!attr_set && L.lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_update_fwd_bwd_wide_heads_kernel<HA / 16, HC / 16>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return PPOAF_E_LAUNCH; }
-        attr_set = true;
-    }
+    if (const int rc = allow_large_lds(ppo_update_fwd_bwd_wide_heads_kernel<HA / 16, HC / 16>, L.lds, attr_set, "ppo_update_fwd_bwd")) return rc;
     const unsigned grid = u.confine ? 8u * (unsigned)((u.n_wg + 1) / 2) : 8u * (unsigned)((u.n_wg + 3) / 4);
     if (L.e0 || L.e1)
         hipExtLaunchKernelGGL((ppo_update_fwd_bwd_wide_heads_kernel<HA / 16, HC / 16>), dim3(grid), dim3(kThreadsU), L.lds, L.s,
