@@ -1259,6 +1259,42 @@ int ppoaf_lstm_backward(const ppoaf_lstm_desc_t* desc, const float* c0, const fl
 int ppoaf_lstm_wgrad(const ppoaf_lstm_desc_t* desc, const float* x, const float* h0, ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * K18, two stacked layers: LSTMNetwork(num_lstm_layers=2).forward_logits and its gradients
+ * replaces nn.LSTM(in, H, 2) -> LayerNorm -> activation -> ff_layers of
+ *          LSTMNetwork.forward                     networks/ppo_networks/lstm.py:103-127
+ * The network above with a second LSTM layer whose input is the first one's h_t; LayerNorm and the head read layer 1's
+ * final hidden state.  Bucket: weight_ih_l0 [4H, in], weight_hh_l0 [4H, H], bias_ih_l0, bias_hh_l0, weight_ih_l1 [4H, H],
+ * weight_hh_l1 [4H, H], bias_ih_l1, bias_hh_l1, layer_norm.weight, layer_norm.bias, the Linears; every tensor padded to
+ * 4 floats.  Coverage and messages are the one-layer entry points'.
+ * h0 / c0 / hn / cn hold both layers' states: element k of layer l of row n lies at
+ * n * state_row_stride + l * state_layer_stride + k, so the module's [2, rows, H] (strides H, rows * H) and the rollout
+ * buffer's [rows, 2, H] (strides 2 H, H) are both read and written where they lie.
+ * ppoaf_lstm2_forward runs the two recurrences as a wavefront (layer 1 one step behind layer 0, one barrier per phase);
+ * with stash != 0 it keeps both layers' gates, c_t, h_t and initial h in the workspace.  ppoaf_lstm2_backward: d out ->
+ * head, LayerNorm, layer 1 backwards over the steps (its gate gradients and d h of layer 0, per step), then layer 0.
+ * ppoaf_lstm2_wgrad ADDS every parameter tensor's gradient to grads, each element reduced by one workgroup in a fixed
+ * order.  ppoaf_lstm2_check validates a descriptor on the host (need_workspace != 0: also the workspace) and launches
+ * nothing.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    int32_t in_dim, hidden, ff_hidden, ff_depth, out_dim, activation;
+    int64_t rows, steps;
+    const float* params;
+    float* grads;
+    float* workspace;
+    int64_t workspace_floats;
+    int64_t state_row_stride, state_layer_stride;    /* floats */
+} ppoaf_lstm2_desc_t;
+
+int ppoaf_lstm2_check(const ppoaf_lstm2_desc_t* desc, int32_t need_workspace);
+int ppoaf_lstm2_workspace_floats(const ppoaf_lstm2_desc_t* desc, int64_t* out /* host [2] */);
+int ppoaf_lstm2_forward(const ppoaf_lstm2_desc_t* desc, const float* x, const float* h0, const float* c0,
+                        float* out, float* hn /* NULL ok */, float* cn /* NULL ok */, int32_t stash,
+                        ppoaf_stream_t stream);
+int ppoaf_lstm2_backward(const ppoaf_lstm2_desc_t* desc, const float* c0, const float* dout, ppoaf_stream_t stream);
+int ppoaf_lstm2_wgrad(const ppoaf_lstm2_desc_t* desc, const float* x, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * K21  one env step of an LSTM actor / critic pair for all E rows in one launch
  * replaces PPOPolicy.get_rollout_actions            policies/ppo_policy.py:729-794
  *          PPO.get_policy_values + denormalisation  ppo.py:1030-1075, utils/misc.py:113-128

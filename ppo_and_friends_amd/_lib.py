@@ -43,6 +43,11 @@ class LstmDesc(C.Structure):
                 ("workspace_floats", C.c_int64)]
 
 
+class Lstm2Desc(C.Structure):
+    """ppoaf_lstm2_desc_t (include/ppoaf_hip.h): LstmDesc's fields, then the two state strides."""
+    _fields_ = LstmDesc._fields_ + [("state_row_stride", C.c_int64), ("state_layer_stride", C.c_int64)]
+
+
 class PpoUpdateArgs(C.Structure):
     """ppoaf_ppo_update_args_t (include/ppoaf_hip.h) -- field order must match the header."""
     _fields_ = [("actor", MlpDesc), ("critic", MlpDesc),
@@ -433,6 +438,11 @@ SIGNATURES = {
     "ppoaf_lstm_forward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int32, _ptr]),
     "ppoaf_lstm_backward": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),
     "ppoaf_lstm_wgrad": (C.c_int, [C.POINTER(LstmDesc), _ptr, _ptr, _ptr]),
+    "ppoaf_lstm2_check": (C.c_int, [C.POINTER(Lstm2Desc), C.c_int32]),
+    "ppoaf_lstm2_workspace_floats": (C.c_int, [C.POINTER(Lstm2Desc), C.POINTER(C.c_int64)]),
+    "ppoaf_lstm2_forward": (C.c_int, [C.POINTER(Lstm2Desc), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, C.c_int32, _ptr]),
+    "ppoaf_lstm2_backward": (C.c_int, [C.POINTER(Lstm2Desc), _ptr, _ptr, _ptr]),
+    "ppoaf_lstm2_wgrad": (C.c_int, [C.POINTER(Lstm2Desc), _ptr, _ptr]),
     "ppoaf_lstm_policy_step": (C.c_int, [C.POINTER(LstmPolicyStepArgs), _ptr]),
     "ppoaf_lstm_policy_step_check": (C.c_int, [C.POINTER(LstmPolicyStepArgs)]),
     "ppoaf_lstm_policy_step_blocks": (C.c_int, [C.POINTER(LstmPolicyStepArgs), C.POINTER(LstmStepBlocks), _ptr]),

@@ -558,9 +558,19 @@ class FusedLstm:
     """
 
     @staticmethod
-    def unsupported_reason(pol):
-        """'' when K18 covers both networks of this LSTM policy, else why not."""
+    def stacked(pol):
+        """True for a policy whose recurrent networks have more than one layer: K18's stacked kernels take it (opt-in
+        `fused_lstm_layers`), K21 and K22 do not."""
+        return any(getattr(net, "num_lstm_layers", 1) != 1 for net in (pol.actor, pol.critic))
+
+    @staticmethod
+    def unsupported_reason(pol, lstm_layers=None):
+        """'' when K18 covers both networks of this LSTM policy, else why not.  Two stacked layers (both networks) are
+        taken with the policy's opt-in `fused_lstm_layers` only (`lstm_layers`: the hypothetical answer with it on / off;
+        the opt-in concerns LSTM policies alone, so it is read here and is no field of FusedOptIns)."""
         from .networks.lstm import LSTMNetwork
+        if lstm_layers is None:
+            lstm_layers = bool(getattr(pol, "fused_lstm_layers", False))
         if not pol.using_lstm:
             return "not an LSTM policy"
         if pol.agent_grouping:
@@ -570,11 +580,21 @@ class FusedLstm:
         for tag, net in (("actor", pol.actor), ("critic", pol.critic)):
             if not isinstance(net, LSTMNetwork):
                 return f"{tag}: {type(net).__name__} is not an LSTMNetwork"
-            why = net.hip_unsupported_reason()
+            why = net._hip_scope(max_layers=2) if lstm_layers else net.hip_unsupported_reason()
             if why:
                 return f"{tag}: {why}"
+        la, lc = pol.actor.num_lstm_layers, pol.critic.num_lstm_layers
+        if la != lc:
+            return f"LSTM layer counts differ (actor {la}, critic {lc}): the stacked kernels take two layers in both networks"
         if pol.critic.out_size != 1:
             return "critic must have one output"
+        return ""
+
+    @staticmethod
+    def layers_hint(pol):
+        """verbose: what to append to the refusal of a policy that only `fused_lstm_layers` keeps off K18."""
+        if pol.using_lstm and FusedLstm.unsupported_reason(pol) and FusedLstm.unsupported_reason(pol, lstm_layers=True) == "":
+            return "; PPOPolicy.fused_lstm_layers = True would take it on K18 (forward_logits and the mini-batch loop)"
         return ""
 
 
@@ -610,6 +630,8 @@ class FusedLstmUpdate(FusedEpoch):
         why = FusedLstm.unsupported_reason(pol)
         if why:
             return why
+        if FusedLstm.stacked(pol):
+            return f"{pol.actor.num_lstm_layers} LSTM layers: K22 covers one; the mini-batch loop on K18 trains it"
         ha, hc = pol.actor.lstm_hidden_size, pol.critic.lstm_hidden_size
         if ha != hc:
             return f"LSTM hidden sizes differ (actor {ha}, critic {hc}): one K22 launch has one block size"

@@ -869,6 +869,75 @@ def lstm_backward(desc, x, h0, c0, dout):
 
 
 # --------------------------------------------------------------------------
+# K18, two stacked layers (csrc/lstm_stacked.hip): LSTMNetwork(num_lstm_layers=2).forward_logits
+# --------------------------------------------------------------------------
+def lstm2_desc(in_dim, hidden, ff_hidden, ff_depth, out_dim, activation, rows, steps, params, grads=None,
+               workspace=None, rows_major_state=False):
+    """ppoaf_lstm2_desc_t over a network's flat buckets.  The states (h0, c0, hn, cn) are [2, rows, H] tensors, or
+    [rows, 2, H] ones (the rollout buffer's rows) with `rows_major_state`: either is read and written where it lies."""
+    d = _lib.Lstm2Desc()
+    d.in_dim, d.hidden, d.ff_hidden, d.ff_depth, d.out_dim, d.activation = \
+        int(in_dim), int(hidden), int(ff_hidden), int(ff_depth), int(out_dim), int(activation)
+    d.rows, d.steps = int(rows), int(steps)
+    d.params = ptr(_f32(params, "params"))
+    d.grads = None if grads is None else ptr(_f32(grads, "grads"))
+    d.workspace = None if workspace is None else ptr(_f32(workspace, "workspace"))
+    d.workspace_floats = 0 if workspace is None else workspace.numel()
+    d.state_row_stride, d.state_layer_stride = (2 * d.hidden, d.hidden) if rows_major_state else (d.hidden, d.rows * d.hidden)
+    return d
+
+
+def lstm2_refusal(desc, need_workspace=False):
+    """'' when ppoaf_lstm2_check accepts the descriptor (host only: nothing is launched), else the library's message."""
+    lib = _lib.load()
+    if lib.ppoaf_lstm2_check(C.byref(desc), 1 if need_workspace else 0) == 0:
+        return ""
+    return lib.ppoaf_last_error().decode()
+
+
+def lstm2_sizes(desc):
+    """(workspace floats, bucket floats of the network) for this shape."""
+    out = (C.c_int64 * 2)()
+    check(_lib.load().ppoaf_lstm2_workspace_floats(C.byref(desc), out), "lstm2_workspace_floats")
+    return int(out[0]), int(out[1])
+
+
+def _lstm2_state(t, desc, name):
+    rows_major = desc.state_layer_stride == desc.hidden and desc.state_row_stride == 2 * desc.hidden
+    shape = (desc.rows, 2, desc.hidden) if rows_major else (2, desc.rows, desc.hidden)
+    _f32(t, name)
+    _req(t.is_contiguous() and tuple(t.shape) == shape, f"{name} must be a contiguous {list(shape)} float32 tensor")
+    return shape
+
+
+def lstm2_forward(desc, x, h0, c0, stash):
+    """x [rows, steps, in_dim] -> (out [rows, out_dim], h_n, c_n), the states of both layers in the layout of h0 / c0
+    ([2, rows, H], or [rows, 2, H] for a descriptor made with rows_major_state); stash: keep what backward reads."""
+    _f32(x, "x")
+    _req(x.is_contiguous() and x.numel() == desc.rows * desc.steps * desc.in_dim,
+         "x must be a contiguous [rows, steps, in_dim] float32 tensor")
+    shape = _lstm2_state(h0, desc, "h0")
+    _lstm2_state(c0, desc, "c0")
+    out = torch.empty(desc.rows, desc.out_dim, dtype=torch.float32, device=x.device)
+    hn = torch.empty(shape, dtype=torch.float32, device=x.device)
+    cn = torch.empty_like(hn)
+    check(_lib.load().ppoaf_lstm2_forward(C.byref(desc), ptr(x), ptr(h0), ptr(c0), ptr(out), ptr(hn), ptr(cn),
+                                          1 if stash else 0, stream()), "lstm2_forward")
+    return out, hn, cn
+
+
+def lstm2_backward(desc, x, c0, dout):
+    """d out [rows, out_dim] -> dgrad into the workspace, then the weight gradients ADDED to desc.grads."""
+    _f32(dout, "dout")
+    _f32(x, "x")
+    _req(dout.is_contiguous() and dout.numel() == desc.rows * desc.out_dim, "dout must be a contiguous [rows, out_dim] tensor")
+    _lstm2_state(c0, desc, "c0")
+    lib = _lib.load()
+    check(lib.ppoaf_lstm2_backward(C.byref(desc), ptr(c0), ptr(dout), stream()), "lstm2_backward")
+    check(lib.ppoaf_lstm2_wgrad(C.byref(desc), ptr(x), stream()), "lstm2_wgrad")
+
+
+# --------------------------------------------------------------------------
 # K21: one env step of an LSTM actor / critic pair (csrc/lstm_policy_step.hip)
 # --------------------------------------------------------------------------
 LSTM_STEP, LSTM_CRITIC_NEXT, LSTM_INFER, LSTM_MASK = 0, 1, 2, 3

@@ -32,9 +32,14 @@ class _HipLstm(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, h0, c0, net, *params):
-        desc = net._hip_desc(x.shape[0], x.shape[1], training=True)
-        out, hn, cn = K.lstm_forward(desc, x, h0, c0, stash=True)
+    def forward(ctx, x, h0, c0, net, rows_major, *params):
+        ctx.rows_major = rows_major
+        if net.num_lstm_layers == 2:                       # (h0 / c0 hold both layers: [2, B, H], or [B, 2, H] rows: rows_major)
+            desc = net._hip_desc(x.shape[0], x.shape[1], training=True, rows_major_state=ctx.rows_major)
+            out, hn, cn = K.lstm2_forward(desc, x, h0, c0, stash=True)
+        else:
+            desc = net._hip_desc(x.shape[0], x.shape[1], training=True)
+            out, hn, cn = K.lstm_forward(desc, x, h0, c0, stash=True)
         ctx.net, ctx.gen, ctx.shape = net, net._hip_gen, (x.shape[0], x.shape[1])
         ctx.save_for_backward(x, h0, c0)
         ctx.mark_non_differentiable(hn, cn)
@@ -48,9 +53,13 @@ class _HipLstm(torch.autograd.Function):
                                "backward reads has been overwritten")
         x, h0, c0 = ctx.saved_tensors
         if dout is not None:
-            desc = net._hip_desc(*ctx.shape, training=True, reuse=True)
-            K.lstm_backward(desc, x, h0, c0, dout.contiguous())
-        return (None, None, None, None) + (None,) * len(net._hip_params())
+            if net.num_lstm_layers == 2:
+                desc = net._hip_desc(*ctx.shape, training=True, reuse=True, rows_major_state=ctx.rows_major)
+                K.lstm2_backward(desc, x, c0, dout.contiguous())
+            else:
+                desc = net._hip_desc(*ctx.shape, training=True, reuse=True)
+                K.lstm_backward(desc, x, h0, c0, dout.contiguous())
+        return (None, None, None, None, None) + (None,) * len(net._hip_params())
 
 
 class PPOLSTMNetwork(PPONetwork):
@@ -97,9 +106,16 @@ class LSTMNetwork(PPOLSTMNetwork):
 
     def hip_unsupported_reason(self):
         """'' when K18 covers this network (shapes, activation, bucket layout), else why not."""
+        return self._hip_scope(max_layers=1)
+
+    def _hip_scope(self, max_layers):
+        """hip_unsupported_reason for a caller that takes up to `max_layers` LSTM layers (2: the stacked kernels of
+        csrc/lstm_stacked.hip, the policy's opt-in `fused_lstm_layers`)."""
         from ..fused_update import _activation_code
-        if self.num_lstm_layers != 1:
+        if self.num_lstm_layers != 1 and max_layers == 1:
             return f"{self.num_lstm_layers} LSTM layers (K18 covers one)"
+        if not 1 <= self.num_lstm_layers <= max_layers:
+            return f"{self.num_lstm_layers} LSTM layers (K18 covers one or two)"
         if self.lstm_hidden_size not in (32, 64, 128):
             return f"LSTM hidden size {self.lstm_hidden_size} is not one of 32, 64, 128"
         if self.sequence_length > 16:
@@ -125,19 +141,25 @@ class LSTMNetwork(PPOLSTMNetwork):
                 off += (p.numel() + 3) // 4 * 4
         return ""
 
-    def _hip_desc(self, rows, steps, training, reuse=False):
+    def _hip_desc(self, rows, steps, training, reuse=False, rows_major_state=False):
         from ..fused_update import _activation_code
         dims = self.ff_layers.layer_dims()
         args = (self.in_size, self.lstm_hidden_size, dims[0][1], len(dims) - 1, self.out_size,
                 _activation_code(self.activation), rows, steps, self.flat_params)
+        if self.num_lstm_layers == 2:
+            def make(**kw):
+                return K.lstm2_desc(*args, rows_major_state=rows_major_state, **kw)
+            sizes = K.lstm2_sizes
+        else:
+            make, sizes = (lambda **kw: K.lstm_desc(*args, **kw)), K.lstm_sizes
         if not training:
-            return K.lstm_desc(*args)
+            return make()
         if not reuse:
-            need, _ = K.lstm_sizes(K.lstm_desc(*args))
+            need, _ = sizes(make())
             if self._hip_ws is None or self._hip_ws.numel() < need or self._hip_ws.device != self.flat_params.device:
                 self._hip_ws = torch.empty(need, dtype=torch.float32, device=self.flat_params.device)
             self._hip_gen += 1
-        return K.lstm_desc(*args, grads=self.flat_grads, workspace=self._hip_ws)
+        return make(grads=self.flat_grads, workspace=self._hip_ws)
 
     def _hip_forward_logits(self, _input):
         x = _input.unsqueeze(1) if _input.dim() == 2 else _input
@@ -145,13 +167,31 @@ class LSTMNetwork(PPOLSTMNetwork):
         batch_size, H = x.shape[0], self.lstm_hidden_size
         if self.hidden_state is None or self.hidden_state[0].shape[1] != batch_size:
             self.reset_hidden_state(batch_size, x.device)
-        h0, c0 = (t.reshape(batch_size, H).contiguous() for t in self.hidden_state)
         params = self._hip_params()
+        if self.num_lstm_layers == 2:
+            return self._hip_forward_logits_stacked(x, params)
+        h0, c0 = (t.reshape(batch_size, H).contiguous() for t in self.hidden_state)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            out, hn, cn = _HipLstm.apply(x, h0, c0, self, *params)
+            out, hn, cn = _HipLstm.apply(x, h0, c0, self, False, *params)
         else:
             out, hn, cn = K.lstm_forward(self._hip_desc(batch_size, x.shape[1], training=False), x, h0, c0, stash=False)
         self.hidden_state = (hn.view(1, batch_size, H), cn.view(1, batch_size, H))
+        return out
+
+    def _hip_forward_logits_stacked(self, x, params):
+        """Two layers: hidden_state is (h, c) of shape [2, B, H], what nn.LSTM would leave.  A state that is a transposed
+        view of [B, 2, H] rows (the update assigns the dataset's rows: PPOPolicy.load_hidden_states) is read, and the
+        new one written, in that layout: no transpose or copy on the host."""
+        B = x.shape[0]
+        h, c = self.hidden_state
+        rows_major = B > 1 and not h.is_contiguous() and h.transpose(0, 1).is_contiguous() and c.transpose(0, 1).is_contiguous()
+        h0, c0 = (h.transpose(0, 1), c.transpose(0, 1)) if rows_major else (h.contiguous(), c.contiguous())
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            out, hn, cn = _HipLstm.apply(x, h0, c0, self, rows_major, *params)
+        else:
+            desc = self._hip_desc(B, x.shape[1], training=False, rows_major_state=rows_major)
+            out, hn, cn = K.lstm2_forward(desc, x, h0, c0, stash=False)
+        self.hidden_state = (hn.transpose(0, 1), cn.transpose(0, 1)) if rows_major else (hn, cn)
         return out
 
     def forward_logits(self, _input):

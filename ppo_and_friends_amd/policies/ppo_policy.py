@@ -131,6 +131,13 @@ class PPOPolicy:
     # those ICMs, with today's messages ("action widths (18, 18) must be in [1, 8]"); an ICM with action widths <= 8 computes
     # bitwise the same, flag on or off.  MultiDiscrete ICMs keep 16 classes in all.
     fused_wide_icm_actions = False
+    # Opt-in: an LSTM policy whose two networks both stack TWO LSTM layers (num_lstm_layers=2) on K18's stacked kernels
+    # (csrc/lstm_stacked.hip) under update_mode="fused": forward_logits in the rollout and in evaluation, the mini-batch loop
+    # in the update.  K21 and K22 stay one-layer, so such a policy takes neither.  Set by hand, on the class or on the policy,
+    # before the first rollout -- no update_mode sets it.  False: two layers are refused with today's message ("2 LSTM layers
+    # (K18 covers one)") under "fused" and train on nn.LSTM under "auto"; a one-layer policy computes bitwise the same, flag
+    # on or off.
+    fused_lstm_layers = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -378,10 +385,11 @@ class PPOPolicy:
 
     def load_hidden_states(self, mb):
         """ppo.py:2312-2319: the mini-batch's stored states become the networks' initial states."""
-        self.actor.hidden_state = (mb["actor_hidden"].transpose(0, 1).contiguous(),
-                                   mb["actor_cell"].transpose(0, 1).contiguous())
-        self.critic.hidden_state = (mb["critic_hidden"].transpose(0, 1).contiguous(),
-                                    mb["critic_cell"].transpose(0, 1).contiguous())
+        for tag, net in (("actor", self.actor), ("critic", self.critic)):
+            h, c = mb[tag + "_hidden"].transpose(0, 1), mb[tag + "_cell"].transpose(0, 1)
+            if not (getattr(net, "use_hip", False) and net.num_lstm_layers == 2):      # (the stacked kernels read [B, 2, H] rows)
+                h, c = h.contiguous(), c.contiguous()
+            net.hidden_state = (h, c)
 
     def write_back_hidden_states(self, dataset, batch_idxs):
         """ppo.py:2450-2466: the states the networks ended the window with replace the stored ones."""
@@ -513,6 +521,8 @@ class PPOPolicy:
         why = FusedLstm.unsupported_reason(self)
         if why:
             return why
+        if FusedLstm.stacked(self):
+            return f"{self.actor.num_lstm_layers} LSTM layers: K21 covers one; forward_logits on K18 steps the policy"
         if not (self.actor.use_hip and self.critic.use_hip):
             return "the networks run nn.LSTM (use_hip is not set: update_mode='auto' keeps today's route)"
         ha, hc = self.actor.lstm_hidden_size, self.critic.lstm_hidden_size

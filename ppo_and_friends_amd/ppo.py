@@ -538,6 +538,7 @@ class PPO:
                 from .fused_update import FusedLstm
                 why = FusedLstm.unsupported_reason(pol)
                 if why:
+                    why += FusedLstm.layers_hint(pol) if verbose else ""
                     raise NotImplementedError(f"update_mode='fused' but policy {policy_id}: {why}")
                 pol.actor.use_hip = pol.critic.use_hip = True
             elif update_mode == "fused" and not pol.agent_grouping and self.device.type == "cuda":
