@@ -1391,6 +1391,53 @@ int ppoaf_lstm_policy_step_blocks(const ppoaf_lstm_policy_step_args_t* args, con
 int ppoaf_lstm_policy_step_blocks_check(const ppoaf_lstm_policy_step_args_t* args, const ppoaf_lstm_step_blocks_t* blocks);
 
 /* ------------------------------------------------------------------------ *
+ * K21 for two stacked LSTM layers: one env step of a two-layer actor / critic pair in one launch
+ * The four modes, the heads, the Philox counters (row e draws at offset + e), the value denormalisation, the observation
+ * copies, the device byte `commit` and the zeroing of terminated envs' stored rows are ppoaf_lstm_policy_step's; the
+ * networks are ppoaf_lstm2_forward's (same descriptors, limits and bucket layout; steps = 1, `rows` is not read: E rules),
+ * both with ONE LSTM hidden size.  A state is two rows of `hidden` floats per env row:
+ *   actor_h / actor_c / critic_h / critic_c   the networks' own states, stepped IN PLACE; element k of layer l of row n
+ *       lies at n * state_row_stride + l * state_layer_stride + k of the network's descriptor ([2, E, H]: strides H and
+ *       E * H; [E, 2, H]: 2 H and H);
+ *   *_hidden_out / *_cell_out   the step's rows of the rollout buffer, at n * stored_row_stride + l * stored_layer_stride
+ *       + k ([E, 2, H]: 2 H and H).  MASK and CRITIC_NEXT zero 2 * hidden floats per terminated row in each of the four.
+ * One workgroup of 2 * hidden / 16 waves per 16-row tile and network: waves [0, hidden / 16) own layer 0, the others
+ * layer 1.  Phase A: layer 0 forms its gates and runs its cell while layer 1 forms h1 . W_hh_l1^T; one barrier; phase B:
+ * layer 1 adds bias + h0' . W_ih_l1^T and runs its cell while layer 0 stores its state and copies the observation; then
+ * LayerNorm, the feed-forward head and the action heads.  Every sum is formed in ppoaf_lstm2_forward's order, so the
+ * stepped (h, c) are bitwise those of ppoaf_lstm2_forward at one step.  STEP launches 2 * ceil(E/16) workgroups grouped
+ * per XCD as ppoaf_lstm_policy_step's, the other modes ceil(E/16).
+ * The block forms read the observations through a ppoaf_lstm_step_blocks_t exactly as ppoaf_lstm_policy_step_blocks does
+ * (STEP and CRITIC_NEXT only; the env action also goes to the env's action blocks; `terminated` holds per-env bytes).
+ * The *_check entry points validate on the host and launch nothing; E = 0 is accepted and launches nothing.
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    ppoaf_lstm2_desc_t actor, critic;
+    const float* obs; const float* critic_obs; int64_t E;
+    float* actor_h; float* actor_c; float* critic_h; float* critic_c;
+    int32_t head_kind; float min_std;
+    const float* log_std;
+    const float* act_lo; const float* act_hi;
+    const void* forced_raw_action;
+    uint64_t seed, offset;
+    int32_t normalize_values; int32_t mode;
+    const float* vn_mean; const float* vn_var;
+    void* raw_action_out; void* action_out; float* logp_out; float* value_out;
+    float* obs_copy_out; float* critic_obs_copy_out;
+    float* actor_hidden_out; float* actor_cell_out; float* critic_hidden_out; float* critic_cell_out;
+    int32_t infer_mode; int32_t _pad;
+    const uint8_t* commit; const uint8_t* terminated;
+    float* boot_value_out;
+    int64_t stored_row_stride, stored_layer_stride;   /* floats: the four *_hidden_out / *_cell_out rows */
+} ppoaf_lstm2_policy_step_args_t;
+
+int ppoaf_lstm2_policy_step(const ppoaf_lstm2_policy_step_args_t* args, ppoaf_stream_t stream);
+int ppoaf_lstm2_policy_step_check(const ppoaf_lstm2_policy_step_args_t* args);
+int ppoaf_lstm2_policy_step_blocks(const ppoaf_lstm2_policy_step_args_t* args, const ppoaf_lstm_step_blocks_t* blocks,
+                                   ppoaf_stream_t stream);
+int ppoaf_lstm2_policy_step_blocks_check(const ppoaf_lstm2_policy_step_args_t* args, const ppoaf_lstm_step_blocks_t* blocks);
+
+/* ------------------------------------------------------------------------ *
  * K22  one mini-batch of the PPO update of an LSTM actor / critic pair as three launches
  * replaces, per mini-batch of PPO._ppo_batch_train    ppo.py:2292-2469
  *          the window gather of the dataset           utils/episode_info.py:775-809,940-987

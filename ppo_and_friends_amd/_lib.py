@@ -126,6 +126,13 @@ class LstmPolicyStepArgs(C.Structure):
                 ("boot_value_out", C.c_void_p)]
 
 
+class Lstm2PolicyStepArgs(C.Structure):
+    """ppoaf_lstm2_policy_step_args_t (include/ppoaf_hip.h): LstmPolicyStepArgs' fields over two Lstm2Desc, then the two
+    strides of the stored rows."""
+    _fields_ = [("actor", Lstm2Desc), ("critic", Lstm2Desc)] + LstmPolicyStepArgs._fields_[2:] + \
+               [("stored_row_stride", C.c_int64), ("stored_layer_stride", C.c_int64)]
+
+
 class LstmUpdateArgs(C.Structure):
     """ppoaf_lstm_update_args_t (include/ppoaf_hip.h) -- field order must match the header."""
     _fields_ = [("actor", LstmDesc), ("critic", LstmDesc),
@@ -447,6 +454,10 @@ SIGNATURES = {
     "ppoaf_lstm_policy_step_check": (C.c_int, [C.POINTER(LstmPolicyStepArgs)]),
     "ppoaf_lstm_policy_step_blocks": (C.c_int, [C.POINTER(LstmPolicyStepArgs), C.POINTER(LstmStepBlocks), _ptr]),
     "ppoaf_lstm_policy_step_blocks_check": (C.c_int, [C.POINTER(LstmPolicyStepArgs), C.POINTER(LstmStepBlocks)]),
+    "ppoaf_lstm2_policy_step": (C.c_int, [C.POINTER(Lstm2PolicyStepArgs), _ptr]),
+    "ppoaf_lstm2_policy_step_check": (C.c_int, [C.POINTER(Lstm2PolicyStepArgs)]),
+    "ppoaf_lstm2_policy_step_blocks": (C.c_int, [C.POINTER(Lstm2PolicyStepArgs), C.POINTER(LstmStepBlocks), _ptr]),
+    "ppoaf_lstm2_policy_step_blocks_check": (C.c_int, [C.POINTER(Lstm2PolicyStepArgs), C.POINTER(LstmStepBlocks)]),
     "ppoaf_lstm_update_check": (C.c_int, [C.POINTER(LstmUpdateArgs), C.c_int32]),
     "ppoaf_lstm_update_workspace_floats": (C.c_int, [C.POINTER(LstmUpdateArgs), C.POINTER(C.c_int64)]),
     "ppoaf_lstm_update_fwd_bwd": (C.c_int, [C.POINTER(LstmUpdateArgs), _ptr]),

@@ -945,11 +945,25 @@ LSTM_STEP, LSTM_CRITIC_NEXT, LSTM_INFER, LSTM_MASK = 0, 1, 2, 3
 
 def lstm_policy_step_refusal(args):
     """'' when ppoaf_lstm_policy_step_check accepts the filled _lib.LstmPolicyStepArgs (host only: nothing is launched,
-    pointers are only compared with NULL), else the library's reason."""
+    pointers are only compared with NULL), else the library's reason.  A _lib.Lstm2PolicyStepArgs (two LSTM layers per
+    network) is asked of ppoaf_lstm2_policy_step_check; the wrappers below take either and launch its entry point."""
     lib = _lib.load()
-    if lib.ppoaf_lstm_policy_step_check(C.byref(args)) == 0:
+    fn = lib.ppoaf_lstm2_policy_step_check if _lstm_layers(args) == 2 else lib.ppoaf_lstm_policy_step_check
+    if fn(C.byref(args)) == 0:
         return ""
     return lib.ppoaf_last_error().decode("utf-8", "replace")
+
+
+def lstm2_policy_step_args(E, hidden):
+    """_lib.Lstm2PolicyStepArgs for E rows of one step with the layouts a policy holds: the networks' states [2, E, H],
+    the step's stored rows [E, 2, H].  The caller fills the descriptors' shapes and buckets and the head fields."""
+    a = _lib.Lstm2PolicyStepArgs()
+    a.E = int(E)
+    for d in (a.actor, a.critic):
+        d.hidden, d.rows, d.steps = int(hidden), int(E), 1
+        d.state_row_stride, d.state_layer_stride = int(hidden), int(E) * int(hidden)
+    a.stored_row_stride, a.stored_layer_stride = 2 * int(hidden), int(hidden)
+    return a
 
 
 def _lstm_rows(t, E, width, name, dtype=torch.float32):
@@ -964,31 +978,52 @@ def _lstm_flags(t, n, name):
     return t.data_ptr()
 
 
+def _lstm_layers(args):
+    """2 for the two-layer arguments (_lib.Lstm2PolicyStepArgs: csrc/lstm_stacked_step.hip), else 1."""
+    return 2 if isinstance(args, _lib.Lstm2PolicyStepArgs) else 1
+
+
 def _lstm_states(args, which, h, c):
-    H = getattr(args, which).hidden
-    setattr(args, which + "_h", _lstm_rows(h, args.E, H, which + " h"))
-    setattr(args, which + "_c", _lstm_rows(c, args.E, H, which + " c"))
+    """The network's own (h, c): [E, H]; two layers: [2, E, H] or [E, 2, H], whichever the descriptor's strides say."""
+    desc = getattr(args, which)
+    if _lstm_layers(args) == 2:
+        _req(desc.rows == args.E, f"{which}: the descriptor's rows must be E = {args.E}")
+        for t, n in ((h, " h"), (c, " c")):
+            _req(t.is_cuda, which + n + " must be a device tensor")
+            _lstm2_state(t, desc, which + n)
+        setattr(args, which + "_h", h.data_ptr())
+        setattr(args, which + "_c", c.data_ptr())
+        return
+    setattr(args, which + "_h", _lstm_rows(h, args.E, desc.hidden, which + " h"))
+    setattr(args, which + "_c", _lstm_rows(c, args.E, desc.hidden, which + " c"))
 
 
 def _lstm_stored(args, stored):
-    """stored: the step's rows (actor_hidden, actor_cell, critic_hidden, critic_cell), each [E, H]."""
+    """stored: the step's rows (actor_hidden, actor_cell, critic_hidden, critic_cell), each [E, H]; two layers: [E, 2, H]."""
+    layers = _lstm_layers(args)
+    if layers == 2:
+        _req(all(tuple(t.shape) == (args.E, 2, args.actor.hidden) for t in stored) and
+             (args.stored_row_stride, args.stored_layer_stride) == (2 * args.actor.hidden, args.actor.hidden),
+             "the stored rows must be [E, 2, H] tensors and the stored strides (2 H, H)")
     for f, t in zip(("actor_hidden_out", "actor_cell_out", "critic_hidden_out", "critic_cell_out"), stored):
-        setattr(args, f, _lstm_rows(t, args.E, args.actor.hidden, f))
+        setattr(args, f, _lstm_rows(t, args.E, args.actor.hidden * layers, f))
 
 
 def _lstm_launch(args, mode, blocks=None):
     args.mode = mode
+    name = "lstm2_policy_step" if _lstm_layers(args) == 2 else "lstm_policy_step"
     if blocks is None:
-        check(_lib.load().ppoaf_lstm_policy_step(C.byref(args), stream()), "lstm_policy_step")
+        check(getattr(_lib.load(), "ppoaf_" + name)(C.byref(args), stream()), name)
     else:
-        check(_lib.load().ppoaf_lstm_policy_step_blocks(C.byref(args), C.byref(blocks), stream()), "lstm_policy_step_blocks")
+        check(getattr(_lib.load(), f"ppoaf_{name}_blocks")(C.byref(args), C.byref(blocks), stream()), name + "_blocks")
 
 
 def lstm_policy_step_blocks_refusal(args, blocks):
     """'' when ppoaf_lstm_policy_step_blocks_check accepts the filled arguments and the _lib.LstmStepBlocks table (host
     only: nothing is launched, pointers are compared with NULL and looked at for their alignment), else the reason."""
     lib = _lib.load()
-    if lib.ppoaf_lstm_policy_step_blocks_check(C.byref(args), C.byref(blocks)) == 0:
+    fn = lib.ppoaf_lstm2_policy_step_blocks_check if _lstm_layers(args) == 2 else lib.ppoaf_lstm_policy_step_blocks_check
+    if fn(C.byref(args), C.byref(blocks)) == 0:
         return ""
     return lib.ppoaf_last_error().decode("utf-8", "replace")
 

@@ -133,11 +133,18 @@ class PPOPolicy:
     fused_wide_icm_actions = False
     # Opt-in: an LSTM policy whose two networks both stack TWO LSTM layers (num_lstm_layers=2) on K18's stacked kernels
     # (csrc/lstm_stacked.hip) under update_mode="fused": forward_logits in the rollout and in evaluation, the mini-batch loop
-    # in the update.  K21 and K22 stay one-layer, so such a policy takes neither.  Set by hand, on the class or on the policy,
+    # in the update.  K22 stays one-layer, and K21 takes such a policy with `fused_lstm_layers_step` (below) only.  Set by hand, on the class or on the policy,
     # before the first rollout -- no update_mode sets it.  False: two layers are refused with today's message ("2 LSTM layers
     # (K18 covers one)") under "fused" and train on nn.LSTM under "auto"; a one-layer policy computes bitwise the same, flag
     # on or off.
     fused_lstm_layers = False
+    # Opt-in, beside `fused_lstm_layers`: such a two-layer policy's rollout and evaluation step in ONE launch (K21 for two
+    # stacked layers, csrc/lstm_stacked_step.hip: lstm_rollout_step, lstm_finish_step, lstm_last_value, the evaluation step
+    # and the block forms of PPO.lstm_members), the networks' [2, E, H] states stepped in place.  K22 stays one-layer: the
+    # update runs the K18 mini-batch loop.  Set by hand, on the class or on the policy, before the first rollout -- no
+    # update_mode sets it.  False: such a policy steps on forward_logits, with today's message ("2 LSTM layers: K21 covers
+    # one"); a one-layer policy computes bitwise the same, flag on or off.
+    fused_lstm_layers_step = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -511,7 +518,8 @@ class PPOPolicy:
             return f"the policy lives on {self.device}: K21 needs a HIP device"
         if getattr(self, "update_mode", "auto") == "torch":
             return "update_mode='torch' keeps the policy on the torch-ROCm path"
-        key = (self.policy_params.data_ptr(), bool(self.actor.use_hip), bool(self.critic.use_hip), bool(self.enable_icm))
+        key = (self.policy_params.data_ptr(), bool(self.actor.use_hip), bool(self.critic.use_hip), bool(self.enable_icm),
+               self._lstm_step_layers())
         if getattr(self, "_lstm_step_reason", (None, ""))[0] != key:
             self._lstm_step_reason = (key, self._lstm_step_scope())
         return self._lstm_step_reason[1]
@@ -521,7 +529,7 @@ class PPOPolicy:
         why = FusedLstm.unsupported_reason(self)
         if why:
             return why
-        if FusedLstm.stacked(self):
+        if FusedLstm.stacked(self) and PPOPolicy._lstm_step_layers(self) != 2:
             return f"{self.actor.num_lstm_layers} LSTM layers: K21 covers one; forward_logits on K18 steps the policy"
         if not (self.actor.use_hip and self.critic.use_hip):
             return "the networks run nn.LSTM (use_hip is not set: update_mode='auto' keeps today's route)"
@@ -531,17 +539,34 @@ class PPOPolicy:
         if self.enable_icm:
             return "ICM policies keep today's route (K21 does not keep the next-observation rows)"
         # what the library itself refuses: host only, nothing is launched and no pointer is followed
-        a = self._new_lstm_step_args(1)
+        a = PPOPolicy._new_lstm_step_args(self, 1)
         a.mode, a.infer_mode = K.LSTM_INFER, K.INFER_DETERMINISTIC
         a.obs = a.actor_h = a.actor_c = a.action_out = self.policy_params.data_ptr()
         return K.lstm_policy_step_refusal(a)
 
+    def _lstm_step_layers(self):
+        """2 when both networks stack two LSTM layers and both opt-ins (`fused_lstm_layers`, `fused_lstm_layers_step`) are
+        on: the step then runs the two-layer launch (ppoaf_lstm2_policy_step); else 1."""
+        on = getattr(self, "fused_lstm_layers", False) and getattr(self, "fused_lstm_layers_step", False)
+        two = all(getattr(net, "num_lstm_layers", 1) == 2 for net in (self.actor, self.critic))
+        return 2 if on and two else 1
+
+    def lstm_step_hint(self):
+        """verbose: what to append to the refusal of a two-layer policy that only `fused_lstm_layers_step` keeps off K21."""
+        if self.using_lstm and self.lstm_step_unsupported_reason().startswith("2 LSTM layers: K21 covers one") \
+                and getattr(self, "fused_lstm_layers", False) and not getattr(self, "fused_lstm_layers_step", False):
+            return "; PPOPolicy.fused_lstm_layers_step = True would step it in one launch (K21 for two stacked layers)"
+        return ""
+
     def _new_lstm_step_args(self, E):
-        """_lib.LstmPolicyStepArgs with everything that stays from step to step, for E rows."""
+        """_lib.LstmPolicyStepArgs with everything that stays from step to step, for E rows; for a two-layer pair under
+        `fused_lstm_layers_step` _lib.Lstm2PolicyStepArgs: the networks' states lie as [2, E, H], the stored rows as
+        [E, 2, H]."""
         from .. import _lib
         from ..fused_update import _activation_code
         from ..networks.distributions import GaussianDistribution
-        a = _lib.LstmPolicyStepArgs()
+        two = PPOPolicy._lstm_step_layers(self) == 2
+        a = K.lstm2_policy_step_args(E, self.actor.lstm_hidden_size) if two else _lib.LstmPolicyStepArgs()
         for tag, net in (("actor", self.actor), ("critic", self.critic)):
             d = getattr(a, tag)
             dims = net.ff_layers.layer_dims()
@@ -549,6 +574,8 @@ class PPOPolicy:
             d.out_dim, d.activation = net.out_size, _activation_code(net.activation)
             d.rows, d.steps = E, 1
             d.params = net.flat_params.data_ptr()
+            if two:
+                d.state_row_stride, d.state_layer_stride = d.hidden, E * d.hidden      # [2, E, H]
         a.E = E
         dist = self.actor.distribution
         gauss = isinstance(dist, GaussianDistribution)
@@ -565,7 +592,7 @@ class PPOPolicy:
         """The K21 arguments for E rows, and both networks' (h, c) as its in / out buffers: reset by the networks' own
         rule (lstm.py:109-113: when the batch size changes), then stepped in place."""
         st = getattr(self, "_lstm_step_state", None)
-        key = (E, self.policy_params.data_ptr())
+        key = (E, self.policy_params.data_ptr(), self._lstm_step_layers())
         if st is None or st["key"] != key:
             st = self._lstm_step_state = dict(key=key, args=self._new_lstm_step_args(E),
                                               one=torch.ones(1, dtype=torch.uint8, device=self.device))
@@ -698,7 +725,7 @@ class PPOPolicy:
         elif not (hs[0].is_contiguous() and hs[1].is_contiguous()):
             self.actor.hidden_state = (hs[0].contiguous(), hs[1].contiguous())
         st = getattr(self, "_lstm_infer_state", None)
-        key = (E, self.policy_params.data_ptr())
+        key = (E, self.policy_params.data_ptr(), self._lstm_step_layers())
         if st is None or st["key"] != key:
             a = self._new_lstm_step_args(E)
             gauss = a.head_kind == K.HEAD_GAUSSIAN

@@ -208,9 +208,10 @@ class _RolloutMember:
         if pol.using_lstm and ppo.verbose and not whole:
             # which step form an LSTM member takes, and why (a block form that a table refuses later says so in act())
             if not self.lstm_kernel:
-                form = f"the torch route ({pol.lstm_step_unsupported_reason()})"
+                form = f"the torch route ({pol.lstm_step_unsupported_reason()}{pol.lstm_step_hint()})"
             elif self.blocks:
-                form = "K21 on the env's row blocks (ppoaf_lstm_policy_step_blocks)"
+                two = pol._lstm_step_layers() == 2
+                form = f"K21 on the env's row blocks (ppoaf_lstm{'2' if two else ''}_policy_step_blocks)"
             else:
                 form = "K21 on gathered rows (step_row_blocks is switched off)"
             rank_print(f"rollout: LSTM policy {policy_id} steps on {form}")
