@@ -1501,6 +1501,50 @@ int ppoaf_lstm_update_wgrad(const ppoaf_lstm_update_args_t* args, ppoaf_stream_t
 int ppoaf_lstm_update_adam(const ppoaf_lstm_update_args_t* args, int32_t norm_mode, ppoaf_stream_t stream);
 
 /* ------------------------------------------------------------------------ *
+ * K22 for two stacked LSTM layers: one mini-batch of the PPO update of a two-layer LSTM pair as four launches
+ * Everything is ppoaf_lstm_update_*'s -- the cursor, `perm` and the per-epoch tables, the windows through row_map, the
+ * terminal rule, the head and loss terms, the records, the stored gradients and their norm partials, the closing launch --
+ * except that the networks are ppoaf_lstm2_forward's (same descriptors, limits and bucket layout) and the four hidden
+ * tables hold both layers' state of a buffer row: [n_rows, 2, hidden], which the descriptors' state_row_stride
+ * (2 * hidden) and state_layer_stride (hidden) must say.  Single rank: there is no norm_mode.
+ *   ppoaf_lstm2_update_forward   2 * ceil(B/16) workgroups of 2 * hidden / 16 waves: prologue, both layers' (h0, c0) of
+ *       the last position's row staged as [B, 2, hidden], the wavefront forward with the stash on, the final (h, c) of
+ *       both layers back to the same rows, head and loss (values scattered, loss_partials, d loss / d out left in the
+ *       workspace).
+ *   ppoaf_lstm2_update_backward  the same grid with hidden / 16 waves: ppoaf_lstm2_backward's body on the tile's rows.
+ *   ppoaf_lstm2_update_wgrad     the stacked weight-gradient jobs of both networks, STORED; norm partials; step counters.
+ *   ppoaf_lstm2_update_adam      ppoaf_lstm_update_adam's kernel at norm_mode 0.
+ * ppoaf_lstm2_update_check / ppoaf_lstm2_update_workspace_floats: as the one-layer entry points (out[2]: LDS bytes of a
+ * forward workgroup).
+ * ------------------------------------------------------------------------ */
+typedef struct {
+    ppoaf_lstm2_desc_t actor, critic;
+    float* params; float* grads; float* exp_avg; float* exp_avg_sq;
+    int64_t bucket_total, actor_size, log_std_offset;
+    int64_t* step_counts; const float* lr; double* norm_scratch; int64_t norm_scratch_doubles;
+    float beta1, beta2, adam_eps, grad_scale, max_norm; int32_t head_kind;
+    const float* obs; const float* critic_obs; const uint8_t* terminal;
+    const int64_t* perm; const int32_t* row_map; int64_t n_rows, n_items;
+    const void* raw_actions; const float* advantages; const float* old_log_probs; const float* rewards_to_go;
+    float* values;
+    float* actor_hidden; float* actor_cell; float* critic_hidden; float* critic_cell;
+    int64_t* cursor; int64_t B, batch_stride;
+    int32_t normalize_values, n_ranks;
+    float* vn_mean; float* vn_var; double* vn_count; const double* vn_records; const double* adv_records;
+    int32_t normalize_adv, use_huber;
+    float surr_clip, entropy_weight, kl_loss_weight, huber_delta, min_std; int32_t _pad;
+    float* loss_partials; double* totals;
+    float* workspace; int64_t workspace_floats;
+} ppoaf_lstm2_update_args_t;
+
+int ppoaf_lstm2_update_check(const ppoaf_lstm2_update_args_t* args, int32_t pointers);
+int ppoaf_lstm2_update_workspace_floats(const ppoaf_lstm2_update_args_t* args, int64_t* out /* host [3] */);
+int ppoaf_lstm2_update_forward(const ppoaf_lstm2_update_args_t* args, ppoaf_stream_t stream);
+int ppoaf_lstm2_update_backward(const ppoaf_lstm2_update_args_t* args, ppoaf_stream_t stream);
+int ppoaf_lstm2_update_wgrad(const ppoaf_lstm2_update_args_t* args, ppoaf_stream_t stream);
+int ppoaf_lstm2_update_adam(const ppoaf_lstm2_update_args_t* args, ppoaf_stream_t stream);
+
+/* ------------------------------------------------------------------------ *
  * K17  gradient exchange between the ranks of one node over peer mappings (xGMI)
  * replaces, inside the per-mini-batch update chain, the comm.Allreduce of
  *          mpi_avg_gradients                       utils/mpi_utils.py:65-86  (called from ppo.py:2443-2448,

@@ -159,6 +159,11 @@ class LstmUpdateArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_floats", C.c_int64)]
 
 
+class Lstm2UpdateArgs(C.Structure):
+    """ppoaf_lstm2_update_args_t (include/ppoaf_hip.h): LstmUpdateArgs' fields over two Lstm2Desc."""
+    _fields_ = [("actor", Lstm2Desc), ("critic", Lstm2Desc)] + LstmUpdateArgs._fields_[2:]
+
+
 class EvalScoresArgs(C.Structure):
     """ppoaf_eval_scores_args_t (include/ppoaf_hip.h)."""
     _fields_ = [("score", C.c_void_p), ("done", C.c_void_p), ("quota", C.c_void_p), ("E", C.c_int64),
@@ -463,6 +468,12 @@ SIGNATURES = {
     "ppoaf_lstm_update_fwd_bwd": (C.c_int, [C.POINTER(LstmUpdateArgs), _ptr]),
     "ppoaf_lstm_update_wgrad": (C.c_int, [C.POINTER(LstmUpdateArgs), _ptr]),
     "ppoaf_lstm_update_adam": (C.c_int, [C.POINTER(LstmUpdateArgs), C.c_int32, _ptr]),
+    "ppoaf_lstm2_update_check": (C.c_int, [C.POINTER(Lstm2UpdateArgs), C.c_int32]),
+    "ppoaf_lstm2_update_workspace_floats": (C.c_int, [C.POINTER(Lstm2UpdateArgs), C.POINTER(C.c_int64)]),
+    "ppoaf_lstm2_update_forward": (C.c_int, [C.POINTER(Lstm2UpdateArgs), _ptr]),
+    "ppoaf_lstm2_update_backward": (C.c_int, [C.POINTER(Lstm2UpdateArgs), _ptr]),
+    "ppoaf_lstm2_update_wgrad": (C.c_int, [C.POINTER(Lstm2UpdateArgs), _ptr]),
+    "ppoaf_lstm2_update_adam": (C.c_int, [C.POINTER(Lstm2UpdateArgs), _ptr]),
     "ppoaf_peer_exchange_create": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "ppoaf_peer_exchange_export": (C.c_int, [_ptr, _ptr]),
     "ppoaf_peer_exchange_connect": (C.c_int, [_ptr, C.c_char_p]),

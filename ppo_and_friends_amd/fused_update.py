@@ -560,7 +560,7 @@ class FusedLstm:
     @staticmethod
     def stacked(pol):
         """True for a policy whose recurrent networks have more than one layer: K18's stacked kernels take it (opt-in
-        `fused_lstm_layers`), K21 and K22 do not."""
+        `fused_lstm_layers`), K21 and K22 with opt-ins of their own beside it."""
         return any(getattr(net, "num_lstm_layers", 1) != 1 for net in (pol.actor, pol.critic))
 
     @staticmethod
@@ -598,11 +598,14 @@ class FusedLstm:
         return ""
 
 
-def _describe_lstm_update(pol, B):
-    """_lib.LstmUpdateArgs with the shapes of an LSTM policy's two networks (no pointer set), for a mini-batch of B rows."""
-    a = _lib.LstmUpdateArgs()
+def _describe_lstm_update(pol, B, layers=1):
+    """_lib.LstmUpdateArgs with the shapes of an LSTM policy's two networks (no pointer set), for a mini-batch of B rows;
+    layers=2: _lib.Lstm2UpdateArgs, whose descriptors also say how the buffer's hidden tables lie ([rows, 2, H])."""
+    a = _lib.Lstm2UpdateArgs() if layers == 2 else _lib.LstmUpdateArgs()
     for tag, net in (("actor", pol.actor), ("critic", pol.critic)):
         d = getattr(a, tag)
+        if layers == 2:
+            d.state_row_stride, d.state_layer_stride = 2 * net.lstm_hidden_size, net.lstm_hidden_size
         dims = net.ff_layers.layer_dims()
         d.in_dim, d.hidden, d.ff_hidden, d.ff_depth = net.in_size, net.lstm_hidden_size, dims[0][1], len(dims) - 1
         d.out_dim, d.activation = net.out_size, _activation_code(net.activation)
@@ -623,15 +626,21 @@ class FusedLstmUpdate(FusedEpoch):
     """
 
     launches = 0                       # launches issued in this process (tests: the path really ran; graph replays not counted)
+    layers = 1                         # LSTM layers per network (FusedLstm2Update: 2)
 
     @staticmethod
     def unsupported_reason(pol, batch_size):
-        """'' when K22 covers this policy at this batch size, else why the mini-batch loop runs."""
+        """'' when K22 covers this policy at this batch size, else why the mini-batch loop runs.  A policy of two stacked
+        layers is taken (by FusedLstm2Update) with both opt-ins `fused_lstm_layers` and `fused_lstm_layers_update` only."""
         why = FusedLstm.unsupported_reason(pol)
         if why:
             return why
-        if FusedLstm.stacked(pol):
+        two = FusedLstm.stacked(pol)
+        if two and not getattr(pol, "fused_lstm_layers_update", False):
             return f"{pol.actor.num_lstm_layers} LSTM layers: K22 covers one; the mini-batch loop on K18 trains it"
+        if two and mpi_utils.distributed_path():        # (the predicate of FusedEpoch.multi: N > 1 ranks or its rehearsal)
+            return (f"{pol.actor.num_lstm_layers} LSTM layers on the multi-rank path ({mpi_utils.get_num_procs()} ranks): the "
+                    "stacked update epoch runs on one rank; the mini-batch loop on K18 trains it")
         ha, hc = pol.actor.lstm_hidden_size, pol.critic.lstm_hidden_size
         if ha != hc:
             return f"LSTM hidden sizes differ (actor {ha}, critic {hc}): one K22 launch has one block size"
@@ -639,7 +648,7 @@ class FusedLstmUpdate(FusedEpoch):
             return f"sequence lengths differ (actor {pol.actor.sequence_length}, critic {pol.critic.sequence_length})"
         if batch_size < 2:
             return "batch size < 2"
-        return K.lstm_update_refusal(_describe_lstm_update(pol, batch_size))     # host only: nothing is launched
+        return K.lstm_update_refusal(_describe_lstm_update(pol, batch_size, 2 if two else 1))    # host only: nothing is launched
 
     def __init__(self, ppo, policy_id):
         super().__init__(ppo, policy_id)
@@ -653,7 +662,7 @@ class FusedLstmUpdate(FusedEpoch):
         self.log_std_offset = -1
         if self.gauss:
             self.log_std_offset = (pol.actor.distribution.log_std.data_ptr() - pol.policy_params.data_ptr()) // 4
-        q = _describe_lstm_update(pol, self.B)
+        q = _describe_lstm_update(pol, self.B, self.layers)
         q.bucket_total, q.actor_size = pol.policy_params.numel(), self.actor_size
         floats, doubles, self.lds_bytes = K.lstm_update_sizes(q)
         self.workspace = torch.zeros(floats, dtype=torch.float32, device=dev)
@@ -664,7 +673,7 @@ class FusedLstmUpdate(FusedEpoch):
     # ------------------------------------------------------------------ args
     def _make_args(self, B):
         pol, ppo, buf, ds, t = self.pol, self.ppo, self.pol.buffer, self.pol.dataset, self.tables
-        a = _describe_lstm_update(pol, B)
+        a = _describe_lstm_update(pol, B, self.layers)
         a.batch_stride = self.B
         na = self.actor_size
         a.params, a.grads = pol.policy_params.data_ptr(), pol.policy_grads.data_ptr()
@@ -785,6 +794,25 @@ class FusedLstmUpdate(FusedEpoch):
 
     def _c_loop(self, args, n):
         return False                   # (no C chain for this driver: the all-reduce fallback is the eager loop)
+
+
+class FusedLstm2Update(FusedLstmUpdate):
+    """
+    Host driver of K22 for two stacked LSTM layers (csrc/lstm_stacked_update.hip): FusedLstmUpdate over
+    _lib.Lstm2UpdateArgs, four launches per mini-batch (forward -> backward -> wgrad -> adam), one rank.  The epoch's
+    inputs and state, the normaliser publishing and the way back (`pol.fused_lstm_update = False`) are inherited.
+    """
+
+    layers = 2
+
+    def gradient_only(self, args):
+        """forward + backward + wgrad of ONE mini-batch, no optimiser step (the step counters advance; the cursor stays)."""
+        K.lstm2_update(args, adam=False)
+        FusedLstmUpdate.launches += 3
+
+    def _one(self, args):
+        K.lstm2_update(args)
+        FusedLstmUpdate.launches += 4
 
 
 # the (actor width, critic width) pairs K6+K7 and K12 are instantiated for (csrc/ppo_update_dev.hpp: PPOAF_WIDTH_PAIRS)

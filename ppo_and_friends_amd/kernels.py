@@ -1095,9 +1095,11 @@ def lstm_policy_infer(args, obs, actor_state, action_out, deterministic):
 # --------------------------------------------------------------------------
 def lstm_update_refusal(args, pointers=False):
     """'' when ppoaf_lstm_update_check accepts the _lib.LstmUpdateArgs (host only: nothing is launched, no pointer is
-    followed; pointers=False: the shapes alone), else the library's reason."""
+    followed; pointers=False: the shapes alone), else the library's reason.  A _lib.Lstm2UpdateArgs (two LSTM layers per
+    network: csrc/lstm_stacked_update.hip) is asked of ppoaf_lstm2_update_check; so is lstm_update_sizes below."""
     lib = _lib.load()
-    if lib.ppoaf_lstm_update_check(C.byref(args), 1 if pointers else 0) == 0:
+    fn = lib.ppoaf_lstm2_update_check if isinstance(args, _lib.Lstm2UpdateArgs) else lib.ppoaf_lstm_update_check
+    if fn(C.byref(args), 1 if pointers else 0) == 0:
         return ""
     return lib.ppoaf_last_error().decode("utf-8", "replace")
 
@@ -1105,7 +1107,9 @@ def lstm_update_refusal(args, pointers=False):
 def lstm_update_sizes(args):
     """(workspace floats for args.B rows, norm_scratch doubles, LDS bytes of a fwd_bwd workgroup)."""
     out = (C.c_int64 * 3)()
-    check(_lib.load().ppoaf_lstm_update_workspace_floats(C.byref(args), out), "lstm_update_workspace_floats")
+    lib = _lib.load()
+    fn = lib.ppoaf_lstm2_update_workspace_floats if isinstance(args, _lib.Lstm2UpdateArgs) else lib.ppoaf_lstm_update_workspace_floats
+    check(fn(C.byref(args), out), "lstm_update_workspace_floats")
     return int(out[0]), int(out[1]), int(out[2])
 
 
@@ -1119,3 +1123,14 @@ def lstm_update_wgrad(args):
 
 def lstm_update_adam(args, norm_mode=0):
     check(_lib.load().ppoaf_lstm_update_adam(C.byref(args), int(norm_mode), stream()), "lstm_update_adam")
+
+
+def lstm2_update(args, adam=True):
+    """One mini-batch of a two-layer LSTM policy's update (_lib.Lstm2UpdateArgs): forward, backward, wgrad and -- unless
+    adam=False, the gradient alone -- the closing launch."""
+    lib, st, ref = _lib.load(), stream(), C.byref(args)
+    check(lib.ppoaf_lstm2_update_forward(ref, st), "lstm2_update_forward")
+    check(lib.ppoaf_lstm2_update_backward(ref, st), "lstm2_update_backward")
+    check(lib.ppoaf_lstm2_update_wgrad(ref, st), "lstm2_update_wgrad")
+    if adam:
+        check(lib.ppoaf_lstm2_update_adam(ref, st), "lstm2_update_adam")

@@ -133,18 +133,24 @@ class PPOPolicy:
     fused_wide_icm_actions = False
     # Opt-in: an LSTM policy whose two networks both stack TWO LSTM layers (num_lstm_layers=2) on K18's stacked kernels
     # (csrc/lstm_stacked.hip) under update_mode="fused": forward_logits in the rollout and in evaluation, the mini-batch loop
-    # in the update.  K22 stays one-layer, and K21 takes such a policy with `fused_lstm_layers_step` (below) only.  Set by hand, on the class or on the policy,
+    # in the update.  K21 and K22 take such a policy with `fused_lstm_layers_step` / `fused_lstm_layers_update` (below) only.  Set by hand, on the class or on the policy,
     # before the first rollout -- no update_mode sets it.  False: two layers are refused with today's message ("2 LSTM layers
     # (K18 covers one)") under "fused" and train on nn.LSTM under "auto"; a one-layer policy computes bitwise the same, flag
     # on or off.
     fused_lstm_layers = False
     # Opt-in, beside `fused_lstm_layers`: such a two-layer policy's rollout and evaluation step in ONE launch (K21 for two
     # stacked layers, csrc/lstm_stacked_step.hip: lstm_rollout_step, lstm_finish_step, lstm_last_value, the evaluation step
-    # and the block forms of PPO.lstm_members), the networks' [2, E, H] states stepped in place.  K22 stays one-layer: the
-    # update runs the K18 mini-batch loop.  Set by hand, on the class or on the policy, before the first rollout -- no
+    # and the block forms of PPO.lstm_members), the networks' [2, E, H] states stepped in place.  The update is
+    # `fused_lstm_layers_update`'s matter.  Set by hand, on the class or on the policy, before the first rollout -- no
     # update_mode sets it.  False: such a policy steps on forward_logits, with today's message ("2 LSTM layers: K21 covers
     # one"); a one-layer policy computes bitwise the same, flag on or off.
     fused_lstm_layers_step = False
+    # Opt-in, beside `fused_lstm_layers` (and honoured only with it): such a two-layer policy's update epoch on K22 for two
+    # stacked layers (csrc/lstm_stacked_update.hip, FusedLstm2Update): four cursor-driven launches per mini-batch, replayed
+    # from hipGraphs, on one rank.  Set by hand, on the class or on the policy, before the first update -- no update_mode
+    # sets it.  False: the update runs the K18 mini-batch loop, with today's message ("2 LSTM layers: K22 covers one");
+    # `fused_lstm_update = False` stays the way back to that loop, read at every epoch.
+    fused_lstm_layers_update = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,

@@ -1437,7 +1437,7 @@ class PPO:
             # LSTM policies: K22 (FusedLstmUpdate) runs the epoch; `pol.fused_lstm_update = False` -- read at every epoch --
             # or a shape K22 does not cover keeps the mini-batch loop, every compute launch of which is ours as well (K18
             # networks, distribution and loss kernels, FlatAdam).  K18's coverage was checked when the networks were switched to it.
-            from .fused_update import FusedLstm, FusedLstmUpdate
+            from .fused_update import FusedLstm, FusedLstm2Update, FusedLstmUpdate
             if not getattr(pol, "fused_lstm_update", True):
                 self._say_lstm_update_path(policy_id, "the mini-batch loop (fused_lstm_update is switched off on this policy)")
                 return None
@@ -1446,9 +1446,11 @@ class PPO:
                 if why:
                     raise NotImplementedError(f"update_mode='fused' but {why}")
                 why = FusedLstmUpdate.unsupported_reason(pol, B)
-                self._fused[key] = None if why else FusedLstmUpdate(self, policy_id)
+                driver = FusedLstm2Update if FusedLstm.stacked(pol) else FusedLstmUpdate
+                self._fused[key] = None if why else driver(self, policy_id)
             if self.verbose:
-                self._say_lstm_update_path(policy_id, "K22 (FusedLstmUpdate)" if self._fused[key] is not None else
+                name = "K22 for two stacked layers (FusedLstm2Update)" if FusedLstm.stacked(pol) else "K22 (FusedLstmUpdate)"
+                self._say_lstm_update_path(policy_id, name if self._fused[key] is not None else
                                            f"the mini-batch loop ({FusedLstmUpdate.unsupported_reason(pol, B)})")
             return self._fused[key]
         if key not in self._fused:
