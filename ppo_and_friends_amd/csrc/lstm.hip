@@ -10,6 +10,7 @@
 // gradients are a separate launch of 16 x 16 output tiles, each reduced over (row, step) samples by four waves in a
 // fixed order and summed in a fixed order: bitwise reproducible, no atomics.
 #include "lstm_device.hpp"
+#include "lstm_wide_device.hpp"
 
 namespace ppoaf {
 namespace {
@@ -34,11 +35,29 @@ __global__ __launch_bounds__(256) void lstm_wgrad_kernel(const WJobs J) {
     lstm_wgrad_tile<true>(J.j[ji], blockIdx.x - J.j[ji].tile_begin, part);
 }
 
+// (hidden == 256 never comes here: the entry points hand it to lstm_wide.hip's launchers first)
 template <template <int> class Launch, typename... T>
 int dispatch_h(int H, T... args) {
     if (H == 32) return Launch<32>::run(args...);
     if (H == 64) return Launch<64>::run(args...);
-    return Launch<128>::run(args...);
+    if (H == 128) return Launch<128>::run(args...);
+    set_error("K18: no kernel for hidden %d", H);
+    return PPOAF_E_INVALID;
+}
+
+// The descriptor check of K18's own one-layer entry points: check_lstm_desc (what K21, K22 and the stacked kernels hold
+// their descriptors to, with the words they have), and hidden == 256 besides, which lstm_wide.hip runs.
+int check_k18_desc(const ppoaf_lstm_desc_t* d, bool need_ws, const char* what) {
+    if (d == nullptr || d->hidden != kWH) return check_lstm_desc(d, need_ws, what);
+    ppoaf_lstm_desc_t narrow = *d;
+    narrow.hidden = 128;                                  // every other limit is the shared one
+    if (int rc = check_lstm_desc(&narrow, false, what)) return rc;
+    if (need_ws) {
+        const LstmLayout L = layout_of(*d);
+        PPOAF_REQUIRE(d->workspace != nullptr && d->workspace_floats >= L.total,
+                      "%s: workspace holds %lld floats, %ld needed", what, (long long)d->workspace_floats, L.total);
+    }
+    return PPOAF_OK;
 }
 
 template <int H> struct FwdLaunch {
@@ -62,7 +81,7 @@ template <int H> struct BwdLaunch {
 using namespace ppoaf;
 
 extern "C" int ppoaf_lstm_workspace_floats(const ppoaf_lstm_desc_t* d, int64_t* floats_out) {
-    if (int rc = check_lstm_desc(d, false, "ppoaf_lstm_workspace_floats")) return rc;
+    if (int rc = check_k18_desc(d, false, "ppoaf_lstm_workspace_floats")) return rc;
     PPOAF_REQUIRE(floats_out != nullptr, "ppoaf_lstm_workspace_floats: floats_out is NULL");
     const LstmLayout L = layout_of(*d);
     floats_out[0] = L.total;
@@ -72,23 +91,25 @@ extern "C" int ppoaf_lstm_workspace_floats(const ppoaf_lstm_desc_t* d, int64_t* 
 
 extern "C" int ppoaf_lstm_forward(const ppoaf_lstm_desc_t* d, const float* x, const float* h0, const float* c0,
                                   float* out, float* hn, float* cn, int32_t stash, ppoaf_stream_t stream) {
-    if (int rc = check_lstm_desc(d, stash != 0, "ppoaf_lstm_forward")) return rc;
+    if (int rc = check_k18_desc(d, stash != 0, "ppoaf_lstm_forward")) return rc;
     PPOAF_REQUIRE(x && h0 && c0 && out, "ppoaf_lstm_forward: x / h0 / c0 / out is NULL");
     LstmArgs a = lstm_args_of(d);
     a.x = x; a.h0 = h0; a.c0 = c0; a.out = out; a.hn = hn; a.cn = cn; a.stash = stash != 0;
+    if (d->hidden == kWH) return lstm_wide_forward(a, (hipStream_t)stream);
     return dispatch_h<FwdLaunch>(d->hidden, a, (hipStream_t)stream);
 }
 
 extern "C" int ppoaf_lstm_backward(const ppoaf_lstm_desc_t* d, const float* c0, const float* dout, ppoaf_stream_t stream) {
-    if (int rc = check_lstm_desc(d, true, "ppoaf_lstm_backward")) return rc;
+    if (int rc = check_k18_desc(d, true, "ppoaf_lstm_backward")) return rc;
     PPOAF_REQUIRE(c0 && dout, "ppoaf_lstm_backward: c0 / dout is NULL");
     LstmArgs a = lstm_args_of(d);
     a.c0 = c0; a.dout = dout;
+    if (d->hidden == kWH) return lstm_wide_backward(a, (hipStream_t)stream);
     return dispatch_h<BwdLaunch>(d->hidden, a, (hipStream_t)stream);
 }
 
 extern "C" int ppoaf_lstm_wgrad(const ppoaf_lstm_desc_t* d, const float* x, const float* h0, ppoaf_stream_t stream) {
-    if (int rc = check_lstm_desc(d, true, "ppoaf_lstm_wgrad")) return rc;
+    if (int rc = check_k18_desc(d, true, "ppoaf_lstm_wgrad")) return rc;
     PPOAF_REQUIRE(x && h0 && d->grads, "ppoaf_lstm_wgrad: x / h0 / grads is NULL");
     WJobs J{};
     const int nt = lstm_wgrad_add_jobs(J.j, J.n, 0, lstm_args_of(d), d->hidden, x, h0, d->grads);

@@ -564,13 +564,16 @@ class FusedLstm:
         return any(getattr(net, "num_lstm_layers", 1) != 1 for net in (pol.actor, pol.critic))
 
     @staticmethod
-    def unsupported_reason(pol, lstm_layers=None):
+    def unsupported_reason(pol, lstm_layers=None, lstm_wide=None):
         """'' when K18 covers both networks of this LSTM policy, else why not.  Two stacked layers (both networks) are
         taken with the policy's opt-in `fused_lstm_layers` only (`lstm_layers`: the hypothetical answer with it on / off;
-        the opt-in concerns LSTM policies alone, so it is read here and is no field of FusedOptIns)."""
+        the opt-in concerns LSTM policies alone, so it is read here and is no field of FusedOptIns), and one layer of 256
+        hidden units with its opt-in `fused_lstm_wide` only (`lstm_wide`, in the same way)."""
         from .networks.lstm import LSTMNetwork
         if lstm_layers is None:
             lstm_layers = bool(getattr(pol, "fused_lstm_layers", False))
+        if lstm_wide is None:
+            lstm_wide = bool(getattr(pol, "fused_lstm_wide", False))
         if not pol.using_lstm:
             return "not an LSTM policy"
         if pol.agent_grouping:
@@ -580,7 +583,7 @@ class FusedLstm:
         for tag, net in (("actor", pol.actor), ("critic", pol.critic)):
             if not isinstance(net, LSTMNetwork):
                 return f"{tag}: {type(net).__name__} is not an LSTMNetwork"
-            why = net._hip_scope(max_layers=2) if lstm_layers else net.hip_unsupported_reason()
+            why = net._hip_scope(max_layers=2 if lstm_layers else 1, wide=lstm_wide)
             if why:
                 return f"{tag}: {why}"
         la, lc = pol.actor.num_lstm_layers, pol.critic.num_lstm_layers
@@ -595,6 +598,18 @@ class FusedLstm:
         """verbose: what to append to the refusal of a policy that only `fused_lstm_layers` keeps off K18."""
         if pol.using_lstm and FusedLstm.unsupported_reason(pol) and FusedLstm.unsupported_reason(pol, lstm_layers=True) == "":
             return "; PPOPolicy.fused_lstm_layers = True would take it on K18 (forward_logits and the mini-batch loop)"
+        return FusedLstm.wide_hint(pol)
+
+    @staticmethod
+    def wide(pol):
+        """True for a policy with a 256-wide recurrent network: K18 takes it (opt-in `fused_lstm_wide`), K21 and K22 do not."""
+        return any(getattr(net, "lstm_hidden_size", 0) == 256 for net in (pol.actor, pol.critic))
+
+    @staticmethod
+    def wide_hint(pol):
+        """verbose: what to append to the refusal of a policy that only `fused_lstm_wide` keeps off K18."""
+        if pol.using_lstm and FusedLstm.unsupported_reason(pol) and FusedLstm.unsupported_reason(pol, lstm_wide=True) == "":
+            return "; PPOPolicy.fused_lstm_wide = True would take it on K18 (forward_logits and the mini-batch loop)"
         return ""
 
 
@@ -635,6 +650,8 @@ class FusedLstmUpdate(FusedEpoch):
         why = FusedLstm.unsupported_reason(pol)
         if why:
             return why
+        if FusedLstm.wide(pol):
+            return "LSTM hidden size 256: K22 covers 32, 64, 128; the mini-batch loop on K18 trains it"
         two = FusedLstm.stacked(pol)
         if two and not getattr(pol, "fused_lstm_layers_update", False):
             return f"{pol.actor.num_lstm_layers} LSTM layers: K22 covers one; the mini-batch loop on K18 trains it"

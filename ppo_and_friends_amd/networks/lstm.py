@@ -108,16 +108,20 @@ class LSTMNetwork(PPOLSTMNetwork):
         """'' when K18 covers this network (shapes, activation, bucket layout), else why not."""
         return self._hip_scope(max_layers=1)
 
-    def _hip_scope(self, max_layers):
+    def _hip_scope(self, max_layers, wide=False):
         """hip_unsupported_reason for a caller that takes up to `max_layers` LSTM layers (2: the stacked kernels of
-        csrc/lstm_stacked.hip, the policy's opt-in `fused_lstm_layers`)."""
+        csrc/lstm_stacked.hip, the policy's opt-in `fused_lstm_layers`) and, with `wide`, one layer of 256 hidden units
+        (csrc/lstm_wide.hip, the policy's opt-in `fused_lstm_wide`)."""
         from ..fused_update import _activation_code
         if self.num_lstm_layers != 1 and max_layers == 1:
             return f"{self.num_lstm_layers} LSTM layers (K18 covers one)"
         if not 1 <= self.num_lstm_layers <= max_layers:
             return f"{self.num_lstm_layers} LSTM layers (K18 covers one or two)"
-        if self.lstm_hidden_size not in (32, 64, 128):
-            return f"LSTM hidden size {self.lstm_hidden_size} is not one of 32, 64, 128"
+        if wide and self.lstm_hidden_size == 256:
+            if self.num_lstm_layers != 1:
+                return "LSTM hidden size 256 with 2 LSTM layers (the stacked kernels cover 32, 64, 128)"
+        elif self.lstm_hidden_size not in (32, 64, 128):
+            return f"LSTM hidden size {self.lstm_hidden_size} is not one of 32, 64, 128" + (", 256" if wide else "")
         if self.sequence_length > 16:
             return f"sequence length {self.sequence_length} > 16"
         if self.in_size > 256:

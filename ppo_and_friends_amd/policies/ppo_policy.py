@@ -151,6 +151,13 @@ class PPOPolicy:
     # sets it.  False: the update runs the K18 mini-batch loop, with today's message ("2 LSTM layers: K22 covers one");
     # `fused_lstm_update = False` stays the way back to that loop, read at every epoch.
     fused_lstm_layers_update = False
+    # Opt-in: an LSTM policy whose two networks have ONE LSTM layer of 256 hidden units on K18's 256-wide kernels
+    # (csrc/lstm_wide.hip: 32-row tiles, W_hh streamed as whole lines) under update_mode="fused": forward_logits in the
+    # rollout and in evaluation, the mini-batch loop in the update.  K21 and K22 do not cover the width and say so.  Set by
+    # hand, on the class or on the policy, before the first rollout -- no update_mode sets it.  False: 256 is refused with
+    # today's message ("LSTM hidden size 256 is not one of 32, 64, 128") under "fused" and trains on nn.LSTM under "auto";
+    # a policy of another width computes bitwise the same, flag on or off.
+    fused_lstm_wide = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -535,6 +542,8 @@ class PPOPolicy:
         why = FusedLstm.unsupported_reason(self)
         if why:
             return why
+        if FusedLstm.wide(self):
+            return "LSTM hidden size 256: K21 covers 32, 64, 128; forward_logits on K18 steps the policy"
         if FusedLstm.stacked(self) and PPOPolicy._lstm_step_layers(self) != 2:
             return f"{self.actor.num_lstm_layers} LSTM layers: K21 covers one; forward_logits on K18 steps the policy"
         if not (self.actor.use_hip and self.critic.use_hip):
