@@ -45,21 +45,6 @@ int dispatch_h(int H, T... args) {
     return PPOAF_E_INVALID;
 }
 
-// The descriptor check of K18's own one-layer entry points: check_lstm_desc (what K21, K22 and the stacked kernels hold
-// their descriptors to, with the words they have), and hidden == 256 besides, which lstm_wide.hip runs.
-int check_k18_desc(const ppoaf_lstm_desc_t* d, bool need_ws, const char* what) {
-    if (d == nullptr || d->hidden != kWH) return check_lstm_desc(d, need_ws, what);
-    ppoaf_lstm_desc_t narrow = *d;
-    narrow.hidden = 128;                                  // every other limit is the shared one
-    if (int rc = check_lstm_desc(&narrow, false, what)) return rc;
-    if (need_ws) {
-        const LstmLayout L = layout_of(*d);
-        PPOAF_REQUIRE(d->workspace != nullptr && d->workspace_floats >= L.total,
-                      "%s: workspace holds %lld floats, %ld needed", what, (long long)d->workspace_floats, L.total);
-    }
-    return PPOAF_OK;
-}
-
 template <int H> struct FwdLaunch {
     static int run(const LstmArgs& a, hipStream_t s) {
         const unsigned blocks = (unsigned)((a.N + kLRows - 1) / kLRows);

@@ -99,6 +99,22 @@ inline int check_lstm_desc(const ppoaf_lstm_desc_t* d, bool need_ws, const char*
     return PPOAF_OK;
 }
 
+// The descriptor check of the entry points that take hidden == 256 beside 32, 64, 128 (K18's one-layer ones in lstm.hip,
+// K21's in lstm_policy_step.hip; the kernels of lstm_wide.hip and lstm_wide_step.hip run that width): check_lstm_desc --
+// what K22 and the stacked kernels hold their descriptors to, with the words they have -- and 256 besides.
+inline int check_k18_desc(const ppoaf_lstm_desc_t* d, bool need_ws, const char* what) {
+    if (d == nullptr || d->hidden != 256) return check_lstm_desc(d, need_ws, what);
+    ppoaf_lstm_desc_t narrow = *d;
+    narrow.hidden = 128;                                  // every other limit is the shared one
+    if (int rc = check_lstm_desc(&narrow, false, what)) return rc;
+    if (need_ws) {
+        const LstmLayout L = layout_of(*d);
+        PPOAF_REQUIRE(d->workspace != nullptr && d->workspace_floats >= L.total,
+                      "%s: workspace holds %lld floats, %ld needed", what, (long long)d->workspace_floats, L.total);
+    }
+    return PPOAF_OK;
+}
+
 inline LstmArgs lstm_args_of(const ppoaf_lstm_desc_t* d) {
     LstmArgs a{};
     a.P = d->params;

@@ -15,6 +15,8 @@
 // and feed-forward head are K18's forward at S = 1 (lstm_device.hpp: lstm_rows_forward), the heads run one lane per row
 // on K6's / K19's functions (action_heads.hpp).  The networks' (h, c) are stepped IN PLACE: a workgroup reads only its
 // own 16 rows, all before its first barrier, and writes them after the recurrent step.
+// H = 256 has kernels of its own behind the same entry points (lstm_wide_step.hip: tiles of 32 rows on 8 waves, K18's
+// 256-wide body in its step form); the checks, the device view and everything said above but the tile height are shared.
 //
 // Block form (ppoaf_lstm_policy_step_blocks, STEP and CRITIC_NEXT): the observations are read where the env left them,
 // through a table of row blocks in the kernel arguments, and STEP also writes the env's action blocks -- a member of a
@@ -22,37 +24,13 @@
 #include <cstddef>
 
 #include "action_heads.hpp"
-#include "lstm_device.hpp"
+#include "lstm_step_device.hpp"
+#include "lstm_wide_device.hpp"
 
 namespace ppoaf {
 
-struct LstmStepDev {
-    LstmArgs net[2];                               // actor, critic
-    long E;
-    int n_wg, mode, head_kind, infer_mode;
-    float min_std;
-    const float* log_std;
-    const float* act_lo; const float* act_hi;
-    const void* forced_raw_action;
-    unsigned long long seed, offset;
-    int normalize_values; const float* vn_mean; const float* vn_var;
-    void* raw_action_out; void* action_out; float* logp_out;
-    float* value_out;                              // values[t] (STEP) or boot_value[t] (CRITIC_NEXT)
-    float* obs_out; float* critic_obs_out;
-    const unsigned char* terminated;
-    float* stored[4];                              // the step's hidden rows, for the zeroing
-};
-
-// The block form (ppoaf_lstm_policy_step_blocks): row r of the launch is row r % rows_per_block of block
-// r / rows_per_block of `obs` / `critic_obs`, its env action (STEP) also goes to that row of `env_action`, and
-// `terminated` (CRITIC_NEXT) holds one byte per row of a block.  The pointers travel in the kernel arguments.
-struct LstmStepBlocks {
-    const float* obs[PPOAF_ROW_BLOCKS_MAX];
-    const float* critic_obs[PPOAF_ROW_BLOCKS_MAX];
-    void* env_action[PPOAF_ROW_BLOCKS_MAX];
-    unsigned rows_per_block;
-    int action_elems;                              // float32 elements of a Gaussian row's env action; int64: 1
-};
+// (LstmStepDev and LstmStepBlocks, the device views the kernels take, live in lstm_step_device.hpp: the 256-wide kernels
+//  of lstm_wide_step.hip take the same)
 
 template <int H>
 __global__ __launch_bounds__(H / 16 * 64) void lstm_policy_step_kernel(const LstmStepDev u) {
@@ -204,8 +182,9 @@ static int check_step_args(const ppoaf_lstm_policy_step_args_t* a, const bool wi
     PPOAF_REQUIRE(a, "lstm_policy_step: null args");
     PPOAF_REQUIRE(a->mode >= PPOAF_LSTM_STEP && a->mode <= PPOAF_LSTM_MASK,
                   "lstm_policy_step: mode=%d (0 step, 1 critic next, 2 infer, 3 mask)", a->mode);
-    if (int rc = check_lstm_desc(&a->actor, false, "lstm_policy_step: actor")) return rc;
-    if (int rc = check_lstm_desc(&a->critic, false, "lstm_policy_step: critic")) return rc;
+    // (hidden 256 besides 32, 64, 128: lstm_wide_step.hip runs it)
+    if (int rc = check_k18_desc(&a->actor, false, "lstm_policy_step: actor")) return rc;
+    if (int rc = check_k18_desc(&a->critic, false, "lstm_policy_step: critic")) return rc;
     PPOAF_REQUIRE(a->actor.hidden == a->critic.hidden,
                   "lstm_policy_step: LSTM hidden sizes differ (actor %d, critic %d): one launch has one block size",
                   a->actor.hidden, a->critic.hidden);
@@ -310,8 +289,9 @@ static_assert(sizeof(ppoaf_lstm_policy_step_args_t) == 392, "ppoaf_lstm_policy_s
 
 extern "C" int ppoaf_lstm_policy_step_check(const ppoaf_lstm_policy_step_args_t* a) { return check_step_args(a); }
 
-// the device view of checked arguments
+// the device view of checked arguments (row tiles of 32 at hidden 256, of 16 otherwise)
 static LstmStepDev step_dev_of(const ppoaf_lstm_policy_step_args_t* a) {
+    const int tile_rows = a->actor.hidden == kWH ? kWRows : kLRows;
     LstmStepDev u{};
     // (the descriptors' own `rows` is not read: E rules)
     u.net[0] = lstm_args_of(&a->actor);
@@ -331,7 +311,7 @@ static LstmStepDev step_dev_of(const ppoaf_lstm_policy_step_args_t* a) {
         u.value_out = a->boot_value_out;
     }
     u.E = a->E;
-    u.n_wg = (int)((a->E + kLRows - 1) / kLRows);
+    u.n_wg = (int)((a->E + tile_rows - 1) / tile_rows);
     u.mode = a->mode; u.head_kind = a->head_kind; u.infer_mode = a->infer_mode; u.min_std = a->min_std;
     u.log_std = a->log_std; u.act_lo = a->act_lo; u.act_hi = a->act_hi;
     u.forced_raw_action = a->mode == PPOAF_LSTM_STEP ? a->forced_raw_action : nullptr;
@@ -352,8 +332,11 @@ extern "C" int ppoaf_lstm_policy_step(const ppoaf_lstm_policy_step_args_t* a, pp
     switch (a->actor.hidden) {
         case 32: return launch_lstm_step<32>(u, s);
         case 64: return launch_lstm_step<64>(u, s);
+        case 128: return launch_lstm_step<128>(u, s);
+        case kWH: return lstm_wide_step(u, s);
     }
-    return launch_lstm_step<128>(u, s);
+    set_error("lstm_policy_step: no kernel for hidden %d", a->actor.hidden);
+    return PPOAF_E_INVALID;
 }
 
 PPOAF_LAYOUT(ppoaf_lstm_step_blocks_t, n_blocks, 0);
@@ -386,6 +369,9 @@ extern "C" int ppoaf_lstm_policy_step_blocks(const ppoaf_lstm_policy_step_args_t
     switch (a->actor.hidden) {
         case 32: return launch_lstm_step_blocks<32>(u, tb, s);
         case 64: return launch_lstm_step_blocks<64>(u, tb, s);
+        case 128: return launch_lstm_step_blocks<128>(u, tb, s);
+        case kWH: return lstm_wide_step_blocks(u, tb, s);
     }
-    return launch_lstm_step_blocks<128>(u, tb, s);
+    set_error("lstm_policy_step_blocks: no kernel for hidden %d", a->actor.hidden);
+    return PPOAF_E_INVALID;
 }

@@ -14,7 +14,7 @@ namespace {
 extern __shared__ __attribute__((aligned(16))) unsigned char lstm_wide_smem[];
 
 __global__ __launch_bounds__(kWThreads) void lstm_wide_fwd_kernel(const LstmArgs a) {
-    lstm_wide_rows_forward(a, blockIdx.x, reinterpret_cast<float*>(lstm_wide_smem));
+    lstm_wide_rows_forward<false>(a, blockIdx.x, reinterpret_cast<float*>(lstm_wide_smem));
 }
 
 __global__ __launch_bounds__(kWThreads) void lstm_wide_bwd_kernel(const LstmArgs a) {

@@ -109,12 +109,22 @@ __device__ __forceinline__ void wide_rows_x_lines(const float* __restrict__ A, c
 
 // Rows [32 g, 32 g + 32) of the network: S recurrent steps, LayerNorm, activation, feed-forward head; `lds`: kWFwdLds
 // floats.  In tile i = 2 q + u (gate q, half u of the wave's units) lane column c is unit 32 w + 16 u + c.
-__device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const int g_tile, float* __restrict__ lds) {
+// STEP = false (K18): the outputs go to a.out; nullptr is returned.  STEP = true (K21 at 256, lstm_wide_step.hip): the
+// contract of lstm_rows_forward<H, true, XRows> -- one step (S is 1 whatever a.S says, so the time loop folds away), the
+// input rows come through XRows, the last Linear's rows stay in LDS (the returned pointer, row stride kLFS, valid for
+// every thread after the call) for the one-lane-per-row heads, the final (h, c) also go to a.hn_row / a.cn_row, a.hn /
+// a.cn are written only when *a.commit says so, and nothing is stashed.  There a.hn / a.cn may be a.h0 / a.c0: a
+// workgroup reads only its own 32 rows of them -- h into LDS, c into registers, both ahead of the first __syncthreads --
+// and writes them after the cell.  Both forms add in one order (bias, the x . W_ih chunks, the eight lines with the
+// even- and odd-chunk accumulators summed last), so a step's states are bitwise those of a one-step K18 call.
+template <bool STEP, class XRows = LstmXDense>
+__device__ __forceinline__ const float* lstm_wide_rows_forward(const LstmArgs& a, const int g_tile, float* __restrict__ lds,
+                                                               const XRows xrows = XRows()) {
     constexpr int H = kWH, HS = kWHS, NT = kWThreads;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, s4 = lane >> 4, c16 = lane & 15;
     const long r0 = (long)g_tile * kWRows;
     const long N = a.N;
-    const int S = a.S, I = a.I, Ip = (a.I + 15) & ~15;
+    const int S = STEP ? 1 : a.S, I = a.I, Ip = (a.I + 15) & ~15;
     float* xs = lds + kWFwdX;
     float* hs = lds + kWFwdH;
     float* slots = lds + kWFwdSlots + w * 2 * kLineSlot;
@@ -133,13 +143,29 @@ __device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const 
         for (int e = tid; e < kWRows * Ip; e += NT) {
             const int r = e / Ip, k = e - r * Ip;
             const long n = r0 + r;
-            xs[r * HS + k] = (n < N && k < I) ? a.x[(n * S + t) * I + k] : 0.f;
+            xs[r * HS + k] = (n < N && k < I) ? xrows.load(a, n, S, t, I, k) : 0.f;
         }
     };
-    for (int e = tid; e < kWRows * H; e += NT) {
-        const int r = e / H, k = e - r * H;
-        const long n = r0 + r;
-        hs[r * HS + k] = n < N ? a.h0[n * H + k] : 0.f;
+    float4 raw[16];
+    constexpr int kHLoads = kWRows * H / NT;              // h values a thread stages
+    [[maybe_unused]] float hv[STEP ? kHLoads : 1];
+    if constexpr (STEP) {
+        // one step: no step before hides the first tile's latency, so the tile is asked for ahead of the h / c / x loads,
+        // and a thread's h loads are all issued before the first is stored (one round trip under the tile's, not 16)
+        wide_request_tile(rs, off, disp_of(0), raw);
+        __builtin_amdgcn_sched_barrier(0);                // (the scheduler would sink the request behind the staging)
+#pragma unroll
+        for (int q = 0; q < kHLoads; ++q) {
+            const int e = tid + q * NT, r = e / H, k = e - r * H;
+            const long n = r0 + r;
+            hv[q] = n < N ? a.h0[n * H + k] : 0.f;
+        }
+    } else {
+        for (int e = tid; e < kWRows * H; e += NT) {
+            const int r = e / H, k = e - r * H;
+            const long n = r0 + r;
+            hs[r * HS + k] = n < N ? a.h0[n * H + k] : 0.f;
+        }
     }
     float cr[2][2][4];                                    // c of (half u, row tile m, row 4 s4 + g)
 #pragma unroll
@@ -151,9 +177,16 @@ __device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const 
                 const long n = r0 + 16 * m + 4 * s4 + g;
                 cr[u][m][g] = n < N ? a.c0[n * H + 32 * w + 16 * u + c16] : 0.f;
             }
+    if constexpr (STEP) {
+#pragma unroll
+        for (int q = 0; q < kHLoads; ++q) {
+            const int e = tid + q * NT, r = e / H;
+            hs[r * HS + (e - r * H)] = hv[q];
+        }
+    }
     load_x(0);
-    float4 raw[16];
-    wide_request_tile(rs, off, disp_of(0), raw);          // (the weights do not change: the first tile of a step is asked
+    if constexpr (!STEP)
+        wide_request_tile(rs, off, disp_of(0), raw);      // (the weights do not change: the first tile of a step is asked
     __syncthreads();                                      //  for during the last tile of the step before, across the barriers)
 
     for (int t = 0; t < S; ++t) {
@@ -205,7 +238,7 @@ __device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const 
                     const float h = og * tanhf(c);
                     cr[u][m][g] = c;
                     hnext[rr * HS + j] = h;
-                    if (a.stash && n < N) {
+                    if (!STEP && a.stash && n < N) {
                         float* gp = a.ws + a.L.gates + (n * S + t) * 4 * H + j;
                         gp[0] = ig; gp[H] = fg; gp[2 * H] = gg; gp[3 * H] = og;
                         a.ws[a.L.cst + (n * S + t) * H + j] = c;
@@ -215,6 +248,8 @@ __device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const 
         __syncthreads();
     }
     const float* hfin = hs + (S & 1) * kWRows * HS;
+    bool keep = true;
+    if constexpr (STEP) keep = a.commit == nullptr || *a.commit != 0;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -224,8 +259,12 @@ __device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const 
                 const int rr = 16 * m + 4 * s4 + g, j = 32 * w + 16 * u + c16;
                 const long n = r0 + rr;
                 if (n < N) {
-                    if (a.hn) a.hn[n * H + j] = hfin[rr * HS + j];
-                    if (a.cn) a.cn[n * H + j] = cr[u][m][g];
+                    if (a.hn && keep) a.hn[n * H + j] = hfin[rr * HS + j];
+                    if (a.cn && keep) a.cn[n * H + j] = cr[u][m][g];
+                    if constexpr (STEP) {
+                        if (a.hn_row) a.hn_row[n * H + j] = hfin[rr * HS + j];
+                        if (a.cn_row) a.cn_row[n * H + j] = cr[u][m][g];
+                    }
                 }
             }
 
@@ -245,9 +284,9 @@ __device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const 
             const float y = (hfin[r * HS + k] - mean) * rstd * a.P[a.L.ln_w + k] + a.P[a.L.ln_b + k];
             const float y2 = act_fwd(y, a.act);
             A0[r * HS + k] = y2;
-            if (a.stash && n < N) a.ws[a.L.acts[0] + n * H + k] = y2;
+            if (!STEP && a.stash && n < N) a.ws[a.L.acts[0] + n * H + k] = y2;
         }
-        if (a.stash && n < N && lane == 0) { a.ws[a.L.stats + 2 * n] = mean; a.ws[a.L.stats + 2 * n + 1] = rstd; }
+        if (!STEP && a.stash && n < N && lane == 0) { a.ws[a.L.stats + 2 * n] = mean; a.ws[a.L.stats + 2 * n + 1] = rstd; }
     }
     __syncthreads();
     // first Linear (256 -> F, never the last: depth >= 1) on the matrix pipe: wave w forms output columns [16 w, 16 w + 16)
@@ -266,7 +305,7 @@ __device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const 
                 const long n = r0 + rr;
                 const float sv = act_fwd(acc[g], a.act);
                 A1[rr * kLFS + mcol] = sv;
-                if (a.stash && n < N) a.ws[a.L.acts[1] + n * a.F + mcol] = sv;
+                if (!STEP && a.stash && n < N) a.ws[a.L.acts[1] + n * a.F + mcol] = sv;
             }
         }
     }
@@ -287,16 +326,18 @@ __device__ __forceinline__ void lstm_wide_rows_forward(const LstmArgs& a, const 
             for (int k = 0; k < K; ++k) s += ir[k] * wr[k];
             s += b[m];
             if (last) {
-                if (n < N) a.out[n * M + m] = s;
+                if constexpr (STEP) ob[r * kLFS + m] = s;
+                else if (n < N) a.out[n * M + m] = s;
             } else {
                 s = act_fwd(s, a.act);
                 ob[r * kLFS + m] = s;
-                if (a.stash && n < N) a.ws[a.L.acts[l + 1] + n * M + m] = s;
+                if (!STEP && a.stash && n < N) a.ws[a.L.acts[l + 1] + n * M + m] = s;
             }
         }
         __syncthreads();
         in = ob;
     }
+    return STEP ? in : nullptr;
 }
 
 // One group of the backward stream: chunks [8 grp, 8 grp + 8) of the 64 chunks of 16 gate rows.  fr[4 c + j] = the two units

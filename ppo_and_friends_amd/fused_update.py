@@ -602,7 +602,8 @@ class FusedLstm:
 
     @staticmethod
     def wide(pol):
-        """True for a policy with a 256-wide recurrent network: K18 takes it (opt-in `fused_lstm_wide`), K21 and K22 do not."""
+        """True for a policy with a 256-wide recurrent network: K18 takes it (opt-in `fused_lstm_wide`), K21 with
+        `fused_lstm_wide_step` beside that (PPOPolicy._lstm_step_scope), K22 does not."""
         return any(getattr(net, "lstm_hidden_size", 0) == 256 for net in (pol.actor, pol.critic))
 
     @staticmethod

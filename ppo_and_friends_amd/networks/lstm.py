@@ -111,7 +111,8 @@ class LSTMNetwork(PPOLSTMNetwork):
     def _hip_scope(self, max_layers, wide=False):
         """hip_unsupported_reason for a caller that takes up to `max_layers` LSTM layers (2: the stacked kernels of
         csrc/lstm_stacked.hip, the policy's opt-in `fused_lstm_layers`) and, with `wide`, one layer of 256 hidden units
-        (csrc/lstm_wide.hip, the policy's opt-in `fused_lstm_wide`)."""
+        (csrc/lstm_wide.hip, the policy's opt-in `fused_lstm_wide`; K21 steps that width with `fused_lstm_wide_step`
+        beside it, csrc/lstm_wide_step.hip)."""
         from ..fused_update import _activation_code
         if self.num_lstm_layers != 1 and max_layers == 1:
             return f"{self.num_lstm_layers} LSTM layers (K18 covers one)"

@@ -158,6 +158,14 @@ class PPOPolicy:
     # today's message ("LSTM hidden size 256 is not one of 32, 64, 128") under "fused" and trains on nn.LSTM under "auto";
     # a policy of another width computes bitwise the same, flag on or off.
     fused_lstm_wide = False
+    # Opt-in, beside `fused_lstm_wide` (and honoured only with it): such a 256-wide policy's rollout and evaluation step in
+    # ONE launch (K21 at 256, csrc/lstm_wide_step.hip: lstm_rollout_step, lstm_finish_step, lstm_last_value, the evaluation
+    # step and the block forms of PPO.lstm_members), the networks' states stepped in place and bitwise those of a one-step
+    # forward_logits on K18.  The update stays the mini-batch loop (K22 does not cover the width).  Set by hand, on the
+    # class or on the policy, before the first rollout -- no update_mode sets it.  False: such a policy steps on
+    # forward_logits, with today's message ("LSTM hidden size 256: K21 covers 32, 64, 128"); a policy of another width
+    # computes bitwise the same, flag on or off.
+    fused_lstm_wide_step = False
 
     def __init__(self, name, action_space, actor_observation_space, critic_observation_space,
                  envs_per_proc, bootstrap_clip=(-100., 100.), ac_network=FeedForwardNetwork,
@@ -532,7 +540,7 @@ class PPOPolicy:
         if getattr(self, "update_mode", "auto") == "torch":
             return "update_mode='torch' keeps the policy on the torch-ROCm path"
         key = (self.policy_params.data_ptr(), bool(self.actor.use_hip), bool(self.critic.use_hip), bool(self.enable_icm),
-               self._lstm_step_layers())
+               self._lstm_step_layers(), self._lstm_step_wide())
         if getattr(self, "_lstm_step_reason", (None, ""))[0] != key:
             self._lstm_step_reason = (key, self._lstm_step_scope())
         return self._lstm_step_reason[1]
@@ -542,7 +550,7 @@ class PPOPolicy:
         why = FusedLstm.unsupported_reason(self)
         if why:
             return why
-        if FusedLstm.wide(self):
+        if FusedLstm.wide(self) and not PPOPolicy._lstm_step_wide(self):
             return "LSTM hidden size 256: K21 covers 32, 64, 128; forward_logits on K18 steps the policy"
         if FusedLstm.stacked(self) and PPOPolicy._lstm_step_layers(self) != 2:
             return f"{self.actor.num_lstm_layers} LSTM layers: K21 covers one; forward_logits on K18 steps the policy"
@@ -566,11 +574,21 @@ class PPOPolicy:
         two = all(getattr(net, "num_lstm_layers", 1) == 2 for net in (self.actor, self.critic))
         return 2 if on and two else 1
 
+    def _lstm_step_wide(self):
+        """True when both opt-ins of the 256-wide step (`fused_lstm_wide`, `fused_lstm_wide_step`) are on: K21 then takes
+        LSTM hidden size 256 (csrc/lstm_wide_step.hip).  Part of the step's cache keys."""
+        return bool(getattr(self, "fused_lstm_wide", False) and getattr(self, "fused_lstm_wide_step", False))
+
     def lstm_step_hint(self):
-        """verbose: what to append to the refusal of a two-layer policy that only `fused_lstm_layers_step` keeps off K21."""
-        if self.using_lstm and self.lstm_step_unsupported_reason().startswith("2 LSTM layers: K21 covers one") \
+        """verbose: what to append to the refusal of a two-layer policy that only `fused_lstm_layers_step` keeps off K21,
+        or of a 256-wide policy that only `fused_lstm_wide_step` keeps off it."""
+        why = self.lstm_step_unsupported_reason() if self.using_lstm else ""
+        if why.startswith("2 LSTM layers: K21 covers one") \
                 and getattr(self, "fused_lstm_layers", False) and not getattr(self, "fused_lstm_layers_step", False):
             return "; PPOPolicy.fused_lstm_layers_step = True would step it in one launch (K21 for two stacked layers)"
+        if why.startswith("LSTM hidden size 256: K21 covers") \
+                and getattr(self, "fused_lstm_wide", False) and not getattr(self, "fused_lstm_wide_step", False):
+            return "; PPOPolicy.fused_lstm_wide_step = True would step it in one launch (K21 at 256)"
         return ""
 
     def _new_lstm_step_args(self, E):
@@ -607,7 +625,7 @@ class PPOPolicy:
         """The K21 arguments for E rows, and both networks' (h, c) as its in / out buffers: reset by the networks' own
         rule (lstm.py:109-113: when the batch size changes), then stepped in place."""
         st = getattr(self, "_lstm_step_state", None)
-        key = (E, self.policy_params.data_ptr(), self._lstm_step_layers())
+        key = (E, self.policy_params.data_ptr(), self._lstm_step_layers(), self._lstm_step_wide())
         if st is None or st["key"] != key:
             st = self._lstm_step_state = dict(key=key, args=self._new_lstm_step_args(E),
                                               one=torch.ones(1, dtype=torch.uint8, device=self.device))
@@ -740,7 +758,7 @@ class PPOPolicy:
         elif not (hs[0].is_contiguous() and hs[1].is_contiguous()):
             self.actor.hidden_state = (hs[0].contiguous(), hs[1].contiguous())
         st = getattr(self, "_lstm_infer_state", None)
-        key = (E, self.policy_params.data_ptr(), self._lstm_step_layers())
+        key = (E, self.policy_params.data_ptr(), self._lstm_step_layers(), self._lstm_step_wide())
         if st is None or st["key"] != key:
             a = self._new_lstm_step_args(E)
             gauss = a.head_kind == K.HEAD_GAUSSIAN
